@@ -59,7 +59,30 @@ def parse():
                     help="run the row-partitioned code path (RCCL communicator, halo plan) even on 1 GPU")
     ap.add_argument("--cpu-sample-nx", type=int, default=400,
                     help="grid edge of the bounded CPU-baseline sample (8 layers of nx*nx)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (solution x and its residuals) to DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_SAMPLE = 1 << 21          # --dump-outputs: longest x written whole; a longer one is sampled (16 MB of values + 16 MB of positions)
+
+
+def dump_outputs(out_dir: str, x: np.ndarray, result) -> list:
+    """--dump-outputs: the arrays the timed path hands its caller after the last timed step -- the solution ``x`` of the
+    reduced system (in the one-GPU path's numbering: every vertex but the ground, ascending) and the iteration count and
+    residuals of its SolveResult -- as float64 .npy files.  ``x`` longer than DUMP_SAMPLE is written at a fixed seeded
+    sample of positions, ascending, which ``x_index`` lists; the inputs are seeded too, so two builds compare entry for entry."""
+    n = len(x)
+    idx = np.arange(n) if n <= DUMP_SAMPLE else np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))
+    arrays = {"x": x[idx], "x_index": idx, "iterations": result.iterations, "rel_residual": result.rel_residual,
+              "abs_residual": result.abs_residual}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
+    return sorted(arrays)
 
 
 def stamps_of(sysm, N):
@@ -613,6 +636,22 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    dumped = None
+    if args.dump_outputs:                     # (before the solves below overwrite x)
+        if not distributed_path:
+            x_host = x.numpy()
+        else:
+            # every rank's owned rows, at their vertices; without the ground they are the one-GPU path's x
+            parts = [None] * world
+            dist.all_gather_object(parts, (dsolver.owned_reduced_global, dsolver.solution()))
+            g = int(sysm.ground)
+            x_host = np.full(nv - 1, np.nan)
+            for verts, vals in parts:
+                x_host[verts - (verts > g)] = vals
+            assert sum(len(p[0]) for p in parts) == nv - 1 and not np.isnan(x_host).any()
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, x_host, last)
+        del x_host
     # one more (untimed) solve with HIP events around every 16th SpMV launch, on the kernels' stream
     prof = solver(time_spmv=True)
     barrier()
@@ -791,6 +830,8 @@ def main():
                         "with the 40 MB map uploaded from pageable host memory in every call"}
             out["value_with_assembly"] = 1e3 / (ms_per_step + asm_ms + red_ms)
             out["ms_per_step_with_assembly"] = ms_per_step + asm_ms + red_ms
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if seam is not None:
             out["seam"] = seam
             out["seam_ms_per_solve"] = seam["ms_per_solve"]

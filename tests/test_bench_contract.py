@@ -5,16 +5,18 @@ import json
 import os
 import subprocess
 import sys
+import types
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.gpu
-def test_bench_prints_one_json_line_with_the_agreed_keys():
+def test_bench_prints_one_json_line_with_the_agreed_keys(tmp_path):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", "C2",
-           "--no-cpu-baseline", "--no-c5", "--no-rank-proxy", "--no-small", "--no-dist-one-rank"]
+           "--no-cpu-baseline", "--no-c5", "--no-rank-proxy", "--no-small", "--no-dist-one-rank", "--dump-outputs", str(tmp_path)]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -35,3 +37,27 @@ def test_bench_prints_one_json_line_with_the_agreed_keys():
     assert d["iterations"] > 5 and d["rel_residual"] <= 1.1e-12 and d["preconditioner"]["kind"] == "amg"
     assert d["assembly"]["ms"] > 0 and len(d["assembly"]["ms_each"]) == 10 and d["seam"]["ms_per_solve"] > d["ms_per_step"]
     assert d["preconditioner"]["launches"]["per_setup"] > 50
+    # --dump-outputs: the whole x of C2 (1 M unknowns, below the sampling limit) and the residuals of the last timed step
+    assert sorted(d["dump_outputs"]["arrays"]) == ["abs_residual", "iterations", "rel_residual", "x", "x_index"]
+    got = {k: np.load(tmp_path / f"{k}.npy") for k in d["dump_outputs"]["arrays"]}
+    assert all(a.dtype == np.float64 for a in got.values())
+    n = d["config"]["n_unknowns"]
+    assert got["x"].shape == (n,) and np.array_equal(got["x_index"], np.arange(n)) and np.isfinite(got["x"]).all()
+    assert int(got["iterations"]) == d["iterations"] and float(got["rel_residual"]) == d["rel_residual"]
+
+
+def test_dump_outputs_samples_a_long_solution_at_fixed_positions(tmp_path):
+    """Above bench.DUMP_SAMPLE entries x is written at the same seeded, ascending positions in every run, well inside 64 MB."""
+    import bench
+    n = bench.DUMP_SAMPLE + 12345
+    x = np.arange(n, dtype=np.float64) * 0.5
+    res = types.SimpleNamespace(iterations=17, rel_residual=9e-13, abs_residual=2e-10)
+    names = bench.dump_outputs(str(tmp_path / "a"), x, res)
+    bench.dump_outputs(str(tmp_path / "b"), x, res)
+    for k in names:
+        assert np.array_equal(np.load(tmp_path / "a" / f"{k}.npy"), np.load(tmp_path / "b" / f"{k}.npy"))
+    idx = np.load(tmp_path / "a" / "x_index.npy")
+    assert len(idx) == bench.DUMP_SAMPLE and np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < n
+    assert np.array_equal(np.load(tmp_path / "a" / "x.npy"), x[idx.astype(np.int64)])
+    assert float(np.load(tmp_path / "a" / "iterations.npy")) == 17
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64 << 20
