@@ -1,0 +1,59 @@
+/* padne_hip_probe.h -- TEST-ONLY kernel probe of libpadne_hip.so.  Neither the drop-in boundary (include/padne_hip.h) nor the
+ * multi-rank scaffolding (include/padne_hip_test.h): one entry that drives a single product launcher of the solver on inputs a
+ * test chooses, so that every SpMV / SpMM kernel form and epilogue can be held against a host reference.  Bound by
+ * padne_amd/_hip.py (PROBE_SIGNATURES). */
+#ifndef PADNE_HIP_PROBE_H
+#define PADNE_HIP_PROBE_H
+
+#include "padne_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* ONE call of one of the product launchers the solver uses (spmv.hip / spmm.hip), for checking every kernel form and epilogue
+ * against a host reference (tests/test_products_vs_reference.py).  The launchers are the solver's own: nothing is instantiated here.
+ *
+ * First the matrix is prepared by the library's builders, as `flags` asks (in this order): PADNE_TEST_HIERARCHY marks it a
+ * multigrid operator (eligible for a wave per row, no x-window plan), then 1/diag, the single-precision copies, the x-window plan,
+ * the wide plan, the interior / boundary split of its first n_owned columns (built although no exchange runs beside it).
+ *
+ * Arguments by launcher (device pointers; unused ones may be null; float launchers take (float)scale):
+ *   SPMV_MODE / SPMV_PART        launch_spmv_mode / _part(mode, part): x, y, dot_with, aux1, aux2, scale            (double)
+ *   SPMV_DOT_X32                 launch_spmv_dot_x32: x (float), y (double)
+ *   SPMV_F32 / SPMV_F32_PART     launch_spmv_f32 / _part(mode, part): x, y, aux1, aux2, scale                        (float)
+ *   SPMV_F32_RESTRICT            r = x, b_c = y, x_c = y2, dinv_c = aux2, c = scale
+ *   SPMV_F32_RESID_PRE           b = x, resid = y, dinv32 = aux2, c = scale
+ *   SPMV_F32_EXIT / _EXIT_PART   x, y (double) or z32 = y2, dot_with, aux1, aux2, scale, out_scale2 (, part)
+ *   SPMV_F32_WUP                 e = x, x_out = y, x_pre = aux0, r_pre = aux1, dinv32 = aux2, scale
+ *   SPMV_F32_WUP_EXIT            the same with z = y (double) or z32 = y2, dot_with, out_scale2, dot_b32 = rhs
+ *   SPMM_MODE / SPMM_F32         launch_spmm_mode / launch_spmm_f32(k, mode): as SPMV_MODE / SPMV_F32 on [n][k] vectors
+ *   SPMM_F32_EXIT                as SPMV_F32_EXIT (y32 = y2), out_scale2[k]
+ *   SPMM_F32_WUP / _WUP_EXIT     as SPMV_F32_WUP / _WUP_EXIT, rhs = the fine level's right-hand side [n][k]
+ *
+ * With partials_host != null the launch gets a partial-sum slot of k (SpMM) or 1 rows of kMaxPartials = 2048 doubles, filled
+ * with the sentinel 0xff bytes before the launch and copied to partials_host afterwards, all of it (n_partials_host >= rows * 2048).
+ * info[8] receives: the kernel form the launch took (PADNE_TEST_FORM_*; the SpMM kernel counts as a tile form), xw_state,
+ * xw_run, xw_nruns, the number of partial sums per row (spmv_partials / spmm8_grid), the interior and boundary tile counts of
+ * the split plan, and where the boundary launch's partial sums start. */
+enum {
+    PADNE_TEST_SPMV_MODE = 0, PADNE_TEST_SPMV_PART = 1, PADNE_TEST_SPMV_DOT_X32 = 2, PADNE_TEST_SPMV_F32 = 3,
+    PADNE_TEST_SPMV_F32_PART = 4, PADNE_TEST_SPMV_F32_RESTRICT = 5, PADNE_TEST_SPMV_F32_RESID_PRE = 6,
+    PADNE_TEST_SPMV_F32_EXIT = 7, PADNE_TEST_SPMV_F32_EXIT_PART = 8, PADNE_TEST_SPMV_F32_WUP = 9,
+    PADNE_TEST_SPMV_F32_WUP_EXIT = 10, PADNE_TEST_SPMM_MODE = 11, PADNE_TEST_SPMM_F32 = 12, PADNE_TEST_SPMM_F32_EXIT = 13,
+    PADNE_TEST_SPMM_F32_WUP = 14, PADNE_TEST_SPMM_F32_WUP_EXIT = 15
+};
+enum { PADNE_TEST_HIERARCHY = 1, PADNE_TEST_DINV = 2, PADNE_TEST_F32 = 4, PADNE_TEST_XW = 8, PADNE_TEST_XW_WIDE = 16,
+       PADNE_TEST_SPLIT = 32 };
+enum { PADNE_TEST_FORM_NONE = 0, PADNE_TEST_FORM_WPR = 1, PADNE_TEST_FORM_LIST = 2, PADNE_TEST_FORM_LONG = 3,
+       PADNE_TEST_FORM_WIDE = 4, PADNE_TEST_FORM_TILE = 5 };
+int padne_test_product(padne_ctx *ctx, padne_csr *m, int32_t flags, int64_t n_owned, int32_t launcher, int32_t mode,
+                       int32_t k, int32_t part, const void *x, void *y, void *y2, const void *aux0, const void *aux1,
+                       const void *aux2, const void *rhs, const double *dot_with, const int32_t *done_flag, double scale,
+                       const double *out_scale2, double *partials_host, int64_t n_partials_host, int32_t *info);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* PADNE_HIP_PROBE_H */

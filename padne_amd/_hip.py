@@ -130,6 +130,12 @@ TEST_SIGNATURES = {
     "padne_ctx_reload_options": (C.c_int, [_P]),
 }
 
+# the kernel probe (include/padne_hip_probe.h): one product launcher of the solver, run once on a test's inputs
+PROBE_SIGNATURES = {
+    "padne_test_product": (C.c_int, [_P, _P, C.c_int32, _I64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P,
+                                     _P, _P, _P, _P, C.c_double, _P, _PF64, _I64, _PI32]),
+}
+
 _lib = None
 
 
@@ -151,7 +157,7 @@ def load_library(path: str | None = None) -> C.CDLL:
         lib = C.CDLL(p, mode=C.RTLD_GLOBAL)
     except OSError as exc:
         raise HipUnavailableError(f"cannot load {p}: {exc}") from exc
-    for name, (res, args) in list(SIGNATURES.items()) + list(TEST_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(TEST_SIGNATURES.items()) + list(PROBE_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

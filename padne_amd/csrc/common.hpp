@@ -11,6 +11,7 @@
 
 #include "../../include/padne_hip.h"
 #include "../../include/padne_hip_test.h"
+#include "../../include/padne_hip_probe.h"
 
 #include <atomic>
 
@@ -240,13 +241,19 @@ int csr_build_f32(padne_ctx *ctx, padne_csr *m);
 int csr_build_xw_plan(padne_ctx *ctx, padne_csr *m);
 int csr_build_xw_plan_wide(padne_ctx *ctx, padne_csr *m, int grid_cap = 0);      // grid_cap: workgroups at most (a build that runs beside latency-bound work of the other stream)      // twelve runs of 20 (single-precision operators with float values only: W)
 // interior / boundary tiles of a row-partitioned operator whose first n_owned columns are the rank's own unknowns
-int csr_build_split_plan(padne_ctx *ctx, padne_csr *m, long long n_owned);
+// (force: build the plan even where no halo exchange runs beside the interior tiles -- the tests' single context)
+int csr_build_split_plan(padne_ctx *ctx, padne_csr *m, long long n_owned, bool force = false);
 // number of per-workgroup partial sums a product with a dot epilogue on `m` writes (spmv_grid, or the grids of the
 // interior and the boundary launch together)
 int spmv_partials(const padne_csr *m);
 // which part of a split operator a launch covers: everything (one after the other), the interior tiles, the boundary
 // tiles.  On an operator without a split plan SPMV_INTERIOR does nothing and SPMV_BOUNDARY is the whole product.
 enum { SPMV_ALL = 0, SPMV_INTERIOR = 1, SPMV_BOUNDARY = 2 };
+// The kernel a product of launch_spmv_typed runs on `m` (spmv.hip): none (nothing to do), a wave per row, the list of interior /
+// boundary tiles, the 16-per-lane gather form, the wide x-window plan, the tile kernel (gather and / or x windows).
+// x_bytes / y_bytes: sizeof the vector / output type; part as the launcher is given it.  The ONE place the choice is made.
+enum { SPMV_FORM_NONE = 0, SPMV_FORM_WPR = 1, SPMV_FORM_LIST = 2, SPMV_FORM_LONG = 3, SPMV_FORM_WIDE = 4, SPMV_FORM_TILE = 5 };
+int spmv_kernel_form(const padne_csr *m, int mode, int x_bytes, int y_bytes, bool with_dot, bool with_partials, int part);
 int launch_spmv_part(padne_ctx *ctx, const padne_csr *m, int mode, int part, const double *x, double *y, const double *dot_with,
                      double *partials, const int32_t *done_flag, const double *aux1, const double *aux2, double scale);
 int launch_spmv_f32_part(padne_ctx *ctx, const padne_csr *m, int mode, int part, const float *x, float *y, double *partials,

@@ -546,6 +546,28 @@ int spmv_partials(const padne_csr *m) {
     return split_grid(m, m->split_n_int) + (m->split_n_bnd > 0 ? split_grid(m, m->split_n_bnd) : 0);
 }
 
+int spmv_kernel_form(const padne_csr *m, int mode, int x_bytes, int y_bytes, bool with_dot, bool with_partials, int part) {
+    if (m->n_rows == 0) return SPMV_FORM_NONE;
+    if (split_in_use(m)) {
+        // (a product with partial sums over the whole split operator is the interior launch and the boundary launch)
+        if (part == SPMV_BOUNDARY && m->split_n_bnd == 0) return SPMV_FORM_NONE;
+        if (part == SPMV_INTERIOR || part == SPMV_BOUNDARY || (part == SPMV_ALL && with_partials)) return SPMV_FORM_LIST;
+    } else if (part == SPMV_INTERIOR) {
+        return SPMV_FORM_NONE;                           // no split plan: the whole product follows the exchange
+    }
+    if (use_wave_per_row(m) && !(mode == SPMV_WUP && with_dot)) return SPMV_FORM_WPR;
+    // single-precision operators of the cycle with long rows, no x windows and few tiles per wave (the levels below the
+    // first coarse one: 139 k rows at C4): the 16-per-lane form of the gather path, -11 us per cycle there.  On the million-row
+    // operators (the fine restriction, the first coarse level) it loses 2-5 us each: the shorter form stays
+    const bool long_rows = x_bytes == 4 && y_bytes == 4 && m->xw_state != 1 && m->n_rows < 500000 &&
+                           m->nnz > 8 * m->n_rows + 4 * (m->n_rows >> 3);
+    if (long_rows && (mode == SPMV_PLAIN || mode == SPMV_RESID || mode == SPMV_ADD || mode == SPMV_JACOBI || mode == SPMV_RESTRICT))
+        return SPMV_FORM_LONG;
+    // the wide plan exists for the fused up-leg product only (single-precision values, csr_build_xw_plan_wide)
+    if (m->xw_state == 1 && m->xw_nruns == kXwRunsWide) return SPMV_FORM_WIDE;
+    return SPMV_FORM_TILE;
+}
+
 template <typename VT, typename XT, typename YT>
 static int launch_spmv_typed(padne_ctx *ctx, const padne_csr *m, const VT *vals, int mode, const XT *x, YT *y,
                              const double *dot_with, double *partials, const int32_t *done_flag, const XT *aux1,
@@ -566,6 +588,7 @@ static int launch_spmv_typed(padne_ctx *ctx, const padne_csr *m, const VT *vals,
         return launch_spmv_typed<VT, XT, YT>(ctx, m, vals, mode, x, y, dot_with, partials, done_flag, aux1, aux2, scale,
                                              out_scale2, aux0, y2, SPMV_BOUNDARY);
     }
+    const int form = spmv_kernel_form(m, mode, (int)sizeof(XT), (int)sizeof(YT), dot_with != nullptr, partials != nullptr, part);
     int g = spmv_grid(m);
     const int *tile_list = nullptr;
     int n_list = 0, partial_off = 0;
@@ -580,7 +603,7 @@ static int launch_spmv_typed(padne_ctx *ctx, const padne_csr *m, const VT *vals,
         partial_off = split_grid(m, m->split_n_int);
         g = split_grid(m, n_list);
     }
-    if (use_wave_per_row(m) && !(mode == SPMV_WUP && dot_with != nullptr)) {
+    if (form == SPMV_FORM_WPR) {
 #define PADNE_SPMV_WPR(M)                                                                                           \
     hipLaunchKernelGGL((csr_spmv_wpr_kernel<M, VT, XT, YT>), dim3(g), dim3(kSpmvThreads), 0, ctx->stream,            \
                        (int)m->n_rows, m->rowptr, m->cols, vals, x, y, dot_with, partials, done_flag, aux1, aux2,    \
@@ -613,7 +636,7 @@ static int launch_spmv_typed(padne_ctx *ctx, const padne_csr *m, const VT *vals,
     hipLaunchKernelGGL((csr_spmv_kernel<M, VT, XT, YT, false, sizeof(XT) == 4 && sizeof(YT) == 4>), dim3(g), dim3(kSpmvThreads), xs_bytes, ctx->stream, PADNE_SPMV_ARGS)
 #define PADNE_SPMV_LAUNCH_LIST(M)                                                                                \
     hipLaunchKernelGGL((csr_spmv_kernel<M, VT, XT, YT, true>), dim3(g), dim3(kSpmvThreads), xs_bytes, ctx->stream, PADNE_SPMV_ARGS)
-    if (tile_list != nullptr) {
+    if (form == SPMV_FORM_LIST) {
         // the products that follow a halo exchange: q = A p of the CG loop, the Lanczos steps, residual and smoothing of the cycle
         switch (mode) {
             case SPMV_PLAIN: PADNE_SPMV_LAUNCH_LIST(SPMV_PLAIN); break;
@@ -626,12 +649,7 @@ static int launch_spmv_typed(padne_ctx *ctx, const padne_csr *m, const VT *vals,
         PADNE_HIP_CHECK(hipGetLastError());
         return PADNE_OK;
     }
-    // single-precision operators of the cycle with long rows, no x windows and few tiles per wave (the levels below the
-    // first coarse one: 139 k rows at C4): the 16-per-lane form of the gather path, -11 us per cycle there.  On the million-row
-    // operators (the fine restriction, the first coarse level) it loses 2-5 us each: the shorter form stays
-    const bool long_rows = sizeof(XT) == 4 && sizeof(YT) == 4 && xw_desc == nullptr && m->n_rows < 500000 &&
-                           m->nnz > 8 * m->n_rows + 4 * (m->n_rows >> 3);
-    if (long_rows && (mode == SPMV_PLAIN || mode == SPMV_RESID || mode == SPMV_ADD || mode == SPMV_JACOBI || mode == SPMV_RESTRICT)) {
+    if (form == SPMV_FORM_LONG) {
         switch (mode) {
             case SPMV_PLAIN: PADNE_SPMV_LAUNCH_LONG(SPMV_PLAIN); break;
             case SPMV_RESID: PADNE_SPMV_LAUNCH_LONG(SPMV_RESID); break;
@@ -642,8 +660,7 @@ static int launch_spmv_typed(padne_ctx *ctx, const padne_csr *m, const VT *vals,
         PADNE_HIP_CHECK(hipGetLastError());
         return PADNE_OK;
     }
-    if (wide) {
-        // the wide plan exists for the fused up-leg product only (single-precision values, csr_build_xw_plan_wide)
+    if (form == SPMV_FORM_WIDE) {
         PADNE_REQUIRE(mode == SPMV_WUP && sizeof(VT) == 4 && sizeof(XT) == 4, "the wide x-window plan serves the W product");
         hipLaunchKernelGGL((csr_spmv_kernel<SPMV_WUP, VT, XT, YT, false, false, true>), dim3(g), dim3(kSpmvThreads), xs_bytes,
                            ctx->stream, PADNE_SPMV_ARGS);
@@ -1091,11 +1108,11 @@ __global__ void split_scatter_kernel(int n_wtiles, const int *__restrict__ flag,
     else tiles[t - pos[t]] = t;
 }
 
-int csr_build_split_plan(padne_ctx *ctx, padne_csr *m, long long n_owned) {
+int csr_build_split_plan(padne_ctx *ctx, padne_csr *m, long long n_owned, bool force) {
     if (m->split_state != 0) return PADNE_OK;
     m->split_state = -1;
     // (only where the exchange really runs beside the interior tiles: otherwise the second launch is pure overhead)
-    if (m->n_cols <= n_owned || m->n_rows < 64 * 64 || ctx->opt.no_split || !comm_exchange_overlaps(ctx))
+    if (m->n_cols <= n_owned || m->n_rows < 64 * 64 || ctx->opt.no_split || !(force || comm_exchange_overlaps(ctx)))
         return PADNE_OK;
     padne_ctx *owner = m->owner ? m->owner : ctx;
     const int n_tiles = (int)((m->n_rows + 63) / 64);
@@ -1215,3 +1232,114 @@ int csr_build_dinv(padne_ctx *ctx, padne_csr *m) {
 }
 
 }  // namespace padne
+
+// ---- test entry: one call of one product launcher (include/padne_hip_test.h) ----------------------------------------
+using namespace padne;
+
+static_assert(PADNE_TEST_FORM_WPR == SPMV_FORM_WPR && PADNE_TEST_FORM_LIST == SPMV_FORM_LIST && PADNE_TEST_FORM_LONG == SPMV_FORM_LONG &&
+                  PADNE_TEST_FORM_WIDE == SPMV_FORM_WIDE && PADNE_TEST_FORM_TILE == SPMV_FORM_TILE,
+              "the test header reports the dispatcher's forms");
+
+extern "C" int padne_test_product(padne_ctx *ctx, padne_csr *m, int32_t flags, int64_t n_owned, int32_t launcher, int32_t mode,
+                                  int32_t k, int32_t part, const void *x, void *y, void *y2, const void *aux0, const void *aux1,
+                                  const void *aux2, const void *rhs, const double *dot_with, const int32_t *done_flag, double scale,
+                                  const double *out_scale2, double *partials_host, int64_t n_partials_host, int32_t *info) {
+    PADNE_REQUIRE(ctx && m && info, "null argument");
+    const bool spmm = launcher >= PADNE_TEST_SPMM_MODE;
+    PADNE_REQUIRE(launcher >= PADNE_TEST_SPMV_MODE && launcher <= PADNE_TEST_SPMM_F32_WUP_EXIT, "launcher");
+    PADNE_REQUIRE(!spmm || k == 8 || k == 4 || k == 2, "lockstep width");
+    const int rows = spmm ? k : 1;      // partial rows of kMaxPartials: one per right-hand side
+    PADNE_REQUIRE(partials_host == nullptr || n_partials_host >= (int64_t)rows * kMaxPartials, "partials buffer too small");
+    PADNE_HIP_CHECK(hipSetDevice(ctx->device));
+    // the matrix, prepared by the library's own builders
+    if (flags & PADNE_TEST_HIERARCHY) m->hierarchy_operator = true;
+    if (flags & PADNE_TEST_DINV) PADNE_TRY(csr_build_dinv(ctx, m));
+    if (flags & PADNE_TEST_F32) PADNE_TRY(csr_build_f32(ctx, m));
+    if (flags & PADNE_TEST_XW) PADNE_TRY(csr_build_xw_plan(ctx, m));
+    if (flags & PADNE_TEST_XW_WIDE) PADNE_TRY(csr_build_xw_plan_wide(ctx, m));
+    if (flags & PADNE_TEST_SPLIT) PADNE_TRY(csr_build_split_plan(ctx, m, n_owned, true));
+    double *partials = nullptr;
+    if (partials_host != nullptr) {
+        PADNE_HIP_CHECK(hipMalloc(&partials, sizeof(double) * (size_t)rows * kMaxPartials));
+        PADNE_HIP_CHECK(hipMemsetAsync(partials, 0xff, sizeof(double) * (size_t)rows * kMaxPartials, ctx->stream));      // sentinel
+    }
+    // the kernel form the launch takes, asked with the arguments the launcher hands to the dispatcher
+    const bool wp = partials != nullptr;
+    int form = SPMV_FORM_TILE;
+    switch (launcher) {
+        case PADNE_TEST_SPMV_MODE: form = spmv_kernel_form(m, mode, 8, 8, dot_with != nullptr, wp, SPMV_ALL); break;
+        case PADNE_TEST_SPMV_PART: form = spmv_kernel_form(m, mode, 8, 8, dot_with != nullptr, wp, part); break;
+        case PADNE_TEST_SPMV_DOT_X32: form = spmv_kernel_form(m, SPMV_DOT, 8, 8, false, wp, SPMV_ALL); break;
+        case PADNE_TEST_SPMV_F32: form = spmv_kernel_form(m, mode, 4, 4, false, wp, SPMV_ALL); break;
+        case PADNE_TEST_SPMV_F32_PART: form = spmv_kernel_form(m, mode, 4, 4, false, wp, part); break;
+        case PADNE_TEST_SPMV_F32_RESTRICT: form = spmv_kernel_form(m, SPMV_RESTRICT, 4, 4, false, false, SPMV_ALL); break;
+        case PADNE_TEST_SPMV_F32_RESID_PRE: form = spmv_kernel_form(m, SPMV_RESID_PRE, 4, 4, false, false, SPMV_ALL); break;
+        case PADNE_TEST_SPMV_F32_EXIT: form = spmv_kernel_form(m, SPMV_JACOBI, 4, y2 ? 4 : 8, dot_with != nullptr, wp, SPMV_ALL); break;
+        case PADNE_TEST_SPMV_F32_EXIT_PART: form = spmv_kernel_form(m, SPMV_JACOBI, 4, y2 ? 4 : 8, dot_with != nullptr, wp, part); break;
+        case PADNE_TEST_SPMV_F32_WUP: form = spmv_kernel_form(m, SPMV_WUP, 4, 4, false, false, SPMV_ALL); break;
+        case PADNE_TEST_SPMV_F32_WUP_EXIT: form = spmv_kernel_form(m, SPMV_WUP, 4, y2 ? 4 : 8, dot_with != nullptr, wp, SPMV_ALL); break;
+        default: form = m->n_rows == 0 ? SPMV_FORM_NONE : SPMV_FORM_TILE; break;      // the SpMM kernel: one form
+    }
+    const double *xd = (const double *)x, *a1d = (const double *)aux1, *a2d = (const double *)aux2;
+    const float *xf = (const float *)x, *a0f = (const float *)aux0, *a1f = (const float *)aux1, *a2f = (const float *)aux2;
+    const float *rhsf = (const float *)rhs;
+    const float sf = (float)scale;
+    int rc = PADNE_OK;
+    switch (launcher) {
+        case PADNE_TEST_SPMV_MODE:
+            rc = launch_spmv_mode(ctx, m, mode, xd, (double *)y, dot_with, partials, done_flag, a1d, a2d, scale);
+            break;
+        case PADNE_TEST_SPMV_PART:
+            rc = launch_spmv_part(ctx, m, mode, part, xd, (double *)y, dot_with, partials, done_flag, a1d, a2d, scale);
+            break;
+        case PADNE_TEST_SPMV_DOT_X32: rc = launch_spmv_dot_x32(ctx, m, xf, (double *)y, partials, done_flag); break;
+        case PADNE_TEST_SPMV_F32: rc = launch_spmv_f32(ctx, m, mode, xf, (float *)y, partials, done_flag, a1f, a2f, sf); break;
+        case PADNE_TEST_SPMV_F32_PART:
+            rc = launch_spmv_f32_part(ctx, m, mode, part, xf, (float *)y, partials, done_flag, a1f, a2f, sf);
+            break;
+        case PADNE_TEST_SPMV_F32_RESTRICT: rc = launch_spmv_f32_restrict(ctx, m, xf, (float *)y, (float *)y2, done_flag, a2f, sf); break;
+        case PADNE_TEST_SPMV_F32_RESID_PRE: rc = launch_spmv_f32_resid_pre(ctx, m, xf, (float *)y, done_flag, a2f, sf); break;
+        case PADNE_TEST_SPMV_F32_EXIT:
+            rc = launch_spmv_f32_exit(ctx, m, xf, (double *)y, dot_with, partials, done_flag, a1f, a2f, sf, out_scale2, (float *)y2);
+            break;
+        case PADNE_TEST_SPMV_F32_EXIT_PART:
+            rc = launch_spmv_f32_exit_part(ctx, m, part, xf, (double *)y, dot_with, partials, done_flag, a1f, a2f, sf, out_scale2,
+                                           (float *)y2);
+            break;
+        case PADNE_TEST_SPMV_F32_WUP: rc = launch_spmv_f32_wup(ctx, m, xf, (float *)y, done_flag, a0f, a1f, a2f, sf); break;
+        case PADNE_TEST_SPMV_F32_WUP_EXIT:
+            rc = launch_spmv_f32_wup_exit(ctx, m, xf, (double *)y, dot_with, partials, done_flag, a0f, a1f, a2f, sf, out_scale2,
+                                          (float *)y2, rhsf);
+            break;
+        case PADNE_TEST_SPMM_MODE:
+            rc = launch_spmm_mode(ctx, m, k, mode, xd, (double *)y, dot_with, partials, done_flag, a1d, a2d, scale);
+            break;
+        case PADNE_TEST_SPMM_F32: rc = launch_spmm_f32(ctx, m, k, mode, xf, (float *)y, partials, done_flag, a1f, a2f, sf); break;
+        case PADNE_TEST_SPMM_F32_EXIT:
+            rc = launch_spmm_f32_exit(ctx, m, k, xf, (double *)y, dot_with, partials, done_flag, a1f, a2f, sf, out_scale2, (float *)y2);
+            break;
+        case PADNE_TEST_SPMM_F32_WUP: rc = launch_spmm_f32_wup(ctx, m, k, xf, (float *)y, done_flag, a0f, a1f, a2f, sf); break;
+        default:
+            rc = launch_spmm_f32_wup_exit(ctx, m, k, xf, (double *)y, dot_with, partials, done_flag, a0f, a1f, a2f, sf, out_scale2,
+                                          (float *)y2, rhsf);
+            break;
+    }
+    hipError_t e = hipStreamSynchronize(ctx->stream);
+    if (rc == PADNE_OK && e == hipSuccess && partials != nullptr)
+        e = hipMemcpy(partials_host, partials, sizeof(double) * (size_t)rows * kMaxPartials, hipMemcpyDeviceToHost);
+    if (partials != nullptr) (void)hipFree(partials);
+    if (rc != PADNE_OK) return rc;
+    if (e != hipSuccess) {
+        set_error("test product: %s", hipGetErrorString(e));
+        return PADNE_E_HIP;
+    }
+    info[0] = form;
+    info[1] = m->xw_state;
+    info[2] = m->xw_run;
+    info[3] = m->xw_nruns;
+    info[4] = spmm ? spmm8_grid(m) : spmv_partials(m);
+    info[5] = m->split_state == 1 ? m->split_n_int : 0;
+    info[6] = m->split_state == 1 ? m->split_n_bnd : 0;
+    info[7] = split_in_use(m) ? split_grid(m, m->split_n_int) : 0;      // where the boundary launch's partial sums start
+    return PADNE_OK;
+}

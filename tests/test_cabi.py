@@ -42,6 +42,19 @@ def test_every_declared_symbol_is_exported_and_bound():
     assert sorted(_hip.TEST_SIGNATURES) == test_names
 
 
+def test_probe_symbols_are_exported_and_bound():
+    """The kernel probe (include/padne_hip_probe.h) is held like the other headers: every declared symbol exported and bound in
+    _hip.PROBE_SIGNATURES, nothing bound there that the header does not declare, no name shared with another header."""
+    build.build(verbose=False)
+    lib = ctypes.CDLL(_hip.LIB_PATH)
+    probe = declared_symbols("padne_hip_probe.h")
+    assert probe == ["padne_test_product"]
+    for name in probe:
+        assert hasattr(lib, name), f"{name} declared in padne_hip_probe.h but not exported"
+    assert sorted(_hip.PROBE_SIGNATURES) == probe
+    assert not set(probe) & (set(declared_symbols()) | set(declared_symbols("padne_hip_test.h")))
+
+
 def test_abi_version_and_error_string():
     lib = _hip.load_library()
     assert lib.padne_abi_version() == 1
