@@ -11,23 +11,27 @@
 extern "C" {
 #endif
 
-/* ONE call of one of the product launchers the solver uses (spmv.hip / spmm.hip), for checking every kernel form and epilogue
- * against a host reference (tests/test_products_vs_reference.py).  The launchers are the solver's own: nothing is instantiated here.
+/* ONE product in one of the call shapes the solver uses (spmv.hip / spmm.hip: launch_spmv, launch_spmm), for checking every kernel
+ * form and epilogue against a host reference (tests/test_products_vs_reference.py).  The entries are the solver's own: nothing is
+ * instantiated here.
  *
  * First the matrix is prepared by the library's builders, as `flags` asks (in this order): PADNE_TEST_HIERARCHY marks it a
  * multigrid operator (eligible for a wave per row, no x-window plan), then 1/diag, the single-precision copies, the x-window plan,
  * the wide plan, the interior / boundary split of its first n_owned columns (built although no exchange runs beside it).
  *
- * Arguments by launcher (device pointers; unused ones may be null; float launchers take (float)scale):
- *   SPMV_MODE / SPMV_PART        launch_spmv_mode / _part(mode, part): x, y, dot_with, aux1, aux2, scale            (double)
- *   SPMV_DOT_X32                 launch_spmv_dot_x32: x (float), y (double)
- *   SPMV_F32 / SPMV_F32_PART     launch_spmv_f32 / _part(mode, part): x, y, aux1, aux2, scale                        (float)
- *   SPMV_F32_RESTRICT            r = x, b_c = y, x_c = y2, dinv_c = aux2, c = scale
- *   SPMV_F32_RESID_PRE           b = x, resid = y, dinv32 = aux2, c = scale
- *   SPMV_F32_EXIT / _EXIT_PART   x, y (double) or z32 = y2, dot_with, aux1, aux2, scale, out_scale2 (, part)
- *   SPMV_F32_WUP                 e = x, x_out = y, x_pre = aux0, r_pre = aux1, dinv32 = aux2, scale
- *   SPMV_F32_WUP_EXIT            the same with z = y (double) or z32 = y2, dot_with, out_scale2, dot_b32 = rhs
- *   SPMM_MODE / SPMM_F32         launch_spmm_mode / launch_spmm_f32(k, mode): as SPMV_MODE / SPMV_F32 on [n][k] vectors
+ * A launcher ID names a call shape: the types, the epilogue and the operands the solver passes.  The flat arguments map onto the
+ * operands by role (ProductArgs, padne_amd/csrc/common.hpp): aux0 = x_pre, aux1 = b, aux2 = dinv, and the rest by name.  Device
+ * pointers; unused ones may be null; the float shapes take (float)scale.
+ *   SPMV_MODE / SPMV_PART        double, `mode` (, part): x, y, b, dinv, scale, dot_with, partials
+ *   SPMV_DOT_X32                 SPMV_DOT with x stored in float, y in double: partials
+ *   SPMV_F32 / SPMV_F32_PART     float, `mode` (, part): x, y, b, dinv, scale, partials
+ *   SPMV_F32_RESTRICT            SPMV_RESTRICT: r = x, b_c = y, x_c = y2, dinv_c = aux2, c = scale
+ *   SPMV_F32_RESID_PRE           SPMV_RESID_PRE: b = x, resid = y, dinv = aux2, c = scale
+ *   SPMV_F32_EXIT / _EXIT_PART   the exit stage, SPMV_JACOBI: x, y (double) or z32 = y2, b, dinv, scale, dot_with, partials,
+ *                                out_scale2 (, part)
+ *   SPMV_F32_WUP                 SPMV_WUP: e = x, x_out = y, x_pre = aux0, r_pre = b = aux1, dinv = aux2, scale
+ *   SPMV_F32_WUP_EXIT            the same as an exit stage: z = y (double) or z32 = y2, dot_with, partials, out_scale2, rhs
+ *   SPMM_MODE / SPMM_F32         as SPMV_MODE / SPMV_F32 on [n][k] vectors (k, mode)
  *   SPMM_F32_EXIT                as SPMV_F32_EXIT (y32 = y2), out_scale2[k]
  *   SPMM_F32_WUP / _WUP_EXIT     as SPMV_F32_WUP / _WUP_EXIT, rhs = the fine level's right-hand side [n][k]
  *

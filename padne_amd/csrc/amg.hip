@@ -4374,6 +4374,14 @@ static int amg_apply_f32(padne_ctx *ctx, Amg *amg, const double *r, double *z, d
         return PADNE_E_INVALID;
     }
     bool fused_start = false;      // the restriction onto this level has already written its pre-smoothed start
+    // the last product of the cycle: z in double (or with z32 in single precision and unscaled) and the r.z partials
+    auto exit_stage = [&](const padne_csr *m, int mode, const float *x, ProductArgs<float> a, int part) {
+        a.dot_with = r;
+        a.partials = partials_rz;
+        a.out_scale2 = bb2;
+        return z32 != nullptr ? launch_spmv<float, float>(ctx, m, mode, x, z32, a, part)
+                              : launch_spmv<float, double>(ctx, m, mode, x, z, a, part);
+    };
     // last partitioned level of a row-partitioned hierarchy: the values of the other ranks' vertices after the coarse
     // correction, x1 + P e, are computed here -- x1 came with the down-leg exchange, their rows of P with the setup, e is
     // the tail solution every rank holds -- instead of a second exchange (same arithmetic as on the owning rank: bitwise
@@ -4425,75 +4433,67 @@ static int amg_apply_f32(padne_ctx *ctx, Amg *amg, const double *r, double *z, d
             // the pre-smoothed iterate goes out, the interior tiles of the residual run while it travels
             HaloTicket tk;
             PADNE_TRY(halo_send_f32(ctx, L.halo, xa, done_flag, &tk));
-            PADNE_TRY(launch_spmv_f32_part(ctx, L.A, SPMV_RESID, SPMV_INTERIOR, xa, tmp, nullptr, done_flag, b, nullptr, 0.f));
+            PADNE_TRY(launch_spmv<float, float>(ctx, L.A, SPMV_RESID, xa, tmp, {.b = b, .done_flag = done_flag}, SPMV_INTERIOR));
             PADNE_TRY(halo_recv_f32(ctx, L.halo, xa, done_flag, tk));
-            PADNE_TRY(launch_spmv_f32_part(ctx, L.A, SPMV_RESID, SPMV_BOUNDARY, xa, tmp, nullptr, done_flag, b, nullptr, 0.f));
+            PADNE_TRY(launch_spmv<float, float>(ctx, L.A, SPMV_RESID, xa, tmp, {.b = b, .done_flag = done_flag}, SPMV_BOUNDARY));
         } else if (l == 0 && L.W != nullptr && spmv_resid_pre_ok(L.A)) {
             // the fine level never looks at its pre-smoothed iterate: the residual is formed from the right-hand side alone
             // (xa = c D^-1 b inside the staging of the product), the up-leg takes c D^-1 (b + residual) (spmv.hip)
-            PADNE_TRY(launch_spmv_f32_resid_pre(ctx, L.A, b, tmp, done_flag, L.A->dinv32, (float)L.jac));
+            PADNE_TRY(launch_spmv<float, float>(ctx, L.A, SPMV_RESID_PRE, b, tmp,
+                                                {.dinv = L.A->dinv32, .scale = (float)L.jac, .done_flag = done_flag}));
         } else {
-            PADNE_TRY(launch_spmv_f32(ctx, L.A, SPMV_RESID, xa, tmp, nullptr, done_flag, b, nullptr, 0.f));
+            PADNE_TRY(launch_spmv<float, float>(ctx, L.A, SPMV_RESID, xa, tmp, {.b = b, .done_flag = done_flag}));
         }
         // the restriction also leaves the first sweep of the level below (from a zero start: x = c D^-1 b), unless that
         // level is the coarsest (solved directly) -- one short launch less per level
         AmgLevel &Lc = amg->levels[l + 1];
         fused_start = l + 1 < nl - 1 && Lc.A->dinv32 != nullptr;
         if (fused_start)
-            PADNE_TRY(launch_spmv_f32_restrict(ctx, L.R, tmp, (float *)Lc.b, (float *)Lc.xa, done_flag, Lc.A->dinv32,
-                                               (float)Lc.jac));
+            PADNE_TRY(launch_spmv<float, float>(ctx, L.R, SPMV_RESTRICT, tmp, (float *)Lc.b,
+                                                {.dinv = Lc.A->dinv32, .scale = (float)Lc.jac, .y2 = (float *)Lc.xa, .done_flag = done_flag}));
         else
-            PADNE_TRY(launch_spmv_f32(ctx, L.R, SPMV_PLAIN, tmp, (float *)Lc.b, nullptr, done_flag, nullptr, nullptr, 0.f));
+            PADNE_TRY(launch_spmv<float, float>(ctx, L.R, SPMV_PLAIN, tmp, (float *)Lc.b, {.done_flag = done_flag}));
     }
     for (int l = nl - 2; l >= 0; --l) {
         AmgLevel &L = amg->levels[l];
         float *b = (float *)L.b, *xa = (float *)L.xa;
-        if (L.W != nullptr && amg->dist) {
-            // row-partitioned level: the same product, its input the coarse solution with the other ranks' exported values
-            // behind it -- computed from the tail solution on the last partitioned level (e_ext), exchanged otherwise: one
-            // exchange of the COARSE level's vector instead of one of this level's corrected iterate
+        if (L.W != nullptr) {
+            // coarse correction + post-smoothing (+ exit) in one product with W = P - c D^-1 A P: x_pre + c D^-1 r_pre + W e, r_pre
+            // the residual of the pre-smoothed iterate that the down-leg restricted (tmp still holds it)
             float *e = (float *)amg->levels[l + 1].xb;
-            if (local_halo && l == nl - 2)
-                e = L.e_ext;
-            else
-                PADNE_TRY(halo_exchange_plan_f32(ctx, amg->levels[l + 1].halo, e, done_flag));
-            if (l == 0)
-                PADNE_TRY(launch_spmv_f32_wup_exit(ctx, L.W, e, z, r, partials_rz, done_flag, xa, (const float *)L.tmp,
-                                                   L.A->dinv32, (float)L.jac, bb2, z32, nullptr));
-            else
-                PADNE_TRY(launch_spmv_f32_wup(ctx, L.W, e, (float *)L.xb, done_flag, xa, (const float *)L.tmp, L.A->dinv32,
-                                              (float)L.jac));
+            if (amg->dist) {
+                // row-partitioned level: its input the coarse solution with the other ranks' exported values behind it --
+                // computed from the tail solution on the last partitioned level (e_ext), exchanged otherwise: one exchange of
+                // the COARSE level's vector instead of one of this level's corrected iterate
+                if (local_halo && l == nl - 2)
+                    e = L.e_ext;
+                else
+                    PADNE_TRY(halo_exchange_plan_f32(ctx, amg->levels[l + 1].halo, e, done_flag));
+            }
+            ProductArgs<float> up{.b = (const float *)L.tmp, .dinv = L.A->dinv32, .scale = (float)L.jac, .x_pre = xa,
+                                  .done_flag = done_flag};
+            if (l > 0) {
+                PADNE_TRY(launch_spmv<float, float>(ctx, L.W, SPMV_WUP, e, (float *)L.xb, up));
+            } else {
+                up.rhs = !amg->dist && spmv_resid_pre_ok(L.A) ? (const float *)b : nullptr;      // (as the down-leg decided)
+                PADNE_TRY(exit_stage(L.W, SPMV_WUP, e, up, SPMV_ALL));
+            }
             continue;
         }
-        if (L.W != nullptr && !amg->dist) {
-            // coarse correction + post-smoothing (+ exit) in one product with W = P - c D^-1 A P (tmp still holds the
-            // residual of the pre-smoothed iterate that the down-leg restricted)
-            if (l == 0)
-                PADNE_TRY(launch_spmv_f32_wup_exit(ctx, L.W, (const float *)amg->levels[1].xb, z, r, partials_rz, done_flag, xa,
-                                                   (const float *)L.tmp, L.A->dinv32, (float)L.jac, bb2, z32,
-                                                   spmv_resid_pre_ok(L.A) ? (const float *)b : nullptr));      // (as the down-leg decided)
-            else
-                PADNE_TRY(launch_spmv_f32_wup(ctx, L.W, (const float *)amg->levels[l + 1].xb, (float *)L.xb, done_flag, xa,
-                                              (const float *)L.tmp, L.A->dinv32, (float)L.jac));
-            continue;
-        }
-        PADNE_TRY(launch_spmv_f32(ctx, L.P, SPMV_ADD, (const float *)amg->levels[l + 1].xb, xa, nullptr, done_flag,
-                                  nullptr, nullptr, 0.f));
+        PADNE_TRY(launch_spmv<float, float>(ctx, L.P, SPMV_ADD, (const float *)amg->levels[l + 1].xb, xa, {.done_flag = done_flag}));
         HaloTicket tk;
         const bool exchange = amg->dist && !(local_halo && l == nl - 2);
         if (amg->dist && !exchange)
-            PADNE_TRY(launch_spmv_f32(ctx, L.P_halo, SPMV_ADD, (const float *)L.e_ext, xa + L.n, nullptr, done_flag, nullptr,
-                                      nullptr, 0.f));
+            PADNE_TRY(launch_spmv<float, float>(ctx, L.P_halo, SPMV_ADD, (const float *)L.e_ext, xa + L.n, {.done_flag = done_flag}));
         // post-smoothing: with an exchange of the corrected iterate its interior tiles run while the halo travels
         for (int part = exchange ? SPMV_INTERIOR : SPMV_ALL; part <= (exchange ? SPMV_BOUNDARY : SPMV_ALL); ++part) {
             if (exchange && part == SPMV_INTERIOR) PADNE_TRY(halo_send_f32(ctx, L.halo, xa, done_flag, &tk));
             if (exchange && part == SPMV_BOUNDARY) PADNE_TRY(halo_recv_f32(ctx, L.halo, xa, done_flag, tk));
+            const ProductArgs<float> sweep{.b = b, .dinv = L.A->dinv32, .scale = (float)L.jac, .done_flag = done_flag};
             if (l > 0)
-                PADNE_TRY(launch_spmv_f32_part(ctx, L.A, SPMV_JACOBI, part, xa, (float *)L.xb, nullptr, done_flag, b, L.A->dinv32,
-                                               (float)L.jac));
+                PADNE_TRY(launch_spmv<float, float>(ctx, L.A, SPMV_JACOBI, xa, (float *)L.xb, sweep, part));
             else
-                PADNE_TRY(launch_spmv_f32_exit_part(ctx, L.A, part, xa, z, r, partials_rz, done_flag, b, L.A->dinv32,
-                                                    (float)L.jac, bb2, z32));
+                PADNE_TRY(exit_stage(L.A, SPMV_JACOBI, xa, sweep, part));
         }
     }
     return PADNE_OK;
@@ -4578,6 +4578,14 @@ static int amg_apply_batch_k(padne_ctx *ctx, const padne_csr *A0, const double *
     hipStream_t s = ctx->stream;
     const int nl = (int)amg->levels.size();
     PADNE_TRY(amg_batch_vectors(ctx, amg));
+    // the last product of the cycle: z8 in double (or with z32 in single precision and unscaled) and the r.z partials
+    auto exit_stage = [&](const padne_csr *m, int mode, const float *x, ProductArgs<float> a) {
+        a.dot_with = r8;
+        a.partials = partials_rz;
+        a.out_scale2 = bb2;
+        return z32 != nullptr ? launch_spmm<float, float>(ctx, m, K, mode, x, z32, a)
+                              : launch_spmm<float, double>(ctx, m, K, mode, x, z8, a);
+    };
     for (int l = 0; l < nl; ++l) {
         AmgLevel &L = amg->levels[l];
         if (l == nl - 1) {
@@ -4596,9 +4604,8 @@ static int amg_apply_batch_k(padne_ctx *ctx, const padne_csr *A0, const double *
             hipLaunchKernelGGL(scale_dinv_xk_kernel<K>, dim3(gv > 0 ? gv : 1), dim3(256), 0, s, L.n, (float)L.jac,
                                (const float *)L.A->dinv32, (const float *)L.b8, L.xa8, done_flag);
         PADNE_HIP_CHECK(hipGetLastError());
-        PADNE_TRY(launch_spmm_f32(ctx, L.A, K, SPMV_RESID, L.xa8, L.tmp8, nullptr, done_flag, L.b8, nullptr, 0.f));
-        PADNE_TRY(launch_spmm_f32(ctx, L.R, K, SPMV_PLAIN, L.tmp8, amg->levels[l + 1].b8, nullptr, done_flag, nullptr,
-                                  nullptr, 0.f));
+        PADNE_TRY(launch_spmm<float, float>(ctx, L.A, K, SPMV_RESID, L.xa8, L.tmp8, {.b = L.b8, .done_flag = done_flag}));
+        PADNE_TRY(launch_spmm<float, float>(ctx, L.R, K, SPMV_PLAIN, L.tmp8, amg->levels[l + 1].b8, {.done_flag = done_flag}));
     }
     for (int l = nl - 2; l >= 0; --l) {
         AmgLevel &L = amg->levels[l];
@@ -4606,24 +4613,24 @@ static int amg_apply_batch_k(padne_ctx *ctx, const padne_csr *A0, const double *
             // coarse correction + post-smoothing (+ exit) in one product with W = P - c D^-1 A P, as in the single cycle (tmp8
             // still holds the residual of the pre-smoothed iterate that the down-leg restricted): 52 M instead of 24 + 70 M
             // non-zeros of the fine level per lockstep iteration
-            if (l == 0)
-                PADNE_TRY(launch_spmm_f32_wup_exit(ctx, L.W, K, amg->levels[1].xb8, z8, r8, partials_rz, done_flag,
-                                                   L.A->dinv32 != nullptr ? (const float *)nullptr : (const float *)L.xa8, L.tmp8,
-                                                   L.A->dinv32, (float)L.jac, bb2, z32,
-                                                   L.A->dinv32 != nullptr ? (const float *)L.b8 : (const float *)nullptr));
-            else
-                PADNE_TRY(launch_spmm_f32_wup(ctx, L.W, K, amg->levels[l + 1].xb8, L.xb8, done_flag, L.xa8, L.tmp8,
-                                              L.A->dinv32, (float)L.jac));
+            ProductArgs<float> up{.b = L.tmp8, .dinv = L.A->dinv32, .scale = (float)L.jac, .x_pre = L.xa8, .done_flag = done_flag};
+            if (l > 0) {
+                PADNE_TRY(launch_spmm<float, float>(ctx, L.W, K, SPMV_WUP, amg->levels[l + 1].xb8, L.xb8, up));
+            } else {
+                if (L.A->dinv32 != nullptr) {      // the fine level's exit stage formed from its right-hand side
+                    up.x_pre = nullptr;
+                    up.rhs = L.b8;
+                }
+                PADNE_TRY(exit_stage(L.W, SPMV_WUP, amg->levels[1].xb8, up));
+            }
             continue;
         }
-        PADNE_TRY(launch_spmm_f32(ctx, L.P, K, SPMV_ADD, amg->levels[l + 1].xb8, L.xa8, nullptr, done_flag, nullptr, nullptr,
-                                  0.f));
+        PADNE_TRY(launch_spmm<float, float>(ctx, L.P, K, SPMV_ADD, amg->levels[l + 1].xb8, L.xa8, {.done_flag = done_flag}));
+        const ProductArgs<float> sweep{.b = L.b8, .dinv = L.A->dinv32, .scale = (float)L.jac, .done_flag = done_flag};
         if (l > 0)
-            PADNE_TRY(launch_spmm_f32(ctx, L.A, K, SPMV_JACOBI, L.xa8, L.xb8, nullptr, done_flag, L.b8, L.A->dinv32,
-                                      (float)L.jac));
+            PADNE_TRY(launch_spmm<float, float>(ctx, L.A, K, SPMV_JACOBI, L.xa8, L.xb8, sweep));
         else
-            PADNE_TRY(launch_spmm_f32_exit(ctx, L.A, K, L.xa8, z8, r8, partials_rz, done_flag, L.b8, L.A->dinv32,
-                                           (float)L.jac, bb2, z32));
+            PADNE_TRY(exit_stage(L.A, SPMV_JACOBI, L.xa8, sweep));
     }
     return PADNE_OK;
 }
@@ -4706,9 +4713,8 @@ int amg_apply(padne_ctx *ctx, const padne_csr *A0, const double *r, double *z, d
                            (const double *)L.A->dinv, b, L.xa, done_flag);
         PADNE_HIP_CHECK(hipGetLastError());
         if (amg->dist) PADNE_TRY(halo_exchange_plan(ctx, L.halo, L.xa, done_flag));
-        PADNE_TRY(launch_spmv_mode(ctx, L.A, SPMV_RESID, L.xa, L.tmp, nullptr, nullptr, done_flag, b, nullptr, 0.0));
-        PADNE_TRY(launch_spmv_mode(ctx, L.R, SPMV_PLAIN, L.tmp, amg->levels[l + 1].b, nullptr, nullptr, done_flag,
-                                   nullptr, nullptr, 0.0));
+        PADNE_TRY(launch_spmv<double, double>(ctx, L.A, SPMV_RESID, L.xa, L.tmp, {.b = b, .done_flag = done_flag}));
+        PADNE_TRY(launch_spmv<double, double>(ctx, L.R, SPMV_PLAIN, L.tmp, amg->levels[l + 1].b, {.done_flag = done_flag}));
     }
     // upward sweep
     for (int l = nl - 2; l >= 0; --l) {
@@ -4716,10 +4722,11 @@ int amg_apply(padne_ctx *ctx, const padne_csr *A0, const double *r, double *z, d
         const double *b = (l == 0) ? r : L.b;
         const double *xc = amg->levels[l + 1].xb;
         double *out = (l == 0) ? z : L.xb;
-        PADNE_TRY(launch_spmv_mode(ctx, L.P, SPMV_ADD, xc, L.xa, nullptr, nullptr, done_flag, nullptr, nullptr, 0.0));
+        PADNE_TRY(launch_spmv<double, double>(ctx, L.P, SPMV_ADD, xc, L.xa, {.done_flag = done_flag}));
         if (amg->dist) PADNE_TRY(halo_exchange_plan(ctx, L.halo, L.xa, done_flag));
-        PADNE_TRY(launch_spmv_mode(ctx, L.A, SPMV_JACOBI, L.xa, out, nullptr, (l == 0) ? partials_rz : nullptr,
-                                   done_flag, b, L.A->dinv, L.jac));
+        PADNE_TRY(launch_spmv<double, double>(ctx, L.A, SPMV_JACOBI, L.xa, out,
+                                              {.b = b, .dinv = L.A->dinv, .scale = L.jac, .partials = (l == 0) ? partials_rz : nullptr,
+                                               .done_flag = done_flag}));
     }
     if (nl == 1 && partials_rz != nullptr && (amg->dist || amg->n_coarse <= 0)) {
         set_error("a hierarchy of one level serves as a preconditioner only through its dense inverse");

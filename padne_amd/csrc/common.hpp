@@ -41,9 +41,10 @@ void set_error(const char *fmt, ...);
         }                                                                                  \
     } while (0)
 
-#define PADNE_TRY(expr)                                                                    \
+// (variadic: the commas of a template call need no extra parentheses)
+#define PADNE_TRY(...)                                                                     \
     do {                                                                                   \
-        int _rc = (expr);                                                                  \
+        int _rc = (__VA_ARGS__);                                                           \
         if (_rc != PADNE_OK) return _rc;                                                   \
     } while (0)
 
@@ -213,30 +214,51 @@ int csr_shrink_nnz(padne_ctx *ctx, padne_csr *m, int64_t nnz);      // allocated
 int csr_build_dinv(padne_ctx *ctx, padne_csr *m);
 
 // kernels launched from several translation units
-int launch_spmv(padne_ctx *ctx, const padne_csr *m, const double *x, double *y,
-                const double *dot_with /* may be null */, double *partials /* may be null */,
-                const int32_t *done_flag /* may be null */);
 int spmv_grid(const padne_csr *m);
+// epilogues of the products (spmv.hip, the table above csr_spmv_kernel; the operands by their names in ProductArgs)
 enum { SPMV_PLAIN = 0, SPMV_DOT = 1, SPMV_RESID = 2, SPMV_ADD = 3, SPMV_JACOBI = 4,
        SPMV_DOT_AUX = 5,     // same as SPMV_DOT; used outside the CG loop (Lanczos estimates) so that kernel profiles keep the two apart
-       SPMV_WUP = 6,         // y = aux0 + scale * aux2 * aux1 + W x  (spmv.hip)
-       SPMV_RESTRICT = 7,    // y = A x ; y2 = scale * aux2 * y
-       SPMV_RESID_PRE = 8 }; // y = x - A (scale * aux2 .* x): residual of the sweep from zero, x the right-hand side (spmv.hip)
-int launch_spmv_mode(padne_ctx *ctx, const padne_csr *m, int mode, const double *x, double *y,
-                     const double *dot_with, double *partials, const int32_t *done_flag, const double *aux1,
-                     const double *aux2, double scale);
+       SPMV_WUP = 6,         // y = x_pre + scale * dinv * b + W x  (spmv.hip)
+       SPMV_RESTRICT = 7,    // y = A x ; y2 = scale * dinv * y
+       SPMV_RESID_PRE = 8 }; // y = x - A (scale * dinv .* x): residual of the sweep from zero, x the right-hand side (spmv.hip)
+// which part of a split operator a launch covers: everything (one after the other), the interior tiles, the boundary
+// tiles.  On an operator without a split plan SPMV_INTERIOR does nothing and SPMV_BOUNDARY is the whole product.
+enum { SPMV_ALL = 0, SPMV_INTERIOR = 1, SPMV_BOUNDARY = 2 };
 
-int launch_spmv_f32(padne_ctx *ctx, const padne_csr *m, int mode, const float *x, float *y, double *partials,
-                    const int32_t *done_flag, const float *aux1, const float *aux2, float scale);
-int launch_spmv_f32_restrict(padne_ctx *ctx, const padne_csr *R, const float *r, float *b_c, float *x_c,
-                             const int32_t *done_flag, const float *dinv_c, float c);
-int launch_spmv_f32_exit(padne_ctx *ctx, const padne_csr *m, const float *x, double *y, const double *dot_with,
-                         double *partials, const int32_t *done_flag, const float *aux1, const float *aux2, float scale,
-                         const double *out_scale2, float *z32 = nullptr);
-int launch_spmv_f32_wup_exit(padne_ctx *ctx, const padne_csr *w, const float *e, double *z, const double *dot_with,
-                             double *partials, const int32_t *done_flag, const float *x_pre, const float *r_pre,
-                             const float *dinv32, float scale, const double *out_scale2, float *z32 = nullptr,
-                             const float *dot_b32 = nullptr);
+// The operands of a product's epilogue, by their role in it.  Everything defaults to null / 0: a call site names what its
+// mode reads, e.g. launch_spmv<float, float>(ctx, A, SPMV_RESID, x, r, {.b = b, .done_flag = done}).
+template <typename XT> struct ProductArgs {
+    const XT *b = nullptr;                 // RESID / JACOBI: the right-hand side; WUP: the residual r_pre of the pre-smoothed iterate
+    const XT *dinv = nullptr;              // 1/diag of JACOBI, WUP, RESID_PRE; of the level restricted to in RESTRICT
+    XT scale = 0;                          // the damping that multiplies dinv
+    const XT *x_pre = nullptr;             // WUP: the pre-smoothed iterate
+    XT *y2 = nullptr;                      // RESTRICT: the second output, scale * dinv .* y
+    const XT *rhs = nullptr;               // WUP exit stage of the fine level: its right-hand side, read instead of x_pre
+    const double *dot_with = nullptr;      // DOT, DOT_AUX and the exit stages: partial sums of dot_with . y
+    double *partials = nullptr;            // per-workgroup partial sums (spmv_partials; SpMM: [k][kMaxPartials])
+    const double *out_scale2 = nullptr;    // exit stages: the result leaves in double multiplied by sqrt(*out_scale2) ([k] for SpMM)
+    const int32_t *done_flag = nullptr;    // stop word: nothing is done once *done_flag != 0
+};
+// the matrix values a product in XT multiplies: the double array, or the single-precision copy (csr_build_f32)
+template <typename XT> inline const XT *product_vals(const padne_csr *m) {
+    if constexpr (sizeof(XT) == 4) return m->vals32;
+    else return m->vals;
+}
+
+// y = A x with the epilogue of `mode` (spmv.hip).  XT: the vectors and the arithmetic, YT: the output, ST: the type x is
+// stored in -- float under a double product only for q = A p of the CG loop (SPMV_DOT, spmv_x32_ok).  Products in double
+// (the solver's own), in float (the multigrid cycle) and the cycle's exit stage <float, double>.
+template <typename XT, typename YT, typename ST = XT>
+int launch_spmv(padne_ctx *ctx, const padne_csr *m, int mode, const ST *x, YT *y, const ProductArgs<XT> &a, int part = SPMV_ALL);
+// the same for k = 8, 4 or 2 interleaved right-hand sides (spmm.hip: vectors [n][k], dinv stays [n], partials [k][kMaxPartials])
+template <typename XT, typename YT>
+int launch_spmm(padne_ctx *ctx, const padne_csr *m, int k, int mode, const XT *x, YT *y, const ProductArgs<XT> &a);
+// y = A x in double; with dot_with the partial sums of dot_with . y
+inline int launch_spmv(padne_ctx *ctx, const padne_csr *m, const double *x, double *y, const double *dot_with, double *partials,
+                       const int32_t *done_flag) {
+    return launch_spmv<double, double>(ctx, m, dot_with != nullptr ? SPMV_DOT : SPMV_PLAIN, x, y,
+                                       {.dot_with = dot_with, .partials = partials, .done_flag = done_flag});
+}
 int csr_build_f32(padne_ctx *ctx, padne_csr *m);
 int csr_build_xw_plan(padne_ctx *ctx, padne_csr *m);
 int csr_build_xw_plan_wide(padne_ctx *ctx, padne_csr *m, int grid_cap = 0);      // grid_cap: workgroups at most (a build that runs beside latency-bound work of the other stream)      // twelve runs of 20 (single-precision operators with float values only: W)
@@ -246,48 +268,11 @@ int csr_build_split_plan(padne_ctx *ctx, padne_csr *m, long long n_owned, bool f
 // number of per-workgroup partial sums a product with a dot epilogue on `m` writes (spmv_grid, or the grids of the
 // interior and the boundary launch together)
 int spmv_partials(const padne_csr *m);
-// which part of a split operator a launch covers: everything (one after the other), the interior tiles, the boundary
-// tiles.  On an operator without a split plan SPMV_INTERIOR does nothing and SPMV_BOUNDARY is the whole product.
-enum { SPMV_ALL = 0, SPMV_INTERIOR = 1, SPMV_BOUNDARY = 2 };
-// The kernel a product of launch_spmv_typed runs on `m` (spmv.hip): none (nothing to do), a wave per row, the list of interior /
-// boundary tiles, the 16-per-lane gather form, the wide x-window plan, the tile kernel (gather and / or x windows).
-// x_bytes / y_bytes: sizeof the vector / output type; part as the launcher is given it.  The ONE place the choice is made.
-enum { SPMV_FORM_NONE = 0, SPMV_FORM_WPR = 1, SPMV_FORM_LIST = 2, SPMV_FORM_LONG = 3, SPMV_FORM_WIDE = 4, SPMV_FORM_TILE = 5 };
-int spmv_kernel_form(const padne_csr *m, int mode, int x_bytes, int y_bytes, bool with_dot, bool with_partials, int part);
-int launch_spmv_part(padne_ctx *ctx, const padne_csr *m, int mode, int part, const double *x, double *y, const double *dot_with,
-                     double *partials, const int32_t *done_flag, const double *aux1, const double *aux2, double scale);
-int launch_spmv_f32_part(padne_ctx *ctx, const padne_csr *m, int mode, int part, const float *x, float *y, double *partials,
-                         const int32_t *done_flag, const float *aux1, const float *aux2, float scale);
-int launch_spmv_f32_exit_part(padne_ctx *ctx, const padne_csr *m, int part, const float *x, double *y, const double *dot_with,
-                              double *partials, const int32_t *done_flag, const float *aux1, const float *aux2, float scale,
-                              const double *out_scale2, float *z32 = nullptr);
-
-// spmm.hip: the same products for 8 interleaved right-hand sides (vectors [n][8]; aux2 = 1/diag stays [n]);
-// dot partials are [8][kMaxPartials]
-int spmm8_grid(const padne_csr *m);
-int launch_spmm8_mode(padne_ctx *ctx, const padne_csr *m, int mode, const double *x, double *y, const double *dot_with,
-                      double *partials, const int32_t *done_flag, const double *aux1, const double *aux2, double scale);
-// the same for k = 8, 4 or 2 interleaved right-hand sides (vectors [n][k]; dot partials [k][kMaxPartials])
-int launch_spmm_mode(padne_ctx *ctx, const padne_csr *m, int k, int mode, const double *x, double *y, const double *dot_with,
-                     double *partials, const int32_t *done_flag, const double *aux1, const double *aux2, double scale);
-int launch_spmm_f32(padne_ctx *ctx, const padne_csr *m, int k, int mode, const float *x, float *y, double *partials,
-                    const int32_t *done_flag, const float *aux1, const float *aux2, float scale);
-int launch_spmm_f32_exit(padne_ctx *ctx, const padne_csr *m, int k, const float *x, double *y, const double *dot_with,
-                         double *partials, const int32_t *done_flag, const float *aux1, const float *aux2,
-                         float scale, const double *out_scale2, float *y32 = nullptr);
-int launch_spmm_f32_wup_exit(padne_ctx *ctx, const padne_csr *w, int k, const float *e, double *z, const double *dot_with,
-                             double *partials, const int32_t *done_flag, const float *x_pre, const float *r_pre,
-                             const float *dinv32, float scale, const double *out_scale2, float *z32 = nullptr,
-                             const float *rhs = nullptr);
+int spmm8_grid(const padne_csr *m);      // the same for the SpMM kernel (spmm.hip)
+// the residual of the sweep from zero (SPMV_RESID_PRE) and a search direction in single precision run on the plain tile kernel
+// only: the callers ask first
 bool spmv_resid_pre_ok(const padne_csr *m);
-int launch_spmv_f32_resid_pre(padne_ctx *ctx, const padne_csr *m, const float *b, float *resid, const int32_t *done_flag,
-                              const float *dinv32, float c);
 bool spmv_x32_ok(const padne_csr *m);
-int launch_spmv_dot_x32(padne_ctx *ctx, const padne_csr *m, const float *x, double *y, double *partials, const int32_t *done_flag);
-int launch_spmv_f32_wup(padne_ctx *ctx, const padne_csr *w, const float *e, float *x_out, const int32_t *done_flag,
-                        const float *x_pre, const float *r_pre, const float *dinv32, float scale);
-int launch_spmm_f32_wup(padne_ctx *ctx, const padne_csr *w, int k, const float *e, float *x_out, const int32_t *done_flag,
-                        const float *x_pre, const float *r_pre, const float *dinv32, float scale);
 int interleave(padne_ctx *ctx, long long n, int k, const double *src, double *dst, bool to_interleaved);
 
 // exclusive scan of int32 counts into int32 offsets (n+1 outputs); returns total via host

@@ -639,9 +639,10 @@ static int halo_product_dot(padne_ctx *ctx, const padne_csr *a, double *v, doubl
     plan.export_idx = ctx->halo_export;
     HaloTicket tk;
     PADNE_TRY(halo_send(ctx, plan, v, done_flag, &tk));
-    PADNE_TRY(launch_spmv_part(ctx, a, SPMV_DOT, SPMV_INTERIOR, v, q, v, partials, done_flag, nullptr, nullptr, 0.0));
+    const ProductArgs<double> dot{.dot_with = v, .partials = partials, .done_flag = done_flag};
+    PADNE_TRY(launch_spmv<double, double>(ctx, a, SPMV_DOT, v, q, dot, SPMV_INTERIOR));
     PADNE_TRY(halo_recv(ctx, plan, v, done_flag, tk));
-    return launch_spmv_part(ctx, a, SPMV_DOT, SPMV_BOUNDARY, v, q, v, partials, done_flag, nullptr, nullptr, 0.0);
+    return launch_spmv<double, double>(ctx, a, SPMV_DOT, v, q, dot, SPMV_BOUNDARY);
 }
 
 int amg_setup(padne_ctx *ctx, padne_csr *A0);
@@ -838,7 +839,9 @@ static int solve_one(padne_ctx *ctx, const padne_csr *a, const padne_csr *prec, 
                     PADNE_HIP_CHECK(hipEventRecord(e0, s));
                 }
                 if (hist != nullptr) p32 = p_place(jq);
-                if (p32 != nullptr) PADNE_TRY(launch_spmv_dot_x32(ctx, a, p32, q, slot(ctx, SLOT_PQ), &st->done));
+                if (p32 != nullptr)
+                    PADNE_TRY(launch_spmv<double, double, float>(ctx, a, SPMV_DOT, p32, q,
+                                                                 {.partials = slot(ctx, SLOT_PQ), .done_flag = &st->done}));
                 else PADNE_TRY(halo_product_dot(ctx, a, p, q, slot(ctx, SLOT_PQ), &st->done));
                 if (sampled) PADNE_HIP_CHECK(hipEventRecord(ev_b.back(), s));
                 if (dist) {
@@ -1535,7 +1538,7 @@ static int solve_batch(padne_ctx *ctx, const padne_csr *a, const double *b_cols,
     bool have_ax = false;
     if (x_is_guess) {
         PADNE_TRY(interleave(ctx, n, K, x_cols, x8, true));
-        PADNE_TRY(launch_spmm_mode(ctx, a, K, SPMV_PLAIN, x8, q8, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0));
+        PADNE_TRY(launch_spmm<double, double>(ctx, a, K, SPMV_PLAIN, x8, q8, {}));
         have_ax = true;
     } else {
         PADNE_HIP_CHECK(hipMemsetAsync(x8, 0, sizeof(double) * nv, s));
@@ -1579,7 +1582,8 @@ static int solve_batch(padne_ctx *ctx, const padne_csr *a, const double *b_cols,
                 double *rz_old = scal + (parity ? C_RZ1 : C_RZ0), *rz_new = scal + (parity ? C_RZ0 : C_RZ1);
                 const int rz_new_slot = parity ? P_RZ0 : P_RZ1;
                 if (hat) {
-                    PADNE_TRY(launch_spmm_mode(ctx, a, K, SPMV_DOT, p8, q8, p8, pslot(P_PQ), &st->done, nullptr, nullptr, 0.0));
+                    PADNE_TRY(launch_spmm<double, double>(ctx, a, K, SPMV_DOT, p8, q8,
+                                                          {.dot_with = p8, .partials = pslot(P_PQ), .done_flag = &st->done}));
                     PADNE_TRY(fold(pslot(P_PQ), gs, scal + C_PQ));
                     hipLaunchKernelGGL(pcg8_update_r_entry_kernel<K>, dim3(gv), dim3(256), 0, s, n, rz_old, scal + C_PQ, q8, r8,
                                        pslot(P_RR), st, unit2, e_jac, e_dinv32, e_b8, e_xa8);
@@ -1591,7 +1595,8 @@ static int solve_batch(padne_ctx *ctx, const padne_csr *a, const double *b_cols,
                                        scal + C_PQ, unit2, (const float *)z32, p8, x8, st, max_iter - total_iters);
                     PADNE_HIP_CHECK(hipGetLastError());
                 } else {
-                    PADNE_TRY(launch_spmm_mode(ctx, a, K, SPMV_DOT, p8, q8, p8, pslot(P_PQ), &st->done, nullptr, nullptr, 0.0));
+                    PADNE_TRY(launch_spmm<double, double>(ctx, a, K, SPMV_DOT, p8, q8,
+                                                          {.dot_with = p8, .partials = pslot(P_PQ), .done_flag = &st->done}));
                     PADNE_TRY(fold(pslot(P_PQ), gs, scal + C_PQ));
                     hipLaunchKernelGGL(pcg8_update_xr_kernel<K>, dim3(gv), dim3(256), 0, s, n, rz_old, scal + C_PQ, p8, q8, x8, r8,
                                        pslot(P_RR), st, (const double *)(scal + C_BB), e_jac, e_dinv32, e_b8, e_xa8);
@@ -1617,7 +1622,7 @@ static int solve_batch(padne_ctx *ctx, const padne_csr *a, const double *b_cols,
             col_iters[c] += hst->col_iters[c];
         }
         // true residuals
-        PADNE_TRY(launch_spmm_mode(ctx, a, K, SPMV_PLAIN, x8, q8, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0));
+        PADNE_TRY(launch_spmm<double, double>(ctx, a, K, SPMV_PLAIN, x8, q8, {}));
         hipLaunchKernelGGL(residual8_kernel<K>, dim3(gv), dim3(256), 0, s, n, b8, q8, pslot(P_TMP));
         PADNE_HIP_CHECK(hipGetLastError());
         PADNE_TRY(fold(pslot(P_TMP), gv, scal + C_TRUE));
@@ -1781,7 +1786,7 @@ int lanczos_enqueue(padne_ctx *ctx, const padne_csr *a, int steps, LanczosJob *j
         double *rz_old_part = slot(ctx, parity ? SLOT_RZ1 : SLOT_RZ0);
         double *rz_new_part = slot(ctx, parity ? SLOT_RZ0 : SLOT_RZ1);
         if (dist) PADNE_TRY(halo_exchange_plan(ctx, *plan, p, nullptr));
-        PADNE_TRY(launch_spmv_mode(ctx, a, SPMV_DOT_AUX, p, q, p, slot(ctx, SLOT_PQ), nullptr, nullptr, nullptr, 0.0));
+        PADNE_TRY(launch_spmv<double, double>(ctx, a, SPMV_DOT_AUX, p, q, {.dot_with = p, .partials = slot(ctx, SLOT_PQ)}));
         if (dist) {
             PADNE_TRY(fold(slot(ctx, SLOT_PQ), gs, H_pq + k));
             PADNE_TRY(comm_allreduce_sum_f64(ctx, H_pq + k, 1));

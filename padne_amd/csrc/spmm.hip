@@ -236,21 +236,21 @@ __global__ __launch_bounds__(kSpmvThreads) void csr_spmm_kernel(
     }
 }
 
-template <int K, typename VT, typename XT, typename YT>
-static int launch_spmm_typed(padne_ctx *ctx, const padne_csr *m, const VT *vals, int mode, const XT *x, YT *y,
-                             const double *dot_with, double *partials, const int32_t *done_flag, const XT *aux1,
-                             const XT *aux2, XT scale, const double *out_scale2, const XT *aux0 = nullptr,
-                             const XT *rhs = nullptr) {
-    if (m->n_rows == 0) return PADNE_OK;
-    const int n_tiles = (int)((m->n_rows + 63) / 64);
+int spmm8_grid(const padne_csr *m) {
     long long g = (m->n_rows + kSpmvRows - 1) / kSpmvRows;
     if (g > kMaxPartials) g = kMaxPartials;
     if (g >= kNumXcd) g -= g % kNumXcd;
-    if (g < 1) g = 1;
-#define PADNE_SPMM_LAUNCH(M)                                                                                      \
-    hipLaunchKernelGGL((csr_spmm_kernel<K, M, VT, XT, YT>), dim3((unsigned)g), dim3(kSpmvThreads), 0, ctx->stream, \
-                       (int)m->n_rows, n_tiles, m->rowptr, m->cols, vals, x, y, dot_with, partials, done_flag,     \
-                       aux1, aux2, scale, out_scale2, aux0, rhs)
+    return (int)(g < 1 ? 1 : g);
+}
+
+template <int K, typename XT, typename YT>
+static int spmm_launch(padne_ctx *ctx, const padne_csr *m, const XT *vals, int mode, const XT *x, YT *y, const ProductArgs<XT> &a) {
+    if (m->n_rows == 0) return PADNE_OK;
+    const int n_tiles = (int)((m->n_rows + 63) / 64);
+#define PADNE_SPMM_LAUNCH(M)                                                                                          \
+    hipLaunchKernelGGL((csr_spmm_kernel<K, M, XT, XT, YT>), dim3((unsigned)spmm8_grid(m)), dim3(kSpmvThreads), 0, ctx->stream, \
+                       (int)m->n_rows, n_tiles, m->rowptr, m->cols, vals, x, y, a.dot_with, a.partials, a.done_flag, a.b,   \
+                       a.dinv, a.scale, a.out_scale2, a.x_pre, a.rhs)
     switch (mode) {
         case SPMV_PLAIN: PADNE_SPMM_LAUNCH(SPMV_PLAIN); break;
         case SPMV_DOT: PADNE_SPMM_LAUNCH(SPMV_DOT); break;
@@ -265,90 +265,27 @@ static int launch_spmm_typed(padne_ctx *ctx, const padne_csr *m, const VT *vals,
     return PADNE_OK;
 }
 
-int spmm8_grid(const padne_csr *m) {
-    long long g = (m->n_rows + kSpmvRows - 1) / kSpmvRows;
-    if (g > kMaxPartials) g = kMaxPartials;
-    if (g >= kNumXcd) g -= g % kNumXcd;
-    return (int)(g < 1 ? 1 : g);
-}
-
-// the width is a run-time choice of the caller (8 for config C5 and groups of regulators, 4 / 2 for one to three)
-#define PADNE_SPMM_WIDTH(k, CALL8, CALL4, CALL2)                       \
-    switch (k) {                                                       \
-        case 8: return CALL8;                                          \
-        case 4: return CALL4;                                          \
-        case 2: return CALL2;                                          \
-        default: set_error("lockstep width %d", k); return PADNE_E_INVALID; \
+template <typename XT, typename YT>
+int launch_spmm(padne_ctx *ctx, const padne_csr *m, int k, int mode, const XT *x, YT *y, const ProductArgs<XT> &a) {
+    const XT *vals = product_vals<XT>(m);
+    PADNE_REQUIRE(vals != nullptr, sizeof(XT) == 4 ? "single-precision copy missing" : "no double-precision values");
+    PADNE_REQUIRE(mode != SPMV_WUP || a.x_pre != nullptr || a.rhs != nullptr, "W stage");
+    // the exit stage of the lockstep cycle takes its r.z partials against dot_with, or, formed from the fine level's
+    // right-hand side, against that
+    const bool exit_stage = sizeof(YT) != sizeof(XT) || a.out_scale2 != nullptr || a.rhs != nullptr;
+    PADNE_REQUIRE(!exit_stage || a.dot_with != nullptr || (mode == SPMV_WUP && a.rhs != nullptr), "single-precision exit stage");
+    // the width is a run-time choice of the caller (8 for config C5 and groups of regulators, 4 / 2 for one to three)
+    switch (k) {
+        case 8: return spmm_launch<8, XT, YT>(ctx, m, vals, mode, x, y, a);
+        case 4: return spmm_launch<4, XT, YT>(ctx, m, vals, mode, x, y, a);
+        case 2: return spmm_launch<2, XT, YT>(ctx, m, vals, mode, x, y, a);
+        default: set_error("lockstep width %d", k); return PADNE_E_INVALID;
     }
-
-int launch_spmm_mode(padne_ctx *ctx, const padne_csr *m, int k, int mode, const double *x, double *y, const double *dot_with,
-                     double *partials, const int32_t *done_flag, const double *aux1, const double *aux2, double scale) {
-#define ARGS ctx, m, m->vals, mode, x, y, dot_with, partials, done_flag, aux1, aux2, scale, nullptr
-    PADNE_SPMM_WIDTH(k, (launch_spmm_typed<8, double, double, double>(ARGS)), (launch_spmm_typed<4, double, double, double>(ARGS)),
-                     (launch_spmm_typed<2, double, double, double>(ARGS)))
-#undef ARGS
 }
-
-int launch_spmm_f32(padne_ctx *ctx, const padne_csr *m, int k, int mode, const float *x, float *y, double *partials,
-                    const int32_t *done_flag, const float *aux1, const float *aux2, float scale) {
-    PADNE_REQUIRE(m->vals32 != nullptr, "single-precision copy missing");
-#define ARGS ctx, m, m->vals32, mode, x, y, nullptr, partials, done_flag, aux1, aux2, scale, nullptr
-    PADNE_SPMM_WIDTH(k, (launch_spmm_typed<8, float, float, float>(ARGS)), (launch_spmm_typed<4, float, float, float>(ARGS)),
-                     (launch_spmm_typed<2, float, float, float>(ARGS)))
-#undef ARGS
-}
-
-// (y32 instead of y: z leaves in single precision and without its factor, the r.z partials are those of the double)
-int launch_spmm_f32_exit(padne_ctx *ctx, const padne_csr *m, int k, const float *x, double *y, const double *dot_with,
-                         double *partials, const int32_t *done_flag, const float *aux1, const float *aux2,
-                         float scale, const double *out_scale2, float *y32) {
-    PADNE_REQUIRE(m->vals32 != nullptr && dot_with != nullptr, "single-precision exit stage");
-    if (y32 != nullptr) {
-#define ARGS ctx, m, m->vals32, SPMV_JACOBI, x, y32, dot_with, partials, done_flag, aux1, aux2, scale, out_scale2
-        PADNE_SPMM_WIDTH(k, (launch_spmm_typed<8, float, float, float>(ARGS)), (launch_spmm_typed<4, float, float, float>(ARGS)),
-                         (launch_spmm_typed<2, float, float, float>(ARGS)))
-#undef ARGS
-    }
-#define ARGS ctx, m, m->vals32, SPMV_JACOBI, x, y, dot_with, partials, done_flag, aux1, aux2, scale, out_scale2
-    PADNE_SPMM_WIDTH(k, (launch_spmm_typed<8, float, float, double>(ARGS)), (launch_spmm_typed<4, float, float, double>(ARGS)),
-                     (launch_spmm_typed<2, float, float, double>(ARGS)))
-#undef ARGS
-}
-
-// last stage of the lockstep cycle in the W form: z = (x_pre + c D^-1 r_pre + W e) * sqrt(out_scale2[j]) in double, with the
-// partial sums of dot_with . z per right-hand side (the lockstep counterpart of launch_spmv_f32_wup_exit)
-int launch_spmm_f32_wup_exit(padne_ctx *ctx, const padne_csr *w, int k, const float *e, double *z, const double *dot_with,
-                             double *partials, const int32_t *done_flag, const float *x_pre, const float *r_pre,
-                             const float *dinv32, float scale, const double *out_scale2, float *z32, const float *rhs) {
-    PADNE_REQUIRE(w->vals32 != nullptr && (dot_with != nullptr || rhs != nullptr) && (x_pre != nullptr || rhs != nullptr),
-                  "single-precision W stage");
-    if (z32 != nullptr) {
-#define ARGS ctx, w, w->vals32, SPMV_WUP, e, z32, dot_with, partials, done_flag, r_pre, dinv32, scale, out_scale2, x_pre, rhs
-        PADNE_SPMM_WIDTH(k, (launch_spmm_typed<8, float, float, float>(ARGS)), (launch_spmm_typed<4, float, float, float>(ARGS)),
-                         (launch_spmm_typed<2, float, float, float>(ARGS)))
-#undef ARGS
-    }
-#define ARGS ctx, w, w->vals32, SPMV_WUP, e, z, dot_with, partials, done_flag, r_pre, dinv32, scale, out_scale2, x_pre, rhs
-    PADNE_SPMM_WIDTH(k, (launch_spmm_typed<8, float, float, double>(ARGS)), (launch_spmm_typed<4, float, float, double>(ARGS)),
-                     (launch_spmm_typed<2, float, float, double>(ARGS)))
-#undef ARGS
-}
-
-// up-leg of an inner level in the W form: x = x_pre + c D^-1 r_pre + W e, single precision throughout
-int launch_spmm_f32_wup(padne_ctx *ctx, const padne_csr *w, int k, const float *e, float *x_out, const int32_t *done_flag,
-                        const float *x_pre, const float *r_pre, const float *dinv32, float scale) {
-    PADNE_REQUIRE(w->vals32 != nullptr, "single-precision W stage");
-#define ARGS ctx, w, w->vals32, SPMV_WUP, e, x_out, nullptr, nullptr, done_flag, r_pre, dinv32, scale, nullptr, x_pre
-    PADNE_SPMM_WIDTH(k, (launch_spmm_typed<8, float, float, float>(ARGS)), (launch_spmm_typed<4, float, float, float>(ARGS)),
-                     (launch_spmm_typed<2, float, float, float>(ARGS)))
-#undef ARGS
-}
-
-int launch_spmm8_mode(padne_ctx *ctx, const padne_csr *m, int mode, const double *x, double *y, const double *dot_with,
-                      double *partials, const int32_t *done_flag, const double *aux1, const double *aux2,
-                      double scale) {
-    return launch_spmm_mode(ctx, m, kSpmmK, mode, x, y, dot_with, partials, done_flag, aux1, aux2, scale);
-}
+// double (the lockstep CG loop), the single-precision cycle and its exit stage with z in double
+template int launch_spmm(padne_ctx *, const padne_csr *, int, int, const double *, double *, const ProductArgs<double> &);
+template int launch_spmm(padne_ctx *, const padne_csr *, int, int, const float *, float *, const ProductArgs<float> &);
+template int launch_spmm(padne_ctx *, const padne_csr *, int, int, const float *, double *, const ProductArgs<float> &);
 
 // [k][n] (one vector after the other) <-> [n][k] (interleaved)
 __global__ void interleave_kernel(long long n, int k, const double *__restrict__ src, double *__restrict__ dst, int to_interleaved) {
@@ -378,8 +315,7 @@ extern "C" int padne_spmm8_dev(padne_ctx *ctx, const padne_csr *m, const void *x
     PADNE_REQUIRE(repeat >= 1, "repeat");
     PADNE_HIP_CHECK(hipSetDevice(ctx->device));
     for (int i = 0; i < repeat; ++i)
-        PADNE_TRY(launch_spmm8_mode(ctx, m, SPMV_PLAIN, (const double *)x_dev, (double *)y_dev, nullptr, nullptr, nullptr,
-                                    nullptr, nullptr, 0.0));
+        PADNE_TRY(launch_spmm<double, double>(ctx, m, kSpmmK, SPMV_PLAIN, (const double *)x_dev, (double *)y_dev, {}));
     PADNE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return PADNE_OK;
 }
@@ -390,12 +326,10 @@ extern "C" int padne_spmm8_time(padne_ctx *ctx, const padne_csr *m, const void *
     PADNE_REQUIRE(repeat >= 1 && warmup >= 0, "repeat / warmup");
     PADNE_HIP_CHECK(hipSetDevice(ctx->device));
     for (int i = 0; i < warmup; ++i)
-        PADNE_TRY(launch_spmm8_mode(ctx, m, SPMV_PLAIN, (const double *)x_dev, (double *)y_dev, nullptr, nullptr, nullptr,
-                                    nullptr, nullptr, 0.0));
+        PADNE_TRY(launch_spmm<double, double>(ctx, m, kSpmmK, SPMV_PLAIN, (const double *)x_dev, (double *)y_dev, {}));
     PADNE_HIP_CHECK(hipEventRecord(ctx->ev0, ctx->stream));
     for (int i = 0; i < repeat; ++i)
-        PADNE_TRY(launch_spmm8_mode(ctx, m, SPMV_PLAIN, (const double *)x_dev, (double *)y_dev, nullptr, nullptr, nullptr,
-                                    nullptr, nullptr, 0.0));
+        PADNE_TRY(launch_spmm<double, double>(ctx, m, kSpmmK, SPMV_PLAIN, (const double *)x_dev, (double *)y_dev, {}));
     PADNE_HIP_CHECK(hipEventRecord(ctx->ev1, ctx->stream));
     PADNE_HIP_CHECK(hipEventSynchronize(ctx->ev1));
     float ms = 0.f;

@@ -257,19 +257,20 @@ __device__ __forceinline__ void stage_windows_wide(const XT *__restrict__ x, con
     }
 }
 
-// Epilogues (acc = (A x)[row]):
+// Epilogues (acc = (A x)[row]), the operands by their roles (ProductArgs, common.hpp); the kernels take b as aux1, dinv as aux2
+// and x_pre as aux0, and launch_spmv hands the read-only rhs of the W exit stage to y2:
 //   SPMV_PLAIN   y = acc
 //   SPMV_DOT     y = acc ; partial sums of dot_with[row] * acc
-//   SPMV_RESID   y = aux1[row] - acc                                   (residual b - A x)
+//   SPMV_RESID   y = b[row] - acc                                      (residual b - A x)
 //   SPMV_ADD     y += acc                                              (prolongation: x += P xc)
-//   SPMV_JACOBI  y = x[row] + scale * aux2[row] * (aux1[row] - acc)    (damped-Jacobi sweep, aux2 = 1/diag)
-//                optional partial sums of aux1[row] * y[row]           (r.z of the preconditioned CG)
-//   SPMV_RESTRICT y = acc ; y2 = scale * aux2[row] * acc                 (restriction, and the first damped-Jacobi sweep of
-//                the level it restricts to from a zero start: aux2 = that level's 1/diag)
-//   SPMV_WUP     y = aux0[row] + scale * aux2[row] * aux1[row] + acc   (coarse correction and post-smoothing in one
-//                product with W = P - c D^-1 A P, see amg.hip: aux0 = pre-smoothed iterate, aux1 = its residual)
+//   SPMV_JACOBI  y = x[row] + scale * dinv[row] * (b[row] - acc)       (damped-Jacobi sweep, dinv = 1/diag)
+//                optional partial sums of b[row] * y[row]              (r.z of the preconditioned CG)
+//   SPMV_RESTRICT y = acc ; y2 = scale * dinv[row] * acc               (restriction, and the first damped-Jacobi sweep of
+//                the level it restricts to from a zero start: dinv = that level's 1/diag)
+//   SPMV_WUP     y = x_pre[row] + scale * dinv[row] * b[row] + acc     (coarse correction and post-smoothing in one
+//                product with W = P - c D^-1 A P, see amg.hip: x_pre = pre-smoothed iterate, b = its residual)
 //
-// Scalar types: VT matrix values, XT the vectors x / aux1 / aux2 and the arithmetic, YT the output.  The solver's
+// Scalar types: VT matrix values, XT the vectors x / b / dinv and the arithmetic, YT the output.  The solver's
 // own products are <double, double, double>; the multigrid cycle runs <float, float, float> (single-precision
 // copies of its operators: 8 instead of 12 bytes per non-zero, half the vector traffic), and its last stage
 // <float, float, double> hands z back to CG in double, multiplied by sqrt(*out_scale2) (the cycle works on
@@ -546,20 +547,25 @@ int spmv_partials(const padne_csr *m) {
     return split_grid(m, m->split_n_int) + (m->split_n_bnd > 0 ? split_grid(m, m->split_n_bnd) : 0);
 }
 
-int spmv_kernel_form(const padne_csr *m, int mode, int x_bytes, int y_bytes, bool with_dot, bool with_partials, int part) {
+// The kernel a product runs on `m`: none (nothing to do), a wave per row, the list of interior / boundary tiles, the 16-per-lane
+// gather form, the wide x-window plan, the tile kernel (gather and / or x windows).  The ONE place the choice is made: launch_spmv
+// asks it with its own arguments, and so does the kernel probe at the end of this file.
+enum { SPMV_FORM_NONE = 0, SPMV_FORM_WPR = 1, SPMV_FORM_LIST = 2, SPMV_FORM_LONG = 3, SPMV_FORM_WIDE = 4, SPMV_FORM_TILE = 5 };
+template <typename XT, typename YT>
+static int spmv_kernel_form(const padne_csr *m, int mode, const ProductArgs<XT> &a, int part) {
     if (m->n_rows == 0) return SPMV_FORM_NONE;
     if (split_in_use(m)) {
         // (a product with partial sums over the whole split operator is the interior launch and the boundary launch)
         if (part == SPMV_BOUNDARY && m->split_n_bnd == 0) return SPMV_FORM_NONE;
-        if (part == SPMV_INTERIOR || part == SPMV_BOUNDARY || (part == SPMV_ALL && with_partials)) return SPMV_FORM_LIST;
+        if (part == SPMV_INTERIOR || part == SPMV_BOUNDARY || (part == SPMV_ALL && a.partials != nullptr)) return SPMV_FORM_LIST;
     } else if (part == SPMV_INTERIOR) {
         return SPMV_FORM_NONE;                           // no split plan: the whole product follows the exchange
     }
-    if (use_wave_per_row(m) && !(mode == SPMV_WUP && with_dot)) return SPMV_FORM_WPR;
+    if (use_wave_per_row(m) && !(mode == SPMV_WUP && a.dot_with != nullptr)) return SPMV_FORM_WPR;
     // single-precision operators of the cycle with long rows, no x windows and few tiles per wave (the levels below the
     // first coarse one: 139 k rows at C4): the 16-per-lane form of the gather path, -11 us per cycle there.  On the million-row
     // operators (the fine restriction, the first coarse level) it loses 2-5 us each: the shorter form stays
-    const bool long_rows = x_bytes == 4 && y_bytes == 4 && m->xw_state != 1 && m->n_rows < 500000 &&
+    const bool long_rows = sizeof(XT) == 4 && sizeof(YT) == 4 && m->xw_state != 1 && m->n_rows < 500000 &&
                            m->nnz > 8 * m->n_rows + 4 * (m->n_rows >> 3);
     if (long_rows && (mode == SPMV_PLAIN || mode == SPMV_RESID || mode == SPMV_ADD || mode == SPMV_JACOBI || mode == SPMV_RESTRICT))
         return SPMV_FORM_LONG;
@@ -568,27 +574,12 @@ int spmv_kernel_form(const padne_csr *m, int mode, int x_bytes, int y_bytes, boo
     return SPMV_FORM_TILE;
 }
 
-template <typename VT, typename XT, typename YT>
-static int launch_spmv_typed(padne_ctx *ctx, const padne_csr *m, const VT *vals, int mode, const XT *x, YT *y,
-                             const double *dot_with, double *partials, const int32_t *done_flag, const XT *aux1,
-                             const XT *aux2, XT scale, const double *out_scale2, const XT *aux0 = nullptr, XT *y2 = nullptr,
-                             int part = SPMV_ALL) {
-    if (m->n_rows == 0) return PADNE_OK;
+// One launch on the tiles of `part` (-1: all tiles of a split operator in one sweep).
+template <typename XT, typename YT, typename ST>
+static int spmv_launch(padne_ctx *ctx, const padne_csr *m, const XT *vals, int mode, const ST *x, YT *y, const ProductArgs<XT> &a,
+                       int part) {
     const int n_tiles = (int)((m->n_rows + 63) / 64);   // wave-tiles of 64 rows
-    if (!split_in_use(m)) {
-        if (part == SPMV_INTERIOR) return PADNE_OK;      // no split plan: the whole product follows the exchange
-        part = SPMV_ALL;
-    } else if (part == SPMV_ALL && partials == nullptr) {
-        part = -1;                                       // one sweep over all tiles: nobody counts partial sums
-    }
-    if (part == SPMV_ALL && split_in_use(m)) {
-        // a product with partial sums on a split operator always leaves them in the layout of the two launches
-        PADNE_TRY((launch_spmv_typed<VT, XT, YT>(ctx, m, vals, mode, x, y, dot_with, partials, done_flag, aux1, aux2, scale,
-                                                 out_scale2, aux0, y2, SPMV_INTERIOR)));
-        return launch_spmv_typed<VT, XT, YT>(ctx, m, vals, mode, x, y, dot_with, partials, done_flag, aux1, aux2, scale,
-                                             out_scale2, aux0, y2, SPMV_BOUNDARY);
-    }
-    const int form = spmv_kernel_form(m, mode, (int)sizeof(XT), (int)sizeof(YT), dot_with != nullptr, partials != nullptr, part);
+    const int form = spmv_kernel_form<XT, YT>(m, mode, a, part);
     int g = spmv_grid(m);
     const int *tile_list = nullptr;
     int n_list = 0, partial_off = 0;
@@ -603,11 +594,32 @@ static int launch_spmv_typed(padne_ctx *ctx, const padne_csr *m, const VT *vals,
         partial_off = split_grid(m, m->split_n_int);
         g = split_grid(m, n_list);
     }
-    if (form == SPMV_FORM_WPR) {
-#define PADNE_SPMV_WPR(M)                                                                                           \
-    hipLaunchKernelGGL((csr_spmv_wpr_kernel<M, VT, XT, YT>), dim3(g), dim3(kSpmvThreads), 0, ctx->stream,            \
-                       (int)m->n_rows, m->rowptr, m->cols, vals, x, y, dot_with, partials, done_flag, aux1, aux2,    \
-                       scale, out_scale2, y2, aux0)
+    // The kernels' y2 is RESTRICT's second output and, in the W product, the fine level's right-hand side, which they only
+    // read: the one place `rhs` is handed to that slot.
+    XT *y2 = mode == SPMV_WUP ? (XT *)a.rhs : a.y2;
+    const bool wide = m->xw_state == 1 && m->xw_nruns == kXwRunsWide;
+    const size_t xs_bytes = m->xw_state == 1 ? sizeof(ST) * 4 * (wide ? (size_t)kXwRunsWide * kXwRunWide : kXwRuns * (size_t)m->xw_run) : 0;
+    const int4 *xw_desc = m->xw_state == 1 ? m->xw_desc : nullptr;
+    const void *xw_lidx = m->xw_state == 1 ? (const void *)m->xw_lidx : nullptr;
+#define PADNE_SPMV_ARGS                                                                                                  \
+    (int)m->n_rows, (int)m->n_cols, n_tiles, m->rowptr, m->cols, vals, x, y, a.dot_with, a.partials, a.done_flag, a.b, a.dinv, \
+        a.scale, a.out_scale2, xw_desc, xw_lidx, m->xw_run, a.x_pre, y2, tile_list, n_list, partial_off
+#define PADNE_SPMV_WPR(M)                                                                                                \
+    hipLaunchKernelGGL((csr_spmv_wpr_kernel<M, XT, XT, YT>), dim3(g), dim3(kSpmvThreads), 0, ctx->stream, (int)m->n_rows,  \
+                       m->rowptr, m->cols, vals, x, y, a.dot_with, a.partials, a.done_flag, a.b, a.dinv, a.scale, a.out_scale2, \
+                       y2, a.x_pre)
+#define PADNE_SPMV_LAUNCH(M)                                                                                             \
+    hipLaunchKernelGGL((csr_spmv_kernel<M, XT, XT, YT, false>), dim3(g), dim3(kSpmvThreads), xs_bytes, ctx->stream, PADNE_SPMV_ARGS)
+#define PADNE_SPMV_LAUNCH_LONG(M)                                                                                        \
+    hipLaunchKernelGGL((csr_spmv_kernel<M, XT, XT, YT, false, sizeof(XT) == 4 && sizeof(YT) == 4>), dim3(g), dim3(kSpmvThreads), \
+                       xs_bytes, ctx->stream, PADNE_SPMV_ARGS)
+#define PADNE_SPMV_LAUNCH_LIST(M)                                                                                        \
+    hipLaunchKernelGGL((csr_spmv_kernel<M, XT, XT, YT, true>), dim3(g), dim3(kSpmvThreads), xs_bytes, ctx->stream, PADNE_SPMV_ARGS)
+    if constexpr (sizeof(ST) != sizeof(XT)) {
+        // q = A p with p stored in single precision: the plain tile kernel only (spmv_x32_ok), no other kernel instantiated
+        hipLaunchKernelGGL((csr_spmv_kernel<SPMV_DOT, XT, XT, YT, false, false, false, ST>), dim3(g), dim3(kSpmvThreads), xs_bytes,
+                           ctx->stream, PADNE_SPMV_ARGS);
+    } else if (form == SPMV_FORM_WPR) {
         switch (mode) {
             case SPMV_PLAIN: PADNE_SPMV_WPR(SPMV_PLAIN); break;
             case SPMV_DOT: PADNE_SPMV_WPR(SPMV_DOT); break;
@@ -619,24 +631,7 @@ static int launch_spmv_typed(padne_ctx *ctx, const padne_csr *m, const VT *vals,
             case SPMV_WUP: PADNE_SPMV_WPR(SPMV_WUP); break;
             default: set_error("bad SpMV mode %d", mode); return PADNE_E_INVALID;
         }
-#undef PADNE_SPMV_WPR
-        PADNE_HIP_CHECK(hipGetLastError());
-        return PADNE_OK;
-    }
-    const bool wide = m->xw_state == 1 && m->xw_nruns == kXwRunsWide;
-    const size_t xs_bytes = m->xw_state == 1 ? sizeof(XT) * 4 * (wide ? (size_t)kXwRunsWide * kXwRunWide : kXwRuns * (size_t)m->xw_run) : 0;
-    const int4 *xw_desc = m->xw_state == 1 ? m->xw_desc : nullptr;
-    const void *xw_lidx = m->xw_state == 1 ? (const void *)m->xw_lidx : nullptr;
-#define PADNE_SPMV_ARGS                                                                                          \
-    (int)m->n_rows, (int)m->n_cols, n_tiles, m->rowptr, m->cols, vals, x, y, dot_with, partials, done_flag, aux1, aux2, \
-        scale, out_scale2, xw_desc, xw_lidx, m->xw_run, aux0, y2, tile_list, n_list, partial_off
-#define PADNE_SPMV_LAUNCH(M)                                                                                     \
-    hipLaunchKernelGGL((csr_spmv_kernel<M, VT, XT, YT, false>), dim3(g), dim3(kSpmvThreads), xs_bytes, ctx->stream, PADNE_SPMV_ARGS)
-#define PADNE_SPMV_LAUNCH_LONG(M)                                                                                \
-    hipLaunchKernelGGL((csr_spmv_kernel<M, VT, XT, YT, false, sizeof(XT) == 4 && sizeof(YT) == 4>), dim3(g), dim3(kSpmvThreads), xs_bytes, ctx->stream, PADNE_SPMV_ARGS)
-#define PADNE_SPMV_LAUNCH_LIST(M)                                                                                \
-    hipLaunchKernelGGL((csr_spmv_kernel<M, VT, XT, YT, true>), dim3(g), dim3(kSpmvThreads), xs_bytes, ctx->stream, PADNE_SPMV_ARGS)
-    if (form == SPMV_FORM_LIST) {
+    } else if (form == SPMV_FORM_LIST) {
         // the products that follow a halo exchange: q = A p of the CG loop, the Lanczos steps, residual and smoothing of the cycle
         switch (mode) {
             case SPMV_PLAIN: PADNE_SPMV_LAUNCH_LIST(SPMV_PLAIN); break;
@@ -646,10 +641,7 @@ static int launch_spmv_typed(padne_ctx *ctx, const padne_csr *m, const VT *vals,
             case SPMV_JACOBI: PADNE_SPMV_LAUNCH_LIST(SPMV_JACOBI); break;
             default: set_error("SpMV mode %d has no interior / boundary form", mode); return PADNE_E_INVALID;
         }
-        PADNE_HIP_CHECK(hipGetLastError());
-        return PADNE_OK;
-    }
-    if (form == SPMV_FORM_LONG) {
+    } else if (form == SPMV_FORM_LONG) {
         switch (mode) {
             case SPMV_PLAIN: PADNE_SPMV_LAUNCH_LONG(SPMV_PLAIN); break;
             case SPMV_RESID: PADNE_SPMV_LAUNCH_LONG(SPMV_RESID); break;
@@ -657,32 +649,29 @@ static int launch_spmv_typed(padne_ctx *ctx, const padne_csr *m, const VT *vals,
             case SPMV_JACOBI: PADNE_SPMV_LAUNCH_LONG(SPMV_JACOBI); break;
             default: PADNE_SPMV_LAUNCH_LONG(SPMV_RESTRICT); break;
         }
-        PADNE_HIP_CHECK(hipGetLastError());
-        return PADNE_OK;
-    }
-    if (form == SPMV_FORM_WIDE) {
-        PADNE_REQUIRE(mode == SPMV_WUP && sizeof(VT) == 4 && sizeof(XT) == 4, "the wide x-window plan serves the W product");
-        hipLaunchKernelGGL((csr_spmv_kernel<SPMV_WUP, VT, XT, YT, false, false, true>), dim3(g), dim3(kSpmvThreads), xs_bytes,
+    } else if (form == SPMV_FORM_WIDE) {
+        PADNE_REQUIRE(mode == SPMV_WUP && sizeof(XT) == 4, "the wide x-window plan serves the W product");
+        hipLaunchKernelGGL((csr_spmv_kernel<SPMV_WUP, XT, XT, YT, false, false, true>), dim3(g), dim3(kSpmvThreads), xs_bytes,
                            ctx->stream, PADNE_SPMV_ARGS);
-        PADNE_HIP_CHECK(hipGetLastError());
-        return PADNE_OK;
-    }
-    switch (mode) {
-        case SPMV_PLAIN: PADNE_SPMV_LAUNCH(SPMV_PLAIN); break;
-        case SPMV_DOT: PADNE_SPMV_LAUNCH(SPMV_DOT); break;
-        case SPMV_DOT_AUX: PADNE_SPMV_LAUNCH(SPMV_DOT_AUX); break;
-        case SPMV_RESID: PADNE_SPMV_LAUNCH(SPMV_RESID); break;
-        case SPMV_ADD: PADNE_SPMV_LAUNCH(SPMV_ADD); break;
-        case SPMV_JACOBI: PADNE_SPMV_LAUNCH(SPMV_JACOBI); break;
-        case SPMV_WUP: PADNE_SPMV_LAUNCH(SPMV_WUP); break;
-        case SPMV_RESTRICT: PADNE_SPMV_LAUNCH(SPMV_RESTRICT); break;
-        case SPMV_RESID_PRE: PADNE_SPMV_LAUNCH(SPMV_RESID_PRE); break;
-        default: set_error("bad SpMV mode %d", mode); return PADNE_E_INVALID;
+    } else {
+        switch (mode) {
+            case SPMV_PLAIN: PADNE_SPMV_LAUNCH(SPMV_PLAIN); break;
+            case SPMV_DOT: PADNE_SPMV_LAUNCH(SPMV_DOT); break;
+            case SPMV_DOT_AUX: PADNE_SPMV_LAUNCH(SPMV_DOT_AUX); break;
+            case SPMV_RESID: PADNE_SPMV_LAUNCH(SPMV_RESID); break;
+            case SPMV_ADD: PADNE_SPMV_LAUNCH(SPMV_ADD); break;
+            case SPMV_JACOBI: PADNE_SPMV_LAUNCH(SPMV_JACOBI); break;
+            case SPMV_WUP: PADNE_SPMV_LAUNCH(SPMV_WUP); break;
+            case SPMV_RESTRICT: PADNE_SPMV_LAUNCH(SPMV_RESTRICT); break;
+            case SPMV_RESID_PRE: PADNE_SPMV_LAUNCH(SPMV_RESID_PRE); break;
+            default: set_error("bad SpMV mode %d", mode); return PADNE_E_INVALID;
+        }
     }
 #undef PADNE_SPMV_LAUNCH_LONG
 #undef PADNE_SPMV_LAUNCH_LIST
-#undef PADNE_SPMV_ARGS
 #undef PADNE_SPMV_LAUNCH
+#undef PADNE_SPMV_WPR
+#undef PADNE_SPMV_ARGS
     PADNE_HIP_CHECK(hipGetLastError());
     return PADNE_OK;
 }
@@ -696,12 +685,6 @@ bool spmv_resid_pre_ok(const padne_csr *m) {
     return m->vals32 != nullptr && m->dinv32 != nullptr && !split_in_use(m) && !use_wave_per_row(m) && !long_rows &&
            !(m->xw_state == 1 && m->xw_nruns == kXwRunsWide);
 }
-int launch_spmv_f32_resid_pre(padne_ctx *ctx, const padne_csr *m, const float *b, float *resid, const int32_t *done_flag,
-                              const float *dinv32, float c) {
-    PADNE_REQUIRE(spmv_resid_pre_ok(m), "residual of the sweep from zero on this operator");
-    return launch_spmv_typed<float, float, float>(ctx, m, m->vals32, SPMV_RESID_PRE, b, resid, nullptr, nullptr, done_flag, nullptr,
-                                                  dinv32, c, nullptr);
-}
 
 // q = A p with p stored in single precision, p.q partials (one GPU, no split plan; same grid and partial layout as the
 // double form).  false from spmv_x32_ok: the caller keeps p in double.
@@ -709,104 +692,38 @@ bool spmv_x32_ok(const padne_csr *m) {
     return m->vals != nullptr && !split_in_use(m) && !use_wave_per_row(m) && !(m->xw_state == 1 && m->xw_nruns == kXwRunsWide) &&
            !(m->owner != nullptr && m->owner->opt.pcg_p64);
 }
-int launch_spmv_dot_x32(padne_ctx *ctx, const padne_csr *m, const float *x, double *y, double *partials, const int32_t *done_flag) {
-    PADNE_REQUIRE(spmv_x32_ok(m), "single-precision search direction on this operator");
+
+template <typename XT, typename YT, typename ST>
+int launch_spmv(padne_ctx *ctx, const padne_csr *m, int mode, const ST *x, YT *y, const ProductArgs<XT> &a, int part) {
+    const XT *vals = product_vals<XT>(m);
+    PADNE_REQUIRE(vals != nullptr, sizeof(XT) == 4 ? "single-precision copy missing" : "no double-precision values");
+    PADNE_REQUIRE(sizeof(ST) == sizeof(XT) || (mode == SPMV_DOT && spmv_x32_ok(m)), "single-precision search direction on this operator");
+    PADNE_REQUIRE(mode != SPMV_RESID_PRE || spmv_resid_pre_ok(m), "residual of the sweep from zero on this operator");
+    PADNE_REQUIRE(mode != SPMV_RESTRICT || (a.y2 != nullptr && a.dinv != nullptr), "restriction");
+    PADNE_REQUIRE(mode != SPMV_WUP || a.x_pre != nullptr || a.rhs != nullptr, "W stage");
+    // the exit stage of the single-precision cycle (z in double, or scaled by sqrt(*out_scale2), or the W product formed from
+    // the fine level's right-hand side) takes its r.z partials against dot_with
+    const bool exit_stage = sizeof(YT) != sizeof(XT) || a.out_scale2 != nullptr || a.rhs != nullptr;
+    PADNE_REQUIRE(!exit_stage || a.dot_with != nullptr, "single-precision exit stage");
     if (m->n_rows == 0) return PADNE_OK;
-    const int n_tiles = (int)((m->n_rows + 63) / 64);
-    const int g = spmv_grid(m);      // (= spmv_partials: the consumers of the p.q partials count on it)
-    const size_t xs_bytes = m->xw_state == 1 ? sizeof(float) * 4 * kXwRuns * (size_t)m->xw_run : 0;
-    const int4 *xw_desc = m->xw_state == 1 ? m->xw_desc : nullptr;
-    const void *xw_lidx = m->xw_state == 1 ? (const void *)m->xw_lidx : nullptr;
-    hipLaunchKernelGGL((csr_spmv_kernel<SPMV_DOT, double, double, double, false, false, false, float>), dim3(g), dim3(kSpmvThreads),
-                       xs_bytes, ctx->stream, (int)m->n_rows, (int)m->n_cols, n_tiles, m->rowptr, m->cols, m->vals, x, y,
-                       (const double *)nullptr, partials, done_flag, (const double *)nullptr, (const double *)nullptr, 0.0,
-                       (const double *)nullptr, xw_desc, xw_lidx, m->xw_run, (const double *)nullptr, (double *)nullptr,
-                       (const int *)nullptr, 0, 0);
-    PADNE_HIP_CHECK(hipGetLastError());
-    return PADNE_OK;
+    if (!split_in_use(m)) {
+        if (part == SPMV_INTERIOR) return PADNE_OK;      // no split plan: the whole product follows the exchange
+        part = SPMV_ALL;
+    } else if (part == SPMV_ALL) {
+        if (a.partials != nullptr) {
+            // a product with partial sums on a split operator always leaves them in the layout of the two launches
+            PADNE_TRY((spmv_launch<XT, YT, ST>(ctx, m, vals, mode, x, y, a, SPMV_INTERIOR)));
+            return spmv_launch<XT, YT, ST>(ctx, m, vals, mode, x, y, a, SPMV_BOUNDARY);
+        }
+        part = -1;                                       // one sweep over all tiles: nobody counts partial sums
+    }
+    return spmv_launch<XT, YT, ST>(ctx, m, vals, mode, x, y, a, part);
 }
-
-int launch_spmv_mode(padne_ctx *ctx, const padne_csr *m, int mode, const double *x, double *y,
-                     const double *dot_with, double *partials, const int32_t *done_flag, const double *aux1,
-                     const double *aux2, double scale) {
-    return launch_spmv_typed<double, double, double>(ctx, m, m->vals, mode, x, y, dot_with, partials, done_flag, aux1,
-                                                     aux2, scale, nullptr);
-}
-
-int launch_spmv_part(padne_ctx *ctx, const padne_csr *m, int mode, int part, const double *x, double *y, const double *dot_with,
-                     double *partials, const int32_t *done_flag, const double *aux1, const double *aux2, double scale) {
-    return launch_spmv_typed<double, double, double>(ctx, m, m->vals, mode, x, y, dot_with, partials, done_flag, aux1,
-                                                     aux2, scale, nullptr, nullptr, nullptr, part);
-}
-
-int launch_spmv_f32_part(padne_ctx *ctx, const padne_csr *m, int mode, int part, const float *x, float *y, double *partials,
-                         const int32_t *done_flag, const float *aux1, const float *aux2, float scale) {
-    PADNE_REQUIRE(m->vals32 != nullptr, "single-precision copy missing");
-    return launch_spmv_typed<float, float, float>(ctx, m, m->vals32, mode, x, y, nullptr, partials, done_flag, aux1,
-                                                  aux2, scale, nullptr, nullptr, nullptr, part);
-}
-
-int launch_spmv_f32_exit_part(padne_ctx *ctx, const padne_csr *m, int part, const float *x, double *y, const double *dot_with,
-                              double *partials, const int32_t *done_flag, const float *aux1, const float *aux2, float scale,
-                              const double *out_scale2, float *z32) {
-    PADNE_REQUIRE(m->vals32 != nullptr && dot_with != nullptr, "single-precision exit stage");
-    if (z32 != nullptr)
-        return launch_spmv_typed<float, float, float>(ctx, m, m->vals32, SPMV_JACOBI, x, z32, dot_with, partials, done_flag,
-                                                      aux1, aux2, scale, out_scale2, nullptr, nullptr, part);
-    return launch_spmv_typed<float, float, double>(ctx, m, m->vals32, SPMV_JACOBI, x, y, dot_with, partials, done_flag,
-                                                   aux1, aux2, scale, out_scale2, nullptr, nullptr, part);
-}
-
-// single-precision operator copy (csr_build_f32) on single-precision vectors
-int launch_spmv_f32(padne_ctx *ctx, const padne_csr *m, int mode, const float *x, float *y, double *partials,
-                    const int32_t *done_flag, const float *aux1, const float *aux2, float scale) {
-    PADNE_REQUIRE(m->vals32 != nullptr, "single-precision copy missing");
-    return launch_spmv_typed<float, float, float>(ctx, m, m->vals32, mode, x, y, nullptr, partials, done_flag, aux1,
-                                                  aux2, scale, nullptr);
-}
-
-// restriction b_c = R r and, in the same pass, the pre-smoothed start of the coarse level x_c = c D_c^-1 b_c
-int launch_spmv_f32_restrict(padne_ctx *ctx, const padne_csr *R, const float *r, float *b_c, float *x_c,
-                             const int32_t *done_flag, const float *dinv_c, float c) {
-    PADNE_REQUIRE(R->vals32 != nullptr && x_c != nullptr && dinv_c != nullptr, "single-precision restriction");
-    return launch_spmv_typed<float, float, float>(ctx, R, R->vals32, SPMV_RESTRICT, r, b_c, nullptr, nullptr, done_flag,
-                                                  nullptr, dinv_c, c, nullptr, nullptr, x_c);
-}
-
-// last stage of the single-precision cycle: damped-Jacobi sweep whose result goes out in double, multiplied by
-// sqrt(*out_scale2), with partial sums of dot_with . y
-// z32 != nullptr: the result goes there in single precision and UNSCALED instead (the dot product is the same)
-int launch_spmv_f32_exit(padne_ctx *ctx, const padne_csr *m, const float *x, double *y, const double *dot_with,
-                         double *partials, const int32_t *done_flag, const float *aux1, const float *aux2, float scale,
-                         const double *out_scale2, float *z32) {
-    PADNE_REQUIRE(m->vals32 != nullptr && dot_with != nullptr, "single-precision exit stage");
-    if (z32 != nullptr)
-        return launch_spmv_typed<float, float, float>(ctx, m, m->vals32, SPMV_JACOBI, x, z32, dot_with, partials, done_flag,
-                                                      aux1, aux2, scale, out_scale2);
-    return launch_spmv_typed<float, float, double>(ctx, m, m->vals32, SPMV_JACOBI, x, y, dot_with, partials, done_flag,
-                                                   aux1, aux2, scale, out_scale2);
-}
-
-// last stage of the single-precision cycle in the W form: z = (x_pre + c D^-1 r_pre + W e) * sqrt(*out_scale2) in double,
-// with partial sums of dot_with . z.  W carries single-precision values only (m->vals32).
-int launch_spmv_f32_wup_exit(padne_ctx *ctx, const padne_csr *w, const float *e, double *z, const double *dot_with,
-                             double *partials, const int32_t *done_flag, const float *x_pre, const float *r_pre,
-                             const float *dinv32, float scale, const double *out_scale2, float *z32, const float *dot_b32) {
-    PADNE_REQUIRE(w->vals32 != nullptr && dot_with != nullptr, "single-precision W stage");
-    if (z32 != nullptr)
-        return launch_spmv_typed<float, float, float>(ctx, w, w->vals32, SPMV_WUP, e, z32, dot_with, partials, done_flag,
-                                                      r_pre, dinv32, scale, out_scale2, x_pre, const_cast<float *>(dot_b32));
-    return launch_spmv_typed<float, float, double>(ctx, w, w->vals32, SPMV_WUP, e, z, dot_with, partials, done_flag, r_pre,
-                                                   dinv32, scale, out_scale2, x_pre, const_cast<float *>(dot_b32));
-}
-
-// up-leg of an inner level in the W form: x = x_pre + c D^-1 r_pre + W e, single precision throughout
-int launch_spmv_f32_wup(padne_ctx *ctx, const padne_csr *w, const float *e, float *x_out, const int32_t *done_flag,
-                        const float *x_pre, const float *r_pre, const float *dinv32, float scale) {
-    PADNE_REQUIRE(w->vals32 != nullptr, "single-precision W stage");
-    return launch_spmv_typed<float, float, float>(ctx, w, w->vals32, SPMV_WUP, e, x_out, nullptr, nullptr, done_flag, r_pre,
-                                                  dinv32, scale, nullptr, x_pre);
-}
+// the products the solver runs: double, the single-precision cycle (its exit stage with z in double), q = A p with p in float
+template int launch_spmv(padne_ctx *, const padne_csr *, int, const float *, float *, const ProductArgs<float> &, int);
+template int launch_spmv(padne_ctx *, const padne_csr *, int, const float *, double *, const ProductArgs<double> &, int);
+template int launch_spmv(padne_ctx *, const padne_csr *, int, const double *, double *, const ProductArgs<double> &, int);
+template int launch_spmv(padne_ctx *, const padne_csr *, int, const float *, double *, const ProductArgs<float> &, int);
 
 // ---- x-window plan -------------------------------------------------------------------------------------
 // One wave per 64-row tile: greedy cover of the tile's columns by runs of kXwRun entries starting at the smallest
@@ -1172,12 +1089,6 @@ int csr_build_f32(padne_ctx *ctx, padne_csr *m) {
     return PADNE_OK;
 }
 
-int launch_spmv(padne_ctx *ctx, const padne_csr *m, const double *x, double *y,
-                const double *dot_with, double *partials, const int32_t *done_flag) {
-    return launch_spmv_mode(ctx, m, dot_with != nullptr ? SPMV_DOT : SPMV_PLAIN, x, y, dot_with, partials,
-                            done_flag, nullptr, nullptr, 0.0);
-}
-
 // ---- 1/diag ---------------------------------------------------------------------------------
 __global__ void csr_dinv_kernel(int n_rows, const int *__restrict__ rowptr,
                                 const int *__restrict__ cols, const double *__restrict__ vals,
@@ -1233,12 +1144,20 @@ int csr_build_dinv(padne_ctx *ctx, padne_csr *m) {
 
 }  // namespace padne
 
-// ---- test entry: one call of one product launcher (include/padne_hip_test.h) ----------------------------------------
+// ---- test entry: one product in one call shape of the solver (include/padne_hip_probe.h) ---------------------------
 using namespace padne;
 
 static_assert(PADNE_TEST_FORM_WPR == SPMV_FORM_WPR && PADNE_TEST_FORM_LIST == SPMV_FORM_LIST && PADNE_TEST_FORM_LONG == SPMV_FORM_LONG &&
                   PADNE_TEST_FORM_WIDE == SPMV_FORM_WIDE && PADNE_TEST_FORM_TILE == SPMV_FORM_TILE,
               "the test header reports the dispatcher's forms");
+
+// one product through the solver's entry, and the form the dispatcher takes for it -- asked with the same arguments
+template <typename XT, typename YT, typename ST = XT>
+static int probe_spmv(padne_ctx *ctx, const padne_csr *m, int mode, const void *x, void *y, const ProductArgs<XT> &a, int part,
+                      int *form) {
+    *form = spmv_kernel_form<XT, YT>(m, mode, a, part);
+    return launch_spmv<XT, YT, ST>(ctx, m, mode, (const ST *)x, (YT *)y, a, part);
+}
 
 extern "C" int padne_test_product(padne_ctx *ctx, padne_csr *m, int32_t flags, int64_t n_owned, int32_t launcher, int32_t mode,
                                   int32_t k, int32_t part, const void *x, void *y, void *y2, const void *aux0, const void *aux1,
@@ -1263,65 +1182,57 @@ extern "C" int padne_test_product(padne_ctx *ctx, padne_csr *m, int32_t flags, i
         PADNE_HIP_CHECK(hipMalloc(&partials, sizeof(double) * (size_t)rows * kMaxPartials));
         PADNE_HIP_CHECK(hipMemsetAsync(partials, 0xff, sizeof(double) * (size_t)rows * kMaxPartials, ctx->stream));      // sentinel
     }
-    // the kernel form the launch takes, asked with the arguments the launcher hands to the dispatcher
-    const bool wp = partials != nullptr;
-    int form = SPMV_FORM_TILE;
-    switch (launcher) {
-        case PADNE_TEST_SPMV_MODE: form = spmv_kernel_form(m, mode, 8, 8, dot_with != nullptr, wp, SPMV_ALL); break;
-        case PADNE_TEST_SPMV_PART: form = spmv_kernel_form(m, mode, 8, 8, dot_with != nullptr, wp, part); break;
-        case PADNE_TEST_SPMV_DOT_X32: form = spmv_kernel_form(m, SPMV_DOT, 8, 8, false, wp, SPMV_ALL); break;
-        case PADNE_TEST_SPMV_F32: form = spmv_kernel_form(m, mode, 4, 4, false, wp, SPMV_ALL); break;
-        case PADNE_TEST_SPMV_F32_PART: form = spmv_kernel_form(m, mode, 4, 4, false, wp, part); break;
-        case PADNE_TEST_SPMV_F32_RESTRICT: form = spmv_kernel_form(m, SPMV_RESTRICT, 4, 4, false, false, SPMV_ALL); break;
-        case PADNE_TEST_SPMV_F32_RESID_PRE: form = spmv_kernel_form(m, SPMV_RESID_PRE, 4, 4, false, false, SPMV_ALL); break;
-        case PADNE_TEST_SPMV_F32_EXIT: form = spmv_kernel_form(m, SPMV_JACOBI, 4, y2 ? 4 : 8, dot_with != nullptr, wp, SPMV_ALL); break;
-        case PADNE_TEST_SPMV_F32_EXIT_PART: form = spmv_kernel_form(m, SPMV_JACOBI, 4, y2 ? 4 : 8, dot_with != nullptr, wp, part); break;
-        case PADNE_TEST_SPMV_F32_WUP: form = spmv_kernel_form(m, SPMV_WUP, 4, 4, false, false, SPMV_ALL); break;
-        case PADNE_TEST_SPMV_F32_WUP_EXIT: form = spmv_kernel_form(m, SPMV_WUP, 4, y2 ? 4 : 8, dot_with != nullptr, wp, SPMV_ALL); break;
-        default: form = m->n_rows == 0 ? SPMV_FORM_NONE : SPMV_FORM_TILE; break;      // the SpMM kernel: one form
-    }
-    const double *xd = (const double *)x, *a1d = (const double *)aux1, *a2d = (const double *)aux2;
-    const float *xf = (const float *)x, *a0f = (const float *)aux0, *a1f = (const float *)aux1, *a2f = (const float *)aux2;
-    const float *rhsf = (const float *)rhs;
-    const float sf = (float)scale;
+    // The call shape of the solver that `launcher` names, its flat arguments mapped onto the operands by role as the header's
+    // table says: aux0 = x_pre, aux1 = b (the residual r_pre of WUP), aux2 = dinv; y2 is RESTRICT's second output or, in an exit
+    // stage, z32 -- the result in single precision in place of the double y.
+    const float *xf = (const float *)x, *b = (const float *)aux1, *dinv = (const float *)aux2, *x_pre = (const float *)aux0;
+    const float c = (float)scale;
+    float *z32 = (float *)y2;
+    const ProductArgs<double> f64{.b = (const double *)aux1, .dinv = (const double *)aux2, .scale = scale, .dot_with = dot_with,
+                                  .partials = partials, .done_flag = done_flag};
+    const ProductArgs<float> f32{.b = b, .dinv = dinv, .scale = c, .partials = partials, .done_flag = done_flag};
+    const ProductArgs<float> exit{.b = b, .dinv = dinv, .scale = c, .dot_with = dot_with, .partials = partials,
+                                  .out_scale2 = out_scale2, .done_flag = done_flag};
+    const ProductArgs<float> wup{.b = b, .dinv = dinv, .scale = c, .x_pre = x_pre, .done_flag = done_flag};
+    const ProductArgs<float> wup_exit{.b = b, .dinv = dinv, .scale = c, .x_pre = x_pre, .rhs = (const float *)rhs, .dot_with = dot_with,
+                                      .partials = partials, .out_scale2 = out_scale2, .done_flag = done_flag};
+    int form = m->n_rows == 0 ? SPMV_FORM_NONE : SPMV_FORM_TILE;      // (the SpMM kernel: one form)
     int rc = PADNE_OK;
     switch (launcher) {
-        case PADNE_TEST_SPMV_MODE:
-            rc = launch_spmv_mode(ctx, m, mode, xd, (double *)y, dot_with, partials, done_flag, a1d, a2d, scale);
+        case PADNE_TEST_SPMV_MODE: part = SPMV_ALL; [[fallthrough]];
+        case PADNE_TEST_SPMV_PART: rc = probe_spmv<double, double>(ctx, m, mode, x, y, f64, part, &form); break;
+        case PADNE_TEST_SPMV_DOT_X32:
+            rc = probe_spmv<double, double, float>(ctx, m, SPMV_DOT, x, y, {.partials = partials, .done_flag = done_flag}, SPMV_ALL, &form);
             break;
-        case PADNE_TEST_SPMV_PART:
-            rc = launch_spmv_part(ctx, m, mode, part, xd, (double *)y, dot_with, partials, done_flag, a1d, a2d, scale);
+        case PADNE_TEST_SPMV_F32: part = SPMV_ALL; [[fallthrough]];
+        case PADNE_TEST_SPMV_F32_PART: rc = probe_spmv<float, float>(ctx, m, mode, x, y, f32, part, &form); break;
+        case PADNE_TEST_SPMV_F32_RESTRICT:
+            rc = probe_spmv<float, float>(ctx, m, SPMV_RESTRICT, x, y, {.dinv = dinv, .scale = c, .y2 = z32, .done_flag = done_flag},
+                                          SPMV_ALL, &form);
             break;
-        case PADNE_TEST_SPMV_DOT_X32: rc = launch_spmv_dot_x32(ctx, m, xf, (double *)y, partials, done_flag); break;
-        case PADNE_TEST_SPMV_F32: rc = launch_spmv_f32(ctx, m, mode, xf, (float *)y, partials, done_flag, a1f, a2f, sf); break;
-        case PADNE_TEST_SPMV_F32_PART:
-            rc = launch_spmv_f32_part(ctx, m, mode, part, xf, (float *)y, partials, done_flag, a1f, a2f, sf);
+        case PADNE_TEST_SPMV_F32_RESID_PRE:
+            rc = probe_spmv<float, float>(ctx, m, SPMV_RESID_PRE, x, y, {.dinv = dinv, .scale = c, .done_flag = done_flag}, SPMV_ALL, &form);
             break;
-        case PADNE_TEST_SPMV_F32_RESTRICT: rc = launch_spmv_f32_restrict(ctx, m, xf, (float *)y, (float *)y2, done_flag, a2f, sf); break;
-        case PADNE_TEST_SPMV_F32_RESID_PRE: rc = launch_spmv_f32_resid_pre(ctx, m, xf, (float *)y, done_flag, a2f, sf); break;
-        case PADNE_TEST_SPMV_F32_EXIT:
-            rc = launch_spmv_f32_exit(ctx, m, xf, (double *)y, dot_with, partials, done_flag, a1f, a2f, sf, out_scale2, (float *)y2);
-            break;
+        case PADNE_TEST_SPMV_F32_EXIT: part = SPMV_ALL; [[fallthrough]];
         case PADNE_TEST_SPMV_F32_EXIT_PART:
-            rc = launch_spmv_f32_exit_part(ctx, m, part, xf, (double *)y, dot_with, partials, done_flag, a1f, a2f, sf, out_scale2,
-                                           (float *)y2);
+            rc = z32 ? probe_spmv<float, float>(ctx, m, SPMV_JACOBI, x, z32, exit, part, &form)
+                     : probe_spmv<float, double>(ctx, m, SPMV_JACOBI, x, y, exit, part, &form);
             break;
-        case PADNE_TEST_SPMV_F32_WUP: rc = launch_spmv_f32_wup(ctx, m, xf, (float *)y, done_flag, a0f, a1f, a2f, sf); break;
+        case PADNE_TEST_SPMV_F32_WUP: rc = probe_spmv<float, float>(ctx, m, SPMV_WUP, x, y, wup, SPMV_ALL, &form); break;
         case PADNE_TEST_SPMV_F32_WUP_EXIT:
-            rc = launch_spmv_f32_wup_exit(ctx, m, xf, (double *)y, dot_with, partials, done_flag, a0f, a1f, a2f, sf, out_scale2,
-                                          (float *)y2, rhsf);
+            rc = z32 ? probe_spmv<float, float>(ctx, m, SPMV_WUP, x, z32, wup_exit, SPMV_ALL, &form)
+                     : probe_spmv<float, double>(ctx, m, SPMV_WUP, x, y, wup_exit, SPMV_ALL, &form);
             break;
-        case PADNE_TEST_SPMM_MODE:
-            rc = launch_spmm_mode(ctx, m, k, mode, xd, (double *)y, dot_with, partials, done_flag, a1d, a2d, scale);
-            break;
-        case PADNE_TEST_SPMM_F32: rc = launch_spmm_f32(ctx, m, k, mode, xf, (float *)y, partials, done_flag, a1f, a2f, sf); break;
+        case PADNE_TEST_SPMM_MODE: rc = launch_spmm<double, double>(ctx, m, k, mode, (const double *)x, (double *)y, f64); break;
+        case PADNE_TEST_SPMM_F32: rc = launch_spmm<float, float>(ctx, m, k, mode, xf, (float *)y, f32); break;
         case PADNE_TEST_SPMM_F32_EXIT:
-            rc = launch_spmm_f32_exit(ctx, m, k, xf, (double *)y, dot_with, partials, done_flag, a1f, a2f, sf, out_scale2, (float *)y2);
+            rc = z32 ? launch_spmm<float, float>(ctx, m, k, SPMV_JACOBI, xf, z32, exit)
+                     : launch_spmm<float, double>(ctx, m, k, SPMV_JACOBI, xf, (double *)y, exit);
             break;
-        case PADNE_TEST_SPMM_F32_WUP: rc = launch_spmm_f32_wup(ctx, m, k, xf, (float *)y, done_flag, a0f, a1f, a2f, sf); break;
+        case PADNE_TEST_SPMM_F32_WUP: rc = launch_spmm<float, float>(ctx, m, k, SPMV_WUP, xf, (float *)y, wup); break;
         default:
-            rc = launch_spmm_f32_wup_exit(ctx, m, k, xf, (double *)y, dot_with, partials, done_flag, a0f, a1f, a2f, sf, out_scale2,
-                                          (float *)y2, rhsf);
+            rc = z32 ? launch_spmm<float, float>(ctx, m, k, SPMV_WUP, xf, z32, wup_exit)
+                     : launch_spmm<float, double>(ctx, m, k, SPMV_WUP, xf, (double *)y, wup_exit);
             break;
     }
     hipError_t e = hipStreamSynchronize(ctx->stream);
