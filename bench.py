@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Headline benchmark: CG solves/s (and SpMV GB/s vs the HBM roofline) on the synthetic layered
+"""Headline benchmark: CG solves/s (and, with --full, SpMV GB/s vs the HBM roofline) on the synthetic layered
 Laplacian of BASELINE.json, MI355X.
 
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -14,7 +15,9 @@ and the right-hand side already resident in HBM.  Workload at every GPU count: c
 1118 x 1118 vertices (N = 10M unknowns, ~70M non-zeros) stitched by via rings; with N GPUs the
 layers are dealt to the ranks (strong scaling: the problem is fixed, ``scaling: "strong"``).
 
-One JSON line is printed by rank 0 (see DESIGN.md "Measurement" for every field).
+One JSON line is printed by rank 0 (see DESIGN.md "Measurement" for every field).  A plain run builds the workload,
+warms up, times the steps, writes --dump-outputs and prints the headline fields; every other measurement (the roofline
+figures, the assembly, the seam, the side configurations, the CPU baseline) takes runs of its own and comes with --full.
 """
 from __future__ import annotations
 
@@ -42,6 +45,10 @@ def parse():
     ap.add_argument("--workload", default="C4", help="C2 | C3 | C4 (default, the headline config)")
     ap.add_argument("--precond", default="amg", choices=["amg", "jacobi"],
                     help="amg: smoothed-aggregation multigrid V-cycle (rebuilt inside every step); jacobi: diagonal")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: the in-situ and standalone SpMV roofline, the "
+                         "whole-step roofline, the warm assembly and reduction, launch counts, the seam, C5, small sizes, the "
+                         "rank proxy, C4 on a one-rank communicator and the CPU baseline (the --no-* options below trim it)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-seam", action="store_true",
                     help="skip the solve_system(L, r) wall-time measurement behind the timed steps (profiling runs)")
@@ -560,18 +567,19 @@ def main():
         L = ctx.assemble_system(N, xy, tri, mvo, mto, sig, rows, cols, vals)
         ctx.synchronize()
         t_assemble = time.perf_counter() - t0
-        # the same assembly WARM (pool blocks in place, code objects loaded): device-resident meshes in, CSR matrix out,
-        # wall time per call with its host looks; the cold call above pays first-use costs and is reported apart
+        # --full: the same assembly WARM (pool blocks in place, code objects loaded): device-resident meshes in, CSR matrix
+        # out, wall time per call with its host looks; the cold call above pays first-use costs and is reported apart
         asm_warm = []
-        for rep in range(ASSEMBLY_REPEATS + 1):
-            ctx.synchronize()
-            t0 = time.perf_counter()
-            L_again = ctx.assemble_system(N, xy, tri, mvo, mto, sig, rows, cols, vals)
-            ctx.synchronize()
-            if rep > 0:      # (the first call beside a live result still draws its 1 GB of result arrays from hipMalloc: 1.5-40 ms by box)
-                asm_warm.append(time.perf_counter() - t0)
-            assert L_again.nnz == L.nnz
-            L_again.close()
+        if args.full:
+            for rep in range(ASSEMBLY_REPEATS + 1):
+                ctx.synchronize()
+                t0 = time.perf_counter()
+                L_again = ctx.assemble_system(N, xy, tri, mvo, mto, sig, rows, cols, vals)
+                ctx.synchronize()
+                if rep > 0:      # (the first call beside a live result still draws its 1 GB of result arrays from hipMalloc: 1.5-40 ms by box)
+                    asm_warm.append(time.perf_counter() - t0)
+                assert L_again.nnz == L.nnz
+                L_again.close()
         imap = np.arange(N, dtype=np.int32)
         imap[sysm.ground] = -1
         imap[imap > sysm.ground] -= 1
@@ -581,17 +589,18 @@ def main():
         ctx.synchronize()
         t_reduce = time.perf_counter() - t0
         red_warm, red_warm_host = [], []
-        imap_dev = ctx.to_device(imap)      # the index map is an input like the mesh: resident in HBM when the timed region starts
-        for host_map in (True, False):
-            for _ in range(ASSEMBLY_REPEATS):
-                ctx.synchronize()
-                t0 = time.perf_counter()
-                A_again = L.reduce(imap if host_map else imap_dev, nv - 1, -1.0)
-                ctx.synchronize()
-                (red_warm_host if host_map else red_warm).append(time.perf_counter() - t0)
-                assert A_again.nnz == A.nnz
-                A_again.close()
-        imap_dev.free()
+        if args.full:
+            imap_dev = ctx.to_device(imap)      # the index map is an input like the mesh: resident in HBM when the timed region starts
+            for host_map in (True, False):
+                for _ in range(ASSEMBLY_REPEATS):
+                    ctx.synchronize()
+                    t0 = time.perf_counter()
+                    A_again = L.reduce(imap if host_map else imap_dev, nv - 1, -1.0)
+                    ctx.synchronize()
+                    (red_warm_host if host_map else red_warm).append(time.perf_counter() - t0)
+                    assert A_again.nnz == A.nnz
+                    A_again.close()
+            imap_dev.free()
         L_nnz = L.nnz
         L_full = L                   # kept for the seam measurement below (solve_system on host vectors)
         keep = np.flatnonzero(imap[:nv] >= 0)
@@ -652,17 +661,20 @@ def main():
         if rank == 0:
             dumped = dump_outputs(args.dump_outputs, x_host, last)
         del x_host
-    # one more (untimed) solve with HIP events around every 16th SpMV launch, on the kernels' stream
-    prof = solver(time_spmv=True)
-    barrier()
-    t_standalone = standalone() if standalone is not None else None
+    # ---- --full only: everything beside the headline figure, untimed, behind the steps ---------------------
+    prof = t_standalone = None
+    if args.full:
+        # one more (untimed) solve with HIP events around every 16th SpMV launch, on the kernels' stream
+        prof = solver(time_spmv=True)
+        barrier()
+        t_standalone = standalone() if standalone is not None else None
     seam = None
-    if not distributed_path and args.precond == "amg" and not args.no_seam:
+    if args.full and not distributed_path and args.precond == "amg" and not args.no_seam:
         seam = seam_timing(ctx, L_full, sysm, rhs, max(2, min(args.steps, 5)))
     if not distributed_path:
         L_full.close()               # (the assembled KKT matrix, ~1 GB at C4: only the seam measurement needed it)
     shapes_now = None
-    if hierarchy_shapes is not None:
+    if args.full and hierarchy_shapes is not None:
         try:
             shapes_now = hierarchy_shapes()      # (of the last timed step's hierarchy, while the matrix is alive)
         except Exception:
@@ -670,7 +682,7 @@ def main():
     # launches of one step, of its setup and per iteration (library-side count, outside the timed region): a whole step, a
     # solve on the cached hierarchy, a shorter solve on it
     launches = None
-    if not distributed_path and args.precond == "amg" and not args.no_launch_count:
+    if args.full and not distributed_path and args.precond == "amg" and not args.no_launch_count:
         try:
             c0 = _hip.launch_count()
             solver()
@@ -688,7 +700,7 @@ def main():
         except Exception as exc:
             launches = {"error": repr(exc)}
     c5 = proxy = small = d1 = None
-    if not distributed_path and args.precond == "amg" and args.workload == "C4":
+    if args.full and not distributed_path and args.precond == "amg" and args.workload == "C4":
         A.close()
         b.free()
         x.free()
@@ -721,22 +733,6 @@ def main():
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
-        t_spmv = prof.spmv_seconds
-        # the product of the multigrid-preconditioned loop on one GPU multiplies a search direction STORED in single precision
-        # (pcg.hip): 4 instead of 8 bytes of x per row; the standalone launches (and every other path) multiply doubles
-        p_stored_f32 = (args.precond == "amg" and not distributed_path and "PADNE_PCG_P64" not in os.environ
-                        and "PADNE_AMG_F64" not in os.environ)
-        spmv_bytes_standalone = spmv_bytes
-        if p_stored_f32:
-            spmv_bytes = spmv_bytes - 4 * n_local
-        achieved = spmv_bytes / t_spmv / 1e9 if t_spmv > 0 else 0.0
-        traffic = None
-        tpath = os.path.join(ROOT, "profiles", "spmv_traffic.json")
-        if os.path.exists(tpath) and not distributed_path:      # measured on the 1-GPU launch; a rank's launch is smaller
-            try:
-                traffic = json.load(open(tpath)).get("bytes_per_launch")
-            except Exception:
-                traffic = None
         out = {
             "metric": "CG solves/s",
             "value": args.steps / elapsed,
@@ -764,19 +760,37 @@ def main():
             "pcg_textbook_gbs": (232.0 * n_local * last.iterations / last.seconds / 1e9
                                  if last.seconds > 0 and args.precond == "jacobi" else None),
             "setup_seconds": {"total": t_setup, "assemble": t_assemble, "reduce": t_reduce},
-            "roofline": {"bound": "hbm", "kernel": "csr_spmv_kernel<SPMV_DOT, double, double, double" +
-                                                   (", x stored as float" if p_stored_f32 else "") + "> (q = A p with p.q epilogue)",
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "traffic_static_from": "profiles/spmv_traffic.json (rocprofv3 --pmc passes of the round's final build, "
-                                                "scripts/pmc_bench.sh; not collected in this run)" if traffic is not None else None,
-                         "bytes_per_launch": int(spmv_bytes), "seconds_per_launch": t_spmv,
-                         "note": "achieved/frac: kernel timed in situ inside the CG loop; standalone_frac: the same "
-                                 "kernel launched back to back (no dirty predecessor)",
-                         "bytes_rule": ("12 nnz + 16 n + 4 (values 8 + columns 4 per non-zero; row pointer 4, x 4, y 8 per row)"
-                                        if p_stored_f32 else "12 nnz + 20 n + 4 (values 8 + columns 4 per non-zero; row pointer 4, x 8, y 8 per row)"),
-                         "standalone_frac": (spmv_bytes_standalone / t_standalone / 1e9 / HBM_PEAK_GBS) if t_standalone else None},
         }
+        if prof is not None:
+            t_spmv = prof.spmv_seconds
+            # the product of the multigrid-preconditioned loop on one GPU multiplies a search direction STORED in single
+            # precision (pcg.hip): 4 instead of 8 bytes of x per row; the standalone launches (and every other path) multiply doubles
+            p_stored_f32 = (args.precond == "amg" and not distributed_path and "PADNE_PCG_P64" not in os.environ
+                            and "PADNE_AMG_F64" not in os.environ)
+            spmv_bytes_standalone = spmv_bytes
+            if p_stored_f32:
+                spmv_bytes = spmv_bytes - 4 * n_local
+            achieved = spmv_bytes / t_spmv / 1e9 if t_spmv > 0 else 0.0
+            traffic = None
+            tpath = os.path.join(ROOT, "profiles", "spmv_traffic.json")
+            if os.path.exists(tpath) and not distributed_path:      # measured on the 1-GPU launch; a rank's launch is smaller
+                try:
+                    traffic = json.load(open(tpath)).get("bytes_per_launch")
+                except Exception:
+                    traffic = None
+            out["roofline"] = {
+                "bound": "hbm", "kernel": "csr_spmv_kernel<SPMV_DOT, double, double, double" +
+                                          (", x stored as float" if p_stored_f32 else "") + "> (q = A p with p.q epilogue)",
+                "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                "traffic_static_from": "profiles/spmv_traffic.json (rocprofv3 --pmc passes of the round's final build, "
+                                       "scripts/pmc_bench.sh; not collected in this run)" if traffic is not None else None,
+                "bytes_per_launch": int(spmv_bytes), "seconds_per_launch": t_spmv,
+                "note": "achieved/frac: kernel timed in situ inside the CG loop; standalone_frac: the same "
+                        "kernel launched back to back (no dirty predecessor)",
+                "bytes_rule": ("12 nnz + 16 n + 4 (values 8 + columns 4 per non-zero; row pointer 4, x 4, y 8 per row)"
+                               if p_stored_f32 else "12 nnz + 20 n + 4 (values 8 + columns 4 per non-zero; row pointer 4, x 8, y 8 per row)"),
+                "standalone_frac": (spmv_bytes_standalone / t_standalone / 1e9 / HBM_PEAK_GBS) if t_standalone else None}
         if shapes_now is not None:
             try:
                 sb = step_algorithmic_bytes(shapes_now, int(last.iterations))
@@ -800,7 +814,7 @@ def main():
                                                "that round's final build; not collected in this run)"})
             except Exception as exc:
                 out["roofline"]["step"] = {"error": repr(exc)}
-        if not distributed_path:
+        if args.full and not distributed_path:
             # per-element stiffness assembly (mesh.py:124-139, solver.py:171-213, 563-575) from device-resident meshes, timed
             # warm in THIS run; algorithmic bytes per SURVEY 8d: 16 N (xy) + 12 T (tri) + 12 nnz (out) = 124 N
             asm_ms = float(np.mean(asm_warm)) * 1e3
@@ -849,7 +863,7 @@ def main():
             out["dist_one_rank"] = d1
         if small is not None:
             out["small"] = small
-        if args.gpus == 1 and not args.no_cpu_baseline:
+        if args.full and args.gpus == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(args.cpu_sample_nx)
             except Exception as exc:  # the GPU numbers stand on their own

@@ -3,6 +3,7 @@
 # Usage: scripts/gpu_prof.sh TAG [filter] [extra bench.py arguments, e.g. --workload C2]
 TAG=${1:-prof}; FILTER=${2:-}; shift; shift
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
+set -- --full "$@"      # the per-solve summaries below count the solves of a --full run
 rm -rf gpurun_out/prof_${TAG}
 timeout -k 10 400 rocprofv3 --kernel-trace -d gpurun_out/prof_${TAG} -o p -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-seam --no-c5 --no-rank-proxy --no-small --no-dist-one-rank "$@" > gpurun_out/${TAG}_bench.log 2>&1 || { tail -20 gpurun_out/${TAG}_bench.log; exit 1; }
 DB=$(ls gpurun_out/prof_${TAG}/*.db | head -1)

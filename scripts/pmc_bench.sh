@@ -2,9 +2,11 @@
 # HBM traffic of the dominant kernel per launch: FETCH_SIZE and WRITE_SIZE in SEPARATE rocprofv3 --pmc passes over one
 # bench step (MI355X_MICROARCH.md, HBM section: FETCH_SIZE x2 on gfx950, calibrated here on a pure streaming kernel).
 # usage (on the GPU box, from the repo root):  bash scripts/pmc_bench.sh gpurun_out/pmc_r01
-OUT="$GRAFT_REPO_ROOT/$1"; mkdir -p "$OUT"; export TMPDIR=/tmp; cd /tmp
+# --full: scripts/pmc_setup_sum.py halves its sums over the timed step and the solve that samples the SpMV with events
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
+OUT="$ROOT/$1"; mkdir -p "$OUT"; export TMPDIR=/tmp; cd /tmp
 for C in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $C --output-format csv -d "$OUT/$C" -o run -- python3 $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-seam --no-c5 --no-rank-proxy --no-small --no-dist-one-rank --no-launch-count > "$OUT/$C.log" 2>&1 || exit 1
+  rocprofv3 --pmc $C --output-format csv -d "$OUT/$C" -o run -- python3 $ROOT/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-seam --no-c5 --no-rank-proxy --no-small --no-dist-one-rank --no-launch-count > "$OUT/$C.log" 2>&1 || exit 1
 done
 python3 - "$OUT" <<'PY'
 import csv, glob, json, sys, collections

@@ -1,6 +1,6 @@
-"""The driver's contract with bench.py: ONE JSON line on stdout with the agreed keys, run here on the small config C2 with
-every side block that needs minutes switched off (the side blocks that remain -- the seam, the launch counts -- are
-checked for their shape)."""
+"""The driver's contract with bench.py: ONE JSON line on stdout with the agreed keys, run here on the small config C2 -- a
+plain run (the headline fields and nothing else) and a --full run with every side block that needs minutes switched off
+(the side blocks that remain -- the roofline, the assembly, the seam, the launch counts -- are checked for their shape)."""
 import json
 import os
 import subprocess
@@ -13,15 +13,38 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.mark.gpu
-def test_bench_prints_one_json_line_with_the_agreed_keys(tmp_path):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", "C2",
-           "--no-cpu-baseline", "--no-c5", "--no-rank-proxy", "--no-small", "--no-dist-one-rank", "--dump-outputs", str(tmp_path)]
+def _bench_line(*args):
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", "C2", *args]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
-    d = json.loads(lines[0])
+    return json.loads(lines[0])
+
+
+@pytest.mark.gpu
+def test_plain_bench_prints_the_headline_and_nothing_that_takes_runs_of_its_own(tmp_path):
+    d = _bench_line("--dump-outputs", str(tmp_path))
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+                "dtype", "data", "config", "preconditioner", "iterations", "rel_residual", "setup_seconds", "dump_outputs"):
+        assert key in d, key
+    assert d["metric"] == "CG solves/s" and d["unit"] == "solves/s" and d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1
+    assert d["higher_is_better"] is True and d["dtype"] == "f64" and d["data"] == "synthetic" and d["vs_baseline"] is None
+    assert abs(d["value"] * d["ms_per_step"] - 1e3) < 1e-6 * 1e3
+    assert d["iterations"] > 5 and d["rel_residual"] <= 1.1e-12 and d["preconditioner"]["kind"] == "amg"
+    for key in ("roofline", "assembly", "value_with_assembly", "seam", "c5", "small", "rank_proxy", "dist_one_rank", "cpu_baseline"):
+        assert key not in d, key
+    assert "launches" not in d["preconditioner"]
+    got = {k: np.load(tmp_path / f"{k}.npy") for k in d["dump_outputs"]["arrays"]}
+    assert sorted(got) == ["abs_residual", "iterations", "rel_residual", "x", "x_index"]
+    n = d["config"]["n_unknowns"]
+    assert got["x"].shape == (n,) and np.isfinite(got["x"]).all() and int(got["iterations"]) == d["iterations"]
+
+
+@pytest.mark.gpu
+def test_bench_prints_one_json_line_with_the_agreed_keys(tmp_path):
+    d = _bench_line("--full", "--no-cpu-baseline", "--no-c5", "--no-rank-proxy", "--no-small", "--no-dist-one-rank",
+                    "--dump-outputs", str(tmp_path))
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
                 "dtype", "data", "config", "roofline"):
         assert key in d, key
