@@ -295,6 +295,7 @@ int padne_kkt_matrix(const padne_kkt *plan, const padne_csr **reduced_out);
  * absolute residual bar, tests/test_solver.py:2083-2089; 0 = off), expands v = c + P y and Z_k = P z_k, and returns
  * probe_out[(1 + n_extra)][n_probe]: rho = r - L v, then L Z_k, at the probed unknowns (the members of the constraint
  * groups) -- what the host needs to peel the multiplier currents from.  v stays on the device.
+ * At most 4095 extra right-hand sides (with r itself, the 4096 padne_kkt_solve_block allows).
  * Returns PADNE_E_NOTCONVERGED like padne_solve_spd (the iterate is kept, padne_kkt_finish may follow). */
 int padne_kkt_solve(padne_ctx *ctx, padne_kkt *plan, const double *r_host, int64_t n_known, const int64_t *known_idx,
                     const double *known_val, int32_t n_extra, const int64_t *extra_ptr, const int64_t *extra_row,
@@ -305,6 +306,23 @@ int padne_kkt_solve(padne_ctx *ctx, padne_kkt *plan, const double *r_host, int64
  * (solver.py:775) while v[N] travels to v_host -- its only crossing of PCIe. */
 int padne_kkt_finish(padne_ctx *ctx, padne_kkt *plan, int32_t n_extra, const double *extra_coeff, int64_t n_mult,
                      const int64_t *mult_idx, const double *mult_val, double *v_host, double *residual_norm_out);
+/* Stage 1 for a block of n_cols right-hand sides (the reference's spsolve with a 2-D r): r_host[N][n_cols] row-major, uploaded
+ * once in that layout; known_val[n_cols][n_known] (one index list for all columns: the union, zero where a column knows
+ * nothing); the extra right-hand sides as in padne_kkt_solve, solved ONCE for the whole block.  The products with L take one
+ * pass over L per group of up to 8 columns; all n_cols + n_extra reduced columns (at most 4096) go through
+ * padne_solve_spd_dev together, so its lockstep grouping sees them all (zero columns are skipped and come back as zeros).
+ * probe_out[n_cols + n_extra][n_probe]: rho_j = r_j - L v_j for every column, then L Z_k.  padne_kkt_solve is the case
+ * n_cols = 1. */
+int padne_kkt_solve_block(padne_ctx *ctx, padne_kkt *plan, int32_t n_cols, const double *r_host, int64_t n_known,
+                          const int64_t *known_idx, const double *known_val, int32_t n_extra, const int64_t *extra_ptr,
+                          const int64_t *extra_row, const double *extra_val, int64_t n_probe, const int64_t *probe_idx,
+                          double *probe_out, const padne_solve_opts *opts, double abs_residual_target, padne_solve_info *info);
+/* Stage 2 of a block: v_j += sum_k extra_coeff[j][k] Z_k, v_j[mult_idx] = mult_val[j][:], then residual_norms_out[j] =
+ * ||L v_j - r_j||_2 while V travels to v_host[N][n_cols] (row-major, the layout r_host had).  n_cols and n_extra as in
+ * the stage 1 before it; padne_kkt_finish is the case n_cols = 1. */
+int padne_kkt_finish_block(padne_ctx *ctx, padne_kkt *plan, int32_t n_cols, int32_t n_extra, const double *extra_coeff,
+                           int64_t n_mult, const int64_t *mult_idx, const double *mult_val, double *v_host,
+                           double *residual_norms_out);
 
 /* Row-partitioned runs, optional: attach the rank's owned x owned diagonal block; with precond = 1 the
  * multigrid hierarchy is then built on that block only (block-Jacobi with multigrid blocks, no

@@ -105,6 +105,9 @@ SIGNATURES = {
     "padne_kkt_solve": (C.c_int, [_P, _P, _PF64, _I64, _PI64, _PF64, C.c_int32, _PI64, _PI64, _PF64, _I64, _PI64, _PF64,
                                   C.POINTER(SolveOpts), C.c_double, C.POINTER(SolveInfo)]),
     "padne_kkt_finish": (C.c_int, [_P, _P, C.c_int32, _PF64, _I64, _PI64, _PF64, _PF64, _PF64]),
+    "padne_kkt_solve_block": (C.c_int, [_P, _P, C.c_int32, _PF64, _I64, _PI64, _PF64, C.c_int32, _PI64, _PI64, _PF64, _I64,
+                                        _PI64, _PF64, C.POINTER(SolveOpts), C.c_double, C.POINTER(SolveInfo)]),
+    "padne_kkt_finish_block": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _PF64, _I64, _PI64, _PF64, _PF64, _PF64]),
     "padne_amg_apply": (C.c_int, [_P, _P, _PF64, _PF64]),
     "padne_csr_set_preconditioner_block": (C.c_int, [_P, _P]),
     "padne_amg_level": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(_P)]),
@@ -613,10 +616,25 @@ class KktPlan:
         """Stage 1.  ``known`` {unknown: c}; ``extras``: list of {row: value} columns; ``probes``: unknowns whose residual
         rows come back.  Returns (probe values [(1 + len(extras)), len(probes)], SolveResult)."""
         r = _f64(r)
-        if r.shape[0] != self.N:
+        if r.ndim != 1 or r.shape[0] != self.N:
             raise ValueError("right-hand side has the wrong length")
         kidx = _i64(sorted(known))
         kval = _f64([known[int(i)] for i in kidx])
+        return self._stage1(None, r, kidx, kval, extras, probes, rtol, max_iter, precond, abs_residual_target, rebuild)
+
+    def solve_block(self, R, known_idx, known_val, extras: list, probes, *, rtol=1e-12, max_iter=200000, precond="amg",
+                    abs_residual_target=0.0, rebuild=False):
+        """Stage 1 for a block ``R`` (N, k) of right-hand sides, uploaded in its row-major layout (a Fortran-ordered block
+        is copied once).  ``known_idx`` [n_known] with ``known_val`` (k, n_known); the ``extras`` are solved once for the
+        block.  Returns (probe values [(k + len(extras)), len(probes)], SolveResult summed over all reduced solves)."""
+        R = _f64(R)
+        if R.ndim != 2 or R.shape[0] != self.N or R.shape[1] < 1:
+            raise ValueError("the block of right-hand sides must have shape (N, k) with k >= 1")
+        kidx = _i64(known_idx)
+        kval = _f64(known_val).reshape(R.shape[1], kidx.shape[0])
+        return self._stage1(R.shape[1], R, kidx, kval, extras, probes, rtol, max_iter, precond, abs_residual_target, rebuild)
+
+    def _stage1(self, n_cols, r, kidx, kval, extras, probes, rtol, max_iter, precond, abs_residual_target, rebuild):
         ptr, rows, vals = [0], [], []
         for col in extras:
             for row, val in col.items():
@@ -625,23 +643,31 @@ class KktPlan:
             ptr.append(len(rows))
         ptr, rows, vals = _i64(ptr), _i64(rows), _f64(vals)
         pidx = _i64(list(probes))
-        out = np.zeros((1 + len(extras), max(len(pidx), 1)), dtype=np.float64)
+        out = np.zeros(((n_cols or 1) + len(extras), max(len(pidx), 1)), dtype=np.float64)
         opts = CsrMatrix._opts(rtol, 0.0, max_iter, 0, False, precond=precond, rebuild=rebuild)
         info = SolveInfo()
-        # the vector stage 2 will hand back: its pages are touched while the device solves (a fresh 80 MB array at 10 M
-        # unknowns is 20 000 page faults in the path of the copy that brings v home)
+        # the array stage 2 will hand back: its pages are touched while the device solves (a fresh 80 MB array at 10 M
+        # unknowns is 20 000 page faults in the path of the copy that brings v home); one thread per 80 MB, up to 8, so that
+        # a block's result is ready when the device is
         self._v_next, self._v_toucher = None, None
-        if self.N >= (1 << 18):
+        if r.size >= (1 << 18):
             import threading
-            v_next = np.empty(self.N, dtype=np.float64)
+            v_next = np.empty(r.shape, dtype=np.float64)
             self._v_next = v_next
-            # (the thread holds the array itself, not just its address: it outlives a plan that is dropped on an error path)
-            self._v_toucher = threading.Thread(target=lambda a=v_next: C.memset(a.ctypes.data, 0, a.nbytes), daemon=True)
-            self._v_toucher.start()
-        rc = self.ctx._lib.padne_kkt_solve(self.ctx._h, self._h, _ptr(r, _PF64), kidx.shape[0], _ptr(kidx, _PI64),
-                                           _ptr(kval, _PF64), len(extras), _ptr(ptr, _PI64), _ptr(rows, _PI64),
-                                           _ptr(vals, _PF64), pidx.shape[0], _ptr(pidx, _PI64), _ptr(out, _PF64),
-                                           C.byref(opts), float(abs_residual_target), C.byref(info))
+            flat = v_next.reshape(-1)
+            parts = np.array_split(flat, min(8, -(-flat.nbytes // (80 << 20))))
+            # (the threads hold the array itself, not just its address: it outlives a plan that is dropped on an error path)
+            self._v_toucher = [threading.Thread(target=lambda a=a: C.memset(a.ctypes.data, 0, a.nbytes), daemon=True)
+                               for a in parts]
+            for t in self._v_toucher:
+                t.start()
+        lib, common = self.ctx._lib, (_ptr(r, _PF64), kidx.shape[0], _ptr(kidx, _PI64), _ptr(kval, _PF64), len(extras),
+                                      _ptr(ptr, _PI64), _ptr(rows, _PI64), _ptr(vals, _PF64), pidx.shape[0], _ptr(pidx, _PI64),
+                                      _ptr(out, _PF64), C.byref(opts), float(abs_residual_target), C.byref(info))
+        if n_cols is None:
+            rc = lib.padne_kkt_solve(self.ctx._h, self._h, *common)
+        else:
+            rc = lib.padne_kkt_solve_block(self.ctx._h, self._h, int(n_cols), *common)
         if rc != OK and rc != E_NOTCONVERGED:
             _check(rc)
         res = SolveResult(None, info.iterations, info.restarts, info.rel_residual, info.abs_residual, info.solve_seconds,
@@ -649,21 +675,40 @@ class KktPlan:
                           info.precond_fallbacks)
         return out[:, :len(pidx)], res
 
+    def _result_array(self, shape):
+        toucher, v = getattr(self, "_v_toucher", None), getattr(self, "_v_next", None)
+        self._v_next, self._v_toucher = None, None
+        for t in toucher or ():
+            t.join()
+        if v is None or v.shape != shape:
+            v = np.empty(shape, dtype=np.float64)
+        return v
+
     def finish(self, extra_coeff, multipliers: dict):
         """Stage 2: (v, ||L v - r||)."""
         coeff = _f64(extra_coeff)
         midx = _i64(sorted(multipliers))
         mval = _f64([multipliers[int(i)] for i in midx])
-        toucher, v = getattr(self, "_v_toucher", None), getattr(self, "_v_next", None)
-        self._v_next, self._v_toucher = None, None
-        if toucher is not None:
-            toucher.join()
-        if v is None:
-            v = np.empty(self.N, dtype=np.float64)
+        v = self._result_array((self.N,))
         norm = C.c_double()
         _check(self.ctx._lib.padne_kkt_finish(self.ctx._h, self._h, coeff.shape[0], _ptr(coeff, _PF64), midx.shape[0],
                                               _ptr(midx, _PI64), _ptr(mval, _PF64), _ptr(v, _PF64), C.byref(norm)))
         return v, norm.value
+
+    def finish_block(self, extra_coeff, mult_idx, mult_val):
+        """Stage 2 of a block: ``extra_coeff`` (k, n_extra) regulator currents per column, ``mult_val`` (k, n_mult)
+        multiplier currents per column at the unknowns ``mult_idx``.  Returns (V (N, k) C-contiguous, ||L v_j - r_j|| (k,))."""
+        coeff = _f64(extra_coeff)
+        if coeff.ndim != 2:
+            raise ValueError("extra_coeff must have shape (k, n_extra)")
+        k = coeff.shape[0]
+        midx = _i64(mult_idx)
+        mval = _f64(mult_val).reshape(k, midx.shape[0])
+        V = self._result_array((self.N, k))
+        norms = np.zeros(k, dtype=np.float64)
+        _check(self.ctx._lib.padne_kkt_finish_block(self.ctx._h, self._h, k, coeff.shape[1], _ptr(coeff, _PF64), midx.shape[0],
+                                                    _ptr(midx, _PI64), _ptr(mval, _PF64), _ptr(V, _PF64), _ptr(norms, _PF64)))
+        return V, norms
 
 
 class CsrMatrix:

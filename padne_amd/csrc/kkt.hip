@@ -41,10 +41,14 @@ struct padne_kkt {
     int32_t *tied_order = nullptr, *tied_gptr = nullptr;
     long long n_tied_groups = 0;
     padne_csr *A = nullptr;              // -P^T L P, owned (with its hierarchy once a solve has built it)
-    double *r = nullptr, *v = nullptr, *w = nullptr, *c = nullptr;      // [N] device vectors: right-hand side, solution, scratch, known part
-    double *b = nullptr, *y = nullptr;   // [(1 + n_extra) * n_free]
+    // [N * vec_cap] device vectors: right-hand sides (the caller's layout), solutions, scratch, known parts (the products'
+    // layout, see "blocks of right-hand sides")
+    double *r = nullptr, *v = nullptr, *w = nullptr, *c = nullptr;
+    double *b = nullptr, *y = nullptr;   // [(n_cols + n_extra) * n_free]
     double *Z = nullptr;                 // [n_extra * N] expanded extra solutions (regulators)
-    int n_extra_cap = 0, n_extra = 0;
+    long long vec_cap = 1;               // doubles per unknown the four N-vectors hold
+    int rhs_cap = 1, z_cap = 0;          // reduced columns b and y hold, expanded extra solutions Z holds
+    int n_cols = 1, n_extra = 0;         // of the last solve
     bool has_c = false, solved = false;
     double setup_seconds_last = 0.0;
 };
@@ -93,38 +97,74 @@ __global__ void kkt_fix_sources(const int n_tied, const long long *__restrict__ 
     if (k < n_tied) src_of[imap[rep[k]]] = (int32_t)rep[k];
 }
 
-__global__ void kkt_scatter_f64(const int n, const long long *__restrict__ idx, const double *__restrict__ val, double *__restrict__ dst) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k < n) dst[idx[k]] = val[k];
+// ---- blocks of right-hand sides ------------------------------------------------------------------------------------
+// A block of n_cols right-hand sides crosses PCIe in the caller's layout, [N][n_cols] row-major (r and the result).  The
+// products with L read another one: columns in groups of 8, group g at offset 8 g N, laid out [N][w] with w the SpMM width of
+// the group (8 for a full group; a last group of `count` columns is widened to 1, 2, 4 or 8, its spare columns zero).  For
+// n_cols = 1, 2, 4 and 8 the two layouts coincide.  The elementwise stages read the caller's layout and write the products'
+// one (or back), so no pass of its own converts between them; with n_cols = 1 every kernel below does exactly the
+// arithmetic of the single-vector stage it generalises.
+__host__ __device__ inline int kkt_group_width(int count) { return count >= 5 ? 8 : count >= 3 ? 4 : count; }
+
+// entry (i, column j) in the products' layout
+__host__ __device__ inline long long kkt_gidx(const long long N, const int n_cols, const int j, const long long i) {
+    const int g = j >> 3;
+    const int rest = n_cols - (g << 3);
+    return (long long)g * 8 * N + i * kkt_group_width(rest < 8 ? rest : 8) + (j & 7);
+}
+
+// doubles per row of the products' layout
+static inline long long kkt_block_width(int n_cols) {
+    return 8LL * (n_cols / 8) + (n_cols % 8 != 0 ? kkt_group_width(n_cols % 8) : 0);
+}
+
+// dst[idx[p]] (column j, products' layout) = val[j][p], and the same into dst_caller ([N][n_cols]) if given
+__global__ __launch_bounds__(256) void kkt_scatter_block(const int n, const long long N, const int n_cols, const long long *__restrict__ idx,
+                                                         const double *__restrict__ val, double *__restrict__ dst,
+                                                         double *__restrict__ dst_caller) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    const int j = blockIdx.y;
+    if (p >= n) return;
+    const long long i = idx[p];
+    const double x = val[(long long)j * n + p];
+    dst[kkt_gidx(N, n_cols, j, i)] = x;
+    if (dst_caller != nullptr) dst_caller[i * n_cols + j] = x;
 }
 
 // ---- right-hand side: b = -P^T (r - L c) ---------------------------------------------------------------------------
-// b[t] = -(r - Lc)[src_of[t]]; the other members of a tied group are added by kkt_rhs_tied, one thread, in index order
-__global__ __launch_bounds__(256) void kkt_rhs(const long long n_free, const int32_t *__restrict__ src_of, const double *__restrict__ r,
-                                               const double *__restrict__ Lc, double *__restrict__ b) {
+// b[j][t] = -(r - Lc)[src_of[t], j] for every column j; the other members of a tied group are added by kkt_rhs_tied
+__global__ __launch_bounds__(256) void kkt_rhs(const long long n_free, const long long N, const int n_cols, const int32_t *__restrict__ src_of,
+                                               const double *__restrict__ r, const double *__restrict__ Lc, double *__restrict__ b) {
     for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < n_free; t += (long long)gridDim.x * 256) {
-        const int32_t i = src_of[t];
-        b[t] = -(Lc != nullptr ? r[i] - Lc[i] : r[i]);
+        const long long i = src_of[t];
+        for (int j = 0; j < n_cols; ++j) {
+            const double ri = r[i * n_cols + j];
+            b[(long long)j * n_free + t] = -(Lc != nullptr ? ri - Lc[kkt_gidx(N, n_cols, j, i)] : ri);
+        }
     }
 }
 
-// One thread per tied GROUP (all further members of one representative): it subtracts its members' terms from the
-// group's reduced row one after the other in ascending member order -- the additions of a single thread walking the whole
-// list in index order (what this kernel was: 0.2 s for 1e5 tied members, a chain of dependent read-modify-writes), in
-// the same order per row, hence the same bits, in parallel over the rows.
-__global__ __launch_bounds__(256) void kkt_rhs_tied(const int n_groups, const int32_t *__restrict__ gptr, const int32_t *__restrict__ order,
+// One thread per tied GROUP (all further members of one representative) and column (blockIdx.y): it subtracts its members'
+// terms from the group's reduced row one after the other in ascending member order -- the additions of a single thread
+// walking the whole list in index order (what this kernel was: 0.2 s for 1e5 tied members, a chain of dependent
+// read-modify-writes), in the same order per row, hence the same bits, in parallel over the rows.
+__global__ __launch_bounds__(256) void kkt_rhs_tied(const int n_groups, const long long n_free, const long long N, const int n_cols,
+                                                    const int32_t *__restrict__ gptr, const int32_t *__restrict__ order,
                                                     const int32_t *__restrict__ member, const int32_t *__restrict__ target,
                                                     const double *__restrict__ r, const double *__restrict__ Lc, double *__restrict__ b) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    const int j = blockIdx.y;
     if (g >= n_groups) return;
     const int e0 = gptr[g], e1 = gptr[g + 1];
+    double *bj = b + (long long)j * n_free;
     const int32_t t = target[order[e0]];
-    double acc = b[t];
+    double acc = bj[t];
     for (int e = e0; e < e1; ++e) {
-        const int32_t i = member[order[e]];
-        acc -= (Lc != nullptr ? r[i] - Lc[i] : r[i]);
+        const long long i = member[order[e]];
+        const double ri = r[i * n_cols + j];
+        acc -= (Lc != nullptr ? ri - Lc[kkt_gidx(N, n_cols, j, i)] : ri);
     }
-    b[t] = acc;
+    bj[t] = acc;
 }
 
 // extra right-hand sides (regulator gain columns): b_k = P^T gamma_k, a handful of entries each, added in list order
@@ -163,19 +203,28 @@ __global__ __launch_bounds__(256) void kkt_fold(const double *__restrict__ parti
     if (threadIdx.x == 0) out[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// ---- expansion: v = c + P y (multipliers zero) ---------------------------------------------------------------------
-__global__ __launch_bounds__(256) void kkt_expand(const long long N, const int32_t *__restrict__ imap, const double *__restrict__ y,
-                                                  const double *__restrict__ c, double *__restrict__ v) {
+// ---- expansion: v = c + P y (multipliers zero), every column (c, v in the products' layout; y: [n_cols][n_free]) ------
+__global__ __launch_bounds__(256) void kkt_expand(const long long N, const int n_cols, const int32_t *__restrict__ imap,
+                                                  const double *__restrict__ y, const long long n_free, const double *__restrict__ c,
+                                                  double *__restrict__ v) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < N; i += (long long)gridDim.x * 256) {
         const int32_t t = imap[i];
-        const double known = c != nullptr ? c[i] : 0.0;
-        v[i] = t >= 0 ? known + y[t] : known;
+        for (int j = 0; j < n_cols; ++j) {
+            const long long g = kkt_gidx(N, n_cols, j, i);
+            const double known = c != nullptr ? c[g] : 0.0;
+            v[g] = t >= 0 ? known + y[(long long)j * n_free + t] : known;
+        }
     }
 }
 
-// w = r - w  (w holds L v on entry): the KCL residual rows of the multiplier recovery
-__global__ __launch_bounds__(256) void kkt_rho(const long long N, const double *__restrict__ r, double *__restrict__ w) {
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < N; i += (long long)gridDim.x * 256) w[i] = r[i] - w[i];
+// out[j][p] = (r - L v)[idx[p], j]: the KCL residual rows of the multiplier recovery, at the probed unknowns only
+__global__ __launch_bounds__(256) void kkt_rho_probe(const int n_probe, const long long N, const int n_cols, const long long *__restrict__ idx,
+                                                     const double *__restrict__ r, const double *__restrict__ Lv, double *__restrict__ out) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    const int j = blockIdx.y;
+    if (p >= n_probe) return;
+    const long long i = idx[p];
+    out[(long long)j * n_probe + p] = r[i * n_cols + j] - Lv[kkt_gidx(N, n_cols, j, i)];
 }
 
 __global__ void kkt_gather_f64(const int n, const long long *__restrict__ idx, const double *__restrict__ src, double *__restrict__ dst) {
@@ -183,29 +232,35 @@ __global__ void kkt_gather_f64(const int n, const long long *__restrict__ idx, c
     if (k < n) dst[k] = src[idx[k]];
 }
 
-// v += sum_k coeff[k] Z_k
-__global__ __launch_bounds__(256) void kkt_add_extras(const long long N, const int n_extra, const double *__restrict__ coeff,
-                                                      const double *__restrict__ Z, double *__restrict__ v) {
+// v[:, j] += sum_k coeff[j][k] Z_k for every column j (Z_k shared by all columns), and the result also into v_caller
+// ([N][n_cols]) if given
+__global__ __launch_bounds__(256) void kkt_add_extras(const long long N, const int n_cols, const int n_extra, const double *__restrict__ coeff,
+                                                      const double *__restrict__ Z, double *__restrict__ v, double *__restrict__ v_caller) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < N; i += (long long)gridDim.x * 256) {
-        double s = v[i];
-        for (int k = 0; k < n_extra; ++k) s += coeff[k] * Z[(long long)k * N + i];
-        v[i] = s;
+        for (int j = 0; j < n_cols; ++j) {
+            const long long g = kkt_gidx(N, n_cols, j, i);
+            double s = v[g];
+            for (int k = 0; k < n_extra; ++k) s += coeff[(long long)j * n_extra + k] * Z[(long long)k * N + i];
+            v[g] = s;
+            if (v_caller != nullptr) v_caller[i * n_cols + j] = s;
+        }
     }
 }
 
-// per-workgroup partial sums of (a - b)^2
-__global__ __launch_bounds__(256) void kkt_diff2(const long long n, const double *__restrict__ a, const double *__restrict__ b,
-                                                 double *__restrict__ partials) {
+// per-workgroup partial sums of (Lv - r)^2 of column blockIdx.y (Lv in the products' layout, r in the caller's)
+__global__ __launch_bounds__(256) void kkt_diff2(const long long N, const int n_cols, const double *__restrict__ Lv,
+                                                 const double *__restrict__ r, double *__restrict__ partials) {
     __shared__ double red[4];
+    const int j = blockIdx.y;
     double s = 0.0;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const double d = a[i] - b[i];
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < N; i += (long long)gridDim.x * 256) {
+        const double d = Lv[kkt_gidx(N, n_cols, j, i)] - r[i * n_cols + j];
         s += d * d;
     }
     for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
-    if (threadIdx.x == 0) partials[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    if (threadIdx.x == 0) partials[(long long)j * kMaxPartials + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
 // ---- locality ordering of the reduced unknowns ("Ordering") ----------------------------------------
@@ -600,14 +655,28 @@ extern "C" int padne_kkt_matrix(const padne_kkt *k, const padne_csr **reduced_ou
     return PADNE_OK;
 }
 
-extern "C" int padne_kkt_solve(padne_ctx *ctx, padne_kkt *k, const double *r_host, int64_t n_known, const int64_t *known_idx,
-                               const double *known_val, int32_t n_extra, const int64_t *extra_ptr, const int64_t *extra_row,
-                               const double *extra_val, int64_t n_probe, const int64_t *probe_idx, double *probe_out,
-                               const padne_solve_opts *opts, double abs_residual_target, padne_solve_info *info) {
+// y = L x for n_cols vectors in the products' layout: one pass over L per group of up to 8 columns (SpMM of width 8 / 4 / 2,
+// a single column SpMV -- for n_cols = 1 the product of the vector path)
+static int kkt_products(padne_ctx *ctx, const padne_kkt *k, const int n_cols, const double *x, double *y) {
+    for (int first = 0; first < n_cols; first += 8) {
+        const int w = kkt_group_width(std::min(8, n_cols - first));
+        const long long off = (long long)first * k->N;
+        if (w == 1) PADNE_TRY(launch_spmv(ctx, k->L, x + off, y + off, nullptr, nullptr, nullptr));
+        else PADNE_TRY((launch_spmm<double, double>(ctx, k->L, w, SPMV_PLAIN, x + off, y + off, {})));
+    }
+    return PADNE_OK;
+}
+
+// Stage 1 for a block of n_cols right-hand sides (n_cols = 1: padne_kkt_solve)
+static int kkt_solve_block(padne_ctx *ctx, padne_kkt *k, const int n_cols, const double *r_host, int64_t n_known,
+                           const int64_t *known_idx, const double *known_val, int32_t n_extra, const int64_t *extra_ptr,
+                           const int64_t *extra_row, const double *extra_val, int64_t n_probe, const int64_t *probe_idx,
+                           double *probe_out, const padne_solve_opts *opts, double abs_residual_target, padne_solve_info *info) {
     PADNE_REQUIRE(ctx && k && r_host && opts, "null argument");
     PADNE_REQUIRE(k->ctx == ctx, "the plan belongs to another context");
+    PADNE_REQUIRE(n_cols >= 1 && n_extra >= 0 && n_cols + n_extra <= 4096, "at most 4096 right-hand sides with the extra ones");
     PADNE_REQUIRE(n_known >= 0 && (n_known == 0 || (known_idx && known_val)), "known potentials");
-    PADNE_REQUIRE(n_extra >= 0 && n_extra <= 4096 && (n_extra == 0 || (extra_ptr && extra_ptr[0] == 0)), "extra right-hand sides");
+    PADNE_REQUIRE(n_extra == 0 || (extra_ptr && extra_ptr[0] == 0), "extra right-hand sides");
     PADNE_REQUIRE(n_probe >= 0 && (n_probe == 0 || (probe_idx && probe_out)), "probes");
     const long long N = k->N, nf = k->n_free;
     for (int64_t j = 0; j < n_known; ++j) PADNE_REQUIRE(known_idx[j] >= 0 && known_idx[j] < k->n_pot, "known potential out of range");
@@ -620,29 +689,47 @@ extern "C" int padne_kkt_solve(padne_ctx *ctx, padne_kkt *k, const double *r_hos
     hipStream_t s = ctx->stream;
     padne_solve_info local;
     memset(&local, 0, sizeof(local));
-    local.n_rhs = 1 + n_extra;
+    const int n_rhs = n_cols + n_extra;      // reduced columns: the block's, then the regulators' (solved once per block)
+    local.n_rhs = n_rhs;
     k->solved = false;
+    k->n_cols = n_cols;
     k->n_extra = n_extra;
-    // more right-hand sides than last time: grow b, y, Z
-    if (n_extra > k->n_extra_cap) {
-        PADNE_HIP_CHECK(hipStreamSynchronize(s));
-        pool_free(ctx, k->b);
-        pool_free(ctx, k->y);
-        pool_free(ctx, k->Z);
-        k->b = k->y = k->Z = nullptr;
-        const size_t nF = (size_t)(nf > 0 ? nf : 1) * (size_t)(1 + n_extra);
-        k->b = (double *)pool_alloc(ctx, sizeof(double) * nF);
-        k->y = (double *)pool_alloc(ctx, sizeof(double) * nF);
-        k->Z = (double *)pool_alloc(ctx, sizeof(double) * (size_t)(N > 0 ? N : 1) * (size_t)n_extra);
-        if (!k->b || !k->y || !k->Z) return PADNE_E_NOMEM;
-        k->n_extra_cap = n_extra;
+    // a wider block or more right-hand sides than last time: grow the N-vectors, b and y, Z (none of them is in flight: the
+    // copy streams were synchronised when their last transfer ended)
+    const long long width = kkt_block_width(n_cols);
+    const size_t nN = (size_t)(N > 0 ? N : 1), nF = (size_t)(nf > 0 ? nf : 1);
+    if (width > k->vec_cap || n_rhs > k->rhs_cap || n_extra > k->z_cap) PADNE_HIP_CHECK(hipStreamSynchronize(s));
+    if (width > k->vec_cap) {
+        for (double **p : {&k->r, &k->v, &k->w, &k->c}) {
+            pool_free(ctx, *p);
+            *p = (double *)pool_alloc(ctx, sizeof(double) * nN * (size_t)width);
+        }
+        k->vec_cap = 0;
+        if (!k->r || !k->v || !k->w || !k->c) return PADNE_E_NOMEM;
+        k->vec_cap = width;
     }
-    // 1. r crosses PCIe on its own streams while this thread builds what does not depend on it: 1/diag, the x-window
-    //    plan and the multigrid hierarchy of A (the counterpart of the factorisation)
+    if (n_rhs > k->rhs_cap) {
+        for (double **p : {&k->b, &k->y}) {
+            pool_free(ctx, *p);
+            *p = (double *)pool_alloc(ctx, sizeof(double) * nF * (size_t)n_rhs);
+        }
+        k->rhs_cap = 0;
+        if (!k->b || !k->y) return PADNE_E_NOMEM;
+        k->rhs_cap = n_rhs;
+    }
+    if (n_extra > k->z_cap) {
+        pool_free(ctx, k->Z);
+        k->Z = (double *)pool_alloc(ctx, sizeof(double) * nN * (size_t)n_extra);
+        k->z_cap = 0;
+        if (!k->Z) return PADNE_E_NOMEM;
+        k->z_cap = n_extra;
+    }
+    // 1. R crosses PCIe on its own streams, in the caller's layout, while this thread builds what does not depend on it:
+    //    1/diag, the x-window plan and the multigrid hierarchy of A (the counterpart of the factorisation)
     int up_rc = PADNE_OK;
     std::thread uploader([&]() {
         (void)hipSetDevice(ctx->device);
-        up_rc = parallel_copy(k, k->r, r_host, sizeof(double) * (size_t)N, hipMemcpyHostToDevice);
+        up_rc = parallel_copy(k, k->r, r_host, sizeof(double) * (size_t)N * (size_t)n_cols, hipMemcpyHostToDevice);
     });
     struct Join {
         std::thread &t;
@@ -664,6 +751,10 @@ extern "C" int padne_kkt_solve(padne_ctx *ctx, padne_kkt *k, const double *r_hos
         }
     }
     k->setup_seconds_last = setup_s;
+    auto products = [&](const double *x, double *y) { return kkt_products(ctx, k, n_cols, x, y); };
+    // the spare columns of a widened last group: zero where the products read them
+    const int last = n_cols - ((n_cols - 1) / 8) * 8, last_w = kkt_group_width(last);
+    const long long last_off = (long long)((n_cols - 1) / 8) * 8 * N;
     // known part of the potentials: c (zero unless sources fix potentials against the ground or against each other)
     Scratch sc(ctx);
     k->has_c = n_known > 0;
@@ -671,26 +762,27 @@ extern "C" int padne_kkt_solve(padne_ctx *ctx, padne_kkt *k, const double *r_hos
         long long *d_idx = nullptr;
         double *d_val = nullptr;
         PADNE_TRY(sc.alloc(&d_idx, (size_t)n_known));
-        PADNE_TRY(sc.alloc(&d_val, (size_t)n_known));
-        PADNE_HIP_CHECK(hipMemsetAsync(k->c, 0, sizeof(double) * (size_t)N, s));
+        PADNE_TRY(sc.alloc(&d_val, (size_t)n_known * (size_t)n_cols));
+        PADNE_HIP_CHECK(hipMemsetAsync(k->c, 0, sizeof(double) * (size_t)N * (size_t)width, s));
         PADNE_HIP_CHECK(hipMemcpyAsync(d_idx, known_idx, sizeof(long long) * (size_t)n_known, hipMemcpyHostToDevice, s));
-        PADNE_HIP_CHECK(hipMemcpyAsync(d_val, known_val, sizeof(double) * (size_t)n_known, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(kkt_scatter_f64, dim3(nblk(n_known)), dim3(256), 0, s, (int)n_known, d_idx, d_val, k->c);
+        PADNE_HIP_CHECK(hipMemcpyAsync(d_val, known_val, sizeof(double) * (size_t)n_known * (size_t)n_cols, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(kkt_scatter_block, dim3(nblk(n_known), n_cols), dim3(256), 0, s, (int)n_known, N, n_cols, d_idx, d_val,
+                           k->c, (double *)nullptr);
         PADNE_HIP_CHECK(hipGetLastError());
         PADNE_TRY(csr_build_xw_plan(ctx, const_cast<padne_csr *>(k->L)));
-        PADNE_TRY(launch_spmv(ctx, k->L, k->c, k->w, nullptr, nullptr, nullptr));       // w = L c
+        PADNE_TRY(products(k->c, k->w));                                                 // w = L c
     }
     uploader.join();
     PADNE_TRY(up_rc);
-    // 2. b = -P^T (r - L c), the extra right-hand sides, their norms
+    // 2. b = -P^T (r - L c) for every column, the extra right-hand sides, their norms
     const double *Lc = k->has_c ? k->w : nullptr;
-    std::vector<double> norm2_buf((size_t)n_extra + 8, 0.0);      // (one per right-hand side: any number of regulators)
+    std::vector<double> norm2_buf((size_t)n_rhs + 8, 0.0);        // (one per right-hand side: any number of them)
     double *h_norm2 = norm2_buf.data();
     if (nf > 0) {
-        hipLaunchKernelGGL(kkt_rhs, dim3(vgrid(nf)), dim3(256), 0, s, nf, k->src_of, k->r, Lc, k->b);
+        hipLaunchKernelGGL(kkt_rhs, dim3(vgrid(nf)), dim3(256), 0, s, nf, N, n_cols, k->src_of, k->r, Lc, k->b);
         if (k->n_tied > 0)
-            hipLaunchKernelGGL(kkt_rhs_tied, dim3(nblk(k->n_tied_groups)), dim3(256), 0, s, (int)k->n_tied_groups, k->tied_gptr,
-                               k->tied_order, k->tied_member, k->tied_target, k->r, Lc, k->b);
+            hipLaunchKernelGGL(kkt_rhs_tied, dim3(nblk(k->n_tied_groups), n_cols), dim3(256), 0, s, (int)k->n_tied_groups, nf, N,
+                               n_cols, k->tied_gptr, k->tied_order, k->tied_member, k->tied_target, k->r, Lc, k->b);
         PADNE_HIP_CHECK(hipGetLastError());
         if (n_extra > 0) {
             long long *d_ptr = nullptr, *d_row = nullptr;
@@ -698,19 +790,20 @@ extern "C" int padne_kkt_solve(padne_ctx *ctx, padne_kkt *k, const double *r_hos
             PADNE_TRY(sc.alloc(&d_ptr, (size_t)n_extra + 1));
             PADNE_TRY(sc.alloc(&d_row, (size_t)n_ex_entries));
             PADNE_TRY(sc.alloc(&d_val, (size_t)n_ex_entries));
-            PADNE_HIP_CHECK(hipMemsetAsync(k->b + nf, 0, sizeof(double) * (size_t)nf * (size_t)n_extra, s));
+            PADNE_HIP_CHECK(hipMemsetAsync(k->b + (long long)n_cols * nf, 0, sizeof(double) * (size_t)nf * (size_t)n_extra, s));
             PADNE_HIP_CHECK(hipMemcpyAsync(d_ptr, extra_ptr, sizeof(long long) * (size_t)(n_extra + 1), hipMemcpyHostToDevice, s));
             if (n_ex_entries > 0) {
                 PADNE_HIP_CHECK(hipMemcpyAsync(d_row, extra_row, sizeof(long long) * (size_t)n_ex_entries, hipMemcpyHostToDevice, s));
                 PADNE_HIP_CHECK(hipMemcpyAsync(d_val, extra_val, sizeof(double) * (size_t)n_ex_entries, hipMemcpyHostToDevice, s));
             }
-            hipLaunchKernelGGL(kkt_rhs_extra, dim3(1), dim3(1), 0, s, (int)n_extra, d_ptr, d_row, d_val, k->imap, nf, k->b + nf);
+            hipLaunchKernelGGL(kkt_rhs_extra, dim3(1), dim3(1), 0, s, (int)n_extra, d_ptr, d_row, d_val, k->imap, nf,
+                               k->b + (long long)n_cols * nf);
             PADNE_HIP_CHECK(hipGetLastError());
         }
         // norms of all right-hand sides (the tolerance rule below; zero right-hand sides are not solved for)
         const int g = vgrid(nf);
-        for (int first = 0; first < 1 + n_extra; first += 8) {
-            const int cnt = std::min(8, 1 + n_extra - first);
+        for (int first = 0; first < n_rhs; first += 8) {
+            const int cnt = std::min(8, n_rhs - first);
             hipLaunchKernelGGL(kkt_norm2, dim3(g, cnt), dim3(256), 0, s, nf, k->b + (long long)first * nf, ctx->partials);
             hipLaunchKernelGGL(kkt_fold, dim3(cnt), dim3(256), 0, s, ctx->partials, g, ctx->scalars + 32);
             PADNE_HIP_CHECK(hipGetLastError());
@@ -724,70 +817,96 @@ extern "C" int padne_kkt_solve(padne_ctx *ctx, padne_kkt *k, const double *r_hos
         }
     }
     // 3. the reference judges a solve by the ABSOLUTE residual of the whole system (tests/test_solver.py:2083-2089): when
-    //    rtol ||b|| is looser than the target the relative tolerance is tightened (never below what binary64 resolves)
+    //    rtol ||b|| is looser than the target the relative tolerance is tightened (never below what binary64 resolves); one
+    //    tolerance for all columns, the tightest any of them needs
     double norm_max = 0.0;
-    for (int j = 0; j < 1 + n_extra; ++j) norm_max = std::max(norm_max, sqrt(h_norm2[j]));
+    for (int j = 0; j < n_rhs; ++j) norm_max = std::max(norm_max, sqrt(h_norm2[j]));
     padne_solve_opts o = *opts;
     o.flags &= ~(1 | 4);                     // x0 = 0; the hierarchy was (re)built above
     if (abs_residual_target > 0.0 && norm_max > 0.0 && o.rtol * norm_max > abs_residual_target)
         o.rtol = std::max(abs_residual_target / norm_max, 2e-15);
-    // right-hand sides that vanish are not solved for; the live ones are packed to the front (they already are unless a
-    // regulator's gain column projects to zero)
+    // right-hand sides that vanish are not solved for (y stays zero there)
     int rc_solve = PADNE_OK;
+    auto solve_run = [&](const double *bb, double *yy, int cnt) -> int {
+        padne_solve_info part;
+        memset(&part, 0, sizeof(part));
+        const int rc = padne_solve_spd_dev(ctx, k->A, bb, yy, cnt, &o, &part);
+        if (rc != PADNE_OK && rc != PADNE_E_NOTCONVERGED) return rc;
+        if (rc != PADNE_OK) rc_solve = rc;
+        local.iterations += part.iterations;
+        local.restarts += part.restarts;
+        local.rel_residual = std::max(local.rel_residual, part.rel_residual);
+        local.abs_residual = std::max(local.abs_residual, part.abs_residual);
+        local.solve_seconds += part.solve_seconds;
+        local.spmv_seconds = std::max(local.spmv_seconds, part.spmv_seconds);
+        local.precond_fallbacks += part.precond_fallbacks;
+        local.levels = part.levels;
+        local.operator_complexity = part.operator_complexity;
+        if (part.status != PADNE_OK) local.status = part.status;
+        return PADNE_OK;
+    };
     if (nf > 0) {
-        PADNE_HIP_CHECK(hipMemsetAsync(k->y, 0, sizeof(double) * (size_t)nf * (size_t)(1 + n_extra), s));
-        int j = 0;
-        while (j < 1 + n_extra) {
-            if (!(h_norm2[j] > 0.0)) {
-                ++j;
-                continue;
+        PADNE_HIP_CHECK(hipMemsetAsync(k->y, 0, sizeof(double) * (size_t)nf * (size_t)n_rhs, s));
+        std::vector<int> live;
+        for (int j = 0; j < n_rhs; ++j)
+            if (h_norm2[j] > 0.0) live.push_back(j);
+        const bool gaps = !live.empty() && live.back() - live.front() + 1 != (int)live.size();
+        if (n_cols > 1 && gaps) {
+            // a block with zero columns among live ones: the live columns are packed, so that the lockstep grouping sees
+            // all of them together, and their solutions are put back in place
+            const int n_live = (int)live.size();
+            double *bp = nullptr, *yp = nullptr;
+            PADNE_TRY(sc.alloc(&bp, (size_t)n_live * (size_t)nf));
+            PADNE_TRY(sc.alloc(&yp, (size_t)n_live * (size_t)nf));
+            for (int q = 0; q < n_live; ++q)
+                PADNE_HIP_CHECK(hipMemcpyAsync(bp + (long long)q * nf, k->b + (long long)live[q] * nf, sizeof(double) * (size_t)nf,
+                                               hipMemcpyDeviceToDevice, s));
+            PADNE_TRY(solve_run(bp, yp, n_live));
+            for (int q = 0; q < n_live; ++q)
+                PADNE_HIP_CHECK(hipMemcpyAsync(k->y + (long long)live[q] * nf, yp + (long long)q * nf, sizeof(double) * (size_t)nf,
+                                               hipMemcpyDeviceToDevice, s));
+        } else {
+            // runs of live right-hand sides, one call each (they are one run unless a regulator's gain column projects to zero)
+            int j = 0;
+            while (j < n_rhs) {
+                if (!(h_norm2[j] > 0.0)) {
+                    ++j;
+                    continue;
+                }
+                int j1 = j;
+                while (j1 < n_rhs && h_norm2[j1] > 0.0) ++j1;
+                PADNE_TRY(solve_run(k->b + (long long)j * nf, k->y + (long long)j * nf, j1 - j));
+                j = j1;
             }
-            int j1 = j;
-            while (j1 < 1 + n_extra && h_norm2[j1] > 0.0) ++j1;        // a run of live right-hand sides: one call
-            padne_solve_info part;
-            memset(&part, 0, sizeof(part));
-            const int rc = padne_solve_spd_dev(ctx, k->A, k->b + (long long)j * nf, k->y + (long long)j * nf, j1 - j, &o, &part);
-            if (rc != PADNE_OK && rc != PADNE_E_NOTCONVERGED) return rc;
-            if (rc != PADNE_OK) rc_solve = rc;
-            local.iterations += part.iterations;
-            local.restarts += part.restarts;
-            local.rel_residual = std::max(local.rel_residual, part.rel_residual);
-            local.abs_residual = std::max(local.abs_residual, part.abs_residual);
-            local.solve_seconds += part.solve_seconds;
-            local.spmv_seconds = std::max(local.spmv_seconds, part.spmv_seconds);
-            local.precond_fallbacks += part.precond_fallbacks;
-            local.levels = part.levels;
-            local.operator_complexity = part.operator_complexity;
-            if (part.status != PADNE_OK) local.status = part.status;
-            j = j1;
         }
     }
     local.precond_setup_seconds = setup_s;
-    // 4. v = c + P y (multipliers still zero), Z_k = P z_k, and the KCL residual rows the host peels the multipliers from
+    // 4. v = c + P y (multipliers still zero), Z_k = P z_k (once per block), and the KCL residual rows the host peels the
+    //    multipliers from
     const double *c = k->has_c ? k->c : nullptr;
-    hipLaunchKernelGGL(kkt_expand, dim3(vgrid(N)), dim3(256), 0, s, N, k->imap, k->y, c, k->v);
+    if (last_w > last) PADNE_HIP_CHECK(hipMemsetAsync(k->v + last_off, 0, sizeof(double) * (size_t)N * (size_t)last_w, s));
+    hipLaunchKernelGGL(kkt_expand, dim3(vgrid(N)), dim3(256), 0, s, N, n_cols, k->imap, k->y, nf, c, k->v);
     for (int j = 0; j < n_extra; ++j)
-        hipLaunchKernelGGL(kkt_expand, dim3(vgrid(N)), dim3(256), 0, s, N, k->imap, k->y + (long long)(1 + j) * nf,
+        hipLaunchKernelGGL(kkt_expand, dim3(vgrid(N)), dim3(256), 0, s, N, 1, k->imap, k->y + (long long)(n_cols + j) * nf, nf,
                            (const double *)nullptr, k->Z + (long long)j * N);
     PADNE_HIP_CHECK(hipGetLastError());
     if (n_probe > 0) {
         long long *d_idx = nullptr;
         double *d_out = nullptr;
         PADNE_TRY(sc.alloc(&d_idx, (size_t)n_probe));
-        PADNE_TRY(sc.alloc(&d_out, (size_t)n_probe * (size_t)(1 + n_extra)));
+        PADNE_TRY(sc.alloc(&d_out, (size_t)n_probe * (size_t)n_rhs));
         PADNE_HIP_CHECK(hipMemcpyAsync(d_idx, probe_idx, sizeof(long long) * (size_t)n_probe, hipMemcpyHostToDevice, s));
         PADNE_TRY(csr_build_xw_plan(ctx, const_cast<padne_csr *>(k->L)));
-        PADNE_TRY(launch_spmv(ctx, k->L, k->v, k->w, nullptr, nullptr, nullptr));
-        hipLaunchKernelGGL(kkt_rho, dim3(vgrid(N)), dim3(256), 0, s, N, k->r, k->w);                    // rho = r - L v
-        hipLaunchKernelGGL(kkt_gather_f64, dim3(nblk(n_probe)), dim3(256), 0, s, (int)n_probe, d_idx, k->w, d_out);
+        PADNE_TRY(products(k->v, k->w));                                                               // L v
+        hipLaunchKernelGGL(kkt_rho_probe, dim3(nblk(n_probe), n_cols), dim3(256), 0, s, (int)n_probe, N, n_cols, d_idx, k->r, k->w,
+                           d_out);                                                                     // rho = r - L v
         for (int j = 0; j < n_extra; ++j) {
             PADNE_TRY(launch_spmv(ctx, k->L, k->Z + (long long)j * N, k->w, nullptr, nullptr, nullptr));  // L Z_k
             hipLaunchKernelGGL(kkt_gather_f64, dim3(nblk(n_probe)), dim3(256), 0, s, (int)n_probe, d_idx, k->w,
-                               d_out + (size_t)(1 + j) * (size_t)n_probe);
+                               d_out + (size_t)(n_cols + j) * (size_t)n_probe);
         }
         PADNE_HIP_CHECK(hipGetLastError());
-        PADNE_HIP_CHECK(hipMemcpyAsync(probe_out, d_out, sizeof(double) * (size_t)n_probe * (size_t)(1 + n_extra),
-                                       hipMemcpyDeviceToHost, s));
+        PADNE_HIP_CHECK(hipMemcpyAsync(probe_out, d_out, sizeof(double) * (size_t)n_probe * (size_t)n_rhs, hipMemcpyDeviceToHost, s));
     }
     PADNE_HIP_CHECK(hipStreamSynchronize(s));
     k->solved = true;
@@ -795,10 +914,13 @@ extern "C" int padne_kkt_solve(padne_ctx *ctx, padne_kkt *k, const double *r_hos
     return rc_solve;
 }
 
-extern "C" int padne_kkt_finish(padne_ctx *ctx, padne_kkt *k, int32_t n_extra, const double *extra_coeff, int64_t n_mult,
-                                const int64_t *mult_idx, const double *mult_val, double *v_host, double *residual_norm_out) {
-    PADNE_REQUIRE(ctx && k && v_host && residual_norm_out, "null argument");
+// Stage 2 for the block of the last stage 1
+static int kkt_finish_block(padne_ctx *ctx, padne_kkt *k, const int n_cols, int32_t n_extra, const double *extra_coeff,
+                            int64_t n_mult, const int64_t *mult_idx, const double *mult_val, double *v_host,
+                            double *residual_norms_out) {
+    PADNE_REQUIRE(ctx && k && v_host && residual_norms_out, "null argument");
     PADNE_REQUIRE(k->ctx == ctx && k->solved, "padne_kkt_finish follows padne_kkt_solve on the same plan");
+    PADNE_REQUIRE(n_cols == k->n_cols, "as many columns as the solve had");
     PADNE_REQUIRE(n_extra == k->n_extra && (n_extra == 0 || extra_coeff), "one coefficient per extra right-hand side");
     PADNE_REQUIRE(n_mult >= 0 && (n_mult == 0 || (mult_idx && mult_val)), "multipliers");
     const long long N = k->N;
@@ -806,47 +928,87 @@ extern "C" int padne_kkt_finish(padne_ctx *ctx, padne_kkt *k, int32_t n_extra, c
     PADNE_HIP_CHECK(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     Scratch sc(ctx);
-    if (n_extra > 0) {
+    // the result travels home in the caller's layout: when the products' layout differs it is written to c (free now) as well
+    const bool same_layout = kkt_block_width(n_cols) == n_cols && n_cols <= 8;
+    double *v_out = same_layout ? k->v : k->c;
+    double *v_caller = same_layout ? nullptr : k->c;
+    if (n_extra > 0 || !same_layout) {
         double *d_coeff = nullptr;
-        PADNE_TRY(sc.alloc(&d_coeff, (size_t)n_extra));
-        PADNE_HIP_CHECK(hipMemcpyAsync(d_coeff, extra_coeff, sizeof(double) * (size_t)n_extra, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(kkt_add_extras, dim3(vgrid(N)), dim3(256), 0, s, N, (int)n_extra, d_coeff, k->Z, k->v);
+        if (n_extra > 0) {
+            PADNE_TRY(sc.alloc(&d_coeff, (size_t)n_extra * (size_t)n_cols));
+            PADNE_HIP_CHECK(hipMemcpyAsync(d_coeff, extra_coeff, sizeof(double) * (size_t)n_extra * (size_t)n_cols,
+                                           hipMemcpyHostToDevice, s));
+        }
+        hipLaunchKernelGGL(kkt_add_extras, dim3(vgrid(N)), dim3(256), 0, s, N, n_cols, (int)n_extra, (const double *)d_coeff, k->Z,
+                           k->v, v_caller);
         PADNE_HIP_CHECK(hipGetLastError());
     }
     if (n_mult > 0) {
         long long *d_idx = nullptr;
         double *d_val = nullptr;
         PADNE_TRY(sc.alloc(&d_idx, (size_t)n_mult));
-        PADNE_TRY(sc.alloc(&d_val, (size_t)n_mult));
+        PADNE_TRY(sc.alloc(&d_val, (size_t)n_mult * (size_t)n_cols));
         PADNE_HIP_CHECK(hipMemcpyAsync(d_idx, mult_idx, sizeof(long long) * (size_t)n_mult, hipMemcpyHostToDevice, s));
-        PADNE_HIP_CHECK(hipMemcpyAsync(d_val, mult_val, sizeof(double) * (size_t)n_mult, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(kkt_scatter_f64, dim3(nblk(n_mult)), dim3(256), 0, s, (int)n_mult, d_idx, d_val, k->v);
+        PADNE_HIP_CHECK(hipMemcpyAsync(d_val, mult_val, sizeof(double) * (size_t)n_mult * (size_t)n_cols, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(kkt_scatter_block, dim3(nblk(n_mult), n_cols), dim3(256), 0, s, (int)n_mult, N, n_cols, d_idx, d_val, k->v,
+                           v_caller);
         PADNE_HIP_CHECK(hipGetLastError());
     }
-    // v is final: it travels home on the copy streams while the main stream evaluates ||L v - r|| (solver.py:775)
+    // V is final: it travels home on the copy streams while the main stream evaluates ||L v_j - r_j|| (solver.py:775)
     PADNE_HIP_CHECK(hipStreamSynchronize(s));
     int down_rc = PADNE_OK;
     std::thread downloader([&]() {
         (void)hipSetDevice(ctx->device);
-        down_rc = parallel_copy(k, v_host, k->v, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost);
+        down_rc = parallel_copy(k, v_host, v_out, sizeof(double) * (size_t)N * (size_t)n_cols, hipMemcpyDeviceToHost);
     });
     struct Join {
         std::thread &t;
         ~Join() { if (t.joinable()) t.join(); }
     } join_guard{downloader};
-    double norm2 = 0.0;
+    std::vector<double> norm2((size_t)n_cols, 0.0);
     if (N > 0) {
+        double *d_part = nullptr, *d_norm2 = nullptr;
+        PADNE_TRY(sc.alloc(&d_part, (size_t)n_cols * kMaxPartials));
+        PADNE_TRY(sc.alloc(&d_norm2, (size_t)n_cols));
         PADNE_TRY(csr_build_xw_plan(ctx, const_cast<padne_csr *>(k->L)));
-        PADNE_TRY(launch_spmv(ctx, k->L, k->v, k->w, nullptr, nullptr, nullptr));
+        PADNE_TRY(kkt_products(ctx, k, n_cols, k->v, k->w));      // L v
         const int g = vgrid(N);
-        hipLaunchKernelGGL(kkt_diff2, dim3(g), dim3(256), 0, s, N, k->w, k->r, ctx->partials);
-        hipLaunchKernelGGL(kkt_fold, dim3(1), dim3(256), 0, s, ctx->partials, g, ctx->scalars + 32);
+        hipLaunchKernelGGL(kkt_diff2, dim3(g, n_cols), dim3(256), 0, s, N, n_cols, k->w, k->r, d_part);
+        hipLaunchKernelGGL(kkt_fold, dim3(n_cols), dim3(256), 0, s, d_part, g, d_norm2);
         PADNE_HIP_CHECK(hipGetLastError());
-        PADNE_TRY(read_back(ctx, ctx->scalars + 32, sizeof(double), &norm2));
+        PADNE_TRY(read_back(ctx, d_norm2, sizeof(double) * (size_t)n_cols, norm2.data()));
     }
     downloader.join();
     PADNE_TRY(down_rc);
-    *residual_norm_out = sqrt(norm2);
+    for (int j = 0; j < n_cols; ++j) residual_norms_out[j] = sqrt(norm2[(size_t)j]);
     k->solved = false;
     return PADNE_OK;
+}
+
+extern "C" int padne_kkt_solve(padne_ctx *ctx, padne_kkt *k, const double *r_host, int64_t n_known, const int64_t *known_idx,
+                               const double *known_val, int32_t n_extra, const int64_t *extra_ptr, const int64_t *extra_row,
+                               const double *extra_val, int64_t n_probe, const int64_t *probe_idx, double *probe_out,
+                               const padne_solve_opts *opts, double abs_residual_target, padne_solve_info *info) {
+    return kkt_solve_block(ctx, k, 1, r_host, n_known, known_idx, known_val, n_extra, extra_ptr, extra_row, extra_val, n_probe,
+                           probe_idx, probe_out, opts, abs_residual_target, info);
+}
+
+extern "C" int padne_kkt_solve_block(padne_ctx *ctx, padne_kkt *k, int32_t n_cols, const double *r_host, int64_t n_known,
+                                     const int64_t *known_idx, const double *known_val, int32_t n_extra, const int64_t *extra_ptr,
+                                     const int64_t *extra_row, const double *extra_val, int64_t n_probe, const int64_t *probe_idx,
+                                     double *probe_out, const padne_solve_opts *opts, double abs_residual_target,
+                                     padne_solve_info *info) {
+    return kkt_solve_block(ctx, k, n_cols, r_host, n_known, known_idx, known_val, n_extra, extra_ptr, extra_row, extra_val, n_probe,
+                           probe_idx, probe_out, opts, abs_residual_target, info);
+}
+
+extern "C" int padne_kkt_finish(padne_ctx *ctx, padne_kkt *k, int32_t n_extra, const double *extra_coeff, int64_t n_mult,
+                                const int64_t *mult_idx, const double *mult_val, double *v_host, double *residual_norm_out) {
+    return kkt_finish_block(ctx, k, 1, n_extra, extra_coeff, n_mult, mult_idx, mult_val, v_host, residual_norm_out);
+}
+
+extern "C" int padne_kkt_finish_block(padne_ctx *ctx, padne_kkt *k, int32_t n_cols, int32_t n_extra, const double *extra_coeff,
+                                      int64_t n_mult, const int64_t *mult_idx, const double *mult_val, double *v_host,
+                                      double *residual_norms_out) {
+    return kkt_finish_block(ctx, k, n_cols, n_extra, extra_coeff, n_mult, mult_idx, mult_val, v_host, residual_norms_out);
 }

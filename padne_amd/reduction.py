@@ -352,7 +352,38 @@ def build_reduction(layout: KKTLayout, pins: list | None = None) -> Reduction:
     see :func:`floating_component_pins`) that are held at 0 V like a second ground.  The reference's matrix is
     singular there (its LU returns whatever the rounding leaves); a pin makes the component's block definite, and the
     current it carries is the component's net injected current (reported in ``Reduction.pin_currents``)."""
+    return _build_reduction(layout, pins, None)
+
+
+def build_block_reduction(layout: KKTLayout, values: dict, pins: list | None = None):
+    """The reduction of a block of k right-hand sides that share ``layout``'s structure: ``values`` {constraint index:
+    array (k,)} are the constraint values of every column (``r[index, :]``).  What is eliminated, tied, grouped, the
+    regulators and the pins do not depend on the values, so they are worked out once; the known parts c are carried
+    through the same union-find as arrays, elementwise the very operations :func:`build_reduction` does on one column.
+
+    Returns ``(red, known_idx, known_val)``: ``red`` the structure (its ``known`` is empty), ``known_idx`` int64 [n_known]
+    the union over the columns of the unknowns with a non-zero known part, ascending, and ``known_val`` float64
+    (k, n_known), zero where a column knows nothing."""
+    vals = {int(i): np.asarray(v, dtype=np.float64).reshape(-1) for i, v in values.items()}
+    k = len(next(iter(vals.values()))) if vals else 1
+    red = _build_reduction(layout, pins, vals)
+    known_idx = np.asarray(sorted(red.known), dtype=np.int64)
+    known_val = np.zeros((k, len(known_idx)), dtype=np.float64)
+    for q, x in enumerate(known_idx.tolist()):
+        known_val[:, q] = red.known[x]
+    red.known = {}
+    return red, known_idx, known_val
+
+
+def _build_reduction(layout: KKTLayout, pins, values) -> Reduction:
+    """``values`` None: the constraints' own (scalar) values; else {constraint index: array (k,)} for a block."""
     N, n_pot = layout.size, layout.n_potential
+    if values is None:
+        value_of, nonzero = (lambda cst: cst.value), (lambda val: val != 0.0)
+    else:
+        k = len(next(iter(values.values()))) if values else 1
+        value_of = lambda cst: values[cst.index] if cst.index in values else np.full(k, float(cst.value))  # noqa: E731
+        nonzero = lambda val: bool(np.any(np.asarray(val) != 0.0))  # noqa: E731
     uf = _UnionFind()
     ground = layout.ground_constraint
     dirichlet = [ground] + [Constraint(index=-(k + 1), p=int(x), n=-1, value=0.0) for k, x in enumerate(pins or [])]
@@ -363,7 +394,7 @@ def build_reduction(layout: KKTLayout, pins: list | None = None) -> Reduction:
             continue
         if cst.p == cst.n:
             raise SingularSystemError("voltage source with both terminals on one node")
-        if not uf.union(cst.p, cst.n, cst.value):
+        if not uf.union(cst.p, cst.n, value_of(cst)):
             raise SingularSystemError("loop of voltage sources: the constraint rows are linearly dependent")
     # collect groups among the nodes touched by constraints
     members: dict = {}
@@ -381,7 +412,7 @@ def build_reduction(layout: KKTLayout, pins: list | None = None) -> Reduction:
                 gcons[root].remove(cst)            # a pin inside an already grounded group is redundant
                 continue
             raise SingularSystemError("two ground rows tie the same group of nodes")
-        known_roots[root] = (cst.value - uf.offset(cst.p), cst.p)
+        known_roots[root] = (value_of(cst) - uf.offset(cst.p), cst.p)
     # representative of a free group = its smallest member, so singletons keep their place
     rep_of = {}
     elim, tied, known = [], [], {}
@@ -391,14 +422,14 @@ def build_reduction(layout: KKTLayout, pins: list | None = None) -> Reduction:
             for x in mem:
                 elim.append(x)
                 val = v_root + uf.offset(x)
-                if val != 0.0:
+                if nonzero(val):
                     known[x] = val
         else:
             rep = min(mem)
             rep_of[root] = rep
             for x in mem:
                 val = uf.offset(x) - uf.offset(rep)
-                if val != 0.0:
+                if nonzero(val):
                     known[x] = val
                 if x != rep:
                     elim.append(x)                # numbered through its representative
@@ -414,6 +445,60 @@ def build_reduction(layout: KKTLayout, pins: list | None = None) -> Reduction:
         groups.append((sorted(mem), gcons[root], r_node))
     regs = [cst for cst in layout.constraints if cst.gamma]
     return Reduction(layout=layout, n_free=n_free, elim=elim, tied=sorted(tied), known=known, groups=groups, regulators=regs)
+
+
+def recover_currents(red: Reduction, members, probes: np.ndarray, n_cols: int = 1):
+    """Regulator and multiplier currents of ``n_cols`` right-hand sides from the device's probe rows.
+
+    ``probes`` [(n_cols + K), len(members)]: rows 0..n_cols-1 are rho_j = r_j - L v_j (v_j with zero multipliers and zero
+    regulator currents) at the ``members`` (ascending), rows n_cols + k are L Z_k with Z_k = P z_k the expanded solution of
+    A z_k = P^T gamma_k of regulator k.  With the currents i of the regulators, row x of the original system reads
+    L_x.v + sum_s sigma_xs i_s + sum_k gamma_k[x] i_k = r_x, so the multipliers peeled from rho_j - sum_k i_k (L Z_k) are
+    affine in i: F(i) = F0_j + J i.  J comes from the L Z_k rows alone and is formed ONCE (from column 0); per column only
+    F0_j and the K x K solve (I - J) i = F0_j remain.
+
+    Returns ``(i_reg, mult)``: i_reg (n_cols, K) in the order of ``red.regulators``, and per column a dict {unknown:
+    current} of the multipliers (sources, regulators, ground row; pins of floating copper left out)."""
+    probes = np.asarray(probes, dtype=np.float64)
+    at = {x: q for q, x in enumerate(members)}
+    K = len(red.regulators)
+    keys = [cst.index for cst in red.regulators]
+
+    class _Rows:                                   # rho_x of a member x, for Reduction.multipliers
+        def __init__(self, col, i_vec):
+            self.col, self.i_vec = col, i_vec
+
+        def __getitem__(self, x):
+            q = at[int(x)]
+            # rho(v + sum_k i_k Z_k) = rho(v) - sum_k i_k (L Z_k): the device returned both at the members
+            return probes[self.col, q] - sum(self.i_vec[j] * probes[n_cols + j, q] for j in range(len(self.i_vec)))
+
+    def currents_for(col, i_vec):
+        return red.multipliers(_Rows(col, i_vec), dict(zip(keys, i_vec)))
+
+    i_all = np.zeros((n_cols, K))
+    mult_all = []
+    J = None
+    for col in range(n_cols):
+        i_reg = np.zeros(K)
+        if K:
+            # y = y0 + sum_k i_k z_k with A z_k = P^T gamma_k:  row x reads L_x.v + gamma_k[x] i_k = r_x, so
+            # summing a group's rows gives  -P^T L P y = -P^T (r - L c) + sum_k i_k P^T gamma_k
+            base = currents_for(col, np.zeros(K))
+            F0 = np.array([base[k] for k in keys])
+            if J is None:
+                J = np.zeros((K, K))
+                for k in range(K):
+                    e = np.zeros(K)
+                    e[k] = 1.0
+                    ck = currents_for(col, e)
+                    J[:, k] = np.array([ck[q] for q in keys]) - F0
+            i_reg = np.linalg.solve(np.eye(K) - J, F0)
+        mult_known = dict(zip(keys, i_reg))
+        # (negative index: the current through the pin of a floating component, not an unknown of the system)
+        mult_all.append({idx: val for idx, val in red.multipliers(_Rows(col, i_reg), mult_known).items() if idx >= 0})
+        i_all[col] = i_reg
+    return i_all, mult_all
 
 
 def floating_component_pins(n_potential: int, ground: int, constraints, *, mesh_offsets=None, links=None,

@@ -34,8 +34,8 @@ import scipy.sparse as sp
 import scipy.spatial
 
 from . import _hip, mesh, problem
-from .reduction import (Constraint, KKTLayout, Reduction, SingularSystemError, build_reduction,
-                        floating_component_pins, infer_layout)
+from .reduction import (Constraint, KKTLayout, Reduction, SingularSystemError, build_block_reduction, build_reduction,
+                        floating_component_pins, infer_layout, recover_currents)
 
 log = logging.getLogger(__name__)
 
@@ -75,6 +75,9 @@ class SolverInfo:
     iterations: int = 0
     rel_residual: float = 0.0
     solve_seconds: float = 0.0
+    # a block r of shape (N, k): ||L v_j - r_j||_2 per column (ground_node_current is then V[-1], residual_norm the
+    # Frobenius norm ||L V - R||_F); None for a single right-hand side
+    residual_norms: Optional[np.ndarray] = None
 
 
 @dataclass
@@ -397,7 +400,19 @@ class SystemMatrix:
         return self.tocsr()[key]
 
     def __matmul__(self, v):
-        return self.dev.matvec(np.asarray(v, dtype=DTYPE))
+        v = np.asarray(v, dtype=DTYPE)
+        if v.ndim != 2:
+            return self.dev.matvec(v)
+        # a block (N, k): 8 columns per pass of the SpMM (the last pass zero-padded), each column bit-identical to L @ v_j
+        if v.shape[0] != self.shape[1]:
+            raise ValueError("dimension mismatch")
+        out = np.empty((self.shape[0], v.shape[1]), dtype=DTYPE)
+        for j in range(0, v.shape[1], 8):
+            w = min(8, v.shape[1] - j)
+            X = np.zeros((self.shape[1], 8), dtype=DTYPE)
+            X[:, :w] = v[:, j:j + w]
+            out[:, j:j + w] = self.dev.matmat8(X)[:, :w]
+        return out
 
 
 def _flatten_meshes(meshes, conductances):
@@ -478,7 +493,24 @@ RTOL_FLOOR = 2e-15
 STALL_WARN_ABOVE = 1e-9
 
 
-def _warn_if_stalled(res, rtol: float) -> None:
+def _stalled(res, rtol: float) -> bool:
+    return res.status != _hip.OK and not res.rel_residual <= max(rtol, STALL_WARN_ABOVE)
+
+
+def _stalled_columns(residual_norms: np.ndarray, R: np.ndarray) -> str:
+    """Which columns of a block a stall is put down to.  The device reports the reduced solves of a block as a whole (one
+    status, the largest relative residual), so this is an ATTRIBUTION, not a per-column status: the columns whose
+    ||L v_j - r_j|| exceeds STALL_WARN_ABOVE ||r_j||, or, if none does, the one worst against its own right-hand side.
+    Only called when the block stalled (an O(N k) pass over R)."""
+    rel = residual_norms / np.maximum(np.sqrt(np.einsum("ij,ij->j", R, R)), 1e-300)
+    cols = np.flatnonzero(rel > STALL_WARN_ABOVE)
+    if not len(cols):
+        cols = [int(np.argmax(rel))]
+    return (f" (block of {len(residual_norms)} right-hand sides, reported as a whole; largest residuals against their own "
+            f"right-hand side in column(s) {', '.join(str(int(j)) for j in cols[:16])})")
+
+
+def _warn_if_stalled(res, rtol: float, where: str = "") -> None:
     """The reference's direct solve always returns *an* answer and reports its quality through
     SolverInfo.residual_norm; an iteration that stalls above the requested tolerance does the same, with a warning in
     the reference's own soft-failure style (solver.py:880-888) when the residual is worse than 1e-9 relative (matrices
@@ -486,9 +518,9 @@ def _warn_if_stalled(res, rtol: float) -> None:
     rounding floor of evaluating b - A x for a system whose solution is large against its right-hand side (a layer
     held at hundreds of volts through a weak link: 1 of 1000 random systems of scripts/fuzz_parity.py, potentials
     still within 4e-11 of the direct solve); it is reported in SolverInfo.residual_norm and not warned about."""
-    if res.status != _hip.OK and not res.rel_residual <= max(rtol, STALL_WARN_ABOVE):
+    if _stalled(res, rtol):
         warnings.warn(f"iterative solve stopped at a relative residual of {res.rel_residual:.2e} "
-                      f"(requested {rtol:.1e}) after {res.iterations} iterations", SolverWarning)
+                      f"(requested {rtol:.1e}) after {res.iterations} iterations{where}", SolverWarning)
 
 
 def solve_system(L, r: np.ndarray, *, rtol: float = RTOL, reorder=None, n_potential: Optional[int] = None):
@@ -499,11 +531,28 @@ def solve_system(L, r: np.ndarray, *, rtol: float = RTOL, reorder=None, n_potent
     potential unknowns in front of the multiplier block, if the caller knows it).  ``reorder``: None = solve in
     a band numbering when the mesh numbering is scattered (decided from the triangles), True / False = force.
 
+    ``r`` may also be a block of shape (N, k), as ``spsolve`` accepts it: ``V`` (N, k) comes back, column j the solution
+    for ``r[:, j]``, with ``ground_node_current = V[-1]``, ``residual_norm = ||L V - R||_F`` and the per-column norms in
+    ``SolverInfo.residual_norms``.  The block is reduced once, its columns and the regulator columns go through one
+    lockstep solve.  A C-ordered block crosses to the device as it is; any other order costs one host copy.  Shape
+    (N, 1) is the single right-hand side ``r[:, 0]``: v of shape (N,).
+
     Copper that nothing ties to the ground node (the reference's matrix is singular there, its LU returns rounding
     noise for those potentials) is held at 0 V at one vertex; ``ground_node_current`` is, as in the reference, the net
     current injected into the grounded component (``tests/test_solver.py:1829-1833``: non-zero for an unterminated
     current loop).
     """
+    r = np.asarray(r)
+    if r.ndim > 2:
+        raise ValueError(f"r must be a vector or an (N, k) block, not of shape {r.shape}")
+    if r.ndim == 2:
+        if r.shape[0] != L.shape[0]:
+            raise ValueError(f"r has {r.shape[0]} rows, the system {L.shape[0]}")
+        if r.shape[1] == 0:
+            raise ValueError("r is a block of no right-hand sides")
+        if r.shape[1] == 1:
+            r = r[:, 0]
+    block = r.ndim == 2
     ctx = get_context()
     r = np.ascontiguousarray(r, dtype=DTYPE)
     if isinstance(L, SystemMatrix):
@@ -516,12 +565,13 @@ def solve_system(L, r: np.ndarray, *, rtol: float = RTOL, reorder=None, n_potent
         Lc.eliminate_zeros()
         Lc.sort_indices()
         dev, layout, owned = ctx.csr_from_scipy(Lc), None, True
-        layout = infer_layout(Lc, r, n_potential)
+        layout = infer_layout(Lc, r[:, 0] if block else r, n_potential)
     if layout is None or not layout.constraints:
         raise SingularSystemError("system has no ground constraint")
-    # multiplier rows take their right-hand side from r (solver.py:505, 530, 560)
-    for cst in layout.constraints:
-        cst.value = float(r[cst.index])
+    if not block:
+        # multiplier rows take their right-hand side from r (solver.py:505, 530, 560)
+        for cst in layout.constraints:
+            cst.value = float(r[cst.index])
     ground_p = layout.ground_constraint.p
     if Lc is not None:
         pins = floating_component_pins(layout.n_potential, ground_p, layout.constraints, matrix=Lc)
@@ -532,8 +582,13 @@ def solve_system(L, r: np.ndarray, *, rtol: float = RTOL, reorder=None, n_potent
         pins = []
     if pins:
         log.info(f"{len(pins)} floating component(s) held at 0 V at unknown(s) {pins[:8]}")
-    # O(#constraints): what the reduction eliminates, ties and knows; the index map itself is made on the device
-    red: Reduction = build_reduction(layout, pins)
+    # O(#constraints): what the reduction eliminates, ties and knows; the index map itself is made on the device.  A block
+    # is reduced once: the structure is the same for every column, the known parts come per column
+    if block:
+        red, known_idx, known_val = build_block_reduction(layout, {cst.index: r[cst.index, :] for cst in layout.constraints},
+                                                          pins)
+    else:
+        red: Reduction = build_reduction(layout, pins)
     want_reorder = False
     if isinstance(L, SystemMatrix) and L.xy is not None and reorder is not False:
         # CGAL numbers vertices in insertion order; when neighbours are far apart in the numbering the SpMV
@@ -580,46 +635,34 @@ def solve_system(L, r: np.ndarray, *, rtol: float = RTOL, reorder=None, n_potent
             L._plans[key] = plan
     try:
         members = sorted({int(x) for mem, cons, _ in red.groups if cons for x in mem})
-        probes, res = plan.solve(r, red.known, [dict(cst.gamma) for cst in red.regulators], members, rtol=rtol,
-                                 max_iter=MAX_ITER, abs_residual_target=ABS_RESIDUAL_TARGET)
-        _warn_if_stalled(res, rtol)
-        at = {x: k for k, x in enumerate(members)}
-
-        class _Rows:                                   # rho_x of a member x, for Reduction.multipliers
-            def __init__(self, i_vec):
-                self.i_vec = i_vec
-
-            def __getitem__(self, x):
-                k = at[int(x)]
-                # rho(v + sum_k i_k Z_k) = rho(v) - sum_k i_k (L Z_k): the device returned both at the members
-                return probes[0, k] - sum(self.i_vec[j] * probes[1 + j, k] for j in range(len(self.i_vec)))
-        K = len(red.regulators)
-        keys = [cst.index for cst in red.regulators]
-        i_reg = np.zeros(K)
-        if K:
-            # y = y0 + sum_k i_k z_k with A z_k = P^T gamma_k:  row x reads L_x.v + gamma_k[x] i_k = r_x, so
-            # summing a group's rows gives  -P^T L P y = -P^T (r - L c) + sum_k i_k P^T gamma_k
-            def currents_for(i_vec):
-                return red.multipliers(_Rows(i_vec), dict(zip(keys, i_vec)))
-            base = currents_for(np.zeros(K))
-            F0 = np.array([base[k] for k in keys])
-            J = np.zeros((K, K))
-            for k in range(K):
-                e = np.zeros(K)
-                e[k] = 1.0
-                ck = currents_for(e)
-                J[:, k] = np.array([ck[q] for q in keys]) - F0
-            i_reg = np.linalg.solve(np.eye(K) - J, F0)
-        mult_known = dict(zip(keys, i_reg))
-        mult = {idx: val for idx, val in red.multipliers(_Rows(i_reg), mult_known).items() if idx >= 0}
-        # (negative index: the current through the pin of a floating component, not an unknown of the system)
-        v, residual_norm = plan.finish(i_reg, mult)
+        extras = [dict(cst.gamma) for cst in red.regulators]
+        if not block:
+            probes, res = plan.solve(r, red.known, extras, members, rtol=rtol, max_iter=MAX_ITER,
+                                     abs_residual_target=ABS_RESIDUAL_TARGET)
+            _warn_if_stalled(res, rtol)
+            i_reg, mult = recover_currents(red, members, probes, 1)
+            v, residual_norm = plan.finish(i_reg[0], mult[0])
+        else:
+            k = r.shape[1]
+            probes, res = plan.solve_block(r, known_idx, known_val, extras, members, rtol=rtol, max_iter=MAX_ITER,
+                                           abs_residual_target=ABS_RESIDUAL_TARGET)
+            i_reg, mult = recover_currents(red, members, probes, k)
+            mult_idx = np.asarray(sorted(mult[0]), dtype=np.int64)
+            mult_val = np.array([[m[int(i)] for i in mult_idx] for m in mult], dtype=DTYPE).reshape(k, len(mult_idx))
+            v, residual_norms = plan.finish_block(i_reg, mult_idx, mult_val)
     finally:
         if owned:
             plan.close()
             dev.close()
-    info = SolverInfo(ground_node_current=float(v[-1]), residual_norm=float(residual_norm),
-                      iterations=int(res.iterations), rel_residual=float(res.rel_residual), solve_seconds=float(res.seconds))
+    if not block:
+        info = SolverInfo(ground_node_current=float(v[-1]), residual_norm=float(residual_norm),
+                          iterations=int(res.iterations), rel_residual=float(res.rel_residual), solve_seconds=float(res.seconds))
+        return v, info
+    if _stalled(res, rtol):
+        _warn_if_stalled(res, rtol, _stalled_columns(residual_norms, r))
+    info = SolverInfo(ground_node_current=v[-1].copy(), residual_norm=float(np.sqrt(np.sum(residual_norms ** 2))),
+                      iterations=int(res.iterations), rel_residual=float(res.rel_residual), solve_seconds=float(res.seconds),
+                      residual_norms=residual_norms)
     return v, info
 
 
