@@ -323,6 +323,20 @@ int padne_kkt_solve_block(padne_ctx *ctx, padne_kkt *plan, int32_t n_cols, const
 int padne_kkt_finish_block(padne_ctx *ctx, padne_kkt *plan, int32_t n_cols, int32_t n_extra, const double *extra_coeff,
                            int64_t n_mult, const int64_t *mult_idx, const double *mult_val, double *v_host,
                            double *residual_norms_out);
+/* padne_kkt_solve_block with the block given as n_entries COO triples (r_row[e], r_col[e], r_val[e]) instead of a dense
+ * r_host: the plan's r block is zeroed on the device and the triples scattered into it, in the same [N][n_cols] layout;
+ * everything after that is padne_kkt_solve_block.  Load cases of one board: only the source terminals and the multiplier
+ * rows are non-zero.  Duplicate or out-of-range (row, column) pairs: PADNE_E_INVALID before the device is touched. */
+int padne_kkt_solve_block_coo(padne_ctx *ctx, padne_kkt *plan, int32_t n_cols, int64_t n_entries, const int64_t *r_row,
+                              const int32_t *r_col, const double *r_val, int64_t n_known, const int64_t *known_idx,
+                              const double *known_val, int32_t n_extra, const int64_t *extra_ptr, const int64_t *extra_row,
+                              const double *extra_val, int64_t n_probe, const int64_t *probe_idx, double *probe_out,
+                              const padne_solve_opts *opts, double abs_residual_target, padne_solve_info *info);
+/* Per-face sigma |grad V|^2 of every column of the block the last padne_kkt_finish_block left on the device, over the mesh
+ * `L` keeps: out_host[n_cols][n_tri] row-major, column j bit-identical to padne_csr_power_density on V[:, j].  Nothing
+ * crosses PCIe but the result.  PADNE_E_INVALID when no block has been finished since the last solve, when n_cols is not
+ * that block's, or when `L` carries no mesh. */
+int padne_kkt_power_density_block(padne_ctx *ctx, padne_kkt *plan, int32_t n_cols, double *out_host);
 
 /* Row-partitioned runs, optional: attach the rank's owned x owned diagonal block; with precond = 1 the
  * multigrid hierarchy is then built on that block only (block-Jacobi with multigrid blocks, no

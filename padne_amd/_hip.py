@@ -108,6 +108,10 @@ SIGNATURES = {
     "padne_kkt_solve_block": (C.c_int, [_P, _P, C.c_int32, _PF64, _I64, _PI64, _PF64, C.c_int32, _PI64, _PI64, _PF64, _I64,
                                         _PI64, _PF64, C.POINTER(SolveOpts), C.c_double, C.POINTER(SolveInfo)]),
     "padne_kkt_finish_block": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _PF64, _I64, _PI64, _PF64, _PF64, _PF64]),
+    "padne_kkt_solve_block_coo": (C.c_int, [_P, _P, C.c_int32, _I64, _PI64, _PI32, _PF64, _I64, _PI64, _PF64, C.c_int32, _PI64,
+                                            _PI64, _PF64, _I64, _PI64, _PF64, C.POINTER(SolveOpts), C.c_double,
+                                            C.POINTER(SolveInfo)]),
+    "padne_kkt_power_density_block": (C.c_int, [_P, _P, C.c_int32, _PF64]),
     "padne_amg_apply": (C.c_int, [_P, _P, _PF64, _PF64]),
     "padne_csr_set_preconditioner_block": (C.c_int, [_P, _P]),
     "padne_amg_level": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(_P)]),
@@ -571,6 +575,23 @@ class SolveResult:
     precond_fallbacks: int = 0      # right-hand sides redone with the Jacobi preconditioner after a multigrid failure
 
 
+def _prefaulted(shape):
+    """A result array of ``shape`` whose pages threads touch while the device works: (array, threads), or (None, None) when
+    it is too small to matter.  A fresh 80 MB array at 10 M unknowns is 20 000 page faults in the path of the copy that
+    brings it home; one thread per 80 MB, up to 8."""
+    if int(np.prod(shape)) < (1 << 18):
+        return None, None
+    import threading
+    arr = np.empty(shape, dtype=np.float64)
+    flat = arr.reshape(-1)
+    parts = np.array_split(flat, min(8, -(-flat.nbytes // (80 << 20))))
+    # (the threads hold the array itself, not just its address: it outlives a plan that is dropped on an error path)
+    threads = [threading.Thread(target=lambda a=a: C.memset(a.ctypes.data, 0, a.nbytes), daemon=True) for a in parts]
+    for t in threads:
+        t.start()
+    return arr, threads
+
+
 class KktPlan:
     """``padne_kkt``: the reduction of one assembled KKT system to its SPD core, resident on the device (index map,
     reduced matrix with its multigrid hierarchy, the N-vectors).  ``solve`` + ``finish`` are the two device stages of
@@ -634,7 +655,25 @@ class KktPlan:
         kval = _f64(known_val).reshape(R.shape[1], kidx.shape[0])
         return self._stage1(R.shape[1], R, kidx, kval, extras, probes, rtol, max_iter, precond, abs_residual_target, rebuild)
 
-    def _stage1(self, n_cols, r, kidx, kval, extras, probes, rtol, max_iter, precond, abs_residual_target, rebuild):
+    def solve_block_coo(self, n_cols, rows, cols, vals, known_idx, known_val, extras: list, probes, *, rtol=1e-12,
+                        max_iter=200000, precond="amg", abs_residual_target=0.0, rebuild=False, power_tri: int = 0):
+        """``solve_block`` with the block (N, n_cols) given by its non-zero entries: R[rows[e], cols[e]] = vals[e], each (row,
+        column) pair at most once.  Only the triples cross PCIe; the device zeroes its block and scatters them.
+        ``power_tri``: the triangles of the mesh the system carries, when ``power_density_block`` will follow -- its result
+        array is then made ready while the device solves, like V's."""
+        rows, cols, vals = _i64(rows).reshape(-1), _i32(cols).reshape(-1), _f64(vals).reshape(-1)
+        if not (rows.shape == cols.shape == vals.shape):
+            raise ValueError("rows, cols and vals must have equal length")
+        n_cols = int(n_cols)
+        if n_cols < 1:
+            raise ValueError("a block has at least one column")
+        kidx = _i64(known_idx)
+        kval = _f64(known_val).reshape(n_cols, kidx.shape[0])
+        return self._stage1(n_cols, (rows, cols, vals), kidx, kval, extras, probes, rtol, max_iter, precond,
+                            abs_residual_target, rebuild, power_tri=int(power_tri))
+
+    def _stage1(self, n_cols, r, kidx, kval, extras, probes, rtol, max_iter, precond, abs_residual_target, rebuild,
+                power_tri=0):
         ptr, rows, vals = [0], [], []
         for col in extras:
             for row, val in col.items():
@@ -646,28 +685,23 @@ class KktPlan:
         out = np.zeros(((n_cols or 1) + len(extras), max(len(pidx), 1)), dtype=np.float64)
         opts = CsrMatrix._opts(rtol, 0.0, max_iter, 0, False, precond=precond, rebuild=rebuild)
         info = SolveInfo()
-        # the array stage 2 will hand back: its pages are touched while the device solves (a fresh 80 MB array at 10 M
-        # unknowns is 20 000 page faults in the path of the copy that brings v home); one thread per 80 MB, up to 8, so that
-        # a block's result is ready when the device is
-        self._v_next, self._v_toucher = None, None
-        if r.size >= (1 << 18):
-            import threading
-            v_next = np.empty(r.shape, dtype=np.float64)
-            self._v_next = v_next
-            flat = v_next.reshape(-1)
-            parts = np.array_split(flat, min(8, -(-flat.nbytes // (80 << 20))))
-            # (the threads hold the array itself, not just its address: it outlives a plan that is dropped on an error path)
-            self._v_toucher = [threading.Thread(target=lambda a=a: C.memset(a.ctypes.data, 0, a.nbytes), daemon=True)
-                               for a in parts]
-            for t in self._v_toucher:
-                t.start()
-        lib, common = self.ctx._lib, (_ptr(r, _PF64), kidx.shape[0], _ptr(kidx, _PI64), _ptr(kval, _PF64), len(extras),
+        # the array stage 2 will hand back (and that of the power densities of a block that asks for them): their pages are
+        # touched while the device solves, so that a block's result is ready when the device is
+        coo = isinstance(r, tuple)
+        v_shape = (self.N, n_cols) if coo else r.shape
+        self._v_next, self._v_toucher = _prefaulted(v_shape)
+        self._pd_next, self._pd_toucher = _prefaulted((n_cols, power_tri)) if coo and power_tri > 0 else (None, None)
+        lib, common = self.ctx._lib, (kidx.shape[0], _ptr(kidx, _PI64), _ptr(kval, _PF64), len(extras),
                                       _ptr(ptr, _PI64), _ptr(rows, _PI64), _ptr(vals, _PF64), pidx.shape[0], _ptr(pidx, _PI64),
                                       _ptr(out, _PF64), C.byref(opts), float(abs_residual_target), C.byref(info))
-        if n_cols is None:
-            rc = lib.padne_kkt_solve(self.ctx._h, self._h, *common)
+        if coo:
+            r_rows, r_cols, r_vals = r
+            rc = lib.padne_kkt_solve_block_coo(self.ctx._h, self._h, int(n_cols), r_rows.shape[0], _ptr(r_rows, _PI64),
+                                               _ptr(r_cols, _PI32), _ptr(r_vals, _PF64), *common)
+        elif n_cols is None:
+            rc = lib.padne_kkt_solve(self.ctx._h, self._h, _ptr(r, _PF64), *common)
         else:
-            rc = lib.padne_kkt_solve_block(self.ctx._h, self._h, int(n_cols), *common)
+            rc = lib.padne_kkt_solve_block(self.ctx._h, self._h, int(n_cols), _ptr(r, _PF64), *common)
         if rc != OK and rc != E_NOTCONVERGED:
             _check(rc)
         res = SolveResult(None, info.iterations, info.restarts, info.rel_residual, info.abs_residual, info.solve_seconds,
@@ -683,6 +717,21 @@ class KktPlan:
         if v is None or v.shape != shape:
             v = np.empty(shape, dtype=np.float64)
         return v
+
+    def power_density_block(self, n_cols: int, n_tri: int) -> np.ndarray:
+        """Per-face sigma |grad V|^2 of every column of the block the last ``finish_block`` left on the device, over the mesh
+        the system was assembled from (``n_tri`` triangles, as ``CsrMatrix.power_density`` takes it): (n_cols, n_tri), row j
+        bit-identical to ``CsrMatrix.power_density`` of V[:, j].  Raises ValueError when no block has been finished since the
+        last solve, on another column count, and on a matrix without a mesh."""
+        toucher, out = getattr(self, "_pd_toucher", None), getattr(self, "_pd_next", None)
+        self._pd_next, self._pd_toucher = None, None
+        n_tri = int(n_tri)
+        for t in toucher or ():
+            t.join()
+        if out is None or out.shape != (int(n_cols), n_tri):
+            out = np.empty((int(n_cols), n_tri), dtype=np.float64)
+        _check(self.ctx._lib.padne_kkt_power_density_block(self.ctx._h, self._h, int(n_cols), _ptr(out, _PF64)))
+        return out
 
     def finish(self, extra_coeff, multipliers: dict):
         """Stage 2: (v, ||L v - r||)."""

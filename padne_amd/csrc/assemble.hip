@@ -2155,6 +2155,18 @@ __device__ __forceinline__ double interp(double x1, double y1, double x2, double
     return l1 * f1 + l2 * f2 + l3 * f3;
 }
 
+// the face gradient and sigma |grad V|^2 of compute_power_density (solver.py:728-745), shared by every form of the kernel
+__device__ __forceinline__ void face_gradient_of(double x1, double y1, double x2, double y2, double x3, double y3, double f1,
+                                                 double f2, double f3, double &gx, double &gy) {
+    gx = interp(x1, y1, x2, y2, x3, y3, f1, f2, f3, x1 + 1, y1) - f1;
+    gy = interp(x1, y1, x2, y2, x3, y3, f1, f2, f3, x1, y1 + 1) - f1;
+}
+
+__device__ __forceinline__ double face_power_of(double gx, double gy, double s) {
+    const double jx = gx * s, jy = gy * s;      // J = E * conductivity
+    return jx * gx + jy * gy;                   // J.dot(E)
+}
+
 __global__ void power_density_kernel(long long n_tri, const int *__restrict__ tri, const double *__restrict__ xy,
                                      int n_mesh, const long long *__restrict__ mesh_voff,
                                      const long long *__restrict__ mesh_toff, const double *__restrict__ sigma,
@@ -2175,16 +2187,60 @@ __global__ void power_density_kernel(long long n_tri, const int *__restrict__ tr
     const double x2 = xy[2 * g2], y2 = xy[2 * g2 + 1];
     const double x3 = xy[2 * g3], y3 = xy[2 * g3 + 1];
     const double f1 = pot[g1], f2 = pot[g2], f3 = pot[g3];
-    const double gx = interp(x1, y1, x2, y2, x3, y3, f1, f2, f3, x1 + 1, y1) - f1;
-    const double gy = interp(x1, y1, x2, y2, x3, y3, f1, f2, f3, x1, y1 + 1) - f1;
+    double gx, gy;
+    face_gradient_of(x1, y1, x2, y2, x3, y3, f1, f2, f3, gx, gy);
     if (gx_out) {
         gx_out[t] = gx;
         gy_out[t] = gy;
     }
-    if (out) {
-        const double s = sigma[m];
-        const double jx = gx * s, jy = gy * s;      // J = E * conductivity
-        out[t] = jx * gx + jy * gy;                 // J.dot(E)
+    if (out) out[t] = face_power_of(gx, gy, sigma[m]);
+}
+
+// power_density_kernel for a block of n_cols potentials V[n_vert][n_cols] (row-major: the potentials of one vertex in all
+// columns are one contiguous run, a 64-byte line for 8 columns) -> out[n_cols][n_tri].  One thread per triangle: the segment
+// lookup, the index check and the corners once, then the columns in chunks of kPowerChunk whose loads are in flight together
+// (the register count does not grow with n_cols); every column gets the arithmetic of power_density_kernel, hence its bits.
+constexpr int kPowerChunk = 8;
+
+__global__ __launch_bounds__(256) void power_density_block_kernel(long long n_tri, const int *__restrict__ tri,
+                                                                  const double *__restrict__ xy, int n_mesh,
+                                                                  const long long *__restrict__ mesh_voff,
+                                                                  const long long *__restrict__ mesh_toff,
+                                                                  const double *__restrict__ sigma, const int n_cols,
+                                                                  const double *__restrict__ V, double *__restrict__ out,
+                                                                  int *__restrict__ err) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_tri) return;
+    const int m = find_segment(mesh_toff, n_mesh, t);
+    const long long v0 = mesh_voff[m];
+    const long long nv = mesh_voff[m + 1] - v0;
+    const int l1 = tri[3 * t + 2], l2 = tri[3 * t], l3 = tri[3 * t + 1];
+    if (l1 < 0 || l2 < 0 || l3 < 0 || l1 >= nv || l2 >= nv || l3 >= nv) {
+        *(volatile int *)err = 1;
+        return;
+    }
+    const long long g1 = v0 + l1, g2 = v0 + l2, g3 = v0 + l3;
+    const double x1 = xy[2 * g1], y1 = xy[2 * g1 + 1];
+    const double x2 = xy[2 * g2], y2 = xy[2 * g2 + 1];
+    const double x3 = xy[2 * g3], y3 = xy[2 * g3 + 1];
+    const double s = sigma[m];
+    const double *p1 = V + g1 * n_cols, *p2 = V + g2 * n_cols, *p3 = V + g3 * n_cols;
+    for (int j0 = 0; j0 < n_cols; j0 += kPowerChunk) {
+        double f1[kPowerChunk], f2[kPowerChunk], f3[kPowerChunk];
+#pragma unroll
+        for (int q = 0; q < kPowerChunk; ++q)
+            if (j0 + q < n_cols) {
+                f1[q] = p1[j0 + q];
+                f2[q] = p2[j0 + q];
+                f3[q] = p3[j0 + q];
+            }
+#pragma unroll
+        for (int q = 0; q < kPowerChunk; ++q)
+            if (j0 + q < n_cols) {
+                double gx, gy;
+                face_gradient_of(x1, y1, x2, y2, x3, y3, f1[q], f2[q], f3[q], gx, gy);
+                out[(long long)(j0 + q) * n_tri + t] = face_power_of(gx, gy, s);
+            }
     }
 }
 
@@ -2723,6 +2779,21 @@ extern "C" int padne_csr_power_density(padne_ctx *ctx, const padne_csr *m, const
     PADNE_HIP_CHECK(hipStreamSynchronize(s));
     return PADNE_OK;
 }
+
+namespace padne {
+// power_density_block_kernel over the mesh `m` keeps, for V_dev[mesh_n_vert..][n_cols] (device) -> out_dev[n_cols][mesh_n_tri];
+// bad_dev (device int, zeroed by the caller) is set when a triangle names a vertex outside its mesh.  Asynchronous.
+int launch_power_density_block(padne_ctx *ctx, const padne_csr *m, int n_cols, const double *V_dev, double *out_dev,
+                               int *bad_dev) {
+    PADNE_REQUIRE(m->mesh_n_mesh > 0 && m->mesh_xy != nullptr, "the matrix does not carry a mesh (only padne_assemble_system keeps it)");
+    if (m->mesh_n_tri == 0 || n_cols == 0) return PADNE_OK;
+    hipLaunchKernelGGL(power_density_block_kernel, dim3(nblk(m->mesh_n_tri)), dim3(256), 0, ctx->stream, (long long)m->mesh_n_tri,
+                       m->mesh_tri, m->mesh_xy, (int)m->mesh_n_mesh, m->mesh_voff, m->mesh_toff, m->mesh_sigma, n_cols, V_dev,
+                       out_dev, bad_dev);
+    PADNE_HIP_CHECK(hipGetLastError());
+    return PADNE_OK;
+}
+}  // namespace padne
 
 // out = scale * R^T M C: entry (i, j, v) becomes (row_map[i], col_map[j], scale*v) when both maps are >= 0,
 // duplicates are added in the order of their position in M.

@@ -21,6 +21,8 @@ namespace padne {
 int csr_relabel(padne_ctx *ctx, const padne_csr *m, const int32_t *row_map, int64_t n_rows_out, const int32_t *col_map,
                 int64_t n_cols_out, double scale, padne_csr **out);
 int amg_setup(padne_ctx *ctx, padne_csr *A0);
+int launch_power_density_block(padne_ctx *ctx, const padne_csr *m, int n_cols, const double *V_dev, double *out_dev,
+                               int *bad_dev);
 void amg_info(const padne_csr *A0, int *levels, double *complexity, double *setup_seconds, long long *coarse_n);
 
 constexpr int kCopyStreams = 4;
@@ -50,6 +52,11 @@ struct padne_kkt {
     int rhs_cap = 1, z_cap = 0;          // reduced columns b and y hold, expanded extra solutions Z holds
     int n_cols = 1, n_extra = 0;         // of the last solve
     bool has_c = false, solved = false;
+    // "finished": the last padne_kkt_finish_block left its final V on the device, [N][finished_cols] row-major in v_final (v,
+    // or c when the products' layout differs from the caller's); any later solve clears it
+    bool finished = false;
+    const double *v_final = nullptr;
+    int finished_cols = 0;
     double setup_seconds_last = 0.0;
 };
 
@@ -129,6 +136,14 @@ __global__ __launch_bounds__(256) void kkt_scatter_block(const int n, const long
     const double x = val[(long long)j * n + p];
     dst[kkt_gidx(N, n_cols, j, i)] = x;
     if (dst_caller != nullptr) dst_caller[i * n_cols + j] = x;
+}
+
+// r[row[e]][col[e]] = val[e] ([N][n_cols], zeroed before): a block of right-hand sides given by its non-zero entries
+__global__ __launch_bounds__(256) void kkt_scatter_coo(const long long n, const int n_cols, const long long *__restrict__ row,
+                                                       const int32_t *__restrict__ col, const double *__restrict__ val,
+                                                       double *__restrict__ r) {
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long long)gridDim.x * 256)
+        r[row[e] * n_cols + col[e]] = val[e];
 }
 
 // ---- right-hand side: b = -P^T (r - L c) ---------------------------------------------------------------------------
@@ -667,14 +682,38 @@ static int kkt_products(padne_ctx *ctx, const padne_kkt *k, const int n_cols, co
     return PADNE_OK;
 }
 
+// The right-hand sides of a stage 1: a dense block r_host[N][n_cols], or (r_host null) n_entries COO triples
+struct KktRhs {
+    const double *dense = nullptr;
+    int64_t n_entries = 0;
+    const int64_t *row = nullptr;
+    const int32_t *col = nullptr;
+    const double *val = nullptr;
+};
+
 // Stage 1 for a block of n_cols right-hand sides (n_cols = 1: padne_kkt_solve)
-static int kkt_solve_block(padne_ctx *ctx, padne_kkt *k, const int n_cols, const double *r_host, int64_t n_known,
+static int kkt_solve_block(padne_ctx *ctx, padne_kkt *k, const int n_cols, const KktRhs &rhs, int64_t n_known,
                            const int64_t *known_idx, const double *known_val, int32_t n_extra, const int64_t *extra_ptr,
                            const int64_t *extra_row, const double *extra_val, int64_t n_probe, const int64_t *probe_idx,
                            double *probe_out, const padne_solve_opts *opts, double abs_residual_target, padne_solve_info *info) {
-    PADNE_REQUIRE(ctx && k && r_host && opts, "null argument");
+    const double *r_host = rhs.dense;
+    PADNE_REQUIRE(ctx && k && opts, "null argument");
     PADNE_REQUIRE(k->ctx == ctx, "the plan belongs to another context");
+    k->finished = false;
+    PADNE_REQUIRE(r_host != nullptr || rhs.n_entries == 0 || (rhs.row && rhs.col && rhs.val), "null argument");
     PADNE_REQUIRE(n_cols >= 1 && n_extra >= 0 && n_cols + n_extra <= 4096, "at most 4096 right-hand sides with the extra ones");
+    PADNE_REQUIRE(r_host != nullptr || rhs.n_entries >= 0, "number of right-hand side entries");
+    if (r_host == nullptr && rhs.n_entries > 0) {
+        // every (row, column) pair once and inside the block: the scatter below writes each entry of r at most once
+        std::vector<long long> keys((size_t)rhs.n_entries);
+        for (int64_t e = 0; e < rhs.n_entries; ++e) {
+            PADNE_REQUIRE(rhs.row[e] >= 0 && rhs.row[e] < k->N && rhs.col[e] >= 0 && rhs.col[e] < n_cols,
+                          "right-hand side entry out of range");
+            keys[(size_t)e] = (long long)rhs.row[e] * n_cols + rhs.col[e];
+        }
+        std::sort(keys.begin(), keys.end());
+        PADNE_REQUIRE(std::adjacent_find(keys.begin(), keys.end()) == keys.end(), "duplicate (row, column) pair in the right-hand sides");
+    }
     PADNE_REQUIRE(n_known >= 0 && (n_known == 0 || (known_idx && known_val)), "known potentials");
     PADNE_REQUIRE(n_extra == 0 || (extra_ptr && extra_ptr[0] == 0), "extra right-hand sides");
     PADNE_REQUIRE(n_probe >= 0 && (n_probe == 0 || (probe_idx && probe_out)), "probes");
@@ -726,15 +765,36 @@ static int kkt_solve_block(padne_ctx *ctx, padne_kkt *k, const int n_cols, const
     }
     // 1. R crosses PCIe on its own streams, in the caller's layout, while this thread builds what does not depend on it:
     //    1/diag, the x-window plan and the multigrid hierarchy of A (the counterpart of the factorisation)
+    //    (a block given by its entries: r is zeroed and the entries scattered into it on the stream, ahead of that work)
     int up_rc = PADNE_OK;
-    std::thread uploader([&]() {
-        (void)hipSetDevice(ctx->device);
-        up_rc = parallel_copy(k, k->r, r_host, sizeof(double) * (size_t)N * (size_t)n_cols, hipMemcpyHostToDevice);
-    });
+    std::thread uploader;
     struct Join {
         std::thread &t;
         ~Join() { if (t.joinable()) t.join(); }
     } join_guard{uploader};
+    Scratch sc_r(ctx);
+    if (r_host != nullptr) {
+        uploader = std::thread([&]() {
+            (void)hipSetDevice(ctx->device);
+            up_rc = parallel_copy(k, k->r, r_host, sizeof(double) * (size_t)N * (size_t)n_cols, hipMemcpyHostToDevice);
+        });
+    } else {
+        PADNE_HIP_CHECK(hipMemsetAsync(k->r, 0, sizeof(double) * (size_t)N * (size_t)n_cols, s));
+        if (rhs.n_entries > 0) {
+            long long *d_row = nullptr;
+            int32_t *d_col = nullptr;
+            double *d_val = nullptr;
+            PADNE_TRY(sc_r.alloc(&d_row, (size_t)rhs.n_entries));
+            PADNE_TRY(sc_r.alloc(&d_col, (size_t)rhs.n_entries));
+            PADNE_TRY(sc_r.alloc(&d_val, (size_t)rhs.n_entries));
+            PADNE_HIP_CHECK(hipMemcpyAsync(d_row, rhs.row, sizeof(long long) * (size_t)rhs.n_entries, hipMemcpyHostToDevice, s));
+            PADNE_HIP_CHECK(hipMemcpyAsync(d_col, rhs.col, sizeof(int32_t) * (size_t)rhs.n_entries, hipMemcpyHostToDevice, s));
+            PADNE_HIP_CHECK(hipMemcpyAsync(d_val, rhs.val, sizeof(double) * (size_t)rhs.n_entries, hipMemcpyHostToDevice, s));
+            hipLaunchKernelGGL(kkt_scatter_coo, dim3(vgrid(rhs.n_entries)), dim3(256), 0, s, (long long)rhs.n_entries, n_cols, d_row,
+                               d_col, d_val, k->r);
+            PADNE_HIP_CHECK(hipGetLastError());
+        }
+    }
     if ((opts->flags & 4) != 0 && k->A->amg != nullptr) {
         amg_destroy(k->A->amg);
         k->A->amg = nullptr;
@@ -772,7 +832,7 @@ static int kkt_solve_block(padne_ctx *ctx, padne_kkt *k, const int n_cols, const
         PADNE_TRY(csr_build_xw_plan(ctx, const_cast<padne_csr *>(k->L)));
         PADNE_TRY(products(k->c, k->w));                                                 // w = L c
     }
-    uploader.join();
+    if (uploader.joinable()) uploader.join();
     PADNE_TRY(up_rc);
     // 2. b = -P^T (r - L c) for every column, the extra right-hand sides, their norms
     const double *Lc = k->has_c ? k->w : nullptr;
@@ -982,6 +1042,9 @@ static int kkt_finish_block(padne_ctx *ctx, padne_kkt *k, const int n_cols, int3
     PADNE_TRY(down_rc);
     for (int j = 0; j < n_cols; ++j) residual_norms_out[j] = sqrt(norm2[(size_t)j]);
     k->solved = false;
+    k->finished = true;
+    k->v_final = v_out;
+    k->finished_cols = n_cols;
     return PADNE_OK;
 }
 
@@ -989,7 +1052,10 @@ extern "C" int padne_kkt_solve(padne_ctx *ctx, padne_kkt *k, const double *r_hos
                                const double *known_val, int32_t n_extra, const int64_t *extra_ptr, const int64_t *extra_row,
                                const double *extra_val, int64_t n_probe, const int64_t *probe_idx, double *probe_out,
                                const padne_solve_opts *opts, double abs_residual_target, padne_solve_info *info) {
-    return kkt_solve_block(ctx, k, 1, r_host, n_known, known_idx, known_val, n_extra, extra_ptr, extra_row, extra_val, n_probe,
+    KktRhs rhs;
+    rhs.dense = r_host;
+    PADNE_REQUIRE(r_host, "null argument");
+    return kkt_solve_block(ctx, k, 1, rhs, n_known, known_idx, known_val, n_extra, extra_ptr, extra_row, extra_val, n_probe,
                            probe_idx, probe_out, opts, abs_residual_target, info);
 }
 
@@ -998,7 +1064,10 @@ extern "C" int padne_kkt_solve_block(padne_ctx *ctx, padne_kkt *k, int32_t n_col
                                      const int64_t *extra_row, const double *extra_val, int64_t n_probe, const int64_t *probe_idx,
                                      double *probe_out, const padne_solve_opts *opts, double abs_residual_target,
                                      padne_solve_info *info) {
-    return kkt_solve_block(ctx, k, n_cols, r_host, n_known, known_idx, known_val, n_extra, extra_ptr, extra_row, extra_val, n_probe,
+    KktRhs rhs;
+    rhs.dense = r_host;
+    PADNE_REQUIRE(r_host, "null argument");
+    return kkt_solve_block(ctx, k, n_cols, rhs, n_known, known_idx, known_val, n_extra, extra_ptr, extra_row, extra_val, n_probe,
                            probe_idx, probe_out, opts, abs_residual_target, info);
 }
 
@@ -1011,4 +1080,52 @@ extern "C" int padne_kkt_finish_block(padne_ctx *ctx, padne_kkt *k, int32_t n_co
                                       int64_t n_mult, const int64_t *mult_idx, const double *mult_val, double *v_host,
                                       double *residual_norms_out) {
     return kkt_finish_block(ctx, k, n_cols, n_extra, extra_coeff, n_mult, mult_idx, mult_val, v_host, residual_norms_out);
+}
+
+extern "C" int padne_kkt_solve_block_coo(padne_ctx *ctx, padne_kkt *k, int32_t n_cols, int64_t n_entries, const int64_t *r_row,
+                                         const int32_t *r_col, const double *r_val, int64_t n_known, const int64_t *known_idx,
+                                         const double *known_val, int32_t n_extra, const int64_t *extra_ptr, const int64_t *extra_row,
+                                         const double *extra_val, int64_t n_probe, const int64_t *probe_idx, double *probe_out,
+                                         const padne_solve_opts *opts, double abs_residual_target, padne_solve_info *info) {
+    KktRhs rhs;
+    rhs.n_entries = n_entries;
+    rhs.row = r_row;
+    rhs.col = r_col;
+    rhs.val = r_val;
+    return kkt_solve_block(ctx, k, n_cols, rhs, n_known, known_idx, known_val, n_extra, extra_ptr, extra_row, extra_val, n_probe,
+                           probe_idx, probe_out, opts, abs_residual_target, info);
+}
+
+// sigma |grad V|^2 of every column of the finished block, from the V that stage 2 left on the device: one launch over the
+// triangles (power_density_block_kernel), then [n_cols][n_tri] home on the copy streams
+extern "C" int padne_kkt_power_density_block(padne_ctx *ctx, padne_kkt *k, int32_t n_cols, double *out_host) {
+    PADNE_REQUIRE(ctx && k, "null argument");
+    PADNE_REQUIRE(k->ctx == ctx, "the plan belongs to another context");
+    PADNE_REQUIRE(k->finished && k->v_final != nullptr,
+                  "padne_kkt_power_density_block follows padne_kkt_finish_block, with no solve on the plan in between");
+    PADNE_REQUIRE(n_cols == k->finished_cols, "as many columns as the finished block has");
+    const padne_csr *L = k->L;
+    PADNE_REQUIRE(L->mesh_n_mesh > 0 && L->mesh_xy != nullptr,
+                  "the system matrix does not carry a mesh (only padne_assemble_system keeps it)");
+    PADNE_REQUIRE(L->mesh_n_vert <= k->N, "the mesh has more vertices than the system has unknowns");
+    const long long n_tri = L->mesh_n_tri;
+    if (n_tri == 0) return PADNE_OK;
+    PADNE_REQUIRE(out_host != nullptr, "null argument");
+    PADNE_HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    Scratch sc(ctx);
+    double *d_out = nullptr;
+    int *d_bad = nullptr;
+    PADNE_TRY(sc.alloc(&d_out, (size_t)n_tri * (size_t)n_cols));
+    PADNE_TRY(sc.alloc(&d_bad, 1));
+    PADNE_HIP_CHECK(hipMemsetAsync(d_bad, 0, sizeof(int), s));
+    PADNE_TRY(launch_power_density_block(ctx, L, n_cols, k->v_final, d_out, d_bad));
+    int h_bad = 0;
+    PADNE_HIP_CHECK(hipMemcpyAsync(&h_bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    PADNE_HIP_CHECK(hipStreamSynchronize(s));
+    if (h_bad) {
+        set_error("invalid argument: triangle index out of range");
+        return PADNE_E_INVALID;
+    }
+    return parallel_copy(k, out_host, d_out, sizeof(double) * (size_t)n_tri * (size_t)n_cols, hipMemcpyDeviceToHost);
 }

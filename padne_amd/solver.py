@@ -16,6 +16,8 @@ solve_system :767-780 (SuperLU)        reduction to SPD (reduction.py) + Jacobi-
                                        multipliers recovered from device residual products
 produce_layer_solutions :578-615       numpy slice per mesh (contiguous blocks) + power kernel
 compute_power_density :728-745         ``power_density_kernel``
+(several load cases of one board)      ``solve_load_cases``: one assembly and plan, one block solve, the block's
+                                       power densities from the potentials on the device
 =====================================  ====================================================
 
 There is no CPU fallback: every entry point that computes raises
@@ -23,9 +25,13 @@ There is no CPU fallback: every entry point that computes raises
 """
 from __future__ import annotations
 
+import dataclasses
 import logging
+import math
 import threading
+import time
 import warnings
+from collections.abc import Mapping
 from dataclasses import dataclass, field
 from typing import Optional, Sequence
 
@@ -497,12 +503,15 @@ def _stalled(res, rtol: float) -> bool:
     return res.status != _hip.OK and not res.rel_residual <= max(rtol, STALL_WARN_ABOVE)
 
 
-def _stalled_columns(residual_norms: np.ndarray, R: np.ndarray) -> str:
+def _stalled_columns(residual_norms: np.ndarray, R: Optional[np.ndarray] = None, *,
+                     col_norms: Optional[np.ndarray] = None) -> str:
     """Which columns of a block a stall is put down to.  The device reports the reduced solves of a block as a whole (one
     status, the largest relative residual), so this is an ATTRIBUTION, not a per-column status: the columns whose
     ||L v_j - r_j|| exceeds STALL_WARN_ABOVE ||r_j||, or, if none does, the one worst against its own right-hand side.
-    Only called when the block stalled (an O(N k) pass over R)."""
-    rel = residual_norms / np.maximum(np.sqrt(np.einsum("ij,ij->j", R, R)), 1e-300)
+    Only called when the block stalled (an O(N k) pass over a dense R; ``col_norms`` = the ||r_j|| when R is not dense)."""
+    if col_norms is None:
+        col_norms = np.sqrt(np.einsum("ij,ij->j", R, R))
+    rel = residual_norms / np.maximum(col_norms, 1e-300)
     cols = np.flatnonzero(rel > STALL_WARN_ABOVE)
     if not len(cols):
         cols = [int(np.argmax(rel))]
@@ -572,6 +581,47 @@ def solve_system(L, r: np.ndarray, *, rtol: float = RTOL, reorder=None, n_potent
         # multiplier rows take their right-hand side from r (solver.py:505, 530, 560)
         for cst in layout.constraints:
             cst.value = float(r[cst.index])
+    pins = _floating_pins(L, layout, Lc)
+    # O(#constraints): what the reduction eliminates, ties and knows; the index map itself is made on the device.  A block
+    # is reduced once: the structure is the same for every column, the known parts come per column
+    if block:
+        red, known_idx, known_val = build_block_reduction(layout, {cst.index: r[cst.index, :] for cst in layout.constraints},
+                                                          pins)
+    else:
+        red: Reduction = build_reduction(layout, pins)
+    plan = _plan_for(L, dev, layout, red, _wants_reorder(L, reorder), owned)
+    try:
+        members = sorted({int(x) for mem, cons, _ in red.groups if cons for x in mem})
+        extras = [dict(cst.gamma) for cst in red.regulators]
+        if not block:
+            probes, res = plan.solve(r, red.known, extras, members, rtol=rtol, max_iter=MAX_ITER,
+                                     abs_residual_target=ABS_RESIDUAL_TARGET)
+            _warn_if_stalled(res, rtol)
+            i_reg, mult = recover_currents(red, members, probes, 1)
+            v, residual_norm = plan.finish(i_reg[0], mult[0])
+        else:
+            k = r.shape[1]
+            probes, res = plan.solve_block(r, known_idx, known_val, extras, members, rtol=rtol, max_iter=MAX_ITER,
+                                           abs_residual_target=ABS_RESIDUAL_TARGET)
+            v, residual_norms = _finish_block(plan, red, members, probes, k)
+    finally:
+        if owned:
+            plan.close()
+            dev.close()
+    if not block:
+        info = SolverInfo(ground_node_current=float(v[-1]), residual_norm=float(residual_norm),
+                          iterations=int(res.iterations), rel_residual=float(res.rel_residual), solve_seconds=float(res.seconds))
+        return v, info
+    if _stalled(res, rtol):
+        _warn_if_stalled(res, rtol, _stalled_columns(residual_norms, r))
+    info = SolverInfo(ground_node_current=v[-1].copy(), residual_norm=float(np.sqrt(np.sum(residual_norms ** 2))),
+                      iterations=int(res.iterations), rel_residual=float(res.rel_residual), solve_seconds=float(res.seconds),
+                      residual_norms=residual_norms)
+    return v, info
+
+
+def _floating_pins(L, layout: KKTLayout, Lc) -> list:
+    """Unknowns that hold copper nothing ties to the ground node at 0 V (see solve_system)."""
     ground_p = layout.ground_constraint.p
     if Lc is not None:
         pins = floating_component_pins(layout.n_potential, ground_p, layout.constraints, matrix=Lc)
@@ -582,13 +632,10 @@ def solve_system(L, r: np.ndarray, *, rtol: float = RTOL, reorder=None, n_potent
         pins = []
     if pins:
         log.info(f"{len(pins)} floating component(s) held at 0 V at unknown(s) {pins[:8]}")
-    # O(#constraints): what the reduction eliminates, ties and knows; the index map itself is made on the device.  A block
-    # is reduced once: the structure is the same for every column, the known parts come per column
-    if block:
-        red, known_idx, known_val = build_block_reduction(layout, {cst.index: r[cst.index, :] for cst in layout.constraints},
-                                                          pins)
-    else:
-        red: Reduction = build_reduction(layout, pins)
+    return pins
+
+
+def _wants_reorder(L, reorder) -> bool:
     want_reorder = False
     if isinstance(L, SystemMatrix) and L.xy is not None and reorder is not False:
         # CGAL numbers vertices in insertion order; when neighbours are far apart in the numbering the SpMV
@@ -603,6 +650,12 @@ def solve_system(L, r: np.ndarray, *, rtol: float = RTOL, reorder=None, n_potent
             if getattr(L, "_scattered", None) is None:
                 L._scattered = bool(ordering_is_scattered(L.tri, len(L.xy)))
             want_reorder = L._scattered
+    return want_reorder
+
+
+def _plan_for(L, dev, layout: KKTLayout, red: Reduction, want_reorder: bool, owned: bool) -> _hip.KktPlan:
+    """The device plan of ``red`` on ``L``: the one kept with an assembled system when its structure matches, else a new one
+    (kept with the system in its place)."""
     # the plan -- index map, A = -P^T L P and its multigrid hierarchy on the device -- depends on the STRUCTURE of the
     # reduction only (the values of the sources enter through c and r): kept with the assembled system, so a second
     # right-hand side on the same system finds everything in place, like a second solve with a kept factorisation
@@ -633,37 +686,15 @@ def solve_system(L, r: np.ndarray, *, rtol: float = RTOL, reorder=None, n_potent
                 old.close()
             L._plans.clear()
             L._plans[key] = plan
-    try:
-        members = sorted({int(x) for mem, cons, _ in red.groups if cons for x in mem})
-        extras = [dict(cst.gamma) for cst in red.regulators]
-        if not block:
-            probes, res = plan.solve(r, red.known, extras, members, rtol=rtol, max_iter=MAX_ITER,
-                                     abs_residual_target=ABS_RESIDUAL_TARGET)
-            _warn_if_stalled(res, rtol)
-            i_reg, mult = recover_currents(red, members, probes, 1)
-            v, residual_norm = plan.finish(i_reg[0], mult[0])
-        else:
-            k = r.shape[1]
-            probes, res = plan.solve_block(r, known_idx, known_val, extras, members, rtol=rtol, max_iter=MAX_ITER,
-                                           abs_residual_target=ABS_RESIDUAL_TARGET)
-            i_reg, mult = recover_currents(red, members, probes, k)
-            mult_idx = np.asarray(sorted(mult[0]), dtype=np.int64)
-            mult_val = np.array([[m[int(i)] for i in mult_idx] for m in mult], dtype=DTYPE).reshape(k, len(mult_idx))
-            v, residual_norms = plan.finish_block(i_reg, mult_idx, mult_val)
-    finally:
-        if owned:
-            plan.close()
-            dev.close()
-    if not block:
-        info = SolverInfo(ground_node_current=float(v[-1]), residual_norm=float(residual_norm),
-                          iterations=int(res.iterations), rel_residual=float(res.rel_residual), solve_seconds=float(res.seconds))
-        return v, info
-    if _stalled(res, rtol):
-        _warn_if_stalled(res, rtol, _stalled_columns(residual_norms, r))
-    info = SolverInfo(ground_node_current=v[-1].copy(), residual_norm=float(np.sqrt(np.sum(residual_norms ** 2))),
-                      iterations=int(res.iterations), rel_residual=float(res.rel_residual), solve_seconds=float(res.seconds),
-                      residual_norms=residual_norms)
-    return v, info
+    return plan
+
+
+def _finish_block(plan: _hip.KktPlan, red: Reduction, members, probes, k: int):
+    """Stage 2 of a block: the multiplier currents of every column from its probe rows, then (V, ||L v_j - r_j||)."""
+    i_reg, mult = recover_currents(red, members, probes, k)
+    mult_idx = np.asarray(sorted(mult[0]), dtype=np.int64)
+    mult_val = np.array([[m[int(i)] for i in mult_idx] for m in mult], dtype=DTYPE).reshape(k, len(mult_idx))
+    return plan.finish_block(i_reg, mult_idx, mult_val)
 
 
 # --------------------------------------------------------------------------------------------
@@ -702,14 +733,15 @@ def compute_power_density(voltage: mesh.ZeroForm, conductivity: float) -> mesh.T
 
 
 def produce_layer_solutions(layers, vindex: VertexIndexer, meshes, mesh_index_to_layer_index, v: np.ndarray,
-                            disconnected_meshes_by_layer, system: Optional["SystemMatrix"] = None) -> list:
+                            disconnected_meshes_by_layer, system: Optional["SystemMatrix"] = None,
+                            power_all: Optional[np.ndarray] = None) -> list:
     """``solver.py:578-615``.  Each mesh's unknowns are one contiguous block of ``v``, so the scatter
-    is a slice; the power densities of all meshes come from one kernel launch."""
+    is a slice; the power densities of all meshes come from one kernel launch.  ``power_all``: the per-face power
+    densities of all meshes in mesh order when the caller has them already (one case of a block of load cases)."""
     ctx = get_context()
     sig = [layers[mesh_index_to_layer_index[i]].conductance for i in range(len(meshes))]
-    power_all = None
     n_tri = sum(len(m.triangles) for m in meshes)
-    if meshes and n_tri:
+    if power_all is None and meshes and n_tri:
         if system is not None and system.tri is not None and len(system.tri) == n_tri:
             # the system was assembled from these meshes: they are still on the device, only the potentials travel
             power_all = system.dev.power_density(v[:len(vindex)], n_tri)
@@ -771,6 +803,26 @@ def _solve_partitioned(prob, meshes, mesh_index_to_layer_index, vindex, filtered
     return v, info
 
 
+def _warn_ground_current(current: float, where: str = "") -> None:
+    """The reference's soft failure for a ground current away from zero (solver.py:880-888)."""
+    if not np.isclose(current, 0):
+        warnings.warn(
+            f"{where}Ground node current is not zero ({current} A), this may indicate an issue "
+            "with the problem being solved. Check for unterminated current loops or floating connected "
+            "components. This may be harmless if the current is small, but it may indicate an "
+            "ill-conditioned system.", SolverWarning)
+
+
+def _meshed_inputs(prob, meshes, filtered_networks, disconnected_meshes_by_layer):
+    """The defaults of solve_meshed's arguments, and the meshes as :class:`mesh.Mesh`."""
+    meshes = [m if isinstance(m, mesh.Mesh) else mesh.Mesh.from_reference(m) for m in meshes]
+    if filtered_networks is None:
+        filtered_networks = list(prob.networks)
+    if disconnected_meshes_by_layer is None:
+        disconnected_meshes_by_layer = [[] for _ in prob.layers]
+    return meshes, filtered_networks, disconnected_meshes_by_layer
+
+
 def solve_meshed(prob, meshes, mesh_index_to_layer_index, *, filtered_networks=None,
                  disconnected_meshes_by_layer=None, partition=None) -> Solution:
     """Steps 4-11 of the reference's ``solve()`` (``solver.py:846-902``): everything after meshing.
@@ -778,11 +830,8 @@ def solve_meshed(prob, meshes, mesh_index_to_layer_index, *, filtered_networks=N
     ``partition``: a :class:`padne_amd.distributed.Partition` -- the rows are dealt to the GPUs of the node (by layer, or
     by strips of layers when there are fewer layers than GPUs); every rank calls this with the same Problem and gets the
     same Solution."""
-    meshes = [m if isinstance(m, mesh.Mesh) else mesh.Mesh.from_reference(m) for m in meshes]
-    if filtered_networks is None:
-        filtered_networks = list(prob.networks)
-    if disconnected_meshes_by_layer is None:
-        disconnected_meshes_by_layer = [[] for _ in prob.layers]
+    meshes, filtered_networks, disconnected_meshes_by_layer = _meshed_inputs(prob, meshes, filtered_networks,
+                                                                             disconnected_meshes_by_layer)
     log.info("Indexing vertices and connections")
     vindex = VertexIndexer.create(meshes)
     node_indexer = NodeIndexer.create(prob, meshes, mesh_index_to_layer_index, vindex, filtered_networks)
@@ -790,12 +839,7 @@ def solve_meshed(prob, meshes, mesh_index_to_layer_index, *, filtered_networks=N
         ctx = get_context()
         v, solver_info = _solve_partitioned(prob, meshes, mesh_index_to_layer_index, vindex, filtered_networks,
                                             node_indexer, partition, ctx)
-        if not np.isclose(solver_info.ground_node_current, 0):
-            warnings.warn(
-                f"Ground node current is not zero ({solver_info.ground_node_current} A), this may indicate an issue "
-                "with the problem being solved. Check for unterminated current loops or floating connected "
-                "components. This may be harmless if the current is small, but it may indicate an "
-                "ill-conditioned system.", SolverWarning)
+        _warn_ground_current(solver_info.ground_node_current)
         layer_solutions = produce_layer_solutions(prob.layers, vindex, meshes, mesh_index_to_layer_index, v,
                                                   disconnected_meshes_by_layer)
         return Solution(problem=prob, layer_solutions=layer_solutions, solver_info=solver_info)
@@ -807,12 +851,7 @@ def solve_meshed(prob, meshes, mesh_index_to_layer_index, *, filtered_networks=N
     except BaseException:
         L.close()
         raise
-    if not np.isclose(solver_info.ground_node_current, 0):
-        warnings.warn(
-            f"Ground node current is not zero ({solver_info.ground_node_current} A), this may indicate an issue "
-            "with the problem being solved. Check for unterminated current loops or floating connected "
-            "components. This may be harmless if the current is small, but it may indicate an "
-            "ill-conditioned system.", SolverWarning)
+    _warn_ground_current(solver_info.ground_node_current)
     log.info("Producing the solution object")
     try:
         # the mesh is still on the device with the assembled system: the power densities need only the potentials
@@ -831,6 +870,13 @@ def solve(prob, mesher_config: Optional[mesh.Mesher.Config] = None, *, mesher=No
     so does :class:`padne_amd.structured.StructuredMesher` for rectangles and annuli); every
     polygon of every layer is meshed and treated as connected.
     """
+    meshes, mesh_index_to_layer_index = _mesh_problem(prob, mesher_config, mesher)
+    return solve_meshed(prob, meshes, mesh_index_to_layer_index, partition=partition)
+
+
+def _mesh_problem(prob, mesher_config, mesher):
+    """Steps 1-3 of the reference's ``solve()``: every polygon of every layer meshed, with the connections of its layer as
+    seeds.  Returns (meshes, mesh_index_to_layer_index)."""
     if mesher is None:
         mesher = mesh.Mesher(mesher_config)
     meshes, mesh_index_to_layer_index = [], []
@@ -841,4 +887,233 @@ def solve(prob, mesher_config: Optional[mesh.Mesher.Config] = None, *, mesher=No
         for geom in layer.geoms:
             meshes.append(mesher.poly_to_mesh(geom, seeds))
             mesh_index_to_layer_index.append(layer_i)
-    return solve_meshed(prob, meshes, mesh_index_to_layer_index, partition=partition)
+    return meshes, mesh_index_to_layer_index
+
+
+# --------------------------------------------------------------------------------------------
+# load cases: one board, several settings of its sources
+# --------------------------------------------------------------------------------------------
+
+# What a load case may set, by source kind: the values that enter r and nothing else (solver.py:483-484, 490, 503).  A
+# resistance, a regulator's gain or a layer's conductance enters L, which all cases of a block share.
+CASE_FIELDS = {"CurrentSource": "current", "VoltageSource": "voltage", "VoltageRegulator": "voltage"}
+
+
+def _ground_terminal(networks, case: dict):
+    """The NodeID find_best_ground_node_index grounds, with the values of ``case`` substituted (None: no voltage source)."""
+    best, node = float("-inf"), None
+    for network in networks:
+        for element in network.elements:
+            if element_kind(element) == "VoltageSource":
+                voltage = case.get(element, element.voltage)
+                if voltage > best:
+                    best, node = voltage, element.n
+    return node
+
+
+def check_load_cases(prob, cases) -> list:
+    """The load cases of ``prob`` as a list of ``{element: float}``, or ValueError.
+
+    ``cases`` is a non-empty sequence of mappings ``{element: value}``; the keys are source elements of ``prob.networks``
+    (looked up like ``NodeIndexer.extra_source_to_global_index`` looks them up), the value is the ``current`` of a
+    CurrentSource or the ``voltage`` of a VoltageSource / VoltageRegulator.  An element that would change L, one that is
+    not in the Problem, a value that is not finite, and a case that moves the ground node (the ``n`` terminal of the
+    highest-voltage source, which L stamps) are refused."""
+    if isinstance(cases, (Mapping, str, bytes)):
+        raise ValueError("cases must be a sequence of mappings {element: value}, one per load case")
+    cases = list(cases)
+    if not cases:
+        raise ValueError("no load cases: give at least one mapping {element: value} ({} is the Problem as given)")
+    elements = {element for network in prob.networks for element in network.elements}
+    out = []
+    for j, case in enumerate(cases):
+        if not isinstance(case, Mapping):
+            raise ValueError(f"load case {j} is not a mapping {{element: value}}")
+        values = {}
+        for element, value in case.items():
+            kind = element_kind(element)
+            if kind not in CASE_FIELDS:
+                raise ValueError(f"load case {j}: a {type(element).__name__} cannot vary between load cases -- only the current "
+                                 "of a CurrentSource and the voltage of a VoltageSource or VoltageRegulator leave the system "
+                                 "matrix L as it is")
+            if element not in elements:
+                raise ValueError(f"load case {j}: the {kind} is not an element of the Problem's networks")
+            try:
+                x = float(value)
+            except (TypeError, ValueError):
+                raise ValueError(f"load case {j}: the {CASE_FIELDS[kind]} of a {kind} must be a number, not {value!r}") from None
+            if not math.isfinite(x):
+                raise ValueError(f"load case {j}: the {CASE_FIELDS[kind]} of a {kind} must be finite, not {value!r}")
+            values[element] = x
+        out.append(values)
+    ground = _ground_terminal(prob.networks, {})
+    for j, values in enumerate(out):
+        if _ground_terminal(prob.networks, values) is not ground:
+            raise ValueError(f"load case {j} changes which voltage source is the highest, and with it the ground node that L "
+                             "stamps (solver.py:671-686); cases share one L")
+    return out
+
+
+def substitute_load_case(prob, case: dict):
+    """``prob`` with the values of one checked load case: the named elements replaced (``dataclasses.replace``), the networks
+    that hold them rebuilt around the same NodeIDs and connections, the layers shared.  Returns (problem, {id(old network):
+    new network})."""
+    if not case:
+        return prob, {}
+    networks, renamed = [], {}
+    for network in prob.networks:
+        if any(element in case for element in network.elements):
+            elements = [dataclasses.replace(e, **{CASE_FIELDS[element_kind(e)]: case[e]}) if e in case else e
+                        for e in network.elements]
+            renamed[id(network)] = dataclasses.replace(network, elements=elements)
+            networks.append(renamed[id(network)])
+        else:
+            networks.append(network)
+    return dataclasses.replace(prob, networks=networks), renamed
+
+
+def stamp_load_cases(filtered_networks, node_indexer: NodeIndexer, n_unknowns: int, cases: list):
+    """The block R (n_unknowns, k) of the checked load ``cases`` as COO triples ``(rows, cols, vals)``: column j is the ``r``
+    that stamp_network_into_system and setup_ground_node give for the Problem with case j substituted, entry for entry --
+    the same stamps in the same order (``r[iv] = voltage`` for a voltage source, ``+=`` for regulators and current
+    sources), duplicates summed as they are stamped.  Entries are listed case by case, each row where it is first stamped;
+    zeros are left out."""
+    idx, extra = node_indexer.node_to_global_index, node_indexer.extra_source_to_global_index
+    program = []            # (row, assign, negate, element, field): the r stamps of solver.py:469-541, in stamping order
+    for network in filtered_networks:
+        for element in network.elements:
+            kind = element_kind(element)
+            if kind == "CurrentSource":
+                program.append((idx[element.f], False, False, element, "current"))
+                program.append((idx[element.t], False, True, element, "current"))
+            elif kind == "VoltageSource":
+                program.append((extra[element], True, False, element, "voltage"))
+            elif kind == "VoltageRegulator":
+                program.append((extra[element], False, False, element, "voltage"))
+    rows, cols, vals = [], [], []
+    for j, case in enumerate(cases):
+        r: dict = {}
+        for row, assign, negate, element, name in program:
+            x = float(case[element]) if element in case else float(getattr(element, name))
+            if assign:
+                r[row] = x
+            else:
+                r[row] = r.get(row, 0.0) + (-x if negate else x)
+        r[int(n_unknowns) - 1] = 0.0                  # setup_ground_node
+        for row, x in r.items():
+            if x != 0.0:
+                rows.append(row)
+                cols.append(j)
+                vals.append(x)
+    return np.asarray(rows, dtype=np.int64), np.asarray(cols, dtype=np.int32), np.asarray(vals, dtype=DTYPE)
+
+
+def load_case_constraint_values(layout: KKTLayout, rows, cols, vals, k: int) -> dict:
+    """``{cst.index: R[cst.index, :]}`` of the block given by its triples, what build_block_reduction takes."""
+    values = {cst.index: np.zeros(int(k), dtype=DTYPE) for cst in layout.constraints}
+    for row, col, val in zip(np.asarray(rows).tolist(), np.asarray(cols).tolist(), np.asarray(vals).tolist()):
+        column = values.get(row)
+        if column is not None:
+            column[col] = val
+    return values
+
+
+def _solve_load_case_block(L: SystemMatrix, rows, cols, vals, k: int, timings: Optional[dict] = None):
+    """solve_system on the block given by its triples, then the power densities of every column from the V stage 2 left on
+    the device.  Returns (V (N, k), ||L v_j - r_j|| (k,), SolveResult, power (k, n_tri) or None without triangles)."""
+    t0 = time.perf_counter()
+    layout = L.layout
+    if layout is None or not layout.constraints:
+        raise SingularSystemError("system has no ground constraint")
+    pins = _floating_pins(L, layout, None)
+    red, known_idx, known_val = build_block_reduction(layout, load_case_constraint_values(layout, rows, cols, vals, k), pins)
+    plan = _plan_for(L, L.dev, layout, red, _wants_reorder(L, None), False)
+    members = sorted({int(x) for mem, cons, _ in red.groups if cons for x in mem})
+    extras = [dict(cst.gamma) for cst in red.regulators]
+    n_tri = len(L.tri) if L.tri is not None else 0
+    probes, res = plan.solve_block_coo(k, rows, cols, vals, known_idx, known_val, extras, members, rtol=RTOL, max_iter=MAX_ITER,
+                                       abs_residual_target=ABS_RESIDUAL_TARGET, power_tri=n_tri)
+    t1 = time.perf_counter()
+    V, residual_norms = _finish_block(plan, red, members, probes, k)
+    t2 = time.perf_counter()
+    power = plan.power_density_block(k, n_tri) if n_tri else None
+    if timings is not None:
+        timings.update(stage1=t1 - t0, stage2=t2 - t1, power_density=time.perf_counter() - t2)
+    return V, residual_norms, res, power
+
+
+def solve_meshed_load_cases(prob, meshes, mesh_index_to_layer_index, cases, *, filtered_networks=None,
+                            disconnected_meshes_by_layer=None, partition=None) -> list:
+    """``solve_meshed`` for several load cases of one board: a list of Solutions, one per mapping of ``cases`` (see
+    :func:`check_load_cases`; elements a case does not name keep their Problem value, and an element whose network is not
+    among ``filtered_networks`` has no effect, as in the Problem itself).
+
+    The connections are snapped, L assembled and its reduction planned once; the cases go through one block solve whose
+    right-hand sides cross to the device as their non-zero entries, and the power densities of all cases are computed from
+    the potentials the device holds.  Solution j carries the Problem with case j substituted, its own potentials and power
+    densities, and a SolverInfo whose ``ground_node_current`` and ``residual_norm`` are its own while ``iterations``,
+    ``rel_residual`` and ``solve_seconds`` are those of the block solve as a whole (``residual_norms`` is None).  One case
+    is ``solve_meshed`` on its substituted Problem.  ValueError, before anything reaches the device, for invalid cases and
+    for a ``partition`` over several GPUs (the row-partitioned path does not take load cases)."""
+    return _load_case_solutions(prob, meshes, mesh_index_to_layer_index, cases, filtered_networks, disconnected_meshes_by_layer,
+                                partition)
+
+
+def _load_case_solutions(prob, meshes, mesh_index_to_layer_index, cases, filtered_networks, disconnected_meshes_by_layer,
+                         partition, timings: Optional[dict] = None) -> list:
+    """solve_meshed_load_cases; ``timings`` (a dict) receives the host time of each step in seconds."""
+    if partition is not None and partition.world > 1:
+        raise ValueError("load cases are solved on one GPU: the row-partitioned path (partition.world > 1) does not take them")
+    cases = check_load_cases(prob, cases)
+    substituted = [substitute_load_case(prob, case) for case in cases]
+    if len(cases) == 1:
+        sub, renamed = substituted[0]
+        if filtered_networks is not None:
+            filtered_networks = [renamed.get(id(network), network) for network in filtered_networks]
+        return [solve_meshed(sub, meshes, mesh_index_to_layer_index, filtered_networks=filtered_networks,
+                             disconnected_meshes_by_layer=disconnected_meshes_by_layer)]
+    k = len(cases)
+    t0 = time.perf_counter()
+    meshes, filtered_networks, disconnected_meshes_by_layer = _meshed_inputs(prob, meshes, filtered_networks,
+                                                                             disconnected_meshes_by_layer)
+    log.info("Indexing vertices and connections")
+    vindex = VertexIndexer.create(meshes)
+    node_indexer = NodeIndexer.create(prob, meshes, mesh_index_to_layer_index, vindex, filtered_networks)
+    t1 = time.perf_counter()
+    log.info("Assembling the global system")
+    L, _ = assemble_system(prob, meshes, mesh_index_to_layer_index, vindex, filtered_networks, node_indexer)
+    try:
+        rows, cols, vals = stamp_load_cases(filtered_networks, node_indexer, L.shape[0], cases)
+        t2 = time.perf_counter()
+        log.info(f"Solving {k} load cases as one block")
+        V, residual_norms, res, power = _solve_load_case_block(L, rows, cols, vals, k, timings)
+    finally:
+        L.close()
+    t3 = time.perf_counter()
+    if _stalled(res, RTOL):
+        col_norms = np.sqrt(np.bincount(cols, weights=vals * vals, minlength=k))
+        _warn_if_stalled(res, RTOL, _stalled_columns(residual_norms, col_norms=col_norms))
+    log.info("Producing the solution objects")
+    solutions = []
+    for j, (sub, _) in enumerate(substituted):
+        ground_node_current = float(V[-1, j])
+        _warn_ground_current(ground_node_current, f"Load case {j}: ")
+        info = SolverInfo(ground_node_current=ground_node_current, residual_norm=float(residual_norms[j]),
+                          iterations=int(res.iterations), rel_residual=float(res.rel_residual), solve_seconds=float(res.seconds))
+        layer_solutions = produce_layer_solutions(prob.layers, vindex, meshes, mesh_index_to_layer_index, V[:, j],
+                                                  disconnected_meshes_by_layer,
+                                                  power_all=None if power is None else power[j])
+        solutions.append(Solution(problem=sub, layer_solutions=layer_solutions, solver_info=info))
+    if timings is not None:
+        timings.update(indexing=t1 - t0, assembly=t2 - t1, solutions=time.perf_counter() - t3)
+    return solutions
+
+
+def solve_load_cases(prob, cases, mesher_config: Optional[mesh.Mesher.Config] = None, *, mesher=None,
+                     partition=None) -> list:
+    """``solve`` for several load cases of one board (see :func:`solve_meshed_load_cases`): the board is meshed once."""
+    if partition is not None and partition.world > 1:
+        raise ValueError("load cases are solved on one GPU: the row-partitioned path (partition.world > 1) does not take them")
+    cases = check_load_cases(prob, cases)
+    meshes, mesh_index_to_layer_index = _mesh_problem(prob, mesher_config, mesher)
+    return solve_meshed_load_cases(prob, meshes, mesh_index_to_layer_index, cases)
