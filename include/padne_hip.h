@@ -337,6 +337,18 @@ int padne_kkt_solve_block_coo(padne_ctx *ctx, padne_kkt *plan, int32_t n_cols, i
  * crosses PCIe but the result.  PADNE_E_INVALID when no block has been finished since the last solve, when n_cols is not
  * that block's, or when `L` carries no mesh. */
 int padne_kkt_power_density_block(padne_ctx *ctx, padne_kkt *plan, int32_t n_cols, double *out_host);
+/* Adjoint sensitivities over the mesh `L` keeps, from the block the last padne_kkt_finish_block left on the device: column 0
+ * of V is the solution x, the other columns are the solutions the adjoints are combined from.  Adjoint j is
+ * lambda_j = sum_m weights[j][m] V[:, m] (weights[n_obj][n_cols] row-major; a selection when L is symmetric, the Woodbury
+ * combination when regulators make it unsymmetric), formed per face in registers, never as an N-vector.  Per face f, with
+ * the assembly's cot weights w_ik = |cot|/2 of the corner opposite edge (i,k) and the sheet conductance sigma of its mesh,
+ * s_j,f = sigma sum_{edges of f} w_ik (lambda_j,i - lambda_j,k)(x_i - x_k) = sigma dJ_j / dsigma_f.  Writes
+ * power_out[n_tri] (column 0's sigma |grad V|^2, bit-identical to padne_csr_power_density on V[:, 0]),
+ * density_out[n_obj][n_tri] = s_j,f / area_f and mesh_total_out[n_obj][n_mesh] = the sum of s_j,f over each mesh, summed
+ * in a fixed order (no floating-point atomics: two calls give the same bits).  Preconditions and errors as
+ * padne_kkt_power_density_block; 1 <= n_obj <= 4096 and finite weights, else PADNE_E_INVALID. */
+int padne_kkt_sensitivity_block(padne_ctx *ctx, padne_kkt *plan, int32_t n_cols, int32_t n_obj, const double *weights,
+                                double *power_out, double *density_out, double *mesh_total_out);
 
 /* Row-partitioned runs, optional: attach the rank's owned x owned diagonal block; with precond = 1 the
  * multigrid hierarchy is then built on that block only (block-Jacobi with multigrid blocks, no

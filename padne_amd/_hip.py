@@ -112,6 +112,7 @@ SIGNATURES = {
                                             _PI64, _PF64, _I64, _PI64, _PF64, C.POINTER(SolveOpts), C.c_double,
                                             C.POINTER(SolveInfo)]),
     "padne_kkt_power_density_block": (C.c_int, [_P, _P, C.c_int32, _PF64]),
+    "padne_kkt_sensitivity_block": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _PF64, _PF64, _PF64, _PF64]),
     "padne_amg_apply": (C.c_int, [_P, _P, _PF64, _PF64]),
     "padne_csr_set_preconditioner_block": (C.c_int, [_P, _P]),
     "padne_amg_level": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(_P)]),
@@ -656,11 +657,13 @@ class KktPlan:
         return self._stage1(R.shape[1], R, kidx, kval, extras, probes, rtol, max_iter, precond, abs_residual_target, rebuild)
 
     def solve_block_coo(self, n_cols, rows, cols, vals, known_idx, known_val, extras: list, probes, *, rtol=1e-12,
-                        max_iter=200000, precond="amg", abs_residual_target=0.0, rebuild=False, power_tri: int = 0):
+                        max_iter=200000, precond="amg", abs_residual_target=0.0, rebuild=False, power_tri: int = 0,
+                        power_rows: int = 0):
         """``solve_block`` with the block (N, n_cols) given by its non-zero entries: R[rows[e], cols[e]] = vals[e], each (row,
         column) pair at most once.  Only the triples cross PCIe; the device zeroes its block and scatters them.
         ``power_tri``: the triangles of the mesh the system carries, when ``power_density_block`` will follow -- its result
-        array is then made ready while the device solves, like V's."""
+        array is then made ready while the device solves, like V's (``power_rows`` rows of it instead of n_cols: 1 + the
+        objectives of a ``sensitivity_block``)."""
         rows, cols, vals = _i64(rows).reshape(-1), _i32(cols).reshape(-1), _f64(vals).reshape(-1)
         if not (rows.shape == cols.shape == vals.shape):
             raise ValueError("rows, cols and vals must have equal length")
@@ -670,10 +673,10 @@ class KktPlan:
         kidx = _i64(known_idx)
         kval = _f64(known_val).reshape(n_cols, kidx.shape[0])
         return self._stage1(n_cols, (rows, cols, vals), kidx, kval, extras, probes, rtol, max_iter, precond,
-                            abs_residual_target, rebuild, power_tri=int(power_tri))
+                            abs_residual_target, rebuild, power_tri=int(power_tri), power_rows=int(power_rows))
 
     def _stage1(self, n_cols, r, kidx, kval, extras, probes, rtol, max_iter, precond, abs_residual_target, rebuild,
-                power_tri=0):
+                power_tri=0, power_rows=0):
         ptr, rows, vals = [0], [], []
         for col in extras:
             for row, val in col.items():
@@ -690,7 +693,8 @@ class KktPlan:
         coo = isinstance(r, tuple)
         v_shape = (self.N, n_cols) if coo else r.shape
         self._v_next, self._v_toucher = _prefaulted(v_shape)
-        self._pd_next, self._pd_toucher = _prefaulted((n_cols, power_tri)) if coo and power_tri > 0 else (None, None)
+        self._pd_next, self._pd_toucher = (_prefaulted((power_rows or n_cols, power_tri)) if coo and power_tri > 0
+                                           else (None, None))
         lib, common = self.ctx._lib, (kidx.shape[0], _ptr(kidx, _PI64), _ptr(kval, _PF64), len(extras),
                                       _ptr(ptr, _PI64), _ptr(rows, _PI64), _ptr(vals, _PF64), pidx.shape[0], _ptr(pidx, _PI64),
                                       _ptr(out, _PF64), C.byref(opts), float(abs_residual_target), C.byref(info))
@@ -732,6 +736,29 @@ class KktPlan:
             out = np.empty((int(n_cols), n_tri), dtype=np.float64)
         _check(self.ctx._lib.padne_kkt_power_density_block(self.ctx._h, self._h, int(n_cols), _ptr(out, _PF64)))
         return out
+
+    def sensitivity_block(self, weights, n_tri: int, n_mesh: int):
+        """Adjoint sensitivities from the block the last ``finish_block`` left on the device, over the mesh the system was
+        assembled from (``n_tri`` triangles in ``n_mesh`` meshes): adjoint j is sum_m weights[j, m] V[:, m] for ``weights``
+        (n_obj, n_cols).  Returns (power (n_tri,) of column 0, bit-identical to ``CsrMatrix.power_density`` of V[:, 0];
+        s_f / area_f (n_obj, n_tri); per-mesh sums of s_f (n_obj, n_mesh)), s_f = sigma dJ_j / dsigma_f (include/padne_hip.h).
+        Raises ValueError as ``power_density_block`` does, and for weights that are not finite."""
+        W = _f64(weights)
+        if W.ndim != 2 or W.shape[0] < 1:
+            raise ValueError("weights must have shape (n_obj, n_cols) with n_obj >= 1")
+        toucher, power = getattr(self, "_pd_toucher", None), getattr(self, "_pd_next", None)
+        self._pd_next, self._pd_toucher = None, None
+        for t in toucher or ():
+            t.join()
+        n_obj, n_tri = W.shape[0], int(n_tri)
+        density = power[1:] if power is not None and power.shape == (n_obj + 1, n_tri) else None
+        if density is None:
+            power = np.empty((n_obj + 1, n_tri), dtype=np.float64)
+            density = power[1:]
+        totals = np.empty((n_obj, int(n_mesh)), dtype=np.float64)
+        _check(self.ctx._lib.padne_kkt_sensitivity_block(self.ctx._h, self._h, W.shape[1], n_obj, _ptr(W, _PF64),
+                                                         _ptr(power[0], _PF64), _ptr(density, _PF64), _ptr(totals, _PF64)))
+        return power[0], density, totals
 
     def finish(self, extra_coeff, multipliers: dict):
         """Stage 2: (v, ||L v - r||)."""

@@ -2244,6 +2244,123 @@ __global__ __launch_bounds__(256) void power_density_block_kernel(long long n_tr
     }
 }
 
+// Adjoint sensitivities of potential differences J_j to the conductance of every face ("Sensitivities").  The
+// block V[n_vert..][n_cols] holds x in column 0 and the solutions the adjoints are combined from; adjoint j is
+// lambda_j = sum_m W[j][m] V[:, m], formed per corner in registers only.  Per face, with the cot weights of the assembly
+// (cot_half, the |cot|/2 of the corner opposite each edge) and the layer's sigma:
+//     s_j = sigma * sum_{edges (i,k)} w_ik (lambda_j,i - lambda_j,k) (x_i - x_k)          (= sigma dJ_j / dsigma_face)
+// out: power[t] of column 0 with the arithmetic of power_density_kernel (hence its bits), density[j][t] = s_j / area, and
+// partial[j][b] = the sum of s_j over block b's faces in a fixed order.  The blocks are tiles of one mesh each (tile_off:
+// the first block of every mesh), so the per-mesh totals need no atomics: sensitivity_mesh_fold sums a mesh's tiles.  The
+// objectives go in chunks of kSensObjChunk and the columns in chunks of kPowerChunk: registers grow with neither.
+constexpr int kSensObjChunk = 4;
+
+__global__ __launch_bounds__(256) void sensitivity_block_kernel(
+    int n_mesh, const long long *__restrict__ tile_off, const int *__restrict__ tri, const double *__restrict__ xy,
+    const long long *__restrict__ mesh_voff, const long long *__restrict__ mesh_toff, const double *__restrict__ sigma,
+    const long long n_tri, const long long n_blocks, const int n_cols, const int n_obj, const double *__restrict__ W,
+    const double *__restrict__ V, double *__restrict__ power, double *__restrict__ density, double *__restrict__ partial,
+    int *__restrict__ err) {
+    __shared__ double red[kSensObjChunk][4];
+    const long long b = blockIdx.x;
+    const int m = find_segment(tile_off, n_mesh, b);
+    const long long t = mesh_toff[m] + (b - tile_off[m]) * 256 + threadIdx.x;
+    bool live = t < mesh_toff[m + 1];
+    const long long v0 = mesh_voff[m];
+    const long long nv = mesh_voff[m + 1] - v0;
+    long long g1 = 0, g2 = 0, g3 = 0;
+    if (live) {
+        const int l1 = tri[3 * t + 2], l2 = tri[3 * t], l3 = tri[3 * t + 1];
+        if (l1 < 0 || l2 < 0 || l3 < 0 || l1 >= nv || l2 >= nv || l3 >= nv) {
+            *(volatile int *)err = 1;
+            live = false;                       // (no return: every thread takes part in the block sums below)
+        } else {
+            g1 = v0 + l1;
+            g2 = v0 + l2;
+            g3 = v0 + l3;
+        }
+    }
+    double x1 = 0, y1 = 0, x2 = 0, y2 = 0, x3 = 0, y3 = 0, u1 = 0, u2 = 0, u3 = 0;
+    double w12 = 0, w23 = 0, w31 = 0, area = 1, s = 0;
+    const double *p1 = V + g1 * n_cols, *p2 = V + g2 * n_cols, *p3 = V + g3 * n_cols;
+    if (live) {
+        x1 = xy[2 * g1]; y1 = xy[2 * g1 + 1];
+        x2 = xy[2 * g2]; y2 = xy[2 * g2 + 1];
+        x3 = xy[2 * g3]; y3 = xy[2 * g3 + 1];
+        s = sigma[m];
+        u1 = p1[0]; u2 = p2[0]; u3 = p3[0];
+        double gx, gy;
+        face_gradient_of(x1, y1, x2, y2, x3, y3, u1, u2, u3, gx, gy);
+        power[t] = face_power_of(gx, gy, s);
+        // the assembly's weights: (tri[0], tri[1], tri[2]) = corners (2, 3, 1) here
+        w23 = cot_half(x2, y2, x3, y3, x1, y1);     // edge 2-3, opposite 1
+        w31 = cot_half(x3, y3, x1, y1, x2, y2);     // edge 3-1, opposite 2
+        w12 = cot_half(x1, y1, x2, y2, x3, y3);     // edge 1-2, opposite 3
+        area = fabs((x2 - x1) * (y3 - y1) - (y2 - y1) * (x3 - x1)) / 2;
+    }
+    const double d12 = u1 - u2, d23 = u2 - u3, d31 = u3 - u1;
+    for (int j0 = 0; j0 < n_obj; j0 += kSensObjChunk) {
+        double a1[kSensObjChunk], a2[kSensObjChunk], a3[kSensObjChunk];
+#pragma unroll
+        for (int q = 0; q < kSensObjChunk; ++q) a1[q] = a2[q] = a3[q] = 0.0;
+        if (live) {
+            for (int c0 = 0; c0 < n_cols; c0 += kPowerChunk) {
+                double f1[kPowerChunk], f2[kPowerChunk], f3[kPowerChunk];
+#pragma unroll
+                for (int c = 0; c < kPowerChunk; ++c)
+                    if (c0 + c < n_cols) {
+                        f1[c] = p1[c0 + c];
+                        f2[c] = p2[c0 + c];
+                        f3[c] = p3[c0 + c];
+                    }
+#pragma unroll
+                for (int q = 0; q < kSensObjChunk; ++q)
+                    if (j0 + q < n_obj) {
+                        const double *w = W + (long long)(j0 + q) * n_cols + c0;
+#pragma unroll
+                        for (int c = 0; c < kPowerChunk; ++c)
+                            if (c0 + c < n_cols) {
+                                a1[q] += w[c] * f1[c];
+                                a2[q] += w[c] * f2[c];
+                                a3[q] += w[c] * f3[c];
+                            }
+                    }
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < kSensObjChunk; ++q) {
+            double sj = 0.0;
+            if (live && j0 + q < n_obj) {
+                sj = s * ((w12 * (a1[q] - a2[q]) * d12 + w23 * (a2[q] - a3[q]) * d23) + w31 * (a3[q] - a1[q]) * d31);
+                density[(long long)(j0 + q) * n_tri + t] = sj / area;
+            }
+            for (int off = 32; off > 0; off >>= 1) sj += __shfl_down(sj, off, 64);
+            if ((threadIdx.x & 63) == 0) red[q][threadIdx.x >> 6] = sj;
+        }
+        __syncthreads();
+        if (threadIdx.x < kSensObjChunk && j0 + (int)threadIdx.x < n_obj) {
+            const int q = threadIdx.x;
+            partial[(long long)(j0 + q) * n_blocks + b] = (red[q][0] + red[q][1]) + (red[q][2] + red[q][3]);
+        }
+        __syncthreads();
+    }
+}
+
+// total[j][m] = the sum of partial[j][tile_off[m] .. tile_off[m+1]) in a fixed order: one workgroup per (mesh, objective)
+__global__ __launch_bounds__(256) void sensitivity_mesh_fold(int n_mesh, const long long *__restrict__ tile_off,
+                                                             const long long n_blocks, const double *__restrict__ partial,
+                                                             double *__restrict__ total) {
+    __shared__ double red[4];
+    const int m = blockIdx.x, j = blockIdx.y;
+    const double *p = partial + (long long)j * n_blocks;
+    double s = 0.0;
+    for (long long i = tile_off[m] + threadIdx.x; i < tile_off[m + 1]; i += 256) s += p[i];
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) total[(long long)j * n_mesh + m] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
 // ---- host orchestration ----------------------------------------------------------------------
 // shared tail: slots (key,val,slot_ptr) already filled -> merged CSR
 // padne_assemble_system_ex(flags & 1): the triangles are a rank's piece of a larger mesh (owned vertices + the ring of
@@ -2791,6 +2908,36 @@ int launch_power_density_block(padne_ctx *ctx, const padne_csr *m, int n_cols, c
                        m->mesh_tri, m->mesh_xy, (int)m->mesh_n_mesh, m->mesh_voff, m->mesh_toff, m->mesh_sigma, n_cols, V_dev,
                        out_dev, bad_dev);
     PADNE_HIP_CHECK(hipGetLastError());
+    return PADNE_OK;
+}
+
+// sensitivity_block_kernel + sensitivity_mesh_fold over the mesh `m` keeps.  tile_off_host[mesh_n_mesh + 1]: the first
+// 256-triangle tile of every mesh (a host array); W_dev[n_obj][n_cols], V_dev[mesh_n_vert..][n_cols], power_dev[mesh_n_tri],
+// density_dev[n_obj][mesh_n_tri], total_dev[n_obj][mesh_n_mesh] (device).  Asynchronous; bad_dev as above.
+int launch_sensitivity_block(padne_ctx *ctx, const padne_csr *m, const long long *tile_off_host, int n_cols, int n_obj,
+                             const double *W_dev, const double *V_dev, double *power_dev, double *density_dev, double *total_dev,
+                             int *bad_dev) {
+    PADNE_REQUIRE(m->mesh_n_mesh > 0 && m->mesh_xy != nullptr, "the matrix does not carry a mesh (only padne_assemble_system keeps it)");
+    const int n_mesh = (int)m->mesh_n_mesh;
+    const long long n_blocks = tile_off_host[n_mesh];
+    if (n_cols == 0 || n_obj == 0) return PADNE_OK;
+    hipStream_t s = ctx->stream;
+    Scratch sc(ctx);
+    long long *d_tile = nullptr;
+    double *d_partial = nullptr;
+    PADNE_TRY(sc.alloc(&d_tile, (size_t)n_mesh + 1));
+    PADNE_TRY(sc.alloc(&d_partial, (size_t)n_obj * (size_t)(n_blocks > 0 ? n_blocks : 1)));
+    PADNE_HIP_CHECK(hipMemcpyAsync(d_tile, tile_off_host, sizeof(long long) * ((size_t)n_mesh + 1), hipMemcpyHostToDevice, s));
+    if (n_blocks > 0) {
+        hipLaunchKernelGGL(sensitivity_block_kernel, dim3((unsigned)n_blocks), dim3(256), 0, s, n_mesh, (const long long *)d_tile,
+                           m->mesh_tri, m->mesh_xy, m->mesh_voff, m->mesh_toff, m->mesh_sigma, (long long)m->mesh_n_tri, n_blocks,
+                           n_cols, n_obj, W_dev, V_dev, power_dev, density_dev, d_partial, bad_dev);
+        PADNE_HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(sensitivity_mesh_fold, dim3((unsigned)n_mesh, (unsigned)n_obj), dim3(256), 0, s, n_mesh,
+                       (const long long *)d_tile, n_blocks, (const double *)d_partial, total_dev);
+    PADNE_HIP_CHECK(hipGetLastError());
+    // (the scratch goes back to the pool on return: the context's one stream orders its reuse after these launches)
     return PADNE_OK;
 }
 }  // namespace padne

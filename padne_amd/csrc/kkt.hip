@@ -11,6 +11,7 @@
 #include <rocprim/device/device_radix_sort.hpp>      // the one stable key-value sort of the locality ordering (section "ordering")
 
 #include <algorithm>
+#include <cmath>
 #include <math.h>
 #include <string.h>
 #include <thread>
@@ -23,6 +24,9 @@ int csr_relabel(padne_ctx *ctx, const padne_csr *m, const int32_t *row_map, int6
 int amg_setup(padne_ctx *ctx, padne_csr *A0);
 int launch_power_density_block(padne_ctx *ctx, const padne_csr *m, int n_cols, const double *V_dev, double *out_dev,
                                int *bad_dev);
+int launch_sensitivity_block(padne_ctx *ctx, const padne_csr *m, const long long *tile_off_host, int n_cols, int n_obj,
+                             const double *W_dev, const double *V_dev, double *power_dev, double *density_dev, double *total_dev,
+                             int *bad_dev);
 void amg_info(const padne_csr *A0, int *levels, double *complexity, double *setup_seconds, long long *coarse_n);
 
 constexpr int kCopyStreams = 4;
@@ -1128,4 +1132,59 @@ extern "C" int padne_kkt_power_density_block(padne_ctx *ctx, padne_kkt *k, int32
         return PADNE_E_INVALID;
     }
     return parallel_copy(k, out_host, d_out, sizeof(double) * (size_t)n_tri * (size_t)n_cols, hipMemcpyDeviceToHost);
+}
+
+// dJ_j / dsigma of every face for the adjoints lambda_j = sum_m weights[j][m] V[:, m] of the finished block, and the power
+// density of its column 0: the tiles of each mesh are laid out here from the mesh's triangle offsets, then one launch over
+// them (sensitivity_block_kernel) and one fold of the per-tile partials per (mesh, objective); the three results go home
+extern "C" int padne_kkt_sensitivity_block(padne_ctx *ctx, padne_kkt *k, int32_t n_cols, int32_t n_obj, const double *weights,
+                                           double *power_out, double *density_out, double *mesh_total_out) {
+    PADNE_REQUIRE(ctx && k, "null argument");
+    PADNE_REQUIRE(k->ctx == ctx, "the plan belongs to another context");
+    PADNE_REQUIRE(k->finished && k->v_final != nullptr,
+                  "padne_kkt_sensitivity_block follows padne_kkt_finish_block, with no solve on the plan in between");
+    PADNE_REQUIRE(n_cols == k->finished_cols, "as many columns as the finished block has");
+    PADNE_REQUIRE(n_obj >= 1 && n_obj <= 4096, "between 1 and 4096 objectives");
+    PADNE_REQUIRE(weights && mesh_total_out, "null argument");
+    for (long long e = 0; e < (long long)n_obj * n_cols; ++e) PADNE_REQUIRE(std::isfinite(weights[e]), "weights must be finite");
+    const padne_csr *L = k->L;
+    PADNE_REQUIRE(L->mesh_n_mesh > 0 && L->mesh_xy != nullptr,
+                  "the system matrix does not carry a mesh (only padne_assemble_system keeps it)");
+    PADNE_REQUIRE(L->mesh_n_vert <= k->N, "the mesh has more vertices than the system has unknowns");
+    const long long n_tri = L->mesh_n_tri;
+    const int n_mesh = (int)L->mesh_n_mesh;
+    PADNE_REQUIRE(n_tri == 0 || (power_out && density_out), "null argument");
+    PADNE_HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    // the first 256-triangle tile of every mesh, from its triangle offsets
+    std::vector<long long> toff((size_t)n_mesh + 1), tile((size_t)n_mesh + 1, 0);
+    PADNE_HIP_CHECK(hipMemcpyAsync(toff.data(), L->mesh_toff, sizeof(long long) * ((size_t)n_mesh + 1), hipMemcpyDeviceToHost, s));
+    PADNE_HIP_CHECK(hipStreamSynchronize(s));
+    for (int m = 0; m < n_mesh; ++m) {
+        PADNE_REQUIRE(toff[(size_t)m + 1] >= toff[(size_t)m], "mesh triangle offsets");
+        tile[(size_t)m + 1] = tile[(size_t)m] + (toff[(size_t)m + 1] - toff[(size_t)m] + 255) / 256;
+    }
+    PADNE_REQUIRE(tile[(size_t)n_mesh] <= 0x7fffffffLL, "too many triangles for one launch");
+    Scratch sc(ctx);
+    double *d_w = nullptr, *d_power = nullptr, *d_density = nullptr, *d_total = nullptr;
+    int *d_bad = nullptr;
+    PADNE_TRY(sc.alloc(&d_w, (size_t)n_obj * (size_t)n_cols));
+    PADNE_TRY(sc.alloc(&d_power, (size_t)n_tri));
+    PADNE_TRY(sc.alloc(&d_density, (size_t)n_tri * (size_t)n_obj));
+    PADNE_TRY(sc.alloc(&d_total, (size_t)n_mesh * (size_t)n_obj));
+    PADNE_TRY(sc.alloc(&d_bad, 1));
+    PADNE_HIP_CHECK(hipMemcpyAsync(d_w, weights, sizeof(double) * (size_t)n_obj * (size_t)n_cols, hipMemcpyHostToDevice, s));
+    PADNE_HIP_CHECK(hipMemsetAsync(d_bad, 0, sizeof(int), s));
+    PADNE_TRY(launch_sensitivity_block(ctx, L, tile.data(), n_cols, n_obj, d_w, k->v_final, d_power, d_density, d_total, d_bad));
+    int h_bad = 0;
+    PADNE_HIP_CHECK(hipMemcpyAsync(&h_bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    PADNE_HIP_CHECK(hipMemcpyAsync(mesh_total_out, d_total, sizeof(double) * (size_t)n_mesh * (size_t)n_obj, hipMemcpyDeviceToHost, s));
+    if (n_tri > 0) PADNE_HIP_CHECK(hipMemcpyAsync(power_out, d_power, sizeof(double) * (size_t)n_tri, hipMemcpyDeviceToHost, s));
+    PADNE_HIP_CHECK(hipStreamSynchronize(s));
+    if (h_bad) {
+        set_error("invalid argument: triangle index out of range");
+        return PADNE_E_INVALID;
+    }
+    if (n_tri == 0) return PADNE_OK;
+    return parallel_copy(k, density_out, d_density, sizeof(double) * (size_t)n_tri * (size_t)n_obj, hipMemcpyDeviceToHost);
 }

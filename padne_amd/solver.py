@@ -18,6 +18,8 @@ produce_layer_solutions :578-615       numpy slice per mesh (contiguous blocks) 
 compute_power_density :728-745         ``power_density_kernel``
 (several load cases of one board)      ``solve_load_cases``: one assembly and plan, one block solve, the block's
                                        power densities from the potentials on the device
+(where a voltage drop comes from)      ``solve_sensitivities``: adjoints on the load-case block, Woodbury for
+                                       regulators, ``sensitivity_block_kernel`` over the faces
 =====================================  ====================================================
 
 There is no CPU fallback: every entry point that computes raises
@@ -1117,3 +1119,348 @@ def solve_load_cases(prob, cases, mesher_config: Optional[mesh.Mesher.Config] = 
     cases = check_load_cases(prob, cases)
     meshes, mesh_index_to_layer_index = _mesh_problem(prob, mesher_config, mesher)
     return solve_meshed_load_cases(prob, meshes, mesh_index_to_layer_index, cases)
+
+
+# --------------------------------------------------------------------------------------------
+# sensitivities: where the drop between two nodes comes from (adjoint method, DESIGN.md "Sensitivities")
+# --------------------------------------------------------------------------------------------
+
+# The parameters of each lumped element that Sensitivity.elements differentiates J by
+SENSITIVITY_FIELDS = {"Resistor": ("resistance",), "CurrentSource": ("current",), "VoltageSource": ("voltage",),
+                      "VoltageRegulator": ("voltage", "gain")}
+
+
+@dataclass
+class Sensitivity:
+    """Derivatives of one objective J = V(p) - V(n) of a solved Problem (see :func:`solve_meshed_sensitivities`)."""
+    nodes: tuple          # (p, n) as given: two NodeIDs
+    value: float          # J = V(p) - V(n) of the solution [V]
+    densities: list       # per layer, per mesh of LayerSolution.meshes: TwoForm, s_f / area_f [V/mm^2]
+    layers: list          # per layer: sigma_l * dJ/dsigma_l [V]  (= sum of s_f over the layer's faces)
+    elements: dict        # lumped element -> {field name: dJ/d(field)}
+
+
+def _is_node_id(obj) -> bool:
+    """A NodeID of padne_amd.problem or of padne's own problem module (by class name, like element_kind)."""
+    return any(cls.__name__ == "NodeID" for cls in type(obj).__mro__)
+
+
+def check_objectives(prob, objectives, filtered_networks=None) -> list:
+    """The objectives as a list of (p, n) NodeID pairs, or ValueError.
+
+    ``objectives`` is a non-empty sequence of pairs (p, n); J = V(p) - V(n).  Both nodes must belong to the same network
+    among ``filtered_networks`` (default: all networks of ``prob``) -- a terminal of one of its elements or the node of one
+    of its connections -- and p is not n."""
+    if isinstance(objectives, (Mapping, str, bytes)) or _is_node_id(objectives):
+        raise ValueError("objectives must be a sequence of (p, n) pairs of NodeIDs")
+    try:
+        objectives = list(objectives)
+    except TypeError:
+        raise ValueError("objectives must be a sequence of (p, n) pairs of NodeIDs") from None
+    if not objectives:
+        raise ValueError("no objectives: give at least one (p, n) pair of NodeIDs")
+    networks = list(prob.networks) if filtered_networks is None else list(filtered_networks)
+    network_of = {}
+    for i, network in enumerate(networks):
+        for node in list(network.nodes) + [conn.node_id for conn in network.connections]:
+            network_of.setdefault(node, i)
+    out = []
+    for j, pair in enumerate(objectives):
+        if isinstance(pair, (str, bytes, Mapping)) or _is_node_id(pair):
+            raise ValueError(f"objective {j} is not a (p, n) pair of NodeIDs")
+        try:
+            pair = tuple(pair)
+        except TypeError:
+            raise ValueError(f"objective {j} is not a (p, n) pair of NodeIDs") from None
+        if len(pair) != 2:
+            raise ValueError(f"objective {j} is not a (p, n) pair of NodeIDs: it has {len(pair)} entries")
+        p, n = pair
+        if not (_is_node_id(p) and _is_node_id(n)):
+            raise ValueError(f"objective {j}: p and n must be NodeIDs, not {type(p).__name__} and {type(n).__name__}")
+        if p is n:
+            raise ValueError(f"objective {j}: p is n, so V(p) - V(n) is zero by definition")
+        for name, node in (("p", p), ("n", n)):
+            if node not in network_of:
+                raise ValueError(f"objective {j}: {name} is not a node of the solved networks")
+        if network_of[p] != network_of[n]:
+            raise ValueError(f"objective {j}: p and n are nodes of different networks")
+        out.append((p, n))
+    return out
+
+
+def global_elements(filtered_networks, node_indexer: NodeIndexer) -> list:
+    """The lumped elements of the solved networks in stamping order, each as ``(element, row)`` with ``row`` the tuple of
+    the reference's stamps on global unknowns: ("R", a, b, resistance), ("I", f, t, current), ("V", p, n, voltage, i_v),
+    ("REG", v_p, v_n, s_f, s_t, voltage, gain, i_v)."""
+    idx, extra = node_indexer.node_to_global_index, node_indexer.extra_source_to_global_index
+    out = []
+    for network in filtered_networks:
+        for element in network.elements:
+            kind = element_kind(element)
+            if kind == "Resistor":
+                row = ("R", idx[element.a], idx[element.b], float(element.resistance))
+            elif kind == "CurrentSource":
+                row = ("I", idx[element.f], idx[element.t], float(element.current))
+            elif kind == "VoltageSource":
+                row = ("V", idx[element.p], idx[element.n], float(element.voltage), extra[element])
+            elif kind == "VoltageRegulator":
+                row = ("REG", idx[element.v_p], idx[element.v_n], idx[element.s_f], idx[element.s_t], float(element.voltage),
+                       float(element.gain), extra[element])
+            else:
+                raise NotImplementedError(f"Unsupported node type {element}")
+            out.append((element, row))
+    return out
+
+
+def woodbury_terms(rows) -> list:
+    """``(s_f, s_t, i_v, gain)`` of every regulator among the element rows (global_elements) whose gain term makes L
+    unsymmetric: L^T = L + U V^T with U = [g_k e_iv,k | -g_k d_k], V = [d_k | e_iv,k], d_k = e_sf,k - e_st,k.  A regulator
+    with gain 0 or with s_f and s_t on one unknown stamps nothing unsymmetric and is left out."""
+    out = []
+    for row in rows:
+        if row[0] == "REG":
+            _, _vp, _vn, sf, st, _u, gain, iv = row
+            if gain != 0.0 and sf != st:
+                out.append((int(sf), int(st), int(iv), float(gain)))
+    return out
+
+
+def sensitivity_block_columns(n_obj: int, n_terms: int) -> int:
+    """Columns of the block of a sensitivity solve: r, the k objectives c_j, then per Woodbury term the unit current from s_f
+    to s_t (columns 1 + k + q) and regulator q's voltage row at 1 (columns 1 + k + K + q)."""
+    return 1 + int(n_obj) + 2 * int(n_terms)
+
+
+def stamp_sensitivity_block(filtered_networks, node_indexer: NodeIndexer, n_unknowns: int, objective_rows, terms):
+    """COO triples (rows, cols, vals) of the block of a sensitivity solve (sensitivity_block_columns): column 0 is the
+    Problem's r as stamp_load_cases lists it, column 1 + j is c_j = e_p - e_n for ``objective_rows[j]`` = (p, n) as global
+    unknowns (empty when both land on one unknown), then d_q and e_iv,q of the Woodbury ``terms``."""
+    rows, cols, vals = stamp_load_cases(filtered_networks, node_indexer, n_unknowns, [{}])
+    rows, cols, vals = rows.tolist(), cols.tolist(), vals.tolist()
+    k, K = len(objective_rows), len(terms)
+
+    def pair(col, a, b):
+        if a != b:
+            rows.extend((int(a), int(b)))
+            cols.extend((col, col))
+            vals.extend((1.0, -1.0))
+    for j, (p, n) in enumerate(objective_rows):
+        pair(1 + j, p, n)
+    for q, (sf, st, iv, _gain) in enumerate(terms):
+        pair(1 + k + q, sf, st)
+        rows.append(int(iv))
+        cols.append(1 + k + K + q)
+        vals.append(1.0)
+    return np.asarray(rows, dtype=np.int64), np.asarray(cols, dtype=np.int32), np.asarray(vals, dtype=DTYPE)
+
+
+def adjoint_weights(V: np.ndarray, n_obj: int, terms) -> np.ndarray:
+    """The weights W (n_obj, n_cols) with lambda_j = V W[j] the solution of L^T lambda_j = c_j, from the solved block V of
+    stamp_sensitivity_block (only its rows s_f, s_t and i_v of the ``terms`` are read).  Without terms W selects column
+    1 + j.  With them, by Woodbury, lambda = y - Z (I + V^T Z)^-1 V^T y for y = L^-1 c, Z = L^-1 U: the 2K x 2K system is
+    solved here, on the host."""
+    V = np.asarray(V, dtype=DTYPE)
+    k, K = int(n_obj), len(terms)
+    n_cols = sensitivity_block_columns(k, K)
+    if V.ndim != 2 or V.shape[1] != n_cols:
+        raise ValueError(f"the block must have {n_cols} columns, not {V.shape}")
+    W = np.zeros((k, n_cols), dtype=DTYPE)
+    W[np.arange(k), 1 + np.arange(k)] = 1.0
+    if not K:
+        return W
+    sf = np.array([t[0] for t in terms], dtype=np.int64)
+    st = np.array([t[1] for t in terms], dtype=np.int64)
+    iv = np.array([t[2] for t in terms], dtype=np.int64)
+    g = np.array([t[3] for t in terms], dtype=DTYPE)
+
+    def vt(cols):                   # V^T applied to the block columns ``cols``: [d_q^T z ; z[iv_q]], (2K, len(cols))
+        return np.concatenate([V[sf][:, cols] - V[st][:, cols], V[iv][:, cols]], axis=0)
+    col_d = 1 + k + np.arange(K)
+    col_e = 1 + k + K + np.arange(K)
+    # Z = [g_q Y_e,q | -g_q Y_d,q] as block columns with coefficients
+    z_cols = np.concatenate([col_e, col_d])
+    z_coef = np.concatenate([g, -g])
+    G = np.eye(2 * K) + vt(z_cols) * z_coef[None, :]
+    A = np.linalg.solve(G, vt(1 + np.arange(k)))            # (2K, k): (I + V^T Z)^-1 V^T y_j
+    # lambda_j = y_j - sum_m A[m, j] z_coef[m] Y[:, z_cols[m]]
+    W[:, z_cols] -= (A * z_coef[:, None]).T
+    return W
+
+
+def element_sensitivities(element_rows, x: np.ndarray, lam: np.ndarray) -> list:
+    """dJ/d(field) of every element row (global_elements' tuples, indices into ``x`` and ``lam``) for the solution ``x``
+    and the adjoint ``lam`` (L^T lam = c), as one dict per row:
+
+    - Resistor:         dJ/dR = -(lam_a - lam_b)(x_a - x_b) / R^2
+    - CurrentSource:    dJ/dI = lam_f - lam_t
+    - VoltageSource:    dJ/dU = lam_iv
+    - VoltageRegulator: dJ/dU = lam_iv,  dJ/dgain = -(lam_sf - lam_st) x_iv"""
+    out = []
+    for row in element_rows:
+        kind = row[0]
+        if kind == "R":
+            _, a, b, res = row
+            out.append({"resistance": float(-(lam[a] - lam[b]) * (x[a] - x[b]) / (res * res))})
+        elif kind == "I":
+            _, f, t, _cur = row
+            out.append({"current": float(lam[f] - lam[t])})
+        elif kind == "V":
+            out.append({"voltage": float(lam[row[4]])})
+        elif kind == "REG":
+            _, _vp, _vn, sf, st, _u, _gain, iv = row
+            out.append({"voltage": float(lam[iv]), "gain": float(-(lam[sf] - lam[st]) * x[iv])})
+        else:
+            raise NotImplementedError(f"Unsupported element row {row}")
+    return out
+
+
+def _sensitivity_elements(pairs, V: np.ndarray, W: np.ndarray) -> list:
+    """element_sensitivities of every objective, with x and lambda gathered at the elements' unknowns only."""
+    rows = [row for _, row in pairs]
+    used = sorted({int(i) for row in rows for i in (row[1:3] if row[0] in ("R", "I") else
+                                                      (row[4],) if row[0] == "V" else (row[3], row[4], row[7]))})
+    at = {g: i for i, g in enumerate(used)}
+    local = []
+    for row in rows:
+        if row[0] in ("R", "I"):
+            local.append((row[0], at[row[1]], at[row[2]], row[3]))
+        elif row[0] == "V":
+            local.append((row[0], row[1], row[2], row[3], at[row[4]]))
+        else:
+            local.append((row[0], row[1], row[2], at[row[3]], at[row[4]], row[5], row[6], at[row[7]]))
+    Vu = V[np.asarray(used, dtype=np.int64)] if used else np.zeros((0, V.shape[1]))
+    x, lam = Vu[:, 0], Vu @ W.T
+    per_obj = [element_sensitivities(local, x, lam[:, j]) for j in range(W.shape[0])]
+    return [{element: d[i] for i, (element, _) in enumerate(pairs)} for d in per_obj]
+
+
+def solve_meshed_sensitivities(prob, meshes, mesh_index_to_layer_index, objectives, *, filtered_networks=None,
+                               disconnected_meshes_by_layer=None, partition=None):
+    """``solve_meshed`` together with the sensitivities of potential differences: (Solution, [Sensitivity per objective]).
+
+    An objective is a pair (p, n) of NodeIDs of one network among ``filtered_networks`` (:func:`check_objectives`); its
+    J = V(p) - V(n).  With M x = r the reference's system (``solver.py:469-560``, M = L) and J = c^T x, c = e_p - e_n, the
+    adjoint lambda solves M^T lambda = c, and for every parameter theta dJ/dtheta = lambda^T (dr/dtheta - dM/dtheta x):
+
+    - face f of a mesh of sheet conductance sigma, whose edges (i, k) carry the assembly's cot weights w_ik (|cot|/2 of the
+      opposite corner, ``HalfEdge.cotan``): s_f = sigma dJ/dsigma_f = sigma sum_edges w_ik (lambda_i - lambda_k)(x_i - x_k);
+      ``densities`` holds s_f / area_f and ``layers[l]`` the sum of s_f over the layer, which is sigma_l dJ/dsigma_l;
+    - ``elements``: every lumped element of the solved networks, {field: dJ/dfield} (:func:`element_sensitivities`).
+
+    Regulators make M unsymmetric; M^T = M + U V^T (:func:`woodbury_terms`) and lambda follows by Woodbury from ordinary
+    solves with M (:func:`adjoint_weights`).  All of it is one block solve of 1 + k + 2K right-hand sides on one assembly and
+    plan (K: regulators with a gain term); the faces come from one kernel over the potentials the device holds.  The
+    Solution is that of ``prob``, filled as ``solve_meshed_load_cases`` fills a case of a block (its SolverInfo reports the
+    block solve as a whole).  ValueError, before anything reaches the device, for invalid objectives and for a
+    ``partition`` over several GPUs."""
+    return _sensitivity_solution(prob, meshes, mesh_index_to_layer_index, objectives, filtered_networks,
+                                 disconnected_meshes_by_layer, partition)
+
+
+def _sensitivity_solution(prob, meshes, mesh_index_to_layer_index, objectives, filtered_networks, disconnected_meshes_by_layer,
+                          partition, timings: Optional[dict] = None):
+    """solve_meshed_sensitivities; ``timings`` (a dict) receives the host time of each step in seconds."""
+    if partition is not None and partition.world > 1:
+        raise ValueError("sensitivities are solved on one GPU: the row-partitioned path (partition.world > 1) does not take "
+                         "them")
+    objectives = check_objectives(prob, objectives, filtered_networks)
+    k = len(objectives)
+    t0 = time.perf_counter()
+    meshes, filtered_networks, disconnected_meshes_by_layer = _meshed_inputs(prob, meshes, filtered_networks,
+                                                                             disconnected_meshes_by_layer)
+    log.info("Indexing vertices and connections")
+    vindex = VertexIndexer.create(meshes)
+    node_indexer = NodeIndexer.create(prob, meshes, mesh_index_to_layer_index, vindex, filtered_networks)
+    pairs = global_elements(filtered_networks, node_indexer)
+    terms = woodbury_terms([row for _, row in pairs])
+    idx = node_indexer.node_to_global_index
+    objective_rows = [(idx[p], idx[n]) for p, n in objectives]
+    n_cols = sensitivity_block_columns(k, len(terms))
+    t1 = time.perf_counter()
+    log.info("Assembling the global system")
+    L, _ = assemble_system(prob, meshes, mesh_index_to_layer_index, vindex, filtered_networks, node_indexer)
+    try:
+        rows, cols, vals = stamp_sensitivity_block(filtered_networks, node_indexer, L.shape[0], objective_rows, terms)
+        t2 = time.perf_counter()
+        log.info(f"Solving {k} adjoint(s) and {2 * len(terms)} regulator column(s) as one block with the Problem")
+        V, residual_norms, res, power, density, totals, W = _solve_sensitivity_block(L, rows, cols, vals, n_cols, k, terms,
+                                                                                     timings)
+    finally:
+        L.close()
+    t3 = time.perf_counter()
+    if _stalled(res, RTOL):
+        col_norms = np.sqrt(np.bincount(cols, weights=vals * vals, minlength=n_cols))
+        _warn_if_stalled(res, RTOL, _stalled_columns(residual_norms, col_norms=col_norms))
+    log.info("Producing the solution and the sensitivities")
+    ground_node_current = float(V[-1, 0])
+    _warn_ground_current(ground_node_current)
+    info = SolverInfo(ground_node_current=ground_node_current, residual_norm=float(residual_norms[0]),
+                      iterations=int(res.iterations), rel_residual=float(res.rel_residual), solve_seconds=float(res.seconds))
+    layer_solutions = produce_layer_solutions(prob.layers, vindex, meshes, mesh_index_to_layer_index, np.ascontiguousarray(V[:, 0]),
+                                              disconnected_meshes_by_layer, power_all=power)
+    solution = Solution(problem=prob, layer_solutions=layer_solutions, solver_info=info)
+    elements = _sensitivity_elements(pairs, V, W)
+    toff = np.concatenate([[0], np.cumsum([len(m.triangles) for m in meshes])]).astype(np.int64)
+    sens = []
+    for j, ((p, n), (ip, in_)) in enumerate(zip(objectives, objective_rows)):
+        densities, layer_sums = [], []
+        for layer_i in range(len(prob.layers)):
+            forms, total = [], 0.0
+            for mesh_i, msh in enumerate(meshes):
+                if mesh_index_to_layer_index[mesh_i] != layer_i:
+                    continue
+                tf = mesh.TwoForm(msh)
+                if density is not None:
+                    tf.values = np.array(density[j, toff[mesh_i]:toff[mesh_i + 1]], dtype=DTYPE)
+                    total += float(totals[j, mesh_i])
+                forms.append(tf)
+            densities.append(forms)
+            layer_sums.append(total)
+        sens.append(Sensitivity(nodes=(p, n), value=float(V[ip, 0] - V[in_, 0]), densities=densities, layers=layer_sums,
+                                elements=elements[j]))
+    if timings is not None:
+        timings.update(indexing=t1 - t0, assembly=t2 - t1, solutions=time.perf_counter() - t3)
+    return solution, sens
+
+
+def _solve_sensitivity_block(L: SystemMatrix, rows, cols, vals, n_cols: int, k: int, terms, timings: Optional[dict] = None):
+    """The block solve of a sensitivity call, then the adjoint weights on the host and the face kernel on the V the device
+    holds.  Returns (V (N, n_cols), ||L v_j - r_j|| (n_cols,), SolveResult, power of column 0 (n_tri,), s_f / area_f
+    (k, n_tri), per-mesh sums of s_f (k, n_mesh), W (k, n_cols)); the three face arrays are None without triangles."""
+    t0 = time.perf_counter()
+    layout = L.layout
+    if layout is None or not layout.constraints:
+        raise SingularSystemError("system has no ground constraint")
+    pins = _floating_pins(L, layout, None)
+    red, known_idx, known_val = build_block_reduction(layout, load_case_constraint_values(layout, rows, cols, vals, n_cols),
+                                                      pins)
+    plan = _plan_for(L, L.dev, layout, red, _wants_reorder(L, None), False)
+    members = sorted({int(x) for mem, cons, _ in red.groups if cons for x in mem})
+    extras = [dict(cst.gamma) for cst in red.regulators]
+    n_tri = len(L.tri) if L.tri is not None else 0
+    n_mesh = len(L.mesh_offsets) - 1 if L.mesh_offsets is not None else 0
+    probes, res = plan.solve_block_coo(n_cols, rows, cols, vals, known_idx, known_val, extras, members, rtol=RTOL,
+                                       max_iter=MAX_ITER, abs_residual_target=ABS_RESIDUAL_TARGET, power_tri=n_tri,
+                                       power_rows=1 + k)
+    t1 = time.perf_counter()
+    V, residual_norms = _finish_block(plan, red, members, probes, n_cols)
+    t2 = time.perf_counter()
+    W = adjoint_weights(V, k, terms)
+    power = density = totals = None
+    if n_tri:
+        power, density, totals = plan.sensitivity_block(W, n_tri, n_mesh)
+    if timings is not None:
+        timings.update(stage1=t1 - t0, stage2=t2 - t1, sensitivity=time.perf_counter() - t2)
+    return V, residual_norms, res, power, density, totals, W
+
+
+def solve_sensitivities(prob, objectives, mesher_config: Optional[mesh.Mesher.Config] = None, *, mesher=None,
+                        partition=None):
+    """``solve`` with the sensitivities of potential differences (see :func:`solve_meshed_sensitivities`): the board is
+    meshed once.  Returns (Solution, [Sensitivity per objective])."""
+    if partition is not None and partition.world > 1:
+        raise ValueError("sensitivities are solved on one GPU: the row-partitioned path (partition.world > 1) does not take "
+                         "them")
+    objectives = check_objectives(prob, objectives)
+    meshes, mesh_index_to_layer_index = _mesh_problem(prob, mesher_config, mesher)
+    return solve_meshed_sensitivities(prob, meshes, mesh_index_to_layer_index, objectives)
