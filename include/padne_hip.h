@@ -349,6 +349,20 @@ int padne_kkt_power_density_block(padne_ctx *ctx, padne_kkt *plan, int32_t n_col
  * padne_kkt_power_density_block; 1 <= n_obj <= 4096 and finite weights, else PADNE_E_INVALID. */
 int padne_kkt_sensitivity_block(padne_ctx *ctx, padne_kkt *plan, int32_t n_cols, int32_t n_obj, const double *weights,
                                 double *power_out, double *density_out, double *mesh_total_out);
+/* Currents over the mesh `L` keeps, from column 0 of the block the last padne_kkt_finish_block left on the device.  Per face
+ * t, with the face gradient of padne_csr_power_density and the sheet conductance sigma of its mesh: J_out[n_tri][2] =
+ * -sigma grad V (so |J|^2 / sigma is the power density) and mag_out[n_tri] = |J|; per mesh m, mesh_max_out[m] = the
+ * largest |J| of its faces and mesh_face_out[m] = that face (global index, the lowest on a tie; -1.0 and -1 for a mesh
+ * without faces).  Cut c is the directed segment cut_xy[c] = (start x, y, end x, y) on the meshes m with
+ * mesh_layer[m] == cut_layer[c]; cut_out[c] = sum over the face edges (P, Q) (P the lower global vertex) that cross it of
+ * sigma |cot|/2 (V_left - V_right), where an edge crosses when orient(start, end, .) > 0 differs between P and Q and
+ * orient(P, Q, .) > 0 differs between start and end (orient(a, b, p) = (b.x - a.x)(p.y - a.y) - (b.y - a.y)(p.x - a.x);
+ * left: orient(start, end, .) > 0).  Everything is summed in a fixed order: two calls give the same bits.  Preconditions
+ * and errors as padne_kkt_sensitivity_block; n_tri and n_mesh must be the mesh's, 0 <= n_cut <= 4096, end points finite
+ * and start != end, else PADNE_E_INVALID. */
+int padne_kkt_current_report(padne_ctx *ctx, padne_kkt *plan, int32_t n_cols, int64_t n_tri, int32_t n_mesh,
+                             const int32_t *mesh_layer, int32_t n_cut, const int32_t *cut_layer, const double *cut_xy,
+                             double *J_out, double *mag_out, double *mesh_max_out, int64_t *mesh_face_out, double *cut_out);
 
 /* Row-partitioned runs, optional: attach the rank's owned x owned diagonal block; with precond = 1 the
  * multigrid hierarchy is then built on that block only (block-Jacobi with multigrid blocks, no

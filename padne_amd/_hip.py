@@ -113,6 +113,8 @@ SIGNATURES = {
                                             C.POINTER(SolveInfo)]),
     "padne_kkt_power_density_block": (C.c_int, [_P, _P, C.c_int32, _PF64]),
     "padne_kkt_sensitivity_block": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _PF64, _PF64, _PF64, _PF64]),
+    "padne_kkt_current_report": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int32, _PI32, C.c_int32, _PI32, _PF64, _PF64, _PF64,
+                                           _PF64, _PI64, _PF64]),
     "padne_amg_apply": (C.c_int, [_P, _P, _PF64, _PF64]),
     "padne_csr_set_preconditioner_block": (C.c_int, [_P, _P]),
     "padne_amg_level": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(_P)]),
@@ -658,12 +660,12 @@ class KktPlan:
 
     def solve_block_coo(self, n_cols, rows, cols, vals, known_idx, known_val, extras: list, probes, *, rtol=1e-12,
                         max_iter=200000, precond="amg", abs_residual_target=0.0, rebuild=False, power_tri: int = 0,
-                        power_rows: int = 0):
+                        power_rows: int = 0, current_tri: int = 0):
         """``solve_block`` with the block (N, n_cols) given by its non-zero entries: R[rows[e], cols[e]] = vals[e], each (row,
         column) pair at most once.  Only the triples cross PCIe; the device zeroes its block and scatters them.
         ``power_tri``: the triangles of the mesh the system carries, when ``power_density_block`` will follow -- its result
         array is then made ready while the device solves, like V's (``power_rows`` rows of it instead of n_cols: 1 + the
-        objectives of a ``sensitivity_block``)."""
+        objectives of a ``sensitivity_block``).  ``current_tri``: the same for the J and |J| arrays of a ``current_report``."""
         rows, cols, vals = _i64(rows).reshape(-1), _i32(cols).reshape(-1), _f64(vals).reshape(-1)
         if not (rows.shape == cols.shape == vals.shape):
             raise ValueError("rows, cols and vals must have equal length")
@@ -673,10 +675,11 @@ class KktPlan:
         kidx = _i64(known_idx)
         kval = _f64(known_val).reshape(n_cols, kidx.shape[0])
         return self._stage1(n_cols, (rows, cols, vals), kidx, kval, extras, probes, rtol, max_iter, precond,
-                            abs_residual_target, rebuild, power_tri=int(power_tri), power_rows=int(power_rows))
+                            abs_residual_target, rebuild, power_tri=int(power_tri), power_rows=int(power_rows),
+                            current_tri=int(current_tri))
 
     def _stage1(self, n_cols, r, kidx, kval, extras, probes, rtol, max_iter, precond, abs_residual_target, rebuild,
-                power_tri=0, power_rows=0):
+                power_tri=0, power_rows=0, current_tri=0):
         ptr, rows, vals = [0], [], []
         for col in extras:
             for row, val in col.items():
@@ -695,6 +698,7 @@ class KktPlan:
         self._v_next, self._v_toucher = _prefaulted(v_shape)
         self._pd_next, self._pd_toucher = (_prefaulted((power_rows or n_cols, power_tri)) if coo and power_tri > 0
                                            else (None, None))
+        self._cur_next, self._cur_toucher = _prefaulted((3 * current_tri,)) if coo and current_tri > 0 else (None, None)
         lib, common = self.ctx._lib, (kidx.shape[0], _ptr(kidx, _PI64), _ptr(kval, _PF64), len(extras),
                                       _ptr(ptr, _PI64), _ptr(rows, _PI64), _ptr(vals, _PF64), pidx.shape[0], _ptr(pidx, _PI64),
                                       _ptr(out, _PF64), C.byref(opts), float(abs_residual_target), C.byref(info))
@@ -759,6 +763,34 @@ class KktPlan:
         _check(self.ctx._lib.padne_kkt_sensitivity_block(self.ctx._h, self._h, W.shape[1], n_obj, _ptr(W, _PF64),
                                                          _ptr(power[0], _PF64), _ptr(density, _PF64), _ptr(totals, _PF64)))
         return power[0], density, totals
+
+    def current_report(self, n_cols: int, n_tri: int, mesh_layer, cut_layer, cut_xy):
+        """The currents of column 0 of the block the last ``finish_block`` left on the device, over the mesh the system was
+        assembled from (``n_tri`` triangles; ``mesh_layer`` (n_mesh,): the layer of each mesh).  Cut c is the segment
+        ``cut_xy[c]`` = (start x, y, end x, y) on layer ``cut_layer[c]``.  Returns (J (n_tri, 2) = -sigma grad V, |J| (n_tri,),
+        the largest |J| of each mesh (n_mesh,), its face (n_mesh,) as a global index (-1 for a mesh without faces), the
+        current through each cut (n_cut,)) (include/padne_hip.h).  Raises ValueError as ``sensitivity_block`` does, for more
+        than 4096 cuts, for end points that are not finite and for a cut whose start is its end."""
+        ml = _i32(mesh_layer).reshape(-1)
+        cl = _i32(cut_layer).reshape(-1)
+        xy = _f64(cut_xy).reshape(-1, 4)
+        if xy.shape[0] != cl.shape[0]:
+            raise ValueError("cut_layer and cut_xy must list the same cuts")
+        n_tri, n_mesh, n_cut = int(n_tri), ml.shape[0], cl.shape[0]
+        toucher, buf = getattr(self, "_cur_toucher", None), getattr(self, "_cur_next", None)
+        self._cur_next, self._cur_toucher = None, None
+        for t in toucher or ():
+            t.join()
+        if buf is None or buf.shape != (3 * n_tri,):
+            buf = np.empty(3 * n_tri, dtype=np.float64)
+        J, mag = buf[:2 * n_tri].reshape(n_tri, 2), buf[2 * n_tri:]
+        mesh_max = np.empty(n_mesh, dtype=np.float64)
+        mesh_face = np.empty(n_mesh, dtype=np.int64)
+        cuts = np.empty(n_cut, dtype=np.float64)
+        _check(self.ctx._lib.padne_kkt_current_report(self.ctx._h, self._h, int(n_cols), n_tri, n_mesh, _ptr(ml, _PI32), n_cut,
+                                                      _ptr(cl, _PI32), _ptr(xy, _PF64), _ptr(J, _PF64), _ptr(mag, _PF64),
+                                                      _ptr(mesh_max, _PF64), _ptr(mesh_face, _PI64), _ptr(cuts, _PF64)))
+        return J, mag, mesh_max, mesh_face, cuts
 
     def finish(self, extra_coeff, multipliers: dict):
         """Stage 2: (v, ||L v - r||)."""

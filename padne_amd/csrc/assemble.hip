@@ -2361,6 +2361,196 @@ __global__ __launch_bounds__(256) void sensitivity_mesh_fold(int n_mesh, const l
     if (threadIdx.x == 0) total[(long long)j * n_mesh + m] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// Currents ("Currents"): the sheet current density J = -sigma grad V of every face, with the face gradient of
+// power_density_kernel (so |J|^2 / sigma is its power density), and the current through cut segments.  Both kernels run
+// over the tile layout of sensitivity_block_kernel: block b is 256 faces of one mesh, its first face below.
+__device__ __forceinline__ long long tile_first_face(const long long *__restrict__ tile_off, int n_mesh,
+                                                     const long long *__restrict__ mesh_toff, long long b, int &m) {
+    m = find_segment(tile_off, n_mesh, b);
+    return mesh_toff[m] + (b - tile_off[m]) * 256;
+}
+
+// the global corners of face t of mesh m, in the order power_density_kernel visits them; false for an index out of range
+__device__ __forceinline__ bool face_corners(const int *__restrict__ tri, const long long *__restrict__ mesh_voff, int m,
+                                             long long t, long long &g1, long long &g2, long long &g3) {
+    const long long v0 = mesh_voff[m];
+    const long long nv = mesh_voff[m + 1] - v0;
+    const int l1 = tri[3 * t + 2], l2 = tri[3 * t], l3 = tri[3 * t + 1];
+    if (l1 < 0 || l2 < 0 || l3 < 0 || l1 >= nv || l2 >= nv || l3 >= nv) return false;
+    g1 = v0 + l1;
+    g2 = v0 + l2;
+    g3 = v0 + l3;
+    return true;
+}
+
+// (|J|, face) pairs: the larger |J| wins, the lower face on a tie
+__device__ __forceinline__ void hotspot_merge(double &v, long long &f, double ov, long long of) {
+    if (ov > v || (ov == v && of < f)) {
+        v = ov;
+        f = of;
+    }
+}
+
+constexpr long long kNoFace = 0x7fffffffffffffffLL;
+
+// out: J[t][2], mag[t] = |J|, and per tile its largest |J| with the face (tile_max, tile_face; -1 and kNoFace for no face)
+// and the bounding box of its corners, box[b] = (x_min, y_min, x_max, y_max) -- what the host lists cut/tile pairs from
+__global__ __launch_bounds__(256) void current_face_kernel(
+    int n_mesh, const long long *__restrict__ tile_off, const int *__restrict__ tri, const double *__restrict__ xy,
+    const long long *__restrict__ mesh_voff, const long long *__restrict__ mesh_toff, const double *__restrict__ sigma,
+    const int n_cols, const double *__restrict__ V, double *__restrict__ J, double *__restrict__ mag,
+    double *__restrict__ tile_max, long long *__restrict__ tile_face, double *__restrict__ box, int *__restrict__ err) {
+    __shared__ double red_v[4], red_box[4][4];
+    __shared__ long long red_f[4];
+    const long long b = blockIdx.x;
+    int m;
+    const long long t = tile_first_face(tile_off, n_mesh, mesh_toff, b, m) + threadIdx.x;
+    bool live = t < mesh_toff[m + 1];
+    long long g1 = 0, g2 = 0, g3 = 0;
+    if (live && !face_corners(tri, mesh_voff, m, t, g1, g2, g3)) {
+        *(volatile int *)err = 1;
+        live = false;                           // (no return: every thread takes part in the block reductions below)
+    }
+    double a = -1.0;
+    long long f = kNoFace;
+    double bx0 = INFINITY, by0 = INFINITY, bx1 = -INFINITY, by1 = -INFINITY;
+    if (live) {
+        const double x1 = xy[2 * g1], y1 = xy[2 * g1 + 1];
+        const double x2 = xy[2 * g2], y2 = xy[2 * g2 + 1];
+        const double x3 = xy[2 * g3], y3 = xy[2 * g3 + 1];
+        double gx, gy;
+        face_gradient_of(x1, y1, x2, y2, x3, y3, V[g1 * n_cols], V[g2 * n_cols], V[g3 * n_cols], gx, gy);
+        const double s = sigma[m];
+        const double jx = -s * gx, jy = -s * gy;
+        a = sqrt(jx * jx + jy * jy);
+        f = t;
+        J[2 * t] = jx;
+        J[2 * t + 1] = jy;
+        mag[t] = a;
+        bx0 = fmin(fmin(x1, x2), x3);
+        by0 = fmin(fmin(y1, y2), y3);
+        bx1 = fmax(fmax(x1, x2), x3);
+        by1 = fmax(fmax(y1, y2), y3);
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        hotspot_merge(a, f, __shfl_down(a, off, 64), __shfl_down(f, off, 64));
+        bx0 = fmin(bx0, __shfl_down(bx0, off, 64));
+        by0 = fmin(by0, __shfl_down(by0, off, 64));
+        bx1 = fmax(bx1, __shfl_down(bx1, off, 64));
+        by1 = fmax(by1, __shfl_down(by1, off, 64));
+    }
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        red_v[w] = a;
+        red_f[w] = f;
+        red_box[w][0] = bx0;
+        red_box[w][1] = by0;
+        red_box[w][2] = bx1;
+        red_box[w][3] = by1;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int q = 1; q < 4; ++q) {
+            hotspot_merge(a, f, red_v[q], red_f[q]);
+            bx0 = fmin(bx0, red_box[q][0]);
+            by0 = fmin(by0, red_box[q][1]);
+            bx1 = fmax(bx1, red_box[q][2]);
+            by1 = fmax(by1, red_box[q][3]);
+        }
+        tile_max[b] = a;
+        tile_face[b] = f;
+        box[4 * b] = bx0;
+        box[4 * b + 1] = by0;
+        box[4 * b + 2] = bx1;
+        box[4 * b + 3] = by1;
+    }
+}
+
+// the largest |J| of every mesh and its face (global index; -1.0 and -1 for a mesh without faces): one workgroup per mesh
+// over its tiles, a fixed order
+__global__ __launch_bounds__(256) void current_mesh_fold(int n_mesh, const long long *__restrict__ tile_off,
+                                                         const double *__restrict__ tile_max,
+                                                         const long long *__restrict__ tile_face,
+                                                         double *__restrict__ mesh_max, long long *__restrict__ mesh_face) {
+    __shared__ double red_v[4];
+    __shared__ long long red_f[4];
+    const int m = blockIdx.x;
+    double a = -1.0;
+    long long f = kNoFace;
+    for (long long i = tile_off[m] + threadIdx.x; i < tile_off[m + 1]; i += 256) hotspot_merge(a, f, tile_max[i], tile_face[i]);
+    for (int off = 32; off > 0; off >>= 1) hotspot_merge(a, f, __shfl_down(a, off, 64), __shfl_down(f, off, 64));
+    if ((threadIdx.x & 63) == 0) {
+        red_v[threadIdx.x >> 6] = a;
+        red_f[threadIdx.x >> 6] = f;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int q = 1; q < 4; ++q) hotspot_merge(a, f, red_v[q], red_f[q]);
+        mesh_max[m] = a;
+        mesh_face[m] = f == kNoFace ? -1 : f;
+    }
+}
+
+// orient(a, b, p) > 0: p lies left of a -> b.  Evaluated exactly so (the library builds with -ffp-contract=off), which
+// lets a numpy restatement reproduce every decision of the cut rule
+__device__ __forceinline__ double orient(double ax, double ay, double bx, double by, double px, double py) {
+    return (bx - ax) * (py - ay) - (by - ay) * (px - ax);
+}
+
+// edge (i, k) of a face, cot weight w, against the cut c = (start x, y, end x, y): w (V_left - V_right) when it crosses,
+// else 0.  The edge runs from its lower global vertex P to the higher Q, so the two faces of an edge decide alike; it
+// crosses when P and Q lie on different sides of the cut's line (on the line counts as right) and start and end on
+// different sides of the edge's line
+__device__ __forceinline__ double cut_edge(long long gi, long long gk, double xi, double yi, double xk, double yk, double ui,
+                                           double uk, double w, const double *c) {
+    if (gk < gi) {
+        const double tx = xi, ty = yi, tu = ui;
+        xi = xk; yi = yk; ui = uk;
+        xk = tx; yk = ty; uk = tu;
+    }
+    const bool lp = orient(c[0], c[1], c[2], c[3], xi, yi) > 0, lq = orient(c[0], c[1], c[2], c[3], xk, yk) > 0;
+    if (lp == lq) return 0.0;
+    const bool ls = orient(xi, yi, xk, yk, c[0], c[1]) > 0, le = orient(xi, yi, xk, yk, c[2], c[3]) > 0;
+    if (ls == le) return 0.0;
+    return w * (lp ? ui - uk : uk - ui);
+}
+
+// one workgroup per (cut, tile) pair: partial[p] = the current of pair p's tile across its cut, summed in a fixed order.
+// The face's share of an edge carries the assembly's weight sigma |cot|/2 of the opposite corner (cot_half), so the two
+// faces of an edge together carry the edge's conductance.  sensitivity_mesh_fold then sums each cut's pairs.
+__global__ __launch_bounds__(256) void cut_current_kernel(
+    int n_mesh, const long long *__restrict__ tile_off, const int *__restrict__ tri, const double *__restrict__ xy,
+    const long long *__restrict__ mesh_voff, const long long *__restrict__ mesh_toff, const double *__restrict__ sigma,
+    const int n_cols, const double *__restrict__ V, const int *__restrict__ pair_cut, const long long *__restrict__ pair_tile,
+    const double *__restrict__ cut_xy, double *__restrict__ partial, int *__restrict__ err) {
+    __shared__ double red[4];
+    const long long p = blockIdx.x;
+    int m;
+    const long long t = tile_first_face(tile_off, n_mesh, mesh_toff, pair_tile[p], m) + threadIdx.x;
+    bool live = t < mesh_toff[m + 1];
+    long long g1 = 0, g2 = 0, g3 = 0;
+    if (live && !face_corners(tri, mesh_voff, m, t, g1, g2, g3)) {
+        *(volatile int *)err = 1;
+        live = false;
+    }
+    double s = 0.0;
+    if (live) {
+        const double *c = cut_xy + 4 * (long long)pair_cut[p];
+        const double x1 = xy[2 * g1], y1 = xy[2 * g1 + 1];
+        const double x2 = xy[2 * g2], y2 = xy[2 * g2 + 1];
+        const double x3 = xy[2 * g3], y3 = xy[2 * g3 + 1];
+        const double u1 = V[g1 * n_cols], u2 = V[g2 * n_cols], u3 = V[g3 * n_cols];
+        const double e12 = cut_edge(g1, g2, x1, y1, x2, y2, u1, u2, cot_half(x1, y1, x2, y2, x3, y3), c);
+        const double e23 = cut_edge(g2, g3, x2, y2, x3, y3, u2, u3, cot_half(x2, y2, x3, y3, x1, y1), c);
+        const double e31 = cut_edge(g3, g1, x3, y3, x1, y1, u3, u1, cot_half(x3, y3, x1, y1, x2, y2), c);
+        s = sigma[m] * ((e12 + e23) + e31);
+    }
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[p] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
 // ---- host orchestration ----------------------------------------------------------------------
 // shared tail: slots (key,val,slot_ptr) already filled -> merged CSR
 // padne_assemble_system_ex(flags & 1): the triangles are a rank's piece of a larger mesh (owned vertices + the ring of
@@ -2938,6 +3128,54 @@ int launch_sensitivity_block(padne_ctx *ctx, const padne_csr *m, const long long
                        (const long long *)d_tile, n_blocks, (const double *)d_partial, total_dev);
     PADNE_HIP_CHECK(hipGetLastError());
     // (the scratch goes back to the pool on return: the context's one stream orders its reuse after these launches)
+    return PADNE_OK;
+}
+
+// current_face_kernel + current_mesh_fold over the mesh `m` keeps, on the tiles tile_dev[mesh_n_mesh + 1] (device) of
+// sensitivity_block_kernel's layout, n_blocks of them.  J_dev[mesh_n_tri][2], mag_dev[mesh_n_tri], tile_max_dev,
+// tile_face_dev[n_blocks], box_dev[n_blocks][4], mesh_max_dev, mesh_face_dev[mesh_n_mesh] (device).  Asynchronous.
+int launch_current_faces(padne_ctx *ctx, const padne_csr *m, const long long *tile_dev, long long n_blocks, int n_cols,
+                         const double *V_dev, double *J_dev, double *mag_dev, double *tile_max_dev, long long *tile_face_dev,
+                         double *box_dev, double *mesh_max_dev, long long *mesh_face_dev, int *bad_dev) {
+    PADNE_REQUIRE(m->mesh_n_mesh > 0 && m->mesh_xy != nullptr, "the matrix does not carry a mesh (only padne_assemble_system keeps it)");
+    const int n_mesh = (int)m->mesh_n_mesh;
+    hipStream_t s = ctx->stream;
+    if (n_blocks > 0) {
+        hipLaunchKernelGGL(current_face_kernel, dim3((unsigned)n_blocks), dim3(256), 0, s, n_mesh, tile_dev, m->mesh_tri, m->mesh_xy,
+                           m->mesh_voff, m->mesh_toff, m->mesh_sigma, n_cols, V_dev, J_dev, mag_dev, tile_max_dev, tile_face_dev,
+                           box_dev, bad_dev);
+        PADNE_HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(current_mesh_fold, dim3((unsigned)n_mesh), dim3(256), 0, s, n_mesh, tile_dev, (const double *)tile_max_dev,
+                       (const long long *)tile_face_dev, mesh_max_dev, mesh_face_dev);
+    PADNE_HIP_CHECK(hipGetLastError());
+    return PADNE_OK;
+}
+
+// cut_current_kernel over n_pairs (cut, tile) pairs sorted by cut (pair_cut_dev, pair_tile_dev; pair_off_host[n_cut + 1]
+// the first pair of every cut, a host array), then each cut's pairs summed in a fixed order by sensitivity_mesh_fold into
+// cut_dev[n_cut].  cut_xy_dev[n_cut][4] (device).  Asynchronous.
+int launch_cut_currents(padne_ctx *ctx, const padne_csr *m, const long long *tile_dev, int n_cols, const double *V_dev,
+                        int n_cut, const double *cut_xy_dev, long long n_pairs, const int *pair_cut_dev,
+                        const long long *pair_tile_dev, const long long *pair_off_host, double *cut_dev, int *bad_dev) {
+    PADNE_REQUIRE(m->mesh_n_mesh > 0 && m->mesh_xy != nullptr, "the matrix does not carry a mesh (only padne_assemble_system keeps it)");
+    if (n_cut == 0) return PADNE_OK;
+    hipStream_t s = ctx->stream;
+    Scratch sc(ctx);
+    long long *d_off = nullptr;
+    double *d_partial = nullptr;
+    PADNE_TRY(sc.alloc(&d_off, (size_t)n_cut + 1));
+    PADNE_TRY(sc.alloc(&d_partial, (size_t)(n_pairs > 0 ? n_pairs : 1)));
+    PADNE_HIP_CHECK(hipMemcpyAsync(d_off, pair_off_host, sizeof(long long) * ((size_t)n_cut + 1), hipMemcpyHostToDevice, s));
+    if (n_pairs > 0) {
+        hipLaunchKernelGGL(cut_current_kernel, dim3((unsigned)n_pairs), dim3(256), 0, s, (int)m->mesh_n_mesh, tile_dev, m->mesh_tri,
+                           m->mesh_xy, m->mesh_voff, m->mesh_toff, m->mesh_sigma, n_cols, V_dev, pair_cut_dev, pair_tile_dev,
+                           cut_xy_dev, d_partial, bad_dev);
+        PADNE_HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(sensitivity_mesh_fold, dim3((unsigned)n_cut, 1u), dim3(256), 0, s, n_cut, (const long long *)d_off, n_pairs,
+                       (const double *)d_partial, cut_dev);
+    PADNE_HIP_CHECK(hipGetLastError());
     return PADNE_OK;
 }
 }  // namespace padne

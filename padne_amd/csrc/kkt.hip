@@ -27,6 +27,12 @@ int launch_power_density_block(padne_ctx *ctx, const padne_csr *m, int n_cols, c
 int launch_sensitivity_block(padne_ctx *ctx, const padne_csr *m, const long long *tile_off_host, int n_cols, int n_obj,
                              const double *W_dev, const double *V_dev, double *power_dev, double *density_dev, double *total_dev,
                              int *bad_dev);
+int launch_current_faces(padne_ctx *ctx, const padne_csr *m, const long long *tile_dev, long long n_blocks, int n_cols,
+                         const double *V_dev, double *J_dev, double *mag_dev, double *tile_max_dev, long long *tile_face_dev,
+                         double *box_dev, double *mesh_max_dev, long long *mesh_face_dev, int *bad_dev);
+int launch_cut_currents(padne_ctx *ctx, const padne_csr *m, const long long *tile_dev, int n_cols, const double *V_dev,
+                        int n_cut, const double *cut_xy_dev, long long n_pairs, const int *pair_cut_dev,
+                        const long long *pair_tile_dev, const long long *pair_off_host, double *cut_dev, int *bad_dev);
 void amg_info(const padne_csr *A0, int *levels, double *complexity, double *setup_seconds, long long *coarse_n);
 
 constexpr int kCopyStreams = 4;
@@ -1134,6 +1140,23 @@ extern "C" int padne_kkt_power_density_block(padne_ctx *ctx, padne_kkt *k, int32
     return parallel_copy(k, out_host, d_out, sizeof(double) * (size_t)n_tri * (size_t)n_cols, hipMemcpyDeviceToHost);
 }
 
+// the first 256-triangle tile of every mesh of `L`, from its triangle offsets: tile[m] .. tile[m + 1] are mesh m's tiles, the
+// layout of sensitivity_block_kernel and the current kernels
+static int mesh_tiles(padne_ctx *ctx, const padne_csr *L, std::vector<long long> &tile) {
+    const int n_mesh = (int)L->mesh_n_mesh;
+    std::vector<long long> toff((size_t)n_mesh + 1);
+    tile.assign((size_t)n_mesh + 1, 0);
+    PADNE_HIP_CHECK(hipMemcpyAsync(toff.data(), L->mesh_toff, sizeof(long long) * ((size_t)n_mesh + 1), hipMemcpyDeviceToHost,
+                                   ctx->stream));
+    PADNE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    for (int m = 0; m < n_mesh; ++m) {
+        PADNE_REQUIRE(toff[(size_t)m + 1] >= toff[(size_t)m], "mesh triangle offsets");
+        tile[(size_t)m + 1] = tile[(size_t)m] + (toff[(size_t)m + 1] - toff[(size_t)m] + 255) / 256;
+    }
+    PADNE_REQUIRE(tile[(size_t)n_mesh] <= 0x7fffffffLL, "too many triangles for one launch");
+    return PADNE_OK;
+}
+
 // dJ_j / dsigma of every face for the adjoints lambda_j = sum_m weights[j][m] V[:, m] of the finished block, and the power
 // density of its column 0: the tiles of each mesh are laid out here from the mesh's triangle offsets, then one launch over
 // them (sensitivity_block_kernel) and one fold of the per-tile partials per (mesh, objective); the three results go home
@@ -1156,15 +1179,8 @@ extern "C" int padne_kkt_sensitivity_block(padne_ctx *ctx, padne_kkt *k, int32_t
     PADNE_REQUIRE(n_tri == 0 || (power_out && density_out), "null argument");
     PADNE_HIP_CHECK(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    // the first 256-triangle tile of every mesh, from its triangle offsets
-    std::vector<long long> toff((size_t)n_mesh + 1), tile((size_t)n_mesh + 1, 0);
-    PADNE_HIP_CHECK(hipMemcpyAsync(toff.data(), L->mesh_toff, sizeof(long long) * ((size_t)n_mesh + 1), hipMemcpyDeviceToHost, s));
-    PADNE_HIP_CHECK(hipStreamSynchronize(s));
-    for (int m = 0; m < n_mesh; ++m) {
-        PADNE_REQUIRE(toff[(size_t)m + 1] >= toff[(size_t)m], "mesh triangle offsets");
-        tile[(size_t)m + 1] = tile[(size_t)m] + (toff[(size_t)m + 1] - toff[(size_t)m] + 255) / 256;
-    }
-    PADNE_REQUIRE(tile[(size_t)n_mesh] <= 0x7fffffffLL, "too many triangles for one launch");
+    std::vector<long long> tile;
+    PADNE_TRY(mesh_tiles(ctx, L, tile));
     Scratch sc(ctx);
     double *d_w = nullptr, *d_power = nullptr, *d_density = nullptr, *d_total = nullptr;
     int *d_bad = nullptr;
@@ -1187,4 +1203,129 @@ extern "C" int padne_kkt_sensitivity_block(padne_ctx *ctx, padne_kkt *k, int32_t
     }
     if (n_tri == 0) return PADNE_OK;
     return parallel_copy(k, density_out, d_density, sizeof(double) * (size_t)n_tri * (size_t)n_obj, hipMemcpyDeviceToHost);
+}
+
+// Does the segment c = (start x, y, end x, y) meet the box (x_min, y_min, x_max, y_max)?  Separating axes: x, y and the
+// segment's normal.  The box is padded by far more than the rounding of orient(), so that no tile holding an edge the cut
+// kernel counts as crossing is left out; a tile the segment only grazes adds work, not current.
+static bool segment_meets_box(const double *c, const double *box) {
+    double scale = 1.0;
+    for (int q = 0; q < 4; ++q) scale = std::max(scale, std::max(std::fabs(c[q]), std::fabs(box[q])));
+    const double pad = 1e-9 * scale;
+    const double x0 = box[0] - pad, y0 = box[1] - pad, x1 = box[2] + pad, y1 = box[3] + pad;
+    if (std::max(c[0], c[2]) < x0 || std::min(c[0], c[2]) > x1 || std::max(c[1], c[3]) < y0 || std::min(c[1], c[3]) > y1)
+        return false;
+    const double dx = c[2] - c[0], dy = c[3] - c[1];
+    const double cx[4] = {x0, x1, x1, x0}, cy[4] = {y0, y0, y1, y1};
+    int pos = 0, neg = 0;
+    for (int q = 0; q < 4; ++q) {
+        const double o = dx * (cy[q] - c[1]) - dy * (cx[q] - c[0]);
+        pos += o > 0;
+        neg += o < 0;
+    }
+    return pos < 4 && neg < 4;
+}
+
+// The currents of column 0 of the finished block ("Currents"): J = -sigma grad V and |J| of every face, the
+// largest |J| of every mesh, and the current through each cut.  One launch over the tiles of sensitivity_block_kernel's
+// layout writes J, |J|, per-tile maxima and per-tile bounding boxes, and one fold per mesh reduces the maxima.  The boxes
+// come home; the (cut, tile) pairs whose box the cut's segment meets are listed here, on the host; one workgroup per pair
+// and one fold per cut give the cut currents.  No floating-point atomics: two calls give the same bits.
+extern "C" int padne_kkt_current_report(padne_ctx *ctx, padne_kkt *k, int32_t n_cols, int64_t n_tri, int32_t n_mesh,
+                                        const int32_t *mesh_layer, int32_t n_cut, const int32_t *cut_layer, const double *cut_xy,
+                                        double *J_out, double *mag_out, double *mesh_max_out, int64_t *mesh_face_out,
+                                        double *cut_out) {
+    PADNE_REQUIRE(ctx && k, "null argument");
+    PADNE_REQUIRE(k->ctx == ctx, "the plan belongs to another context");
+    PADNE_REQUIRE(k->finished && k->v_final != nullptr,
+                  "padne_kkt_current_report follows padne_kkt_finish_block, with no solve on the plan in between");
+    PADNE_REQUIRE(n_cols == k->finished_cols, "as many columns as the finished block has");
+    PADNE_REQUIRE(n_cut >= 0 && n_cut <= 4096, "between 0 and 4096 cuts");
+    PADNE_REQUIRE(mesh_max_out && mesh_face_out, "null argument");
+    PADNE_REQUIRE(n_cut == 0 || (mesh_layer && cut_layer && cut_xy && cut_out), "null argument");
+    for (int c = 0; c < n_cut; ++c) {
+        const double *p = cut_xy + 4 * (size_t)c;
+        for (int q = 0; q < 4; ++q) PADNE_REQUIRE(std::isfinite(p[q]), "cut end points must be finite");
+        PADNE_REQUIRE(p[0] != p[2] || p[1] != p[3], "a cut's start and end must differ");
+    }
+    const padne_csr *L = k->L;
+    PADNE_REQUIRE(L->mesh_n_mesh > 0 && L->mesh_xy != nullptr,
+                  "the system matrix does not carry a mesh (only padne_assemble_system keeps it)");
+    PADNE_REQUIRE(L->mesh_n_vert <= k->N, "the mesh has more vertices than the system has unknowns");
+    PADNE_REQUIRE(n_tri == L->mesh_n_tri && n_mesh == L->mesh_n_mesh, "n_tri and n_mesh must be those of the system's mesh");
+    PADNE_REQUIRE(n_tri == 0 || (J_out && mag_out), "null argument");
+    PADNE_HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    std::vector<long long> tile;
+    PADNE_TRY(mesh_tiles(ctx, L, tile));
+    const long long n_blocks = tile[(size_t)n_mesh];
+    const size_t nb = (size_t)(n_blocks > 0 ? n_blocks : 1), nt = (size_t)(n_tri > 0 ? n_tri : 1);
+    Scratch sc(ctx);
+    long long *d_tile = nullptr, *d_tface = nullptr, *d_mface = nullptr;
+    double *d_J = nullptr, *d_mag = nullptr, *d_tmax = nullptr, *d_box = nullptr, *d_mmax = nullptr;
+    int *d_bad = nullptr;
+    PADNE_TRY(sc.alloc(&d_tile, (size_t)n_mesh + 1));
+    PADNE_TRY(sc.alloc(&d_J, 2 * nt));
+    PADNE_TRY(sc.alloc(&d_mag, nt));
+    PADNE_TRY(sc.alloc(&d_tmax, nb));
+    PADNE_TRY(sc.alloc(&d_tface, nb));
+    PADNE_TRY(sc.alloc(&d_box, 4 * nb));
+    PADNE_TRY(sc.alloc(&d_mmax, (size_t)n_mesh));
+    PADNE_TRY(sc.alloc(&d_mface, (size_t)n_mesh));
+    PADNE_TRY(sc.alloc(&d_bad, 1));
+    PADNE_HIP_CHECK(hipMemcpyAsync(d_tile, tile.data(), sizeof(long long) * ((size_t)n_mesh + 1), hipMemcpyHostToDevice, s));
+    PADNE_HIP_CHECK(hipMemsetAsync(d_bad, 0, sizeof(int), s));
+    PADNE_TRY(launch_current_faces(ctx, L, d_tile, n_blocks, n_cols, k->v_final, d_J, d_mag, d_tmax, d_tface, d_box, d_mmax,
+                                   d_mface, d_bad));
+    if (n_cut > 0) {
+        // the (cut, tile) pairs, by cut and then by tile: the tiles of the meshes on the cut's layer whose box the segment meets
+        std::vector<double> box(4 * nb);
+        if (n_blocks > 0)
+            PADNE_HIP_CHECK(hipMemcpyAsync(box.data(), d_box, sizeof(double) * 4 * (size_t)n_blocks, hipMemcpyDeviceToHost, s));
+        PADNE_HIP_CHECK(hipStreamSynchronize(s));
+        std::vector<int> pair_cut;
+        std::vector<long long> pair_tile, pair_off((size_t)n_cut + 1, 0);
+        for (int c = 0; c < n_cut; ++c) {
+            for (int m = 0; m < n_mesh; ++m) {
+                if (mesh_layer[m] != cut_layer[c]) continue;
+                for (long long b = tile[(size_t)m]; b < tile[(size_t)m + 1]; ++b)
+                    if (segment_meets_box(cut_xy + 4 * (size_t)c, box.data() + 4 * (size_t)b)) {
+                        pair_cut.push_back(c);
+                        pair_tile.push_back(b);
+                    }
+            }
+            pair_off[(size_t)c + 1] = (long long)pair_tile.size();
+        }
+        const long long n_pairs = (long long)pair_tile.size();
+        PADNE_REQUIRE(n_pairs <= 0x7fffffffLL, "too many (cut, tile) pairs for one launch");
+        const size_t np = (size_t)(n_pairs > 0 ? n_pairs : 1);
+        double *d_cut_xy = nullptr, *d_cut = nullptr;
+        int *d_pair_cut = nullptr;
+        long long *d_pair_tile = nullptr;
+        PADNE_TRY(sc.alloc(&d_cut_xy, 4 * (size_t)n_cut));
+        PADNE_TRY(sc.alloc(&d_cut, (size_t)n_cut));
+        PADNE_TRY(sc.alloc(&d_pair_cut, np));
+        PADNE_TRY(sc.alloc(&d_pair_tile, np));
+        PADNE_HIP_CHECK(hipMemcpyAsync(d_cut_xy, cut_xy, sizeof(double) * 4 * (size_t)n_cut, hipMemcpyHostToDevice, s));
+        if (n_pairs > 0) {
+            PADNE_HIP_CHECK(hipMemcpyAsync(d_pair_cut, pair_cut.data(), sizeof(int) * (size_t)n_pairs, hipMemcpyHostToDevice, s));
+            PADNE_HIP_CHECK(hipMemcpyAsync(d_pair_tile, pair_tile.data(), sizeof(long long) * (size_t)n_pairs, hipMemcpyHostToDevice, s));
+        }
+        PADNE_TRY(launch_cut_currents(ctx, L, d_tile, n_cols, k->v_final, n_cut, d_cut_xy, n_pairs, d_pair_cut, d_pair_tile,
+                                      pair_off.data(), d_cut, d_bad));
+        PADNE_HIP_CHECK(hipMemcpyAsync(cut_out, d_cut, sizeof(double) * (size_t)n_cut, hipMemcpyDeviceToHost, s));
+        PADNE_HIP_CHECK(hipStreamSynchronize(s));       // (the copies read the host vectors above before they go)
+    }
+    int h_bad = 0;
+    PADNE_HIP_CHECK(hipMemcpyAsync(&h_bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    PADNE_HIP_CHECK(hipMemcpyAsync(mesh_max_out, d_mmax, sizeof(double) * (size_t)n_mesh, hipMemcpyDeviceToHost, s));
+    PADNE_HIP_CHECK(hipMemcpyAsync(mesh_face_out, d_mface, sizeof(long long) * (size_t)n_mesh, hipMemcpyDeviceToHost, s));
+    PADNE_HIP_CHECK(hipStreamSynchronize(s));
+    if (h_bad) {
+        set_error("invalid argument: triangle index out of range");
+        return PADNE_E_INVALID;
+    }
+    if (n_tri == 0) return PADNE_OK;
+    PADNE_TRY(parallel_copy(k, J_out, d_J, sizeof(double) * 2 * (size_t)n_tri, hipMemcpyDeviceToHost));
+    return parallel_copy(k, mag_out, d_mag, sizeof(double) * (size_t)n_tri, hipMemcpyDeviceToHost);
 }

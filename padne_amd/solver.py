@@ -20,6 +20,8 @@ compute_power_density :728-745         ``power_density_kernel``
                                        power densities from the potentials on the device
 (where a voltage drop comes from)      ``solve_sensitivities``: adjoints on the load-case block, Woodbury for
                                        regulators, ``sensitivity_block_kernel`` over the faces
+(where the current goes)               ``solve_currents``: the load-case block with one column, ``current_face_kernel``
+                                       and ``cut_current_kernel`` over the faces, element flows from V's rows
 =====================================  ====================================================
 
 There is no CPU fallback: every entry point that computes raises
@@ -1316,22 +1318,24 @@ def element_sensitivities(element_rows, x: np.ndarray, lam: np.ndarray) -> list:
 
 def _sensitivity_elements(pairs, V: np.ndarray, W: np.ndarray) -> list:
     """element_sensitivities of every objective, with x and lambda gathered at the elements' unknowns only."""
-    rows = [row for _, row in pairs]
-    used = sorted({int(i) for row in rows for i in (row[1:3] if row[0] in ("R", "I") else
-                                                      (row[4],) if row[0] == "V" else (row[3], row[4], row[7]))})
-    at = {g: i for i, g in enumerate(used)}
-    local = []
-    for row in rows:
-        if row[0] in ("R", "I"):
-            local.append((row[0], at[row[1]], at[row[2]], row[3]))
-        elif row[0] == "V":
-            local.append((row[0], row[1], row[2], row[3], at[row[4]]))
-        else:
-            local.append((row[0], row[1], row[2], at[row[3]], at[row[4]], row[5], row[6], at[row[7]]))
-    Vu = V[np.asarray(used, dtype=np.int64)] if used else np.zeros((0, V.shape[1]))
+    local, Vu = _gather_element_rows([row for _, row in pairs], V)
     x, lam = Vu[:, 0], Vu @ W.T
     per_obj = [element_sensitivities(local, x, lam[:, j]) for j in range(W.shape[0])]
     return [{element: d[i] for i, (element, _) in enumerate(pairs)} for d in per_obj]
+
+
+_ROW_UNKNOWNS = {"R": (1, 2), "I": (1, 2), "V": (1, 2, 4), "REG": (1, 2, 3, 4, 7)}     # where global_elements' rows name unknowns
+_ROW_SENSITIVITY_UNKNOWNS = {"R": (1, 2), "I": (1, 2), "V": (4,), "REG": (3, 4, 7)}       # the ones element_sensitivities reads
+
+
+def _gather_element_rows(rows, V: np.ndarray, positions=_ROW_SENSITIVITY_UNKNOWNS):
+    """(the element rows with the unknowns at ``positions`` renumbered into the gathered rows, V's rows at those unknowns
+    (n_used, n_cols)): V is read at the elements' unknowns only."""
+    used = sorted({int(row[p]) for row in rows for p in positions[row[0]]})
+    at = {g: i for i, g in enumerate(used)}
+    local = [tuple(at[int(v)] if p in positions[row[0]] else v for p, v in enumerate(row)) for row in rows]
+    Vu = V[np.asarray(used, dtype=np.int64)] if used else np.zeros((0, V.shape[1]))
+    return local, Vu
 
 
 def solve_meshed_sensitivities(prob, meshes, mesh_index_to_layer_index, objectives, *, filtered_networks=None,
@@ -1355,6 +1359,22 @@ def solve_meshed_sensitivities(prob, meshes, mesh_index_to_layer_index, objectiv
     ``partition`` over several GPUs."""
     return _sensitivity_solution(prob, meshes, mesh_index_to_layer_index, objectives, filtered_networks,
                                  disconnected_meshes_by_layer, partition)
+
+
+def _block_column_zero_solution(prob, vindex, meshes, mesh_index_to_layer_index, disconnected_meshes_by_layer, V, residual_norms,
+                                res, power, cols, vals, n_cols: int) -> Solution:
+    """The Solution of ``prob`` from column 0 of a solved block (the block's triples ``cols``, ``vals`` name the stalled
+    columns in the warning) and column 0's power densities ``power``; its SolverInfo reports the block solve as a whole."""
+    if _stalled(res, RTOL):
+        col_norms = np.sqrt(np.bincount(cols, weights=vals * vals, minlength=n_cols))
+        _warn_if_stalled(res, RTOL, _stalled_columns(residual_norms, col_norms=col_norms))
+    ground_node_current = float(V[-1, 0])
+    _warn_ground_current(ground_node_current)
+    info = SolverInfo(ground_node_current=ground_node_current, residual_norm=float(residual_norms[0]),
+                      iterations=int(res.iterations), rel_residual=float(res.rel_residual), solve_seconds=float(res.seconds))
+    layer_solutions = produce_layer_solutions(prob.layers, vindex, meshes, mesh_index_to_layer_index, np.ascontiguousarray(V[:, 0]),
+                                              disconnected_meshes_by_layer, power_all=power)
+    return Solution(problem=prob, layer_solutions=layer_solutions, solver_info=info)
 
 
 def _sensitivity_solution(prob, meshes, mesh_index_to_layer_index, objectives, filtered_networks, disconnected_meshes_by_layer,
@@ -1388,17 +1408,9 @@ def _sensitivity_solution(prob, meshes, mesh_index_to_layer_index, objectives, f
     finally:
         L.close()
     t3 = time.perf_counter()
-    if _stalled(res, RTOL):
-        col_norms = np.sqrt(np.bincount(cols, weights=vals * vals, minlength=n_cols))
-        _warn_if_stalled(res, RTOL, _stalled_columns(residual_norms, col_norms=col_norms))
     log.info("Producing the solution and the sensitivities")
-    ground_node_current = float(V[-1, 0])
-    _warn_ground_current(ground_node_current)
-    info = SolverInfo(ground_node_current=ground_node_current, residual_norm=float(residual_norms[0]),
-                      iterations=int(res.iterations), rel_residual=float(res.rel_residual), solve_seconds=float(res.seconds))
-    layer_solutions = produce_layer_solutions(prob.layers, vindex, meshes, mesh_index_to_layer_index, np.ascontiguousarray(V[:, 0]),
-                                              disconnected_meshes_by_layer, power_all=power)
-    solution = Solution(problem=prob, layer_solutions=layer_solutions, solver_info=info)
+    solution = _block_column_zero_solution(prob, vindex, meshes, mesh_index_to_layer_index, disconnected_meshes_by_layer, V,
+                                           residual_norms, res, power, cols, vals, n_cols)
     elements = _sensitivity_elements(pairs, V, W)
     toff = np.concatenate([[0], np.cumsum([len(m.triangles) for m in meshes])]).astype(np.int64)
     sens = []
@@ -1427,6 +1439,23 @@ def _solve_sensitivity_block(L: SystemMatrix, rows, cols, vals, n_cols: int, k: 
     """The block solve of a sensitivity call, then the adjoint weights on the host and the face kernel on the V the device
     holds.  Returns (V (N, n_cols), ||L v_j - r_j|| (n_cols,), SolveResult, power of column 0 (n_tri,), s_f / area_f
     (k, n_tri), per-mesh sums of s_f (k, n_mesh), W (k, n_cols)); the three face arrays are None without triangles."""
+    plan, V, residual_norms, res, n_tri, n_mesh = _solve_block_on_device(L, rows, cols, vals, n_cols, 1 + k, timings)
+    t2 = time.perf_counter()
+    W = adjoint_weights(V, k, terms)
+    power = density = totals = None
+    if n_tri:
+        power, density, totals = plan.sensitivity_block(W, n_tri, n_mesh)
+    if timings is not None:
+        timings.update(sensitivity=time.perf_counter() - t2)
+    return V, residual_norms, res, power, density, totals, W
+
+
+def _solve_block_on_device(L: SystemMatrix, rows, cols, vals, n_cols: int, power_rows: int, timings: Optional[dict] = None,
+                           currents: bool = False):
+    """The load-case block path up to the potentials: reduction, plan, ``solve_block_coo`` of the triples, ``_finish_block``.
+    The final V stays on the device for the face kernels that follow; ``power_rows``: the rows of the power-density array
+    those return, made ready while the device solves (with ``currents``, the arrays of ``current_report`` too).  Returns
+    (plan, V (N, n_cols), ||L v_j - r_j|| (n_cols,), SolveResult, n_tri, n_mesh); ``timings`` receives stage1 and stage2."""
     t0 = time.perf_counter()
     layout = L.layout
     if layout is None or not layout.constraints:
@@ -1441,17 +1470,12 @@ def _solve_sensitivity_block(L: SystemMatrix, rows, cols, vals, n_cols: int, k: 
     n_mesh = len(L.mesh_offsets) - 1 if L.mesh_offsets is not None else 0
     probes, res = plan.solve_block_coo(n_cols, rows, cols, vals, known_idx, known_val, extras, members, rtol=RTOL,
                                        max_iter=MAX_ITER, abs_residual_target=ABS_RESIDUAL_TARGET, power_tri=n_tri,
-                                       power_rows=1 + k)
+                                       power_rows=power_rows, current_tri=n_tri if currents else 0)
     t1 = time.perf_counter()
     V, residual_norms = _finish_block(plan, red, members, probes, n_cols)
-    t2 = time.perf_counter()
-    W = adjoint_weights(V, k, terms)
-    power = density = totals = None
-    if n_tri:
-        power, density, totals = plan.sensitivity_block(W, n_tri, n_mesh)
     if timings is not None:
-        timings.update(stage1=t1 - t0, stage2=t2 - t1, sensitivity=time.perf_counter() - t2)
-    return V, residual_norms, res, power, density, totals, W
+        timings.update(stage1=t1 - t0, stage2=time.perf_counter() - t1)
+    return plan, V, residual_norms, res, n_tri, n_mesh
 
 
 def solve_sensitivities(prob, objectives, mesher_config: Optional[mesh.Mesher.Config] = None, *, mesher=None,
@@ -1464,3 +1488,231 @@ def solve_sensitivities(prob, objectives, mesher_config: Optional[mesh.Mesher.Co
     objectives = check_objectives(prob, objectives)
     meshes, mesh_index_to_layer_index = _mesh_problem(prob, mesher_config, mesher)
     return solve_meshed_sensitivities(prob, meshes, mesh_index_to_layer_index, objectives)
+
+
+# --------------------------------------------------------------------------------------------
+# currents: where the current goes (DESIGN.md "Currents")
+# --------------------------------------------------------------------------------------------
+
+MAX_CUTS = 4096
+
+
+@dataclass(frozen=True)
+class Cut:
+    """A directed straight segment on one layer of a Problem (``layer`` is matched by identity).  ``start`` and ``end`` are
+    (x, y) in mm: a 2-sequence or an object with ``.x`` / ``.y``, like ``Connection.point``.  Its current is the current
+    that crosses it from the left of start -> end to its right."""
+    layer: object
+    start: object
+    end: object
+
+
+@dataclass
+class CurrentReport:
+    """Where the current of a solved Problem goes (see :func:`solve_meshed_currents`)."""
+    vectors: list         # per layer, per mesh of LayerSolution.meshes: (n_faces, 2) J = -sigma grad V [A/mm]
+    magnitudes: list      # per layer, per mesh: TwoForm of |J| [A/mm]
+    hotspots: list        # per layer: (max |J|, mesh index within the layer, face index, centroid x, y), None without faces
+    layers: list          # per layer: the power dissipated in its copper [W]
+    elements: dict        # lumped element -> {"current": A, "power": W} (+ "input_current", "input_power": regulators)
+    cuts: list            # per cut, in the order given: the current crossing it [A]
+
+
+def _cut_point(p, j: int, which: str) -> tuple:
+    if hasattr(p, "x") and hasattr(p, "y"):
+        xy = (p.x, p.y)
+    elif isinstance(p, (str, bytes, Mapping)):
+        raise ValueError(f"cut {j}: {which} must be (x, y) or have .x and .y")
+    else:
+        try:
+            xy = tuple(p)
+        except TypeError:
+            raise ValueError(f"cut {j}: {which} must be (x, y) or have .x and .y") from None
+        if len(xy) != 2:
+            raise ValueError(f"cut {j}: {which} must be (x, y), not {len(xy)} numbers")
+    try:
+        x, y = float(xy[0]), float(xy[1])
+    except (TypeError, ValueError):
+        raise ValueError(f"cut {j}: {which} must be two numbers") from None
+    if not (math.isfinite(x) and math.isfinite(y)):
+        raise ValueError(f"cut {j}: {which} is not finite")
+    return x, y
+
+
+def check_cuts(prob, cuts) -> list:
+    """The cuts as (layer index, (x0, y0), (x1, y1)), or ValueError: at most MAX_CUTS of them, each a :class:`Cut` (or an
+    object with ``layer``, ``start``, ``end``) whose layer is one of ``prob.layers`` (by identity), with finite end points
+    that differ."""
+    if isinstance(cuts, (str, bytes, Mapping)) or all(hasattr(cuts, a) for a in ("layer", "start", "end")):
+        raise ValueError("cuts must be a sequence of Cut")
+    try:
+        cuts = list(cuts)
+    except TypeError:
+        raise ValueError("cuts must be a sequence of Cut") from None
+    if len(cuts) > MAX_CUTS:
+        raise ValueError(f"{len(cuts)} cuts: at most {MAX_CUTS} in one call")
+    out = []
+    for j, cut in enumerate(cuts):
+        if not all(hasattr(cut, a) for a in ("layer", "start", "end")):
+            raise ValueError(f"cut {j} is not a Cut(layer, start, end)")
+        layer_i = next((i for i, layer in enumerate(prob.layers) if layer is cut.layer), None)
+        if layer_i is None:
+            raise ValueError(f"cut {j}: its layer is not one of the Problem's layers")
+        a, b = _cut_point(cut.start, j, "start"), _cut_point(cut.end, j, "end")
+        if a == b:
+            raise ValueError(f"cut {j}: start and end are the same point")
+        out.append((layer_i, a, b))
+    return out
+
+
+def element_flows(element_rows, x: np.ndarray) -> list:
+    """Current and power of every element row (global_elements' tuples, indices into ``x``), one dict per row.
+
+    Passive sign convention: ``current`` flows through the element from its first terminal to its second, and ``power`` =
+    (x_first - x_second) current is what the element absorbs.  With L = -G, row j of L x = r says that minus the current
+    leaving j through the copper and the resistors, plus the stamped source terms, is r_j: every element term of row j is
+    minus the current that leaves j through that element.  Hence:
+
+    - Resistor (a, b):         row a holds -(x_a - x_b)/R, so current = (x_a - x_b) / R;
+    - CurrentSource (f, t):    r_f = +current moves to the left as -current: the source takes ``current`` out of f and
+      delivers it to t, so current = its ``current`` field, exactly;
+    - VoltageSource (p, n):    row p holds +x_iv, so -x_iv leaves p through the source: current = -x_iv;
+    - VoltageRegulator output (v_p, v_n): the same stamps, current = -x_iv;
+    - VoltageRegulator input (s_f, s_t):  row s_f holds +gain x_iv: input_current = -gain x_iv, and input_power =
+      (x_sf - x_st) input_current.
+
+    The powers of all elements and the copper's dissipation add up to zero (Tellegen)."""
+    out = []
+    for row in element_rows:
+        kind = row[0]
+        if kind == "R":
+            _, a, b, res = row
+            cur = (x[a] - x[b]) / res
+            out.append({"current": float(cur), "power": float((x[a] - x[b]) * cur)})
+        elif kind == "I":
+            _, f, t, cur = row
+            out.append({"current": float(cur), "power": float((x[f] - x[t]) * cur)})
+        elif kind == "V":
+            _, p, n, _u, iv = row
+            cur = -x[iv]
+            out.append({"current": float(cur), "power": float((x[p] - x[n]) * cur)})
+        elif kind == "REG":
+            _, vp, vn, sf, st, _u, gain, iv = row
+            cur, cin = -x[iv], -gain * x[iv]
+            out.append({"current": float(cur), "power": float((x[vp] - x[vn]) * cur), "input_current": float(cin),
+                        "input_power": float((x[sf] - x[st]) * cin)})
+        else:
+            raise NotImplementedError(f"Unsupported element row {row}")
+    return out
+
+
+def solve_meshed_currents(prob, meshes, mesh_index_to_layer_index, cuts=(), *, filtered_networks=None,
+                          disconnected_meshes_by_layer=None, partition=None):
+    """``solve_meshed`` together with where the current goes: (Solution, CurrentReport).
+
+    - ``vectors`` / ``magnitudes``: per face J = -sigma grad V [A/mm], the sheet current density, with sigma the layer's
+      conductance and grad V the face gradient of the power density, so |J|^2 / sigma is the power density;
+    - ``hotspots``: per layer the largest |J| (the lowest global face on a tie), its mesh within the layer, its face and the
+      face's centroid;
+    - ``layers``: per layer the power in its copper, sum over faces of sigma sum_edges w_ik (V_i - V_k)^2 with the
+      assembly's |cot|/2 weights.  Not the gradient form A |J|^2 / sigma: the two differ on obtuse faces, and only the
+      weights' form balances the elements' powers exactly;
+    - ``elements``: current and power of every lumped element of the solved networks (:func:`element_flows`);
+    - ``cuts``: per :class:`Cut`, the current crossing it from its left to its right.  Every face edge (P, Q), P the lower
+      global vertex, whose ends lie on different sides of the cut's line (a vertex on the line counts as right) and which
+      the segment crosses adds sigma |cot|/2 (V_left - V_right) from each of its faces.  A cut whose ends lie outside the
+      copper and which splits a piece of copper in two gives the current between the two parts exactly (KCL on L x = r).
+      A cut that ends inside copper measures a flux through the segment that is not conserved: it depends on where the
+      segment ends.  Polylines and closed contours are out of scope; several cuts sum.
+
+    One call is the load-case block path with one column and its face kernels on the V the device holds; element currents
+    come from V's rows at the elements' unknowns.  Disconnected meshes carry no current and take no part.  The Solution is
+    that of ``prob``, filled as ``solve_meshed_sensitivities`` fills it.  ValueError, before anything reaches the device, for
+    invalid cuts (:func:`check_cuts`) and for a ``partition`` over several GPUs."""
+    return _currents_solution(prob, meshes, mesh_index_to_layer_index, cuts, filtered_networks, disconnected_meshes_by_layer,
+                              partition)
+
+
+def _refuse_partition(partition) -> None:
+    if partition is not None and partition.world > 1:
+        raise ValueError("currents are solved on one GPU: the row-partitioned path (partition.world > 1) does not take them")
+
+
+def _currents_solution(prob, meshes, mesh_index_to_layer_index, cuts, filtered_networks, disconnected_meshes_by_layer,
+                       partition, timings: Optional[dict] = None):
+    """solve_meshed_currents; ``timings`` (a dict) receives the host time of each step in seconds."""
+    _refuse_partition(partition)
+    cuts = check_cuts(prob, cuts)
+    t0 = time.perf_counter()
+    meshes, filtered_networks, disconnected_meshes_by_layer = _meshed_inputs(prob, meshes, filtered_networks,
+                                                                             disconnected_meshes_by_layer)
+    log.info("Indexing vertices and connections")
+    vindex = VertexIndexer.create(meshes)
+    node_indexer = NodeIndexer.create(prob, meshes, mesh_index_to_layer_index, vindex, filtered_networks)
+    pairs = global_elements(filtered_networks, node_indexer)
+    t1 = time.perf_counter()
+    log.info("Assembling the global system")
+    L, _ = assemble_system(prob, meshes, mesh_index_to_layer_index, vindex, filtered_networks, node_indexer)
+    try:
+        rows, cols, vals = stamp_load_cases(filtered_networks, node_indexer, L.shape[0], [{}])
+        t2 = time.perf_counter()
+        log.info("Solving the Problem and its currents")
+        plan, V, residual_norms, res, n_tri, _n_mesh = _solve_block_on_device(L, rows, cols, vals, 1, 2, timings, currents=True)
+        t3 = time.perf_counter()
+        power = J = mag = mesh_max = mesh_face = totals = None
+        cut_values = np.zeros(len(cuts))
+        if n_tri:
+            # sigma sum w (dx)^2 per mesh: the sensitivity kernel with lambda = x; then the current kernels
+            power, _, totals = plan.sensitivity_block(np.ones((1, 1)), n_tri, len(meshes))
+            J, mag, mesh_max, mesh_face, cut_values = plan.current_report(
+                1, n_tri, np.asarray(mesh_index_to_layer_index, dtype=np.int32), [c[0] for c in cuts],
+                np.array([[*a, *b] for _, a, b in cuts], dtype=DTYPE).reshape(-1, 4))
+    finally:
+        L.close()
+    t4 = time.perf_counter()
+    log.info("Producing the solution and the current report")
+    solution = _block_column_zero_solution(prob, vindex, meshes, mesh_index_to_layer_index, disconnected_meshes_by_layer, V,
+                                           residual_norms, res, power, cols, vals, 1)
+    local, Vu = _gather_element_rows([row for _, row in pairs], V, _ROW_UNKNOWNS)
+    flows = element_flows(local, Vu[:, 0])
+    toff = np.concatenate([[0], np.cumsum([len(m.triangles) for m in meshes])]).astype(np.int64)
+    vectors, magnitudes, hotspots, layer_power = [], [], [], []
+    for layer_i in range(len(prob.layers)):
+        vecs, forms, total, best = [], [], 0.0, None
+        for mesh_i, msh in enumerate(meshes):
+            if mesh_index_to_layer_index[mesh_i] != layer_i:
+                continue
+            tf = mesh.TwoForm(msh)
+            if J is not None:
+                lo, hi = toff[mesh_i], toff[mesh_i + 1]
+                vecs.append(J[lo:hi])                     # views of this call's own result arrays: no copies
+                tf.values = mag[lo:hi]
+                total += float(totals[0, mesh_i])
+                # meshes come in global face order: a later mesh wins only with a strictly larger |J|
+                if mesh_face[mesh_i] >= 0 and (best is None or mesh_max[mesh_i] > best[0]):
+                    face = int(mesh_face[mesh_i] - lo)
+                    cx, cy = msh.points[msh.triangles[face]].mean(axis=0)
+                    best = (float(mesh_max[mesh_i]), len(forms), face, float(cx), float(cy))
+            else:
+                vecs.append(np.zeros((len(msh.triangles), 2), dtype=DTYPE))
+            forms.append(tf)
+        vectors.append(vecs)
+        magnitudes.append(forms)
+        hotspots.append(best)
+        layer_power.append(total)
+    report = CurrentReport(vectors=vectors, magnitudes=magnitudes, hotspots=hotspots, layers=layer_power,
+                           elements={element: flows[i] for i, (element, _) in enumerate(pairs)},
+                           cuts=[float(c) for c in cut_values])
+    if timings is not None:
+        timings.update(indexing=t1 - t0, assembly=t2 - t1, currents=t4 - t3, solutions=time.perf_counter() - t4)
+    return solution, report
+
+
+def solve_currents(prob, cuts=(), mesher_config: Optional[mesh.Mesher.Config] = None, *, mesher=None, partition=None):
+    """``solve`` with where the current goes (see :func:`solve_meshed_currents`): the board is meshed once.  Returns
+    (Solution, CurrentReport)."""
+    _refuse_partition(partition)
+    cuts = check_cuts(prob, cuts)
+    meshes, mesh_index_to_layer_index = _mesh_problem(prob, mesher_config, mesher)
+    return solve_meshed_currents(prob, meshes, mesh_index_to_layer_index,
+                                 [Cut(prob.layers[i], a, b) for i, a, b in cuts])
