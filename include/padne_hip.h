@@ -47,6 +47,7 @@ extern "C" {
 typedef struct padne_ctx padne_ctx;   /* device, stream, workspaces, optional RCCL communicator */
 typedef struct padne_csr padne_csr;   /* device-resident CSR matrix (f64 values, i32 indices)  */
 typedef struct padne_kkt padne_kkt;   /* device-resident plan of solve_system for one assembled system */
+typedef struct padne_sampler padne_sampler;   /* device-resident meshes, potentials and point-location index of a solved board */
 
 /* ---- library / context ------------------------------------------------------------------- */
 int         padne_abi_version(void);
@@ -415,6 +416,40 @@ int padne_face_gradient(padne_ctx *ctx, int64_t n_vert, const double *xy_host,
                         int64_t n_mesh, const int64_t *mesh_vertex_offset,
                         const int64_t *mesh_tri_offset, const double *potential_host,
                         double *gx_out_host, double *gy_out_host);
+
+/* ---- field sampler: the solved fields at points and on rasters --------------------------------
+ * No reference counterpart in the solver: the reference's viewer reads out the nearest vertex / nearest face centroid under
+ * the cursor (ui.py:192-267).  A sampler keeps the meshes, the potentials and one uniform grid of bins per layer on the
+ * device until it is destroyed (before its context).  Meshes as in padne_power_density, mesh_layer[m] in [0, n_layer) the
+ * layer of mesh m, potential_host[n_vert] in the global vertex numbering.  bins_hint: the number of bins of every layer's
+ * grid, 0 = chosen from the face count (one bin per two faces); a layer whose lists come to more than 16 entries per face
+ * is rebuilt with half the bins per side.
+ *
+ * The owner of a query point q on a layer: side(i, k) = orient(P, Q, q) for the edge from its lower global vertex P to its
+ * higher Q, negated where the face runs the edge from Q to P (orient as in padne_kkt_current_report).  A face contains q
+ * when its three sides are all >= 0 or all <= 0 and not all zero; the owner is the containing face with the lowest global
+ * index among the meshes of the layer.  The index never changes an answer.  Per query: face_out = the owner (global face
+ * index; -1 outside the copper, and then the other three are NaN); v_out = ((o_a / s) V_a + (o_b / s) V_b) + (o_c / s) V_c
+ * with o_a the side of the edge opposite corner a = tri[0] (o_b, o_c alike) and s = (o_a + o_b) + o_c; j_out[2] and p_out
+ * = the owner's row of padne_kkt_current_report's J_out and its padne_power_density value, bit for bit. */
+int padne_sampler_create(padne_ctx *ctx, int64_t n_vert, const double *xy_host, int64_t n_tri, const int32_t *tri_host,
+                         int32_t n_mesh, const int64_t *mesh_vertex_offset, const int64_t *mesh_tri_offset,
+                         const int32_t *mesh_layer, const double *conductance, int32_t n_layer, const double *potential_host,
+                         int64_t bins_hint, padne_sampler **out);
+int padne_sampler_destroy(padne_sampler *s);
+/* n query points xy_host[n][2] on `layer` -> face_out[n], v_out[n], j_out[n][2], p_out[n].  PADNE_E_INVALID for a null
+ * handle, a layer out of range, a point that is not finite and more than 2^26 points. */
+int padne_sampler_points(padne_ctx *ctx, padne_sampler *s, int32_t layer, int64_t n, const double *xy_host, int32_t *face_out,
+                         double *v_out, double *j_out, double *p_out);
+/* The same at the pixel centres (x0 + (i + 0.5) dx, y0 + (j + 0.5) dy) of a raster, row j and column i at j * width + i;
+ * the kernel forms the points itself, nothing is uploaded.  PADNE_E_INVALID also for a pixel size that is not finite and
+ * positive, a width or height below 1 and more than 2^26 pixels. */
+int padne_sampler_raster(padne_ctx *ctx, padne_sampler *s, int32_t layer, double x0, double y0, double dx, double dy,
+                         int64_t width, int64_t height, int32_t *face_out, double *v_out, double *j_out, double *p_out);
+/* counts_out[6] = bins along x and y, list entries and faces of `layer`, then the candidate faces tested and the queries of
+ * the last query call (any layer); seconds_out[3] = host time of the upload and of the index build in create, device time
+ * of the last query kernel. */
+int padne_sampler_stats(const padne_sampler *s, int32_t layer, int64_t *counts_out, double *seconds_out);
 
 /* ---- introspection for benchmarks ---------------------------------------------------------- */
 /* algorithmic bytes of one CSR SpMV: 12*nnz + 20*n_rows + 4   */

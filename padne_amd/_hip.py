@@ -123,6 +123,13 @@ SIGNATURES = {
     "padne_power_density": (C.c_int, [_P, _I64, _PF64, _I64, _PI32, _I64, _PI64, _PI64, _PF64, _PF64, _PF64]),
     "padne_csr_power_density": (C.c_int, [_P, _P, _PF64, _PF64]),
     "padne_face_gradient": (C.c_int, [_P, _I64, _PF64, _I64, _PI32, _I64, _PI64, _PI64, _PF64, _PF64, _PF64]),
+    "padne_sampler_create": (C.c_int, [_P, _I64, _PF64, _I64, _PI32, C.c_int32, _PI64, _PI64, _PI32, _PF64, C.c_int32, _PF64, _I64,
+                                       C.POINTER(_P)]),
+    "padne_sampler_destroy": (C.c_int, [_P]),
+    "padne_sampler_points": (C.c_int, [_P, _P, C.c_int32, _I64, _PF64, _PI32, _PF64, _PF64, _PF64]),
+    "padne_sampler_raster": (C.c_int, [_P, _P, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, _I64, _I64, _PI32,
+                                       _PF64, _PF64, _PF64]),
+    "padne_sampler_stats": (C.c_int, [_P, C.c_int32, _PI64, _PF64]),
     "padne_spmv_algorithmic_bytes": (_I64, [_P]),
     "padne_spmv_time": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _PF64]),
 }
@@ -817,6 +824,70 @@ class KktPlan:
         _check(self.ctx._lib.padne_kkt_finish_block(self.ctx._h, self._h, k, coeff.shape[1], _ptr(coeff, _PF64), midx.shape[0],
                                                     _ptr(midx, _PI64), _ptr(mval, _PF64), _ptr(V, _PF64), _ptr(norms, _PF64)))
         return V, norms
+
+
+class Sampler:
+    """``padne_sampler``: meshes, potentials and a point-location index per layer, resident on the device until ``close``
+    (include/padne_hip.h, "field sampler").  Queries return (face (n,) int32 global face or -1, V (n,), J (n, 2), p (n,))."""
+
+    def __init__(self, ctx: "Context", xy, tri, mesh_vertex_offset, mesh_tri_offset, mesh_layer, conductance, n_layer: int,
+                 potential, bins_hint: int = 0):
+        xy, tri = _f64(xy).reshape(-1, 2), _i32(tri).reshape(-1, 3)
+        mvo, mto, ml, sig = _i64(mesh_vertex_offset), _i64(mesh_tri_offset), _i32(mesh_layer).reshape(-1), _f64(conductance)
+        pot = _f64(potential).reshape(-1)
+        n_mesh = ml.shape[0]
+        if mvo.shape[0] != n_mesh + 1 or mto.shape[0] != n_mesh + 1 or sig.shape[0] != n_mesh:
+            raise ValueError("offset tables must have n_mesh+1 entries and every mesh a conductance")
+        if pot.shape[0] != xy.shape[0]:
+            raise ValueError("one potential per vertex")
+        self.ctx, self.n_layer = ctx, int(n_layer)
+        h = _P()
+        _check(ctx._lib.padne_sampler_create(ctx._h, xy.shape[0], _ptr(xy, _PF64), tri.shape[0], _ptr(tri, _PI32), n_mesh,
+                                             _ptr(mvo, _PI64), _ptr(mto, _PI64), _ptr(ml, _PI32), _ptr(sig, _PF64), int(n_layer),
+                                             _ptr(pot, _PF64), int(bins_hint), C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None) and self.ctx._h:
+            self.ctx._lib.padne_sampler_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _outputs(n: int):
+        return (np.empty(n, dtype=np.int32), np.empty(n, dtype=np.float64), np.empty((n, 2), dtype=np.float64),
+                np.empty(n, dtype=np.float64))
+
+    def points(self, layer: int, xy):
+        q = _f64(xy).reshape(-1, 2)
+        face, v, j, p = self._outputs(q.shape[0])
+        _check(self.ctx._lib.padne_sampler_points(self.ctx._h, self._h, int(layer), q.shape[0], _ptr(q, _PF64),
+                                                  _ptr(face, _PI32), _ptr(v, _PF64), _ptr(j, _PF64), _ptr(p, _PF64)))
+        return face, v, j, p
+
+    def raster(self, layer: int, x0: float, y0: float, dx: float, dy: float, width: int, height: int):
+        """Row j, column i of the raster at index j * width + i of the flat results."""
+        n = max(int(width), 0) * max(int(height), 0)
+        face, v, j, p = self._outputs(n)
+        _check(self.ctx._lib.padne_sampler_raster(self.ctx._h, self._h, int(layer), float(x0), float(y0), float(dx), float(dy),
+                                                  int(width), int(height), _ptr(face, _PI32), _ptr(v, _PF64), _ptr(j, _PF64),
+                                                  _ptr(p, _PF64)))
+        return face, v, j, p
+
+    def stats(self, layer: int) -> dict:
+        """Of ``layer``: bins along x and y, list entries, faces; of the last query call: candidate faces tested, queries,
+        device seconds of its kernel; of the creation: host seconds of the upload and of the index build."""
+        counts = np.zeros(6, dtype=np.int64)
+        secs = np.zeros(3, dtype=np.float64)
+        _check(self.ctx._lib.padne_sampler_stats(self._h, int(layer), _ptr(counts, _PI64), _ptr(secs, _PF64)))
+        return {"bins_x": int(counts[0]), "bins_y": int(counts[1]), "entries": int(counts[2]), "faces": int(counts[3]),
+                "last_candidates": int(counts[4]), "last_queries": int(counts[5]), "upload_seconds": float(secs[0]),
+                "build_seconds": float(secs[1]), "last_kernel_seconds": float(secs[2])}
 
 
 class CsrMatrix:

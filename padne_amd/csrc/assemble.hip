@@ -29,6 +29,7 @@
 // This file is compiled with -ffp-contract=off: the cotangent and gradient expressions must
 // round exactly like the reference's Python floats (no fused multiply-add).
 #include "common.hpp"
+#include "face.hpp"
 
 #include <atomic>
 
@@ -348,16 +349,6 @@ enum { ERR_BAD_INDEX = 0, ERR_NONMANIFOLD = 1, ERR_LONG_ROWS = 2, ERR_HUB = 4, E
        ERR_GAVE_UP = 6,      // a bounded wait of asm_rows_in_place's in-kernel scan ran out: not an error of the input, the
                              // host builds the rows again in two passes (asm_rows_two_pass)
        ERR_WORDS = 8 };
-
-__device__ __forceinline__ int find_segment(const long long *__restrict__ offs, int n_seg, long long i) {
-    // largest m with offs[m] <= i   (offs has n_seg+1 entries, offs[0] = 0)
-    int lo = 0, hi = n_seg;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (offs[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
 
 // Vertex -> incident triangles, counted and listed in ONE pass: every vertex owns kIncCap list entries (a structured
 // grid has 6 triangles around a vertex, Delaunay meshes rarely more than 10); the counter keeps counting beyond that,
@@ -2143,30 +2134,7 @@ __global__ __launch_bounds__(256) void relabel_fill_wave(const int n_rows, const
 }
 
 // ---- power density ---------------------------------------------------------------------------
-// compute_triangle_gradient (solver.py:689-725) with the face vertex order of the reference:
-// Face.edge is the last interior half-edge created (v3->v1, mesh.py:320-325) so face.vertices
-// yields (v3, v1, v2).
-__device__ __forceinline__ double interp(double x1, double y1, double x2, double y2, double x3, double y3,
-                                         double f1, double f2, double f3, double x, double y) {
-    const double D = (y2 - y3) * (x1 - x3) + (x3 - x2) * (y1 - y3);
-    const double l1 = ((y2 - y3) * (x - x3) + (x3 - x2) * (y - y3)) / D;
-    const double l2 = ((y3 - y1) * (x - x3) + (x1 - x3) * (y - y3)) / D;
-    const double l3 = 1 - l1 - l2;
-    return l1 * f1 + l2 * f2 + l3 * f3;
-}
-
-// the face gradient and sigma |grad V|^2 of compute_power_density (solver.py:728-745), shared by every form of the kernel
-__device__ __forceinline__ void face_gradient_of(double x1, double y1, double x2, double y2, double x3, double y3, double f1,
-                                                 double f2, double f3, double &gx, double &gy) {
-    gx = interp(x1, y1, x2, y2, x3, y3, f1, f2, f3, x1 + 1, y1) - f1;
-    gy = interp(x1, y1, x2, y2, x3, y3, f1, f2, f3, x1, y1 + 1) - f1;
-}
-
-__device__ __forceinline__ double face_power_of(double gx, double gy, double s) {
-    const double jx = gx * s, jy = gy * s;      // J = E * conductivity
-    return jx * gx + jy * gy;                   // J.dot(E)
-}
-
+// (interp, face_gradient_of and face_power_of: face.hpp)
 __global__ void power_density_kernel(long long n_tri, const int *__restrict__ tri, const double *__restrict__ xy,
                                      int n_mesh, const long long *__restrict__ mesh_voff,
                                      const long long *__restrict__ mesh_toff, const double *__restrict__ sigma,
@@ -2489,12 +2457,6 @@ __global__ __launch_bounds__(256) void current_mesh_fold(int n_mesh, const long 
         mesh_max[m] = a;
         mesh_face[m] = f == kNoFace ? -1 : f;
     }
-}
-
-// orient(a, b, p) > 0: p lies left of a -> b.  Evaluated exactly so (the library builds with -ffp-contract=off), which
-// lets a numpy restatement reproduce every decision of the cut rule
-__device__ __forceinline__ double orient(double ax, double ay, double bx, double by, double px, double py) {
-    return (bx - ax) * (py - ay) - (by - ay) * (px - ax);
 }
 
 // edge (i, k) of a face, cot weight w, against the cut c = (start x, y, end x, y): w (V_left - V_right) when it crosses,

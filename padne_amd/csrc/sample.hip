@@ -1,0 +1,514 @@
+// Field sampler: the solved fields read out at points, along lines and on rasters ("Sampling").
+//
+//   padne_sampler_create : meshes + potentials -> device-resident sampler with a point-location index per layer
+//   padne_sampler_points : uploaded query points   -> owner face, V, J, p per point
+//   padne_sampler_raster : pixel centres formed by the kernel -> the same four as images
+//
+// The owner rule (what "the face that contains q" means, bit for bit):
+//   edge (i, k) of a face is evaluated from its lower global vertex to its higher one, side = orient(P, Q, q), and negated
+//   where the face runs the edge the other way, so the two faces of an edge see the same number with opposite signs.  A
+//   face contains q when its three sides are all >= 0 or all <= 0 and not all zero; the owner is the containing face with
+//   the lowest global index.  The index only proposes candidates; tests/sampling_ref.py states the rule by brute force.
+//
+// This file is compiled with -ffp-contract=off, like assemble.hip: every expression rounds as written.
+#include "common.hpp"
+#include "face.hpp"
+
+#include <float.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+
+namespace padne {
+
+constexpr int kListBound = 16;                    // list entries per face of a layer at the most; beyond it the grid is coarsened
+constexpr long long kMaxSamples = 1LL << 26;      // query points / pixels of one call
+constexpr int kMaxBinsPerSide = 32768;
+
+// the grid of one layer: bin (bx, by) is number bin0 + by * nbx + bx of the sampler's bins
+struct LayerGrid {
+    double x0 = 0, y0 = 0, sx = 0, sy = 0;        // lower corner of the layer's bounding box, bins per mm
+    int nbx = 1, nby = 1;
+    long long bin0 = 0;
+};
+
+struct RasterSpec {
+    double x0, y0, dx, dy;
+    long long width;
+};
+
+// the bin of a coordinate: monotone in x (a difference, a product with a positive constant, floor and a clamp are), so a
+// point between the ends of an interval falls into a bin between the bins of the ends -- also beyond the bounding box
+__device__ __forceinline__ int bin_of(double x, double x0, double s, int n) {
+    if (n == 1) return 0;
+    double t = floor((x - x0) * s);
+    t = fmin(fmax(t, 0.0), (double)(n - 1));
+    return (int)t;
+}
+
+// The bins face f may own a point of: those its bounding box meets, grown by a margin that covers the points the rounding
+// of orient() can add to it.  With S the longer side of the box, A the area and d the distance of q from the face, one of
+// the three exact sides is <= -d A / L_max and another >= d A / (2 L_max) (they sum to 2 A), while a computed side is off
+// by at most 8 eps S (S + d): beyond d = 64 eps S^3 / A the signs are the exact ones and the face does not contain q
+// (for 16 sqrt(2) eps S^2 / A <= 1/8).  A face too thin for that bound may own points anywhere: it is listed in every bin.
+__device__ __forceinline__ bool face_bin_range(const int *__restrict__ gtri, const double *__restrict__ xy, long long f,
+                                               const LayerGrid &g, int &bx0, int &bx1, int &by0, int &by1) {
+    const long long a = gtri[3 * f], b = gtri[3 * f + 1], c = gtri[3 * f + 2];
+    const double xa = xy[2 * a], ya = xy[2 * a + 1], xb = xy[2 * b], yb = xy[2 * b + 1], xc = xy[2 * c], yc = xy[2 * c + 1];
+    const double lx = fmin(fmin(xa, xb), xc), hx = fmax(fmax(xa, xb), xc);
+    const double ly = fmin(fmin(ya, yb), yc), hy = fmax(fmax(ya, yb), yc);
+    const double S = fmax(hx - lx, hy - ly);
+    if (!(S > 0.0)) return false;                 // three corners in one point: all sides are exact zeros, it contains nothing
+    const double area2 = fabs(orient(xa, ya, xb, yb, xc, yc)) - 16.0 * DBL_EPSILON * S * S;       // a lower bound of 2 A
+    if (!(area2 >= 256.0 * DBL_EPSILON * S * S)) {
+        bx0 = by0 = 0;
+        bx1 = g.nbx - 1;
+        by1 = g.nby - 1;
+        return true;
+    }
+    const double m = 128.0 * DBL_EPSILON * S * S * S / area2;
+    bx0 = bin_of(lx - m, g.x0, g.sx, g.nbx);
+    bx1 = bin_of(hx + m, g.x0, g.sx, g.nbx);
+    by0 = bin_of(ly - m, g.y0, g.sy, g.nby);
+    by1 = bin_of(hy + m, g.y0, g.sy, g.nby);
+    return true;
+}
+
+// global corners of every face, checked once: gtri[f] = mesh_voff[m] + tri[f]
+__global__ __launch_bounds__(256) void sampler_corners_kernel(long long n_tri, const int *__restrict__ tri, int n_mesh,
+                                                              const long long *__restrict__ mesh_voff,
+                                                              const long long *__restrict__ mesh_toff, int *__restrict__ gtri,
+                                                              int *__restrict__ err) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_tri) return;
+    const int m = find_segment(mesh_toff, n_mesh, t);
+    const long long v0 = mesh_voff[m], nv = mesh_voff[m + 1] - v0;
+    for (int k = 0; k < 3; ++k) {
+        const int l = tri[3 * t + k];
+        if (l < 0 || l >= nv) {
+            *(volatile int *)err = 1;
+            gtri[3 * t + k] = (int)v0;
+        } else {
+            gtri[3 * t + k] = (int)(v0 + l);
+        }
+    }
+}
+
+// FILL = false: count[bin] += 1 for every bin of every face; FILL = true: the face takes the next place of each of its bins
+// (count is then the cursor, a copy of the offsets).  Integer atomics; nothing depends on the order inside a bin.
+template <bool FILL>
+__global__ __launch_bounds__(256) void sampler_bin_kernel(long long n_tri, const int *__restrict__ gtri,
+                                                          const double *__restrict__ xy, int n_mesh,
+                                                          const long long *__restrict__ mesh_toff,
+                                                          const int *__restrict__ mesh_layer,
+                                                          const LayerGrid *__restrict__ grids, int *__restrict__ count,
+                                                          int *__restrict__ bin_face) {
+    const long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= n_tri) return;
+    const LayerGrid g = grids[mesh_layer[find_segment(mesh_toff, n_mesh, f)]];
+    int bx0, bx1, by0, by1;
+    if (!face_bin_range(gtri, xy, f, g, bx0, bx1, by0, by1)) return;
+    for (int by = by0; by <= by1; ++by)
+        for (int bx = bx0; bx <= bx1; ++bx) {
+            const int at = atomicAdd(&count[g.bin0 + (long long)by * g.nbx + bx], 1);
+            if (FILL) bin_face[at] = (int)f;
+        }
+}
+
+// side of q of the edge (i, k) as the face runs it (the owner rule above)
+__device__ __forceinline__ double edge_side(int gi, int gk, double xi, double yi, double xk, double yk, double qx, double qy) {
+    return gi < gk ? orient(xi, yi, xk, yk, qx, qy) : -orient(xk, yk, xi, yi, qx, qy);
+}
+
+// One thread per query: the bin of q, the candidates of that bin, the owner, then the owner's values.  RASTER: q is the
+// centre of pixel (row j, column i) of `r`, formed here; otherwise q = q_xy[idx].  Outside the copper: face -1, NaN.
+//   potential   s = (o_a + o_b) + o_c;  V = ((o_a / s) V_a + (o_b / s) V_b) + (o_c / s) V_c     (o_a: the side of the edge
+//               opposite corner a = tri[0], and so on: DESIGN.md)
+//   J, p        current_face_kernel's and power_density_kernel's arithmetic on the owner, corners as (tri[2], tri[0], tri[1])
+template <bool RASTER>
+__global__ __launch_bounds__(256) void sample_kernel(const LayerGrid g, const int *__restrict__ bin_off,
+                                                     const int *__restrict__ bin_face, const int *__restrict__ gtri,
+                                                     const double *__restrict__ xy, int n_mesh,
+                                                     const long long *__restrict__ mesh_toff, const double *__restrict__ sigma,
+                                                     const double *__restrict__ V, long long n, const double *__restrict__ q_xy,
+                                                     const RasterSpec r, int *__restrict__ face_out, double *__restrict__ v_out,
+                                                     double *__restrict__ j_out, double *__restrict__ p_out,
+                                                     unsigned long long *__restrict__ tested) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = idx < n;
+    unsigned long long n_tested = 0;
+    if (live) {
+        double qx, qy;
+        if (RASTER) {
+            const long long j = idx / r.width, i = idx - j * r.width;
+            qx = r.x0 + ((double)i + 0.5) * r.dx;
+            qy = r.y0 + ((double)j + 0.5) * r.dy;
+        } else {
+            qx = q_xy[2 * idx];
+            qy = q_xy[2 * idx + 1];
+        }
+        const long long bin = g.bin0 + (long long)bin_of(qy, g.y0, g.sy, g.nby) * g.nbx + bin_of(qx, g.x0, g.sx, g.nbx);
+        const int lo = bin_off[bin], hi = bin_off[bin + 1];
+        n_tested = (unsigned long long)(hi - lo);
+        int owner = 0x7fffffff;
+        double wa = 0.0, wb = 0.0, wc = 0.0;
+        for (int e = lo; e < hi; ++e) {
+            const int f = bin_face[e];
+            const int a = gtri[3 * (long long)f], b = gtri[3 * (long long)f + 1], c = gtri[3 * (long long)f + 2];
+            const double xa = xy[2 * (long long)a], ya = xy[2 * (long long)a + 1];
+            const double xb = xy[2 * (long long)b], yb = xy[2 * (long long)b + 1];
+            const double xc = xy[2 * (long long)c], yc = xy[2 * (long long)c + 1];
+            const double oa = edge_side(b, c, xb, yb, xc, yc, qx, qy);
+            const double ob = edge_side(c, a, xc, yc, xa, ya, qx, qy);
+            const double oc = edge_side(a, b, xa, ya, xb, yb, qx, qy);
+            const bool in = ((oa >= 0.0 && ob >= 0.0 && oc >= 0.0) || (oa <= 0.0 && ob <= 0.0 && oc <= 0.0)) &&
+                            !(oa == 0.0 && ob == 0.0 && oc == 0.0);
+            if (in && f < owner) {
+                owner = f;
+                wa = oa;
+                wb = ob;
+                wc = oc;
+            }
+        }
+        int face = -1;
+        double v = NAN, jx = NAN, jy = NAN, p = NAN;
+        if (owner != 0x7fffffff) {
+            face = owner;
+            const long long a = gtri[3 * (long long)owner], b = gtri[3 * (long long)owner + 1], c = gtri[3 * (long long)owner + 2];
+            const double va = V[a], vb = V[b], vc = V[c];
+            const double s = (wa + wb) + wc;
+            v = ((wa / s) * va + (wb / s) * vb) + (wc / s) * vc;
+            double gx, gy;
+            face_gradient_of(xy[2 * c], xy[2 * c + 1], xy[2 * a], xy[2 * a + 1], xy[2 * b], xy[2 * b + 1], vc, va, vb, gx, gy);
+            const double sg = sigma[find_segment(mesh_toff, n_mesh, owner)];
+            jx = -sg * gx;
+            jy = -sg * gy;
+            p = face_power_of(gx, gy, sg);
+        }
+        face_out[idx] = face;
+        v_out[idx] = v;
+        j_out[2 * idx] = jx;
+        j_out[2 * idx + 1] = jy;
+        p_out[idx] = p;
+    }
+    // candidates tested by this call (padne_sampler_stats): one integer atomic per wave
+    for (int off = 32; off > 0; off >>= 1) n_tested += __shfl_down(n_tested, off, 64);
+    if ((threadIdx.x & 63) == 0 && n_tested) atomicAdd(tested, n_tested);
+}
+
+}  // namespace padne
+
+using namespace padne;
+
+struct padne_sampler {
+    padne_ctx *owner = nullptr;
+    int64_t n_vert = 0, n_tri = 0;
+    int32_t n_mesh = 0, n_layer = 0;
+    // device (the owner's pool)
+    double *xy = nullptr, *sigma = nullptr, *V = nullptr;
+    int *gtri = nullptr, *mesh_layer = nullptr, *bin_off = nullptr, *bin_face = nullptr;
+    long long *toff = nullptr;
+    unsigned long long *tested = nullptr;
+    // host
+    std::vector<LayerGrid> grid;
+    std::vector<int64_t> layer_faces, layer_entries;
+    int64_t last_candidates = 0, last_queries = 0;
+    double upload_seconds = 0, build_seconds = 0, last_kernel_seconds = 0;
+};
+
+static void sampler_free(padne_sampler *s) {
+    if (s == nullptr) return;
+    void *blocks[] = {s->xy, s->sigma, s->V, s->gtri, s->mesh_layer, s->bin_off, s->bin_face, s->toff, s->tested};
+    for (void *p : blocks)
+        if (p) pool_free(s->owner, p);
+    delete s;
+}
+
+template <typename T> static int sampler_alloc(padne_ctx *ctx, T **out, size_t count) {
+    *out = (T *)pool_alloc(ctx, sizeof(T) * (count ? count : 1));
+    return *out ? PADNE_OK : PADNE_E_NOMEM;
+}
+
+static double seconds_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// the grid of a layer with n_faces faces in the box [lo, hi]: `bins` bins in all, as square as the box allows
+static void choose_grid(LayerGrid &g, const double lo[2], const double hi[2], int64_t bins) {
+    const double w = hi[0] - lo[0], h = hi[1] - lo[1];
+    g.nbx = g.nby = 1;
+    if (bins > 1 && w > 0 && h > 0) {
+        g.nbx = (int)std::min<double>(kMaxBinsPerSide, std::max(1.0, std::floor(std::sqrt((double)bins * w / h) + 0.5)));
+        g.nby = (int)std::min<double>(kMaxBinsPerSide, std::max(1.0, std::floor((double)bins / g.nbx + 0.5)));
+    }
+}
+
+static void set_scale(LayerGrid &g, const double lo[2], const double hi[2]) {
+    g.x0 = lo[0];
+    g.y0 = lo[1];
+    g.sx = g.nbx > 1 ? g.nbx / (hi[0] - lo[0]) : 0.0;
+    g.sy = g.nby > 1 ? g.nby / (hi[1] - lo[1]) : 0.0;
+}
+
+extern "C" int padne_sampler_create(padne_ctx *ctx, int64_t n_vert, const double *xy_host, int64_t n_tri,
+                                    const int32_t *tri_host, int32_t n_mesh, const int64_t *mesh_vertex_offset,
+                                    const int64_t *mesh_tri_offset, const int32_t *mesh_layer, const double *conductance,
+                                    int32_t n_layer, const double *potential_host, int64_t bins_hint, padne_sampler **out) {
+    PADNE_REQUIRE(ctx && out, "null argument");
+    *out = nullptr;
+    PADNE_REQUIRE(n_vert >= 0 && n_tri >= 0 && n_mesh >= 0 && n_layer >= 1 && bins_hint >= 0, "negative size or no layer");
+    PADNE_REQUIRE(n_vert < (1LL << 31) && n_tri < (1LL << 27), "a sampler takes fewer than 2^31 vertices and 2^27 faces");
+    PADNE_REQUIRE(mesh_vertex_offset && mesh_tri_offset, "null argument");
+    PADNE_REQUIRE(n_mesh == 0 || (mesh_layer && conductance), "null argument");
+    PADNE_REQUIRE((n_vert == 0 || (xy_host && potential_host)) && (n_tri == 0 || tri_host), "null argument");
+    PADNE_REQUIRE(mesh_vertex_offset[0] == 0 && mesh_tri_offset[0] == 0, "offset tables must start at 0");
+    PADNE_REQUIRE(mesh_vertex_offset[n_mesh] == n_vert && mesh_tri_offset[n_mesh] == n_tri, "offset tables");
+    for (int32_t m = 0; m < n_mesh; ++m) {
+        PADNE_REQUIRE(mesh_vertex_offset[m] <= mesh_vertex_offset[m + 1] && mesh_tri_offset[m] <= mesh_tri_offset[m + 1],
+                      "offset tables not monotone");
+        PADNE_REQUIRE(mesh_layer[m] >= 0 && mesh_layer[m] < n_layer, "mesh layer out of range");
+    }
+    for (int64_t i = 0; i < 2 * n_vert; ++i) PADNE_REQUIRE(std::isfinite(xy_host[i]), "vertex coordinates must be finite");
+    PADNE_HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const auto t0 = std::chrono::steady_clock::now();
+    padne_sampler *s = new padne_sampler;
+    s->owner = ctx;
+    s->n_vert = n_vert;
+    s->n_tri = n_tri;
+    s->n_mesh = n_mesh;
+    s->n_layer = n_layer;
+    s->grid.resize(n_layer);
+    s->layer_faces.assign(n_layer, 0);
+    s->layer_entries.assign(n_layer, 0);
+    struct Guard {      // an error path hands everything back
+        padne_sampler *s;
+        ~Guard() { sampler_free(s); }
+    } guard{s};
+    std::vector<long long> toff(mesh_tri_offset, mesh_tri_offset + n_mesh + 1), voff(mesh_vertex_offset, mesh_vertex_offset + n_mesh + 1);
+    Scratch sc(ctx);
+    int *d_tri = nullptr, *d_err = nullptr;
+    struct PoolBlock {      // the counters of the round under way
+        padne_ctx *ctx;
+        void *p;
+        ~PoolBlock() { if (p) pool_free(ctx, p); }
+    } count{ctx, nullptr};
+    long long *d_voff = nullptr;
+    LayerGrid *d_grid = nullptr;
+    PADNE_TRY(sampler_alloc(ctx, &s->xy, (size_t)n_vert * 2));
+    PADNE_TRY(sampler_alloc(ctx, &s->V, (size_t)n_vert));
+    PADNE_TRY(sampler_alloc(ctx, &s->sigma, (size_t)n_mesh));
+    PADNE_TRY(sampler_alloc(ctx, &s->gtri, (size_t)n_tri * 3));
+    PADNE_TRY(sampler_alloc(ctx, &s->mesh_layer, (size_t)n_mesh));
+    PADNE_TRY(sampler_alloc(ctx, &s->toff, (size_t)n_mesh + 1));
+    PADNE_TRY(sampler_alloc(ctx, &s->tested, 1));
+    PADNE_TRY(sc.alloc(&d_tri, (size_t)n_tri * 3));
+    PADNE_TRY(sc.alloc(&d_voff, (size_t)n_mesh + 1));
+    PADNE_TRY(sc.alloc(&d_err, 1));
+    PADNE_TRY(sc.alloc(&d_grid, (size_t)n_layer));
+    PADNE_HIP_CHECK(hipMemsetAsync(d_err, 0, sizeof(int), st));
+    PADNE_HIP_CHECK(hipMemcpyAsync(s->xy, xy_host, sizeof(double) * 2 * (size_t)n_vert, hipMemcpyHostToDevice, st));
+    PADNE_HIP_CHECK(hipMemcpyAsync(s->V, potential_host, sizeof(double) * (size_t)n_vert, hipMemcpyHostToDevice, st));
+    PADNE_HIP_CHECK(hipMemcpyAsync(d_tri, tri_host, sizeof(int) * 3 * (size_t)n_tri, hipMemcpyHostToDevice, st));
+    PADNE_HIP_CHECK(hipMemcpyAsync(s->sigma, conductance, sizeof(double) * (size_t)n_mesh, hipMemcpyHostToDevice, st));
+    PADNE_HIP_CHECK(hipMemcpyAsync(s->mesh_layer, mesh_layer, sizeof(int) * (size_t)n_mesh, hipMemcpyHostToDevice, st));
+    PADNE_HIP_CHECK(hipMemcpyAsync(s->toff, toff.data(), sizeof(long long) * (size_t)(n_mesh + 1), hipMemcpyHostToDevice, st));
+    PADNE_HIP_CHECK(hipMemcpyAsync(d_voff, voff.data(), sizeof(long long) * (size_t)(n_mesh + 1), hipMemcpyHostToDevice, st));
+    if (n_tri > 0) {
+        hipLaunchKernelGGL(sampler_corners_kernel, dim3(nblk(n_tri)), dim3(256), 0, st, (long long)n_tri, d_tri, (int)n_mesh, d_voff,
+                           s->toff, s->gtri, d_err);
+        PADNE_HIP_CHECK(hipGetLastError());
+    }
+    int h_err = 0;
+    PADNE_HIP_CHECK(hipMemcpyAsync(&h_err, d_err, sizeof(int), hipMemcpyDeviceToHost, st));
+    PADNE_HIP_CHECK(hipStreamSynchronize(st));
+    if (h_err) {
+        set_error("invalid argument: triangle index out of range");
+        return PADNE_E_INVALID;
+    }
+    s->upload_seconds = seconds_since(t0);
+
+    // ---- the index: bounding box and grid of every layer, then count, scan, fill; coarsened while a layer's lists are
+    // longer than kListBound entries per face
+    const auto t1 = std::chrono::steady_clock::now();
+    std::vector<double> lo(2 * (size_t)n_layer, INFINITY), hi(2 * (size_t)n_layer, -INFINITY);
+    for (int32_t m = 0; m < n_mesh; ++m) {
+        const int l = mesh_layer[m];
+        s->layer_faces[l] += mesh_tri_offset[m + 1] - mesh_tri_offset[m];
+        for (int64_t v = mesh_vertex_offset[m]; v < mesh_vertex_offset[m + 1]; ++v)
+            for (int k = 0; k < 2; ++k) {
+                lo[2 * l + k] = std::min(lo[2 * l + k], xy_host[2 * v + k]);
+                hi[2 * l + k] = std::max(hi[2 * l + k], xy_host[2 * v + k]);
+            }
+    }
+    for (int l = 0; l < n_layer; ++l) {
+        if (!(lo[2 * l] <= hi[2 * l])) lo[2 * l] = lo[2 * l + 1] = hi[2 * l] = hi[2 * l + 1] = 0.0;      // a layer without vertices
+        choose_grid(s->grid[l], &lo[2 * l], &hi[2 * l], bins_hint > 0 ? bins_hint : std::max<int64_t>(1, s->layer_faces[l] / 2));
+    }
+    for (;;) {
+        long long n_bins = 0;
+        for (int l = 0; l < n_layer; ++l) {
+            set_scale(s->grid[l], &lo[2 * l], &hi[2 * l]);
+            s->grid[l].bin0 = n_bins;
+            n_bins += (long long)s->grid[l].nbx * s->grid[l].nby;
+        }
+        PADNE_REQUIRE(n_bins < (1LL << 30), "too many bins");
+        if (s->bin_off) pool_free(ctx, s->bin_off);
+        s->bin_off = nullptr;
+        PADNE_TRY(sampler_alloc(ctx, &s->bin_off, (size_t)n_bins + 1));
+        if (count.p) pool_free(ctx, count.p);
+        count.p = pool_alloc(ctx, sizeof(int) * (size_t)(n_bins + 1));
+        if (count.p == nullptr) return PADNE_E_NOMEM;
+        int *d_count = (int *)count.p;
+        PADNE_HIP_CHECK(hipMemsetAsync(d_count, 0, sizeof(int) * (size_t)(n_bins + 1), st));
+        PADNE_HIP_CHECK(hipMemcpyAsync(d_grid, s->grid.data(), sizeof(LayerGrid) * (size_t)n_layer, hipMemcpyHostToDevice, st));
+        if (n_tri > 0) {
+            hipLaunchKernelGGL(sampler_bin_kernel<false>, dim3(nblk(n_tri)), dim3(256), 0, st, (long long)n_tri, s->gtri, s->xy,
+                               (int)n_mesh, s->toff, s->mesh_layer, d_grid, d_count, (int *)nullptr);
+            PADNE_HIP_CHECK(hipGetLastError());
+        }
+        bool negative = false;
+        int64_t total = 0;
+        PADNE_TRY(exclusive_scan_i32_flagged(ctx, d_count, s->bin_off, n_bins, &total, &negative));
+        if (negative || total >= (1LL << 31)) {       // a count wrapped: only far finer than kListBound allows; coarsen
+            total = -1;
+        }
+        std::vector<int> first(n_layer + 1, 0);
+        bool again = false;
+        if (total >= 0) {
+            for (int l = 0; l < n_layer; ++l)
+                PADNE_HIP_CHECK(hipMemcpyAsync(&first[l], s->bin_off + s->grid[l].bin0, sizeof(int), hipMemcpyDeviceToHost, st));
+            PADNE_HIP_CHECK(hipStreamSynchronize(st));
+            first[n_layer] = (int)total;
+        }
+        for (int l = 0; l < n_layer; ++l) {
+            LayerGrid &g = s->grid[l];
+            s->layer_entries[l] = total >= 0 ? (int64_t)first[l + 1] - first[l] : -1;
+            const bool too_long = total < 0 || s->layer_entries[l] > kListBound * s->layer_faces[l];
+            if (too_long && (g.nbx > 1 || g.nby > 1)) {
+                g.nbx = (g.nbx + 1) / 2;
+                g.nby = (g.nby + 1) / 2;
+                again = true;
+            }
+        }
+        if (again) continue;
+        PADNE_REQUIRE(total >= 0, "the face lists do not fit 32-bit offsets");
+        PADNE_TRY(sampler_alloc(ctx, &s->bin_face, (size_t)total));
+        PADNE_HIP_CHECK(hipMemcpyAsync(d_count, s->bin_off, sizeof(int) * (size_t)n_bins, hipMemcpyDeviceToDevice, st));
+        if (n_tri > 0) {
+            hipLaunchKernelGGL(sampler_bin_kernel<true>, dim3(nblk(n_tri)), dim3(256), 0, st, (long long)n_tri, s->gtri, s->xy,
+                               (int)n_mesh, s->toff, s->mesh_layer, d_grid, d_count, s->bin_face);
+            PADNE_HIP_CHECK(hipGetLastError());
+        }
+        PADNE_HIP_CHECK(hipStreamSynchronize(st));
+        break;
+    }
+    s->build_seconds = seconds_since(t1);
+    guard.s = nullptr;
+    *out = s;
+    return PADNE_OK;
+}
+
+extern "C" int padne_sampler_destroy(padne_sampler *s) {
+    if (s == nullptr) return PADNE_OK;
+    if (s->owner) {
+        (void)hipSetDevice(s->owner->device);
+        (void)hipStreamSynchronize(s->owner->stream);
+    }
+    sampler_free(s);
+    return PADNE_OK;
+}
+
+// the shared body of the two query entries: q_host != nullptr -> points, else the raster r
+static int sampler_query(padne_ctx *ctx, padne_sampler *s, int32_t layer, int64_t n, const double *q_host, const RasterSpec &r,
+                         int32_t *face_out, double *v_out, double *j_out, double *p_out) {
+    PADNE_HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    Scratch sc(ctx);
+    double *d_q = nullptr, *d_v = nullptr, *d_j = nullptr, *d_p = nullptr;
+    int *d_face = nullptr;
+    if (q_host) PADNE_TRY(sc.alloc(&d_q, (size_t)n * 2));
+    PADNE_TRY(sc.alloc(&d_face, (size_t)n));
+    PADNE_TRY(sc.alloc(&d_v, (size_t)n));
+    PADNE_TRY(sc.alloc(&d_j, (size_t)n * 2));
+    PADNE_TRY(sc.alloc(&d_p, (size_t)n));
+    PADNE_HIP_CHECK(hipMemsetAsync(s->tested, 0, sizeof(unsigned long long), st));
+    if (q_host) PADNE_HIP_CHECK(hipMemcpyAsync(d_q, q_host, sizeof(double) * 2 * (size_t)n, hipMemcpyHostToDevice, st));
+    PADNE_HIP_CHECK(hipEventRecord(ctx->ev0, st));
+    if (q_host)
+        hipLaunchKernelGGL(sample_kernel<false>, dim3(nblk(n)), dim3(256), 0, st, s->grid[layer], s->bin_off, s->bin_face, s->gtri,
+                           s->xy, (int)s->n_mesh, s->toff, s->sigma, s->V, (long long)n, d_q, r, d_face, d_v, d_j, d_p, s->tested);
+    else
+        hipLaunchKernelGGL(sample_kernel<true>, dim3(nblk(n)), dim3(256), 0, st, s->grid[layer], s->bin_off, s->bin_face, s->gtri,
+                           s->xy, (int)s->n_mesh, s->toff, s->sigma, s->V, (long long)n, (const double *)nullptr, r, d_face, d_v,
+                           d_j, d_p, s->tested);
+    PADNE_HIP_CHECK(hipGetLastError());
+    PADNE_HIP_CHECK(hipEventRecord(ctx->ev1, st));
+    unsigned long long tested = 0;
+    PADNE_HIP_CHECK(hipMemcpyAsync(&tested, s->tested, sizeof(tested), hipMemcpyDeviceToHost, st));
+    PADNE_HIP_CHECK(hipMemcpyAsync(face_out, d_face, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st));
+    PADNE_HIP_CHECK(hipMemcpyAsync(v_out, d_v, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
+    PADNE_HIP_CHECK(hipMemcpyAsync(j_out, d_j, sizeof(double) * 2 * (size_t)n, hipMemcpyDeviceToHost, st));
+    PADNE_HIP_CHECK(hipMemcpyAsync(p_out, d_p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
+    PADNE_HIP_CHECK(hipStreamSynchronize(st));
+    float ms = 0.0f;
+    PADNE_HIP_CHECK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    s->last_kernel_seconds = 1e-3 * ms;
+    s->last_candidates = (int64_t)tested;
+    s->last_queries = n;
+    return PADNE_OK;
+}
+
+static int sampler_query_checks(padne_ctx *ctx, padne_sampler *s, int32_t layer, int64_t n, const void *a, const void *b,
+                                const void *c, const void *d) {
+    PADNE_REQUIRE(ctx && s, "null argument");
+    PADNE_REQUIRE(s->owner == ctx, "the sampler belongs to another context");
+    PADNE_REQUIRE(layer >= 0 && layer < s->n_layer, "layer out of range");
+    PADNE_REQUIRE(n >= 0 && n <= kMaxSamples, "at most 2^26 samples in one call");
+    PADNE_REQUIRE(n == 0 || (a && b && c && d), "null argument");
+    return PADNE_OK;
+}
+
+extern "C" int padne_sampler_points(padne_ctx *ctx, padne_sampler *s, int32_t layer, int64_t n, const double *xy_host,
+                                    int32_t *face_out, double *v_out, double *j_out, double *p_out) {
+    PADNE_TRY(sampler_query_checks(ctx, s, layer, n, face_out, v_out, j_out, p_out));
+    PADNE_REQUIRE(n == 0 || xy_host, "null argument");
+    for (int64_t i = 0; i < 2 * n; ++i) PADNE_REQUIRE(std::isfinite(xy_host[i]), "query points must be finite");
+    if (n == 0) {
+        s->last_candidates = s->last_queries = 0;
+        s->last_kernel_seconds = 0;
+        return PADNE_OK;
+    }
+    return sampler_query(ctx, s, layer, n, xy_host, RasterSpec{0, 0, 0, 0, 1}, face_out, v_out, j_out, p_out);
+}
+
+extern "C" int padne_sampler_raster(padne_ctx *ctx, padne_sampler *s, int32_t layer, double x0, double y0, double dx, double dy,
+                                    int64_t width, int64_t height, int32_t *face_out, double *v_out, double *j_out,
+                                    double *p_out) {
+    PADNE_REQUIRE(width >= 1 && height >= 1, "a raster has at least one pixel");
+    PADNE_REQUIRE(width <= kMaxSamples && height <= kMaxSamples, "at most 2^26 samples in one call");
+    PADNE_TRY(sampler_query_checks(ctx, s, layer, width * height, face_out, v_out, j_out, p_out));
+    PADNE_REQUIRE(std::isfinite(x0) && std::isfinite(y0), "the raster's origin must be finite");
+    PADNE_REQUIRE(std::isfinite(dx) && std::isfinite(dy) && dx > 0 && dy > 0, "the pixel size must be finite and positive");
+    // the last pixel centre is the largest coordinate the kernel forms
+    PADNE_REQUIRE(std::isfinite(x0 + ((double)(width - 1) + 0.5) * dx) && std::isfinite(y0 + ((double)(height - 1) + 0.5) * dy),
+                  "the raster's pixel centres must be finite");
+    return sampler_query(ctx, s, layer, width * height, nullptr, RasterSpec{x0, y0, dx, dy, (long long)width}, face_out, v_out,
+                         j_out, p_out);
+}
+
+extern "C" int padne_sampler_stats(const padne_sampler *s, int32_t layer, int64_t *counts_out, double *seconds_out) {
+    PADNE_REQUIRE(s && counts_out && seconds_out, "null argument");
+    PADNE_REQUIRE(layer >= 0 && layer < s->n_layer, "layer out of range");
+    counts_out[0] = s->grid[layer].nbx;
+    counts_out[1] = s->grid[layer].nby;
+    counts_out[2] = s->layer_entries[layer];
+    counts_out[3] = s->layer_faces[layer];
+    counts_out[4] = s->last_candidates;
+    counts_out[5] = s->last_queries;
+    seconds_out[0] = s->upload_seconds;
+    seconds_out[1] = s->build_seconds;
+    seconds_out[2] = s->last_kernel_seconds;
+    return PADNE_OK;
+}

@@ -22,6 +22,8 @@ compute_power_density :728-745         ``power_density_kernel``
                                        regulators, ``sensitivity_block_kernel`` over the faces
 (where the current goes)               ``solve_currents``: the load-case block with one column, ``current_face_kernel``
                                        and ``cut_current_kernel`` over the faces, element flows from V's rows
+read-out under the cursor ui.py:192    ``FieldSampler``: owner face by ``sample_kernel`` over a grid of bins per layer,
+                                       V interpolated in the face, J and p of the face
 =====================================  ====================================================
 
 There is no CPU fallback: every entry point that computes raises
@@ -1716,3 +1718,186 @@ def solve_currents(prob, cuts=(), mesher_config: Optional[mesh.Mesher.Config] = 
     meshes, mesh_index_to_layer_index = _mesh_problem(prob, mesher_config, mesher)
     return solve_meshed_currents(prob, meshes, mesh_index_to_layer_index,
                                  [Cut(prob.layers[i], a, b) for i, a, b in cuts])
+
+
+# --------------------------------------------------------------------------------------------
+# sampling: the solved fields at points, along lines and on rasters
+# --------------------------------------------------------------------------------------------
+
+MAX_SAMPLE_POINTS = 2 ** 26
+MAX_RASTER_PIXELS = 2 ** 26
+
+
+@dataclass
+class FieldSamples:
+    """What a :class:`FieldSampler` returns: per sample the owner face as (``mesh`` within ``LayerSolution.meshes``, ``face``
+    within that mesh), -1 / -1 outside the copper, the ``potential`` [V] interpolated in that face, and the face's
+    ``current_density`` (.., 2) [A/mm] and ``power_density``; NaN outside.  ``points`` are the sampled (x, y); a line also
+    carries the ``arc_length`` of each sample from its start.  A raster's arrays are shaped (height, width[, 2])."""
+    points: np.ndarray
+    face: np.ndarray
+    mesh: np.ndarray
+    potential: np.ndarray
+    current_density: np.ndarray
+    power_density: np.ndarray
+    arc_length: Optional[np.ndarray] = None
+
+
+def _layer_index(prob, layer) -> int:
+    layer_i = next((i for i, own in enumerate(prob.layers) if own is layer), None)
+    if layer_i is None:
+        raise ValueError("the layer is not one of the Problem's layers")
+    return layer_i
+
+
+def check_sample_points(prob, layer, xy) -> tuple:
+    """(layer index, the points as a float64 (n, 2) array), or ValueError: ``layer`` is one of ``prob.layers`` (by
+    identity), ``xy`` is (n, 2) with n <= MAX_SAMPLE_POINTS and finite."""
+    layer_i = _layer_index(prob, layer)
+    try:
+        pts = np.asarray(xy)
+    except (TypeError, ValueError):
+        raise ValueError("sample points must be an (n, 2) array of numbers") from None
+    if pts.ndim != 2 or pts.shape[1] != 2:
+        raise ValueError(f"sample points must have shape (n, 2), not {pts.shape}")
+    if len(pts) > MAX_SAMPLE_POINTS:
+        raise ValueError(f"{len(pts)} sample points: at most {MAX_SAMPLE_POINTS} in one call")
+    try:
+        pts = np.array(pts, dtype=DTYPE)
+    except (TypeError, ValueError):
+        raise ValueError("sample points must be an (n, 2) array of numbers") from None
+    if not np.isfinite(pts).all():
+        raise ValueError("sample points are not finite")
+    return layer_i, np.ascontiguousarray(pts)
+
+
+def check_raster(prob, layer, origin, pixel, width, height) -> tuple:
+    """(layer index, x0, y0, dx, dy, width, height), or ValueError: ``origin`` is a finite (x, y), the lower corner of pixel
+    (0, 0); ``pixel`` a finite positive size, one number or (dx, dy); ``width`` and ``height`` integers >= 1 with at most
+    MAX_RASTER_PIXELS pixels, all of whose centres are finite."""
+    layer_i = _layer_index(prob, layer)
+    x0, y0 = _cut_point(origin, 0, "the raster's origin")
+    try:
+        dx, dy = (float(pixel), float(pixel)) if np.ndim(pixel) == 0 else (float(pixel[0]), float(pixel[1]))
+        if np.ndim(pixel) != 0 and len(pixel) != 2:
+            raise ValueError
+    except (TypeError, ValueError, IndexError):
+        raise ValueError("the pixel size must be one number or (dx, dy)") from None
+    if not (math.isfinite(dx) and math.isfinite(dy) and dx > 0 and dy > 0):
+        raise ValueError("the pixel size must be finite and positive")
+    try:
+        w, h = int(width), int(height)
+        if w != width or h != height:
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError("width and height must be integers") from None
+    if w < 1 or h < 1:
+        raise ValueError("a raster has at least one pixel in each direction")
+    if w * h > MAX_RASTER_PIXELS:
+        raise ValueError(f"{w} x {h} pixels: at most {MAX_RASTER_PIXELS} in one call")
+    if not (math.isfinite(x0 + ((w - 1) + 0.5) * dx) and math.isfinite(y0 + ((h - 1) + 0.5) * dy)):
+        raise ValueError("the raster's pixel centres are not finite")
+    return layer_i, x0, y0, dx, dy, w, h
+
+
+class FieldSampler:
+    """Reads a :class:`Solution` out at arbitrary points: built once, it keeps the meshes, the potentials and a
+    point-location index on the device and answers ``points``, ``line`` and ``raster`` until ``close`` (a context manager).
+
+    For a point q on a layer, with the layer's faces numbered in the order of ``LayerSolution.meshes``:
+
+    - the *owner* is the lowest face that contains q.  side(i, k) = orient(P, Q, q) for a face's edge taken from its lower
+      vertex index P to its higher Q, negated where the face runs it from Q to P, so the two faces of an edge see the same
+      number with opposite signs; a face contains q when its three sides are all >= 0 or all <= 0 and not all zero.  A
+      point on a shared edge or vertex has exactly one owner; a point outside the outline or in a hole has none (-1, NaN);
+    - ``potential`` is the linear interpolant of the owner's corner potentials with the weights side / (sum of the sides);
+    - ``current_density`` and ``power_density`` are the owner's face values, the same bits as ``CurrentReport.vectors`` and
+      ``LayerSolution.power_densities``.
+
+    ``disconnected_meshes`` carry no field and take no part.  Works on any Solution whose meshes have ``points`` and
+    ``triangles`` arrays (:class:`padne_amd.mesh.Mesh`).  ``bins_hint``: bins of each layer's grid, 0 = chosen."""
+
+    def __init__(self, solution: Solution, *, bins_hint: int = 0):
+        self.solution = solution
+        self.problem = solution.problem
+        pts, tris, pots, sig, layer_of = [], [], [], [], []
+        self._first_mesh, self._toff = [], []          # per layer: its first mesh in the flat order, its faces' offsets
+        for layer_i, (layer, ls) in enumerate(zip(self.problem.layers, solution.layer_solutions)):
+            self._first_mesh.append(len(layer_of))
+            for msh, zf in zip(ls.meshes, ls.potentials):
+                pts.append(np.asarray(msh.points, dtype=DTYPE).reshape(-1, 2))
+                tris.append(np.asarray(msh.triangles, dtype=np.int32).reshape(-1, 3))
+                pots.append(np.asarray(zf.values, dtype=DTYPE).reshape(-1))
+                sig.append(float(layer.conductance))
+                layer_of.append(layer_i)
+        mvo = np.concatenate([[0], np.cumsum([len(p) for p in pts])]).astype(np.int64)
+        self._mto = np.concatenate([[0], np.cumsum([len(t) for t in tris])]).astype(np.int64)
+        cat = lambda arrays, shape, dtype: (np.concatenate(arrays) if arrays else np.zeros(shape, dtype=dtype))  # noqa: E731
+        self._dev = _hip.Sampler(get_context(), cat(pts, (0, 2), DTYPE), cat(tris, (0, 3), np.int32), mvo, self._mto, layer_of,
+                                 sig, len(self.problem.layers), cat(pots, (0,), DTYPE), bins_hint)
+
+    def close(self) -> None:
+        if self._dev is not None:
+            self._dev.close()
+        self._dev = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _device(self) -> _hip.Sampler:
+        if self._dev is None:
+            raise ValueError("the FieldSampler is closed")
+        return self._dev
+
+    def _samples(self, layer_i: int, points, raw, shape=None, arc=None) -> FieldSamples:
+        gface, v, j, p = raw
+        # global face -> (mesh within the layer, face within the mesh): the meshes of a layer are adjacent in the flat order
+        g = gface.astype(np.int64)
+        m = np.searchsorted(self._mto, g, side="right") - 1
+        inside = g >= 0
+        mesh_i = np.where(inside, m - self._first_mesh[layer_i], -1)
+        face = np.where(inside, g - self._mto[np.clip(m, 0, len(self._mto) - 1)], -1)
+        if shape is not None:
+            mesh_i, face, v, p = (a.reshape(shape) for a in (mesh_i, face, v, p))
+            j = j.reshape(shape + (2,))
+        return FieldSamples(points=points, face=face, mesh=mesh_i, potential=v, current_density=j, power_density=p,
+                            arc_length=arc)
+
+    def points(self, layer, xy) -> FieldSamples:
+        """The fields at the points ``xy`` (n, 2) of ``layer``."""
+        layer_i, pts = check_sample_points(self.problem, layer, xy)
+        return self._samples(layer_i, pts, self._device().points(layer_i, pts))
+
+    def line(self, layer, start, end, n: int) -> FieldSamples:
+        """``n`` >= 2 points from ``start`` to ``end`` inclusive (``np.linspace`` per coordinate), with ``arc_length``
+        ``np.linspace(0, |end - start|, n)``: the profile along a trace."""
+        _layer_index(self.problem, layer)
+        a, b = _cut_point(start, 0, "the line's start"), _cut_point(end, 0, "the line's end")
+        try:
+            count = int(n)
+        except (TypeError, ValueError):
+            raise ValueError("a line has an integer number of points") from None
+        if count != n or count < 2:
+            raise ValueError("a line has at least 2 points")
+        if count > MAX_SAMPLE_POINTS:
+            raise ValueError(f"{count} sample points: at most {MAX_SAMPLE_POINTS} in one call")
+        xy = np.stack([np.linspace(a[0], b[0], count), np.linspace(a[1], b[1], count)], axis=1)
+        layer_i, pts = check_sample_points(self.problem, layer, xy)
+        arc = np.linspace(0.0, math.hypot(b[0] - a[0], b[1] - a[1]), count)
+        return self._samples(layer_i, pts, self._device().points(layer_i, pts), arc=arc)
+
+    def raster(self, layer, origin, pixel, width: int, height: int) -> FieldSamples:
+        """The fields at the centres of ``width`` x ``height`` pixels of size ``pixel`` (one number or (dx, dy)), pixel
+        (row j, column i) centred at (origin.x + (i + 0.5) dx, origin.y + (j + 0.5) dy).  Arrays are (height, width)."""
+        layer_i, x0, y0, dx, dy, w, h = check_raster(self.problem, layer, origin, pixel, width, height)
+        raw = self._device().raster(layer_i, x0, y0, dx, dy, w, h)
+        xs, ys = x0 + (np.arange(w) + 0.5) * dx, y0 + (np.arange(h) + 0.5) * dy
+        pts = np.stack(np.broadcast_arrays(xs[None, :], ys[:, None]), axis=2)
+        return self._samples(layer_i, pts, raw, shape=(h, w))
+
+    def stats(self, layer) -> dict:
+        """Index and timing figures of ``layer`` (``_hip.Sampler.stats``)."""
+        return self._device().stats(_layer_index(self.problem, layer))
