@@ -702,10 +702,11 @@ class KktPlan:
         # touched while the device solves, so that a block's result is ready when the device is
         coo = isinstance(r, tuple)
         v_shape = (self.N, n_cols) if coo else r.shape
-        self._v_next, self._v_toucher = _prefaulted(v_shape)
-        self._pd_next, self._pd_toucher = (_prefaulted((power_rows or n_cols, power_tri)) if coo and power_tri > 0
-                                           else (None, None))
-        self._cur_next, self._cur_toucher = _prefaulted((3 * current_tri,)) if coo and current_tri > 0 else (None, None)
+        self._prefault = {"v": _prefaulted(v_shape)}
+        if coo and power_tri > 0:
+            self._prefault["pd"] = _prefaulted((power_rows or n_cols, power_tri))
+        if coo and current_tri > 0:
+            self._prefault["cur"] = _prefaulted((3 * current_tri,))
         lib, common = self.ctx._lib, (kidx.shape[0], _ptr(kidx, _PI64), _ptr(kval, _PF64), len(extras),
                                       _ptr(ptr, _PI64), _ptr(rows, _PI64), _ptr(vals, _PF64), pidx.shape[0], _ptr(pidx, _PI64),
                                       _ptr(out, _PF64), C.byref(opts), float(abs_residual_target), C.byref(info))
@@ -724,27 +725,22 @@ class KktPlan:
                           info.precond_fallbacks)
         return out[:, :len(pidx)], res
 
-    def _result_array(self, shape):
-        toucher, v = getattr(self, "_v_toucher", None), getattr(self, "_v_next", None)
-        self._v_next, self._v_toucher = None, None
+    def _result_array(self, shape, slot: str = "v"):
+        """The array stage 1 made ready for ``slot`` ("v": stage 2's result, "pd": power densities, "cur": J and |J|) once
+        its pages are touched, if it has ``shape``; else a fresh one.  The slot is left empty."""
+        arr, toucher = getattr(self, "_prefault", {}).pop(slot, (None, None))
         for t in toucher or ():
             t.join()
-        if v is None or v.shape != shape:
-            v = np.empty(shape, dtype=np.float64)
-        return v
+        if arr is None or arr.shape != shape:
+            arr = np.empty(shape, dtype=np.float64)
+        return arr
 
     def power_density_block(self, n_cols: int, n_tri: int) -> np.ndarray:
         """Per-face sigma |grad V|^2 of every column of the block the last ``finish_block`` left on the device, over the mesh
         the system was assembled from (``n_tri`` triangles, as ``CsrMatrix.power_density`` takes it): (n_cols, n_tri), row j
         bit-identical to ``CsrMatrix.power_density`` of V[:, j].  Raises ValueError when no block has been finished since the
         last solve, on another column count, and on a matrix without a mesh."""
-        toucher, out = getattr(self, "_pd_toucher", None), getattr(self, "_pd_next", None)
-        self._pd_next, self._pd_toucher = None, None
-        n_tri = int(n_tri)
-        for t in toucher or ():
-            t.join()
-        if out is None or out.shape != (int(n_cols), n_tri):
-            out = np.empty((int(n_cols), n_tri), dtype=np.float64)
+        out = self._result_array((int(n_cols), int(n_tri)), "pd")
         _check(self.ctx._lib.padne_kkt_power_density_block(self.ctx._h, self._h, int(n_cols), _ptr(out, _PF64)))
         return out
 
@@ -757,15 +753,9 @@ class KktPlan:
         W = _f64(weights)
         if W.ndim != 2 or W.shape[0] < 1:
             raise ValueError("weights must have shape (n_obj, n_cols) with n_obj >= 1")
-        toucher, power = getattr(self, "_pd_toucher", None), getattr(self, "_pd_next", None)
-        self._pd_next, self._pd_toucher = None, None
-        for t in toucher or ():
-            t.join()
-        n_obj, n_tri = W.shape[0], int(n_tri)
-        density = power[1:] if power is not None and power.shape == (n_obj + 1, n_tri) else None
-        if density is None:
-            power = np.empty((n_obj + 1, n_tri), dtype=np.float64)
-            density = power[1:]
+        n_obj = W.shape[0]
+        power = self._result_array((n_obj + 1, int(n_tri)), "pd")
+        density = power[1:]
         totals = np.empty((n_obj, int(n_mesh)), dtype=np.float64)
         _check(self.ctx._lib.padne_kkt_sensitivity_block(self.ctx._h, self._h, W.shape[1], n_obj, _ptr(W, _PF64),
                                                          _ptr(power[0], _PF64), _ptr(density, _PF64), _ptr(totals, _PF64)))
@@ -784,12 +774,7 @@ class KktPlan:
         if xy.shape[0] != cl.shape[0]:
             raise ValueError("cut_layer and cut_xy must list the same cuts")
         n_tri, n_mesh, n_cut = int(n_tri), ml.shape[0], cl.shape[0]
-        toucher, buf = getattr(self, "_cur_toucher", None), getattr(self, "_cur_next", None)
-        self._cur_next, self._cur_toucher = None, None
-        for t in toucher or ():
-            t.join()
-        if buf is None or buf.shape != (3 * n_tri,):
-            buf = np.empty(3 * n_tri, dtype=np.float64)
+        buf = self._result_array((3 * n_tri,), "cur")
         J, mag = buf[:2 * n_tri].reshape(n_tri, 2), buf[2 * n_tri:]
         mesh_max = np.empty(n_mesh, dtype=np.float64)
         mesh_face = np.empty(n_mesh, dtype=np.int64)

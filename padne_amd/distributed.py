@@ -592,7 +592,7 @@ def solve_partitioned(plan: RankPlan, ctx, dist=None, team=None, rtol: float = 1
         # ---- regulators and multiplier currents, as solver.solve_system does on one GPU ----------------------------------
         N = red.layout.size
         n_pot = red.layout.n_potential
-        members = sorted({int(x) for mem, cons, _ in red.groups if cons for x in mem})
+        members = red.probe_members
 
         def residual_at_members(v_potentials):
             rho = np.zeros(N)

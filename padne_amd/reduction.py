@@ -231,6 +231,17 @@ class Reduction:
         return int(x - k)
 
     @property
+    def probe_members(self) -> list:
+        """The potentials of the groups that carry constraints, sorted: the rows whose residuals the multiplier recovery
+        reads (``recover_currents``)."""
+        return sorted({int(x) for mem, cons, _ in self.groups if cons for x in mem})
+
+    @property
+    def regulator_columns(self) -> list:
+        """Per regulator the column {row: gain} its current multiplies: the extra right-hand sides of a solve."""
+        return [dict(cst.gamma) for cst in self.regulators]
+
+    @property
     def has_known_part(self) -> bool:
         """Is c non-zero anywhere?  c lives on the members of the constraint groups only: a handful of entries."""
         return any(val != 0.0 for val in self.known.values())

@@ -31,6 +31,7 @@ There is no CPU fallback: every entry point that computes raises
 """
 from __future__ import annotations
 
+import contextlib
 import dataclasses
 import logging
 import math
@@ -73,6 +74,11 @@ def set_context(ctx: Optional[_hip.Context]) -> None:
 
 
 NEAREST_ON_DEVICE_FROM = 50000     # vertices of a layer from which connections are snapped on the device
+
+
+def _offsets(sizes) -> np.ndarray:
+    """[0, s0, s0 + s1, ...]: where each of consecutive blocks of the given sizes starts, and the total."""
+    return np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
 
 
 class SolverWarning(Warning):
@@ -120,7 +126,7 @@ class VertexIndexer:
     """
 
     def __init__(self, sizes: Sequence[int] = ()):
-        self.offsets = np.concatenate([[0], np.cumsum(np.asarray(list(sizes), dtype=np.int64))]).astype(np.int64)
+        self.offsets = _offsets(np.asarray(list(sizes), dtype=np.int64))
         self._g2v = None
         self._v2g = None
 
@@ -430,8 +436,8 @@ class SystemMatrix:
 def _flatten_meshes(meshes, conductances):
     xy = np.concatenate([m.points for m in meshes]) if meshes else np.zeros((0, 2))
     tri = np.concatenate([m.triangles for m in meshes]) if meshes else np.zeros((0, 3), np.int32)
-    mvo = np.concatenate([[0], np.cumsum([len(m.points) for m in meshes])]).astype(np.int64)
-    mto = np.concatenate([[0], np.cumsum([len(m.triangles) for m in meshes])]).astype(np.int64)
+    mvo = _offsets([len(m.points) for m in meshes])
+    mto = _offsets([len(m.triangles) for m in meshes])
     return xy, tri, mvo, mto, np.asarray(conductances, dtype=np.float64)
 
 
@@ -466,13 +472,20 @@ def assemble_system(prob, meshes, mesh_index_to_layer_index, vindex: VertexIndex
     """``solver.py:783-812``: allocate, mesh Laplacians, network stamps, ground -> ``(L, r)``.
 
     ``L`` is a :class:`SystemMatrix` on the device (convertible with ``.tocsr()`` / ``.tolil()``)."""
+    conductances, stamps, r, n_potential = _stamp_problem(prob, meshes, mesh_index_to_layer_index, vindex, filtered_networks,
+                                                          node_indexer)
+    return assemble_from_arrays(meshes, conductances, stamps, n_potential=n_potential), r
+
+
+def _stamp_problem(prob, meshes, mesh_index_to_layer_index, vindex: VertexIndexer, filtered_networks, node_indexer: NodeIndexer):
+    """What the Problem puts into the system besides the mesh terms: (conductance of each mesh, the network and ground stamps
+    as a StampList, r, number of potential unknowns)."""
     conductances = [prob.layers[mesh_index_to_layer_index[i]].conductance for i in range(len(meshes))]
     stamps, r = allocate_system(vindex, node_indexer)
     for network in filtered_networks:
         stamp_network_into_system(network, node_indexer, stamps, r)
     setup_ground_node(find_best_ground_node_index(prob, node_indexer), stamps, r)
-    L = assemble_from_arrays(meshes, conductances, stamps, n_potential=len(vindex) + node_indexer.internal_node_count)
-    return L, r
+    return conductances, stamps, r, len(vindex) + node_indexer.internal_node_count
 
 
 def assemble_from_arrays(meshes, conductances, stamps: StampList, n_potential: int) -> SystemMatrix:
@@ -523,6 +536,19 @@ def _stalled_columns(residual_norms: np.ndarray, R: Optional[np.ndarray] = None,
         cols = [int(np.argmax(rel))]
     return (f" (block of {len(residual_norms)} right-hand sides, reported as a whole; largest residuals against their own "
             f"right-hand side in column(s) {', '.join(str(int(j)) for j in cols[:16])})")
+
+
+def _warn_if_block_stalled(res, residual_norms: np.ndarray, cols, vals, n_cols: int) -> None:
+    """_warn_if_stalled for a block given by its triples: their ``cols`` and ``vals`` give the ||r_j|| that name the columns."""
+    if _stalled(res, RTOL):
+        col_norms = np.sqrt(np.bincount(cols, weights=vals * vals, minlength=n_cols))
+        _warn_if_stalled(res, RTOL, _stalled_columns(residual_norms, col_norms=col_norms))
+
+
+def _solver_info(res, ground, residual_norm, residual_norms=None) -> SolverInfo:
+    """The SolverInfo of a device solve ``res`` (a SolveResult) with the figures the caller took from the solution."""
+    return SolverInfo(ground_node_current=ground, residual_norm=float(residual_norm), iterations=int(res.iterations),
+                      rel_residual=float(res.rel_residual), solve_seconds=float(res.seconds), residual_norms=residual_norms)
 
 
 def _warn_if_stalled(res, rtol: float, where: str = "") -> None:
@@ -597,8 +623,7 @@ def solve_system(L, r: np.ndarray, *, rtol: float = RTOL, reorder=None, n_potent
         red: Reduction = build_reduction(layout, pins)
     plan = _plan_for(L, dev, layout, red, _wants_reorder(L, reorder), owned)
     try:
-        members = sorted({int(x) for mem, cons, _ in red.groups if cons for x in mem})
-        extras = [dict(cst.gamma) for cst in red.regulators]
+        members, extras = red.probe_members, red.regulator_columns
         if not block:
             probes, res = plan.solve(r, red.known, extras, members, rtol=rtol, max_iter=MAX_ITER,
                                      abs_residual_target=ABS_RESIDUAL_TARGET)
@@ -615,15 +640,10 @@ def solve_system(L, r: np.ndarray, *, rtol: float = RTOL, reorder=None, n_potent
             plan.close()
             dev.close()
     if not block:
-        info = SolverInfo(ground_node_current=float(v[-1]), residual_norm=float(residual_norm),
-                          iterations=int(res.iterations), rel_residual=float(res.rel_residual), solve_seconds=float(res.seconds))
-        return v, info
+        return v, _solver_info(res, float(v[-1]), residual_norm)
     if _stalled(res, rtol):
         _warn_if_stalled(res, rtol, _stalled_columns(residual_norms, r))
-    info = SolverInfo(ground_node_current=v[-1].copy(), residual_norm=float(np.sqrt(np.sum(residual_norms ** 2))),
-                      iterations=int(res.iterations), rel_residual=float(res.rel_residual), solve_seconds=float(res.seconds),
-                      residual_norms=residual_norms)
-    return v, info
+    return v, _solver_info(res, v[-1].copy(), np.sqrt(np.sum(residual_norms ** 2)), residual_norms)
 
 
 def _floating_pins(L, layout: KKTLayout, Lc) -> list:
@@ -738,6 +758,14 @@ def compute_power_density(voltage: mesh.ZeroForm, conductivity: float) -> mesh.T
     return out
 
 
+def _layer_meshes(meshes, mesh_index_to_layer_index, tri_offsets, layer_i: int):
+    """The meshes of layer ``layer_i`` in mesh order, each as (mesh index, mesh, lo, hi): its faces are lo:hi of the per-face
+    arrays over all meshes (``tri_offsets`` = _offsets of the meshes' face counts)."""
+    for mesh_i, msh in enumerate(meshes):
+        if mesh_index_to_layer_index[mesh_i] == layer_i:
+            yield mesh_i, msh, int(tri_offsets[mesh_i]), int(tri_offsets[mesh_i + 1])
+
+
 def produce_layer_solutions(layers, vindex: VertexIndexer, meshes, mesh_index_to_layer_index, v: np.ndarray,
                             disconnected_meshes_by_layer, system: Optional["SystemMatrix"] = None,
                             power_all: Optional[np.ndarray] = None) -> list:
@@ -754,19 +782,17 @@ def produce_layer_solutions(layers, vindex: VertexIndexer, meshes, mesh_index_to
         else:
             xy, tri, mvo, mto, sg = _flatten_meshes(meshes, sig)
             power_all = ctx.power_density(xy, tri, mvo, mto, sg, v[:len(vindex)])
-    toff = np.concatenate([[0], np.cumsum([len(m.triangles) for m in meshes])]).astype(np.int64)
+    toff = _offsets([len(m.triangles) for m in meshes])
     out = []
     for layer_i, _layer in enumerate(layers):
         sol = LayerSolution(meshes=[], potentials=[], power_densities=[],
                             disconnected_meshes=disconnected_meshes_by_layer[layer_i])
-        for mesh_i, msh in enumerate(meshes):
-            if mesh_index_to_layer_index[mesh_i] != layer_i:
-                continue
+        for mesh_i, msh, lo, hi in _layer_meshes(meshes, mesh_index_to_layer_index, toff, layer_i):
             zf = mesh.ZeroForm(msh)
             zf.values = np.array(v[vindex.offsets[mesh_i]:vindex.offsets[mesh_i + 1]], dtype=DTYPE)
             tf = mesh.TwoForm(msh)
             if power_all is not None:
-                tf.values = np.array(power_all[toff[mesh_i]:toff[mesh_i + 1]], dtype=DTYPE)
+                tf.values = np.array(power_all[lo:hi], dtype=DTYPE)
             sol.meshes.append(msh)
             sol.potentials.append(zf)
             sol.power_densities.append(tf)
@@ -784,12 +810,8 @@ def _solve_partitioned(prob, meshes, mesh_index_to_layer_index, vindex, filtered
     """The solve of ``solve_meshed`` with the rows dealt to several GPUs (``distributed.py``): every rank lists the
     same stamps, assembles and solves its own rows, and all ranks end up with all potentials."""
     from . import distributed
-    conductances = [prob.layers[mesh_index_to_layer_index[i]].conductance for i in range(len(meshes))]
-    stamps, r = allocate_system(vindex, node_indexer)
-    for network in filtered_networks:
-        stamp_network_into_system(network, node_indexer, stamps, r)
-    setup_ground_node(find_best_ground_node_index(prob, node_indexer), stamps, r)
-    n_pot = len(vindex) + node_indexer.internal_node_count
+    conductances, stamps, r, n_pot = _stamp_problem(prob, meshes, mesh_index_to_layer_index, vindex, filtered_networks,
+                                                    node_indexer)
     plan = distributed.build_problem_partition(meshes, conductances, list(mesh_index_to_layer_index), stamps, r, n_pot,
                                                partition.rank, partition.world)
     v_pot, res = distributed.solve_partitioned(plan, ctx, dist=partition.dist, team=partition.team, rtol=RTOL,
@@ -804,9 +826,7 @@ def _solve_partitioned(prob, meshes, mesh_index_to_layer_index, vindex, filtered
         # KCL over all potential rows: the mesh and resistor terms cancel, what is left is the ground current (row of
         # solver.py:558-560) = the net current the sources inject
         v[-1] = float(np.sum(r[:n_pot]))
-    info = SolverInfo(ground_node_current=float(v[-1]), residual_norm=float(res.abs_residual),
-                      iterations=int(res.iterations), rel_residual=float(res.rel_residual), solve_seconds=float(res.seconds))
-    return v, info
+    return v, _solver_info(res, float(v[-1]), res.abs_residual)
 
 
 def _warn_ground_current(current: float, where: str = "") -> None:
@@ -819,14 +839,67 @@ def _warn_ground_current(current: float, where: str = "") -> None:
             "ill-conditioned system.", SolverWarning)
 
 
-def _meshed_inputs(prob, meshes, filtered_networks, disconnected_meshes_by_layer):
-    """The defaults of solve_meshed's arguments, and the meshes as :class:`mesh.Mesh`."""
+@dataclass
+class IndexedBoard:
+    """A meshed Problem with its unknowns numbered: what every ``solve_meshed*`` entry point starts from."""
+    prob: object
+    meshes: list                           # as mesh.Mesh
+    layer_of: list                         # mesh_index_to_layer_index
+    filtered_networks: list
+    disconnected_meshes_by_layer: list
+    vindex: VertexIndexer
+    node_indexer: NodeIndexer
+    tri_offsets: np.ndarray                # where each mesh's faces start in the per-face arrays over all meshes
+
+    def layer_meshes(self, layer_i: int):
+        """(mesh index, mesh, lo, hi) of every mesh of the layer (_layer_meshes)."""
+        return _layer_meshes(self.meshes, self.layer_of, self.tri_offsets, layer_i)
+
+    @contextlib.contextmanager
+    def assembled(self):
+        """``assemble_system`` of the board as a context: (L on the device, r) inside, L closed on the way out."""
+        log.info("Assembling the global system")
+        L, r = assemble_system(self.prob, self.meshes, self.layer_of, self.vindex, self.filtered_networks, self.node_indexer)
+        try:
+            yield L, r
+        finally:
+            L.close()
+
+
+def index_board(prob, meshes, mesh_index_to_layer_index, filtered_networks=None,
+                disconnected_meshes_by_layer=None) -> IndexedBoard:
+    """The :class:`IndexedBoard` of solve_meshed's arguments: their defaults filled in, the meshes as :class:`mesh.Mesh`, the
+    connections snapped to vertices and the unknowns numbered."""
     meshes = [m if isinstance(m, mesh.Mesh) else mesh.Mesh.from_reference(m) for m in meshes]
     if filtered_networks is None:
         filtered_networks = list(prob.networks)
     if disconnected_meshes_by_layer is None:
         disconnected_meshes_by_layer = [[] for _ in prob.layers]
-    return meshes, filtered_networks, disconnected_meshes_by_layer
+    log.info("Indexing vertices and connections")
+    vindex = VertexIndexer.create(meshes)
+    node_indexer = NodeIndexer.create(prob, meshes, mesh_index_to_layer_index, vindex, filtered_networks)
+    return IndexedBoard(prob, meshes, mesh_index_to_layer_index, filtered_networks, disconnected_meshes_by_layer, vindex,
+                        node_indexer, _offsets([len(m.triangles) for m in meshes]))
+
+
+def _refuse_partition(partition, what: str) -> None:
+    """The block features run on one GPU: ValueError for a ``partition`` over several."""
+    if partition is not None and partition.world > 1:
+        raise ValueError(f"{what} are solved on one GPU: the row-partitioned path (partition.world > 1) does not take them")
+
+
+class _Laps:
+    """The host time of consecutive steps of an entry point, written into its ``timings`` dict (None: nothing is kept)."""
+
+    def __init__(self, timings: Optional[dict]):
+        self.timings, self.since = timings, time.perf_counter()
+
+    def lap(self, key: Optional[str] = None) -> None:
+        """The time since the last lap goes under ``key`` (None: to nobody), and the next lap starts."""
+        now = time.perf_counter()
+        if key is not None and self.timings is not None:
+            self.timings[key] = now - self.since
+        self.since = now
 
 
 def solve_meshed(prob, meshes, mesh_index_to_layer_index, *, filtered_networks=None,
@@ -836,35 +909,23 @@ def solve_meshed(prob, meshes, mesh_index_to_layer_index, *, filtered_networks=N
     ``partition``: a :class:`padne_amd.distributed.Partition` -- the rows are dealt to the GPUs of the node (by layer, or
     by strips of layers when there are fewer layers than GPUs); every rank calls this with the same Problem and gets the
     same Solution."""
-    meshes, filtered_networks, disconnected_meshes_by_layer = _meshed_inputs(prob, meshes, filtered_networks,
-                                                                             disconnected_meshes_by_layer)
-    log.info("Indexing vertices and connections")
-    vindex = VertexIndexer.create(meshes)
-    node_indexer = NodeIndexer.create(prob, meshes, mesh_index_to_layer_index, vindex, filtered_networks)
+    board = index_board(prob, meshes, mesh_index_to_layer_index, filtered_networks, disconnected_meshes_by_layer)
     if partition is not None and partition.world > 1:
         ctx = get_context()
-        v, solver_info = _solve_partitioned(prob, meshes, mesh_index_to_layer_index, vindex, filtered_networks,
-                                            node_indexer, partition, ctx)
+        v, solver_info = _solve_partitioned(prob, board.meshes, mesh_index_to_layer_index, board.vindex, board.filtered_networks,
+                                            board.node_indexer, partition, ctx)
         _warn_ground_current(solver_info.ground_node_current)
-        layer_solutions = produce_layer_solutions(prob.layers, vindex, meshes, mesh_index_to_layer_index, v,
-                                                  disconnected_meshes_by_layer)
+        layer_solutions = produce_layer_solutions(prob.layers, board.vindex, board.meshes, mesh_index_to_layer_index, v,
+                                                  board.disconnected_meshes_by_layer)
         return Solution(problem=prob, layer_solutions=layer_solutions, solver_info=solver_info)
-    log.info("Assembling the global system")
-    L, r = assemble_system(prob, meshes, mesh_index_to_layer_index, vindex, filtered_networks, node_indexer)
-    log.info("Solving the system of equations")
-    try:
+    with board.assembled() as (L, r):
+        log.info("Solving the system of equations")
         v, solver_info = solve_system(L, r)
-    except BaseException:
-        L.close()
-        raise
-    _warn_ground_current(solver_info.ground_node_current)
-    log.info("Producing the solution object")
-    try:
+        _warn_ground_current(solver_info.ground_node_current)
+        log.info("Producing the solution object")
         # the mesh is still on the device with the assembled system: the power densities need only the potentials
-        layer_solutions = produce_layer_solutions(prob.layers, vindex, meshes, mesh_index_to_layer_index, v,
-                                                  disconnected_meshes_by_layer, system=L)
-    finally:
-        L.close()
+        layer_solutions = produce_layer_solutions(prob.layers, board.vindex, board.meshes, mesh_index_to_layer_index, v,
+                                                  board.disconnected_meshes_by_layer, system=L)
     return Solution(problem=prob, layer_solutions=layer_solutions, solver_info=solver_info)
 
 
@@ -876,11 +937,11 @@ def solve(prob, mesher_config: Optional[mesh.Mesher.Config] = None, *, mesher=No
     so does :class:`padne_amd.structured.StructuredMesher` for rectangles and annuli); every
     polygon of every layer is meshed and treated as connected.
     """
-    meshes, mesh_index_to_layer_index = _mesh_problem(prob, mesher_config, mesher)
+    meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
     return solve_meshed(prob, meshes, mesh_index_to_layer_index, partition=partition)
 
 
-def _mesh_problem(prob, mesher_config, mesher):
+def mesh_problem(prob, mesher_config=None, mesher=None):
     """Steps 1-3 of the reference's ``solve()``: every polygon of every layer meshed, with the connections of its layer as
     seeds.  Returns (meshes, mesh_index_to_layer_index)."""
     if mesher is None:
@@ -1024,32 +1085,50 @@ def load_case_constraint_values(layout: KKTLayout, rows, cols, vals, k: int) -> 
     return values
 
 
-def _solve_load_case_block(L: SystemMatrix, rows, cols, vals, k: int, timings: Optional[dict] = None):
-    """solve_system on the block given by its triples, then the power densities of every column from the V stage 2 left on
-    the device.  Returns (V (N, k), ||L v_j - r_j|| (k,), SolveResult, power (k, n_tri) or None without triangles)."""
-    t0 = time.perf_counter()
+def block_plan_inputs(L: SystemMatrix, rows, cols, vals, n_cols: int):
+    """What a device plan of the block given by its triples takes, as ``build_block_reduction`` returns it: (the Reduction of
+    L with its floating copper pinned, known_idx, known_val (n_cols, n_known))."""
     layout = L.layout
     if layout is None or not layout.constraints:
         raise SingularSystemError("system has no ground constraint")
     pins = _floating_pins(L, layout, None)
-    red, known_idx, known_val = build_block_reduction(layout, load_case_constraint_values(layout, rows, cols, vals, k), pins)
-    plan = _plan_for(L, L.dev, layout, red, _wants_reorder(L, None), False)
-    members = sorted({int(x) for mem, cons, _ in red.groups if cons for x in mem})
-    extras = [dict(cst.gamma) for cst in red.regulators]
+    return build_block_reduction(layout, load_case_constraint_values(layout, rows, cols, vals, n_cols), pins)
+
+
+def _solve_block_on_device(L: SystemMatrix, rows, cols, vals, n_cols: int, power_rows: int, laps: _Laps,
+                           currents: bool = False):
+    """solve_system on the block given by its triples, up to the potentials: reduction, plan, ``solve_block_coo``,
+    ``_finish_block``.  The final V stays on the device for the face kernels that follow; ``power_rows``: the rows of the
+    power-density array those return, made ready while the device solves (with ``currents``, the arrays of
+    ``current_report`` too).  Returns (plan, V (N, n_cols), ||L v_j - r_j|| (n_cols,), SolveResult, n_tri, n_mesh); ``laps``
+    receives stage1 and stage2."""
+    red, known_idx, known_val = block_plan_inputs(L, rows, cols, vals, n_cols)
+    plan = _plan_for(L, L.dev, L.layout, red, _wants_reorder(L, None), False)
+    members = red.probe_members
     n_tri = len(L.tri) if L.tri is not None else 0
-    probes, res = plan.solve_block_coo(k, rows, cols, vals, known_idx, known_val, extras, members, rtol=RTOL, max_iter=MAX_ITER,
-                                       abs_residual_target=ABS_RESIDUAL_TARGET, power_tri=n_tri)
-    t1 = time.perf_counter()
-    V, residual_norms = _finish_block(plan, red, members, probes, k)
-    t2 = time.perf_counter()
-    power = plan.power_density_block(k, n_tri) if n_tri else None
-    if timings is not None:
-        timings.update(stage1=t1 - t0, stage2=t2 - t1, power_density=time.perf_counter() - t2)
-    return V, residual_norms, res, power
+    n_mesh = len(L.mesh_offsets) - 1 if L.mesh_offsets is not None else 0
+    probes, res = plan.solve_block_coo(n_cols, rows, cols, vals, known_idx, known_val, red.regulator_columns, members,
+                                       rtol=RTOL, max_iter=MAX_ITER, abs_residual_target=ABS_RESIDUAL_TARGET, power_tri=n_tri,
+                                       power_rows=power_rows, current_tri=n_tri if currents else 0)
+    laps.lap("stage1")
+    V, residual_norms = _finish_block(plan, red, members, probes, n_cols)
+    laps.lap("stage2")
+    return plan, V, residual_norms, res, n_tri, n_mesh
+
+
+def _column_solution(board: IndexedBoard, prob, v: np.ndarray, residual_norm, res, power, where: str = "") -> Solution:
+    """The Solution of ``prob`` from one column ``v`` of a solved block and that column's power densities ``power`` (None
+    without triangles); its SolverInfo reports the block solve as a whole.  ``where`` opens the ground-current warning."""
+    ground_node_current = float(v[-1])
+    _warn_ground_current(ground_node_current, where)
+    layer_solutions = produce_layer_solutions(board.prob.layers, board.vindex, board.meshes, board.layer_of, v,
+                                              board.disconnected_meshes_by_layer, power_all=power)
+    return Solution(problem=prob, layer_solutions=layer_solutions,
+                    solver_info=_solver_info(res, ground_node_current, residual_norm))
 
 
 def solve_meshed_load_cases(prob, meshes, mesh_index_to_layer_index, cases, *, filtered_networks=None,
-                            disconnected_meshes_by_layer=None, partition=None) -> list:
+                            disconnected_meshes_by_layer=None, partition=None, timings: Optional[dict] = None) -> list:
     """``solve_meshed`` for several load cases of one board: a list of Solutions, one per mapping of ``cases`` (see
     :func:`check_load_cases`; elements a case does not name keep their Problem value, and an element whose network is not
     among ``filtered_networks`` has no effect, as in the Problem itself).
@@ -1060,16 +1139,9 @@ def solve_meshed_load_cases(prob, meshes, mesh_index_to_layer_index, cases, *, f
     densities, and a SolverInfo whose ``ground_node_current`` and ``residual_norm`` are its own while ``iterations``,
     ``rel_residual`` and ``solve_seconds`` are those of the block solve as a whole (``residual_norms`` is None).  One case
     is ``solve_meshed`` on its substituted Problem.  ValueError, before anything reaches the device, for invalid cases and
-    for a ``partition`` over several GPUs (the row-partitioned path does not take load cases)."""
-    return _load_case_solutions(prob, meshes, mesh_index_to_layer_index, cases, filtered_networks, disconnected_meshes_by_layer,
-                                partition)
-
-
-def _load_case_solutions(prob, meshes, mesh_index_to_layer_index, cases, filtered_networks, disconnected_meshes_by_layer,
-                         partition, timings: Optional[dict] = None) -> list:
-    """solve_meshed_load_cases; ``timings`` (a dict) receives the host time of each step in seconds."""
-    if partition is not None and partition.world > 1:
-        raise ValueError("load cases are solved on one GPU: the row-partitioned path (partition.world > 1) does not take them")
+    for a ``partition`` over several GPUs (the row-partitioned path does not take load cases).
+    ``timings`` (a dict) receives the host time of each step of a block in seconds."""
+    _refuse_partition(partition, "load cases")
     cases = check_load_cases(prob, cases)
     substituted = [substitute_load_case(prob, case) for case in cases]
     if len(cases) == 1:
@@ -1079,49 +1151,31 @@ def _load_case_solutions(prob, meshes, mesh_index_to_layer_index, cases, filtere
         return [solve_meshed(sub, meshes, mesh_index_to_layer_index, filtered_networks=filtered_networks,
                              disconnected_meshes_by_layer=disconnected_meshes_by_layer)]
     k = len(cases)
-    t0 = time.perf_counter()
-    meshes, filtered_networks, disconnected_meshes_by_layer = _meshed_inputs(prob, meshes, filtered_networks,
-                                                                             disconnected_meshes_by_layer)
-    log.info("Indexing vertices and connections")
-    vindex = VertexIndexer.create(meshes)
-    node_indexer = NodeIndexer.create(prob, meshes, mesh_index_to_layer_index, vindex, filtered_networks)
-    t1 = time.perf_counter()
-    log.info("Assembling the global system")
-    L, _ = assemble_system(prob, meshes, mesh_index_to_layer_index, vindex, filtered_networks, node_indexer)
-    try:
-        rows, cols, vals = stamp_load_cases(filtered_networks, node_indexer, L.shape[0], cases)
-        t2 = time.perf_counter()
+    laps = _Laps(timings)
+    board = index_board(prob, meshes, mesh_index_to_layer_index, filtered_networks, disconnected_meshes_by_layer)
+    laps.lap("indexing")
+    with board.assembled() as (L, _):
+        rows, cols, vals = stamp_load_cases(board.filtered_networks, board.node_indexer, L.shape[0], cases)
+        laps.lap("assembly")
         log.info(f"Solving {k} load cases as one block")
-        V, residual_norms, res, power = _solve_load_case_block(L, rows, cols, vals, k, timings)
-    finally:
-        L.close()
-    t3 = time.perf_counter()
-    if _stalled(res, RTOL):
-        col_norms = np.sqrt(np.bincount(cols, weights=vals * vals, minlength=k))
-        _warn_if_stalled(res, RTOL, _stalled_columns(residual_norms, col_norms=col_norms))
+        plan, V, residual_norms, res, n_tri, _n_mesh = _solve_block_on_device(L, rows, cols, vals, k, k, laps)
+        power = plan.power_density_block(k, n_tri) if n_tri else None
+        laps.lap("power_density")
+    laps.lap()
+    _warn_if_block_stalled(res, residual_norms, cols, vals, k)
     log.info("Producing the solution objects")
-    solutions = []
-    for j, (sub, _) in enumerate(substituted):
-        ground_node_current = float(V[-1, j])
-        _warn_ground_current(ground_node_current, f"Load case {j}: ")
-        info = SolverInfo(ground_node_current=ground_node_current, residual_norm=float(residual_norms[j]),
-                          iterations=int(res.iterations), rel_residual=float(res.rel_residual), solve_seconds=float(res.seconds))
-        layer_solutions = produce_layer_solutions(prob.layers, vindex, meshes, mesh_index_to_layer_index, V[:, j],
-                                                  disconnected_meshes_by_layer,
-                                                  power_all=None if power is None else power[j])
-        solutions.append(Solution(problem=sub, layer_solutions=layer_solutions, solver_info=info))
-    if timings is not None:
-        timings.update(indexing=t1 - t0, assembly=t2 - t1, solutions=time.perf_counter() - t3)
+    solutions = [_column_solution(board, sub, V[:, j], residual_norms[j], res, None if power is None else power[j],
+                                  f"Load case {j}: ") for j, (sub, _) in enumerate(substituted)]
+    laps.lap("solutions")
     return solutions
 
 
 def solve_load_cases(prob, cases, mesher_config: Optional[mesh.Mesher.Config] = None, *, mesher=None,
                      partition=None) -> list:
     """``solve`` for several load cases of one board (see :func:`solve_meshed_load_cases`): the board is meshed once."""
-    if partition is not None and partition.world > 1:
-        raise ValueError("load cases are solved on one GPU: the row-partitioned path (partition.world > 1) does not take them")
+    _refuse_partition(partition, "load cases")
     cases = check_load_cases(prob, cases)
-    meshes, mesh_index_to_layer_index = _mesh_problem(prob, mesher_config, mesher)
+    meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
     return solve_meshed_load_cases(prob, meshes, mesh_index_to_layer_index, cases)
 
 
@@ -1341,7 +1395,8 @@ def _gather_element_rows(rows, V: np.ndarray, positions=_ROW_SENSITIVITY_UNKNOWN
 
 
 def solve_meshed_sensitivities(prob, meshes, mesh_index_to_layer_index, objectives, *, filtered_networks=None,
-                               disconnected_meshes_by_layer=None, partition=None):
+                               disconnected_meshes_by_layer=None, partition=None,
+                               timings: Optional[dict] = None):
     """``solve_meshed`` together with the sensitivities of potential differences: (Solution, [Sensitivity per objective]).
 
     An objective is a pair (p, n) of NodeIDs of one network among ``filtered_networks`` (:func:`check_objectives`); its
@@ -1358,137 +1413,61 @@ def solve_meshed_sensitivities(prob, meshes, mesh_index_to_layer_index, objectiv
     plan (K: regulators with a gain term); the faces come from one kernel over the potentials the device holds.  The
     Solution is that of ``prob``, filled as ``solve_meshed_load_cases`` fills a case of a block (its SolverInfo reports the
     block solve as a whole).  ValueError, before anything reaches the device, for invalid objectives and for a
-    ``partition`` over several GPUs."""
-    return _sensitivity_solution(prob, meshes, mesh_index_to_layer_index, objectives, filtered_networks,
-                                 disconnected_meshes_by_layer, partition)
-
-
-def _block_column_zero_solution(prob, vindex, meshes, mesh_index_to_layer_index, disconnected_meshes_by_layer, V, residual_norms,
-                                res, power, cols, vals, n_cols: int) -> Solution:
-    """The Solution of ``prob`` from column 0 of a solved block (the block's triples ``cols``, ``vals`` name the stalled
-    columns in the warning) and column 0's power densities ``power``; its SolverInfo reports the block solve as a whole."""
-    if _stalled(res, RTOL):
-        col_norms = np.sqrt(np.bincount(cols, weights=vals * vals, minlength=n_cols))
-        _warn_if_stalled(res, RTOL, _stalled_columns(residual_norms, col_norms=col_norms))
-    ground_node_current = float(V[-1, 0])
-    _warn_ground_current(ground_node_current)
-    info = SolverInfo(ground_node_current=ground_node_current, residual_norm=float(residual_norms[0]),
-                      iterations=int(res.iterations), rel_residual=float(res.rel_residual), solve_seconds=float(res.seconds))
-    layer_solutions = produce_layer_solutions(prob.layers, vindex, meshes, mesh_index_to_layer_index, np.ascontiguousarray(V[:, 0]),
-                                              disconnected_meshes_by_layer, power_all=power)
-    return Solution(problem=prob, layer_solutions=layer_solutions, solver_info=info)
-
-
-def _sensitivity_solution(prob, meshes, mesh_index_to_layer_index, objectives, filtered_networks, disconnected_meshes_by_layer,
-                          partition, timings: Optional[dict] = None):
-    """solve_meshed_sensitivities; ``timings`` (a dict) receives the host time of each step in seconds."""
-    if partition is not None and partition.world > 1:
-        raise ValueError("sensitivities are solved on one GPU: the row-partitioned path (partition.world > 1) does not take "
-                         "them")
+    ``partition`` over several GPUs.  ``timings`` (a dict) receives the host time of each step in seconds."""
+    _refuse_partition(partition, "sensitivities")
     objectives = check_objectives(prob, objectives, filtered_networks)
     k = len(objectives)
-    t0 = time.perf_counter()
-    meshes, filtered_networks, disconnected_meshes_by_layer = _meshed_inputs(prob, meshes, filtered_networks,
-                                                                             disconnected_meshes_by_layer)
-    log.info("Indexing vertices and connections")
-    vindex = VertexIndexer.create(meshes)
-    node_indexer = NodeIndexer.create(prob, meshes, mesh_index_to_layer_index, vindex, filtered_networks)
-    pairs = global_elements(filtered_networks, node_indexer)
+    laps = _Laps(timings)
+    board = index_board(prob, meshes, mesh_index_to_layer_index, filtered_networks, disconnected_meshes_by_layer)
+    pairs = global_elements(board.filtered_networks, board.node_indexer)
     terms = woodbury_terms([row for _, row in pairs])
-    idx = node_indexer.node_to_global_index
+    idx = board.node_indexer.node_to_global_index
     objective_rows = [(idx[p], idx[n]) for p, n in objectives]
     n_cols = sensitivity_block_columns(k, len(terms))
-    t1 = time.perf_counter()
-    log.info("Assembling the global system")
-    L, _ = assemble_system(prob, meshes, mesh_index_to_layer_index, vindex, filtered_networks, node_indexer)
-    try:
-        rows, cols, vals = stamp_sensitivity_block(filtered_networks, node_indexer, L.shape[0], objective_rows, terms)
-        t2 = time.perf_counter()
+    laps.lap("indexing")
+    with board.assembled() as (L, _):
+        rows, cols, vals = stamp_sensitivity_block(board.filtered_networks, board.node_indexer, L.shape[0], objective_rows, terms)
+        laps.lap("assembly")
         log.info(f"Solving {k} adjoint(s) and {2 * len(terms)} regulator column(s) as one block with the Problem")
-        V, residual_norms, res, power, density, totals, W = _solve_sensitivity_block(L, rows, cols, vals, n_cols, k, terms,
-                                                                                     timings)
-    finally:
-        L.close()
-    t3 = time.perf_counter()
+        plan, V, residual_norms, res, n_tri, n_mesh = _solve_block_on_device(L, rows, cols, vals, n_cols, 1 + k, laps)
+        # the adjoint weights on the host, then the face kernel on the V the device holds: the power of column 0 (n_tri,),
+        # s_f / area_f (k, n_tri) and the per-mesh sums of s_f (k, n_mesh)
+        W = adjoint_weights(V, k, terms)
+        power = density = totals = None
+        if n_tri:
+            power, density, totals = plan.sensitivity_block(W, n_tri, n_mesh)
+        laps.lap("sensitivity")
+    laps.lap()
     log.info("Producing the solution and the sensitivities")
-    solution = _block_column_zero_solution(prob, vindex, meshes, mesh_index_to_layer_index, disconnected_meshes_by_layer, V,
-                                           residual_norms, res, power, cols, vals, n_cols)
+    _warn_if_block_stalled(res, residual_norms, cols, vals, n_cols)
+    solution = _column_solution(board, prob, np.ascontiguousarray(V[:, 0]), residual_norms[0], res, power)
     elements = _sensitivity_elements(pairs, V, W)
-    toff = np.concatenate([[0], np.cumsum([len(m.triangles) for m in meshes])]).astype(np.int64)
     sens = []
     for j, ((p, n), (ip, in_)) in enumerate(zip(objectives, objective_rows)):
         densities, layer_sums = [], []
         for layer_i in range(len(prob.layers)):
             forms, total = [], 0.0
-            for mesh_i, msh in enumerate(meshes):
-                if mesh_index_to_layer_index[mesh_i] != layer_i:
-                    continue
+            for mesh_i, msh, lo, hi in board.layer_meshes(layer_i):
                 tf = mesh.TwoForm(msh)
                 if density is not None:
-                    tf.values = np.array(density[j, toff[mesh_i]:toff[mesh_i + 1]], dtype=DTYPE)
+                    tf.values = np.array(density[j, lo:hi], dtype=DTYPE)
                     total += float(totals[j, mesh_i])
                 forms.append(tf)
             densities.append(forms)
             layer_sums.append(total)
         sens.append(Sensitivity(nodes=(p, n), value=float(V[ip, 0] - V[in_, 0]), densities=densities, layers=layer_sums,
                                 elements=elements[j]))
-    if timings is not None:
-        timings.update(indexing=t1 - t0, assembly=t2 - t1, solutions=time.perf_counter() - t3)
+    laps.lap("solutions")
     return solution, sens
-
-
-def _solve_sensitivity_block(L: SystemMatrix, rows, cols, vals, n_cols: int, k: int, terms, timings: Optional[dict] = None):
-    """The block solve of a sensitivity call, then the adjoint weights on the host and the face kernel on the V the device
-    holds.  Returns (V (N, n_cols), ||L v_j - r_j|| (n_cols,), SolveResult, power of column 0 (n_tri,), s_f / area_f
-    (k, n_tri), per-mesh sums of s_f (k, n_mesh), W (k, n_cols)); the three face arrays are None without triangles."""
-    plan, V, residual_norms, res, n_tri, n_mesh = _solve_block_on_device(L, rows, cols, vals, n_cols, 1 + k, timings)
-    t2 = time.perf_counter()
-    W = adjoint_weights(V, k, terms)
-    power = density = totals = None
-    if n_tri:
-        power, density, totals = plan.sensitivity_block(W, n_tri, n_mesh)
-    if timings is not None:
-        timings.update(sensitivity=time.perf_counter() - t2)
-    return V, residual_norms, res, power, density, totals, W
-
-
-def _solve_block_on_device(L: SystemMatrix, rows, cols, vals, n_cols: int, power_rows: int, timings: Optional[dict] = None,
-                           currents: bool = False):
-    """The load-case block path up to the potentials: reduction, plan, ``solve_block_coo`` of the triples, ``_finish_block``.
-    The final V stays on the device for the face kernels that follow; ``power_rows``: the rows of the power-density array
-    those return, made ready while the device solves (with ``currents``, the arrays of ``current_report`` too).  Returns
-    (plan, V (N, n_cols), ||L v_j - r_j|| (n_cols,), SolveResult, n_tri, n_mesh); ``timings`` receives stage1 and stage2."""
-    t0 = time.perf_counter()
-    layout = L.layout
-    if layout is None or not layout.constraints:
-        raise SingularSystemError("system has no ground constraint")
-    pins = _floating_pins(L, layout, None)
-    red, known_idx, known_val = build_block_reduction(layout, load_case_constraint_values(layout, rows, cols, vals, n_cols),
-                                                      pins)
-    plan = _plan_for(L, L.dev, layout, red, _wants_reorder(L, None), False)
-    members = sorted({int(x) for mem, cons, _ in red.groups if cons for x in mem})
-    extras = [dict(cst.gamma) for cst in red.regulators]
-    n_tri = len(L.tri) if L.tri is not None else 0
-    n_mesh = len(L.mesh_offsets) - 1 if L.mesh_offsets is not None else 0
-    probes, res = plan.solve_block_coo(n_cols, rows, cols, vals, known_idx, known_val, extras, members, rtol=RTOL,
-                                       max_iter=MAX_ITER, abs_residual_target=ABS_RESIDUAL_TARGET, power_tri=n_tri,
-                                       power_rows=power_rows, current_tri=n_tri if currents else 0)
-    t1 = time.perf_counter()
-    V, residual_norms = _finish_block(plan, red, members, probes, n_cols)
-    if timings is not None:
-        timings.update(stage1=t1 - t0, stage2=time.perf_counter() - t1)
-    return plan, V, residual_norms, res, n_tri, n_mesh
 
 
 def solve_sensitivities(prob, objectives, mesher_config: Optional[mesh.Mesher.Config] = None, *, mesher=None,
                         partition=None):
     """``solve`` with the sensitivities of potential differences (see :func:`solve_meshed_sensitivities`): the board is
     meshed once.  Returns (Solution, [Sensitivity per objective])."""
-    if partition is not None and partition.world > 1:
-        raise ValueError("sensitivities are solved on one GPU: the row-partitioned path (partition.world > 1) does not take "
-                         "them")
+    _refuse_partition(partition, "sensitivities")
     objectives = check_objectives(prob, objectives)
-    meshes, mesh_index_to_layer_index = _mesh_problem(prob, mesher_config, mesher)
+    meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
     return solve_meshed_sensitivities(prob, meshes, mesh_index_to_layer_index, objectives)
 
 
@@ -1609,7 +1588,7 @@ def element_flows(element_rows, x: np.ndarray) -> list:
 
 
 def solve_meshed_currents(prob, meshes, mesh_index_to_layer_index, cuts=(), *, filtered_networks=None,
-                          disconnected_meshes_by_layer=None, partition=None):
+                          disconnected_meshes_by_layer=None, partition=None, timings: Optional[dict] = None):
     """``solve_meshed`` together with where the current goes: (Solution, CurrentReport).
 
     - ``vectors`` / ``magnitudes``: per face J = -sigma grad V [A/mm], the sheet current density, with sigma the layer's
@@ -1630,63 +1609,39 @@ def solve_meshed_currents(prob, meshes, mesh_index_to_layer_index, cuts=(), *, f
     One call is the load-case block path with one column and its face kernels on the V the device holds; element currents
     come from V's rows at the elements' unknowns.  Disconnected meshes carry no current and take no part.  The Solution is
     that of ``prob``, filled as ``solve_meshed_sensitivities`` fills it.  ValueError, before anything reaches the device, for
-    invalid cuts (:func:`check_cuts`) and for a ``partition`` over several GPUs."""
-    return _currents_solution(prob, meshes, mesh_index_to_layer_index, cuts, filtered_networks, disconnected_meshes_by_layer,
-                              partition)
-
-
-def _refuse_partition(partition) -> None:
-    if partition is not None and partition.world > 1:
-        raise ValueError("currents are solved on one GPU: the row-partitioned path (partition.world > 1) does not take them")
-
-
-def _currents_solution(prob, meshes, mesh_index_to_layer_index, cuts, filtered_networks, disconnected_meshes_by_layer,
-                       partition, timings: Optional[dict] = None):
-    """solve_meshed_currents; ``timings`` (a dict) receives the host time of each step in seconds."""
-    _refuse_partition(partition)
+    invalid cuts (:func:`check_cuts`) and for a ``partition`` over several GPUs.  ``timings`` (a dict) receives the host
+    time of each step in seconds."""
+    _refuse_partition(partition, "currents")
     cuts = check_cuts(prob, cuts)
-    t0 = time.perf_counter()
-    meshes, filtered_networks, disconnected_meshes_by_layer = _meshed_inputs(prob, meshes, filtered_networks,
-                                                                             disconnected_meshes_by_layer)
-    log.info("Indexing vertices and connections")
-    vindex = VertexIndexer.create(meshes)
-    node_indexer = NodeIndexer.create(prob, meshes, mesh_index_to_layer_index, vindex, filtered_networks)
-    pairs = global_elements(filtered_networks, node_indexer)
-    t1 = time.perf_counter()
-    log.info("Assembling the global system")
-    L, _ = assemble_system(prob, meshes, mesh_index_to_layer_index, vindex, filtered_networks, node_indexer)
-    try:
-        rows, cols, vals = stamp_load_cases(filtered_networks, node_indexer, L.shape[0], [{}])
-        t2 = time.perf_counter()
+    laps = _Laps(timings)
+    board = index_board(prob, meshes, mesh_index_to_layer_index, filtered_networks, disconnected_meshes_by_layer)
+    pairs = global_elements(board.filtered_networks, board.node_indexer)
+    laps.lap("indexing")
+    with board.assembled() as (L, _):
+        rows, cols, vals = stamp_load_cases(board.filtered_networks, board.node_indexer, L.shape[0], [{}])
+        laps.lap("assembly")
         log.info("Solving the Problem and its currents")
-        plan, V, residual_norms, res, n_tri, _n_mesh = _solve_block_on_device(L, rows, cols, vals, 1, 2, timings, currents=True)
-        t3 = time.perf_counter()
+        plan, V, residual_norms, res, n_tri, _n_mesh = _solve_block_on_device(L, rows, cols, vals, 1, 2, laps, currents=True)
         power = J = mag = mesh_max = mesh_face = totals = None
         cut_values = np.zeros(len(cuts))
         if n_tri:
             # sigma sum w (dx)^2 per mesh: the sensitivity kernel with lambda = x; then the current kernels
-            power, _, totals = plan.sensitivity_block(np.ones((1, 1)), n_tri, len(meshes))
+            power, _, totals = plan.sensitivity_block(np.ones((1, 1)), n_tri, len(board.meshes))
             J, mag, mesh_max, mesh_face, cut_values = plan.current_report(
                 1, n_tri, np.asarray(mesh_index_to_layer_index, dtype=np.int32), [c[0] for c in cuts],
                 np.array([[*a, *b] for _, a, b in cuts], dtype=DTYPE).reshape(-1, 4))
-    finally:
-        L.close()
-    t4 = time.perf_counter()
+    laps.lap("currents")
     log.info("Producing the solution and the current report")
-    solution = _block_column_zero_solution(prob, vindex, meshes, mesh_index_to_layer_index, disconnected_meshes_by_layer, V,
-                                           residual_norms, res, power, cols, vals, 1)
+    _warn_if_block_stalled(res, residual_norms, cols, vals, 1)
+    solution = _column_solution(board, prob, np.ascontiguousarray(V[:, 0]), residual_norms[0], res, power)
     local, Vu = _gather_element_rows([row for _, row in pairs], V, _ROW_UNKNOWNS)
     flows = element_flows(local, Vu[:, 0])
-    toff = np.concatenate([[0], np.cumsum([len(m.triangles) for m in meshes])]).astype(np.int64)
     vectors, magnitudes, hotspots, layer_power = [], [], [], []
     for layer_i in range(len(prob.layers)):
         vecs, forms, total, best = [], [], 0.0, None
-        for mesh_i, msh in enumerate(meshes):
-            if mesh_index_to_layer_index[mesh_i] != layer_i:
-                continue
+        for mesh_i, msh, lo, hi in board.layer_meshes(layer_i):
             tf = mesh.TwoForm(msh)
             if J is not None:
-                lo, hi = toff[mesh_i], toff[mesh_i + 1]
                 vecs.append(J[lo:hi])                     # views of this call's own result arrays: no copies
                 tf.values = mag[lo:hi]
                 total += float(totals[0, mesh_i])
@@ -1705,17 +1660,16 @@ def _currents_solution(prob, meshes, mesh_index_to_layer_index, cuts, filtered_n
     report = CurrentReport(vectors=vectors, magnitudes=magnitudes, hotspots=hotspots, layers=layer_power,
                            elements={element: flows[i] for i, (element, _) in enumerate(pairs)},
                            cuts=[float(c) for c in cut_values])
-    if timings is not None:
-        timings.update(indexing=t1 - t0, assembly=t2 - t1, currents=t4 - t3, solutions=time.perf_counter() - t4)
+    laps.lap("solutions")
     return solution, report
 
 
 def solve_currents(prob, cuts=(), mesher_config: Optional[mesh.Mesher.Config] = None, *, mesher=None, partition=None):
     """``solve`` with where the current goes (see :func:`solve_meshed_currents`): the board is meshed once.  Returns
     (Solution, CurrentReport)."""
-    _refuse_partition(partition)
+    _refuse_partition(partition, "currents")
     cuts = check_cuts(prob, cuts)
-    meshes, mesh_index_to_layer_index = _mesh_problem(prob, mesher_config, mesher)
+    meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
     return solve_meshed_currents(prob, meshes, mesh_index_to_layer_index,
                                  [Cut(prob.layers[i], a, b) for i, a, b in cuts])
 
@@ -1821,7 +1775,7 @@ class FieldSampler:
         self.solution = solution
         self.problem = solution.problem
         pts, tris, pots, sig, layer_of = [], [], [], [], []
-        self._first_mesh, self._toff = [], []          # per layer: its first mesh in the flat order, its faces' offsets
+        self._first_mesh = []                          # per layer: its first mesh in the flat order
         for layer_i, (layer, ls) in enumerate(zip(self.problem.layers, solution.layer_solutions)):
             self._first_mesh.append(len(layer_of))
             for msh, zf in zip(ls.meshes, ls.potentials):
@@ -1830,8 +1784,8 @@ class FieldSampler:
                 pots.append(np.asarray(zf.values, dtype=DTYPE).reshape(-1))
                 sig.append(float(layer.conductance))
                 layer_of.append(layer_i)
-        mvo = np.concatenate([[0], np.cumsum([len(p) for p in pts])]).astype(np.int64)
-        self._mto = np.concatenate([[0], np.cumsum([len(t) for t in tris])]).astype(np.int64)
+        mvo = _offsets([len(p) for p in pts])
+        self._mto = _offsets([len(t) for t in tris])
         cat = lambda arrays, shape, dtype: (np.concatenate(arrays) if arrays else np.zeros(shape, dtype=dtype))  # noqa: E731
         self._dev = _hip.Sampler(get_context(), cat(pts, (0, 2), DTYPE), cat(tris, (0, 3), np.int32), mvo, self._mto, layer_of,
                                  sig, len(self.problem.layers), cat(pots, (0,), DTYPE), bins_hint)

@@ -59,12 +59,12 @@ def main():
     prob, loads, _source = board(args.side, args.via_pitch)
     cuts = {0: [], 64: line_cuts(prob, args.side)}
     mesher = StructuredMesher(mesh.Mesher.Config(maximum_size=args.h))
-    meshes, layer_of = solver._mesh_problem(prob, None, mesher)
+    meshes, layer_of = solver.mesh_problem(prob, None, mesher)
     n_vert = sum(len(m.points) for m in meshes)
     n_tri = sum(len(m.triangles) for m in meshes)
 
     def currents(k, timings=None):
-        return solver._currents_solution(prob, meshes, layer_of, cuts[k], None, None, None, timings=timings)
+        return solver.solve_meshed_currents(prob, meshes, layer_of, cuts[k], timings=timings)
 
     def plain():
         return solver.solve_meshed(prob, meshes, layer_of)

@@ -76,14 +76,14 @@ def main():
     k = len(cases)
     mesher = StructuredMesher(mesh.Mesher.Config(maximum_size=args.h))
     t = time.perf_counter()
-    meshes, layer_of = solver._mesh_problem(prob, None, mesher)
+    meshes, layer_of = solver.mesh_problem(prob, None, mesher)
     mesh_s = time.perf_counter() - t
     n_vert = sum(len(m.points) for m in meshes)
     n_tri = sum(len(m.triangles) for m in meshes)
     substituted = [solver.substitute_load_case(prob, c)[0] for c in solver.check_load_cases(prob, cases)]
 
     def block(timings=None):
-        return solver._load_case_solutions(prob, meshes, layer_of, cases, None, None, None, timings=timings)
+        return solver.solve_meshed_load_cases(prob, meshes, layer_of, cases, timings=timings)
 
     def loop():
         return [solver.solve_meshed(p, meshes, layer_of) for p in substituted]

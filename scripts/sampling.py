@@ -51,7 +51,7 @@ def main():
 
     prob, _loads, _source = board(args.side, args.via_pitch)
     mesher = StructuredMesher(mesh.Mesher.Config(maximum_size=args.h))
-    meshes, layer_of = solver._mesh_problem(prob, None, mesher)
+    meshes, layer_of = solver.mesh_problem(prob, None, mesher)
     warnings.simplefilter("ignore", solver.SolverWarning)
     t = time.perf_counter()
     sol = solver.solve_meshed(prob, meshes, layer_of)

@@ -46,12 +46,12 @@ def main():
     prob, loads, _source = board(args.side, args.via_pitch)
     objectives = {1: [(loads[0].f, loads[0].t)], 8: [(load.f, load.t) for load in loads]}
     mesher = StructuredMesher(mesh.Mesher.Config(maximum_size=args.h))
-    meshes, layer_of = solver._mesh_problem(prob, None, mesher)
+    meshes, layer_of = solver.mesh_problem(prob, None, mesher)
     n_vert = sum(len(m.points) for m in meshes)
     n_tri = sum(len(m.triangles) for m in meshes)
 
     def sens(k, timings=None):
-        return solver._sensitivity_solution(prob, meshes, layer_of, objectives[k], None, None, None, timings=timings)
+        return solver.solve_meshed_sensitivities(prob, meshes, layer_of, objectives[k], timings=timings)
 
     def plain():
         return solver.solve_meshed(prob, meshes, layer_of)

@@ -102,7 +102,7 @@ def test_multiplier_recovery_from_probe_rows_matches_the_direct_solve(name, monk
     if pins:
         pytest.skip("floating copper: the direct solve is singular there")
     V = spla.spsolve(L.tocsc(), B)
-    members = sorted({int(x) for mem, cons, _ in red.groups if cons for x in mem})
+    members = red.probe_members
     probes = host_probes(L, B, red, kidx, kval, members, V)
     calls = []
     peel = red.multipliers
@@ -127,7 +127,7 @@ def test_recovery_of_one_column_is_the_single_right_hand_side_arithmetic():
     L, r, layout = layout_of("regulator")
     B = block_of(L, r, layout, 3, seed=3)
     red, kidx, kval = R.build_block_reduction(layout, {c.index: B[c.index, :] for c in layout.constraints}, [])
-    members = sorted({int(x) for mem, cons, _ in red.groups if cons for x in mem})
+    members = red.probe_members
     V = spla.spsolve(L.tocsc(), B)
     probes = host_probes(L, B, red, kidx, kval, members, V)
     i3, m3 = R.recover_currents(red, members, probes, 3)

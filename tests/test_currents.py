@@ -264,7 +264,7 @@ def load_case_board(side=20.0):
     spec.loader.exec_module(mod)
     from padne_amd.structured import StructuredMesher
     prob, loads, source = mod.board(side, 5.0)
-    meshes, layer_of = solver._mesh_problem(prob, None, StructuredMesher(mesh.Mesher.Config(maximum_size=0.2)))
+    meshes, layer_of = solver.mesh_problem(prob, None, StructuredMesher(mesh.Mesher.Config(maximum_size=0.2)))
     return prob, meshes, layer_of
 
 
@@ -294,16 +294,12 @@ def test_repeatable_bitwise_and_a_cut_alone_is_the_same_cut(ctx):
 def test_plan_level_entry_refuses_what_it_cannot_do(ctx):
     system = S.problem_system("problem_mixed")
     meshes, _ = board_of(system, "problem_mixed")
-    prob, layer_of = system.prob, system.layer_of
-    vindex = solver.VertexIndexer.create(meshes)
-    nodes = solver.NodeIndexer.create(prob, meshes, layer_of, vindex, list(prob.networks))
-    L, _ = solver.assemble_system(prob, meshes, layer_of, vindex, list(prob.networks), nodes)
-    try:
-        rows, cols, vals = solver.stamp_load_cases(list(prob.networks), nodes, L.shape[0], [{}])
-        red, kidx, kval = solver.build_block_reduction(
-            L.layout, solver.load_case_constraint_values(L.layout, rows, cols, vals, 1), solver._floating_pins(L, L.layout, None))
-        members = sorted({int(x) for mem, cons, _ in red.groups if cons for x in mem})
-        extras = [dict(cst.gamma) for cst in red.regulators]
+    layer_of = system.layer_of
+    board = solver.index_board(system.prob, meshes, layer_of)
+    with board.assembled() as (L, _):
+        rows, cols, vals = solver.stamp_load_cases(board.filtered_networks, board.node_indexer, L.shape[0], [{}])
+        red, kidx, kval = solver.block_plan_inputs(L, rows, cols, vals, 1)
+        members, extras = red.probe_members, red.regulator_columns
         plan = _hip.KktPlan(L.dev, L.layout.n_potential, red.elim, red.tied, red.n_free)
         n_tri, ml = len(L.tri), np.asarray(layer_of, dtype=np.int32)
         one = ([0], [[0.5, 0.5, 1.5, 1.0]])
@@ -327,5 +323,3 @@ def test_plan_level_entry_refuses_what_it_cannot_do(ctx):
         assert all(np.array_equal(a, b) for a, b in zip(first, second))
         assert first[0].shape == (n_tri, 2) and first[3].shape == (len(meshes),) and first[4].shape == (1,)
         plan.close()
-    finally:
-        L.close()

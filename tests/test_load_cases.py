@@ -1,6 +1,7 @@
 """``solve_meshed_load_cases`` on the device: every case of a block against ``solve_meshed`` on its substituted Problem and
 against a direct solve of that Problem's system, one case against ``solve_meshed`` bit for bit, the block's power
 densities against the single-vector kernel, and the COO entry and the block power density at the plan level."""
+import contextlib
 import warnings
 
 import numpy as np
@@ -64,14 +65,10 @@ def powers(sol):
 
 def direct_solve(prob, meshes, layer_of):
     """v of a direct solve of ``prob``'s assembled system (L downloaded, r stamped on the host)."""
-    vindex = solver.VertexIndexer.create(meshes)
-    nodes = solver.NodeIndexer.create(prob, meshes, layer_of, vindex, list(prob.networks))
-    L, r = solver.assemble_system(prob, meshes, layer_of, vindex, list(prob.networks), nodes)
-    try:
+    board = solver.index_board(prob, meshes, layer_of)
+    with board.assembled() as (L, r):
         v, _, _ = O.solve_system(L.tocsr(), r)
-    finally:
-        L.close()
-    return v, len(vindex)
+    return v, len(board.vindex)
 
 
 @pytest.mark.parametrize("name", ["problem_mixed", "problem_c1", "problem_many_meshes"])
@@ -149,28 +146,25 @@ def test_ground_current_warning_names_the_case(ctx):
         assert len(named) == (0 if np.isclose(sol.solver_info.ground_node_current, 0) else 1)
 
 
+@contextlib.contextmanager
 def plan_inputs(name, k, seed):
-    """An assembled fixture system with its block of k load cases: (L, rows, cols, vals, N, n_tri, reduction pieces)."""
+    """An assembled fixture system with its block of k load cases, closed on the way out: (L, rows, cols, vals, reduction
+    pieces)."""
     prob, meshes, layer_of, _disc, flat = fixture_board(name)
     cases = solver.check_load_cases(prob, block_cases(flat, k, seed))
-    vindex = solver.VertexIndexer.create(meshes)
-    nodes = solver.NodeIndexer.create(prob, meshes, layer_of, vindex, list(prob.networks))
-    L, _ = solver.assemble_system(prob, meshes, layer_of, vindex, list(prob.networks), nodes)
-    rows, cols, vals = solver.stamp_load_cases(list(prob.networks), nodes, L.shape[0], cases)
-    red, kidx, kval = solver.build_block_reduction(L.layout, solver.load_case_constraint_values(L.layout, rows, cols, vals, k),
-                                                   solver._floating_pins(L, L.layout, None))
-    members = sorted({int(x) for mem, cons, _ in red.groups if cons for x in mem})
-    extras = [dict(cst.gamma) for cst in red.regulators]
-    return L, rows, cols, vals, red, kidx, kval, members, extras
+    board = solver.index_board(prob, meshes, layer_of)
+    with board.assembled() as (L, _):
+        rows, cols, vals = solver.stamp_load_cases(board.filtered_networks, board.node_indexer, L.shape[0], cases)
+        red, kidx, kval = solver.block_plan_inputs(L, rows, cols, vals, k)
+        yield L, rows, cols, vals, red, kidx, kval, red.probe_members, red.regulator_columns
 
 
 @pytest.mark.parametrize("name,k", [("problem_mixed", 3), ("problem_two_planes", 10)])
 def test_coo_entry_is_the_dense_entry_and_power_density_block_is_the_vector_kernel(ctx, name, k):
-    L, rows, cols, vals, red, kidx, kval, members, extras = plan_inputs(name, k, seed=5)
-    N, n_tri, n_vert = L.shape[0], len(L.tri), len(L.xy)
-    R = np.zeros((N, k))
-    R[rows, cols] = vals
-    try:
+    with plan_inputs(name, k, seed=5) as (L, rows, cols, vals, red, kidx, kval, members, extras):
+        N, n_tri, n_vert = L.shape[0], len(L.tri), len(L.xy)
+        R = np.zeros((N, k))
+        R[rows, cols] = vals
         plan = _hip.KktPlan(L.dev, L.layout.n_potential, red.elim, red.tied, red.n_free)
         with pytest.raises(ValueError, match="follows padne_kkt_finish_block"):
             plan.power_density_block(k, n_tri)                                          # nothing finished yet
@@ -209,5 +203,3 @@ def test_coo_entry_is_the_dense_entry_and_power_density_block_is_the_vector_kern
             plan.close()
         finally:
             bare.close()
-    finally:
-        L.close()

@@ -137,14 +137,11 @@ def device_J(g, p_num, n_num):
     prob, ids, _ = H.build_problem(g, problem)
     ms = H.problem_meshes(g)
     meshes, layer_of = [mesh.Mesh(xy, tri) for xy, tri, _ in ms], [layer for _, _, layer in ms]
-    vindex = solver.VertexIndexer.create(meshes)
-    nodes = solver.NodeIndexer.create(prob, meshes, layer_of, vindex, list(prob.networks))
-    L, r = solver.assemble_system(prob, meshes, layer_of, vindex, list(prob.networks), nodes)
-    try:
+    board = solver.index_board(prob, meshes, layer_of)
+    with board.assembled() as (L, r):
         v, _ = solver.solve_system(L, r)
-    finally:
-        L.close()
-    return v[nodes.node_to_global_index[ids[p_num]]] - v[nodes.node_to_global_index[ids[n_num]]]
+    idx = board.node_indexer.node_to_global_index
+    return v[idx[ids[p_num]]] - v[idx[ids[n_num]]]
 
 
 def test_finite_differences_of_device_solves(ctx):
@@ -189,7 +186,7 @@ def test_objectives_together_equal_single_calls_and_repeat_bitwise(ctx):
     spec.loader.exec_module(mod)
     from padne_amd.structured import StructuredMesher
     prob, loads, source = mod.board(20.0, 5.0)
-    meshes, layer_of = solver._mesh_problem(prob, None, StructuredMesher(mesh.Mesher.Config(maximum_size=0.2)))
+    meshes, layer_of = solver.mesh_problem(prob, None, StructuredMesher(mesh.Mesher.Config(maximum_size=0.2)))
     assert 35000 < sum(len(m.points) for m in meshes) < 45000
     objectives = [(load.f, load.t) for load in loads] + [(source.p, source.n)]
     assert len(objectives) == 9                            # > 4 objectives per chunk, 10 columns > 8 per column chunk
@@ -214,18 +211,14 @@ def test_objectives_together_equal_single_calls_and_repeat_bitwise(ctx):
 def test_plan_level_entry_refuses_what_it_cannot_do(ctx):
     system = S.problem_system("problem_mixed")
     meshes, _ = board_of(system, "problem_mixed")
-    prob, layer_of = system.prob, system.layer_of
-    vindex = solver.VertexIndexer.create(meshes)
-    nodes = solver.NodeIndexer.create(prob, meshes, layer_of, vindex, list(prob.networks))
-    L, _ = solver.assemble_system(prob, meshes, layer_of, vindex, list(prob.networks), nodes)
-    try:
+    board = solver.index_board(system.prob, meshes, system.layer_of)
+    with board.assembled() as (L, _):
         terms = solver.woodbury_terms(system.rows)
         n_cols = solver.sensitivity_block_columns(1, len(terms))
-        rows, cols, vals = solver.stamp_sensitivity_block(list(prob.networks), nodes, L.shape[0], [(3, 40)], terms)
-        red, kidx, kval = solver.build_block_reduction(
-            L.layout, solver.load_case_constraint_values(L.layout, rows, cols, vals, n_cols), solver._floating_pins(L, L.layout, None))
-        members = sorted({int(x) for mem, cons, _ in red.groups if cons for x in mem})
-        extras = [dict(cst.gamma) for cst in red.regulators]
+        rows, cols, vals = solver.stamp_sensitivity_block(board.filtered_networks, board.node_indexer, L.shape[0], [(3, 40)],
+                                                          terms)
+        red, kidx, kval = solver.block_plan_inputs(L, rows, cols, vals, n_cols)
+        members, extras = red.probe_members, red.regulator_columns
         plan = _hip.KktPlan(L.dev, L.layout.n_potential, red.elim, red.tied, red.n_free)
         n_tri, n_mesh = len(L.tri), len(meshes)
         W = np.zeros((1, n_cols))
@@ -245,5 +238,3 @@ def test_plan_level_entry_refuses_what_it_cannot_do(ctx):
         power2, density2, totals2 = plan.sensitivity_block(W, n_tri, n_mesh)      # the V stays: a second call, same bits
         assert np.array_equal(power, power2) and np.array_equal(density, density2) and np.array_equal(totals, totals2)
         plan.close()
-    finally:
-        L.close()
