@@ -364,6 +364,20 @@ int padne_kkt_sensitivity_block(padne_ctx *ctx, padne_kkt *plan, int32_t n_cols,
 int padne_kkt_current_report(padne_ctx *ctx, padne_kkt *plan, int32_t n_cols, int64_t n_tri, int32_t n_mesh,
                              const int32_t *mesh_layer, int32_t n_cut, const int32_t *cut_layer, const double *cut_xy,
                              double *J_out, double *mag_out, double *mesh_max_out, int64_t *mesh_face_out, double *cut_out);
+/* Gradient-recovery (Zienkiewicz-Zhu) estimate of the discretisation error over the mesh `L` keeps, from column 0 of the
+ * block the last padne_kkt_finish_block left on the device.  Per face f (corners in the order of padne_csr_power_density):
+ * g_f its gradient, A_f its area.  G_out[n_vert][2] = (sum A_f g_f) / (sum A_f) over the faces incident to each vertex, added
+ * in ascending global face number (0 for a vertex without faces or whose areas sum to zero; no special case on the
+ * boundary).  eta_out[n_tri] = sqrt(sigma (A_f / 3) (|m_12|^2 + |m_23|^2 + |m_31|^2)) with d_c = G_(corner c) - g_f and
+ * m_ab = (d_a + d_b) / 2: sigma times the integral over f of |G_h - g_f|^2 for the piecewise-linear G_h, in watts under the
+ * root.  Per mesh m: mesh_error_out[m] = sum eta_f^2, mesh_power_out[m] = sum sigma A_f |g_f|^2, mesh_max_out[m] = the
+ * largest eta_f and mesh_face_out[m] its face (global index, the lowest on a tie; -1.0 and -1 for a mesh without faces).
+ * The vertex -> faces lists are built on the first call and kept with the plan.  Everything is summed in a fixed order:
+ * two calls give the same bits.  Preconditions and errors as padne_kkt_current_report; n_tri, n_vert and n_mesh must be the
+ * mesh's, else PADNE_E_INVALID. */
+int padne_kkt_error_estimate(padne_ctx *ctx, padne_kkt *plan, int32_t n_cols, int64_t n_tri, int64_t n_vert, int32_t n_mesh,
+                             double *G_out, double *eta_out, double *mesh_error_out, double *mesh_power_out,
+                             double *mesh_max_out, int64_t *mesh_face_out);
 
 /* Row-partitioned runs, optional: attach the rank's owned x owned diagonal block; with precond = 1 the
  * multigrid hierarchy is then built on that block only (block-Jacobi with multigrid blocks, no
@@ -416,6 +430,13 @@ int padne_face_gradient(padne_ctx *ctx, int64_t n_vert, const double *xy_host,
                         int64_t n_mesh, const int64_t *mesh_vertex_offset,
                         const int64_t *mesh_tri_offset, const double *potential_host,
                         double *gx_out_host, double *gy_out_host);
+
+/* padne_kkt_error_estimate for meshes and potentials given from the host (arguments as padne_power_density, at least one
+ * mesh): the same passes, the vertex -> faces lists built for this call alone. */
+int padne_error_estimate(padne_ctx *ctx, int64_t n_vert, const double *xy_host, int64_t n_tri, const int32_t *tri_host,
+                         int64_t n_mesh, const int64_t *mesh_vertex_offset, const int64_t *mesh_tri_offset,
+                         const double *conductance, const double *potential_host, double *G_out, double *eta_out,
+                         double *mesh_error_out, double *mesh_power_out, double *mesh_max_out, int64_t *mesh_face_out);
 
 /* ---- field sampler: the solved fields at points and on rasters --------------------------------
  * No reference counterpart in the solver: the reference's viewer reads out the nearest vertex / nearest face centroid under

@@ -115,6 +115,8 @@ SIGNATURES = {
     "padne_kkt_sensitivity_block": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _PF64, _PF64, _PF64, _PF64]),
     "padne_kkt_current_report": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int32, _PI32, C.c_int32, _PI32, _PF64, _PF64, _PF64,
                                            _PF64, _PI64, _PF64]),
+    "padne_kkt_error_estimate": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int64, C.c_int32, _PF64, _PF64, _PF64, _PF64, _PF64,
+                                           _PI64]),
     "padne_amg_apply": (C.c_int, [_P, _P, _PF64, _PF64]),
     "padne_csr_set_preconditioner_block": (C.c_int, [_P, _P]),
     "padne_amg_level": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(_P)]),
@@ -123,6 +125,8 @@ SIGNATURES = {
     "padne_power_density": (C.c_int, [_P, _I64, _PF64, _I64, _PI32, _I64, _PI64, _PI64, _PF64, _PF64, _PF64]),
     "padne_csr_power_density": (C.c_int, [_P, _P, _PF64, _PF64]),
     "padne_face_gradient": (C.c_int, [_P, _I64, _PF64, _I64, _PI32, _I64, _PI64, _PI64, _PF64, _PF64, _PF64]),
+    "padne_error_estimate": (C.c_int, [_P, _I64, _PF64, _I64, _PI32, _I64, _PI64, _PI64, _PF64, _PF64, _PF64, _PF64, _PF64, _PF64,
+                                       _PF64, _PI64]),
     "padne_sampler_create": (C.c_int, [_P, _I64, _PF64, _I64, _PI32, C.c_int32, _PI64, _PI64, _PI32, _PF64, C.c_int32, _PF64, _I64,
                                        C.POINTER(_P)]),
     "padne_sampler_destroy": (C.c_int, [_P]),
@@ -510,6 +514,28 @@ class Context:
                                              _ptr(gx, _PF64), _ptr(gy, _PF64)))
         return gx, gy
 
+    def error_estimate(self, xy, tri, mesh_vertex_offset, mesh_tri_offset, conductance, potential):
+        """The gradient-recovery error estimate (include/padne_hip.h, ``padne_error_estimate``) of ``potential`` on meshes
+        given as ``power_density`` takes them: (G (n_vert, 2), eta (n_tri,), and per mesh sum eta^2, sum sigma A |g|^2, the
+        largest eta and its face as a global index, -1 for a mesh without faces)."""
+        xy = _f64(xy).reshape(-1, 2)
+        tri = _i32(tri).reshape(-1, 3)
+        mvo, mto, sig, pot = _i64(mesh_vertex_offset), _i64(mesh_tri_offset), _f64(conductance), _f64(potential)
+        n_mesh = sig.shape[0]
+        if mvo.shape[0] != n_mesh + 1 or mto.shape[0] != n_mesh + 1:
+            raise ValueError("the offset tables must have one entry more than there are meshes")
+        if pot.shape[0] < xy.shape[0]:
+            raise ValueError("potential vector shorter than the vertex count")
+        G = np.empty((xy.shape[0], 2), dtype=np.float64)
+        eta = np.empty(tri.shape[0], dtype=np.float64)
+        mesh_error, mesh_power, mesh_max = (np.empty(n_mesh, dtype=np.float64) for _ in range(3))
+        mesh_face = np.empty(n_mesh, dtype=np.int64)
+        _check(self._lib.padne_error_estimate(self._h, xy.shape[0], _ptr(xy, _PF64), tri.shape[0], _ptr(tri, _PI32), n_mesh,
+                                              _ptr(mvo, _PI64), _ptr(mto, _PI64), _ptr(sig, _PF64), _ptr(pot, _PF64),
+                                              _ptr(G, _PF64), _ptr(eta, _PF64), _ptr(mesh_error, _PF64), _ptr(mesh_power, _PF64),
+                                              _ptr(mesh_max, _PF64), _ptr(mesh_face, _PI64)))
+        return G, eta, mesh_error, mesh_power, mesh_max, mesh_face
+
 
 class LocalTeam:
     """In-process team of contexts acting as ranks on one GPU (rehearsal of the multi-rank path)."""
@@ -783,6 +809,22 @@ class KktPlan:
                                                       _ptr(cl, _PI32), _ptr(xy, _PF64), _ptr(J, _PF64), _ptr(mag, _PF64),
                                                       _ptr(mesh_max, _PF64), _ptr(mesh_face, _PI64), _ptr(cuts, _PF64)))
         return J, mag, mesh_max, mesh_face, cuts
+
+    def error_estimate(self, n_cols: int, n_tri: int, n_vert: int, n_mesh: int):
+        """The gradient-recovery error estimate of column 0 of the block the last ``finish_block`` left on the device, over
+        the mesh the system was assembled from (``n_tri`` triangles and ``n_vert`` vertices in ``n_mesh`` meshes).  Returns
+        (G (n_vert, 2) the recovered gradient, eta (n_tri,) the indicators, and per mesh sum eta^2, sum sigma A |g|^2, the
+        largest eta and its face as a global index, -1 for a mesh without faces) (include/padne_hip.h).  The vertex lists
+        are built by the first call and kept with the plan.  Raises ValueError as ``current_report`` does."""
+        n_tri, n_vert, n_mesh = int(n_tri), int(n_vert), int(n_mesh)
+        G = np.empty((n_vert, 2), dtype=np.float64)
+        eta = np.empty(n_tri, dtype=np.float64)
+        mesh_error, mesh_power, mesh_max = (np.empty(n_mesh, dtype=np.float64) for _ in range(3))
+        mesh_face = np.empty(n_mesh, dtype=np.int64)
+        _check(self.ctx._lib.padne_kkt_error_estimate(self.ctx._h, self._h, int(n_cols), n_tri, n_vert, n_mesh, _ptr(G, _PF64),
+                                                      _ptr(eta, _PF64), _ptr(mesh_error, _PF64), _ptr(mesh_power, _PF64),
+                                                      _ptr(mesh_max, _PF64), _ptr(mesh_face, _PI64)))
+        return G, eta, mesh_error, mesh_power, mesh_max, mesh_face
 
     def finish(self, extra_coeff, multipliers: dict):
         """Stage 2: (v, ||L v - r||)."""

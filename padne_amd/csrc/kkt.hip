@@ -33,6 +33,9 @@ int launch_current_faces(padne_ctx *ctx, const padne_csr *m, const long long *ti
 int launch_cut_currents(padne_ctx *ctx, const padne_csr *m, const long long *tile_dev, int n_cols, const double *V_dev,
                         int n_cut, const double *cut_xy_dev, long long n_pairs, const int *pair_cut_dev,
                         const long long *pair_tile_dev, const long long *pair_off_host, double *cut_dev, int *bad_dev);
+int csr_error_estimate(padne_ctx *ctx, const padne_csr *L, int **vptr, int **vface, int n_cols, const double *V_dev,
+                       double *G_dev, double *eta_dev, double *mesh_E_dev, double *mesh_P_dev, double *mesh_max_dev,
+                       long long *mesh_face_dev, int *bad_dev);
 void amg_info(const padne_csr *A0, int *levels, double *complexity, double *setup_seconds, long long *coarse_n);
 
 constexpr int kCopyStreams = 4;
@@ -68,6 +71,9 @@ struct padne_kkt {
     const double *v_final = nullptr;
     int finished_cols = 0;
     double setup_seconds_last = 0.0;
+    // vertex -> incident faces of L's mesh, rows in ascending face order (error.hip): built by the first
+    // padne_kkt_error_estimate and kept, [mesh_n_vert + 1] and [3 mesh_n_tri]
+    int *err_vptr = nullptr, *err_vface = nullptr;
 };
 
 namespace padne {
@@ -539,7 +545,8 @@ static void kkt_free(padne_kkt *k) {
     if (k->A != nullptr) padne_csr_destroy(k->A);
     for (void *p : {(void *)k->imap, (void *)k->src_of, (void *)k->tied_member, (void *)k->tied_target, (void *)k->tied_order,
                     (void *)k->tied_gptr, (void *)k->r, (void *)k->v,
-                    (void *)k->w, (void *)k->c, (void *)k->b, (void *)k->y, (void *)k->Z})
+                    (void *)k->w, (void *)k->c, (void *)k->b, (void *)k->y, (void *)k->Z, (void *)k->err_vptr,
+                    (void *)k->err_vface})
         if (p != nullptr) pool_free(ctx, p);
     delete k;
 }
@@ -1328,4 +1335,55 @@ extern "C" int padne_kkt_current_report(padne_ctx *ctx, padne_kkt *k, int32_t n_
     if (n_tri == 0) return PADNE_OK;
     PADNE_TRY(parallel_copy(k, J_out, d_J, sizeof(double) * 2 * (size_t)n_tri, hipMemcpyDeviceToHost));
     return parallel_copy(k, mag_out, d_mag, sizeof(double) * (size_t)n_tri, hipMemcpyDeviceToHost);
+}
+
+// The gradient-recovery error estimate of column 0 of the finished block (error.hip; DESIGN.md, "Error estimate"): the
+// vertex -> faces lists of L's mesh are built on the first call and stay with the plan, then three passes over the mesh and
+// one fold per mesh.  No floating-point atomics: two calls give the same bits.  Only the results cross PCIe.
+extern "C" int padne_kkt_error_estimate(padne_ctx *ctx, padne_kkt *k, int32_t n_cols, int64_t n_tri, int64_t n_vert, int32_t n_mesh,
+                                        double *G_out, double *eta_out, double *mesh_error_out, double *mesh_power_out,
+                                        double *mesh_max_out, int64_t *mesh_face_out) {
+    PADNE_REQUIRE(ctx && k, "null argument");
+    PADNE_REQUIRE(k->ctx == ctx, "the plan belongs to another context");
+    PADNE_REQUIRE(k->finished && k->v_final != nullptr,
+                  "padne_kkt_error_estimate follows padne_kkt_finish_block, with no solve on the plan in between");
+    PADNE_REQUIRE(n_cols == k->finished_cols, "as many columns as the finished block has");
+    PADNE_REQUIRE(mesh_error_out && mesh_power_out && mesh_max_out && mesh_face_out, "null argument");
+    const padne_csr *L = k->L;
+    PADNE_REQUIRE(L->mesh_n_mesh > 0 && L->mesh_xy != nullptr,
+                  "the system matrix does not carry a mesh (only padne_assemble_system keeps it)");
+    PADNE_REQUIRE(L->mesh_n_vert <= k->N, "the mesh has more vertices than the system has unknowns");
+    PADNE_REQUIRE(n_tri == L->mesh_n_tri && n_vert == L->mesh_n_vert && n_mesh == L->mesh_n_mesh,
+                  "n_tri, n_vert and n_mesh must be those of the system's mesh");
+    PADNE_REQUIRE((n_tri == 0 || eta_out) && (n_vert == 0 || G_out), "null argument");
+    PADNE_HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const size_t nt = (size_t)(n_tri > 0 ? n_tri : 1), nv = (size_t)(n_vert > 0 ? n_vert : 1);
+    Scratch sc(ctx);
+    double *d_G = nullptr, *d_eta = nullptr, *d_E = nullptr, *d_P = nullptr, *d_max = nullptr;
+    long long *d_face = nullptr;
+    int *d_bad = nullptr;
+    PADNE_TRY(sc.alloc(&d_G, 2 * nv));
+    PADNE_TRY(sc.alloc(&d_eta, nt));
+    PADNE_TRY(sc.alloc(&d_E, (size_t)n_mesh));
+    PADNE_TRY(sc.alloc(&d_P, (size_t)n_mesh));
+    PADNE_TRY(sc.alloc(&d_max, (size_t)n_mesh));
+    PADNE_TRY(sc.alloc(&d_face, (size_t)n_mesh));
+    PADNE_TRY(sc.alloc(&d_bad, 1));
+    PADNE_HIP_CHECK(hipMemsetAsync(d_bad, 0, sizeof(int), s));
+    PADNE_TRY(csr_error_estimate(ctx, L, &k->err_vptr, &k->err_vface, n_cols, k->v_final, d_G, d_eta, d_E, d_P, d_max, d_face, d_bad));
+    int h_bad = 0;
+    PADNE_HIP_CHECK(hipMemcpyAsync(&h_bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    PADNE_HIP_CHECK(hipMemcpyAsync(mesh_error_out, d_E, sizeof(double) * (size_t)n_mesh, hipMemcpyDeviceToHost, s));
+    PADNE_HIP_CHECK(hipMemcpyAsync(mesh_power_out, d_P, sizeof(double) * (size_t)n_mesh, hipMemcpyDeviceToHost, s));
+    PADNE_HIP_CHECK(hipMemcpyAsync(mesh_max_out, d_max, sizeof(double) * (size_t)n_mesh, hipMemcpyDeviceToHost, s));
+    PADNE_HIP_CHECK(hipMemcpyAsync(mesh_face_out, d_face, sizeof(long long) * (size_t)n_mesh, hipMemcpyDeviceToHost, s));
+    PADNE_HIP_CHECK(hipStreamSynchronize(s));
+    if (h_bad) {
+        set_error("invalid argument: triangle index out of range");
+        return PADNE_E_INVALID;
+    }
+    if (n_vert > 0) PADNE_TRY(parallel_copy(k, G_out, d_G, sizeof(double) * 2 * (size_t)n_vert, hipMemcpyDeviceToHost));
+    if (n_tri > 0) PADNE_TRY(parallel_copy(k, eta_out, d_eta, sizeof(double) * (size_t)n_tri, hipMemcpyDeviceToHost));
+    return PADNE_OK;
 }

@@ -22,6 +22,8 @@ compute_power_density :728-745         ``power_density_kernel``
                                        regulators, ``sensitivity_block_kernel`` over the faces
 (where the current goes)               ``solve_currents``: the load-case block with one column, ``current_face_kernel``
                                        and ``cut_current_kernel`` over the faces, element flows from V's rows
+(how far the mesh is from the board)   ``solve_error``: the same block, gradient recovery through vertex -> faces lists
+                                       (``error_recover_kernel``) and ``error_indicator_kernel`` over the faces
 read-out under the cursor ui.py:192    ``FieldSampler``: owner face by ``sample_kernel`` over a grid of bins per layer,
                                        V interpolated in the face, J and p of the face
 =====================================  ====================================================
@@ -745,6 +747,15 @@ def ctx_face_gradient(ctx, xy, tri, pot):
     one = np.array([0, len(xy)], dtype=np.int64)
     onet = np.array([0, len(tri)], dtype=np.int64)
     return ctx.face_gradient(xy, tri, one, onet, pot)
+
+
+def ctx_error_estimate(ctx, xy, tri, conductance: float, pot):
+    """The gradient-recovery error estimate of ``pot`` on one mesh of sheet conductance ``conductance``
+    (``Context.error_estimate``): (G, eta, sum eta^2, sum sigma A |g|^2, the largest eta, its face)."""
+    one = np.array([0, len(xy)], dtype=np.int64)
+    onet = np.array([0, len(tri)], dtype=np.int64)
+    G, eta, E, P, top, face = ctx.error_estimate(xy, tri, one, onet, [conductance], pot)
+    return G, eta, float(E[0]), float(P[0]), float(top[0]), int(face[0])
 
 
 def compute_power_density(voltage: mesh.ZeroForm, conductivity: float) -> mesh.TwoForm:
@@ -1672,6 +1683,175 @@ def solve_currents(prob, cuts=(), mesher_config: Optional[mesh.Mesher.Config] = 
     meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
     return solve_meshed_currents(prob, meshes, mesh_index_to_layer_index,
                                  [Cut(prob.layers[i], a, b) for i, a, b in cuts])
+
+
+# --------------------------------------------------------------------------------------------
+# error estimate: how far the discrete answer is from the board, per face
+# --------------------------------------------------------------------------------------------
+
+
+@dataclass
+class ErrorReport:
+    """The estimated discretisation error of a solved Problem (see :func:`solve_meshed_error`)."""
+    recovered: list       # per layer, per mesh of LayerSolution.meshes: (n_vert, 2) J* = -sigma G, the recovered J [A/mm]
+    indicators: list      # per layer, per mesh: TwoForm of eta_f [sqrt(W)]
+    worst: list           # per layer: (max eta, mesh index within the layer, face index, centroid x, y), None without faces
+    layers: list          # per layer: (sum eta_f^2, sum sigma A_f |g_f|^2) [W]
+    power_error: float    # sum of eta_f^2 over all faces [W]
+    estimate: float       # sqrt(power_error / (power + power_error)): the estimated relative error in the energy norm
+    ratios: Optional[list] = None     # with a tolerance: per layer, per mesh (n_faces,) xi_f = eta_f / e_bar; above 1: refine
+    sizes: Optional[list] = None      # with a tolerance: per layer, per mesh (n_faces,) suggested size h_f / xi_f [mm]
+    tolerance: Optional[float] = None
+
+
+def check_tolerance(tolerance) -> Optional[float]:
+    """``tolerance`` as a float, None for None, or ValueError: a finite number strictly between 0 and 1 (a relative error
+    in the energy norm); no bool and no string."""
+    if tolerance is None:
+        return None
+    if isinstance(tolerance, (bool, np.bool_, str, bytes)):
+        raise ValueError("tolerance must be a number in (0, 1)")
+    try:
+        value = float(tolerance)
+    except (TypeError, ValueError):
+        raise ValueError("tolerance must be a number in (0, 1)") from None
+    if not (math.isfinite(value) and 0.0 < value < 1.0):
+        raise ValueError(f"tolerance must be a finite number in (0, 1), not {tolerance!r}")
+    return value
+
+
+def error_estimate_of(mesh_error, mesh_power) -> tuple:
+    """(power_error, estimate) from the per-mesh sums E_m and P_m of the connected meshes: power_error = sum E_m and
+    estimate = sqrt(power_error / (sum P_m + power_error)), 0.0 when the denominator is 0."""
+    power_error = float(np.sum(np.asarray(mesh_error, dtype=DTYPE)))
+    total = float(np.sum(np.asarray(mesh_power, dtype=DTYPE))) + power_error
+    return power_error, (math.sqrt(power_error / total) if total > 0.0 else 0.0)
+
+
+def face_sizes(points, triangles) -> np.ndarray:
+    """h_f = sqrt(4 A_f / sqrt(3)) of every face: the edge of the equilateral triangle of the face's area, with A_f as the
+    device forms it (corners (tri[2], tri[0], tri[1]))."""
+    p, t = np.asarray(points, dtype=DTYPE).reshape(-1, 2), np.asarray(triangles).reshape(-1, 3)
+    a, b, c = p[t[:, 2]], p[t[:, 0]], p[t[:, 1]]
+    area = np.abs((b[:, 0] - a[:, 0]) * (c[:, 1] - a[:, 1]) - (b[:, 1] - a[:, 1]) * (c[:, 0] - a[:, 0])) / 2
+    return np.sqrt(4 * area / math.sqrt(3.0))
+
+
+def refinement_ratios(eta, h, total_power: float, n_faces: int, tolerance: float) -> tuple:
+    """(xi_f, suggested size) of the faces with indicators ``eta`` and sizes ``h`` (:func:`face_sizes`): the permissible
+    error per face is e_bar = tolerance sqrt(total_power / n_faces) with total_power = sum P_m + power_error and n_faces
+    the faces of all connected meshes; xi_f = eta_f / e_bar and the size h_f / xi_f (linear elements: the error falls
+    with h at rate 1), inf where xi_f = 0.  A board without power (e_bar = 0) has xi = 0 everywhere."""
+    eta, h = np.asarray(eta, dtype=DTYPE), np.asarray(h, dtype=DTYPE)
+    e_bar = tolerance * math.sqrt(total_power / n_faces) if n_faces > 0 and total_power > 0.0 else 0.0
+    xi = eta / e_bar if e_bar > 0.0 else np.zeros_like(eta)
+    sizes = np.full(eta.shape, np.inf, dtype=DTYPE)
+    np.divide(h, xi, out=sizes, where=xi > 0)
+    return xi, sizes
+
+
+def solve_meshed_error(prob, meshes, mesh_index_to_layer_index, *, tolerance=None, filtered_networks=None,
+                       disconnected_meshes_by_layer=None, partition=None, timings: Optional[dict] = None):
+    """``solve_meshed`` together with an estimate of how far its answer is from the board: (Solution, ErrorReport).
+
+    A gradient-recovery (Zienkiewicz-Zhu) estimator on the solved potentials.  Per connected mesh with sheet conductance
+    sigma, with g_f the face gradient of the power density and A_f the face's area:
+
+    - ``recovered``: J* = -sigma G at every vertex, G_v = (sum A_f g_f) / (sum A_f) over the faces incident to v, added in
+      ascending face order; 0 for a vertex without faces.  Boundary vertices get no special treatment, and nothing is
+      averaged across meshes or layers;
+    - ``indicators``: eta_f = sqrt(sigma (A_f / 3) (|m_12|^2 + |m_23|^2 + |m_31|^2)) with d_c = G_(corner c) - g_f and
+      m_ab = (d_a + d_b) / 2: sigma times the exact integral over the face of |G_h - g_f|^2 for the piecewise-linear G_h;
+      eta_f^2 is in watts;
+    - ``worst``: per layer the largest eta_f (the lowest global face on a tie), its mesh within the layer, its face and the
+      face's centroid;
+    - ``layers``: per layer (E, P) = (sum eta_f^2, sum sigma A_f |g_f|^2).  P is the gradient form of the power, not the
+      |cot|/2 weights' form of ``CurrentReport.layers``: the estimator measures the distance between two gradients;
+    - ``power_error`` = sum E and ``estimate`` = sqrt(power_error / (sum P + power_error)), the estimated relative error in
+      the energy norm (0.0 for a board without power);
+    - with a ``tolerance`` (relative, in (0, 1)): ``ratios`` xi_f = eta_f / e_bar with the permissible error per face
+      e_bar = tolerance sqrt((sum P + power_error) / n_faces) (above 1: refine here), and ``sizes`` h_f / xi_f with
+      h_f = sqrt(4 A_f / sqrt(3)), the edge of the equilateral triangle of the face's area (inf where xi_f = 0).  How a
+      mesher's own size measure (``Mesher.Config.maximum_size``, a circumradius bound, ...) maps onto h_f is the
+      integrator's business.
+
+    Disconnected meshes carry no current: they are not among ``LayerSolution.meshes``, have no entries here and do not
+    count in n_faces.  What the estimator does not see: connections snap to single vertices, where the exact solution is
+    logarithmically singular, so the faces around terminals stay flagged however fine the mesh; and the consistency error
+    of the assembly's |cot| weights on obtuse faces is not a gradient jump and is not measured.
+
+    One call is the load-case block path with one column; the estimator's kernels run on the V the device holds, through
+    vertex -> faces lists built once per plan, with every sum in a fixed order: two calls give the same bits.  The Solution
+    is that of ``prob``, with the bits ``solve_meshed_currents`` gives it; its power densities come from
+    ``padne_kkt_power_density_block`` (there: from the sensitivity kernel, which writes the same bits).  A degenerate face
+    (zero area) has no finite gradient: its three vertices recover NaN, as its power density is NaN.  ValueError, before anything reaches the device, for
+    an invalid tolerance (:func:`check_tolerance`) and for a ``partition`` over several GPUs.  ``timings`` (a dict)
+    receives the host time of each step in seconds; ``"error"`` is the estimator's."""
+    _refuse_partition(partition, "error estimates")
+    tolerance = check_tolerance(tolerance)
+    laps = _Laps(timings)
+    board = index_board(prob, meshes, mesh_index_to_layer_index, filtered_networks, disconnected_meshes_by_layer)
+    laps.lap("indexing")
+    with board.assembled() as (L, _):
+        rows, cols, vals = stamp_load_cases(board.filtered_networks, board.node_indexer, L.shape[0], [{}])
+        laps.lap("assembly")
+        log.info("Solving the Problem and estimating its error")
+        plan, V, residual_norms, res, n_tri, n_mesh = _solve_block_on_device(L, rows, cols, vals, 1, 1, laps)
+        power = G = eta = mesh_error = mesh_power = mesh_max = mesh_face = None
+        if n_tri:
+            power = plan.power_density_block(1, n_tri)[0]
+            laps.lap("power")
+            G, eta, mesh_error, mesh_power, mesh_max, mesh_face = plan.error_estimate(1, n_tri, len(board.vindex), n_mesh)
+        laps.lap("error")
+    log.info("Producing the solution and the error report")
+    _warn_if_block_stalled(res, residual_norms, cols, vals, 1)
+    solution = _column_solution(board, prob, np.ascontiguousarray(V[:, 0]), residual_norms[0], res, power)
+    power_error, estimate = error_estimate_of(mesh_error, mesh_power) if eta is not None else (0.0, 0.0)
+    total_power = (float(np.sum(mesh_power)) + power_error) if eta is not None else 0.0
+    voff = board.vindex.offsets
+    recovered, indicators, worst, layer_sums = [], [], [], []
+    ratios, sizes = ([], []) if tolerance is not None else (None, None)
+    for layer_i, layer in enumerate(prob.layers):
+        vecs, forms, xis, hs, E, P, best = [], [], [], [], 0.0, 0.0, None
+        for mesh_i, msh, lo, hi in board.layer_meshes(layer_i):
+            tf = mesh.TwoForm(msh)
+            if eta is not None:
+                vecs.append(-layer.conductance * G[voff[mesh_i]:voff[mesh_i + 1]])
+                tf.values = eta[lo:hi]                    # views of this call's own result array: no copies
+                E += float(mesh_error[mesh_i])
+                P += float(mesh_power[mesh_i])
+                # meshes come in global face order: a later mesh wins only with a strictly larger eta
+                if mesh_face[mesh_i] >= 0 and (best is None or mesh_max[mesh_i] > best[0]):
+                    face = int(mesh_face[mesh_i] - lo)
+                    cx, cy = msh.points[msh.triangles[face]].mean(axis=0)
+                    best = (float(mesh_max[mesh_i]), len(forms), face, float(cx), float(cy))
+            else:
+                vecs.append(np.zeros((len(msh.points), 2), dtype=DTYPE))
+            if tolerance is not None:
+                xi, size = refinement_ratios(tf.values, face_sizes(msh.points, msh.triangles), total_power, n_tri, tolerance)
+                xis.append(xi)
+                hs.append(size)
+            forms.append(tf)
+        recovered.append(vecs)
+        indicators.append(forms)
+        worst.append(best)
+        layer_sums.append((E, P))
+        if tolerance is not None:
+            ratios.append(xis)
+            sizes.append(hs)
+    report = ErrorReport(recovered=recovered, indicators=indicators, worst=worst, layers=layer_sums, power_error=power_error,
+                         estimate=estimate, ratios=ratios, sizes=sizes, tolerance=tolerance)
+    laps.lap("solutions")
+    return solution, report
+
+
+def solve_error(prob, mesher_config: Optional[mesh.Mesher.Config] = None, *, tolerance=None, mesher=None, partition=None):
+    """``solve`` with the error estimate of :func:`solve_meshed_error`: the board is meshed once.  Returns
+    (Solution, ErrorReport)."""
+    _refuse_partition(partition, "error estimates")
+    tolerance = check_tolerance(tolerance)
+    meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
+    return solve_meshed_error(prob, meshes, mesh_index_to_layer_index, tolerance=tolerance)
 
 
 # --------------------------------------------------------------------------------------------
