@@ -47,6 +47,7 @@ extern "C" {
 typedef struct padne_ctx padne_ctx;   /* device, stream, workspaces, optional RCCL communicator */
 typedef struct padne_csr padne_csr;   /* device-resident CSR matrix (f64 values, i32 indices)  */
 typedef struct padne_kkt padne_kkt;   /* device-resident plan of solve_system for one assembled system */
+typedef struct padne_refine padne_refine;     /* device-resident result of one refinement round */
 typedef struct padne_sampler padne_sampler;   /* device-resident meshes, potentials and point-location index of a solved board */
 
 /* ---- library / context ------------------------------------------------------------------- */
@@ -437,6 +438,33 @@ int padne_error_estimate(padne_ctx *ctx, int64_t n_vert, const double *xy_host, 
                          int64_t n_mesh, const int64_t *mesh_vertex_offset, const int64_t *mesh_tri_offset,
                          const double *conductance, const double *potential_host, double *G_out, double *eta_out,
                          double *mesh_error_out, double *mesh_power_out, double *mesh_max_out, int64_t *mesh_face_out);
+
+/* ---- refinement: conforming refined meshes from one flag per face -----------------------------
+ * No reference counterpart.  4-triangle longest-edge refinement with conforming closure ("Refinement") of a batch
+ * of meshes given as padne_power_density takes them, flag_host[n_tri] != 0 for the faces to refine.  Edges are the distinct
+ * keys lo * n_vert + hi over the global vertex numbers of the corners (tri[f][c], tri[f][(c + 1) % 3]), numbered in
+ * ascending key order; d_e = dx * dx + dy * dy from lo to hi; a face's longest edge has the greatest d_e, the lowest edge
+ * number on a tie.  Every edge of a flagged face is marked, then the longest edge of every face with a marked edge, until
+ * nothing changes.  One new vertex 0.5 * (p[lo] + p[hi]) per marked edge, behind the old vertices of its mesh in ascending
+ * edge number; old vertices keep index and coordinates.  With the face rotated so that its longest edge is (a, b), c
+ * opposite, m, p, q the midpoints of ab, bc, ca: an unmarked face is copied; otherwise (a, m, q), (q, m, c) if ca is marked
+ * else (a, m, c), then (m, b, p), (m, p, c) if bc is marked else (m, b, c).  Children lie in parent order.
+ * The sizes of the result are known only afterwards, so it stays on the device behind a handle (destroyed before its
+ * context): new_vertex_count_out[n_mesh] and new_face_count_out[n_mesh] size the arrays of padne_refine_fetch;
+ * counts_out[4] (may be null) = edges of the batch, edges marked by the flags, edges marked after the closure, closure
+ * sweeps queued.  PADNE_E_INVALID for a triangle index out of range and a face that names a vertex twice,
+ * PADNE_E_NONMANIFOLD for an edge with more than two faces or with two faces that run it in the same direction.  Two calls
+ * give the same bits. */
+int padne_refine_create(padne_ctx *ctx, int64_t n_vert, const double *xy_host, int64_t n_tri, const int32_t *tri_host,
+                        int64_t n_mesh, const int64_t *mesh_vertex_offset, const int64_t *mesh_tri_offset,
+                        const uint8_t *flag_host, int64_t *new_vertex_count_out, int64_t *new_face_count_out,
+                        int64_t *counts_out, padne_refine **out);
+/* xy_out[sum of the vertex counts][2]; tri_out[sum of the face counts][3] and parent_out[...] with mesh-local vertex and
+ * parent-face indices; ends_out[new vertices][2] the mesh-local (lo, hi) ends of the edge every new vertex halves, mesh by
+ * mesh in the order of the new vertices. */
+int padne_refine_fetch(padne_ctx *ctx, const padne_refine *r, double *xy_out, int32_t *tri_out, int32_t *parent_out,
+                       int32_t *ends_out);
+int padne_refine_destroy(padne_refine *r);     /* NULL is accepted */
 
 /* ---- field sampler: the solved fields at points and on rasters --------------------------------
  * No reference counterpart in the solver: the reference's viewer reads out the nearest vertex / nearest face centroid under

@@ -127,6 +127,10 @@ SIGNATURES = {
     "padne_face_gradient": (C.c_int, [_P, _I64, _PF64, _I64, _PI32, _I64, _PI64, _PI64, _PF64, _PF64, _PF64]),
     "padne_error_estimate": (C.c_int, [_P, _I64, _PF64, _I64, _PI32, _I64, _PI64, _PI64, _PF64, _PF64, _PF64, _PF64, _PF64, _PF64,
                                        _PF64, _PI64]),
+    "padne_refine_create": (C.c_int, [_P, _I64, _PF64, _I64, _PI32, _I64, _PI64, _PI64, C.POINTER(C.c_uint8), _PI64, _PI64, _PI64,
+                                      C.POINTER(_P)]),
+    "padne_refine_fetch": (C.c_int, [_P, _P, _PF64, _PI32, _PI32, _PI32]),
+    "padne_refine_destroy": (C.c_int, [_P]),
     "padne_sampler_create": (C.c_int, [_P, _I64, _PF64, _I64, _PI32, C.c_int32, _PI64, _PI64, _PI32, _PF64, C.c_int32, _PF64, _I64,
                                        C.POINTER(_P)]),
     "padne_sampler_destroy": (C.c_int, [_P]),
@@ -915,6 +919,38 @@ class Sampler:
         return {"bins_x": int(counts[0]), "bins_y": int(counts[1]), "entries": int(counts[2]), "faces": int(counts[3]),
                 "last_candidates": int(counts[4]), "last_queries": int(counts[5]), "upload_seconds": float(secs[0]),
                 "build_seconds": float(secs[1]), "last_kernel_seconds": float(secs[2])}
+
+
+def refine(ctx: "Context", xy, tri, mesh_vertex_offset, mesh_tri_offset, flags):
+    """One refinement round (include/padne_hip.h, ``padne_refine_create`` / ``_fetch`` / ``_destroy``) of meshes given as
+    ``power_density`` takes them, ``flags`` one uint8 per face.  Returns (xy (n, 2), tri (k, 3) and parent (k,) with
+    mesh-local indices, ends (n_new, 2) mesh-local, vertex counts and face counts per mesh, and the counts dict: edges,
+    edges marked by the flags, edges marked after the closure, closure sweeps queued)."""
+    xy, tri = _f64(xy).reshape(-1, 2), _i32(tri).reshape(-1, 3)
+    mvo, mto = _i64(mesh_vertex_offset), _i64(mesh_tri_offset)
+    flag = np.ascontiguousarray(flags, dtype=np.uint8).reshape(-1)
+    n_mesh = mvo.shape[0] - 1
+    if n_mesh < 1 or mto.shape[0] != n_mesh + 1:
+        raise ValueError("the offset tables must have one entry more than there are meshes, and there is at least one mesh")
+    if flag.shape[0] != tri.shape[0]:
+        raise ValueError("one flag per face")
+    n_vert_out, n_tri_out = np.zeros(n_mesh, dtype=np.int64), np.zeros(n_mesh, dtype=np.int64)
+    counts = np.zeros(4, dtype=np.int64)
+    h = _P()
+    _check(ctx._lib.padne_refine_create(ctx._h, xy.shape[0], _ptr(xy, _PF64), tri.shape[0], _ptr(tri, _PI32), n_mesh,
+                                        _ptr(mvo, _PI64), _ptr(mto, _PI64), _ptr(flag, C.POINTER(C.c_uint8)),
+                                        _ptr(n_vert_out, _PI64), _ptr(n_tri_out, _PI64), _ptr(counts, _PI64), C.byref(h)))
+    try:
+        nv, nt = int(n_vert_out.sum()), int(n_tri_out.sum())
+        xy_out = np.empty((nv, 2), dtype=np.float64)
+        tri_out, parent = np.empty((nt, 3), dtype=np.int32), np.empty(nt, dtype=np.int32)
+        ends = np.empty((nv - xy.shape[0], 2), dtype=np.int32)
+        _check(ctx._lib.padne_refine_fetch(ctx._h, h, _ptr(xy_out, _PF64), _ptr(tri_out, _PI32), _ptr(parent, _PI32),
+                                           _ptr(ends, _PI32)))
+    finally:
+        ctx._lib.padne_refine_destroy(h)
+    return xy_out, tri_out, parent, ends, n_vert_out, n_tri_out, {
+        "edges": int(counts[0]), "marked_by_flags": int(counts[1]), "marked": int(counts[2]), "sweeps": int(counts[3])}
 
 
 class CsrMatrix:

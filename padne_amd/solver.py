@@ -24,6 +24,8 @@ compute_power_density :728-745         ``power_density_kernel``
                                        and ``cut_current_kernel`` over the faces, element flows from V's rows
 (how far the mesh is from the board)   ``solve_error``: the same block, gradient recovery through vertex -> faces lists
                                        (``error_recover_kernel``) and ``error_indicator_kernel`` over the faces
+(a finer mesh where that asks)         ``refine_meshes`` / ``solve_adaptive``: longest-edge refinement with conforming
+                                       closure, edges by a sort of corner keys, ``refine_emit_kernel`` over the faces
 read-out under the cursor ui.py:192    ``FieldSampler``: owner face by ``sample_kernel`` over a grid of bins per layer,
                                        V interpolated in the face, J and p of the face
 =====================================  ====================================================
@@ -1852,6 +1854,193 @@ def solve_error(prob, mesher_config: Optional[mesh.Mesher.Config] = None, *, tol
     tolerance = check_tolerance(tolerance)
     meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
     return solve_meshed_error(prob, meshes, mesh_index_to_layer_index, tolerance=tolerance)
+
+
+# --------------------------------------------------------------------------------------------
+# refinement: act on the error estimate
+# --------------------------------------------------------------------------------------------
+
+
+@dataclass
+class Refinement:
+    """One refinement round of a list of meshes (see :func:`refine_meshes`)."""
+    meshes: list             # the refined meshes, mesh.Mesh: old vertices first (same index, same coordinates), then the new
+    parents: list            # per mesh (n_faces,) int32: the face of the input mesh every face came from
+    midpoint_ends: list      # per mesh (n_new, 2) int32: the (lo, hi) ends of the edge every new vertex halves
+    edges: int = 0           # edges of all meshes
+    marked_by_flags: int = 0     # edges of the flagged faces
+    marked: int = 0          # edges halved: those, and what the conforming closure added
+    sweeps: int = 0          # closure sweeps the device queued
+
+
+def check_refine_flags(meshes, flags) -> list:
+    """``flags`` as one contiguous boolean array per mesh, or ValueError: a list of the meshes' length, each entry a boolean
+    array with one entry per face."""
+    try:
+        flags = list(flags)
+    except TypeError:
+        raise ValueError("flags must have one array per mesh: a list of boolean arrays") from None
+    if len(flags) != len(meshes):
+        raise ValueError(f"flags must have one array per mesh: {len(flags)} arrays for {len(meshes)} meshes")
+    out = []
+    for i, (msh, f) in enumerate(zip(meshes, flags)):
+        f = np.asarray(f)
+        if f.dtype != np.bool_:
+            raise ValueError(f"the flags of mesh {i} must be a boolean array, not {f.dtype}")
+        if f.ndim != 1 or f.shape[0] != len(msh.triangles):
+            raise ValueError(f"the flags of mesh {i} must have one entry per face: shape {f.shape} for {len(msh.triangles)} faces")
+        out.append(np.ascontiguousarray(f))
+    return out
+
+
+def refine_meshes(meshes, flags) -> Refinement:
+    """Conforming refined meshes from one flag per face: 4-triangle longest-edge refinement with conforming closure
+    ("Refinement"), on the device, all meshes in one batch.
+
+    A flagged face is cut into four through the midpoints of its edges, its longest edge first; a face that shares a
+    halved edge is cut into two or three, again longest edge first, so that no vertex is left hanging on an edge -- which
+    may halve further edges (the closure).  The smallest angle of a descendant is at least half that of its ancestor.
+    Old vertices keep their index and coordinates (a terminal that sat on a vertex still does), new vertices follow them
+    in ascending edge number, children lie in the order of their parents and keep the parents' winding.  Edges stay
+    straight: a new vertex on a curved outline is not moved onto it, the copper's area is unchanged.  A mesh without
+    faces passes through.  Two calls give the same bits.
+
+    ``meshes``: mesh.Mesh objects (or the reference's); ``flags``: one boolean array per mesh, one entry per face.
+    ValueError, before anything reaches the device, for a flags list of the wrong length, an array of the wrong size or
+    one that is not boolean; from the device for a non-manifold mesh and a triangle index out of range."""
+    meshes = [m if isinstance(m, mesh.Mesh) else mesh.Mesh.from_reference(m) for m in meshes]
+    flags = check_refine_flags(meshes, flags)
+    if sum(len(m.triangles) for m in meshes) == 0:
+        return Refinement([mesh.Mesh(m.points.copy(), m.triangles.copy()) for m in meshes],
+                          [np.zeros(0, dtype=np.int32) for _ in meshes], [np.zeros((0, 2), dtype=np.int32) for _ in meshes])
+    xy, tri = _flatten_points_triangles(meshes)
+    voff, toff = _offsets([len(m.points) for m in meshes]), _offsets([len(m.triangles) for m in meshes])
+    xy_out, tri_out, parent, ends, nv, nt, counts = _hip.refine(get_context(), xy, tri, voff, toff,
+                                                                 np.concatenate(flags).astype(np.uint8))
+    v1, t1 = _offsets(nv), _offsets(nt)
+    e1 = _offsets([int(n) - len(m.points) for n, m in zip(nv, meshes)])
+    return Refinement(meshes=[mesh.Mesh(xy_out[v1[i]:v1[i + 1]], tri_out[t1[i]:t1[i + 1]]) for i in range(len(meshes))],
+                      parents=[parent[t1[i]:t1[i + 1]] for i in range(len(meshes))],
+                      midpoint_ends=[ends[e1[i]:e1[i + 1]] for i in range(len(meshes))], **counts)
+
+
+def _flatten_points_triangles(meshes):
+    xy = np.concatenate([m.points for m in meshes]) if meshes else np.zeros((0, 2), dtype=DTYPE)
+    tri = np.concatenate([m.triangles for m in meshes]) if meshes else np.zeros((0, 3), dtype=np.int32)
+    return np.ascontiguousarray(xy, dtype=DTYPE), np.ascontiguousarray(tri, dtype=np.int32)
+
+
+@dataclass
+class AdaptiveHistory:
+    """What :func:`solve_meshed_adaptive` did, one entry per solve."""
+    faces: list = field(default_factory=list)            # faces of the connected meshes solved
+    vertices: list = field(default_factory=list)         # their vertices
+    estimates: list = field(default_factory=list)        # ErrorReport.estimate
+    flagged: list = field(default_factory=list)          # faces flagged after the solve (0 where the loop stopped before flagging)
+    closure_edges: list = field(default_factory=list)    # edges the conforming closure halved beyond those of the flagged faces
+    reason: str = ""                                     # "tolerance", "floor", "rounds" or "faces"
+    meshes: list = field(default_factory=list)           # the meshes of the last solve
+
+
+def check_adaptive_arguments(tolerance, max_rounds, max_faces, min_size) -> tuple:
+    """(tolerance, max_rounds, max_faces, min_size) checked, or ValueError: a tolerance as :func:`check_tolerance` wants it
+    and not None, max_rounds an integer >= 1, max_faces None or an integer >= 1, min_size a finite number >= 0."""
+    tolerance = check_tolerance(tolerance)
+    if tolerance is None:
+        raise ValueError("tolerance must be a number in (0, 1): an adaptive solve needs one")
+    for name, value, optional in (("max_rounds", max_rounds, False), ("max_faces", max_faces, True)):
+        if value is None and optional:
+            continue
+        if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or value < 1:
+            raise ValueError(f"{name} must be an integer >= 1, not {value!r}")
+    if isinstance(min_size, (bool, np.bool_, str, bytes)):
+        raise ValueError("min_size must be a finite number >= 0")
+    try:
+        min_size = float(min_size)
+    except (TypeError, ValueError):
+        raise ValueError("min_size must be a finite number >= 0") from None
+    if not (math.isfinite(min_size) and min_size >= 0.0):
+        raise ValueError(f"min_size must be a finite number >= 0, not {min_size!r}")
+    return tolerance, int(max_rounds), None if max_faces is None else int(max_faces), min_size
+
+
+def solve_meshed_adaptive(prob, meshes, mesh_index_to_layer_index, *, tolerance, max_rounds=8, max_faces=None, min_size=0.0,
+                          filtered_networks=None, disconnected_meshes_by_layer=None, partition=None,
+                          timings: Optional[dict] = None):
+    """Solve, estimate, flag, refine, until the estimate meets ``tolerance``: (Solution, ErrorReport, AdaptiveHistory).
+
+    Every round calls :func:`solve_meshed_error` with ``tolerance`` and stops with ``history.reason``
+
+    - ``"tolerance"`` when ``report.estimate <= tolerance``;
+    - ``"floor"`` when no face has xi_f > 1 and h_f > ``min_size`` (h_f of :func:`face_sizes`, in mm);
+    - ``"rounds"`` after ``max_rounds`` solves;
+    - ``"faces"`` when the refined meshes would have more than ``max_faces`` faces: they are discarded.
+
+    Otherwise the flagged faces are refined (:func:`refine_meshes`, all connected meshes in one batch) and the loop goes
+    round again.  Disconnected meshes are never touched.  The Solution and the ErrorReport are those of the last solve,
+    the bits ``solve_meshed_error`` gives on ``history.meshes``.  Terminals are point singularities whose faces stay
+    flagged however fine the mesh (see :func:`solve_meshed_error`): without ``min_size`` or a budget only ``max_rounds``
+    ends the loop on a board whose tolerance is out of reach.  Every solve starts from zero: nothing is interpolated from
+    the round before.  New vertices are numbered behind the old ones of their mesh, which scatters the rows of
+    neighbours; ``solve_system``'s own reordering is all that answers that.
+
+    Arguments are checked once, before the first solve (:func:`check_adaptive_arguments`, and a ``partition`` over several
+    GPUs is refused).  ``timings`` receives ``"solve"`` and ``"refine"``: the host time of all solves and all refinements."""
+    _refuse_partition(partition, "adaptive solves")
+    tolerance, max_rounds, max_faces, min_size = check_adaptive_arguments(tolerance, max_rounds, max_faces, min_size)
+    meshes = [m if isinstance(m, mesh.Mesh) else mesh.Mesh.from_reference(m) for m in meshes]
+    layer_of = list(mesh_index_to_layer_index)
+    history = AdaptiveHistory()
+    spent = {"solve": 0.0, "refine": 0.0}
+    while True:
+        since = time.perf_counter()
+        solution, report = solve_meshed_error(prob, meshes, layer_of, tolerance=tolerance, filtered_networks=filtered_networks,
+                                              disconnected_meshes_by_layer=disconnected_meshes_by_layer)
+        spent["solve"] += time.perf_counter() - since
+        history.faces.append(sum(len(m.triangles) for m in meshes))
+        history.vertices.append(sum(len(m.points) for m in meshes))
+        history.estimates.append(report.estimate)
+        history.flagged.append(0)
+        history.closure_edges.append(0)
+        history.meshes = meshes
+        log.info("Adaptive round %d: %d faces, estimate %.3e", len(history.faces), history.faces[-1], report.estimate)
+        if report.estimate <= tolerance:
+            history.reason = "tolerance"
+            break
+        flags = [None] * len(meshes)
+        for layer_i in range(len(prob.layers)):
+            members = [mi for mi, l in enumerate(layer_of) if l == layer_i]
+            for mi, xi in zip(members, report.ratios[layer_i]):
+                flags[mi] = (xi > 1.0) & (face_sizes(meshes[mi].points, meshes[mi].triangles) > min_size)
+        history.flagged[-1] = int(sum(int(f.sum()) for f in flags))
+        if history.flagged[-1] == 0:
+            history.reason = "floor"
+            break
+        if len(history.faces) >= max_rounds:
+            history.reason = "rounds"
+            break
+        since = time.perf_counter()
+        refined = refine_meshes(meshes, flags)
+        spent["refine"] += time.perf_counter() - since
+        history.closure_edges[-1] = refined.marked - refined.marked_by_flags
+        if max_faces is not None and sum(len(m.triangles) for m in refined.meshes) > max_faces:
+            history.reason = "faces"
+            break
+        meshes = refined.meshes
+    if timings is not None:
+        timings.update(spent)
+    return solution, report, history
+
+
+def solve_adaptive(prob, mesher_config: Optional[mesh.Mesher.Config] = None, *, tolerance, mesher=None, max_rounds=8,
+                   max_faces=None, min_size=0.0, partition=None, timings: Optional[dict] = None):
+    """``solve`` refined where the error estimate asks: the board is meshed once, then :func:`solve_meshed_adaptive`.
+    Returns (Solution, ErrorReport, AdaptiveHistory)."""
+    _refuse_partition(partition, "adaptive solves")
+    check_adaptive_arguments(tolerance, max_rounds, max_faces, min_size)
+    meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
+    return solve_meshed_adaptive(prob, meshes, mesh_index_to_layer_index, tolerance=tolerance, max_rounds=max_rounds,
+                                 max_faces=max_faces, min_size=min_size, timings=timings)
 
 
 # --------------------------------------------------------------------------------------------
