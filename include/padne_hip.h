@@ -365,6 +365,21 @@ int padne_kkt_sensitivity_block(padne_ctx *ctx, padne_kkt *plan, int32_t n_cols,
 int padne_kkt_current_report(padne_ctx *ctx, padne_kkt *plan, int32_t n_cols, int64_t n_tri, int32_t n_mesh,
                              const int32_t *mesh_layer, int32_t n_cut, const int32_t *cut_layer, const double *cut_xy,
                              double *J_out, double *mag_out, double *mesh_max_out, int64_t *mesh_face_out, double *cut_out);
+/* padne_kkt_current_report for every column j of the block the last padne_kkt_finish_block left on the device (load cases),
+ * and the envelope over the columns.  Column-major results: J_out[n_cols][n_tri][2], mag_out[n_cols][n_tri],
+ * mesh_max_out / mesh_face_out[n_cols][n_mesh], cut_out[n_cols][n_cut]; row 0 of each holds the bits padne_kkt_current_report
+ * gives (any n_cols >= 1).  mesh_power_out[n_cols][n_mesh] = per mesh the sum over its faces of sigma sum_{edges} w_ik
+ * (V_i - V_k)^2 with the assembly's |cot|/2 weights: for column 0 the bits of padne_kkt_sensitivity_block's mesh_total_out
+ * with one objective of weight 1 on a one-column block.  env_out[n_tri] = max_j |J_j| per face and env_case_out[n_tri] the
+ * lowest column that attains it: the columns are visited in order from column 0 and a later one replaces the value only
+ * when strictly greater, so a face whose |J| is NaN in column 0 keeps NaN and case 0.  J_out and mag_out may both be null
+ * ("envelope only"): then no per-column field is written on the device or copied home; every other result is the same.
+ * Everything is summed in a fixed order: two calls give the same bits.  Preconditions and errors as
+ * padne_kkt_current_report. */
+int padne_kkt_current_cases(padne_ctx *ctx, padne_kkt *plan, int32_t n_cols, int64_t n_tri, int32_t n_mesh,
+                            const int32_t *mesh_layer, int32_t n_cut, const int32_t *cut_layer, const double *cut_xy,
+                            double *J_out, double *mag_out, double *env_out, int32_t *env_case_out, double *mesh_max_out,
+                            int64_t *mesh_face_out, double *mesh_power_out, double *cut_out);
 /* Gradient-recovery (Zienkiewicz-Zhu) estimate of the discretisation error over the mesh `L` keeps, from column 0 of the
  * block the last padne_kkt_finish_block left on the device.  Per face f (corners in the order of padne_csr_power_density):
  * g_f its gradient, A_f its area.  G_out[n_vert][2] = (sum A_f g_f) / (sum A_f) over the faces incident to each vertex, added

@@ -115,6 +115,8 @@ SIGNATURES = {
     "padne_kkt_sensitivity_block": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _PF64, _PF64, _PF64, _PF64]),
     "padne_kkt_current_report": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int32, _PI32, C.c_int32, _PI32, _PF64, _PF64, _PF64,
                                            _PF64, _PI64, _PF64]),
+    "padne_kkt_current_cases": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int32, _PI32, C.c_int32, _PI32, _PF64, _PF64, _PF64,
+                                          _PF64, _PI32, _PF64, _PI64, _PF64, _PF64]),
     "padne_kkt_error_estimate": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int64, C.c_int32, _PF64, _PF64, _PF64, _PF64, _PF64,
                                            _PI64]),
     "padne_amg_apply": (C.c_int, [_P, _P, _PF64, _PF64]),
@@ -697,12 +699,13 @@ class KktPlan:
 
     def solve_block_coo(self, n_cols, rows, cols, vals, known_idx, known_val, extras: list, probes, *, rtol=1e-12,
                         max_iter=200000, precond="amg", abs_residual_target=0.0, rebuild=False, power_tri: int = 0,
-                        power_rows: int = 0, current_tri: int = 0):
+                        power_rows: int = 0, current_tri: int = 0, current_cols: int = 1):
         """``solve_block`` with the block (N, n_cols) given by its non-zero entries: R[rows[e], cols[e]] = vals[e], each (row,
         column) pair at most once.  Only the triples cross PCIe; the device zeroes its block and scatters them.
         ``power_tri``: the triangles of the mesh the system carries, when ``power_density_block`` will follow -- its result
         array is then made ready while the device solves, like V's (``power_rows`` rows of it instead of n_cols: 1 + the
-        objectives of a ``sensitivity_block``).  ``current_tri``: the same for the J and |J| arrays of a ``current_report``."""
+        objectives of a ``sensitivity_block``).  ``current_tri``: the same for the J and |J| arrays of a ``current_report``, or,
+        with ``current_cols`` = the columns whose fields a ``current_cases`` will bring home, for those."""
         rows, cols, vals = _i64(rows).reshape(-1), _i32(cols).reshape(-1), _f64(vals).reshape(-1)
         if not (rows.shape == cols.shape == vals.shape):
             raise ValueError("rows, cols and vals must have equal length")
@@ -713,10 +716,10 @@ class KktPlan:
         kval = _f64(known_val).reshape(n_cols, kidx.shape[0])
         return self._stage1(n_cols, (rows, cols, vals), kidx, kval, extras, probes, rtol, max_iter, precond,
                             abs_residual_target, rebuild, power_tri=int(power_tri), power_rows=int(power_rows),
-                            current_tri=int(current_tri))
+                            current_tri=int(current_tri), current_cols=int(current_cols))
 
     def _stage1(self, n_cols, r, kidx, kval, extras, probes, rtol, max_iter, precond, abs_residual_target, rebuild,
-                power_tri=0, power_rows=0, current_tri=0):
+                power_tri=0, power_rows=0, current_tri=0, current_cols=1):
         ptr, rows, vals = [0], [], []
         for col in extras:
             for row, val in col.items():
@@ -736,7 +739,7 @@ class KktPlan:
         if coo and power_tri > 0:
             self._prefault["pd"] = _prefaulted((power_rows or n_cols, power_tri))
         if coo and current_tri > 0:
-            self._prefault["cur"] = _prefaulted((3 * current_tri,))
+            self._prefault["cur"] = _prefaulted((3 * current_cols * current_tri,))
         lib, common = self.ctx._lib, (kidx.shape[0], _ptr(kidx, _PI64), _ptr(kval, _PF64), len(extras),
                                       _ptr(ptr, _PI64), _ptr(rows, _PI64), _ptr(vals, _PF64), pidx.shape[0], _ptr(pidx, _PI64),
                                       _ptr(out, _PF64), C.byref(opts), float(abs_residual_target), C.byref(info))
@@ -813,6 +816,36 @@ class KktPlan:
                                                       _ptr(cl, _PI32), _ptr(xy, _PF64), _ptr(J, _PF64), _ptr(mag, _PF64),
                                                       _ptr(mesh_max, _PF64), _ptr(mesh_face, _PI64), _ptr(cuts, _PF64)))
         return J, mag, mesh_max, mesh_face, cuts
+
+    def current_cases(self, n_cols: int, n_tri: int, mesh_layer, cut_layer, cut_xy, fields: bool = True):
+        """``current_report`` for every column of the block the last ``finish_block`` left on the device, and the envelope
+        over the columns.  Returns (J (n_cols, n_tri, 2), |J| (n_cols, n_tri) -- both None without ``fields``: the device
+        then writes and sends home no per-column field --, max_j |J_j| (n_tri,), the lowest column that attains it (n_tri,)
+        int32, and per column the largest |J| of each mesh (n_cols, n_mesh), its face (n_cols, n_mesh), the power of each
+        mesh in the |cot|/2 weights' form (n_cols, n_mesh) and the current through each cut (n_cols, n_cut))
+        (include/padne_hip.h).  Row 0 holds ``current_report``'s bits.  Raises ValueError as ``current_report`` does."""
+        ml = _i32(mesh_layer).reshape(-1)
+        cl = _i32(cut_layer).reshape(-1)
+        xy = _f64(cut_xy).reshape(-1, 4)
+        if xy.shape[0] != cl.shape[0]:
+            raise ValueError("cut_layer and cut_xy must list the same cuts")
+        n_cols, n_tri, n_mesh, n_cut = int(n_cols), int(n_tri), ml.shape[0], cl.shape[0]
+        if n_cols < 1:
+            raise ValueError("a block has at least one column")
+        J = mag = None
+        if fields:
+            buf = self._result_array((3 * n_cols * n_tri,), "cur")
+            J, mag = buf[:2 * n_cols * n_tri].reshape(n_cols, n_tri, 2), buf[2 * n_cols * n_tri:].reshape(n_cols, n_tri)
+        env = np.empty(n_tri, dtype=np.float64)
+        env_case = np.empty(n_tri, dtype=np.int32)
+        mesh_max, mesh_power = (np.empty((n_cols, n_mesh), dtype=np.float64) for _ in range(2))
+        mesh_face = np.empty((n_cols, n_mesh), dtype=np.int64)
+        cuts = np.empty((n_cols, n_cut), dtype=np.float64)
+        _check(self.ctx._lib.padne_kkt_current_cases(
+            self.ctx._h, self._h, n_cols, n_tri, n_mesh, _ptr(ml, _PI32), n_cut, _ptr(cl, _PI32), _ptr(xy, _PF64),
+            None if J is None else _ptr(J, _PF64), None if mag is None else _ptr(mag, _PF64), _ptr(env, _PF64),
+            _ptr(env_case, _PI32), _ptr(mesh_max, _PF64), _ptr(mesh_face, _PI64), _ptr(mesh_power, _PF64), _ptr(cuts, _PF64)))
+        return J, mag, env, env_case, mesh_max, mesh_face, mesh_power, cuts
 
     def error_estimate(self, n_cols: int, n_tri: int, n_vert: int, n_mesh: int):
         """The gradient-recovery error estimate of column 0 of the block the last ``finish_block`` left on the device, over

@@ -2513,6 +2513,230 @@ __global__ __launch_bounds__(256) void cut_current_kernel(
     if (threadIdx.x == 0) partial[p] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// Currents of every column of a block ("Load-case currents"): what current_face_kernel, cut_current_kernel and
+// sensitivity_block_kernel with W = 1 give for one column, for all n_cols columns of V[g * n_cols + j] in one pass, and the
+// envelope over the columns.  The corners and xy of a face are read once; the columns go in register chunks of kCaseChunk
+// (three gathers of 64 contiguous bytes each), so registers do not grow with n_cols.
+constexpr int kCaseChunk = 8;
+
+// out, per column j: J[j][t][2] and mag[j][t] = |J| (both null: not written), per tile its largest |J| with the face
+// (tile_max[j][b], tile_face[j][b]; -1 and kNoFace for no face) and partial[j][b] = the tile's sum of sigma sum_edges w_ik
+// (V_i - V_k)^2 in the order of sensitivity_block_kernel.  Per face: env[t] = max_j |J_j| and env_case[t] the lowest j that
+// attains it (sequential over j: column 0 first, replaced on strictly greater only, so a NaN stays with column 0).  Per
+// tile, once: box[b] as current_face_kernel writes it.
+__global__ __launch_bounds__(256) void current_cases_face_kernel(
+    int n_mesh, const long long *__restrict__ tile_off, const int *__restrict__ tri, const double *__restrict__ xy,
+    const long long *__restrict__ mesh_voff, const long long *__restrict__ mesh_toff, const double *__restrict__ sigma,
+    const long long n_tri, const long long n_blocks, const int n_cols, const double *__restrict__ V, double *__restrict__ J,
+    double *__restrict__ mag, double *__restrict__ env, int *__restrict__ env_case, double *__restrict__ tile_max,
+    long long *__restrict__ tile_face, double *__restrict__ partial, double *__restrict__ box, int *__restrict__ err) {
+    __shared__ double red_v[kCaseChunk][4], red_p[kCaseChunk][4], red_box[4][4];
+    __shared__ long long red_f[kCaseChunk][4];
+    const long long b = blockIdx.x;
+    int m;
+    const long long t = tile_first_face(tile_off, n_mesh, mesh_toff, b, m) + threadIdx.x;
+    bool live = t < mesh_toff[m + 1];
+    long long g1 = 0, g2 = 0, g3 = 0;
+    if (live && !face_corners(tri, mesh_voff, m, t, g1, g2, g3)) {
+        *(volatile int *)err = 1;
+        live = false;                           // (no return: every thread takes part in the block reductions below)
+    }
+    double x1 = 0, y1 = 0, x2 = 0, y2 = 0, x3 = 0, y3 = 0, w12 = 0, w23 = 0, w31 = 0, s = 0;
+    double bx0 = INFINITY, by0 = INFINITY, bx1 = -INFINITY, by1 = -INFINITY;
+    if (live) {
+        x1 = xy[2 * g1]; y1 = xy[2 * g1 + 1];
+        x2 = xy[2 * g2]; y2 = xy[2 * g2 + 1];
+        x3 = xy[2 * g3]; y3 = xy[2 * g3 + 1];
+        s = sigma[m];
+        w23 = cot_half(x2, y2, x3, y3, x1, y1);     // the weights of sensitivity_block_kernel
+        w31 = cot_half(x3, y3, x1, y1, x2, y2);
+        w12 = cot_half(x1, y1, x2, y2, x3, y3);
+        bx0 = fmin(fmin(x1, x2), x3);
+        by0 = fmin(fmin(y1, y2), y3);
+        bx1 = fmax(fmax(x1, x2), x3);
+        by1 = fmax(fmax(y1, y2), y3);
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        bx0 = fmin(bx0, __shfl_down(bx0, off, 64));
+        by0 = fmin(by0, __shfl_down(by0, off, 64));
+        bx1 = fmax(bx1, __shfl_down(bx1, off, 64));
+        by1 = fmax(by1, __shfl_down(by1, off, 64));
+    }
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        red_box[w][0] = bx0;
+        red_box[w][1] = by0;
+        red_box[w][2] = bx1;
+        red_box[w][3] = by1;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int q = 1; q < 4; ++q) {
+            bx0 = fmin(bx0, red_box[q][0]);
+            by0 = fmin(by0, red_box[q][1]);
+            bx1 = fmax(bx1, red_box[q][2]);
+            by1 = fmax(by1, red_box[q][3]);
+        }
+        box[4 * b] = bx0;
+        box[4 * b + 1] = by0;
+        box[4 * b + 2] = bx1;
+        box[4 * b + 3] = by1;
+    }
+    const double *p1 = V + g1 * n_cols, *p2 = V + g2 * n_cols, *p3 = V + g3 * n_cols;
+    const bool fields = J != nullptr;
+    double e = -1.0;
+    int ec = 0;
+    for (int j0 = 0; j0 < n_cols; j0 += kCaseChunk) {
+        double f1[kCaseChunk], f2[kCaseChunk], f3[kCaseChunk];
+        if (live) {
+#pragma unroll
+            for (int q = 0; q < kCaseChunk; ++q)
+                if (j0 + q < n_cols) {
+                    f1[q] = p1[j0 + q];
+                    f2[q] = p2[j0 + q];
+                    f3[q] = p3[j0 + q];
+                }
+        }
+#pragma unroll
+        for (int q = 0; q < kCaseChunk; ++q) {
+            double a = -1.0, pw = 0.0;
+            long long f = kNoFace;
+            if (live && j0 + q < n_cols) {
+                double gx, gy;
+                face_gradient_of(x1, y1, x2, y2, x3, y3, f1[q], f2[q], f3[q], gx, gy);
+                const double jx = -s * gx, jy = -s * gy;
+                a = sqrt(jx * jx + jy * jy);
+                f = t;
+                if (fields) {
+                    const long long at = (long long)(j0 + q) * n_tri + t;
+                    J[2 * at] = jx;
+                    J[2 * at + 1] = jy;
+                    mag[at] = a;
+                }
+                if (j0 + q == 0 || a > e) {
+                    e = a;
+                    ec = j0 + q;
+                }
+                const double d12 = f1[q] - f2[q], d23 = f2[q] - f3[q], d31 = f3[q] - f1[q];
+                pw = s * ((w12 * d12 * d12 + w23 * d23 * d23) + w31 * d31 * d31);
+            }
+            for (int off = 32; off > 0; off >>= 1) {
+                hotspot_merge(a, f, __shfl_down(a, off, 64), __shfl_down(f, off, 64));
+                pw += __shfl_down(pw, off, 64);
+            }
+            if ((threadIdx.x & 63) == 0) {
+                red_v[q][w] = a;
+                red_f[q][w] = f;
+                red_p[q][w] = pw;
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x < kCaseChunk && j0 + (int)threadIdx.x < n_cols) {
+            const int q = threadIdx.x;
+            double a = red_v[q][0];
+            long long f = red_f[q][0];
+            for (int r = 1; r < 4; ++r) hotspot_merge(a, f, red_v[q][r], red_f[q][r]);
+            const long long at = (long long)(j0 + q) * n_blocks + b;
+            tile_max[at] = a;
+            tile_face[at] = f;
+            partial[at] = (red_p[q][0] + red_p[q][1]) + (red_p[q][2] + red_p[q][3]);
+        }
+        __syncthreads();
+    }
+    if (live) {
+        env[t] = e;
+        env_case[t] = ec;
+    }
+}
+
+// per (mesh m, column j = blockIdx.y), over the mesh's tiles in a fixed order: the largest |J| and its face as
+// current_mesh_fold folds them, and the power as sensitivity_mesh_fold sums it
+__global__ __launch_bounds__(256) void current_cases_mesh_fold(int n_mesh, const long long *__restrict__ tile_off,
+                                                               const long long n_blocks, const double *__restrict__ tile_max,
+                                                               const long long *__restrict__ tile_face,
+                                                               const double *__restrict__ partial, double *__restrict__ mesh_max,
+                                                               long long *__restrict__ mesh_face, double *__restrict__ mesh_power) {
+    __shared__ double red_v[4], red_p[4];
+    __shared__ long long red_f[4];
+    const int m = blockIdx.x;
+    const long long col = (long long)blockIdx.y * n_blocks;
+    double a = -1.0, s = 0.0;
+    long long f = kNoFace;
+    for (long long i = tile_off[m] + threadIdx.x; i < tile_off[m + 1]; i += 256) {
+        hotspot_merge(a, f, tile_max[col + i], tile_face[col + i]);
+        s += partial[col + i];
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        hotspot_merge(a, f, __shfl_down(a, off, 64), __shfl_down(f, off, 64));
+        s += __shfl_down(s, off, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        red_v[threadIdx.x >> 6] = a;
+        red_f[threadIdx.x >> 6] = f;
+        red_p[threadIdx.x >> 6] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int q = 1; q < 4; ++q) hotspot_merge(a, f, red_v[q], red_f[q]);
+        const long long at = (long long)blockIdx.y * n_mesh + m;
+        mesh_max[at] = a;
+        mesh_face[at] = f == kNoFace ? -1 : f;
+        mesh_power[at] = (red_p[0] + red_p[1]) + (red_p[2] + red_p[3]);
+    }
+}
+
+// one workgroup per (cut, tile) pair, all columns: partial[j][p] = what cut_current_kernel gives for column j
+__global__ __launch_bounds__(256) void current_cases_cut_kernel(
+    int n_mesh, const long long *__restrict__ tile_off, const int *__restrict__ tri, const double *__restrict__ xy,
+    const long long *__restrict__ mesh_voff, const long long *__restrict__ mesh_toff, const double *__restrict__ sigma,
+    const int n_cols, const double *__restrict__ V, const long long n_pairs, const int *__restrict__ pair_cut,
+    const long long *__restrict__ pair_tile, const double *__restrict__ cut_xy, double *__restrict__ partial,
+    int *__restrict__ err) {
+    __shared__ double red[kCaseChunk][4];
+    const long long p = blockIdx.x;
+    int m;
+    const long long t = tile_first_face(tile_off, n_mesh, mesh_toff, pair_tile[p], m) + threadIdx.x;
+    bool live = t < mesh_toff[m + 1];
+    long long g1 = 0, g2 = 0, g3 = 0;
+    if (live && !face_corners(tri, mesh_voff, m, t, g1, g2, g3)) {
+        *(volatile int *)err = 1;
+        live = false;
+    }
+    const double *c = cut_xy + 4 * (long long)pair_cut[p];
+    double x1 = 0, y1 = 0, x2 = 0, y2 = 0, x3 = 0, y3 = 0, w12 = 0, w23 = 0, w31 = 0, sg = 0;
+    if (live) {
+        x1 = xy[2 * g1]; y1 = xy[2 * g1 + 1];
+        x2 = xy[2 * g2]; y2 = xy[2 * g2 + 1];
+        x3 = xy[2 * g3]; y3 = xy[2 * g3 + 1];
+        w12 = cot_half(x1, y1, x2, y2, x3, y3);
+        w23 = cot_half(x2, y2, x3, y3, x1, y1);
+        w31 = cot_half(x3, y3, x1, y1, x2, y2);
+        sg = sigma[m];
+    }
+    const double *p1 = V + g1 * n_cols, *p2 = V + g2 * n_cols, *p3 = V + g3 * n_cols;
+    for (int j0 = 0; j0 < n_cols; j0 += kCaseChunk) {
+#pragma unroll
+        for (int q = 0; q < kCaseChunk; ++q) {
+            double s = 0.0;
+            if (live && j0 + q < n_cols) {
+                const double u1 = p1[j0 + q], u2 = p2[j0 + q], u3 = p3[j0 + q];
+                const double e12 = cut_edge(g1, g2, x1, y1, x2, y2, u1, u2, w12, c);
+                const double e23 = cut_edge(g2, g3, x2, y2, x3, y3, u2, u3, w23, c);
+                const double e31 = cut_edge(g3, g1, x3, y3, x1, y1, u3, u1, w31, c);
+                s = sg * ((e12 + e23) + e31);
+            }
+            for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+            if ((threadIdx.x & 63) == 0) red[q][threadIdx.x >> 6] = s;
+        }
+        __syncthreads();
+        if (threadIdx.x < kCaseChunk && j0 + (int)threadIdx.x < n_cols) {
+            const int q = threadIdx.x;
+            partial[(long long)(j0 + q) * n_pairs + p] = (red[q][0] + red[q][1]) + (red[q][2] + red[q][3]);
+        }
+        __syncthreads();
+    }
+}
+
 // ---- host orchestration ----------------------------------------------------------------------
 // shared tail: slots (key,val,slot_ptr) already filled -> merged CSR
 // padne_assemble_system_ex(flags & 1): the triangles are a rank's piece of a larger mesh (owned vertices + the ring of
@@ -3137,6 +3361,66 @@ int launch_cut_currents(padne_ctx *ctx, const padne_csr *m, const long long *til
     }
     hipLaunchKernelGGL(sensitivity_mesh_fold, dim3((unsigned)n_cut, 1u), dim3(256), 0, s, n_cut, (const long long *)d_off, n_pairs,
                        (const double *)d_partial, cut_dev);
+    PADNE_HIP_CHECK(hipGetLastError());
+    return PADNE_OK;
+}
+
+// current_cases_face_kernel + current_cases_mesh_fold over the mesh `m` keeps, on the tiles of launch_current_faces.
+// J_dev[n_cols][mesh_n_tri][2] and mag_dev[n_cols][mesh_n_tri] (both null: envelope only), env_dev, env_case_dev[mesh_n_tri],
+// box_dev[n_blocks][4], mesh_max_dev, mesh_face_dev, mesh_power_dev[n_cols][mesh_n_mesh] (device).  Asynchronous.
+int launch_current_cases_faces(padne_ctx *ctx, const padne_csr *m, const long long *tile_dev, long long n_blocks, int n_cols,
+                               const double *V_dev, double *J_dev, double *mag_dev, double *env_dev, int *env_case_dev,
+                               double *box_dev, double *mesh_max_dev, long long *mesh_face_dev, double *mesh_power_dev,
+                               int *bad_dev) {
+    PADNE_REQUIRE(m->mesh_n_mesh > 0 && m->mesh_xy != nullptr, "the matrix does not carry a mesh (only padne_assemble_system keeps it)");
+    PADNE_REQUIRE(n_cols >= 1 && n_cols <= 65535, "between 1 and 65535 columns");
+    PADNE_REQUIRE((J_dev == nullptr) == (mag_dev == nullptr), "J and |J| go together");
+    const int n_mesh = (int)m->mesh_n_mesh;
+    hipStream_t s = ctx->stream;
+    Scratch sc(ctx);
+    const size_t nb = (size_t)n_cols * (size_t)(n_blocks > 0 ? n_blocks : 1);
+    double *d_tmax = nullptr, *d_partial = nullptr;
+    long long *d_tface = nullptr;
+    PADNE_TRY(sc.alloc(&d_tmax, nb));
+    PADNE_TRY(sc.alloc(&d_tface, nb));
+    PADNE_TRY(sc.alloc(&d_partial, nb));
+    if (n_blocks > 0) {
+        hipLaunchKernelGGL(current_cases_face_kernel, dim3((unsigned)n_blocks), dim3(256), 0, s, n_mesh, tile_dev, m->mesh_tri,
+                           m->mesh_xy, m->mesh_voff, m->mesh_toff, m->mesh_sigma, (long long)m->mesh_n_tri, n_blocks, n_cols, V_dev,
+                           J_dev, mag_dev, env_dev, env_case_dev, d_tmax, d_tface, d_partial, box_dev, bad_dev);
+        PADNE_HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(current_cases_mesh_fold, dim3((unsigned)n_mesh, (unsigned)n_cols), dim3(256), 0, s, n_mesh, tile_dev, n_blocks,
+                       (const double *)d_tmax, (const long long *)d_tface, (const double *)d_partial, mesh_max_dev, mesh_face_dev,
+                       mesh_power_dev);
+    PADNE_HIP_CHECK(hipGetLastError());
+    // (the scratch goes back to the pool on return: the context's one stream orders its reuse after these launches)
+    return PADNE_OK;
+}
+
+// current_cases_cut_kernel over the (cut, tile) pairs of launch_cut_currents, then each (cut, column)'s pairs summed in
+// the order of launch_cut_currents into cut_dev[n_cols][n_cut].  Asynchronous.
+int launch_current_cases_cuts(padne_ctx *ctx, const padne_csr *m, const long long *tile_dev, int n_cols, const double *V_dev,
+                              int n_cut, const double *cut_xy_dev, long long n_pairs, const int *pair_cut_dev,
+                              const long long *pair_tile_dev, const long long *pair_off_host, double *cut_dev, int *bad_dev) {
+    PADNE_REQUIRE(m->mesh_n_mesh > 0 && m->mesh_xy != nullptr, "the matrix does not carry a mesh (only padne_assemble_system keeps it)");
+    PADNE_REQUIRE(n_cols >= 1 && n_cols <= 65535, "between 1 and 65535 columns");
+    if (n_cut == 0) return PADNE_OK;
+    hipStream_t s = ctx->stream;
+    Scratch sc(ctx);
+    long long *d_off = nullptr;
+    double *d_partial = nullptr;
+    PADNE_TRY(sc.alloc(&d_off, (size_t)n_cut + 1));
+    PADNE_TRY(sc.alloc(&d_partial, (size_t)n_cols * (size_t)(n_pairs > 0 ? n_pairs : 1)));
+    PADNE_HIP_CHECK(hipMemcpyAsync(d_off, pair_off_host, sizeof(long long) * ((size_t)n_cut + 1), hipMemcpyHostToDevice, s));
+    if (n_pairs > 0) {
+        hipLaunchKernelGGL(current_cases_cut_kernel, dim3((unsigned)n_pairs), dim3(256), 0, s, (int)m->mesh_n_mesh, tile_dev,
+                           m->mesh_tri, m->mesh_xy, m->mesh_voff, m->mesh_toff, m->mesh_sigma, n_cols, V_dev, n_pairs, pair_cut_dev,
+                           pair_tile_dev, cut_xy_dev, d_partial, bad_dev);
+        PADNE_HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(sensitivity_mesh_fold, dim3((unsigned)n_cut, (unsigned)n_cols), dim3(256), 0, s, n_cut,
+                       (const long long *)d_off, n_pairs, (const double *)d_partial, cut_dev);
     PADNE_HIP_CHECK(hipGetLastError());
     return PADNE_OK;
 }

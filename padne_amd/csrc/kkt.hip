@@ -33,6 +33,13 @@ int launch_current_faces(padne_ctx *ctx, const padne_csr *m, const long long *ti
 int launch_cut_currents(padne_ctx *ctx, const padne_csr *m, const long long *tile_dev, int n_cols, const double *V_dev,
                         int n_cut, const double *cut_xy_dev, long long n_pairs, const int *pair_cut_dev,
                         const long long *pair_tile_dev, const long long *pair_off_host, double *cut_dev, int *bad_dev);
+int launch_current_cases_faces(padne_ctx *ctx, const padne_csr *m, const long long *tile_dev, long long n_blocks, int n_cols,
+                               const double *V_dev, double *J_dev, double *mag_dev, double *env_dev, int *env_case_dev,
+                               double *box_dev, double *mesh_max_dev, long long *mesh_face_dev, double *mesh_power_dev,
+                               int *bad_dev);
+int launch_current_cases_cuts(padne_ctx *ctx, const padne_csr *m, const long long *tile_dev, int n_cols, const double *V_dev,
+                              int n_cut, const double *cut_xy_dev, long long n_pairs, const int *pair_cut_dev,
+                              const long long *pair_tile_dev, const long long *pair_off_host, double *cut_dev, int *bad_dev);
 int csr_error_estimate(padne_ctx *ctx, const padne_csr *L, int **vptr, int **vface, int n_cols, const double *V_dev,
                        double *G_dev, double *eta_dev, double *mesh_E_dev, double *mesh_P_dev, double *mesh_max_dev,
                        long long *mesh_face_dev, int *bad_dev);
@@ -1233,6 +1240,37 @@ static bool segment_meets_box(const double *c, const double *box) {
     return pos < 4 && neg < 4;
 }
 
+// the end points of n_cut cuts, cut_xy[c] = (start x, y, end x, y): finite, and start != end
+static int check_cut_segments(int n_cut, const double *cut_xy) {
+    for (int c = 0; c < n_cut; ++c) {
+        const double *p = cut_xy + 4 * (size_t)c;
+        for (int q = 0; q < 4; ++q) PADNE_REQUIRE(std::isfinite(p[q]), "cut end points must be finite");
+        PADNE_REQUIRE(p[0] != p[2] || p[1] != p[3], "a cut's start and end must differ");
+    }
+    return PADNE_OK;
+}
+
+// the (cut, tile) pairs, by cut and then by tile: the tiles of the meshes on the cut's layer whose box the segment meets;
+// pair_off[c] .. pair_off[c + 1] are cut c's pairs
+static void list_cut_pairs(int n_cut, int n_mesh, const int32_t *mesh_layer, const int32_t *cut_layer, const double *cut_xy,
+                           const std::vector<long long> &tile, const std::vector<double> &box, std::vector<int> &pair_cut,
+                           std::vector<long long> &pair_tile, std::vector<long long> &pair_off) {
+    pair_cut.clear();
+    pair_tile.clear();
+    pair_off.assign((size_t)n_cut + 1, 0);
+    for (int c = 0; c < n_cut; ++c) {
+        for (int m = 0; m < n_mesh; ++m) {
+            if (mesh_layer[m] != cut_layer[c]) continue;
+            for (long long b = tile[(size_t)m]; b < tile[(size_t)m + 1]; ++b)
+                if (segment_meets_box(cut_xy + 4 * (size_t)c, box.data() + 4 * (size_t)b)) {
+                    pair_cut.push_back(c);
+                    pair_tile.push_back(b);
+                }
+        }
+        pair_off[(size_t)c + 1] = (long long)pair_tile.size();
+    }
+}
+
 // The currents of column 0 of the finished block ("Currents"): J = -sigma grad V and |J| of every face, the
 // largest |J| of every mesh, and the current through each cut.  One launch over the tiles of sensitivity_block_kernel's
 // layout writes J, |J|, per-tile maxima and per-tile bounding boxes, and one fold per mesh reduces the maxima.  The boxes
@@ -1250,11 +1288,7 @@ extern "C" int padne_kkt_current_report(padne_ctx *ctx, padne_kkt *k, int32_t n_
     PADNE_REQUIRE(n_cut >= 0 && n_cut <= 4096, "between 0 and 4096 cuts");
     PADNE_REQUIRE(mesh_max_out && mesh_face_out, "null argument");
     PADNE_REQUIRE(n_cut == 0 || (mesh_layer && cut_layer && cut_xy && cut_out), "null argument");
-    for (int c = 0; c < n_cut; ++c) {
-        const double *p = cut_xy + 4 * (size_t)c;
-        for (int q = 0; q < 4; ++q) PADNE_REQUIRE(std::isfinite(p[q]), "cut end points must be finite");
-        PADNE_REQUIRE(p[0] != p[2] || p[1] != p[3], "a cut's start and end must differ");
-    }
+    PADNE_TRY(check_cut_segments(n_cut, cut_xy));
     const padne_csr *L = k->L;
     PADNE_REQUIRE(L->mesh_n_mesh > 0 && L->mesh_xy != nullptr,
                   "the system matrix does not carry a mesh (only padne_assemble_system keeps it)");
@@ -1285,24 +1319,13 @@ extern "C" int padne_kkt_current_report(padne_ctx *ctx, padne_kkt *k, int32_t n_
     PADNE_TRY(launch_current_faces(ctx, L, d_tile, n_blocks, n_cols, k->v_final, d_J, d_mag, d_tmax, d_tface, d_box, d_mmax,
                                    d_mface, d_bad));
     if (n_cut > 0) {
-        // the (cut, tile) pairs, by cut and then by tile: the tiles of the meshes on the cut's layer whose box the segment meets
         std::vector<double> box(4 * nb);
         if (n_blocks > 0)
             PADNE_HIP_CHECK(hipMemcpyAsync(box.data(), d_box, sizeof(double) * 4 * (size_t)n_blocks, hipMemcpyDeviceToHost, s));
         PADNE_HIP_CHECK(hipStreamSynchronize(s));
         std::vector<int> pair_cut;
-        std::vector<long long> pair_tile, pair_off((size_t)n_cut + 1, 0);
-        for (int c = 0; c < n_cut; ++c) {
-            for (int m = 0; m < n_mesh; ++m) {
-                if (mesh_layer[m] != cut_layer[c]) continue;
-                for (long long b = tile[(size_t)m]; b < tile[(size_t)m + 1]; ++b)
-                    if (segment_meets_box(cut_xy + 4 * (size_t)c, box.data() + 4 * (size_t)b)) {
-                        pair_cut.push_back(c);
-                        pair_tile.push_back(b);
-                    }
-            }
-            pair_off[(size_t)c + 1] = (long long)pair_tile.size();
-        }
+        std::vector<long long> pair_tile, pair_off;
+        list_cut_pairs(n_cut, n_mesh, mesh_layer, cut_layer, cut_xy, tile, box, pair_cut, pair_tile, pair_off);
         const long long n_pairs = (long long)pair_tile.size();
         PADNE_REQUIRE(n_pairs <= 0x7fffffffLL, "too many (cut, tile) pairs for one launch");
         const size_t np = (size_t)(n_pairs > 0 ? n_pairs : 1);
@@ -1335,6 +1358,103 @@ extern "C" int padne_kkt_current_report(padne_ctx *ctx, padne_kkt *k, int32_t n_
     if (n_tri == 0) return PADNE_OK;
     PADNE_TRY(parallel_copy(k, J_out, d_J, sizeof(double) * 2 * (size_t)n_tri, hipMemcpyDeviceToHost));
     return parallel_copy(k, mag_out, d_mag, sizeof(double) * (size_t)n_tri, hipMemcpyDeviceToHost);
+}
+
+// The currents of every column of the finished block and their envelope ("Load-case currents"): the launches of
+// padne_kkt_current_report with the k-column kernels in their place.  With J_out and mag_out null no per-column field is
+// written on the device or copied home.  No floating-point atomics: two calls give the same bits.
+extern "C" int padne_kkt_current_cases(padne_ctx *ctx, padne_kkt *k, int32_t n_cols, int64_t n_tri, int32_t n_mesh,
+                                       const int32_t *mesh_layer, int32_t n_cut, const int32_t *cut_layer, const double *cut_xy,
+                                       double *J_out, double *mag_out, double *env_out, int32_t *env_case_out,
+                                       double *mesh_max_out, int64_t *mesh_face_out, double *mesh_power_out, double *cut_out) {
+    PADNE_REQUIRE(ctx && k, "null argument");
+    PADNE_REQUIRE(k->ctx == ctx, "the plan belongs to another context");
+    PADNE_REQUIRE(k->finished && k->v_final != nullptr,
+                  "padne_kkt_current_cases follows padne_kkt_finish_block, with no solve on the plan in between");
+    PADNE_REQUIRE(n_cols == k->finished_cols, "as many columns as the finished block has");
+    PADNE_REQUIRE(n_cut >= 0 && n_cut <= 4096, "between 0 and 4096 cuts");
+    PADNE_REQUIRE(mesh_max_out && mesh_face_out && mesh_power_out, "null argument");
+    PADNE_REQUIRE(n_cut == 0 || (mesh_layer && cut_layer && cut_xy && cut_out), "null argument");
+    PADNE_REQUIRE((J_out == nullptr) == (mag_out == nullptr), "J_out and mag_out are given or left out together");
+    PADNE_TRY(check_cut_segments(n_cut, cut_xy));
+    const padne_csr *L = k->L;
+    PADNE_REQUIRE(L->mesh_n_mesh > 0 && L->mesh_xy != nullptr,
+                  "the system matrix does not carry a mesh (only padne_assemble_system keeps it)");
+    PADNE_REQUIRE(L->mesh_n_vert <= k->N, "the mesh has more vertices than the system has unknowns");
+    PADNE_REQUIRE(n_tri == L->mesh_n_tri && n_mesh == L->mesh_n_mesh, "n_tri and n_mesh must be those of the system's mesh");
+    PADNE_REQUIRE(n_tri == 0 || (env_out && env_case_out), "null argument");
+    const bool fields = J_out != nullptr;
+    PADNE_HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    std::vector<long long> tile;
+    PADNE_TRY(mesh_tiles(ctx, L, tile));
+    const long long n_blocks = tile[(size_t)n_mesh];
+    const size_t nb = (size_t)(n_blocks > 0 ? n_blocks : 1), nt = (size_t)(n_tri > 0 ? n_tri : 1), nc = (size_t)n_cols;
+    Scratch sc(ctx);
+    long long *d_tile = nullptr, *d_mface = nullptr;
+    double *d_J = nullptr, *d_mag = nullptr, *d_env = nullptr, *d_box = nullptr, *d_mmax = nullptr, *d_mpow = nullptr;
+    int *d_case = nullptr, *d_bad = nullptr;
+    PADNE_TRY(sc.alloc(&d_tile, (size_t)n_mesh + 1));
+    if (fields) {
+        PADNE_TRY(sc.alloc(&d_J, 2 * nt * nc));
+        PADNE_TRY(sc.alloc(&d_mag, nt * nc));
+    }
+    PADNE_TRY(sc.alloc(&d_env, nt));
+    PADNE_TRY(sc.alloc(&d_case, nt));
+    PADNE_TRY(sc.alloc(&d_box, 4 * nb));
+    PADNE_TRY(sc.alloc(&d_mmax, (size_t)n_mesh * nc));
+    PADNE_TRY(sc.alloc(&d_mface, (size_t)n_mesh * nc));
+    PADNE_TRY(sc.alloc(&d_mpow, (size_t)n_mesh * nc));
+    PADNE_TRY(sc.alloc(&d_bad, 1));
+    PADNE_HIP_CHECK(hipMemcpyAsync(d_tile, tile.data(), sizeof(long long) * ((size_t)n_mesh + 1), hipMemcpyHostToDevice, s));
+    PADNE_HIP_CHECK(hipMemsetAsync(d_bad, 0, sizeof(int), s));
+    PADNE_TRY(launch_current_cases_faces(ctx, L, d_tile, n_blocks, n_cols, k->v_final, d_J, d_mag, d_env, d_case, d_box, d_mmax,
+                                         d_mface, d_mpow, d_bad));
+    if (n_cut > 0) {
+        std::vector<double> box(4 * nb);
+        if (n_blocks > 0)
+            PADNE_HIP_CHECK(hipMemcpyAsync(box.data(), d_box, sizeof(double) * 4 * (size_t)n_blocks, hipMemcpyDeviceToHost, s));
+        PADNE_HIP_CHECK(hipStreamSynchronize(s));
+        std::vector<int> pair_cut;
+        std::vector<long long> pair_tile, pair_off;
+        list_cut_pairs(n_cut, n_mesh, mesh_layer, cut_layer, cut_xy, tile, box, pair_cut, pair_tile, pair_off);
+        const long long n_pairs = (long long)pair_tile.size();
+        PADNE_REQUIRE(n_pairs <= 0x7fffffffLL, "too many (cut, tile) pairs for one launch");
+        const size_t np = (size_t)(n_pairs > 0 ? n_pairs : 1);
+        double *d_cut_xy = nullptr, *d_cut = nullptr;
+        int *d_pair_cut = nullptr;
+        long long *d_pair_tile = nullptr;
+        PADNE_TRY(sc.alloc(&d_cut_xy, 4 * (size_t)n_cut));
+        PADNE_TRY(sc.alloc(&d_cut, (size_t)n_cut * nc));
+        PADNE_TRY(sc.alloc(&d_pair_cut, np));
+        PADNE_TRY(sc.alloc(&d_pair_tile, np));
+        PADNE_HIP_CHECK(hipMemcpyAsync(d_cut_xy, cut_xy, sizeof(double) * 4 * (size_t)n_cut, hipMemcpyHostToDevice, s));
+        if (n_pairs > 0) {
+            PADNE_HIP_CHECK(hipMemcpyAsync(d_pair_cut, pair_cut.data(), sizeof(int) * (size_t)n_pairs, hipMemcpyHostToDevice, s));
+            PADNE_HIP_CHECK(hipMemcpyAsync(d_pair_tile, pair_tile.data(), sizeof(long long) * (size_t)n_pairs, hipMemcpyHostToDevice, s));
+        }
+        PADNE_TRY(launch_current_cases_cuts(ctx, L, d_tile, n_cols, k->v_final, n_cut, d_cut_xy, n_pairs, d_pair_cut, d_pair_tile,
+                                            pair_off.data(), d_cut, d_bad));
+        PADNE_HIP_CHECK(hipMemcpyAsync(cut_out, d_cut, sizeof(double) * (size_t)n_cut * nc, hipMemcpyDeviceToHost, s));
+        PADNE_HIP_CHECK(hipStreamSynchronize(s));       // (the copies read the host vectors above before they go)
+    }
+    int h_bad = 0;
+    PADNE_HIP_CHECK(hipMemcpyAsync(&h_bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    PADNE_HIP_CHECK(hipMemcpyAsync(mesh_max_out, d_mmax, sizeof(double) * (size_t)n_mesh * nc, hipMemcpyDeviceToHost, s));
+    PADNE_HIP_CHECK(hipMemcpyAsync(mesh_face_out, d_mface, sizeof(long long) * (size_t)n_mesh * nc, hipMemcpyDeviceToHost, s));
+    PADNE_HIP_CHECK(hipMemcpyAsync(mesh_power_out, d_mpow, sizeof(double) * (size_t)n_mesh * nc, hipMemcpyDeviceToHost, s));
+    PADNE_HIP_CHECK(hipStreamSynchronize(s));
+    if (h_bad) {
+        set_error("invalid argument: triangle index out of range");
+        return PADNE_E_INVALID;
+    }
+    if (n_tri == 0) return PADNE_OK;
+    if (fields) {
+        PADNE_TRY(parallel_copy(k, J_out, d_J, sizeof(double) * 2 * (size_t)n_tri * nc, hipMemcpyDeviceToHost));
+        PADNE_TRY(parallel_copy(k, mag_out, d_mag, sizeof(double) * (size_t)n_tri * nc, hipMemcpyDeviceToHost));
+    }
+    PADNE_TRY(parallel_copy(k, env_out, d_env, sizeof(double) * (size_t)n_tri, hipMemcpyDeviceToHost));
+    return parallel_copy(k, env_case_out, d_case, sizeof(int32_t) * (size_t)n_tri, hipMemcpyDeviceToHost);
 }
 
 // The gradient-recovery error estimate of column 0 of the finished block (error.hip; DESIGN.md, "Error estimate"): the

@@ -1109,11 +1109,11 @@ def block_plan_inputs(L: SystemMatrix, rows, cols, vals, n_cols: int):
 
 
 def _solve_block_on_device(L: SystemMatrix, rows, cols, vals, n_cols: int, power_rows: int, laps: _Laps,
-                           currents: bool = False):
+                           currents: bool = False, current_cols: int = 1):
     """solve_system on the block given by its triples, up to the potentials: reduction, plan, ``solve_block_coo``,
     ``_finish_block``.  The final V stays on the device for the face kernels that follow; ``power_rows``: the rows of the
     power-density array those return, made ready while the device solves (with ``currents``, the arrays of
-    ``current_report`` too).  Returns (plan, V (N, n_cols), ||L v_j - r_j|| (n_cols,), SolveResult, n_tri, n_mesh); ``laps``
+    ``current_report`` too, or those of ``current_cases`` for ``current_cols`` columns).  Returns (plan, V (N, n_cols), ||L v_j - r_j|| (n_cols,), SolveResult, n_tri, n_mesh); ``laps``
     receives stage1 and stage2."""
     red, known_idx, known_val = block_plan_inputs(L, rows, cols, vals, n_cols)
     plan = _plan_for(L, L.dev, L.layout, red, _wants_reorder(L, None), False)
@@ -1122,7 +1122,8 @@ def _solve_block_on_device(L: SystemMatrix, rows, cols, vals, n_cols: int, power
     n_mesh = len(L.mesh_offsets) - 1 if L.mesh_offsets is not None else 0
     probes, res = plan.solve_block_coo(n_cols, rows, cols, vals, known_idx, known_val, red.regulator_columns, members,
                                        rtol=RTOL, max_iter=MAX_ITER, abs_residual_target=ABS_RESIDUAL_TARGET, power_tri=n_tri,
-                                       power_rows=power_rows, current_tri=n_tri if currents else 0)
+                                       power_rows=power_rows, current_tri=n_tri if currents else 0,
+                                       current_cols=current_cols)
     laps.lap("stage1")
     V, residual_norms = _finish_block(plan, red, members, probes, n_cols)
     laps.lap("stage2")
@@ -1685,6 +1686,183 @@ def solve_currents(prob, cuts=(), mesher_config: Optional[mesh.Mesher.Config] = 
     meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
     return solve_meshed_currents(prob, meshes, mesh_index_to_layer_index,
                                  [Cut(prob.layers[i], a, b) for i, a, b in cuts])
+
+
+# --------------------------------------------------------------------------------------------
+# load-case currents: the currents of every load case of one block, and their envelope (DESIGN.md "Load-case currents")
+# --------------------------------------------------------------------------------------------
+
+
+@dataclass
+class CurrentEnvelope:
+    """The worst case of every quantity of the CurrentReports of one block of load cases (see
+    :func:`solve_meshed_load_case_currents`): the maximum over the cases of an absolute value, with the lowest case that
+    attains it (:func:`envelope_of`)."""
+    magnitudes: list      # per layer, per mesh: TwoForm of max_j |J_j| per face [A/mm]
+    cases: list           # per layer, per mesh: (n_faces,) int32, the case of that maximum
+    hotspots: list        # per layer: (max |J|, case, mesh index within the layer, face index, centroid x, y), None without faces
+    layers: list          # per layer: (the largest power in its copper [W], case)
+    elements: dict        # lumped element of the Problem -> {"current": (signed value of largest magnitude, case), "power": ...}
+    cuts: list            # per cut: (signed current of largest magnitude [A], case)
+
+
+def envelope_of(values) -> tuple:
+    """(max_j |values[j]|, the lowest j that attains it) down the first axis of ``values`` (k, n): (n,) float64 and (n,)
+    int32.  The rule is sequential over the cases: case 0 first, and a later case replaces the value only when its
+    magnitude is strictly greater -- so ties go to the lowest case, and an entry that is NaN in case 0 stays NaN with case
+    0.  It is the rule the device applies per face."""
+    a = np.abs(np.asarray(values, dtype=DTYPE))
+    if a.ndim != 2 or a.shape[0] < 1:
+        raise ValueError("values must have shape (k, n) with k >= 1")
+    best, case = a[0].copy(), np.zeros(a.shape[1], dtype=np.int32)
+    for j in range(1, a.shape[0]):
+        greater = a[j] > best
+        best[greater] = a[j][greater]
+        case[greater] = j
+    return best, case
+
+
+def _signed_envelope(values) -> list:
+    """Per column of ``values`` (k, n): (the signed entry of largest magnitude, its case), by :func:`envelope_of`."""
+    values = np.asarray(values, dtype=DTYPE).reshape(len(values), -1)
+    _, case = envelope_of(values)
+    return [(float(values[c, i]), int(c)) for i, c in enumerate(case)]
+
+
+_ROW_VALUE = {"I": 3, "V": 3, "REG": 5}        # where global_elements' rows hold the value a load case may set
+
+
+def _case_element_rows(pairs, rows, case: dict) -> list:
+    """The element ``rows`` (those of ``pairs``, global_elements' order) with the values of one checked load case."""
+    out = []
+    for (element, _), row in zip(pairs, rows):
+        if element in case:
+            at = _ROW_VALUE[row[0]]
+            row = row[:at] + (float(case[element]),) + row[at + 1:]
+        out.append(row)
+    return out
+
+
+def solve_meshed_load_case_currents(prob, meshes, mesh_index_to_layer_index, cases, cuts=(), *, per_case_fields=True,
+                                    filtered_networks=None, disconnected_meshes_by_layer=None, partition=None,
+                                    timings: Optional[dict] = None):
+    """``solve_meshed_load_cases`` together with where the current goes in every case and in the worst case: ([Solution per
+    case], [CurrentReport per case], CurrentEnvelope).
+
+    Solution j is what ``solve_meshed_load_cases`` gives for case j of a block; ``reports[j]`` is the CurrentReport of
+    ``solve_meshed_currents`` for that case, its ``elements`` keyed by the elements of the substituted Problem.  The
+    envelope holds, for every face, layer, element and cut, the maximum over the cases of the absolute value and the
+    lowest case that attains it (:func:`envelope_of`); its ``elements`` are keyed by the elements of ``prob``.  A layer's
+    envelope hotspot is the hotspot of the lowest case whose hotspot is the largest, so ties go to the lowest case and then
+    to the lowest global face.
+
+    One indexing, one assembly and one block solve of k columns; the face and cut kernels then walk all columns of the V
+    the device holds and reduce over the cases there.  With ``per_case_fields=False`` the device neither writes nor sends
+    home any per-case J or |J|: ``vectors`` and ``magnitudes`` of every report are None and everything else has the same
+    bits.  One case goes through the same path.  ValueError, before anything reaches the device, for invalid cases
+    (:func:`check_load_cases`), invalid cuts (:func:`check_cuts`) and a ``partition`` over several GPUs.  ``timings`` (a
+    dict) receives the host time of each step in seconds."""
+    _refuse_partition(partition, "load-case currents")
+    cases = check_load_cases(prob, cases)
+    cuts = check_cuts(prob, cuts)
+    substituted = [substitute_load_case(prob, case) for case in cases]
+    k, n_layers, fields = len(cases), len(prob.layers), bool(per_case_fields)
+    laps = _Laps(timings)
+    board = index_board(prob, meshes, mesh_index_to_layer_index, filtered_networks, disconnected_meshes_by_layer)
+    pairs = global_elements(board.filtered_networks, board.node_indexer)
+    laps.lap("indexing")
+    with board.assembled() as (L, _):
+        rows, cols, vals = stamp_load_cases(board.filtered_networks, board.node_indexer, L.shape[0], cases)
+        laps.lap("assembly")
+        log.info(f"Solving {k} load case(s) as one block, with their currents")
+        plan, V, residual_norms, res, n_tri, _n_mesh = _solve_block_on_device(L, rows, cols, vals, k, k, laps, currents=fields,
+                                                                              current_cols=k)
+        power = J = mag = env = env_case = mesh_max = mesh_face = totals = None
+        cut_values = np.zeros((k, len(cuts)))
+        if n_tri:
+            power = plan.power_density_block(k, n_tri)
+            J, mag, env, env_case, mesh_max, mesh_face, totals, cut_values = plan.current_cases(
+                k, n_tri, np.asarray(mesh_index_to_layer_index, dtype=np.int32), [c[0] for c in cuts],
+                np.array([[*a, *b] for _, a, b in cuts], dtype=DTYPE).reshape(-1, 4), fields=fields)
+        laps.lap("currents")
+    laps.lap()
+    _warn_if_block_stalled(res, residual_norms, cols, vals, k)
+    log.info("Producing the solution objects, the current reports and the envelope")
+    solutions = [_column_solution(board, sub, np.ascontiguousarray(V[:, j]), residual_norms[j], res,
+                                  None if power is None else power[j], f"Load case {j}: " if k > 1 else "")
+                 for j, (sub, _) in enumerate(substituted)]
+    local, Vu = _gather_element_rows([row for _, row in pairs], V, _ROW_UNKNOWNS)
+    reports, flows_by_case = [], []
+    for j, (case, (_, renamed)) in enumerate(zip(cases, substituted)):
+        flows = element_flows(_case_element_rows(pairs, local, case), Vu[:, j])
+        flows_by_case.append(flows)
+        case_elements = [e for network in board.filtered_networks for e in renamed.get(id(network), network).elements]
+        vectors, magnitudes, hotspots, layer_power = [], [], [], []
+        for layer_i in range(n_layers):
+            vecs, forms, total, best = [], [], 0.0, None
+            for in_layer, (mesh_i, msh, lo, hi) in enumerate(board.layer_meshes(layer_i)):
+                if n_tri:
+                    total += float(totals[j, mesh_i])
+                    # meshes come in global face order: a later mesh wins only with a strictly larger |J|
+                    if mesh_face[j, mesh_i] >= 0 and (best is None or mesh_max[j, mesh_i] > best[0]):
+                        face = int(mesh_face[j, mesh_i] - lo)
+                        cx, cy = msh.points[msh.triangles[face]].mean(axis=0)
+                        best = (float(mesh_max[j, mesh_i]), in_layer, face, float(cx), float(cy))
+                if fields:
+                    tf = mesh.TwoForm(msh)
+                    if J is not None:
+                        vecs.append(J[j, lo:hi])              # views of this call's own result arrays: no copies
+                        tf.values = mag[j, lo:hi]
+                    else:
+                        vecs.append(np.zeros((len(msh.triangles), 2), dtype=DTYPE))
+                    forms.append(tf)
+            vectors.append(vecs)
+            magnitudes.append(forms)
+            hotspots.append(best)
+            layer_power.append(total)
+        reports.append(CurrentReport(vectors=vectors if fields else None, magnitudes=magnitudes if fields else None,
+                                     hotspots=hotspots, layers=layer_power,
+                                     elements={element: flows[i] for i, element in enumerate(case_elements)},
+                                     cuts=[float(c) for c in cut_values[j]]))
+    # the envelope: per face from the device, everything else by the same rule from the per-case scalars
+    env_forms, env_cases, env_hotspots = [], [], []
+    for layer_i in range(n_layers):
+        forms, which = [], []
+        for _mesh_i, msh, lo, hi in board.layer_meshes(layer_i):
+            tf = mesh.TwoForm(msh)
+            if env is not None:
+                tf.values = env[lo:hi]
+            forms.append(tf)
+            which.append(env_case[lo:hi] if env is not None else np.zeros(len(msh.triangles), dtype=np.int32))
+        env_forms.append(forms)
+        env_cases.append(which)
+        spots = [rep.hotspots[layer_i] for rep in reports]
+        if spots[0] is None:
+            env_hotspots.append(None)
+        else:
+            c = int(envelope_of([[spot[0]] for spot in spots])[1][0])
+            env_hotspots.append((spots[c][0], c, *spots[c][1:]))
+    env_elements = {}
+    for i, (element, _) in enumerate(pairs):
+        keys = list(flows_by_case[0][i])
+        env_elements[element] = dict(zip(keys, _signed_envelope([[flows[i][key] for key in keys] for flows in flows_by_case])))
+    envelope = CurrentEnvelope(magnitudes=env_forms, cases=env_cases, hotspots=env_hotspots,
+                               layers=_signed_envelope([rep.layers for rep in reports]), elements=env_elements,
+                               cuts=_signed_envelope([rep.cuts for rep in reports]))
+    laps.lap("solutions")
+    return solutions, reports, envelope
+
+
+def solve_load_case_currents(prob, cases, cuts=(), mesher_config: Optional[mesh.Mesher.Config] = None, *, mesher=None,
+                             per_case_fields=True, partition=None):
+    """``solve`` for several load cases with their currents and the envelope (see
+    :func:`solve_meshed_load_case_currents`): the board is meshed once."""
+    _refuse_partition(partition, "load-case currents")
+    cases = check_load_cases(prob, cases)
+    cuts = check_cuts(prob, cuts)
+    meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
+    return solve_meshed_load_case_currents(prob, meshes, mesh_index_to_layer_index, cases,
+                                           [Cut(prob.layers[i], a, b) for i, a, b in cuts], per_case_fields=per_case_fields)
 
 
 # --------------------------------------------------------------------------------------------
