@@ -361,7 +361,8 @@ int padne_kkt_power_density_block(padne_ctx *ctx, padne_kkt *plan, int32_t n_col
  * padne_kkt_power_density_block; 1 <= n_obj <= 4096 and finite weights, else PADNE_E_INVALID. */
 int padne_kkt_sensitivity_block(padne_ctx *ctx, padne_kkt *plan, int32_t n_cols, int32_t n_obj, const double *weights,
                                 double *power_out, double *density_out, double *mesh_total_out);
-/* Currents over the mesh `L` keeps, from column 0 of the block the last padne_kkt_finish_block left on the device.  Per face
+/* Currents over the mesh `L` keeps, from column 0 of the block the last padne_kkt_finish_block left on the device (a block
+ * of any width: padne_kkt_current_cases below with one reported column, without its envelope and its power).  Per face
  * t, with the face gradient of padne_csr_power_density and the sheet conductance sigma of its mesh: J_out[n_tri][2] =
  * -sigma grad V (so |J|^2 / sigma is the power density) and mag_out[n_tri] = |J|; per mesh m, mesh_max_out[m] = the
  * largest |J| of its faces and mesh_face_out[m] = that face (global index, the lowest on a tie; -1.0 and -1 for a mesh
@@ -376,7 +377,7 @@ int padne_kkt_current_report(padne_ctx *ctx, padne_kkt *plan, int32_t n_cols, in
                              const int32_t *mesh_layer, int32_t n_cut, const int32_t *cut_layer, const double *cut_xy,
                              double *J_out, double *mag_out, double *mesh_max_out, int64_t *mesh_face_out, double *cut_out);
 /* padne_kkt_current_report for every column j of the block the last padne_kkt_finish_block left on the device (load cases),
- * and the envelope over the columns.  Column-major results: J_out[n_cols][n_tri][2], mag_out[n_cols][n_tri],
+ * and the envelope over the columns: the two entries are one function and one set of kernels.  Column-major results: J_out[n_cols][n_tri][2], mag_out[n_cols][n_tri],
  * mesh_max_out / mesh_face_out[n_cols][n_mesh], cut_out[n_cols][n_cut]; row 0 of each holds the bits padne_kkt_current_report
  * gives (any n_cols >= 1).  mesh_power_out[n_cols][n_mesh] = per mesh the sum over its faces of sigma sum_{edges} w_ik
  * (V_i - V_k)^2 with the assembly's |cot|/2 weights: for column 0 the bits of padne_kkt_sensitivity_block's mesh_total_out
@@ -384,6 +385,7 @@ int padne_kkt_current_report(padne_ctx *ctx, padne_kkt *plan, int32_t n_cols, in
  * lowest column that attains it: the columns are visited in order from column 0 and a later one replaces the value only
  * when strictly greater, so a face whose |J| is NaN in column 0 keeps NaN and case 0.  J_out and mag_out may both be null
  * ("envelope only"): then no per-column field is written on the device or copied home; every other result is the same.
+ * env_out and env_case_out may both be null likewise: then no envelope is computed.
  * Everything is summed in a fixed order: two calls give the same bits.  Preconditions and errors as
  * padne_kkt_current_report. */
 int padne_kkt_current_cases(padne_ctx *ctx, padne_kkt *plan, int32_t n_cols, int64_t n_tri, int32_t n_mesh,

@@ -795,41 +795,40 @@ class KktPlan:
                                                          _ptr(power[0], _PF64), _ptr(density, _PF64), _ptr(totals, _PF64)))
         return power[0], density, totals
 
+    @staticmethod
+    def _cut_arguments(mesh_layer, cut_layer, cut_xy):
+        """The arrays as the currents entries take them; ValueError when the two cut arrays do not list the same cuts."""
+        ml, cl, xy = _i32(mesh_layer).reshape(-1), _i32(cut_layer).reshape(-1), _f64(cut_xy).reshape(-1, 4)
+        if xy.shape[0] != cl.shape[0]:
+            raise ValueError("cut_layer and cut_xy must list the same cuts")
+        return ml, cl, xy
+
     def current_report(self, n_cols: int, n_tri: int, mesh_layer, cut_layer, cut_xy):
         """The currents of column 0 of the block the last ``finish_block`` left on the device, over the mesh the system was
         assembled from (``n_tri`` triangles; ``mesh_layer`` (n_mesh,): the layer of each mesh).  Cut c is the segment
         ``cut_xy[c]`` = (start x, y, end x, y) on layer ``cut_layer[c]``.  Returns (J (n_tri, 2) = -sigma grad V, |J| (n_tri,),
         the largest |J| of each mesh (n_mesh,), its face (n_mesh,) as a global index (-1 for a mesh without faces), the
-        current through each cut (n_cut,)) (include/padne_hip.h).  Raises ValueError as ``sensitivity_block`` does, for more
-        than 4096 cuts, for end points that are not finite and for a cut whose start is its end."""
-        ml = _i32(mesh_layer).reshape(-1)
-        cl = _i32(cut_layer).reshape(-1)
-        xy = _f64(cut_xy).reshape(-1, 4)
-        if xy.shape[0] != cl.shape[0]:
-            raise ValueError("cut_layer and cut_xy must list the same cuts")
+        current through each cut (n_cut,)): ``current_cases`` of one column, less the envelope and the power.  Raises
+        ValueError as ``sensitivity_block`` does, for over 4096 cuts, end points not finite and a cut of no length."""
+        ml, cl, xy = self._cut_arguments(mesh_layer, cut_layer, cut_xy)
         n_tri, n_mesh, n_cut = int(n_tri), ml.shape[0], cl.shape[0]
         buf = self._result_array((3 * n_tri,), "cur")
         J, mag = buf[:2 * n_tri].reshape(n_tri, 2), buf[2 * n_tri:]
-        mesh_max = np.empty(n_mesh, dtype=np.float64)
-        mesh_face = np.empty(n_mesh, dtype=np.int64)
+        mesh_max, mesh_face = np.empty(n_mesh, dtype=np.float64), np.empty(n_mesh, dtype=np.int64)
         cuts = np.empty(n_cut, dtype=np.float64)
         _check(self.ctx._lib.padne_kkt_current_report(self.ctx._h, self._h, int(n_cols), n_tri, n_mesh, _ptr(ml, _PI32), n_cut,
                                                       _ptr(cl, _PI32), _ptr(xy, _PF64), _ptr(J, _PF64), _ptr(mag, _PF64),
                                                       _ptr(mesh_max, _PF64), _ptr(mesh_face, _PI64), _ptr(cuts, _PF64)))
         return J, mag, mesh_max, mesh_face, cuts
 
-    def current_cases(self, n_cols: int, n_tri: int, mesh_layer, cut_layer, cut_xy, fields: bool = True):
+    def current_cases(self, n_cols: int, n_tri: int, mesh_layer, cut_layer, cut_xy, fields: bool = True, envelope: bool = True):
         """``current_report`` for every column of the block the last ``finish_block`` left on the device, and the envelope
         over the columns.  Returns (J (n_cols, n_tri, 2), |J| (n_cols, n_tri) -- both None without ``fields``: the device
         then writes and sends home no per-column field --, max_j |J_j| (n_tri,), the lowest column that attains it (n_tri,)
-        int32, and per column the largest |J| of each mesh (n_cols, n_mesh), its face (n_cols, n_mesh), the power of each
+        int32 -- both None without ``envelope``, likewise --, and per column the largest |J| of each mesh (n_cols, n_mesh), its face (n_cols, n_mesh), the power of each
         mesh in the |cot|/2 weights' form (n_cols, n_mesh) and the current through each cut (n_cols, n_cut))
         (include/padne_hip.h).  Row 0 holds ``current_report``'s bits.  Raises ValueError as ``current_report`` does."""
-        ml = _i32(mesh_layer).reshape(-1)
-        cl = _i32(cut_layer).reshape(-1)
-        xy = _f64(cut_xy).reshape(-1, 4)
-        if xy.shape[0] != cl.shape[0]:
-            raise ValueError("cut_layer and cut_xy must list the same cuts")
+        ml, cl, xy = self._cut_arguments(mesh_layer, cut_layer, cut_xy)
         n_cols, n_tri, n_mesh, n_cut = int(n_cols), int(n_tri), ml.shape[0], cl.shape[0]
         if n_cols < 1:
             raise ValueError("a block has at least one column")
@@ -837,15 +836,15 @@ class KktPlan:
         if fields:
             buf = self._result_array((3 * n_cols * n_tri,), "cur")
             J, mag = buf[:2 * n_cols * n_tri].reshape(n_cols, n_tri, 2), buf[2 * n_cols * n_tri:].reshape(n_cols, n_tri)
-        env = np.empty(n_tri, dtype=np.float64)
-        env_case = np.empty(n_tri, dtype=np.int32)
+        env = np.empty(n_tri, dtype=np.float64) if envelope else None
+        env_case = np.empty(n_tri, dtype=np.int32) if envelope else None
         mesh_max, mesh_power = (np.empty((n_cols, n_mesh), dtype=np.float64) for _ in range(2))
         mesh_face = np.empty((n_cols, n_mesh), dtype=np.int64)
         cuts = np.empty((n_cols, n_cut), dtype=np.float64)
         _check(self.ctx._lib.padne_kkt_current_cases(
             self.ctx._h, self._h, n_cols, n_tri, n_mesh, _ptr(ml, _PI32), n_cut, _ptr(cl, _PI32), _ptr(xy, _PF64),
-            None if J is None else _ptr(J, _PF64), None if mag is None else _ptr(mag, _PF64), _ptr(env, _PF64),
-            _ptr(env_case, _PI32), _ptr(mesh_max, _PF64), _ptr(mesh_face, _PI64), _ptr(mesh_power, _PF64), _ptr(cuts, _PF64)))
+            None if J is None else _ptr(J, _PF64), None if mag is None else _ptr(mag, _PF64),
+            None if env is None else _ptr(env, _PF64), None if env_case is None else _ptr(env_case, _PI32), _ptr(mesh_max, _PF64), _ptr(mesh_face, _PI64), _ptr(mesh_power, _PF64), _ptr(cuts, _PF64)))
         return J, mag, env, env_case, mesh_max, mesh_face, mesh_power, cuts
 
     def error_estimate(self, n_cols: int, n_tri: int, n_vert: int, n_mesh: int):

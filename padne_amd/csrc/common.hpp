@@ -381,6 +381,19 @@ int lanczos_enqueue(padne_ctx *ctx, const padne_csr *a, int steps, LanczosJob *j
 int lanczos_finish(LanczosJob *job, double *lambda);
 // assemble.hip: rows of `top` followed by the rows of `bottom`, n_cols columns
 int csr_vstack(padne_ctx *ctx, const padne_csr *top, const padne_csr *bottom, int64_t n_cols, padne_csr **out);
+// fields.hip: the face kernels over the mesh a matrix keeps, on a block V_dev[..][n_cols] (kkt.hip's post-processing
+// entries; the arguments are described at the definitions).  Asynchronous; bad_dev is a zeroed device int.
+int launch_power_density_block(padne_ctx *ctx, const padne_csr *m, int n_cols, const double *V_dev, double *out_dev,
+                               int *bad_dev);
+int launch_sensitivity_block(padne_ctx *ctx, const padne_csr *m, const long long *tile_off_host, int n_cols, int n_obj,
+                             const double *W_dev, const double *V_dev, double *power_dev, double *density_dev, double *total_dev,
+                             int *bad_dev);
+int launch_current_faces(padne_ctx *ctx, const padne_csr *m, const long long *tile_dev, long long n_blocks, int n_cols,
+                         int n_report, const double *V_dev, double *J_dev, double *mag_dev, double *env_dev, int *env_case_dev,
+                         double *box_dev, double *mesh_max_dev, long long *mesh_face_dev, double *mesh_power_dev, int *bad_dev);
+int launch_current_cuts(padne_ctx *ctx, const padne_csr *m, const long long *tile_dev, int n_cols, int n_report,
+                        const double *V_dev, int n_cut, const double *cut_xy_dev, long long n_pairs, const int *pair_cut_dev,
+                        const long long *pair_tile_dev, const long long *pair_off_host, double *cut_dev, int *bad_dev);
 
 // Per-context caching allocator.  All work of a context is ordered on its one stream, so a block handed back
 // may be reused by later launches without synchronisation.  Blocks are kept (up to kPoolCacheLimit) until the

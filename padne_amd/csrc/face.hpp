@@ -1,6 +1,6 @@
-// Per-face arithmetic shared by the face kernels of assemble.hip and the field sampler of sample.hip.  Every translation
-// unit that includes this is compiled with -ffp-contract=off: the expressions round exactly as written, which is what lets
-// a numpy restatement reproduce their bits.
+// Per-face arithmetic shared by the assembly (assemble.hip), the face kernels (fields.hip) and the field sampler
+// (sample.hip).  Every translation unit that includes this is compiled with -ffp-contract=off: the expressions round
+// exactly as written, which is what lets a numpy restatement reproduce their bits.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -15,6 +15,15 @@ __device__ __forceinline__ int find_segment(const long long *__restrict__ offs, 
         if (offs[mid] <= i) lo = mid; else hi = mid;
     }
     return lo;
+}
+
+// |cot(theta_o)| / 2 for the edge (i,k) seen from the opposite corner o   -- mesh.py:136-138
+__device__ __forceinline__ double cot_half(double ix, double iy, double kx, double ky, double ox, double oy) {
+    const double vix = ix - ox, viy = iy - oy;
+    const double vkx = kx - ox, vky = ky - oy;
+    const double dot = vix * vkx + viy * vky;
+    const double cross = vix * vky - viy * vkx;
+    return fabs(dot / cross) / 2;
 }
 
 // ---- power density ---------------------------------------------------------------------------

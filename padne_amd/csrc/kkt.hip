@@ -22,24 +22,6 @@ namespace padne {
 int csr_relabel(padne_ctx *ctx, const padne_csr *m, const int32_t *row_map, int64_t n_rows_out, const int32_t *col_map,
                 int64_t n_cols_out, double scale, padne_csr **out);
 int amg_setup(padne_ctx *ctx, padne_csr *A0);
-int launch_power_density_block(padne_ctx *ctx, const padne_csr *m, int n_cols, const double *V_dev, double *out_dev,
-                               int *bad_dev);
-int launch_sensitivity_block(padne_ctx *ctx, const padne_csr *m, const long long *tile_off_host, int n_cols, int n_obj,
-                             const double *W_dev, const double *V_dev, double *power_dev, double *density_dev, double *total_dev,
-                             int *bad_dev);
-int launch_current_faces(padne_ctx *ctx, const padne_csr *m, const long long *tile_dev, long long n_blocks, int n_cols,
-                         const double *V_dev, double *J_dev, double *mag_dev, double *tile_max_dev, long long *tile_face_dev,
-                         double *box_dev, double *mesh_max_dev, long long *mesh_face_dev, int *bad_dev);
-int launch_cut_currents(padne_ctx *ctx, const padne_csr *m, const long long *tile_dev, int n_cols, const double *V_dev,
-                        int n_cut, const double *cut_xy_dev, long long n_pairs, const int *pair_cut_dev,
-                        const long long *pair_tile_dev, const long long *pair_off_host, double *cut_dev, int *bad_dev);
-int launch_current_cases_faces(padne_ctx *ctx, const padne_csr *m, const long long *tile_dev, long long n_blocks, int n_cols,
-                               const double *V_dev, double *J_dev, double *mag_dev, double *env_dev, int *env_case_dev,
-                               double *box_dev, double *mesh_max_dev, long long *mesh_face_dev, double *mesh_power_dev,
-                               int *bad_dev);
-int launch_current_cases_cuts(padne_ctx *ctx, const padne_csr *m, const long long *tile_dev, int n_cols, const double *V_dev,
-                              int n_cut, const double *cut_xy_dev, long long n_pairs, const int *pair_cut_dev,
-                              const long long *pair_tile_dev, const long long *pair_off_host, double *cut_dev, int *bad_dev);
 int csr_error_estimate(padne_ctx *ctx, const padne_csr *L, int **vptr, int **vface, int n_cols, const double *V_dev,
                        double *G_dev, double *eta_dev, double *mesh_E_dev, double *mesh_P_dev, double *mesh_max_dev,
                        long long *mesh_face_dev, int *bad_dev);
@@ -1120,18 +1102,46 @@ extern "C" int padne_kkt_solve_block_coo(padne_ctx *ctx, padne_kkt *k, int32_t n
                            probe_idx, probe_out, opts, abs_residual_target, info);
 }
 
-// sigma |grad V|^2 of every column of the finished block, from the V that stage 2 left on the device: one launch over the
-// triangles (power_density_block_kernel), then [n_cols][n_tri] home on the copy streams
-extern "C" int padne_kkt_power_density_block(padne_ctx *ctx, padne_kkt *k, int32_t n_cols, double *out_host) {
+// What every post-processing entry asks before it reads the V that stage 2 left on the device: the plan is the context's, a
+// block is finished (`entry` names the caller in the message) and has n_cols columns, and the system matrix carries a mesh
+// of no more vertices than the system has unknowns.
+static int require_finished_block(const char *entry, padne_ctx *ctx, const padne_kkt *k, int32_t n_cols) {
     PADNE_REQUIRE(ctx && k, "null argument");
     PADNE_REQUIRE(k->ctx == ctx, "the plan belongs to another context");
     PADNE_REQUIRE(k->finished && k->v_final != nullptr,
-                  "padne_kkt_power_density_block follows padne_kkt_finish_block, with no solve on the plan in between");
+                  (std::string(entry) + " follows padne_kkt_finish_block, with no solve on the plan in between").c_str());
     PADNE_REQUIRE(n_cols == k->finished_cols, "as many columns as the finished block has");
     const padne_csr *L = k->L;
     PADNE_REQUIRE(L->mesh_n_mesh > 0 && L->mesh_xy != nullptr,
                   "the system matrix does not carry a mesh (only padne_assemble_system keeps it)");
     PADNE_REQUIRE(L->mesh_n_vert <= k->N, "the mesh has more vertices than the system has unknowns");
+    return PADNE_OK;
+}
+
+// The flag a face kernel sets when a triangle names a vertex outside its mesh: a zeroed device int from `sc` ...
+static int bad_flag_alloc(Scratch &sc, hipStream_t s, int **d_bad) {
+    PADNE_TRY(sc.alloc(d_bad, 1));
+    PADNE_HIP_CHECK(hipMemsetAsync(*d_bad, 0, sizeof(int), s));
+    return PADNE_OK;
+}
+
+// ... and its read-back: waits for everything queued on `s` (the caller's own small copies home included)
+static int bad_flag_check(hipStream_t s, const int *d_bad) {
+    int h_bad = 0;
+    PADNE_HIP_CHECK(hipMemcpyAsync(&h_bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    PADNE_HIP_CHECK(hipStreamSynchronize(s));
+    if (h_bad) {
+        set_error("invalid argument: triangle index out of range");
+        return PADNE_E_INVALID;
+    }
+    return PADNE_OK;
+}
+
+// sigma |grad V|^2 of every column of the finished block, from the V that stage 2 left on the device: one launch over the
+// triangles (power_density_block_kernel), then [n_cols][n_tri] home on the copy streams
+extern "C" int padne_kkt_power_density_block(padne_ctx *ctx, padne_kkt *k, int32_t n_cols, double *out_host) {
+    PADNE_TRY(require_finished_block("padne_kkt_power_density_block", ctx, k, n_cols));
+    const padne_csr *L = k->L;
     const long long n_tri = L->mesh_n_tri;
     if (n_tri == 0) return PADNE_OK;
     PADNE_REQUIRE(out_host != nullptr, "null argument");
@@ -1141,16 +1151,9 @@ extern "C" int padne_kkt_power_density_block(padne_ctx *ctx, padne_kkt *k, int32
     double *d_out = nullptr;
     int *d_bad = nullptr;
     PADNE_TRY(sc.alloc(&d_out, (size_t)n_tri * (size_t)n_cols));
-    PADNE_TRY(sc.alloc(&d_bad, 1));
-    PADNE_HIP_CHECK(hipMemsetAsync(d_bad, 0, sizeof(int), s));
+    PADNE_TRY(bad_flag_alloc(sc, s, &d_bad));
     PADNE_TRY(launch_power_density_block(ctx, L, n_cols, k->v_final, d_out, d_bad));
-    int h_bad = 0;
-    PADNE_HIP_CHECK(hipMemcpyAsync(&h_bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
-    PADNE_HIP_CHECK(hipStreamSynchronize(s));
-    if (h_bad) {
-        set_error("invalid argument: triangle index out of range");
-        return PADNE_E_INVALID;
-    }
+    PADNE_TRY(bad_flag_check(s, d_bad));
     return parallel_copy(k, out_host, d_out, sizeof(double) * (size_t)n_tri * (size_t)n_cols, hipMemcpyDeviceToHost);
 }
 
@@ -1176,18 +1179,11 @@ static int mesh_tiles(padne_ctx *ctx, const padne_csr *L, std::vector<long long>
 // them (sensitivity_block_kernel) and one fold of the per-tile partials per (mesh, objective); the three results go home
 extern "C" int padne_kkt_sensitivity_block(padne_ctx *ctx, padne_kkt *k, int32_t n_cols, int32_t n_obj, const double *weights,
                                            double *power_out, double *density_out, double *mesh_total_out) {
-    PADNE_REQUIRE(ctx && k, "null argument");
-    PADNE_REQUIRE(k->ctx == ctx, "the plan belongs to another context");
-    PADNE_REQUIRE(k->finished && k->v_final != nullptr,
-                  "padne_kkt_sensitivity_block follows padne_kkt_finish_block, with no solve on the plan in between");
-    PADNE_REQUIRE(n_cols == k->finished_cols, "as many columns as the finished block has");
+    PADNE_TRY(require_finished_block("padne_kkt_sensitivity_block", ctx, k, n_cols));
     PADNE_REQUIRE(n_obj >= 1 && n_obj <= 4096, "between 1 and 4096 objectives");
     PADNE_REQUIRE(weights && mesh_total_out, "null argument");
     for (long long e = 0; e < (long long)n_obj * n_cols; ++e) PADNE_REQUIRE(std::isfinite(weights[e]), "weights must be finite");
     const padne_csr *L = k->L;
-    PADNE_REQUIRE(L->mesh_n_mesh > 0 && L->mesh_xy != nullptr,
-                  "the system matrix does not carry a mesh (only padne_assemble_system keeps it)");
-    PADNE_REQUIRE(L->mesh_n_vert <= k->N, "the mesh has more vertices than the system has unknowns");
     const long long n_tri = L->mesh_n_tri;
     const int n_mesh = (int)L->mesh_n_mesh;
     PADNE_REQUIRE(n_tri == 0 || (power_out && density_out), "null argument");
@@ -1202,19 +1198,12 @@ extern "C" int padne_kkt_sensitivity_block(padne_ctx *ctx, padne_kkt *k, int32_t
     PADNE_TRY(sc.alloc(&d_power, (size_t)n_tri));
     PADNE_TRY(sc.alloc(&d_density, (size_t)n_tri * (size_t)n_obj));
     PADNE_TRY(sc.alloc(&d_total, (size_t)n_mesh * (size_t)n_obj));
-    PADNE_TRY(sc.alloc(&d_bad, 1));
     PADNE_HIP_CHECK(hipMemcpyAsync(d_w, weights, sizeof(double) * (size_t)n_obj * (size_t)n_cols, hipMemcpyHostToDevice, s));
-    PADNE_HIP_CHECK(hipMemsetAsync(d_bad, 0, sizeof(int), s));
+    PADNE_TRY(bad_flag_alloc(sc, s, &d_bad));
     PADNE_TRY(launch_sensitivity_block(ctx, L, tile.data(), n_cols, n_obj, d_w, k->v_final, d_power, d_density, d_total, d_bad));
-    int h_bad = 0;
-    PADNE_HIP_CHECK(hipMemcpyAsync(&h_bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
     PADNE_HIP_CHECK(hipMemcpyAsync(mesh_total_out, d_total, sizeof(double) * (size_t)n_mesh * (size_t)n_obj, hipMemcpyDeviceToHost, s));
     if (n_tri > 0) PADNE_HIP_CHECK(hipMemcpyAsync(power_out, d_power, sizeof(double) * (size_t)n_tri, hipMemcpyDeviceToHost, s));
-    PADNE_HIP_CHECK(hipStreamSynchronize(s));
-    if (h_bad) {
-        set_error("invalid argument: triangle index out of range");
-        return PADNE_E_INVALID;
-    }
+    PADNE_TRY(bad_flag_check(s, d_bad));
     if (n_tri == 0) return PADNE_OK;
     return parallel_copy(k, density_out, d_density, sizeof(double) * (size_t)n_tri * (size_t)n_obj, hipMemcpyDeviceToHost);
 }
@@ -1271,125 +1260,33 @@ static void list_cut_pairs(int n_cut, int n_mesh, const int32_t *mesh_layer, con
     }
 }
 
-// The currents of column 0 of the finished block ("Currents"): J = -sigma grad V and |J| of every face, the
-// largest |J| of every mesh, and the current through each cut.  One launch over the tiles of sensitivity_block_kernel's
-// layout writes J, |J|, per-tile maxima and per-tile bounding boxes, and one fold per mesh reduces the maxima.  The boxes
-// come home; the (cut, tile) pairs whose box the cut's segment meets are listed here, on the host; one workgroup per pair
-// and one fold per cut give the cut currents.  No floating-point atomics: two calls give the same bits.
-extern "C" int padne_kkt_current_report(padne_ctx *ctx, padne_kkt *k, int32_t n_cols, int64_t n_tri, int32_t n_mesh,
-                                        const int32_t *mesh_layer, int32_t n_cut, const int32_t *cut_layer, const double *cut_xy,
-                                        double *J_out, double *mag_out, double *mesh_max_out, int64_t *mesh_face_out,
-                                        double *cut_out) {
-    PADNE_REQUIRE(ctx && k, "null argument");
-    PADNE_REQUIRE(k->ctx == ctx, "the plan belongs to another context");
-    PADNE_REQUIRE(k->finished && k->v_final != nullptr,
-                  "padne_kkt_current_report follows padne_kkt_finish_block, with no solve on the plan in between");
-    PADNE_REQUIRE(n_cols == k->finished_cols, "as many columns as the finished block has");
+// The currents of the n_report leading columns of the finished block and their envelope ("Currents"): J = -sigma
+// grad V and |J| of every face, the largest |J| and the power of every mesh, and the current through each cut.  One launch
+// over the tiles of sensitivity_block_kernel's layout writes J, |J|, the envelope, per-tile maxima and powers and per-tile
+// bounding boxes, and one fold per (mesh, column) reduces the tiles.  The boxes come home; the (cut, tile) pairs whose box
+// the cut's segment meets are listed here, on the host; one workgroup per pair and one fold per (cut, column) give the cut
+// currents.  J_out and mag_out, env_out and env_case_out, mesh_power_out: null for an output that is not wanted, which is
+// then neither written on the device nor copied home.  No floating-point atomics: two calls give the same bits.
+static int kkt_currents(const char *entry, padne_ctx *ctx, padne_kkt *k, int32_t n_cols, int32_t n_report, int64_t n_tri,
+                        int32_t n_mesh, const int32_t *mesh_layer, int32_t n_cut, const int32_t *cut_layer, const double *cut_xy,
+                        double *J_out, double *mag_out, double *env_out, int32_t *env_case_out, double *mesh_max_out,
+                        int64_t *mesh_face_out, double *mesh_power_out, double *cut_out) {
+    PADNE_TRY(require_finished_block(entry, ctx, k, n_cols));
     PADNE_REQUIRE(n_cut >= 0 && n_cut <= 4096, "between 0 and 4096 cuts");
     PADNE_REQUIRE(mesh_max_out && mesh_face_out, "null argument");
     PADNE_REQUIRE(n_cut == 0 || (mesh_layer && cut_layer && cut_xy && cut_out), "null argument");
-    PADNE_TRY(check_cut_segments(n_cut, cut_xy));
-    const padne_csr *L = k->L;
-    PADNE_REQUIRE(L->mesh_n_mesh > 0 && L->mesh_xy != nullptr,
-                  "the system matrix does not carry a mesh (only padne_assemble_system keeps it)");
-    PADNE_REQUIRE(L->mesh_n_vert <= k->N, "the mesh has more vertices than the system has unknowns");
-    PADNE_REQUIRE(n_tri == L->mesh_n_tri && n_mesh == L->mesh_n_mesh, "n_tri and n_mesh must be those of the system's mesh");
-    PADNE_REQUIRE(n_tri == 0 || (J_out && mag_out), "null argument");
-    PADNE_HIP_CHECK(hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    std::vector<long long> tile;
-    PADNE_TRY(mesh_tiles(ctx, L, tile));
-    const long long n_blocks = tile[(size_t)n_mesh];
-    const size_t nb = (size_t)(n_blocks > 0 ? n_blocks : 1), nt = (size_t)(n_tri > 0 ? n_tri : 1);
-    Scratch sc(ctx);
-    long long *d_tile = nullptr, *d_tface = nullptr, *d_mface = nullptr;
-    double *d_J = nullptr, *d_mag = nullptr, *d_tmax = nullptr, *d_box = nullptr, *d_mmax = nullptr;
-    int *d_bad = nullptr;
-    PADNE_TRY(sc.alloc(&d_tile, (size_t)n_mesh + 1));
-    PADNE_TRY(sc.alloc(&d_J, 2 * nt));
-    PADNE_TRY(sc.alloc(&d_mag, nt));
-    PADNE_TRY(sc.alloc(&d_tmax, nb));
-    PADNE_TRY(sc.alloc(&d_tface, nb));
-    PADNE_TRY(sc.alloc(&d_box, 4 * nb));
-    PADNE_TRY(sc.alloc(&d_mmax, (size_t)n_mesh));
-    PADNE_TRY(sc.alloc(&d_mface, (size_t)n_mesh));
-    PADNE_TRY(sc.alloc(&d_bad, 1));
-    PADNE_HIP_CHECK(hipMemcpyAsync(d_tile, tile.data(), sizeof(long long) * ((size_t)n_mesh + 1), hipMemcpyHostToDevice, s));
-    PADNE_HIP_CHECK(hipMemsetAsync(d_bad, 0, sizeof(int), s));
-    PADNE_TRY(launch_current_faces(ctx, L, d_tile, n_blocks, n_cols, k->v_final, d_J, d_mag, d_tmax, d_tface, d_box, d_mmax,
-                                   d_mface, d_bad));
-    if (n_cut > 0) {
-        std::vector<double> box(4 * nb);
-        if (n_blocks > 0)
-            PADNE_HIP_CHECK(hipMemcpyAsync(box.data(), d_box, sizeof(double) * 4 * (size_t)n_blocks, hipMemcpyDeviceToHost, s));
-        PADNE_HIP_CHECK(hipStreamSynchronize(s));
-        std::vector<int> pair_cut;
-        std::vector<long long> pair_tile, pair_off;
-        list_cut_pairs(n_cut, n_mesh, mesh_layer, cut_layer, cut_xy, tile, box, pair_cut, pair_tile, pair_off);
-        const long long n_pairs = (long long)pair_tile.size();
-        PADNE_REQUIRE(n_pairs <= 0x7fffffffLL, "too many (cut, tile) pairs for one launch");
-        const size_t np = (size_t)(n_pairs > 0 ? n_pairs : 1);
-        double *d_cut_xy = nullptr, *d_cut = nullptr;
-        int *d_pair_cut = nullptr;
-        long long *d_pair_tile = nullptr;
-        PADNE_TRY(sc.alloc(&d_cut_xy, 4 * (size_t)n_cut));
-        PADNE_TRY(sc.alloc(&d_cut, (size_t)n_cut));
-        PADNE_TRY(sc.alloc(&d_pair_cut, np));
-        PADNE_TRY(sc.alloc(&d_pair_tile, np));
-        PADNE_HIP_CHECK(hipMemcpyAsync(d_cut_xy, cut_xy, sizeof(double) * 4 * (size_t)n_cut, hipMemcpyHostToDevice, s));
-        if (n_pairs > 0) {
-            PADNE_HIP_CHECK(hipMemcpyAsync(d_pair_cut, pair_cut.data(), sizeof(int) * (size_t)n_pairs, hipMemcpyHostToDevice, s));
-            PADNE_HIP_CHECK(hipMemcpyAsync(d_pair_tile, pair_tile.data(), sizeof(long long) * (size_t)n_pairs, hipMemcpyHostToDevice, s));
-        }
-        PADNE_TRY(launch_cut_currents(ctx, L, d_tile, n_cols, k->v_final, n_cut, d_cut_xy, n_pairs, d_pair_cut, d_pair_tile,
-                                      pair_off.data(), d_cut, d_bad));
-        PADNE_HIP_CHECK(hipMemcpyAsync(cut_out, d_cut, sizeof(double) * (size_t)n_cut, hipMemcpyDeviceToHost, s));
-        PADNE_HIP_CHECK(hipStreamSynchronize(s));       // (the copies read the host vectors above before they go)
-    }
-    int h_bad = 0;
-    PADNE_HIP_CHECK(hipMemcpyAsync(&h_bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
-    PADNE_HIP_CHECK(hipMemcpyAsync(mesh_max_out, d_mmax, sizeof(double) * (size_t)n_mesh, hipMemcpyDeviceToHost, s));
-    PADNE_HIP_CHECK(hipMemcpyAsync(mesh_face_out, d_mface, sizeof(long long) * (size_t)n_mesh, hipMemcpyDeviceToHost, s));
-    PADNE_HIP_CHECK(hipStreamSynchronize(s));
-    if (h_bad) {
-        set_error("invalid argument: triangle index out of range");
-        return PADNE_E_INVALID;
-    }
-    if (n_tri == 0) return PADNE_OK;
-    PADNE_TRY(parallel_copy(k, J_out, d_J, sizeof(double) * 2 * (size_t)n_tri, hipMemcpyDeviceToHost));
-    return parallel_copy(k, mag_out, d_mag, sizeof(double) * (size_t)n_tri, hipMemcpyDeviceToHost);
-}
-
-// The currents of every column of the finished block and their envelope ("Load-case currents"): the launches of
-// padne_kkt_current_report with the k-column kernels in their place.  With J_out and mag_out null no per-column field is
-// written on the device or copied home.  No floating-point atomics: two calls give the same bits.
-extern "C" int padne_kkt_current_cases(padne_ctx *ctx, padne_kkt *k, int32_t n_cols, int64_t n_tri, int32_t n_mesh,
-                                       const int32_t *mesh_layer, int32_t n_cut, const int32_t *cut_layer, const double *cut_xy,
-                                       double *J_out, double *mag_out, double *env_out, int32_t *env_case_out,
-                                       double *mesh_max_out, int64_t *mesh_face_out, double *mesh_power_out, double *cut_out) {
-    PADNE_REQUIRE(ctx && k, "null argument");
-    PADNE_REQUIRE(k->ctx == ctx, "the plan belongs to another context");
-    PADNE_REQUIRE(k->finished && k->v_final != nullptr,
-                  "padne_kkt_current_cases follows padne_kkt_finish_block, with no solve on the plan in between");
-    PADNE_REQUIRE(n_cols == k->finished_cols, "as many columns as the finished block has");
-    PADNE_REQUIRE(n_cut >= 0 && n_cut <= 4096, "between 0 and 4096 cuts");
-    PADNE_REQUIRE(mesh_max_out && mesh_face_out && mesh_power_out, "null argument");
-    PADNE_REQUIRE(n_cut == 0 || (mesh_layer && cut_layer && cut_xy && cut_out), "null argument");
     PADNE_REQUIRE((J_out == nullptr) == (mag_out == nullptr), "J_out and mag_out are given or left out together");
+    PADNE_REQUIRE((env_out == nullptr) == (env_case_out == nullptr), "env_out and env_case_out are given or left out together");
     PADNE_TRY(check_cut_segments(n_cut, cut_xy));
     const padne_csr *L = k->L;
-    PADNE_REQUIRE(L->mesh_n_mesh > 0 && L->mesh_xy != nullptr,
-                  "the system matrix does not carry a mesh (only padne_assemble_system keeps it)");
-    PADNE_REQUIRE(L->mesh_n_vert <= k->N, "the mesh has more vertices than the system has unknowns");
     PADNE_REQUIRE(n_tri == L->mesh_n_tri && n_mesh == L->mesh_n_mesh, "n_tri and n_mesh must be those of the system's mesh");
-    PADNE_REQUIRE(n_tri == 0 || (env_out && env_case_out), "null argument");
-    const bool fields = J_out != nullptr;
+    const bool fields = J_out != nullptr, envelope = env_out != nullptr, power = mesh_power_out != nullptr;
     PADNE_HIP_CHECK(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     std::vector<long long> tile;
     PADNE_TRY(mesh_tiles(ctx, L, tile));
     const long long n_blocks = tile[(size_t)n_mesh];
-    const size_t nb = (size_t)(n_blocks > 0 ? n_blocks : 1), nt = (size_t)(n_tri > 0 ? n_tri : 1), nc = (size_t)n_cols;
+    const size_t nb = (size_t)(n_blocks > 0 ? n_blocks : 1), nt = (size_t)(n_tri > 0 ? n_tri : 1), nc = (size_t)n_report;
     Scratch sc(ctx);
     long long *d_tile = nullptr, *d_mface = nullptr;
     double *d_J = nullptr, *d_mag = nullptr, *d_env = nullptr, *d_box = nullptr, *d_mmax = nullptr, *d_mpow = nullptr;
@@ -1399,17 +1296,18 @@ extern "C" int padne_kkt_current_cases(padne_ctx *ctx, padne_kkt *k, int32_t n_c
         PADNE_TRY(sc.alloc(&d_J, 2 * nt * nc));
         PADNE_TRY(sc.alloc(&d_mag, nt * nc));
     }
-    PADNE_TRY(sc.alloc(&d_env, nt));
-    PADNE_TRY(sc.alloc(&d_case, nt));
+    if (envelope) {
+        PADNE_TRY(sc.alloc(&d_env, nt));
+        PADNE_TRY(sc.alloc(&d_case, nt));
+    }
     PADNE_TRY(sc.alloc(&d_box, 4 * nb));
     PADNE_TRY(sc.alloc(&d_mmax, (size_t)n_mesh * nc));
     PADNE_TRY(sc.alloc(&d_mface, (size_t)n_mesh * nc));
-    PADNE_TRY(sc.alloc(&d_mpow, (size_t)n_mesh * nc));
-    PADNE_TRY(sc.alloc(&d_bad, 1));
+    if (power) PADNE_TRY(sc.alloc(&d_mpow, (size_t)n_mesh * nc));
     PADNE_HIP_CHECK(hipMemcpyAsync(d_tile, tile.data(), sizeof(long long) * ((size_t)n_mesh + 1), hipMemcpyHostToDevice, s));
-    PADNE_HIP_CHECK(hipMemsetAsync(d_bad, 0, sizeof(int), s));
-    PADNE_TRY(launch_current_cases_faces(ctx, L, d_tile, n_blocks, n_cols, k->v_final, d_J, d_mag, d_env, d_case, d_box, d_mmax,
-                                         d_mface, d_mpow, d_bad));
+    PADNE_TRY(bad_flag_alloc(sc, s, &d_bad));
+    PADNE_TRY(launch_current_faces(ctx, L, d_tile, n_blocks, n_cols, n_report, k->v_final, d_J, d_mag, d_env, d_case, d_box, d_mmax,
+                                   d_mface, d_mpow, d_bad));
     if (n_cut > 0) {
         std::vector<double> box(4 * nb);
         if (n_blocks > 0)
@@ -1433,28 +1331,47 @@ extern "C" int padne_kkt_current_cases(padne_ctx *ctx, padne_kkt *k, int32_t n_c
             PADNE_HIP_CHECK(hipMemcpyAsync(d_pair_cut, pair_cut.data(), sizeof(int) * (size_t)n_pairs, hipMemcpyHostToDevice, s));
             PADNE_HIP_CHECK(hipMemcpyAsync(d_pair_tile, pair_tile.data(), sizeof(long long) * (size_t)n_pairs, hipMemcpyHostToDevice, s));
         }
-        PADNE_TRY(launch_current_cases_cuts(ctx, L, d_tile, n_cols, k->v_final, n_cut, d_cut_xy, n_pairs, d_pair_cut, d_pair_tile,
-                                            pair_off.data(), d_cut, d_bad));
+        PADNE_TRY(launch_current_cuts(ctx, L, d_tile, n_cols, n_report, k->v_final, n_cut, d_cut_xy, n_pairs, d_pair_cut, d_pair_tile,
+                                      pair_off.data(), d_cut, d_bad));
         PADNE_HIP_CHECK(hipMemcpyAsync(cut_out, d_cut, sizeof(double) * (size_t)n_cut * nc, hipMemcpyDeviceToHost, s));
         PADNE_HIP_CHECK(hipStreamSynchronize(s));       // (the copies read the host vectors above before they go)
     }
-    int h_bad = 0;
-    PADNE_HIP_CHECK(hipMemcpyAsync(&h_bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
     PADNE_HIP_CHECK(hipMemcpyAsync(mesh_max_out, d_mmax, sizeof(double) * (size_t)n_mesh * nc, hipMemcpyDeviceToHost, s));
     PADNE_HIP_CHECK(hipMemcpyAsync(mesh_face_out, d_mface, sizeof(long long) * (size_t)n_mesh * nc, hipMemcpyDeviceToHost, s));
-    PADNE_HIP_CHECK(hipMemcpyAsync(mesh_power_out, d_mpow, sizeof(double) * (size_t)n_mesh * nc, hipMemcpyDeviceToHost, s));
-    PADNE_HIP_CHECK(hipStreamSynchronize(s));
-    if (h_bad) {
-        set_error("invalid argument: triangle index out of range");
-        return PADNE_E_INVALID;
-    }
+    if (power)
+        PADNE_HIP_CHECK(hipMemcpyAsync(mesh_power_out, d_mpow, sizeof(double) * (size_t)n_mesh * nc, hipMemcpyDeviceToHost, s));
+    PADNE_TRY(bad_flag_check(s, d_bad));
     if (n_tri == 0) return PADNE_OK;
     if (fields) {
         PADNE_TRY(parallel_copy(k, J_out, d_J, sizeof(double) * 2 * (size_t)n_tri * nc, hipMemcpyDeviceToHost));
         PADNE_TRY(parallel_copy(k, mag_out, d_mag, sizeof(double) * (size_t)n_tri * nc, hipMemcpyDeviceToHost));
     }
-    PADNE_TRY(parallel_copy(k, env_out, d_env, sizeof(double) * (size_t)n_tri, hipMemcpyDeviceToHost));
-    return parallel_copy(k, env_case_out, d_case, sizeof(int32_t) * (size_t)n_tri, hipMemcpyDeviceToHost);
+    if (envelope) {
+        PADNE_TRY(parallel_copy(k, env_out, d_env, sizeof(double) * (size_t)n_tri, hipMemcpyDeviceToHost));
+        PADNE_TRY(parallel_copy(k, env_case_out, d_case, sizeof(int32_t) * (size_t)n_tri, hipMemcpyDeviceToHost));
+    }
+    return PADNE_OK;
+}
+
+// the currents of column 0 of the finished block: kkt_currents with one reported column, no envelope and no power
+extern "C" int padne_kkt_current_report(padne_ctx *ctx, padne_kkt *k, int32_t n_cols, int64_t n_tri, int32_t n_mesh,
+                                        const int32_t *mesh_layer, int32_t n_cut, const int32_t *cut_layer, const double *cut_xy,
+                                        double *J_out, double *mag_out, double *mesh_max_out, int64_t *mesh_face_out,
+                                        double *cut_out) {
+    PADNE_REQUIRE(n_tri == 0 || (J_out && mag_out), "null argument");
+    return kkt_currents("padne_kkt_current_report", ctx, k, n_cols, 1, n_tri, n_mesh, mesh_layer, n_cut, cut_layer, cut_xy, J_out,
+                        mag_out, nullptr, nullptr, mesh_max_out, mesh_face_out, nullptr, cut_out);
+}
+
+// the currents of every column of the finished block and their envelope ("Load-case currents"); with J_out and
+// mag_out null no per-column field is written on the device or copied home, with env_out and env_case_out null no envelope
+extern "C" int padne_kkt_current_cases(padne_ctx *ctx, padne_kkt *k, int32_t n_cols, int64_t n_tri, int32_t n_mesh,
+                                       const int32_t *mesh_layer, int32_t n_cut, const int32_t *cut_layer, const double *cut_xy,
+                                       double *J_out, double *mag_out, double *env_out, int32_t *env_case_out,
+                                       double *mesh_max_out, int64_t *mesh_face_out, double *mesh_power_out, double *cut_out) {
+    PADNE_REQUIRE(mesh_power_out != nullptr, "null argument");
+    return kkt_currents("padne_kkt_current_cases", ctx, k, n_cols, n_cols, n_tri, n_mesh, mesh_layer, n_cut, cut_layer, cut_xy, J_out,
+                        mag_out, env_out, env_case_out, mesh_max_out, mesh_face_out, mesh_power_out, cut_out);
 }
 
 // The gradient-recovery error estimate of column 0 of the finished block (error.hip; DESIGN.md, "Error estimate"): the
@@ -1463,16 +1380,9 @@ extern "C" int padne_kkt_current_cases(padne_ctx *ctx, padne_kkt *k, int32_t n_c
 extern "C" int padne_kkt_error_estimate(padne_ctx *ctx, padne_kkt *k, int32_t n_cols, int64_t n_tri, int64_t n_vert, int32_t n_mesh,
                                         double *G_out, double *eta_out, double *mesh_error_out, double *mesh_power_out,
                                         double *mesh_max_out, int64_t *mesh_face_out) {
-    PADNE_REQUIRE(ctx && k, "null argument");
-    PADNE_REQUIRE(k->ctx == ctx, "the plan belongs to another context");
-    PADNE_REQUIRE(k->finished && k->v_final != nullptr,
-                  "padne_kkt_error_estimate follows padne_kkt_finish_block, with no solve on the plan in between");
-    PADNE_REQUIRE(n_cols == k->finished_cols, "as many columns as the finished block has");
+    PADNE_TRY(require_finished_block("padne_kkt_error_estimate", ctx, k, n_cols));
     PADNE_REQUIRE(mesh_error_out && mesh_power_out && mesh_max_out && mesh_face_out, "null argument");
     const padne_csr *L = k->L;
-    PADNE_REQUIRE(L->mesh_n_mesh > 0 && L->mesh_xy != nullptr,
-                  "the system matrix does not carry a mesh (only padne_assemble_system keeps it)");
-    PADNE_REQUIRE(L->mesh_n_vert <= k->N, "the mesh has more vertices than the system has unknowns");
     PADNE_REQUIRE(n_tri == L->mesh_n_tri && n_vert == L->mesh_n_vert && n_mesh == L->mesh_n_mesh,
                   "n_tri, n_vert and n_mesh must be those of the system's mesh");
     PADNE_REQUIRE((n_tri == 0 || eta_out) && (n_vert == 0 || G_out), "null argument");
@@ -1489,20 +1399,13 @@ extern "C" int padne_kkt_error_estimate(padne_ctx *ctx, padne_kkt *k, int32_t n_
     PADNE_TRY(sc.alloc(&d_P, (size_t)n_mesh));
     PADNE_TRY(sc.alloc(&d_max, (size_t)n_mesh));
     PADNE_TRY(sc.alloc(&d_face, (size_t)n_mesh));
-    PADNE_TRY(sc.alloc(&d_bad, 1));
-    PADNE_HIP_CHECK(hipMemsetAsync(d_bad, 0, sizeof(int), s));
+    PADNE_TRY(bad_flag_alloc(sc, s, &d_bad));
     PADNE_TRY(csr_error_estimate(ctx, L, &k->err_vptr, &k->err_vface, n_cols, k->v_final, d_G, d_eta, d_E, d_P, d_max, d_face, d_bad));
-    int h_bad = 0;
-    PADNE_HIP_CHECK(hipMemcpyAsync(&h_bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
     PADNE_HIP_CHECK(hipMemcpyAsync(mesh_error_out, d_E, sizeof(double) * (size_t)n_mesh, hipMemcpyDeviceToHost, s));
     PADNE_HIP_CHECK(hipMemcpyAsync(mesh_power_out, d_P, sizeof(double) * (size_t)n_mesh, hipMemcpyDeviceToHost, s));
     PADNE_HIP_CHECK(hipMemcpyAsync(mesh_max_out, d_max, sizeof(double) * (size_t)n_mesh, hipMemcpyDeviceToHost, s));
     PADNE_HIP_CHECK(hipMemcpyAsync(mesh_face_out, d_face, sizeof(long long) * (size_t)n_mesh, hipMemcpyDeviceToHost, s));
-    PADNE_HIP_CHECK(hipStreamSynchronize(s));
-    if (h_bad) {
-        set_error("invalid argument: triangle index out of range");
-        return PADNE_E_INVALID;
-    }
+    PADNE_TRY(bad_flag_check(s, d_bad));
     if (n_vert > 0) PADNE_TRY(parallel_copy(k, G_out, d_G, sizeof(double) * 2 * (size_t)n_vert, hipMemcpyDeviceToHost));
     if (n_tri > 0) PADNE_TRY(parallel_copy(k, eta_out, d_eta, sizeof(double) * (size_t)n_tri, hipMemcpyDeviceToHost));
     return PADNE_OK;

@@ -20,8 +20,8 @@ compute_power_density :728-745         ``power_density_kernel``
                                        power densities from the potentials on the device
 (where a voltage drop comes from)      ``solve_sensitivities``: adjoints on the load-case block, Woodbury for
                                        regulators, ``sensitivity_block_kernel`` over the faces
-(where the current goes)               ``solve_currents``: the load-case block with one column, ``current_face_kernel``
-                                       and ``cut_current_kernel`` over the faces, element flows from V's rows
+(where the current goes)               ``solve_currents``: the load-case block with one column, ``current_cases_face_kernel``
+                                       and ``current_cases_cut_kernel`` over the faces, element flows from V's rows
 (how far the mesh is from the board)   ``solve_error``: the same block, gradient recovery through vertex -> faces lists
                                        (``error_recover_kernel``) and ``error_indicator_kernel`` over the faces
 (a finer mesh where that asks)         ``refine_meshes`` / ``solve_adaptive``: longest-edge refinement with conforming
@@ -1626,54 +1626,9 @@ def solve_meshed_currents(prob, meshes, mesh_index_to_layer_index, cuts=(), *, f
     invalid cuts (:func:`check_cuts`) and for a ``partition`` over several GPUs.  ``timings`` (a dict) receives the host
     time of each step in seconds."""
     _refuse_partition(partition, "currents")
-    cuts = check_cuts(prob, cuts)
     laps = _Laps(timings)
-    board = index_board(prob, meshes, mesh_index_to_layer_index, filtered_networks, disconnected_meshes_by_layer)
-    pairs = global_elements(board.filtered_networks, board.node_indexer)
-    laps.lap("indexing")
-    with board.assembled() as (L, _):
-        rows, cols, vals = stamp_load_cases(board.filtered_networks, board.node_indexer, L.shape[0], [{}])
-        laps.lap("assembly")
-        log.info("Solving the Problem and its currents")
-        plan, V, residual_norms, res, n_tri, _n_mesh = _solve_block_on_device(L, rows, cols, vals, 1, 2, laps, currents=True)
-        power = J = mag = mesh_max = mesh_face = totals = None
-        cut_values = np.zeros(len(cuts))
-        if n_tri:
-            # sigma sum w (dx)^2 per mesh: the sensitivity kernel with lambda = x; then the current kernels
-            power, _, totals = plan.sensitivity_block(np.ones((1, 1)), n_tri, len(board.meshes))
-            J, mag, mesh_max, mesh_face, cut_values = plan.current_report(
-                1, n_tri, np.asarray(mesh_index_to_layer_index, dtype=np.int32), [c[0] for c in cuts],
-                np.array([[*a, *b] for _, a, b in cuts], dtype=DTYPE).reshape(-1, 4))
-    laps.lap("currents")
-    log.info("Producing the solution and the current report")
-    _warn_if_block_stalled(res, residual_norms, cols, vals, 1)
-    solution = _column_solution(board, prob, np.ascontiguousarray(V[:, 0]), residual_norms[0], res, power)
-    local, Vu = _gather_element_rows([row for _, row in pairs], V, _ROW_UNKNOWNS)
-    flows = element_flows(local, Vu[:, 0])
-    vectors, magnitudes, hotspots, layer_power = [], [], [], []
-    for layer_i in range(len(prob.layers)):
-        vecs, forms, total, best = [], [], 0.0, None
-        for mesh_i, msh, lo, hi in board.layer_meshes(layer_i):
-            tf = mesh.TwoForm(msh)
-            if J is not None:
-                vecs.append(J[lo:hi])                     # views of this call's own result arrays: no copies
-                tf.values = mag[lo:hi]
-                total += float(totals[0, mesh_i])
-                # meshes come in global face order: a later mesh wins only with a strictly larger |J|
-                if mesh_face[mesh_i] >= 0 and (best is None or mesh_max[mesh_i] > best[0]):
-                    face = int(mesh_face[mesh_i] - lo)
-                    cx, cy = msh.points[msh.triangles[face]].mean(axis=0)
-                    best = (float(mesh_max[mesh_i]), len(forms), face, float(cx), float(cy))
-            else:
-                vecs.append(np.zeros((len(msh.triangles), 2), dtype=DTYPE))
-            forms.append(tf)
-        vectors.append(vecs)
-        magnitudes.append(forms)
-        hotspots.append(best)
-        layer_power.append(total)
-    report = CurrentReport(vectors=vectors, magnitudes=magnitudes, hotspots=hotspots, layers=layer_power,
-                           elements={element: flows[i] for i, (element, _) in enumerate(pairs)},
-                           cuts=[float(c) for c in cut_values])
+    (solution,), (report,), _ = _solve_block_currents(prob, meshes, mesh_index_to_layer_index, [{}], check_cuts(prob, cuts), True,
+                                                      False, filtered_networks, disconnected_meshes_by_layer, laps)
     laps.lap("solutions")
     return solution, report
 
@@ -1743,31 +1698,16 @@ def _case_element_rows(pairs, rows, case: dict) -> list:
     return out
 
 
-def solve_meshed_load_case_currents(prob, meshes, mesh_index_to_layer_index, cases, cuts=(), *, per_case_fields=True,
-                                    filtered_networks=None, disconnected_meshes_by_layer=None, partition=None,
-                                    timings: Optional[dict] = None):
-    """``solve_meshed_load_cases`` together with where the current goes in every case and in the worst case: ([Solution per
-    case], [CurrentReport per case], CurrentEnvelope).
-
-    Solution j is what ``solve_meshed_load_cases`` gives for case j of a block; ``reports[j]`` is the CurrentReport of
-    ``solve_meshed_currents`` for that case, its ``elements`` keyed by the elements of the substituted Problem.  The
-    envelope holds, for every face, layer, element and cut, the maximum over the cases of the absolute value and the
-    lowest case that attains it (:func:`envelope_of`); its ``elements`` are keyed by the elements of ``prob``.  A layer's
-    envelope hotspot is the hotspot of the lowest case whose hotspot is the largest, so ties go to the lowest case and then
-    to the lowest global face.
-
-    One indexing, one assembly and one block solve of k columns; the face and cut kernels then walk all columns of the V
-    the device holds and reduce over the cases there.  With ``per_case_fields=False`` the device neither writes nor sends
-    home any per-case J or |J|: ``vectors`` and ``magnitudes`` of every report are None and everything else has the same
-    bits.  One case goes through the same path.  ValueError, before anything reaches the device, for invalid cases
-    (:func:`check_load_cases`), invalid cuts (:func:`check_cuts`) and a ``partition`` over several GPUs.  ``timings`` (a
-    dict) receives the host time of each step in seconds."""
-    _refuse_partition(partition, "load-case currents")
-    cases = check_load_cases(prob, cases)
-    cuts = check_cuts(prob, cuts)
+def _solve_block_currents(prob, meshes, mesh_index_to_layer_index, cases, cuts, fields: bool, envelope: bool,
+                          filtered_networks, disconnected_meshes_by_layer, laps: _Laps):
+    """The checked ``cases`` of ``prob`` as one block with the currents of every column: index, assemble, solve the block,
+    ``power_density_block`` and ``current_cases`` on the V the device holds, then a Solution and a CurrentReport per case
+    (``fields``: with their ``vectors`` and ``magnitudes``).  ``cuts`` as :func:`check_cuts` returns them.  Without
+    ``envelope`` the per-face envelope is neither computed nor sent home.  Returns (solutions, reports, what a
+    CurrentEnvelope is built from: (board, pairs, the element flows per case, env, env_case)); ``laps`` receives every step
+    up to the currents."""
     substituted = [substitute_load_case(prob, case) for case in cases]
-    k, n_layers, fields = len(cases), len(prob.layers), bool(per_case_fields)
-    laps = _Laps(timings)
+    k, n_layers = len(cases), len(prob.layers)
     board = index_board(prob, meshes, mesh_index_to_layer_index, filtered_networks, disconnected_meshes_by_layer)
     pairs = global_elements(board.filtered_networks, board.node_indexer)
     laps.lap("indexing")
@@ -1783,11 +1723,11 @@ def solve_meshed_load_case_currents(prob, meshes, mesh_index_to_layer_index, cas
             power = plan.power_density_block(k, n_tri)
             J, mag, env, env_case, mesh_max, mesh_face, totals, cut_values = plan.current_cases(
                 k, n_tri, np.asarray(mesh_index_to_layer_index, dtype=np.int32), [c[0] for c in cuts],
-                np.array([[*a, *b] for _, a, b in cuts], dtype=DTYPE).reshape(-1, 4), fields=fields)
+                np.array([[*a, *b] for _, a, b in cuts], dtype=DTYPE).reshape(-1, 4), fields=fields, envelope=envelope)
         laps.lap("currents")
     laps.lap()
     _warn_if_block_stalled(res, residual_norms, cols, vals, k)
-    log.info("Producing the solution objects, the current reports and the envelope")
+    log.info("Producing the solution objects and the current reports")
     solutions = [_column_solution(board, sub, np.ascontiguousarray(V[:, j]), residual_norms[j], res,
                                   None if power is None else power[j], f"Load case {j}: " if k > 1 else "")
                  for j, (sub, _) in enumerate(substituted)]
@@ -1824,9 +1764,37 @@ def solve_meshed_load_case_currents(prob, meshes, mesh_index_to_layer_index, cas
                                      hotspots=hotspots, layers=layer_power,
                                      elements={element: flows[i] for i, element in enumerate(case_elements)},
                                      cuts=[float(c) for c in cut_values[j]]))
+    return solutions, reports, (board, pairs, flows_by_case, env, env_case)
+
+
+def solve_meshed_load_case_currents(prob, meshes, mesh_index_to_layer_index, cases, cuts=(), *, per_case_fields=True,
+                                    filtered_networks=None, disconnected_meshes_by_layer=None, partition=None,
+                                    timings: Optional[dict] = None):
+    """``solve_meshed_load_cases`` together with where the current goes in every case and in the worst case: ([Solution per
+    case], [CurrentReport per case], CurrentEnvelope).
+
+    Solution j is what ``solve_meshed_load_cases`` gives for case j of a block; ``reports[j]`` is the CurrentReport of
+    ``solve_meshed_currents`` for that case, its ``elements`` keyed by the elements of the substituted Problem.  The
+    envelope holds, for every face, layer, element and cut, the maximum over the cases of the absolute value and the
+    lowest case that attains it (:func:`envelope_of`); its ``elements`` are keyed by the elements of ``prob``.  A layer's
+    envelope hotspot is the hotspot of the lowest case whose hotspot is the largest, so ties go to the lowest case and then
+    to the lowest global face.
+
+    One indexing, one assembly and one block solve of k columns; the face and cut kernels then walk all columns of the V
+    the device holds and reduce over the cases there.  With ``per_case_fields=False`` the device neither writes nor sends
+    home any per-case J or |J|: ``vectors`` and ``magnitudes`` of every report are None and everything else has the same
+    bits.  One case goes through the same path.  ValueError, before anything reaches the device, for invalid cases
+    (:func:`check_load_cases`), invalid cuts (:func:`check_cuts`) and a ``partition`` over several GPUs.  ``timings`` (a
+    dict) receives the host time of each step in seconds."""
+    _refuse_partition(partition, "load-case currents")
+    cases = check_load_cases(prob, cases)
+    laps = _Laps(timings)
+    solutions, reports, (board, pairs, flows_by_case, env, env_case) = _solve_block_currents(
+        prob, meshes, mesh_index_to_layer_index, cases, check_cuts(prob, cuts), bool(per_case_fields), True, filtered_networks,
+        disconnected_meshes_by_layer, laps)
     # the envelope: per face from the device, everything else by the same rule from the per-case scalars
     env_forms, env_cases, env_hotspots = [], [], []
-    for layer_i in range(n_layers):
+    for layer_i in range(len(prob.layers)):
         forms, which = [], []
         for _mesh_i, msh, lo, hi in board.layer_meshes(layer_i):
             tf = mesh.TwoForm(msh)

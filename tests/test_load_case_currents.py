@@ -190,7 +190,8 @@ def test_column_0_is_the_existing_kernels_bit_for_bit(ctx, name):
     """On one finished block of 3 columns, column 0 of ``current_cases`` is ``current_report`` (which reads column 0) and
     its per-mesh power is ``sensitivity_block`` with lambda = column 0 (W = e_0: 1 x_0 + 0 x_1 + 0 x_2 is x_0 exactly).  A
     one-column block of case 0's right-hand side then gives ``sensitivity_block(ones((1, 1)))``'s bits too: bitwise equality
-    is asked of two kernels on the same V, never across two solves."""
+    is asked of two kernels on the same V, never across two solves.  A finished block of 9 columns in between: there too
+    ``current_report`` is row 0 of ``current_cases``."""
     system = S.problem_system(name)
     meshes, _ = board_of(system, name)
     cases = solver.check_load_cases(system.prob, block_cases(system.flat, 3, seed=3))
@@ -212,6 +213,14 @@ def test_column_0_is_the_existing_kernels_bit_for_bit(ctx, name):
         want_env, want_case = solver.envelope_of(mag)
         assert np.array_equal(env, want_env) and np.array_equal(env_case, want_case) and env_case.dtype == np.int32
         plan.close()
+        # nine columns: column 0 is read with a stride beyond one chunk, and both chunk sizes meet a second, partial chunk
+        nine, _ = finished_block(board, L, solver.check_load_cases(system.prob, block_cases(system.flat, 9, seed=9)))
+        J9, mag9, _, _, mmax9, mface9, _, cut9 = nine.current_cases(9, n_tri, ml, cl, cxy)
+        J0, mag0, mmax0, mface0, cut0 = nine.current_report(9, n_tri, ml, cl, cxy)
+        assert np.array_equal(J9[0], J0) and np.array_equal(mag9[0], mag0)
+        assert np.array_equal(mmax9[0], mmax0) and np.array_equal(mface9[0], mface0) and np.array_equal(cut9[0], cut0)
+        assert np.abs(cut0).max() > 0 and not np.array_equal(mag9[8], mag9[0])
+        nine.close()
         one, _ = finished_block(board, L, cases[:1])
         *_, mpow1, _ = one.current_cases(1, n_tri, ml, cl, cxy)
         _, _, totals1 = one.sensitivity_block(np.ones((1, 1)), n_tri, n_mesh)
