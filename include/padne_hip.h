@@ -406,6 +406,25 @@ int padne_kkt_current_cases(padne_ctx *ctx, padne_kkt *plan, int32_t n_cols, int
 int padne_kkt_error_estimate(padne_ctx *ctx, padne_kkt *plan, int32_t n_cols, int64_t n_tri, int64_t n_vert, int32_t n_mesh,
                              double *G_out, double *eta_out, double *mesh_error_out, double *mesh_power_out,
                              double *mesh_max_out, int64_t *mesh_face_out);
+/* Goal-oriented (dual-weighted) error estimate over the mesh `L` keeps, from the block the last padne_kkt_finish_block left
+ * on the device.  Field 0 is column 0 of V, field 1 + j the adjoint lambda_j = sum_m weights[j][m] V[:, m] of objective j
+ * (weights[n_obj][n_cols] as padne_kkt_sensitivity_block takes them).  Every field a goes through the passes of
+ * padne_kkt_error_estimate: g_f^a, G_v^a, d_c^a = G^a_(corner c) - g_f^a, m_12^a = (d_1^a + d_2^a) / 2 (likewise m_23, m_31),
+ * eta_f^a.  Field 0's results (G_out .. mesh_face_out) are padne_kkt_error_estimate's, bit for bit, and power_out[n_tri] is
+ * column 0's sigma |grad V|^2, bit-identical to padne_csr_power_density on V[:, 0].  Per objective j and face
+ * f: dual_eta_out[n_obj][n_tri] = eta_f^(1+j); delta_out[n_obj][n_tri] = sigma (A_f / 3) (m_12^0 . m_12^(1+j) + m_23^0 .
+ * m_23^(1+j) + m_31^0 . m_31^(1+j)), signed: sigma times the integral over f of the product of the two recovered-minus-raw
+ * gradient fields; omega_out[n_obj][n_tri] = eta_f^0 eta_f^(1+j) >= |delta|.  Per objective and mesh:
+ * mesh_omega_out / mesh_delta_out[n_obj][n_mesh] = the sums over the mesh's faces, mesh_top_out[n_obj][n_mesh] = the
+ * largest omega and mesh_top_face_out its face (global index, the lowest on a tie; -1.0 and -1 for a mesh without faces).
+ * Objectives are processed 8 per launch.  The vertex -> faces lists are those of padne_kkt_error_estimate, built by the
+ * first call of either and kept with the plan.  Everything is summed in a fixed order: two calls give the same bits.
+ * Preconditions and errors as padne_kkt_sensitivity_block and padne_kkt_error_estimate. */
+int padne_kkt_goal_error(padne_ctx *ctx, padne_kkt *plan, int32_t n_cols, int32_t n_obj, const double *weights, int64_t n_tri,
+                         int64_t n_vert, int32_t n_mesh, double *power_out, double *G_out, double *eta_out,
+                         double *mesh_error_out, double *mesh_power_out, double *mesh_max_out, int64_t *mesh_face_out, double *dual_eta_out,
+                         double *delta_out, double *omega_out, double *mesh_omega_out, double *mesh_delta_out,
+                         double *mesh_top_out, int64_t *mesh_top_face_out);
 
 /* Row-partitioned runs, optional: attach the rank's owned x owned diagonal block; with precond = 1 the
  * multigrid hierarchy is then built on that block only (block-Jacobi with multigrid blocks, no
@@ -471,6 +490,17 @@ int padne_error_estimate(padne_ctx *ctx, int64_t n_vert, const double *xy_host, 
                          int64_t n_mesh, const int64_t *mesh_vertex_offset, const int64_t *mesh_tri_offset,
                          const double *conductance, const double *potential_host, double *G_out, double *eta_out,
                          double *mesh_error_out, double *mesh_power_out, double *mesh_max_out, int64_t *mesh_face_out);
+
+/* padne_kkt_goal_error for meshes and fields given from the host: potential_host[n_vert][n_fields] row-major holds
+ * n_fields >= 2 (at most 4097) potentials per vertex, field 0 is paired with each of the other n_fields - 1, which take the
+ * place of the adjoints (n_obj = n_fields - 1 in the shapes of the outputs).  The other arguments are
+ * padne_error_estimate's, and so are the field-0 results, bit for bit; power_out[n_tri] has the bits of padne_power_density. */
+int padne_goal_error(padne_ctx *ctx, int64_t n_vert, const double *xy_host, int64_t n_tri, const int32_t *tri_host,
+                     int64_t n_mesh, const int64_t *mesh_vertex_offset, const int64_t *mesh_tri_offset,
+                     const double *conductance, int32_t n_fields, const double *potential_host, double *power_out,
+                     double *G_out, double *eta_out, double *mesh_error_out, double *mesh_power_out, double *mesh_max_out,
+                     int64_t *mesh_face_out, double *dual_eta_out, double *delta_out, double *omega_out,
+                     double *mesh_omega_out, double *mesh_delta_out, double *mesh_top_out, int64_t *mesh_top_face_out);
 
 /* ---- refinement: conforming refined meshes from one flag per face -----------------------------
  * No reference counterpart.  4-triangle longest-edge refinement with conforming closure ("Refinement") of a batch

@@ -119,6 +119,8 @@ SIGNATURES = {
                                           _PF64, _PI32, _PF64, _PI64, _PF64, _PF64]),
     "padne_kkt_error_estimate": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int64, C.c_int32, _PF64, _PF64, _PF64, _PF64, _PF64,
                                            _PI64]),
+    "padne_kkt_goal_error": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _PF64, C.c_int64, C.c_int64, C.c_int32, _PF64, _PF64, _PF64, _PF64,
+                                       _PF64, _PF64, _PI64, _PF64, _PF64, _PF64, _PF64, _PF64, _PF64, _PI64]),
     "padne_amg_apply": (C.c_int, [_P, _P, _PF64, _PF64]),
     "padne_amg_apply_batch": (C.c_int, [_P, _P, C.c_int32, _PF64, _PF64, _PF64]),
     "padne_csr_set_preconditioner_block": (C.c_int, [_P, _P]),
@@ -130,6 +132,8 @@ SIGNATURES = {
     "padne_face_gradient": (C.c_int, [_P, _I64, _PF64, _I64, _PI32, _I64, _PI64, _PI64, _PF64, _PF64, _PF64]),
     "padne_error_estimate": (C.c_int, [_P, _I64, _PF64, _I64, _PI32, _I64, _PI64, _PI64, _PF64, _PF64, _PF64, _PF64, _PF64, _PF64,
                                        _PF64, _PI64]),
+    "padne_goal_error": (C.c_int, [_P, _I64, _PF64, _I64, _PI32, _I64, _PI64, _PI64, _PF64, C.c_int32, _PF64, _PF64, _PF64, _PF64, _PF64,
+                                   _PF64, _PF64, _PI64, _PF64, _PF64, _PF64, _PF64, _PF64, _PF64, _PI64]),
     "padne_refine_create": (C.c_int, [_P, _I64, _PF64, _I64, _PI32, _I64, _PI64, _PI64, C.POINTER(C.c_uint8), _PI64, _PI64, _PI64,
                                       C.POINTER(_P)]),
     "padne_refine_fetch": (C.c_int, [_P, _P, _PF64, _PI32, _PI32, _PI32]),
@@ -543,6 +547,40 @@ class Context:
                                               _ptr(mesh_max, _PF64), _ptr(mesh_face, _PI64)))
         return G, eta, mesh_error, mesh_power, mesh_max, mesh_face
 
+    def goal_error(self, xy, tri, mesh_vertex_offset, mesh_tri_offset, conductance, fields):
+        """The goal-oriented error estimate (include/padne_hip.h, ``padne_goal_error``) of ``fields`` (n_fields, n_vert),
+        n_fields >= 2, on meshes given as ``error_estimate`` takes them: field 0 is paired with each of the others.  Returns
+        (the power density of field 0 (n_tri,), the bits of ``power_density``; ``error_estimate``'s six results for field 0,
+        bit for bit; then per other field j: eta (n_obj, n_tri), delta
+        (n_obj, n_tri), omega (n_obj, n_tri), and per mesh the sums of omega and of delta (n_obj, n_mesh), the largest omega
+        and its face as a global index, -1 for a mesh without faces)."""
+        xy = _f64(xy).reshape(-1, 2)
+        tri = _i32(tri).reshape(-1, 3)
+        mvo, mto, sig = _i64(mesh_vertex_offset), _i64(mesh_tri_offset), _f64(conductance)
+        F = _f64(fields)
+        n_mesh, n_vert, n_tri = sig.shape[0], xy.shape[0], tri.shape[0]
+        if mvo.shape[0] != n_mesh + 1 or mto.shape[0] != n_mesh + 1:
+            raise ValueError("the offset tables must have one entry more than there are meshes")
+        if F.ndim != 2 or F.shape[0] < 2:
+            raise ValueError("fields must have shape (n_fields, n_vert) with n_fields >= 2")
+        if F.shape[1] < n_vert:
+            raise ValueError("potential vectors shorter than the vertex count")
+        pot = np.ascontiguousarray(F[:, :n_vert].T)                      # (n_vert, n_fields): one row per vertex
+        n_obj = F.shape[0] - 1
+        G = np.empty((n_vert, 2), dtype=np.float64)
+        power, eta = np.empty(n_tri, dtype=np.float64), np.empty(n_tri, dtype=np.float64)
+        mesh_error, mesh_power, mesh_max = (np.empty(n_mesh, dtype=np.float64) for _ in range(3))
+        mesh_face = np.empty(n_mesh, dtype=np.int64)
+        dual, delta, omega = (np.empty((n_obj, n_tri), dtype=np.float64) for _ in range(3))
+        m_omega, m_delta, m_top = (np.empty((n_obj, n_mesh), dtype=np.float64) for _ in range(3))
+        m_face = np.empty((n_obj, n_mesh), dtype=np.int64)
+        _check(self._lib.padne_goal_error(self._h, n_vert, _ptr(xy, _PF64), n_tri, _ptr(tri, _PI32), n_mesh, _ptr(mvo, _PI64),
+                                          _ptr(mto, _PI64), _ptr(sig, _PF64), F.shape[0], _ptr(pot, _PF64), _ptr(power, _PF64), _ptr(G, _PF64),
+                                          _ptr(eta, _PF64), _ptr(mesh_error, _PF64), _ptr(mesh_power, _PF64), _ptr(mesh_max, _PF64),
+                                          _ptr(mesh_face, _PI64), _ptr(dual, _PF64), _ptr(delta, _PF64), _ptr(omega, _PF64),
+                                          _ptr(m_omega, _PF64), _ptr(m_delta, _PF64), _ptr(m_top, _PF64), _ptr(m_face, _PI64)))
+        return power, (G, eta, mesh_error, mesh_power, mesh_max, mesh_face), dual, delta, omega, m_omega, m_delta, m_top, m_face
+
 
 class LocalTeam:
     """In-process team of contexts acting as ranks on one GPU (rehearsal of the multi-rank path)."""
@@ -862,6 +900,32 @@ class KktPlan:
                                                       _ptr(eta, _PF64), _ptr(mesh_error, _PF64), _ptr(mesh_power, _PF64),
                                                       _ptr(mesh_max, _PF64), _ptr(mesh_face, _PI64)))
         return G, eta, mesh_error, mesh_power, mesh_max, mesh_face
+
+    def goal_error(self, weights, n_tri: int, n_vert: int, n_mesh: int):
+        """The goal-oriented error estimate of the block the last ``finish_block`` left on the device: field 0 is column 0,
+        field 1 + j the adjoint sum_m weights[j, m] V[:, m] for ``weights`` (n_obj, n_cols), as ``sensitivity_block`` takes
+        them.  Returns (the power density of column 0 (n_tri,), bit-identical to ``CsrMatrix.power_density``; ``error_estimate``'s six
+        results, bit for bit; then per objective: eta of the adjoint (n_obj, n_tri),
+        delta (n_obj, n_tri), omega (n_obj, n_tri), and per mesh the sums of omega and of delta (n_obj, n_mesh), the largest
+        omega and its face as a global index, -1 for a mesh without faces) (include/padne_hip.h).  The vertex lists are
+        ``error_estimate``'s.  Raises ValueError as ``sensitivity_block`` and ``error_estimate`` do."""
+        W = _f64(weights)
+        if W.ndim != 2 or W.shape[0] < 1:
+            raise ValueError("weights must have shape (n_obj, n_cols) with n_obj >= 1")
+        n_obj, n_tri, n_vert, n_mesh = W.shape[0], int(n_tri), int(n_vert), int(n_mesh)
+        G = np.empty((n_vert, 2), dtype=np.float64)
+        power, eta = np.empty(n_tri, dtype=np.float64), np.empty(n_tri, dtype=np.float64)
+        mesh_error, mesh_power, mesh_max = (np.empty(n_mesh, dtype=np.float64) for _ in range(3))
+        mesh_face = np.empty(n_mesh, dtype=np.int64)
+        dual, delta, omega = (np.empty((n_obj, n_tri), dtype=np.float64) for _ in range(3))
+        m_omega, m_delta, m_top = (np.empty((n_obj, n_mesh), dtype=np.float64) for _ in range(3))
+        m_face = np.empty((n_obj, n_mesh), dtype=np.int64)
+        _check(self.ctx._lib.padne_kkt_goal_error(self.ctx._h, self._h, W.shape[1], n_obj, _ptr(W, _PF64), n_tri, n_vert, n_mesh,
+                                                  _ptr(power, _PF64), _ptr(G, _PF64), _ptr(eta, _PF64), _ptr(mesh_error, _PF64), _ptr(mesh_power, _PF64),
+                                                  _ptr(mesh_max, _PF64), _ptr(mesh_face, _PI64), _ptr(dual, _PF64),
+                                                  _ptr(delta, _PF64), _ptr(omega, _PF64), _ptr(m_omega, _PF64), _ptr(m_delta, _PF64),
+                                                  _ptr(m_top, _PF64), _ptr(m_face, _PI64)))
+        return power, (G, eta, mesh_error, mesh_power, mesh_max, mesh_face), dual, delta, omega, m_omega, m_delta, m_top, m_face
 
     def finish(self, extra_coeff, multipliers: dict):
         """Stage 2: (v, ||L v - r||)."""

@@ -12,46 +12,13 @@
 // are a CSR whose rows ascend in face number BY CONSTRUCTION: the (vertex, face) pairs are written in face order and sorted
 // by vertex with a stable radix sort; the row pointer is a binary search per vertex.  Nothing is left to the order in
 // which atomics land.
-#include "common.hpp"
-#include "face.hpp"
+#include "error.hpp"
 
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include <vector>
 
 namespace padne {
-
-// the mesh the passes run over: device arrays, as padne_csr keeps them
-struct ErrorMesh {
-    const double *xy = nullptr, *sigma = nullptr;
-    const int32_t *tri = nullptr;
-    const long long *voff = nullptr, *toff = nullptr;
-    long long n_vert = 0, n_tri = 0;
-    int n_mesh = 0;
-};
-
-constexpr long long kErrNoFace = 0x7fffffffffffffffLL;
-
-// (eta, face) pairs: the larger eta wins, the lower face on a tie
-__device__ __forceinline__ void error_merge(double &v, long long &f, double ov, long long of) {
-    if (ov > v || (ov == v && of < f)) {
-        v = ov;
-        f = of;
-    }
-}
-
-// the global corners of face t of mesh m in the order power_density_kernel visits them; false for an index out of range
-__device__ __forceinline__ bool error_corners(const int32_t *__restrict__ tri, const long long *__restrict__ voff, int m,
-                                              long long t, long long &g1, long long &g2, long long &g3) {
-    const long long v0 = voff[m];
-    const long long nv = voff[m + 1] - v0;
-    const int l1 = tri[3 * t + 2], l2 = tri[3 * t], l3 = tri[3 * t + 1];
-    if (l1 < 0 || l2 < 0 || l3 < 0 || l1 >= nv || l2 >= nv || l3 >= nv) return false;
-    g1 = v0 + l1;
-    g2 = v0 + l2;
-    g3 = v0 + l3;
-    return true;
-}
 
 // ---- vertex -> incident faces ----------------------------------------------------------------------------------------
 // key[3 t + c] = the global vertex of corner c of face t (n_vert for an index out of range: sorted behind every list),
@@ -155,7 +122,7 @@ __global__ __launch_bounds__(256) void error_face_kernel(const long long n_tri, 
     face_gradient_of(x1, y1, x2, y2, x3, y3, V[g1 * n_cols], V[g2 * n_cols], V[g3 * n_cols], gx, gy);
     gA[3 * t] = gx;
     gA[3 * t + 1] = gy;
-    gA[3 * t + 2] = fabs((x2 - x1) * (y3 - y1) - (y2 - y1) * (x3 - x1)) / 2;
+    gA[3 * t + 2] = error_area(x1, y1, x2, y2, x3, y3);
 }
 
 // G[v] = (sum A_f g_f) / (sum A_f) over the list of v, front to back: one thread per vertex
@@ -168,13 +135,10 @@ __global__ __launch_bounds__(256) void error_recover_kernel(const long long n_ve
     for (int e = vptr[v], e1 = vptr[v + 1]; e < e1; ++e) {
         const double *p = gA + 3 * (long long)vface[e];
         const double a = p[2];
-        sx += a * p[0];
-        sy += a * p[1];
+        error_recover_add(sx, sy, p[0], p[1], a);
         sa += a;
     }
-    const bool some = sa > 0.0;
-    G[2 * v] = some ? sx / sa : 0.0;
-    G[2 * v + 1] = some ? sy / sa : 0.0;
+    error_recover_end(sx, sy, sa, G[2 * v], G[2 * v + 1]);
 }
 
 // eta[t], and per tile (256 faces of one mesh, the layout of sensitivity_block_kernel) the sums of eta^2 and of
@@ -197,25 +161,19 @@ __global__ __launch_bounds__(256) void error_indicator_kernel(
         double value = 0.0;
         if (error_corners(tri, voff, m, t, g1, g2, g3)) {       // (an index out of range was reported by error_face_kernel)
             const double gx = gA[3 * t], gy = gA[3 * t + 1], area = gA[3 * t + 2], s = sigma[m];
-            const double d1x = G[2 * g1] - gx, d1y = G[2 * g1 + 1] - gy;
-            const double d2x = G[2 * g2] - gx, d2y = G[2 * g2 + 1] - gy;
-            const double d3x = G[2 * g3] - gx, d3y = G[2 * g3 + 1] - gy;
-            const double m12x = (d1x + d2x) / 2, m12y = (d1y + d2y) / 2;
-            const double m23x = (d2x + d3x) / 2, m23y = (d2y + d3y) / 2;
-            const double m31x = (d3x + d1x) / 2, m31y = (d3y + d1y) / 2;
-            e2 = s * (area / 3) * (((m12x * m12x + m12y * m12y) + (m23x * m23x + m23y * m23y)) + (m31x * m31x + m31y * m31y));
-            p = s * area * (gx * gx + gy * gy);
+            double mid[6];
+            error_midpoints(G[2 * g1], G[2 * g1 + 1], G[2 * g2], G[2 * g2 + 1], G[2 * g3], G[2 * g3 + 1], gx, gy, mid);
+            e2 = error_midpoint_form(s, area, mid, mid);
+            p = error_power(s, area, gx, gy);
             value = sqrt(e2);
         }
         eta[t] = value;
         a = value;
         f = t;
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        e2 += __shfl_down(e2, off, 64);
-        p += __shfl_down(p, off, 64);
-        error_merge(a, f, __shfl_down(a, off, 64), __shfl_down(f, off, 64));
-    }
+    e2 = error_wave_sum(e2);
+    p = error_wave_sum(p);
+    error_wave_top(a, f);
     const int w = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) {
         red_E[w] = e2;
@@ -226,8 +184,8 @@ __global__ __launch_bounds__(256) void error_indicator_kernel(
     __syncthreads();
     if (threadIdx.x == 0) {
         for (int q = 1; q < 4; ++q) error_merge(a, f, red_v[q], red_f[q]);
-        tile_E[b] = (red_E[0] + red_E[1]) + (red_E[2] + red_E[3]);
-        tile_P[b] = (red_P[0] + red_P[1]) + (red_P[2] + red_P[3]);
+        tile_E[b] = error_sum4(red_E);
+        tile_P[b] = error_sum4(red_P);
         tile_max[b] = a;
         tile_face[b] = f;
     }
@@ -243,33 +201,8 @@ __global__ __launch_bounds__(256) void error_mesh_fold(const long long *__restri
     __shared__ double red_E[4], red_P[4], red_v[4];
     __shared__ long long red_f[4];
     const int m = blockIdx.x;
-    double e2 = 0.0, p = 0.0, a = -1.0;
-    long long f = kErrNoFace;
-    for (long long i = tile_off[m] + threadIdx.x; i < tile_off[m + 1]; i += 256) {
-        e2 += tile_E[i];
-        p += tile_P[i];
-        error_merge(a, f, tile_max[i], tile_face[i]);
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        e2 += __shfl_down(e2, off, 64);
-        p += __shfl_down(p, off, 64);
-        error_merge(a, f, __shfl_down(a, off, 64), __shfl_down(f, off, 64));
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        red_E[w] = e2;
-        red_P[w] = p;
-        red_v[w] = a;
-        red_f[w] = f;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int q = 1; q < 4; ++q) error_merge(a, f, red_v[q], red_f[q]);
-        mesh_E[m] = (red_E[0] + red_E[1]) + (red_E[2] + red_E[3]);
-        mesh_P[m] = (red_P[0] + red_P[1]) + (red_P[2] + red_P[3]);
-        mesh_max[m] = a;
-        mesh_face[m] = f == kErrNoFace ? -1 : f;
-    }
+    error_fold_tiles(tile_off, m, tile_E, tile_P, tile_max, tile_face, red_E, red_P, red_v, red_f, mesh_E + m, mesh_P + m, mesh_max + m,
+                     mesh_face + m);
 }
 
 // The three passes and the fold over the mesh M with its lists, from column 0 of V_dev[..][n_cols]; toff_host[n_mesh + 1]
@@ -322,13 +255,7 @@ int launch_error_estimate(padne_ctx *ctx, const ErrorMesh &M, const long long *t
     return PADNE_OK;
 }
 
-// The estimate of the mesh a system keeps, with the lists *vptr / *vface of the caller (built here on first use and left
-// with the caller): device results as launch_error_estimate leaves them.  Every call waits once for the mesh's triangle
-// offsets to come home (the tile layout is made on the host, as in padne_kkt_current_report); the first also for the lists'
-// index check.  The launches themselves are asynchronous.
-int csr_error_estimate(padne_ctx *ctx, const padne_csr *L, int **vptr, int **vface, int n_cols, const double *V_dev,
-                       double *G_dev, double *eta_dev, double *mesh_E_dev, double *mesh_P_dev, double *mesh_max_dev,
-                       long long *mesh_face_dev, int *bad_dev) {
+ErrorMesh error_mesh_of(const padne_csr *L) {
     ErrorMesh M;
     M.xy = L->mesh_xy;
     M.sigma = L->mesh_sigma;
@@ -338,6 +265,17 @@ int csr_error_estimate(padne_ctx *ctx, const padne_csr *L, int **vptr, int **vfa
     M.n_vert = L->mesh_n_vert;
     M.n_tri = L->mesh_n_tri;
     M.n_mesh = (int)L->mesh_n_mesh;
+    return M;
+}
+
+// The estimate of the mesh a system keeps, with the lists *vptr / *vface of the caller (built here on first use and left
+// with the caller): device results as launch_error_estimate leaves them.  Every call waits once for the mesh's triangle
+// offsets to come home (the tile layout is made on the host, as in padne_kkt_current_report); the first also for the lists'
+// index check.  The launches themselves are asynchronous.
+int csr_error_estimate(padne_ctx *ctx, const padne_csr *L, int **vptr, int **vface, int n_cols, const double *V_dev,
+                       double *G_dev, double *eta_dev, double *mesh_E_dev, double *mesh_P_dev, double *mesh_max_dev,
+                       long long *mesh_face_dev, int *bad_dev) {
+    const ErrorMesh M = error_mesh_of(L);
     if (*vptr == nullptr) PADNE_TRY(error_vertex_faces(ctx, M, vptr, vface));
     std::vector<long long> toff((size_t)M.n_mesh + 1);
     PADNE_HIP_CHECK(hipMemcpyAsync(toff.data(), M.toff, sizeof(long long) * ((size_t)M.n_mesh + 1), hipMemcpyDeviceToHost, ctx->stream));

@@ -6,6 +6,7 @@
 // by its O(#constraints) lists, r crosses PCIe once (while the reduced matrix and its multigrid hierarchy are being
 // built), v once.
 #include "common.hpp"
+#include "error.hpp"                                  // GoalOut, csr_goal_error
 
 #include <string.h>
 #include <rocprim/device/device_radix_sort.hpp>      // the one stable key-value sort of the locality ordering (section "ordering")
@@ -1408,5 +1409,69 @@ extern "C" int padne_kkt_error_estimate(padne_ctx *ctx, padne_kkt *k, int32_t n_
     PADNE_TRY(bad_flag_check(s, d_bad));
     if (n_vert > 0) PADNE_TRY(parallel_copy(k, G_out, d_G, sizeof(double) * 2 * (size_t)n_vert, hipMemcpyDeviceToHost));
     if (n_tri > 0) PADNE_TRY(parallel_copy(k, eta_out, d_eta, sizeof(double) * (size_t)n_tri, hipMemcpyDeviceToHost));
+    return PADNE_OK;
+}
+
+// The goal-oriented (dual-weighted) error estimate of the finished block (goal.hip; DESIGN.md, "Goal-oriented error"): field 0
+// is column 0, field 1 + j the adjoint sum_m weights[j][m] V[:, m], as padne_kkt_sensitivity_block takes the weights.  The
+// vertex -> faces lists are those of padne_kkt_error_estimate, built by whichever of the two is called first and kept with
+// the plan; the field-0 results are that entry's bits.  Only the results cross PCIe.
+extern "C" int padne_kkt_goal_error(padne_ctx *ctx, padne_kkt *k, int32_t n_cols, int32_t n_obj, const double *weights, int64_t n_tri,
+                                    int64_t n_vert, int32_t n_mesh, double *power_out, double *G_out, double *eta_out,
+                                    double *mesh_error_out, double *mesh_power_out, double *mesh_max_out, int64_t *mesh_face_out, double *dual_eta_out,
+                                    double *delta_out, double *omega_out, double *mesh_omega_out, double *mesh_delta_out,
+                                    double *mesh_top_out, int64_t *mesh_top_face_out) {
+    PADNE_TRY(require_finished_block("padne_kkt_goal_error", ctx, k, n_cols));
+    PADNE_REQUIRE(n_obj >= 1 && n_obj <= 4096, "between 1 and 4096 objectives");
+    PADNE_REQUIRE(weights, "null argument");
+    for (long long e = 0; e < (long long)n_obj * n_cols; ++e) PADNE_REQUIRE(std::isfinite(weights[e]), "weights must be finite");
+    PADNE_REQUIRE(mesh_error_out && mesh_power_out && mesh_max_out && mesh_face_out, "null argument");
+    PADNE_REQUIRE(mesh_omega_out && mesh_delta_out && mesh_top_out && mesh_top_face_out, "null argument");
+    const padne_csr *L = k->L;
+    PADNE_REQUIRE(n_tri == L->mesh_n_tri && n_vert == L->mesh_n_vert && n_mesh == L->mesh_n_mesh,
+                  "n_tri, n_vert and n_mesh must be those of the system's mesh");
+    PADNE_REQUIRE((n_tri == 0 || (power_out && eta_out && dual_eta_out && delta_out && omega_out)) && (n_vert == 0 || G_out), "null argument");
+    PADNE_HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const size_t nt = (size_t)(n_tri > 0 ? n_tri : 1), nv = (size_t)(n_vert > 0 ? n_vert : 1), nm = (size_t)n_mesh, no = (size_t)n_obj;
+    Scratch sc(ctx);
+    GoalOut out;
+    double *d_w = nullptr;
+    int *d_bad = nullptr;
+    PADNE_TRY(sc.alloc(&d_w, no * (size_t)n_cols));
+    PADNE_TRY(sc.alloc(&out.power, nt));
+    PADNE_TRY(sc.alloc(&out.G0, 2 * nv));
+    PADNE_TRY(sc.alloc(&out.eta0, nt));
+    PADNE_TRY(sc.alloc(&out.mesh_E, nm));
+    PADNE_TRY(sc.alloc(&out.mesh_P, nm));
+    PADNE_TRY(sc.alloc(&out.mesh_max, nm));
+    PADNE_TRY(sc.alloc(&out.mesh_face, nm));
+    PADNE_TRY(sc.alloc(&out.eta, no * nt));
+    PADNE_TRY(sc.alloc(&out.delta, no * nt));
+    PADNE_TRY(sc.alloc(&out.omega, no * nt));
+    PADNE_TRY(sc.alloc(&out.obj_omega, no * nm));
+    PADNE_TRY(sc.alloc(&out.obj_delta, no * nm));
+    PADNE_TRY(sc.alloc(&out.obj_top, no * nm));
+    PADNE_TRY(sc.alloc(&out.obj_face, no * nm));
+    PADNE_HIP_CHECK(hipMemcpyAsync(d_w, weights, sizeof(double) * no * (size_t)n_cols, hipMemcpyHostToDevice, s));
+    PADNE_TRY(bad_flag_alloc(sc, s, &d_bad));
+    PADNE_TRY(csr_goal_error(ctx, L, &k->err_vptr, &k->err_vface, n_cols, n_obj, d_w, k->v_final, out, d_bad));
+    PADNE_HIP_CHECK(hipMemcpyAsync(mesh_error_out, out.mesh_E, sizeof(double) * nm, hipMemcpyDeviceToHost, s));
+    PADNE_HIP_CHECK(hipMemcpyAsync(mesh_power_out, out.mesh_P, sizeof(double) * nm, hipMemcpyDeviceToHost, s));
+    PADNE_HIP_CHECK(hipMemcpyAsync(mesh_max_out, out.mesh_max, sizeof(double) * nm, hipMemcpyDeviceToHost, s));
+    PADNE_HIP_CHECK(hipMemcpyAsync(mesh_face_out, out.mesh_face, sizeof(long long) * nm, hipMemcpyDeviceToHost, s));
+    PADNE_HIP_CHECK(hipMemcpyAsync(mesh_omega_out, out.obj_omega, sizeof(double) * no * nm, hipMemcpyDeviceToHost, s));
+    PADNE_HIP_CHECK(hipMemcpyAsync(mesh_delta_out, out.obj_delta, sizeof(double) * no * nm, hipMemcpyDeviceToHost, s));
+    PADNE_HIP_CHECK(hipMemcpyAsync(mesh_top_out, out.obj_top, sizeof(double) * no * nm, hipMemcpyDeviceToHost, s));
+    PADNE_HIP_CHECK(hipMemcpyAsync(mesh_top_face_out, out.obj_face, sizeof(long long) * no * nm, hipMemcpyDeviceToHost, s));
+    PADNE_TRY(bad_flag_check(s, d_bad));
+    if (n_vert > 0) PADNE_TRY(parallel_copy(k, G_out, out.G0, sizeof(double) * 2 * (size_t)n_vert, hipMemcpyDeviceToHost));
+    if (n_tri > 0) {
+        PADNE_TRY(parallel_copy(k, power_out, out.power, sizeof(double) * (size_t)n_tri, hipMemcpyDeviceToHost));
+        PADNE_TRY(parallel_copy(k, eta_out, out.eta0, sizeof(double) * (size_t)n_tri, hipMemcpyDeviceToHost));
+        PADNE_TRY(parallel_copy(k, dual_eta_out, out.eta, sizeof(double) * no * (size_t)n_tri, hipMemcpyDeviceToHost));
+        PADNE_TRY(parallel_copy(k, delta_out, out.delta, sizeof(double) * no * (size_t)n_tri, hipMemcpyDeviceToHost));
+        PADNE_TRY(parallel_copy(k, omega_out, out.omega, sizeof(double) * no * (size_t)n_tri, hipMemcpyDeviceToHost));
+    }
     return PADNE_OK;
 }

@@ -1898,6 +1898,46 @@ def refinement_ratios(eta, h, total_power: float, n_faces: int, tolerance: float
     return xi, sizes
 
 
+def _error_report(prob, board, n_tri: int, estimate_arrays, tolerance) -> ErrorReport:
+    """The ErrorReport of ``KktPlan.error_estimate``'s six arrays on the indexed ``board`` (all None on a board without faces)."""
+    G, eta, mesh_error, mesh_power, mesh_max, mesh_face = estimate_arrays
+    power_error, estimate = error_estimate_of(mesh_error, mesh_power) if eta is not None else (0.0, 0.0)
+    total_power = (float(np.sum(mesh_power)) + power_error) if eta is not None else 0.0
+    voff = board.vindex.offsets
+    recovered, indicators, worst, layer_sums = [], [], [], []
+    ratios, sizes = ([], []) if tolerance is not None else (None, None)
+    for layer_i, layer in enumerate(prob.layers):
+        vecs, forms, xis, hs, E, P, best = [], [], [], [], 0.0, 0.0, None
+        for mesh_i, msh, lo, hi in board.layer_meshes(layer_i):
+            tf = mesh.TwoForm(msh)
+            if eta is not None:
+                vecs.append(-layer.conductance * G[voff[mesh_i]:voff[mesh_i + 1]])
+                tf.values = eta[lo:hi]                    # views of this call's own result array: no copies
+                E += float(mesh_error[mesh_i])
+                P += float(mesh_power[mesh_i])
+                # meshes come in global face order: a later mesh wins only with a strictly larger eta
+                if mesh_face[mesh_i] >= 0 and (best is None or mesh_max[mesh_i] > best[0]):
+                    face = int(mesh_face[mesh_i] - lo)
+                    cx, cy = msh.points[msh.triangles[face]].mean(axis=0)
+                    best = (float(mesh_max[mesh_i]), len(forms), face, float(cx), float(cy))
+            else:
+                vecs.append(np.zeros((len(msh.points), 2), dtype=DTYPE))
+            if tolerance is not None:
+                xi, size = refinement_ratios(tf.values, face_sizes(msh.points, msh.triangles), total_power, n_tri, tolerance)
+                xis.append(xi)
+                hs.append(size)
+            forms.append(tf)
+        recovered.append(vecs)
+        indicators.append(forms)
+        worst.append(best)
+        layer_sums.append((E, P))
+        if tolerance is not None:
+            ratios.append(xis)
+            sizes.append(hs)
+    return ErrorReport(recovered=recovered, indicators=indicators, worst=worst, layers=layer_sums, power_error=power_error,
+                       estimate=estimate, ratios=ratios, sizes=sizes, tolerance=tolerance)
+
+
 def solve_meshed_error(prob, meshes, mesh_index_to_layer_index, *, tolerance=None, filtered_networks=None,
                        disconnected_meshes_by_layer=None, partition=None, timings: Optional[dict] = None):
     """``solve_meshed`` together with an estimate of how far its answer is from the board: (Solution, ErrorReport).
@@ -1954,41 +1994,7 @@ def solve_meshed_error(prob, meshes, mesh_index_to_layer_index, *, tolerance=Non
     log.info("Producing the solution and the error report")
     _warn_if_block_stalled(res, residual_norms, cols, vals, 1)
     solution = _column_solution(board, prob, np.ascontiguousarray(V[:, 0]), residual_norms[0], res, power)
-    power_error, estimate = error_estimate_of(mesh_error, mesh_power) if eta is not None else (0.0, 0.0)
-    total_power = (float(np.sum(mesh_power)) + power_error) if eta is not None else 0.0
-    voff = board.vindex.offsets
-    recovered, indicators, worst, layer_sums = [], [], [], []
-    ratios, sizes = ([], []) if tolerance is not None else (None, None)
-    for layer_i, layer in enumerate(prob.layers):
-        vecs, forms, xis, hs, E, P, best = [], [], [], [], 0.0, 0.0, None
-        for mesh_i, msh, lo, hi in board.layer_meshes(layer_i):
-            tf = mesh.TwoForm(msh)
-            if eta is not None:
-                vecs.append(-layer.conductance * G[voff[mesh_i]:voff[mesh_i + 1]])
-                tf.values = eta[lo:hi]                    # views of this call's own result array: no copies
-                E += float(mesh_error[mesh_i])
-                P += float(mesh_power[mesh_i])
-                # meshes come in global face order: a later mesh wins only with a strictly larger eta
-                if mesh_face[mesh_i] >= 0 and (best is None or mesh_max[mesh_i] > best[0]):
-                    face = int(mesh_face[mesh_i] - lo)
-                    cx, cy = msh.points[msh.triangles[face]].mean(axis=0)
-                    best = (float(mesh_max[mesh_i]), len(forms), face, float(cx), float(cy))
-            else:
-                vecs.append(np.zeros((len(msh.points), 2), dtype=DTYPE))
-            if tolerance is not None:
-                xi, size = refinement_ratios(tf.values, face_sizes(msh.points, msh.triangles), total_power, n_tri, tolerance)
-                xis.append(xi)
-                hs.append(size)
-            forms.append(tf)
-        recovered.append(vecs)
-        indicators.append(forms)
-        worst.append(best)
-        layer_sums.append((E, P))
-        if tolerance is not None:
-            ratios.append(xis)
-            sizes.append(hs)
-    report = ErrorReport(recovered=recovered, indicators=indicators, worst=worst, layers=layer_sums, power_error=power_error,
-                         estimate=estimate, ratios=ratios, sizes=sizes, tolerance=tolerance)
+    report = _error_report(prob, board, n_tri, (G, eta, mesh_error, mesh_power, mesh_max, mesh_face), tolerance)
     laps.lap("solutions")
     return solution, report
 
@@ -2187,6 +2193,272 @@ def solve_adaptive(prob, mesher_config: Optional[mesh.Mesher.Config] = None, *, 
     meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
     return solve_meshed_adaptive(prob, meshes, mesh_index_to_layer_index, tolerance=tolerance, max_rounds=max_rounds,
                                  max_faces=max_faces, min_size=min_size, timings=timings)
+
+
+# --------------------------------------------------------------------------------------------
+# goal-oriented error: how far is a voltage drop off, and where must the mesh be finer for it (DESIGN.md "Goal-oriented error")
+# --------------------------------------------------------------------------------------------
+
+# correction = GOAL_CORRECTION_SIGN * sum_f delta_f estimates J(exact) - J_h: on the copper block M = -K, so the adjoint
+# lambda = M^-T c is minus the dual solution z of K z = c, and J(e) = a(e, z - z_h) = -a(e, lambda - lambda_h)
+GOAL_CORRECTION_SIGN = -1.0
+
+
+@dataclass
+class GoalError:
+    """The estimated discretisation error of one objective J = V(p) - V(n) (see :func:`solve_meshed_goal_error`)."""
+    nodes: tuple              # (p, n) as given: two NodeIDs
+    value: float              # J_h = V(p) - V(n) of the solution [V]
+    dual_indicators: list     # per layer, per mesh of LayerSolution.meshes: TwoForm of eta_f of the adjoint [sqrt(ohm)]
+    contributions: list       # per layer, per mesh: TwoForm of delta_f, signed [V]
+    weights: list             # per layer, per mesh: TwoForm of omega_f = eta_f eta_f^adjoint >= |delta_f| [V]
+    layers: list              # per layer: (sum omega_f, sum delta_f) [V]
+    worst: list               # per layer: (max omega, mesh index within the layer, face index, centroid x, y), None without faces
+    bound: float              # sum of omega_f over all faces [V]: bounds |sum delta_f|
+    correction: float         # GOAL_CORRECTION_SIGN * sum delta_f: the estimate of J(exact) - J_h [V]
+    ratios: Optional[list] = None     # with a tolerance: per layer, per mesh (n_faces,) xi_f = omega_f n_faces / tolerance
+    tolerance: Optional[float] = None
+
+
+def check_goal_tolerance(tolerance) -> Optional[float]:
+    """``tolerance`` as a float, None for None, or ValueError: a finite number greater than 0 (absolute, in volts); no bool
+    and no string."""
+    if tolerance is None:
+        return None
+    if isinstance(tolerance, (bool, np.bool_, str, bytes)):
+        raise ValueError("tolerance must be a number of volts greater than 0")
+    try:
+        value = float(tolerance)
+    except (TypeError, ValueError):
+        raise ValueError("tolerance must be a number of volts greater than 0") from None
+    if not (math.isfinite(value) and value > 0.0):
+        raise ValueError(f"tolerance must be a finite number of volts greater than 0, not {tolerance!r}")
+    return value
+
+
+def goal_ratios(omega, n_faces: int, tolerance: float) -> np.ndarray:
+    """xi_f = omega_f / (tolerance / n_faces): the permissible share of every face is the tolerance [V] divided evenly over
+    the ``n_faces`` faces of the connected meshes.  Above 1: refine here."""
+    omega = np.asarray(omega, dtype=DTYPE)
+    return omega / (tolerance / n_faces) if n_faces > 0 else np.zeros_like(omega)
+
+
+def solve_meshed_goal_error(prob, meshes, mesh_index_to_layer_index, objectives, *, tolerance=None, filtered_networks=None,
+                            disconnected_meshes_by_layer=None, partition=None, timings: Optional[dict] = None):
+    """``solve_meshed`` with an estimate of how far each voltage drop is off: (Solution, ErrorReport, [GoalError per objective]).
+
+    An objective is a pair (p, n) of NodeIDs (:func:`check_objectives`), J = V(p) - V(n).  The estimate is dual-weighted:
+    face by face, the gradient-recovery error of the solution x (field 0) against that of the adjoint lambda_j of the
+    objective (field 1 + j; lambda_j = V W[j] as in :func:`solve_meshed_sensitivities`).  With the notation of
+    :func:`solve_meshed_error`, for a field a: d_c^a = G^a_(corner c) - g_f^a, m_12^a = (d_1^a + d_2^a) / 2, and
+
+    - ``dual_indicators``: eta_f of the adjoint, as ``ErrorReport.indicators`` is eta_f of the solution;
+    - ``contributions``: delta_f = sigma (A_f / 3) (m_12^0 . m_12^(1+j) + m_23^0 . m_23^(1+j) + m_31^0 . m_31^(1+j)), signed:
+      sigma times the exact integral over the face of the product of the two recovered-minus-raw gradient fields [V];
+    - ``weights``: omega_f = eta_f^0 eta_f^(1+j), at least |delta_f| (Cauchy-Schwarz) up to rounding;
+    - ``layers``: per layer (sum omega_f, sum delta_f); ``worst``: per layer the largest omega_f (the lowest global face on
+      a tie), its mesh within the layer, its face and the face's centroid;
+    - ``bound`` = sum omega_f and ``correction`` = -sum delta_f, the estimate of J(exact) - J_h.  The sign: on the copper
+      block M = -K with K the positive stiffness matrix, so lambda = -z for the dual solution K z = c, and
+      J(exact) - J_h = a(e, z - z_h) = -a(e, lambda - lambda_h); the lumped elements' part of the form is left out;
+    - with a ``tolerance`` (absolute, in volts, > 0): ``ratios`` xi_f = omega_f / (tolerance / n_faces) with n_faces the
+      faces of the connected meshes; above 1: refine here.
+
+    The product is small wherever either field is smooth, so a terminal that does not matter to the drop is not flagged.
+    Connections snap to one vertex.  If an objective node lands on the vertex of a source terminal, the drop itself grows
+    like log(1/h) under refinement (the point-terminal model's own property): neither the drop nor the bound settles, and
+    only ``min_size`` or a budget ends an adaptive run.  Objectives on probe nodes away from the sources -- the ends of a
+    high-ohm "voltmeter" resistor between two connections -- converge, and those are what this is for.  An objective whose
+    p and n snap to one unknown has a zero adjoint: all zeros, bound 0.  On meshes with obtuse faces the reference's |cot|
+    edge weights add a consistency error to J_h that is no gradient jump and does not fall with h: the drop then does not
+    settle across meshes and ``correction`` can have the wrong sign, while ``weights`` and ``bound`` still steer the
+    refinement (DESIGN.md, "Goal-oriented error", with figures).
+
+    One call is the block solve of :func:`solve_meshed_sensitivities` (1 + k + 2K columns), then one estimator over all
+    fields on the V the device holds (``padne_kkt_goal_error``, objectives 8 per launch), every sum in a fixed order: two
+    calls give the same bits.  The ErrorReport is ``solve_meshed_error``'s without a tolerance, computed by the same
+    arithmetic on column 0 of this block.  Do not rely on its bits being those of a separate ``solve_meshed_error`` call:
+    column 0 of a block of 1 + k + 2K columns agrees with a one-column solve to the solver's tolerance only, even where the
+    two happen to coincide bit for bit (small boards).  The Solution is filled as ``solve_meshed_sensitivities`` fills it.  ValueError,
+    before anything reaches the device, for invalid objectives, an invalid tolerance (:func:`check_goal_tolerance`) and a
+    ``partition`` over several GPUs.  ``timings`` receives the host time of each step; ``"goal"`` is the estimator's."""
+    _refuse_partition(partition, "goal-oriented error estimates")
+    objectives = check_objectives(prob, objectives, filtered_networks)
+    tolerance = check_goal_tolerance(tolerance)
+    k = len(objectives)
+    laps = _Laps(timings)
+    board = index_board(prob, meshes, mesh_index_to_layer_index, filtered_networks, disconnected_meshes_by_layer)
+    pairs = global_elements(board.filtered_networks, board.node_indexer)
+    terms = woodbury_terms([row for _, row in pairs])
+    idx = board.node_indexer.node_to_global_index
+    objective_rows = [(idx[p], idx[n]) for p, n in objectives]
+    n_cols = sensitivity_block_columns(k, len(terms))
+    laps.lap("indexing")
+    with board.assembled() as (L, _):
+        rows, cols, vals = stamp_sensitivity_block(board.filtered_networks, board.node_indexer, L.shape[0], objective_rows, terms)
+        laps.lap("assembly")
+        log.info(f"Solving {k} adjoint(s) and {2 * len(terms)} regulator column(s) as one block with the Problem")
+        plan, V, residual_norms, res, n_tri, n_mesh = _solve_block_on_device(L, rows, cols, vals, n_cols, 1, laps)
+        W = adjoint_weights(V, k, terms)
+        power = dual = delta = omega = m_omega = m_delta = m_top = m_face = None
+        estimate_arrays = (None,) * 6
+        if n_tri:
+            power, estimate_arrays, dual, delta, omega, m_omega, m_delta, m_top, m_face = plan.goal_error(
+                W, n_tri, len(board.vindex), n_mesh)
+        laps.lap("goal")
+    log.info("Producing the solution, the error report and the goal-oriented estimates")
+    _warn_if_block_stalled(res, residual_norms, cols, vals, n_cols)
+    solution = _column_solution(board, prob, np.ascontiguousarray(V[:, 0]), residual_norms[0], res, power)
+    report = _error_report(prob, board, n_tri, estimate_arrays, None)
+    goals = []
+    for j, ((p, n), (ip, in_)) in enumerate(zip(objectives, objective_rows)):
+        duals, contribs, weights, layer_sums, worst = [], [], [], [], []
+        ratios = [] if tolerance is not None else None
+        bound = total_delta = 0.0
+        for layer_i in range(len(prob.layers)):
+            fd, fc, fw, xis, s_om, s_de, best = [], [], [], [], 0.0, 0.0, None
+            for mesh_i, msh, lo, hi in board.layer_meshes(layer_i):
+                forms = [mesh.TwoForm(msh) for _ in range(3)]
+                if omega is not None:
+                    for tf, arr in zip(forms, (dual, delta, omega)):
+                        tf.values = arr[j, lo:hi]                 # views of this call's own result arrays: no copies
+                    s_om += float(m_omega[j, mesh_i])
+                    s_de += float(m_delta[j, mesh_i])
+                    # meshes come in global face order: a later mesh wins only with a strictly larger omega
+                    if m_face[j, mesh_i] >= 0 and (best is None or m_top[j, mesh_i] > best[0]):
+                        face = int(m_face[j, mesh_i] - lo)
+                        cx, cy = msh.points[msh.triangles[face]].mean(axis=0)
+                        best = (float(m_top[j, mesh_i]), len(fd), face, float(cx), float(cy))
+                if tolerance is not None:
+                    xis.append(goal_ratios(forms[2].values, n_tri, tolerance))
+                fd.append(forms[0])
+                fc.append(forms[1])
+                fw.append(forms[2])
+            duals.append(fd)
+            contribs.append(fc)
+            weights.append(fw)
+            layer_sums.append((s_om, s_de))
+            worst.append(best)
+            bound += s_om
+            total_delta += s_de
+            if tolerance is not None:
+                ratios.append(xis)
+        goals.append(GoalError(nodes=(p, n), value=float(V[ip, 0] - V[in_, 0]), dual_indicators=duals, contributions=contribs,
+                               weights=weights, layers=layer_sums, worst=worst, bound=bound,
+                               correction=GOAL_CORRECTION_SIGN * total_delta, ratios=ratios, tolerance=tolerance))
+    laps.lap("solutions")
+    return solution, report, goals
+
+
+def solve_goal_error(prob, objectives, mesher_config: Optional[mesh.Mesher.Config] = None, *, tolerance=None, mesher=None,
+                     partition=None):
+    """``solve`` with the goal-oriented estimates of :func:`solve_meshed_goal_error`: the board is meshed once.  Returns
+    (Solution, ErrorReport, [GoalError per objective])."""
+    _refuse_partition(partition, "goal-oriented error estimates")
+    objectives = check_objectives(prob, objectives)
+    tolerance = check_goal_tolerance(tolerance)
+    meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
+    return solve_meshed_goal_error(prob, meshes, mesh_index_to_layer_index, objectives, tolerance=tolerance)
+
+
+@dataclass
+class GoalAdaptiveHistory(AdaptiveHistory):
+    """What :func:`solve_meshed_goal_adaptive` did: an AdaptiveHistory (``estimates`` stays the energy-norm estimate of each
+    solve) with, per solve, one entry per objective."""
+    values: list = field(default_factory=list)           # J_h [V]
+    bounds: list = field(default_factory=list)           # GoalError.bound [V]
+
+
+def check_goal_adaptive_arguments(tolerance, max_rounds, max_faces, min_size) -> tuple:
+    """:func:`check_adaptive_arguments` with the goal tolerance in place of the relative one: (tolerance, max_rounds,
+    max_faces, min_size) checked, or ValueError; the tolerance as :func:`check_goal_tolerance` wants it and not None."""
+    tolerance = check_goal_tolerance(tolerance)
+    if tolerance is None:
+        raise ValueError("tolerance must be a number of volts greater than 0: an adaptive solve needs one")
+    _, max_rounds, max_faces, min_size = check_adaptive_arguments(0.5, max_rounds, max_faces, min_size)
+    return tolerance, max_rounds, max_faces, min_size
+
+
+def solve_meshed_goal_adaptive(prob, meshes, mesh_index_to_layer_index, objectives, *, tolerance, max_rounds=8, max_faces=None,
+                               min_size=0.0, filtered_networks=None, disconnected_meshes_by_layer=None, partition=None,
+                               timings: Optional[dict] = None):
+    """Solve, estimate, flag, refine, until every drop's bound meets ``tolerance`` [V]: (Solution, ErrorReport,
+    [GoalError per objective], GoalAdaptiveHistory).
+
+    The loop and the reasons are those of :func:`solve_meshed_adaptive`, steered by :func:`solve_meshed_goal_error`:
+
+    - ``"tolerance"`` when max_j bound_j <= ``tolerance``;
+    - ``"floor"`` when no face has max_j xi_jf > 1 and h_f > ``min_size``;
+    - ``"rounds"`` after ``max_rounds`` solves;
+    - ``"faces"`` when the refined meshes would have more than ``max_faces`` faces: they are discarded.
+
+    ``history.values`` and ``history.bounds`` hold J_h and the bound of every objective for each solve;
+    ``history.estimates`` stays the energy-norm estimate.  The results are those of the last solve, the bits
+    ``solve_meshed_goal_error`` gives on ``history.meshes``.  See there for objectives that sit on a source terminal: their
+    bound does not settle and only ``min_size`` or a budget ends the run.  Arguments are checked once, before the first
+    solve (:func:`check_objectives`, :func:`check_goal_adaptive_arguments`; a ``partition`` over several GPUs is refused)."""
+    _refuse_partition(partition, "adaptive solves")
+    objectives = check_objectives(prob, objectives, filtered_networks)
+    tolerance, max_rounds, max_faces, min_size = check_goal_adaptive_arguments(tolerance, max_rounds, max_faces, min_size)
+    meshes = [m if isinstance(m, mesh.Mesh) else mesh.Mesh.from_reference(m) for m in meshes]
+    layer_of = list(mesh_index_to_layer_index)
+    history = GoalAdaptiveHistory()
+    spent = {"solve": 0.0, "refine": 0.0}
+    while True:
+        since = time.perf_counter()
+        solution, report, goals = solve_meshed_goal_error(prob, meshes, layer_of, objectives, tolerance=tolerance,
+                                                          filtered_networks=filtered_networks,
+                                                          disconnected_meshes_by_layer=disconnected_meshes_by_layer)
+        spent["solve"] += time.perf_counter() - since
+        history.faces.append(sum(len(m.triangles) for m in meshes))
+        history.vertices.append(sum(len(m.points) for m in meshes))
+        history.estimates.append(report.estimate)
+        history.values.append([g.value for g in goals])
+        history.bounds.append([g.bound for g in goals])
+        history.flagged.append(0)
+        history.closure_edges.append(0)
+        history.meshes = meshes
+        log.info("Goal-adaptive round %d: %d faces, largest bound %.3e V", len(history.faces), history.faces[-1],
+                 max(history.bounds[-1]))
+        if max(history.bounds[-1]) <= tolerance:
+            history.reason = "tolerance"
+            break
+        flags = [None] * len(meshes)
+        for layer_i in range(len(prob.layers)):
+            members = [mi for mi, l in enumerate(layer_of) if l == layer_i]
+            for pos, mi in enumerate(members):
+                xi = np.max([g.ratios[layer_i][pos] for g in goals], axis=0)
+                flags[mi] = (xi > 1.0) & (face_sizes(meshes[mi].points, meshes[mi].triangles) > min_size)
+        history.flagged[-1] = int(sum(int(f.sum()) for f in flags))
+        if history.flagged[-1] == 0:
+            history.reason = "floor"
+            break
+        if len(history.faces) >= max_rounds:
+            history.reason = "rounds"
+            break
+        since = time.perf_counter()
+        refined = refine_meshes(meshes, flags)
+        spent["refine"] += time.perf_counter() - since
+        history.closure_edges[-1] = refined.marked - refined.marked_by_flags
+        if max_faces is not None and sum(len(m.triangles) for m in refined.meshes) > max_faces:
+            history.reason = "faces"
+            break
+        meshes = refined.meshes
+    if timings is not None:
+        timings.update(spent)
+    return solution, report, goals, history
+
+
+def solve_goal_adaptive(prob, objectives, mesher_config: Optional[mesh.Mesher.Config] = None, *, tolerance, mesher=None,
+                        max_rounds=8, max_faces=None, min_size=0.0, partition=None, timings: Optional[dict] = None):
+    """``solve`` refined where the voltage drops ask: the board is meshed once, then :func:`solve_meshed_goal_adaptive`.
+    Returns (Solution, ErrorReport, [GoalError per objective], GoalAdaptiveHistory)."""
+    _refuse_partition(partition, "adaptive solves")
+    objectives = check_objectives(prob, objectives)
+    check_goal_adaptive_arguments(tolerance, max_rounds, max_faces, min_size)
+    meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
+    return solve_meshed_goal_adaptive(prob, meshes, mesh_index_to_layer_index, objectives, tolerance=tolerance,
+                                      max_rounds=max_rounds, max_faces=max_faces, min_size=min_size, timings=timings)
 
 
 # --------------------------------------------------------------------------------------------
