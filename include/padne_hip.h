@@ -349,6 +349,18 @@ int padne_kkt_solve_block_coo(padne_ctx *ctx, padne_kkt *plan, int32_t n_cols, i
  * crosses PCIe but the result.  PADNE_E_INVALID when no block has been finished since the last solve, when n_cols is not
  * that block's, or when `L` carries no mesh. */
 int padne_kkt_power_density_block(padne_ctx *ctx, padne_kkt *plan, int32_t n_cols, double *out_host);
+/* Element cases: from the block V[N][n_cols] the last padne_kkt_finish_block left on the device, form V'[N][n_out] with
+ * V'[i][c] = sum over the entries e = w_ptr[c] .. w_ptr[c + 1] - 1 of row c, in that order, of w_val[e] * V[i][w_col[e]]
+ * (CSR weights, one row per output column).  The first product starts the sum and no product is fused with its addition,
+ * so a row of one entry with coefficient 1.0 copies the column's bits; a row without entries gives zeros.  V' becomes the
+ * block the plan holds, as if padne_kkt_finish_block had left it with n_out columns: padne_kkt_power_density_block,
+ * padne_kkt_current_cases, padne_kkt_error_estimate and the others then work on it unchanged (and a further
+ * padne_kkt_combine_block combines V').  V' also goes to v_host[N][n_out] if that is not null.  Out of place: V and V'
+ * are on the device together, (n_cols + n_out) * N * 8 bytes.  No atomics: two calls give the same bits.  Preconditions
+ * and errors as padne_kkt_power_density_block; PADNE_E_INVALID also unless 1 <= n_out <= 4096, w_ptr[0] = 0 and w_ptr is
+ * monotone, the columns of every row are strictly ascending and in [0, n_cols), and every coefficient is finite. */
+int padne_kkt_combine_block(padne_ctx *ctx, padne_kkt *plan, int32_t n_cols, int32_t n_out, const int64_t *w_ptr,
+                            const int32_t *w_col, const double *w_val, double *v_host);
 /* Adjoint sensitivities over the mesh `L` keeps, from the block the last padne_kkt_finish_block left on the device: column 0
  * of V is the solution x, the other columns are the solutions the adjoints are combined from.  Adjoint j is
  * lambda_j = sum_m weights[j][m] V[:, m] (weights[n_obj][n_cols] row-major; a selection when L is symmetric, the Woodbury

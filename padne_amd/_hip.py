@@ -112,6 +112,7 @@ SIGNATURES = {
                                             _PI64, _PF64, _I64, _PI64, _PF64, C.POINTER(SolveOpts), C.c_double,
                                             C.POINTER(SolveInfo)]),
     "padne_kkt_power_density_block": (C.c_int, [_P, _P, C.c_int32, _PF64]),
+    "padne_kkt_combine_block": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _PI64, _PI32, _PF64, _PF64]),
     "padne_kkt_sensitivity_block": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _PF64, _PF64, _PF64, _PF64]),
     "padne_kkt_current_report": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int32, _PI32, C.c_int32, _PI32, _PF64, _PF64, _PF64,
                                            _PF64, _PI64, _PF64]),
@@ -814,6 +815,23 @@ class KktPlan:
         last solve, on another column count, and on a matrix without a mesh."""
         out = self._result_array((int(n_cols), int(n_tri)), "pd")
         _check(self.ctx._lib.padne_kkt_power_density_block(self.ctx._h, self._h, int(n_cols), _ptr(out, _PF64)))
+        return out
+
+    def combine_block(self, n_cols: int, w_ptr, w_col, w_val, download: bool = True):
+        """Element cases: the block V (N, n_cols) the last ``finish_block`` left on the device becomes V' (N, n_out) with
+        V'[:, c] = sum_e w_val[e] V[:, w_col[e]] over the entries e = w_ptr[c] .. w_ptr[c + 1] - 1 of row c of the CSR weights,
+        in that order (the first product starts the sum; a row of one entry 1.0 copies the column's bits).  V' takes the
+        block's place on the device -- ``power_density_block(n_out, ...)``, ``current_cases`` and the others then work on it --
+        and is returned (N, n_out) C-contiguous unless ``download`` is False (then None).  V and V' are on the device
+        together: (n_cols + n_out) * N * 8 bytes.  Raises ValueError as ``power_density_block`` does, and unless
+        1 <= n_out <= 4096, every row's columns are strictly ascending and in [0, n_cols) and every coefficient is finite."""
+        ptr, col, val = _i64(w_ptr).reshape(-1), _i32(w_col).reshape(-1), _f64(w_val).reshape(-1)
+        if ptr.shape[0] < 1 or col.shape[0] != val.shape[0] or (ptr.shape[0] > 1 and int(ptr[-1]) != col.shape[0]):
+            raise ValueError("w_ptr must have n_out + 1 entries, the last one the number of weights in w_col and w_val")
+        n_out = ptr.shape[0] - 1
+        out = np.empty((self.N, n_out), dtype=np.float64) if download and 1 <= n_out <= 4096 else None
+        _check(self.ctx._lib.padne_kkt_combine_block(self.ctx._h, self._h, int(n_cols), n_out, _ptr(ptr, _PI64), _ptr(col, _PI32),
+                                                     _ptr(val, _PF64), _ptr(out, _PF64) if out is not None else None))
         return out
 
     def sensitivity_block(self, weights, n_tri: int, n_mesh: int):

@@ -394,6 +394,9 @@ int launch_current_faces(padne_ctx *ctx, const padne_csr *m, const long long *ti
 int launch_current_cuts(padne_ctx *ctx, const padne_csr *m, const long long *tile_dev, int n_cols, int n_report,
                         const double *V_dev, int n_cut, const double *cut_xy_dev, long long n_pairs, const int *pair_cut_dev,
                         const long long *pair_tile_dev, const long long *pair_off_host, double *cut_dev, int *bad_dev);
+// cases.hip: out_dev[N][n_out] = V_dev[N][n_cols] times the transposed CSR weights on the device (padne_kkt_combine_block)
+int launch_combine_block(padne_ctx *ctx, long long N, int n_cols, int n_out, long long nnz, const int *w_ptr_dev,
+                         const int *w_col_dev, const double *w_val_dev, const double *V_dev, double *out_dev);
 
 // Per-context caching allocator.  All work of a context is ordered on its one stream, so a block handed back
 // may be reused by later launches without synchronisation.  Blocks are kept (up to kPoolCacheLimit) until the

@@ -60,6 +60,8 @@ struct padne_kkt {
     bool finished = false;
     const double *v_final = nullptr;
     int finished_cols = 0;
+    // the block padne_kkt_combine_block formed, [N][finished_cols] (v_final points at it until the next solve frees it)
+    double *combined = nullptr;
     double setup_seconds_last = 0.0;
     // vertex -> incident faces of L's mesh, rows in ascending face order (error.hip): built by the first
     // padne_kkt_error_estimate and kept, [mesh_n_vert + 1] and [3 mesh_n_tri]
@@ -536,7 +538,7 @@ static void kkt_free(padne_kkt *k) {
     for (void *p : {(void *)k->imap, (void *)k->src_of, (void *)k->tied_member, (void *)k->tied_target, (void *)k->tied_order,
                     (void *)k->tied_gptr, (void *)k->r, (void *)k->v,
                     (void *)k->w, (void *)k->c, (void *)k->b, (void *)k->y, (void *)k->Z, (void *)k->err_vptr,
-                    (void *)k->err_vface})
+                    (void *)k->err_vface, (void *)k->combined})
         if (p != nullptr) pool_free(ctx, p);
     delete k;
 }
@@ -707,6 +709,11 @@ static int kkt_solve_block(padne_ctx *ctx, padne_kkt *k, const int n_cols, const
     PADNE_REQUIRE(ctx && k && opts, "null argument");
     PADNE_REQUIRE(k->ctx == ctx, "the plan belongs to another context");
     k->finished = false;
+    if (k->combined != nullptr) {            // a combined block ends with the solve that follows it
+        pool_free(ctx, k->combined);
+        k->combined = nullptr;
+        k->v_final = nullptr;
+    }
     PADNE_REQUIRE(r_host != nullptr || rhs.n_entries == 0 || (rhs.row && rhs.col && rhs.val), "null argument");
     PADNE_REQUIRE(n_cols >= 1 && n_extra >= 0 && n_cols + n_extra <= 4096, "at most 4096 right-hand sides with the extra ones");
     PADNE_REQUIRE(r_host != nullptr || rhs.n_entries >= 0, "number of right-hand side entries");
@@ -1156,6 +1163,53 @@ extern "C" int padne_kkt_power_density_block(padne_ctx *ctx, padne_kkt *k, int32
     PADNE_TRY(launch_power_density_block(ctx, L, n_cols, k->v_final, d_out, d_bad));
     PADNE_TRY(bad_flag_check(s, d_bad));
     return parallel_copy(k, out_host, d_out, sizeof(double) * (size_t)n_tri * (size_t)n_cols, hipMemcpyDeviceToHost);
+}
+
+// Element cases (cases.hip; DESIGN.md, "Element cases"): V' = V W^T for the CSR weights W [n_out][n_cols], out of place into
+// a block of its own that takes the finished block's place.  The weights are checked here, before the device is touched.
+extern "C" int padne_kkt_combine_block(padne_ctx *ctx, padne_kkt *k, int32_t n_cols, int32_t n_out, const int64_t *w_ptr,
+                                       const int32_t *w_col, const double *w_val, double *v_host) {
+    PADNE_TRY(require_finished_block("padne_kkt_combine_block", ctx, k, n_cols));
+    PADNE_REQUIRE(n_out >= 1 && n_out <= 4096, "between 1 and 4096 combined columns");
+    PADNE_REQUIRE(w_ptr != nullptr, "null argument");
+    PADNE_REQUIRE(w_ptr[0] == 0, "the weights' row pointer starts at 0");
+    for (int c = 0; c < n_out; ++c)
+        PADNE_REQUIRE(w_ptr[c + 1] >= w_ptr[c] && w_ptr[c + 1] - w_ptr[c] <= n_cols, "the weights' row pointer must be monotone");
+    const long long nnz = w_ptr[n_out];
+    PADNE_REQUIRE(nnz == 0 || (w_col && w_val), "null argument");
+    std::vector<int> h_ptr((size_t)n_out + 1);
+    for (int c = 0; c <= n_out; ++c) h_ptr[(size_t)c] = (int)w_ptr[c];
+    for (int c = 0; c < n_out; ++c)
+        for (long long e = w_ptr[c]; e < w_ptr[c + 1]; ++e) {
+            PADNE_REQUIRE(w_col[e] >= 0 && w_col[e] < n_cols, "weight column out of range");
+            PADNE_REQUIRE(e == w_ptr[c] || w_col[e] > w_col[e - 1], "the columns of a row of weights must be strictly ascending");
+            PADNE_REQUIRE(std::isfinite(w_val[e]), "weights must be finite");
+        }
+    PADNE_HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const long long N = k->N;
+    Scratch sc(ctx);
+    int *d_ptr = nullptr, *d_col = nullptr;
+    double *d_val = nullptr, *d_new = nullptr;
+    PADNE_TRY(sc.alloc(&d_ptr, (size_t)n_out + 1));
+    PADNE_TRY(sc.alloc(&d_col, (size_t)nnz));
+    PADNE_TRY(sc.alloc(&d_val, (size_t)nnz));
+    PADNE_TRY(sc.alloc(&d_new, (size_t)(N > 0 ? N : 1) * (size_t)n_out));
+    PADNE_HIP_CHECK(hipMemcpyAsync(d_ptr, h_ptr.data(), sizeof(int) * ((size_t)n_out + 1), hipMemcpyHostToDevice, s));
+    if (nnz > 0) {
+        PADNE_HIP_CHECK(hipMemcpyAsync(d_col, w_col, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, s));
+        PADNE_HIP_CHECK(hipMemcpyAsync(d_val, w_val, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, s));
+    }
+    PADNE_TRY(launch_combine_block(ctx, N, n_cols, n_out, nnz, d_ptr, d_col, d_val, k->v_final, d_new));
+    PADNE_HIP_CHECK(hipStreamSynchronize(s));           // the host arrays above are the caller's and h_ptr is this frame's
+    sc.disown(d_new);
+    if (k->combined != nullptr) pool_free(ctx, k->combined);       // a block combined before: it was this call's input
+    k->combined = d_new;
+    k->v_final = d_new;
+    k->finished_cols = n_out;
+    if (v_host != nullptr && N > 0)
+        PADNE_TRY(parallel_copy(k, v_host, d_new, sizeof(double) * (size_t)N * (size_t)n_out, hipMemcpyDeviceToHost));
+    return PADNE_OK;
 }
 
 // the first 256-triangle tile of every mesh of `L`, from its triangle offsets: tile[m] .. tile[m + 1] are mesh m's tiles, the

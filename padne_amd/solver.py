@@ -22,6 +22,8 @@ compute_power_density :728-745         ``power_density_kernel``
                                        regulators, ``sensitivity_block_kernel`` over the faces
 (where the current goes)               ``solve_currents``: the load-case block with one column, ``current_cases_face_kernel``
                                        and ``current_cases_cut_kernel`` over the faces, element flows from V's rows
+(what if a via cracks open)            ``solve_element_cases``: the load-case block plus one unit-current column per changed
+                                       resistor, Woodbury on the host, ``combine_block_kernel`` forms the cases' potentials
 (how far the mesh is from the board)   ``solve_error``: the same block, gradient recovery through vertex -> faces lists
                                        (``error_recover_kernel``) and ``error_indicator_kernel`` over the faces
 (a finer mesh where that asks)         ``refine_meshes`` / ``solve_adaptive``: longest-edge refinement with conforming
@@ -1831,6 +1833,299 @@ def solve_load_case_currents(prob, cases, cuts=(), mesher_config: Optional[mesh.
     meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
     return solve_meshed_load_case_currents(prob, meshes, mesh_index_to_layer_index, cases,
                                            [Cut(prob.layers[i], a, b) for i, a, b in cuts], per_case_fields=per_case_fields)
+
+
+# --------------------------------------------------------------------------------------------
+# element cases: what-if cases that change resistors as well as sources (DESIGN.md "Element cases")
+# --------------------------------------------------------------------------------------------
+
+# sigma_c, the smallest singular value of a case's G = I + C D_S^T Z_S, is 1 for a case without resistors, and 1 / sigma_c
+# is how much the case amplifies the error of the block's columns (held to 1e-8): at or below the first no digit is left
+# (the change disconnects driven copper or leaves a node floating), below the second the case is reported.
+ELEMENT_CASE_SINGULAR_AT = 1e-8
+ELEMENT_CASE_WARN_BELOW = 1e-3
+
+
+@dataclass
+class ElementCaseReport:
+    """What :func:`solve_meshed_element_cases` reports next to the Solutions."""
+    conditioning: np.ndarray          # (n_cases,) sigma_c: smallest singular value of the case's G (1.0 without resistors)
+    columns: int                      # columns of the one block solve behind all cases
+    drops: Optional[np.ndarray]       # (n_cases, n_objectives) V(p) - V(n) per case [V]; None without objectives
+
+
+def check_element_cases(prob, cases) -> list:
+    """The element cases of ``prob`` as a list of ``{element: float}``, or ValueError.
+
+    ``cases`` is a non-empty sequence of mappings ``{element: value}``.  A source key is taken exactly as
+    :func:`check_load_cases` takes it (its ground rule included); a ``Resistor`` of ``prob.networks`` takes a resistance
+    > 0, or ``math.inf`` for the resistor left open.  NaN, a resistance <= 0, an element that is not in the Problem and
+    any other key -- a regulator's gain, a layer's conductance: they are not resistor stamps -- are refused."""
+    if isinstance(cases, (Mapping, str, bytes)):
+        raise ValueError("cases must be a sequence of mappings {element: value}, one per element case")
+    cases = list(cases)
+    if not cases:
+        raise ValueError("no element cases: give at least one mapping {element: value} ({} is the Problem as given)")
+    elements = {element for network in prob.networks for element in network.elements}
+    source_parts, resistor_parts = [], []
+    for j, case in enumerate(cases):
+        if not isinstance(case, Mapping):
+            raise ValueError(f"element case {j} is not a mapping {{element: value}}")
+        sources, resistors = {}, {}
+        for element, value in case.items():
+            kind = element_kind(element)
+            if kind in CASE_FIELDS:
+                sources[element] = value
+                continue
+            if kind != "Resistor":
+                raise ValueError(f"element case {j}: a {type(element).__name__} key cannot vary between element cases -- only "
+                                 "the value of a source and the resistance of a Resistor can; a regulator's gain and a layer's "
+                                 "conductance are not resistor stamps")
+            if element not in elements:
+                raise ValueError(f"element case {j}: the Resistor is not an element of the Problem's networks")
+            try:
+                x = float(value)
+            except (TypeError, ValueError):
+                raise ValueError(f"element case {j}: the resistance of a Resistor must be a number, not {value!r}") from None
+            if not x > 0:
+                raise ValueError(f"element case {j}: the resistance of a Resistor must be > 0 (math.inf leaves it open), "
+                                 f"not {value!r}")
+            resistors[element] = x
+        source_parts.append(sources)
+        resistor_parts.append(resistors)
+    source_parts = check_load_cases(prob, source_parts)
+    return [{**sources, **resistors} for sources, resistors in zip(source_parts, resistor_parts)]
+
+
+def substitute_element_case(prob, case: dict):
+    """``prob`` with one checked element case applied: sources and resistors replaced (``dataclasses.replace``), a resistor
+    at ``math.inf`` removed from its network; the networks rebuilt around the same NodeIDs and connections, the layers
+    shared.  Returns the Problem."""
+    if not case:
+        return prob
+    networks = []
+    for network in prob.networks:
+        if not any(element in case for element in network.elements):
+            networks.append(network)
+            continue
+        elements = []
+        for e in network.elements:
+            if e not in case:
+                elements.append(e)
+            elif element_kind(e) == "Resistor":
+                if math.isfinite(case[e]):
+                    elements.append(dataclasses.replace(e, resistance=case[e]))
+            else:
+                elements.append(dataclasses.replace(e, **{CASE_FIELDS[element_kind(e)]: case[e]}))
+        networks.append(dataclasses.replace(network, elements=elements))
+    return dataclasses.replace(prob, networks=networks)
+
+
+def open_circuit_cases(prob, elements=None) -> list:
+    """The N-1 list: ``[{R: math.inf}]`` for every Resistor of ``prob.networks`` in stamping order, or for those among
+    ``elements`` (ValueError for one that is not a Resistor of the Problem)."""
+    resistors = [e for network in prob.networks for e in network.elements if element_kind(e) == "Resistor"]
+    if elements is not None:
+        wanted = list(elements)
+        for e in wanted:
+            if element_kind(e) != "Resistor" or e not in resistors:
+                raise ValueError("open_circuit_cases: every element must be a Resistor of the Problem's networks")
+        resistors = [e for e in resistors if e in wanted]
+    return [{e: math.inf} for e in resistors]
+
+
+def element_case_columns(pairs, cases: list):
+    """How the checked element ``cases`` share one block, from the solved networks' ``pairs`` (:func:`global_elements`):
+
+    - ``source_cases``: the distinct source settings among the cases in first-appearance order (``{}`` is the Problem's),
+      one block column each; when no case names a resistor, one per case as :func:`stamp_load_cases` takes them;
+    - ``case_source[c]``: the column of case c's setting;
+    - ``resistor_rows``: ``(a, b, g)`` on global unknowns of every resistor row that a case changes, in stamping order, one
+      column ``d = e_a - e_b`` each after the source columns; a resistor with both terminals on one unknown gets none;
+    - ``case_changes[c]``: ``(m, g, g')`` per changed resistor column m of case c, ascending (g' = 0: open)."""
+    named = {e for case in cases for e in case if element_kind(e) == "Resistor"}
+    source_cases, case_source, seen = [], [], {}
+    for case in cases:
+        sources = {e: v for e, v in case.items() if element_kind(e) != "Resistor"}
+        key = frozenset(sources.items()) if named else len(source_cases)
+        if key not in seen:
+            seen[key] = len(source_cases)
+            source_cases.append(sources)
+        case_source.append(seen[key])
+    resistor_rows, column_of = [], {}
+    for i, (element, row) in enumerate(pairs):
+        if row[0] == "R" and element in named and row[1] != row[2]:
+            column_of[i] = len(resistor_rows)
+            resistor_rows.append((int(row[1]), int(row[2]), 1.0 / row[3]))
+    case_changes = []
+    for case in cases:
+        changes = []
+        for i, m in column_of.items():
+            element = pairs[i][0]
+            if element in case:
+                g, g_new = resistor_rows[m][2], (1.0 / case[element] if math.isfinite(case[element]) else 0.0)
+                if g_new != g:
+                    changes.append((m, g, g_new))
+        case_changes.append(changes)
+    return source_cases, case_source, resistor_rows, case_changes
+
+
+def stamp_element_case_block(filtered_networks, node_indexer: NodeIndexer, n_unknowns: int, source_cases: list,
+                             resistor_rows: list):
+    """COO triples (rows, cols, vals) of the block [R_src | D] of element cases: the columns of :func:`stamp_load_cases` for
+    ``source_cases``, then ``d = e_a - e_b`` per entry of ``resistor_rows`` (the unit-current column of
+    :func:`stamp_sensitivity_block`)."""
+    rows, cols, vals = stamp_load_cases(filtered_networks, node_indexer, n_unknowns, source_cases)
+    rows, cols, vals = rows.tolist(), cols.tolist(), vals.tolist()
+    for m, (a, b, _g) in enumerate(resistor_rows):
+        rows.extend((int(a), int(b)))
+        cols.extend((len(source_cases) + m, len(source_cases) + m))
+        vals.extend((1.0, -1.0))
+    return np.asarray(rows, dtype=np.int64), np.asarray(cols, dtype=np.int32), np.asarray(vals, dtype=DTYPE)
+
+
+def element_case_weights(DtV: np.ndarray, n_src: int, case_source: list, case_changes: list):
+    """The weights of every element case on the columns of the solved block V = M^-1 [R_src | D], as CSR rows
+    ``(w_ptr (n_cases + 1,), w_col, w_val)``, and ``sigma (n_cases,)``.  ``DtV`` (n_resistor_columns, n_cols) is D^T V: row m
+    is V[a_m] - V[b_m], all that is read of V.
+
+    A set S of changed resistors makes the system M + D_S C D_S^T with C = diag(g - g').  By Woodbury, with Z_S the solved
+    ``d`` columns and s the case's source column, G = I + C (D_S^T Z_S), w = -G^-1 C (D_S^T V[:, s]) and
+    x' = V[:, s] + Z_S w: only forward solves with M, so a regulator's unsymmetric M is no exception.  A row lists the source
+    column with coefficient exactly 1.0 and then the non-zero w, columns ascending.  sigma_c is the smallest singular value
+    of G: SingularSystemError naming the case at or below ELEMENT_CASE_SINGULAR_AT, a SolverWarning naming the case and
+    1 / sigma_c below ELEMENT_CASE_WARN_BELOW."""
+    DtV = np.asarray(DtV, dtype=DTYPE)
+    w_ptr, w_col, w_val, sigma = [0], [], [], np.ones(len(case_source), dtype=DTYPE)
+    for c, (s, changes) in enumerate(zip(case_source, case_changes)):
+        w_col.append(int(s))
+        w_val.append(1.0)
+        if changes:
+            S = np.array([m for m, _, _ in changes], dtype=np.int64)
+            C = np.array([g - g_new for _, g, g_new in changes], dtype=DTYPE)
+            G = np.eye(len(S)) + C[:, None] * DtV[S][:, int(n_src) + S]
+            sigma[c] = np.linalg.svd(G, compute_uv=False).min()
+            if not sigma[c] > ELEMENT_CASE_SINGULAR_AT:
+                raise SingularSystemError(f"element case {c}: the changed system is singular to working precision (smallest "
+                                          f"singular value of its {len(S)} x {len(S)} update {sigma[c]:.1e}): the change "
+                                          "disconnects driven copper or leaves a node floating")
+            if sigma[c] < ELEMENT_CASE_WARN_BELOW:
+                warnings.warn(f"element case {c} is ill-conditioned: it amplifies the error of the block's columns "
+                              f"{1.0 / sigma[c]:.1e} times", SolverWarning)
+            w = -np.linalg.solve(G, C * DtV[S, int(s)])
+            for m, x in zip(S.tolist(), w.tolist()):
+                if x != 0.0:
+                    w_col.append(int(n_src) + m)
+                    w_val.append(x)
+        w_ptr.append(len(w_col))
+    return (np.asarray(w_ptr, dtype=np.int64), np.asarray(w_col, dtype=np.int32), np.asarray(w_val, dtype=DTYPE), sigma)
+
+
+def _case_weight_matrix(w_ptr, w_col, w_val, n_cols: int) -> sp.csr_matrix:
+    return sp.csr_matrix((w_val, w_col, w_ptr), shape=(len(w_ptr) - 1, int(n_cols)))
+
+
+def element_case_residual_bounds(w_ptr, w_col, w_val, residual_norms: np.ndarray) -> np.ndarray:
+    """``sum_m |w_cm| residual_norms[m]`` per case: with rho_m = M V[:, m] - R[:, m], the changed system's residual of case c
+    is exactly sum_m w_cm rho_m (the defining equation of w cancels the rest), so this bounds its norm."""
+    W = _case_weight_matrix(w_ptr, w_col, np.abs(w_val), len(residual_norms))
+    return np.asarray(W @ np.asarray(residual_norms, dtype=DTYPE)).reshape(-1)
+
+
+def solve_meshed_element_cases(prob, meshes, mesh_index_to_layer_index, cases, *, objectives=None, fields=True,
+                               filtered_networks=None, disconnected_meshes_by_layer=None, partition=None,
+                               timings: Optional[dict] = None):
+    """``solve_meshed`` for what-if cases that change resistors as well as sources -- a via cracked open, a tolerance corner of
+    a sense resistor, a second via -- from one block solve: ([Solution per case], :class:`ElementCaseReport`).
+
+    ``cases`` as :func:`check_element_cases` takes them.  A resistor between unknowns a and b stamps -g d d^T into the system
+    M, d = e_a - e_b, so a set of changed resistors is a low-rank update of M and every case follows from V = M^-1 [R_src | D]
+    by Woodbury (:func:`element_case_columns`, :func:`element_case_weights`): one indexing, assembly, reduction and
+    multigrid setup for all cases.  The small systems are solved on the host from the rows of V at the resistors' unknowns;
+    the device then turns V into the cases' potentials (``KktPlan.combine_block``) without V crossing again, and
+    ``power_density_block`` runs on the result.  V (N, columns) and the cases' potentials (N, n_cases) are on the device
+    together, ``(columns + n_cases) * N * 8`` bytes; nothing is chunked.
+
+    Solution c carries the Problem with case c substituted (:func:`substitute_element_case`), its own potentials and power
+    densities, and a SolverInfo whose ``ground_node_current`` is its own (warned about as usual, opened by ``"Case c: "``)
+    and whose ``residual_norm`` is a BOUND on the residual of the changed system, sum_m |w_cm| ||M V[:, m] - R[:, m]||
+    (:func:`element_case_residual_bounds`); ``iterations``, ``rel_residual`` and ``solve_seconds`` are the block's.  The
+    report holds each case's conditioning sigma_c (SingularSystemError at or below 1e-8, a SolverWarning below 1e-3), the
+    number of block columns and, with ``objectives`` (pairs (p, n) as :func:`check_objectives` takes them), ``drops[c, j]``
+    = V(p_j) - V(n_j) in case c, formed on the host from the rows of V at those nodes.
+
+    ``fields=False`` skips the combination and the power densities: ``solutions`` is None and only the report comes back
+    (the N-1 sweep over hundreds of vias).  When no case names a resistor, with ``fields`` and without ``objectives``, the
+    call is ``solve_meshed_load_cases``.  ValueError, before anything reaches the device, for invalid cases or objectives
+    and for a ``partition`` over several GPUs.  ``timings`` (a dict) receives the host time of each step in seconds and
+    ``combine_calls``, how often ``combine_block`` ran."""
+    _refuse_partition(partition, "element cases")
+    cases = check_element_cases(prob, cases)
+    if objectives is not None:
+        objectives = check_objectives(prob, objectives, filtered_networks)
+    n_cases = len(cases)
+    if fields and objectives is None and not any(element_kind(e) == "Resistor" for case in cases for e in case):
+        solutions = solve_meshed_load_cases(prob, meshes, mesh_index_to_layer_index, cases, filtered_networks=filtered_networks,
+                                            disconnected_meshes_by_layer=disconnected_meshes_by_layer, timings=timings)
+        if timings is not None:
+            timings["combine_calls"] = 0
+        return solutions, ElementCaseReport(conditioning=np.ones(n_cases, dtype=DTYPE), columns=n_cases, drops=None)
+    laps = _Laps(timings)
+    board = index_board(prob, meshes, mesh_index_to_layer_index, filtered_networks, disconnected_meshes_by_layer)
+    pairs = global_elements(board.filtered_networks, board.node_indexer)
+    source_cases, case_source, resistor_rows, case_changes = element_case_columns(pairs, cases)
+    n_src = len(source_cases)
+    n_cols = n_src + len(resistor_rows)
+    idx = board.node_indexer.node_to_global_index
+    laps.lap("indexing")
+    combine_calls = 0
+    with board.assembled() as (L, _):
+        rows, cols, vals = stamp_element_case_block(board.filtered_networks, board.node_indexer, L.shape[0], source_cases,
+                                                    resistor_rows)
+        laps.lap("assembly")
+        log.info(f"Solving {n_cases} element case(s) from one block of {n_src} source and {len(resistor_rows)} resistor column(s)")
+        plan, V, residual_norms, res, n_tri, _n_mesh = _solve_block_on_device(L, rows, cols, vals, n_cols, n_cases, laps)
+        a = np.array([r[0] for r in resistor_rows], dtype=np.int64)
+        b = np.array([r[1] for r in resistor_rows], dtype=np.int64)
+        w_ptr, w_col, w_val, sigma = element_case_weights(V[a] - V[b], n_src, case_source, case_changes)
+        laps.lap("weights")
+        Vc = power = None
+        if fields:
+            Vc = plan.combine_block(n_cols, w_ptr, w_col, w_val)
+            combine_calls += 1
+            laps.lap("combine")
+            power = plan.power_density_block(n_cases, n_tri) if n_tri else None
+            laps.lap("power_density")
+    laps.lap()
+    if timings is not None:
+        timings["combine_calls"] = combine_calls
+    _warn_if_block_stalled(res, residual_norms, cols, vals, n_cols)
+    drops = None
+    if objectives is not None:
+        p = np.array([idx[p] for p, _ in objectives], dtype=np.int64)
+        n = np.array([idx[n] for _, n in objectives], dtype=np.int64)
+        drops = np.asarray(_case_weight_matrix(w_ptr, w_col, w_val, n_cols) @ (V[p] - V[n]).T)
+    report = ElementCaseReport(conditioning=sigma, columns=n_cols, drops=drops)
+    if not fields:
+        laps.lap("solutions")
+        return None, report
+    log.info("Producing the solution objects")
+    bounds = element_case_residual_bounds(w_ptr, w_col, w_val, residual_norms)
+    solutions = [_column_solution(board, substitute_element_case(prob, case), np.ascontiguousarray(Vc[:, c]), bounds[c], res,
+                                  None if power is None else power[c], f"Case {c}: ") for c, case in enumerate(cases)]
+    laps.lap("solutions")
+    return solutions, report
+
+
+def solve_element_cases(prob, cases, mesher_config: Optional[mesh.Mesher.Config] = None, *, mesher=None, objectives=None,
+                        fields=True, partition=None):
+    """``solve`` for element cases (see :func:`solve_meshed_element_cases`): the board is meshed once."""
+    _refuse_partition(partition, "element cases")
+    cases = check_element_cases(prob, cases)
+    if objectives is not None:
+        objectives = check_objectives(prob, objectives)
+    meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
+    return solve_meshed_element_cases(prob, meshes, mesh_index_to_layer_index, cases, objectives=objectives, fields=fields)
 
 
 # --------------------------------------------------------------------------------------------
