@@ -1,6 +1,7 @@
-/* padne_hip_probe.h -- TEST-ONLY kernel probe of libpadne_hip.so.  Neither the drop-in boundary (include/padne_hip.h) nor the
- * multi-rank scaffolding (include/padne_hip_test.h): one entry that drives a single product launcher of the solver on inputs a
- * test chooses, so that every SpMV / SpMM kernel form and epilogue can be held against a host reference.  Bound by
+/* padne_hip_probe.h -- TEST-ONLY probes of libpadne_hip.so.  Neither the drop-in boundary (include/padne_hip.h) nor the
+ * multi-rank scaffolding (include/padne_hip_test.h): two entries.  padne_test_product drives a single product launcher of the
+ * solver on inputs a test chooses, so that every SpMV / SpMM kernel form and epilogue can be held against a host reference;
+ * padne_test_kkt_state copies one device array of a padne_kkt plan out, so that every stage of the plan can.  Bound by
  * padne_amd/_hip.py (PROBE_SIGNATURES). */
 #ifndef PADNE_HIP_PROBE_H
 #define PADNE_HIP_PROBE_H
@@ -55,6 +56,24 @@ int padne_test_product(padne_ctx *ctx, padne_csr *m, int32_t flags, int64_t n_ow
                        int32_t k, int32_t part, const void *x, void *y, void *y2, const void *aux0, const void *aux1,
                        const void *aux2, const void *rhs, const double *dot_with, const int32_t *done_flag, double scale,
                        const double *out_scale2, double *partials_host, int64_t n_partials_host, int32_t *info);
+
+/* ONE device array of a padne_kkt plan, copied to out_host as it lies on the device (tests/test_kkt_plan_vs_reference.py).
+ * Read-only: the entry waits for the context's stream, copies, and changes nothing.
+ *   IMAP     int32[N]                           reduced unknown of every unknown, -1 = none
+ *   SRC_OF   int32[n_free]                      the unknown whose row opens the sum of reduced row t
+ *   B, Y     double[(n_cols + n_extra) n_free]  right-hand sides and solutions of the reduced system, column after column
+ *   C        double[N width]                    known part of the potentials, in the products' layout (kkt.hip, "blocks of
+ *                                               right-hand sides"); only when the last stage 1 had known potentials, and not
+ *                                               after a stage 2 that used the array for the caller's layout (every n_cols
+ *                                               but 1, 2, 4 and 8, where the two layouts coincide)
+ *   V        double[N width]                    the potentials in the products' layout: of stage 1, or final after stage 2
+ *   Z        double[n_extra N]                  expanded solutions of the extra right-hand sides
+ * with n_cols, n_extra of the last stage 1 and width = the doubles per row of its products' layout (n_cols / 8 full groups of
+ * 8, the rest widened to 1, 2, 4 or 8).  PADNE_E_INVALID when n_bytes is not the size of the array, or the array does not
+ * exist yet: B .. Z before the first completed stage 1, C as said. */
+enum { PADNE_TEST_KKT_IMAP = 0, PADNE_TEST_KKT_SRC_OF = 1, PADNE_TEST_KKT_B = 2, PADNE_TEST_KKT_Y = 3, PADNE_TEST_KKT_C = 4,
+       PADNE_TEST_KKT_V = 5, PADNE_TEST_KKT_Z = 6 };
+int padne_test_kkt_state(const padne_kkt *plan, int32_t which, void *out_host, int64_t n_bytes);
 
 #ifdef __cplusplus
 }

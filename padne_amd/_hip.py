@@ -163,10 +163,12 @@ TEST_SIGNATURES = {
     "padne_ctx_reload_options": (C.c_int, [_P]),
 }
 
-# the kernel probe (include/padne_hip_probe.h): one product launcher of the solver, run once on a test's inputs
+# the test probes (include/padne_hip_probe.h): one product launcher of the solver, run once on a test's inputs; one device
+# array of a padne_kkt plan, copied out
 PROBE_SIGNATURES = {
     "padne_test_product": (C.c_int, [_P, _P, C.c_int32, _I64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P,
                                      _P, _P, _P, _P, C.c_double, _P, _PF64, _I64, _PI32]),
+    "padne_test_kkt_state": (C.c_int, [_P, C.c_int32, _P, _I64]),
 }
 
 _lib = None
@@ -713,6 +715,17 @@ class KktPlan:
         m = CsrMatrix(self.ctx, h)
         m._borrowed = True
         return m
+
+    STATE = {"IMAP": (0, np.int32), "SRC_OF": (1, np.int32), "B": (2, np.float64), "Y": (3, np.float64), "C": (4, np.float64),
+             "V": (5, np.float64), "Z": (6, np.float64)}
+
+    def state(self, which: str, n: int) -> np.ndarray:
+        """TEST-ONLY (``padne_test_kkt_state``): the ``n`` elements of the plan's device array ``which`` as they lie there.
+        ValueError when the array has another size or does not exist yet."""
+        sel, dtype = self.STATE[which]
+        out = np.empty(int(n), dtype=dtype)
+        _check(self.ctx._lib.padne_test_kkt_state(self._h, sel, out.ctypes.data_as(_P), out.nbytes))
+        return out
 
     def solve(self, r, known: dict, extras: list, probes, *, rtol=1e-12, max_iter=200000, precond="amg",
               abs_residual_target=0.0, rebuild=False):

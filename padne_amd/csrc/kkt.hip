@@ -1529,3 +1529,34 @@ extern "C" int padne_kkt_goal_error(padne_ctx *ctx, padne_kkt *k, int32_t n_cols
     }
     return PADNE_OK;
 }
+
+// ---- test entry: one device array of the plan, as it lies there (include/padne_hip_probe.h) ----------------------------
+extern "C" int padne_test_kkt_state(const padne_kkt *k, int32_t which, void *out_host, int64_t n_bytes) {
+    PADNE_REQUIRE(k && k->ctx, "null argument");
+    const bool ran = k->solved || k->finished;            // a stage 1 has completed: its columns are the plan's
+    const long long N = k->N, nf = k->n_free, width = kkt_block_width(k->n_cols), n_rhs = k->n_cols + k->n_extra;
+    const void *src = nullptr;
+    long long bytes = 0;
+    switch (which) {
+    case PADNE_TEST_KKT_IMAP: src = k->imap; bytes = (long long)sizeof(int32_t) * N; break;
+    case PADNE_TEST_KKT_SRC_OF: src = k->src_of; bytes = (long long)sizeof(int32_t) * nf; break;
+    case PADNE_TEST_KKT_B: src = ran ? k->b : nullptr; bytes = (long long)sizeof(double) * n_rhs * nf; break;
+    case PADNE_TEST_KKT_Y: src = ran ? k->y : nullptr; bytes = (long long)sizeof(double) * n_rhs * nf; break;
+    case PADNE_TEST_KKT_C:
+        // (stage 2 writes the caller's layout into c when it differs from the products' one: kkt_finish_block, same_layout)
+        src = ran && k->has_c && !(k->finished && !(width == k->n_cols && k->n_cols <= 8)) ? k->c : nullptr;
+        bytes = (long long)sizeof(double) * N * width;
+        break;
+    case PADNE_TEST_KKT_V: src = ran ? k->v : nullptr; bytes = (long long)sizeof(double) * N * width; break;
+    case PADNE_TEST_KKT_Z: src = ran ? k->Z : nullptr; bytes = (long long)sizeof(double) * k->n_extra * N; break;
+    default: break;
+    }
+    if (which == PADNE_TEST_KKT_Z && ran && k->n_extra == 0) src = k->v;      // (an empty array: any address serves)
+    PADNE_REQUIRE(which >= PADNE_TEST_KKT_IMAP && which <= PADNE_TEST_KKT_Z, "unknown array");
+    PADNE_REQUIRE(src != nullptr, "the plan does not hold this array (yet)");
+    PADNE_REQUIRE(n_bytes == bytes && (bytes == 0 || out_host != nullptr), "byte count of the array");
+    PADNE_HIP_CHECK(hipSetDevice(k->ctx->device));
+    PADNE_HIP_CHECK(hipStreamSynchronize(k->ctx->stream));
+    if (bytes > 0) PADNE_HIP_CHECK(hipMemcpy(out_host, src, (size_t)bytes, hipMemcpyDeviceToHost));
+    return PADNE_OK;
+}
