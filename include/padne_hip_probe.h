@@ -1,7 +1,8 @@
 /* padne_hip_probe.h -- TEST-ONLY probes of libpadne_hip.so.  Neither the drop-in boundary (include/padne_hip.h) nor the
- * multi-rank scaffolding (include/padne_hip_test.h): two entries.  padne_test_product drives a single product launcher of the
+ * multi-rank scaffolding (include/padne_hip_test.h): three entries.  padne_test_product drives a single product launcher of the
  * solver on inputs a test chooses, so that every SpMV / SpMM kernel form and epilogue can be held against a host reference;
- * padne_test_kkt_state copies one device array of a padne_kkt plan out, so that every stage of the plan can.  Bound by
+ * padne_test_kkt_state copies one device array of a padne_kkt plan out, so that every stage of the plan can;
+ * padne_test_amg_state copies out what a level of the multigrid hierarchy decided in its setup.  Bound by
  * padne_amd/_hip.py (PROBE_SIGNATURES). */
 #ifndef PADNE_HIP_PROBE_H
 #define PADNE_HIP_PROBE_H
@@ -74,6 +75,19 @@ int padne_test_product(padne_ctx *ctx, padne_csr *m, int32_t flags, int64_t n_ow
 enum { PADNE_TEST_KKT_IMAP = 0, PADNE_TEST_KKT_SRC_OF = 1, PADNE_TEST_KKT_B = 2, PADNE_TEST_KKT_Y = 3, PADNE_TEST_KKT_C = 4,
        PADNE_TEST_KKT_V = 5, PADNE_TEST_KKT_Z = 6 };
 int padne_test_kkt_state(const padne_kkt *plan, int32_t which, void *out_host, int64_t n_bytes);
+
+/* What level `level` of the multigrid hierarchy of `m` decided in its setup, copied to out_host
+ * (tests/test_amg_vs_reference.py).  Read-only: the entry waits for the context's stream, copies, and changes nothing; it
+ * does not build a hierarchy that is not there.
+ *   AGG      int32[n_l]   aggregate (column of P_l) of every vertex of the level
+ *   ROOT     int8[n_l]    1 where the independent-set rounds made the vertex a root
+ *   SCALARS  double[4]    lambda (the bound of D^-1 A the smoother uses), jac (its damping), 1.0 if the level has a fused
+ *                         up-leg operator W, 1.0 if the cycle runs in single precision
+ * AGG and ROOT exist only on levels that were coarsened by a setup that ran under PADNE_AMG_KEEP=1 (the switch makes the
+ * setup copy them out of its scratch; without it nothing is kept).  PADNE_E_INVALID when n_bytes is not the size of the
+ * array, the array was not kept, the level does not exist, or the hierarchy is a row-partitioned one. */
+enum { PADNE_TEST_AMG_AGG = 0, PADNE_TEST_AMG_ROOT = 1, PADNE_TEST_AMG_SCALARS = 2 };
+int padne_test_amg_state(padne_ctx *ctx, const padne_csr *m, int32_t level, int32_t which, void *out_host, int64_t n_bytes);
 
 #ifdef __cplusplus
 }

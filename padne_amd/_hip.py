@@ -164,11 +164,12 @@ TEST_SIGNATURES = {
 }
 
 # the test probes (include/padne_hip_probe.h): one product launcher of the solver, run once on a test's inputs; one device
-# array of a padne_kkt plan, copied out
+# array of a padne_kkt plan, copied out; what a multigrid level decided in its setup, copied out
 PROBE_SIGNATURES = {
     "padne_test_product": (C.c_int, [_P, _P, C.c_int32, _I64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P,
                                      _P, _P, _P, _P, C.c_double, _P, _PF64, _I64, _PI32]),
     "padne_test_kkt_state": (C.c_int, [_P, C.c_int32, _P, _I64]),
+    "padne_test_amg_state": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _I64]),
 }
 
 _lib = None
@@ -1248,6 +1249,17 @@ class CsrMatrix:
         a, b = C.c_int64(), C.c_int64()
         _check(self.ctx._lib.padne_csr_split_tiles(self._h, int(level), C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    AMG_STATE = {"AGG": (0, np.int32), "ROOT": (1, np.int8), "SCALARS": (2, np.float64)}
+
+    def amg_state(self, level: int, which: str) -> np.ndarray:
+        """TEST-ONLY (``padne_test_amg_state``): what level ``level`` of the cached hierarchy decided in its setup -- "AGG",
+        "ROOT" (both kept only under PADNE_AMG_KEEP=1) or "SCALARS" = (lambda, jac, has W, single precision)."""
+        sel, dtype = self.AMG_STATE[which]
+        n = 4 if which == "SCALARS" else self.amg_shapes()[int(level)]["A"][0]
+        out = np.empty(n, dtype=dtype)
+        _check(self.ctx._lib.padne_test_amg_state(self.ctx._h, self._h, int(level), sel, out.ctypes.data_as(_P), out.nbytes))
+        return out
 
     def amg_apply(self, r) -> np.ndarray:
         """z = M^-1 r: one multigrid V-cycle (the preconditioner of solve_spd)."""

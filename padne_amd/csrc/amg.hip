@@ -3,22 +3,32 @@
 // counterpart (the reference factorises with SuperLU); it only changes how fast
 // ||b - A x|| <= rtol ||b|| is reached, not what is solved.
 //
-// Setup per level (all deterministic -- priorities are hashes of the index, sums have a fixed order):
-//   strength   j is a strong neighbour of i  <=>  a_ij^2 >= theta^2 a_ii a_jj          (theta = 0.08)
+// Setup per level (all deterministic -- priorities are hashes of the index, sums have a fixed order).  This is the
+// specification tests/amg_ref.py evaluates in extended precision; the two say the same thing.
+//   strength   j is a strong neighbour of i  <=>  a_ij^2 >= theta^2 a_ii a_jj          (theta = 0.08), evaluated as
+//              a_ij a_ij (1/a_ii) (1/a_jj) >= theta^2 with the rounded reciprocals of the diagonal
 //   aggregate  distance-2 maximal independent set of the strength graph (MIS-k rounds on unique 32-bit
-//              priority words, two neighbour-max passes per round) -> roots; every other vertex joins the
-//              aggregate of its strongest aggregated neighbour (two passes); vertices without strong
+//              priority words, two neighbour-max passes per round) -> roots: no two of them within two strong hops,
+//              every vertex with a strong neighbour within two strong hops of one.  Then two join passes: a vertex
+//              without an aggregate joins the aggregate of its strongest aggregated strong neighbour (largest |a_ij|,
+//              ties to the smaller column), the second pass on the result of the first; vertices without strong
 //              neighbours become singletons
 //   prolong    P = (I - omega D_F^-1 A_F) T,  T = piecewise constant, A_F = A with the weak entries lumped into
-//              the diagonal,  omega = 1.5 / lambda,  lambda = Gershgorin bound of D_F^-1 A_F
+//              the diagonal (d^F_i = a_ii + sum of the weak a_ij; a row with d^F_i / a_ii <= 0.05 is not filtered: it
+//              keeps all its entries and d^F_i = a_ii),  omega = 1.5 / min(lambda_F, lambda),  lambda_F and lambda the
+//              Gershgorin bounds max_i sum_j |a_ij| / |a_ii| of D_F^-1 A_F and of D^-1 A
 //   restrict   R = P^T stored explicitly (CSR, placed in column order without a sort) so that restriction is the same SpMV kernel
 //   coarse     A_c = R (A P) by two row-wise sparse products: one thread per row with a short list in LDS for the fine
 //              level's A P, 16 / 32 / 64 lanes per row with a lane mask per column everywhere else, a dense LDS
 //              accumulator for the long rows of the coarse levels; products are always added in generation order
+//   smoother   lambda_0 = the Gershgorin bound of D^-1 A; on the levels below, the smaller of that bound and 1.08 times
+//              the largest Ritz value of 8 Lanczos steps (an estimate from below: the margin keeps c lambda_max < 2)
 // until n <= 2048, where the dense inverse is formed by a blocked Gauss-Jordan on the f64 matrix cores (SPD: no pivoting).
 //
-// Apply: V(1,1) cycle with damped Jacobi (first-degree Chebyshev on [lambda/10, lambda]); every
-// stage is the SpMV kernel of spmv.hip with a different epilogue (residual formed from the right-hand side alone,
+// Apply: V(1,1) cycle with damped Jacobi (first-degree Chebyshev on [lambda/10, lambda]: c = 1 / (0.55 lambda)),
+//   x1 = c D^-1 b,   r1 = b - A x1,   e = cycle of the level below on R r1 (the coarsest: e = A^-1 R r1),
+//   x2 = x1 + P e,   z = x2 + c D^-1 (b - A x2);
+// every stage is the SpMV kernel of spmv.hip with a different epilogue (residual formed from the right-hand side alone,
 // restriction with the first sweep of the level below, coarse correction + post-smoothing in ONE product with
 // W = P - c D^-1 A P), so the fine level costs two and a half matrix passes per CG iteration.  The cycle is a
 // fixed symmetric positive definite linear operator, hence plain PCG applies.  By default it runs in
@@ -59,6 +69,10 @@ struct AmgLevel {
     // last partitioned level, whose coarse level is the gathered one -- every rank holds the whole tail solution, so the
     // neighbours' corrected values there are computed, not exchanged (amg_apply_f32)
     padne_csr *P_halo = nullptr;
+    // PADNE_AMG_KEEP=1 (tests): the aggregate of every vertex and the state the independent-set rounds left (1 = root),
+    // copied out of the setup's scratch; null otherwise
+    int *agg_keep = nullptr;
+    signed char *state_keep = nullptr;
     float *e_ext = nullptr;            // [n_{l+1} | world * m_{l+1}] coarse correction incl. the other ranks' exported aggregates
 };
 
@@ -2402,7 +2416,7 @@ static int gershgorin(padne_ctx *ctx, const padne_csr *A, double *lambda, bool f
 // aggregates of A -> device array agg[n], count n_agg
 static int aggregate(padne_ctx *ctx, Scratch &sc, const padne_csr *A, int **agg_out, int *n_agg, double *lambda_f = nullptr,
                      double *lambda_plain = nullptr, unsigned char **spos_out = nullptr, int **scol_out = nullptr,
-                     float *vals32_out = nullptr) {
+                     float *vals32_out = nullptr, signed char **state_out = nullptr) {
     hipStream_t s = ctx->stream;
     const int n = (int)A->n_rows;
     const double theta2 = kTheta * kTheta;
@@ -2567,6 +2581,7 @@ static int aggregate(padne_ctx *ctx, Scratch &sc, const padne_csr *A, int **agg_
     *n_agg = (int)(n_roots + n_single);
     if (spos_out != nullptr) *spos_out = spos;      // lives in the caller's scratch, like agg
     if (scol_out != nullptr) *scol_out = scol;
+    if (state_out != nullptr) *state_out = state;
     return PADNE_OK;
 }
 
@@ -3418,6 +3433,8 @@ void amg_destroy(void *p) {
         pool_free(amg->ctx, L.xb8);
         pool_free(amg->ctx, L.tmp8);
         pool_free(amg->ctx, L.export_owned);
+        pool_free(amg->ctx, L.agg_keep);
+        pool_free(amg->ctx, L.state_keep);
     }
     pool_free(amg->ctx, amg->coarse_inv);
     pool_free(amg->ctx, amg->coarse_inv32);
@@ -3620,8 +3637,18 @@ int amg_setup(padne_ctx *ctx, padne_csr *A0) {
             if (v32 == nullptr) { rc = PADNE_E_NOMEM; amg->levels.push_back(L); break; }
             Am->vals32 = v32;
         }
-        if ((rc = aggregate(ctx, sc, A, &agg, &n_agg, &lambda_f, &L.lambda, &spos, &scol, v32)) != PADNE_OK) { amg->levels.push_back(L); break; }
+        signed char *mis_state = nullptr;
+        if ((rc = aggregate(ctx, sc, A, &agg, &n_agg, &lambda_f, &L.lambda, &spos, &scol, v32, &mis_state)) != PADNE_OK) { amg->levels.push_back(L); break; }
         pt.lap("aggregate");
+        if (ctx->opt.amg_keep && L.n > 0) {
+            // tests only: the map and the roots outlive the level's scratch (nothing is allocated or queued without the switch)
+            L.agg_keep = (int *)pool_alloc(ctx, sizeof(int) * (size_t)L.n);
+            L.state_keep = (signed char *)pool_alloc(ctx, (size_t)L.n);
+            if (L.agg_keep == nullptr || L.state_keep == nullptr) { rc = PADNE_E_NOMEM; amg->levels.push_back(L); break; }
+            hipError_t he = hipMemcpyAsync(L.agg_keep, agg, sizeof(int) * (size_t)L.n, hipMemcpyDeviceToDevice, ctx->stream);
+            if (he == hipSuccess) he = hipMemcpyAsync(L.state_keep, mis_state, (size_t)L.n, hipMemcpyDeviceToDevice, ctx->stream);
+            if (he != hipSuccess) { set_error("multigrid setup: %s", hipGetErrorString(he)); rc = PADNE_E_HIP; amg->levels.push_back(L); break; }
+        }
         if (n_agg == 0 || (double)n_agg > 0.8 * (double)A->n_rows) {   // coarsening stalled: stop here
             rc = queue_level_extras();
             amg->levels.push_back(L);
@@ -4759,6 +4786,36 @@ void amg_info(const padne_csr *A0, int *levels, double *complexity, double *setu
 }
 
 }  // namespace padne
+
+// ---- test entry: what a level of the hierarchy kept of its setup (include/padne_hip_probe.h) -----------------------------
+extern "C" int padne_test_amg_state(padne_ctx *ctx, const padne_csr *m, int32_t level, int32_t which, void *out_host,
+                                    int64_t n_bytes) {
+    PADNE_REQUIRE(ctx && m, "null argument");
+    const padne::Amg *amg = (const padne::Amg *)m->amg;
+    PADNE_REQUIRE(amg != nullptr && !amg->dist, "no single-GPU multigrid hierarchy on this matrix");
+    PADNE_REQUIRE(level >= 0 && level < (int)amg->levels.size(), "no such multigrid level");
+    PADNE_REQUIRE(which >= PADNE_TEST_AMG_AGG && which <= PADNE_TEST_AMG_SCALARS, "unknown array");
+    const padne::AmgLevel &L = amg->levels[(size_t)level];
+    PADNE_HIP_CHECK(hipSetDevice(ctx->device));
+    PADNE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (which == PADNE_TEST_AMG_SCALARS) {
+        PADNE_REQUIRE(n_bytes == (int64_t)(4 * sizeof(double)) && out_host != nullptr, "byte count of the array");
+        const double h[4] = {L.lambda, L.jac, L.W != nullptr ? 1.0 : 0.0, amg->f32 ? 1.0 : 0.0};
+        memcpy(out_host, h, sizeof(h));
+        return PADNE_OK;
+    }
+    const bool want_agg = which == PADNE_TEST_AMG_AGG;
+    const void *src = want_agg ? (const void *)L.agg_keep : (const void *)L.state_keep;
+    const long long bytes = (long long)(want_agg ? sizeof(int32_t) : sizeof(int8_t)) * L.n;
+    PADNE_REQUIRE(src != nullptr, "the level did not keep this array (PADNE_AMG_KEEP=1 at setup; not the coarsest level)");
+    PADNE_REQUIRE(n_bytes == bytes && out_host != nullptr, "byte count of the array");
+    PADNE_HIP_CHECK(hipMemcpy(out_host, src, (size_t)bytes, hipMemcpyDeviceToHost));
+    if (!want_agg) {                                   // the rounds' state word: 1 = root
+        int8_t *f = (int8_t *)out_host;
+        for (long long i = 0; i < L.n; ++i) f[i] = f[i] == 1 ? 1 : 0;
+    }
+    return PADNE_OK;
+}
 
 extern "C" int padne_csr_split_tiles(const padne_csr *m, int level, int64_t *interior, int64_t *boundary) {
     PADNE_REQUIRE(m && interior && boundary, "null argument");

@@ -28,6 +28,7 @@ void options_from_env(padne_options *o) {
     o->amg_f64 = on("PADNE_AMG_F64");
     if (const char *e = getenv("PADNE_AMG_W")) o->amg_w = strcmp(e, "none") == 0 ? 0 : (strcmp(e, "fine") == 0 ? 1 : 2);
     o->amg_exchange_all = on("PADNE_AMG_EXCHANGE_ALL");
+    o->amg_keep = on("PADNE_AMG_KEEP");
     o->pcg_p64 = on("PADNE_PCG_P64");
     o->pcg_no_xhist = on("PADNE_PCG_NO_XHIST");
     o->gj_vector = on("PADNE_GJ_VECTOR");
