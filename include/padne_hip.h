@@ -575,6 +575,67 @@ int padne_sampler_raster(padne_ctx *ctx, padne_sampler *s, int32_t layer, double
  * of the last query kernel. */
 int padne_sampler_stats(const padne_sampler *s, int32_t layer, int64_t *counts_out, double *seconds_out);
 
+/* ---- thermal: steady-state temperature rise of the copper from Joule heating --------------------
+ * No reference counterpart ("Thermal").  Unknown: theta = T - T_ambient [K] at the first n_potential unknowns of
+ * the assembled electrical system `L` (the vertices of its meshes, then the internal nodes); multiplier rows take no part.
+ *     A theta = b,   A = K_kappa + diag(h_m(v) M_v) + links
+ * K_kappa: the cotangent stiffness of padne_assemble_system over the mesh `L` keeps on the device, with kappa[m] [W/K], the
+ * thermal sheet conductance of mesh m, in the place of its electrical conductance, positive sign.  M_v = the sum over the
+ * faces incident to vertex v, in ascending global face number, of A_f / 3 (A_f = |cross| / 2 as padne_kkt_error_estimate
+ * forms it).  film[m] > 0 [W / (K length^2)]: every loss of mesh m to ambient.  Link e is a thermal conductance link_g[e]
+ * [W/K] between the unknowns link_a[e] and link_b[e], stamped like a resistor (0: no link, nothing stamped).  A's stored
+ * diagonal at a vertex is the one rounded sum (-K_ii) + film M_v; every other entry is K's, negated.
+ * b_v = the sum over the faces incident to v, ascending, of P_f / 3, P_f [W] the Joule power of face f, then the node-heat
+ * triples added in list order.  K and the links annihilate constants: sum_v film M_v theta_v = sum_v b_v.
+ * The handle borrows `L` (which must outlive it) and is destroyed before its context.  PADNE_E_INVALID for a kappa or film
+ * that is not finite and positive, a link conductance that is negative or not finite, a terminal out of range, a system
+ * without a mesh, and an unknown whose row has no diagonal (a vertex without a face of non-zero area, an internal node no
+ * link of positive conductance reaches).  Nothing crosses PCIe but the O(n_mesh + n_link) lists. */
+typedef struct padne_thermal padne_thermal;
+int padne_thermal_create(padne_ctx *ctx, const padne_csr *L, int64_t n_potential, int32_t n_mesh, const double *kappa,
+                         const double *film, int64_t n_link, const int64_t *link_a, const int64_t *link_b, const double *link_g,
+                         padne_thermal **out);
+int padne_thermal_destroy(padne_thermal *th);     /* NULL is accepted */
+/* borrowed handle of A (n_potential x n_potential; do not destroy) */
+int padne_thermal_matrix(const padne_thermal *th, const padne_csr **csr_out);
+/* M_out[n_vert] = M_v */
+int padne_thermal_lumped(padne_ctx *ctx, const padne_thermal *th, double *M_out);
+/* Solve for n_cols (1 .. 4096) heat loads at once.  face_power_host[n_cols][n_tri]: P_f of every column.  Node heat:
+ * n_heat triples (heat_node[e] in [0, n_potential), heat_col[e] in [0, n_cols), heat_val[e] [W], finite), added to b in list
+ * order after the faces' part.  b is formed on the device, 8 columns per launch, by a gather through the vertex -> faces
+ * lists (no floating-point atomics), and all columns go through padne_solve_spd_dev together (opts null: rtol 1e-12, the
+ * multigrid preconditioner; bit 0 of opts.flags is ignored: theta starts from zero, a zero column comes back as exact
+ * zeros).  theta_host[n_cols][n_potential] (may be null: theta stays on the device for padne_thermal_report).
+ * PADNE_E_NOTCONVERGED still keeps and returns the iterate. */
+int padne_thermal_solve(padne_ctx *ctx, padne_thermal *th, int32_t n_cols, const double *face_power_host, int64_t n_heat,
+                        const int64_t *heat_node, const int32_t *heat_col, const double *heat_val, const padne_solve_opts *opts,
+                        double *theta_host, padne_solve_info *info);
+/* The heat load alone, as padne_thermal_solve forms it from the same arguments: b_out[n_cols][n_potential].  Nothing is
+ * solved, and the handle then holds no solve to report on. */
+int padne_thermal_load(padne_ctx *ctx, padne_thermal *th, int32_t n_cols, const double *face_power_host, int64_t n_heat,
+                       const int64_t *heat_node, const int32_t *heat_col, const double *heat_val, double *b_out);
+/* The same with the face powers of every column of the block the last padne_kkt_finish_block left on the device of `plan`
+ * (a plan of the `L` the handle was made from), computed there: P_f = sigma sum_{edges (i,k) of f} w_ik (V_i - V_k)^2 with
+ * the assembly's |cot|/2 weights, the term padne_kkt_current_cases sums into mesh_power_out.  The powers never visit the
+ * host; with the same triples theta has the bits of padne_thermal_solve fed with padne_thermal_face_power's result.
+ * Preconditions and errors as padne_kkt_power_density_block. */
+int padne_thermal_solve_kkt(padne_ctx *ctx, padne_thermal *th, padne_kkt *plan, int32_t n_cols, int64_t n_heat,
+                            const int64_t *heat_node, const int32_t *heat_col, const double *heat_val,
+                            const padne_solve_opts *opts, double *theta_host, padne_solve_info *info);
+/* out_host[n_cols][n_tri]: the face powers of the last solve, as the handle holds them */
+int padne_thermal_face_power(padne_ctx *ctx, const padne_thermal *th, int32_t n_cols, double *out_host);
+/* Report on the theta of the last solve (n_cols its columns; n_tri, n_vert, n_mesh the mesh's).  Per column c:
+ * face_mean_out[n_cols][n_tri] = ((theta_1 + theta_2) + theta_3) / 3 with the corners in the order of
+ * padne_csr_power_density (may be null); per mesh m, mesh_max_out[c][m] = the largest theta of its vertices and
+ * mesh_vertex_out[c][m] that vertex (global index, the lowest on a tie; -infinity and -1 for a mesh without vertices),
+ * mesh_heat_out[c][m] = the sum of P_f over its faces and mesh_loss_out[c][m] = the sum of (film M_v) theta_v over its
+ * vertices.  env_out[n_vert] = max_c theta_c per vertex and env_case_out[n_vert] the lowest column that attains it, visited
+ * from column 0 and replaced on strictly greater only (both may be null: no envelope).  Sums of 256 items go down each wave
+ * by halving strides and join as (0 + 1) + (2 + 3), tiles are summed per mesh in a fixed order: two calls give the same bits. */
+int padne_thermal_report(padne_ctx *ctx, padne_thermal *th, int32_t n_cols, int64_t n_tri, int64_t n_vert, int32_t n_mesh,
+                         double *face_mean_out, double *mesh_max_out, int64_t *mesh_vertex_out, double *mesh_heat_out,
+                         double *mesh_loss_out, double *env_out, int32_t *env_case_out);
+
 /* ---- introspection for benchmarks ---------------------------------------------------------- */
 /* algorithmic bytes of one CSR SpMV: 12*nnz + 20*n_rows + 4   */
 int64_t padne_spmv_algorithmic_bytes(const padne_csr *m);

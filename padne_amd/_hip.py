@@ -146,6 +146,17 @@ SIGNATURES = {
     "padne_sampler_raster": (C.c_int, [_P, _P, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, _I64, _I64, _PI32,
                                        _PF64, _PF64, _PF64]),
     "padne_sampler_stats": (C.c_int, [_P, C.c_int32, _PI64, _PF64]),
+    "padne_thermal_create": (C.c_int, [_P, _P, _I64, C.c_int32, _PF64, _PF64, _I64, _PI64, _PI64, _PF64, C.POINTER(_P)]),
+    "padne_thermal_destroy": (C.c_int, [_P]),
+    "padne_thermal_matrix": (C.c_int, [_P, C.POINTER(_P)]),
+    "padne_thermal_lumped": (C.c_int, [_P, _P, _PF64]),
+    "padne_thermal_solve": (C.c_int, [_P, _P, C.c_int32, _PF64, _I64, _PI64, _PI32, _PF64, C.POINTER(SolveOpts), _PF64,
+                                      C.POINTER(SolveInfo)]),
+    "padne_thermal_load": (C.c_int, [_P, _P, C.c_int32, _PF64, _I64, _PI64, _PI32, _PF64, _PF64]),
+    "padne_thermal_solve_kkt": (C.c_int, [_P, _P, _P, C.c_int32, _I64, _PI64, _PI32, _PF64, C.POINTER(SolveOpts), _PF64,
+                                          C.POINTER(SolveInfo)]),
+    "padne_thermal_face_power": (C.c_int, [_P, _P, C.c_int32, _PF64]),
+    "padne_thermal_report": (C.c_int, [_P, _P, C.c_int32, _I64, _I64, C.c_int32, _PF64, _PF64, _PI64, _PF64, _PF64, _PF64, _PI32]),
     "padne_spmv_algorithmic_bytes": (_I64, [_P]),
     "padne_spmv_time": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _PF64]),
 }
@@ -984,6 +995,128 @@ class KktPlan:
         _check(self.ctx._lib.padne_kkt_finish_block(self.ctx._h, self._h, k, coeff.shape[1], _ptr(coeff, _PF64), midx.shape[0],
                                                     _ptr(midx, _PI64), _ptr(mval, _PF64), _ptr(V, _PF64), _ptr(norms, _PF64)))
         return V, norms
+
+
+class Thermal:
+    """``padne_thermal``: the thermal sheet problem A theta = b on the meshes an assembled system ``L`` keeps on the device
+    (include/padne_hip.h, "thermal").  ``kappa`` and ``film`` per mesh, ``links`` an (n, 2) array of unknowns with
+    ``link_g`` (n,) W/K.  Holds A with its hierarchy, the lumped areas and, after a solve, the face powers and theta."""
+
+    def __init__(self, L: "CsrMatrix", n_potential: int, kappa, film, link_a=(), link_b=(), link_g=()):
+        self.ctx, self.L = L.ctx, L
+        kap, flm = _f64(kappa).reshape(-1), _f64(film).reshape(-1)
+        la, lb, lg = _i64(link_a).reshape(-1), _i64(link_b).reshape(-1), _f64(link_g).reshape(-1)
+        if kap.shape != flm.shape:
+            raise ValueError("one kappa and one film per mesh")
+        if not (la.shape == lb.shape == lg.shape):
+            raise ValueError("link_a, link_b and link_g must list the same links")
+        h = _P()
+        _check(self.ctx._lib.padne_thermal_create(self.ctx._h, L._h, int(n_potential), kap.shape[0], _ptr(kap, _PF64),
+                                                  _ptr(flm, _PF64), la.shape[0], _ptr(la, _PI64), _ptr(lb, _PI64), _ptr(lg, _PF64),
+                                                  C.byref(h)))
+        self._h = h
+        self.n_potential, self.n_mesh = int(n_potential), kap.shape[0]
+
+    def close(self):
+        if getattr(self, "_h", None) and self.ctx._h:
+            self.ctx._lib.padne_thermal_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def matrix(self) -> "CsrMatrix":
+        """Borrowed view of A (valid while the handle lives)."""
+        h = _P()
+        _check(self.ctx._lib.padne_thermal_matrix(self._h, C.byref(h)))
+        m = CsrMatrix(self.ctx, h)
+        m._borrowed = True
+        return m
+
+    def lumped(self, n_vert: int) -> np.ndarray:
+        """M_v (n_vert,)."""
+        out = np.empty(int(n_vert), dtype=np.float64)
+        _check(self.ctx._lib.padne_thermal_lumped(self.ctx._h, self._h, _ptr(out, _PF64)))
+        return out
+
+    @staticmethod
+    def _heat(heat):
+        node, col, val = heat if heat is not None else ((), (), ())
+        node, col, val = _i64(node).reshape(-1), _i32(col).reshape(-1), _f64(val).reshape(-1)
+        if not (node.shape == col.shape == val.shape):
+            raise ValueError("the node-heat triples must have equal lengths")
+        return node, col, val
+
+    def _solve(self, call, n_cols, heat, rtol, max_iter, precond, download):
+        node, col, val = self._heat(heat)
+        opts = CsrMatrix._opts(rtol, 0.0, max_iter, 0, False, precond=precond)
+        info = SolveInfo()
+        theta = np.empty((n_cols, self.n_potential), dtype=np.float64) if download else None
+        rc = call(node.shape[0], _ptr(node, _PI64), _ptr(col, _PI32), _ptr(val, _PF64), C.byref(opts),
+                  None if theta is None else _ptr(theta, _PF64), C.byref(info))
+        if rc != OK and rc != E_NOTCONVERGED:
+            _check(rc)
+        res = SolveResult(None, info.iterations, info.restarts, info.rel_residual, info.abs_residual, info.solve_seconds,
+                          info.status, info.spmv_seconds, info.precond_setup_seconds, info.operator_complexity, info.levels,
+                          info.precond_fallbacks)
+        return theta, res
+
+    def load(self, face_power, heat=None) -> np.ndarray:
+        """The heat load b (n_cols, n_potential) as ``solve`` forms it from the same arguments; nothing is solved."""
+        P = _f64(face_power)
+        if P.ndim != 2 or P.shape[0] < 1:
+            raise ValueError("face_power must have shape (n_cols, n_tri) with n_cols >= 1")
+        node, col, val = self._heat(heat)
+        out = np.empty((P.shape[0], self.n_potential), dtype=np.float64)
+        _check(self.ctx._lib.padne_thermal_load(self.ctx._h, self._h, P.shape[0], _ptr(P, _PF64), node.shape[0], _ptr(node, _PI64),
+                                                _ptr(col, _PI32), _ptr(val, _PF64), _ptr(out, _PF64)))
+        return out
+
+    def solve(self, face_power, heat=None, *, rtol=1e-12, max_iter=200000, precond="amg", download=True):
+        """theta (n_cols, n_potential) for the face powers ``face_power`` (n_cols, n_tri) [W] and the node-heat triples
+        ``heat`` = (node, column, watts), and the SolveResult of the block solve.  Without ``download`` theta stays on the
+        device for ``report`` and None is returned in its place."""
+        P = _f64(face_power)
+        if P.ndim != 2 or P.shape[0] < 1:
+            raise ValueError("face_power must have shape (n_cols, n_tri) with n_cols >= 1")
+        lib = self.ctx._lib
+        return self._solve(lambda *a: lib.padne_thermal_solve(self.ctx._h, self._h, P.shape[0], _ptr(P, _PF64), *a), P.shape[0],
+                           heat, rtol, max_iter, precond, download)
+
+    def solve_kkt(self, plan: "KktPlan", n_cols: int, heat=None, *, rtol=1e-12, max_iter=200000, precond="amg", download=True):
+        """``solve`` with the face powers of every column of the block ``plan``'s last ``finish_block`` left on the device,
+        computed there (the |cot|/2 weights' form that ``current_cases`` sums per mesh)."""
+        lib, n_cols = self.ctx._lib, int(n_cols)
+        if n_cols < 1:
+            raise ValueError("a block has at least one column")
+        return self._solve(lambda *a: lib.padne_thermal_solve_kkt(self.ctx._h, self._h, plan._h, n_cols, *a), n_cols, heat, rtol,
+                           max_iter, precond, download)
+
+    def face_power(self, n_cols: int, n_tri: int) -> np.ndarray:
+        """The face powers (n_cols, n_tri) of the last solve, as the handle holds them."""
+        out = np.empty((int(n_cols), int(n_tri)), dtype=np.float64)
+        _check(self.ctx._lib.padne_thermal_face_power(self.ctx._h, self._h, int(n_cols), _ptr(out, _PF64)))
+        return out
+
+    def report(self, n_cols: int, n_tri: int, n_vert: int, fields: bool = True, envelope: bool = True):
+        """On the theta of the last solve: (face means (n_cols, n_tri) or None without ``fields``; per column and mesh the
+        largest theta (n_cols, n_mesh), its vertex as a global index (-1 for a mesh without vertices), the heat put in and the
+        film loss; max over the columns per vertex (n_vert,) and the lowest column that attains it (n_vert,) int32, both None
+        without ``envelope``) (include/padne_hip.h)."""
+        n_cols, n_tri, n_vert, n_mesh = int(n_cols), int(n_tri), int(n_vert), self.n_mesh
+        mean = np.empty((n_cols, n_tri), dtype=np.float64) if fields else None
+        mesh_max, heat, loss = (np.empty((n_cols, n_mesh), dtype=np.float64) for _ in range(3))
+        vert = np.empty((n_cols, n_mesh), dtype=np.int64)
+        env = np.empty(n_vert, dtype=np.float64) if envelope else None
+        env_case = np.empty(n_vert, dtype=np.int32) if envelope else None
+        _check(self.ctx._lib.padne_thermal_report(
+            self.ctx._h, self._h, n_cols, n_tri, n_vert, n_mesh, None if mean is None else _ptr(mean, _PF64), _ptr(mesh_max, _PF64),
+            _ptr(vert, _PI64), _ptr(heat, _PF64), _ptr(loss, _PF64), None if env is None else _ptr(env, _PF64),
+            None if env_case is None else _ptr(env_case, _PI32)))
+        return mean, mesh_max, vert, heat, loss, env, env_case
 
 
 class Sampler:

@@ -51,6 +51,14 @@ __device__ __forceinline__ double face_power_of(double gx, double gy, double s) 
     return jx * gx + jy * gy;                   // J.dot(E)
 }
 
+// The power of a face in the weights' form, sigma sum_{edges (i,k)} w_ik (f_i - f_k)^2 with w_ik = cot_half of the corner
+// opposite the edge: what the assembly's rows dissipate, so the faces' sum balances the elements' powers (Tellegen).  Shared
+// by the per-mesh power of current_cases_face_kernel (fields.hip) and the heat load of thermal.hip: both round alike
+__device__ __forceinline__ double face_edge_power(double s, double w12, double w23, double w31, double f1, double f2, double f3) {
+    const double d12 = f1 - f2, d23 = f2 - f3, d31 = f3 - f1;
+    return s * ((w12 * d12 * d12 + w23 * d23 * d23) + w31 * d31 * d31);
+}
+
 // orient(a, b, p) > 0: p lies left of a -> b.  Evaluated exactly so (the library builds with -ffp-contract=off), which
 // lets a numpy restatement reproduce every decision of the cut rule and of the sampler's owner rule
 __device__ __forceinline__ double orient(double ax, double ay, double bx, double by, double px, double py) {

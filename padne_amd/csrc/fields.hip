@@ -357,10 +357,7 @@ __global__ __launch_bounds__(256) void current_cases_face_kernel(
                     e = a;
                     ec = j0 + q;
                 }
-                if (power) {
-                    const double d12 = f1[q] - f2[q], d23 = f2[q] - f3[q], d31 = f3[q] - f1[q];
-                    pw = s * ((w12 * d12 * d12 + w23 * d23 * d23) + w31 * d31 * d31);
-                }
+                if (power) pw = face_edge_power(s, w12, w23, w31, f1[q], f2[q], f3[q]);
             }
             for (int off = 32; off > 0; off >>= 1) {
                 hotspot_merge(a, f, __shfl_down(a, off, 64), __shfl_down(f, off, 64));

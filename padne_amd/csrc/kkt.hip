@@ -1126,6 +1126,19 @@ static int require_finished_block(const char *entry, padne_ctx *ctx, const padne
     return PADNE_OK;
 }
 
+// The finished block of a plan for a consumer in another translation unit (thermal.hip): after the same checks, the V that
+// stage 2 left on the device ([N][n_cols] row-major), N and the system the plan was made for.
+namespace padne {
+int kkt_finished_block(const char *entry, padne_ctx *ctx, const padne_kkt *k, int32_t n_cols, const double **V_out, long long *N_out,
+                       const padne_csr **L_out) {
+    PADNE_TRY(require_finished_block(entry, ctx, k, n_cols));
+    *V_out = k->v_final;
+    *N_out = k->N;
+    *L_out = k->L;
+    return PADNE_OK;
+}
+}  // namespace padne
+
 // The flag a face kernel sets when a triangle names a vertex outside its mesh: a zeroed device int from `sc` ...
 static int bad_flag_alloc(Scratch &sc, hipStream_t s, int **d_bad) {
     PADNE_TRY(sc.alloc(d_bad, 1));

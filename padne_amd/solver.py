@@ -28,6 +28,8 @@ compute_power_density :728-745         ``power_density_kernel``
                                        (``error_recover_kernel``) and ``error_indicator_kernel`` over the faces
 (a finer mesh where that asks)         ``refine_meshes`` / ``solve_adaptive``: longest-edge refinement with conforming
                                        closure, edges by a sort of corner keys, ``refine_emit_kernel`` over the faces
+(how hot that makes the copper)        ``solve_thermal``: the load-case block, then ``thermal_face_power_kernel``, the gather
+                                       ``thermal_load_kernel`` and one more block solve on the thermal sheet operator
 read-out under the cursor ui.py:192    ``FieldSampler``: owner face by ``sample_kernel`` over a grid of bins per layer,
                                        V interpolated in the face, J and p of the face
 =====================================  ====================================================
@@ -1833,6 +1835,361 @@ def solve_load_case_currents(prob, cases, cuts=(), mesher_config: Optional[mesh.
     meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
     return solve_meshed_load_case_currents(prob, meshes, mesh_index_to_layer_index, cases,
                                            [Cut(prob.layers[i], a, b) for i, a, b in cuts], per_case_fields=per_case_fields)
+
+
+# --------------------------------------------------------------------------------------------
+# thermal: the steady-state temperature of the copper from its Joule heating (DESIGN.md "Thermal")
+# --------------------------------------------------------------------------------------------
+
+LORENZ_NUMBER = 2.44e-8                 # L0 [W Ohm / K^2] of Wiedemann-Franz: kappa = L0 T sigma for a metal
+
+
+@dataclass
+class ThermalModel:
+    """What turns dissipated power into a temperature (see :func:`solve_meshed_thermal`).
+
+    - ``film``: the film coefficient h [W / (K mesh-unit^2)] that lumps every loss from the sheet to ambient, one float for
+      all layers or a mapping {layer or layer name: float} that names every layer.  Required: there is no sensible
+      default.  With meshes in mm, 10 W/(m^2 K) is 1e-5.
+    - ``ambient``: the ambient temperature, in the unit the temperatures are reported in.
+    - ``sheet_conductance``: None, or a mapping {layer or name: kappa [W/K]}, the thermal conductance of a square of the
+      sheet.  A layer that is not named gets Wiedemann-Franz, kappa = L0 T_ref layer.conductance.
+    - ``link_conductance``: None, or a mapping {Resistor: g [W/K]}, the thermal conductance between the resistor's
+      terminals; 0 is no link.  A resistor that is not named gets g = L0 T_ref / R.  Sources and regulators are no
+      thermal path.
+    - ``element_heat``: half of every resistor's dissipation is put into each of its terminals.
+    - ``reference_temperature``: T_ref [K] of the Wiedemann-Franz defaults."""
+    film: object
+    ambient: float = 25.0
+    sheet_conductance: Optional[Mapping] = None
+    link_conductance: Optional[Mapping] = None
+    element_heat: bool = True
+    reference_temperature: float = 293.15
+
+
+@dataclass
+class CheckedThermalModel:
+    """A :class:`ThermalModel` resolved against a Problem (:func:`check_thermal_model`)."""
+    film: list                 # per layer
+    kappa: list                # per layer
+    links: dict                # Resistor of the solved networks -> g [W/K]
+    ambient: float
+    element_heat: bool
+
+
+@dataclass
+class ThermalReport:
+    """The temperatures of one load case (see :func:`solve_meshed_thermal`)."""
+    temperatures: Optional[list]        # per layer, per mesh: ZeroForm of T = theta + ambient at the vertices
+    face_temperatures: Optional[list]   # per layer, per mesh: TwoForm of the mean T of each face's corners
+    disconnected_temperatures: list     # per layer, per disconnected mesh: ZeroForm filled with the ambient temperature
+    hotspots: list                      # per layer: (T, mesh index within the layer, vertex index, x, y), None without vertices
+    layers: list                        # per layer: {"heat": the Joule heat put into its copper [W], "loss": its film loss [W]}
+    elements: dict                      # Resistor -> {"heat": dissipation deposited at its terminals [W], "flow": heat a -> b through its link [W]}
+    total_heat: float                   # copper and elements
+    total_loss: float                   # what the films carry to ambient: equals total_heat up to the solve's tolerance
+    info: dict                          # {"iterations", "rel_residual", "seconds"} of the thermal block solve
+
+
+@dataclass
+class ThermalEnvelope:
+    """The worst case over the load cases of one block (the sequential rule of :func:`envelope_of`)."""
+    temperatures: list    # per layer, per mesh: ZeroForm of max_j T_j per vertex
+    cases: list           # per layer, per mesh: (n_vertices,) int32, the lowest case of that maximum
+    hotspots: list        # per layer: (T, case, mesh index within the layer, vertex index, x, y), None without vertices
+
+
+_TERMINAL_FIELDS = {"Resistor": ("a", "b"), "CurrentSource": ("f", "t"), "VoltageSource": ("p", "n"),
+                    "VoltageRegulator": ("v_p", "v_n", "s_f", "s_t")}
+
+
+def _positive_number(value, what: str, allow_zero: bool = False) -> float:
+    try:
+        x = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} must be a number, not {value!r}") from None
+    if not math.isfinite(x) or x < 0.0 or (x == 0.0 and not allow_zero):
+        raise ValueError(f"{what} must be finite and {'not negative' if allow_zero else 'positive'}, not {value!r}")
+    return x
+
+
+def _per_layer(prob, mapping, what: str) -> dict:
+    """{layer index: value} of a mapping {layer or layer name: value}; ValueError for a key that is no layer of ``prob``."""
+    out = {}
+    for key, value in mapping.items():
+        if isinstance(key, str):
+            found = [i for i, layer in enumerate(prob.layers) if layer.name == key]
+        else:
+            found = [i for i, layer in enumerate(prob.layers) if layer is key or layer == key]
+        if not found:
+            raise ValueError(f"{what}: {key!r} is no layer of the Problem")
+        for i in found:
+            out[i] = _positive_number(value, f"{what} of layer {prob.layers[i].name!r}")
+    return out
+
+
+def check_thermal_model(prob, model, filtered_networks=None) -> CheckedThermalModel:
+    """``model`` resolved against ``prob``, or ValueError -- before anything reaches the device -- for: a film that is
+    missing for a layer; a film, sheet conductance or reference temperature that is not finite and positive; a link
+    conductance that is negative or not finite (0 is allowed: no link); a mapping key that is no layer, or no Resistor, of
+    the Problem; an ambient temperature that is not finite; and an internal node (a terminal without a connection to
+    copper) that reaches no copper through links of positive conductance -- its temperature would be undetermined.  That
+    last check walks a small graph over the lumped elements only, and the error names an element at the node."""
+    if not isinstance(model, ThermalModel):
+        raise ValueError("model must be a ThermalModel")
+    networks = list(prob.networks) if filtered_networks is None else list(filtered_networks)
+    t_ref = _positive_number(model.reference_temperature, "the reference temperature")
+    try:
+        ambient = float(model.ambient)
+    except (TypeError, ValueError):
+        raise ValueError(f"the ambient temperature must be a number, not {model.ambient!r}") from None
+    if not math.isfinite(ambient):
+        raise ValueError(f"the ambient temperature must be finite, not {model.ambient!r}")
+    n_layers = len(prob.layers)
+    if model.film is None:
+        raise ValueError("the film coefficient is required: a float, or a mapping {layer: float}")
+    if isinstance(model.film, Mapping):
+        given = _per_layer(prob, model.film, "film")
+        for i, layer in enumerate(prob.layers):
+            if i not in given:
+                raise ValueError(f"layer {layer.name!r} has no film coefficient")
+        film = [given[i] for i in range(n_layers)]
+    else:
+        film = [_positive_number(model.film, "the film coefficient")] * n_layers
+    given = {} if model.sheet_conductance is None else _per_layer(prob, model.sheet_conductance, "sheet_conductance")
+    kappa = []
+    for i, layer in enumerate(prob.layers):
+        kappa.append(given[i] if i in given else
+                     _positive_number(LORENZ_NUMBER * t_ref * float(layer.conductance),
+                                      f"the Wiedemann-Franz sheet conductance of layer {layer.name!r}"))
+    all_elements = [element for network in prob.networks for element in network.elements]
+    overrides = {}
+    if model.link_conductance is not None:
+        if not isinstance(model.link_conductance, Mapping):
+            raise ValueError("link_conductance must be a mapping {Resistor: W/K}")
+        for key, value in model.link_conductance.items():
+            if not any(element is key or element == key for element in all_elements):
+                raise ValueError(f"link_conductance: {key!r} is no element of the Problem")
+            if element_kind(key) != "Resistor":
+                raise ValueError(f"link_conductance: a {type(key).__name__} is no thermal path, only resistors are")
+            overrides[key] = _positive_number(value, "the link conductance of a Resistor", allow_zero=True)
+    links = {}
+    for network in networks:
+        for element in network.elements:
+            if element_kind(element) == "Resistor":
+                links[element] = overrides[element] if element in overrides else \
+                    _positive_number(LORENZ_NUMBER * t_ref / float(element.resistance), "the Wiedemann-Franz link conductance")
+    # every internal node must reach copper through links of positive conductance
+    on_copper = {conn.node_id for network in networks for conn in network.connections}
+    neighbours: dict = {}
+    at_node: dict = {}
+    for network in networks:
+        for element in network.elements:
+            kind = element_kind(element)
+            if kind is None:
+                raise NotImplementedError(f"Unsupported node type {element}")
+            nodes = [getattr(element, name) for name in _TERMINAL_FIELDS[kind]]
+            for node in nodes:
+                at_node.setdefault(node, element)
+                neighbours.setdefault(node, [])
+            if kind == "Resistor" and links[element] > 0.0:
+                neighbours[nodes[0]].append(nodes[1])
+                neighbours[nodes[1]].append(nodes[0])
+    reached = {node for node in neighbours if node in on_copper}
+    stack = list(reached)
+    while stack:
+        for other in neighbours[stack.pop()]:
+            if other not in reached:
+                reached.add(other)
+                stack.append(other)
+    for node, element in at_node.items():
+        if node not in reached:
+            raise ValueError(f"an internal node of {element!r} reaches no copper through a thermal link of positive conductance: "
+                             "its temperature is undetermined (give a resistor at the node a link_conductance above 0)")
+    return CheckedThermalModel(film=film, kappa=kappa, links=links, ambient=ambient, element_heat=bool(model.element_heat))
+
+
+def _refuse_bare_vertices(board: IndexedBoard) -> None:
+    """ValueError for a vertex of a connected mesh that no face names: the thermal system has no equation for it."""
+    for mesh_i, msh in enumerate(board.meshes):
+        used = np.bincount(np.asarray(msh.triangles, dtype=np.int64).reshape(-1), minlength=len(msh.points))
+        if len(msh.points) and (used[:len(msh.points)] == 0).any():
+            raise ValueError(f"mesh {mesh_i} has a vertex without a face ({int(np.flatnonzero(used == 0)[0])}): the thermal "
+                             "model has no equation for it")
+
+
+def thermal_heat_triples(pairs, flows_by_case) -> tuple:
+    """The node-heat triples (unknown, case, watts) that put half of every resistor's dissipation into each of its
+    terminals, case by case in element order, terminal a before terminal b."""
+    node, col, val = [], [], []
+    for j, flows in enumerate(flows_by_case):
+        for (_, row), flow in zip(pairs, flows):
+            if row[0] == "R":
+                half = flow["power"] / 2
+                node += [row[1], row[2]]
+                col += [j, j]
+                val += [half, half]
+    return np.asarray(node, dtype=np.int64), np.asarray(col, dtype=np.int32), np.asarray(val, dtype=DTYPE)
+
+
+def _solve_block_thermal(prob, meshes, mesh_index_to_layer_index, checked: CheckedThermalModel, cases, fields: bool,
+                         filtered_networks, disconnected_meshes_by_layer, laps: _Laps):
+    """The checked ``cases`` of ``prob`` as one electrical block and one thermal block on top of it, for the checked model:
+    ([Solution], [ThermalReport], ThermalEnvelope).  ``fields``: with the per-case temperatures of vertices and faces."""
+    substituted = [substitute_load_case(prob, case) for case in cases]
+    k, n_layers = len(cases), len(prob.layers)
+    board = index_board(prob, meshes, mesh_index_to_layer_index, filtered_networks, disconnected_meshes_by_layer)
+    _refuse_bare_vertices(board)
+    n_vert = len(board.vindex)
+    if n_vert == 0 or not int(board.tri_offsets[-1]):
+        raise ValueError("the thermal model needs connected copper: the board has no connected mesh with faces")
+    pairs = global_elements(board.filtered_networks, board.node_indexer)
+    laps.lap("indexing")
+    layer_of = board.layer_of
+    with board.assembled() as (L, _):
+        rows, cols, vals = stamp_load_cases(board.filtered_networks, board.node_indexer, L.shape[0], cases)
+        laps.lap("assembly")
+        log.info(f"Solving {k} load case(s) as one block, with their temperatures")
+        plan, V, residual_norms, res, n_tri, _n_mesh = _solve_block_on_device(L, rows, cols, vals, k, k, laps)
+        power = plan.power_density_block(k, n_tri)
+        local, Vu = _gather_element_rows([row for _, row in pairs], V, _ROW_UNKNOWNS)
+        flows_by_case = [element_flows(_case_element_rows(pairs, local, case), Vu[:, j]) for j, case in enumerate(cases)]
+        laps.lap("power_density")
+        resistors = [(element, row) for element, row in pairs if row[0] == "R"]
+        n_potential = L.layout.n_potential
+        thermal = _hip.Thermal(L.dev, n_potential, [checked.kappa[layer_of[i]] for i in range(len(board.meshes))],
+                               [checked.film[layer_of[i]] for i in range(len(board.meshes))],
+                               [row[1] for _, row in resistors], [row[2] for _, row in resistors],
+                               [checked.links[element] for element, _ in resistors])
+        try:
+            laps.lap("thermal_setup")
+            heat = thermal_heat_triples(pairs, flows_by_case) if checked.element_heat else None
+            theta, tres = thermal.solve_kkt(plan, k, heat, rtol=RTOL, max_iter=MAX_ITER)
+            laps.lap("thermal_solve")
+            mean, mesh_max, mesh_vert, mesh_heat, mesh_loss, env, env_case = thermal.report(k, n_tri, n_vert, fields=fields)
+            laps.lap("thermal_report")
+        finally:
+            thermal.close()
+    laps.lap()
+    _warn_if_block_stalled(res, residual_norms, cols, vals, k)
+    if tres.status != _hip.OK and not tres.rel_residual <= max(RTOL, STALL_WARN_ABOVE):
+        warnings.warn(f"The thermal solve stopped at a relative residual of {tres.rel_residual:.3e}", SolverWarning)
+    solutions = [_column_solution(board, sub, np.ascontiguousarray(V[:, j]), residual_norms[j], res, power[j],
+                                  f"Load case {j}: " if k > 1 else "") for j, (sub, _) in enumerate(substituted)]
+    ambient, voff = checked.ambient, board.vindex.offsets
+    info = {"iterations": int(tres.iterations), "rel_residual": float(tres.rel_residual), "seconds": float(tres.seconds)}
+    heat_val = heat[2].reshape(k, len(resistors), 2) if heat is not None else None
+
+    def cold(layer_i):
+        out = []
+        for msh in board.disconnected_meshes_by_layer[layer_i]:
+            msh = msh if isinstance(msh, mesh.Mesh) else mesh.Mesh.from_reference(msh)
+            zf = mesh.ZeroForm(msh)
+            zf.values = np.full(len(msh.vertices), ambient, dtype=DTYPE)
+            out.append(zf)
+        return out
+
+    reports = []
+    for j, (_, renamed) in enumerate(substituted):
+        case_resistors = [e for network in board.filtered_networks for e in renamed.get(id(network), network).elements
+                          if element_kind(e) == "Resistor"]
+        temps, faces, hotspots, layers = [], [], [], []
+        for layer_i in range(n_layers):
+            zfs, tfs, best, heat_in, loss = [], [], None, [], []
+            for in_layer, (mesh_i, msh, lo, hi) in enumerate(board.layer_meshes(layer_i)):
+                heat_in.append(float(mesh_heat[j, mesh_i]))
+                loss.append(float(mesh_loss[j, mesh_i]))
+                # meshes come in global vertex order: a later mesh wins only with a strictly larger temperature
+                if mesh_vert[j, mesh_i] >= 0 and (best is None or mesh_max[j, mesh_i] + ambient > best[0]):
+                    v = int(mesh_vert[j, mesh_i] - voff[mesh_i])
+                    best = (float(mesh_max[j, mesh_i] + ambient), in_layer, v, float(msh.points[v][0]), float(msh.points[v][1]))
+                if fields:
+                    zf, tf = mesh.ZeroForm(msh), mesh.TwoForm(msh)
+                    zf.values = theta[j, voff[mesh_i]:voff[mesh_i + 1]] + ambient
+                    tf.values = mean[j, lo:hi] + ambient
+                    zfs.append(zf)
+                    tfs.append(tf)
+            temps.append(zfs)
+            faces.append(tfs)
+            hotspots.append(best)
+            layers.append({"heat": math.fsum(heat_in), "loss": math.fsum(loss)})
+        elements = {}
+        for i, ((element, row), case_element) in enumerate(zip(resistors, case_resistors)):
+            deposited = float(heat_val[j, i].sum()) if heat_val is not None else 0.0
+            elements[case_element] = {"heat": deposited,
+                                      "flow": float(checked.links[element] * (theta[j, row[1]] - theta[j, row[2]]))}
+        reports.append(ThermalReport(
+            temperatures=temps if fields else None, face_temperatures=faces if fields else None,
+            disconnected_temperatures=[cold(layer_i) for layer_i in range(n_layers)], hotspots=hotspots, layers=layers,
+            elements=elements, total_heat=math.fsum([layer["heat"] for layer in layers] + [e["heat"] for e in elements.values()]),
+            total_loss=math.fsum(layer["loss"] for layer in layers), info=info))
+    env_temps, env_cases, env_hotspots = [], [], []
+    for layer_i in range(n_layers):
+        zfs, which = [], []
+        for mesh_i, msh, _lo, _hi in board.layer_meshes(layer_i):
+            zf = mesh.ZeroForm(msh)
+            zf.values = env[voff[mesh_i]:voff[mesh_i + 1]] + ambient
+            zfs.append(zf)
+            which.append(env_case[voff[mesh_i]:voff[mesh_i + 1]])
+        env_temps.append(zfs)
+        env_cases.append(which)
+        spots = [rep.hotspots[layer_i] for rep in reports]
+        if spots[0] is None:
+            env_hotspots.append(None)
+        else:
+            c = max(range(k), key=lambda j: (spots[j][0], -j))          # the lowest case of the largest temperature
+            env_hotspots.append((spots[c][0], c, *spots[c][1:]))
+    laps.lap("solutions")
+    return solutions, reports, ThermalEnvelope(temperatures=env_temps, cases=env_cases, hotspots=env_hotspots)
+
+
+def solve_meshed_thermal(prob, meshes, mesh_index_to_layer_index, model: ThermalModel, *, cases=None, per_case_fields=True,
+                         filtered_networks=None, disconnected_meshes_by_layer=None, partition=None,
+                         timings: Optional[dict] = None):
+    """``solve_meshed`` together with how hot the Joule heating makes the copper: ``(Solution, ThermalReport)``, or for a list
+    of load ``cases`` (the mappings :func:`check_load_cases` accepts) ``([Solution], [ThermalReport], ThermalEnvelope)``.
+
+    The model (DESIGN.md "Thermal") is one more sheet problem on the same meshes, for the temperature rise theta = T -
+    ambient at every vertex of the connected meshes and every internal node:
+
+        (K_kappa + diag(h M_v) + links) theta = b
+
+    with K_kappa the cotangent stiffness with the layer's thermal sheet conductance kappa [W/K] in the place of sigma, M_v a
+    third of the area of the faces around v, h the layer's film coefficient [W/(K mesh-unit^2)], a thermal conductance g
+    [W/K] per resistor, and b_v a third of the Joule power [W] of the faces around v -- the weights' form sigma sum_edges
+    w_ik (V_i - V_k)^2 that ``CurrentReport.layers`` sums, which balances the elements' powers exactly -- plus, with
+    ``model.element_heat``, half of every resistor's dissipation at each of its terminals.  Since K and the links annihilate
+    constants, ``total_loss`` (what the films carry away) equals ``total_heat`` (what the sources deliver) up to the
+    solve's tolerance.  The coupling is one-way: the copper's resistivity does not follow the temperature.
+
+    The electrical block is the load-case path; the thermal operator is then assembled from the meshes the device still
+    holds, the face powers of every case are computed from the potentials it holds, and all cases go through one block
+    solve with the multigrid preconditioner -- the powers never visit the host.  Disconnected meshes take no part and
+    report the ambient temperature.  With ``per_case_fields=False`` no per-face temperature is computed and the reports
+    carry no ``temperatures`` or ``face_temperatures``; hotspots, sums and the envelope are the same.  ValueError, before
+    anything reaches the device, for an invalid model (:func:`check_thermal_model`), invalid cases, a mesh vertex without
+    a face, and a ``partition`` over several GPUs.  ``timings`` (a dict) receives the host time of each step in seconds."""
+    _refuse_partition(partition, "temperatures")
+    checked = check_thermal_model(prob, model, filtered_networks)
+    single = cases is None
+    checked_cases = [{}] if single else check_load_cases(prob, cases)
+    solutions, reports, envelope = _solve_block_thermal(prob, meshes, mesh_index_to_layer_index, checked, checked_cases,
+                                                        bool(per_case_fields) or single, filtered_networks,
+                                                        disconnected_meshes_by_layer, _Laps(timings))
+    if single:
+        return solutions[0], reports[0]
+    return solutions, reports, envelope
+
+
+def solve_thermal(prob, model: ThermalModel, mesher_config: Optional[mesh.Mesher.Config] = None, *, mesher=None, cases=None,
+                  per_case_fields=True, partition=None):
+    """``solve`` with the copper's temperatures (see :func:`solve_meshed_thermal`): the board is meshed once."""
+    _refuse_partition(partition, "temperatures")
+    check_thermal_model(prob, model)
+    if cases is not None:
+        cases = check_load_cases(prob, cases)
+    meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
+    return solve_meshed_thermal(prob, meshes, mesh_index_to_layer_index, model, cases=cases, per_case_fields=per_case_fields)
 
 
 # --------------------------------------------------------------------------------------------
