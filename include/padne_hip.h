@@ -636,6 +636,50 @@ int padne_thermal_report(padne_ctx *ctx, padne_thermal *th, int32_t n_cols, int6
                          double *face_mean_out, double *mesh_max_out, int64_t *mesh_vertex_out, double *mesh_heat_out,
                          double *mesh_loss_out, double *env_out, int32_t *env_case_out);
 
+/* ---- electro-thermal coupling: the copper's conductance follows its temperature ----------------
+ * No reference counterpart ("Electro-thermal").  Face t of mesh m conducts sigma[m] * s[t],
+ *     s[t] = 1 / (1 + alpha[m] * ((mean[t] + ambient) - conductance_temperature)),
+ * mean[t] = ((theta_1 + theta_2) + theta_3) / 3 the face mean of padne_thermal_report.  The handle borrows the assembled
+ * system `L`, whose values it rewrites in place, and the thermal handle `th` made from it (both must outlive it); it owns a
+ * copy L0 of L's values, the scale of the next revalue, the scale of the last one and the face means of the last update.
+ * Created with the copper at ambient: theta = 0, s = s^(0).  PADNE_E_INVALID for a null or foreign handle, an n_mesh that
+ * is not the mesh's, a system whose rows' columns do not ascend (an uploaded matrix), an alpha or temperature that is not
+ * finite, and a face whose 1 + alpha (T - T0) is not finite and positive (the message names the lowest such face).
+ * Lumped resistors keep their resistance. */
+typedef struct padne_coupled padne_coupled;
+int padne_coupled_create(padne_ctx *ctx, padne_csr *L, padne_thermal *th, int32_t n_mesh, const double *alpha, double ambient,
+                         double conductance_temperature, padne_coupled **out);
+/* L gets the values it was assembled with again (NULL is accepted).  Destroy before `th`, `L` and the context. */
+int padne_coupled_destroy(padne_coupled *cp);
+/* back to the copper at ambient: the face means 0, the next scale s^(0) */
+int padne_coupled_reset(padne_ctx *ctx, padne_coupled *cp);
+/* the next revalue's scale from scale_host[n_tri] (finite and positive), for tests */
+int padne_coupled_set_scale(padne_ctx *ctx, padne_coupled *cp, int64_t n_tri, const double *scale_host);
+/* scale_out[n_tri]: the next revalue's scale (used = 0) or the last one's (used = 1); face_mean_out[n_tri] (may be null): the
+ * face means of the last update */
+int padne_coupled_get_scale(padne_ctx *ctx, const padne_coupled *cp, int32_t used, int64_t n_tri, double *scale_out,
+                            double *face_mean_out);
+/* L's values from L0 and the scale: L = L0 + sum_f (s_f - 1) sigma_m K_f.  Row v of a vertex: for every face f incident to
+ * v in ascending global face number, with t_f = (s_f - 1) * sigma_m and the |cot|/2 weights of the face's two edges at v,
+ * (v, a) then (v, b) in the face's cyclic corner order after v: c_a = t_f * w_a, c_b = t_f * w_b, acc[v, a] += c_a,
+ * acc[v, b] += c_b, acc[v, v] = (acc[v, v] - c_a) - c_b, every acc starting at 0.0; then L[v, j] = L0[v, j] + acc[v, j].
+ * Other rows are L0's.  The stiffness block stays symmetric bit for bit, and a scale of 1 everywhere gives the bits of L0.
+ * What L had derived from its values (1 / diagonal, single-precision copy, multigrid hierarchy) is dropped; a padne_kkt plan
+ * made from L before the call holds the old values and must not be used again.  The scale becomes the one "used". */
+int padne_coupled_revalue(padne_ctx *ctx, padne_coupled *cp);
+/* The next scale and *increment_out = max_t |mean[t] - previous mean[t]| from the theta of the thermal handle's last solve
+ * (one column; theta_host null), or from theta_host[n_theta], n_theta = n_potential.  The maximum is taken per 256 faces
+ * and then by one workgroup: two calls give the same bits. */
+int padne_coupled_update(padne_ctx *ctx, padne_coupled *cp, int64_t n_theta, const double *theta_host, double *increment_out);
+/* padne_thermal_solve_kkt for the one column of `plan`'s finished block with sigma[m] * s[t], s the used scale, in the
+ * place of sigma[m] in the face powers (one product, then face_edge_power as before).  Arguments and errors as there. */
+int padne_coupled_solve_kkt(padne_ctx *ctx, padne_coupled *cp, padne_kkt *plan, int64_t n_heat, const int64_t *heat_node,
+                            const int32_t *heat_col, const double *heat_val, const padne_solve_opts *opts, double *theta_host,
+                            padne_solve_info *info);
+/* out_host[n_tri] = padne_kkt_power_density_block's value of the one column of `plan`'s finished block, times the used
+ * scale of the face (one product on the device) */
+int padne_coupled_power_density(padne_ctx *ctx, padne_coupled *cp, padne_kkt *plan, double *out_host);
+
 /* ---- introspection for benchmarks ---------------------------------------------------------- */
 /* algorithmic bytes of one CSR SpMV: 12*nnz + 20*n_rows + 4   */
 int64_t padne_spmv_algorithmic_bytes(const padne_csr *m);

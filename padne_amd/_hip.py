@@ -157,6 +157,15 @@ SIGNATURES = {
                                           C.POINTER(SolveInfo)]),
     "padne_thermal_face_power": (C.c_int, [_P, _P, C.c_int32, _PF64]),
     "padne_thermal_report": (C.c_int, [_P, _P, C.c_int32, _I64, _I64, C.c_int32, _PF64, _PF64, _PI64, _PF64, _PF64, _PF64, _PI32]),
+    "padne_coupled_create": (C.c_int, [_P, _P, _P, C.c_int32, _PF64, C.c_double, C.c_double, C.POINTER(_P)]),
+    "padne_coupled_destroy": (C.c_int, [_P]),
+    "padne_coupled_reset": (C.c_int, [_P, _P]),
+    "padne_coupled_set_scale": (C.c_int, [_P, _P, _I64, _PF64]),
+    "padne_coupled_get_scale": (C.c_int, [_P, _P, C.c_int32, _I64, _PF64, _PF64]),
+    "padne_coupled_revalue": (C.c_int, [_P, _P]),
+    "padne_coupled_update": (C.c_int, [_P, _P, _I64, _PF64, _PF64]),
+    "padne_coupled_solve_kkt": (C.c_int, [_P, _P, _P, _I64, _PI64, _PI32, _PF64, C.POINTER(SolveOpts), _PF64, C.POINTER(SolveInfo)]),
+    "padne_coupled_power_density": (C.c_int, [_P, _P, _P, _PF64]),
     "padne_spmv_algorithmic_bytes": (_I64, [_P]),
     "padne_spmv_time": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _PF64]),
 }
@@ -1117,6 +1126,73 @@ class Thermal:
             _ptr(vert, _PI64), _ptr(heat, _PF64), _ptr(loss, _PF64), None if env is None else _ptr(env, _PF64),
             None if env_case is None else _ptr(env_case, _PI32)))
         return mean, mesh_max, vert, heat, loss, env, env_case
+
+
+class Coupled:
+    """``padne_coupled``: the electro-thermal coupling of an assembled system ``L`` and the :class:`Thermal` made from it
+    (include/padne_hip.h, "electro-thermal coupling").  ``alpha`` per mesh [1/K].  Rewrites L's values in place (``revalue``)
+    and puts the assembled ones back on ``close``; close it before ``thermal`` and ``L``."""
+
+    def __init__(self, L: "CsrMatrix", thermal: "Thermal", alpha, ambient: float, conductance_temperature: float):
+        self.ctx, self.L, self.thermal = L.ctx, L, thermal
+        a = _f64(alpha).reshape(-1)
+        h = _P()
+        _check(self.ctx._lib.padne_coupled_create(self.ctx._h, L._h, thermal._h, a.shape[0], _ptr(a, _PF64), float(ambient),
+                                                  float(conductance_temperature), C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None) and self.ctx._h:
+            self.ctx._lib.padne_coupled_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self) -> None:
+        """Back to the copper at ambient."""
+        _check(self.ctx._lib.padne_coupled_reset(self.ctx._h, self._h))
+
+    def set_scale(self, scale) -> None:
+        s = _f64(scale).reshape(-1)
+        _check(self.ctx._lib.padne_coupled_set_scale(self.ctx._h, self._h, s.shape[0], _ptr(s, _PF64)))
+
+    def get_scale(self, n_tri: int, used: bool = False, means: bool = False):
+        """The next revalue's scale (n_tri,), or with ``used`` the last one's; with ``means`` also the face means of the
+        last update."""
+        s = np.empty(int(n_tri), dtype=np.float64)
+        mean = np.empty(int(n_tri), dtype=np.float64) if means else None
+        _check(self.ctx._lib.padne_coupled_get_scale(self.ctx._h, self._h, 1 if used else 0, int(n_tri), _ptr(s, _PF64),
+                                                     None if mean is None else _ptr(mean, _PF64)))
+        return (s, mean) if means else s
+
+    def revalue(self) -> None:
+        """L's values from the assembled ones and the scale; plans made from L before this hold the old values."""
+        _check(self.ctx._lib.padne_coupled_revalue(self.ctx._h, self._h))
+
+    def update(self, theta=None) -> float:
+        """The next scale from the thermal handle's last solve (or from ``theta`` (n_potential,)): the largest change of a
+        face mean [K]."""
+        d = C.c_double()
+        th = None if theta is None else _f64(theta).reshape(-1)
+        _check(self.ctx._lib.padne_coupled_update(self.ctx._h, self._h, 0 if th is None else th.shape[0],
+                                                  None if th is None else _ptr(th, _PF64), C.byref(d)))
+        return d.value
+
+    def solve_kkt(self, plan: "KktPlan", heat=None, *, rtol=1e-12, max_iter=200000, precond="amg", download=True):
+        """``Thermal.solve_kkt`` for the one column of ``plan``'s finished block with the used scale in the face powers."""
+        lib = self.ctx._lib
+        return self.thermal._solve(lambda *a: lib.padne_coupled_solve_kkt(self.ctx._h, self._h, plan._h, *a), 1, heat, rtol,
+                                   max_iter, precond, download)
+
+    def power_density(self, plan: "KktPlan", n_tri: int) -> np.ndarray:
+        """``KktPlan.power_density_block(1, n_tri)[0]`` times the used scale, on the device."""
+        out = np.empty(int(n_tri), dtype=np.float64)
+        _check(self.ctx._lib.padne_coupled_power_density(self.ctx._h, self._h, plan._h, _ptr(out, _PF64)))
+        return out
 
 
 class Sampler:

@@ -19,38 +19,12 @@
 // field-major ([column][vertex], [column][face]) so the lanes of a wave read and write neighbouring doubles.  No
 // floating-point atomics; the sums of the report go through the fixed-order tile reductions of error.hpp: two calls give
 // the same bits.  Compiled with -ffp-contract=off: the expressions round as written, a numpy restatement reproduces them.
-#include "error.hpp"
+#include "thermal.hpp"
 
 #include <algorithm>
 #include <cmath>
 #include <numeric>
 #include <vector>
-
-namespace padne {
-
-// kkt.hip: the V the last padne_kkt_finish_block left on the device, after the checks of every post-processing entry
-int kkt_finished_block(const char *entry, padne_ctx *ctx, const padne_kkt *k, int32_t n_cols, const double **V_out, long long *N_out,
-                       const padne_csr **L_out);
-
-constexpr int kThermalChunk = 8;       // columns per launch of the load kernel, per step of the face-power kernel (goal.hip's 8)
-
-}  // namespace padne
-
-struct padne_thermal {
-    padne_ctx *ctx = nullptr;
-    const padne_csr *L = nullptr;            // borrowed: the electrical system, for its mesh
-    long long n_pot = 0, n_vert = 0, n_tri = 0;
-    int n_mesh = 0;
-    padne_csr *A = nullptr;                  // owned (with its multigrid hierarchy once a solve has built it)
-    int *vptr = nullptr, *vface = nullptr;   // vertex -> incident faces, rows in ascending face order (error_vertex_faces)
-    double *Mv = nullptr, *hM = nullptr;     // [n_vert] lumped area and film conductance h_m M_v of every vertex
-    std::vector<int64_t> voff, toff;         // the mesh's offset tables on the host
-    // of the last solve: face powers [n_cols][n_tri] and temperature rises [n_cols][n_pot], field-major
-    double *P = nullptr, *theta = nullptr;
-    size_t P_cap = 0, theta_cap = 0;
-    int n_cols = 0;
-    bool solved = false;
-};
 
 namespace padne {
 
@@ -108,12 +82,15 @@ __global__ __launch_bounds__(256) void thermal_form_kernel(const long long n_row
 // ---- heat load -----------------------------------------------------------------------------------------------------------
 // P[c][t] = sigma sum_edges w_ik (V_i - V_k)^2 of every column c of V[..][n_cols], the arithmetic of
 // current_cases_face_kernel's per-mesh power.  One thread per face: corners, xy and weights once, the columns in register
-// chunks whose gathers are in flight together
+// chunks whose gathers are in flight together.  SCALED (the electro-thermal coupling): the one product sigma[m] * scale[t] in
+// the place of sigma[m]
+template <bool SCALED>
 __global__ __launch_bounds__(256) void thermal_face_power_kernel(const long long n_tri, const int n_mesh,
                                                                  const int32_t *__restrict__ tri, const double *__restrict__ xy,
                                                                  const long long *__restrict__ voff,
                                                                  const long long *__restrict__ toff,
-                                                                 const double *__restrict__ sigma, const int n_cols,
+                                                                 const double *__restrict__ sigma,
+                                                                 const double *__restrict__ scale, const int n_cols,
                                                                  const double *__restrict__ V, double *__restrict__ P,
                                                                  int *__restrict__ err) {
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -128,7 +105,7 @@ __global__ __launch_bounds__(256) void thermal_face_power_kernel(const long long
     const double x1 = xy[2 * g1], y1 = xy[2 * g1 + 1];
     const double x2 = xy[2 * g2], y2 = xy[2 * g2 + 1];
     const double x3 = xy[2 * g3], y3 = xy[2 * g3 + 1];
-    const double s = sigma[m];
+    const double s = SCALED ? sigma[m] * scale[t] : sigma[m];
     const double w23 = cot_half(x2, y2, x3, y3, x1, y1);     // edge 2-3, opposite 1
     const double w31 = cot_half(x3, y3, x1, y1, x2, y2);
     const double w12 = cot_half(x1, y1, x2, y2, x3, y3);
@@ -601,14 +578,15 @@ extern "C" int padne_thermal_solve(padne_ctx *ctx, padne_thermal *th, int32_t n_
     return thermal_solve_core(ctx, th, n_cols, n_heat, heat_node, heat_col, heat_val, opts, theta_host, info);
 }
 
-extern "C" int padne_thermal_solve_kkt(padne_ctx *ctx, padne_thermal *th, padne_kkt *plan, int32_t n_cols, int64_t n_heat,
-                                       const int64_t *heat_node, const int32_t *heat_col, const double *heat_val,
-                                       const padne_solve_opts *opts, double *theta_host, padne_solve_info *info) {
-    PADNE_TRY(thermal_require("padne_thermal_solve_kkt", ctx, th));
+int padne::thermal_solve_kkt_scaled(const char *entry, padne_ctx *ctx, padne_thermal *th, padne_kkt *plan, int32_t n_cols,
+                                    const double *scale, int64_t n_heat, const int64_t *heat_node, const int32_t *heat_col,
+                                    const double *heat_val, const padne_solve_opts *opts, double *theta_host,
+                                    padne_solve_info *info) {
+    PADNE_TRY(thermal_require(entry, ctx, th));
     const double *V = nullptr;
     long long N = 0;
     const padne_csr *L = nullptr;
-    PADNE_TRY(kkt_finished_block("padne_thermal_solve_kkt", ctx, plan, n_cols, &V, &N, &L));
+    PADNE_TRY(kkt_finished_block(entry, ctx, plan, n_cols, &V, &N, &L));
     PADNE_REQUIRE(L == th->L, "the plan and the thermal model must come from the same assembled system");
     PADNE_TRY(thermal_check_heat(th, n_cols, n_heat, heat_node, heat_col, heat_val));
     PADNE_HIP_CHECK(hipSetDevice(ctx->device));
@@ -620,12 +598,23 @@ extern "C" int padne_thermal_solve_kkt(padne_ctx *ctx, padne_thermal *th, padne_
         int *d_bad = nullptr;
         PADNE_TRY(sc.alloc(&d_bad, 1));
         PADNE_HIP_CHECK(hipMemsetAsync(d_bad, 0, sizeof(int), s));
-        hipLaunchKernelGGL(thermal_face_power_kernel, dim3(nblk(th->n_tri)), dim3(256), 0, s, th->n_tri, th->n_mesh, M.tri, M.xy, M.voff,
-                           M.toff, M.sigma, (int)n_cols, V, th->P, d_bad);
+        if (scale != nullptr)
+            hipLaunchKernelGGL(thermal_face_power_kernel<true>, dim3(nblk(th->n_tri)), dim3(256), 0, s, th->n_tri, th->n_mesh, M.tri,
+                               M.xy, M.voff, M.toff, M.sigma, scale, (int)n_cols, V, th->P, d_bad);
+        else
+            hipLaunchKernelGGL(thermal_face_power_kernel<false>, dim3(nblk(th->n_tri)), dim3(256), 0, s, th->n_tri, th->n_mesh, M.tri,
+                               M.xy, M.voff, M.toff, M.sigma, (const double *)nullptr, (int)n_cols, V, th->P, d_bad);
         PADNE_HIP_CHECK(hipGetLastError());
         PADNE_TRY(thermal_bad_flag(s, d_bad, "triangle index out of range"));
     }
     return thermal_solve_core(ctx, th, n_cols, n_heat, heat_node, heat_col, heat_val, opts, theta_host, info);
+}
+
+extern "C" int padne_thermal_solve_kkt(padne_ctx *ctx, padne_thermal *th, padne_kkt *plan, int32_t n_cols, int64_t n_heat,
+                                       const int64_t *heat_node, const int32_t *heat_col, const double *heat_val,
+                                       const padne_solve_opts *opts, double *theta_host, padne_solve_info *info) {
+    return thermal_solve_kkt_scaled("padne_thermal_solve_kkt", ctx, th, plan, n_cols, nullptr, n_heat, heat_node, heat_col, heat_val,
+                                    opts, theta_host, info);
 }
 
 extern "C" int padne_thermal_face_power(padne_ctx *ctx, const padne_thermal *th, int32_t n_cols, double *out_host) {

@@ -1,0 +1,43 @@
+// The thermal handle (thermal.hip) as the translation units that work on it see it: thermal.hip itself and the electro-thermal
+// coupling (coupled.hip), which borrows the handle's vertex -> faces lists and its theta.
+#pragma once
+
+#include "error.hpp"
+
+#include <vector>
+
+namespace padne {
+
+// kkt.hip: the V the last padne_kkt_finish_block left on the device, after the checks of every post-processing entry
+int kkt_finished_block(const char *entry, padne_ctx *ctx, const padne_kkt *k, int32_t n_cols, const double **V_out, long long *N_out,
+                       const padne_csr **L_out);
+
+constexpr int kThermalChunk = 8;       // columns per launch of the load kernel, per step of the face-power kernel (goal.hip's 8)
+
+}  // namespace padne
+
+struct padne_thermal {
+    padne_ctx *ctx = nullptr;
+    const padne_csr *L = nullptr;            // borrowed: the electrical system, for its mesh
+    long long n_pot = 0, n_vert = 0, n_tri = 0;
+    int n_mesh = 0;
+    padne_csr *A = nullptr;                  // owned (with its multigrid hierarchy once a solve has built it)
+    int *vptr = nullptr, *vface = nullptr;   // vertex -> incident faces, rows in ascending face order (error_vertex_faces)
+    double *Mv = nullptr, *hM = nullptr;     // [n_vert] lumped area and film conductance h_m M_v of every vertex
+    std::vector<int64_t> voff, toff;         // the mesh's offset tables on the host
+    // of the last solve: face powers [n_cols][n_tri] and temperature rises [n_cols][n_pot], field-major
+    double *P = nullptr, *theta = nullptr;
+    size_t P_cap = 0, theta_cap = 0;
+    int n_cols = 0;
+    bool solved = false;
+};
+
+namespace padne {
+
+// thermal.hip: padne_thermal_solve_kkt with every face's conductance sigma[m] * scale[t] in the place of sigma[m] (scale
+// [n_tri] on the device; null: sigma[m] alone, the bits of padne_thermal_solve_kkt)
+int thermal_solve_kkt_scaled(const char *entry, padne_ctx *ctx, padne_thermal *th, padne_kkt *plan, int32_t n_cols,
+                             const double *scale, int64_t n_heat, const int64_t *heat_node, const int32_t *heat_col,
+                             const double *heat_val, const padne_solve_opts *opts, double *theta_host, padne_solve_info *info);
+
+}  // namespace padne

@@ -2032,53 +2032,13 @@ def thermal_heat_triples(pairs, flows_by_case) -> tuple:
     return np.asarray(node, dtype=np.int64), np.asarray(col, dtype=np.int32), np.asarray(val, dtype=DTYPE)
 
 
-def _solve_block_thermal(prob, meshes, mesh_index_to_layer_index, checked: CheckedThermalModel, cases, fields: bool,
-                         filtered_networks, disconnected_meshes_by_layer, laps: _Laps):
-    """The checked ``cases`` of ``prob`` as one electrical block and one thermal block on top of it, for the checked model:
-    ([Solution], [ThermalReport], ThermalEnvelope).  ``fields``: with the per-case temperatures of vertices and faces."""
-    substituted = [substitute_load_case(prob, case) for case in cases]
-    k, n_layers = len(cases), len(prob.layers)
-    board = index_board(prob, meshes, mesh_index_to_layer_index, filtered_networks, disconnected_meshes_by_layer)
-    _refuse_bare_vertices(board)
-    n_vert = len(board.vindex)
-    if n_vert == 0 or not int(board.tri_offsets[-1]):
-        raise ValueError("the thermal model needs connected copper: the board has no connected mesh with faces")
-    pairs = global_elements(board.filtered_networks, board.node_indexer)
-    laps.lap("indexing")
-    layer_of = board.layer_of
-    with board.assembled() as (L, _):
-        rows, cols, vals = stamp_load_cases(board.filtered_networks, board.node_indexer, L.shape[0], cases)
-        laps.lap("assembly")
-        log.info(f"Solving {k} load case(s) as one block, with their temperatures")
-        plan, V, residual_norms, res, n_tri, _n_mesh = _solve_block_on_device(L, rows, cols, vals, k, k, laps)
-        power = plan.power_density_block(k, n_tri)
-        local, Vu = _gather_element_rows([row for _, row in pairs], V, _ROW_UNKNOWNS)
-        flows_by_case = [element_flows(_case_element_rows(pairs, local, case), Vu[:, j]) for j, case in enumerate(cases)]
-        laps.lap("power_density")
-        resistors = [(element, row) for element, row in pairs if row[0] == "R"]
-        n_potential = L.layout.n_potential
-        thermal = _hip.Thermal(L.dev, n_potential, [checked.kappa[layer_of[i]] for i in range(len(board.meshes))],
-                               [checked.film[layer_of[i]] for i in range(len(board.meshes))],
-                               [row[1] for _, row in resistors], [row[2] for _, row in resistors],
-                               [checked.links[element] for element, _ in resistors])
-        try:
-            laps.lap("thermal_setup")
-            heat = thermal_heat_triples(pairs, flows_by_case) if checked.element_heat else None
-            theta, tres = thermal.solve_kkt(plan, k, heat, rtol=RTOL, max_iter=MAX_ITER)
-            laps.lap("thermal_solve")
-            mean, mesh_max, mesh_vert, mesh_heat, mesh_loss, env, env_case = thermal.report(k, n_tri, n_vert, fields=fields)
-            laps.lap("thermal_report")
-        finally:
-            thermal.close()
-    laps.lap()
-    _warn_if_block_stalled(res, residual_norms, cols, vals, k)
-    if tres.status != _hip.OK and not tres.rel_residual <= max(RTOL, STALL_WARN_ABOVE):
-        warnings.warn(f"The thermal solve stopped at a relative residual of {tres.rel_residual:.3e}", SolverWarning)
-    solutions = [_column_solution(board, sub, np.ascontiguousarray(V[:, j]), residual_norms[j], res, power[j],
-                                  f"Load case {j}: " if k > 1 else "") for j, (sub, _) in enumerate(substituted)]
-    ambient, voff = checked.ambient, board.vindex.offsets
-    info = {"iterations": int(tres.iterations), "rel_residual": float(tres.rel_residual), "seconds": float(tres.seconds)}
-    heat_val = heat[2].reshape(k, len(resistors), 2) if heat is not None else None
+def _thermal_reports(board: IndexedBoard, checked: CheckedThermalModel, substituted, resistors, fields: bool, theta, mean,
+                     mesh_max, mesh_vert, mesh_heat, mesh_loss, heat_val, infos) -> list:
+    """The ThermalReports of k cases from what ``Thermal.report`` returns for them: ``theta`` (k, n_potential), ``mean`` (k,
+    n_tri) or None without ``fields``, the per-mesh arrays (k, n_mesh), ``heat_val`` (k, n_resistors, 2) the heat put into the
+    resistors' terminals or None, ``infos`` the info dict of each case.  ``substituted``: substitute_load_case of each case;
+    ``resistors``: the (element, row) pairs of the board's resistors."""
+    ambient, voff, n_layers = checked.ambient, board.vindex.offsets, len(board.prob.layers)
 
     def cold(layer_i):
         out = []
@@ -2122,7 +2082,14 @@ def _solve_block_thermal(prob, meshes, mesh_index_to_layer_index, checked: Check
             temperatures=temps if fields else None, face_temperatures=faces if fields else None,
             disconnected_temperatures=[cold(layer_i) for layer_i in range(n_layers)], hotspots=hotspots, layers=layers,
             elements=elements, total_heat=math.fsum([layer["heat"] for layer in layers] + [e["heat"] for e in elements.values()]),
-            total_loss=math.fsum(layer["loss"] for layer in layers), info=info))
+            total_loss=math.fsum(layer["loss"] for layer in layers), info=infos[j]))
+    return reports
+
+
+def _thermal_envelope(board: IndexedBoard, ambient: float, env, env_case, reports) -> ThermalEnvelope:
+    """The ThermalEnvelope from the per-vertex maximum ``env`` of theta over the cases, the case ``env_case`` that attains it,
+    and the cases' reports."""
+    voff, n_layers, k = board.vindex.offsets, len(board.prob.layers), len(reports)
     env_temps, env_cases, env_hotspots = [], [], []
     for layer_i in range(n_layers):
         zfs, which = [], []
@@ -2139,8 +2106,60 @@ def _solve_block_thermal(prob, meshes, mesh_index_to_layer_index, checked: Check
         else:
             c = max(range(k), key=lambda j: (spots[j][0], -j))          # the lowest case of the largest temperature
             env_hotspots.append((spots[c][0], c, *spots[c][1:]))
+    return ThermalEnvelope(temperatures=env_temps, cases=env_cases, hotspots=env_hotspots)
+
+
+def _solve_block_thermal(prob, meshes, mesh_index_to_layer_index, checked: CheckedThermalModel, cases, fields: bool,
+                         filtered_networks, disconnected_meshes_by_layer, laps: _Laps):
+    """The checked ``cases`` of ``prob`` as one electrical block and one thermal block on top of it, for the checked model:
+    ([Solution], [ThermalReport], ThermalEnvelope).  ``fields``: with the per-case temperatures of vertices and faces."""
+    substituted = [substitute_load_case(prob, case) for case in cases]
+    k = len(cases)
+    board = index_board(prob, meshes, mesh_index_to_layer_index, filtered_networks, disconnected_meshes_by_layer)
+    _refuse_bare_vertices(board)
+    n_vert = len(board.vindex)
+    if n_vert == 0 or not int(board.tri_offsets[-1]):
+        raise ValueError("the thermal model needs connected copper: the board has no connected mesh with faces")
+    pairs = global_elements(board.filtered_networks, board.node_indexer)
+    laps.lap("indexing")
+    layer_of = board.layer_of
+    with board.assembled() as (L, _):
+        rows, cols, vals = stamp_load_cases(board.filtered_networks, board.node_indexer, L.shape[0], cases)
+        laps.lap("assembly")
+        log.info(f"Solving {k} load case(s) as one block, with their temperatures")
+        plan, V, residual_norms, res, n_tri, _n_mesh = _solve_block_on_device(L, rows, cols, vals, k, k, laps)
+        power = plan.power_density_block(k, n_tri)
+        local, Vu = _gather_element_rows([row for _, row in pairs], V, _ROW_UNKNOWNS)
+        flows_by_case = [element_flows(_case_element_rows(pairs, local, case), Vu[:, j]) for j, case in enumerate(cases)]
+        laps.lap("power_density")
+        resistors = [(element, row) for element, row in pairs if row[0] == "R"]
+        n_potential = L.layout.n_potential
+        thermal = _hip.Thermal(L.dev, n_potential, [checked.kappa[layer_of[i]] for i in range(len(board.meshes))],
+                               [checked.film[layer_of[i]] for i in range(len(board.meshes))],
+                               [row[1] for _, row in resistors], [row[2] for _, row in resistors],
+                               [checked.links[element] for element, _ in resistors])
+        try:
+            laps.lap("thermal_setup")
+            heat = thermal_heat_triples(pairs, flows_by_case) if checked.element_heat else None
+            theta, tres = thermal.solve_kkt(plan, k, heat, rtol=RTOL, max_iter=MAX_ITER)
+            laps.lap("thermal_solve")
+            mean, mesh_max, mesh_vert, mesh_heat, mesh_loss, env, env_case = thermal.report(k, n_tri, n_vert, fields=fields)
+            laps.lap("thermal_report")
+        finally:
+            thermal.close()
+    laps.lap()
+    _warn_if_block_stalled(res, residual_norms, cols, vals, k)
+    if tres.status != _hip.OK and not tres.rel_residual <= max(RTOL, STALL_WARN_ABOVE):
+        warnings.warn(f"The thermal solve stopped at a relative residual of {tres.rel_residual:.3e}", SolverWarning)
+    solutions = [_column_solution(board, sub, np.ascontiguousarray(V[:, j]), residual_norms[j], res, power[j],
+                                  f"Load case {j}: " if k > 1 else "") for j, (sub, _) in enumerate(substituted)]
+    info = {"iterations": int(tres.iterations), "rel_residual": float(tres.rel_residual), "seconds": float(tres.seconds)}
+    heat_val = heat[2].reshape(k, len(resistors), 2) if heat is not None else None
+    reports = _thermal_reports(board, checked, substituted, resistors, fields, theta, mean, mesh_max, mesh_vert, mesh_heat,
+                               mesh_loss, heat_val, [info] * k)
+    envelope = _thermal_envelope(board, checked.ambient, env, env_case, reports)
     laps.lap("solutions")
-    return solutions, reports, ThermalEnvelope(temperatures=env_temps, cases=env_cases, hotspots=env_hotspots)
+    return solutions, reports, envelope
 
 
 def solve_meshed_thermal(prob, meshes, mesh_index_to_layer_index, model: ThermalModel, *, cases=None, per_case_fields=True,
@@ -2160,7 +2179,8 @@ def solve_meshed_thermal(prob, meshes, mesh_index_to_layer_index, model: Thermal
     w_ik (V_i - V_k)^2 that ``CurrentReport.layers`` sums, which balances the elements' powers exactly -- plus, with
     ``model.element_heat``, half of every resistor's dissipation at each of its terminals.  Since K and the links annihilate
     constants, ``total_loss`` (what the films carry away) equals ``total_heat`` (what the sources deliver) up to the
-    solve's tolerance.  The coupling is one-way: the copper's resistivity does not follow the temperature.
+    solve's tolerance.  The coupling is one-way: the copper's resistivity does not follow the temperature
+    (:func:`solve_meshed_electrothermal` closes that loop).
 
     The electrical block is the load-case path; the thermal operator is then assembled from the meshes the device still
     holds, the face powers of every case are computed from the potentials it holds, and all cases go through one block
@@ -2190,6 +2210,296 @@ def solve_thermal(prob, model: ThermalModel, mesher_config: Optional[mesh.Mesher
         cases = check_load_cases(prob, cases)
     meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
     return solve_meshed_thermal(prob, meshes, mesh_index_to_layer_index, model, cases=cases, per_case_fields=per_case_fields)
+
+
+# --------------------------------------------------------------------------------------------
+# electro-thermal: the copper's conductance follows its temperature (DESIGN.md "Electro-thermal")
+# --------------------------------------------------------------------------------------------
+
+COPPER_TEMPERATURE_COEFFICIENT = 3.93e-3        # alpha [1/K] of copper's resistivity around room temperature
+
+
+class ThermalRunawayError(RuntimeError):
+    """The Picard loop of :func:`solve_meshed_electrothermal` diverges: the increments grew in three consecutive rounds."""
+
+
+@dataclass
+class ElectroThermalModel:
+    """What couples the temperatures back into the conductances (see :func:`solve_meshed_electrothermal`).
+
+    - ``thermal``: the :class:`ThermalModel`.
+    - ``temperature_coefficient``: alpha [1/K], one float for all layers or a mapping {layer or layer name: float}; a layer
+      that is not named gets copper's 3.93e-3.  A face at the mean temperature T conducts
+      ``layer.conductance / (1 + alpha (T - conductance_temperature))``.
+    - ``conductance_temperature``: T0, the temperature at which ``Layer.conductance`` holds, in the unit of
+      ``thermal.ambient``.
+    - ``tolerance``: the loop stops when no face mean moved by more than this [K] in a round.
+    - ``max_rounds``: the most rounds of the loop."""
+    thermal: ThermalModel
+    temperature_coefficient: object = COPPER_TEMPERATURE_COEFFICIENT
+    conductance_temperature: float = 20.0
+    tolerance: float = 0.01
+    max_rounds: int = 20
+
+
+@dataclass
+class CheckedElectroThermalModel:
+    """An :class:`ElectroThermalModel` resolved against a Problem (:func:`check_electrothermal_model`)."""
+    thermal: CheckedThermalModel
+    alpha: list                # per layer
+    conductance_temperature: float
+    tolerance: float
+    max_rounds: int
+
+
+@dataclass
+class CouplingReport:
+    """How the loop of :func:`solve_meshed_electrothermal` went for one load case."""
+    rounds: int
+    converged: bool
+    increments: list           # d_k [K] of every round: the largest change of a face's mean temperature
+    conductance_scale: list    # per layer, per mesh: TwoForm of s_f, the scale the last electrical solve used
+    iterations: list           # per round: {"electrical": iterations of the electrical solve, "thermal": of the thermal one}
+    elements: dict             # lumped element -> its element_flows entry in the last electrical solve (current, power, ...)
+
+
+def check_electrothermal_model(prob, model, filtered_networks=None) -> CheckedElectroThermalModel:
+    """``model`` resolved against ``prob``, or ValueError -- before anything reaches the device -- for what
+    :func:`check_thermal_model` refuses in ``model.thermal``; a temperature coefficient or conductance temperature that is
+    not finite; a mapping key that is no layer of the Problem; a tolerance that is not finite and positive; ``max_rounds``
+    below 1; and an ambient temperature at which a layer's 1 + alpha (ambient - T0) is not positive."""
+    if not isinstance(model, ElectroThermalModel):
+        raise ValueError("model must be an ElectroThermalModel")
+    thermal = check_thermal_model(prob, model.thermal, filtered_networks)
+
+    def finite(value, what):
+        try:
+            x = float(value)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what} must be a number, not {value!r}") from None
+        if not math.isfinite(x):
+            raise ValueError(f"{what} must be finite, not {value!r}")
+        return x
+
+    t0 = finite(model.conductance_temperature, "the conductance temperature")
+    alpha = [COPPER_TEMPERATURE_COEFFICIENT] * len(prob.layers)
+    if isinstance(model.temperature_coefficient, Mapping):
+        for key, value in model.temperature_coefficient.items():
+            if isinstance(key, str):
+                found = [i for i, layer in enumerate(prob.layers) if layer.name == key]
+            else:
+                found = [i for i, layer in enumerate(prob.layers) if layer is key or layer == key]
+            if not found:
+                raise ValueError(f"temperature_coefficient: {key!r} is no layer of the Problem")
+            for i in found:
+                alpha[i] = finite(value, f"the temperature coefficient of layer {prob.layers[i].name!r}")
+    else:
+        alpha = [finite(model.temperature_coefficient, "the temperature coefficient")] * len(prob.layers)
+    tolerance = _positive_number(model.tolerance, "the tolerance")
+    try:
+        max_rounds = int(model.max_rounds)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"max_rounds must be an integer, not {model.max_rounds!r}") from None
+    if max_rounds < 1 or max_rounds != model.max_rounds:
+        raise ValueError(f"max_rounds must be an integer of at least 1, not {model.max_rounds!r}")
+    for layer, a in zip(prob.layers, alpha):
+        if not 1 + a * (thermal.ambient - t0) > 0.0:
+            raise ValueError(f"layer {layer.name!r}: 1 + alpha (ambient - T0) = {1 + a * (thermal.ambient - t0)!r} is not "
+                             "positive: the conductance model does not hold at the ambient temperature")
+    return CheckedElectroThermalModel(thermal=thermal, alpha=alpha, conductance_temperature=t0, tolerance=tolerance,
+                                      max_rounds=max_rounds)
+
+
+def picard_verdict(increments, tolerance: float) -> Optional[str]:
+    """What the increments d_1 .. d_k say after round k: "converged" when d_k <= tolerance, "runaway" when d grew in three
+    consecutive rounds (d_k > d_k-1 > d_k-2 > d_k-3), else None."""
+    d = list(increments)
+    if d[-1] <= tolerance:
+        return "converged"
+    if len(d) >= 4 and d[-1] > d[-2] > d[-3] > d[-4]:
+        return "runaway"
+    return None
+
+
+def _drop_plans(L: SystemMatrix) -> None:
+    """The device plans kept with ``L`` hold A = -P^T L P of L's values: closed before those change."""
+    for plan in L._plans.values():
+        plan.close()
+    L._plans.clear()
+    L._host = None
+
+
+def _solve_electrothermal(prob, meshes, mesh_index_to_layer_index, checked: CheckedElectroThermalModel, cases, fields: bool,
+                          filtered_networks, disconnected_meshes_by_layer, laps: _Laps):
+    """The checked ``cases`` of ``prob``, each converged by the Picard loop on one assembly and one thermal handle:
+    ([Solution], [ThermalReport], [CouplingReport], ThermalEnvelope)."""
+    thermal_model = checked.thermal
+    substituted = [substitute_load_case(prob, case) for case in cases]
+    k, n_layers = len(cases), len(prob.layers)
+    board = index_board(prob, meshes, mesh_index_to_layer_index, filtered_networks, disconnected_meshes_by_layer)
+    _refuse_bare_vertices(board)
+    n_vert = len(board.vindex)
+    if n_vert == 0 or not int(board.tri_offsets[-1]):
+        raise ValueError("the thermal model needs connected copper: the board has no connected mesh with faces")
+    pairs = global_elements(board.filtered_networks, board.node_indexer)
+    laps.lap("indexing")
+    layer_of = board.layer_of
+    n_mesh = len(board.meshes)
+    one_round = all(a == 0.0 for a in checked.alpha)
+    rounds_log = []
+    if laps.timings is not None:
+        laps.timings["rounds"] = rounds_log
+    per_case = []
+    with board.assembled() as (L, _):
+        laps.lap("assembly")
+        resistors = [(element, row) for element, row in pairs if row[0] == "R"]
+        n_potential = L.layout.n_potential
+        n_tri = len(L.tri)
+        thermal = _hip.Thermal(L.dev, n_potential, [thermal_model.kappa[layer_of[i]] for i in range(n_mesh)],
+                               [thermal_model.film[layer_of[i]] for i in range(n_mesh)],
+                               [row[1] for _, row in resistors], [row[2] for _, row in resistors],
+                               [thermal_model.links[element] for element, _ in resistors])
+        coupled = None
+        try:
+            coupled = _hip.Coupled(L.dev, thermal, [checked.alpha[layer_of[i]] for i in range(n_mesh)], thermal_model.ambient,
+                                   checked.conductance_temperature)
+            laps.lap("thermal_setup")
+            element_rows = [row for _, row in pairs]
+            for j, case in enumerate(cases):
+                rows, cols, vals = stamp_load_cases(board.filtered_networks, board.node_indexer, L.shape[0], [case])
+                log.info(f"Load case {j}: the electro-thermal loop")
+                if j > 0:
+                    coupled.reset()
+                increments, iterations, verdict = [], [], None
+                for round_i in range(1, checked.max_rounds + 1):
+                    lap = {}
+                    round_laps = _Laps(lap)
+                    _drop_plans(L)
+                    coupled.revalue()
+                    round_laps.lap("revalue")
+                    plan, V, residual_norms, res, _n_tri, _n_mesh = _solve_block_on_device(L, rows, cols, vals, 1, 1, round_laps)
+                    local, Vu = _gather_element_rows(element_rows, V, _ROW_UNKNOWNS)
+                    flows = element_flows(_case_element_rows(pairs, local, case), Vu[:, 0])
+                    heat = thermal_heat_triples(pairs, [flows]) if thermal_model.element_heat else None
+                    theta, tres = coupled.solve_kkt(plan, heat, rtol=RTOL, max_iter=MAX_ITER)
+                    round_laps.lap("thermal_solve")
+                    increments.append(coupled.update())
+                    round_laps.lap("update")
+                    iterations.append({"electrical": int(res.iterations), "thermal": int(tres.iterations)})
+                    rounds_log.append(dict(lap, case=j, round=round_i))
+                    verdict = "converged" if one_round else picard_verdict(increments, checked.tolerance)
+                    if verdict is not None:
+                        break
+                if verdict == "runaway":
+                    _m, mesh_max, *_rest = thermal.report(1, n_tri, n_vert, fields=False, envelope=False)
+                    hottest = prob.layers[layer_of[int(np.argmax(mesh_max[0]))]].name
+                    first = len(increments) - 3
+                    raise ThermalRunawayError(
+                        f"Load case {j}: thermal runaway -- the largest change of a face temperature grew in rounds {first} to "
+                        f"{len(increments)}: {', '.join(f'{d:.6g} K' for d in increments[-4:])}; the hottest layer is "
+                        f"{hottest!r} at {float(mesh_max[0].max()) + thermal_model.ambient:.6g}.  A current-driven conductor "
+                        "whose heating outgrows its cooling has no steady state")
+                converged = verdict == "converged"
+                if not converged:
+                    warnings.warn(f"Load case {j}: the electro-thermal loop did not converge in {checked.max_rounds} round(s): "
+                                  f"the last change of a face temperature was {increments[-1]:.3e} K, above the tolerance of "
+                                  f"{checked.tolerance:.3e} K", SolverWarning)
+                power = coupled.power_density(plan, n_tri)
+                scale = coupled.get_scale(n_tri, used=True)
+                report = thermal.report(1, n_tri, n_vert, fields=fields, envelope=False)
+                per_case.append((V, residual_norms, res, cols, vals, power, scale, theta, tres, report, heat, increments,
+                                 iterations, converged, flows))
+            laps.lap("loop")
+        finally:
+            if coupled is not None:
+                _drop_plans(L)
+                coupled.close()
+            thermal.close()
+    laps.lap()
+    solutions, couplings, infos = [], [], []
+    for j, (V, residual_norms, res, cols, vals, power, scale, theta, tres, report, heat, increments, iterations,
+            converged, flows) in enumerate(per_case):
+        where = f"Load case {j}: " if k > 1 else ""
+        _warn_if_block_stalled(res, residual_norms, cols, vals, 1)
+        if tres.status != _hip.OK and not tres.rel_residual <= max(RTOL, STALL_WARN_ABOVE):
+            warnings.warn(f"{where}The thermal solve stopped at a relative residual of {tres.rel_residual:.3e}", SolverWarning)
+        solutions.append(_column_solution(board, substituted[j][0], np.ascontiguousarray(V[:, 0]), residual_norms[0], res, power,
+                                          where))
+        infos.append({"iterations": int(tres.iterations), "rel_residual": float(tres.rel_residual), "seconds": float(tres.seconds)})
+        scales = []
+        for layer_i in range(n_layers):
+            tfs = []
+            for _mesh_i, msh, lo, hi in board.layer_meshes(layer_i):
+                tf = mesh.TwoForm(msh)
+                tf.values = scale[lo:hi]
+                tfs.append(tf)
+            scales.append(tfs)
+        renamed = substituted[j][1]
+        case_elements = [e for network in board.filtered_networks for e in renamed.get(id(network), network).elements]
+        couplings.append(CouplingReport(rounds=len(increments), converged=converged, increments=increments,
+                                        conductance_scale=scales, iterations=iterations,
+                                        elements=dict(zip(case_elements, flows))))
+    theta = np.concatenate([c[7] for c in per_case])
+    stacked = [None if not fields and i == 0 else np.concatenate([c[9][i] for c in per_case]) for i in range(5)]
+    heat_val = np.stack([c[10][2].reshape(len(resistors), 2) for c in per_case]) if thermal_model.element_heat else None
+    reports = _thermal_reports(board, thermal_model, substituted, resistors, fields, theta, *stacked, heat_val, infos)
+    env, env_case = envelope_of(theta[:, :n_vert])
+    envelope = _thermal_envelope(board, thermal_model.ambient, env, env_case, reports)
+    laps.lap("solutions")
+    return solutions, reports, couplings, envelope
+
+
+def solve_meshed_electrothermal(prob, meshes, mesh_index_to_layer_index, model: ElectroThermalModel, *, cases=None,
+                                per_case_fields=True, filtered_networks=None, disconnected_meshes_by_layer=None, partition=None,
+                                timings: Optional[dict] = None):
+    """``solve_meshed_thermal`` with the loop closed: the sheet conductance of every face follows its temperature, so the
+    drops, currents and temperatures are those of the warm copper.  ``(Solution, ThermalReport, CouplingReport)``, or for a
+    list of load ``cases`` ``([Solution], [ThermalReport], [CouplingReport], ThermalEnvelope)``.
+
+    Face f of a mesh of layer m conducts ``sigma_m s_f`` with ``s_f = 1 / (1 + alpha_m (Tbar_f - T0))``, ``Tbar_f`` the mean
+    of its corners' temperatures as the ThermalReport's ``face_temperatures`` hold it.  The thermal side stays as it is: by
+    Wiedemann-Franz kappa = L0 T sigma(T) is constant to first order.  Lumped resistors keep their resistance: a
+    temperature coefficient for vias and other lumped elements is out of scope.  The loop is Picard, one load case at a
+    time, from the copper at ambient:
+
+        round k:  L = L0 + sum_f (s_f - 1) sigma_m K_f     the electrical system revalued on the device, same pattern
+                  V_k from the electrical solve, the face powers with sigma_m s_f, theta_k from the thermal solve
+                  d_k = max_f |thetabar_k,f - thetabar_k-1,f|;   s from theta_k;   stop when d_k <= model.tolerance
+
+    With every alpha 0 the loop is one round and the results have the bits of ``solve_meshed_thermal``.  The Solution holds
+    the potentials and power densities of the last electrical solve and the ThermalReport is that of the last thermal
+    solve, whose load came from that electrical solve with the same scale: ``total_loss`` equals ``total_heat`` equals the
+    power the sources deliver in every round, converged or not.  Cases are converged one after another on one assembly and
+    one thermal handle; the envelope is formed from their vertex temperatures by the rule of :func:`envelope_of`.
+
+    :class:`ThermalRunawayError` when the increments grew in three consecutive rounds (a current-driven neck may have no
+    steady state); a SolverWarning and ``converged=False`` when ``model.max_rounds`` end the loop first; ValueError for an
+    invalid model (:func:`check_electrothermal_model`), invalid cases and a ``partition`` over several GPUs before anything
+    reaches the device, and for a face whose 1 + alpha (T - T0) is not finite and positive, found on the device.
+    ``timings`` (a dict) receives the host time of each step in seconds and under "rounds" one dict of laps per round."""
+    _refuse_partition(partition, "electro-thermal solves")
+    checked = check_electrothermal_model(prob, model, filtered_networks)
+    single = cases is None
+    checked_cases = [{}] if single else check_load_cases(prob, cases)
+    solutions, reports, couplings, envelope = _solve_electrothermal(
+        prob, meshes, mesh_index_to_layer_index, checked, checked_cases, bool(per_case_fields) or single, filtered_networks,
+        disconnected_meshes_by_layer, _Laps(timings))
+    if single:
+        return solutions[0], reports[0], couplings[0]
+    return solutions, reports, couplings, envelope
+
+
+def solve_electrothermal(prob, model: ElectroThermalModel, mesher_config: Optional[mesh.Mesher.Config] = None, *, mesher=None,
+                         cases=None, per_case_fields=True, partition=None):
+    """``solve`` with the copper's temperatures and the conductances that follow them (see
+    :func:`solve_meshed_electrothermal`): the board is meshed once."""
+    _refuse_partition(partition, "electro-thermal solves")
+    check_electrothermal_model(prob, model)
+    if cases is not None:
+        cases = check_load_cases(prob, cases)
+    meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
+    return solve_meshed_electrothermal(prob, meshes, mesh_index_to_layer_index, model, cases=cases,
+                                       per_case_fields=per_case_fields)
 
 
 # --------------------------------------------------------------------------------------------
