@@ -1,9 +1,11 @@
 /* padne_hip_probe.h -- TEST-ONLY probes of libpadne_hip.so.  Neither the drop-in boundary (include/padne_hip.h) nor the
- * multi-rank scaffolding (include/padne_hip_test.h): three entries.  padne_test_product drives a single product launcher of the
+ * multi-rank scaffolding (include/padne_hip_test.h): six entries.  padne_test_product drives a single product launcher of the
  * solver on inputs a test chooses, so that every SpMV / SpMM kernel form and epilogue can be held against a host reference;
  * padne_test_kkt_state copies one device array of a padne_kkt plan out, so that every stage of the plan can;
- * padne_test_amg_state copies out what a level of the multigrid hierarchy decided in its setup.  Bound by
- * padne_amd/_hip.py (PROBE_SIGNATURES). */
+ * padne_test_amg_state copies out what a level of the multigrid hierarchy decided in its setup, padne_test_amg_tail hands
+ * out the gathered operator of a row-partitioned hierarchy; padne_test_halo_exchange and padne_test_amg_apply_dist run one
+ * halo exchange and one cycle of a row-partitioned hierarchy on a test's vector.  Bound by padne_amd/_hip.py
+ * (PROBE_SIGNATURES). */
 #ifndef PADNE_HIP_PROBE_H
 #define PADNE_HIP_PROBE_H
 
@@ -83,11 +85,35 @@ int padne_test_kkt_state(const padne_kkt *plan, int32_t which, void *out_host, i
  *   ROOT     int8[n_l]    1 where the independent-set rounds made the vertex a root
  *   SCALARS  double[4]    lambda (the bound of D^-1 A the smoother uses), jac (its damping), 1.0 if the level has a fused
  *                         up-leg operator W, 1.0 if the cycle runs in single precision
+ *   EXPORT   int32[n_export]  row-partitioned levels: the owned vertices of the level whose values the other ranks read,
+ *                         in the order of this rank's exchange segment
+ *   HALO     int64[4]     row-partitioned levels: m (length of every rank's exchange segment on this level), n_export, and
+ *                         of the hierarchy: rows of the gathered tail, first gathered row of this rank's piece
  * AGG and ROOT exist only on levels that were coarsened by a setup that ran under PADNE_AMG_KEEP=1 (the switch makes the
- * setup copy them out of its scratch; without it nothing is kept).  PADNE_E_INVALID when n_bytes is not the size of the
- * array, the array was not kept, the level does not exist, or the hierarchy is a row-partitioned one. */
-enum { PADNE_TEST_AMG_AGG = 0, PADNE_TEST_AMG_ROOT = 1, PADNE_TEST_AMG_SCALARS = 2 };
+ * setup copy them out of its scratch; without it nothing is kept).  On a row-partitioned level they describe the rank's own
+ * block: n_l owned vertices, aggregates numbered within the rank.  PADNE_E_INVALID when n_bytes is not the size of the
+ * array, the array was not kept, the level does not exist, or EXPORT / HALO are asked of a single-GPU hierarchy. */
+enum { PADNE_TEST_AMG_AGG = 0, PADNE_TEST_AMG_ROOT = 1, PADNE_TEST_AMG_SCALARS = 2, PADNE_TEST_AMG_EXPORT = 3,
+       PADNE_TEST_AMG_HALO = 4 };
 int padne_test_amg_state(padne_ctx *ctx, const padne_csr *m, int32_t level, int32_t which, void *out_host, int64_t n_bytes);
+
+/* The gathered operator of the row-partitioned hierarchy of `m` -- the last partitioned level with the rows of all ranks, in
+ * rank order, which every rank holds and coarsens further on its own -- as a BORROWED handle: valid while `m` lives, never to
+ * be destroyed by the caller.  padne_csr_to_host, padne_amg_level, padne_test_amg_state and padne_amg_apply work on it as on
+ * any single-GPU matrix.  PADNE_E_INVALID when `m` has no row-partitioned hierarchy. */
+int padne_test_amg_tail(const padne_csr *m, const padne_csr **tail);
+
+/* ONE halo exchange of the caller's vector through the context's plan (padne_ctx_set_halo): x_host[n_owned] is uploaded
+ * (as_float: converted to float first), halo_exchange_plan / halo_exchange_plan_f32 runs once, and the whole vector comes
+ * back, out_host[n_owned + world * m] (as_float: widened again).  The exchange area is filled with 0xff bytes before the
+ * exchange, so a slot in which nothing arrives reads as NaN; slots behind a rank's n_export are padding and undefined.
+ * Collective: every rank of the team or communicator calls it.  Waits for the context's stream. */
+int padne_test_halo_exchange(padne_ctx *ctx, int32_t as_float, const double *x_host, double *out_host);
+
+/* padne_amg_apply for this rank's rows of a row-partitioned matrix, n_owned x (n_owned + world * m) under the context's halo
+ * plan: builds the hierarchy over all ranks if needed and runs ONE cycle, r_host[n_owned] -> z_host[n_owned], with the
+ * partial-sum slot and the null unit of padne_amg_apply.  Collective.  Waits for the context's stream. */
+int padne_test_amg_apply_dist(padne_ctx *ctx, padne_csr *a, const double *r_host, double *z_host);
 
 #ifdef __cplusplus
 }

@@ -184,12 +184,16 @@ TEST_SIGNATURES = {
 }
 
 # the test probes (include/padne_hip_probe.h): one product launcher of the solver, run once on a test's inputs; one device
-# array of a padne_kkt plan, copied out; what a multigrid level decided in its setup, copied out
+# array of a padne_kkt plan, copied out; what a multigrid level decided in its setup, copied out; the gathered operator, one
+# halo exchange and one cycle of a row-partitioned hierarchy
 PROBE_SIGNATURES = {
     "padne_test_product": (C.c_int, [_P, _P, C.c_int32, _I64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P,
                                      _P, _P, _P, _P, C.c_double, _P, _PF64, _I64, _PI32]),
     "padne_test_kkt_state": (C.c_int, [_P, C.c_int32, _P, _I64]),
     "padne_test_amg_state": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _I64]),
+    "padne_test_amg_tail": (C.c_int, [_P, C.POINTER(_P)]),
+    "padne_test_halo_exchange": (C.c_int, [_P, C.c_int32, _PF64, _PF64]),
+    "padne_test_amg_apply_dist": (C.c_int, [_P, _P, _PF64, _PF64]),
 }
 
 _lib = None
@@ -395,6 +399,16 @@ class Context:
         t = C.c_double(0.0)
         _check(self._lib.padne_ctx_halo_exchange_time(self._h, int(repeats), C.byref(t)))
         return float(t.value)
+
+    def halo_exchange_probe(self, x, m: int, world: int, as_float: bool = False) -> np.ndarray:
+        """TEST-ONLY (``padne_test_halo_exchange``): one exchange of x[n_owned] through this context's halo plan; returns the
+        whole vector [n_owned + world * m] as the device holds it afterwards (collective)."""
+        x = _f64(x)
+        if x.shape != (self.halo_n_owned,):
+            raise ValueError("x must hold the owned values")
+        out = np.empty(x.shape[0] + int(world) * int(m))
+        _check(self._lib.padne_test_halo_exchange(self._h, 1 if as_float else 0, _ptr(x, _PF64), _ptr(out, _PF64)))
+        return out
 
     def lockstep_groups(self) -> int:
         """Groups of right-hand sides this context has advanced in lockstep so far (test introspection)."""
@@ -1459,16 +1473,43 @@ class CsrMatrix:
         _check(self.ctx._lib.padne_csr_split_tiles(self._h, int(level), C.byref(a), C.byref(b)))
         return a.value, b.value
 
-    AMG_STATE = {"AGG": (0, np.int32), "ROOT": (1, np.int8), "SCALARS": (2, np.float64)}
+    AMG_STATE = {"AGG": (0, np.int32), "ROOT": (1, np.int8), "SCALARS": (2, np.float64), "EXPORT": (3, np.int32),
+                 "HALO": (4, np.int64)}
 
     def amg_state(self, level: int, which: str) -> np.ndarray:
         """TEST-ONLY (``padne_test_amg_state``): what level ``level`` of the cached hierarchy decided in its setup -- "AGG",
-        "ROOT" (both kept only under PADNE_AMG_KEEP=1) or "SCALARS" = (lambda, jac, has W, single precision)."""
+        "ROOT" (both kept only under PADNE_AMG_KEEP=1), "SCALARS" = (lambda, jac, has W, single precision) or, on a level of
+        a row-partitioned hierarchy, "EXPORT" (the exported owned vertices) and "HALO" = (m, n_export, tail_n, tail_off)."""
         sel, dtype = self.AMG_STATE[which]
-        n = 4 if which == "SCALARS" else self.amg_shapes()[int(level)]["A"][0]
+        if which in ("SCALARS", "HALO"):
+            n = 4
+        elif which == "EXPORT":
+            n = int(self.amg_state(level, "HALO")[1])
+        else:
+            n = self.amg_shapes()[int(level)]["A"][0]
         out = np.empty(n, dtype=dtype)
         _check(self.ctx._lib.padne_test_amg_state(self.ctx._h, self._h, int(level), sel, out.ctypes.data_as(_P), out.nbytes))
         return out
+
+    def amg_tail(self) -> "CsrMatrix":
+        """TEST-ONLY (``padne_test_amg_tail``): the gathered operator of this matrix's row-partitioned hierarchy, as a
+        borrowed handle -- it belongs to the hierarchy and is not destroyed with the wrapper."""
+        h = _P()
+        _check(self.ctx._lib.padne_test_amg_tail(self._h, C.byref(h)))
+        t = CsrMatrix(self.ctx, h)
+        t._borrowed = True
+        t._lender = self             # the hierarchy lives as long as its matrix
+        return t
+
+    def amg_apply_dist(self, r) -> np.ndarray:
+        """TEST-ONLY (``padne_test_amg_apply_dist``): z = M^-1 r on this rank's rows, one cycle of the row-partitioned
+        hierarchy (collective)."""
+        r = _f64(r)
+        if r.shape != (self.shape[0],):
+            raise ValueError("dimension mismatch")
+        z = np.empty_like(r)
+        _check(self.ctx._lib.padne_test_amg_apply_dist(self.ctx._h, self._h, _ptr(r, _PF64), _ptr(z, _PF64)))
+        return z
 
     def amg_apply(self, r) -> np.ndarray:
         """z = M^-1 r: one multigrid V-cycle (the preconditioner of solve_spd)."""

@@ -4277,8 +4277,21 @@ static int amg_setup_dist(padne_ctx *ctx, padne_csr *A0) {
         Scratch sc(ctx);
         int *agg = nullptr, n_agg = 0;
         double lambda_f = 2.0, lambda_g = 2.0;
-        if ((rc = csr_build_dinv(ctx, blk)) == PADNE_OK && (rc = aggregate(ctx, sc, blk, &agg, &n_agg, &lambda_f)) == PADNE_OK)
+        signed char *mis_state = nullptr;
+        if ((rc = csr_build_dinv(ctx, blk)) == PADNE_OK &&
+            (rc = aggregate(ctx, sc, blk, &agg, &n_agg, &lambda_f, nullptr, nullptr, nullptr, nullptr, &mis_state)) == PADNE_OK)
             rc = gershgorin(ctx, blk, &lambda_g, false);
+        if (rc == PADNE_OK && ctx->opt.amg_keep && Lr.n > 0) {
+            // tests only, as in amg_setup: the map and the roots outlive the level's scratch (nothing without the switch)
+            Lr.agg_keep = (int *)pool_alloc(ctx, sizeof(int) * (size_t)Lr.n);
+            Lr.state_keep = (signed char *)pool_alloc(ctx, (size_t)Lr.n);
+            if (Lr.agg_keep == nullptr || Lr.state_keep == nullptr) rc = PADNE_E_NOMEM;
+            hipError_t he = rc == PADNE_OK ? hipMemcpyAsync(Lr.agg_keep, agg, sizeof(int) * (size_t)Lr.n, hipMemcpyDeviceToDevice, s)
+                                           : hipSuccess;
+            if (rc == PADNE_OK && he == hipSuccess)
+                he = hipMemcpyAsync(Lr.state_keep, mis_state, (size_t)Lr.n, hipMemcpyDeviceToDevice, s);
+            if (he != hipSuccess) { set_error("multigrid setup: %s", hipGetErrorString(he)); rc = PADNE_E_HIP; }
+        }
         if (rc != PADNE_OK) { padne_csr_destroy(blk); break; }
         std::vector<double> ag = {(double)n_agg}, ags;
         if ((rc = host_allgather(ctx, ag, ags)) != PADNE_OK) { padne_csr_destroy(blk); break; }
@@ -4792,12 +4805,26 @@ extern "C" int padne_test_amg_state(padne_ctx *ctx, const padne_csr *m, int32_t 
                                     int64_t n_bytes) {
     PADNE_REQUIRE(ctx && m, "null argument");
     const padne::Amg *amg = (const padne::Amg *)m->amg;
-    PADNE_REQUIRE(amg != nullptr && !amg->dist, "no single-GPU multigrid hierarchy on this matrix");
+    PADNE_REQUIRE(amg != nullptr, "no multigrid hierarchy on this matrix");
     PADNE_REQUIRE(level >= 0 && level < (int)amg->levels.size(), "no such multigrid level");
-    PADNE_REQUIRE(which >= PADNE_TEST_AMG_AGG && which <= PADNE_TEST_AMG_SCALARS, "unknown array");
+    PADNE_REQUIRE(which >= PADNE_TEST_AMG_AGG && which <= PADNE_TEST_AMG_HALO, "unknown array");
     const padne::AmgLevel &L = amg->levels[(size_t)level];
     PADNE_HIP_CHECK(hipSetDevice(ctx->device));
     PADNE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (which == PADNE_TEST_AMG_EXPORT || which == PADNE_TEST_AMG_HALO) {
+        PADNE_REQUIRE(amg->dist, "the level has an exchange plan only in a row-partitioned hierarchy");
+        if (which == PADNE_TEST_AMG_HALO) {
+            PADNE_REQUIRE(n_bytes == (int64_t)(4 * sizeof(int64_t)) && out_host != nullptr, "byte count of the array");
+            const int64_t h[4] = {(int64_t)L.halo.m, (int64_t)L.halo.n_export, (int64_t)amg->tail_n, (int64_t)amg->tail_off};
+            memcpy(out_host, h, sizeof(h));
+            return PADNE_OK;
+        }
+        PADNE_REQUIRE((size_t)L.halo.n_export == L.export_host.size(), "export list of the level");
+        const size_t bytes = sizeof(int32_t) * L.export_host.size();
+        PADNE_REQUIRE(n_bytes == (int64_t)bytes && (out_host != nullptr || bytes == 0), "byte count of the array");
+        if (bytes > 0) memcpy(out_host, L.export_host.data(), bytes);
+        return PADNE_OK;
+    }
     if (which == PADNE_TEST_AMG_SCALARS) {
         PADNE_REQUIRE(n_bytes == (int64_t)(4 * sizeof(double)) && out_host != nullptr, "byte count of the array");
         const double h[4] = {L.lambda, L.jac, L.W != nullptr ? 1.0 : 0.0, amg->f32 ? 1.0 : 0.0};
@@ -4814,6 +4841,15 @@ extern "C" int padne_test_amg_state(padne_ctx *ctx, const padne_csr *m, int32_t 
         int8_t *f = (int8_t *)out_host;
         for (long long i = 0; i < L.n; ++i) f[i] = f[i] == 1 ? 1 : 0;
     }
+    return PADNE_OK;
+}
+
+// ---- test entry: the gathered operator below the partitioned levels, borrowed (include/padne_hip_probe.h) ----------------
+extern "C" int padne_test_amg_tail(const padne_csr *m, const padne_csr **tail) {
+    PADNE_REQUIRE(m && tail, "null argument");
+    const padne::Amg *amg = (const padne::Amg *)m->amg;
+    PADNE_REQUIRE(amg != nullptr && amg->dist && amg->tail != nullptr, "no row-partitioned multigrid hierarchy on this matrix");
+    *tail = amg->tail;
     return PADNE_OK;
 }
 

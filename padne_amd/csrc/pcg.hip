@@ -626,6 +626,44 @@ extern "C" int padne_ctx_halo_exchange_time(padne_ctx *ctx, int32_t repeats, dou
     *seconds_out = (double)ms * 1e-3 / repeats;
     return PADNE_OK;
 }
+// (probe header) ONE halo exchange of the caller's vector through the context's plan, in double or in single precision (the
+// values are converted on the host: the exchange itself moves them as they are).  Collective.
+extern "C" int padne_test_halo_exchange(padne_ctx *ctx, int32_t as_float, const double *x_host, double *out_host) {
+    using namespace padne;
+    PADNE_REQUIRE(ctx && x_host && out_host, "null argument");
+    PADNE_REQUIRE(ctx->halo_on, "no halo plan on this context");
+    PADNE_HIP_CHECK(hipSetDevice(ctx->device));
+    const size_t n_owned = (size_t)ctx->halo_n_owned, n = n_owned + (size_t)ctx->world * (size_t)ctx->halo_m;
+    const size_t elem = as_float ? sizeof(float) : sizeof(double);
+    HaloPlan plan;
+    plan.n_owned = ctx->halo_n_owned;
+    plan.m = ctx->halo_m;
+    plan.n_export = ctx->halo_n_export;
+    plan.export_idx = ctx->halo_export;
+    std::vector<float> h32(as_float ? n : 0);
+    for (size_t i = 0; as_float && i < n_owned; ++i) h32[i] = (float)x_host[i];
+    void *v = pool_alloc(ctx, elem * (n ? n : 1));
+    if (v == nullptr) return PADNE_E_NOMEM;
+    int rc = PADNE_OK;
+    hipError_t e = hipMemsetAsync(v, 0xff, elem * n, ctx->stream);      // (a slot nothing arrives in reads as NaN)
+    if (e == hipSuccess && n_owned > 0)
+        e = hipMemcpyAsync(v, as_float ? (const void *)h32.data() : (const void *)x_host, elem * n_owned, hipMemcpyHostToDevice,
+                           ctx->stream);
+    if (e == hipSuccess) rc = as_float ? halo_exchange_plan_f32(ctx, plan, (float *)v, nullptr) : halo_exchange_plan(ctx, plan, (double *)v, nullptr);
+    if (e == hipSuccess && rc == PADNE_OK && n > 0)
+        e = hipMemcpyAsync(as_float ? (void *)h32.data() : (void *)out_host, v, elem * n, hipMemcpyDeviceToHost, ctx->stream);
+    const hipError_t es = hipStreamSynchronize(ctx->stream);      // (also on the way out of a failure: the buffer goes back to the pool)
+    if (e == hipSuccess) e = es;
+    pool_free(ctx, v);
+    if (e != hipSuccess) {
+        set_error("halo exchange failed: %s", hipGetErrorString(e));
+        return PADNE_E_HIP;
+    }
+    PADNE_TRY(rc);
+    PADNE_TRY(comm_p2p_check(ctx));
+    for (size_t i = 0; as_float && i < n; ++i) out_host[i] = (double)h32[i];
+    return PADNE_OK;
+}
 namespace padne {
 
 // q = A v for a vector whose exchange area has to be refreshed first: the halo goes out, the interior tiles of the product
@@ -1903,6 +1941,35 @@ extern "C" int padne_amg_apply(padne_ctx *ctx, padne_csr *a, const double *r_hos
     (void)hipFree(r);
     (void)hipFree(z);
     if (rc == PADNE_E_HIP) set_error("multigrid apply failed: %s", hipGetErrorString(hipGetLastError()));
+    return rc;
+}
+
+// (probe header) the same for this rank's rows of a row-partitioned matrix under the context's halo plan: one cycle of the
+// hierarchy over all ranks, owned pieces of r in and of z out.  Collective.
+extern "C" int padne_test_amg_apply_dist(padne_ctx *ctx, padne_csr *a, const double *r_host, double *z_host) {
+    PADNE_REQUIRE(ctx && a && r_host && z_host, "null argument");
+    PADNE_REQUIRE(ctx->halo_on && a->n_rows == ctx->halo_n_owned &&
+                      a->n_cols == ctx->halo_n_owned + (long long)ctx->world * ctx->halo_m && a->n_cols != a->n_rows,
+                  "the matrix must be owned rows x [owned | world * m] columns under the context's halo plan");
+    PADNE_HIP_CHECK(hipSetDevice(ctx->device));
+    PADNE_TRY(amg_setup(ctx, a));
+    const size_t bytes = sizeof(double) * (size_t)(a->n_rows > 0 ? a->n_rows : 1), used = sizeof(double) * (size_t)a->n_rows;
+    double *r = nullptr, *z = nullptr;
+    PADNE_HIP_CHECK(hipMalloc((void **)&r, bytes));
+    if (hipMalloc((void **)&z, bytes) != hipSuccess) {
+        (void)hipFree(r);
+        set_error("hipMalloc failed");
+        return PADNE_E_NOMEM;
+    }
+    int rc = PADNE_OK;
+    if (used > 0 && hipMemcpyAsync(r, r_host, used, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = PADNE_E_HIP;
+    if (rc == PADNE_OK) rc = amg_apply(ctx, a, r, z, slot(ctx, SLOT_TMP), nullptr);
+    if (rc == PADNE_OK && used > 0 && hipMemcpyAsync(z_host, z, used, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = PADNE_E_HIP;
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == PADNE_OK) rc = PADNE_E_HIP;
+    (void)hipFree(r);
+    (void)hipFree(z);
+    if (rc == PADNE_E_HIP) set_error("multigrid apply failed: %s", hipGetErrorString(hipGetLastError()));
+    if (rc == PADNE_OK) rc = comm_p2p_check(ctx);
     return rc;
 }
 
