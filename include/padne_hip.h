@@ -680,6 +680,78 @@ int padne_coupled_solve_kkt(padne_ctx *ctx, padne_coupled *cp, padne_kkt *plan, 
  * scale of the face (one product on the device) */
 int padne_coupled_power_density(padne_ctx *ctx, padne_coupled *cp, padne_kkt *plan, double *out_host);
 
+/* ---- transient: the copper's temperature rise under a schedule of load cases ---------------------
+ * No reference counterpart ("Transient").  Backward Euler on C dtheta/dt + A theta = b(t), A the thermal handle's
+ * operator and C = diag(c_m M_v) the lumped heat capacity of the vertices, capacity[m] = c_m [J / (K length^2)] the areal heat
+ * capacity of mesh m; internal nodes carry none.  One step of length dt for column c running load case j = case_of_col[c]
+ * (-1: sources off), every expression rounded as written:
+ *     Cv[v] = c_m(v) * M_v;   cdt[v] = Cv[v] / dt
+ *     S = A with S_vv = A_vv + cdt[v] for a vertex v (one rounded sum); every other entry has A's bits
+ *     rhs[c][v] = cdt[v] * theta_n[c][v] + B[j][v] at a vertex (without the sum when j = -1); B[j][v], or 0.0, elsewhere
+ *     S theta_{n+1}[c] = rhs[c]  by padne_solve_spd_dev with theta_n[c] as the initial guess
+ * K and the links annihilate constants: sum_v Cv (theta_{n+1} - theta_n) / dt + sum_v film M_v theta_{n+1} = sum_v B[j]_v.
+ * The handle borrows the thermal handle `th` (which must outlive it; destroy this one first) and owns Cv, S (A's pattern,
+ * its own values, the dt they hold), the load table B[n_case][n_potential], the state theta[n_cols][n_potential], the
+ * running envelope and the step counter.  The coupling is one-way: the face powers do not follow the temperature.
+ * PADNE_E_INVALID for a null or foreign handle, an n_mesh that is not the mesh's and a capacity that is not finite and
+ * positive; a refused call leaves the handle as it was. */
+typedef struct padne_transient padne_transient;
+int padne_transient_create(padne_ctx *ctx, padne_thermal *th, int32_t n_mesh, const double *capacity, padne_transient **out);
+int padne_transient_destroy(padne_transient *tr);     /* NULL is accepted */
+/* Cv_out[n_vert] = Cv */
+int padne_transient_capacity(padne_ctx *ctx, const padne_transient *tr, double *Cv_out);
+/* The load table: B[j] = the heat load padne_thermal_load forms of column j of the same arguments, bit for bit (n_case
+ * 1 .. 4096; the triples' columns name cases).  The face powers pass through the thermal handle's array: it then holds no
+ * solve to report on.  A schedule under way ends: padne_transient_start follows. */
+int padne_transient_loads(padne_ctx *ctx, padne_transient *tr, int32_t n_case, const double *face_power_host, int64_t n_heat,
+                          const int64_t *heat_node, const int32_t *heat_col, const double *heat_val);
+/* The same with the face powers of the block the last padne_kkt_finish_block left on the device of `plan`, as
+ * padne_thermal_solve_kkt computes them: they never visit the host.  Preconditions and errors as there. */
+int padne_transient_loads_kkt(padne_ctx *ctx, padne_transient *tr, padne_kkt *plan, int32_t n_case, int64_t n_heat,
+                              const int64_t *heat_node, const int32_t *heat_col, const double *heat_val);
+/* b_out[n_case][n_potential] = B, for tests */
+int padne_transient_load_vectors(padne_ctx *ctx, const padne_transient *tr, int32_t n_case, double *b_out);
+/* The state at time 0 for n_cols (1 .. 4096) columns: a column with initial_case[c] = -1 starts at ambient, exact zeros; one
+ * with initial_case[c] = j from the steady state A theta = B[j], all such columns in one block solve on A from zero as
+ * padne_thermal_solve does (opts and info as there).  The envelope becomes theta_0 with step 0, the step counter and the
+ * time 0.  PADNE_E_INVALID before padne_transient_loads and for a case out of range.  PADNE_E_NOTCONVERGED keeps the iterate. */
+int padne_transient_start(padne_ctx *ctx, padne_transient *tr, int32_t n_cols, const int32_t *initial_case,
+                          const padne_solve_opts *opts, padne_solve_info *info);
+/* S revalued for dt, as a borrowed handle (do not destroy), for tests */
+int padne_transient_matrix(padne_transient *tr, double dt, const padne_csr **csr_out);
+/* rhs_out[n_cols][n_potential]: the right-hand side the next step of length dt would solve; the state does not advance */
+int padne_transient_rhs(padne_ctx *ctx, padne_transient *tr, double dt, const int32_t *case_of_col, double *rhs_out);
+/* Advance every column by n_steps steps of length dt (finite and positive) under case_of_col[n_cols].  If the bits of dt
+ * differ from the held ones S is revalued in place and what was derived from its values (1 / diagonal, single-precision
+ * copies, multigrid hierarchy) is dropped; its x-window plan depends on the pattern only and stays.  Otherwise the hierarchy
+ * built at the first step of a dt serves every later step -- the point of the design: step_setup_seconds_out is 0 on all
+ * but that step.  opts null: rtol 1e-12, the multigrid preconditioner; bit 0 of opts.flags is forced on.  A step that ends
+ * with PADNE_E_NOTCONVERGED keeps its iterate and the run goes on (the call then returns that code); info: the iterations
+ * and seconds summed over the steps, the worst residuals.  Per-step results are written on the device and downloaded once
+ * at the end: no host wait is added per step beyond the solver's own convergence polls.  Per step k, column c, mesh m:
+ * mesh_max_out[k][c][m] and mesh_vertex_out[k][c][m] by the rule of padne_thermal_report (the lowest vertex on a tie,
+ * -infinity and -1 for a mesh without vertices), mesh_stored_out = sum Cv theta [J] and mesh_loss_out = sum (film M_v) theta
+ * [W] over the mesh's vertices, in the fixed order of padne_thermal_report's sums: two calls give the same bits.
+ * probe_out[k][c][p] = theta[c][probe_idx[p]], exact bits (n_probe may be 0; an index may name an internal node).  After
+ * every step the envelope takes, per column and vertex, a theta strictly greater than the held one together with the
+ * global number of the step: the earliest step keeps a tie.  step_iterations_out[n_steps], step_residual_out[n_steps],
+ * step_seconds_out[n_steps] (the iteration loop) and step_setup_seconds_out[n_steps]: of each step's solve (each may be null).  PADNE_E_INVALID before padne_transient_start,
+ * for a dt that is not finite and positive, n_steps < 1, and a case or probe index out of range. */
+int padne_transient_run(padne_ctx *ctx, padne_transient *tr, double dt, int32_t n_steps, const int32_t *case_of_col,
+                        int32_t n_probe, const int64_t *probe_idx, const padne_solve_opts *opts, double *mesh_max_out,
+                        int64_t *mesh_vertex_out, double *mesh_stored_out, double *mesh_loss_out, double *probe_out,
+                        int32_t *step_iterations_out, double *step_residual_out, double *step_seconds_out,
+                        double *step_setup_seconds_out, padne_solve_info *info);
+/* the per-mesh results of padne_transient_run for the current state, [n_cols][n_mesh]; the envelope is left alone */
+int padne_transient_report(padne_ctx *ctx, padne_transient *tr, double *mesh_max_out, int64_t *mesh_vertex_out,
+                           double *mesh_stored_out, double *mesh_loss_out);
+/* theta_out[n_cols][n_potential]: the current state */
+int padne_transient_state(padne_ctx *ctx, const padne_transient *tr, double *theta_out);
+/* env_out[n_cols][n_vert] and env_step_out[n_cols][n_vert]: the running envelope and the steps that attained it */
+int padne_transient_envelope(padne_ctx *ctx, const padne_transient *tr, double *env_out, int32_t *env_step_out);
+/* steps and time since the start, multigrid hierarchies built for S since creation (each may be null) */
+int padne_transient_clock(const padne_transient *tr, int64_t *step_out, double *time_out, int64_t *hierarchies_out);
+
 /* ---- introspection for benchmarks ---------------------------------------------------------- */
 /* algorithmic bytes of one CSR SpMV: 12*nnz + 20*n_rows + 4   */
 int64_t padne_spmv_algorithmic_bytes(const padne_csr *m);

@@ -157,6 +157,21 @@ SIGNATURES = {
                                           C.POINTER(SolveInfo)]),
     "padne_thermal_face_power": (C.c_int, [_P, _P, C.c_int32, _PF64]),
     "padne_thermal_report": (C.c_int, [_P, _P, C.c_int32, _I64, _I64, C.c_int32, _PF64, _PF64, _PI64, _PF64, _PF64, _PF64, _PI32]),
+    "padne_transient_create": (C.c_int, [_P, _P, C.c_int32, _PF64, C.POINTER(_P)]),
+    "padne_transient_destroy": (C.c_int, [_P]),
+    "padne_transient_capacity": (C.c_int, [_P, _P, _PF64]),
+    "padne_transient_loads": (C.c_int, [_P, _P, C.c_int32, _PF64, _I64, _PI64, _PI32, _PF64]),
+    "padne_transient_loads_kkt": (C.c_int, [_P, _P, _P, C.c_int32, _I64, _PI64, _PI32, _PF64]),
+    "padne_transient_load_vectors": (C.c_int, [_P, _P, C.c_int32, _PF64]),
+    "padne_transient_start": (C.c_int, [_P, _P, C.c_int32, _PI32, C.POINTER(SolveOpts), C.POINTER(SolveInfo)]),
+    "padne_transient_matrix": (C.c_int, [_P, C.c_double, C.POINTER(_P)]),
+    "padne_transient_rhs": (C.c_int, [_P, _P, C.c_double, _PI32, _PF64]),
+    "padne_transient_run": (C.c_int, [_P, _P, C.c_double, C.c_int32, _PI32, C.c_int32, _PI64, C.POINTER(SolveOpts), _PF64, _PI64,
+                                      _PF64, _PF64, _PF64, _PI32, _PF64, _PF64, _PF64, C.POINTER(SolveInfo)]),
+    "padne_transient_report": (C.c_int, [_P, _P, _PF64, _PI64, _PF64, _PF64]),
+    "padne_transient_state": (C.c_int, [_P, _P, _PF64]),
+    "padne_transient_envelope": (C.c_int, [_P, _P, _PF64, _PI32]),
+    "padne_transient_clock": (C.c_int, [_P, C.POINTER(_I64), C.POINTER(C.c_double), C.POINTER(_I64)]),
     "padne_coupled_create": (C.c_int, [_P, _P, _P, C.c_int32, _PF64, C.c_double, C.c_double, C.POINTER(_P)]),
     "padne_coupled_destroy": (C.c_int, [_P]),
     "padne_coupled_reset": (C.c_int, [_P, _P]),
@@ -1140,6 +1155,153 @@ class Thermal:
             _ptr(vert, _PI64), _ptr(heat, _PF64), _ptr(loss, _PF64), None if env is None else _ptr(env, _PF64),
             None if env_case is None else _ptr(env_case, _PI32)))
         return mean, mesh_max, vert, heat, loss, env, env_case
+
+
+class Transient:
+    """``padne_transient``: backward-Euler steps of C dtheta/dt + A theta = b(t) on a :class:`Thermal` handle
+    (include/padne_hip.h, "transient").  ``capacity`` per mesh [J / (K mesh-unit^2)].  Holds the lumped capacities, the
+    step matrix S with the dt it was formed for, the load table, the state of every column and its running envelope.
+    Close it before ``thermal``."""
+
+    def __init__(self, thermal: "Thermal", capacity):
+        self.ctx, self.thermal = thermal.ctx, thermal
+        cap = _f64(capacity).reshape(-1)
+        h = _P()
+        _check(self.ctx._lib.padne_transient_create(self.ctx._h, thermal._h, cap.shape[0], _ptr(cap, _PF64), C.byref(h)))
+        self._h = h
+        self.n_potential, self.n_mesh, self.n_case, self.n_cols = thermal.n_potential, thermal.n_mesh, 0, 0
+
+    def close(self):
+        if getattr(self, "_h", None) and self.ctx._h:
+            self.ctx._lib.padne_transient_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def capacity(self, n_vert: int) -> np.ndarray:
+        """Cv (n_vert,) [J/K]."""
+        out = np.empty(int(n_vert), dtype=np.float64)
+        _check(self.ctx._lib.padne_transient_capacity(self.ctx._h, self._h, _ptr(out, _PF64)))
+        return out
+
+    def loads(self, face_power, heat=None) -> None:
+        """The load table from the face powers (n_case, n_tri) [W] and the node-heat triples (node, case, watts):
+        ``Thermal.load``'s bits."""
+        P = _f64(face_power)
+        if P.ndim != 2 or P.shape[0] < 1:
+            raise ValueError("face_power must have shape (n_case, n_tri) with n_case >= 1")
+        node, col, val = Thermal._heat(heat)
+        _check(self.ctx._lib.padne_transient_loads(self.ctx._h, self._h, P.shape[0], _ptr(P, _PF64), node.shape[0],
+                                                   _ptr(node, _PI64), _ptr(col, _PI32), _ptr(val, _PF64)))
+        self.n_case = P.shape[0]
+
+    def loads_kkt(self, plan: "KktPlan", n_case: int, heat=None) -> None:
+        """``loads`` with the face powers of every column of the block ``plan``'s last ``finish_block`` left on the device."""
+        node, col, val = Thermal._heat(heat)
+        _check(self.ctx._lib.padne_transient_loads_kkt(self.ctx._h, self._h, plan._h, int(n_case), node.shape[0],
+                                                       _ptr(node, _PI64), _ptr(col, _PI32), _ptr(val, _PF64)))
+        self.n_case = int(n_case)
+
+    def load_vectors(self) -> np.ndarray:
+        """The load table (n_case, n_potential)."""
+        out = np.empty((self.n_case, self.n_potential), dtype=np.float64)
+        _check(self.ctx._lib.padne_transient_load_vectors(self.ctx._h, self._h, self.n_case, _ptr(out, _PF64)))
+        return out
+
+    @staticmethod
+    def _cases(cases) -> np.ndarray:
+        return _i32([-1 if c is None else int(c) for c in cases]).reshape(-1)
+
+    def start(self, initial, *, rtol=1e-12, max_iter=200000, precond="amg") -> SolveResult:
+        """The state at time 0, one column per entry of ``initial``: None or -1 = ambient, j = the steady state of case j.
+        Returns the SolveResult of the block solve for the steady states (all zeros when no column needs one)."""
+        ini = self._cases(initial)
+        opts = CsrMatrix._opts(rtol, 0.0, max_iter, 0, False, precond=precond)
+        info = SolveInfo()
+        rc = self.ctx._lib.padne_transient_start(self.ctx._h, self._h, ini.shape[0], _ptr(ini, _PI32), C.byref(opts), C.byref(info))
+        if rc != OK and rc != E_NOTCONVERGED:
+            _check(rc)
+        self.n_cols = ini.shape[0]
+        return SolveResult(None, info.iterations, info.restarts, info.rel_residual, info.abs_residual, info.solve_seconds,
+                           info.status, info.spmv_seconds, info.precond_setup_seconds, info.operator_complexity, info.levels,
+                           info.precond_fallbacks)
+
+    def matrix(self, dt: float) -> "CsrMatrix":
+        """Borrowed view of S revalued for ``dt`` (valid while the handle lives and until the next change of dt)."""
+        h = _P()
+        _check(self.ctx._lib.padne_transient_matrix(self._h, float(dt), C.byref(h)))
+        m = CsrMatrix(self.ctx, h)
+        m._borrowed = True
+        return m
+
+    def rhs(self, dt: float, case_of_col) -> np.ndarray:
+        """The right-hand side (n_cols, n_potential) the next step of length ``dt`` would solve."""
+        cases = self._cases(case_of_col)
+        if cases.shape[0] != self.n_cols:
+            raise ValueError("one case per column of the start")
+        out = np.empty((self.n_cols, self.n_potential), dtype=np.float64)
+        _check(self.ctx._lib.padne_transient_rhs(self.ctx._h, self._h, float(dt), _ptr(cases, _PI32), _ptr(out, _PF64)))
+        return out
+
+    def run(self, dt: float, n_steps: int, case_of_col, probes=(), *, rtol=1e-12, max_iter=200000, precond="amg") -> dict:
+        """``n_steps`` steps of length ``dt`` under ``case_of_col`` (None or -1: sources off).  A dict of per-step arrays:
+        ``max``, ``vertex``, ``stored``, ``loss`` (n_steps, n_cols, n_mesh), ``probes`` (n_steps, n_cols, n_probe),
+        ``iterations``, ``rel_residual``, ``seconds``, ``setup_seconds`` (n_steps,), and ``result`` the SolveResult over the run."""
+        cases, probe = self._cases(case_of_col), _i64(probes).reshape(-1)
+        if cases.shape[0] != self.n_cols:
+            raise ValueError("one case per column of the start")
+        n_steps, k, m = int(n_steps), self.n_cols, self.n_mesh
+        shape = (max(n_steps, 0), k, m)
+        top, stored, loss = (np.empty(shape, dtype=np.float64) for _ in range(3))
+        vert = np.empty(shape, dtype=np.int64)
+        trace = np.empty((max(n_steps, 0), k, probe.shape[0]), dtype=np.float64)
+        its = np.zeros(max(n_steps, 0), dtype=np.int32)
+        rel, secs, setup = (np.zeros(max(n_steps, 0), dtype=np.float64) for _ in range(3))
+        opts = CsrMatrix._opts(rtol, 0.0, max_iter, 0, True, precond=precond)
+        info = SolveInfo()
+        rc = self.ctx._lib.padne_transient_run(
+            self.ctx._h, self._h, float(dt), n_steps, _ptr(cases, _PI32), probe.shape[0], _ptr(probe, _PI64), C.byref(opts),
+            _ptr(top, _PF64), _ptr(vert, _PI64), _ptr(stored, _PF64), _ptr(loss, _PF64), _ptr(trace, _PF64), _ptr(its, _PI32),
+            _ptr(rel, _PF64), _ptr(secs, _PF64), _ptr(setup, _PF64), C.byref(info))
+        if rc != OK and rc != E_NOTCONVERGED:
+            _check(rc)
+        res = SolveResult(None, info.iterations, info.restarts, info.rel_residual, info.abs_residual, info.solve_seconds,
+                          info.status, info.spmv_seconds, info.precond_setup_seconds, info.operator_complexity, info.levels,
+                          info.precond_fallbacks)
+        return {"max": top, "vertex": vert, "stored": stored, "loss": loss, "probes": trace, "iterations": its,
+                "rel_residual": rel, "seconds": secs, "setup_seconds": setup, "result": res}
+
+    def report(self):
+        """Of the current state: (max, vertex, stored, loss), each (n_cols, n_mesh)."""
+        shape = (self.n_cols, self.n_mesh)
+        top, stored, loss = (np.empty(shape, dtype=np.float64) for _ in range(3))
+        vert = np.empty(shape, dtype=np.int64)
+        _check(self.ctx._lib.padne_transient_report(self.ctx._h, self._h, _ptr(top, _PF64), _ptr(vert, _PI64), _ptr(stored, _PF64),
+                                                    _ptr(loss, _PF64)))
+        return top, vert, stored, loss
+
+    def state(self) -> np.ndarray:
+        """theta (n_cols, n_potential)."""
+        out = np.empty((self.n_cols, self.n_potential), dtype=np.float64)
+        _check(self.ctx._lib.padne_transient_state(self.ctx._h, self._h, _ptr(out, _PF64)))
+        return out
+
+    def envelope(self, n_vert: int):
+        """(the largest theta seen (n_cols, n_vert), the first step that attained it (n_cols, n_vert) int32)."""
+        env = np.empty((self.n_cols, int(n_vert)), dtype=np.float64)
+        step = np.empty((self.n_cols, int(n_vert)), dtype=np.int32)
+        _check(self.ctx._lib.padne_transient_envelope(self.ctx._h, self._h, _ptr(env, _PF64), _ptr(step, _PI32)))
+        return env, step
+
+    def clock(self) -> tuple:
+        """(steps since the start, their time, hierarchies built for S since creation)."""
+        step, hier, t = _I64(), _I64(), C.c_double()
+        _check(self.ctx._lib.padne_transient_clock(self._h, C.byref(step), C.byref(t), C.byref(hier)))
+        return int(step.value), float(t.value), int(hier.value)
 
 
 class Coupled:

@@ -184,18 +184,7 @@ static int coupled_require(const char *entry, padne_ctx *ctx, const padne_couple
 }
 
 // what was derived from L's values: rebuilt on next use from the values in place
-static void coupled_invalidate(padne_csr *L) {
-    if (L->amg != nullptr) amg_destroy(L->amg);
-    L->amg = nullptr;
-    if (L->owner != nullptr) {
-        pool_free(L->owner, L->dinv);
-        pool_free(L->owner, L->vals32);
-        pool_free(L->owner, L->dinv32);
-    }
-    L->dinv = nullptr;
-    L->vals32 = nullptr;
-    L->dinv32 = nullptr;
-}
+static void coupled_invalidate(padne_csr *L) { csr_invalidate_values(L); }
 
 static void coupled_free(padne_coupled *cp) {
     if (cp == nullptr) return;

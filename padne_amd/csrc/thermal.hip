@@ -287,7 +287,7 @@ __global__ __launch_bounds__(256) void thermal_fold_kernel(const int n_mesh, con
 }
 
 // tiles of 256 items per segment of `off`: tile[m] .. tile[m + 1] are segment m's
-static std::vector<long long> thermal_tiles(const std::vector<int64_t> &off) {
+std::vector<long long> thermal_tiles(const std::vector<int64_t> &off) {
     std::vector<long long> tile(off.size(), 0);
     for (size_t m = 0; m + 1 < off.size(); ++m) tile[m + 1] = tile[m] + (off[m + 1] - off[m] + 255) / 256;
     return tile;
@@ -326,7 +326,7 @@ static int thermal_reserve(padne_ctx *ctx, double **p, size_t *cap, size_t count
     return PADNE_OK;
 }
 
-static int thermal_require(const char *entry, padne_ctx *ctx, const padne_thermal *th) {
+int thermal_require(const char *entry, padne_ctx *ctx, const padne_thermal *th) {
     PADNE_REQUIRE(ctx && th, "null argument");
     PADNE_REQUIRE(th->ctx == ctx, (std::string(entry) + ": the handle belongs to another context").c_str());
     return PADNE_OK;
@@ -334,7 +334,7 @@ static int thermal_require(const char *entry, padne_ctx *ctx, const padne_therma
 
 // b[n_cols][n_pot] on the device from the face powers th->P[n_cols][n_tri] and the node-heat triples: the gather through the
 // vertex lists, 8 columns per launch, then the triples.  Returns once the host lists have been read
-static int thermal_form_load(padne_ctx *ctx, padne_thermal *th, int32_t n_cols, int64_t n_heat, const int64_t *heat_node,
+int thermal_form_load(padne_ctx *ctx, padne_thermal *th, int32_t n_cols, int64_t n_heat, const int64_t *heat_node,
                              const int32_t *heat_col, const double *heat_val, double *d_b) {
     hipStream_t s = ctx->stream;
     const long long n_pot = th->n_pot;
@@ -418,7 +418,7 @@ static int thermal_solve_core(padne_ctx *ctx, padne_thermal *th, int32_t n_cols,
     return rc;
 }
 
-static int thermal_check_heat(const padne_thermal *th, int32_t n_cols, int64_t n_heat, const int64_t *heat_node,
+int thermal_check_heat(const padne_thermal *th, int32_t n_cols, int64_t n_heat, const int64_t *heat_node,
                               const int32_t *heat_col, const double *heat_val) {
     PADNE_REQUIRE(n_cols >= 1 && n_cols <= 4096, "between 1 and 4096 columns");
     PADNE_REQUIRE(n_heat >= 0 && n_heat <= 0x7fffffffLL, "number of node-heat triples");
@@ -541,7 +541,7 @@ extern "C" int padne_thermal_lumped(padne_ctx *ctx, const padne_thermal *th, dou
 }
 
 // the face powers of the caller on the device, in the handle's array (any earlier solve's results are no longer reported)
-static int thermal_upload_power(padne_ctx *ctx, padne_thermal *th, int32_t n_cols, const double *face_power_host) {
+int padne::thermal_upload_power(padne_ctx *ctx, padne_thermal *th, int32_t n_cols, const double *face_power_host) {
     PADNE_REQUIRE(th->n_tri == 0 || face_power_host != nullptr, "null argument");
     PADNE_HIP_CHECK(hipSetDevice(ctx->device));
     const size_t count = (size_t)n_cols * (size_t)th->n_tri;
@@ -578,22 +578,25 @@ extern "C" int padne_thermal_solve(padne_ctx *ctx, padne_thermal *th, int32_t n_
     return thermal_solve_core(ctx, th, n_cols, n_heat, heat_node, heat_col, heat_val, opts, theta_host, info);
 }
 
-int padne::thermal_solve_kkt_scaled(const char *entry, padne_ctx *ctx, padne_thermal *th, padne_kkt *plan, int32_t n_cols,
-                                    const double *scale, int64_t n_heat, const int64_t *heat_node, const int32_t *heat_col,
-                                    const double *heat_val, const padne_solve_opts *opts, double *theta_host,
-                                    padne_solve_info *info) {
+// the checks of an entry that reads the block `plan`'s last padne_kkt_finish_block left on the device: *V_out that block
+int padne::thermal_kkt_block(const char *entry, padne_ctx *ctx, const padne_thermal *th, padne_kkt *plan, int32_t n_cols,
+                             const double **V_out) {
     PADNE_TRY(thermal_require(entry, ctx, th));
-    const double *V = nullptr;
     long long N = 0;
     const padne_csr *L = nullptr;
-    PADNE_TRY(kkt_finished_block(entry, ctx, plan, n_cols, &V, &N, &L));
+    PADNE_TRY(kkt_finished_block(entry, ctx, plan, n_cols, V_out, &N, &L));
     PADNE_REQUIRE(L == th->L, "the plan and the thermal model must come from the same assembled system");
-    PADNE_TRY(thermal_check_heat(th, n_cols, n_heat, heat_node, heat_col, heat_val));
+    return PADNE_OK;
+}
+
+// th->P[n_cols][n_tri] from the block V of thermal_kkt_block (scale as in thermal_solve_kkt_scaled)
+int padne::thermal_kkt_face_power(padne_ctx *ctx, padne_thermal *th, int32_t n_cols, const double *V, const double *scale) {
     PADNE_HIP_CHECK(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
+    th->solved = false;
     PADNE_TRY(thermal_reserve(ctx, &th->P, &th->P_cap, (size_t)n_cols * (size_t)th->n_tri));
     if (th->n_tri > 0) {
-        const ErrorMesh M = error_mesh_of(L);
+        const ErrorMesh M = error_mesh_of(th->L);
         Scratch sc(ctx);
         int *d_bad = nullptr;
         PADNE_TRY(sc.alloc(&d_bad, 1));
@@ -607,6 +610,17 @@ int padne::thermal_solve_kkt_scaled(const char *entry, padne_ctx *ctx, padne_the
         PADNE_HIP_CHECK(hipGetLastError());
         PADNE_TRY(thermal_bad_flag(s, d_bad, "triangle index out of range"));
     }
+    return PADNE_OK;
+}
+
+int padne::thermal_solve_kkt_scaled(const char *entry, padne_ctx *ctx, padne_thermal *th, padne_kkt *plan, int32_t n_cols,
+                                    const double *scale, int64_t n_heat, const int64_t *heat_node, const int32_t *heat_col,
+                                    const double *heat_val, const padne_solve_opts *opts, double *theta_host,
+                                    padne_solve_info *info) {
+    const double *V = nullptr;
+    PADNE_TRY(thermal_kkt_block(entry, ctx, th, plan, n_cols, &V));
+    PADNE_TRY(thermal_check_heat(th, n_cols, n_heat, heat_node, heat_col, heat_val));
+    PADNE_TRY(thermal_kkt_face_power(ctx, th, n_cols, V, scale));
     return thermal_solve_core(ctx, th, n_cols, n_heat, heat_node, heat_col, heat_val, opts, theta_host, info);
 }
 

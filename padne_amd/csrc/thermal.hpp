@@ -40,4 +40,35 @@ int thermal_solve_kkt_scaled(const char *entry, padne_ctx *ctx, padne_thermal *t
                              const double *scale, int64_t n_heat, const int64_t *heat_node, const int32_t *heat_col,
                              const double *heat_val, const padne_solve_opts *opts, double *theta_host, padne_solve_info *info);
 
+// thermal.hip, for the handles built on a thermal one (transient.hip).  thermal_require: the handle is the context's.
+// thermal_check_heat: the checks of the node-heat triples of padne_thermal_solve.  thermal_upload_power: face powers of the
+// caller into th->P.  thermal_kkt_block / thermal_kkt_face_power: th->P from the finished block of a plan, in the two halves
+// of thermal_solve_kkt_scaled.  thermal_form_load: b[n_cols][n_pot] on the device from th->P[n_cols][n_tri] and the triples.
+// thermal_tiles: tiles of 256 items per segment of an offset table
+int thermal_require(const char *entry, padne_ctx *ctx, const padne_thermal *th);
+int thermal_check_heat(const padne_thermal *th, int32_t n_cols, int64_t n_heat, const int64_t *heat_node, const int32_t *heat_col,
+                       const double *heat_val);
+int thermal_upload_power(padne_ctx *ctx, padne_thermal *th, int32_t n_cols, const double *face_power_host);
+int thermal_kkt_block(const char *entry, padne_ctx *ctx, const padne_thermal *th, padne_kkt *plan, int32_t n_cols,
+                      const double **V_out);
+int thermal_kkt_face_power(padne_ctx *ctx, padne_thermal *th, int32_t n_cols, const double *V, const double *scale);
+int thermal_form_load(padne_ctx *ctx, padne_thermal *th, int32_t n_cols, int64_t n_heat, const int64_t *heat_node,
+                      const int32_t *heat_col, const double *heat_val, double *d_b);
+std::vector<long long> thermal_tiles(const std::vector<int64_t> &off);
+
+// What a matrix derived from its values (1 / diagonal, single-precision copies, multigrid hierarchy) is dropped and rebuilt
+// on next use from the values in place; the x-window plan depends on the pattern only and stays
+inline void csr_invalidate_values(padne_csr *L) {
+    if (L->amg != nullptr) amg_destroy(L->amg);
+    L->amg = nullptr;
+    if (L->owner != nullptr) {
+        pool_free(L->owner, L->dinv);
+        pool_free(L->owner, L->vals32);
+        pool_free(L->owner, L->dinv32);
+    }
+    L->dinv = nullptr;
+    L->vals32 = nullptr;
+    L->dinv32 = nullptr;
+}
+
 }  // namespace padne

@@ -30,6 +30,8 @@ compute_power_density :728-745         ``power_density_kernel``
                                        closure, edges by a sort of corner keys, ``refine_emit_kernel`` over the faces
 (how hot that makes the copper)        ``solve_thermal``: the load-case block, then ``thermal_face_power_kernel``, the gather
                                        ``thermal_load_kernel`` and one more block solve on the thermal sheet operator
+(and how fast)                         ``solve_thermal_transient``: backward-Euler steps on S = A + C/dt from the previous state,
+                                       ``transient_rhs_kernel`` and ``transient_report_kernel`` per step, one hierarchy per dt
 read-out under the cursor ui.py:192    ``FieldSampler``: owner face by ``sample_kernel`` over a grid of bins per layer,
                                        V interpolated in the face, J and p of the face
 =====================================  ====================================================
@@ -45,6 +47,7 @@ import logging
 import math
 import threading
 import time
+import types
 import warnings
 from collections.abc import Mapping
 from dataclasses import dataclass, field
@@ -2109,10 +2112,13 @@ def _thermal_envelope(board: IndexedBoard, ambient: float, env, env_case, report
     return ThermalEnvelope(temperatures=env_temps, cases=env_cases, hotspots=env_hotspots)
 
 
-def _solve_block_thermal(prob, meshes, mesh_index_to_layer_index, checked: CheckedThermalModel, cases, fields: bool,
-                         filtered_networks, disconnected_meshes_by_layer, laps: _Laps):
-    """The checked ``cases`` of ``prob`` as one electrical block and one thermal block on top of it, for the checked model:
-    ([Solution], [ThermalReport], ThermalEnvelope).  ``fields``: with the per-case temperatures of vertices and faces."""
+@contextlib.contextmanager
+def _thermal_block(prob, meshes, mesh_index_to_layer_index, checked: CheckedThermalModel, cases, filtered_networks,
+                   disconnected_meshes_by_layer, laps: _Laps, what: str):
+    """What the steady and the transient thermal paths share: the checked ``cases`` of ``prob`` solved as one electrical block
+    on the load-case path, the element flows of every case, and the ``_hip.Thermal`` handle of the checked model on top of
+    the assembled system.  A context: inside it the system, the plan and the handle live on the device; the value is a
+    namespace of everything the two paths read.  On the way out the handle is closed and a stalled block is warned about."""
     substituted = [substitute_load_case(prob, case) for case in cases]
     k = len(cases)
     board = index_board(prob, meshes, mesh_index_to_layer_index, filtered_networks, disconnected_meshes_by_layer)
@@ -2126,7 +2132,7 @@ def _solve_block_thermal(prob, meshes, mesh_index_to_layer_index, checked: Check
     with board.assembled() as (L, _):
         rows, cols, vals = stamp_load_cases(board.filtered_networks, board.node_indexer, L.shape[0], cases)
         laps.lap("assembly")
-        log.info(f"Solving {k} load case(s) as one block, with their temperatures")
+        log.info(f"Solving {k} load case(s) as one block, with their {what}")
         plan, V, residual_norms, res, n_tri, _n_mesh = _solve_block_on_device(L, rows, cols, vals, k, k, laps)
         power = plan.power_density_block(k, n_tri)
         local, Vu = _gather_element_rows([row for _, row in pairs], V, _ROW_UNKNOWNS)
@@ -2141,21 +2147,39 @@ def _solve_block_thermal(prob, meshes, mesh_index_to_layer_index, checked: Check
         try:
             laps.lap("thermal_setup")
             heat = thermal_heat_triples(pairs, flows_by_case) if checked.element_heat else None
-            theta, tres = thermal.solve_kkt(plan, k, heat, rtol=RTOL, max_iter=MAX_ITER)
-            laps.lap("thermal_solve")
-            mean, mesh_max, mesh_vert, mesh_heat, mesh_loss, env, env_case = thermal.report(k, n_tri, n_vert, fields=fields)
-            laps.lap("thermal_report")
+            yield types.SimpleNamespace(board=board, substituted=substituted, pairs=pairs, resistors=resistors, plan=plan, V=V,
+                                        residual_norms=residual_norms, res=res, n_tri=n_tri, n_vert=n_vert,
+                                        n_potential=n_potential, power=power, thermal=thermal, heat=heat, k=k)
         finally:
             thermal.close()
     laps.lap()
     _warn_if_block_stalled(res, residual_norms, cols, vals, k)
+
+
+def _block_solutions(blk) -> list:
+    """The Solution of every case of a :func:`_thermal_block`."""
+    return [_column_solution(blk.board, sub, np.ascontiguousarray(blk.V[:, j]), blk.residual_norms[j], blk.res, blk.power[j],
+                             f"Load case {j}: " if blk.k > 1 else "") for j, (sub, _) in enumerate(blk.substituted)]
+
+
+def _solve_block_thermal(prob, meshes, mesh_index_to_layer_index, checked: CheckedThermalModel, cases, fields: bool,
+                         filtered_networks, disconnected_meshes_by_layer, laps: _Laps):
+    """The checked ``cases`` of ``prob`` as one electrical block and one thermal block on top of it, for the checked model:
+    ([Solution], [ThermalReport], ThermalEnvelope).  ``fields``: with the per-case temperatures of vertices and faces."""
+    with _thermal_block(prob, meshes, mesh_index_to_layer_index, checked, cases, filtered_networks,
+                        disconnected_meshes_by_layer, laps, "temperatures") as blk:
+        k, heat = blk.k, blk.heat
+        theta, tres = blk.thermal.solve_kkt(blk.plan, k, heat, rtol=RTOL, max_iter=MAX_ITER)
+        laps.lap("thermal_solve")
+        mean, mesh_max, mesh_vert, mesh_heat, mesh_loss, env, env_case = blk.thermal.report(k, blk.n_tri, blk.n_vert, fields=fields)
+        laps.lap("thermal_report")
     if tres.status != _hip.OK and not tres.rel_residual <= max(RTOL, STALL_WARN_ABOVE):
         warnings.warn(f"The thermal solve stopped at a relative residual of {tres.rel_residual:.3e}", SolverWarning)
-    solutions = [_column_solution(board, sub, np.ascontiguousarray(V[:, j]), residual_norms[j], res, power[j],
-                                  f"Load case {j}: " if k > 1 else "") for j, (sub, _) in enumerate(substituted)]
+    board = blk.board
+    solutions = _block_solutions(blk)
     info = {"iterations": int(tres.iterations), "rel_residual": float(tres.rel_residual), "seconds": float(tres.seconds)}
-    heat_val = heat[2].reshape(k, len(resistors), 2) if heat is not None else None
-    reports = _thermal_reports(board, checked, substituted, resistors, fields, theta, mean, mesh_max, mesh_vert, mesh_heat,
+    heat_val = heat[2].reshape(k, len(blk.resistors), 2) if heat is not None else None
+    reports = _thermal_reports(board, checked, blk.substituted, blk.resistors, fields, theta, mean, mesh_max, mesh_vert, mesh_heat,
                                mesh_loss, heat_val, [info] * k)
     envelope = _thermal_envelope(board, checked.ambient, env, env_case, reports)
     laps.lap("solutions")
@@ -2210,6 +2234,388 @@ def solve_thermal(prob, model: ThermalModel, mesher_config: Optional[mesh.Mesher
         cases = check_load_cases(prob, cases)
     meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
     return solve_meshed_thermal(prob, meshes, mesh_index_to_layer_index, model, cases=cases, per_case_fields=per_case_fields)
+
+
+# --------------------------------------------------------------------------------------------
+# transient: the copper's temperatures under a schedule of load cases (DESIGN.md "Transient")
+# --------------------------------------------------------------------------------------------
+
+MAX_TRANSIENT_STEPS = 100000
+
+
+@dataclass
+class Segment:
+    """A stretch of a schedule with one load and equal steps (see :func:`solve_meshed_thermal_transient`).
+
+    - ``duration``: seconds, finite and positive.
+    - ``steps``: the number (>= 1) of backward-Euler steps of ``duration / steps`` it is covered with.
+    - ``case``: an index into the ``cases`` of the call, None = sources off; or a tuple with one such entry per scenario."""
+    duration: float
+    steps: int
+    case: object = None
+
+
+@dataclass
+class TransientModel:
+    """What turns a schedule of loads into temperatures over time (see :func:`solve_meshed_thermal_transient`).
+
+    - ``thermal``: the :class:`ThermalModel` of the steady problem.
+    - ``areal_capacity``: the heat capacity per area c [J / (K mesh-unit^2)] of the sheet, one float for all layers or a
+      mapping {layer or layer name: float} that names every layer.  Required: it lumps the board under the foil as well as
+      the foil, and there is no sensible default.  With meshes in mm, 35 um of copper alone are 1.2e-4 J/(K mm^2) and
+      1.6 mm of FR4 about 3e-3 J/(K mm^2).
+    - ``initial``: None = every scenario starts at ambient; a case index = from that case's steady state; or a tuple with
+      one such entry per scenario."""
+    thermal: ThermalModel
+    areal_capacity: object
+    initial: object = None
+
+
+@dataclass
+class CheckedTransientModel:
+    """A :class:`TransientModel` resolved against a Problem (:func:`check_transient_model`)."""
+    thermal: CheckedThermalModel
+    capacity: list             # per layer
+    initial: object            # None, an int, or a tuple of None / int
+
+
+@dataclass
+class TransientEnvelope:
+    """The hottest each vertex got during one scenario (the sequential rule of :func:`envelope_of`, applied along time: the
+    earliest time keeps a tie)."""
+    temperatures: list    # per layer, per mesh: ZeroForm of max_n T_n per vertex
+    times: list           # per layer, per mesh: (n_vertices,) the first time of that maximum [s]
+    hotspots: list        # per layer: (T, time, mesh index within the layer, vertex index, x, y), None without vertices
+
+
+@dataclass
+class TransientReport:
+    """The temperatures of one scenario over time (see :func:`solve_meshed_thermal_transient`).  Arrays over time have
+    n_steps + 1 entries: entry 0 is the start, entry n the state after step n."""
+    times: np.ndarray                   # [s]
+    hotspots: list                      # per layer, per time: (T, mesh index within the layer, vertex index, x, y), None without vertices
+    layers: list                        # per layer: {"stored": heat held above ambient [J], "loss": film loss [W], "heat": Joule heat put into its copper by the step that led here [W]}, arrays over time
+    total_stored: np.ndarray            # [J]
+    total_loss: np.ndarray              # [W]
+    total_heat: np.ndarray              # [W]: copper and elements, of the case of the step that led here (0 at the start and with the sources off)
+    probes: dict                        # node id -> T over time
+    peak: Optional[tuple]               # (T, time, layer index, mesh index within the layer, vertex index, x, y): the first time of the largest hotspot
+    envelope: TransientEnvelope
+    snapshot_times: list                # the times of the kept fields
+    temperatures: list                  # per kept time: per layer, per mesh ZeroForm of T
+    face_temperatures: list             # per kept time: per layer, per mesh TwoForm of the mean T of each face's corners
+    disconnected_temperatures: list     # per layer, per disconnected mesh: ZeroForm filled with the ambient temperature
+    info: dict                          # {"iterations", "iterations_per_step", "seconds_per_step", "setup_seconds_per_step", "rel_residual", "hierarchies", "seconds"}
+
+
+def _case_entry(value, n_cases: int, what: str):
+    """None, or the int of a case index in range; ValueError otherwise."""
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
+        raise ValueError(f"{what} must be None (sources off) or the index of a load case, not {value!r}")
+    if not 0 <= int(value) < n_cases:
+        raise ValueError(f"{what}: {int(value)} is no load case (there are {n_cases})")
+    return int(value)
+
+
+def _scenario_entries(value, n_cases: int, what: str):
+    """``value`` as a checked scalar entry, or as a tuple of them when it is a tuple or list."""
+    if isinstance(value, (tuple, list)):
+        if not value:
+            raise ValueError(f"{what}: a tuple names at least one scenario")
+        return tuple(_case_entry(v, n_cases, what) for v in value)
+    return _case_entry(value, n_cases, what)
+
+
+def check_transient_model(prob, model, filtered_networks=None) -> CheckedTransientModel:
+    """``model`` resolved against ``prob``, or ValueError -- before anything reaches the device -- for everything
+    :func:`check_thermal_model` refuses of ``model.thermal``; an areal capacity that is missing, not finite or not
+    positive; a layer without a capacity; and a mapping key that is no layer.  ``initial`` is checked against the cases and
+    the schedule by :func:`solve_meshed_thermal_transient`."""
+    if not isinstance(model, TransientModel):
+        raise ValueError("model must be a TransientModel")
+    thermal = check_thermal_model(prob, model.thermal, filtered_networks)
+    if model.areal_capacity is None:
+        raise ValueError("the areal heat capacity is required: a float, or a mapping {layer: float}")
+    if isinstance(model.areal_capacity, Mapping):
+        given = _per_layer(prob, model.areal_capacity, "areal_capacity")
+        for i, layer in enumerate(prob.layers):
+            if i not in given:
+                raise ValueError(f"layer {layer.name!r} has no areal heat capacity")
+        capacity = [given[i] for i in range(len(prob.layers))]
+    else:
+        capacity = [_positive_number(model.areal_capacity, "the areal heat capacity")] * len(prob.layers)
+    return CheckedTransientModel(thermal=thermal, capacity=capacity, initial=model.initial)
+
+
+def check_schedule(schedule, n_cases: int, repeat=1) -> tuple:
+    """(the flattened segments, the number of scenarios) of a schedule, or ValueError.
+
+    ``schedule`` is a non-empty sequence of :class:`Segment`; it is run ``repeat`` (>= 1) times back to back, and the
+    flattened list holds ``repeat * len(schedule)`` checked Segments.  A segment's ``case`` is None, an index below
+    ``n_cases``, or a tuple of those with one entry per scenario; all tuples have the same length, which is the number of
+    scenarios (1 without tuples), and tuples come back as tuples.  Refused: an empty schedule, a duration that is not finite
+    and positive, ``steps`` that is not an integer >= 1, a case out of range, tuples of unequal length, ``repeat < 1`` and
+    more than 100 000 steps in total."""
+    if isinstance(repeat, bool) or not isinstance(repeat, (int, np.integer)) or repeat < 1:
+        raise ValueError(f"repeat must be an integer >= 1, not {repeat!r}")
+    if isinstance(schedule, (Segment, Mapping, str, bytes)):
+        raise ValueError("the schedule must be a sequence of Segments")
+    try:
+        schedule = list(schedule)
+    except TypeError:
+        raise ValueError("the schedule must be a sequence of Segments") from None
+    if not schedule:
+        raise ValueError("an empty schedule: give at least one Segment")
+    checked, n_scen = [], None
+    for i, seg in enumerate(schedule):
+        if not isinstance(seg, Segment):
+            raise ValueError(f"segment {i} is not a Segment")
+        duration = _positive_number(seg.duration, f"the duration of segment {i}")
+        if isinstance(seg.steps, bool) or not isinstance(seg.steps, (int, np.integer)) or seg.steps < 1:
+            raise ValueError(f"the steps of segment {i} must be an integer >= 1, not {seg.steps!r}")
+        case = _scenario_entries(seg.case, n_cases, f"the case of segment {i}")
+        if isinstance(case, tuple):
+            if n_scen is not None and len(case) != n_scen:
+                raise ValueError(f"segment {i} names {len(case)} scenarios, an earlier one {n_scen}")
+            n_scen = len(case)
+        checked.append(Segment(duration=duration, steps=int(seg.steps), case=case))
+    total = int(repeat) * sum(seg.steps for seg in checked)
+    if total > MAX_TRANSIENT_STEPS:
+        raise ValueError(f"{total} steps in total: more than {MAX_TRANSIENT_STEPS}")
+    return [dataclasses.replace(seg) for _ in range(int(repeat)) for seg in checked], (1 if n_scen is None else n_scen)
+
+
+def check_probes(prob, probes, filtered_networks=None) -> list:
+    """The probes as a list of NodeIDs of the solved networks (connection nodes or internal nodes, as
+    :func:`check_objectives` accepts them), or ValueError."""
+    if isinstance(probes, (Mapping, str, bytes)) or _is_node_id(probes):
+        raise ValueError("probes must be a sequence of NodeIDs")
+    try:
+        probes = list(probes)
+    except TypeError:
+        raise ValueError("probes must be a sequence of NodeIDs") from None
+    networks = list(prob.networks) if filtered_networks is None else list(filtered_networks)
+    known = {node for network in networks for node in list(network.nodes) + [conn.node_id for conn in network.connections]}
+    for j, node in enumerate(probes):
+        if not _is_node_id(node):
+            raise ValueError(f"probe {j} must be a NodeID, not {type(node).__name__}")
+        if node not in known:
+            raise ValueError(f"probe {j} is not a node of the solved networks")
+    return probes
+
+
+def _check_transient_arguments(prob, model, schedule, cases, repeat, probes, keep, filtered_networks):
+    """Every check of :func:`solve_meshed_thermal_transient`: (checked model, checked cases, per flattened segment (dt, steps,
+    per-scenario cases), per-scenario initial cases, probes)."""
+    checked = check_transient_model(prob, model, filtered_networks)
+    checked_cases = [{}] if cases is None else check_load_cases(prob, cases)
+    segments, n_scen = check_schedule(schedule, len(checked_cases), repeat)
+    tuples = any(isinstance(seg.case, tuple) for seg in segments)
+    initial = _scenario_entries(checked.initial, len(checked_cases), "initial")
+    if isinstance(initial, tuple):
+        if tuples and len(initial) != n_scen:
+            raise ValueError(f"initial names {len(initial)} scenarios, the schedule {n_scen}")
+        n_scen = len(initial)
+    else:
+        initial = (initial,) * n_scen
+    flat = [(seg.duration / seg.steps, seg.steps, seg.case if isinstance(seg.case, tuple) else (seg.case,) * n_scen)
+            for seg in segments]
+    if keep not in ("end", "segments", "none"):
+        raise ValueError(f'keep must be "end", "segments" or "none", not {keep!r}')
+    return checked, checked_cases, flat, initial, check_probes(prob, probes, filtered_networks)
+
+
+def _snapshot(board: IndexedBoard, ambient: float, theta: np.ndarray) -> tuple:
+    """(per layer, per mesh ZeroForm of T; per layer, per mesh TwoForm of the mean T of each face's corners) of one state,
+    the mean as padne_thermal_report forms it: ((theta_1 + theta_2) + theta_3) / 3 on the corners (2, 0, 1)."""
+    voff, temps, faces = board.vindex.offsets, [], []
+    for layer_i in range(len(board.prob.layers)):
+        zfs, tfs = [], []
+        for mesh_i, msh, _lo, _hi in board.layer_meshes(layer_i):
+            th = theta[voff[mesh_i]:voff[mesh_i + 1]]
+            tri = np.asarray(msh.triangles, dtype=np.int64).reshape(-1, 3)
+            zf, tf = mesh.ZeroForm(msh), mesh.TwoForm(msh)
+            zf.values = th + ambient
+            tf.values = ((th[tri[:, 2]] + th[tri[:, 0]]) + th[tri[:, 1]]) / 3 + ambient
+            zfs.append(zf)
+            tfs.append(tf)
+        temps.append(zfs)
+        faces.append(tfs)
+    return temps, faces
+
+
+def _transient_report(board: IndexedBoard, ambient: float, times, mesh_max, mesh_vert, stored, loss, layer_heat, total_heat,
+                      probes, env, env_step, snapshots, info) -> TransientReport:
+    """The TransientReport of one scenario from its per-time arrays (n_steps + 1, n_mesh), the heats per time, the probe
+    traces {node: theta over time}, the envelope of theta with its steps (n_vert,) and the kept states [(time, theta)]."""
+    voff, n_layers, n_times = board.vindex.offsets, len(board.prob.layers), len(times)
+    hotspots, layers, env_temps, env_times, env_spots, peak = [], [], [], [], [], None
+    for layer_i in range(n_layers):
+        in_layer = list(board.layer_meshes(layer_i))
+        spots = []
+        for n in range(n_times):
+            best = None
+            for at, (mesh_i, msh, _lo, _hi) in enumerate(in_layer):
+                # meshes come in global vertex order: a later mesh wins only with a strictly larger temperature
+                if mesh_vert[n, mesh_i] >= 0 and (best is None or mesh_max[n, mesh_i] + ambient > best[0]):
+                    v = int(mesh_vert[n, mesh_i] - voff[mesh_i])
+                    best = (float(mesh_max[n, mesh_i] + ambient), at, v, float(msh.points[v][0]), float(msh.points[v][1]))
+            spots.append(best)
+            if best is not None and (peak is None or best[0] > peak[0]):      # the first time, then the lowest layer
+                peak = (best[0], float(times[n]), layer_i, *best[1:])
+        hotspots.append(spots)
+        ids = [mesh_i for mesh_i, *_ in in_layer]
+        layers.append({"stored": np.array([math.fsum(stored[n, ids].tolist()) for n in range(n_times)]),
+                       "loss": np.array([math.fsum(loss[n, ids].tolist()) for n in range(n_times)]),
+                       "heat": np.asarray(layer_heat[layer_i], dtype=DTYPE)})
+        zfs, whens, spot = [], [], None
+        for at, (mesh_i, msh, _lo, _hi) in enumerate(in_layer):
+            values, steps = env[voff[mesh_i]:voff[mesh_i + 1]], env_step[voff[mesh_i]:voff[mesh_i + 1]]
+            zf = mesh.ZeroForm(msh)
+            zf.values = values + ambient
+            zfs.append(zf)
+            whens.append(np.asarray(times)[steps])
+            if len(values):
+                v = int(np.argmax(values))
+                if spot is None or values[v] + ambient > spot[0]:
+                    spot = (float(values[v] + ambient), float(times[steps[v]]), at, v, float(msh.points[v][0]), float(msh.points[v][1]))
+        env_temps.append(zfs)
+        env_times.append(whens)
+        env_spots.append(spot)
+    cold = []
+    for layer_i in range(n_layers):
+        out = []
+        for msh in board.disconnected_meshes_by_layer[layer_i]:
+            msh = msh if isinstance(msh, mesh.Mesh) else mesh.Mesh.from_reference(msh)
+            zf = mesh.ZeroForm(msh)
+            zf.values = np.full(len(msh.vertices), ambient, dtype=DTYPE)
+            out.append(zf)
+        cold.append(out)
+    fields = [_snapshot(board, ambient, theta) for _, theta in snapshots]
+    return TransientReport(
+        times=np.asarray(times, dtype=DTYPE), hotspots=hotspots, layers=layers,
+        total_stored=np.array([math.fsum(stored[n].tolist()) for n in range(n_times)]),
+        total_loss=np.array([math.fsum(loss[n].tolist()) for n in range(n_times)]), total_heat=np.asarray(total_heat, dtype=DTYPE),
+        probes={node: trace + ambient for node, trace in probes.items()}, peak=peak,
+        envelope=TransientEnvelope(temperatures=env_temps, times=env_times, hotspots=env_spots),
+        snapshot_times=[t for t, _ in snapshots], temperatures=[f[0] for f in fields], face_temperatures=[f[1] for f in fields],
+        disconnected_temperatures=cold, info=info)
+
+
+def solve_meshed_thermal_transient(prob, meshes, mesh_index_to_layer_index, model: TransientModel, schedule, *, cases=None,
+                                   repeat=1, probes=(), keep="end", filtered_networks=None, disconnected_meshes_by_layer=None,
+                                   partition=None, timings: Optional[dict] = None):
+    """How hot the copper gets, and when, under a schedule of load cases: ``([Solution] per case, [TransientReport] per
+    scenario)``, with one scenario ``(solutions, report)``.
+
+    The model (DESIGN.md "Transient") adds a heat capacity to the steady problem of :func:`solve_meshed_thermal`:
+
+        C dtheta/dt + A theta = b(t),    C = diag(c M_v)
+
+    with c the layer's areal heat capacity ``model.areal_capacity`` and M_v the lumped area of the vertex; internal nodes
+    carry no capacity and follow the copper algebraically.  Time is stepped by backward Euler: first order,
+    unconditionally stable, and free of oscillation on a load step, which is why it is preferred to Crank-Nicolson here.
+    One step of length dt is one solve with S = A + C/dt from the previous state.  Every step obeys the balance
+    (stored_{n+1} - stored_n) / dt + loss_{n+1} = heat of the step's case, up to the solve's tolerance.
+
+    ``cases`` are load cases as :func:`check_load_cases` accepts them (None: the one case ``{}``, the Problem as given).
+    ``schedule`` is a sequence of :class:`Segment`, each naming the case that is on (None: sources off), run ``repeat``
+    times back to back (a duty cycle).  Several scenarios -- the tuple form of ``Segment.case`` and of ``model.initial`` --
+    share the time grid and advance in lockstep as the columns of one block.  ``probes``: node ids (connection nodes or
+    internal nodes) whose temperature traces are wanted.  ``keep``: ``"end"`` keeps the field at the end, ``"segments"`` at
+    the end of every segment, ``"none"`` none.  Temperatures are theta + ambient.  The coupling is one-way: the
+    resistivity does not follow the temperature (stepping inside the Picard loop of :func:`solve_meshed_electrothermal` is
+    not built).
+
+    On the device: one electrical block solve of the cases on the load-case path, the thermal operator and the heat load
+    of every case from the potentials it holds (the powers never visit the host), then per segment the steps, each with
+    the right-hand side, the block solve from the previous state, the per-mesh report and the running envelope; the
+    multigrid hierarchy of S is built once per distinct dt in a row (``info["hierarchies"]``).  ValueError, before anything
+    reaches the device, for what :func:`check_transient_model`, :func:`check_load_cases`, :func:`check_schedule` and
+    :func:`check_probes` refuse, an ``initial`` that names a case out of range or another number of scenarios than the
+    schedule, an unknown ``keep``, and a ``partition`` over several GPUs.  A SolverWarning when a step ends above the
+    tolerance.  ``timings`` (a dict) receives the host time of each stage in seconds."""
+    _refuse_partition(partition, "transient temperatures")
+    checked, checked_cases, flat, initial, probe_nodes = _check_transient_arguments(prob, model, schedule, cases, repeat, probes,
+                                                                                     keep, filtered_networks)
+    laps, ambient, n_scen = _Laps(timings), checked.thermal.ambient, len(initial)
+    with _thermal_block(prob, meshes, mesh_index_to_layer_index, checked.thermal, checked_cases, filtered_networks,
+                        disconnected_meshes_by_layer, laps, "temperatures over time") as blk:
+        board, k, heat = blk.board, blk.k, blk.heat
+        layer_of, n_mesh, n_vert = board.layer_of, len(board.meshes), blk.n_vert
+        # the Joule heat of every mesh's copper, per case: the sum current_cases forms of the same face powers
+        *_, mesh_power, _cuts = blk.plan.current_cases(k, blk.n_tri, np.asarray(layer_of, dtype=np.int32), [], np.zeros((0, 4)),
+                                                       fields=False, envelope=False)
+        transient = _hip.Transient(blk.thermal, [checked.capacity[layer_of[i]] for i in range(n_mesh)])
+        try:
+            transient.loads_kkt(blk.plan, k, heat)
+            first = transient.start(initial, rtol=RTOL, max_iter=MAX_ITER)
+            laps.lap("transient_start")
+            probe_idx = [board.node_indexer.node_to_global_index[node] for node in probe_nodes]
+            top0, vert0, stored0, loss0 = transient.report()
+            runs, snapshots, worst = [], [], (first.rel_residual if first.status != _hip.OK else 0.0)
+            theta0 = transient.state() if probe_idx else None
+            t, times = 0.0, [0.0]
+            for at, (dt, steps, seg_cases) in enumerate(flat):
+                out = transient.run(dt, steps, seg_cases, probe_idx, rtol=RTOL, max_iter=MAX_ITER)
+                runs.append(out)
+                if out["result"].status != _hip.OK:
+                    worst = max(worst, float(out["result"].rel_residual))
+                for _ in range(steps):
+                    t = t + dt
+                    times.append(t)
+                if keep == "segments" or (keep == "end" and at == len(flat) - 1):
+                    snapshots.append((t, transient.state()))
+            env, env_step = transient.envelope(n_vert)
+            _steps, _time, hierarchies = transient.clock()
+            laps.lap("transient_run")
+        finally:
+            transient.close()
+    if worst > max(RTOL, STALL_WARN_ABOVE):
+        warnings.warn(f"A step of the transient thermal solve stopped at a relative residual of {worst:.3e}", SolverWarning)
+    solutions = _block_solutions(blk)
+    join = lambda key, head: np.concatenate([head[None]] + [out[key] for out in runs])      # (n_steps + 1, n_scen, n_mesh)
+    mesh_max, mesh_vert, stored, loss = join("max", top0), join("vertex", vert0), join("stored", stored0), join("loss", loss0)
+    iterations = np.concatenate([out["iterations"] for out in runs])
+    info = {"iterations": int(first.iterations) + int(iterations.sum()), "iterations_per_step": iterations,
+            "seconds_per_step": np.concatenate([out["seconds"] for out in runs]),
+            "setup_seconds_per_step": np.concatenate([out["setup_seconds"] for out in runs]),
+            "rel_residual": max([float(first.rel_residual)] + [float(out["result"].rel_residual) for out in runs]),
+            "hierarchies": int(hierarchies), "seconds": float(first.seconds) + sum(float(out["result"].seconds) for out in runs)}
+    n_layers = len(prob.layers)
+    case_layer_heat = [[math.fsum(float(mesh_power[j, i]) for i in range(n_mesh) if layer_of[i] == layer_i)
+                        for layer_i in range(n_layers)] for j in range(k)]
+    element_heat = [math.fsum(heat[2][heat[1] == j].tolist()) if heat is not None else 0.0 for j in range(k)]
+    case_total = [math.fsum(case_layer_heat[j] + [element_heat[j]]) for j in range(k)]
+    reports = []
+    for c in range(n_scen):
+        # the case that led to every time: the initial case at the start (its steady state balances it), then each step's
+        led = [initial[c]] + [seg_cases[c] for _dt, steps, seg_cases in flat for _ in range(steps)]
+        layer_heat = [[0.0 if j is None else case_layer_heat[j][layer_i] for j in led] for layer_i in range(n_layers)]
+        total_heat = [0.0 if j is None else case_total[j] for j in led]
+        traces = {}
+        for p, node in enumerate(probe_nodes):
+            traces[node] = np.concatenate([[theta0[c, probe_idx[p]]]] + [out["probes"][:, c, p] for out in runs])
+        reports.append(_transient_report(board, ambient, times, mesh_max[:, c], mesh_vert[:, c], stored[:, c], loss[:, c],
+                                         layer_heat, total_heat, traces, env[c], env_step[c],
+                                         [(when, theta[c]) for when, theta in snapshots], info))
+    laps.lap("solutions")
+    if n_scen == 1:
+        return solutions, reports[0]
+    return solutions, reports
+
+
+def solve_thermal_transient(prob, model: TransientModel, schedule, mesher_config: Optional[mesh.Mesher.Config] = None, *,
+                            mesher=None, cases=None, repeat=1, probes=(), keep="end", partition=None):
+    """``solve`` with the copper's temperatures over a schedule (see :func:`solve_meshed_thermal_transient`): the board is
+    meshed once."""
+    _refuse_partition(partition, "transient temperatures")
+    _check_transient_arguments(prob, model, schedule, cases, repeat, probes, keep, None)
+    meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
+    return solve_meshed_thermal_transient(prob, meshes, mesh_index_to_layer_index, model, schedule, cases=cases, repeat=repeat,
+                                          probes=probes, keep=keep)
 
 
 # --------------------------------------------------------------------------------------------
