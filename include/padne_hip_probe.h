@@ -1,11 +1,11 @@
 /* padne_hip_probe.h -- TEST-ONLY probes of libpadne_hip.so.  Neither the drop-in boundary (include/padne_hip.h) nor the
- * multi-rank scaffolding (include/padne_hip_test.h): six entries.  padne_test_product drives a single product launcher of the
+ * multi-rank scaffolding (include/padne_hip_test.h): seven entries.  padne_test_product drives a single product launcher of the
  * solver on inputs a test chooses, so that every SpMV / SpMM kernel form and epilogue can be held against a host reference;
  * padne_test_kkt_state copies one device array of a padne_kkt plan out, so that every stage of the plan can;
  * padne_test_amg_state copies out what a level of the multigrid hierarchy decided in its setup, padne_test_amg_tail hands
  * out the gathered operator of a row-partitioned hierarchy; padne_test_halo_exchange and padne_test_amg_apply_dist run one
- * halo exchange and one cycle of a row-partitioned hierarchy on a test's vector.  Bound by padne_amd/_hip.py
- * (PROBE_SIGNATURES). */
+ * halo exchange and one cycle of a row-partitioned hierarchy on a test's vector; padne_test_pool_guard reads the counters of
+ * the device allocator's guarded mode and runs its self-test.  Bound by padne_amd/_hip.py (PROBE_SIGNATURES). */
 #ifndef PADNE_HIP_PROBE_H
 #define PADNE_HIP_PROBE_H
 
@@ -114,6 +114,20 @@ int padne_test_halo_exchange(padne_ctx *ctx, int32_t as_float, const double *x_h
  * plan: builds the hierarchy over all ranks if needed and runs ONE cycle, r_host[n_owned] -> z_host[n_owned], with the
  * partial-sum slot and the null unit of padne_amg_apply.  Collective.  Waits for the context's stream. */
 int padne_test_amg_apply_dist(padne_ctx *ctx, padne_csr *a, const double *r_host, double *z_host);
+
+/* The guarded mode of the context's device allocator, PADNE_POOL_GUARD=<hex fill byte> (INTEGRATION.md;
+ * tests/test_device_memory.py): every block handed out lies between two guard zones that are compared with their canary when
+ * the block is freed, and its bytes are filled with the fill byte first.  Counters of the context plus its second stream's.
+ *   op 0  copy the counters out
+ *   op 1  reset them, then as op 0
+ *   op 2  the self-test (PADNE_E_INVALID without the switch): two blocks of 1000 bytes; the first is read back, then eight
+ *         bytes are copied from the host to offset 1000 of the first and to offset -8 of the second -- inside their guard
+ *         zones, which belong to the blocks' own allocations -- and both are freed: two violations.  Then as op 0.
+ * out[8]: guarded blocks handed out; violations; of the first violation the requested bytes, the side (1 in front of the
+ * block, 2 behind it) and the offset of the first changed byte from the block's start (negative in front); side and offset of
+ * the last violation; and in out[7] the fill byte (-1: mode off), or after op 2 whether every byte read back was the fill
+ * byte (1 / 0).  A violation is only ever counted: nothing aborts. */
+int padne_test_pool_guard(padne_ctx *ctx, int32_t op, int64_t *out);
 
 #ifdef __cplusplus
 }

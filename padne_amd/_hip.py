@@ -209,6 +209,7 @@ PROBE_SIGNATURES = {
     "padne_test_amg_tail": (C.c_int, [_P, C.POINTER(_P)]),
     "padne_test_halo_exchange": (C.c_int, [_P, C.c_int32, _PF64, _PF64]),
     "padne_test_amg_apply_dist": (C.c_int, [_P, _P, _PF64, _PF64]),
+    "padne_test_pool_guard": (C.c_int, [_P, C.c_int32, _P]),
 }
 
 _lib = None
@@ -330,6 +331,16 @@ class Context:
         if getattr(self, "_h", None):
             self._lib.padne_ctx_destroy(self._h)
             self._h = None
+
+    def pool_guard(self, op: int = 0) -> dict:
+        """TEST-ONLY (``padne_test_pool_guard``): counters of the allocator's guarded mode, PADNE_POOL_GUARD (op 0), after a
+        reset (op 1) or after the mode's self-test (op 2); of this context and its second stream's together."""
+        out = np.zeros(8, dtype=np.int64)
+        _check(self._lib.padne_test_pool_guard(self._h, int(op), out.ctypes.data_as(_P)))
+        side = {0: None, 1: "front", 2: "back"}
+        return {"allocations": int(out[0]), "violations": int(out[1]),
+                "first": (int(out[2]), side[int(out[3])], int(out[4])), "last": (side[int(out[5])], int(out[6])),
+                "fill": int(out[7])}
 
     def __del__(self):
         try:

@@ -55,6 +55,11 @@ void options_from_env(padne_options *o) {
         o->force_relabel_lanes = has(f, "relabel_lanes") != nullptr;
         if (const char *w = has(f, "spgemm_split")) o->force_spgemm_split = w[12] == ':' ? atoll(w + 13) : 30000;
     }
+    if (const char *e = getenv("PADNE_POOL_GUARD")) {      // two hex digits at the most: the fill byte
+        char *end = nullptr;
+        const long v = strtol(e, &end, 16);
+        if (end != e && *end == '\0' && strlen(e) <= 2 && v >= 0 && v <= 255) o->pool_guard = (int)v;
+    }
     if (const char *v = getenv("PADNE_VERBOSE")) {
         o->verbose_amg = has(v, "amg") != nullptr;
         o->verbose_xw = has(v, "xw") != nullptr;
@@ -71,8 +76,18 @@ void set_error(const char *fmt, ...) {
     va_end(ap);
 }
 
+// PADNE_POOL_GUARD: the whole workspace holds the fill byte when an operation starts to carve it up.  No caller keeps anything
+// in the workspace across a later ensure_workspace of the same operation -- the two CG loops and the Lanczos job (pcg.hip) and
+// the two host-vector products below each call it once, before their first launch, and the Lanczos jobs of a multigrid setup
+// run on the second stream's context, which has a workspace of its own -- so all of it is filled, on every call.
+static int workspace_poison(padne_ctx *ctx) {
+    PADNE_HIP_CHECK(hipMemsetAsync(ctx->ws, ctx->opt.pool_guard, ctx->ws_bytes, ctx->stream));
+    PADNE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return PADNE_OK;
+}
+
 int ensure_workspace(padne_ctx *ctx, size_t bytes) {
-    if (ctx->ws_bytes >= bytes) return PADNE_OK;
+    if (ctx->ws_bytes >= bytes) return ctx->opt.pool_guard < 0 ? PADNE_OK : workspace_poison(ctx);
     if (ctx->ws) {
         PADNE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
         PADNE_HIP_CHECK(hipFree(ctx->ws));
@@ -84,77 +99,109 @@ int ensure_workspace(padne_ctx *ctx, size_t bytes) {
         return PADNE_E_NOMEM;
     }
     ctx->ws_bytes = bytes;
-    return PADNE_OK;
+    return ctx->opt.pool_guard < 0 ? PADNE_OK : workspace_poison(ctx);
 }
 
 constexpr size_t kPoolCacheLimit = (size_t)240 << 30;  // bytes kept for reuse (the card has 288 GB; a failed hipMalloc releases them and retries)
 
-static size_t pool_round(size_t bytes) {
-    if (bytes < 256) bytes = 256;
-    if (bytes >= ((size_t)1 << 20)) return (bytes + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);   // MiB granules
-    size_t p = 256;
-    while (p < bytes) p <<= 1;
-    return p;
+// ---- the guarded mode, PADNE_POOL_GUARD=<fill byte> (tests/test_device_memory.py; the layout of a block: pool_book.hpp) ----
+// The zones hold a canary byte that differs from the fill byte and, like 0xff, reads as a negative integer in every width.
+static unsigned char pool_canary(const padne_ctx *ctx) { return ctx->opt.pool_guard == 0xa5 ? 0xc3 : 0xa5; }
+
+// zones and fill of a block about to be handed out.  Fill, then wait: the block may be used on any stream.
+static int pool_guard_arm(padne_ctx *ctx, void *p) {
+    const PoolBook::Block &b = *ctx->pool.find(p);
+    char *base = (char *)b.base;
+    PADNE_HIP_CHECK(hipMemsetAsync(base, b.canary, b.front(), ctx->stream));
+    if (b.requested > 0) PADNE_HIP_CHECK(hipMemsetAsync(p, ctx->opt.pool_guard, b.requested, ctx->stream));
+    PADNE_HIP_CHECK(hipMemsetAsync(base + b.back_begin(), b.canary, b.back_bytes(), ctx->stream));
+    PADNE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    ++ctx->pool_guard_allocs;
+    return PADNE_OK;
+}
+
+// both zones of a guarded block that is being freed against its canary.  Waits for the whole device: the block may have been
+// used on another stream.  A changed zone is counted and described, nothing else happens.
+static void pool_guard_check(padne_ctx *ctx, const PoolBook::Block &b) {
+    if (hipDeviceSynchronize() != hipSuccess) {
+        (void)hipGetLastError();
+        return;
+    }
+    std::vector<unsigned char> h(std::max(b.front(), b.back_bytes()));
+    for (int side = 1; side <= 2; ++side) {
+        const size_t begin = side == 1 ? 0 : b.back_begin(), len = side == 1 ? b.front() : b.back_bytes();
+        if (hipMemcpy(h.data(), (const char *)b.base + begin, len, hipMemcpyDeviceToHost) != hipSuccess) {
+            (void)hipGetLastError();
+            return;
+        }
+        size_t i = 0;
+        while (i < len && h[i] == b.canary) ++i;
+        if (i == len) continue;
+        padne_ctx::PoolViolation v;
+        v.requested = (long long)b.requested;
+        v.side = side;
+        v.offset = (long long)(begin + i) - (long long)b.front();
+        if (ctx->pool_guard_violations++ == 0) ctx->pool_first_violation = v;
+        ctx->pool_last_violation = v;
+        set_error("pool guard: a block of %lld bytes was written %s: first changed byte at offset %lld of the block",
+                  v.requested, side == 1 ? "in front of its start" : "behind its end", v.offset);
+    }
 }
 
 void *pool_alloc(padne_ctx *ctx, size_t bytes) {
-    const size_t want = pool_round(bytes);
-    auto it = ctx->pool_free_blocks.lower_bound(want);
-    if (it != ctx->pool_free_blocks.end() && it->first <= want + want / 2 + ((size_t)1 << 20)) {
-        void *p = it->second;
-        ctx->pool_cached_bytes -= it->first;
-        ctx->pool_free_blocks.erase(it);
-        return p;
+    const bool guard = ctx->opt.pool_guard >= 0;
+    const unsigned char canary = pool_canary(ctx);
+    void *p = ctx->pool.take(bytes, guard, canary);
+    if (p == nullptr) {
+        const size_t want = PoolBook::underlying(bytes, guard);
+        void *base = nullptr;
+        const bool trace = ctx->opt.verbose_pool;      // every miss of the cache (steady state: none)
+        if (trace) fprintf(stderr, "[pool] %s hipMalloc %zu bytes (cached %zu)\n", ctx->is_aux ? "aux" : "main", want, ctx->pool.cached_bytes);
+        hipError_t e = hipMalloc(&base, want);
+        if (e != hipSuccess) {   // give cached blocks back to the driver and retry once
+            (void)hipGetLastError();
+            pool_release_all(ctx);
+            e = hipMalloc(&base, want);
+        }
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("hipMalloc of %zu bytes failed: %s", want, hipGetErrorString(e));
+            return nullptr;
+        }
+        p = ctx->pool.adopt(base, bytes, guard, canary);
     }
-    void *p = nullptr;
-    const bool trace = ctx->opt.verbose_pool;      // every miss of the cache (steady state: none)
-    if (trace) fprintf(stderr, "[pool] %s hipMalloc %zu bytes (cached %zu)\n", ctx->is_aux ? "aux" : "main", want, ctx->pool_cached_bytes);
-    hipError_t e = hipMalloc(&p, want);
-    if (e != hipSuccess) {   // give cached blocks back to the driver and retry once
-        (void)hipGetLastError();
-        pool_release_all(ctx);
-        e = hipMalloc(&p, want);
-    }
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        set_error("hipMalloc of %zu bytes failed: %s", want, hipGetErrorString(e));
+    if (guard && pool_guard_arm(ctx, p) != PADNE_OK) {
+        ctx->pool.give_back(p, kPoolCacheLimit);
         return nullptr;
     }
-    ctx->pool_sizes[p] = want;
     return p;
 }
 
 void pool_free(padne_ctx *ctx, void *p) {
     if (p == nullptr) return;
-    auto it = ctx->pool_sizes.find(p);
-    if (it == ctx->pool_sizes.end()) {
+    const PoolBook::Block *b = ctx->pool.find(p);
+    if (b == nullptr) {
         padne_ctx *other = ctx->is_aux ? ctx->parent : ctx->aux;     // a block of the sibling stream's pool
-        if (other != nullptr && other->pool_sizes.count(p)) {
+        if (other != nullptr && other->pool.find(p) != nullptr) {
             pool_free(other, p);
             return;
         }
         (void)hipFree(p);                // not ours: plain free
         return;
     }
-    if (ctx->pool_cached_bytes + it->second > kPoolCacheLimit) {
-        if (ctx->opt.verbose_pool) fprintf(stderr, "[pool] cache limit: hipFree %zu bytes\n", it->second);
+    if (b->cached) return;
+    if (b->guarded) pool_guard_check(ctx, *b);
+    if (!ctx->pool.give_back(p, kPoolCacheLimit)) {
+        if (ctx->opt.verbose_pool) fprintf(stderr, "[pool] cache limit: hipFree %zu bytes\n", b->size);
         (void)hipStreamSynchronize(ctx->stream);
-        (void)hipFree(p);
-        ctx->pool_sizes.erase(it);
-        return;
+        (void)hipFree(b->base);
+        ctx->pool.forget(p);
     }
-    ctx->pool_free_blocks.emplace(it->second, p);
-    ctx->pool_cached_bytes += it->second;
 }
 
 void pool_release_all(padne_ctx *ctx) {
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    for (auto &kv : ctx->pool_free_blocks) {
-        (void)hipFree(kv.second);
-        ctx->pool_sizes.erase(kv.second);
-    }
-    ctx->pool_free_blocks.clear();
-    ctx->pool_cached_bytes = 0;
+    ctx->pool.release_cached([](void *base) { (void)hipFree(base); });
 }
 
 static int ctx_init_resources(padne_ctx *ctx) {
@@ -340,9 +387,75 @@ using namespace padne;
 // (test header) the environment switches again, for a context that lives across a change of them
 extern "C" int padne_ctx_reload_options(padne_ctx *ctx) {
     PADNE_REQUIRE(ctx, "ctx");
+    const bool was_guarded = ctx->opt.pool_guard >= 0;
     options_from_env(&ctx->opt);
     ctx->p2p_timeout_ms = ctx->opt.p2p_timeout_ms;
     if (ctx->aux != nullptr) ctx->aux->opt = ctx->opt;
+    if ((ctx->opt.pool_guard >= 0) != was_guarded) {     // no block cached under one mode is handed out under the other
+        pool_release_all(ctx);
+        if (ctx->aux != nullptr) pool_release_all(ctx->aux);
+    }
+    return PADNE_OK;
+}
+
+// (probe header) counters and self-test of the pool's guarded mode
+extern "C" int padne_test_pool_guard(padne_ctx *ctx, int32_t op, int64_t *out) {
+    PADNE_REQUIRE(ctx && out && op >= 0 && op <= 2, "arguments");
+    PADNE_HIP_CHECK(hipSetDevice(ctx->device));
+    padne_ctx *both[2] = {ctx, ctx->aux};
+    if (op == 1) {
+        for (padne_ctx *c : both)
+            if (c != nullptr) {
+                c->pool_guard_allocs = c->pool_guard_violations = 0;
+                c->pool_first_violation = c->pool_last_violation = padne_ctx::PoolViolation();
+            }
+    }
+    int64_t all_fill = ctx->opt.pool_guard;
+    if (op == 2) {
+        PADNE_REQUIRE(ctx->opt.pool_guard >= 0, "the self-test needs PADNE_POOL_GUARD");
+        constexpr size_t kBytes = 1000;
+        unsigned char *a = (unsigned char *)pool_alloc(ctx, kBytes), *b = (unsigned char *)pool_alloc(ctx, kBytes);
+        if (a == nullptr || b == nullptr) {
+            pool_free(ctx, a);
+            pool_free(ctx, b);
+            return PADNE_E_NOMEM;
+        }
+        unsigned char h[kBytes], w[8];
+        int rc = PADNE_OK;
+        if (hipMemcpy(h, a, kBytes, hipMemcpyDeviceToHost) != hipSuccess) rc = PADNE_E_HIP;
+        all_fill = 1;
+        for (size_t i = 0; i < kBytes; ++i) all_fill &= h[i] == (unsigned char)ctx->opt.pool_guard;
+        // eight bytes behind the end of the first block and eight in front of the second: inside their guard zones
+        memset(w, (unsigned char)~pool_canary(ctx), sizeof(w));
+        if (rc == PADNE_OK && (hipMemcpy(a + kBytes, w, sizeof(w), hipMemcpyHostToDevice) != hipSuccess ||
+                               hipMemcpy(b - sizeof(w), w, sizeof(w), hipMemcpyHostToDevice) != hipSuccess))
+            rc = PADNE_E_HIP;
+        pool_free(ctx, a);
+        pool_free(ctx, b);
+        if (rc != PADNE_OK) {
+            set_error("pool guard self-test: %s", hipGetErrorString(hipGetLastError()));
+            return rc;
+        }
+    }
+    memset(out, 0, sizeof(int64_t) * 8);
+    const padne_ctx *first = nullptr, *last = nullptr;
+    for (padne_ctx *c : both)
+        if (c != nullptr) {
+            out[0] += c->pool_guard_allocs;
+            out[1] += c->pool_guard_violations;
+            if (c->pool_guard_violations > 0) {
+                if (first == nullptr) first = c;
+                last = c;
+            }
+        }
+    if (first != nullptr) {
+        out[2] = first->pool_first_violation.requested;
+        out[3] = first->pool_first_violation.side;
+        out[4] = first->pool_first_violation.offset;
+        out[5] = last->pool_last_violation.side;
+        out[6] = last->pool_last_violation.offset;
+    }
+    out[7] = all_fill;
     return PADNE_OK;
 }
 
@@ -400,8 +513,11 @@ int padne_ctx_destroy(padne_ctx *ctx) {
     }
     comm_destroy(ctx);
     pool_release_all(ctx);
-    for (auto &kv : ctx->pool_sizes) (void)hipFree(kv.first);   // blocks still held by live matrices
-    ctx->pool_sizes.clear();
+    for (auto &kv : ctx->pool.blocks) {                         // blocks still held by live matrices
+        if (kv.second.guarded) pool_guard_check(ctx, kv.second);
+        (void)hipFree(kv.second.base);
+    }
+    ctx->pool.blocks.clear();
     if (ctx->halo_export) hipFree(ctx->halo_export);
     if (ctx->ws) hipFree(ctx->ws);
     if (ctx->partials) hipFree(ctx->partials);

@@ -12,6 +12,7 @@
 #include "../../include/padne_hip.h"
 #include "../../include/padne_hip_test.h"
 #include "../../include/padne_hip_probe.h"
+#include "pool_book.hpp"
 
 #include <atomic>
 
@@ -149,6 +150,9 @@ struct padne_options {
     long long force_spgemm_split = 0;  // spgemm_split:<slots>
     // PADNE_VERBOSE=amg,xw,pool: diagnostics on stderr
     bool verbose_amg = false, verbose_xw = false, verbose_pool = false;
+    // PADNE_POOL_GUARD=<hex byte>: the pool's debug mode (tests).  Every block handed out lies between two guard zones that
+    // are checked when it is freed, its bytes and the whole workspace are filled with this byte first; -1: off
+    int pool_guard = -1;
 };
 namespace padne { void options_from_env(padne_options *o); }
 
@@ -202,9 +206,13 @@ struct padne_ctx {
     hipEvent_t ev_order = nullptr;
     // caching device allocator (see pool_alloc): hipMalloc/hipFree of GB-sized blocks cost up to hundreds of
     // milliseconds, which would dominate the multigrid setup that runs inside every solve
-    std::multimap<size_t, void *> pool_free_blocks;
-    std::unordered_map<void *, size_t> pool_sizes;
-    size_t pool_cached_bytes = 0;
+    padne::PoolBook pool;
+    // the guarded mode (PADNE_POOL_GUARD): blocks handed out with guard zones, zones found changed at a free, and of the
+    // first and the last of those the requested bytes, the side (1 front, 2 back) and the offset of the first changed byte
+    // from the pointer handed out (negative in the front zone)
+    struct PoolViolation { long long requested = 0, side = 0, offset = 0; };
+    long long pool_guard_allocs = 0, pool_guard_violations = 0;
+    PoolViolation pool_first_violation, pool_last_violation;
 };
 
 namespace padne {
@@ -401,7 +409,8 @@ int launch_combine_block(padne_ctx *ctx, long long N, int n_cols, int n_out, lon
 
 // Per-context caching allocator.  All work of a context is ordered on its one stream, so a block handed back
 // may be reused by later launches without synchronisation.  Blocks are kept (up to kPoolCacheLimit) until the
-// context is destroyed.
+// context is destroyed.  Under PADNE_POOL_GUARD (tests) every block is poisoned and lies between guard zones that
+// pool_free checks: see capi.hip and pool_book.hpp.
 void *pool_alloc(padne_ctx *ctx, size_t bytes);     // nullptr on failure (error message set)
 void pool_free(padne_ctx *ctx, void *p);
 void pool_release_all(padne_ctx *ctx);

@@ -1925,21 +1925,15 @@ extern "C" int padne_amg_apply(padne_ctx *ctx, padne_csr *a, const double *r_hos
     PADNE_HIP_CHECK(hipSetDevice(ctx->device));
     PADNE_TRY(amg_setup(ctx, a));
     const size_t bytes = sizeof(double) * (size_t)a->n_rows;
+    Scratch sc(ctx);
     double *r = nullptr, *z = nullptr;
-    PADNE_HIP_CHECK(hipMalloc((void **)&r, bytes));
-    if (hipMalloc((void **)&z, bytes) != hipSuccess) {
-        (void)hipFree(r);
-        set_error("hipMalloc failed");
-        return PADNE_E_NOMEM;
-    }
+    PADNE_TRY(sc.alloc(&r, (size_t)a->n_rows));
+    PADNE_TRY(sc.alloc(&z, (size_t)a->n_rows));
     int rc = PADNE_OK;
     if (hipMemcpyAsync(r, r_host, bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = PADNE_E_HIP;
     if (rc == PADNE_OK) rc = amg_apply(ctx, a, r, z, slot(ctx, SLOT_TMP), nullptr);
-    if (rc == PADNE_OK && (hipMemcpyAsync(z_host, z, bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-                           hipStreamSynchronize(ctx->stream) != hipSuccess))
-        rc = PADNE_E_HIP;
-    (void)hipFree(r);
-    (void)hipFree(z);
+    if (rc == PADNE_OK && hipMemcpyAsync(z_host, z, bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = PADNE_E_HIP;
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == PADNE_OK) rc = PADNE_E_HIP;
     if (rc == PADNE_E_HIP) set_error("multigrid apply failed: %s", hipGetErrorString(hipGetLastError()));
     return rc;
 }
