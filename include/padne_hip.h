@@ -636,6 +636,45 @@ int padne_thermal_report(padne_ctx *ctx, padne_thermal *th, int32_t n_cols, int6
                          double *face_mean_out, double *mesh_max_out, int64_t *mesh_vertex_out, double *mesh_heat_out,
                          double *mesh_loss_out, double *env_out, int32_t *env_case_out);
 
+/* ---- stack: heat conduction between layers through the dielectric --------------------------------
+ * No reference counterpart ("Stack").  padne_thermal_create with the layer mesh_layer[m] in [0, n_layer) of every
+ * mesh and n_pair pairs of layers (pair_a[p] != pair_b[p], every unordered pair at most once) with an areal conductance
+ * pair_g[p] >= 0 [W / (K length^2)] (0: no pair).  For both sides (s -> t) of a pair and every vertex v of a mesh of layer s:
+ * f = the owner face of xy[v] among the meshes of layer t by the rule of padne_sampler_create (none: nothing), lambda_k =
+ * o_k / ((o_a + o_b) + o_c) the sampler's weights of its corners, and for k = 0, 1, 2 a thermal conductance
+ *     c_k = ((0.5 pair_g) M_v) lambda_k       (c_k == 0: nothing)
+ * between v and corner k of f.  G = the sum of these links: G_ij = -(the sum of the links between i and j, at most one from
+ * each side), G_ii = the sum along row i, in ascending j, of (-G_ij) from 0.0.  The handle's matrix becomes A' = A + G on
+ * the union pattern (one rounded add where both are stored, the diagonal included), with ascending columns, before the
+ * entry returns: padne_thermal_matrix, the solves, padne_coupled_* and padne_transient_* work on A'.  G annihilates
+ * constants: the film loss still equals the heat put in.  M_v, film M_v and the load are those of padne_thermal_create, and
+ * with n_pair = 0 so is the matrix, bit for bit.  Meshes the system does not keep take no part.  No floating-point atomics:
+ * two calls give the same bits.  PADNE_E_INVALID in addition for a mesh layer or pair layer out of range, a pair that
+ * names one layer twice, a repeated pair and a pair_g that is negative or not finite.  Nothing crosses PCIe but the
+ * O(n_mesh + n_link + n_pair) lists. */
+int padne_thermal_create_stacked(padne_ctx *ctx, const padne_csr *L, int64_t n_potential, int32_t n_mesh, const double *kappa,
+                                 const double *film, int64_t n_link, const int64_t *link_a, const int64_t *link_b,
+                                 const double *link_g, int32_t n_layer, const int32_t *mesh_layer, int32_t n_pair,
+                                 const int32_t *pair_a, const int32_t *pair_b, const double *pair_g, padne_thermal **out);
+/* After a solve of n_cols columns on a handle of padne_thermal_create_stacked: flow_out[n_cols][n_pair] = the heat [W] that
+ * flows from layer pair_a[p] to layer pair_b[p], the sum over the vertices i of layer a and their stored partners j in layer
+ * b, ascending, of (-G_ij)(theta_i - theta_j); area_out[n_pair] = (the same sum of (-G_ij)) / pair_g[p], the coupled area
+ * (0 for pair_g = 0).  n_cols = 0: the areas alone, no solve needed.  Tiles of 256 vertices of one mesh in the fixed order of
+ * padne_thermal_report, the meshes of layer a in ascending order: two calls give the same bits. */
+int padne_thermal_stack_flows(padne_ctx *ctx, padne_thermal *th, int32_t n_cols, double *flow_out, double *area_out);
+/* Read-outs of the coupling (tests).  counts_out[4] = pairs, sides (two per pair with pair_g > 0, in pair order, a -> b
+ * first), (side, vertex) slots, stored off-diagonals of G. */
+int padne_thermal_stack_sizes(const padne_thermal *th, int64_t *counts_out);
+/* The slots, side by side, within a side the vertices of the source layer in ascending global order: side_offset_out
+ * [sides + 1] the first slot of every side, vertex_out[n_query] the vertex, owner_out[n_query] its owner face (global, -1:
+ * none), weight_out[n_query][3] = lambda_k and cond_out[n_query][3] = c_k (0 without an owner). */
+int padne_thermal_stack_links(padne_ctx *ctx, const padne_thermal *th, int64_t n_query, int64_t *side_offset_out,
+                              int32_t *vertex_out, int32_t *owner_out, double *weight_out, double *cond_out);
+/* G: its off-diagonals as CSR (indptr_out[n_potential + 1], indices_out[nnz] ascending, data_out[nnz]) and its diagonal
+ * diag_out[n_potential] (0 for a row without partners). */
+int padne_thermal_stack_matrix(padne_ctx *ctx, const padne_thermal *th, int64_t nnz, int32_t *indptr_out, int32_t *indices_out,
+                               double *data_out, double *diag_out);
+
 /* ---- electro-thermal coupling: the copper's conductance follows its temperature ----------------
  * No reference counterpart ("Electro-thermal").  Face t of mesh m conducts sigma[m] * s[t],
  *     s[t] = 1 / (1 + alpha[m] * ((mean[t] + ambient) - conductance_temperature)),

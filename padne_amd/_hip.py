@@ -157,6 +157,12 @@ SIGNATURES = {
                                           C.POINTER(SolveInfo)]),
     "padne_thermal_face_power": (C.c_int, [_P, _P, C.c_int32, _PF64]),
     "padne_thermal_report": (C.c_int, [_P, _P, C.c_int32, _I64, _I64, C.c_int32, _PF64, _PF64, _PI64, _PF64, _PF64, _PF64, _PI32]),
+    "padne_thermal_create_stacked": (C.c_int, [_P, _P, _I64, C.c_int32, _PF64, _PF64, _I64, _PI64, _PI64, _PF64, C.c_int32, _PI32,
+                                               C.c_int32, _PI32, _PI32, _PF64, C.POINTER(_P)]),
+    "padne_thermal_stack_flows": (C.c_int, [_P, _P, C.c_int32, _PF64, _PF64]),
+    "padne_thermal_stack_sizes": (C.c_int, [_P, _PI64]),
+    "padne_thermal_stack_links": (C.c_int, [_P, _P, _I64, _PI64, _PI32, _PI32, _PF64, _PF64]),
+    "padne_thermal_stack_matrix": (C.c_int, [_P, _P, _I64, _PI32, _PI32, _PF64, _PF64]),
     "padne_transient_create": (C.c_int, [_P, _P, C.c_int32, _PF64, C.POINTER(_P)]),
     "padne_transient_destroy": (C.c_int, [_P]),
     "padne_transient_capacity": (C.c_int, [_P, _P, _PF64]),
@@ -1049,9 +1055,14 @@ class KktPlan:
 class Thermal:
     """``padne_thermal``: the thermal sheet problem A theta = b on the meshes an assembled system ``L`` keeps on the device
     (include/padne_hip.h, "thermal").  ``kappa`` and ``film`` per mesh, ``links`` an (n, 2) array of unknowns with
-    ``link_g`` (n,) W/K.  Holds A with its hierarchy, the lumped areas and, after a solve, the face powers and theta."""
+    ``link_g`` (n,) W/K.  Holds A with its hierarchy, the lumped areas and, after a solve, the face powers and theta.
 
-    def __init__(self, L: "CsrMatrix", n_potential: int, kappa, film, link_a=(), link_b=(), link_g=()):
+    With ``mesh_layer`` (the layer of every mesh) the handle is made by ``padne_thermal_create_stacked`` (include/padne_hip.h,
+    "stack"): ``pairs`` is a sequence of (layer a, layer b, g [W/(K mesh-unit^2)]) and the matrix is A' = A + G, the heat
+    conduction between the layers of every pair; ``stack_flows`` and the ``stack_*`` read-outs then work."""
+
+    def __init__(self, L: "CsrMatrix", n_potential: int, kappa, film, link_a=(), link_b=(), link_g=(), *, mesh_layer=None,
+                 pairs=(), n_layer=None):
         self.ctx, self.L = L.ctx, L
         kap, flm = _f64(kappa).reshape(-1), _f64(film).reshape(-1)
         la, lb, lg = _i64(link_a).reshape(-1), _i64(link_b).reshape(-1), _f64(link_g).reshape(-1)
@@ -1060,11 +1071,63 @@ class Thermal:
         if not (la.shape == lb.shape == lg.shape):
             raise ValueError("link_a, link_b and link_g must list the same links")
         h = _P()
-        _check(self.ctx._lib.padne_thermal_create(self.ctx._h, L._h, int(n_potential), kap.shape[0], _ptr(kap, _PF64),
-                                                  _ptr(flm, _PF64), la.shape[0], _ptr(la, _PI64), _ptr(lb, _PI64), _ptr(lg, _PF64),
-                                                  C.byref(h)))
+        self.stacked, self.n_pair = mesh_layer is not None, 0
+        if not self.stacked:
+            if len(pairs):
+                raise ValueError("pairs of layers need mesh_layer")
+            _check(self.ctx._lib.padne_thermal_create(self.ctx._h, L._h, int(n_potential), kap.shape[0], _ptr(kap, _PF64),
+                                                      _ptr(flm, _PF64), la.shape[0], _ptr(la, _PI64), _ptr(lb, _PI64),
+                                                      _ptr(lg, _PF64), C.byref(h)))
+        else:
+            ml = _i32(mesh_layer).reshape(-1)
+            if ml.shape != kap.shape:
+                raise ValueError("one layer per mesh")
+            pairs = list(pairs)
+            pa, pb = _i32([p[0] for p in pairs]), _i32([p[1] for p in pairs])
+            pg = _f64([p[2] for p in pairs])
+            if n_layer is None:
+                n_layer = max([1] + [int(x) + 1 for x in ml] + [int(x) + 1 for x in pa] + [int(x) + 1 for x in pb])
+            _check(self.ctx._lib.padne_thermal_create_stacked(
+                self.ctx._h, L._h, int(n_potential), kap.shape[0], _ptr(kap, _PF64), _ptr(flm, _PF64), la.shape[0], _ptr(la, _PI64),
+                _ptr(lb, _PI64), _ptr(lg, _PF64), int(n_layer), _ptr(ml, _PI32), len(pairs), _ptr(pa, _PI32), _ptr(pb, _PI32),
+                _ptr(pg, _PF64), C.byref(h)))
+            self.n_pair = len(pairs)
         self._h = h
         self.n_potential, self.n_mesh = int(n_potential), kap.shape[0]
+
+    def stack_sizes(self):
+        """(pairs, sides, (side, vertex) slots, stored off-diagonals of G) of a stacked handle."""
+        out = np.zeros(4, dtype=np.int64)
+        _check(self.ctx._lib.padne_thermal_stack_sizes(self._h, _ptr(out, _PI64)))
+        return tuple(int(x) for x in out)
+
+    def stack_links(self):
+        """The link slots of a stacked handle: (side offsets (sides + 1,), vertex (n,), owner face (n,) or -1, weights (n, 3),
+        conductances (n, 3)), side by side (include/padne_hip.h)."""
+        _, n_side, n, _ = self.stack_sizes()
+        off = np.zeros(n_side + 1, dtype=np.int64)
+        vert, owner = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
+        w, c = np.empty((n, 3), dtype=np.float64), np.empty((n, 3), dtype=np.float64)
+        _check(self.ctx._lib.padne_thermal_stack_links(self.ctx._h, self._h, n, _ptr(off, _PI64), _ptr(vert, _PI32),
+                                                       _ptr(owner, _PI32), _ptr(w, _PF64), _ptr(c, _PF64)))
+        return off, vert, owner, w, c
+
+    def stack_matrix(self):
+        """G of a stacked handle: (indptr, indices, data) of its off-diagonals as CSR and its diagonal (n_potential,)."""
+        nnz = self.stack_sizes()[3]
+        indptr, indices = np.empty(self.n_potential + 1, dtype=np.int32), np.empty(nnz, dtype=np.int32)
+        data, diag = np.empty(nnz, dtype=np.float64), np.empty(self.n_potential, dtype=np.float64)
+        _check(self.ctx._lib.padne_thermal_stack_matrix(self.ctx._h, self._h, nnz, _ptr(indptr, _PI32), _ptr(indices, _PI32),
+                                                        _ptr(data, _PF64), _ptr(diag, _PF64)))
+        return indptr, indices, data, diag
+
+    def stack_flows(self, n_cols: int):
+        """On the theta of the last solve: (flow (n_cols, n_pair) [W] from layer a to layer b of every pair, coupled area
+        (n_pair,)).  ``n_cols`` 0: the areas alone."""
+        n_cols = int(n_cols)
+        flow, area = np.zeros((n_cols, self.n_pair), dtype=np.float64), np.zeros(self.n_pair, dtype=np.float64)
+        _check(self.ctx._lib.padne_thermal_stack_flows(self.ctx._h, self._h, n_cols, _ptr(flow, _PF64), _ptr(area, _PF64)))
+        return flow, area
 
     def close(self):
         if getattr(self, "_h", None) and self.ctx._h:

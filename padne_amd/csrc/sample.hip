@@ -11,8 +11,7 @@
 //   the lowest global index.  The index only proposes candidates; tests/sampling_ref.py states the rule by brute force.
 //
 // This file is compiled with -ffp-contract=off, like assemble.hip: every expression rounds as written.
-#include "common.hpp"
-#include "face.hpp"
+#include "locate.hpp"
 
 #include <float.h>
 
@@ -22,30 +21,12 @@
 
 namespace padne {
 
-constexpr int kListBound = 16;                    // list entries per face of a layer at the most; beyond it the grid is coarsened
 constexpr long long kMaxSamples = 1LL << 26;      // query points / pixels of one call
-constexpr int kMaxBinsPerSide = 32768;
-
-// the grid of one layer: bin (bx, by) is number bin0 + by * nbx + bx of the sampler's bins
-struct LayerGrid {
-    double x0 = 0, y0 = 0, sx = 0, sy = 0;        // lower corner of the layer's bounding box, bins per mm
-    int nbx = 1, nby = 1;
-    long long bin0 = 0;
-};
 
 struct RasterSpec {
     double x0, y0, dx, dy;
     long long width;
 };
-
-// the bin of a coordinate: monotone in x (a difference, a product with a positive constant, floor and a clamp are), so a
-// point between the ends of an interval falls into a bin between the bins of the ends -- also beyond the bounding box
-__device__ __forceinline__ int bin_of(double x, double x0, double s, int n) {
-    if (n == 1) return 0;
-    double t = floor((x - x0) * s);
-    t = fmin(fmax(t, 0.0), (double)(n - 1));
-    return (int)t;
-}
 
 // The bins face f may own a point of: those its bounding box meets, grown by a margin that covers the points the rounding
 // of orient() can add to it.  With S the longer side of the box, A the area and d the distance of q from the face, one of
@@ -106,7 +87,9 @@ __global__ __launch_bounds__(256) void sampler_bin_kernel(long long n_tri, const
                                                           int *__restrict__ bin_face) {
     const long long f = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= n_tri) return;
-    const LayerGrid g = grids[mesh_layer[find_segment(mesh_toff, n_mesh, f)]];
+    const int layer = mesh_layer[find_segment(mesh_toff, n_mesh, f)];
+    if (layer < 0) return;                        // a mesh the index leaves out (stack.hip: a layer no pair names)
+    const LayerGrid g = grids[layer];
     int bx0, bx1, by0, by1;
     if (!face_bin_range(gtri, xy, f, g, bx0, bx1, by0, by1)) return;
     for (int by = by0; by <= by1; ++by)
@@ -114,11 +97,6 @@ __global__ __launch_bounds__(256) void sampler_bin_kernel(long long n_tri, const
             const int at = atomicAdd(&count[g.bin0 + (long long)by * g.nbx + bx], 1);
             if (FILL) bin_face[at] = (int)f;
         }
-}
-
-// side of q of the edge (i, k) as the face runs it (the owner rule above)
-__device__ __forceinline__ double edge_side(int gi, int gk, double xi, double yi, double xk, double yk, double qx, double qy) {
-    return gi < gk ? orient(xi, yi, xk, yk, qx, qy) : -orient(xk, yk, xi, yi, qx, qy);
 }
 
 // One thread per query: the bin of q, the candidates of that bin, the owner, then the owner's values.  RASTER: q is the
@@ -148,32 +126,11 @@ __global__ __launch_bounds__(256) void sample_kernel(const LayerGrid g, const in
             qx = q_xy[2 * idx];
             qy = q_xy[2 * idx + 1];
         }
-        const long long bin = g.bin0 + (long long)bin_of(qy, g.y0, g.sy, g.nby) * g.nbx + bin_of(qx, g.x0, g.sx, g.nbx);
-        const int lo = bin_off[bin], hi = bin_off[bin + 1];
-        n_tested = (unsigned long long)(hi - lo);
-        int owner = 0x7fffffff;
-        double wa = 0.0, wb = 0.0, wc = 0.0;
-        for (int e = lo; e < hi; ++e) {
-            const int f = bin_face[e];
-            const int a = gtri[3 * (long long)f], b = gtri[3 * (long long)f + 1], c = gtri[3 * (long long)f + 2];
-            const double xa = xy[2 * (long long)a], ya = xy[2 * (long long)a + 1];
-            const double xb = xy[2 * (long long)b], yb = xy[2 * (long long)b + 1];
-            const double xc = xy[2 * (long long)c], yc = xy[2 * (long long)c + 1];
-            const double oa = edge_side(b, c, xb, yb, xc, yc, qx, qy);
-            const double ob = edge_side(c, a, xc, yc, xa, ya, qx, qy);
-            const double oc = edge_side(a, b, xa, ya, xb, yb, qx, qy);
-            const bool in = ((oa >= 0.0 && ob >= 0.0 && oc >= 0.0) || (oa <= 0.0 && ob <= 0.0 && oc <= 0.0)) &&
-                            !(oa == 0.0 && ob == 0.0 && oc == 0.0);
-            if (in && f < owner) {
-                owner = f;
-                wa = oa;
-                wb = ob;
-                wc = oc;
-            }
-        }
+        double wa, wb, wc;
+        const int owner = locate_owner(g, bin_off, bin_face, gtri, xy, qx, qy, wa, wb, wc, n_tested);
         int face = -1;
         double v = NAN, jx = NAN, jy = NAN, p = NAN;
-        if (owner != 0x7fffffff) {
+        if (owner != kNoOwner) {
             face = owner;
             const long long a = gtri[3 * (long long)owner], b = gtri[3 * (long long)owner + 1], c = gtri[3 * (long long)owner + 2];
             const double va = V[a], vb = V[b], vc = V[c];
@@ -251,6 +208,92 @@ static void set_scale(LayerGrid &g, const double lo[2], const double hi[2]) {
     g.sy = g.nby > 1 ? g.nby / (hi[1] - lo[1]) : 0.0;
 }
 
+int padne::locate_global_corners(padne_ctx *ctx, long long n_tri, const int *tri, int n_mesh, const long long *mesh_voff,
+                                 const long long *mesh_toff, int *gtri, int *err_dev) {
+    if (n_tri > 0) {
+        hipLaunchKernelGGL(sampler_corners_kernel, dim3(nblk(n_tri)), dim3(256), 0, ctx->stream, n_tri, tri, n_mesh, mesh_voff,
+                           mesh_toff, gtri, err_dev);
+        PADNE_HIP_CHECK(hipGetLastError());
+    }
+    return PADNE_OK;
+}
+
+int padne::locate_build_bins(padne_ctx *ctx, int n_layer, const double *lo, const double *hi, int64_t bins_hint,
+                             const std::vector<int64_t> &layer_faces, long long n_tri, const int *gtri, const double *xy,
+                             int n_mesh, const long long *mesh_toff, const int *mesh_layer, std::vector<LayerGrid> &grid,
+                             std::vector<int64_t> &layer_entries, int **bin_off, int **bin_face) {
+    hipStream_t st = ctx->stream;
+    Scratch sc(ctx);
+    struct PoolBlock {      // the counters of the round under way
+        padne_ctx *ctx;
+        void *p;
+        ~PoolBlock() { if (p) pool_free(ctx, p); }
+    } count{ctx, nullptr};
+    LayerGrid *d_grid = nullptr;
+    PADNE_TRY(sc.alloc(&d_grid, (size_t)n_layer));
+    for (int l = 0; l < n_layer; ++l)
+        choose_grid(grid[l], &lo[2 * l], &hi[2 * l], bins_hint > 0 ? bins_hint : std::max<int64_t>(1, layer_faces[l] / 2));
+    for (;;) {
+        long long n_bins = 0;
+        for (int l = 0; l < n_layer; ++l) {
+            set_scale(grid[l], &lo[2 * l], &hi[2 * l]);
+            grid[l].bin0 = n_bins;
+            n_bins += (long long)grid[l].nbx * grid[l].nby;
+        }
+        PADNE_REQUIRE(n_bins < (1LL << 30), "too many bins");
+        if (*bin_off) pool_free(ctx, *bin_off);
+        *bin_off = nullptr;
+        PADNE_TRY(sampler_alloc(ctx, bin_off, (size_t)n_bins + 1));
+        if (count.p) pool_free(ctx, count.p);
+        count.p = pool_alloc(ctx, sizeof(int) * (size_t)(n_bins + 1));
+        if (count.p == nullptr) return PADNE_E_NOMEM;
+        int *d_count = (int *)count.p;
+        PADNE_HIP_CHECK(hipMemsetAsync(d_count, 0, sizeof(int) * (size_t)(n_bins + 1), st));
+        PADNE_HIP_CHECK(hipMemcpyAsync(d_grid, grid.data(), sizeof(LayerGrid) * (size_t)n_layer, hipMemcpyHostToDevice, st));
+        if (n_tri > 0) {
+            hipLaunchKernelGGL(sampler_bin_kernel<false>, dim3(nblk(n_tri)), dim3(256), 0, st, n_tri, gtri, xy,
+                               n_mesh, mesh_toff, mesh_layer, d_grid, d_count, (int *)nullptr);
+            PADNE_HIP_CHECK(hipGetLastError());
+        }
+        bool negative = false;
+        int64_t total = 0;
+        PADNE_TRY(exclusive_scan_i32_flagged(ctx, d_count, *bin_off, n_bins, &total, &negative));
+        if (negative || total >= (1LL << 31)) {       // a count wrapped: only far finer than kListBound allows; coarsen
+            total = -1;
+        }
+        std::vector<int> first(n_layer + 1, 0);
+        bool again = false;
+        if (total >= 0) {
+            for (int l = 0; l < n_layer; ++l)
+                PADNE_HIP_CHECK(hipMemcpyAsync(&first[l], *bin_off + grid[l].bin0, sizeof(int), hipMemcpyDeviceToHost, st));
+            PADNE_HIP_CHECK(hipStreamSynchronize(st));
+            first[n_layer] = (int)total;
+        }
+        for (int l = 0; l < n_layer; ++l) {
+            LayerGrid &g = grid[l];
+            layer_entries[l] = total >= 0 ? (int64_t)first[l + 1] - first[l] : -1;
+            const bool too_long = total < 0 || layer_entries[l] > kListBound * layer_faces[l];
+            if (too_long && (g.nbx > 1 || g.nby > 1)) {
+                g.nbx = (g.nbx + 1) / 2;
+                g.nby = (g.nby + 1) / 2;
+                again = true;
+            }
+        }
+        if (again) continue;
+        PADNE_REQUIRE(total >= 0, "the face lists do not fit 32-bit offsets");
+        PADNE_TRY(sampler_alloc(ctx, bin_face, (size_t)total));
+        PADNE_HIP_CHECK(hipMemcpyAsync(d_count, *bin_off, sizeof(int) * (size_t)n_bins, hipMemcpyDeviceToDevice, st));
+        if (n_tri > 0) {
+            hipLaunchKernelGGL(sampler_bin_kernel<true>, dim3(nblk(n_tri)), dim3(256), 0, st, n_tri, gtri, xy,
+                               n_mesh, mesh_toff, mesh_layer, d_grid, d_count, *bin_face);
+            PADNE_HIP_CHECK(hipGetLastError());
+        }
+        PADNE_HIP_CHECK(hipStreamSynchronize(st));
+        break;
+    }
+    return PADNE_OK;
+}
+
 extern "C" int padne_sampler_create(padne_ctx *ctx, int64_t n_vert, const double *xy_host, int64_t n_tri,
                                     const int32_t *tri_host, int32_t n_mesh, const int64_t *mesh_vertex_offset,
                                     const int64_t *mesh_tri_offset, const int32_t *mesh_layer, const double *conductance,
@@ -289,13 +332,7 @@ extern "C" int padne_sampler_create(padne_ctx *ctx, int64_t n_vert, const double
     std::vector<long long> toff(mesh_tri_offset, mesh_tri_offset + n_mesh + 1), voff(mesh_vertex_offset, mesh_vertex_offset + n_mesh + 1);
     Scratch sc(ctx);
     int *d_tri = nullptr, *d_err = nullptr;
-    struct PoolBlock {      // the counters of the round under way
-        padne_ctx *ctx;
-        void *p;
-        ~PoolBlock() { if (p) pool_free(ctx, p); }
-    } count{ctx, nullptr};
     long long *d_voff = nullptr;
-    LayerGrid *d_grid = nullptr;
     PADNE_TRY(sampler_alloc(ctx, &s->xy, (size_t)n_vert * 2));
     PADNE_TRY(sampler_alloc(ctx, &s->V, (size_t)n_vert));
     PADNE_TRY(sampler_alloc(ctx, &s->sigma, (size_t)n_mesh));
@@ -306,7 +343,6 @@ extern "C" int padne_sampler_create(padne_ctx *ctx, int64_t n_vert, const double
     PADNE_TRY(sc.alloc(&d_tri, (size_t)n_tri * 3));
     PADNE_TRY(sc.alloc(&d_voff, (size_t)n_mesh + 1));
     PADNE_TRY(sc.alloc(&d_err, 1));
-    PADNE_TRY(sc.alloc(&d_grid, (size_t)n_layer));
     PADNE_HIP_CHECK(hipMemsetAsync(d_err, 0, sizeof(int), st));
     PADNE_HIP_CHECK(hipMemcpyAsync(s->xy, xy_host, sizeof(double) * 2 * (size_t)n_vert, hipMemcpyHostToDevice, st));
     PADNE_HIP_CHECK(hipMemcpyAsync(s->V, potential_host, sizeof(double) * (size_t)n_vert, hipMemcpyHostToDevice, st));
@@ -315,11 +351,7 @@ extern "C" int padne_sampler_create(padne_ctx *ctx, int64_t n_vert, const double
     PADNE_HIP_CHECK(hipMemcpyAsync(s->mesh_layer, mesh_layer, sizeof(int) * (size_t)n_mesh, hipMemcpyHostToDevice, st));
     PADNE_HIP_CHECK(hipMemcpyAsync(s->toff, toff.data(), sizeof(long long) * (size_t)(n_mesh + 1), hipMemcpyHostToDevice, st));
     PADNE_HIP_CHECK(hipMemcpyAsync(d_voff, voff.data(), sizeof(long long) * (size_t)(n_mesh + 1), hipMemcpyHostToDevice, st));
-    if (n_tri > 0) {
-        hipLaunchKernelGGL(sampler_corners_kernel, dim3(nblk(n_tri)), dim3(256), 0, st, (long long)n_tri, d_tri, (int)n_mesh, d_voff,
-                           s->toff, s->gtri, d_err);
-        PADNE_HIP_CHECK(hipGetLastError());
-    }
+    PADNE_TRY(locate_global_corners(ctx, (long long)n_tri, d_tri, (int)n_mesh, d_voff, s->toff, s->gtri, d_err));
     int h_err = 0;
     PADNE_HIP_CHECK(hipMemcpyAsync(&h_err, d_err, sizeof(int), hipMemcpyDeviceToHost, st));
     PADNE_HIP_CHECK(hipStreamSynchronize(st));
@@ -342,68 +374,10 @@ extern "C" int padne_sampler_create(padne_ctx *ctx, int64_t n_vert, const double
                 hi[2 * l + k] = std::max(hi[2 * l + k], xy_host[2 * v + k]);
             }
     }
-    for (int l = 0; l < n_layer; ++l) {
+    for (int l = 0; l < n_layer; ++l)
         if (!(lo[2 * l] <= hi[2 * l])) lo[2 * l] = lo[2 * l + 1] = hi[2 * l] = hi[2 * l + 1] = 0.0;      // a layer without vertices
-        choose_grid(s->grid[l], &lo[2 * l], &hi[2 * l], bins_hint > 0 ? bins_hint : std::max<int64_t>(1, s->layer_faces[l] / 2));
-    }
-    for (;;) {
-        long long n_bins = 0;
-        for (int l = 0; l < n_layer; ++l) {
-            set_scale(s->grid[l], &lo[2 * l], &hi[2 * l]);
-            s->grid[l].bin0 = n_bins;
-            n_bins += (long long)s->grid[l].nbx * s->grid[l].nby;
-        }
-        PADNE_REQUIRE(n_bins < (1LL << 30), "too many bins");
-        if (s->bin_off) pool_free(ctx, s->bin_off);
-        s->bin_off = nullptr;
-        PADNE_TRY(sampler_alloc(ctx, &s->bin_off, (size_t)n_bins + 1));
-        if (count.p) pool_free(ctx, count.p);
-        count.p = pool_alloc(ctx, sizeof(int) * (size_t)(n_bins + 1));
-        if (count.p == nullptr) return PADNE_E_NOMEM;
-        int *d_count = (int *)count.p;
-        PADNE_HIP_CHECK(hipMemsetAsync(d_count, 0, sizeof(int) * (size_t)(n_bins + 1), st));
-        PADNE_HIP_CHECK(hipMemcpyAsync(d_grid, s->grid.data(), sizeof(LayerGrid) * (size_t)n_layer, hipMemcpyHostToDevice, st));
-        if (n_tri > 0) {
-            hipLaunchKernelGGL(sampler_bin_kernel<false>, dim3(nblk(n_tri)), dim3(256), 0, st, (long long)n_tri, s->gtri, s->xy,
-                               (int)n_mesh, s->toff, s->mesh_layer, d_grid, d_count, (int *)nullptr);
-            PADNE_HIP_CHECK(hipGetLastError());
-        }
-        bool negative = false;
-        int64_t total = 0;
-        PADNE_TRY(exclusive_scan_i32_flagged(ctx, d_count, s->bin_off, n_bins, &total, &negative));
-        if (negative || total >= (1LL << 31)) {       // a count wrapped: only far finer than kListBound allows; coarsen
-            total = -1;
-        }
-        std::vector<int> first(n_layer + 1, 0);
-        bool again = false;
-        if (total >= 0) {
-            for (int l = 0; l < n_layer; ++l)
-                PADNE_HIP_CHECK(hipMemcpyAsync(&first[l], s->bin_off + s->grid[l].bin0, sizeof(int), hipMemcpyDeviceToHost, st));
-            PADNE_HIP_CHECK(hipStreamSynchronize(st));
-            first[n_layer] = (int)total;
-        }
-        for (int l = 0; l < n_layer; ++l) {
-            LayerGrid &g = s->grid[l];
-            s->layer_entries[l] = total >= 0 ? (int64_t)first[l + 1] - first[l] : -1;
-            const bool too_long = total < 0 || s->layer_entries[l] > kListBound * s->layer_faces[l];
-            if (too_long && (g.nbx > 1 || g.nby > 1)) {
-                g.nbx = (g.nbx + 1) / 2;
-                g.nby = (g.nby + 1) / 2;
-                again = true;
-            }
-        }
-        if (again) continue;
-        PADNE_REQUIRE(total >= 0, "the face lists do not fit 32-bit offsets");
-        PADNE_TRY(sampler_alloc(ctx, &s->bin_face, (size_t)total));
-        PADNE_HIP_CHECK(hipMemcpyAsync(d_count, s->bin_off, sizeof(int) * (size_t)n_bins, hipMemcpyDeviceToDevice, st));
-        if (n_tri > 0) {
-            hipLaunchKernelGGL(sampler_bin_kernel<true>, dim3(nblk(n_tri)), dim3(256), 0, st, (long long)n_tri, s->gtri, s->xy,
-                               (int)n_mesh, s->toff, s->mesh_layer, d_grid, d_count, s->bin_face);
-            PADNE_HIP_CHECK(hipGetLastError());
-        }
-        PADNE_HIP_CHECK(hipStreamSynchronize(st));
-        break;
-    }
+    PADNE_TRY(locate_build_bins(ctx, (int)n_layer, lo.data(), hi.data(), bins_hint, s->layer_faces, (long long)n_tri, s->gtri, s->xy,
+                                (int)n_mesh, s->toff, s->mesh_layer, s->grid, s->layer_entries, &s->bin_off, &s->bin_face));
     s->build_seconds = seconds_since(t1);
     guard.s = nullptr;
     *out = s;

@@ -309,6 +309,7 @@ static void thermal_free(padne_thermal *th) {
     padne_ctx *ctx = th->ctx;
     if (ctx != nullptr && ctx->stream != nullptr) (void)hipStreamSynchronize(ctx->stream);
     if (th->A != nullptr) padne_csr_destroy(th->A);
+    if (th->stack != nullptr) stack_free(ctx, th->stack);
     for (void *p : {(void *)th->vptr, (void *)th->vface, (void *)th->Mv, (void *)th->hM, (void *)th->P, (void *)th->theta})
         if (p != nullptr) pool_free(ctx, p);
     delete th;

@@ -16,6 +16,9 @@ constexpr int kThermalChunk = 8;       // columns per launch of the load kernel,
 
 }  // namespace padne
 
+struct padne_stack;      // stack.hip
+namespace padne { void stack_free(padne_ctx *ctx, padne_stack *st); }
+
 struct padne_thermal {
     padne_ctx *ctx = nullptr;
     const padne_csr *L = nullptr;            // borrowed: the electrical system, for its mesh
@@ -30,6 +33,7 @@ struct padne_thermal {
     size_t P_cap = 0, theta_cap = 0;
     int n_cols = 0;
     bool solved = false;
+    padne_stack *stack = nullptr;            // owned: the inter-layer coupling of padne_thermal_create_stacked (stack.hip), or null
 };
 
 namespace padne {

@@ -1861,13 +1861,19 @@ class ThermalModel:
       terminals; 0 is no link.  A resistor that is not named gets g = L0 T_ref / R.  Sources and regulators are no
       thermal path.
     - ``element_heat``: half of every resistor's dissipation is put into each of its terminals.
-    - ``reference_temperature``: T_ref [K] of the Wiedemann-Franz defaults."""
+    - ``reference_temperature``: T_ref [K] of the Wiedemann-Franz defaults.
+    - ``interlayer``: None, or a mapping {(layer or name, layer or name): g [W / (K mesh-unit^2)]}, the areal conductance
+      of the dielectric between two layers (DESIGN.md "Stack").  The Problem carries no z-order, so the pairs are named
+      and need not be neighbours; 0 is no pair.  0.2 mm of FR4 (0.3 W/(m K)) between two foils is 1.5e-3 with meshes in
+      mm, 150 times the still-air film above.  Only the connected meshes take part: electrically disconnected copper
+      stays at ambient and spreads no heat."""
     film: object
     ambient: float = 25.0
     sheet_conductance: Optional[Mapping] = None
     link_conductance: Optional[Mapping] = None
     element_heat: bool = True
     reference_temperature: float = 293.15
+    interlayer: Optional[Mapping] = None
 
 
 @dataclass
@@ -1878,6 +1884,7 @@ class CheckedThermalModel:
     links: dict                # Resistor of the solved networks -> g [W/K]
     ambient: float
     element_heat: bool
+    interlayer: list = field(default_factory=list)      # (layer index a < b, g [W / (K mesh-unit^2)]), in the mapping's order
 
 
 @dataclass
@@ -1887,11 +1894,15 @@ class ThermalReport:
     face_temperatures: Optional[list]   # per layer, per mesh: TwoForm of the mean T of each face's corners
     disconnected_temperatures: list     # per layer, per disconnected mesh: ZeroForm filled with the ambient temperature
     hotspots: list                      # per layer: (T, mesh index within the layer, vertex index, x, y), None without vertices
-    layers: list                        # per layer: {"heat": the Joule heat put into its copper [W], "loss": its film loss [W]}
+    layers: list                        # per layer: {"heat": the Joule heat put into its copper [W], "loss": its film loss [W],
+                                        # "exchange": the net heat that leaves it through the pairs of ``interlayer`` [W]}
     elements: dict                      # Resistor -> {"heat": dissipation deposited at its terminals [W], "flow": heat a -> b through its link [W]}
     total_heat: float                   # copper and elements
     total_loss: float                   # what the films carry to ambient: equals total_heat up to the solve's tolerance
     info: dict                          # {"iterations", "rel_residual", "seconds"} of the thermal block solve
+    # per pair of ThermalModel.interlayer: {"layers": (index a, index b), a < b, "conductance": g, "flow": the heat from a to
+    # b through the dielectric [W], "area": the coupled area [mesh-unit^2]}
+    interlayer: list = field(default_factory=list)
 
 
 @dataclass
@@ -1935,7 +1946,9 @@ def check_thermal_model(prob, model, filtered_networks=None) -> CheckedThermalMo
     """``model`` resolved against ``prob``, or ValueError -- before anything reaches the device -- for: a film that is
     missing for a layer; a film, sheet conductance or reference temperature that is not finite and positive; a link
     conductance that is negative or not finite (0 is allowed: no link); a mapping key that is no layer, or no Resistor, of
-    the Problem; an ambient temperature that is not finite; and an internal node (a terminal without a connection to
+    the Problem; an ``interlayer`` key that is not a 2-tuple of layers of the Problem, that pairs a layer with itself or
+    that repeats an unordered pair, or an ``interlayer`` conductance that is negative or not finite (0 is allowed: no
+    pair); an ambient temperature that is not finite; and an internal node (a terminal without a connection to
     copper) that reaches no copper through links of positive conductance -- its temperature would be undetermined.  That
     last check walks a small graph over the lumped elements only, and the error names an element at the node."""
     if not isinstance(model, ThermalModel):
@@ -2009,7 +2022,57 @@ def check_thermal_model(prob, model, filtered_networks=None) -> CheckedThermalMo
         if node not in reached:
             raise ValueError(f"an internal node of {element!r} reaches no copper through a thermal link of positive conductance: "
                              "its temperature is undetermined (give a resistor at the node a link_conductance above 0)")
-    return CheckedThermalModel(film=film, kappa=kappa, links=links, ambient=ambient, element_heat=bool(model.element_heat))
+    return CheckedThermalModel(film=film, kappa=kappa, links=links, ambient=ambient, element_heat=bool(model.element_heat),
+                               interlayer=_check_interlayer(prob, model.interlayer))
+
+
+def _check_interlayer(prob, interlayer) -> list:
+    """``ThermalModel.interlayer`` resolved to [(layer index a < b, g)], or ValueError (see :func:`check_thermal_model`)."""
+    if interlayer is None:
+        return []
+    if not isinstance(interlayer, Mapping):
+        raise ValueError("interlayer must be a mapping {(layer, layer): W/(K mesh-unit^2)}")
+
+    def index_of(key):
+        if isinstance(key, str):
+            found = [i for i, layer in enumerate(prob.layers) if layer.name == key]
+        else:
+            found = [i for i, layer in enumerate(prob.layers) if layer is key] or \
+                    [i for i, layer in enumerate(prob.layers) if layer == key]
+        if len(found) != 1:
+            raise ValueError(f"interlayer: {key!r} is no layer of the Problem" if not found else
+                             f"interlayer: {key!r} names {len(found)} layers of the Problem")
+        return found[0]
+
+    out, seen = [], set()
+    for key, value in interlayer.items():
+        if not isinstance(key, tuple) or len(key) != 2:
+            raise ValueError(f"interlayer: a key is a pair (layer, layer), not {key!r}")
+        a, b = index_of(key[0]), index_of(key[1])
+        if a == b:
+            raise ValueError(f"interlayer: {key!r} pairs layer {prob.layers[a].name!r} with itself")
+        a, b = min(a, b), max(a, b)
+        if (a, b) in seen:
+            raise ValueError(f"interlayer: the layers {prob.layers[a].name!r} and {prob.layers[b].name!r} are paired twice")
+        seen.add((a, b))
+        out.append((a, b, _positive_number(value, f"the interlayer conductance of {key!r}", allow_zero=True)))
+    return out
+
+
+def _thermal_handle(L, n_potential: int, checked: CheckedThermalModel, layer_of, n_mesh: int, resistors) -> "_hip.Thermal":
+    """The ``_hip.Thermal`` of the checked model on the assembled system ``L``; with ``interlayer`` pairs the stacked one."""
+    stack = {}
+    if checked.interlayer:
+        stack = dict(mesh_layer=[layer_of[i] for i in range(n_mesh)], pairs=checked.interlayer, n_layer=len(checked.film))
+    return _hip.Thermal(L.dev, n_potential, [checked.kappa[layer_of[i]] for i in range(n_mesh)],
+                        [checked.film[layer_of[i]] for i in range(n_mesh)],
+                        [row[1] for _, row in resistors], [row[2] for _, row in resistors],
+                        [checked.links[element] for element, _ in resistors], **stack)
+
+
+def _stack_flows(thermal, checked: CheckedThermalModel, n_cols: int):
+    """(flows (n_cols, n_pair), areas (n_pair,)) of the last solve of ``thermal`` for the model's pairs, or None without."""
+    return thermal.stack_flows(n_cols) if checked.interlayer else None
 
 
 def _refuse_bare_vertices(board: IndexedBoard) -> None:
@@ -2036,11 +2099,12 @@ def thermal_heat_triples(pairs, flows_by_case) -> tuple:
 
 
 def _thermal_reports(board: IndexedBoard, checked: CheckedThermalModel, substituted, resistors, fields: bool, theta, mean,
-                     mesh_max, mesh_vert, mesh_heat, mesh_loss, heat_val, infos) -> list:
+                     mesh_max, mesh_vert, mesh_heat, mesh_loss, heat_val, infos, stack=None) -> list:
     """The ThermalReports of k cases from what ``Thermal.report`` returns for them: ``theta`` (k, n_potential), ``mean`` (k,
     n_tri) or None without ``fields``, the per-mesh arrays (k, n_mesh), ``heat_val`` (k, n_resistors, 2) the heat put into the
     resistors' terminals or None, ``infos`` the info dict of each case.  ``substituted``: substitute_load_case of each case;
-    ``resistors``: the (element, row) pairs of the board's resistors."""
+    ``resistors``: the (element, row) pairs of the board's resistors.  ``stack``: (flows (k, n_pair), areas (n_pair,)) of
+    the model's ``interlayer`` pairs as ``Thermal.stack_flows`` returns them, or None without pairs."""
     ambient, voff, n_layers = checked.ambient, board.vindex.offsets, len(board.prob.layers)
 
     def cold(layer_i):
@@ -2075,7 +2139,12 @@ def _thermal_reports(board: IndexedBoard, checked: CheckedThermalModel, substitu
             temps.append(zfs)
             faces.append(tfs)
             hotspots.append(best)
-            layers.append({"heat": math.fsum(heat_in), "loss": math.fsum(loss)})
+            exchange = [] if stack is None else [float(stack[0][j, p]) * (1.0 if a == layer_i else -1.0)
+                                                 for p, (a, b, _) in enumerate(checked.interlayer) if layer_i in (a, b)]
+            layers.append({"heat": math.fsum(heat_in), "loss": math.fsum(loss), "exchange": math.fsum(exchange)})
+        interlayer = [] if stack is None else [
+            {"layers": (a, b), "conductance": g, "flow": float(stack[0][j, p]), "area": float(stack[1][p])}
+            for p, (a, b, g) in enumerate(checked.interlayer)]
         elements = {}
         for i, ((element, row), case_element) in enumerate(zip(resistors, case_resistors)):
             deposited = float(heat_val[j, i].sum()) if heat_val is not None else 0.0
@@ -2085,7 +2154,7 @@ def _thermal_reports(board: IndexedBoard, checked: CheckedThermalModel, substitu
             temperatures=temps if fields else None, face_temperatures=faces if fields else None,
             disconnected_temperatures=[cold(layer_i) for layer_i in range(n_layers)], hotspots=hotspots, layers=layers,
             elements=elements, total_heat=math.fsum([layer["heat"] for layer in layers] + [e["heat"] for e in elements.values()]),
-            total_loss=math.fsum(layer["loss"] for layer in layers), info=infos[j]))
+            total_loss=math.fsum(layer["loss"] for layer in layers), info=infos[j], interlayer=interlayer))
     return reports
 
 
@@ -2140,10 +2209,7 @@ def _thermal_block(prob, meshes, mesh_index_to_layer_index, checked: CheckedTher
         laps.lap("power_density")
         resistors = [(element, row) for element, row in pairs if row[0] == "R"]
         n_potential = L.layout.n_potential
-        thermal = _hip.Thermal(L.dev, n_potential, [checked.kappa[layer_of[i]] for i in range(len(board.meshes))],
-                               [checked.film[layer_of[i]] for i in range(len(board.meshes))],
-                               [row[1] for _, row in resistors], [row[2] for _, row in resistors],
-                               [checked.links[element] for element, _ in resistors])
+        thermal = _thermal_handle(L, n_potential, checked, layer_of, len(board.meshes), resistors)
         try:
             laps.lap("thermal_setup")
             heat = thermal_heat_triples(pairs, flows_by_case) if checked.element_heat else None
@@ -2172,6 +2238,7 @@ def _solve_block_thermal(prob, meshes, mesh_index_to_layer_index, checked: Check
         theta, tres = blk.thermal.solve_kkt(blk.plan, k, heat, rtol=RTOL, max_iter=MAX_ITER)
         laps.lap("thermal_solve")
         mean, mesh_max, mesh_vert, mesh_heat, mesh_loss, env, env_case = blk.thermal.report(k, blk.n_tri, blk.n_vert, fields=fields)
+        stack = _stack_flows(blk.thermal, checked, k)
         laps.lap("thermal_report")
     if tres.status != _hip.OK and not tres.rel_residual <= max(RTOL, STALL_WARN_ABOVE):
         warnings.warn(f"The thermal solve stopped at a relative residual of {tres.rel_residual:.3e}", SolverWarning)
@@ -2180,7 +2247,7 @@ def _solve_block_thermal(prob, meshes, mesh_index_to_layer_index, checked: Check
     info = {"iterations": int(tres.iterations), "rel_residual": float(tres.rel_residual), "seconds": float(tres.seconds)}
     heat_val = heat[2].reshape(k, len(blk.resistors), 2) if heat is not None else None
     reports = _thermal_reports(board, checked, blk.substituted, blk.resistors, fields, theta, mean, mesh_max, mesh_vert, mesh_heat,
-                               mesh_loss, heat_val, [info] * k)
+                               mesh_loss, heat_val, [info] * k, stack)
     envelope = _thermal_envelope(board, checked.ambient, env, env_case, reports)
     laps.lap("solutions")
     return solutions, reports, envelope
@@ -2205,6 +2272,13 @@ def solve_meshed_thermal(prob, meshes, mesh_index_to_layer_index, model: Thermal
     constants, ``total_loss`` (what the films carry away) equals ``total_heat`` (what the sources deliver) up to the
     solve's tolerance.  The coupling is one-way: the copper's resistivity does not follow the temperature
     (:func:`solve_meshed_electrothermal` closes that loop).
+
+    With ``model.interlayer`` (DESIGN.md "Stack") the operator gains G, the heat conduction through the dielectric between
+    the named pairs of layers: every vertex of one layer of a pair is linked to the three corners of the face of the other
+    layer that contains it, with the conductance g M_v / 2 shared out by the barycentric weights, from both sides.  G
+    annihilates constants, so the balance above holds; ``ThermalReport.interlayer`` gives the heat through every pair and
+    the coupled area, and ``layers[i]["exchange"]`` the net heat layer i passes on.  Only connected meshes take part:
+    floating copper as a pure heat spreader is out of scope.
 
     The electrical block is the load-case path; the thermal operator is then assembled from the meshes the device still
     holds, the face powers of every case are computed from the potentials it holds, and all cases go through one block
@@ -2755,16 +2829,13 @@ def _solve_electrothermal(prob, meshes, mesh_index_to_layer_index, checked: Chec
     rounds_log = []
     if laps.timings is not None:
         laps.timings["rounds"] = rounds_log
-    per_case = []
+    per_case, stack_flows = [], []
     with board.assembled() as (L, _):
         laps.lap("assembly")
         resistors = [(element, row) for element, row in pairs if row[0] == "R"]
         n_potential = L.layout.n_potential
         n_tri = len(L.tri)
-        thermal = _hip.Thermal(L.dev, n_potential, [thermal_model.kappa[layer_of[i]] for i in range(n_mesh)],
-                               [thermal_model.film[layer_of[i]] for i in range(n_mesh)],
-                               [row[1] for _, row in resistors], [row[2] for _, row in resistors],
-                               [thermal_model.links[element] for element, _ in resistors])
+        thermal = _thermal_handle(L, n_potential, thermal_model, layer_of, n_mesh, resistors)
         coupled = None
         try:
             coupled = _hip.Coupled(L.dev, thermal, [checked.alpha[layer_of[i]] for i in range(n_mesh)], thermal_model.ambient,
@@ -2813,6 +2884,7 @@ def _solve_electrothermal(prob, meshes, mesh_index_to_layer_index, checked: Chec
                 power = coupled.power_density(plan, n_tri)
                 scale = coupled.get_scale(n_tri, used=True)
                 report = thermal.report(1, n_tri, n_vert, fields=fields, envelope=False)
+                stack_flows.append(_stack_flows(thermal, thermal_model, 1))
                 per_case.append((V, residual_norms, res, cols, vals, power, scale, theta, tres, report, heat, increments,
                                  iterations, converged, flows))
             laps.lap("loop")
@@ -2848,7 +2920,8 @@ def _solve_electrothermal(prob, meshes, mesh_index_to_layer_index, checked: Chec
     theta = np.concatenate([c[7] for c in per_case])
     stacked = [None if not fields and i == 0 else np.concatenate([c[9][i] for c in per_case]) for i in range(5)]
     heat_val = np.stack([c[10][2].reshape(len(resistors), 2) for c in per_case]) if thermal_model.element_heat else None
-    reports = _thermal_reports(board, thermal_model, substituted, resistors, fields, theta, *stacked, heat_val, infos)
+    stack = (np.concatenate([f[0] for f in stack_flows]), stack_flows[0][1]) if thermal_model.interlayer else None
+    reports = _thermal_reports(board, thermal_model, substituted, resistors, fields, theta, *stacked, heat_val, infos, stack)
     env, env_case = envelope_of(theta[:, :n_vert])
     envelope = _thermal_envelope(board, thermal_model.ambient, env, env_case, reports)
     laps.lap("solutions")
