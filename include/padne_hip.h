@@ -675,6 +675,42 @@ int padne_thermal_stack_links(padne_ctx *ctx, const padne_thermal *th, int64_t n
 int padne_thermal_stack_matrix(padne_ctx *ctx, const padne_thermal *th, int64_t nnz, int32_t *indptr_out, int32_t *indices_out,
                                double *data_out, double *diag_out);
 
+/* ---- heat sources: footprints of components that dissipate watts ----------------------------------
+ * No reference counterpart ("Heat sources").  Source s is a layer source_layer[s] in [0, n_layer), a polygon of
+ * 3 to 256 vertices poly_xy[poly_ptr[s] .. poly_ptr[s + 1]][2] (poly_ptr[0] = 0) and, per column of a load, a power [W].
+ * With mesh_layer[m] in [0, n_layer) the layer of every mesh of the handle's system, padne_thermal_set_sources builds on the
+ * device, once per handle:
+ *   - the list of s: the faces of the meshes of its layer whose centroid ((x1 + x2) + x3) / 3 (corners in the order of
+ *     padne_thermal_report's face mean) lies inside the polygon by the even-odd rule -- the edge from (xj, yj), the
+ *     previous vertex, to (xi, yi) crosses when (yi > cy) != (yj > cy) and cx < (xj - xi) * (cy - yi) / (yj - yi) + xi --
+ *     in ascending global face number; counts_out[s] their number;
+ *   - for a source that covers no centroid (fallback_out[s] = 1, counts_out[s] = 1) the one face that owns the vertex mean
+ *     of the polygon (coordinates summed in vertex order, divided by n) by the rule of padne_sampler_create; where no face
+ *     does, fallback_out[s] = 2 and the call fails with PADNE_E_INVALID: the source lies on no copper the system keeps;
+ *   - area_out[s] = A_s, the sum of the list's face areas in tiles of 256 (the workgroup order of padne_thermal_report;
+ *     thread i mod 256 adds tile i to its partial sum, one more workgroup sum joins the partial sums);
+ *   - the sources of every face, in ascending source number.
+ * The handle owns them until it is destroyed; a second call replaces them and n_source = 0 removes them.  From then on every
+ * load the handle forms (padne_thermal_load, the solves, padne_coupled_solve_kkt, padne_transient_loads*) adds, after the
+ * face gather and the node-heat triples, b[c][v] += the sum from 0.0 over the faces f around v, ascending, and over the
+ * sources s of f, ascending, of ((area_f / A_s) * power[c][s]) / 3 -- with the powers padne_thermal_source_power gave last,
+ * power[n_cols][n_source], finite and >= 0.  A handle with sources and no powers, or powers for another number of columns
+ * than the load has, forms no load: PADNE_E_INVALID.  The weights of a source sum to 1, so its load sums to its power and
+ * the film loss still equals the heat put in; the face powers of padne_thermal_face_power and the heat of
+ * padne_thermal_report do not contain it.  No floating-point atomics: two calls give the same bits.  PADNE_E_INVALID also
+ * for a layer out of range, a null pointer, a poly_ptr that does not ascend by 3 to 256, more than 4096 sources, a
+ * coordinate that is not finite and a handle of another context. */
+int padne_thermal_set_sources(padne_ctx *ctx, padne_thermal *th, int32_t n_layer, int32_t n_mesh, const int32_t *mesh_layer,
+                              int32_t n_source, const int32_t *source_layer, const int64_t *poly_ptr, const double *poly_xy,
+                              int64_t *counts_out, int32_t *fallback_out, double *area_out);
+int padne_thermal_source_power(padne_ctx *ctx, padne_thermal *th, int32_t n_cols, const double *power);
+/* Read-out of the lists (tests): ptr_out[n_source + 1] and face_out[n_entries], n_entries the sum of counts_out. */
+int padne_thermal_source_lists(padne_ctx *ctx, const padne_thermal *th, int32_t n_source, int64_t n_entries, int64_t *ptr_out,
+                               int32_t *face_out);
+/* After a solve of n_cols columns: temperature_out[n_cols][n_source] = T_s - ambient = the sum over the list of s, in the
+ * order of A_s, of (area_f / A_s) * mean[c][f], mean the face mean of padne_thermal_report.  Two calls give the same bits. */
+int padne_thermal_source_report(padne_ctx *ctx, padne_thermal *th, int32_t n_cols, double *temperature_out);
+
 /* ---- electro-thermal coupling: the copper's conductance follows its temperature ----------------
  * No reference counterpart ("Electro-thermal").  Face t of mesh m conducts sigma[m] * s[t],
  *     s[t] = 1 / (1 + alpha[m] * ((mean[t] + ambient) - conductance_temperature)),

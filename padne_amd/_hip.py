@@ -163,6 +163,11 @@ SIGNATURES = {
     "padne_thermal_stack_sizes": (C.c_int, [_P, _PI64]),
     "padne_thermal_stack_links": (C.c_int, [_P, _P, _I64, _PI64, _PI32, _PI32, _PF64, _PF64]),
     "padne_thermal_stack_matrix": (C.c_int, [_P, _P, _I64, _PI32, _PI32, _PF64, _PF64]),
+    "padne_thermal_set_sources": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _PI32, C.c_int32, _PI32, _PI64, _PF64, _PI64, _PI32,
+                                            _PF64]),
+    "padne_thermal_source_power": (C.c_int, [_P, _P, C.c_int32, _PF64]),
+    "padne_thermal_source_lists": (C.c_int, [_P, _P, C.c_int32, _I64, _PI64, _PI32]),
+    "padne_thermal_source_report": (C.c_int, [_P, _P, C.c_int32, _PF64]),
     "padne_transient_create": (C.c_int, [_P, _P, C.c_int32, _PF64, C.POINTER(_P)]),
     "padne_transient_destroy": (C.c_int, [_P]),
     "padne_transient_capacity": (C.c_int, [_P, _P, _PF64]),
@@ -1052,6 +1057,14 @@ class KktPlan:
         return V, norms
 
 
+class SourceOffCopperError(ValueError):
+    """``Thermal.set_sources``: the heat sources ``sources`` (indices) cover no face and no face owns their vertex mean."""
+
+    def __init__(self, message: str, sources: list):
+        super().__init__(message)
+        self.sources = sources
+
+
 class Thermal:
     """``padne_thermal``: the thermal sheet problem A theta = b on the meshes an assembled system ``L`` keeps on the device
     (include/padne_hip.h, "thermal").  ``kappa`` and ``film`` per mesh, ``links`` an (n, 2) array of unknowns with
@@ -1094,6 +1107,7 @@ class Thermal:
             self.n_pair = len(pairs)
         self._h = h
         self.n_potential, self.n_mesh = int(n_potential), kap.shape[0]
+        self.n_source, self.n_source_entries = 0, 0
 
     def stack_sizes(self):
         """(pairs, sides, (side, vertex) slots, stored off-diagonals of G) of a stacked handle."""
@@ -1128,6 +1142,50 @@ class Thermal:
         flow, area = np.zeros((n_cols, self.n_pair), dtype=np.float64), np.zeros(self.n_pair, dtype=np.float64)
         _check(self.ctx._lib.padne_thermal_stack_flows(self.ctx._h, self._h, n_cols, _ptr(flow, _PF64), _ptr(area, _PF64)))
         return flow, area
+
+    def set_sources(self, n_layer: int, mesh_layer, source_layer, polygons):
+        """The heat sources of the handle (include/padne_hip.h, "heat sources"): ``mesh_layer`` the layer of every mesh,
+        ``source_layer`` (n,) and ``polygons`` a sequence of n arrays (m, 2).  Returns (faces in each source's list (n,) int64,
+        fallback flags (n,) int32, A_s (n,)); a second call replaces the sources, none removes them.
+        :class:`SourceOffCopperError` for sources that lie on no copper the system keeps."""
+        ml, sl = _i32(mesh_layer).reshape(-1), _i32(source_layer).reshape(-1)
+        polys = [_f64(p) for p in polygons]
+        if len(polys) != sl.shape[0] or any(p.ndim != 2 or p.shape[1] != 2 for p in polys):
+            raise ValueError("one polygon of shape (m, 2) per source")
+        ptr = _i64(np.concatenate([[0], np.cumsum([len(p) for p in polys])]))
+        xy = _f64(np.concatenate(polys)) if polys else np.zeros((0, 2))
+        n = sl.shape[0]
+        counts, fallback, area = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.float64)
+        self.n_source, self.n_source_entries = 0, 0
+        rc = self.ctx._lib.padne_thermal_set_sources(self.ctx._h, self._h, int(n_layer), ml.shape[0], _ptr(ml, _PI32), n,
+                                                     _ptr(sl, _PI32), _ptr(ptr, _PI64), _ptr(xy, _PF64), _ptr(counts, _PI64),
+                                                     _ptr(fallback, _PI32), _ptr(area, _PF64))
+        if rc == E_INVALID and (fallback == 2).any():
+            msg = (load_library().padne_last_error() or b"").decode("utf-8", "replace")
+            raise SourceOffCopperError(msg, [int(i) for i in np.flatnonzero(fallback == 2)])
+        _check(rc)
+        self.n_source, self.n_source_entries = n, int(counts.sum())
+        return counts, fallback, area
+
+    def source_power(self, power) -> None:
+        """The powers (n_cols, n_source) [W] the next loads of the handle use; a load of another number of columns fails."""
+        P = _f64(power)
+        if P.ndim != 2 or P.shape[1] != self.n_source:
+            raise ValueError("power must have shape (n_cols, n_source)")
+        _check(self.ctx._lib.padne_thermal_source_power(self.ctx._h, self._h, P.shape[0], _ptr(P, _PF64)))
+
+    def source_lists(self):
+        """(ptr (n_source + 1,), face (entries,)): the faces of every source in ascending global number."""
+        ptr, face = np.zeros(self.n_source + 1, dtype=np.int64), np.empty(self.n_source_entries, dtype=np.int32)
+        _check(self.ctx._lib.padne_thermal_source_lists(self.ctx._h, self._h, self.n_source, self.n_source_entries, _ptr(ptr, _PI64),
+                                                        _ptr(face, _PI32)))
+        return ptr, face
+
+    def source_report(self, n_cols: int) -> np.ndarray:
+        """On the theta of the last solve: T_s - ambient (n_cols, n_source), the area-weighted mean over every source's list."""
+        out = np.empty((int(n_cols), self.n_source), dtype=np.float64)
+        _check(self.ctx._lib.padne_thermal_source_report(self.ctx._h, self._h, int(n_cols), _ptr(out, _PF64)))
+        return out
 
     def close(self):
         if getattr(self, "_h", None) and self.ctx._h:

@@ -310,6 +310,7 @@ static void thermal_free(padne_thermal *th) {
     if (ctx != nullptr && ctx->stream != nullptr) (void)hipStreamSynchronize(ctx->stream);
     if (th->A != nullptr) padne_csr_destroy(th->A);
     if (th->stack != nullptr) stack_free(ctx, th->stack);
+    if (th->sources != nullptr) sources_free(ctx, th->sources);
     for (void *p : {(void *)th->vptr, (void *)th->vface, (void *)th->Mv, (void *)th->hM, (void *)th->P, (void *)th->theta})
         if (p != nullptr) pool_free(ctx, p);
     delete th;
@@ -334,7 +335,8 @@ int thermal_require(const char *entry, padne_ctx *ctx, const padne_thermal *th) 
 }
 
 // b[n_cols][n_pot] on the device from the face powers th->P[n_cols][n_tri] and the node-heat triples: the gather through the
-// vertex lists, 8 columns per launch, then the triples.  Returns once the host lists have been read
+// vertex lists, 8 columns per launch, then the triples, then the heat sources of a handle that has some.  Returns once the
+// host lists have been read
 int thermal_form_load(padne_ctx *ctx, padne_thermal *th, int32_t n_cols, int64_t n_heat, const int64_t *heat_node,
                              const int32_t *heat_col, const double *heat_val, double *d_b) {
     hipStream_t s = ctx->stream;
@@ -380,7 +382,7 @@ int thermal_form_load(padne_ctx *ctx, padne_thermal *th, int32_t n_cols, int64_t
         PADNE_HIP_CHECK(hipGetLastError());
         PADNE_HIP_CHECK(hipStreamSynchronize(s));       // (the copies read the host vectors above before they go)
     }
-    return PADNE_OK;
+    return sources_add_load(ctx, th, n_cols, d_b);      // the handle's heat sources, if it has any (sources.hip)
 }
 
 // What follows the face powers th->P[n_cols][n_tri]: b, the block solve, theta home.  PADNE_E_NOTCONVERGED still keeps and

@@ -18,6 +18,8 @@ constexpr int kThermalChunk = 8;       // columns per launch of the load kernel,
 
 struct padne_stack;      // stack.hip
 namespace padne { void stack_free(padne_ctx *ctx, padne_stack *st); }
+struct padne_sources;    // sources.hip
+namespace padne { void sources_free(padne_ctx *ctx, padne_sources *sr); }
 
 struct padne_thermal {
     padne_ctx *ctx = nullptr;
@@ -34,6 +36,7 @@ struct padne_thermal {
     int n_cols = 0;
     bool solved = false;
     padne_stack *stack = nullptr;            // owned: the inter-layer coupling of padne_thermal_create_stacked (stack.hip), or null
+    padne_sources *sources = nullptr;        // owned: the heat sources of padne_thermal_set_sources (sources.hip), or null
 };
 
 namespace padne {
@@ -59,6 +62,10 @@ int thermal_kkt_face_power(padne_ctx *ctx, padne_thermal *th, int32_t n_cols, co
 int thermal_form_load(padne_ctx *ctx, padne_thermal *th, int32_t n_cols, int64_t n_heat, const int64_t *heat_node,
                       const int32_t *heat_col, const double *heat_val, double *d_b);
 std::vector<long long> thermal_tiles(const std::vector<int64_t> &off);
+// sources.hip: what thermal_form_load adds for a handle with heat sources -- their load into b[n_cols][n_pot] on the device,
+// queued behind the face gather and the triples; PADNE_E_INVALID without powers for exactly n_cols columns.  Nothing
+// without sources
+int sources_add_load(padne_ctx *ctx, padne_thermal *th, int32_t n_cols, double *d_b);
 
 // What a matrix derived from its values (1 / diagonal, single-precision copies, multigrid hierarchy) is dropped and rebuilt
 // on next use from the values in place; the x-window plan depends on the pattern only and stays

@@ -1845,6 +1845,44 @@ def solve_load_case_currents(prob, cases, cuts=(), mesher_config: Optional[mesh.
 # --------------------------------------------------------------------------------------------
 
 LORENZ_NUMBER = 2.44e-8                 # L0 [W Ohm / K^2] of Wiedemann-Franz: kappa = L0 T sigma for a metal
+MAX_HEAT_SOURCES = 4096
+MAX_HEAT_SOURCE_VERTICES = 256
+
+
+@dataclass
+class HeatSource:
+    """A component that dissipates into the copper under its footprint (DESIGN.md "Heat sources").
+
+    - ``layer``: the layer, or its name.
+    - ``polygon``: array-like (n, 2), n >= 3, in mesh units: the footprint.  Inside is decided by the even-odd rule, so a
+      self-intersecting polygon is whatever that rule makes of it; footprints may overlap.
+    - ``power``: the watts it dissipates, a float for every load case or a sequence with one entry per case.
+    - ``name``: what the report and the error messages call it."""
+    layer: object
+    polygon: object
+    power: object
+    name: Optional[str] = None
+
+    @classmethod
+    def rectangle(cls, layer, x0, y0, x1, y1, power, name=None) -> "HeatSource":
+        """The axis-parallel rectangle with the corners (x0, y0) and (x1, y1)."""
+        return cls(layer, [(x0, y0), (x1, y0), (x1, y1), (x0, y1)], power, name)
+
+    @classmethod
+    def disc(cls, layer, centre, radius, power, segments=32, name=None) -> "HeatSource":
+        """The regular polygon of ``segments`` vertices on the circle of ``radius`` around ``centre``, the first at angle 0."""
+        angles = 2.0 * np.pi * np.arange(int(segments)) / int(segments)
+        ring = np.stack([centre[0] + radius * np.cos(angles), centre[1] + radius * np.sin(angles)], axis=1)
+        return cls(layer, ring, power, name)
+
+
+@dataclass(frozen=True)
+class CheckedHeatSource:
+    """A :class:`HeatSource` resolved against a Problem (:func:`check_thermal_model`)."""
+    name: str
+    layer: int                 # index into Problem.layers
+    polygon: tuple             # ((x, y), ...)
+    power: object              # float, or a tuple of floats (one per load case)
 
 
 @dataclass
@@ -1866,7 +1904,16 @@ class ThermalModel:
       of the dielectric between two layers (DESIGN.md "Stack").  The Problem carries no z-order, so the pairs are named
       and need not be neighbours; 0 is no pair.  0.2 mm of FR4 (0.3 W/(m K)) between two foils is 1.5e-3 with meshes in
       mm, 150 times the still-air film above.  Only the connected meshes take part: electrically disconnected copper
-      stays at ambient and spreads no heat."""
+      stays at ambient and spreads no heat.
+    - ``heat_sources``: None, or a sequence of :class:`HeatSource` (DESIGN.md "Heat sources"): components that put watts
+      into the copper under their footprints, on top of the Joule heat.  A source loads the faces of the connected meshes
+      of its layer whose centroid lies inside its polygon, each with the share area_f / A_s of its power (A_s the area of
+      those faces together), a third of it at each corner; a footprint that covers no centroid (an 0402 on a coarse mesh)
+      loads the one face that contains the mean of its vertices.  The power is per load case: a float serves every case,
+      a sequence names one per case and is checked against the cases by the solve.  A source that lies on no connected
+      copper is a ValueError of the solve.  At most 4096 sources of at most 256 vertices each.  Honoured by every thermal
+      entry point: steady, load cases, electro-thermal (the same watts in every round, not scaled by the resistivity) and
+      transient (a segment without a case has no source heat)."""
     film: object
     ambient: float = 25.0
     sheet_conductance: Optional[Mapping] = None
@@ -1874,6 +1921,7 @@ class ThermalModel:
     element_heat: bool = True
     reference_temperature: float = 293.15
     interlayer: Optional[Mapping] = None
+    heat_sources: Optional[Sequence] = None
 
 
 @dataclass
@@ -1885,6 +1933,7 @@ class CheckedThermalModel:
     ambient: float
     element_heat: bool
     interlayer: list = field(default_factory=list)      # (layer index a < b, g [W / (K mesh-unit^2)]), in the mapping's order
+    sources: list = field(default_factory=list)         # CheckedHeatSource, in the model's order
 
 
 @dataclass
@@ -1903,6 +1952,11 @@ class ThermalReport:
     # per pair of ThermalModel.interlayer: {"layers": (index a, index b), a < b, "conductance": g, "flow": the heat from a to
     # b through the dielectric [W], "area": the coupled area [mesh-unit^2]}
     interlayer: list = field(default_factory=list)
+    # per source of ThermalModel.heat_sources: {"name", "layer": index, "power": of this case [W], "area": A_s, the area of
+    # the faces it loads [mesh-unit^2], "faces": their number, "fallback": True when it covers no centroid and loads the
+    # one face under its middle, "temperature": the area-weighted mean of those faces' temperatures}
+    sources: list = field(default_factory=list)
+    source_heat: float = 0.0            # the powers of the sources in this case; part of total_heat
 
 
 @dataclass
@@ -1948,7 +2002,10 @@ def check_thermal_model(prob, model, filtered_networks=None) -> CheckedThermalMo
     conductance that is negative or not finite (0 is allowed: no link); a mapping key that is no layer, or no Resistor, of
     the Problem; an ``interlayer`` key that is not a 2-tuple of layers of the Problem, that pairs a layer with itself or
     that repeats an unordered pair, or an ``interlayer`` conductance that is negative or not finite (0 is allowed: no
-    pair); an ambient temperature that is not finite; and an internal node (a terminal without a connection to
+    pair); ``heat_sources`` that is no sequence of :class:`HeatSource` or holds more than 4096, a source whose layer is no
+    layer of the Problem or names several, whose polygon is not (n >= 3, 2), not finite, of zero signed area or of more
+    than 256 vertices, or whose power is negative, not finite or not a number (the length of a sequence of powers is
+    checked against the load cases by the solve); an ambient temperature that is not finite; and an internal node (a terminal without a connection to
     copper) that reaches no copper through links of positive conductance -- its temperature would be undetermined.  That
     last check walks a small graph over the lumped elements only, and the error names an element at the node."""
     if not isinstance(model, ThermalModel):
@@ -2023,7 +2080,114 @@ def check_thermal_model(prob, model, filtered_networks=None) -> CheckedThermalMo
             raise ValueError(f"an internal node of {element!r} reaches no copper through a thermal link of positive conductance: "
                              "its temperature is undetermined (give a resistor at the node a link_conductance above 0)")
     return CheckedThermalModel(film=film, kappa=kappa, links=links, ambient=ambient, element_heat=bool(model.element_heat),
-                               interlayer=_check_interlayer(prob, model.interlayer))
+                               interlayer=_check_interlayer(prob, model.interlayer),
+                               sources=_check_heat_sources(prob, model.heat_sources))
+
+
+def _check_heat_sources(prob, heat_sources) -> list:
+    """``ThermalModel.heat_sources`` resolved to [CheckedHeatSource], or ValueError (see :func:`check_thermal_model`)."""
+    if heat_sources is None:
+        return []
+    if isinstance(heat_sources, (str, bytes, Mapping, HeatSource)) or not isinstance(heat_sources, (Sequence, np.ndarray)):
+        raise ValueError("heat_sources must be a sequence of HeatSource")
+    if len(heat_sources) > MAX_HEAT_SOURCES:
+        raise ValueError(f"heat_sources: {len(heat_sources)} sources, at most {MAX_HEAT_SOURCES} are taken")
+
+    def watts(value, what):
+        if isinstance(value, (str, bytes)) or value is None:
+            raise ValueError(f"heat_sources: the power of {what} must be a number, not {value!r}")
+        try:
+            x = float(value)
+        except (TypeError, ValueError):
+            raise ValueError(f"heat_sources: the power of {what} must be a number, not {value!r}") from None
+        if not math.isfinite(x) or x < 0.0:
+            raise ValueError(f"heat_sources: the power of {what} must be finite and not negative, not {value!r}")
+        return x
+
+    out = []
+    for i, source in enumerate(heat_sources):
+        if not isinstance(source, HeatSource):
+            raise ValueError(f"heat_sources: entry {i} is no HeatSource but {source!r}")
+        name = f"source {i}" if source.name is None else str(source.name)
+        key = source.layer
+        if isinstance(key, str):
+            found = [l for l, layer in enumerate(prob.layers) if layer.name == key]
+        else:
+            found = [l for l, layer in enumerate(prob.layers) if layer is key] or \
+                    [l for l, layer in enumerate(prob.layers) if layer == key]
+        if len(found) != 1:
+            raise ValueError(f"heat_sources: the layer {key!r} of {name!r} is no layer of the Problem" if not found else
+                             f"heat_sources: the layer {key!r} of {name!r} names {len(found)} layers of the Problem")
+        try:
+            polygon = np.array(source.polygon, dtype=DTYPE)
+        except (TypeError, ValueError):
+            raise ValueError(f"heat_sources: the polygon of {name!r} must be array-like of shape (n, 2)") from None
+        if polygon.ndim != 2 or polygon.shape[1] != 2 or polygon.shape[0] < 3:
+            raise ValueError(f"heat_sources: the polygon of {name!r} must have shape (n >= 3, 2), not {polygon.shape}")
+        if polygon.shape[0] > MAX_HEAT_SOURCE_VERTICES:
+            raise ValueError(f"heat_sources: the polygon of {name!r} has {polygon.shape[0]} vertices, at most "
+                             f"{MAX_HEAT_SOURCE_VERTICES} are taken")
+        if not np.isfinite(polygon).all():
+            raise ValueError(f"heat_sources: the polygon of {name!r} must be finite")
+        x, y = polygon[:, 0], polygon[:, 1]
+        signed = math.fsum((x * np.roll(y, -1) - np.roll(x, -1) * y).tolist())
+        if not math.isfinite(signed) or signed == 0.0:
+            raise ValueError(f"heat_sources: the polygon of {name!r} has no area")
+        power = source.power
+        if isinstance(power, (Sequence, np.ndarray)) and not isinstance(power, (str, bytes)) and np.ndim(power) > 0:
+            if np.ndim(power) != 1:
+                raise ValueError(f"heat_sources: the power of {name!r} must be a number or a sequence of numbers")
+            power = tuple(watts(p, f"{name!r} in case {j}") for j, p in enumerate(power))
+        else:
+            power = watts(power, repr(name))
+        out.append(CheckedHeatSource(name=name, layer=found[0], polygon=tuple((float(a), float(b)) for a, b in polygon), power=power))
+    return out
+
+
+def _source_powers(sources: list, n_cases: int) -> Optional[np.ndarray]:
+    """The powers (n_cases, n_sources) of the checked ``sources``, or None without sources; ValueError for a source whose
+    sequence of powers does not have one entry per case."""
+    if not sources:
+        return None
+    out = np.zeros((n_cases, len(sources)), dtype=DTYPE)
+    for i, source in enumerate(sources):
+        if isinstance(source.power, tuple):
+            if len(source.power) != n_cases:
+                raise ValueError(f"heat_sources: {source.name!r} names {len(source.power)} powers, the solve has {n_cases} "
+                                 "load case(s)")
+            out[:, i] = source.power
+        else:
+            out[:, i] = source.power
+    return out
+
+
+def _attach_heat_sources(thermal, prob, checked: CheckedThermalModel, layer_of, n_mesh: int):
+    """The checked model's heat sources given to the handle ``thermal``: None without sources, else a namespace of what
+    ``Thermal.set_sources`` returns -- ``faces``, ``fallback`` and ``area`` per source.  ValueError for sources on no
+    connected copper, naming them and their layers."""
+    if not checked.sources:
+        return None
+    try:
+        faces, fallback, area = thermal.set_sources(len(prob.layers), [layer_of[i] for i in range(n_mesh)],
+                                                    [source.layer for source in checked.sources],
+                                                    [np.asarray(source.polygon, dtype=DTYPE) for source in checked.sources])
+    except _hip.SourceOffCopperError as exc:
+        lost = [checked.sources[i] for i in exc.sources]
+        raise ValueError("heat_sources: " + ", ".join(f"{source.name!r} on layer {prob.layers[source.layer].name!r}" for source in lost)
+                         + (" lies" if len(lost) == 1 else " lie") + " on no connected copper: neither a face centroid under "
+                         "the footprint nor a face under its middle") from None
+    return types.SimpleNamespace(faces=faces, fallback=fallback, area=area)
+
+
+def _source_entries(checked: CheckedThermalModel, attached, powers, rises, j: int) -> tuple:
+    """(``ThermalReport.sources``, ``source_heat``) of case ``j``: ``attached`` as :func:`_attach_heat_sources` returns it,
+    ``powers`` (k, n) and ``rises`` (k, n) the footprint temperatures above ambient; ([], 0.0) without sources."""
+    if attached is None:
+        return [], 0.0
+    entries = [{"name": source.name, "layer": source.layer, "power": float(powers[j, i]), "area": float(attached.area[i]),
+                "faces": int(attached.faces[i]), "fallback": bool(attached.fallback[i]),
+                "temperature": float(checked.ambient + rises[j, i])} for i, source in enumerate(checked.sources)]
+    return entries, math.fsum(powers[j].tolist())
 
 
 def _check_interlayer(prob, interlayer) -> list:
@@ -2099,12 +2263,14 @@ def thermal_heat_triples(pairs, flows_by_case) -> tuple:
 
 
 def _thermal_reports(board: IndexedBoard, checked: CheckedThermalModel, substituted, resistors, fields: bool, theta, mean,
-                     mesh_max, mesh_vert, mesh_heat, mesh_loss, heat_val, infos, stack=None) -> list:
+                     mesh_max, mesh_vert, mesh_heat, mesh_loss, heat_val, infos, stack=None, sources=None) -> list:
     """The ThermalReports of k cases from what ``Thermal.report`` returns for them: ``theta`` (k, n_potential), ``mean`` (k,
     n_tri) or None without ``fields``, the per-mesh arrays (k, n_mesh), ``heat_val`` (k, n_resistors, 2) the heat put into the
     resistors' terminals or None, ``infos`` the info dict of each case.  ``substituted``: substitute_load_case of each case;
     ``resistors``: the (element, row) pairs of the board's resistors.  ``stack``: (flows (k, n_pair), areas (n_pair,)) of
-    the model's ``interlayer`` pairs as ``Thermal.stack_flows`` returns them, or None without pairs."""
+    the model's ``interlayer`` pairs as ``Thermal.stack_flows`` returns them, or None without pairs.  ``sources``: (what
+    :func:`_attach_heat_sources` returned, powers (k, n_source), footprint temperatures above ambient (k, n_source)) of the
+    model's ``heat_sources``, or None without."""
     ambient, voff, n_layers = checked.ambient, board.vindex.offsets, len(board.prob.layers)
 
     def cold(layer_i):
@@ -2150,11 +2316,16 @@ def _thermal_reports(board: IndexedBoard, checked: CheckedThermalModel, substitu
             deposited = float(heat_val[j, i].sum()) if heat_val is not None else 0.0
             elements[case_element] = {"heat": deposited,
                                       "flow": float(checked.links[element] * (theta[j, row[1]] - theta[j, row[2]]))}
+        total_heat = math.fsum([layer["heat"] for layer in layers] + [e["heat"] for e in elements.values()])
+        entries, source_heat = ([], 0.0) if sources is None else _source_entries(checked, *sources, j)
+        if sources is not None:
+            total_heat = total_heat + source_heat
         reports.append(ThermalReport(
             temperatures=temps if fields else None, face_temperatures=faces if fields else None,
             disconnected_temperatures=[cold(layer_i) for layer_i in range(n_layers)], hotspots=hotspots, layers=layers,
-            elements=elements, total_heat=math.fsum([layer["heat"] for layer in layers] + [e["heat"] for e in elements.values()]),
-            total_loss=math.fsum(layer["loss"] for layer in layers), info=infos[j], interlayer=interlayer))
+            elements=elements, total_heat=total_heat,
+            total_loss=math.fsum(layer["loss"] for layer in layers), info=infos[j], interlayer=interlayer, sources=entries,
+            source_heat=source_heat))
     return reports
 
 
@@ -2190,6 +2361,7 @@ def _thermal_block(prob, meshes, mesh_index_to_layer_index, checked: CheckedTher
     namespace of everything the two paths read.  On the way out the handle is closed and a stalled block is warned about."""
     substituted = [substitute_load_case(prob, case) for case in cases]
     k = len(cases)
+    source_power = _source_powers(checked.sources, k)
     board = index_board(prob, meshes, mesh_index_to_layer_index, filtered_networks, disconnected_meshes_by_layer)
     _refuse_bare_vertices(board)
     n_vert = len(board.vindex)
@@ -2211,11 +2383,15 @@ def _thermal_block(prob, meshes, mesh_index_to_layer_index, checked: CheckedTher
         n_potential = L.layout.n_potential
         thermal = _thermal_handle(L, n_potential, checked, layer_of, len(board.meshes), resistors)
         try:
+            sources = _attach_heat_sources(thermal, prob, checked, layer_of, len(board.meshes))
+            if sources is not None:
+                thermal.source_power(source_power)           # column j of every load carries the sources of case j
             laps.lap("thermal_setup")
             heat = thermal_heat_triples(pairs, flows_by_case) if checked.element_heat else None
             yield types.SimpleNamespace(board=board, substituted=substituted, pairs=pairs, resistors=resistors, plan=plan, V=V,
                                         residual_norms=residual_norms, res=res, n_tri=n_tri, n_vert=n_vert,
-                                        n_potential=n_potential, power=power, thermal=thermal, heat=heat, k=k)
+                                        n_potential=n_potential, power=power, thermal=thermal, heat=heat, k=k, sources=sources,
+                                        source_power=source_power)
         finally:
             thermal.close()
     laps.lap()
@@ -2239,6 +2415,7 @@ def _solve_block_thermal(prob, meshes, mesh_index_to_layer_index, checked: Check
         laps.lap("thermal_solve")
         mean, mesh_max, mesh_vert, mesh_heat, mesh_loss, env, env_case = blk.thermal.report(k, blk.n_tri, blk.n_vert, fields=fields)
         stack = _stack_flows(blk.thermal, checked, k)
+        sources = None if blk.sources is None else (blk.sources, blk.source_power, blk.thermal.source_report(k))
         laps.lap("thermal_report")
     if tres.status != _hip.OK and not tres.rel_residual <= max(RTOL, STALL_WARN_ABOVE):
         warnings.warn(f"The thermal solve stopped at a relative residual of {tres.rel_residual:.3e}", SolverWarning)
@@ -2247,7 +2424,7 @@ def _solve_block_thermal(prob, meshes, mesh_index_to_layer_index, checked: Check
     info = {"iterations": int(tres.iterations), "rel_residual": float(tres.rel_residual), "seconds": float(tres.seconds)}
     heat_val = heat[2].reshape(k, len(blk.resistors), 2) if heat is not None else None
     reports = _thermal_reports(board, checked, blk.substituted, blk.resistors, fields, theta, mean, mesh_max, mesh_vert, mesh_heat,
-                               mesh_loss, heat_val, [info] * k, stack)
+                               mesh_loss, heat_val, [info] * k, stack, sources)
     envelope = _thermal_envelope(board, checked.ambient, env, env_case, reports)
     laps.lap("solutions")
     return solutions, reports, envelope
@@ -2279,6 +2456,16 @@ def solve_meshed_thermal(prob, meshes, mesh_index_to_layer_index, model: Thermal
     annihilates constants, so the balance above holds; ``ThermalReport.interlayer`` gives the heat through every pair and
     the coupled area, and ``layers[i]["exchange"]`` the net heat layer i passes on.  Only connected meshes take part:
     floating copper as a pure heat spreader is out of scope.
+
+    With ``model.heat_sources`` (DESIGN.md "Heat sources") b also carries the watts of components: source s loads the
+    faces of the connected meshes of its layer whose centroid lies inside its polygon (even-odd rule), face f with the
+    share area_f / A_s of the source's power in this case, a third of it at each corner; a footprint that covers no
+    centroid loads the one face that contains the mean of its vertices.  The shares sum to 1, so ``total_heat`` is the
+    Joule and element heat plus ``source_heat``, the sum of the powers, and ``total_loss`` still equals it.  The heat of
+    ``layers[i]`` and the power densities stay the Joule heat alone.  ``ThermalReport.sources`` tells per source the power,
+    the loaded area and faces, whether the fallback was taken, and the area-weighted mean temperature of the copper under
+    it -- also with ``per_case_fields=False``.  A sequence of powers must have one entry per load case, and a source on
+    no connected copper is refused: ValueError, the latter after the device handles have been closed.
 
     The electrical block is the load-case path; the thermal operator is then assembled from the meshes the device still
     holds, the face powers of every case are computed from the potentials it holds, and all cases go through one block
@@ -2605,7 +2792,9 @@ def solve_meshed_thermal_transient(prob, meshes, mesh_index_to_layer_index, mode
 
     On the device: one electrical block solve of the cases on the load-case path, the thermal operator and the heat load
     of every case from the potentials it holds (the powers never visit the host), then per segment the steps, each with
-    the right-hand side, the block solve from the previous state, the per-mesh report and the running envelope; the
+    the right-hand side, the block solve from the previous state, the per-mesh report and the running envelope.  The
+    ``heat_sources`` of ``model.thermal`` are part of every case's load -- a segment without a case has no source heat --
+    and of ``TransientReport.total_heat``, so the balance above holds with them; the
     multigrid hierarchy of S is built once per distinct dt in a row (``info["hierarchies"]``).  ValueError, before anything
     reaches the device, for what :func:`check_transient_model`, :func:`check_load_cases`, :func:`check_schedule` and
     :func:`check_probes` refuse, an ``initial`` that names a case out of range or another number of scenarios than the
@@ -2663,6 +2852,8 @@ def solve_meshed_thermal_transient(prob, meshes, mesh_index_to_layer_index, mode
                         for layer_i in range(n_layers)] for j in range(k)]
     element_heat = [math.fsum(heat[2][heat[1] == j].tolist()) if heat is not None else 0.0 for j in range(k)]
     case_total = [math.fsum(case_layer_heat[j] + [element_heat[j]]) for j in range(k)]
+    if blk.sources is not None:                              # the load table's column j carries the sources of case j
+        case_total = [case_total[j] + math.fsum(blk.source_power[j].tolist()) for j in range(k)]
     reports = []
     for c in range(n_scen):
         # the case that led to every time: the initial case at the start (its steady state balances it), then each step's
@@ -2816,6 +3007,7 @@ def _solve_electrothermal(prob, meshes, mesh_index_to_layer_index, checked: Chec
     thermal_model = checked.thermal
     substituted = [substitute_load_case(prob, case) for case in cases]
     k, n_layers = len(cases), len(prob.layers)
+    source_power = _source_powers(thermal_model.sources, k)
     board = index_board(prob, meshes, mesh_index_to_layer_index, filtered_networks, disconnected_meshes_by_layer)
     _refuse_bare_vertices(board)
     n_vert = len(board.vindex)
@@ -2829,7 +3021,7 @@ def _solve_electrothermal(prob, meshes, mesh_index_to_layer_index, checked: Chec
     rounds_log = []
     if laps.timings is not None:
         laps.timings["rounds"] = rounds_log
-    per_case, stack_flows = [], []
+    per_case, stack_flows, source_rises, sources = [], [], [], None
     with board.assembled() as (L, _):
         laps.lap("assembly")
         resistors = [(element, row) for element, row in pairs if row[0] == "R"]
@@ -2840,6 +3032,7 @@ def _solve_electrothermal(prob, meshes, mesh_index_to_layer_index, checked: Chec
         try:
             coupled = _hip.Coupled(L.dev, thermal, [checked.alpha[layer_of[i]] for i in range(n_mesh)], thermal_model.ambient,
                                    checked.conductance_temperature)
+            sources = _attach_heat_sources(thermal, prob, thermal_model, layer_of, n_mesh)
             laps.lap("thermal_setup")
             element_rows = [row for _, row in pairs]
             for j, case in enumerate(cases):
@@ -2847,6 +3040,8 @@ def _solve_electrothermal(prob, meshes, mesh_index_to_layer_index, checked: Chec
                 log.info(f"Load case {j}: the electro-thermal loop")
                 if j > 0:
                     coupled.reset()
+                if sources is not None:                      # the same watts in every round: not scaled by the resistivity
+                    thermal.source_power(source_power[j:j + 1])
                 increments, iterations, verdict = [], [], None
                 for round_i in range(1, checked.max_rounds + 1):
                     lap = {}
@@ -2885,6 +3080,8 @@ def _solve_electrothermal(prob, meshes, mesh_index_to_layer_index, checked: Chec
                 scale = coupled.get_scale(n_tri, used=True)
                 report = thermal.report(1, n_tri, n_vert, fields=fields, envelope=False)
                 stack_flows.append(_stack_flows(thermal, thermal_model, 1))
+                if sources is not None:
+                    source_rises.append(thermal.source_report(1))
                 per_case.append((V, residual_norms, res, cols, vals, power, scale, theta, tres, report, heat, increments,
                                  iterations, converged, flows))
             laps.lap("loop")
@@ -2921,7 +3118,9 @@ def _solve_electrothermal(prob, meshes, mesh_index_to_layer_index, checked: Chec
     stacked = [None if not fields and i == 0 else np.concatenate([c[9][i] for c in per_case]) for i in range(5)]
     heat_val = np.stack([c[10][2].reshape(len(resistors), 2) for c in per_case]) if thermal_model.element_heat else None
     stack = (np.concatenate([f[0] for f in stack_flows]), stack_flows[0][1]) if thermal_model.interlayer else None
-    reports = _thermal_reports(board, thermal_model, substituted, resistors, fields, theta, *stacked, heat_val, infos, stack)
+    heat_sources = None if sources is None else (sources, source_power, np.concatenate(source_rises))
+    reports = _thermal_reports(board, thermal_model, substituted, resistors, fields, theta, *stacked, heat_val, infos, stack,
+                               heat_sources)
     env, env_case = envelope_of(theta[:, :n_vert])
     envelope = _thermal_envelope(board, thermal_model.ambient, env, env_case, reports)
     laps.lap("solutions")
@@ -2949,7 +3148,8 @@ def solve_meshed_electrothermal(prob, meshes, mesh_index_to_layer_index, model: 
     the potentials and power densities of the last electrical solve and the ThermalReport is that of the last thermal
     solve, whose load came from that electrical solve with the same scale: ``total_loss`` equals ``total_heat`` equals the
     power the sources deliver in every round, converged or not.  Cases are converged one after another on one assembly and
-    one thermal handle; the envelope is formed from their vertex temperatures by the rule of :func:`envelope_of`.
+    one thermal handle; the envelope is formed from their vertex temperatures by the rule of :func:`envelope_of`.  The
+    ``heat_sources`` of ``model.thermal`` put the same watts into every round: they are not scaled by the resistivity.
 
     :class:`ThermalRunawayError` when the increments grew in three consecutive rounds (a current-driven neck may have no
     steady state); a SolverWarning and ``converged=False`` when ``model.max_rounds`` end the loop first; ValueError for an
