@@ -24,6 +24,7 @@ import scipy.sparse as sp
 
 import sampling_ref as R
 import thermal_ref as T
+from fold_ref import mesh_sum, workgroup_sum  # noqa: F401   (definition 5's order, stated in tests/fold_ref.py)
 
 
 def board_of(meshes, mesh_layer) -> R.Board:
@@ -141,24 +142,6 @@ def operator(meshes, mesh_layer, kappa, film, n_internal, links, pairs):
 def full(G, diag):
     """G with its diagonal, as one csr_matrix."""
     return sp.csr_matrix(G + sp.diags(diag))
-
-
-def workgroup_sum(v) -> float:
-    """256 values in the device's fixed order (definition 5)."""
-    w = np.array(v, dtype=np.float64).reshape(4, 64)
-    for h in (32, 16, 8, 4, 2, 1):
-        w[:, :h] = w[:, :h] + w[:, h:2 * h]
-    return float((w[0, 0] + w[1, 0]) + (w[2, 0] + w[3, 0]))
-
-
-def mesh_sum(per_vertex) -> float:
-    """One mesh's vertices: tiles of 256, then the fold of the tiles."""
-    n = len(per_vertex)
-    tiles = [workgroup_sum(np.concatenate([per_vertex[i:i + 256], np.zeros(max(0, i + 256 - n))])) for i in range(0, n, 256)]
-    part = np.zeros(256)
-    for i, t in enumerate(tiles):
-        part[i % 256] = part[i % 256] + t
-    return workgroup_sum(part)
 
 
 def flows(meshes, mesh_layer, pairs, G, theta):

@@ -1,0 +1,449 @@
+"""Every kernel that folds in the fixed order of error.hpp (tests/fold_ref.py states it in numpy) on one board whose meshes
+have many tiles, so that the strided loop of a fold takes a second and a third step, all four waves of a fold hold tiles, and
+the list of a heat source wraps its slot ``tile & 255``.  Every comparison is made on the device's own solution.
+
+The board (jittered synthetic.jittered_grid meshes, chosen for their tile counts; h = 0.125):
+
+  mesh  layer  grid                         vertices (tiles)      faces (tiles)            what it reaches
+  A     0      257 x 258                    66 306 (260, ragged)  131 584 (514, full)      strided loop taken 2-3 times, all four waves
+  B     0      2 x 2                        4 (1)                 2 (1)                    one lane
+  C     0      92 x 92                      8 464 (34)            16 562 (65)              first lane of wave 1
+  D     1      129 x 130, spacing 2 h,      16 770 (66)           33 024 (129)             lane 0 of wave 2 (faces), wave 1 (vertices)
+               over A
+
+A source drives A against D through a lattice of vias, a second one drives C against A and returns through B: every mesh
+carries current in case 0.  Three load cases, the last one dead.  One block solve, shared by the tests.
+
+Where the summed term is a device output, or one IEEE operation on device outputs, the per-mesh sum is compared bit for bit
+with fold_ref.  Elsewhere it is compared with math.fsum of the restatement's per-item terms within fold_ref.fold_bound plus
+the tolerance the entry's own test grants per item, summed over the items.  Tops and their indices are exact everywhere."""
+import contextlib
+import math
+
+import numpy as np
+import pytest
+import scipy.sparse as sp
+
+import coupled_ref as CR
+import currents_ref as C
+import fold_ref as F
+import goal_ref as GR
+import helpers as H
+import sensitivity_ref as S
+import sources_ref as SR
+import stack_ref as K
+import thermal_ref as T
+import transient_ref as R
+from padne_amd import _hip, mesh, problem as P, solver, synthetic
+from test_load_case_currents import finished_block, plan_cuts
+from test_stack_host import G
+from test_thermal import FILM_STIFF, links_of, per_mesh, quiet
+
+pytestmark = pytest.mark.gpu
+
+TOL = 1e-12                  # tests/test_currents.py's, tests/test_error.py's and tests/test_goal_error.py's, per item
+REL_TOL = 1e-8               # tests/test_sensitivity.py's, per item
+U = 2.0 ** -53
+HA = 0.125
+#            layer, nx, ny, h, origin, seed
+GRIDS = {"A": (0, 257, 258, HA, (0.0, 0.0), 1), "B": (0, 2, 2, 1.0, (40.0, 0.0), 2), "C": (0, 92, 92, HA, (40.0, 5.0), 3),
+         "D": (1, 129, 130, 2 * HA, (0.0, 0.0), 4)}
+#            vertices, their tiles, faces, their tiles
+COUNTS = {"A": (66_306, 260, 131_584, 514), "B": (4, 1, 2, 1), "C": (8_464, 34, 16_562, 65), "D": (16_770, 66, 33_024, 129)}
+NEG_INF = (-np.inf, F.NO_INDEX)
+
+
+def tiles(n) -> int:
+    return -(-int(n) // 256)
+
+
+def fsum(a) -> float:
+    return math.fsum(np.asarray(a, dtype=np.float64).reshape(-1).tolist())
+
+
+class Wide:
+    """The board, its restatement's arrays and, inside the fixture, the assembled system with the finished block."""
+
+    def __init__(self):
+        self.meshes, self.layer_of = [], []
+        for name, (layer, nx, ny, h, origin, seed) in GRIDS.items():
+            xy, tri = synthetic.jittered_grid(nx, ny, h=h, seed=seed, jitter=0.2, origin=origin)
+            m = mesh.Mesh(np.asarray(xy, dtype=np.float64).reshape(-1, 2), np.asarray(tri, dtype=np.int32).reshape(-1, 3))
+            got = (len(m.points), tiles(len(m.points)), len(m.triangles), tiles(len(m.triangles)))
+            assert got == COUNTS[name], (name, got)
+            self.meshes.append(m)
+            self.layer_of.append(layer)
+        assert COUNTS["A"][0] % 256 != 0 and COUNTS["A"][2] % 256 == 0 and COUNTS["A"][1] > 256 and COUNTS["A"][3] > 2 * 256
+        top = P.Layer(shape=H.Geoms(1), name="F.Cu", conductance=2000.0)
+        bottom = P.Layer(shape=H.Geoms(1), name="B.Cu", conductance=1000.0)
+        at = lambda layer, x, y: P.Connection(layer=layer, point=H.XY(x, y))      # noqa: E731
+        c = [at(top, 4, 4), at(bottom, 28, 28), at(top, 50, 15), at(top, 20, 4), at(top, 30, 20), at(top, 40, 0), at(top, 41, 1),
+             at(top, 41, 6)]
+        self.sources = [P.CurrentSource(f=c[0].node_id, t=c[1].node_id, current=2.0),
+                        P.CurrentSource(f=c[2].node_id, t=c[3].node_id, current=0.5)]
+        elements = self.sources + [P.Resistor(a=c[4].node_id, b=c[5].node_id, resistance=0.01),       # A - B
+                                   P.Resistor(a=c[6].node_id, b=c[7].node_id, resistance=0.01)]       # B - C
+        for x in (6, 12, 18, 24):                            # the via lattice between A and D
+            for y in (8, 16, 24):
+                a, b = at(top, x, y), at(bottom, x, y)
+                c += [a, b]
+                elements.append(P.Resistor(a=a.node_id, b=b.node_id, resistance=0.002))
+        self.prob = P.Problem(layers=[top, bottom], networks=[P.Network(connections=c, elements=elements)])
+        self.cases = [{}, {self.sources[0]: 3.4, self.sources[1]: -0.3}, {e: 0.0 for e in self.sources}]
+        self.board = solver.index_board(self.prob, self.meshes, self.layer_of)
+        nodes = self.board.node_indexer
+        self.pairs = solver.global_elements(list(self.prob.networks), nodes)
+        self.n_internal = nodes.internal_node_count
+        sigma = [self.prob.layers[l].conductance for l in self.layer_of]
+        self.system = S.System(meshes=[(m.points, m.triangles, s) for m, s in zip(self.meshes, sigma)], n_internal=self.n_internal,
+                               rows=[row for _, row in self.pairs], ground=solver.find_best_ground_node_index(self.prob, nodes),
+                               layer_of=self.layer_of, prob=self.prob, pairs=self.pairs, nodes=nodes, flat=elements)
+        self.flat = [(np.asarray(m.points, dtype=np.float64), np.asarray(m.triangles, dtype=np.int64)) for m in self.meshes]
+        self.xy, self.tri, self.face_mesh, self.voff, self.toff = T.flatten(self.flat)
+        self.sigma = np.asarray(sigma, dtype=np.float64)
+        self.n_vert, self.n_tri, self.n_mesh = len(self.xy), len(self.tri), len(self.meshes)
+        self.n_pot = self.n_vert + self.n_internal
+        self.ml = np.asarray(self.layer_of, dtype=np.int32)
+        checked = solver.check_thermal_model(self.prob, solver.ThermalModel(film=FILM_STIFF))
+        self.kappa, self.film = per_mesh(checked, self.layer_of)
+        self.links = links_of(self.pairs, checked)
+        self.M = T.lumped(self.xy, self.tri)
+        self.hM = np.repeat(np.asarray(self.film, dtype=np.float64), np.diff(self.voff)) * self.M
+        self.face_area = T.face_area(self.xy, self.tri)
+
+    def faces(self, m):
+        return int(self.toff[m]), int(self.toff[m + 1])
+
+    def verts(self, m):
+        return int(self.voff[m]), int(self.voff[m + 1])
+
+    def thermal(self, **kw):
+        return _hip.Thermal(self.L.dev, self.n_pot, self.kappa, self.film, [l[0] for l in self.links], [l[1] for l in self.links],
+                            [l[2] for l in self.links], **kw)
+
+    def sum_check(self, got, terms, per_item, n_tiles, what):
+        """``got`` against math.fsum of ``terms`` within fold_bound plus ``per_item`` summed; the figures are printed."""
+        want, size, grant = fsum(terms), fsum(np.abs(terms)), fsum(per_item)
+        bound = F.fold_bound(n_tiles, size)
+        print(what, "sum", want, "error", abs(got - want), "fold bound", bound, "per-item grant", grant)
+        assert abs(got - want) <= bound + grant, what
+
+
+@pytest.fixture(scope="module")
+def wide(ctx):
+    w = Wide()
+    assert 91_000 < w.n_pot < 92_000
+    with w.board.assembled() as (L, _r):
+        w.L = L
+        w.plan, w.V = quiet(finished_block, w.board, L, solver.check_load_cases(w.prob, w.cases))
+        try:
+            yield w
+        finally:
+            w.plan.close()
+
+
+def test_the_board_has_the_tile_counts_of_the_table(wide):
+    for m, name in enumerate(GRIDS):
+        assert (wide.voff[m + 1] - wide.voff[m], tiles(wide.voff[m + 1] - wide.voff[m]), wide.toff[m + 1] - wide.toff[m],
+                tiles(wide.toff[m + 1] - wide.toff[m])) == COUNTS[name]
+    assert wide.V.shape[1] == 3 and (wide.V[:, 2] == 0.0).all()                   # the dead case
+    assert wide.n_internal == 0
+
+
+# ---- currents and load-case currents -----------------------------------------------------------------------------------------
+
+def cuts_of(w):
+    """Down the whole height of A (a line no vertex lies on), and a line between A and the meshes B and C."""
+    top = w.prob.layers[0]
+    return [solver.Cut(top, (15.97, -1.0), (15.97, 34.0)), solver.Cut(top, (36.0, -1.0), (36.0, 34.0))]
+
+
+def test_currents_of_three_cases(wide):
+    """Per case and mesh: the hotspot is the fold of the device's own |J|, exactly; the power against math.fsum of the
+    restated face powers (TOL per face, as tests/test_currents.py grants a layer's sum) and, since those are the bits
+    thermal_face_power_kernel writes from the same expression (tests/test_thermal.py), bit for bit against fold_ref.  The long
+    cut against math.fsum of the cut rule's terms (TOL of each, as tests/test_currents.py grants a cut); its fold runs over
+    (cut, tile) pairs, at most the tiles of the layer.  The dead case: zeros, and every hotspot at its mesh's first face."""
+    w = wide
+    cl, cxy = plan_cuts(w.system, cuts_of(w))
+    first = w.plan.current_cases(3, w.n_tri, w.ml, cl, cxy)
+    second = w.plan.current_cases(3, w.n_tri, w.ml, cl, cxy)
+    assert all(np.array_equal(a, b) for a, b in zip(first, second))              # two calls, the same bits
+    J, mag, env, env_case, mmax, mface, mpow, cut = first
+    one = w.plan.current_report(3, w.n_tri, w.ml, cl, cxy)
+    assert np.array_equal(one[2], mmax[0]) and np.array_equal(one[3], mface[0]) and np.array_equal(one[4], cut[0])
+    assert (mmax[0] > 0).all() and (mpow[0] > 0).all()                            # every mesh carries current in case 0
+    # the tiles the long cut crosses: more than one stride of its fold
+    lo, hi = w.faces(0)
+    x = w.xy[w.tri[lo:hi], 0]
+    crossed = np.unique(np.flatnonzero((x.min(axis=1) < 15.97) & (x.max(axis=1) > 15.97)) // 256)
+    print("tiles of A the long cut crosses:", len(crossed))
+    assert len(crossed) > 256
+    layer_tiles = sum(tiles(w.toff[m + 1] - w.toff[m]) for m in range(w.n_mesh) if w.layer_of[m] == 0)
+    for j in range(3):
+        xj = w.V[:, j]
+        power = T.face_power(w.xy, w.tri, w.face_mesh, w.sigma, xj[:w.n_vert])
+        for m in range(w.n_mesh):
+            lo, hi = w.faces(m)
+            assert (mmax[j, m], mface[j, m]) == F.mesh_top(mag[j, lo:hi], np.arange(lo, hi)), (j, m)
+            w.sum_check(mpow[j, m], power[lo:hi], TOL * power[lo:hi], tiles(hi - lo), f"power, case {j}, mesh {m}")
+            assert mpow[j, m] == F.mesh_sum(power[lo:hi]), (j, m)
+        terms = C.cut_terms(w.system, xj, 0, cxy[0, :2], cxy[0, 2:])
+        w.sum_check(cut[j, 0], terms, TOL * np.abs(terms), layer_tiles, f"long cut, case {j}")
+        assert len(C.cut_terms(w.system, xj, 0, cxy[1, :2], cxy[1, 2:])) == 0 and cut[j, 1] == 0.0
+    assert abs(cut[0, 0]) > 0 and len(terms) > 2 * 257
+    assert np.array_equal(mface[2], w.toff[:-1]) and (mmax[2] == 0.0).all() and (mpow[2] == 0.0).all() and (cut[2] == 0.0).all()
+    want_env, want_case = solver.envelope_of(mag)
+    assert np.array_equal(env, want_env) and np.array_equal(env_case, want_case)
+    assert (env_case == 1).any() and (env_case == 0).any()
+
+
+# ---- sensitivities -----------------------------------------------------------------------------------------------------------
+
+def test_sensitivity_totals_of_two_objectives(wide):
+    """Adjoint j is column j of the block (W = e_j: the other columns enter as 0 x, exactly).  Objective 0 is the power,
+    objective 1 a signed sum.  The totals against the restatement's s_f with what tests/test_sensitivity.py grants a density
+    (REL_TOL of the largest, times the face's area); and against the device's own densities, whose products with the area
+    are the summed s_f up to the two roundings of s_f / area * area."""
+    w = wide
+    _power, density, totals = w.plan.sensitivity_block(np.array([[1.0, 0.0, 0.0], [0.0, 1.0, 0.0]]), w.n_tri, w.n_mesh)
+    *_, area = S.faces(w.system)
+    x = w.V[:, 0]
+    for j in range(2):
+        lam = w.V[:, j]
+        sf, size = S.face_s(w.system, x, lam), S.face_s_bound(w.system, x, lam)
+        grant = REL_TOL * max(np.abs(sf / area).max(), (size / area).max()) * area
+        own = density[j] * w.face_area
+        for m in range(w.n_mesh):
+            lo, hi = w.faces(m)
+            w.sum_check(totals[j, m], sf[lo:hi], grant[lo:hi], tiles(hi - lo), f"sensitivity, objective {j}, mesh {m}")
+            w.sum_check(totals[j, m], own[lo:hi], 3 * U * np.abs(own[lo:hi]), tiles(hi - lo), f"the same from the densities, {j}, {m}")
+    assert (totals[0] > 0).all() and (density[1] < 0).any() and (density[1] > 0).any()
+
+
+# ---- error estimate and goal error ---------------------------------------------------------------------------------------------
+
+def test_error_estimate_and_goal_error_of_one_objective(wide):
+    """Field 0 is column 0 and the adjoint column 1 (W = e_1).  Per mesh against math.fsum of the restatement's terms with
+    what tests/test_goal_error.py grants them: E to TOL of the squared scale of every eta_f (and the three roundings between
+    eta_f^2, its root and its square), P to TOL of itself, omega and delta to TOL of the pair's scale.  omega_f and delta_f
+    come home, so their sums are also held to fold_ref bit for bit.  The tops are the folds of the device's own eta and omega."""
+    w = wide
+    G_, eta, mesh_E, mesh_P, mesh_max, mesh_face = w.plan.error_estimate(3, w.n_tri, w.n_vert, w.n_mesh)
+    _p, field0, dual, delta, omega, m_omega, m_delta, m_top, m_face = w.plan.goal_error(np.array([[0.0, 1.0, 0.0]]), w.n_tri, w.n_vert,
+                                                                                     w.n_mesh)
+    for a, b in zip(field0, (G_, eta, mesh_E, mesh_P, mesh_max, mesh_face)):
+        assert np.array_equal(a, b)                          # goal.hip's fold of field 0 is error.hip's, bit for bit
+    want = GR.goal_flat(w.xy, w.tri, w.face_mesh, w.sigma, np.stack([w.V[:w.n_vert, 0], w.V[:w.n_vert, 1]]))
+    est = want.primal
+    s0 = est.eta_scale(w.tri)
+    pair = want.pair_scale(w.tri, 0)
+    eta2 = est.eta * est.eta                                 # eta_f^2 of the restatement, up to the roundings of sqrt and square
+    power = est.sigma * est.area * (est.g ** 2).sum(axis=1)
+    for m in range(w.n_mesh):
+        lo, hi = w.faces(m)
+        n, idx = tiles(hi - lo), np.arange(lo, hi)
+        w.sum_check(mesh_E[m], eta2[lo:hi], TOL * s0[lo:hi] ** 2 + 3 * U * eta2[lo:hi], n, f"E, mesh {m}")
+        w.sum_check(mesh_P[m], power[lo:hi], TOL * power[lo:hi], n, f"P, mesh {m}")
+        assert (mesh_max[m], mesh_face[m]) == F.mesh_top(eta[lo:hi], idx), m
+        w.sum_check(m_omega[0, m], want.omega[0, lo:hi], TOL * pair[lo:hi], n, f"omega, mesh {m}")
+        w.sum_check(m_delta[0, m], want.delta[0, lo:hi], TOL * pair[lo:hi], n, f"delta, mesh {m}")
+        assert m_omega[0, m] == F.mesh_sum(omega[0, lo:hi]) and m_delta[0, m] == F.mesh_sum(delta[0, lo:hi]), m
+        assert (m_top[0, m], m_face[0, m]) == F.mesh_top(omega[0, lo:hi], idx), m
+    assert (mesh_E > 0).all() and (delta[0] < 0).any() and (delta[0] > 0).any()
+
+
+# ---- the thermal report, the interlayer flows and the heat sources ------------------------------------------------------------
+
+def footprints(w):
+    """All of A (B and C lie beyond x = 40); a disc on A; a speck inside a face of A's last tile, off its centroid."""
+    angle = 2 * np.pi * np.arange(64) / 64
+    disc = np.stack([16.0 + 8.5 * np.cos(angle), 16.0 + 8.5 * np.sin(angle)], axis=1)
+    f = w.faces(0)[0] + 513 * 256 + 100
+    p = 0.5 * w.xy[w.tri[f, 0]] + 0.3 * w.xy[w.tri[f, 1]] + 0.2 * w.xy[w.tri[f, 2]]
+    return [np.array([(-1.0, -1.0), (33.0, -1.0), (33.0, 33.2), (-1.0, 33.2)]), disc,
+            np.array([p + (-1e-7, -1e-7), p + (1e-7, -1e-7), p + (1e-7, 1e-7), p + (-1e-7, 1e-7)])], f
+
+
+def loads_of(w):
+    """Four columns of face powers and node heat as tests/test_thermal.py's report test makes them: column 2 is empty,
+    column 3 repeats column 0.  And the powers of the three sources, likewise."""
+    rng = np.random.default_rng(11)
+    Pf = rng.uniform(0.0, 1e-3, (4, w.n_tri))
+    nodes, cols, vals = rng.integers(0, w.n_pot, 15), rng.integers(0, 2, 15), rng.uniform(0.0, 1e-2, 15)
+    Pf[2], Pf[3] = 0.0, Pf[0]
+    again = cols == 0
+    heat = (np.concatenate([nodes, nodes[again]]), np.concatenate([cols, np.full(again.sum(), 3)]), np.concatenate([vals, vals[again]]))
+    watts = rng.uniform(0.01, 0.4, (4, 3))
+    watts[2], watts[3] = 0.0, watts[0]
+    return Pf, heat, watts
+
+
+@pytest.fixture(scope="module")
+def heated(wide):
+    """The stacked handle with its three sources, one solve of four columns and everything read from it, twice where two
+    calls must agree."""
+    w = wide
+    polygons, speck_face = footprints(w)
+    Pf, heat, watts = loads_of(w)
+    th = w.thermal(mesh_layer=w.layer_of, pairs=[(0, 1, G)])
+    try:
+        out = dict(polygons=polygons, speck_face=speck_face, Pf=Pf, watts=watts)
+        out["set"] = th.set_sources(2, w.layer_of, [0, 0, 0], polygons)
+        out["lists"] = th.source_lists()
+        th.source_power(watts[:1])
+        out["load"] = th.load(np.zeros((1, w.n_tri)))
+        th.source_power(watts)
+        out["theta"], res = th.solve(Pf, heat)
+        assert res.status == _hip.OK
+        out["report"] = [th.report(4, w.n_tri, w.n_vert) for _ in range(2)]
+        out["flows"] = [th.stack_flows(4) for _ in range(2)]
+        out["rise"] = [th.source_report(4) for _ in range(2)]
+        out["G"] = th.stack_matrix()
+        out["M"] = th.lumped(w.n_vert)
+    finally:
+        th.close()
+    return out
+
+
+def test_thermal_report_of_four_columns(wide, heated):
+    """Face means, heat input (the sum of the face powers) and film loss (the sum of hM theta, one product of device
+    outputs) bit for bit; the hotspot with its vertex exactly, in the empty column each mesh's first vertex; the envelope by
+    the sequential rule."""
+    w, theta, Pf = wide, heated["theta"], heated["Pf"]
+    mean, top, vert, heat_in, loss, env, env_case = heated["report"][0]
+    assert all(np.array_equal(a, b) for a, b in zip(heated["report"][0], heated["report"][1]))      # two calls, the same bits
+    assert np.array_equal(heated["M"], w.M)
+    c = T.corners(w.tri)
+    for j in range(4):
+        assert np.array_equal(mean[j], ((theta[j][c[:, 0]] + theta[j][c[:, 1]]) + theta[j][c[:, 2]]) / 3)
+        for m in range(w.n_mesh):
+            (lo, hi), (v0, v1) = w.faces(m), w.verts(m)
+            assert heat_in[j, m] == F.mesh_sum(Pf[j, lo:hi]), (j, m)
+            terms = w.hM[v0:v1] * theta[j, v0:v1]
+            assert loss[j, m] == F.mesh_sum(terms), (j, m)
+            assert abs(loss[j, m] - fsum(terms)) <= F.fold_bound(tiles(v1 - v0), fsum(np.abs(terms))), (j, m)
+            assert (top[j, m], vert[j, m]) == F.mesh_top(theta[j, v0:v1], np.arange(v0, v1), empty=NEG_INF), (j, m)
+    assert np.array_equal(vert[2], w.voff[:-1]) and (top[2] == 0.0).all()         # the complete tie over 260 tiles
+    assert (theta[2] == 0.0).all() and np.array_equal(theta[3], theta[0]) and (top[0] > 0).all()
+    best, which = T.envelope(theta[:, :w.n_vert])
+    assert np.array_equal(env, best) and np.array_equal(env_case, which)
+    assert (env_case == 0).any() and (env_case == 1).any() and not (env_case >= 2).any()
+
+
+def test_interlayer_flows(wide, heated):
+    """padne_thermal_stack_flows against stack_ref.flows on the device's own G and theta, bit for bit: A's 260 vertex tiles
+    take the stack fold's strided loop twice."""
+    w, theta = wide, heated["theta"]
+    flow, area = heated["flows"][0]
+    assert np.array_equal(flow, heated["flows"][1][0]) and np.array_equal(area, heated["flows"][1][1])
+    indptr, indices, data, _diag = heated["G"]
+    Goff = sp.csr_matrix((data, indices.astype(np.int64), indptr.astype(np.int64)), shape=(w.n_pot, w.n_pot))
+    flow_want, area_want = K.flows(w.flat, w.layer_of, [(0, 1, G)], Goff, theta)
+    print("flows", flow[:, 0], "area", area)
+    assert np.array_equal(flow, flow_want) and np.array_equal(area, area_want)
+    assert flow[2, 0] == 0.0 and flow[0, 0] != 0.0 and area[0] > 0.9 * 32.0 * 32.0
+
+
+def test_heat_sources_lists_areas_loads_and_footprint_temperatures(wide, heated):
+    """The list of 131 584 faces wraps the slot ``tile & 255`` twice, the disc's fills some slots and leaves others empty, the
+    speck's owner is found in the last of the 514 strides of the owner search.  Everything is sources_ref's, bit for bit."""
+    w = wide
+    counts, fallback, area = heated["set"]
+    ptr, face = heated["lists"]
+    ref = SR.Restated(w.flat, w.layer_of, [(0, polygon) for polygon in heated["polygons"]])
+    print("list lengths", counts, "fallback", fallback)
+    assert counts[0] == COUNTS["A"][2] and 16_384 < counts[1] < 65_536 and counts[2] == 1
+    assert np.array_equal(fallback, [0, 0, 1]) and face[ptr[2]] == heated["speck_face"]
+    assert np.array_equal(counts, ref.counts) and np.array_equal(fallback.astype(bool), ref.fallback)
+    assert np.array_equal(ptr, ref.ptr) and np.array_equal(face, ref.face)
+    assert np.array_equal(area, ref.A)
+    assert [F.list_sum(w.face_area[face[ptr[s]:ptr[s + 1]]]) for s in range(3)] == list(area)
+    assert np.array_equal(heated["load"], ref.load(w.n_pot, heated["watts"][:1]))
+    assert abs(fsum(heated["load"]) - fsum(heated["watts"][0])) <= 1e-13 * fsum(heated["watts"][0])
+    assert np.array_equal(heated["rise"][0], heated["rise"][1])
+    assert np.array_equal(heated["rise"][0], ref.temperature(heated["theta"], 0.0))
+    assert (heated["rise"][0][[0, 1, 3]] > 0.0).all() and (heated["rise"][0][2] == 0.0).all()
+
+
+# ---- transient ------------------------------------------------------------------------------------------------------------------
+
+def test_two_transient_steps(wide):
+    """Column 0 heats from ambient, column 1 holds the steady state of case 1, column 2 stays off: the complete tie."""
+    w = wide
+    cap_of_mesh = [3e-3 * (1 + layer) for layer in w.layer_of]
+    Cv = R.capacity(w.voff, cap_of_mesh, w.M)
+    Pf, heat, _watts = loads_of(w)
+    keep = heat[1] < 2
+    probes = np.array([0, w.voff[1] - 1, w.n_pot - 1], dtype=np.int64)
+    dt = 3e-3 / FILM_STIFF / 20
+    with contextlib.ExitStack() as stack:
+        th = w.thermal()
+        stack.callback(th.close)
+        tr = _hip.Transient(th, cap_of_mesh)
+        stack.callback(tr.close)
+        assert np.array_equal(tr.capacity(w.n_vert), Cv)
+        tr.loads(Pf[:2], (heat[0][keep], heat[1][keep], heat[2][keep]))
+        tr.start([None, 1, None])
+        states, outs = [tr.state()], []
+        for _ in range(2):
+            outs.append(tr.run(dt, 1, [0, 1, None], probes))
+            states.append(tr.state())
+        env, env_step = tr.envelope(w.n_vert)
+    for out, theta in zip(outs, states[1:]):
+        assert np.array_equal(out["probes"][0], theta[:, probes])
+        for c in range(3):
+            for m in range(w.n_mesh):
+                v0, v1 = w.verts(m)
+                assert out["stored"][0, c, m] == F.mesh_sum(Cv[v0:v1] * theta[c, v0:v1]), (c, m)
+                assert out["loss"][0, c, m] == F.mesh_sum(w.hM[v0:v1] * theta[c, v0:v1]), (c, m)
+                assert (out["max"][0, c, m], out["vertex"][0, c, m]) == F.mesh_top(theta[c, v0:v1], np.arange(v0, v1), empty=NEG_INF)
+            top, vert, stored, loss = R.mesh_report(w.voff, Cv, w.hM, theta[c])          # transient_ref's own statement
+            assert np.array_equal(out["max"][0, c], top) and np.array_equal(out["vertex"][0, c], vert)
+            for m in range(w.n_mesh):
+                v0, v1 = w.verts(m)
+                n = tiles(v1 - v0)
+                assert abs(out["stored"][0, c, m] - stored[m]) <= F.fold_bound(n, fsum(np.abs(Cv[v0:v1] * theta[c, v0:v1])))
+                assert abs(out["loss"][0, c, m] - loss[m]) <= F.fold_bound(n, fsum(np.abs(w.hM[v0:v1] * theta[c, v0:v1])))
+    assert np.array_equal(outs[1]["vertex"][0, 2], w.voff[:-1]) and (outs[1]["max"][0, 2] == 0.0).all()
+    assert (outs[1]["stored"][0, 0] > outs[0]["stored"][0, 0]).all()              # column 0 heats
+    states = np.stack(states)
+    for c in range(3):
+        best, step = R.envelope(states[:, c, :w.n_vert])
+        assert np.array_equal(env[c], best) and np.array_equal(env_step[c], step), c
+    assert (env_step[2] == 0).all() and env_step[0].max() == 2
+
+
+# ---- electro-thermal --------------------------------------------------------------------------------------------------------------
+
+def test_scale_means_and_increment(wide):
+    """The increment is the largest change of a face mean, found by one workgroup over all 708 tiles: first anywhere (a
+    random theta), then with the only change in the board's last faces (the third stride, wave 3), then in tile 300 (the
+    second stride, wave 0)."""
+    w = wide
+    alpha = [3.93e-3 * (1 + 0.25 * m) for m in range(w.n_mesh)]
+    rng = np.random.default_rng(8)
+    thetas = [rng.uniform(0.0, 80.0, w.n_pot)]
+    bumped = (w.n_tri - 1, 300 * 256 + 7)
+    for f, bump in zip(bumped, (7.5, 3.25)):
+        thetas.append(thetas[-1].copy())
+        thetas[-1][w.tri[f]] += bump
+    assert tiles(w.n_tri) == 708                             # (this kernel's tiles run over all faces, not mesh by mesh)
+    with contextlib.ExitStack() as stack:
+        th = w.thermal()
+        stack.callback(th.close)
+        coupled = _hip.Coupled(w.L.dev, th, alpha, 31.0, 20.0)
+        stack.callback(coupled.close)
+        coupled.set_scale(rng.uniform(0.5, 1.5, w.n_tri))
+        got = []
+        for theta in thetas:
+            d = coupled.update(theta)
+            got.append((d, *coupled.get_scale(w.n_tri, means=True)))
+    prev = np.zeros(w.n_tri)
+    for theta, (d, s, mean), f in zip(thetas, got, (None,) + bumped):
+        s_want, mean_want = CR.scale(w.tri, w.face_mesh, alpha, 31.0, 20.0, theta)
+        assert np.array_equal(mean, mean_want) and np.array_equal(s, s_want)
+        at = int(np.argmax(np.abs(mean_want - prev)))
+        print("increment", d, "at face", at, "tile", at // 256)
+        assert d == np.abs(mean_want - prev).max() and d > 0 and f in (None, at)
+        prev = mean_want
