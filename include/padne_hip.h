@@ -767,7 +767,8 @@ int padne_coupled_power_density(padne_ctx *ctx, padne_coupled *cp, padne_kkt *pl
  * K and the links annihilate constants: sum_v Cv (theta_{n+1} - theta_n) / dt + sum_v film M_v theta_{n+1} = sum_v B[j]_v.
  * The handle borrows the thermal handle `th` (which must outlive it; destroy this one first) and owns Cv, S (A's pattern,
  * its own values, the dt they hold), the load table B[n_case][n_potential], the state theta[n_cols][n_potential], the
- * running envelope and the step counter.  The coupling is one-way: the face powers do not follow the temperature.
+ * running envelope and the step counter.  The coupling is one-way: the face powers do not follow the temperature (with the
+ * entries of "transient electro-thermal" below, which rewrite a load slot between two steps, they do).
  * PADNE_E_INVALID for a null or foreign handle, an n_mesh that is not the mesh's and a capacity that is not finite and
  * positive; a refused call leaves the handle as it was. */
 typedef struct padne_transient padne_transient;
@@ -826,6 +827,36 @@ int padne_transient_state(padne_ctx *ctx, const padne_transient *tr, double *the
 int padne_transient_envelope(padne_ctx *ctx, const padne_transient *tr, double *env_out, int32_t *env_step_out);
 /* steps and time since the start, multigrid hierarchies built for S since creation (each may be null) */
 int padne_transient_clock(const padne_transient *tr, int64_t *step_out, double *time_out, int64_t *hierarchies_out);
+
+/* ---- transient electro-thermal: the resistivity follows the temperature over time ------------------
+ * No reference counterpart ("Transient electro-thermal").  A coupling handle and a transient handle made on one
+ * thermal handle, joined: a step from t_n while case j is on is padne_coupled_update_transient (the scale from theta_n),
+ * padne_coupled_revalue, the caller's one-column electrical solve of case j on a fresh padne_kkt plan,
+ * padne_coupled_transient_load (that solve's heat into slot j of the load table) and one step of padne_transient_run under
+ * case j.  The nonlinear term is lagged by one step.  Every entry returns PADNE_E_INVALID, leaving the handles as they were,
+ * for a null or foreign handle, handles that do not stand on one thermal handle, and what it names below. */
+/* The load table as n_case (1 .. 4096) slots of exact zeros, for padne_coupled_transient_load to fill.  Like
+ * padne_transient_loads, a schedule under way ends: padne_transient_start follows. */
+int padne_transient_reserve_loads(padne_ctx *ctx, padne_transient *tr, int32_t n_case);
+/* B[slot] = the heat load padne_coupled_solve_kkt forms before it solves, bit for bit: the face powers of the one column the
+ * last padne_kkt_finish_block left on `plan` with sigma[m] * s[t], s the used scale, a third of each to every corner, the
+ * node-heat triples (columns 0), the thermal handle's heat sources with the powers set for one column.  The state, the
+ * clock, the envelope and a schedule under way are untouched: the next step under case `slot` uses the new load.  The same
+ * launch sequence writes mesh_heat_out[n_mesh], the sum of every mesh's face powers [W] in the fixed order of
+ * padne_thermal_report's sums: two calls give the same bits.  The face powers pass through the thermal handle's array, which
+ * then holds no solve to report on.  PADNE_E_INVALID for a slot out of range (or no table), an n_mesh that is not the mesh's,
+ * a plan without a finished one-column block of this system, and what padne_thermal_solve refuses of the triples. */
+int padne_coupled_transient_load(padne_ctx *ctx, padne_coupled *cp, padne_transient *tr, padne_kkt *plan, int32_t slot,
+                                 int64_t n_heat, const int64_t *heat_node, const int32_t *heat_col, const double *heat_val,
+                                 int32_t n_mesh, double *mesh_heat_out);
+/* padne_coupled_update reading column `col` of the transient handle's state on the device: the bits of padne_coupled_update
+ * given that theta from the host, and no vector crosses to the host.  PADNE_E_INVALID before padne_transient_start and for a
+ * column out of range; for a face whose 1 + alpha (T - T0) is not finite and positive, the message of padne_coupled_update. */
+int padne_coupled_update_transient(padne_ctx *ctx, padne_coupled *cp, const padne_transient *tr, int32_t col,
+                                   double *increment_out);
+/* *min_out, *max_out: the smallest and the largest used scale over the faces, per 256 faces and then by one workgroup (exact:
+ * no rounding is involved).  PADNE_E_INVALID for a mesh without faces. */
+int padne_coupled_scale_range(padne_ctx *ctx, const padne_coupled *cp, double *min_out, double *max_out);
 
 /* ---- introspection for benchmarks ---------------------------------------------------------- */
 /* algorithmic bytes of one CSR SpMV: 12*nnz + 20*n_rows + 4   */

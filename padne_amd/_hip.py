@@ -192,6 +192,10 @@ SIGNATURES = {
     "padne_coupled_update": (C.c_int, [_P, _P, _I64, _PF64, _PF64]),
     "padne_coupled_solve_kkt": (C.c_int, [_P, _P, _P, _I64, _PI64, _PI32, _PF64, C.POINTER(SolveOpts), _PF64, C.POINTER(SolveInfo)]),
     "padne_coupled_power_density": (C.c_int, [_P, _P, _P, _PF64]),
+    "padne_transient_reserve_loads": (C.c_int, [_P, _P, C.c_int32]),
+    "padne_coupled_transient_load": (C.c_int, [_P, _P, _P, _P, C.c_int32, _I64, _PI64, _PI32, _PF64, C.c_int32, _PF64]),
+    "padne_coupled_update_transient": (C.c_int, [_P, _P, _P, C.c_int32, _PF64]),
+    "padne_coupled_scale_range": (C.c_int, [_P, _P, _PF64, _PF64]),
     "padne_spmv_algorithmic_bytes": (_I64, [_P]),
     "padne_spmv_time": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _PF64]),
 }
@@ -1338,6 +1342,11 @@ class Transient:
                                                        _ptr(node, _PI64), _ptr(col, _PI32), _ptr(val, _PF64)))
         self.n_case = int(n_case)
 
+    def reserve_loads(self, n_case: int) -> None:
+        """The load table as ``n_case`` slots of zeros, for ``Coupled.transient_load`` to fill; ``start`` follows."""
+        _check(self.ctx._lib.padne_transient_reserve_loads(self.ctx._h, self._h, int(n_case)))
+        self.n_case = int(n_case)
+
     def load_vectors(self) -> np.ndarray:
         """The load table (n_case, n_potential)."""
         out = np.empty((self.n_case, self.n_potential), dtype=np.float64)
@@ -1495,6 +1504,30 @@ class Coupled:
         lib = self.ctx._lib
         return self.thermal._solve(lambda *a: lib.padne_coupled_solve_kkt(self.ctx._h, self._h, plan._h, *a), 1, heat, rtol,
                                    max_iter, precond, download)
+
+    def update_transient(self, transient: "Transient", col: int = 0) -> float:
+        """``update`` reading column ``col`` of ``transient``'s state on the device (include/padne_hip.h, "transient
+        electro-thermal"): the largest change of a face mean [K]."""
+        d = C.c_double()
+        _check(self.ctx._lib.padne_coupled_update_transient(self.ctx._h, self._h, transient._h, int(col), C.byref(d)))
+        return d.value
+
+    def transient_load(self, transient: "Transient", plan: "KktPlan", slot: int, heat=None) -> np.ndarray:
+        """Slot ``slot`` of ``transient``'s load table from the one column of ``plan``'s finished block, with the used scale in
+        the face powers, the node-heat triples ``heat`` (columns 0) and the thermal handle's heat sources: the load
+        ``solve_kkt`` forms.  Returns the copper heat of every mesh (n_mesh,) [W]."""
+        node, col, val = Thermal._heat(heat)
+        out = np.empty(transient.n_mesh, dtype=np.float64)
+        _check(self.ctx._lib.padne_coupled_transient_load(self.ctx._h, self._h, transient._h, plan._h, int(slot), node.shape[0],
+                                                          _ptr(node, _PI64), _ptr(col, _PI32), _ptr(val, _PF64), transient.n_mesh,
+                                                          _ptr(out, _PF64)))
+        return out
+
+    def scale_range(self) -> tuple:
+        """(the smallest, the largest) used scale over the faces."""
+        lo, hi = C.c_double(), C.c_double()
+        _check(self.ctx._lib.padne_coupled_scale_range(self.ctx._h, self._h, C.byref(lo), C.byref(hi)))
+        return lo.value, hi.value
 
     def power_density(self, plan: "KktPlan", n_tri: int) -> np.ndarray:
         """``KktPlan.power_density_block(1, n_tri)[0]`` times the used scale, on the device."""

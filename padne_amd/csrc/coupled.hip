@@ -29,21 +29,7 @@
 #include <cmath>
 #include <vector>
 
-struct padne_coupled {
-    padne_ctx *ctx = nullptr;
-    padne_csr *L = nullptr;                  // borrowed: the electrical system, revalued in place
-    padne_thermal *th = nullptr;             // borrowed: its lists and its theta
-    long long n_vert = 0, n_tri = 0, nnz = 0;
-    int n_mesh = 0;
-    double *L0 = nullptr;                    // [nnz] the assembled values
-    // [n_tri]: the scale of the next revalue, the scale of the last one (what the face kernels use: they belong to the system
-    // that was solved), and the face means of the last update
-    double *s = nullptr, *s_used = nullptr, *prev = nullptr;
-    double *alpha = nullptr;                 // [n_mesh] on the device
-    double ambient = 0.0, t0 = 0.0;
-};
-
-namespace padne {
+namespace padne {                            // (struct padne_coupled: thermal.hpp)
 
 constexpr unsigned long long kCoupledNoFace = ~0ULL;
 
@@ -197,7 +183,7 @@ static void coupled_free(padne_coupled *cp) {
 
 // the scale kernel and its fold on `theta` (device, null: zeros): *d_out (may be null) the largest change of a face mean;
 // PADNE_E_INVALID names the lowest face whose scale is invalid
-static int coupled_run_scale(padne_ctx *ctx, padne_coupled *cp, const double *theta, double *d_out) {
+int coupled_run_scale(padne_ctx *ctx, padne_coupled *cp, const double *theta, double *d_out) {
     hipStream_t st = ctx->stream;
     if (d_out != nullptr) *d_out = 0.0;
     if (cp->n_tri == 0) return PADNE_OK;

@@ -1,5 +1,6 @@
-// The thermal handle (thermal.hip) as the translation units that work on it see it: thermal.hip itself and the electro-thermal
-// coupling (coupled.hip), which borrows the handle's vertex -> faces lists and its theta.
+// The thermal handle (thermal.hip) as the translation units that work on it see it: thermal.hip itself, the electro-thermal
+// coupling (coupled.hip), which borrows the handle's vertex -> faces lists and its theta, the transient handle
+// (transient.hip), and coupled_transient.hip, which joins the last two.
 #pragma once
 
 #include "error.hpp"
@@ -39,7 +40,48 @@ struct padne_thermal {
     padne_sources *sources = nullptr;        // owned: the heat sources of padne_thermal_set_sources (sources.hip), or null
 };
 
+// The coupling handle (coupled.hip) and the transient handle (transient.hip), as coupled_transient.hip -- which steps the
+// one with the scale of the other -- sees them
+struct padne_coupled {
+    padne_ctx *ctx = nullptr;
+    padne_csr *L = nullptr;                  // borrowed: the electrical system, revalued in place
+    padne_thermal *th = nullptr;             // borrowed: its lists and its theta
+    long long n_vert = 0, n_tri = 0, nnz = 0;
+    int n_mesh = 0;
+    double *L0 = nullptr;                    // [nnz] the assembled values
+    // [n_tri]: the scale of the next revalue, the scale of the last one (what the face kernels use: they belong to the system
+    // that was solved), and the face means of the last update
+    double *s = nullptr, *s_used = nullptr, *prev = nullptr;
+    double *alpha = nullptr;                 // [n_mesh] on the device
+    double ambient = 0.0, t0 = 0.0;
+};
+
+struct padne_transient {
+    padne_ctx *ctx = nullptr;
+    padne_thermal *th = nullptr;             // borrowed: A, M_v, hM, the vertex -> faces lists, the face powers' array
+    long long n_pot = 0, n_vert = 0;
+    int n_mesh = 0;
+    double *Cv = nullptr;                    // [n_vert]
+    padne_csr *S = nullptr;                  // owned: A's pattern (a copy), its own values
+    double dt = 0.0;                         // the dt S holds (compared as bits)
+    bool have_dt = false;
+    double *B = nullptr;                     // [n_case][n_pot]
+    int n_case = 0;
+    double *theta = nullptr;                 // [n_cols][n_pot]
+    double *env = nullptr;                   // [n_cols][n_vert] the largest theta seen ...
+    int *env_step = nullptr;                 // ... and the global step that attained it first
+    int n_cols = 0;
+    bool started = false;
+    long long step = 0;                      // steps since the start
+    double time = 0.0;                       // their dt, added one by one
+    long long hierarchies = 0;               // multigrid setups of S since creation
+};
+
 namespace padne {
+
+// coupled.hip: the scale kernel and its fold on `theta` (device, null: zeros) -- *d_out (may be null) the largest change of a
+// face mean; PADNE_E_INVALID names the lowest face whose scale is invalid
+int coupled_run_scale(padne_ctx *ctx, padne_coupled *cp, const double *theta, double *d_out);
 
 // thermal.hip: padne_thermal_solve_kkt with every face's conductance sigma[m] * scale[t] in the place of sigma[m] (scale
 // [n_tri] on the device; null: sigma[m] alone, the bits of padne_thermal_solve_kkt)

@@ -26,28 +26,7 @@
 #include <cstring>
 #include <vector>
 
-struct padne_transient {
-    padne_ctx *ctx = nullptr;
-    padne_thermal *th = nullptr;             // borrowed: A, M_v, hM, the vertex -> faces lists, the face powers' array
-    long long n_pot = 0, n_vert = 0;
-    int n_mesh = 0;
-    double *Cv = nullptr;                    // [n_vert]
-    padne_csr *S = nullptr;                  // owned: A's pattern (a copy), its own values
-    double dt = 0.0;                         // the dt S holds (compared as bits)
-    bool have_dt = false;
-    double *B = nullptr;                     // [n_case][n_pot]
-    int n_case = 0;
-    double *theta = nullptr;                 // [n_cols][n_pot]
-    double *env = nullptr;                   // [n_cols][n_vert] the largest theta seen ...
-    int *env_step = nullptr;                 // ... and the global step that attained it first
-    int n_cols = 0;
-    bool started = false;
-    long long step = 0;                      // steps since the start
-    double time = 0.0;                       // their dt, added one by one
-    long long hierarchies = 0;               // multigrid setups of S since creation
-};
-
-namespace padne {
+namespace padne {                            // (struct padne_transient: thermal.hpp)
 
 // Cv[v] = c_m(v) * M_v
 __global__ __launch_bounds__(256) void transient_capacity_kernel(const long long n_vert, const int n_mesh,

@@ -2787,8 +2787,8 @@ def solve_meshed_thermal_transient(prob, meshes, mesh_index_to_layer_index, mode
     share the time grid and advance in lockstep as the columns of one block.  ``probes``: node ids (connection nodes or
     internal nodes) whose temperature traces are wanted.  ``keep``: ``"end"`` keeps the field at the end, ``"segments"`` at
     the end of every segment, ``"none"`` none.  Temperatures are theta + ambient.  The coupling is one-way: the
-    resistivity does not follow the temperature (stepping inside the Picard loop of :func:`solve_meshed_electrothermal` is
-    not built).
+    resistivity does not follow the temperature; :func:`solve_meshed_electrothermal_transient` is the call in which it
+    does.
 
     On the device: one electrical block solve of the cases on the load-case path, the thermal operator and the heat load
     of every case from the potentials it holds (the powers never visit the host), then per segment the steps, each with
@@ -3179,6 +3179,342 @@ def solve_electrothermal(prob, model: ElectroThermalModel, mesher_config: Option
     meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
     return solve_meshed_electrothermal(prob, meshes, mesh_index_to_layer_index, model, cases=cases,
                                        per_case_fields=per_case_fields)
+
+
+# --------------------------------------------------------------------------------------------
+# transient electro-thermal: the resistivity follows the temperature over time (DESIGN.md "Transient electro-thermal")
+# --------------------------------------------------------------------------------------------
+
+@dataclass
+class ElectroThermalTransientModel:
+    """What steps the electro-thermal problem through time (see :func:`solve_meshed_electrothermal_transient`).
+
+    - ``electrothermal``: the :class:`ElectroThermalModel`; its ``tolerance`` and ``max_rounds`` govern the loop that finds
+      the initial state.
+    - ``areal_capacity``: as in :class:`TransientModel`.
+    - ``initial``: None = the copper starts at ambient; a case index = from that case's converged electro-thermal steady
+      state.  The tuple form (several scenarios) is refused."""
+    electrothermal: ElectroThermalModel
+    areal_capacity: object
+    initial: object = None
+
+
+@dataclass
+class CheckedElectroThermalTransientModel:
+    """An :class:`ElectroThermalTransientModel` resolved against a Problem (:func:`check_electrothermal_transient_model`)."""
+    electrothermal: CheckedElectroThermalModel
+    capacity: list             # per layer
+    initial: object            # None or an int
+
+
+@dataclass
+class CouplingTrace:
+    """How the coupling went, step by step (see :func:`solve_meshed_electrothermal_transient`).  Arrays over time as
+    :class:`TransientReport` holds them: entry 0 is the start -- zeros and NaN from ambient, the last round of the initial
+    loop otherwise -- and entry n belongs to step n."""
+    increments: np.ndarray     # [K]: the largest change of a face mean since the last electrical solve (NaN in off steps)
+    scale_min: np.ndarray      # the smallest and ...
+    scale_max: np.ndarray      # ... the largest scale the step's electrical solve used (NaN where no electrical solve ran)
+    delivered: np.ndarray      # [W]: what the sources deliver by element_flows of the step's solve (0 in off steps)
+    iterations: list           # per time: {"electrical": iterations of the electrical solve, "thermal": of the thermal one}
+    potentials: dict           # node id -> V over time (NaN where no electrical solve ran)
+    stopped: Optional[tuple]   # None, or (time, T, layer index, mesh index within the layer, vertex index, x, y) of the stop
+
+
+_NO_SCENARIOS = ("the transient electro-thermal solve runs one scenario: several in lockstep are not built, because each "
+                 "needs its own electrical matrix")
+
+
+def check_electrothermal_transient_model(prob, model, filtered_networks=None) -> CheckedElectroThermalTransientModel:
+    """``model`` resolved against ``prob``, or ValueError -- before anything reaches the device -- for everything
+    :func:`check_electrothermal_model` refuses of ``model.electrothermal``, everything :func:`check_transient_model` refuses
+    of the capacity, and an ``initial`` in the tuple form.  ``initial`` is checked against the cases by
+    :func:`solve_meshed_electrothermal_transient`."""
+    if not isinstance(model, ElectroThermalTransientModel):
+        raise ValueError("model must be an ElectroThermalTransientModel")
+    electrothermal = check_electrothermal_model(prob, model.electrothermal, filtered_networks)
+    capacity = check_transient_model(prob, TransientModel(thermal=model.electrothermal.thermal, areal_capacity=model.areal_capacity),
+                                     filtered_networks).capacity
+    if isinstance(model.initial, (tuple, list)):
+        raise ValueError(f"initial: {_NO_SCENARIOS}")
+    return CheckedElectroThermalTransientModel(electrothermal=electrothermal, capacity=capacity, initial=model.initial)
+
+
+def _check_electrothermal_transient_arguments(prob, model, schedule, cases, repeat, probes, voltage_probes, stop_above, keep,
+                                              filtered_networks):
+    """Every check of :func:`solve_meshed_electrothermal_transient`: (checked model, checked cases, per flattened segment (dt,
+    steps, case), the initial case, probes, voltage probes, stop_above as a float or None)."""
+    checked = check_electrothermal_transient_model(prob, model, filtered_networks)
+    checked_cases = [{}] if cases is None else check_load_cases(prob, cases)
+    segments, _n_scen = check_schedule(schedule, len(checked_cases), repeat)
+    if any(isinstance(seg.case, tuple) for seg in segments):
+        raise ValueError(f"the case of a segment: {_NO_SCENARIOS}")
+    initial = _case_entry(checked.initial, len(checked_cases), "initial")
+    _source_powers(checked.electrothermal.thermal.sources, len(checked_cases))
+    if keep not in ("end", "segments", "none"):
+        raise ValueError(f'keep must be "end", "segments" or "none", not {keep!r}')
+    if stop_above is not None:
+        ambient = checked.electrothermal.thermal.ambient
+        try:
+            stop_above = float(stop_above)
+        except (TypeError, ValueError):
+            raise ValueError(f"stop_above must be a temperature, not {stop_above!r}") from None
+        if not math.isfinite(stop_above) or not stop_above > ambient:
+            raise ValueError(f"stop_above must be finite and above the ambient temperature of {ambient!r}, not {stop_above!r}")
+    flat = [(seg.duration / seg.steps, seg.steps, seg.case) for seg in segments]
+    return (checked, checked_cases, flat, initial, check_probes(prob, probes, filtered_networks),
+            check_probes(prob, voltage_probes, filtered_networks), stop_above)
+
+
+def _delivered_power(element_rows, flows) -> float:
+    """What the sources deliver [W]: minus what the rows that are no resistor absorb in ``flows`` (:func:`element_flows`)."""
+    terms = []
+    for row, flow in zip(element_rows, flows):
+        if row[0] != "R":
+            terms += [-flow["power"], -flow.get("input_power", 0.0)]
+    return math.fsum(terms)
+
+
+def solve_meshed_electrothermal_transient(prob, meshes, mesh_index_to_layer_index, model: ElectroThermalTransientModel, schedule,
+                                          *, cases=None, repeat=1, probes=(), voltage_probes=(), stop_above=None, keep="end",
+                                          filtered_networks=None, disconnected_meshes_by_layer=None, partition=None,
+                                          timings: Optional[dict] = None):
+    """:func:`solve_meshed_thermal_transient` with the loop closed: the sheet conductance of every face follows its
+    temperature while the copper heats and cools.  ``([Solution or None] per case, TransientReport, CouplingTrace)``.
+
+    The scheme (DESIGN.md "Transient electro-thermal") is semi-implicit backward Euler, one scenario.  The step from t_n
+    while case j is on:
+
+        s_f = 1 / (1 + alpha_m (Tbar_f(theta_n) - T0)),   d = max_f |thetabar_f - the thetabar_f of the last electrical solve|
+        L = L0 + sum_f (s_f - 1) sigma_m K_f                   the electrical system revalued on the device
+        V of case j on that L, on a fresh plan                 as a round of :func:`solve_meshed_electrothermal`
+        b = the face powers with sigma_m s_f, a third to each corner, the resistors' halves, the heat sources of case j
+        (A + C/dt) theta_n+1 = (C/dt) theta_n + b              the step of :func:`solve_meshed_thermal_transient`
+
+    With the sources off only the last line runs, without b.  The resistivity is that of the start of the step: the
+    nonlinear term lags by one step, which is first order like backward Euler itself and, on a uniformly heated
+    current-driven strip, stable exactly where a steady state exists.  Every step balances (stored_n+1 - stored_n) / dt +
+    loss_n+1 against the heat of its own electrical solve, which ``TransientReport.total_heat`` and the layers' ``heat``
+    now hold step by step; that heat is the power the sources deliver (``CouplingTrace.delivered``) plus the heat sources'.
+    Nothing iterates within a step, and lumped resistors keep their resistance.
+
+    ``model.initial`` None starts at ambient; a case index starts from that case's steady state, found on the same handles
+    by the Picard loop of :func:`solve_meshed_electrothermal` (``tolerance``, ``max_rounds`` and :func:`picard_verdict` of
+    ``model.electrothermal`` apply; :class:`ThermalRunawayError` and the warning on non-convergence as there).  The
+    stepping itself never raises ThermalRunawayError: a neck without a steady state just gets hotter, and ``stop_above`` -- a
+    finite temperature above ambient -- ends the run after the first step whose hotspot over all meshes is strictly
+    greater: every array ends with that step and ``CouplingTrace.stopped`` names it (the fusing-time question).
+    ``voltage_probes``: node ids whose potentials are wanted over time.  ``solutions[j]`` is the Solution of the last step
+    that ran case j, None for a case that never ran.  ``cases``, ``schedule``, ``repeat``, ``probes`` and ``keep`` as in
+    :func:`solve_meshed_thermal_transient`; ``info["iterations_per_step"]`` counts the thermal solves.
+
+    ValueError, before anything reaches the device, for an invalid model (:func:`check_electrothermal_transient_model`),
+    invalid cases, schedule or probes, the tuple forms of ``Segment.case`` and ``initial``, an unknown ``keep``, a
+    ``stop_above`` that is not finite or not above ambient, and a ``partition`` over several GPUs; for a face whose
+    1 + alpha (T - T0) is not finite and positive, found on the device.  A SolverWarning when a step's electrical or thermal
+    solve ends above the tolerance.  ``timings`` (a dict) receives the host time of each stage and under "steps" one dict
+    of laps per step: scale, revalue, stage1 and stage2 (the electrical plan and solve), load, thermal_step."""
+    _refuse_partition(partition, "transient electro-thermal solves")
+    checked, checked_cases, flat, initial, probe_nodes, vprobe_nodes, stop_above = _check_electrothermal_transient_arguments(
+        prob, model, schedule, cases, repeat, probes, voltage_probes, stop_above, keep, filtered_networks)
+    electro = checked.electrothermal
+    thermal_model = electro.thermal
+    laps, ambient, k, n_layers = _Laps(timings), thermal_model.ambient, len(checked_cases), len(prob.layers)
+    substituted = [substitute_load_case(prob, case) for case in checked_cases]
+    source_power = _source_powers(thermal_model.sources, k)
+    board = index_board(prob, meshes, mesh_index_to_layer_index, filtered_networks, disconnected_meshes_by_layer)
+    _refuse_bare_vertices(board)
+    n_vert = len(board.vindex)
+    if n_vert == 0 or not int(board.tri_offsets[-1]):
+        raise ValueError("the thermal model needs connected copper: the board has no connected mesh with faces")
+    pairs = global_elements(board.filtered_networks, board.node_indexer)
+    element_rows = [row for _, row in pairs]
+    laps.lap("indexing")
+    layer_of, n_mesh = board.layer_of, len(board.meshes)
+    one_round = all(a == 0.0 for a in electro.alpha)
+    steps_log = []
+    if laps.timings is not None:
+        laps.timings["steps"] = steps_log
+    nan = float("nan")
+    last_step_of = {}                                        # case -> the last step of the schedule that runs it
+    for n, case in enumerate(j for _dt, steps, j in flat for _ in range(steps)):
+        if case is not None:
+            last_step_of[case] = n + 1
+    with board.assembled() as (L, _):
+        laps.lap("assembly")
+        resistors = [(element, row) for element, row in pairs if row[0] == "R"]
+        n_tri = len(L.tri)
+        thermal = _thermal_handle(L, L.layout.n_potential, thermal_model, layer_of, n_mesh, resistors)
+        coupled = transient = None
+        try:
+            coupled = _hip.Coupled(L.dev, thermal, [electro.alpha[layer_of[i]] for i in range(n_mesh)], ambient,
+                                   electro.conductance_temperature)
+            sources = _attach_heat_sources(thermal, prob, thermal_model, layer_of, n_mesh)
+            transient = _hip.Transient(thermal, [checked.capacity[layer_of[i]] for i in range(n_mesh)])
+            transient.reserve_loads(k)
+            laps.lap("thermal_setup")
+            stamps = [stamp_load_cases(board.filtered_networks, board.node_indexer, L.shape[0], [case]) for case in checked_cases]
+            probe_idx = [board.node_indexer.node_to_global_index[node] for node in probe_nodes]
+            vprobe_idx = [board.node_indexer.node_to_global_index[node] for node in vprobe_nodes]
+
+            def electrical(j, step_laps, want_power):
+                """Parts 2 to 4 of a step for case ``j`` on the scale the coupling holds: what the step keeps of them."""
+                rows, cols, vals = stamps[j]
+                _drop_plans(L)
+                coupled.revalue()
+                step_laps.lap("revalue")
+                plan, V, residual_norms, res, _n_tri, _n_mesh = _solve_block_on_device(L, rows, cols, vals, 1, 1, step_laps)
+                local, Vu = _gather_element_rows(element_rows, V, _ROW_UNKNOWNS)
+                case_rows = _case_element_rows(pairs, local, checked_cases[j])
+                flows = element_flows(case_rows, Vu[:, 0])
+                heat = thermal_heat_triples(pairs, [flows]) if thermal_model.element_heat else None
+                if sources is not None:                      # not scaled by the resistivity
+                    thermal.source_power(source_power[j:j + 1])
+                mesh_heat = coupled.transient_load(transient, plan, j, heat)
+                step_laps.lap("load")
+                _warn_if_block_stalled(res, residual_norms, cols, vals, 1)
+                layer_heat = [math.fsum(float(mesh_heat[i]) for i in range(n_mesh) if layer_of[i] == layer_i)
+                              for layer_i in range(n_layers)]
+                total = math.fsum(layer_heat + [math.fsum(heat[2].tolist()) if heat is not None else 0.0])
+                if sources is not None:
+                    total = total + math.fsum(source_power[j].tolist())
+                return types.SimpleNamespace(
+                    case=j, V=np.ascontiguousarray(V[:, 0]), residual_norm=residual_norms[0], res=res,
+                    power=coupled.power_density(plan, n_tri) if want_power else None, layer_heat=layer_heat, total_heat=total,
+                    delivered=_delivered_power(case_rows, flows), scale_range=coupled.scale_range(),
+                    potentials=[float(V[i, 0]) for i in vprobe_idx])
+
+            # the start: ambient, or the steady electro-thermal state of a case by the Picard loop on these handles
+            start, start_increment, start_iterations, first = None, 0.0, {"electrical": 0, "thermal": 0}, None
+            if initial is None:
+                first = transient.start([None], rtol=RTOL, max_iter=MAX_ITER)
+            else:
+                increments, verdict = [], None
+                for _round in range(1, electro.max_rounds + 1):
+                    start = electrical(initial, _Laps(None), stop_above is not None or initial not in last_step_of)
+                    first = transient.start([initial], rtol=RTOL, max_iter=MAX_ITER)
+                    increments.append(coupled.update_transient(transient, 0))
+                    start_iterations = {"electrical": start_iterations["electrical"] + int(start.res.iterations),
+                                        "thermal": start_iterations["thermal"] + int(first.iterations)}
+                    verdict = "converged" if one_round else picard_verdict(increments, electro.tolerance)
+                    if verdict is not None:
+                        break
+                if verdict == "runaway":
+                    mesh_max = transient.report()[0]
+                    hottest = prob.layers[layer_of[int(np.argmax(mesh_max[0]))]].name
+                    raise ThermalRunawayError(
+                        f"The initial state of load case {initial}: thermal runaway -- the largest change of a face temperature "
+                        f"grew in rounds {len(increments) - 3} to {len(increments)}: "
+                        f"{', '.join(f'{d:.6g} K' for d in increments[-4:])}; the hottest layer is {hottest!r} at "
+                        f"{float(mesh_max[0].max()) + ambient:.6g}.  A current-driven conductor whose heating outgrows its "
+                        "cooling has no steady state")
+                if verdict != "converged":
+                    warnings.warn(f"The initial state of load case {initial}: the electro-thermal loop did not converge in "
+                                  f"{electro.max_rounds} round(s): the last change of a face temperature was "
+                                  f"{increments[-1]:.3e} K, above the tolerance of {electro.tolerance:.3e} K", SolverWarning)
+                start_increment = increments[-1]
+            laps.lap("transient_start")
+            top0, vert0, stored0, loss0 = transient.report()
+            theta0 = transient.state() if probe_idx else None
+            worst = first.rel_residual if first.status != _hip.OK else 0.0
+            runs, snapshots, stepped, last_of_case, stopped_at = [], [], [], {}, None
+            if start is not None:
+                last_of_case[initial] = start
+            t, times = 0.0, [0.0]
+            for at, (dt, steps, case) in enumerate(flat):
+                for _ in range(steps):
+                    lap = {}
+                    step_laps = _Laps(lap)
+                    el, d = None, nan
+                    if case is not None:
+                        d = coupled.update_transient(transient, 0)
+                        step_laps.lap("scale")
+                        el = electrical(case, step_laps, stop_above is not None or last_step_of[case] == len(times))
+                        last_of_case[case] = el
+                        step_laps.lap()
+                    out = transient.run(dt, 1, [case], probe_idx, rtol=RTOL, max_iter=MAX_ITER)
+                    step_laps.lap("thermal_step")
+                    steps_log.append(dict(lap, step=len(times), case=case))
+                    runs.append(out)
+                    stepped.append((el, d))
+                    if out["result"].status != _hip.OK:
+                        worst = max(worst, float(out["result"].rel_residual))
+                    t = t + dt
+                    times.append(t)
+                    if stop_above is not None and any(out["vertex"][0, 0, i] >= 0 and out["max"][0, 0, i] + ambient > stop_above
+                                                      for i in range(n_mesh)):
+                        stopped_at = len(times) - 1
+                        break
+                if keep == "segments" or (keep == "end" and (at == len(flat) - 1 or stopped_at is not None)):
+                    snapshots.append((t, transient.state()[0]))
+                if stopped_at is not None:
+                    break
+            env, env_step = transient.envelope(n_vert)
+            _steps, _time, hierarchies = transient.clock()
+            laps.lap("transient_run")
+        finally:
+            if transient is not None:
+                transient.close()
+            if coupled is not None:
+                _drop_plans(L)
+                coupled.close()
+            thermal.close()
+    laps.lap()
+    if worst > max(RTOL, STALL_WARN_ABOVE):
+        warnings.warn(f"A step of the transient thermal solve stopped at a relative residual of {worst:.3e}", SolverWarning)
+    solutions = []
+    for j in range(k):
+        el = last_of_case.get(j)
+        solutions.append(None if el is None else _column_solution(board, substituted[j][0], el.V, el.residual_norm, el.res, el.power,
+                                                                  f"Load case {j}: " if k > 1 else ""))
+    join = lambda key, head: np.concatenate([head[None]] + [out[key] for out in runs])[:, 0]      # (n_steps + 1, n_mesh)
+    mesh_max, mesh_vert, stored, loss = join("max", top0), join("vertex", vert0), join("stored", stored0), join("loss", loss0)
+    iterations = np.concatenate([out["iterations"] for out in runs])
+    info = {"iterations": int(first.iterations) + int(iterations.sum()), "iterations_per_step": iterations,
+            "seconds_per_step": np.concatenate([out["seconds"] for out in runs]),
+            "setup_seconds_per_step": np.concatenate([out["setup_seconds"] for out in runs]),
+            "rel_residual": max([float(first.rel_residual)] + [float(out["result"].rel_residual) for out in runs]),
+            "hierarchies": int(hierarchies), "seconds": float(first.seconds) + sum(float(out["result"].seconds) for out in runs)}
+    led = [start] + [el for el, _d in stepped]             # the electrical solve that led to every time, None without
+    layer_heat = [[0.0 if el is None else el.layer_heat[layer_i] for el in led] for layer_i in range(n_layers)]
+    total_heat = [0.0 if el is None else el.total_heat for el in led]
+    traces = {}
+    for p, node in enumerate(probe_nodes):
+        traces[node] = np.concatenate([[theta0[0, probe_idx[p]]]] + [out["probes"][:, 0, p] for out in runs])
+    report = _transient_report(board, ambient, times, mesh_max, mesh_vert, stored, loss, layer_heat, total_heat, traces, env[0],
+                               env_step[0], snapshots, info)
+    stopped = None
+    if stopped_at is not None:
+        spots = [(report.hotspots[layer_i][-1], layer_i) for layer_i in range(n_layers) if report.hotspots[layer_i][-1] is not None]
+        spot, layer_i = max(spots, key=lambda entry: (entry[0][0], -entry[1]))      # the lowest layer of the largest temperature
+        stopped = (float(times[-1]), spot[0], layer_i, *spot[1:])
+    thermal_its = [int(first.iterations)] + [int(i) for i in iterations]
+    trace = CouplingTrace(
+        increments=np.array([start_increment] + [d for _el, d in stepped], dtype=DTYPE),
+        scale_min=np.array([nan if el is None else el.scale_range[0] for el in led], dtype=DTYPE),
+        scale_max=np.array([nan if el is None else el.scale_range[1] for el in led], dtype=DTYPE),
+        delivered=np.array([0.0 if el is None else el.delivered for el in led], dtype=DTYPE),
+        iterations=[dict(start_iterations) if n == 0 and start is not None else
+                    {"electrical": 0 if el is None else int(el.res.iterations), "thermal": thermal_its[n]}
+                    for n, el in enumerate(led)],
+        potentials={node: np.array([nan if el is None else el.potentials[p] for el in led], dtype=DTYPE)
+                    for p, node in enumerate(vprobe_nodes)},
+        stopped=stopped)
+    laps.lap("solutions")
+    return solutions, report, trace
+
+
+def solve_electrothermal_transient(prob, model: ElectroThermalTransientModel, schedule,
+                                   mesher_config: Optional[mesh.Mesher.Config] = None, *, mesher=None, cases=None, repeat=1,
+                                   probes=(), voltage_probes=(), stop_above=None, keep="end", partition=None):
+    """``solve`` with the copper's temperatures over a schedule and the conductances that follow them (see
+    :func:`solve_meshed_electrothermal_transient`): the board is meshed once."""
+    _refuse_partition(partition, "transient electro-thermal solves")
+    _check_electrothermal_transient_arguments(prob, model, schedule, cases, repeat, probes, voltage_probes, stop_above, keep, None)
+    meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
+    return solve_meshed_electrothermal_transient(prob, meshes, mesh_index_to_layer_index, model, schedule, cases=cases,
+                                                 repeat=repeat, probes=probes, voltage_probes=voltage_probes,
+                                                 stop_above=stop_above, keep=keep)
 
 
 # --------------------------------------------------------------------------------------------
