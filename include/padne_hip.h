@@ -828,6 +828,42 @@ int padne_transient_envelope(padne_ctx *ctx, const padne_transient *tr, double *
 /* steps and time since the start, multigrid hierarchies built for S since creation (each may be null) */
 int padne_transient_clock(const padne_transient *tr, int64_t *step_out, double *time_out, int64_t *hierarchies_out);
 
+/* ---- adaptive transient: second-order steps with an error estimate ----------------------------------
+ * No reference counterpart ("Adaptive transient").  Alexander's two-stage SDIRK2 on the transient handle, from
+ * two backward-Euler solves on one matrix.  gamma = 1 - 1/sqrt(2) = 0.29289321881345247560 and q = (1 - gamma) / gamma =
+ * sqrt(2) + 1 = 2.41421356237309504880, both as the nearest double.  One step of length dt from theta_n, for column c running
+ * case j, every expression rounded as written:
+ *     dts = gamma * dt
+ *     stage 1:  S(dts) theta_1 = rhs(dts, theta_n, B[j])        exactly one step of padne_transient_run of length dts
+ *     theta*[v] = theta_n[v] + q * (theta_1[v] - theta_n[v])   at a vertex; theta_1 at an internal node
+ *     stage 2:  S(dts) theta_{n+1} = rhs(dts, theta*, B[j])     the same step with theta* in the place of theta_n
+ *     est[v] = q * ((theta_1[v] - theta_n[v]) - (theta_{n+1}[v] - theta*[v]))   at a vertex
+ *     err[c] = max_v |est[c][v]| [K]; an |est| that is not finite counts as +infinity
+ * The caller decides what to do with err: padne_transient_accept, or another trial with another dt. */
+/* The two stages into the handle's trial arrays; state, clock, envelope and load table are untouched.  err_out[n_cols] and
+ * err_vertex_out[n_cols]: the estimate and the global vertex that attains it, the lowest on a tie (0.0 and -1 without
+ * vertices), by the fixed order of padne_thermal_report's maxima per mesh and then over the meshes in ascending order,
+ * replaced only on strictly greater: two calls give the same bits.  guess: what stage 2's solve starts from -- 0 theta_1,
+ * 1 theta*, 2 theta_n + (theta_1 - theta_n) / gamma (internal nodes: theta_1); the result depends on it within the solve's
+ * tolerance only.  Stage 1 starts from theta_n.  opts and info as in padne_transient_run, info summed over the stages;
+ * stage_iterations_out[2] and stage_setup_seconds_out[2] (each may be null) per stage.  PADNE_E_NOTCONVERGED keeps the trial
+ * and is reported.  PADNE_E_INVALID for what padne_transient_run refuses, a dt whose gamma * dt is not positive and a guess
+ * out of range.  A live trial ends with the next padne_transient_try_step, padne_transient_start, padne_transient_run,
+ * padne_transient_loads, padne_transient_loads_kkt and padne_transient_reserve_loads. */
+int padne_transient_try_step(padne_ctx *ctx, padne_transient *tr, double dt, const int32_t *case_of_col, int32_t guess,
+                             const padne_solve_opts *opts, double *err_out, int64_t *err_vertex_out,
+                             int32_t *stage_iterations_out, double *stage_setup_seconds_out, padne_solve_info *info);
+/* The live trial becomes the state (the arrays change places, nothing is copied): the step counter advances by one, the time
+ * by the trial's dt, the envelope by the rule of padne_transient_run.  mesh_*_out[n_cols][n_mesh] and probe_out[n_cols][n_probe]
+ * as one step of padne_transient_run writes them for theta_{n+1}; mesh_stage_loss_out[n_cols][n_mesh] the film loss of
+ * theta_1 in the same fixed order.  With them (stored_{n+1} - stored_n) / dt + (1 - gamma) stage_loss + gamma loss_{n+1} =
+ * the heat of the case, up to the solves' tolerance.  PADNE_E_INVALID without a live trial, and for a probe out of range. */
+int padne_transient_accept(padne_ctx *ctx, padne_transient *tr, int32_t n_probe, const int64_t *probe_idx, double *mesh_max_out,
+                           int64_t *mesh_vertex_out, double *mesh_stored_out, double *mesh_loss_out, double *mesh_stage_loss_out,
+                           double *probe_out);
+/* out[n_cols][n_potential] = theta_1 (which 0), theta* (1) or theta_{n+1} (2) of the live trial, for tests */
+int padne_transient_trial(padne_ctx *ctx, const padne_transient *tr, int32_t which, double *out);
+
 /* ---- transient electro-thermal: the resistivity follows the temperature over time ------------------
  * No reference counterpart ("Transient electro-thermal").  A coupling handle and a transient handle made on one
  * thermal handle, joined: a step from t_n while case j is on is padne_coupled_update_transient (the scale from theta_n),

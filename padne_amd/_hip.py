@@ -183,6 +183,10 @@ SIGNATURES = {
     "padne_transient_state": (C.c_int, [_P, _P, _PF64]),
     "padne_transient_envelope": (C.c_int, [_P, _P, _PF64, _PI32]),
     "padne_transient_clock": (C.c_int, [_P, C.POINTER(_I64), C.POINTER(C.c_double), C.POINTER(_I64)]),
+    "padne_transient_try_step": (C.c_int, [_P, _P, C.c_double, _PI32, C.c_int32, C.POINTER(SolveOpts), _PF64, _PI64, _PI32, _PF64,
+                                           C.POINTER(SolveInfo)]),
+    "padne_transient_accept": (C.c_int, [_P, _P, C.c_int32, _PI64, _PF64, _PI64, _PF64, _PF64, _PF64, _PF64]),
+    "padne_transient_trial": (C.c_int, [_P, _P, C.c_int32, _PF64]),
     "padne_coupled_create": (C.c_int, [_P, _P, _P, C.c_int32, _PF64, C.c_double, C.c_double, C.POINTER(_P)]),
     "padne_coupled_destroy": (C.c_int, [_P]),
     "padne_coupled_reset": (C.c_int, [_P, _P]),
@@ -1293,6 +1297,11 @@ class Thermal:
         return mean, mesh_max, vert, heat, loss, env, env_case
 
 
+SDIRK_GAMMA = 0.29289321881345247560        # 1 - 1/sqrt(2), the library's kSdirkGamma
+SDIRK_Q = 2.41421356237309504880            # sqrt(2) + 1 = (1 - gamma) / gamma, the library's kSdirkQ
+SDIRK_GUESS = 2                             # what stage 2 starts from by default (DESIGN.md "Adaptive transient")
+
+
 class Transient:
     """``padne_transient``: backward-Euler steps of C dtheta/dt + A theta = b(t) on a :class:`Thermal` handle
     (include/padne_hip.h, "transient").  ``capacity`` per mesh [J / (K mesh-unit^2)].  Holds the lumped capacities, the
@@ -1443,6 +1452,48 @@ class Transient:
         step, hier, t = _I64(), _I64(), C.c_double()
         _check(self.ctx._lib.padne_transient_clock(self._h, C.byref(step), C.byref(t), C.byref(hier)))
         return int(step.value), float(t.value), int(hier.value)
+
+    def try_step(self, dt: float, case_of_col, *, guess=None, rtol=1e-12, max_iter=200000, precond="amg") -> dict:
+        """One SDIRK2 trial step of length ``dt`` under ``case_of_col`` (include/padne_hip.h, "adaptive transient"); the state
+        does not advance.  ``err`` (n_cols,) [K] with ``vertex`` (n_cols,), ``stage_iterations`` (2,), ``stage_setup_seconds``
+        (2,) and ``result`` the SolveResult over both stages.  ``guess``: what stage 2's solve starts from (0 theta_1,
+        1 theta*, 2 the line through theta_n and theta_1 at the end of the step; None: ``SDIRK_GUESS``)."""
+        guess = SDIRK_GUESS if guess is None else guess
+        cases = self._cases(case_of_col)
+        if cases.shape[0] != self.n_cols:
+            raise ValueError("one case per column of the start")
+        err, vert = np.empty(self.n_cols, dtype=np.float64), np.empty(self.n_cols, dtype=np.int64)
+        its, setup = np.zeros(2, dtype=np.int32), np.zeros(2, dtype=np.float64)
+        opts = CsrMatrix._opts(rtol, 0.0, max_iter, 0, True, precond=precond)
+        info = SolveInfo()
+        rc = self.ctx._lib.padne_transient_try_step(self.ctx._h, self._h, float(dt), _ptr(cases, _PI32), int(guess), C.byref(opts),
+                                                    _ptr(err, _PF64), _ptr(vert, _PI64), _ptr(its, _PI32), _ptr(setup, _PF64),
+                                                    C.byref(info))
+        if rc != OK and rc != E_NOTCONVERGED:
+            _check(rc)
+        res = SolveResult(None, info.iterations, info.restarts, info.rel_residual, info.abs_residual, info.solve_seconds,
+                          info.status, info.spmv_seconds, info.precond_setup_seconds, info.operator_complexity, info.levels,
+                          info.precond_fallbacks)
+        return {"err": err, "vertex": vert, "stage_iterations": its, "stage_setup_seconds": setup, "result": res}
+
+    def accept(self, probes=()) -> dict:
+        """The live trial becomes the state.  ``max``, ``vertex``, ``stored``, ``loss`` (n_cols, n_mesh) of the new state as
+        ``run`` reports a step, ``stage_loss`` (n_cols, n_mesh) the film loss of theta_1, ``probes`` (n_cols, n_probe)."""
+        probe = _i64(probes).reshape(-1)
+        shape = (self.n_cols, self.n_mesh)
+        top, stored, loss, stage = (np.empty(shape, dtype=np.float64) for _ in range(4))
+        vert = np.empty(shape, dtype=np.int64)
+        trace = np.empty((self.n_cols, probe.shape[0]), dtype=np.float64)
+        _check(self.ctx._lib.padne_transient_accept(self.ctx._h, self._h, probe.shape[0], _ptr(probe, _PI64), _ptr(top, _PF64),
+                                                    _ptr(vert, _PI64), _ptr(stored, _PF64), _ptr(loss, _PF64), _ptr(stage, _PF64),
+                                                    _ptr(trace, _PF64)))
+        return {"max": top, "vertex": vert, "stored": stored, "loss": loss, "stage_loss": stage, "probes": trace}
+
+    def trial(self, which: int) -> np.ndarray:
+        """theta_1 (0), theta* (1) or theta_{n+1} (2) of the live trial, (n_cols, n_potential)."""
+        out = np.empty((self.n_cols, self.n_potential), dtype=np.float64)
+        _check(self.ctx._lib.padne_transient_trial(self.ctx._h, self._h, int(which), _ptr(out, _PF64)))
+        return out
 
 
 class Coupled:

@@ -138,6 +138,7 @@ extern "C" int padne_transient_reserve_loads(padne_ctx *ctx, padne_transient *tr
     tr->B = B;
     tr->n_case = n_case;
     tr->started = false;                                // a running schedule names cases of the old table
+    tr->trial_live = false;
     return PADNE_OK;
 }
 

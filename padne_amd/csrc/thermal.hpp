@@ -1,6 +1,7 @@
 // The thermal handle (thermal.hip) as the translation units that work on it see it: thermal.hip itself, the electro-thermal
 // coupling (coupled.hip), which borrows the handle's vertex -> faces lists and its theta, the transient handle
-// (transient.hip), and coupled_transient.hip, which joins the last two.
+// (transient.hip), coupled_transient.hip, which joins the last two, and sdirk.hip, which steps the transient handle by
+// error-controlled second-order steps.
 #pragma once
 
 #include "error.hpp"
@@ -75,6 +76,11 @@ struct padne_transient {
     long long step = 0;                      // steps since the start
     double time = 0.0;                       // their dt, added one by one
     long long hierarchies = 0;               // multigrid setups of S since creation
+    // sdirk.hip: the trial step theta_1, theta*, theta_{n+1}, each [n_cols][n_pot] (made by the first trial, dropped with
+    // theta when the number of columns changes); live between padne_transient_try_step and whatever ends it
+    double *trial[3] = {nullptr, nullptr, nullptr};
+    double trial_dt = 0.0;
+    bool trial_live = false;
 };
 
 namespace padne {
@@ -108,6 +114,30 @@ std::vector<long long> thermal_tiles(const std::vector<int64_t> &off);
 // queued behind the face gather and the triples; PADNE_E_INVALID without powers for exactly n_cols columns.  Nothing
 // without sources
 int sources_add_load(padne_ctx *ctx, padne_thermal *th, int32_t n_cols, double *d_b);
+
+// transient.hip, for sdirk.hip.  transient_require: the handle is the context's.  transient_set_dt: S revalued for dt when
+// its bits differ from the held ones.  transient_check_cases: case_of_col[n_cols] checked and copied.  transient_opts: the
+// defaults of padne_transient_run for null options.  transient_upload_cases: the table on the device, complete on return.
+// transient_rhs: the kernel of the step's right-hand side on `theta` [n_cols][n_pot].  TransientPass / transient_pass_init /
+// transient_pass: the report kernel and its fold on `theta`, the per-mesh results at out_*[n_cols][n_mesh] on the device;
+// the envelope is touched as env_mode says, with `step` as the step that attains
+struct TransientPass {
+    long long n_vb = 0;
+    long long *d_vtile = nullptr, *d_tvert = nullptr;
+    double *d_tstored = nullptr, *d_tloss = nullptr, *d_tmax = nullptr;
+};
+int transient_require(const char *entry, padne_ctx *ctx, const padne_transient *tr);
+bool transient_good_dt(double dt);
+int transient_set_dt(padne_transient *tr, double dt);
+int transient_check_cases(const padne_transient *tr, const int32_t *case_of_col, int n_cols, std::vector<int> *out);
+padne_solve_opts transient_opts(const padne_solve_opts *opts);
+int transient_upload_cases(padne_transient *tr, Scratch &sc, const std::vector<int> &cases, int **d_case);
+int transient_rhs(padne_transient *tr, const int *d_case, double dt, int mode, const double *theta, double *d_rhs);
+int transient_pass_init(padne_transient *tr, Scratch &sc, TransientPass *ps);
+int transient_pass(padne_transient *tr, const TransientPass &ps, const double *theta, int env_mode, long long step,
+                   double *out_stored, double *out_loss, double *out_max, long long *out_vert);
+// out[c][p] = theta[c][probe[p]] on the device, queued on the stream
+int transient_probe(padne_transient *tr, int n_probe, const long long *d_probe, const double *theta, double *d_out);
 
 // What a matrix derived from its values (1 / diagonal, single-precision copies, multigrid hierarchy) is dropped and rebuilt
 // on next use from the values in place; the x-window plan depends on the pattern only and stays

@@ -182,21 +182,22 @@ static void transient_free(padne_transient *tr) {
     padne_ctx *ctx = tr->ctx;
     if (ctx != nullptr && ctx->stream != nullptr) (void)hipStreamSynchronize(ctx->stream);
     if (tr->S != nullptr) padne_csr_destroy(tr->S);
-    for (void *p : {(void *)tr->Cv, (void *)tr->B, (void *)tr->theta, (void *)tr->env, (void *)tr->env_step})
+    for (void *p : {(void *)tr->Cv, (void *)tr->B, (void *)tr->theta, (void *)tr->env, (void *)tr->env_step, (void *)tr->trial[0],
+                    (void *)tr->trial[1], (void *)tr->trial[2]})
         if (p != nullptr) pool_free(ctx, p);
     delete tr;
 }
 
-static int transient_require(const char *entry, padne_ctx *ctx, const padne_transient *tr) {
+int transient_require(const char *entry, padne_ctx *ctx, const padne_transient *tr) {
     PADNE_REQUIRE(ctx && tr, "null argument");
     PADNE_REQUIRE(tr->ctx == ctx, (std::string(entry) + ": the handle belongs to another context").c_str());
     return PADNE_OK;
 }
 
-static bool transient_good_dt(double dt) { return std::isfinite(dt) && dt > 0.0; }
+bool transient_good_dt(double dt) { return std::isfinite(dt) && dt > 0.0; }
 
 // S holds dt: revalued in place when the bits of dt differ from the held ones, and what was derived from its values dropped
-static int transient_set_dt(padne_transient *tr, double dt) {
+int transient_set_dt(padne_transient *tr, double dt) {
     if (tr->have_dt && std::memcmp(&tr->dt, &dt, sizeof(double)) == 0) return PADNE_OK;
     padne_ctx *ctx = tr->ctx;
     csr_invalidate_values(tr->S);
@@ -213,7 +214,7 @@ static int transient_set_dt(padne_transient *tr, double dt) {
     return PADNE_OK;
 }
 
-static int transient_check_cases(const padne_transient *tr, const int32_t *case_of_col, int n_cols, std::vector<int> *out) {
+int transient_check_cases(const padne_transient *tr, const int32_t *case_of_col, int n_cols, std::vector<int> *out) {
     PADNE_REQUIRE(case_of_col != nullptr, "null argument");
     out->resize((size_t)n_cols);
     for (int c = 0; c < n_cols; ++c) {
@@ -223,7 +224,7 @@ static int transient_check_cases(const padne_transient *tr, const int32_t *case_
     return PADNE_OK;
 }
 
-static padne_solve_opts transient_opts(const padne_solve_opts *opts) {
+padne_solve_opts transient_opts(const padne_solve_opts *opts) {
     padne_solve_opts o;
     if (opts != nullptr) {
         o = *opts;
@@ -238,14 +239,8 @@ static padne_solve_opts transient_opts(const padne_solve_opts *opts) {
     return o;
 }
 
-// the device side of a report pass: tile tables and tile results, made once per call
-struct TransientPass {
-    long long n_vb = 0;
-    long long *d_vtile = nullptr, *d_tvert = nullptr;
-    double *d_tstored = nullptr, *d_tloss = nullptr, *d_tmax = nullptr;
-};
-
-static int transient_pass_init(padne_transient *tr, Scratch &sc, TransientPass *ps) {
+// the device side of a report pass (TransientPass, thermal.hpp): tile tables and tile results, made once per call
+int transient_pass_init(padne_transient *tr, Scratch &sc, TransientPass *ps) {
     padne_ctx *ctx = tr->ctx;
     const std::vector<long long> vtile = thermal_tiles(tr->th->voff);
     ps->n_vb = vtile[(size_t)tr->n_mesh];
@@ -261,17 +256,17 @@ static int transient_pass_init(padne_transient *tr, Scratch &sc, TransientPass *
     return PADNE_OK;
 }
 
-// the report kernel and its fold on the current theta: the per-mesh results at out_*[n_cols][n_mesh] on the device
-static int transient_pass(padne_transient *tr, const TransientPass &ps, int env_mode, double *out_stored, double *out_loss,
-                          double *out_max, long long *out_vert) {
+// the report kernel and its fold on `theta`: the per-mesh results at out_*[n_cols][n_mesh] on the device
+int transient_pass(padne_transient *tr, const TransientPass &ps, const double *theta, int env_mode, long long step,
+                   double *out_stored, double *out_loss, double *out_max, long long *out_vert) {
     padne_ctx *ctx = tr->ctx;
     hipStream_t s = ctx->stream;
     const ErrorMesh M = error_mesh_of(tr->th->L);
     if (ps.n_vb > 0) {
         hipLaunchKernelGGL(transient_report_kernel, dim3((unsigned)ps.n_vb, (unsigned)tr->n_cols), dim3(256), 0, s, tr->n_mesh,
-                           (const long long *)ps.d_vtile, M.voff, tr->n_pot, tr->n_vert, ps.n_vb, (const double *)tr->theta,
+                           (const long long *)ps.d_vtile, M.voff, tr->n_pot, tr->n_vert, ps.n_vb, theta,
                            (const double *)tr->th->hM, (const double *)tr->Cv, ps.d_tstored, ps.d_tloss, ps.d_tmax, ps.d_tvert,
-                           env_mode, (int)tr->step, tr->env, tr->env_step);
+                           env_mode, (int)step, tr->env, tr->env_step);
         PADNE_HIP_CHECK(hipGetLastError());
     }
     hipLaunchKernelGGL(transient_fold_kernel, dim3((unsigned)tr->n_mesh, (unsigned)tr->n_cols), dim3(256), 0, s, tr->n_mesh, ps.n_vb,
@@ -281,16 +276,24 @@ static int transient_pass(padne_transient *tr, const TransientPass &ps, int env_
     return PADNE_OK;
 }
 
-static int transient_rhs(padne_transient *tr, const int *d_case, double dt, int mode, double *d_rhs) {
+int transient_rhs(padne_transient *tr, const int *d_case, double dt, int mode, const double *theta, double *d_rhs) {
     if (tr->n_pot == 0) return PADNE_OK;
     hipLaunchKernelGGL(transient_rhs_kernel, dim3(nblk(tr->n_pot), (unsigned)tr->n_cols), dim3(256), 0, tr->ctx->stream, tr->n_pot,
-                       tr->n_vert, d_case, (const double *)tr->Cv, dt, (const double *)tr->theta, (const double *)tr->B, mode, d_rhs);
+                       tr->n_vert, d_case, (const double *)tr->Cv, dt, theta, (const double *)tr->B, mode, d_rhs);
+    PADNE_HIP_CHECK(hipGetLastError());
+    return PADNE_OK;
+}
+
+int transient_probe(padne_transient *tr, int n_probe, const long long *d_probe, const double *theta, double *d_out) {
+    const long long pcells = (long long)tr->n_cols * n_probe;
+    hipLaunchKernelGGL(transient_probe_kernel, dim3(nblk(pcells)), dim3(256), 0, tr->ctx->stream, tr->n_pot, tr->n_cols, n_probe,
+                       d_probe, theta, d_out);
     PADNE_HIP_CHECK(hipGetLastError());
     return PADNE_OK;
 }
 
 // the per-column case table on the device (the copy is complete when this returns: the host vector may go)
-static int transient_upload_cases(padne_transient *tr, Scratch &sc, const std::vector<int> &cases, int **d_case) {
+int transient_upload_cases(padne_transient *tr, Scratch &sc, const std::vector<int> &cases, int **d_case) {
     PADNE_TRY(sc.alloc(d_case, cases.size()));
     PADNE_HIP_CHECK(hipMemcpyAsync(*d_case, cases.data(), sizeof(int) * cases.size(), hipMemcpyHostToDevice, tr->ctx->stream));
     PADNE_HIP_CHECK(hipStreamSynchronize(tr->ctx->stream));
@@ -303,6 +306,7 @@ static int transient_set_loads(padne_ctx *ctx, padne_transient *tr, int32_t n_ca
     if (tr->B != nullptr) pool_free(ctx, tr->B);
     tr->n_case = 0;
     tr->started = false;                     // a running schedule names cases of the old table
+    tr->trial_live = false;
     tr->B = (double *)pool_alloc(ctx, sizeof(double) * count);
     if (tr->B == nullptr) return PADNE_E_NOMEM;
     PADNE_TRY(thermal_form_load(ctx, tr->th, n_case, n_heat, heat_node, heat_col, heat_val, tr->B));
@@ -414,10 +418,12 @@ extern "C" int padne_transient_start(padne_ctx *ctx, padne_transient *tr, int32_
     hipStream_t s = ctx->stream;
     if (info != nullptr) memset(info, 0, sizeof(*info));
     tr->started = false;
+    tr->trial_live = false;
     if (n_cols != tr->n_cols || tr->theta == nullptr) {
-        for (void *p : {(void *)tr->theta, (void *)tr->env, (void *)tr->env_step})
+        for (void *p : {(void *)tr->theta, (void *)tr->env, (void *)tr->env_step, (void *)tr->trial[0], (void *)tr->trial[1],
+                        (void *)tr->trial[2]})
             if (p != nullptr) pool_free(ctx, p);
-        tr->theta = tr->env = nullptr;
+        tr->theta = tr->env = tr->trial[0] = tr->trial[1] = tr->trial[2] = nullptr;
         tr->env_step = nullptr;
         tr->n_cols = 0;
         const size_t np = (size_t)n_cols * (size_t)(tr->n_pot > 0 ? tr->n_pot : 1), nv = (size_t)n_cols * (size_t)(tr->n_vert > 0 ? tr->n_vert : 1);
@@ -440,7 +446,7 @@ extern "C" int padne_transient_start(padne_ctx *ctx, padne_transient *tr, int32_
         double *d_b = nullptr;
         PADNE_TRY(transient_upload_cases(tr, sc, cases, &d_case));
         PADNE_TRY(sc.alloc(&d_b, count));
-        PADNE_TRY(transient_rhs(tr, d_case, 1.0, 1, d_b));
+        PADNE_TRY(transient_rhs(tr, d_case, 1.0, 1, tr->theta, d_b));
         padne_solve_opts o = transient_opts(opts);
         o.flags &= ~1;
         rc = padne_solve_spd_dev(ctx, tr->th->A, d_b, tr->theta, n_cols, &o, info);
@@ -456,7 +462,7 @@ extern "C" int padne_transient_start(padne_ctx *ctx, padne_transient *tr, int32_
     PADNE_TRY(transient_pass_init(tr, sc, &ps));
     PADNE_TRY(sc.alloc(&d_res, 3 * cells));
     PADNE_TRY(sc.alloc(&d_vert, cells));
-    PADNE_TRY(transient_pass(tr, ps, 1, d_res, d_res + cells, d_res + 2 * cells, d_vert));
+    PADNE_TRY(transient_pass(tr, ps, tr->theta, 1, tr->step, d_res, d_res + cells, d_res + 2 * cells, d_vert));
     PADNE_HIP_CHECK(hipStreamSynchronize(s));
     tr->started = true;
     return rc;
@@ -486,7 +492,7 @@ extern "C" int padne_transient_rhs(padne_ctx *ctx, padne_transient *tr, double d
     double *d_rhs = nullptr;
     PADNE_TRY(transient_upload_cases(tr, sc, cases, &d_case));
     PADNE_TRY(sc.alloc(&d_rhs, count));
-    PADNE_TRY(transient_rhs(tr, d_case, dt, 0, d_rhs));
+    PADNE_TRY(transient_rhs(tr, d_case, dt, 0, tr->theta, d_rhs));
     PADNE_HIP_CHECK(hipMemcpyAsync(rhs_out, d_rhs, sizeof(double) * count, hipMemcpyDeviceToHost, ctx->stream));
     PADNE_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return PADNE_OK;
@@ -509,6 +515,7 @@ extern "C" int padne_transient_run(padne_ctx *ctx, padne_transient *tr, double d
     PADNE_TRY(transient_check_cases(tr, case_of_col, tr->n_cols, &cases));
     PADNE_HIP_CHECK(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
+    tr->trial_live = false;                             // a trial step (sdirk.hip) stood on the state that now advances
     const int n_cols = tr->n_cols;
     const size_t count = (size_t)n_cols * (size_t)tr->n_pot, cells = (size_t)n_cols * (size_t)tr->n_mesh,
                  pcells = (size_t)n_cols * (size_t)n_probe, ns = (size_t)n_steps;
@@ -542,7 +549,7 @@ extern "C" int padne_transient_run(padne_ctx *ctx, padne_transient *tr, double d
         padne_solve_info one;
         memset(&one, 0, sizeof(one));
         if (count > 0) {
-            PADNE_TRY(transient_rhs(tr, d_case, dt, 0, d_rhs));
+            PADNE_TRY(transient_rhs(tr, d_case, dt, 0, tr->theta, d_rhs));
             const bool fresh = tr->S->amg == nullptr;
             const int rc = padne_solve_spd_dev(ctx, tr->S, d_rhs, tr->theta, n_cols, &o, &one);
             if (rc != PADNE_OK && rc != PADNE_E_NOTCONVERGED) return rc;
@@ -551,13 +558,9 @@ extern "C" int padne_transient_run(padne_ctx *ctx, padne_transient *tr, double d
         }
         tr->step += 1;
         tr->time += dt;
-        PADNE_TRY(transient_pass(tr, ps, 2, d_stored + (size_t)k * cells, d_loss + (size_t)k * cells, d_max + (size_t)k * cells,
+        PADNE_TRY(transient_pass(tr, ps, tr->theta, 2, tr->step, d_stored + (size_t)k * cells, d_loss + (size_t)k * cells, d_max + (size_t)k * cells,
                                  d_vert + (size_t)k * cells));
-        if (n_probe > 0 && count > 0) {
-            hipLaunchKernelGGL(transient_probe_kernel, dim3(nblk((long long)pcells)), dim3(256), 0, s, tr->n_pot, n_cols, (int)n_probe,
-                               (const long long *)d_probe, (const double *)tr->theta, d_pout + (size_t)k * pcells);
-            PADNE_HIP_CHECK(hipGetLastError());
-        }
+        if (n_probe > 0 && count > 0) PADNE_TRY(transient_probe(tr, (int)n_probe, d_probe, tr->theta, d_pout + (size_t)k * pcells));
         total.iterations += one.iterations;
         total.restarts += one.restarts;
         if (one.rel_residual > total.rel_residual) total.rel_residual = one.rel_residual;
@@ -600,7 +603,7 @@ extern "C" int padne_transient_report(padne_ctx *ctx, padne_transient *tr, doubl
     PADNE_TRY(transient_pass_init(tr, sc, &ps));
     PADNE_TRY(sc.alloc(&d_res, 3 * cells));
     PADNE_TRY(sc.alloc(&d_vert, cells));
-    PADNE_TRY(transient_pass(tr, ps, 0, d_res, d_res + cells, d_res + 2 * cells, d_vert));
+    PADNE_TRY(transient_pass(tr, ps, tr->theta, 0, tr->step, d_res, d_res + cells, d_res + 2 * cells, d_vert));
     PADNE_HIP_CHECK(hipMemcpyAsync(mesh_stored_out, d_res, sizeof(double) * cells, hipMemcpyDeviceToHost, s));
     PADNE_HIP_CHECK(hipMemcpyAsync(mesh_loss_out, d_res + cells, sizeof(double) * cells, hipMemcpyDeviceToHost, s));
     PADNE_HIP_CHECK(hipMemcpyAsync(mesh_max_out, d_res + 2 * cells, sizeof(double) * cells, hipMemcpyDeviceToHost, s));

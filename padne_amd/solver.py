@@ -2884,6 +2884,303 @@ def solve_thermal_transient(prob, model: TransientModel, schedule, mesher_config
 
 
 # --------------------------------------------------------------------------------------------
+# adaptive transient: second-order steps whose size follows an error estimate (DESIGN.md "Adaptive transient")
+# --------------------------------------------------------------------------------------------
+
+SDIRK_GAMMA = _hip.SDIRK_GAMMA          # 1 - 1/sqrt(2)
+DEFAULT_FIRST_LEVEL = 10                # the first step of a span is duration / 2^10 ...
+DEFAULT_MAX_LEVEL = 30                  # ... and no step is shorter than duration / 2^30
+
+
+@dataclass
+class Span:
+    """A stretch of a schedule with one load, covered by as many steps as the tolerance asks for (see
+    :func:`solve_meshed_thermal_transient_adaptive`).
+
+    - ``duration``: seconds, finite and positive.
+    - ``case``: as in :class:`Segment`."""
+    duration: float
+    case: object = None
+
+
+def check_spans(schedule, n_cases: int, repeat=1) -> tuple:
+    """(the flattened spans, the number of scenarios) of a schedule of :class:`Span`, or ValueError: :func:`check_schedule`
+    without the steps.  Refused: an empty schedule, an entry that is no Span, a duration that is not finite and positive, a
+    case out of range, tuples of unequal length and ``repeat < 1``."""
+    if isinstance(repeat, bool) or not isinstance(repeat, (int, np.integer)) or repeat < 1:
+        raise ValueError(f"repeat must be an integer >= 1, not {repeat!r}")
+    if isinstance(schedule, (Span, Segment, Mapping, str, bytes)):
+        raise ValueError("the schedule must be a sequence of Spans")
+    try:
+        schedule = list(schedule)
+    except TypeError:
+        raise ValueError("the schedule must be a sequence of Spans") from None
+    if not schedule:
+        raise ValueError("an empty schedule: give at least one Span")
+    checked, n_scen = [], None
+    for i, span in enumerate(schedule):
+        if not isinstance(span, Span):
+            raise ValueError(f"span {i} is not a Span")
+        duration = _positive_number(span.duration, f"the duration of span {i}")
+        case = _scenario_entries(span.case, n_cases, f"the case of span {i}")
+        if isinstance(case, tuple):
+            if n_scen is not None and len(case) != n_scen:
+                raise ValueError(f"span {i} names {len(case)} scenarios, an earlier one {n_scen}")
+            n_scen = len(case)
+        checked.append(Span(duration=duration, case=case))
+    return [dataclasses.replace(span) for _ in range(int(repeat)) for span in checked], (1 if n_scen is None else n_scen)
+
+
+def check_step_control(tolerance, first_step=None, min_step=None, max_steps=MAX_TRANSIENT_STEPS) -> tuple:
+    """(tolerance [K], first_step, min_step [s] or None, max_steps) of the step-size control, or ValueError: a tolerance that
+    is not finite and positive; a ``first_step`` or ``min_step`` that is neither None nor finite and positive;
+    ``min_step > first_step``; a ``max_steps`` that is not an integer >= 1."""
+    tolerance = _positive_number(tolerance, "the tolerance")
+    first_step = None if first_step is None else _positive_number(first_step, "first_step")
+    min_step = None if min_step is None else _positive_number(min_step, "min_step")
+    if first_step is not None and min_step is not None and min_step > first_step:
+        raise ValueError(f"min_step ({min_step}) must not exceed first_step ({first_step})")
+    if isinstance(max_steps, bool) or not isinstance(max_steps, (int, np.integer)) or max_steps < 1:
+        raise ValueError(f"max_steps must be an integer >= 1, not {max_steps!r}")
+    return tolerance, first_step, min_step, int(max_steps)
+
+
+def dyadic_levels(duration: float, first_step=None, min_step=None) -> tuple:
+    """(the level k a span of ``duration`` starts at, the deepest level it may reach): steps are duration / 2^k.  The start is
+    the smallest k >= 0 with duration / 2^k <= first_step (None: duration / 1024), the deepest the largest k with
+    duration / 2^k >= min_step (None: duration / 2^30; 0 when even the whole span is shorter)."""
+    start = DEFAULT_FIRST_LEVEL
+    if first_step is not None:
+        start = 0
+        while math.ldexp(duration, -start) > first_step:
+            start += 1
+    deepest = DEFAULT_MAX_LEVEL
+    if min_step is not None:
+        deepest = 0
+        while math.ldexp(duration, -(deepest + 1)) >= min_step:
+            deepest += 1
+    return start, deepest
+
+
+def dyadic_controller(duration: float, tolerance: float, first_step=None, min_step=None):
+    """The step-size rule of one span as a generator: deterministic, and every step a dyadic fraction of the span, so that
+    steps land exactly on its end.  It yields ``(verdict, dt, level, pos)``: the verdict on the trial just judged (None at
+    first; "accept", "forced" or "reject"), the next step to try, dt = duration / 2^level (None once the span is covered),
+    and ``pos``, the accepted steps in units of that dt -- the time reached is pos * dt after the span's begin.  ``send`` it
+    the error estimate of the trial, the largest over the columns.
+
+    - reject: err > tolerance above the deepest level: level + 1, pos * 2, again from the same state;
+    - forced: err > tolerance at the deepest level (:func:`dyadic_levels`): accepted all the same;
+    - accept: pos + 1; the span ends when pos = 2^level;
+    - grow: after an accepted step with err <= tolerance / 4 (the estimate goes with dt^2), an even pos and level > 0:
+      level - 1, pos / 2.
+
+    An estimate that is not finite raises RuntimeError."""
+    level, deepest = dyadic_levels(duration, first_step, min_step)
+    pos, verdict = 0, None
+    while True:
+        err = yield verdict, math.ldexp(duration, -level), level, pos
+        err = float(err)
+        if not math.isfinite(err):
+            raise RuntimeError(f"the error estimate of a step of {math.ldexp(duration, -level)} s is not finite")
+        if err > tolerance and level < deepest:
+            level, pos, verdict = level + 1, pos * 2, "reject"
+            continue
+        verdict = "forced" if err > tolerance else "accept"
+        pos += 1
+        if pos == 2 ** level:
+            yield verdict, None, level, pos
+            return
+        if err <= tolerance / 4 and pos % 2 == 0 and level > 0:
+            level, pos = level - 1, pos // 2
+
+
+def adaptive_walk(spans, tolerance: float, first_step, min_step, max_steps: int, try_step, accept, end_of_span=None) -> dict:
+    """:func:`dyadic_controller` over ``spans`` = [(duration, load)], on the host.  ``try_step(dt, load)`` returns the error
+    estimates of a trial (their largest decides); ``accept(dt, time, load, errors)`` is called for every step that is taken,
+    with the time it reaches: the begin of the span + pos * dt, and begin + duration at its end, where the begins add up as
+    the durations do; ``end_of_span(index, time)`` after the last step of every span.  Returns {"tried", "rejected",
+    "forced", "decisions": the verdict on every trial in order}.  One SolverWarning per call when steps were forced;
+    RuntimeError for an estimate that is not finite and when ``max_steps`` trials do not cover the schedule (the message names
+    the time reached)."""
+    decisions, begin = [], 0.0
+    for at, (duration, load) in enumerate(spans):
+        control = dyadic_controller(duration, tolerance, first_step, min_step)
+        _verdict, dt, _level, pos = next(control)
+        while dt is not None:
+            if len(decisions) >= max_steps:
+                control.close()
+                raise RuntimeError(f"{max_steps} steps tried and the schedule is not covered: t = {begin + pos * dt} s reached "
+                                   f"with a step of {dt} s")
+            errors = np.asarray(try_step(dt, load), dtype=DTYPE).reshape(-1)
+            worst = float(errors.max()) if np.isfinite(errors).all() else float("nan")
+            # (after a growth pos counts in units of the doubled step: pos * dt is the same number either way)
+            verdict, dt_next, _level, pos = control.send(worst)
+            decisions.append(verdict)
+            if verdict != "reject":
+                accept(dt, begin + (duration if dt_next is None else pos * dt_next), load, errors)
+            dt = dt_next
+        begin = begin + duration
+        if end_of_span is not None:
+            end_of_span(at, begin)
+    forced = decisions.count("forced")
+    if forced:
+        warnings.warn(f"{forced} steps were accepted above the tolerance of {tolerance} K at the smallest step allowed",
+                      SolverWarning)
+    return {"tried": len(decisions), "rejected": decisions.count("reject"), "forced": forced, "decisions": decisions}
+
+
+def _check_adaptive_transient_arguments(prob, model, schedule, cases, repeat, probes, keep, tolerance, first_step, min_step,
+                                        max_steps, filtered_networks):
+    """Every check of :func:`solve_meshed_thermal_transient_adaptive`: (checked model, checked cases, per flattened span
+    (duration, per-scenario cases), per-scenario initial cases, probes, the step control)."""
+    checked = check_transient_model(prob, model, filtered_networks)
+    checked_cases = [{}] if cases is None else check_load_cases(prob, cases)
+    spans, n_scen = check_spans(schedule, len(checked_cases), repeat)
+    tuples = any(isinstance(span.case, tuple) for span in spans)
+    initial = _scenario_entries(checked.initial, len(checked_cases), "initial")
+    if isinstance(initial, tuple):
+        if tuples and len(initial) != n_scen:
+            raise ValueError(f"initial names {len(initial)} scenarios, the schedule {n_scen}")
+        n_scen = len(initial)
+    else:
+        initial = (initial,) * n_scen
+    flat = [(span.duration, span.case if isinstance(span.case, tuple) else (span.case,) * n_scen) for span in spans]
+    if keep not in ("end", "segments", "none"):
+        raise ValueError(f'keep must be "end", "segments" or "none", not {keep!r}')
+    control = check_step_control(tolerance, first_step, min_step, max_steps)
+    return checked, checked_cases, flat, initial, check_probes(prob, probes, filtered_networks), control
+
+
+def solve_meshed_thermal_transient_adaptive(prob, meshes, mesh_index_to_layer_index, model: TransientModel, schedule, *,
+                                            tolerance, cases=None, repeat=1, probes=(), keep="end", first_step=None,
+                                            min_step=None, max_steps=MAX_TRANSIENT_STEPS, filtered_networks=None,
+                                            disconnected_meshes_by_layer=None, partition=None, timings: Optional[dict] = None):
+    """:func:`solve_meshed_thermal_transient` without a time grid to choose: second-order steps whose size follows an error
+    estimate.  ``schedule`` is a sequence of :class:`Span` (a duration and the case that is on), ``tolerance`` the error in
+    kelvin a single step may add at any vertex.  The return value has the shape of the fixed-step call; ``times`` is not
+    uniform, and the envelope's steps count the accepted steps.
+
+    A step (DESIGN.md "Adaptive transient") is Alexander's two-stage SDIRK2 -- second order, L-stable like backward Euler and
+    so free of ringing on a load step -- from two backward-Euler solves of length gamma dt, gamma = 1 - 1/sqrt(2), on one
+    matrix.  Its difference to the embedded first-order solution estimates the step's error, conservatively.  Per span of
+    duration D the step is D / 2^k (:func:`dyadic_controller`): it starts at ``first_step`` (None: D / 1024), halves when the
+    estimate exceeds the tolerance, doubles when it is below a quarter of it and the position allows, and never falls below
+    ``min_step`` (None: D / 2^30), where steps are accepted with one SolverWarning per call.  Steps land exactly on the ends
+    of the spans, and two calls take the same path.  Every accepted step obeys
+    (stored_{n+1} - stored_n) / dt + (1 - gamma) stage_loss + gamma loss_{n+1} = heat of the span's case.
+
+    ``info`` holds what the fixed-step call's does (``iterations_per_step`` the sum of a step's two solves, ``hierarchies``
+    one per run of equal steps) and ``"step_sizes"`` (n_steps,), ``"error_estimates"`` (n_steps, n_scenarios) [K],
+    ``"stage_loss"`` (n_steps, n_scenarios): the film loss of the first stage [W], ``"stage_iterations"`` (n_steps, 2),
+    ``"tried"`` and ``"rejected"`` and ``"tried_step_sizes"`` (tried,), the rejected trials included.  ValueError, before anything reaches the device, for what the fixed-step call refuses of
+    its arguments, what :func:`check_spans` and :func:`check_step_control` refuse, and a ``partition`` over several GPUs;
+    RuntimeError for an estimate that is not finite and when ``max_steps`` trials do not cover the schedule."""
+    _refuse_partition(partition, "transient temperatures")
+    checked, checked_cases, flat, initial, probe_nodes, control = _check_adaptive_transient_arguments(
+        prob, model, schedule, cases, repeat, probes, keep, tolerance, first_step, min_step, max_steps, filtered_networks)
+    tolerance, first_step, min_step, max_steps = control
+    laps, ambient, n_scen = _Laps(timings), checked.thermal.ambient, len(initial)
+    with _thermal_block(prob, meshes, mesh_index_to_layer_index, checked.thermal, checked_cases, filtered_networks,
+                        disconnected_meshes_by_layer, laps, "temperatures over time") as blk:
+        board, k, heat = blk.board, blk.k, blk.heat
+        layer_of, n_mesh, n_vert = board.layer_of, len(board.meshes), blk.n_vert
+        *_, mesh_power, _cuts = blk.plan.current_cases(k, blk.n_tri, np.asarray(layer_of, dtype=np.int32), [], np.zeros((0, 4)),
+                                                       fields=False, envelope=False)
+        transient = _hip.Transient(blk.thermal, [checked.capacity[layer_of[i]] for i in range(n_mesh)])
+        try:
+            transient.loads_kkt(blk.plan, k, heat)
+            first = transient.start(initial, rtol=RTOL, max_iter=MAX_ITER)
+            laps.lap("transient_start")
+            probe_idx = [board.node_indexer.node_to_global_index[node] for node in probe_nodes]
+            top0, vert0, stored0, loss0 = transient.report()
+            theta0 = transient.state() if probe_idx else None
+            steps, times, led, snapshots, last, tried_sizes = [], [0.0], [], [], {}, []
+            worst = [first.rel_residual if first.status != _hip.OK else 0.0]
+
+            def try_step(dt, seg_cases):
+                last["trial"] = transient.try_step(dt, seg_cases, rtol=RTOL, max_iter=MAX_ITER)
+                tried_sizes.append(dt)
+                if last["trial"]["result"].status != _hip.OK:
+                    worst[0] = max(worst[0], float(last["trial"]["result"].rel_residual))
+                return last["trial"]["err"]
+
+            def accept(dt, time, seg_cases, errors):
+                out = transient.accept(probe_idx)
+                out.update(dt=dt, err=errors.copy(), trial=last["trial"])
+                steps.append(out)
+                times.append(time)
+                led.append(seg_cases)
+
+            def end_of_span(at, time):
+                if keep == "segments" or (keep == "end" and at == len(flat) - 1):
+                    snapshots.append((time, transient.state()))
+
+            walk = adaptive_walk(flat, tolerance, first_step, min_step, max_steps, try_step, accept, end_of_span)
+            env, env_step = transient.envelope(n_vert)
+            _steps, _time, hierarchies = transient.clock()
+            laps.lap("transient_run")
+        finally:
+            transient.close()
+    if worst[0] > max(RTOL, STALL_WARN_ABOVE):
+        warnings.warn(f"A step of the transient thermal solve stopped at a relative residual of {worst[0]:.3e}", SolverWarning)
+    solutions = _block_solutions(blk)
+    join = lambda key, head: np.stack([head] + [out[key] for out in steps])      # (n_steps + 1, n_scen, n_mesh)
+    mesh_max, mesh_vert, stored, loss = join("max", top0), join("vertex", vert0), join("stored", stored0), join("loss", loss0)
+    n_steps = len(steps)
+    stage_iterations = np.array([out["trial"]["stage_iterations"] for out in steps], dtype=np.int32).reshape(n_steps, 2)
+    iterations = stage_iterations.sum(axis=1).astype(np.int32)
+    info = {"iterations": int(first.iterations) + int(iterations.sum()), "iterations_per_step": iterations,
+            "seconds_per_step": np.array([float(out["trial"]["result"].seconds) for out in steps]),
+            "setup_seconds_per_step": np.array([float(out["trial"]["stage_setup_seconds"].sum()) for out in steps]),
+            "rel_residual": max([float(first.rel_residual)] + [float(out["trial"]["result"].rel_residual) for out in steps]),
+            "hierarchies": int(hierarchies),
+            "seconds": float(first.seconds) + sum(float(out["trial"]["result"].seconds) for out in steps),
+            "step_sizes": np.array([out["dt"] for out in steps], dtype=DTYPE),
+            "error_estimates": np.array([out["err"] for out in steps], dtype=DTYPE).reshape(n_steps, n_scen),
+            "stage_loss": np.array([[math.fsum(out["stage_loss"][c].tolist()) for c in range(n_scen)] for out in steps],
+                                   dtype=DTYPE).reshape(n_steps, n_scen),
+            "stage_iterations": stage_iterations, "tried": walk["tried"], "rejected": walk["rejected"],
+            "tried_step_sizes": np.array(tried_sizes, dtype=DTYPE)}
+    n_layers = len(prob.layers)
+    case_layer_heat = [[math.fsum(float(mesh_power[j, i]) for i in range(n_mesh) if layer_of[i] == layer_i)
+                        for layer_i in range(n_layers)] for j in range(k)]
+    element_heat = [math.fsum(heat[2][heat[1] == j].tolist()) if heat is not None else 0.0 for j in range(k)]
+    case_total = [math.fsum(case_layer_heat[j] + [element_heat[j]]) for j in range(k)]
+    if blk.sources is not None:                              # the load table's column j carries the sources of case j
+        case_total = [case_total[j] + math.fsum(blk.source_power[j].tolist()) for j in range(k)]
+    reports = []
+    for c in range(n_scen):
+        on = [initial[c]] + [seg_cases[c] for seg_cases in led]
+        layer_heat = [[0.0 if j is None else case_layer_heat[j][layer_i] for j in on] for layer_i in range(n_layers)]
+        total_heat = [0.0 if j is None else case_total[j] for j in on]
+        traces = {}
+        for p, node in enumerate(probe_nodes):
+            traces[node] = np.array([theta0[c, probe_idx[p]]] + [out["probes"][c, p] for out in steps])
+        reports.append(_transient_report(board, ambient, times, mesh_max[:, c], mesh_vert[:, c], stored[:, c], loss[:, c],
+                                         layer_heat, total_heat, traces, env[c], env_step[c],
+                                         [(when, theta[c]) for when, theta in snapshots], info))
+    laps.lap("solutions")
+    if n_scen == 1:
+        return solutions, reports[0]
+    return solutions, reports
+
+
+def solve_thermal_transient_adaptive(prob, model: TransientModel, schedule, mesher_config: Optional[mesh.Mesher.Config] = None, *,
+                                     tolerance, mesher=None, cases=None, repeat=1, probes=(), keep="end", first_step=None,
+                                     min_step=None, max_steps=MAX_TRANSIENT_STEPS, partition=None):
+    """``solve`` with the copper's temperatures over a schedule of spans (see
+    :func:`solve_meshed_thermal_transient_adaptive`): the board is meshed once."""
+    _refuse_partition(partition, "transient temperatures")
+    _check_adaptive_transient_arguments(prob, model, schedule, cases, repeat, probes, keep, tolerance, first_step, min_step,
+                                        max_steps, None)
+    meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
+    return solve_meshed_thermal_transient_adaptive(prob, meshes, mesh_index_to_layer_index, model, schedule, tolerance=tolerance,
+                                                   cases=cases, repeat=repeat, probes=probes, keep=keep, first_step=first_step,
+                                                   min_step=min_step, max_steps=max_steps)
+
+
+# --------------------------------------------------------------------------------------------
 # electro-thermal: the copper's conductance follows its temperature (DESIGN.md "Electro-thermal")
 # --------------------------------------------------------------------------------------------
 
