@@ -344,6 +344,13 @@ int padne_kkt_solve_block_coo(padne_ctx *ctx, padne_kkt *plan, int32_t n_cols, i
                               const double *known_val, int32_t n_extra, const int64_t *extra_ptr, const int64_t *extra_row,
                               const double *extra_val, int64_t n_probe, const int64_t *probe_idx, double *probe_out,
                               const padne_solve_opts *opts, double abs_residual_target, padne_solve_info *info);
+/* padne_kkt_solve_block with the block r_dev[N][n_cols] (row-major) already on the device, on the context's stream: one
+ * device-to-device copy into the plan's r takes the place of the upload, everything after that is padne_kkt_solve_block and
+ * gives its bits for the same block.  The caller keeps r_dev; it is read before the call returns. */
+int padne_kkt_solve_block_dev(padne_ctx *ctx, padne_kkt *plan, int32_t n_cols, const void *r_dev, int64_t n_known,
+                              const int64_t *known_idx, const double *known_val, int32_t n_extra, const int64_t *extra_ptr,
+                              const int64_t *extra_row, const double *extra_val, int64_t n_probe, const int64_t *probe_idx,
+                              double *probe_out, const padne_solve_opts *opts, double abs_residual_target, padne_solve_info *info);
 /* Per-face sigma |grad V|^2 of every column of the block the last padne_kkt_finish_block left on the device, over the mesh
  * `L` keeps: out_host[n_cols][n_tri] row-major, column j bit-identical to padne_csr_power_density on V[:, j].  Nothing
  * crosses PCIe but the result.  PADNE_E_INVALID when no block has been finished since the last solve, when n_cols is not
@@ -710,6 +717,64 @@ int padne_thermal_source_lists(padne_ctx *ctx, const padne_thermal *th, int32_t 
 /* After a solve of n_cols columns: temperature_out[n_cols][n_source] = T_s - ambient = the sum over the list of s, in the
  * order of A_s, of (area_f / A_s) * mean[c][f], mean the face mean of padne_thermal_report.  Two calls give the same bits. */
 int padne_thermal_source_report(padne_ctx *ctx, padne_thermal *th, int32_t n_cols, double *temperature_out);
+
+/* ---- temperature sensitivities: what cools a hotspot, by adjoints ---------------------------------
+ * No reference counterpart ("Temperature sensitivities").  After padne_kkt_finish_block of the n_cases load cases
+ * (M x_c = r_c) and padne_thermal_solve_kkt of as many columns (A theta_c = b(x_c)) on `th`, an objective j of case c is the
+ * temperature T_j = ambient + g_j^T theta_c.  With the corners (1, 2, 3) of a face as padne_thermal_report visits them and
+ * w_ik the assembly's |cot| / 2 weights:
+ *     A lambda_j = g_j;     lbar_f = ((lambda_1 + lambda_2) + lambda_3) / 3
+ *     c_j = grad_x (sum_f lbar_f P_f(x) [+ sum_R ((lambda_a + lambda_b) / 2) (x_a - x_b)^2 / R]);     M^T mu_j = c_j
+ *     e_f = lbar_f P_f + sigma sum_edges w_ik (mu_i - mu_k)(x_i - x_k)               (= sigma dT_j / dsigma_f)
+ *     k_f = -kappa sum_edges w_ik (lambda_i - lambda_k)(theta_i - theta_k)           (= kappa dT_j / dkappa_f)
+ * The handle borrows `th` and `plan` (both must outlive it) and owns device copies of what the later solves overwrite: the
+ * cases' potentials and theta, field-major [n_cases][n_potential], then lambda [n_obj][n_potential] and the block c
+ * [N][n_obj].  kappa[n_mesh]: the thermal sheet conductance the handle `th` was made with.  No floating-point atomics: two
+ * calls give the same bits.  PADNE_E_INVALID for a null or foreign handle, a plan without a finished block of n_cases
+ * columns or of another system, a thermal handle without a solve of n_cases columns, and a wrong n_mesh. */
+typedef struct padne_tsens padne_tsens;
+int padne_tsens_create(padne_ctx *ctx, padne_thermal *th, padne_kkt *plan, int32_t n_cases, int32_t n_mesh, const double *kappa,
+                       padne_tsens **out);
+int padne_tsens_destroy(padne_tsens *ts);     /* NULL is accepted */
+/* lambda_j for n_obj (1 .. 4096) objectives, formed and solved on the device: g never crosses PCIe.  Objective j reads case
+ * obj_case[j].  obj_kind[j] = 0: the point obj_xy[j] on layer obj_arg[j] (mesh_layer[n_mesh]: the layer of every mesh) --
+ * the owner face is the containing face of the layer with the lowest global number, by the sides of the field sampler, and
+ * g_j is the sampler's weights o_k / s, s = (o_a + o_b) + o_c, at its corners; obj_unknown[3 j ..] and obj_weight[3 j ..]
+ * RETURN the corners and weights.  Kind 1: g_j = the up to three pairs (obj_unknown[3 j + k], obj_weight[3 j + k]) the caller
+ * lists (unknown -1: no pair).  Kind 2: heat source obj_arg[j] of the handle, g_v = the sum over the faces f of v's list,
+ * front to back, that the source loads of (area_f / A_s) / 3: its load with unit power, so g_j^T theta is its footprint
+ * temperature.  All columns go through one padne_solve_spd_dev on A, whose hierarchy exists from the forward solve (opts null:
+ * the defaults of padne_thermal_solve).  probe_out[n_obj][n_probe] = lambda_j at the unknowns probe_idx.  PADNE_E_INVALID for
+ * counts, cases, kinds, unknowns or sources out of range, values that are not finite, and a point on no face of its layer:
+ * the message names the lowest such objective and nothing is solved.  PADNE_E_NOTCONVERGED keeps the iterate. */
+int padne_tsens_thermal_adjoints(padne_ctx *ctx, padne_tsens *ts, int32_t n_obj, const int32_t *obj_case, const int32_t *obj_kind,
+                                 const int32_t *obj_arg, const double *obj_xy, int64_t *obj_unknown, double *obj_weight,
+                                 int32_t n_mesh, const int32_t *mesh_layer, int64_t n_probe, const int64_t *probe_idx,
+                                 double *probe_out, const padne_solve_opts *opts, padne_solve_info *info);
+/* The block c[N][n_obj] (row-major, the layout of the plan's right-hand sides) on the device, *r_dev_out, for
+ * padne_kkt_solve_block_dev: row i of a vertex = the sum over the faces f of its list, front to back, of (2 lbar_f) * (sigma *
+ * d), d the two edge terms w_ik (x_i - x_k) of f at i; then per resistor (res_a, res_b, res_R) in list order, grouped by the
+ * unknown, +t at a and -t at b with t = (2 ((lambda_a + lambda_b) / 2)) * ((x_a - x_b) / R) (n_res = 0: no element heat); zero
+ * on every other row.  One thread per unknown, the objectives in register chunks of 4.  PADNE_E_INVALID unless it follows
+ * padne_tsens_thermal_adjoints of n_obj objectives, and for a terminal out of range or a resistance of 0. */
+int padne_tsens_electrical_rhs(padne_ctx *ctx, padne_tsens *ts, int32_t n_obj, int64_t n_res, const int64_t *res_a,
+                               const int64_t *res_b, const double *res_R, const void **r_dev_out);
+/* After padne_kkt_solve_block_dev of that block and padne_kkt_finish_block of n_obj columns on the handle's plan (mu is read
+ * from the finished block): electrical_out, thermal_out, copper_out[n_obj][n_tri] = e_f / area_f, k_f / area_f and (e_f +
+ * k_f) / area_f, and mesh_electrical_out, mesh_thermal_out[n_obj][n_mesh] the sums of e_f and k_f per mesh: tiles of 256
+ * faces of one mesh, folded in the fixed order of padne_thermal_report.  PADNE_E_INVALID without that finished block. */
+int padne_tsens_faces(padne_ctx *ctx, padne_tsens *ts, int32_t n_obj, int64_t n_tri, int32_t n_mesh, double *electrical_out,
+                      double *thermal_out, double *copper_out, double *mesh_electrical_out, double *mesh_thermal_out);
+/* mesh_film_out[n_obj][n_mesh] = the sum over the vertices v of the mesh of -((film M_v lambda_v) theta_v) = film dT_j / dfilm
+ * of the mesh, in tiles of 256 vertices and the fold of padne_thermal_report. */
+int padne_tsens_vertices(padne_ctx *ctx, padne_tsens *ts, int32_t n_obj, int32_t n_mesh, double *mesh_film_out);
+/* pair_out[n_obj][n_pair] = pair_g dT_j / dpair_g = -(the sum over the vertices i of layer a and their stored partners k in
+ * layer b, ascending, of (-G_ik) ((lambda_i - lambda_k) (theta_i - theta_k))), in the order of padne_thermal_stack_flows.
+ * n_pair: the pairs of the thermal handle (0 without a stack: nothing is written). */
+int padne_tsens_pairs(padne_ctx *ctx, padne_tsens *ts, int32_t n_obj, int32_t n_pair, double *pair_out);
+/* source_out[n_obj][n_source] = dT_j / dP_s [K/W] = padne_thermal_source_report's sum with lambda_j in the place of theta.
+ * n_source: the heat sources of the thermal handle (0: nothing is written). */
+int padne_tsens_sources(padne_ctx *ctx, padne_tsens *ts, int32_t n_obj, int32_t n_source, double *source_out);
 
 /* ---- electro-thermal coupling: the copper's conductance follows its temperature ----------------
  * No reference counterpart ("Electro-thermal").  Face t of mesh m conducts sigma[m] * s[t],

@@ -111,6 +111,8 @@ SIGNATURES = {
     "padne_kkt_solve_block_coo": (C.c_int, [_P, _P, C.c_int32, _I64, _PI64, _PI32, _PF64, _I64, _PI64, _PF64, C.c_int32, _PI64,
                                             _PI64, _PF64, _I64, _PI64, _PF64, C.POINTER(SolveOpts), C.c_double,
                                             C.POINTER(SolveInfo)]),
+    "padne_kkt_solve_block_dev": (C.c_int, [_P, _P, C.c_int32, _P, _I64, _PI64, _PF64, C.c_int32, _PI64, _PI64, _PF64, _I64,
+                                            _PI64, _PF64, C.POINTER(SolveOpts), C.c_double, C.POINTER(SolveInfo)]),
     "padne_kkt_power_density_block": (C.c_int, [_P, _P, C.c_int32, _PF64]),
     "padne_kkt_combine_block": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _PI64, _PI32, _PF64, _PF64]),
     "padne_kkt_sensitivity_block": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _PF64, _PF64, _PF64, _PF64]),
@@ -168,6 +170,15 @@ SIGNATURES = {
     "padne_thermal_source_power": (C.c_int, [_P, _P, C.c_int32, _PF64]),
     "padne_thermal_source_lists": (C.c_int, [_P, _P, C.c_int32, _I64, _PI64, _PI32]),
     "padne_thermal_source_report": (C.c_int, [_P, _P, C.c_int32, _PF64]),
+    "padne_tsens_create": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _PF64, C.POINTER(_P)]),
+    "padne_tsens_destroy": (C.c_int, [_P]),
+    "padne_tsens_thermal_adjoints": (C.c_int, [_P, _P, C.c_int32, _PI32, _PI32, _PI32, _PF64, _PI64, _PF64, C.c_int32, _PI32, _I64,
+                                               _PI64, _PF64, C.POINTER(SolveOpts), C.POINTER(SolveInfo)]),
+    "padne_tsens_electrical_rhs": (C.c_int, [_P, _P, C.c_int32, _I64, _PI64, _PI64, _PF64, C.POINTER(_P)]),
+    "padne_tsens_faces": (C.c_int, [_P, _P, C.c_int32, _I64, C.c_int32, _PF64, _PF64, _PF64, _PF64, _PF64]),
+    "padne_tsens_vertices": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _PF64]),
+    "padne_tsens_pairs": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _PF64]),
+    "padne_tsens_sources": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _PF64]),
     "padne_transient_create": (C.c_int, [_P, _P, C.c_int32, _PF64, C.POINTER(_P)]),
     "padne_transient_destroy": (C.c_int, [_P]),
     "padne_transient_capacity": (C.c_int, [_P, _P, _PF64]),
@@ -851,6 +862,24 @@ class KktPlan:
                             abs_residual_target, rebuild, power_tri=int(power_tri), power_rows=int(power_rows),
                             current_tri=int(current_tri), current_cols=int(current_cols))
 
+    def solve_block_dev(self, n_cols, r_dev, known_idx, known_val, extras: list, probes, *, rtol=1e-12, max_iter=200000,
+                        precond="amg", abs_residual_target=0.0, rebuild=False):
+        """``solve_block`` with the block (N, n_cols), row-major, already on the device: ``r_dev`` is its address (an int, or a
+        :class:`DeviceArray`).  One device copy takes the place of the upload; the results have the bits of ``solve_block``
+        on the same block."""
+        n_cols = int(n_cols)
+        if n_cols < 1:
+            raise ValueError("a block has at least one column")
+        if isinstance(r_dev, DeviceArray):
+            if int(np.prod(r_dev.shape)) != self.N * n_cols:
+                raise ValueError("the device block must hold N * n_cols doubles")
+            r_dev = r_dev.ptr
+        if not r_dev:
+            raise ValueError("the device block is a null pointer")
+        kidx = _i64(known_idx)
+        kval = _f64(known_val).reshape(n_cols, kidx.shape[0])
+        return self._stage1(n_cols, int(r_dev), kidx, kval, extras, probes, rtol, max_iter, precond, abs_residual_target, rebuild)
+
     def _stage1(self, n_cols, r, kidx, kval, extras, probes, rtol, max_iter, precond, abs_residual_target, rebuild,
                 power_tri=0, power_rows=0, current_tri=0, current_cols=1):
         ptr, rows, vals = [0], [], []
@@ -866,8 +895,8 @@ class KktPlan:
         info = SolveInfo()
         # the array stage 2 will hand back (and that of the power densities of a block that asks for them): their pages are
         # touched while the device solves, so that a block's result is ready when the device is
-        coo = isinstance(r, tuple)
-        v_shape = (self.N, n_cols) if coo else r.shape
+        coo, dev = isinstance(r, tuple), isinstance(r, int)
+        v_shape = (self.N, n_cols) if coo or dev else r.shape
         self._prefault = {"v": _prefaulted(v_shape)}
         if coo and power_tri > 0:
             self._prefault["pd"] = _prefaulted((power_rows or n_cols, power_tri))
@@ -880,6 +909,8 @@ class KktPlan:
             r_rows, r_cols, r_vals = r
             rc = lib.padne_kkt_solve_block_coo(self.ctx._h, self._h, int(n_cols), r_rows.shape[0], _ptr(r_rows, _PI64),
                                                _ptr(r_cols, _PI32), _ptr(r_vals, _PF64), *common)
+        elif dev:
+            rc = lib.padne_kkt_solve_block_dev(self.ctx._h, self._h, int(n_cols), _P(r), *common)
         elif n_cols is None:
             rc = lib.padne_kkt_solve(self.ctx._h, self._h, _ptr(r, _PF64), *common)
         else:
@@ -1584,6 +1615,103 @@ class Coupled:
         """``KktPlan.power_density_block(1, n_tri)[0]`` times the used scale, on the device."""
         out = np.empty(int(n_tri), dtype=np.float64)
         _check(self.ctx._lib.padne_coupled_power_density(self.ctx._h, self._h, plan._h, _ptr(out, _PF64)))
+        return out
+
+
+class ThermalSensitivities:
+    """``padne_tsens``: the adjoints of temperature objectives on a solved :class:`Thermal` handle and the plan whose
+    finished block holds the load cases' potentials (include/padne_hip.h, "temperature sensitivities").  ``kappa`` per mesh,
+    as the thermal handle was made with.  The calls follow one another: ``thermal_adjoints``, ``electrical_rhs``, the plan's
+    ``solve_block_dev`` and ``finish_block``, then ``faces``; ``vertices``, ``pairs`` and ``sources`` need the thermal
+    adjoints only."""
+
+    KIND_POINT, KIND_UNKNOWNS, KIND_SOURCE = 0, 1, 2
+
+    def __init__(self, thermal: "Thermal", plan: "KktPlan", n_cases: int, kappa):
+        self.ctx, self.thermal, self.plan = thermal.ctx, thermal, plan
+        kap = _f64(kappa).reshape(-1)
+        h = _P()
+        _check(self.ctx._lib.padne_tsens_create(self.ctx._h, thermal._h, plan._h, int(n_cases), kap.shape[0], _ptr(kap, _PF64),
+                                                C.byref(h)))
+        self._h = h
+        self.n_cases, self.n_obj = int(n_cases), 0
+
+    def close(self):
+        if getattr(self, "_h", None) and self.ctx._h:
+            self.ctx._lib.padne_tsens_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def thermal_adjoints(self, case, kind, arg, xy, unknown, weight, mesh_layer, probes=(), *, rtol=1e-12, max_iter=200000,
+                         precond="amg"):
+        """lambda of the objectives: ``case``, ``kind`` and ``arg`` (n_obj,), ``xy`` (n_obj, 2), ``unknown`` and ``weight``
+        (n_obj, 3) as the header states them.  Returns (unknown (n_obj, 3) int64 and weight (n_obj, 3) with the owners of the
+        points filled in, lambda at the unknowns ``probes`` (n_obj, n_probe), SolveResult)."""
+        case, kind, arg = _i32(case).reshape(-1), _i32(kind).reshape(-1), _i32(arg).reshape(-1)
+        n_obj = case.shape[0]
+        xy = _f64(xy).reshape(n_obj, 2)
+        unknown, weight = np.array(unknown, dtype=np.int64).reshape(n_obj, 3), np.array(weight, dtype=np.float64).reshape(n_obj, 3)
+        if not (kind.shape == arg.shape == case.shape):
+            raise ValueError("case, kind and arg must list the same objectives")
+        ml, pidx = _i32(mesh_layer).reshape(-1), _i64(list(probes))
+        out = np.zeros((n_obj, max(pidx.shape[0], 1)), dtype=np.float64)
+        opts = CsrMatrix._opts(rtol, 0.0, max_iter, 0, False, precond=precond)
+        info = SolveInfo()
+        self.n_obj = 0
+        rc = self.ctx._lib.padne_tsens_thermal_adjoints(
+            self.ctx._h, self._h, n_obj, _ptr(case, _PI32), _ptr(kind, _PI32), _ptr(arg, _PI32), _ptr(xy, _PF64),
+            _ptr(unknown, _PI64), _ptr(weight, _PF64), ml.shape[0], _ptr(ml, _PI32), pidx.shape[0], _ptr(pidx, _PI64),
+            _ptr(out, _PF64), C.byref(opts), C.byref(info))
+        if rc != OK and rc != E_NOTCONVERGED:
+            _check(rc)
+        self.n_obj = n_obj
+        res = SolveResult(None, info.iterations, info.restarts, info.rel_residual, info.abs_residual, info.solve_seconds,
+                          info.status, info.spmv_seconds, info.precond_setup_seconds, info.operator_complexity, info.levels,
+                          info.precond_fallbacks)
+        return unknown, weight, out[:, :pidx.shape[0]], res
+
+    def electrical_rhs(self, res_a=(), res_b=(), res_R=()) -> int:
+        """The right-hand sides of the electrical adjoints, formed on the device; the resistors (terminals as unknowns,
+        resistance) with element heat, none without.  Returns the address of the block (N, n_obj) for ``solve_block_dev``."""
+        a, b, R = _i64(res_a).reshape(-1), _i64(res_b).reshape(-1), _f64(res_R).reshape(-1)
+        if not (a.shape == b.shape == R.shape):
+            raise ValueError("res_a, res_b and res_R must list the same resistors")
+        out = _P()
+        _check(self.ctx._lib.padne_tsens_electrical_rhs(self.ctx._h, self._h, self.n_obj, a.shape[0], _ptr(a, _PI64),
+                                                        _ptr(b, _PI64), _ptr(R, _PF64), C.byref(out)))
+        return int(out.value)
+
+    def faces(self, n_tri: int, n_mesh: int):
+        """(e_f / area, k_f / area, (e_f + k_f) / area, each (n_obj, n_tri); the per-mesh sums of e_f and of k_f, each (n_obj,
+        n_mesh)), after the plan's ``finish_block`` of the electrical adjoints."""
+        n_tri, n_mesh, n_obj = int(n_tri), int(n_mesh), self.n_obj
+        e, k, c = (np.empty((n_obj, n_tri), dtype=np.float64) for _ in range(3))
+        me, mk = (np.empty((n_obj, n_mesh), dtype=np.float64) for _ in range(2))
+        _check(self.ctx._lib.padne_tsens_faces(self.ctx._h, self._h, n_obj, n_tri, n_mesh, _ptr(e, _PF64), _ptr(k, _PF64),
+                                               _ptr(c, _PF64), _ptr(me, _PF64), _ptr(mk, _PF64)))
+        return e, k, c, me, mk
+
+    def vertices(self, n_mesh: int) -> np.ndarray:
+        """film dT/dfilm of every mesh, (n_obj, n_mesh)."""
+        out = np.empty((self.n_obj, int(n_mesh)), dtype=np.float64)
+        _check(self.ctx._lib.padne_tsens_vertices(self.ctx._h, self._h, self.n_obj, int(n_mesh), _ptr(out, _PF64)))
+        return out
+
+    def pairs(self) -> np.ndarray:
+        """g dT/dg of every pair of the stacked thermal handle, (n_obj, n_pair)."""
+        out = np.zeros((self.n_obj, self.thermal.n_pair), dtype=np.float64)
+        _check(self.ctx._lib.padne_tsens_pairs(self.ctx._h, self._h, self.n_obj, self.thermal.n_pair, _ptr(out, _PF64)))
+        return out
+
+    def sources(self) -> np.ndarray:
+        """dT/dP of every heat source of the thermal handle, (n_obj, n_source)."""
+        out = np.zeros((self.n_obj, self.thermal.n_source), dtype=np.float64)
+        _check(self.ctx._lib.padne_tsens_sources(self.ctx._h, self._h, self.n_obj, self.thermal.n_source, _ptr(out, _PF64)))
         return out
 
 

@@ -691,9 +691,11 @@ static int kkt_products(padne_ctx *ctx, const padne_kkt *k, const int n_cols, co
     return PADNE_OK;
 }
 
-// The right-hand sides of a stage 1: a dense block r_host[N][n_cols], or (r_host null) n_entries COO triples
+// The right-hand sides of a stage 1: a dense block r_host[N][n_cols], the same block already on the device (dense_dev), or
+// (both null) n_entries COO triples
 struct KktRhs {
     const double *dense = nullptr;
+    const double *dense_dev = nullptr;
     int64_t n_entries = 0;
     const int64_t *row = nullptr;
     const int32_t *col = nullptr;
@@ -792,6 +794,9 @@ static int kkt_solve_block(padne_ctx *ctx, padne_kkt *k, const int n_cols, const
             (void)hipSetDevice(ctx->device);
             up_rc = parallel_copy(k, k->r, r_host, sizeof(double) * (size_t)N * (size_t)n_cols, hipMemcpyHostToDevice);
         });
+    } else if (rhs.dense_dev != nullptr) {
+        // a block another handle formed on the device: one copy on the stream into the plan's r, in the same layout
+        PADNE_HIP_CHECK(hipMemcpyAsync(k->r, rhs.dense_dev, sizeof(double) * (size_t)N * (size_t)n_cols, hipMemcpyDeviceToDevice, s));
     } else {
         PADNE_HIP_CHECK(hipMemsetAsync(k->r, 0, sizeof(double) * (size_t)N * (size_t)n_cols, s));
         if (rhs.n_entries > 0) {
@@ -1081,6 +1086,18 @@ extern "C" int padne_kkt_solve_block(padne_ctx *ctx, padne_kkt *k, int32_t n_col
     KktRhs rhs;
     rhs.dense = r_host;
     PADNE_REQUIRE(r_host, "null argument");
+    return kkt_solve_block(ctx, k, n_cols, rhs, n_known, known_idx, known_val, n_extra, extra_ptr, extra_row, extra_val, n_probe,
+                           probe_idx, probe_out, opts, abs_residual_target, info);
+}
+
+extern "C" int padne_kkt_solve_block_dev(padne_ctx *ctx, padne_kkt *k, int32_t n_cols, const void *r_dev, int64_t n_known,
+                                         const int64_t *known_idx, const double *known_val, int32_t n_extra, const int64_t *extra_ptr,
+                                         const int64_t *extra_row, const double *extra_val, int64_t n_probe, const int64_t *probe_idx,
+                                         double *probe_out, const padne_solve_opts *opts, double abs_residual_target,
+                                         padne_solve_info *info) {
+    KktRhs rhs;
+    rhs.dense_dev = (const double *)r_dev;
+    PADNE_REQUIRE(r_dev, "null argument");
     return kkt_solve_block(ctx, k, n_cols, rhs, n_known, known_idx, known_val, n_extra, extra_ptr, extra_row, extra_val, n_probe,
                            probe_idx, probe_out, opts, abs_residual_target, info);
 }

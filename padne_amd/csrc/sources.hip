@@ -37,20 +37,6 @@
 #include <string>
 #include <vector>
 
-struct padne_sources {
-    int n_source = 0, n_layer = 0;
-    long long n_entries = 0;                 // list entries of all sources together
-    std::vector<int> layer;                  // per source
-    std::vector<long long> lptr_host;        // [n_source + 1]
-    // device (the context's pool)
-    int *lptr = nullptr, *lface = nullptr;   // source -> faces, ascending
-    int *fptr = nullptr, *fsrc = nullptr;    // face -> sources, ascending
-    double *A = nullptr;                     // [n_source] A_s
-    double *face_area = nullptr;             // [n_tri]
-    double *power = nullptr;                 // [power_cols][n_source]
-    int power_cols = 0;
-};
-
 namespace padne {
 
 constexpr int kSourceMaxVertices = 256;      // of a polygon: what the LDS image of the walk holds
@@ -523,12 +509,11 @@ extern "C" int padne_thermal_source_lists(padne_ctx *ctx, const padne_thermal *t
     return PADNE_OK;
 }
 
-extern "C" int padne_thermal_source_report(padne_ctx *ctx, padne_thermal *th, int32_t n_cols, double *temperature_out) {
-    PADNE_TRY(thermal_require("padne_thermal_source_report", ctx, th));
-    PADNE_REQUIRE(th->sources != nullptr, "padne_thermal_source_report follows padne_thermal_set_sources");
-    PADNE_REQUIRE(th->solved && n_cols == th->n_cols, "padne_thermal_source_report follows a solve of as many columns");
-    PADNE_REQUIRE(n_cols <= 65535, "too many columns for one launch");
-    PADNE_REQUIRE(temperature_out != nullptr, "null argument");
+// out_host[n_cols][n_source] = the sum over every source's list, in the order of A_s, of (area_f / A_s) * the face mean of the
+// field[n_cols][n_pot] on the device: the report of theta, and of an adjoint field for thermal_sens.hip
+int padne::sources_report_field(padne_ctx *ctx, const padne_thermal *th, int32_t n_cols, const double *field, double *out_host) {
+    PADNE_REQUIRE(n_cols >= 1 && n_cols <= 65535, "too many columns for one launch");
+    PADNE_REQUIRE(out_host != nullptr, "null argument");
     const padne_sources *sr = th->sources;
     PADNE_HIP_CHECK(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
@@ -539,9 +524,16 @@ extern "C" int padne_thermal_source_report(padne_ctx *ctx, padne_thermal *th, in
     PADNE_TRY(sc.alloc(&d_out, count));
     hipLaunchKernelGGL(sources_sum_kernel<true>, dim3((unsigned)sr->n_source, (unsigned)n_cols), dim3(256), 0, s, sr->n_source,
                        (const int *)sr->lptr, (const int *)sr->lface, (const double *)sr->face_area, (const double *)sr->A, th->n_mesh,
-                       M.tri, M.voff, M.toff, th->n_pot, (const double *)th->theta, d_out);
+                       M.tri, M.voff, M.toff, th->n_pot, field, d_out);
     PADNE_HIP_CHECK(hipGetLastError());
-    PADNE_HIP_CHECK(hipMemcpyAsync(temperature_out, d_out, sizeof(double) * count, hipMemcpyDeviceToHost, s));
+    PADNE_HIP_CHECK(hipMemcpyAsync(out_host, d_out, sizeof(double) * count, hipMemcpyDeviceToHost, s));
     PADNE_HIP_CHECK(hipStreamSynchronize(s));
     return PADNE_OK;
+}
+
+extern "C" int padne_thermal_source_report(padne_ctx *ctx, padne_thermal *th, int32_t n_cols, double *temperature_out) {
+    PADNE_TRY(thermal_require("padne_thermal_source_report", ctx, th));
+    PADNE_REQUIRE(th->sources != nullptr, "padne_thermal_source_report follows padne_thermal_set_sources");
+    PADNE_REQUIRE(th->solved && n_cols == th->n_cols, "padne_thermal_source_report follows a solve of as many columns");
+    return sources_report_field(ctx, th, n_cols, th->theta, temperature_out);
 }

@@ -33,21 +33,6 @@
 #include <string>
 #include <vector>
 
-struct padne_stack {
-    int n_layer = 0, n_pair = 0, n_side = 0;
-    std::vector<int> mesh_layer, pair_a, pair_b;         // as given
-    std::vector<double> pair_g;
-    long long n_query = 0, nnz = 0;                      // (side, vertex) slots; stored off-diagonals of G
-    std::vector<long long> q_side_off;                   // [n_side + 1] the first slot of every side
-    // device (the context's pool).  Slots: owner[q] the global face or -1, vertex[q], weight and cond [q][3]
-    int *owner = nullptr, *vertex = nullptr, *mesh_layer_dev = nullptr;
-    int *vertex_layer = nullptr;                         // [n_vert] the layer of every vertex (the flows)
-    double *weight = nullptr, *cond = nullptr;
-    // G without its diagonal as CSR [n_pot], and the diagonal
-    int *gptr = nullptr, *gcol = nullptr;
-    double *gval = nullptr, *gdiag = nullptr;
-};
-
 namespace padne {
 
 void stack_free(padne_ctx *ctx, padne_stack *st) {

@@ -18,9 +18,37 @@ constexpr int kThermalChunk = 8;       // columns per launch of the load kernel,
 
 }  // namespace padne
 
-struct padne_stack;      // stack.hip
+// the inter-layer coupling of a stacked handle (stack.hip) and the heat sources of a handle (sources.hip), as thermal_sens.hip
+// reads them
+struct padne_stack {
+    int n_layer = 0, n_pair = 0, n_side = 0;
+    std::vector<int> mesh_layer, pair_a, pair_b;         // as given
+    std::vector<double> pair_g;
+    long long n_query = 0, nnz = 0;                      // (side, vertex) slots; stored off-diagonals of G
+    std::vector<long long> q_side_off;                   // [n_side + 1] the first slot of every side
+    // device (the context's pool).  Slots: owner[q] the global face or -1, vertex[q], weight and cond [q][3]
+    int *owner = nullptr, *vertex = nullptr, *mesh_layer_dev = nullptr;
+    int *vertex_layer = nullptr;                         // [n_vert] the layer of every vertex (the flows)
+    double *weight = nullptr, *cond = nullptr;
+    // G without its diagonal as CSR [n_pot], and the diagonal
+    int *gptr = nullptr, *gcol = nullptr;
+    double *gval = nullptr, *gdiag = nullptr;
+};
 namespace padne { void stack_free(padne_ctx *ctx, padne_stack *st); }
-struct padne_sources;    // sources.hip
+
+struct padne_sources {
+    int n_source = 0, n_layer = 0;
+    long long n_entries = 0;                 // list entries of all sources together
+    std::vector<int> layer;                  // per source
+    std::vector<long long> lptr_host;        // [n_source + 1]
+    // device (the context's pool)
+    int *lptr = nullptr, *lface = nullptr;   // source -> faces, ascending
+    int *fptr = nullptr, *fsrc = nullptr;    // face -> sources, ascending
+    double *A = nullptr;                     // [n_source] A_s
+    double *face_area = nullptr;             // [n_tri]
+    double *power = nullptr;                 // [power_cols][n_source]
+    int power_cols = 0;
+};
 namespace padne { void sources_free(padne_ctx *ctx, padne_sources *sr); }
 
 struct padne_thermal {
@@ -114,6 +142,8 @@ std::vector<long long> thermal_tiles(const std::vector<int64_t> &off);
 // queued behind the face gather and the triples; PADNE_E_INVALID without powers for exactly n_cols columns.  Nothing
 // without sources
 int sources_add_load(padne_ctx *ctx, padne_thermal *th, int32_t n_cols, double *d_b);
+// sources.hip: padne_thermal_source_report's sums for any field[n_cols][n_pot] on the device, out_host[n_cols][n_source]
+int sources_report_field(padne_ctx *ctx, const padne_thermal *th, int32_t n_cols, const double *field, double *out_host);
 
 // transient.hip, for sdirk.hip.  transient_require: the handle is the context's.  transient_set_dt: S revalued for dt when
 // its bits differ from the held ones.  transient_check_cases: case_of_col[n_cols] checked and copied.  transient_opts: the

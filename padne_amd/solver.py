@@ -2262,6 +2262,18 @@ def thermal_heat_triples(pairs, flows_by_case) -> tuple:
     return np.asarray(node, dtype=np.int64), np.asarray(col, dtype=np.int32), np.asarray(val, dtype=DTYPE)
 
 
+def _layer_hotspot(board: IndexedBoard, ambient: float, mesh_max, mesh_vert, j: int, layer_i: int):
+    """``ThermalReport.hotspots[layer_i]`` of case ``j`` from the per-mesh maxima (k, n_mesh) of ``Thermal.report``: (T, mesh
+    index within the layer, vertex index, x, y), None for a layer without connected vertices."""
+    voff, best = board.vindex.offsets, None
+    for in_layer, (mesh_i, msh, _lo, _hi) in enumerate(board.layer_meshes(layer_i)):
+        # meshes come in global vertex order: a later mesh wins only with a strictly larger temperature
+        if mesh_vert[j, mesh_i] >= 0 and (best is None or mesh_max[j, mesh_i] + ambient > best[0]):
+            v = int(mesh_vert[j, mesh_i] - voff[mesh_i])
+            best = (float(mesh_max[j, mesh_i] + ambient), in_layer, v, float(msh.points[v][0]), float(msh.points[v][1]))
+    return best
+
+
 def _thermal_reports(board: IndexedBoard, checked: CheckedThermalModel, substituted, resistors, fields: bool, theta, mean,
                      mesh_max, mesh_vert, mesh_heat, mesh_loss, heat_val, infos, stack=None, sources=None) -> list:
     """The ThermalReports of k cases from what ``Thermal.report`` returns for them: ``theta`` (k, n_potential), ``mean`` (k,
@@ -2288,14 +2300,11 @@ def _thermal_reports(board: IndexedBoard, checked: CheckedThermalModel, substitu
                           if element_kind(e) == "Resistor"]
         temps, faces, hotspots, layers = [], [], [], []
         for layer_i in range(n_layers):
-            zfs, tfs, best, heat_in, loss = [], [], None, [], []
+            zfs, tfs, heat_in, loss = [], [], [], []
+            best = _layer_hotspot(board, ambient, mesh_max, mesh_vert, j, layer_i)
             for in_layer, (mesh_i, msh, lo, hi) in enumerate(board.layer_meshes(layer_i)):
                 heat_in.append(float(mesh_heat[j, mesh_i]))
                 loss.append(float(mesh_loss[j, mesh_i]))
-                # meshes come in global vertex order: a later mesh wins only with a strictly larger temperature
-                if mesh_vert[j, mesh_i] >= 0 and (best is None or mesh_max[j, mesh_i] + ambient > best[0]):
-                    v = int(mesh_vert[j, mesh_i] - voff[mesh_i])
-                    best = (float(mesh_max[j, mesh_i] + ambient), in_layer, v, float(msh.points[v][0]), float(msh.points[v][1]))
                 if fields:
                     zf, tf = mesh.ZeroForm(msh), mesh.TwoForm(msh)
                     zf.values = theta[j, voff[mesh_i]:voff[mesh_i + 1]] + ambient
@@ -2354,11 +2363,12 @@ def _thermal_envelope(board: IndexedBoard, ambient: float, env, env_case, report
 
 @contextlib.contextmanager
 def _thermal_block(prob, meshes, mesh_index_to_layer_index, checked: CheckedThermalModel, cases, filtered_networks,
-                   disconnected_meshes_by_layer, laps: _Laps, what: str):
+                   disconnected_meshes_by_layer, laps: _Laps, what: str, check=None):
     """What the steady and the transient thermal paths share: the checked ``cases`` of ``prob`` solved as one electrical block
     on the load-case path, the element flows of every case, and the ``_hip.Thermal`` handle of the checked model on top of
     the assembled system.  A context: inside it the system, the plan and the handle live on the device; the value is a
-    namespace of everything the two paths read.  On the way out the handle is closed and a stalled block is warned about."""
+    namespace of everything the two paths read.  On the way out the handle is closed and a stalled block is warned about.
+    ``check(board, pairs)``, if given, runs once the board is indexed and before anything reaches the device."""
     substituted = [substitute_load_case(prob, case) for case in cases]
     k = len(cases)
     source_power = _source_powers(checked.sources, k)
@@ -2368,6 +2378,8 @@ def _thermal_block(prob, meshes, mesh_index_to_layer_index, checked: CheckedTher
     if n_vert == 0 or not int(board.tri_offsets[-1]):
         raise ValueError("the thermal model needs connected copper: the board has no connected mesh with faces")
     pairs = global_elements(board.filtered_networks, board.node_indexer)
+    if check is not None:
+        check(board, pairs)
     laps.lap("indexing")
     layer_of = board.layer_of
     with board.assembled() as (L, _):
@@ -2391,7 +2403,7 @@ def _thermal_block(prob, meshes, mesh_index_to_layer_index, checked: CheckedTher
             yield types.SimpleNamespace(board=board, substituted=substituted, pairs=pairs, resistors=resistors, plan=plan, V=V,
                                         residual_norms=residual_norms, res=res, n_tri=n_tri, n_vert=n_vert,
                                         n_potential=n_potential, power=power, thermal=thermal, heat=heat, k=k, sources=sources,
-                                        source_power=source_power)
+                                        source_power=source_power, L=L)
         finally:
             thermal.close()
     laps.lap()
@@ -2405,11 +2417,14 @@ def _block_solutions(blk) -> list:
 
 
 def _solve_block_thermal(prob, meshes, mesh_index_to_layer_index, checked: CheckedThermalModel, cases, fields: bool,
-                         filtered_networks, disconnected_meshes_by_layer, laps: _Laps):
+                         filtered_networks, disconnected_meshes_by_layer, laps: _Laps, check=None, inside=None):
     """The checked ``cases`` of ``prob`` as one electrical block and one thermal block on top of it, for the checked model:
-    ([Solution], [ThermalReport], ThermalEnvelope).  ``fields``: with the per-case temperatures of vertices and faces."""
+    ([Solution], [ThermalReport], ThermalEnvelope).  ``fields``: with the per-case temperatures of vertices and faces.
+    ``check``: see :func:`_thermal_block`.  ``inside(blk, theta, mesh_max, mesh_vert, sources)``, if given, runs after the reports
+    have been read, while the block and the handle still live on the device; its value is returned as a fourth item."""
+    extra = None
     with _thermal_block(prob, meshes, mesh_index_to_layer_index, checked, cases, filtered_networks,
-                        disconnected_meshes_by_layer, laps, "temperatures") as blk:
+                        disconnected_meshes_by_layer, laps, "temperatures", check) as blk:
         k, heat = blk.k, blk.heat
         theta, tres = blk.thermal.solve_kkt(blk.plan, k, heat, rtol=RTOL, max_iter=MAX_ITER)
         laps.lap("thermal_solve")
@@ -2417,6 +2432,8 @@ def _solve_block_thermal(prob, meshes, mesh_index_to_layer_index, checked: Check
         stack = _stack_flows(blk.thermal, checked, k)
         sources = None if blk.sources is None else (blk.sources, blk.source_power, blk.thermal.source_report(k))
         laps.lap("thermal_report")
+        if inside is not None:
+            extra = inside(blk, theta, mesh_max, mesh_vert, sources)
     if tres.status != _hip.OK and not tres.rel_residual <= max(RTOL, STALL_WARN_ABOVE):
         warnings.warn(f"The thermal solve stopped at a relative residual of {tres.rel_residual:.3e}", SolverWarning)
     board = blk.board
@@ -2427,6 +2444,8 @@ def _solve_block_thermal(prob, meshes, mesh_index_to_layer_index, checked: Check
                                mesh_loss, heat_val, [info] * k, stack, sources)
     envelope = _thermal_envelope(board, checked.ambient, env, env_case, reports)
     laps.lap("solutions")
+    if inside is not None:
+        return solutions, reports, envelope, extra
     return solutions, reports, envelope
 
 
@@ -2495,6 +2514,333 @@ def solve_thermal(prob, model: ThermalModel, mesher_config: Optional[mesh.Mesher
         cases = check_load_cases(prob, cases)
     meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
     return solve_meshed_thermal(prob, meshes, mesh_index_to_layer_index, model, cases=cases, per_case_fields=per_case_fields)
+
+
+# --------------------------------------------------------------------------------------------
+# temperature sensitivities: what cools a hotspot (DESIGN.md "Temperature sensitivities")
+# --------------------------------------------------------------------------------------------
+
+MAX_TEMPERATURE_OBJECTIVES = 4096
+
+
+@dataclass(frozen=True)
+class TemperatureObjective:
+    """A temperature of one load case that :func:`solve_meshed_thermal_sensitivities` differentiates: a linear functional
+    T = ambient + g^T theta of the case's temperature rise.  Made by one of the three constructors."""
+    kind: str                      # "at", "source" or "hotspot"
+    layer: object = None           # the layer, its name, or (checked) its index
+    point: Optional[tuple] = None  # (x, y) of "at"
+    source: object = None          # the name or index of a heat source, or (checked) its index
+    case: int = 0
+
+    @classmethod
+    def at(cls, layer, point, case: int = 0) -> "TemperatureObjective":
+        """The temperature interpolated at ``point`` = (x, y) of ``layer``: the field sampler's owner face (the containing
+        face with the lowest global number) and its barycentric weights.  A point on no connected copper of the layer is a
+        ValueError of the solve."""
+        return cls("at", layer=layer, point=point, case=case)
+
+    @classmethod
+    def of_source(cls, source, case: int = 0) -> "TemperatureObjective":
+        """The footprint temperature of one of ``model.heat_sources`` (by name or index): the number
+        ``ThermalReport.sources[i]["temperature"]`` reports."""
+        return cls("source", source=source, case=case)
+
+    @classmethod
+    def hotspot(cls, layer, case: int = 0) -> "TemperatureObjective":
+        """The temperature at the vertex ``ThermalReport.hotspots[layer]`` names for that case, held fixed: the derivative
+        is that of this vertex's temperature, valid while the argmax does not move to another vertex."""
+        return cls("hotspot", layer=layer, case=case)
+
+
+@dataclass
+class ThermalSensitivity:
+    """Derivatives of one :class:`TemperatureObjective` (see :func:`solve_meshed_thermal_sensitivities`)."""
+    objective: TemperatureObjective
+    case: int
+    value: float          # the temperature, ambient included
+    electrical: list      # per layer, per mesh of LayerSolution.meshes: TwoForm of e_f / area_f, e_f = sigma dT/dsigma_f [K]
+    thermal: list         # likewise k_f / area_f, k_f = kappa dT/dkappa_f
+    copper: list          # likewise (e_f + k_f) / area_f: kelvin per relative thickening of the face, per area
+    layers: list          # per layer: {"electrical": sum e_f, "thermal": sum k_f, "copper": their sum, "film": h_l dT/dh_l}
+    interlayer: list      # per pair of model.interlayer: {"layers": (a, b), "value": g_p dT/dg_p}
+    sources: list         # per heat source: dT/dP_s [K/W] for the objective's case
+    elements: dict        # lumped element -> {field: dT/dfield}; a Resistor also "link": dT/dg_link
+
+
+def _resolve_layer(prob, layer, what: str) -> int:
+    if isinstance(layer, str):
+        found = [i for i, own in enumerate(prob.layers) if own.name == layer]
+    else:
+        found = [i for i, own in enumerate(prob.layers) if own is layer] or [i for i, own in enumerate(prob.layers) if own == layer]
+    if len(found) != 1:
+        raise ValueError(f"{what}: {layer!r} is no layer of the Problem" if not found else
+                         f"{what}: {layer!r} names {len(found)} layers of the Problem")
+    return found[0]
+
+
+def check_temperature_objectives(prob, model, objectives, n_cases, filtered_networks=None) -> list:
+    """The ``objectives`` resolved against ``prob`` and ``model`` as a list of :class:`TemperatureObjective` whose ``layer``
+    and ``source`` are indices, or ValueError: ``objectives`` is a non-empty sequence of at most 4096
+    :class:`TemperatureObjective`; a ``case`` is an integer in [0, n_cases); a layer is a layer of the Problem (itself or
+    its name); a point is two finite numbers; a source is the name or the index of one of ``model.heat_sources``.
+    ``filtered_networks`` is accepted for symmetry with the other checks: no objective depends on the networks."""
+    if isinstance(objectives, (Mapping, str, bytes, TemperatureObjective)):
+        raise ValueError("objectives must be a sequence of TemperatureObjective")
+    try:
+        objectives = list(objectives)
+    except TypeError:
+        raise ValueError("objectives must be a sequence of TemperatureObjective") from None
+    if not objectives:
+        raise ValueError("no objectives: give at least one TemperatureObjective")
+    if len(objectives) > MAX_TEMPERATURE_OBJECTIVES:
+        raise ValueError(f"{len(objectives)} objectives: at most {MAX_TEMPERATURE_OBJECTIVES} in one call")
+    names = [source.name for source in _check_heat_sources(prob, getattr(model, "heat_sources", None))]
+    out = []
+    for j, obj in enumerate(objectives):
+        if not isinstance(obj, TemperatureObjective):
+            raise ValueError(f"objective {j} is no TemperatureObjective but {obj!r}")
+        what = f"objective {j}"
+        if isinstance(obj.case, bool) or not isinstance(obj.case, (int, np.integer)) or not 0 <= int(obj.case) < int(n_cases):
+            raise ValueError(f"{what}: case {obj.case!r} is not one of the {int(n_cases)} load case(s)")
+        case = int(obj.case)
+        if obj.kind == "at":
+            layer = _resolve_layer(prob, obj.layer, what)
+            try:
+                x, y = (float(c) for c in obj.point)
+            except (TypeError, ValueError):
+                raise ValueError(f"{what}: the point must be a pair (x, y) of numbers, not {obj.point!r}") from None
+            if not (math.isfinite(x) and math.isfinite(y)):
+                raise ValueError(f"{what}: the point {obj.point!r} is not finite")
+            out.append(TemperatureObjective("at", layer=layer, point=(x, y), case=case))
+        elif obj.kind == "hotspot":
+            out.append(TemperatureObjective("hotspot", layer=_resolve_layer(prob, obj.layer, what), case=case))
+        elif obj.kind == "source":
+            key = obj.source
+            if isinstance(key, str):
+                found = [i for i, name in enumerate(names) if name == key]
+            elif isinstance(key, (int, np.integer)) and not isinstance(key, bool):
+                found = [int(key)] if 0 <= int(key) < len(names) else []
+            else:
+                found = []
+            if len(found) != 1:
+                raise ValueError(f"{what}: {key!r} is no heat source of the model" if not found else
+                                 f"{what}: {key!r} names {len(found)} heat sources of the model")
+            out.append(TemperatureObjective("source", source=found[0], case=case))
+        else:
+            raise ValueError(f"{what}: unknown kind {obj.kind!r}; use TemperatureObjective.at, .of_source or .hotspot")
+    return out
+
+
+def _refuse_gain_regulators(pairs) -> None:
+    """ValueError for a Problem whose :func:`woodbury_terms` is not empty: the electrical adjoint would need M^T."""
+    for element, row in pairs:
+        if woodbury_terms([row]):
+            raise ValueError(f"temperature sensitivities do not take a regulator with a gain term on distinct sense nodes "
+                             f"({element!r}): its stamps make the electrical system unsymmetric, and the adjoint through both "
+                             "physics is solved with the symmetric system only")
+
+
+def thermal_element_sensitivities(element_rows, x, mu, lam_at, theta, element_heat: bool) -> list:
+    """dT/dfield of every element row (global_elements' tuples on global unknowns) for the case's potentials ``x``, the
+    electrical adjoint ``mu``, the thermal adjoint at the resistors' terminals ``lam_at`` {unknown: lambda} and the case's
+    ``theta``: :func:`element_sensitivities` of (x, mu), and for a Resistor
+
+    - "resistance": with ``element_heat``, plus -((lambda_a + lambda_b) / 2) (x_a - x_b)^2 / R^2 -- its own dissipation,
+    - "link": dT/dg_link = -(lambda_a - lambda_b)(theta_a - theta_b)."""
+    out = element_sensitivities(element_rows, x, mu)
+    for row, d in zip(element_rows, out):
+        if row[0] == "R":
+            _, a, b, res = row
+            la, lb = lam_at[int(a)], lam_at[int(b)]
+            if element_heat:
+                dx = x[a] - x[b]
+                d["resistance"] = float(d["resistance"] - ((la + lb) / 2) * (dx * dx) / (res * res))
+            d["link"] = float(-(la - lb) * (theta[a] - theta[b]))
+    return out
+
+
+def _thermal_sensitivities_inside(checked: CheckedThermalModel, cases, objs, given, laps: _Laps):
+    """The pass of :func:`solve_meshed_thermal_sensitivities` that runs while the block lives on the device (the ``inside`` of
+    :func:`_solve_block_thermal`): adjoints, right-hand sides, block solve, finish, the face, vertex, pair and source
+    kernels, elements."""
+    def inside(blk, theta, mesh_max, mesh_vert, sources):
+        board, k, prob = blk.board, blk.k, blk.board.prob
+        n_mesh, layer_of, voff, n_obj = len(board.meshes), board.layer_of, board.vindex.offsets, len(objs)
+        case, kind, arg = [o.case for o in objs], [], []
+        xy, unknown, weight = np.zeros((n_obj, 2)), np.full((n_obj, 3), -1, dtype=np.int64), np.zeros((n_obj, 3))
+        spots = {}
+        for j, o in enumerate(objs):
+            if o.kind == "at":
+                kind.append(_hip.ThermalSensitivities.KIND_POINT)
+                arg.append(o.layer)
+                xy[j] = o.point
+            elif o.kind == "hotspot":
+                spot = _layer_hotspot(board, checked.ambient, mesh_max, mesh_vert, o.case, o.layer)
+                if spot is None:
+                    raise ValueError(f"objective {j}: layer {prob.layers[o.layer].name!r} has no connected vertices, so no hotspot")
+                spots[j] = spot
+                mesh_i = list(board.layer_meshes(o.layer))[spot[1]][0]
+                kind.append(_hip.ThermalSensitivities.KIND_UNKNOWNS)
+                arg.append(0)
+                unknown[j, 0], weight[j, 0] = voff[mesh_i] + spot[2], 1.0
+            else:
+                kind.append(_hip.ThermalSensitivities.KIND_SOURCE)
+                arg.append(o.source)
+        res_rows = [row for _, row in blk.resistors]
+        terminals = sorted({int(row[p]) for row in res_rows for p in (1, 2)})
+        ts = _hip.ThermalSensitivities(blk.thermal, blk.plan, k, [checked.kappa[layer_of[i]] for i in range(n_mesh)])
+        try:
+            try:
+                unknown, weight, lam_p, lres = ts.thermal_adjoints(case, kind, arg, xy, unknown, weight,
+                                                                   [layer_of[i] for i in range(n_mesh)], terminals,
+                                                                   rtol=RTOL, max_iter=MAX_ITER)
+            except ValueError as exc:
+                if "lies on no face" not in str(exc):
+                    raise
+                j = int(str(exc).split("objective ")[1].split(":")[0])       # the lowest such objective, named by the device
+                raise ValueError(f"objective {j} ({given[j]!r}): the point {objs[j].point} lies on no connected copper of layer "
+                                 f"{prob.layers[objs[j].layer].name!r}") from None
+            laps.lap("thermal_adjoints")
+            heat_rows = res_rows if checked.element_heat else []
+            r_dev = ts.electrical_rhs([row[1] for row in heat_rows], [row[2] for row in heat_rows], [row[3] for row in heat_rows])
+            laps.lap("electrical_rhs")
+            # M^T mu = c through the plan, like the adjoints of solve_meshed_sensitivities: the known values are zero
+            none = (np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=DTYPE))
+            red, known_idx, known_val = block_plan_inputs(blk.L, *none, n_obj)
+            members = red.probe_members
+            probes, ares = blk.plan.solve_block_dev(n_obj, r_dev, known_idx, known_val, red.regulator_columns, members, rtol=RTOL,
+                                                    max_iter=MAX_ITER, abs_residual_target=ABS_RESIDUAL_TARGET)
+            laps.lap("adjoint_stage1")
+            MU, _mu_norms = _finish_block(blk.plan, red, members, probes, n_obj)
+            laps.lap("adjoint_stage2")
+            e_d, k_d, c_d, mesh_e, mesh_k = ts.faces(blk.n_tri, n_mesh)
+            mesh_film = ts.vertices(n_mesh)
+            pair_v = ts.pairs() if checked.interlayer else None
+            source_v = ts.sources() if blk.sources is not None else None
+            laps.lap("sensitivity_kernels")
+        finally:
+            ts.close()
+        for what, res in (("thermal", lres), ("electrical", ares)):
+            if res.status != _hip.OK and not res.rel_residual <= max(RTOL, STALL_WARN_ABOVE):
+                warnings.warn(f"The {what} adjoint solve stopped at a relative residual of {res.rel_residual:.3e}", SolverWarning)
+        if laps.timings is not None:        # what the two adjoint solves spent on multigrid setups: 0.0 on hierarchies that exist
+            laps.timings["adjoint_setup_seconds"] = float(lres.setup_seconds + ares.setup_seconds)
+        lam_at = [dict(zip(terminals, lam_p[j].tolist())) for j in range(n_obj)]
+        all_rows = [row for _, row in blk.pairs]
+        out = []
+        for j, o in enumerate(objs):
+            c = o.case
+            if o.kind == "at":
+                value = float(checked.ambient + sum(weight[j, q] * theta[c, unknown[j, q]] for q in range(3)))
+            elif o.kind == "hotspot":
+                value = spots[j][0]
+            else:
+                value = float(checked.ambient + sources[2][c, o.source])
+            forms = {"electrical": [], "thermal": [], "copper": []}
+            layers = []
+            for layer_i in range(len(prob.layers)):
+                per = {name: [] for name in forms}
+                tot_e, tot_k, film = [], [], []
+                for mesh_i, msh, lo, hi in board.layer_meshes(layer_i):
+                    for name, dens in (("electrical", e_d), ("thermal", k_d), ("copper", c_d)):
+                        tf = mesh.TwoForm(msh)
+                        tf.values = np.array(dens[j, lo:hi], dtype=DTYPE)
+                        per[name].append(tf)
+                    tot_e.append(float(mesh_e[j, mesh_i]))
+                    tot_k.append(float(mesh_k[j, mesh_i]))
+                    film.append(float(mesh_film[j, mesh_i]))
+                for name in forms:
+                    forms[name].append(per[name])
+                se, sk = math.fsum(tot_e), math.fsum(tot_k)
+                layers.append({"electrical": se, "thermal": sk, "copper": se + sk, "film": math.fsum(film)})
+            interlayer = [] if pair_v is None else [{"layers": (a, b), "value": float(pair_v[j, p])}
+                                                    for p, (a, b, _g) in enumerate(checked.interlayer)]
+            rows_c = _case_element_rows(blk.pairs, all_rows, cases[c])
+            per_element = thermal_element_sensitivities(rows_c, blk.V[:, c], MU[:, j], lam_at[j], theta[c], checked.element_heat)
+            out.append(ThermalSensitivity(
+                objective=given[j], case=c, value=value, electrical=forms["electrical"], thermal=forms["thermal"],
+                copper=forms["copper"], layers=layers, interlayer=interlayer,
+                sources=[] if source_v is None else [float(v) for v in source_v[j]],
+                elements={element: per_element[i] for i, (element, _) in enumerate(blk.pairs)}))
+        laps.lap("sensitivities")
+        return out
+    return inside
+
+
+def solve_meshed_thermal_sensitivities(prob, meshes, mesh_index_to_layer_index, model: ThermalModel, objectives, *, cases=None,
+                                       filtered_networks=None, disconnected_meshes_by_layer=None, partition=None,
+                                       timings: Optional[dict] = None):
+    """``solve_meshed_thermal`` together with what every parameter does to chosen temperatures: ``(Solution, ThermalReport,
+    [ThermalSensitivity])``, or for a list of load ``cases`` ``([Solution], [ThermalReport], ThermalEnvelope,
+    [ThermalSensitivity])``, one :class:`ThermalSensitivity` per objective in the order given.  The first items carry the
+    bits ``solve_meshed_thermal`` returns for the same arguments.
+
+    An objective (:class:`TemperatureObjective`) is a linear functional T = ambient + g^T theta of one load case: the
+    temperature at a point, the footprint temperature of a heat source, or the temperature at the case's hotspot vertex of a
+    layer, held fixed (valid while the argmax does not move).  With M x = r the electrical system and A theta = b(x) the
+    thermal one (DESIGN.md "Temperature sensitivities"), two adjoints carry the chain through both physics:
+
+        A lambda = g,    M^T mu = grad_x (lambda^T b(x)),    dT/dp = lambda^T (db/dp - dA/dp theta) + mu^T (dr/dp - dM/dp x)
+
+    - ``electrical``: e_f = sigma dT/dsigma_f = lbar_f P_f + sigma sum_edges w_ik (mu_i - mu_k)(x_i - x_k) per face, as a
+      density e_f / area_f: what the face's electrical conductance does through the Joule heat (lbar_f the mean of lambda at
+      the face's corners, P_f its Joule power);
+    - ``thermal``: k_f = kappa dT/dkappa_f = -kappa sum_edges w_ik (lambda_i - lambda_k)(theta_i - theta_k): what its thermal
+      conductance does by spreading the heat;
+    - ``copper``: e_f + k_f, kelvin per relative thickening of the face, since both conductances are proportional to
+      thickness; ``layers[l]`` holds the three sums over the layer and ``"film"`` = h_l dT/dh_l;
+    - ``interlayer``: g_p dT/dg_p of every pair; ``sources``: dT/dP_s [K/W]; ``elements``: {field: dT/dfield} with the fields
+      of ``SENSITIVITY_FIELDS``, and for a Resistor also ``"link"``: dT/dg_link.
+
+    All derivatives are partial derivatives with respect to the parameters of the *checked* model: kappa does not move with
+    sigma through the Wiedemann-Franz default, and a link conductance does not move with R.  The call costs one
+    ``solve_meshed_thermal`` plus one thermal and one electrical adjoint column per objective, on hierarchies the forward
+    solves have built; every adjoint right-hand side is formed on the device.
+
+    ValueError, before anything reaches the device, for what ``solve_meshed_thermal`` refuses, for invalid objectives
+    (:func:`check_temperature_objectives`, more than 4096 among them), a ``partition`` over several GPUs, a model that is no
+    ThermalModel (the electro-thermal and the transient models are not accepted: the resistivity feedback and the time
+    stepping change the adjoint system), and a Problem with a regulator whose gain term acts on distinct sense nodes
+    (:func:`woodbury_terms` not empty; the message names it).  ValueError of the solve for a point on no connected copper of
+    its layer and a hotspot on a layer without connected vertices, naming the objective.  ``timings`` (a dict) receives the
+    host time of each step in seconds, and ``"adjoint_setup_seconds"``: what the two adjoint solves spent building multigrid
+    hierarchies, 0.0 when those of the forward solves were reused."""
+    _refuse_partition(partition, "temperature sensitivities")
+    if not isinstance(model, ThermalModel):
+        raise ValueError("temperature sensitivities take a ThermalModel: the electro-thermal and the transient models are not "
+                         f"accepted, not {type(model).__name__}")
+    checked = check_thermal_model(prob, model, filtered_networks)
+    single = cases is None
+    checked_cases = [{}] if single else check_load_cases(prob, cases)
+    given = objectives
+    if hasattr(objectives, "__iter__") and not isinstance(objectives, (Mapping, str, bytes, TemperatureObjective)):
+        given = list(objectives)                     # (an iterator is read once)
+    objs = check_temperature_objectives(prob, model, given, len(checked_cases), filtered_networks)
+    laps = _Laps(timings)
+    solutions, reports, envelope, sens = _solve_block_thermal(
+        prob, meshes, mesh_index_to_layer_index, checked, checked_cases, True, filtered_networks, disconnected_meshes_by_layer, laps,
+        check=lambda board, pairs: _refuse_gain_regulators(pairs),
+        inside=_thermal_sensitivities_inside(checked, checked_cases, objs, given, laps))
+    if single:
+        return solutions[0], reports[0], sens
+    return solutions, reports, envelope, sens
+
+
+def solve_thermal_sensitivities(prob, model: ThermalModel, objectives, mesher_config: Optional[mesh.Mesher.Config] = None, *,
+                                mesher=None, cases=None, partition=None):
+    """``solve`` with the temperatures and their sensitivities (see :func:`solve_meshed_thermal_sensitivities`): the board is
+    meshed once."""
+    _refuse_partition(partition, "temperature sensitivities")
+    if not isinstance(model, ThermalModel):
+        raise ValueError("temperature sensitivities take a ThermalModel: the electro-thermal and the transient models are not "
+                         f"accepted, not {type(model).__name__}")
+    check_thermal_model(prob, model)
+    if cases is not None:
+        cases = check_load_cases(prob, cases)
+    check_temperature_objectives(prob, model, objectives, 1 if cases is None else len(cases))
+    meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
+    return solve_meshed_thermal_sensitivities(prob, meshes, mesh_index_to_layer_index, model, objectives, cases=cases)
 
 
 # --------------------------------------------------------------------------------------------
