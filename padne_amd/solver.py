@@ -2262,16 +2262,29 @@ def thermal_heat_triples(pairs, flows_by_case) -> tuple:
     return np.asarray(node, dtype=np.int64), np.asarray(col, dtype=np.int32), np.asarray(val, dtype=DTYPE)
 
 
-def _layer_hotspot(board: IndexedBoard, ambient: float, mesh_max, mesh_vert, j: int, layer_i: int):
+def _layer_hotspot(board: IndexedBoard, ambient: float, mesh_max, mesh_vert, j: int, layer_i: int, layer_meshes=None):
     """``ThermalReport.hotspots[layer_i]`` of case ``j`` from the per-mesh maxima (k, n_mesh) of ``Thermal.report``: (T, mesh
-    index within the layer, vertex index, x, y), None for a layer without connected vertices."""
+    index within the layer, vertex index, x, y), None for a layer without connected vertices.  ``layer_meshes``: the list of
+    ``board.layer_meshes(layer_i)``, for a caller that asks row after row."""
     voff, best = board.vindex.offsets, None
-    for in_layer, (mesh_i, msh, _lo, _hi) in enumerate(board.layer_meshes(layer_i)):
+    for in_layer, (mesh_i, msh, _lo, _hi) in enumerate(board.layer_meshes(layer_i) if layer_meshes is None else layer_meshes):
         # meshes come in global vertex order: a later mesh wins only with a strictly larger temperature
         if mesh_vert[j, mesh_i] >= 0 and (best is None or mesh_max[j, mesh_i] + ambient > best[0]):
             v = int(mesh_vert[j, mesh_i] - voff[mesh_i])
             best = (float(mesh_max[j, mesh_i] + ambient), in_layer, v, float(msh.points[v][0]), float(msh.points[v][1]))
     return best
+
+
+def _cold_temperatures(board: IndexedBoard, ambient: float) -> list:
+    """Per layer, per disconnected mesh: a ZeroForm filled with the ambient temperature."""
+    cold = [[] for _ in board.prob.layers]
+    for layer_i, out in enumerate(cold):
+        for msh in board.disconnected_meshes_by_layer[layer_i]:
+            msh = msh if isinstance(msh, mesh.Mesh) else mesh.Mesh.from_reference(msh)
+            zf = mesh.ZeroForm(msh)
+            zf.values = np.full(len(msh.vertices), ambient, dtype=DTYPE)
+            out.append(zf)
+    return cold
 
 
 def _thermal_reports(board: IndexedBoard, checked: CheckedThermalModel, substituted, resistors, fields: bool, theta, mean,
@@ -2284,16 +2297,6 @@ def _thermal_reports(board: IndexedBoard, checked: CheckedThermalModel, substitu
     :func:`_attach_heat_sources` returned, powers (k, n_source), footprint temperatures above ambient (k, n_source)) of the
     model's ``heat_sources``, or None without."""
     ambient, voff, n_layers = checked.ambient, board.vindex.offsets, len(board.prob.layers)
-
-    def cold(layer_i):
-        out = []
-        for msh in board.disconnected_meshes_by_layer[layer_i]:
-            msh = msh if isinstance(msh, mesh.Mesh) else mesh.Mesh.from_reference(msh)
-            zf = mesh.ZeroForm(msh)
-            zf.values = np.full(len(msh.vertices), ambient, dtype=DTYPE)
-            out.append(zf)
-        return out
-
     reports = []
     for j, (_, renamed) in enumerate(substituted):
         case_resistors = [e for network in board.filtered_networks for e in renamed.get(id(network), network).elements
@@ -2331,7 +2334,7 @@ def _thermal_reports(board: IndexedBoard, checked: CheckedThermalModel, substitu
             total_heat = total_heat + source_heat
         reports.append(ThermalReport(
             temperatures=temps if fields else None, face_temperatures=faces if fields else None,
-            disconnected_temperatures=[cold(layer_i) for layer_i in range(n_layers)], hotspots=hotspots, layers=layers,
+            disconnected_temperatures=_cold_temperatures(board, ambient), hotspots=hotspots, layers=layers,
             elements=elements, total_heat=total_heat,
             total_loss=math.fsum(layer["loss"] for layer in layers), info=infos[j], interlayer=interlayer, sources=entries,
             source_heat=source_heat))
@@ -2361,14 +2364,12 @@ def _thermal_envelope(board: IndexedBoard, ambient: float, env, env_case, report
     return ThermalEnvelope(temperatures=env_temps, cases=env_cases, hotspots=env_hotspots)
 
 
-@contextlib.contextmanager
-def _thermal_block(prob, meshes, mesh_index_to_layer_index, checked: CheckedThermalModel, cases, filtered_networks,
-                   disconnected_meshes_by_layer, laps: _Laps, what: str, check=None):
-    """What the steady and the transient thermal paths share: the checked ``cases`` of ``prob`` solved as one electrical block
-    on the load-case path, the element flows of every case, and the ``_hip.Thermal`` handle of the checked model on top of
-    the assembled system.  A context: inside it the system, the plan and the handle live on the device; the value is a
-    namespace of everything the two paths read.  On the way out the handle is closed and a stalled block is warned about.
-    ``check(board, pairs)``, if given, runs once the board is indexed and before anything reaches the device."""
+def _thermal_board(prob, meshes, mesh_index_to_layer_index, checked: CheckedThermalModel, cases, filtered_networks,
+                   disconnected_meshes_by_layer, check=None) -> tuple:
+    """What every thermal call does before anything reaches the device: (the indexed board, its ``global_elements`` pairs,
+    ``substitute_load_case`` of every case, the heat sources' powers (k, n_source) or None, the number of vertices, k).
+    ValueError for powers that are not one per case, a vertex without a face and a board without connected copper.
+    ``check(board, pairs)``, if given, runs last."""
     substituted = [substitute_load_case(prob, case) for case in cases]
     k = len(cases)
     source_power = _source_powers(checked.sources, k)
@@ -2380,6 +2381,19 @@ def _thermal_block(prob, meshes, mesh_index_to_layer_index, checked: CheckedTher
     pairs = global_elements(board.filtered_networks, board.node_indexer)
     if check is not None:
         check(board, pairs)
+    return board, pairs, substituted, source_power, n_vert, k
+
+
+@contextlib.contextmanager
+def _thermal_block(prob, meshes, mesh_index_to_layer_index, checked: CheckedThermalModel, cases, filtered_networks,
+                   disconnected_meshes_by_layer, laps: _Laps, what: str, check=None):
+    """What the steady and the transient thermal paths share: the checked ``cases`` of ``prob`` solved as one electrical block
+    on the load-case path, the element flows of every case, and the ``_hip.Thermal`` handle of the checked model on top of
+    the assembled system.  A context: inside it the system, the plan and the handle live on the device; the value is a
+    namespace of everything the two paths read.  On the way out the handle is closed and a stalled block is warned about.
+    ``check``: see :func:`_thermal_board`."""
+    board, pairs, substituted, source_power, n_vert, k = _thermal_board(
+        prob, meshes, mesh_index_to_layer_index, checked, cases, filtered_networks, disconnected_meshes_by_layer, check)
     laps.lap("indexing")
     layer_of = board.layer_of
     with board.assembled() as (L, _):
@@ -2956,6 +2970,36 @@ def check_transient_model(prob, model, filtered_networks=None) -> CheckedTransie
     return CheckedTransientModel(thermal=thermal, capacity=capacity, initial=model.initial)
 
 
+def _check_entries(schedule, n_cases: int, repeat, kind, more=None) -> tuple:
+    """What :func:`check_schedule` and :func:`check_spans` share: (the checked entries of the sequence ``schedule`` of ``kind``
+    -- Segment or Span --, the number of scenarios), or ValueError.  ``more(i, entry)`` checks and returns the fields of entry
+    ``i`` beyond ``duration`` and ``case``."""
+    name, lower = kind.__name__, kind.__name__.lower()
+    if isinstance(repeat, bool) or not isinstance(repeat, (int, np.integer)) or repeat < 1:
+        raise ValueError(f"repeat must be an integer >= 1, not {repeat!r}")
+    if isinstance(schedule, (Span, Segment, Mapping, str, bytes)):
+        raise ValueError(f"the schedule must be a sequence of {name}s")
+    try:
+        schedule = list(schedule)
+    except TypeError:
+        raise ValueError(f"the schedule must be a sequence of {name}s") from None
+    if not schedule:
+        raise ValueError(f"an empty schedule: give at least one {name}")
+    checked, n_scen = [], None
+    for i, entry in enumerate(schedule):
+        if not isinstance(entry, kind):
+            raise ValueError(f"{lower} {i} is not a {name}")
+        duration = _positive_number(entry.duration, f"the duration of {lower} {i}")
+        fields = more(i, entry) if more is not None else {}
+        case = _scenario_entries(entry.case, n_cases, f"the case of {lower} {i}")
+        if isinstance(case, tuple):
+            if n_scen is not None and len(case) != n_scen:
+                raise ValueError(f"{lower} {i} names {len(case)} scenarios, an earlier one {n_scen}")
+            n_scen = len(case)
+        checked.append(kind(duration=duration, case=case, **fields))
+    return checked, (1 if n_scen is None else n_scen)
+
+
 def check_schedule(schedule, n_cases: int, repeat=1) -> tuple:
     """(the flattened segments, the number of scenarios) of a schedule, or ValueError.
 
@@ -2965,33 +3009,16 @@ def check_schedule(schedule, n_cases: int, repeat=1) -> tuple:
     scenarios (1 without tuples), and tuples come back as tuples.  Refused: an empty schedule, a duration that is not finite
     and positive, ``steps`` that is not an integer >= 1, a case out of range, tuples of unequal length, ``repeat < 1`` and
     more than 100 000 steps in total."""
-    if isinstance(repeat, bool) or not isinstance(repeat, (int, np.integer)) or repeat < 1:
-        raise ValueError(f"repeat must be an integer >= 1, not {repeat!r}")
-    if isinstance(schedule, (Segment, Mapping, str, bytes)):
-        raise ValueError("the schedule must be a sequence of Segments")
-    try:
-        schedule = list(schedule)
-    except TypeError:
-        raise ValueError("the schedule must be a sequence of Segments") from None
-    if not schedule:
-        raise ValueError("an empty schedule: give at least one Segment")
-    checked, n_scen = [], None
-    for i, seg in enumerate(schedule):
-        if not isinstance(seg, Segment):
-            raise ValueError(f"segment {i} is not a Segment")
-        duration = _positive_number(seg.duration, f"the duration of segment {i}")
+    def steps_of(i, seg):
         if isinstance(seg.steps, bool) or not isinstance(seg.steps, (int, np.integer)) or seg.steps < 1:
             raise ValueError(f"the steps of segment {i} must be an integer >= 1, not {seg.steps!r}")
-        case = _scenario_entries(seg.case, n_cases, f"the case of segment {i}")
-        if isinstance(case, tuple):
-            if n_scen is not None and len(case) != n_scen:
-                raise ValueError(f"segment {i} names {len(case)} scenarios, an earlier one {n_scen}")
-            n_scen = len(case)
-        checked.append(Segment(duration=duration, steps=int(seg.steps), case=case))
+        return {"steps": int(seg.steps)}
+
+    checked, n_scen = _check_entries(schedule, n_cases, repeat, Segment, steps_of)
     total = int(repeat) * sum(seg.steps for seg in checked)
     if total > MAX_TRANSIENT_STEPS:
         raise ValueError(f"{total} steps in total: more than {MAX_TRANSIENT_STEPS}")
-    return [dataclasses.replace(seg) for _ in range(int(repeat)) for seg in checked], (1 if n_scen is None else n_scen)
+    return [dataclasses.replace(seg) for _ in range(int(repeat)) for seg in checked], n_scen
 
 
 def check_probes(prob, probes, filtered_networks=None) -> list:
@@ -3013,25 +3040,46 @@ def check_probes(prob, probes, filtered_networks=None) -> list:
     return probes
 
 
+def _check_transient_call(prob, initial, schedule, cases, repeat, probes, keep, filtered_networks, check_entries, entry_of,
+                          scenarios=True, sources=(), extra=None) -> tuple:
+    """The checks the three transient calls share, in the order in which they refuse: (checked cases, per flattened entry
+    ``entry_of(entry, per-scenario cases)``, per-scenario initial cases, probes, the value of ``extra``).  ``check_entries``
+    is :func:`check_schedule` or :func:`check_spans`; ``initial`` and every entry's case are broadcast to the scenarios.
+    Without ``scenarios`` the tuple form of a case is refused, and cases and ``initial`` come back as they are; ``sources``
+    are checked heat sources whose powers must be one per case.  ``extra()`` holds a call's own checks, which come after
+    ``keep`` and before the probes."""
+    checked_cases = [{}] if cases is None else check_load_cases(prob, cases)
+    entries, n_scen = check_entries(schedule, len(checked_cases), repeat)
+    tuples = any(isinstance(entry.case, tuple) for entry in entries)
+    if not scenarios:
+        if tuples:
+            raise ValueError(f"the case of a segment: {_NO_SCENARIOS}")
+        initial = _case_entry(initial, len(checked_cases), "initial")
+        flat = [entry_of(entry, entry.case) for entry in entries]
+    else:
+        initial = _scenario_entries(initial, len(checked_cases), "initial")
+        if isinstance(initial, tuple):
+            if tuples and len(initial) != n_scen:
+                raise ValueError(f"initial names {len(initial)} scenarios, the schedule {n_scen}")
+            n_scen = len(initial)
+        else:
+            initial = (initial,) * n_scen
+        flat = [entry_of(entry, entry.case if isinstance(entry.case, tuple) else (entry.case,) * n_scen) for entry in entries]
+    _source_powers(sources, len(checked_cases))
+    if keep not in ("end", "segments", "none"):
+        raise ValueError(f'keep must be "end", "segments" or "none", not {keep!r}')
+    own = extra() if extra is not None else None
+    return checked_cases, flat, initial, check_probes(prob, probes, filtered_networks), own
+
+
 def _check_transient_arguments(prob, model, schedule, cases, repeat, probes, keep, filtered_networks):
     """Every check of :func:`solve_meshed_thermal_transient`: (checked model, checked cases, per flattened segment (dt, steps,
     per-scenario cases), per-scenario initial cases, probes)."""
     checked = check_transient_model(prob, model, filtered_networks)
-    checked_cases = [{}] if cases is None else check_load_cases(prob, cases)
-    segments, n_scen = check_schedule(schedule, len(checked_cases), repeat)
-    tuples = any(isinstance(seg.case, tuple) for seg in segments)
-    initial = _scenario_entries(checked.initial, len(checked_cases), "initial")
-    if isinstance(initial, tuple):
-        if tuples and len(initial) != n_scen:
-            raise ValueError(f"initial names {len(initial)} scenarios, the schedule {n_scen}")
-        n_scen = len(initial)
-    else:
-        initial = (initial,) * n_scen
-    flat = [(seg.duration / seg.steps, seg.steps, seg.case if isinstance(seg.case, tuple) else (seg.case,) * n_scen)
-            for seg in segments]
-    if keep not in ("end", "segments", "none"):
-        raise ValueError(f'keep must be "end", "segments" or "none", not {keep!r}')
-    return checked, checked_cases, flat, initial, check_probes(prob, probes, filtered_networks)
+    checked_cases, flat, initial, probe_nodes, _ = _check_transient_call(
+        prob, checked.initial, schedule, cases, repeat, probes, keep, filtered_networks, check_schedule,
+        lambda seg, seg_cases: (seg.duration / seg.steps, seg.steps, seg_cases))
+    return checked, checked_cases, flat, initial, probe_nodes
 
 
 def _snapshot(board: IndexedBoard, ambient: float, theta: np.ndarray) -> tuple:
@@ -3061,15 +3109,8 @@ def _transient_report(board: IndexedBoard, ambient: float, times, mesh_max, mesh
     hotspots, layers, env_temps, env_times, env_spots, peak = [], [], [], [], [], None
     for layer_i in range(n_layers):
         in_layer = list(board.layer_meshes(layer_i))
-        spots = []
-        for n in range(n_times):
-            best = None
-            for at, (mesh_i, msh, _lo, _hi) in enumerate(in_layer):
-                # meshes come in global vertex order: a later mesh wins only with a strictly larger temperature
-                if mesh_vert[n, mesh_i] >= 0 and (best is None or mesh_max[n, mesh_i] + ambient > best[0]):
-                    v = int(mesh_vert[n, mesh_i] - voff[mesh_i])
-                    best = (float(mesh_max[n, mesh_i] + ambient), at, v, float(msh.points[v][0]), float(msh.points[v][1]))
-            spots.append(best)
+        spots = [_layer_hotspot(board, ambient, mesh_max, mesh_vert, n, layer_i, in_layer) for n in range(n_times)]
+        for n, best in enumerate(spots):
             if best is not None and (peak is None or best[0] > peak[0]):      # the first time, then the lowest layer
                 peak = (best[0], float(times[n]), layer_i, *best[1:])
         hotspots.append(spots)
@@ -3091,15 +3132,6 @@ def _transient_report(board: IndexedBoard, ambient: float, times, mesh_max, mesh
         env_temps.append(zfs)
         env_times.append(whens)
         env_spots.append(spot)
-    cold = []
-    for layer_i in range(n_layers):
-        out = []
-        for msh in board.disconnected_meshes_by_layer[layer_i]:
-            msh = msh if isinstance(msh, mesh.Mesh) else mesh.Mesh.from_reference(msh)
-            zf = mesh.ZeroForm(msh)
-            zf.values = np.full(len(msh.vertices), ambient, dtype=DTYPE)
-            out.append(zf)
-        cold.append(out)
     fields = [_snapshot(board, ambient, theta) for _, theta in snapshots]
     return TransientReport(
         times=np.asarray(times, dtype=DTYPE), hotspots=hotspots, layers=layers,
@@ -3108,7 +3140,101 @@ def _transient_report(board: IndexedBoard, ambient: float, times, mesh_max, mesh
         probes={node: trace + ambient for node, trace in probes.items()}, peak=peak,
         envelope=TransientEnvelope(temperatures=env_temps, times=env_times, hotspots=env_spots),
         snapshot_times=[t for t, _ in snapshots], temperatures=[f[0] for f in fields], face_temperatures=[f[1] for f in fields],
-        disconnected_temperatures=cold, info=info)
+        disconnected_temperatures=_cold_temperatures(board, ambient), info=info)
+
+
+def _worse(worst: float, result) -> float:
+    """``worst``, or the relative residual of a solve that ended above the tolerance if that is larger."""
+    return max(worst, float(result.rel_residual)) if result.status != _hip.OK else worst
+
+
+def _transient_head(transient, first, probe_idx) -> dict:
+    """Time 0 in the form in which ``Transient.run`` records steps: ``max``, ``vertex``, ``stored`` and ``loss`` (1, n_scen,
+    n_mesh) and ``probes`` (1, n_scen, n_probe) of the state ``Transient.start`` left; ``result``: ``first``, the SolveResult
+    of that start, and ``worst``: what :func:`_worse` starts from."""
+    top, vert, stored, loss = transient.report()
+    probes = transient.state()[:, probe_idx] if probe_idx else np.empty((top.shape[0], 0), dtype=DTYPE)
+    return {"max": top[None], "vertex": vert[None], "stored": stored[None], "loss": loss[None], "probes": probes[None],
+            "result": first, "worst": first.rel_residual if first.status != _hip.OK else 0.0}
+
+
+def _transient_end(transient, n_vert: int, laps: _Laps) -> tuple:
+    """Once the steps are taken: (the envelope of theta (n_scen, n_vert), the step of each maximum, the hierarchies built)."""
+    env, env_step = transient.envelope(n_vert)
+    _steps, _time, hierarchies = transient.clock()
+    laps.lap("transient_run")
+    return env, env_step, hierarchies
+
+
+@contextlib.contextmanager
+def _transient_session(prob, meshes, mesh_index_to_layer_index, checked: CheckedTransientModel, cases, initial, probe_nodes,
+                       filtered_networks, disconnected_meshes_by_layer, laps: _Laps):
+    """What the two one-way transient calls do before they step, as a context: the :func:`_thermal_block` of the cases, the
+    Joule heat of every mesh, the ``_hip.Transient`` with the cases' loads, and the start from ``initial``.  The value is a
+    namespace: ``blk``, ``transient``, ``mesh_power`` (k, n_mesh), ``probe_idx`` (the probes' unknowns) and ``head``
+    (:func:`_transient_head`).  On the way out the transient handle is closed, then the block."""
+    with _thermal_block(prob, meshes, mesh_index_to_layer_index, checked.thermal, cases, filtered_networks,
+                        disconnected_meshes_by_layer, laps, "temperatures over time") as blk:
+        board, layer_of = blk.board, blk.board.layer_of
+        # the Joule heat of every mesh's copper, per case: the sum current_cases forms of the same face powers
+        *_, mesh_power, _cuts = blk.plan.current_cases(blk.k, blk.n_tri, np.asarray(layer_of, dtype=np.int32), [], np.zeros((0, 4)),
+                                                       fields=False, envelope=False)
+        transient = _hip.Transient(blk.thermal, [checked.capacity[layer_of[i]] for i in range(len(board.meshes))])
+        try:
+            transient.loads_kkt(blk.plan, blk.k, blk.heat)
+            first = transient.start(initial, rtol=RTOL, max_iter=MAX_ITER)
+            laps.lap("transient_start")
+            probe_idx = [board.node_indexer.node_to_global_index[node] for node in probe_nodes]
+            yield types.SimpleNamespace(blk=blk, transient=transient, mesh_power=mesh_power, probe_idx=probe_idx,
+                                        head=_transient_head(transient, first, probe_idx))
+        finally:
+            transient.close()
+
+
+def _case_heats(blk, mesh_power, led) -> list:
+    """Per scenario (the Joule heat of every layer over time, the total heat over time) of a :func:`_thermal_block` whose
+    meshes dissipate ``mesh_power`` (k, n_mesh).  ``led``: per time, the case of every scenario that led there -- the
+    initial case at the start (its steady state balances it), then each step's; None = no heat."""
+    k, heat, layer_of = blk.k, blk.heat, blk.board.layer_of
+    n_mesh, n_layers = len(blk.board.meshes), len(blk.board.prob.layers)
+    case_layer_heat = [[math.fsum(float(mesh_power[j, i]) for i in range(n_mesh) if layer_of[i] == layer_i)
+                        for layer_i in range(n_layers)] for j in range(k)]
+    element_heat = [math.fsum(heat[2][heat[1] == j].tolist()) if heat is not None else 0.0 for j in range(k)]
+    case_total = [math.fsum(case_layer_heat[j] + [element_heat[j]]) for j in range(k)]
+    if blk.sources is not None:                              # the load table's column j carries the sources of case j
+        case_total = [case_total[j] + math.fsum(blk.source_power[j].tolist()) for j in range(k)]
+    heats = []
+    for c in range(len(led[0])):
+        on = [at_time[c] for at_time in led]
+        heats.append(([[0.0 if j is None else case_layer_heat[j][layer_i] for j in on] for layer_i in range(n_layers)],
+                      [0.0 if j is None else case_total[j] for j in on]))
+    return heats
+
+
+def _transient_reports(board: IndexedBoard, ambient: float, times, head: dict, records, heats, probe_nodes, end, snapshots,
+                       worst: float) -> tuple:
+    """([TransientReport] per scenario, the ``info`` they share) of a transient run.  ``records``: the steps in order, in
+    lots as ``Transient.run`` returns them -- ``max``, ``vertex``, ``stored``, ``loss`` (steps, n_scen, n_mesh), ``probes``
+    (steps, n_scen, n_probe), ``iterations``, ``seconds``, ``setup_seconds`` and ``rel_residual`` (steps,) -- after ``head``
+    (:func:`_transient_head`).  ``heats``: per scenario (the layers' heats, the total heat) that led to every time;
+    ``end``: :func:`_transient_end`; ``snapshots``: [(time, theta (n_scen, n_potential))].  Warns when ``worst``, the largest
+    relative residual of a step that ended above the tolerance, is worth it."""
+    if worst > max(RTOL, STALL_WARN_ABOVE):
+        warnings.warn(f"A step of the transient thermal solve stopped at a relative residual of {worst:.3e}", SolverWarning)
+    first, (env, env_step, hierarchies) = head["result"], end
+    over_time = lambda key: np.concatenate([head[key]] + [lot[key] for lot in records])        # (n_steps + 1, n_scen, ...)
+    per_step = lambda key: np.concatenate([lot[key] for lot in records])                       # (n_steps,)
+    mesh_max, mesh_vert, stored, loss, traces = (over_time(key) for key in ("max", "vertex", "stored", "loss", "probes"))
+    iterations, seconds = per_step("iterations"), per_step("seconds")
+    info = {"iterations": int(first.iterations) + int(iterations.sum()), "iterations_per_step": iterations,
+            "seconds_per_step": seconds, "setup_seconds_per_step": per_step("setup_seconds"),
+            "rel_residual": max([float(first.rel_residual)] + per_step("rel_residual").tolist()),
+            "hierarchies": int(hierarchies), "seconds": float(first.seconds) + sum(seconds.tolist())}
+    reports = [_transient_report(board, ambient, times, mesh_max[:, c], mesh_vert[:, c], stored[:, c], loss[:, c], layer_heat,
+                                 total_heat, {node: traces[:, c, p] for p, node in enumerate(probe_nodes)}, env[c], env_step[c],
+                                 [(when, theta[c]) for when, theta in snapshots], info)
+               for c, (layer_heat, total_heat) in enumerate(heats)]
+    return reports, info
 
 
 def solve_meshed_thermal_transient(prob, meshes, mesh_index_to_layer_index, model: TransientModel, schedule, *, cases=None,
@@ -3149,71 +3275,27 @@ def solve_meshed_thermal_transient(prob, meshes, mesh_index_to_layer_index, mode
     _refuse_partition(partition, "transient temperatures")
     checked, checked_cases, flat, initial, probe_nodes = _check_transient_arguments(prob, model, schedule, cases, repeat, probes,
                                                                                      keep, filtered_networks)
-    laps, ambient, n_scen = _Laps(timings), checked.thermal.ambient, len(initial)
-    with _thermal_block(prob, meshes, mesh_index_to_layer_index, checked.thermal, checked_cases, filtered_networks,
-                        disconnected_meshes_by_layer, laps, "temperatures over time") as blk:
-        board, k, heat = blk.board, blk.k, blk.heat
-        layer_of, n_mesh, n_vert = board.layer_of, len(board.meshes), blk.n_vert
-        # the Joule heat of every mesh's copper, per case: the sum current_cases forms of the same face powers
-        *_, mesh_power, _cuts = blk.plan.current_cases(k, blk.n_tri, np.asarray(layer_of, dtype=np.int32), [], np.zeros((0, 4)),
-                                                       fields=False, envelope=False)
-        transient = _hip.Transient(blk.thermal, [checked.capacity[layer_of[i]] for i in range(n_mesh)])
-        try:
-            transient.loads_kkt(blk.plan, k, heat)
-            first = transient.start(initial, rtol=RTOL, max_iter=MAX_ITER)
-            laps.lap("transient_start")
-            probe_idx = [board.node_indexer.node_to_global_index[node] for node in probe_nodes]
-            top0, vert0, stored0, loss0 = transient.report()
-            runs, snapshots, worst = [], [], (first.rel_residual if first.status != _hip.OK else 0.0)
-            theta0 = transient.state() if probe_idx else None
-            t, times = 0.0, [0.0]
-            for at, (dt, steps, seg_cases) in enumerate(flat):
-                out = transient.run(dt, steps, seg_cases, probe_idx, rtol=RTOL, max_iter=MAX_ITER)
-                runs.append(out)
-                if out["result"].status != _hip.OK:
-                    worst = max(worst, float(out["result"].rel_residual))
-                for _ in range(steps):
-                    t = t + dt
-                    times.append(t)
-                if keep == "segments" or (keep == "end" and at == len(flat) - 1):
-                    snapshots.append((t, transient.state()))
-            env, env_step = transient.envelope(n_vert)
-            _steps, _time, hierarchies = transient.clock()
-            laps.lap("transient_run")
-        finally:
-            transient.close()
-    if worst > max(RTOL, STALL_WARN_ABOVE):
-        warnings.warn(f"A step of the transient thermal solve stopped at a relative residual of {worst:.3e}", SolverWarning)
-    solutions = _block_solutions(blk)
-    join = lambda key, head: np.concatenate([head[None]] + [out[key] for out in runs])      # (n_steps + 1, n_scen, n_mesh)
-    mesh_max, mesh_vert, stored, loss = join("max", top0), join("vertex", vert0), join("stored", stored0), join("loss", loss0)
-    iterations = np.concatenate([out["iterations"] for out in runs])
-    info = {"iterations": int(first.iterations) + int(iterations.sum()), "iterations_per_step": iterations,
-            "seconds_per_step": np.concatenate([out["seconds"] for out in runs]),
-            "setup_seconds_per_step": np.concatenate([out["setup_seconds"] for out in runs]),
-            "rel_residual": max([float(first.rel_residual)] + [float(out["result"].rel_residual) for out in runs]),
-            "hierarchies": int(hierarchies), "seconds": float(first.seconds) + sum(float(out["result"].seconds) for out in runs)}
-    n_layers = len(prob.layers)
-    case_layer_heat = [[math.fsum(float(mesh_power[j, i]) for i in range(n_mesh) if layer_of[i] == layer_i)
-                        for layer_i in range(n_layers)] for j in range(k)]
-    element_heat = [math.fsum(heat[2][heat[1] == j].tolist()) if heat is not None else 0.0 for j in range(k)]
-    case_total = [math.fsum(case_layer_heat[j] + [element_heat[j]]) for j in range(k)]
-    if blk.sources is not None:                              # the load table's column j carries the sources of case j
-        case_total = [case_total[j] + math.fsum(blk.source_power[j].tolist()) for j in range(k)]
-    reports = []
-    for c in range(n_scen):
-        # the case that led to every time: the initial case at the start (its steady state balances it), then each step's
-        led = [initial[c]] + [seg_cases[c] for _dt, steps, seg_cases in flat for _ in range(steps)]
-        layer_heat = [[0.0 if j is None else case_layer_heat[j][layer_i] for j in led] for layer_i in range(n_layers)]
-        total_heat = [0.0 if j is None else case_total[j] for j in led]
-        traces = {}
-        for p, node in enumerate(probe_nodes):
-            traces[node] = np.concatenate([[theta0[c, probe_idx[p]]]] + [out["probes"][:, c, p] for out in runs])
-        reports.append(_transient_report(board, ambient, times, mesh_max[:, c], mesh_vert[:, c], stored[:, c], loss[:, c],
-                                         layer_heat, total_heat, traces, env[c], env_step[c],
-                                         [(when, theta[c]) for when, theta in snapshots], info))
+    laps = _Laps(timings)
+    with _transient_session(prob, meshes, mesh_index_to_layer_index, checked, checked_cases, initial, probe_nodes,
+                            filtered_networks, disconnected_meshes_by_layer, laps) as ses:
+        transient, runs, snapshots, worst = ses.transient, [], [], ses.head["worst"]
+        t, times = 0.0, [0.0]
+        for at, (dt, steps, seg_cases) in enumerate(flat):
+            out = transient.run(dt, steps, seg_cases, ses.probe_idx, rtol=RTOL, max_iter=MAX_ITER)
+            runs.append(out)
+            worst = _worse(worst, out["result"])
+            for _ in range(steps):
+                t = t + dt
+                times.append(t)
+            if keep == "segments" or (keep == "end" and at == len(flat) - 1):
+                snapshots.append((t, transient.state()))
+        end = _transient_end(transient, ses.blk.n_vert, laps)
+    led = [initial] + [seg_cases for _dt, steps, seg_cases in flat for _ in range(steps)]
+    reports, _info = _transient_reports(ses.blk.board, checked.thermal.ambient, times, ses.head, runs,
+                                        _case_heats(ses.blk, ses.mesh_power, led), probe_nodes, end, snapshots, worst)
+    solutions = _block_solutions(ses.blk)
     laps.lap("solutions")
-    if n_scen == 1:
+    if len(reports) == 1:
         return solutions, reports[0]
     return solutions, reports
 
@@ -3253,28 +3335,8 @@ def check_spans(schedule, n_cases: int, repeat=1) -> tuple:
     """(the flattened spans, the number of scenarios) of a schedule of :class:`Span`, or ValueError: :func:`check_schedule`
     without the steps.  Refused: an empty schedule, an entry that is no Span, a duration that is not finite and positive, a
     case out of range, tuples of unequal length and ``repeat < 1``."""
-    if isinstance(repeat, bool) or not isinstance(repeat, (int, np.integer)) or repeat < 1:
-        raise ValueError(f"repeat must be an integer >= 1, not {repeat!r}")
-    if isinstance(schedule, (Span, Segment, Mapping, str, bytes)):
-        raise ValueError("the schedule must be a sequence of Spans")
-    try:
-        schedule = list(schedule)
-    except TypeError:
-        raise ValueError("the schedule must be a sequence of Spans") from None
-    if not schedule:
-        raise ValueError("an empty schedule: give at least one Span")
-    checked, n_scen = [], None
-    for i, span in enumerate(schedule):
-        if not isinstance(span, Span):
-            raise ValueError(f"span {i} is not a Span")
-        duration = _positive_number(span.duration, f"the duration of span {i}")
-        case = _scenario_entries(span.case, n_cases, f"the case of span {i}")
-        if isinstance(case, tuple):
-            if n_scen is not None and len(case) != n_scen:
-                raise ValueError(f"span {i} names {len(case)} scenarios, an earlier one {n_scen}")
-            n_scen = len(case)
-        checked.append(Span(duration=duration, case=case))
-    return [dataclasses.replace(span) for _ in range(int(repeat)) for span in checked], (1 if n_scen is None else n_scen)
+    checked, n_scen = _check_entries(schedule, n_cases, repeat, Span)
+    return [dataclasses.replace(span) for _ in range(int(repeat)) for span in checked], n_scen
 
 
 def check_step_control(tolerance, first_step=None, min_step=None, max_steps=MAX_TRANSIENT_STEPS) -> tuple:
@@ -3381,21 +3443,10 @@ def _check_adaptive_transient_arguments(prob, model, schedule, cases, repeat, pr
     """Every check of :func:`solve_meshed_thermal_transient_adaptive`: (checked model, checked cases, per flattened span
     (duration, per-scenario cases), per-scenario initial cases, probes, the step control)."""
     checked = check_transient_model(prob, model, filtered_networks)
-    checked_cases = [{}] if cases is None else check_load_cases(prob, cases)
-    spans, n_scen = check_spans(schedule, len(checked_cases), repeat)
-    tuples = any(isinstance(span.case, tuple) for span in spans)
-    initial = _scenario_entries(checked.initial, len(checked_cases), "initial")
-    if isinstance(initial, tuple):
-        if tuples and len(initial) != n_scen:
-            raise ValueError(f"initial names {len(initial)} scenarios, the schedule {n_scen}")
-        n_scen = len(initial)
-    else:
-        initial = (initial,) * n_scen
-    flat = [(span.duration, span.case if isinstance(span.case, tuple) else (span.case,) * n_scen) for span in spans]
-    if keep not in ("end", "segments", "none"):
-        raise ValueError(f'keep must be "end", "segments" or "none", not {keep!r}')
-    control = check_step_control(tolerance, first_step, min_step, max_steps)
-    return checked, checked_cases, flat, initial, check_probes(prob, probes, filtered_networks), control
+    return (checked, *_check_transient_call(
+        prob, checked.initial, schedule, cases, repeat, probes, keep, filtered_networks, check_spans,
+        lambda span, span_cases: (span.duration, span_cases),
+        extra=lambda: check_step_control(tolerance, first_step, min_step, max_steps)))
 
 
 def solve_meshed_thermal_transient_adaptive(prob, meshes, mesh_index_to_layer_index, model: TransientModel, schedule, *,
@@ -3426,86 +3477,46 @@ def solve_meshed_thermal_transient_adaptive(prob, meshes, mesh_index_to_layer_in
     checked, checked_cases, flat, initial, probe_nodes, control = _check_adaptive_transient_arguments(
         prob, model, schedule, cases, repeat, probes, keep, tolerance, first_step, min_step, max_steps, filtered_networks)
     tolerance, first_step, min_step, max_steps = control
-    laps, ambient, n_scen = _Laps(timings), checked.thermal.ambient, len(initial)
-    with _thermal_block(prob, meshes, mesh_index_to_layer_index, checked.thermal, checked_cases, filtered_networks,
-                        disconnected_meshes_by_layer, laps, "temperatures over time") as blk:
-        board, k, heat = blk.board, blk.k, blk.heat
-        layer_of, n_mesh, n_vert = board.layer_of, len(board.meshes), blk.n_vert
-        *_, mesh_power, _cuts = blk.plan.current_cases(k, blk.n_tri, np.asarray(layer_of, dtype=np.int32), [], np.zeros((0, 4)),
-                                                       fields=False, envelope=False)
-        transient = _hip.Transient(blk.thermal, [checked.capacity[layer_of[i]] for i in range(n_mesh)])
-        try:
-            transient.loads_kkt(blk.plan, k, heat)
-            first = transient.start(initial, rtol=RTOL, max_iter=MAX_ITER)
-            laps.lap("transient_start")
-            probe_idx = [board.node_indexer.node_to_global_index[node] for node in probe_nodes]
-            top0, vert0, stored0, loss0 = transient.report()
-            theta0 = transient.state() if probe_idx else None
-            steps, times, led, snapshots, last, tried_sizes = [], [0.0], [], [], {}, []
-            worst = [first.rel_residual if first.status != _hip.OK else 0.0]
+    laps, n_scen = _Laps(timings), len(initial)
+    with _transient_session(prob, meshes, mesh_index_to_layer_index, checked, checked_cases, initial, probe_nodes,
+                            filtered_networks, disconnected_meshes_by_layer, laps) as ses:
+        transient = ses.transient
+        steps, times, led, snapshots, last, tried_sizes, worst = [], [0.0], [initial], [], {}, [], [ses.head["worst"]]
 
-            def try_step(dt, seg_cases):
-                last["trial"] = transient.try_step(dt, seg_cases, rtol=RTOL, max_iter=MAX_ITER)
-                tried_sizes.append(dt)
-                if last["trial"]["result"].status != _hip.OK:
-                    worst[0] = max(worst[0], float(last["trial"]["result"].rel_residual))
-                return last["trial"]["err"]
+        def try_step(dt, seg_cases):
+            last["trial"] = transient.try_step(dt, seg_cases, rtol=RTOL, max_iter=MAX_ITER)
+            tried_sizes.append(dt)
+            worst[0] = _worse(worst[0], last["trial"]["result"])
+            return last["trial"]["err"]
 
-            def accept(dt, time, seg_cases, errors):
-                out = transient.accept(probe_idx)
-                out.update(dt=dt, err=errors.copy(), trial=last["trial"])
-                steps.append(out)
-                times.append(time)
-                led.append(seg_cases)
+        def accept(dt, time, seg_cases, errors):
+            out, trial = transient.accept(ses.probe_idx), last["trial"]
+            # a lot of one step, as Transient.run would have recorded it: the iterations of a step are those of its two stages
+            steps.append(dict({key: out[key][None] for key in ("max", "vertex", "stored", "loss", "probes")},
+                              iterations=trial["stage_iterations"].sum(keepdims=True).astype(np.int32),
+                              seconds=[float(trial["result"].seconds)], setup_seconds=[float(trial["stage_setup_seconds"].sum())],
+                              rel_residual=[float(trial["result"].rel_residual)], dt=dt, err=errors.copy(),
+                              stage_loss=out["stage_loss"], stage_iterations=trial["stage_iterations"]))
+            times.append(time)
+            led.append(seg_cases)
 
-            def end_of_span(at, time):
-                if keep == "segments" or (keep == "end" and at == len(flat) - 1):
-                    snapshots.append((time, transient.state()))
+        def end_of_span(at, time):
+            if keep == "segments" or (keep == "end" and at == len(flat) - 1):
+                snapshots.append((time, transient.state()))
 
-            walk = adaptive_walk(flat, tolerance, first_step, min_step, max_steps, try_step, accept, end_of_span)
-            env, env_step = transient.envelope(n_vert)
-            _steps, _time, hierarchies = transient.clock()
-            laps.lap("transient_run")
-        finally:
-            transient.close()
-    if worst[0] > max(RTOL, STALL_WARN_ABOVE):
-        warnings.warn(f"A step of the transient thermal solve stopped at a relative residual of {worst[0]:.3e}", SolverWarning)
-    solutions = _block_solutions(blk)
-    join = lambda key, head: np.stack([head] + [out[key] for out in steps])      # (n_steps + 1, n_scen, n_mesh)
-    mesh_max, mesh_vert, stored, loss = join("max", top0), join("vertex", vert0), join("stored", stored0), join("loss", loss0)
+        walk = adaptive_walk(flat, tolerance, first_step, min_step, max_steps, try_step, accept, end_of_span)
+        end = _transient_end(transient, ses.blk.n_vert, laps)
+    reports, info = _transient_reports(ses.blk.board, checked.thermal.ambient, times, ses.head, steps,
+                                       _case_heats(ses.blk, ses.mesh_power, led), probe_nodes, end, snapshots, worst[0])
     n_steps = len(steps)
-    stage_iterations = np.array([out["trial"]["stage_iterations"] for out in steps], dtype=np.int32).reshape(n_steps, 2)
-    iterations = stage_iterations.sum(axis=1).astype(np.int32)
-    info = {"iterations": int(first.iterations) + int(iterations.sum()), "iterations_per_step": iterations,
-            "seconds_per_step": np.array([float(out["trial"]["result"].seconds) for out in steps]),
-            "setup_seconds_per_step": np.array([float(out["trial"]["stage_setup_seconds"].sum()) for out in steps]),
-            "rel_residual": max([float(first.rel_residual)] + [float(out["trial"]["result"].rel_residual) for out in steps]),
-            "hierarchies": int(hierarchies),
-            "seconds": float(first.seconds) + sum(float(out["trial"]["result"].seconds) for out in steps),
-            "step_sizes": np.array([out["dt"] for out in steps], dtype=DTYPE),
-            "error_estimates": np.array([out["err"] for out in steps], dtype=DTYPE).reshape(n_steps, n_scen),
-            "stage_loss": np.array([[math.fsum(out["stage_loss"][c].tolist()) for c in range(n_scen)] for out in steps],
-                                   dtype=DTYPE).reshape(n_steps, n_scen),
-            "stage_iterations": stage_iterations, "tried": walk["tried"], "rejected": walk["rejected"],
-            "tried_step_sizes": np.array(tried_sizes, dtype=DTYPE)}
-    n_layers = len(prob.layers)
-    case_layer_heat = [[math.fsum(float(mesh_power[j, i]) for i in range(n_mesh) if layer_of[i] == layer_i)
-                        for layer_i in range(n_layers)] for j in range(k)]
-    element_heat = [math.fsum(heat[2][heat[1] == j].tolist()) if heat is not None else 0.0 for j in range(k)]
-    case_total = [math.fsum(case_layer_heat[j] + [element_heat[j]]) for j in range(k)]
-    if blk.sources is not None:                              # the load table's column j carries the sources of case j
-        case_total = [case_total[j] + math.fsum(blk.source_power[j].tolist()) for j in range(k)]
-    reports = []
-    for c in range(n_scen):
-        on = [initial[c]] + [seg_cases[c] for seg_cases in led]
-        layer_heat = [[0.0 if j is None else case_layer_heat[j][layer_i] for j in on] for layer_i in range(n_layers)]
-        total_heat = [0.0 if j is None else case_total[j] for j in on]
-        traces = {}
-        for p, node in enumerate(probe_nodes):
-            traces[node] = np.array([theta0[c, probe_idx[p]]] + [out["probes"][c, p] for out in steps])
-        reports.append(_transient_report(board, ambient, times, mesh_max[:, c], mesh_vert[:, c], stored[:, c], loss[:, c],
-                                         layer_heat, total_heat, traces, env[c], env_step[c],
-                                         [(when, theta[c]) for when, theta in snapshots], info))
+    info.update({
+        "step_sizes": np.array([out["dt"] for out in steps], dtype=DTYPE),
+        "error_estimates": np.array([out["err"] for out in steps], dtype=DTYPE).reshape(n_steps, n_scen),
+        "stage_loss": np.array([[math.fsum(out["stage_loss"][c].tolist()) for c in range(n_scen)] for out in steps],
+                               dtype=DTYPE).reshape(n_steps, n_scen),
+        "stage_iterations": np.array([out["stage_iterations"] for out in steps], dtype=np.int32).reshape(n_steps, 2),
+        "tried": walk["tried"], "rejected": walk["rejected"], "tried_step_sizes": np.array(tried_sizes, dtype=DTYPE)})
+    solutions = _block_solutions(ses.blk)
     laps.lap("solutions")
     if n_scen == 1:
         return solutions, reports[0]
@@ -3643,96 +3654,136 @@ def _drop_plans(L: SystemMatrix) -> None:
     L._host = None
 
 
-def _solve_electrothermal(prob, meshes, mesh_index_to_layer_index, checked: CheckedElectroThermalModel, cases, fields: bool,
-                          filtered_networks, disconnected_meshes_by_layer, laps: _Laps):
-    """The checked ``cases`` of ``prob``, each converged by the Picard loop on one assembly and one thermal handle:
-    ([Solution], [ThermalReport], [CouplingReport], ThermalEnvelope)."""
-    thermal_model = checked.thermal
-    substituted = [substitute_load_case(prob, case) for case in cases]
-    k, n_layers = len(cases), len(prob.layers)
-    source_power = _source_powers(thermal_model.sources, k)
-    board = index_board(prob, meshes, mesh_index_to_layer_index, filtered_networks, disconnected_meshes_by_layer)
-    _refuse_bare_vertices(board)
-    n_vert = len(board.vindex)
-    if n_vert == 0 or not int(board.tri_offsets[-1]):
-        raise ValueError("the thermal model needs connected copper: the board has no connected mesh with faces")
-    pairs = global_elements(board.filtered_networks, board.node_indexer)
-    laps.lap("indexing")
-    layer_of = board.layer_of
-    n_mesh = len(board.meshes)
-    one_round = all(a == 0.0 for a in checked.alpha)
-    rounds_log = []
-    if laps.timings is not None:
-        laps.timings["rounds"] = rounds_log
-    per_case, stack_flows, source_rises, sources = [], [], [], None
+@contextlib.contextmanager
+def _coupled_handles(board: IndexedBoard, pairs, electro: CheckedElectroThermalModel, laps: _Laps, capacity=None, n_loads=0):
+    """What both electro-thermal calls hold on the device, as a context: the assembled system ``L``, the ``thermal`` handle of
+    ``electro.thermal`` on it, the ``coupled`` handle, the attached heat ``sources`` (None without) and, given the layers'
+    ``capacity``, a ``transient`` handle with room for ``n_loads`` loads (else None); with them ``resistors`` and ``n_tri``.
+    On the way out: the transient handle, the plans kept with L, the coupling, the thermal handle, L."""
+    thermal_model, layer_of, n_mesh = electro.thermal, board.layer_of, len(board.meshes)
     with board.assembled() as (L, _):
         laps.lap("assembly")
         resistors = [(element, row) for element, row in pairs if row[0] == "R"]
-        n_potential = L.layout.n_potential
-        n_tri = len(L.tri)
-        thermal = _thermal_handle(L, n_potential, thermal_model, layer_of, n_mesh, resistors)
-        coupled = None
+        thermal = _thermal_handle(L, L.layout.n_potential, thermal_model, layer_of, n_mesh, resistors)
+        coupled = transient = None
         try:
-            coupled = _hip.Coupled(L.dev, thermal, [checked.alpha[layer_of[i]] for i in range(n_mesh)], thermal_model.ambient,
-                                   checked.conductance_temperature)
-            sources = _attach_heat_sources(thermal, prob, thermal_model, layer_of, n_mesh)
+            coupled = _hip.Coupled(L.dev, thermal, [electro.alpha[layer_of[i]] for i in range(n_mesh)], thermal_model.ambient,
+                                   electro.conductance_temperature)
+            sources = _attach_heat_sources(thermal, board.prob, thermal_model, layer_of, n_mesh)
+            if capacity is not None:
+                transient = _hip.Transient(thermal, [capacity[layer_of[i]] for i in range(n_mesh)])
+                transient.reserve_loads(n_loads)
             laps.lap("thermal_setup")
-            element_rows = [row for _, row in pairs]
-            for j, case in enumerate(cases):
-                rows, cols, vals = stamp_load_cases(board.filtered_networks, board.node_indexer, L.shape[0], [case])
-                log.info(f"Load case {j}: the electro-thermal loop")
-                if j > 0:
-                    coupled.reset()
-                if sources is not None:                      # the same watts in every round: not scaled by the resistivity
-                    thermal.source_power(source_power[j:j + 1])
-                increments, iterations, verdict = [], [], None
-                for round_i in range(1, checked.max_rounds + 1):
-                    lap = {}
-                    round_laps = _Laps(lap)
-                    _drop_plans(L)
-                    coupled.revalue()
-                    round_laps.lap("revalue")
-                    plan, V, residual_norms, res, _n_tri, _n_mesh = _solve_block_on_device(L, rows, cols, vals, 1, 1, round_laps)
-                    local, Vu = _gather_element_rows(element_rows, V, _ROW_UNKNOWNS)
-                    flows = element_flows(_case_element_rows(pairs, local, case), Vu[:, 0])
-                    heat = thermal_heat_triples(pairs, [flows]) if thermal_model.element_heat else None
-                    theta, tres = coupled.solve_kkt(plan, heat, rtol=RTOL, max_iter=MAX_ITER)
-                    round_laps.lap("thermal_solve")
-                    increments.append(coupled.update())
-                    round_laps.lap("update")
-                    iterations.append({"electrical": int(res.iterations), "thermal": int(tres.iterations)})
-                    rounds_log.append(dict(lap, case=j, round=round_i))
-                    verdict = "converged" if one_round else picard_verdict(increments, checked.tolerance)
-                    if verdict is not None:
-                        break
-                if verdict == "runaway":
-                    _m, mesh_max, *_rest = thermal.report(1, n_tri, n_vert, fields=False, envelope=False)
-                    hottest = prob.layers[layer_of[int(np.argmax(mesh_max[0]))]].name
-                    first = len(increments) - 3
-                    raise ThermalRunawayError(
-                        f"Load case {j}: thermal runaway -- the largest change of a face temperature grew in rounds {first} to "
-                        f"{len(increments)}: {', '.join(f'{d:.6g} K' for d in increments[-4:])}; the hottest layer is "
-                        f"{hottest!r} at {float(mesh_max[0].max()) + thermal_model.ambient:.6g}.  A current-driven conductor "
-                        "whose heating outgrows its cooling has no steady state")
-                converged = verdict == "converged"
-                if not converged:
-                    warnings.warn(f"Load case {j}: the electro-thermal loop did not converge in {checked.max_rounds} round(s): "
-                                  f"the last change of a face temperature was {increments[-1]:.3e} K, above the tolerance of "
-                                  f"{checked.tolerance:.3e} K", SolverWarning)
-                power = coupled.power_density(plan, n_tri)
-                scale = coupled.get_scale(n_tri, used=True)
-                report = thermal.report(1, n_tri, n_vert, fields=fields, envelope=False)
-                stack_flows.append(_stack_flows(thermal, thermal_model, 1))
-                if sources is not None:
-                    source_rises.append(thermal.source_report(1))
-                per_case.append((V, residual_norms, res, cols, vals, power, scale, theta, tres, report, heat, increments,
-                                 iterations, converged, flows))
-            laps.lap("loop")
+            yield types.SimpleNamespace(L=L, thermal=thermal, coupled=coupled, transient=transient, sources=sources,
+                                        resistors=resistors, n_tri=len(L.tri))
         finally:
+            if transient is not None:
+                transient.close()
             if coupled is not None:
                 _drop_plans(L)
                 coupled.close()
             thermal.close()
+
+
+def _revalued_solve(handles, board: IndexedBoard, pairs, case: dict, stamps, element_heat: bool, laps: _Laps):
+    """One electrical solve of ``case`` (``stamps``: its :func:`stamp_load_cases`) on the conductances the coupling holds: the
+    plans of ``handles.L`` dropped, L revalued, a fresh plan and the block solve of one column.  A namespace of ``plan``,
+    ``V``, ``residual_norms``, ``res``, ``cols`` and ``vals``, the case's element rows ``case_rows`` with their ``flows``, and
+    ``heat``: the resistors' node-heat triples, None without ``element_heat``."""
+    rows, cols, vals = stamps
+    _drop_plans(handles.L)
+    handles.coupled.revalue()
+    laps.lap("revalue")
+    plan, V, residual_norms, res, _n_tri, _n_mesh = _solve_block_on_device(handles.L, rows, cols, vals, 1, 1, laps)
+    local, Vu = _gather_element_rows([row for _, row in pairs], V, _ROW_UNKNOWNS)
+    case_rows = _case_element_rows(pairs, local, case)
+    flows = element_flows(case_rows, Vu[:, 0])
+    heat = thermal_heat_triples(pairs, [flows]) if element_heat else None
+    return types.SimpleNamespace(plan=plan, V=V, residual_norms=residual_norms, res=res, cols=cols, vals=vals,
+                                 case_rows=case_rows, flows=flows, heat=heat)
+
+
+def _picard(round_fn, electro: CheckedElectroThermalModel) -> tuple:
+    """The Picard loop: ``round_fn(round)`` runs a round and returns its increment d [K].  (the increments, the verdict of
+    :func:`picard_verdict` on them, None when ``electro.max_rounds`` ended the loop); with every alpha 0 one round converges."""
+    one_round = all(a == 0.0 for a in electro.alpha)
+    increments, verdict = [], None
+    for round_i in range(1, electro.max_rounds + 1):
+        increments.append(round_fn(round_i))
+        verdict = "converged" if one_round else picard_verdict(increments, electro.tolerance)
+        if verdict is not None:
+            break
+    return increments, verdict
+
+
+def _picard_outcome(verdict, increments, where: str, board: IndexedBoard, electro: CheckedElectroThermalModel, hottest) -> bool:
+    """Whether the loop of :func:`_picard` converged: :class:`ThermalRunawayError` on "runaway", a SolverWarning when the
+    rounds ran out, both beginning with ``where``.  ``hottest()`` returns the largest theta of every mesh (n_mesh,) and is
+    called on runaway only."""
+    if verdict == "runaway":
+        mesh_max = hottest()
+        layer = board.prob.layers[board.layer_of[int(np.argmax(mesh_max))]].name
+        raise ThermalRunawayError(
+            f"{where}: thermal runaway -- the largest change of a face temperature grew in rounds {len(increments) - 3} to "
+            f"{len(increments)}: {', '.join(f'{d:.6g} K' for d in increments[-4:])}; the hottest layer is "
+            f"{layer!r} at {float(mesh_max.max()) + electro.thermal.ambient:.6g}.  A current-driven conductor "
+            "whose heating outgrows its cooling has no steady state")
+    if verdict != "converged":
+        warnings.warn(f"{where}: the electro-thermal loop did not converge in {electro.max_rounds} round(s): "
+                      f"the last change of a face temperature was {increments[-1]:.3e} K, above the tolerance of "
+                      f"{electro.tolerance:.3e} K", SolverWarning)
+    return verdict == "converged"
+
+
+def _solve_electrothermal(prob, meshes, mesh_index_to_layer_index, checked: CheckedElectroThermalModel, cases, fields: bool,
+                          filtered_networks, disconnected_meshes_by_layer, laps: _Laps):
+    """The checked ``cases`` of ``prob``, each converged by the Picard loop on one assembly and one thermal handle:
+    ([Solution], [ThermalReport], [CouplingReport], ThermalEnvelope)."""
+    thermal_model, n_layers = checked.thermal, len(prob.layers)
+    board, pairs, substituted, source_power, n_vert, k = _thermal_board(
+        prob, meshes, mesh_index_to_layer_index, thermal_model, cases, filtered_networks, disconnected_meshes_by_layer)
+    laps.lap("indexing")
+    rounds_log = []
+    if laps.timings is not None:
+        laps.timings["rounds"] = rounds_log
+    per_case, stack_flows, source_rises = [], [], []
+    with _coupled_handles(board, pairs, checked, laps) as h:
+        thermal, coupled, sources, resistors, n_tri = h.thermal, h.coupled, h.sources, h.resistors, h.n_tri
+        for j, case in enumerate(cases):
+            stamps = stamp_load_cases(board.filtered_networks, board.node_indexer, h.L.shape[0], [case])
+            log.info(f"Load case {j}: the electro-thermal loop")
+            if j > 0:
+                coupled.reset()
+            if sources is not None:                          # the same watts in every round: not scaled by the resistivity
+                thermal.source_power(source_power[j:j + 1])
+            iterations, last = [], {}
+
+            def one_round(round_i):
+                lap = {}
+                round_laps = _Laps(lap)
+                el = _revalued_solve(h, board, pairs, case, stamps, thermal_model.element_heat, round_laps)
+                theta, tres = coupled.solve_kkt(el.plan, el.heat, rtol=RTOL, max_iter=MAX_ITER)
+                round_laps.lap("thermal_solve")
+                increment = coupled.update()
+                round_laps.lap("update")
+                iterations.append({"electrical": int(el.res.iterations), "thermal": int(tres.iterations)})
+                rounds_log.append(dict(lap, case=j, round=round_i))
+                last.update(el=el, theta=theta, tres=tres)
+                return increment
+
+            increments, verdict = _picard(one_round, checked)
+            converged = _picard_outcome(verdict, increments, f"Load case {j}", board, checked,
+                                        lambda: thermal.report(1, n_tri, n_vert, fields=False, envelope=False)[1][0])
+            el = last["el"]
+            power = coupled.power_density(el.plan, n_tri)
+            scale = coupled.get_scale(n_tri, used=True)
+            report = thermal.report(1, n_tri, n_vert, fields=fields, envelope=False)
+            stack_flows.append(_stack_flows(thermal, thermal_model, 1))
+            if sources is not None:
+                source_rises.append(thermal.source_report(1))
+            per_case.append((el.V, el.residual_norms, el.res, el.cols, el.vals, power, scale, last["theta"], last["tres"], report,
+                             el.heat, increments, iterations, converged, el.flows))
+        laps.lap("loop")
     laps.lap()
     solutions, couplings, infos = [], [], []
     for j, (V, residual_norms, res, cols, vals, power, scale, theta, tres, report, heat, increments, iterations,
@@ -3888,25 +3939,25 @@ def _check_electrothermal_transient_arguments(prob, model, schedule, cases, repe
     """Every check of :func:`solve_meshed_electrothermal_transient`: (checked model, checked cases, per flattened segment (dt,
     steps, case), the initial case, probes, voltage probes, stop_above as a float or None)."""
     checked = check_electrothermal_transient_model(prob, model, filtered_networks)
-    checked_cases = [{}] if cases is None else check_load_cases(prob, cases)
-    segments, _n_scen = check_schedule(schedule, len(checked_cases), repeat)
-    if any(isinstance(seg.case, tuple) for seg in segments):
-        raise ValueError(f"the case of a segment: {_NO_SCENARIOS}")
-    initial = _case_entry(checked.initial, len(checked_cases), "initial")
-    _source_powers(checked.electrothermal.thermal.sources, len(checked_cases))
-    if keep not in ("end", "segments", "none"):
-        raise ValueError(f'keep must be "end", "segments" or "none", not {keep!r}')
-    if stop_above is not None:
-        ambient = checked.electrothermal.thermal.ambient
+    thermal_model = checked.electrothermal.thermal
+
+    def checked_stop_above():
+        if stop_above is None:
+            return None
         try:
-            stop_above = float(stop_above)
+            stop = float(stop_above)
         except (TypeError, ValueError):
             raise ValueError(f"stop_above must be a temperature, not {stop_above!r}") from None
-        if not math.isfinite(stop_above) or not stop_above > ambient:
-            raise ValueError(f"stop_above must be finite and above the ambient temperature of {ambient!r}, not {stop_above!r}")
-    flat = [(seg.duration / seg.steps, seg.steps, seg.case) for seg in segments]
-    return (checked, checked_cases, flat, initial, check_probes(prob, probes, filtered_networks),
-            check_probes(prob, voltage_probes, filtered_networks), stop_above)
+        if not math.isfinite(stop) or not stop > thermal_model.ambient:
+            raise ValueError(f"stop_above must be finite and above the ambient temperature of {thermal_model.ambient!r}, "
+                             f"not {stop!r}")
+        return stop
+
+    checked_cases, flat, initial, probe_nodes, stop = _check_transient_call(
+        prob, checked.initial, schedule, cases, repeat, probes, keep, filtered_networks, check_schedule,
+        lambda seg, case: (seg.duration / seg.steps, seg.steps, case), scenarios=False, sources=thermal_model.sources,
+        extra=checked_stop_above)
+    return checked, checked_cases, flat, initial, probe_nodes, check_probes(prob, voltage_probes, filtered_networks), stop
 
 
 def _delivered_power(element_rows, flows) -> float:
@@ -3962,19 +4013,11 @@ def solve_meshed_electrothermal_transient(prob, meshes, mesh_index_to_layer_inde
         prob, model, schedule, cases, repeat, probes, voltage_probes, stop_above, keep, filtered_networks)
     electro = checked.electrothermal
     thermal_model = electro.thermal
-    laps, ambient, k, n_layers = _Laps(timings), thermal_model.ambient, len(checked_cases), len(prob.layers)
-    substituted = [substitute_load_case(prob, case) for case in checked_cases]
-    source_power = _source_powers(thermal_model.sources, k)
-    board = index_board(prob, meshes, mesh_index_to_layer_index, filtered_networks, disconnected_meshes_by_layer)
-    _refuse_bare_vertices(board)
-    n_vert = len(board.vindex)
-    if n_vert == 0 or not int(board.tri_offsets[-1]):
-        raise ValueError("the thermal model needs connected copper: the board has no connected mesh with faces")
-    pairs = global_elements(board.filtered_networks, board.node_indexer)
-    element_rows = [row for _, row in pairs]
+    laps, ambient, n_layers = _Laps(timings), thermal_model.ambient, len(prob.layers)
+    board, pairs, substituted, source_power, n_vert, k = _thermal_board(
+        prob, meshes, mesh_index_to_layer_index, thermal_model, checked_cases, filtered_networks, disconnected_meshes_by_layer)
     laps.lap("indexing")
     layer_of, n_mesh = board.layer_of, len(board.meshes)
-    one_round = all(a == 0.0 for a in electro.alpha)
     steps_log = []
     if laps.timings is not None:
         laps.timings["steps"] = steps_log
@@ -3983,155 +4026,101 @@ def solve_meshed_electrothermal_transient(prob, meshes, mesh_index_to_layer_inde
     for n, case in enumerate(j for _dt, steps, j in flat for _ in range(steps)):
         if case is not None:
             last_step_of[case] = n + 1
-    with board.assembled() as (L, _):
-        laps.lap("assembly")
-        resistors = [(element, row) for element, row in pairs if row[0] == "R"]
-        n_tri = len(L.tri)
-        thermal = _thermal_handle(L, L.layout.n_potential, thermal_model, layer_of, n_mesh, resistors)
-        coupled = transient = None
-        try:
-            coupled = _hip.Coupled(L.dev, thermal, [electro.alpha[layer_of[i]] for i in range(n_mesh)], ambient,
-                                   electro.conductance_temperature)
-            sources = _attach_heat_sources(thermal, prob, thermal_model, layer_of, n_mesh)
-            transient = _hip.Transient(thermal, [checked.capacity[layer_of[i]] for i in range(n_mesh)])
-            transient.reserve_loads(k)
-            laps.lap("thermal_setup")
-            stamps = [stamp_load_cases(board.filtered_networks, board.node_indexer, L.shape[0], [case]) for case in checked_cases]
-            probe_idx = [board.node_indexer.node_to_global_index[node] for node in probe_nodes]
-            vprobe_idx = [board.node_indexer.node_to_global_index[node] for node in vprobe_nodes]
+    with _coupled_handles(board, pairs, electro, laps, checked.capacity, k) as h:
+        thermal, coupled, transient, sources = h.thermal, h.coupled, h.transient, h.sources
+        stamps = [stamp_load_cases(board.filtered_networks, board.node_indexer, h.L.shape[0], [case]) for case in checked_cases]
+        probe_idx = [board.node_indexer.node_to_global_index[node] for node in probe_nodes]
+        vprobe_idx = [board.node_indexer.node_to_global_index[node] for node in vprobe_nodes]
 
-            def electrical(j, step_laps, want_power):
-                """Parts 2 to 4 of a step for case ``j`` on the scale the coupling holds: what the step keeps of them."""
-                rows, cols, vals = stamps[j]
-                _drop_plans(L)
-                coupled.revalue()
-                step_laps.lap("revalue")
-                plan, V, residual_norms, res, _n_tri, _n_mesh = _solve_block_on_device(L, rows, cols, vals, 1, 1, step_laps)
-                local, Vu = _gather_element_rows(element_rows, V, _ROW_UNKNOWNS)
-                case_rows = _case_element_rows(pairs, local, checked_cases[j])
-                flows = element_flows(case_rows, Vu[:, 0])
-                heat = thermal_heat_triples(pairs, [flows]) if thermal_model.element_heat else None
-                if sources is not None:                      # not scaled by the resistivity
-                    thermal.source_power(source_power[j:j + 1])
-                mesh_heat = coupled.transient_load(transient, plan, j, heat)
-                step_laps.lap("load")
-                _warn_if_block_stalled(res, residual_norms, cols, vals, 1)
-                layer_heat = [math.fsum(float(mesh_heat[i]) for i in range(n_mesh) if layer_of[i] == layer_i)
-                              for layer_i in range(n_layers)]
-                total = math.fsum(layer_heat + [math.fsum(heat[2].tolist()) if heat is not None else 0.0])
-                if sources is not None:
-                    total = total + math.fsum(source_power[j].tolist())
-                return types.SimpleNamespace(
-                    case=j, V=np.ascontiguousarray(V[:, 0]), residual_norm=residual_norms[0], res=res,
-                    power=coupled.power_density(plan, n_tri) if want_power else None, layer_heat=layer_heat, total_heat=total,
-                    delivered=_delivered_power(case_rows, flows), scale_range=coupled.scale_range(),
-                    potentials=[float(V[i, 0]) for i in vprobe_idx])
+        def electrical(j, step_laps, want_power):
+            """Parts 2 to 4 of a step for case ``j`` on the scale the coupling holds: what the step keeps of them."""
+            el = _revalued_solve(h, board, pairs, checked_cases[j], stamps[j], thermal_model.element_heat, step_laps)
+            if sources is not None:                          # not scaled by the resistivity
+                thermal.source_power(source_power[j:j + 1])
+            mesh_heat = coupled.transient_load(transient, el.plan, j, el.heat)
+            step_laps.lap("load")
+            _warn_if_block_stalled(el.res, el.residual_norms, el.cols, el.vals, 1)
+            layer_heat = [math.fsum(float(mesh_heat[i]) for i in range(n_mesh) if layer_of[i] == layer_i)
+                          for layer_i in range(n_layers)]
+            total = math.fsum(layer_heat + [math.fsum(el.heat[2].tolist()) if el.heat is not None else 0.0])
+            if sources is not None:
+                total = total + math.fsum(source_power[j].tolist())
+            return types.SimpleNamespace(
+                case=j, V=np.ascontiguousarray(el.V[:, 0]), residual_norm=el.residual_norms[0], res=el.res,
+                power=coupled.power_density(el.plan, h.n_tri) if want_power else None, layer_heat=layer_heat, total_heat=total,
+                delivered=_delivered_power(el.case_rows, el.flows), scale_range=coupled.scale_range(),
+                potentials=[float(el.V[i, 0]) for i in vprobe_idx])
 
-            # the start: ambient, or the steady electro-thermal state of a case by the Picard loop on these handles
-            start, start_increment, start_iterations, first = None, 0.0, {"electrical": 0, "thermal": 0}, None
-            if initial is None:
-                first = transient.start([None], rtol=RTOL, max_iter=MAX_ITER)
-            else:
-                increments, verdict = [], None
-                for _round in range(1, electro.max_rounds + 1):
-                    start = electrical(initial, _Laps(None), stop_above is not None or initial not in last_step_of)
-                    first = transient.start([initial], rtol=RTOL, max_iter=MAX_ITER)
-                    increments.append(coupled.update_transient(transient, 0))
-                    start_iterations = {"electrical": start_iterations["electrical"] + int(start.res.iterations),
-                                        "thermal": start_iterations["thermal"] + int(first.iterations)}
-                    verdict = "converged" if one_round else picard_verdict(increments, electro.tolerance)
-                    if verdict is not None:
-                        break
-                if verdict == "runaway":
-                    mesh_max = transient.report()[0]
-                    hottest = prob.layers[layer_of[int(np.argmax(mesh_max[0]))]].name
-                    raise ThermalRunawayError(
-                        f"The initial state of load case {initial}: thermal runaway -- the largest change of a face temperature "
-                        f"grew in rounds {len(increments) - 3} to {len(increments)}: "
-                        f"{', '.join(f'{d:.6g} K' for d in increments[-4:])}; the hottest layer is {hottest!r} at "
-                        f"{float(mesh_max[0].max()) + ambient:.6g}.  A current-driven conductor whose heating outgrows its "
-                        "cooling has no steady state")
-                if verdict != "converged":
-                    warnings.warn(f"The initial state of load case {initial}: the electro-thermal loop did not converge in "
-                                  f"{electro.max_rounds} round(s): the last change of a face temperature was "
-                                  f"{increments[-1]:.3e} K, above the tolerance of {electro.tolerance:.3e} K", SolverWarning)
-                start_increment = increments[-1]
-            laps.lap("transient_start")
-            top0, vert0, stored0, loss0 = transient.report()
-            theta0 = transient.state() if probe_idx else None
-            worst = first.rel_residual if first.status != _hip.OK else 0.0
-            runs, snapshots, stepped, last_of_case, stopped_at = [], [], [], {}, None
-            if start is not None:
-                last_of_case[initial] = start
-            t, times = 0.0, [0.0]
-            for at, (dt, steps, case) in enumerate(flat):
-                for _ in range(steps):
-                    lap = {}
-                    step_laps = _Laps(lap)
-                    el, d = None, nan
-                    if case is not None:
-                        d = coupled.update_transient(transient, 0)
-                        step_laps.lap("scale")
-                        el = electrical(case, step_laps, stop_above is not None or last_step_of[case] == len(times))
-                        last_of_case[case] = el
-                        step_laps.lap()
-                    out = transient.run(dt, 1, [case], probe_idx, rtol=RTOL, max_iter=MAX_ITER)
-                    step_laps.lap("thermal_step")
-                    steps_log.append(dict(lap, step=len(times), case=case))
-                    runs.append(out)
-                    stepped.append((el, d))
-                    if out["result"].status != _hip.OK:
-                        worst = max(worst, float(out["result"].rel_residual))
-                    t = t + dt
-                    times.append(t)
-                    if stop_above is not None and any(out["vertex"][0, 0, i] >= 0 and out["max"][0, 0, i] + ambient > stop_above
-                                                      for i in range(n_mesh)):
-                        stopped_at = len(times) - 1
-                        break
-                if keep == "segments" or (keep == "end" and (at == len(flat) - 1 or stopped_at is not None)):
-                    snapshots.append((t, transient.state()[0]))
-                if stopped_at is not None:
+        # the start: ambient, or the steady electro-thermal state of a case by the Picard loop on these handles
+        start_increment, start_iterations, last = 0.0, {"electrical": 0, "thermal": 0}, {"start": None}
+        if initial is None:
+            last["first"] = transient.start([None], rtol=RTOL, max_iter=MAX_ITER)
+        else:
+            def one_round(_round):
+                start = electrical(initial, _Laps(None), stop_above is not None or initial not in last_step_of)
+                first = transient.start([initial], rtol=RTOL, max_iter=MAX_ITER)
+                increment = coupled.update_transient(transient, 0)
+                start_iterations["electrical"] += int(start.res.iterations)
+                start_iterations["thermal"] += int(first.iterations)
+                last.update(start=start, first=first)
+                return increment
+
+            increments, verdict = _picard(one_round, electro)
+            _picard_outcome(verdict, increments, f"The initial state of load case {initial}", board, electro,
+                            lambda: transient.report()[0][0])
+            start_increment = increments[-1]
+        start = last["start"]
+        laps.lap("transient_start")
+        head = _transient_head(transient, last["first"], probe_idx)
+        runs, snapshots, stepped, last_of_case, stopped_at, worst = [], [], [], {}, None, head["worst"]
+        if start is not None:
+            last_of_case[initial] = start
+        t, times = 0.0, [0.0]
+        for at, (dt, steps, case) in enumerate(flat):
+            for _ in range(steps):
+                lap = {}
+                step_laps = _Laps(lap)
+                el, d = None, nan
+                if case is not None:
+                    d = coupled.update_transient(transient, 0)
+                    step_laps.lap("scale")
+                    el = electrical(case, step_laps, stop_above is not None or last_step_of[case] == len(times))
+                    last_of_case[case] = el
+                    step_laps.lap()
+                out = transient.run(dt, 1, [case], probe_idx, rtol=RTOL, max_iter=MAX_ITER)
+                step_laps.lap("thermal_step")
+                steps_log.append(dict(lap, step=len(times), case=case))
+                runs.append(out)
+                stepped.append((el, d))
+                worst = _worse(worst, out["result"])
+                t = t + dt
+                times.append(t)
+                if stop_above is not None and any(out["vertex"][0, 0, i] >= 0 and out["max"][0, 0, i] + ambient > stop_above
+                                                  for i in range(n_mesh)):
+                    stopped_at = len(times) - 1
                     break
-            env, env_step = transient.envelope(n_vert)
-            _steps, _time, hierarchies = transient.clock()
-            laps.lap("transient_run")
-        finally:
-            if transient is not None:
-                transient.close()
-            if coupled is not None:
-                _drop_plans(L)
-                coupled.close()
-            thermal.close()
+            if keep == "segments" or (keep == "end" and (at == len(flat) - 1 or stopped_at is not None)):
+                snapshots.append((t, transient.state()))
+            if stopped_at is not None:
+                break
+        end = _transient_end(transient, n_vert, laps)
     laps.lap()
-    if worst > max(RTOL, STALL_WARN_ABOVE):
-        warnings.warn(f"A step of the transient thermal solve stopped at a relative residual of {worst:.3e}", SolverWarning)
+    led = [start] + [el for el, _d in stepped]             # the electrical solve that led to every time, None without
+    layer_heat = [[0.0 if el is None else el.layer_heat[layer_i] for el in led] for layer_i in range(n_layers)]
+    total_heat = [0.0 if el is None else el.total_heat for el in led]
+    (report,), info = _transient_reports(board, ambient, times, head, runs, [(layer_heat, total_heat)], probe_nodes, end, snapshots,
+                                         worst)
     solutions = []
     for j in range(k):
         el = last_of_case.get(j)
         solutions.append(None if el is None else _column_solution(board, substituted[j][0], el.V, el.residual_norm, el.res, el.power,
                                                                   f"Load case {j}: " if k > 1 else ""))
-    join = lambda key, head: np.concatenate([head[None]] + [out[key] for out in runs])[:, 0]      # (n_steps + 1, n_mesh)
-    mesh_max, mesh_vert, stored, loss = join("max", top0), join("vertex", vert0), join("stored", stored0), join("loss", loss0)
-    iterations = np.concatenate([out["iterations"] for out in runs])
-    info = {"iterations": int(first.iterations) + int(iterations.sum()), "iterations_per_step": iterations,
-            "seconds_per_step": np.concatenate([out["seconds"] for out in runs]),
-            "setup_seconds_per_step": np.concatenate([out["setup_seconds"] for out in runs]),
-            "rel_residual": max([float(first.rel_residual)] + [float(out["result"].rel_residual) for out in runs]),
-            "hierarchies": int(hierarchies), "seconds": float(first.seconds) + sum(float(out["result"].seconds) for out in runs)}
-    led = [start] + [el for el, _d in stepped]             # the electrical solve that led to every time, None without
-    layer_heat = [[0.0 if el is None else el.layer_heat[layer_i] for el in led] for layer_i in range(n_layers)]
-    total_heat = [0.0 if el is None else el.total_heat for el in led]
-    traces = {}
-    for p, node in enumerate(probe_nodes):
-        traces[node] = np.concatenate([[theta0[0, probe_idx[p]]]] + [out["probes"][:, 0, p] for out in runs])
-    report = _transient_report(board, ambient, times, mesh_max, mesh_vert, stored, loss, layer_heat, total_heat, traces, env[0],
-                               env_step[0], snapshots, info)
     stopped = None
     if stopped_at is not None:
         spots = [(report.hotspots[layer_i][-1], layer_i) for layer_i in range(n_layers) if report.hotspots[layer_i][-1] is not None]
         spot, layer_i = max(spots, key=lambda entry: (entry[0][0], -entry[1]))      # the lowest layer of the largest temperature
         stopped = (float(times[-1]), spot[0], layer_i, *spot[1:])
-    thermal_its = [int(first.iterations)] + [int(i) for i in iterations]
+    thermal_its = [int(head["result"].iterations)] + [int(i) for i in info["iterations_per_step"]]
     trace = CouplingTrace(
         increments=np.array([start_increment] + [d for _el, d in stepped], dtype=DTYPE),
         scale_min=np.array([nan if el is None else el.scale_range[0] for el in led], dtype=DTYPE),

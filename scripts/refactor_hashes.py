@@ -8,11 +8,21 @@ the random cuts and the load cases of the test suite: ``solve_meshed_currents`` 
 shape and dtype, every float with it; timings are left out.  Prints a one-line summary, and writes {entry: [hashes in
 visiting order]} to ``--out``.
 
-    python scripts/refactor_hashes.py [--tree DIR] [--out FILE]
+    python scripts/refactor_hashes.py [--set faces|thermal] [--tree DIR] [--out FILE]
 
 ``--tree``: the root of the tree whose ``padne_amd`` and ``tests`` are used (default: this script's own).  Run it in one
 process per tree (parent, this tree, parent again) and compare the files: the parent's two runs must agree with each other
 before their agreement with this tree means anything.
+
+``--set thermal`` is the same for the thermal family, on the boards and with the drivers of its tests: ``solve_meshed_thermal``
+with k = 1 and 3 with and without ``per_case_fields``, ``solve_meshed_thermal_sensitivities`` for a point and a hotspot,
+``solve_meshed_thermal_transient`` (two scenarios from ``initial=(None, 0)``; ``repeat=2`` with probes and
+``keep="segments"``; two segments of different dt), ``solve_meshed_thermal_transient_adaptive``,
+``solve_meshed_electrothermal`` with two cases, and ``solve_meshed_electrothermal_transient`` from ambient, from a case's
+steady state and stopped early by ``stop_above``.  Besides ``"hashes"`` the file holds per entry ``"warnings"``, the
+[category, message] of every warning in order, and ``"timings"``, the sorted keys of the ``timings`` dict (those of its lists
+of laps as one set); under ``"refusals"`` the [type, message] of every invalid call of the host tests' lists, which never
+reach the device.  These four are what must agree.  ``"seconds"``, the wall time of every entry, is there to be read.
 """
 from __future__ import annotations
 
@@ -21,8 +31,10 @@ import dataclasses
 import hashlib
 import json
 import os
+import re
 import struct
 import sys
+import time
 import warnings
 
 import numpy as np
@@ -39,8 +51,9 @@ def hashes(obj, out: list) -> list:
         for item in obj:
             hashes(item, out)
     elif isinstance(obj, dict):
-        for item in obj.values():
-            hashes(item, out)
+        for key, item in obj.items():
+            if not (isinstance(key, str) and "seconds" in key):          # (a timing)
+                hashes(item, out)
     elif type(obj).__name__ == "SolverInfo":
         hashes([obj.ground_node_current, obj.residual_norm], out)            # (the rest counts iterations and seconds)
     elif dataclasses.is_dataclass(obj) and type(obj).__module__.endswith("solver"):
@@ -52,21 +65,13 @@ def hashes(obj, out: list) -> list:
     return out
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--tree", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
-    tree = os.path.abspath(args.tree)
-    sys.path[:0] = [tree, os.path.join(tree, "tests")]
-
+def face_set(solver) -> dict:
+    """{"hashes": {entry: hashes}} of the face-kernel entries."""
     import sensitivity_ref as S
-    from padne_amd import solver
     from test_currents import board_of, random_cuts
     from test_load_cases import block_cases
     from test_sensitivity import fixture_objectives
 
-    assert os.path.dirname(os.path.dirname(os.path.abspath(solver.__file__))) == tree, solver.__file__
     warnings.simplefilter("ignore", solver.SolverWarning)
     ctx = solver.get_context()
     out = {}
@@ -102,7 +107,180 @@ def main():
             out[f"{name}/csr_power_density"] = hashes(L.dev.power_density(pot, len(tri)), [])
         out[f"{name}/ctx_power_density"] = hashes(ctx.power_density(xy, tri, voff, toff, sigma, pot), [])
         out[f"{name}/ctx_face_gradient"] = hashes(ctx.face_gradient(xy, tri, voff, toff, pot), [])
-    result = {"tree": tree, "arrays": sum(len(v) for v in out.values()), "hashes": out}
+    return {"hashes": out}
+
+
+def timing_keys(timings: dict) -> list:
+    """The sorted keys of a ``timings`` dict; a list of laps ("rounds", "steps") counts with the keys of all its dicts."""
+    keys = set(timings)
+    for name, value in timings.items():
+        if isinstance(value, list):
+            keys |= {f"{name}/{key}" for lap in value for key in lap}
+    return sorted(keys)
+
+
+def refusals(solver) -> dict:
+    """{list: [[type, message] of every invalid call]} for the lists of invalid arguments of tests/test_transient_host.py,
+    test_adaptive_transient_host.py, test_coupled_transient_host.py and test_coupled_host.py, rebuilt: each call is made with
+    empty mesh lists and has to raise before anything reaches the device.  Addresses in messages are blanked."""
+    import types
+
+    import test_coupled_transient_host as CTH
+    from padne_amd import problem as P
+    from test_coupled_host import small_problem
+    from test_thermal_host import board
+    from test_transient_host import model_of
+
+    def refused(call, *args, **kw):
+        try:
+            call(*args, **kw)
+        except Exception as exc:
+            return [type(exc).__name__, re.sub(r"0x[0-9a-f]+", "0x", str(exc))]
+        return ["no refusal", ""]
+
+    prob = board()[0]
+    source, world = prob.networks[0].elements[0], types.SimpleNamespace(world=2)
+    nan, inf = float("nan"), float("inf")
+    S, Sp, thermal = solver.Segment, solver.Span, solver.ThermalModel(film=1e-5)
+    out = {}
+    ok = [S(1.0, 2, 0)]
+    out["transient"] = [refused(solver.solve_meshed_thermal_transient, prob, [], [], kw.pop("model", model_of()),
+                                kw.pop("schedule", ok), **kw) for kw in (
+        dict(model=model_of(None)), dict(model=model_of({"F.Cu": 3e-3})), dict(schedule=[]), dict(schedule=[S(1.0, 2, 1)]),
+        dict(cases=[{source: nan}]), dict(model=model_of(initial=2)),
+        dict(model=model_of(initial=(0, None, 0)), schedule=[S(1.0, 2, (0, None))]), dict(repeat=0), dict(probes=[P.NodeID()]),
+        dict(probes=["pad"]), dict(keep="all"), dict(partition=world), dict(model=thermal),
+        # several at once: the first in the order of the checks is named
+        dict(schedule=[], keep="all", probes=["pad"]), dict(keep="all", probes=["pad"]), dict(model=model_of(initial=2), keep="all"))]
+    ok = [Sp(1.0, 0)]
+    out["adaptive"] = [refused(solver.solve_meshed_thermal_transient_adaptive, prob, [], [], kw.pop("model", model_of()),
+                               kw.pop("schedule", ok), **dict({"tolerance": 0.1}, **kw)) for kw in (
+        dict(model=model_of(None)), dict(schedule=[]), dict(schedule=[Sp(1.0, 1)]), dict(schedule=[S(1.0, 2, 0)]),
+        dict(cases=[{source: nan}]), dict(model=model_of(initial=2)),
+        dict(model=model_of(initial=(0, None, 0)), schedule=[Sp(1.0, (0, None))]), dict(repeat=0), dict(probes=[P.NodeID()]),
+        dict(keep="all"), dict(partition=world), dict(tolerance=0.0), dict(tolerance=nan), dict(first_step=-1.0),
+        dict(first_step=0.1, min_step=0.2), dict(max_steps=0), dict(model=thermal),
+        dict(keep="all", tolerance=0.0, probes=["pad"]), dict(tolerance=0.0, probes=["pad"]))]
+    prob, _top = small_problem()
+    electro = solver.ElectroThermalModel(thermal=thermal)
+    out["coupled_transient_model"] = [refused(solver.solve_meshed_electrothermal_transient, prob, [], [], model, CTH.ON) for model in (
+        solver.TransientModel(thermal=thermal, areal_capacity=CTH.CAP), electro, CTH.model_of(tolerance=0.0),
+        CTH.model_of(max_rounds=0), CTH.model_of(temperature_coefficient=nan),
+        solver.ElectroThermalTransientModel(solver.ElectroThermalModel(thermal=solver.ThermalModel(film=-1.0)), CTH.CAP),
+        CTH.model_of(capacity=None), CTH.model_of(capacity=-1.0), CTH.model_of(capacity=nan), CTH.model_of(capacity={"F.Cu": 1e-3}),
+        CTH.model_of(capacity={"In1.Cu": 1e-3, "F.Cu": 1e-3, "B.Cu": 1e-3}), CTH.model_of(initial=(0, None)),
+        CTH.model_of(initial=[0]), CTH.model_of(initial=3), CTH.model_of(initial=-1), CTH.model_of(initial=0.5))]
+    out["coupled_transient"] = [refused(solver.solve_meshed_electrothermal_transient, prob, [], [], CTH.model_of(),
+                                        kw.pop("schedule", CTH.ON), **kw) for kw in (
+        dict(schedule=[]), dict(schedule=[S(-1.0, 1, 0)]), dict(schedule=[S(1.0, 0, 0)]), dict(schedule=[S(1.0, 1, 1)]),
+        dict(schedule=S(1.0, 1, 0)), dict(schedule=[S(1.0, 1, (0, 0))]), dict(schedule=[S(1.0, 1, (0,))]),
+        dict(cases=[{object(): 1.0}]), dict(cases=[]), dict(repeat=0), dict(probes=[object()]), dict(probes=[P.NodeID()]),
+        dict(voltage_probes=[object()]), dict(voltage_probes=[P.NodeID()]), dict(voltage_probes="node"), dict(keep="all"),
+        dict(keep=None), dict(stop_above=nan), dict(stop_above=inf), dict(stop_above=25.0), dict(stop_above=10.0),
+        dict(stop_above="hot"), dict(partition=world),
+        dict(keep="all", stop_above=10.0, probes=[object()]), dict(stop_above=10.0, probes=[object()], voltage_probes="node"),
+        dict(probes=[object()], voltage_probes="node"))]
+    out["coupled"] = [refused(solver.check_electrothermal_model, prob, solver.ElectroThermalModel(thermal=thermal, **bad)) for bad in (
+        dict(temperature_coefficient=nan), dict(temperature_coefficient={"F.Cu": inf}), dict(temperature_coefficient={"In1.Cu": 1e-3}),
+        dict(temperature_coefficient="copper"), dict(conductance_temperature=nan), dict(tolerance=0.0), dict(tolerance=-1.0),
+        dict(tolerance=nan), dict(max_rounds=0), dict(max_rounds=2.5), dict(max_rounds=inf),
+        dict(conductance_temperature=25.0 + 1 / 3.93e-3), dict(temperature_coefficient=-1.0, conductance_temperature=24.0))]
+    out["coupled"] += [refused(solver.check_electrothermal_model, prob, thermal),
+                       refused(solver.check_electrothermal_model, prob, solver.ElectroThermalModel(thermal=solver.ThermalModel(film=-1.0))),
+                       refused(solver.solve_meshed_electrothermal, prob, [], [], solver.ElectroThermalModel(thermal=thermal, tolerance=0.0))]
+    return out
+
+
+def thermal_set(solver) -> dict:
+    """{"hashes", "warnings", "timings", "seconds": {entry: ...}, "refusals"} of the thermal family (see the module's docstring)."""
+    import coupled_ref as C
+    import test_adaptive_transient as TA
+    import test_coupled as TC
+    import test_coupled_transient as TCT
+    import test_thermal as TT
+    import test_transient as TR
+
+    out = {"hashes": {}, "warnings": {}, "timings": {}, "seconds": {}, "refusals": refusals(solver)}
+
+    def entry(name, call, *args, **kw):
+        timings = {}
+        with warnings.catch_warnings(record=True) as caught:
+            warnings.simplefilter("always")
+            began = time.perf_counter()
+            result = call(*args, timings=timings, **kw)
+            out["seconds"][name] = time.perf_counter() - began
+        out["hashes"][name] = hashes(result, [])
+        out["warnings"][name] = [[w.category.__name__, str(w.message)] for w in caught]
+        out["timings"][name] = timing_keys(timings)
+        return result
+
+    S, OBJ = solver.Segment, solver.TemperatureObjective
+    for name in ("two_layer", "problem_many_meshes"):
+        prob, meshes, layer_of, disc, *_ = TR.board(name)
+        args, kw = (prob, meshes, layer_of), dict(disconnected_meshes_by_layer=disc)
+        sources = [e for n in prob.networks for e in n.elements if solver.element_kind(e) in solver.CASE_FIELDS]
+        cases = [{}, C.scaled_case(prob, 1.7), {e: 0.0 for e in sources}]
+        nodes = [conn.node_id for conn in prob.networks[0].connections][:2]
+        steady = TT.model_of(TT.FILM_STIFF, ambient=40.0)
+        for k in (1, 3):
+            for fields in (True, False):
+                entry(f"{name}/thermal/k{k}/fields{int(fields)}", solver.solve_meshed_thermal, *args, steady, cases=cases[:k],
+                      per_case_fields=fields, **kw)
+        inside = np.asarray(meshes[0].points)[np.asarray(meshes[0].triangles)[0]].mean(axis=0)      # the first face's centroid
+        entry(f"{name}/thermal_sensitivities", solver.solve_meshed_thermal_sensitivities, *args, steady,
+              [OBJ.at(prob.layers[layer_of[0]].name, tuple(inside.tolist()), case=1), OBJ.hotspot(prob.layers[layer_of[-1]].name)],
+              cases=cases[:2], **kw)
+        model = TR.model_of(film=TT.FILM_REAL)
+        entry(f"{name}/transient/scenarios", solver.solve_meshed_thermal_transient, *args,
+              TR.model_of(film=TT.FILM_REAL, initial=(None, 0)), [S(4 * TR.DT1, 4, (0, None)), S(4 * TR.DT2, 4, (None, 1))],
+              cases=cases[:2], **kw)
+        entry(f"{name}/transient/repeat", solver.solve_meshed_thermal_transient, *args, model,
+              [S(3 * TR.DT1, 3, 0), S(2 * TR.DT2, 2, None)], repeat=2, probes=nodes, keep="segments", **kw)
+        entry(f"{name}/transient/two_dt", solver.solve_meshed_thermal_transient, *args, model, [S(4 * TR.DT1, 4, 0), S(4 * TR.DT2, 4, 0)], **kw)
+        entry(f"{name}/transient_adaptive", solver.solve_meshed_thermal_transient_adaptive, *args,
+              TR.model_of(film=TT.FILM_REAL, **TA.EXTRAS.get(name, {})),
+              [solver.Span(TR.TAU / 4, (0, None)), solver.Span(TR.TAU / 8, (None, 0))], tolerance=0.05, first_step=TR.TAU / 16,
+              probes=nodes, keep="segments", **kw)
+    for name in sorted(C.COUPLED_BOARDS):
+        film, factor = C.COUPLED_BOARDS[name]
+        prob, meshes, layer_of, disc, *_ = TT.board(name)
+        args, kw = (prob, meshes, layer_of), dict(disconnected_meshes_by_layer=disc)
+        nodes = [conn.node_id for conn in prob.networks[0].connections][:2]
+        entry(f"{name}/electrothermal", solver.solve_meshed_electrothermal, *args, TC.model_of(film),
+              cases=[C.scaled_case(prob, factor), C.scaled_case(prob, factor / 2)], **kw)
+        schedule = [S(3 * TR.DT1, 3, 0), S(2 * TR.DT2, 2, None), S(2 * TR.DT2, 2, 0)]
+        kw.update(cases=[C.scaled_case(prob, factor)], probes=nodes, voltage_probes=nodes, keep="segments")
+        _sols, report, _trace = entry(f"{name}/electrothermal_transient/ambient", solver.solve_meshed_electrothermal_transient, *args,
+                                      TCT.model_of(film), schedule, **kw)
+        entry(f"{name}/electrothermal_transient/initial", solver.solve_meshed_electrothermal_transient, *args,
+              TCT.model_of(film, initial=0), schedule, **kw)
+        # one round is too few: both loops warn, each in its own words
+        entry(f"{name}/electrothermal/one_round", solver.solve_meshed_electrothermal, *args, TC.model_of(film, max_rounds=1),
+              disconnected_meshes_by_layer=disc)
+        entry(f"{name}/electrothermal_transient/one_round", solver.solve_meshed_electrothermal_transient, *args,
+              TCT.model_of(film, initial=0, max_rounds=1), schedule, **kw)
+        # between the hotspot after the first step and the hottest of the run: the stop comes before the end
+        tops = [max(spots[n][0] for spots in report.hotspots if spots[n] is not None) for n in range(1, len(report.times))]
+        entry(f"{name}/electrothermal_transient/stopped", solver.solve_meshed_electrothermal_transient, *args, TCT.model_of(film),
+              schedule, stop_above=(tops[0] + max(tops)) / 2, **kw)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--set", default="faces", choices=("faces", "thermal"))
+    ap.add_argument("--tree", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    tree = os.path.abspath(args.tree)
+    sys.path[:0] = [tree, os.path.join(tree, "tests")]
+
+    from padne_amd import solver
+
+    assert os.path.dirname(os.path.dirname(os.path.abspath(solver.__file__))) == tree, solver.__file__
+    result = face_set(solver) if args.set == "faces" else thermal_set(solver)
+    out = result["hashes"]
+    result = {"tree": tree, "arrays": sum(len(v) for v in out.values()), **result}
     print(json.dumps({"tree": tree, "arrays": result["arrays"], "entries": len(out)}), flush=True)
     if args.out:
         with open(args.out, "w") as f:
