@@ -959,6 +959,57 @@ int padne_coupled_update_transient(padne_ctx *ctx, padne_coupled *cp, const padn
  * no rounding is involved).  PADNE_E_INVALID for a mesh without faces. */
 int padne_coupled_scale_range(padne_ctx *ctx, const padne_coupled *cp, double *min_out, double *max_out);
 
+/* ---- periodic steady state: the Krylov arithmetic of a duty cycle's period map ---------------------
+ * No reference counterpart ("Periodic steady state").  The period map of padne_transient_run under a fixed
+ * schedule is affine, theta(T) = Phi theta(0) + d, so the periodic state solves (I - Phi) theta* = d.  The caller runs GMRES
+ * without restart on it, per column, all columns in lockstep; Phi v is one period of padne_transient_run from v with every
+ * column's sources off.  These entries put a state into the transient handle and keep the basis on the device.
+ * <x, y>_C = sum_v Cv[v] x[v] y[v] over the vertices, in which Phi is self-adjoint.  Vectors carry all n_potential entries;
+ * dots, norms and maxima run over the vertices only.  Every expression rounded as written:
+ *     dot      term[v] = (Cv[v] * w[v]) * v_i[v], up to 8 basis vectors per pass over w; per tile of 256 vertices of the
+ *              column's whole vertex range in the fixed order of padne_thermal_report's sums, the tiles folded by one
+ *              workgroup whose thread t takes tiles t, t + 256, ... front to back
+ *     update   s = 0.0; s = s + d_i * v_i[e] for i ascending; w[e] = w[e] - s
+ *     combine  a = base[e]; a = a + c_i * v_i[e] for i ascending
+ *     top      the largest |a| over the vertices, the lowest vertex on a tie, by the same tiles and fold; a value that is not
+ *              finite counts as +infinity; 0.0 and -1 without vertices
+ * No floating-point atomics: two calls give the same bits.  The handle borrows a started transient handle `tr` (destroy this
+ * one first) and owns x0, r0, w and the basis V[max_vectors][n_cols][n_potential] in the context's pool, n_cols that of the
+ * start.  Every entry returns PADNE_E_INVALID, leaving both handles as they were, for a null or foreign handle, a transient
+ * handle that has not been started or has been started anew with another number of columns, an index out of range and a
+ * call out of the order stated below. */
+typedef struct padne_periodic padne_periodic;
+/* max_vectors 1 .. 4095.  PADNE_E_NOMEM when the basis does not fit. */
+int padne_periodic_create(padne_ctx *ctx, padne_transient *tr, int32_t max_vectors, padne_periodic **out);
+int padne_periodic_destroy(padne_periodic *pd);       /* NULL is accepted */
+/* x0 = the state.  The basis and r0 hold nothing afterwards. */
+int padne_periodic_mark(padne_ctx *ctx, padne_periodic *pd);
+/* After padne_periodic_mark: r0 = state - x0; beta_out[c] = sqrt(<r0, r0>_C); max_out[c] = max_v |r0[c][v]| with
+ * vertex_out[c]; v_0 = r0 / beta, exact zeros in a column whose beta is not positive (a frozen column).  The basis then
+ * holds one vector. */
+int padne_periodic_residual(padne_ctx *ctx, padne_periodic *pd, double *beta_out, double *max_out, int64_t *vertex_out);
+/* state = v_j (a vector the basis holds).  The clock, the envelope and a live trial step are reset as by
+ * padne_transient_start: step and time 0, the envelope the state with step 0.  The load table is untouched. */
+int padne_periodic_load(padne_ctx *ctx, padne_periodic *pd, int32_t j);
+/* j the newest vector of a basis that is not full: w = v_j - state, orthogonalised against v_0 .. v_j by classical
+ * Gram-Schmidt applied twice (per pass the dots of w, then one update), h_out[c][i] = the sum of the two passes'
+ * coefficients for i <= j, h_out[c][j + 1] = sqrt(<w, w>_C) of the result, v_{j+1} = w / h_out[c][j + 1], exact zeros in a
+ * column where that is not positive.  h_out[n_cols][j + 2].  The state is left alone. */
+int padne_periodic_push(padne_ctx *ctx, padne_periodic *pd, int32_t j, double *h_out);
+/* After padne_periodic_residual, n_coef <= the vectors held: max_out[c] = max_v |r0 - sum_i coef[c][i] v_i| with
+ * vertex_out[c]; coef[n_cols][n_coef].  Nothing is written on the device but the result. */
+int padne_periodic_predict(padne_ctx *ctx, padne_periodic *pd, int32_t n_coef, const double *coef, double *max_out,
+                           int64_t *vertex_out);
+/* After padne_periodic_mark, n_y <= the vectors held: state = x0 + sum_i y[c][i] v_i, y[n_cols][n_y] (n_y = 0: x0's bits),
+ * then reset as in padne_periodic_load. */
+int padne_periodic_combine(padne_ctx *ctx, padne_periodic *pd, int32_t n_y, const double *y);
+/* out[n_cols][n_potential] = v_j; j = -1: r0, j = -2: x0.  For tests. */
+int padne_periodic_vector(padne_ctx *ctx, const padne_periodic *pd, int32_t j, double *out);
+/* v_j = in[n_cols][n_potential] for j up to the number of vectors held (the basis then holds j + 1 at the least); j = -1:
+ * r0, j = -2: x0, both then count as formed; j = -3: the state, reset as in padne_periodic_load.  For tests: the kernels on
+ * vectors of the caller. */
+int padne_periodic_put(padne_ctx *ctx, padne_periodic *pd, int32_t j, const double *in);
+
 /* ---- introspection for benchmarks ---------------------------------------------------------- */
 /* algorithmic bytes of one CSR SpMV: 12*nnz + 20*n_rows + 4   */
 int64_t padne_spmv_algorithmic_bytes(const padne_csr *m);

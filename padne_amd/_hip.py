@@ -198,6 +198,16 @@ SIGNATURES = {
                                            C.POINTER(SolveInfo)]),
     "padne_transient_accept": (C.c_int, [_P, _P, C.c_int32, _PI64, _PF64, _PI64, _PF64, _PF64, _PF64, _PF64]),
     "padne_transient_trial": (C.c_int, [_P, _P, C.c_int32, _PF64]),
+    "padne_periodic_create": (C.c_int, [_P, _P, C.c_int32, C.POINTER(_P)]),
+    "padne_periodic_destroy": (C.c_int, [_P]),
+    "padne_periodic_mark": (C.c_int, [_P, _P]),
+    "padne_periodic_residual": (C.c_int, [_P, _P, _PF64, _PF64, _PI64]),
+    "padne_periodic_load": (C.c_int, [_P, _P, C.c_int32]),
+    "padne_periodic_push": (C.c_int, [_P, _P, C.c_int32, _PF64]),
+    "padne_periodic_predict": (C.c_int, [_P, _P, C.c_int32, _PF64, _PF64, _PI64]),
+    "padne_periodic_combine": (C.c_int, [_P, _P, C.c_int32, _PF64]),
+    "padne_periodic_vector": (C.c_int, [_P, _P, C.c_int32, _PF64]),
+    "padne_periodic_put": (C.c_int, [_P, _P, C.c_int32, _PF64]),
     "padne_coupled_create": (C.c_int, [_P, _P, _P, C.c_int32, _PF64, C.c_double, C.c_double, C.POINTER(_P)]),
     "padne_coupled_destroy": (C.c_int, [_P]),
     "padne_coupled_reset": (C.c_int, [_P, _P]),
@@ -1525,6 +1535,85 @@ class Transient:
         out = np.empty((self.n_cols, self.n_potential), dtype=np.float64)
         _check(self.ctx._lib.padne_transient_trial(self.ctx._h, self._h, int(which), _ptr(out, _PF64)))
         return out
+
+
+class Periodic:
+    """``padne_periodic``: the Krylov arithmetic of a duty cycle's period map on a started :class:`Transient`
+    (include/padne_hip.h, "periodic steady state").  Holds x0, r0 and up to ``max_vectors`` basis vectors per column on the
+    device.  Close it before ``transient``."""
+
+    R0, X0, STATE = -1, -2, -3               # what ``vector`` and ``put`` name besides a basis vector
+
+    def __init__(self, transient: "Transient", max_vectors: int):
+        self.ctx, self.transient = transient.ctx, transient
+        h = _P()
+        _check(self.ctx._lib.padne_periodic_create(self.ctx._h, transient._h, int(max_vectors), C.byref(h)))
+        self._h = h
+        self.n_potential, self.n_cols, self.max_vectors = transient.n_potential, transient.n_cols, int(max_vectors)
+
+    def close(self):
+        if getattr(self, "_h", None) and self.ctx._h:
+            self.ctx._lib.padne_periodic_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def mark(self) -> None:
+        """x0 = the state."""
+        _check(self.ctx._lib.padne_periodic_mark(self.ctx._h, self._h))
+
+    def residual(self):
+        """r0 = state - x0 and v_0: (beta (n_cols,), max |r0| over the vertices (n_cols,), its vertex (n_cols,))."""
+        beta, top = np.empty(self.n_cols, dtype=np.float64), np.empty(self.n_cols, dtype=np.float64)
+        vert = np.empty(self.n_cols, dtype=np.int64)
+        _check(self.ctx._lib.padne_periodic_residual(self.ctx._h, self._h, _ptr(beta, _PF64), _ptr(top, _PF64), _ptr(vert, _PI64)))
+        return beta, top, vert
+
+    def load(self, j: int) -> None:
+        """state = v_j; clock and envelope as after a start."""
+        _check(self.ctx._lib.padne_periodic_load(self.ctx._h, self._h, int(j)))
+
+    def push(self, j: int) -> np.ndarray:
+        """w = v_j - state orthogonalised into v_{j+1}: the Hessenberg column (n_cols, j + 2)."""
+        h = np.empty((self.n_cols, int(j) + 2), dtype=np.float64)
+        _check(self.ctx._lib.padne_periodic_push(self.ctx._h, self._h, int(j), _ptr(h, _PF64)))
+        return h
+
+    def _coefficients(self, coef) -> np.ndarray:
+        coef = _f64(coef)
+        if coef.ndim != 2 or coef.shape[0] != self.n_cols:
+            raise ValueError("coefficients must have shape (n_cols, n)")
+        return np.ascontiguousarray(coef)
+
+    def predict(self, coef):
+        """(max_v |r0 - sum_i coef[c][i] v_i| (n_cols,), its vertex (n_cols,))."""
+        coef = self._coefficients(coef)
+        top, vert = np.empty(self.n_cols, dtype=np.float64), np.empty(self.n_cols, dtype=np.int64)
+        _check(self.ctx._lib.padne_periodic_predict(self.ctx._h, self._h, coef.shape[1], _ptr(coef, _PF64), _ptr(top, _PF64),
+                                                    _ptr(vert, _PI64)))
+        return top, vert
+
+    def combine(self, y) -> None:
+        """state = x0 + sum_i y[c][i] v_i; clock and envelope as after a start."""
+        y = self._coefficients(y)
+        _check(self.ctx._lib.padne_periodic_combine(self.ctx._h, self._h, y.shape[1], _ptr(y, _PF64)))
+
+    def vector(self, j: int) -> np.ndarray:
+        """v_j (n_cols, n_potential); ``R0`` and ``X0`` name r0 and x0."""
+        out = np.empty((self.n_cols, self.n_potential), dtype=np.float64)
+        _check(self.ctx._lib.padne_periodic_vector(self.ctx._h, self._h, int(j), _ptr(out, _PF64)))
+        return out
+
+    def put(self, j: int, values) -> None:
+        """v_j = ``values`` (n_cols, n_potential); ``R0``, ``X0`` and ``STATE`` name r0, x0 and the transient state."""
+        values = np.ascontiguousarray(_f64(values))
+        if values.shape != (self.n_cols, self.n_potential):
+            raise ValueError("values must have shape (n_cols, n_potential)")
+        _check(self.ctx._lib.padne_periodic_put(self.ctx._h, self._h, int(j), _ptr(values, _PF64)))
 
 
 class Coupled:

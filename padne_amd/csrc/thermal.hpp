@@ -1,7 +1,7 @@
 // The thermal handle (thermal.hip) as the translation units that work on it see it: thermal.hip itself, the electro-thermal
 // coupling (coupled.hip), which borrows the handle's vertex -> faces lists and its theta, the transient handle
-// (transient.hip), coupled_transient.hip, which joins the last two, and sdirk.hip, which steps the transient handle by
-// error-controlled second-order steps.
+// (transient.hip), coupled_transient.hip, which joins the last two, sdirk.hip, which steps the transient handle by
+// error-controlled second-order steps, and periodic.hip, which puts states into it for the Krylov iteration on a period.
 #pragma once
 
 #include "error.hpp"

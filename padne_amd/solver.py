@@ -3312,6 +3312,222 @@ def solve_thermal_transient(prob, model: TransientModel, schedule, mesher_config
 
 
 # --------------------------------------------------------------------------------------------
+# periodic steady state: the regime a duty cycle settles into, by GMRES on the period (DESIGN.md "Periodic steady state")
+# --------------------------------------------------------------------------------------------
+
+MIN_PERIODS, MAX_PERIODS = 3, 4096
+
+
+@dataclass
+class PeriodicReport:
+    """The periodic steady state of one scenario under a duty cycle (see :func:`solve_meshed_thermal_periodic`)."""
+    cycle: TransientReport              # one period from the periodic state: times 0 .. T; the envelope is the hottest each vertex gets in every cycle
+    closure: float                      # max_v |theta(T) - theta(0)| measured on the recorded cycle [K]
+    closure_at: Optional[tuple]         # (layer index, mesh index within the layer, vertex index, x, y) of that maximum, None without vertices
+    predicted: list                     # the closure the Krylov iteration predicted after each of its steps [K]
+    periods: int                        # period applications spent: the first, the Krylov ones and the recorded one
+    converged: bool                     # closure <= tolerance
+    info: dict                          # {"iterations", "seconds"} summed over all periods, "hierarchies", "rel_residual"
+
+
+def check_periodic_control(tolerance, max_periods=64) -> tuple:
+    """(tolerance [K], max_periods) of the periodic iteration, or ValueError: a tolerance that is not finite and positive, a
+    ``max_periods`` that is not an integer from 3 to 4096 (the first period, at least one Krylov period and the recorded
+    one)."""
+    tolerance = _positive_number(tolerance, "the tolerance")
+    if isinstance(max_periods, bool) or not isinstance(max_periods, (int, np.integer)) or not MIN_PERIODS <= max_periods <= MAX_PERIODS:
+        raise ValueError(f"max_periods must be an integer from {MIN_PERIODS} to {MAX_PERIODS}, not {max_periods!r}")
+    return tolerance, int(max_periods)
+
+
+def _check_periodic_arguments(prob, model, schedule, cases, probes, keep, tolerance, max_periods, filtered_networks):
+    """Every check of :func:`solve_meshed_thermal_periodic`: what :func:`_check_transient_arguments` returns for one period,
+    and (tolerance, max_periods)."""
+    checked = check_transient_model(prob, model, filtered_networks)
+    checked_cases, flat, initial, probe_nodes, control = _check_transient_call(
+        prob, checked.initial, schedule, cases, 1, probes, keep, filtered_networks, check_schedule,
+        lambda seg, seg_cases: (seg.duration / seg.steps, seg.steps, seg_cases),
+        extra=lambda: check_periodic_control(tolerance, max_periods))
+    return checked, checked_cases, flat, initial, probe_nodes, control
+
+
+class _PeriodicColumn:
+    """The small problem of one column of the lockstep GMRES: beta, the Hessenberg matrix, the coefficients y of the iterate
+    and H y of its predicted residual.  A column is frozen when beta or a subdiagonal entry is not positive: its later
+    basis vectors are zeros and its coefficients stay put."""
+
+    def __init__(self, beta: float):
+        self.beta, self.H, self.y = float(beta), np.zeros((1, 0)), np.zeros(0)
+        self.frozen = not self.beta > 0.0
+
+    def push(self, h: np.ndarray) -> None:
+        if self.frozen:
+            return
+        j = self.H.shape[1]
+        self.H = np.pad(self.H, ((0, 1), (0, 1)))
+        self.H[:j + 2, j] = h
+        e = np.zeros(j + 2)
+        e[0] = self.beta
+        self.y = np.linalg.lstsq(self.H, e, rcond=None)[0]
+        self.frozen = not h[-1] > 0.0
+
+    def padded(self, values: np.ndarray, n: int) -> np.ndarray:
+        out = np.zeros(n)
+        out[:len(values)] = values
+        return out
+
+
+def periodic_iteration(transient, periodic, flat, tolerance: float, max_periods: int) -> dict:
+    """Steps 1 to 3 of the periodic iteration (DESIGN.md "Periodic steady state") on a started ``_hip.Transient`` and its
+    ``_hip.Periodic``; on return the state is the iterate x0 + V y with the clock at 0.  ``flat``: the period as (dt, steps,
+    per-column cases).  ``first``: the closure of the start (n_cols,), ``predicted``: per Krylov step the predicted closures
+    (n_cols,), ``applications``: period applications so far, ``runs``: what every ``Transient.run`` returned."""
+    n_cols = transient.n_cols
+    off = [None] * n_cols
+    runs = []
+
+    def period(cases_of):
+        for dt, steps, seg_cases in flat:
+            runs.append(transient.run(dt, steps, cases_of(seg_cases), rtol=RTOL, max_iter=MAX_ITER))
+
+    periodic.mark()
+    period(lambda seg_cases: seg_cases)
+    beta, first, _vert = periodic.residual()
+    columns = [_PeriodicColumn(b) for b in beta]
+    predicted = []
+    if not (first <= tolerance).all():
+        for j in range(max_periods - 2):
+            periodic.load(j)
+            period(lambda _seg_cases: off)
+            h = periodic.push(j)
+            for c, col in enumerate(columns):
+                col.push(h[c])
+            top, _vert = periodic.predict(np.stack([col.padded(col.H @ col.y, j + 2) for col in columns]))
+            predicted.append(top)
+            if (top <= tolerance).all() or all(col.frozen for col in columns):
+                break
+    n = len(predicted)
+    periodic.combine(np.stack([col.padded(col.y, n) for col in columns]) if n else np.zeros((n_cols, 0)))
+    return {"first": first, "predicted": predicted, "applications": 1 + n, "runs": runs}
+
+
+def _vertex_place(board: IndexedBoard, vertex: int) -> Optional[tuple]:
+    """(layer index, mesh index within the layer, vertex index, x, y) of a global vertex, None for -1."""
+    if vertex < 0:
+        return None
+    voff = board.vindex.offsets
+    mesh_i = int(np.searchsorted(voff, vertex, side="right") - 1)
+    layer_i, v = board.layer_of[mesh_i], int(vertex - voff[mesh_i])
+    in_layer = [i for i, *_ in board.layer_meshes(layer_i)].index(mesh_i)
+    msh = board.meshes[mesh_i]
+    return layer_i, in_layer, v, float(msh.points[v][0]), float(msh.points[v][1])
+
+
+def solve_meshed_thermal_periodic(prob, meshes, mesh_index_to_layer_index, model: TransientModel, schedule, *, tolerance,
+                                  cases=None, max_periods=64, probes=(), keep="end", filtered_networks=None,
+                                  disconnected_meshes_by_layer=None, partition=None, timings: Optional[dict] = None):
+    """The regime a duty cycle settles into -- the hottest each vertex gets in every cycle, and how far it swings --
+    without running the cycle until the start-up transient has died: ``([Solution] per case, PeriodicReport)``, with
+    several scenarios a list of reports.
+
+    ``schedule`` is ONE period, a sequence of :class:`Segment` as :func:`solve_meshed_thermal_transient` takes them
+    (``repeat`` is 1); ``cases``, scenarios, ``probes``, ``keep`` and the model are that call's.  ``model.initial`` is only
+    the guess the iteration starts from, not part of the answer.  The period map of the fixed-step scheme is affine,
+    theta(T) = Phi theta(0) + d, so the periodic state solves (I - Phi) theta* = d (DESIGN.md "Periodic steady state").
+    That system is solved by GMRES without restart, per scenario, all scenarios in lockstep: a product with I - Phi is one
+    period of the stepping with the sources off, and the basis stays on the device, orthogonalised in the inner product
+    sum_v Cv x y in which Phi is self-adjoint.  Only the modes slower than the period sit near 1 in Phi's spectrum, so the
+    iteration needs about as many periods as there are such modes, where repetition needs tau / T of them.
+
+    ``tolerance`` [K], required, bounds the closure max_v |theta(T) - theta(0)| over the vertices.  ``max_periods`` (3 to
+    4096) bounds the period applications in all: the first, the Krylov ones and the recorded one; the basis holds
+    ``max_periods - 1`` vectors per scenario on the device, and MemoryError says so when that does not fit.  The iterate is
+    then put into the transient handle and one period is run the normal way: ``PeriodicReport.cycle`` is the
+    :class:`TransientReport` of that period -- ``times`` from 0 to T, the envelope from the periodic state, ``total_heat[0]``
+    the heat of the step that leads there, the cycle's last -- and ``closure`` is measured on it.  ``predicted`` holds what
+    the iteration expected after each step.  A SolverWarning when ``max_periods`` ends the iteration first (the best
+    iterate's cycle is still recorded), and when the measured closure exceeds the tolerance although the predicted one met
+    it, which inexact step solves can do.
+
+    Limits: fixed-step schedules only (the adaptive controller's step choice depends on the state, so its period map is
+    not affine); one-way coupling only (the electro-thermal period map is nonlinear); one GPU.  The hierarchy is rebuilt at
+    every change of dt within a period, as under ``repeat=`` (``info["hierarchies"]``).  ValueError, before anything
+    reaches the device, for everything :func:`solve_meshed_thermal_transient` refuses and what
+    :func:`check_periodic_control` refuses."""
+    _refuse_partition(partition, "periodic temperatures")
+    checked, checked_cases, flat, initial, probe_nodes, (tolerance, max_periods) = _check_periodic_arguments(
+        prob, model, schedule, cases, probes, keep, tolerance, max_periods, filtered_networks)
+    laps = _Laps(timings)
+    with _transient_session(prob, meshes, mesh_index_to_layer_index, checked, checked_cases, initial, probe_nodes,
+                            filtered_networks, disconnected_meshes_by_layer, laps) as ses:
+        transient, first = ses.transient, ses.head["result"]
+        periodic = _hip.Periodic(transient, max_periods - 1)
+        try:
+            found = periodic_iteration(transient, periodic, flat, tolerance, max_periods)
+            laps.lap("periodic_iteration")
+            # the recorded cycle: a plain run from the iterate, as solve_meshed_thermal_transient takes it from a start
+            periodic.mark()
+            head = _transient_head(transient, _hip.SolveResult(None, 0, 0, 0.0, 0.0, 0.0, _hip.OK), ses.probe_idx)
+            runs, snapshots, worst = [], [], ses.head["worst"]
+            for out in found["runs"]:
+                worst = _worse(worst, out["result"])
+            t, times = 0.0, [0.0]
+            for at, (dt, steps, seg_cases) in enumerate(flat):
+                out = transient.run(dt, steps, seg_cases, ses.probe_idx, rtol=RTOL, max_iter=MAX_ITER)
+                runs.append(out)
+                worst = _worse(worst, out["result"])
+                for _ in range(steps):
+                    t = t + dt
+                    times.append(t)
+                if keep == "segments" or (keep == "end" and at == len(flat) - 1):
+                    snapshots.append((t, transient.state()))
+            _beta, closure, closure_vertex = periodic.residual()
+            end = _transient_end(transient, ses.blk.n_vert, laps)
+        finally:
+            periodic.close()
+    board = ses.blk.board
+    led = [flat[-1][2]] + [seg_cases for _dt, steps, seg_cases in flat for _ in range(steps)]
+    reports, _info = _transient_reports(board, checked.thermal.ambient, times, head, runs,
+                                        _case_heats(ses.blk, ses.mesh_power, led), probe_nodes, end, snapshots, worst)
+    every = found["runs"] + runs
+    info = {"iterations": int(first.iterations) + int(sum(int(out["iterations"].sum()) for out in every)),
+            "seconds": float(first.seconds) + float(sum(float(out["seconds"].sum()) for out in every)),
+            "hierarchies": int(end[2]), "rel_residual": max([float(first.rel_residual)] + [float(out["rel_residual"].max()) for out in every])}
+    periods = found["applications"] + 1
+    out = []
+    for c, cycle in enumerate(reports):
+        predicted = [float(top[c]) for top in found["predicted"]]
+        expected = predicted[-1] if predicted else float(found["first"][c])
+        report = PeriodicReport(cycle=cycle, closure=float(closure[c]), closure_at=_vertex_place(board, int(closure_vertex[c])),
+                                predicted=predicted, periods=periods, converged=bool(closure[c] <= tolerance), info=info)
+        if not report.converged:
+            where = f" of scenario {c}" if len(reports) > 1 else ""
+            if expected > tolerance:
+                warnings.warn(f"The periodic iteration{where} spent its {max_periods} periods: the cycle closes within "
+                              f"{report.closure:.3e} K, not {tolerance:.3e} K", SolverWarning)
+            else:
+                warnings.warn(f"The recorded cycle{where} closes within {report.closure:.3e} K although {expected:.3e} K was "
+                              f"predicted: the step solves are inexact at a tolerance of {tolerance:.3e} K", SolverWarning)
+        out.append(report)
+    solutions = _block_solutions(ses.blk)
+    laps.lap("solutions")
+    if len(out) == 1:
+        return solutions, out[0]
+    return solutions, out
+
+
+def solve_thermal_periodic(prob, model: TransientModel, schedule, mesher_config: Optional[mesh.Mesher.Config] = None, *,
+                           mesher=None, tolerance, cases=None, max_periods=64, probes=(), keep="end", partition=None):
+    """``solve`` with the periodic steady state of a duty cycle (see :func:`solve_meshed_thermal_periodic`): the board is
+    meshed once."""
+    _refuse_partition(partition, "periodic temperatures")
+    _check_periodic_arguments(prob, model, schedule, cases, probes, keep, tolerance, max_periods, None)
+    meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
+    return solve_meshed_thermal_periodic(prob, meshes, mesh_index_to_layer_index, model, schedule, tolerance=tolerance, cases=cases,
+                                         max_periods=max_periods, probes=probes, keep=keep)
+
+
+# --------------------------------------------------------------------------------------------
 # adaptive transient: second-order steps whose size follows an error estimate (DESIGN.md "Adaptive transient")
 # --------------------------------------------------------------------------------------------
 
