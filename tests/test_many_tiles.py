@@ -14,11 +14,28 @@ The board (jittered synthetic.jittered_grid meshes, chosen for their tile counts
 A source drives A against D through a lattice of vias, a second one drives C against A and returns through B: every mesh
 carries current in case 0.  Three load cases, the last one dead.  One block solve, shared by the tests.
 
+Folds added after the first ones, and what each reaches on this board:
+
+  fold                                     test                                          strides and waves
+  tsens_fold_kernel, faces (e_f, k_f)      test_temperature_sensitivities_of_nine_...    A: 514 tiles, lanes 0-1 take 3 strides, the rest
+                                                                                         2, all four waves; D: 129, waves 0-2; C: 65,
+                                                                                         wave 0 and lane 0 of wave 1; B: one lane
+  tsens_fold_kernel, vertices (film,       the same                                      A: 260 tiles, lanes 0-3 take 2 strides, all four
+  pairs)                                                                                 waves; D: 66 and C: 34, wave 0 (and 1); B: one lane
+  tsens_owner_kernel                       the same                                      A's 131 584 faces in 514 strides, the owner in the
+                                                                                         last; D, B and tile 300 of A
+  sdirk_fold_kernel (err and its vertex)   test_one_adaptive_trial_step_of_four_...      A: the winner in tile 259 (lane 3, second stride),
+                                                                                         257 (lane 1, second stride), 200 (wave 3, first)
+  coupled_transient_heat_fold_kernel       test_electrothermal_transient_load_and_...    per mesh as the faces above: A 514 tiles
+  coupled_transient_range_fold_kernel      the same                                      all 708 face tiles by one workgroup: 3 strides, the
+                                                                                         smallest in the last tile, the largest in tile 300
+
 Where the summed term is a device output, or one IEEE operation on device outputs, the per-mesh sum is compared bit for bit
 with fold_ref.  Elsewhere it is compared with math.fsum of the restatement's per-item terms within fold_ref.fold_bound plus
 the tolerance the entry's own test grants per item, summed over the items.  Tops and their indices are exact everywhere."""
 import contextlib
 import math
+import types
 
 import numpy as np
 import pytest
@@ -29,9 +46,11 @@ import currents_ref as C
 import fold_ref as F
 import goal_ref as GR
 import helpers as H
+import sdirk_ref as SD
 import sensitivity_ref as S
 import sources_ref as SR
 import stack_ref as K
+import test_thermal_sensitivity_kernels as KT
 import thermal_ref as T
 import transient_ref as R
 from padne_amd import _hip, mesh, problem as P, solver, synthetic
@@ -447,3 +466,173 @@ def test_scale_means_and_increment(wide):
         print("increment", d, "at face", at, "tile", at // 256)
         assert d == np.abs(mean_want - prev).max() and d > 0 and f in (None, at)
         prev = mean_want
+
+
+# ---- temperature sensitivities ------------------------------------------------------------------------------------------------------
+
+def test_temperature_sensitivities_of_nine_objectives(ctx, wide):
+    """tests/test_thermal_sensitivity_kernels.py's sequence and checks on this board, with a plan of the test's own (the
+    adjoint block solve replaces a plan's finished block, and the shared one keeps V for the other tests): the owners, the
+    right-hand sides with resistors and without, the three densities, and every per-mesh, per-pair and per-source sum against
+    tests/tsens_kernel_ref.py and fold_ref bit for bit, on the device's own x, theta, lambda and mu; and every sum against
+    math.fsum of the restated terms within fold_bound.  A's 514 face tiles and 260 vertex tiles make tsens_fold_kernel stride
+    twice and three times with tiles in all four waves.  The objective in the dead case gives zeros everywhere but in dT/dP_s,
+    which does not depend on the case."""
+    w = wide
+    polygons, speck_face = footprints(w)
+    p = 0.5 * w.xy[w.tri[speck_face, 0]] + 0.3 * w.xy[w.tri[speck_face, 1]] + 0.2 * w.xy[w.tri[speck_face, 2]]
+    (_a0, a1), _b, (c0, c1), (d0, _d1) = (w.verts(m) for m in range(4))
+    in_D, in_B, in_300 = w.faces(3)[0] + 12_345, w.faces(1)[0], 300 * 256 + 7
+    objectives = [KT.point(0, 0, p), KT.point(1, 1, KT.inside_face(w.xy, w.tri, in_D)), KT.point(0, 0, KT.inside_face(w.xy, w.tri, in_B)),
+                  KT.point(1, 0, KT.inside_face(w.xy, w.tri, in_300)), KT.listed(0, [a1 - 1], [1.0]),
+                  KT.listed(1, [c0 + 10, c0 + 4000, c1 - 1], [0.2, 0.3, 0.5]), KT.of_source(0, 0), KT.of_source(1, 1),
+                  KT.listed(2, [1000], [1.0])]
+    own = [(int(row[1]), int(row[2]), float(row[3])) for _, row in w.pairs if row[0] == "R"]
+    resistors = KT.with_more(own, own[0][0], 30_000, c0 + 50, d0 + 77)
+    watts = np.array([[0.2, 0.1, 0.05], [0.1, 0.3, 0.02], [0.0, 0.0, 0.0]])
+    with contextlib.ExitStack() as stack:
+        plan, V = quiet(finished_block, w.board, w.L, solver.check_load_cases(w.prob, w.cases))
+        stack.callback(plan.close)
+        th = w.thermal(mesh_layer=w.layer_of, pairs=[(0, 1, G)])
+        stack.callback(th.close)
+        th.set_sources(2, w.layer_of, [0, 0, 0], polygons)
+        th.source_power(watts)
+        theta, res = quiet(th.solve_kkt, plan, 3, rtol=solver.RTOL)
+        assert res.status == _hip.OK
+        indptr, indices, data, _diag = th.stack_matrix()
+        out = KT.drive(ctx, th, plan, w.L, 3, w.kappa, w.layer_of, w.n_tri, objectives, resistors)
+        Goff = sp.csr_matrix((data, indices.astype(np.int64), indptr.astype(np.int64)), shape=(w.n_pot, w.n_pot))
+        B = KT.restated_board(w.flat, w.layer_of, w.sigma, w.kappa, w.hM, w.n_pot, w.L.shape[0], [(0, 1, G)], Goff,
+                              SR.Restated(w.flat, w.layer_of, [(0, polygon) for polygon in polygons]))
+        dev = types.SimpleNamespace(thermal=th, n_tri=w.n_tri, n_pot=w.n_pot)
+        KT.check_g_through_the_solve(B, dev, objectives, out, watts)
+    x = np.ascontiguousarray(V[:w.n_pot].T)
+    assert (x[2] == 0.0).all() and (theta[2] == 0.0).all()                    # the dead case
+    terms = KT.check(B, objectives, resistors, x, theta, out, "wide")
+    assert KT.orders_show(B, objectives, resistors, x, out)
+    assert np.array_equal(out.unknown[0], w.tri[speck_face]) and np.array_equal(out.unknown[1], w.tri[in_D])
+    assert np.array_equal(out.unknown[2], w.tri[in_B]) and np.array_equal(out.unknown[3], w.tri[in_300])
+    _ed, _kd, _cd, mesh_e, mesh_k = out.faces[0]
+    none = np.zeros(1)
+    for j, (ef, kf, ft, per) in enumerate(terms):
+        for m in range(w.n_mesh):
+            (lo, hi), (v0, v1) = w.faces(m), w.verts(m)
+            w.sum_check(mesh_e[j, m], ef[lo:hi], none, tiles(hi - lo), f"e, objective {j}, mesh {m}")
+            w.sum_check(mesh_k[j, m], kf[lo:hi], none, tiles(hi - lo), f"k, objective {j}, mesh {m}")
+            w.sum_check(out.film[0][j, m], ft[v0:v1], none, tiles(v1 - v0), f"film, objective {j}, mesh {m}")
+        # the pair: the meshes of layer 0 folded one by one, then joined by two more additions
+        pt = per[0]
+        bound = sum(F.fold_bound(tiles(w.verts(m)[1] - w.verts(m)[0]), fsum(np.abs(pt[w.verts(m)[0]:w.verts(m)[1]]))) for m in range(3))
+        bound += 3 * U * fsum(np.abs(pt))
+        print("pair, objective", j, out.pairs[0][j, 0], "error", abs(out.pairs[0][j, 0] + fsum(pt)), "bound", bound)
+        assert abs(out.pairs[0][j, 0] + fsum(pt)) <= bound and not pt[d0:].any()
+        lam = out.lam[j]
+        c = T.corners(w.tri)
+        mean = ((lam[c[:, 0]] + lam[c[:, 1]]) + lam[c[:, 2]]) / 3
+        for s in range(3):
+            mine = B.sources.face[B.sources.ptr[s]:B.sources.ptr[s + 1]]
+            w.sum_check(out.sources[0][j, s], (w.face_area[mine] / B.sources.A[s]) * mean[mine], none, tiles(len(mine)),
+                        f"source {s}, objective {j}")
+    dead = 8
+    assert not out.rhs[:, dead].any() and not out.mu[:, dead].any() and out.lam[dead].any()
+    assert all(not a[dead].any() for a in out.faces[0]) and not out.film[0][dead].any() and not out.pairs[0][dead].any()
+    assert (out.sources[0][dead] > 0.0).all()
+    live = [j for j in range(9) if j != dead]
+    assert (np.abs(mesh_e[live]) > 0).all() and (out.film[0][live] < 0).all() and (out.pairs[0][live] != 0).all()
+
+
+# ---- the adaptive transient ---------------------------------------------------------------------------------------------------------
+
+def test_one_adaptive_trial_step_of_four_columns(wide):
+    """One trial of 4 dt from ambient (dt and the capacities of test_two_transient_steps); the only load of columns 0, 1 and 2
+    is node heat of 1e-2 W at one vertex of A each, column 3 is off.  theta* is sdirk_ref.extrapolate's; err and its vertex are
+    fold_ref.mesh_top per mesh on the restated estimate, then the meshes in ascending order.  The condition under which this
+    reaches what the table says: the winners lie in A's vertex tiles 259, 257 and 200 -- the second stride of lanes 3 and 1 of
+    sdirk_fold_kernel, and wave 3 of the first stride -- which holds because one step after a point heat is switched on the
+    estimate peaks at the heated vertex (asserted).  Column 3: err exactly 0.0 at vertex 0."""
+    w = wide
+    cap_of_mesh = [3e-3 * (1 + layer) for layer in w.layer_of]
+    dt = 3e-3 / FILM_STIFF / 20
+    hot = np.array([w.voff[1] - 1, w.voff[1] - 300, 200 * 256 + 5], dtype=np.int64)
+    assert (hot // 256).tolist() == [259, 257, 200] and hot.max() < w.voff[1]
+    with contextlib.ExitStack() as stack:
+        th = w.thermal()
+        stack.callback(th.close)
+        tr = _hip.Transient(th, cap_of_mesh)
+        stack.callback(tr.close)
+        tr.loads(np.zeros((3, w.n_tri)), (hot, np.arange(3), np.full(3, 1e-2)))
+        tr.start([None] * 4)
+        first = quiet(tr.try_step, 4 * dt, [0, 1, 2, None])
+        out = quiet(tr.try_step, 4 * dt, [0, 1, 2, None])
+        theta_n, theta_1, star, theta_new = tr.state(), tr.trial(0), tr.trial(1), tr.trial(2)
+    assert np.array_equal(first["err"], out["err"]) and np.array_equal(first["vertex"], out["vertex"])      # two calls, the same bits
+    assert not theta_n.any() and np.array_equal(star, SD.extrapolate(theta_n, theta_1, w.n_vert))
+    est = SD.estimate(theta_n, theta_1, star, theta_new, w.n_vert)
+    for c in range(4):
+        best = (0.0, -1)
+        for m in range(w.n_mesh):
+            v0, v1 = w.verts(m)
+            top = F.mesh_top(np.abs(est[c, v0:v1]), np.arange(v0, v1), empty=NEG_INF)
+            if v1 > v0 and (best[1] < 0 or top[0] > best[0]):
+                best = top
+        print("column", c, "err", out["err"][c], "at", out["vertex"][c], "tile", out["vertex"][c] // 256)
+        assert (out["err"][c], out["vertex"][c]) == best, c
+        assert (out["err"][c], out["vertex"][c]) == SD.error_of(est[c]), c
+    assert (out["vertex"][:3] // 256).tolist() == [259, 257, 200] and np.array_equal(out["vertex"][:3], hot)
+    assert (out["err"][:3] > 0.0).all()
+    assert out["err"][3] == 0.0 and not np.signbit(out["err"][3]) and out["vertex"][3] == 0
+
+
+# ---- the electro-thermal transient --------------------------------------------------------------------------------------------------
+
+def test_electrothermal_transient_load_and_scale_range(wide):
+    """tests/test_coupled_transient.py::test_the_new_entries_are_the_restatement_bit_for_bit on this board: a scale with its
+    smallest value planted in the board's last face (tile 707, the third stride) and its largest in face 300 * 256 + 7 (tile
+    300, the second stride), revalued; the range of the used scale is found over all 708 tiles.  Then a slot of a reserved
+    table from a block solved on the revalued system: the load is the restatement's on the block's own potentials, the per-mesh
+    copper heat is fold_ref's sum of the restated face powers bit for bit, math.fsum's within fold_bound, and the bits of
+    padne_thermal_report's heat after padne_coupled_solve_kkt.  The assembled values are put back at the end (a scale of 1)."""
+    w = wide
+    alpha = [3.93e-3 * (1 + 0.25 * m) for m in range(w.n_mesh)]
+    cap_of_mesh = [3e-3 * (1 + layer) for layer in w.layer_of]
+    rng = np.random.default_rng(9)
+    s = rng.uniform(0.5, 1.5, w.n_tri)
+    s[w.n_tri - 1], s[300 * 256 + 7] = 0.25, 1.75
+    nodes = rng.integers(0, w.n_pot, 6)
+    nodes[:2] = nodes[0]
+    heat = (nodes, np.zeros(6, dtype=np.int32), rng.uniform(0.0, 1e-2, 6))
+    assert tiles(w.n_tri) == 708 and (w.n_tri - 1) // 256 == 707
+    with contextlib.ExitStack() as stack:
+        th = w.thermal()
+        stack.callback(th.close)
+        tr = _hip.Transient(th, cap_of_mesh)
+        stack.callback(tr.close)
+        coupled = _hip.Coupled(w.L.dev, th, alpha, 31.0, 20.0)
+        stack.callback(coupled.close)
+
+        def restore():                                       # L's assembled values back for whatever runs after this test
+            coupled.set_scale(np.ones(w.n_tri))
+            coupled.revalue()
+        coupled.set_scale(s)
+        coupled.revalue()
+        stack.callback(restore)
+        s_used = coupled.get_scale(w.n_tri, used=True)
+        ranges = [coupled.scale_range() for _ in range(2)]
+        plan, V = quiet(finished_block, w.board, w.L, solver.check_load_cases(w.prob, w.cases)[:1])
+        stack.callback(plan.close)
+        tr.reserve_loads(2)
+        mesh_heat = coupled.transient_load(tr, plan, 1, heat)
+        again = coupled.transient_load(tr, plan, 1, heat)
+        table = tr.load_vectors()
+        quiet(coupled.solve_kkt, plan, heat)
+        report_heat = th.report(1, w.n_tri, w.n_vert, fields=False, envelope=False)[3][0]
+    assert np.array_equal(s_used, s) and ranges[0] == ranges[1] == (s_used.min(), s_used.max()) == (0.25, 1.75)
+    Pf = CR.face_power(w.xy, w.tri, w.face_mesh, w.sigma, s_used, V[:w.n_vert, 0])
+    want = T.load(w.n_pot, w.tri, Pf, [(int(n), float(v)) for n, v in zip(heat[0], heat[2])])
+    assert np.array_equal(table[1], want) and not table[0].any() and np.abs(want).max() > 0.0
+    assert np.array_equal(mesh_heat, again) and np.array_equal(mesh_heat, report_heat)      # two calls, the same bits
+    for m in range(w.n_mesh):
+        lo, hi = w.faces(m)
+        assert mesh_heat[m] == F.mesh_sum(Pf[lo:hi]), m
+        w.sum_check(mesh_heat[m], Pf[lo:hi], np.zeros(1), tiles(hi - lo), f"copper heat, mesh {m}")
+    assert (mesh_heat > 0.0).all()
