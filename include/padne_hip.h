@@ -582,6 +582,36 @@ int padne_sampler_raster(padne_ctx *ctx, padne_sampler *s, int32_t layer, double
  * of the last query kernel. */
 int padne_sampler_stats(const padne_sampler *s, int32_t layer, int64_t *counts_out, double *seconds_out);
 
+/* ---- thermal images: a block of temperature fields at points and on rasters ----------------------
+ * No reference counterpart ("Thermal images").  A sampler may hold, next to its potentials, a block of n_field
+ * <= 256 vertex fields fields_host[n_field][n_vert] (field-major, the global vertex numbering of padne_sampler_create) and
+ * the sheet conductance kappa[n_mesh] [W/K] of every mesh (NULL: no heat flux).  The handle owns its copy; a second call
+ * replaces the block, n_field = 0 removes it.  The index and padne_sampler_points / _raster are not touched.
+ *
+ * A field query locates q ONCE, by the owner rule above, and reads every field f out at it.  With a = tri[0], b = tri[1],
+ * c = tri[2] of the owner and s = (o_a + o_b) + o_c:
+ *     t_out[f][i]      = ((o_a / s) T_f[a] + (o_b / s) T_f[b]) + (o_c / s) T_f[c]       (v_out's formula)
+ *     q_out[f][i][2]   = -kappa_m grad T_f on the owner, the gradient of j_out with corners as (tri[2], tri[0], tri[1]) and
+ *                        kappa_m of the owner's mesh [W per mesh unit of length]
+ *     hot_out[i], hot_field_out[i] = the maximum over the fields and the field that attains it, sequentially: field 0
+ *                        first, replaced by a later field only when it is strictly greater
+ * face_out[i] = the owner or -1; outside the copper t_out, q_out and hot_out are NaN and hot_field_out is -1.  t_out and
+ * q_out may each be NULL: that output is neither computed nor stored, and a call with both NULL moves 16 bytes per sample.
+ * No floating-point atomics: two calls give the same bits.  PADNE_E_INVALID, with nothing written, for a null handle, a
+ * sampler without fields, q_out without kappa, a layer out of range, a point that is not finite, more than 2^26 samples,
+ * and more than 2^28 values n_field x n where t_out or q_out is wanted. */
+int padne_sampler_set_fields(padne_ctx *ctx, padne_sampler *s, int32_t n_field, const double *fields_host, const double *kappa);
+int padne_sampler_field_points(padne_ctx *ctx, padne_sampler *s, int32_t layer, int64_t n, const double *xy_host,
+                               int32_t *face_out, double *t_out, double *q_out, double *hot_out, int32_t *hot_field_out);
+/* The same at the pixel centres of padne_sampler_raster's raster, plus the hottest pixel of every slot -- the n_field fields,
+ * then hot_out: top_out[n_field + 1] the largest value among the pixels that have an owner and top_pixel_out[n_field + 1]
+ * its flat index j * width + i, the lowest index on a tie; -infinity and -1 where no pixel lies on copper.  The maximum is
+ * exact, so the fold's order does not show: per workgroup of 256 pixels a (value, pixel) top, then one workgroup per slot
+ * over those.  PADNE_E_INVALID also for what padne_sampler_raster refuses. */
+int padne_sampler_field_raster(padne_ctx *ctx, padne_sampler *s, int32_t layer, double x0, double y0, double dx, double dy,
+                               int64_t width, int64_t height, int32_t *face_out, double *t_out, double *q_out, double *hot_out,
+                               int32_t *hot_field_out, double *top_out, int64_t *top_pixel_out);
+
 /* ---- thermal: steady-state temperature rise of the copper from Joule heating --------------------
  * No reference counterpart ("Thermal").  Unknown: theta = T - T_ambient [K] at the first n_potential unknowns of
  * the assembled electrical system `L` (the vertices of its meshes, then the internal nodes); multiplier rows take no part.

@@ -148,6 +148,10 @@ SIGNATURES = {
     "padne_sampler_raster": (C.c_int, [_P, _P, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, _I64, _I64, _PI32,
                                        _PF64, _PF64, _PF64]),
     "padne_sampler_stats": (C.c_int, [_P, C.c_int32, _PI64, _PF64]),
+    "padne_sampler_set_fields": (C.c_int, [_P, _P, C.c_int32, _PF64, _PF64]),
+    "padne_sampler_field_points": (C.c_int, [_P, _P, C.c_int32, _I64, _PF64, _PI32, _PF64, _PF64, _PF64, _PI32]),
+    "padne_sampler_field_raster": (C.c_int, [_P, _P, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, _I64, _I64, _PI32,
+                                             _PF64, _PF64, _PF64, _PI32, _PF64, _PI64]),
     "padne_thermal_create": (C.c_int, [_P, _P, _I64, C.c_int32, _PF64, _PF64, _I64, _PI64, _PI64, _PF64, C.POINTER(_P)]),
     "padne_thermal_destroy": (C.c_int, [_P]),
     "padne_thermal_matrix": (C.c_int, [_P, C.POINTER(_P)]),
@@ -1819,6 +1823,7 @@ class Sampler:
         if pot.shape[0] != xy.shape[0]:
             raise ValueError("one potential per vertex")
         self.ctx, self.n_layer = ctx, int(n_layer)
+        self.n_vert, self.n_mesh, self.n_field = int(xy.shape[0]), int(n_mesh), 0
         h = _P()
         _check(ctx._lib.padne_sampler_create(ctx._h, xy.shape[0], _ptr(xy, _PF64), tri.shape[0], _ptr(tri, _PI32), n_mesh,
                                              _ptr(mvo, _PI64), _ptr(mto, _PI64), _ptr(ml, _PI32), _ptr(sig, _PF64), int(n_layer),
@@ -1866,6 +1871,53 @@ class Sampler:
         return {"bins_x": int(counts[0]), "bins_y": int(counts[1]), "entries": int(counts[2]), "faces": int(counts[3]),
                 "last_candidates": int(counts[4]), "last_queries": int(counts[5]), "upload_seconds": float(secs[0]),
                 "build_seconds": float(secs[1]), "last_kernel_seconds": float(secs[2])}
+
+    # ---- thermal images: a block of fields on the same handle (include/padne_hip.h, "thermal images")
+
+    def set_fields(self, fields, kappa=None) -> None:
+        """``fields`` (n_field, n_vert) replaces the handle's block, (0, n_vert) or None removes it; ``kappa`` (n_mesh,) the
+        sheet conductances of the heat flux, None for none."""
+        block = _f64(np.zeros((0, 0)) if fields is None else fields)
+        if block.ndim != 2:
+            raise ValueError("fields must have shape (n_field, n_vert)")
+        if block.shape[0] and block.shape[1] != self.n_vert:
+            raise ValueError("every field has one value per vertex")
+        kap = None if kappa is None else _f64(kappa).reshape(-1)
+        if kap is not None and kap.shape[0] != self.n_mesh:
+            raise ValueError("every mesh has a sheet conductance")
+        _check(self.ctx._lib.padne_sampler_set_fields(self.ctx._h, self._h, block.shape[0], _ptr(block, _PF64),
+                                                      None if kap is None else _ptr(kap, _PF64)))
+        self.n_field = int(block.shape[0])
+
+    def _field_outputs(self, n: int, per_field: bool, flux: bool):
+        f = self.n_field
+        return (np.empty(n, dtype=np.int32), np.empty((f, n), dtype=np.float64) if per_field else None,
+                np.empty((f, n, 2), dtype=np.float64) if flux else None, np.empty(n, dtype=np.float64),
+                np.empty(n, dtype=np.int32))
+
+    def field_points(self, layer: int, xy, per_field: bool = True, flux: bool = False):
+        """(face (n,), T (n_field, n) or None, q (n_field, n, 2) or None, hottest (n,), hottest field (n,) int32)."""
+        q = _f64(xy).reshape(-1, 2)
+        face, t, flx, hot, hot_field = self._field_outputs(q.shape[0], per_field, flux)
+        _check(self.ctx._lib.padne_sampler_field_points(
+            self.ctx._h, self._h, int(layer), q.shape[0], _ptr(q, _PF64), _ptr(face, _PI32),
+            None if t is None else _ptr(t, _PF64), None if flx is None else _ptr(flx, _PF64), _ptr(hot, _PF64),
+            _ptr(hot_field, _PI32)))
+        return face, t, flx, hot, hot_field
+
+    def field_raster(self, layer: int, x0: float, y0: float, dx: float, dy: float, width: int, height: int,
+                     per_field: bool = True, flux: bool = False):
+        """The five of ``field_points`` with row j, column i at j * width + i, then the tops of the n_field + 1 slots: the
+        values (n_field + 1,) and their flat pixels (n_field + 1,) int64, -inf and -1 for a slot without a pixel on copper."""
+        n = max(int(width), 0) * max(int(height), 0)
+        face, t, flx, hot, hot_field = self._field_outputs(n, per_field, flux)
+        slots = self.n_field + 1
+        top, top_pixel = np.empty(slots, dtype=np.float64), np.empty(slots, dtype=np.int64)
+        _check(self.ctx._lib.padne_sampler_field_raster(
+            self.ctx._h, self._h, int(layer), float(x0), float(y0), float(dx), float(dy), int(width), int(height),
+            _ptr(face, _PI32), None if t is None else _ptr(t, _PF64), None if flx is None else _ptr(flx, _PF64),
+            _ptr(hot, _PF64), _ptr(hot_field, _PI32), _ptr(top, _PF64), _ptr(top_pixel, _PI64)))
+        return face, t, flx, hot, hot_field, top, top_pixel
 
 
 def refine(ctx: "Context", xy, tri, mesh_vertex_offset, mesh_tri_offset, flags):

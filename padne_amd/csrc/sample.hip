@@ -3,6 +3,8 @@
 //   padne_sampler_create : meshes + potentials -> device-resident sampler with a point-location index per layer
 //   padne_sampler_points : uploaded query points   -> owner face, V, J, p per point
 //   padne_sampler_raster : pixel centres formed by the kernel -> the same four as images
+//   padne_sampler_set_fields / _field_points / _field_raster : a block of temperature fields on the same handle, every
+//                          field read out at the one owner of a query ("Thermal images")
 //
 // The owner rule (what "the face that contains q" means, bit for bit):
 //   edge (i, k) of a face is evaluated from its lower global vertex to its higher one, side = orient(P, Q, q), and negated
@@ -11,6 +13,7 @@
 //   the lowest global index.  The index only proposes candidates; tests/sampling_ref.py states the rule by brute force.
 //
 // This file is compiled with -ffp-contract=off, like assemble.hip: every expression rounds as written.
+#include "error.hpp"
 #include "locate.hpp"
 
 #include <float.h>
@@ -154,6 +157,157 @@ __global__ __launch_bounds__(256) void sample_kernel(const LayerGrid g, const in
     if ((threadIdx.x & 63) == 0 && n_tested) atomicAdd(tested, n_tested);
 }
 
+// ---- thermal images: a block of fields read out at one located point ("Thermal images") -----------------------
+constexpr int kMaxSampleFields = 256;
+constexpr long long kMaxSampleValues = 1LL << 28;     // n_field x samples of one call that wants every field
+
+// The (value, pixel) top of a 256-thread workgroup, in error.hpp's order: down each wave by halving strides, then waves 0 to
+// 3 by thread 0, which alone holds the result.  red_*: 4 entries of shared memory each, free again after the caller's next
+// barrier
+__device__ __forceinline__ void field_block_top(double &v, long long &pix, double *red_v, long long *red_p) {
+    error_wave_top(v, pix);
+    if ((threadIdx.x & 63) == 0) {
+        red_v[threadIdx.x >> 6] = v;
+        red_p[threadIdx.x >> 6] = pix;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int w = 1; w < 4; ++w) error_merge(v, pix, red_v[w], red_p[w]);
+}
+
+// One thread per query: the owner ONCE, its weights and corners kept in registers, then every field of the field-major
+// block T[n_field][n_vert] at it, stored field-major to t_out[n_field][n] and q_out[n_field][n][2] (either may be null:
+// not computed, not stored), and the sequential maximum over the fields to hot_out / hot_field_out (field 0 first,
+// replaced on strictly greater).  Outside the copper: face -1, NaN, field -1.
+//   T_f   s = (o_a + o_b) + o_c;  ((o_a / s) T_f[a] + (o_b / s) T_f[b]) + (o_c / s) T_f[c]: sample_kernel's potential
+//   q_f   -kappa_m grad T_f with sample_kernel's gradient, corners as (tri[2], tri[0], tri[1])
+// RASTER: the pixel centres are formed here, and every workgroup leaves the top of its 256 pixels per slot (the fields, then
+// the hottest) in tile_v / tile_p[slot][tile]: the larger value, the lower pixel on a tie, (-inf, kErrNoFace) for a
+// workgroup without a pixel on copper.  No floating-point atomics anywhere.
+template <bool RASTER>
+__global__ __launch_bounds__(256) void sample_fields_kernel(const LayerGrid g, const int *__restrict__ bin_off,
+                                                            const int *__restrict__ bin_face, const int *__restrict__ gtri,
+                                                            const double *__restrict__ xy, int n_mesh,
+                                                            const long long *__restrict__ mesh_toff,
+                                                            const double *__restrict__ kappa, const double *__restrict__ T,
+                                                            int n_field, long long n_vert, long long n,
+                                                            const double *__restrict__ q_xy, const RasterSpec r,
+                                                            int *__restrict__ face_out, double *__restrict__ t_out,
+                                                            double *__restrict__ q_out, double *__restrict__ hot_out,
+                                                            int *__restrict__ hot_field_out, double *__restrict__ tile_v,
+                                                            long long *__restrict__ tile_p,
+                                                            unsigned long long *__restrict__ tested) {
+    __shared__ double red_v[2][4];
+    __shared__ long long red_p[2][4];
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = idx < n;
+    unsigned long long n_tested = 0;
+    bool has = false;
+    long long a = 0, b = 0, c = 0;
+    double la = 0.0, lb = 0.0, lc = 0.0, kap = 0.0;
+    double xa = 0.0, ya = 0.0, xb = 0.0, yb = 0.0, xc = 0.0, yc = 0.0;
+    if (live) {
+        double qx, qy;
+        if (RASTER) {
+            const long long j = idx / r.width, i = idx - j * r.width;
+            qx = r.x0 + ((double)i + 0.5) * r.dx;
+            qy = r.y0 + ((double)j + 0.5) * r.dy;
+        } else {
+            qx = q_xy[2 * idx];
+            qy = q_xy[2 * idx + 1];
+        }
+        double wa, wb, wc;
+        const int owner = locate_owner(g, bin_off, bin_face, gtri, xy, qx, qy, wa, wb, wc, n_tested);
+        has = owner != kNoOwner;
+        if (has) {
+            a = gtri[3 * (long long)owner];
+            b = gtri[3 * (long long)owner + 1];
+            c = gtri[3 * (long long)owner + 2];
+            const double s = (wa + wb) + wc;
+            la = wa / s;
+            lb = wb / s;
+            lc = wc / s;
+            if (q_out) {
+                xa = xy[2 * a]; ya = xy[2 * a + 1];
+                xb = xy[2 * b]; yb = xy[2 * b + 1];
+                xc = xy[2 * c]; yc = xy[2 * c + 1];
+                kap = kappa[find_segment(mesh_toff, n_mesh, owner)];
+            }
+        }
+        face_out[idx] = has ? owner : -1;
+    }
+    double hot = NAN;
+    int hot_field = -1;
+    const long long tile = blockIdx.x, n_tile = gridDim.x;
+    for (int f = 0; f < n_field; ++f) {
+        double t = NAN, qx = NAN, qy = NAN;
+        if (has) {
+            const double *__restrict__ Tf = T + (long long)f * n_vert;
+            const double ta = Tf[a], tb = Tf[b], tc = Tf[c];
+            t = (la * ta + lb * tb) + lc * tc;
+            if (f == 0 || t > hot) {
+                hot = t;
+                hot_field = f;
+            }
+            if (q_out) {
+                double gx, gy;
+                face_gradient_of(xc, yc, xa, ya, xb, yb, tc, ta, tb, gx, gy);
+                qx = -kap * gx;
+                qy = -kap * gy;
+            }
+        }
+        if (live) {
+            if (t_out) t_out[(long long)f * n + idx] = t;
+            if (q_out) {
+                q_out[2 * ((long long)f * n + idx)] = qx;
+                q_out[2 * ((long long)f * n + idx) + 1] = qy;
+            }
+        }
+        if (RASTER) {
+            double v = has ? t : -INFINITY;
+            long long pix = has ? idx : kErrNoFace;
+            field_block_top(v, pix, red_v[f & 1], red_p[f & 1]);
+            if (threadIdx.x == 0) {
+                tile_v[(long long)f * n_tile + tile] = v;
+                tile_p[(long long)f * n_tile + tile] = pix;
+            }
+        }
+    }
+    if (live) {
+        hot_out[idx] = hot;
+        hot_field_out[idx] = hot_field;
+    }
+    if (RASTER) {
+        double v = has ? hot : -INFINITY;
+        long long pix = has ? idx : kErrNoFace;
+        field_block_top(v, pix, red_v[n_field & 1], red_p[n_field & 1]);
+        if (threadIdx.x == 0) {
+            tile_v[(long long)n_field * n_tile + tile] = v;
+            tile_p[(long long)n_field * n_tile + tile] = pix;
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) n_tested += __shfl_down(n_tested, off, 64);
+    if ((threadIdx.x & 63) == 0 && n_tested) atomicAdd(tested, n_tested);
+}
+
+// A workgroup per slot folds the slot's tiles: a thread takes tiles threadIdx.x, + 256, ... in order, then the workgroup's
+// top.  top_p = -1 and top_v = -inf for a raster without a pixel on copper
+__global__ __launch_bounds__(256) void sample_fields_fold_kernel(long long n_tile, const double *__restrict__ tile_v,
+                                                                 const long long *__restrict__ tile_p,
+                                                                 double *__restrict__ top_v, long long *__restrict__ top_p) {
+    __shared__ double red_v[4];
+    __shared__ long long red_p[4];
+    const long long slot = blockIdx.x;
+    double v = -INFINITY;
+    long long pix = kErrNoFace;
+    for (long long i = threadIdx.x; i < n_tile; i += 256) error_merge(v, pix, tile_v[slot * n_tile + i], tile_p[slot * n_tile + i]);
+    field_block_top(v, pix, red_v, red_p);
+    if (threadIdx.x == 0) {
+        top_v[slot] = v;
+        top_p[slot] = pix == kErrNoFace ? -1 : pix;
+    }
+}
+
 }  // namespace padne
 
 using namespace padne;
@@ -167,6 +321,8 @@ struct padne_sampler {
     int *gtri = nullptr, *mesh_layer = nullptr, *bin_off = nullptr, *bin_face = nullptr;
     long long *toff = nullptr;
     unsigned long long *tested = nullptr;
+    double *T = nullptr, *kappa = nullptr;        // the field block [n_field][n_vert] and kappa[n_mesh] of padne_sampler_set_fields
+    int32_t n_field = 0;
     // host
     std::vector<LayerGrid> grid;
     std::vector<int64_t> layer_faces, layer_entries;
@@ -176,7 +332,7 @@ struct padne_sampler {
 
 static void sampler_free(padne_sampler *s) {
     if (s == nullptr) return;
-    void *blocks[] = {s->xy, s->sigma, s->V, s->gtri, s->mesh_layer, s->bin_off, s->bin_face, s->toff, s->tested};
+    void *blocks[] = {s->xy, s->sigma, s->V, s->gtri, s->mesh_layer, s->bin_off, s->bin_face, s->toff, s->tested, s->T, s->kappa};
     for (void *p : blocks)
         if (p) pool_free(s->owner, p);
     delete s;
@@ -485,4 +641,151 @@ extern "C" int padne_sampler_stats(const padne_sampler *s, int32_t layer, int64_
     seconds_out[1] = s->build_seconds;
     seconds_out[2] = s->last_kernel_seconds;
     return PADNE_OK;
+}
+
+// ---- thermal images ------------------------------------------------------------------------------------------------------
+
+extern "C" int padne_sampler_set_fields(padne_ctx *ctx, padne_sampler *s, int32_t n_field, const double *fields_host,
+                                        const double *kappa) {
+    PADNE_REQUIRE(ctx && s, "null argument");
+    PADNE_REQUIRE(s->owner == ctx, "the sampler belongs to another context");
+    PADNE_REQUIRE(n_field >= 0 && n_field <= kMaxSampleFields, "a sampler takes at most 256 fields");
+    PADNE_REQUIRE(n_field == 0 || s->n_vert == 0 || fields_host, "null argument");
+    PADNE_HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    double *T = nullptr, *kap = nullptr;
+    if (n_field > 0) {
+        PADNE_TRY(sampler_alloc(ctx, &T, (size_t)n_field * (size_t)s->n_vert));
+        if (kappa && sampler_alloc(ctx, &kap, (size_t)s->n_mesh) != PADNE_OK) {
+            pool_free(ctx, T);
+            return PADNE_E_NOMEM;
+        }
+        hipError_t e = hipSuccess;
+        if (s->n_vert > 0)
+            e = hipMemcpyAsync(T, fields_host, sizeof(double) * (size_t)n_field * (size_t)s->n_vert, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && kap && s->n_mesh > 0)
+            e = hipMemcpyAsync(kap, kappa, sizeof(double) * (size_t)s->n_mesh, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) {
+            pool_free(ctx, T);
+            if (kap) pool_free(ctx, kap);
+            PADNE_HIP_CHECK(e);
+        }
+    }
+    PADNE_HIP_CHECK(hipStreamSynchronize(st));      // nothing queued reads the block that leaves
+    if (s->T) pool_free(ctx, s->T);
+    if (s->kappa) pool_free(ctx, s->kappa);
+    s->T = T;
+    s->kappa = kap;
+    s->n_field = n_field;
+    return PADNE_OK;
+}
+
+static int sampler_field_checks(padne_ctx *ctx, padne_sampler *s, int32_t layer, int64_t n, const void *face_out,
+                                const void *t_out, const void *q_out, const void *hot_out, const void *hot_field_out) {
+    PADNE_REQUIRE(ctx && s, "null argument");
+    PADNE_REQUIRE(s->owner == ctx, "the sampler belongs to another context");
+    PADNE_REQUIRE(s->n_field > 0, "the sampler has no fields: padne_sampler_set_fields comes first");
+    PADNE_REQUIRE(q_out == nullptr || s->kappa, "the heat flux needs the sheet conductances kappa");
+    PADNE_REQUIRE(layer >= 0 && layer < s->n_layer, "layer out of range");
+    PADNE_REQUIRE(n >= 0 && n <= kMaxSamples, "at most 2^26 samples in one call");
+    PADNE_REQUIRE((t_out == nullptr && q_out == nullptr) || (long long)s->n_field * n <= kMaxSampleValues,
+                  "at most 2^28 values (fields x samples) in one call that returns every field");
+    PADNE_REQUIRE(n == 0 || (face_out && hot_out && hot_field_out), "null argument");
+    return PADNE_OK;
+}
+
+// the shared body of the two field entries: q_host != nullptr -> points, else the raster r with its tops
+static int sampler_field_query(padne_ctx *ctx, padne_sampler *s, int32_t layer, int64_t n, const double *q_host,
+                               const RasterSpec &r, int32_t *face_out, double *t_out, double *q_out, double *hot_out,
+                               int32_t *hot_field_out, double *top_out, int64_t *top_pixel_out) {
+    PADNE_HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    Scratch sc(ctx);
+    const size_t F = (size_t)s->n_field, n_tile = nblk(n);
+    double *d_q = nullptr, *d_t = nullptr, *d_flux = nullptr, *d_hot = nullptr, *d_tile_v = nullptr, *d_top_v = nullptr;
+    long long *d_tile_p = nullptr, *d_top_p = nullptr;
+    int *d_face = nullptr, *d_hot_field = nullptr;
+    if (q_host) PADNE_TRY(sc.alloc(&d_q, (size_t)n * 2));
+    PADNE_TRY(sc.alloc(&d_face, (size_t)n));
+    if (t_out) PADNE_TRY(sc.alloc(&d_t, F * (size_t)n));
+    if (q_out) PADNE_TRY(sc.alloc(&d_flux, F * (size_t)n * 2));
+    PADNE_TRY(sc.alloc(&d_hot, (size_t)n));
+    PADNE_TRY(sc.alloc(&d_hot_field, (size_t)n));
+    if (!q_host) {
+        PADNE_TRY(sc.alloc(&d_tile_v, (F + 1) * n_tile));
+        PADNE_TRY(sc.alloc(&d_tile_p, (F + 1) * n_tile));
+        PADNE_TRY(sc.alloc(&d_top_v, F + 1));
+        PADNE_TRY(sc.alloc(&d_top_p, F + 1));
+    }
+    PADNE_HIP_CHECK(hipMemsetAsync(s->tested, 0, sizeof(unsigned long long), st));
+    if (q_host) PADNE_HIP_CHECK(hipMemcpyAsync(d_q, q_host, sizeof(double) * 2 * (size_t)n, hipMemcpyHostToDevice, st));
+    PADNE_HIP_CHECK(hipEventRecord(ctx->ev0, st));
+    if (q_host) {
+        hipLaunchKernelGGL(sample_fields_kernel<false>, dim3(n_tile), dim3(256), 0, st, s->grid[layer], s->bin_off, s->bin_face,
+                           s->gtri, s->xy, (int)s->n_mesh, s->toff, s->kappa, s->T, (int)s->n_field, (long long)s->n_vert,
+                           (long long)n, d_q, r, d_face, d_t, d_flux, d_hot, d_hot_field, (double *)nullptr,
+                           (long long *)nullptr, s->tested);
+        PADNE_HIP_CHECK(hipGetLastError());
+    } else {
+        hipLaunchKernelGGL(sample_fields_kernel<true>, dim3(n_tile), dim3(256), 0, st, s->grid[layer], s->bin_off, s->bin_face,
+                           s->gtri, s->xy, (int)s->n_mesh, s->toff, s->kappa, s->T, (int)s->n_field, (long long)s->n_vert,
+                           (long long)n, (const double *)nullptr, r, d_face, d_t, d_flux, d_hot, d_hot_field, d_tile_v,
+                           d_tile_p, s->tested);
+        PADNE_HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(sample_fields_fold_kernel, dim3(F + 1), dim3(256), 0, st, (long long)n_tile, d_tile_v, d_tile_p,
+                           d_top_v, d_top_p);
+        PADNE_HIP_CHECK(hipGetLastError());
+    }
+    PADNE_HIP_CHECK(hipEventRecord(ctx->ev1, st));
+    unsigned long long tested = 0;
+    PADNE_HIP_CHECK(hipMemcpyAsync(&tested, s->tested, sizeof(tested), hipMemcpyDeviceToHost, st));
+    PADNE_HIP_CHECK(hipMemcpyAsync(face_out, d_face, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st));
+    if (t_out) PADNE_HIP_CHECK(hipMemcpyAsync(t_out, d_t, sizeof(double) * F * (size_t)n, hipMemcpyDeviceToHost, st));
+    if (q_out) PADNE_HIP_CHECK(hipMemcpyAsync(q_out, d_flux, sizeof(double) * 2 * F * (size_t)n, hipMemcpyDeviceToHost, st));
+    PADNE_HIP_CHECK(hipMemcpyAsync(hot_out, d_hot, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
+    PADNE_HIP_CHECK(hipMemcpyAsync(hot_field_out, d_hot_field, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st));
+    if (!q_host) {
+        static_assert(sizeof(long long) == sizeof(int64_t), "the tops' pixels are copied as they are");
+        PADNE_HIP_CHECK(hipMemcpyAsync(top_out, d_top_v, sizeof(double) * (F + 1), hipMemcpyDeviceToHost, st));
+        PADNE_HIP_CHECK(hipMemcpyAsync(top_pixel_out, d_top_p, sizeof(int64_t) * (F + 1), hipMemcpyDeviceToHost, st));
+    }
+    PADNE_HIP_CHECK(hipStreamSynchronize(st));
+    float ms = 0.0f;
+    PADNE_HIP_CHECK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    s->last_kernel_seconds = 1e-3 * ms;
+    s->last_candidates = (int64_t)tested;
+    s->last_queries = n;
+    return PADNE_OK;
+}
+
+extern "C" int padne_sampler_field_points(padne_ctx *ctx, padne_sampler *s, int32_t layer, int64_t n, const double *xy_host,
+                                          int32_t *face_out, double *t_out, double *q_out, double *hot_out,
+                                          int32_t *hot_field_out) {
+    PADNE_TRY(sampler_field_checks(ctx, s, layer, n, face_out, t_out, q_out, hot_out, hot_field_out));
+    PADNE_REQUIRE(n == 0 || xy_host, "null argument");
+    for (int64_t i = 0; i < 2 * n; ++i) PADNE_REQUIRE(std::isfinite(xy_host[i]), "query points must be finite");
+    if (n == 0) {
+        s->last_candidates = s->last_queries = 0;
+        s->last_kernel_seconds = 0;
+        return PADNE_OK;
+    }
+    return sampler_field_query(ctx, s, layer, n, xy_host, RasterSpec{0, 0, 0, 0, 1}, face_out, t_out, q_out, hot_out,
+                               hot_field_out, nullptr, nullptr);
+}
+
+extern "C" int padne_sampler_field_raster(padne_ctx *ctx, padne_sampler *s, int32_t layer, double x0, double y0, double dx,
+                                          double dy, int64_t width, int64_t height, int32_t *face_out, double *t_out,
+                                          double *q_out, double *hot_out, int32_t *hot_field_out, double *top_out,
+                                          int64_t *top_pixel_out) {
+    PADNE_REQUIRE(width >= 1 && height >= 1, "a raster has at least one pixel");
+    PADNE_REQUIRE(width <= kMaxSamples && height <= kMaxSamples, "at most 2^26 samples in one call");
+    PADNE_TRY(sampler_field_checks(ctx, s, layer, width * height, face_out, t_out, q_out, hot_out, hot_field_out));
+    PADNE_REQUIRE(top_out && top_pixel_out, "null argument");
+    PADNE_REQUIRE(std::isfinite(x0) && std::isfinite(y0), "the raster's origin must be finite");
+    PADNE_REQUIRE(std::isfinite(dx) && std::isfinite(dy) && dx > 0 && dy > 0, "the pixel size must be finite and positive");
+    PADNE_REQUIRE(std::isfinite(x0 + ((double)(width - 1) + 0.5) * dx) && std::isfinite(y0 + ((double)(height - 1) + 0.5) * dy),
+                  "the raster's pixel centres must be finite");
+    return sampler_field_query(ctx, s, layer, width * height, nullptr, RasterSpec{x0, y0, dx, dy, (long long)width}, face_out,
+                               t_out, q_out, hot_out, hot_field_out, top_out, top_pixel_out);
 }

@@ -34,6 +34,8 @@ compute_power_density :728-745         ``power_density_kernel``
                                        ``transient_rhs_kernel`` and ``transient_report_kernel`` per step, one hierarchy per dt
 read-out under the cursor ui.py:192    ``FieldSampler``: owner face by ``sample_kernel`` over a grid of bins per layer,
                                        V interpolated in the face, J and p of the face
+thermal image (no counterpart)         ``TemperatureSampler``: the same owner, found once per query by
+                                       ``sample_fields_kernel``, then every field of a block read out at it
 =====================================  ====================================================
 
 There is no CPU fallback: every entry point that computes raises
@@ -5366,6 +5368,24 @@ def check_raster(prob, layer, origin, pixel, width, height) -> tuple:
     return layer_i, x0, y0, dx, dy, w, h
 
 
+def check_sample_line(prob, layer, start, end, n) -> tuple:
+    """(layer index, the points (n, 2), their arc lengths (n,)) of a line of ``n`` >= 2 points from ``start`` to ``end``
+    inclusive, or ValueError: the ends are finite (x, y), ``n`` an integer of at most MAX_SAMPLE_POINTS."""
+    _layer_index(prob, layer)
+    a, b = _cut_point(start, 0, "the line's start"), _cut_point(end, 0, "the line's end")
+    try:
+        count = int(n)
+    except (TypeError, ValueError):
+        raise ValueError("a line has an integer number of points") from None
+    if count != n or count < 2:
+        raise ValueError("a line has at least 2 points")
+    if count > MAX_SAMPLE_POINTS:
+        raise ValueError(f"{count} sample points: at most {MAX_SAMPLE_POINTS} in one call")
+    xy = np.stack([np.linspace(a[0], b[0], count), np.linspace(a[1], b[1], count)], axis=1)
+    layer_i, pts = check_sample_points(prob, layer, xy)
+    return layer_i, pts, np.linspace(0.0, math.hypot(b[0] - a[0], b[1] - a[1]), count)
+
+
 class FieldSampler:
     """Reads a :class:`Solution` out at arbitrary points: built once, it keeps the meshes, the potentials and a
     point-location index on the device and answers ``points``, ``line`` and ``raster`` until ``close`` (a context manager).
@@ -5440,19 +5460,7 @@ class FieldSampler:
     def line(self, layer, start, end, n: int) -> FieldSamples:
         """``n`` >= 2 points from ``start`` to ``end`` inclusive (``np.linspace`` per coordinate), with ``arc_length``
         ``np.linspace(0, |end - start|, n)``: the profile along a trace."""
-        _layer_index(self.problem, layer)
-        a, b = _cut_point(start, 0, "the line's start"), _cut_point(end, 0, "the line's end")
-        try:
-            count = int(n)
-        except (TypeError, ValueError):
-            raise ValueError("a line has an integer number of points") from None
-        if count != n or count < 2:
-            raise ValueError("a line has at least 2 points")
-        if count > MAX_SAMPLE_POINTS:
-            raise ValueError(f"{count} sample points: at most {MAX_SAMPLE_POINTS} in one call")
-        xy = np.stack([np.linspace(a[0], b[0], count), np.linspace(a[1], b[1], count)], axis=1)
-        layer_i, pts = check_sample_points(self.problem, layer, xy)
-        arc = np.linspace(0.0, math.hypot(b[0] - a[0], b[1] - a[1]), count)
+        layer_i, pts, arc = check_sample_line(self.problem, layer, start, end, n)
         return self._samples(layer_i, pts, self._device().points(layer_i, pts), arc=arc)
 
     def raster(self, layer, origin, pixel, width: int, height: int) -> FieldSamples:
@@ -5460,6 +5468,235 @@ class FieldSampler:
         (row j, column i) centred at (origin.x + (i + 0.5) dx, origin.y + (j + 0.5) dy).  Arrays are (height, width)."""
         layer_i, x0, y0, dx, dy, w, h = check_raster(self.problem, layer, origin, pixel, width, height)
         raw = self._device().raster(layer_i, x0, y0, dx, dy, w, h)
+        xs, ys = x0 + (np.arange(w) + 0.5) * dx, y0 + (np.arange(h) + 0.5) * dy
+        pts = np.stack(np.broadcast_arrays(xs[None, :], ys[:, None]), axis=2)
+        return self._samples(layer_i, pts, raw, shape=(h, w))
+
+    def stats(self, layer) -> dict:
+        """Index and timing figures of ``layer`` (``_hip.Sampler.stats``)."""
+        return self._device().stats(_layer_index(self.problem, layer))
+
+
+# --------------------------------------------------------------------------------------------
+# thermal images: temperature fields at points, along lines and on rasters
+# --------------------------------------------------------------------------------------------
+
+MAX_SAMPLE_FIELDS = 256
+MAX_SAMPLE_VALUES = 2 ** 28
+
+
+@dataclass
+class TemperatureSamples:
+    """What a :class:`TemperatureSampler` returns.  ``points``, ``face``, ``mesh`` and ``arc_length`` as in
+    :class:`FieldSamples` (-1 / -1 outside the copper).  With F fields and n samples, or a raster of (height, width):
+
+    - ``temperature`` (F, n) or (F, height, width): every field interpolated in the owner face, NaN outside the copper;
+      None with ``per_field=False``;
+    - ``heat_flux`` (F, n, 2) or (F, height, width, 2): -kappa grad T of the owner face [W per mesh unit of length]; None
+      unless ``flux=True``;
+    - ``hottest`` and ``hottest_field`` (int32): the maximum over the fields per sample and the field that attains it, by
+      the sequential rule of :func:`envelope_of` (field 0 first, replaced on strictly greater); NaN and -1 outside;
+    - ``names``: the fields' names, ``hottest_field`` indexes them;
+    - ``tops``: None for points and lines; for a raster F + 1 entries, one per field and a last one for ``hottest``, each
+      ``(T, row, column, x, y)`` of the hottest pixel that lies on copper -- the lowest ``row * width + column`` keeps a
+      tie -- or None where no pixel does."""
+    points: np.ndarray
+    face: np.ndarray
+    mesh: np.ndarray
+    temperature: Optional[np.ndarray]
+    heat_flux: Optional[np.ndarray]
+    hottest: np.ndarray
+    hottest_field: np.ndarray
+    names: list
+    arc_length: Optional[np.ndarray] = None
+    tops: Optional[list] = None
+
+
+def check_temperature_fields(prob, fields, names=None) -> tuple:
+    """(the meshes of field 0 as (layer index, Mesh) in flat order, the values as an (F, n_vert) block, the names), or
+    ValueError: ``fields`` is a sequence of 1 <= F <= MAX_SAMPLE_FIELDS fields, each per layer of ``prob`` a list of
+    :class:`padne_amd.mesh.ZeroForm` -- with the layers and meshes of field 0, per mesh the same Mesh or one of equal
+    ``points`` and ``triangles``, and one finite value per vertex.  ``names`` names the fields (default 0 .. F - 1)."""
+    try:
+        fields = list(fields)
+    except TypeError:
+        raise ValueError("fields must be a sequence of temperature fields") from None
+    count = len(fields)
+    if not 1 <= count <= MAX_SAMPLE_FIELDS:
+        raise ValueError(f"{count} fields: a TemperatureSampler takes 1 to {MAX_SAMPLE_FIELDS}")
+    names = list(range(count)) if names is None else list(names)
+    if len(names) != count:
+        raise ValueError(f"{len(names)} names for {count} fields")
+    n_layers = len(prob.layers)
+    flat, rows = [], []
+    for f, (name, fld) in enumerate(zip(names, fields)):
+        what = f"field {name!r}"
+        if fld is None:
+            raise ValueError(f"{what} is None: a report made with per_case_fields=False keeps no field to sample")
+        try:
+            layers = [list(per_layer) for per_layer in fld]
+        except TypeError:
+            raise ValueError(f"{what} must hold, per layer, a list of ZeroForms") from None
+        if len(layers) != n_layers:
+            raise ValueError(f"{what} has {len(layers)} layers, the Problem has {n_layers}")
+        values, at = [], 0
+        for li, per_layer in enumerate(layers):
+            if f and len(per_layer) != sum(1 for lj, _ in flat if lj == li):
+                raise ValueError(f"{what}, layer {li}: {len(per_layer)} meshes, field {names[0]!r} has "
+                                 f"{sum(1 for lj, _ in flat if lj == li)}")
+            for mi, zf in enumerate(per_layer):
+                where = f"{what}, layer {li}, mesh {mi}"
+                msh, vals = getattr(zf, "mesh", None), getattr(zf, "values", None)
+                if msh is None or vals is None or not hasattr(msh, "points") or not hasattr(msh, "triangles"):
+                    raise ValueError(f"{where}: not a ZeroForm on a mesh with points and triangles")
+                if f == 0:
+                    flat.append((li, msh))
+                else:
+                    own = flat[at][1]
+                    if msh is not own and not (np.array_equal(np.asarray(msh.points), np.asarray(own.points)) and
+                                               np.array_equal(np.asarray(msh.triangles), np.asarray(own.triangles))):
+                        raise ValueError(f"{where}: another mesh than field {names[0]!r}'s")
+                try:
+                    vals = np.asarray(vals, dtype=DTYPE).reshape(-1)
+                except (TypeError, ValueError):
+                    raise ValueError(f"{where}: the values are not numbers") from None
+                n_vert = len(np.asarray(flat[at][1].points).reshape(-1, 2))
+                if len(vals) != n_vert:
+                    raise ValueError(f"{where}: {len(vals)} values for {n_vert} vertices")
+                if not np.isfinite(vals).all():
+                    raise ValueError(f"{where}: the values are not finite")
+                values.append(vals)
+                at += 1
+        rows.append(np.concatenate(values) if values else np.zeros(0, dtype=DTYPE))
+    return flat, np.ascontiguousarray(np.stack(rows)), names
+
+
+class TemperatureSampler:
+    """Reads a block of temperature fields out at arbitrary points: the thermal image, the profile along a trace, the
+    temperature at a sensor.  A *field* is what the thermal reports hold -- per layer, per connected mesh, a ZeroForm of T
+    (``ThermalReport.temperatures``, ``ThermalEnvelope.temperatures``, ``TransientReport.temperatures[i]``,
+    ``TransientEnvelope.temperatures``); ``fields`` is a sequence of them on the meshes of field 0.  Built once, it keeps the
+    meshes, the fields and :class:`FieldSampler`'s point-location index on the device until ``close`` (a context manager),
+    and every query locates each point once and reads all fields at it.
+
+    The owner of a point is :class:`FieldSampler`'s.  ``temperature`` is the linear interpolant of the owner's corner values
+    with the weights side / (sum of the sides), so at a vertex it is the vertex value itself; ``heat_flux`` is -kappa grad T
+    of the owner, kappa the sheet conductance ``model`` (a :class:`ThermalModel`, resolved by :func:`check_thermal_model`)
+    gives the owner's layer -- without a model, asking for it is a ValueError.  See :class:`TemperatureSamples`.
+
+    Limits: disconnected meshes carry no field and take no part (a point on them is outside the copper: NaN, not ambient);
+    there is no interpolation in time between kept snapshots; one GPU.  ``bins_hint`` as in :class:`FieldSampler`."""
+
+    def __init__(self, prob, fields, *, names=None, model=None, bins_hint: int = 0):
+        self.problem = prob
+        flat, block, self.names = check_temperature_fields(prob, fields, names)
+        checked = None
+        if model is not None:
+            checked = model if isinstance(model, CheckedThermalModel) else check_thermal_model(prob, model)
+        self.n_fields = block.shape[0]
+        pts = [np.asarray(msh.points, dtype=DTYPE).reshape(-1, 2) for _, msh in flat]
+        tris = [np.asarray(msh.triangles, dtype=np.int32).reshape(-1, 3) for _, msh in flat]
+        layer_of = [li for li, _ in flat]
+        self._first_mesh = [sum(1 for lj in layer_of if lj < li) for li in range(len(prob.layers))]
+        mvo = _offsets([len(p) for p in pts])
+        self._mto = _offsets([len(t) for t in tris])
+        cat = lambda arrays, shape, dtype: (np.concatenate(arrays) if arrays else np.zeros(shape, dtype=dtype))  # noqa: E731
+        self._kappa = None if checked is None else np.array([checked.kappa[li] for li in layer_of], dtype=DTYPE)
+        # the handle is a FieldSampler's: zero potentials, the layers' electrical conductances
+        self._dev = _hip.Sampler(get_context(), cat(pts, (0, 2), DTYPE), cat(tris, (0, 3), np.int32), mvo, self._mto, layer_of,
+                                 [float(prob.layers[li].conductance) for li in layer_of], len(prob.layers),
+                                 np.zeros(block.shape[1], dtype=DTYPE), bins_hint)
+        try:
+            self._dev.set_fields(block, self._kappa)
+        except Exception:
+            self.close()
+            raise
+
+    @classmethod
+    def of_reports(cls, prob, reports, *, envelope=None, model=None, bins_hint: int = 0):
+        """Of one :class:`ThermalReport` or a list of them (the load cases of :func:`solve_meshed_thermal`), and optionally
+        their :class:`ThermalEnvelope`: the cases in order named 0 .. k - 1, then the field ``"envelope"``."""
+        reports = [reports] if isinstance(reports, ThermalReport) else list(reports)
+        if not all(isinstance(r, ThermalReport) for r in reports):
+            raise ValueError("reports must be a ThermalReport or a sequence of them")
+        fields, names = [r.temperatures for r in reports], list(range(len(reports)))
+        if envelope is not None:
+            if not isinstance(envelope, ThermalEnvelope):
+                raise ValueError("envelope must be a ThermalEnvelope")
+            fields.append(envelope.temperatures)
+            names.append("envelope")
+        return cls(prob, fields, names=names, model=model, bins_hint=bins_hint)
+
+    @classmethod
+    def of_transient(cls, prob, report, *, model=None, bins_hint: int = 0):
+        """Of a :class:`TransientReport` (also ``PeriodicReport.cycle``): the kept snapshots in order, named by their
+        ``snapshot_times``, then ``report.envelope.temperatures`` as ``"envelope"`` -- alone where no field was kept."""
+        if not isinstance(report, TransientReport):
+            raise ValueError("report must be a TransientReport")
+        fields = list(report.temperatures or []) + [report.envelope.temperatures]
+        names = list(report.snapshot_times or [])[:len(fields) - 1] + ["envelope"]
+        return cls(prob, fields, names=names, model=model, bins_hint=bins_hint)
+
+    def close(self) -> None:
+        if getattr(self, "_dev", None) is not None:
+            self._dev.close()
+        self._dev = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _device(self) -> _hip.Sampler:
+        if self._dev is None:
+            raise ValueError("the TemperatureSampler is closed")
+        return self._dev
+
+    def _check_outputs(self, n: int, flux: bool, per_field: bool) -> None:
+        if flux and self._kappa is None:
+            raise ValueError("heat_flux needs the sheet conductances: give the TemperatureSampler a model")
+        if (per_field or flux) and self.n_fields * n > MAX_SAMPLE_VALUES:
+            raise ValueError(f"{self.n_fields} fields x {n} samples: at most {MAX_SAMPLE_VALUES} values in one call that "
+                             "returns every field (per_field=False without flux returns the hottest alone)")
+
+    def _samples(self, layer_i: int, points, raw, shape=None, arc=None) -> TemperatureSamples:
+        gface, t, q, hot, hot_field = raw[:5]
+        g = gface.astype(np.int64)
+        m = np.searchsorted(self._mto, g, side="right") - 1
+        inside = g >= 0
+        mesh_i = np.where(inside, m - self._first_mesh[layer_i], -1)
+        face = np.where(inside, g - self._mto[np.clip(m, 0, len(self._mto) - 1)], -1)
+        tops = None
+        if shape is not None:
+            mesh_i, face, hot, hot_field = (a.reshape(shape) for a in (mesh_i, face, hot, hot_field))
+            t = None if t is None else t.reshape((self.n_fields,) + shape)
+            q = None if q is None else q.reshape((self.n_fields,) + shape + (2,))
+            tops = []
+            for value, pixel in zip(raw[5], raw[6]):
+                row, col = divmod(int(pixel), shape[1])
+                tops.append(None if pixel < 0 else (float(value), row, col, float(points[row, col, 0]), float(points[row, col, 1])))
+        return TemperatureSamples(points=points, face=face, mesh=mesh_i, temperature=t, heat_flux=q, hottest=hot,
+                                  hottest_field=hot_field, names=list(self.names), arc_length=arc, tops=tops)
+
+    def points(self, layer, xy, *, flux: bool = False, per_field: bool = True) -> TemperatureSamples:
+        """The fields at the points ``xy`` (n, 2) of ``layer``."""
+        layer_i, pts = check_sample_points(self.problem, layer, xy)
+        self._check_outputs(len(pts), flux, per_field)
+        return self._samples(layer_i, pts, self._device().field_points(layer_i, pts, per_field, flux))
+
+    def line(self, layer, start, end, n: int, *, flux: bool = False, per_field: bool = True) -> TemperatureSamples:
+        """``n`` >= 2 points from ``start`` to ``end`` inclusive with their ``arc_length``, as :meth:`FieldSampler.line`."""
+        layer_i, pts, arc = check_sample_line(self.problem, layer, start, end, n)
+        self._check_outputs(len(pts), flux, per_field)
+        return self._samples(layer_i, pts, self._device().field_points(layer_i, pts, per_field, flux), arc=arc)
+
+    def raster(self, layer, origin, pixel, width: int, height: int, *, flux: bool = False,
+               per_field: bool = True) -> TemperatureSamples:
+        """The fields at the pixel centres of :meth:`FieldSampler.raster`'s raster, arrays (F, height, width), and ``tops``."""
+        layer_i, x0, y0, dx, dy, w, h = check_raster(self.problem, layer, origin, pixel, width, height)
+        self._check_outputs(w * h, flux, per_field)
+        raw = self._device().field_raster(layer_i, x0, y0, dx, dy, w, h, per_field, flux)
         xs, ys = x0 + (np.arange(w) + 0.5) * dx, y0 + (np.arange(h) + 0.5) * dy
         pts = np.stack(np.broadcast_arrays(xs[None, :], ys[:, None]), axis=2)
         return self._samples(layer_i, pts, raw, shape=(h, w))
