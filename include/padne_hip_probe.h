@@ -1,11 +1,14 @@
 /* padne_hip_probe.h -- TEST-ONLY probes of libpadne_hip.so.  Neither the drop-in boundary (include/padne_hip.h) nor the
- * multi-rank scaffolding (include/padne_hip_test.h): seven entries.  padne_test_product drives a single product launcher of the
+ * multi-rank scaffolding (include/padne_hip_test.h): nine entries.  padne_test_product drives a single product launcher of the
  * solver on inputs a test chooses, so that every SpMV / SpMM kernel form and epilogue can be held against a host reference;
  * padne_test_kkt_state copies one device array of a padne_kkt plan out, so that every stage of the plan can;
  * padne_test_amg_state copies out what a level of the multigrid hierarchy decided in its setup, padne_test_amg_tail hands
  * out the gathered operator of a row-partitioned hierarchy; padne_test_halo_exchange and padne_test_amg_apply_dist run one
  * halo exchange and one cycle of a row-partitioned hierarchy on a test's vector; padne_test_pool_guard reads the counters of
- * the device allocator's guarded mode and runs its self-test.  Bound by padne_amd/_hip.py (PROBE_SIGNATURES). */
+ * the device allocator's guarded mode and runs its self-test; padne_test_scan runs one exclusive scan, in any of its host
+ * forms, on counts a test chooses, and padne_test_csr_op one transpose or sparse product of the multigrid setup on matrices a
+ * test chooses, so that the sparse primitives under the assembly and the setup can be held against host references at their
+ * own limits.  Bound by padne_amd/_hip.py (PROBE_SIGNATURES). */
 #ifndef PADNE_HIP_PROBE_H
 #define PADNE_HIP_PROBE_H
 
@@ -128,6 +131,34 @@ int padne_test_amg_apply_dist(padne_ctx *ctx, padne_csr *a, const double *r_host
  * the last violation; and in out[7] the fill byte (-1: mode off), or after op 2 whether every byte read back was the fill
  * byte (1 / 0).  A violation is only ever counted: nothing aborts. */
 int padne_test_pool_guard(padne_ctx *ctx, int32_t op, int64_t *out);
+
+/* ONE exclusive scan of int32 counts (assemble.hip; tests/test_sparse_primitives_vs_reference.py), through the library's own
+ * host forms: nothing is instantiated here.  in_host[n] is uploaded to a device buffer that starts `misalign` (0 to 3) int32
+ * elements behind a 16-byte boundary; `out` (n + 1 elements) lies at the same offset of a buffer of its own, filled with 0xff
+ * bytes first, or with in_place != 0 is the input buffer itself.  The scan runs in the form asked for and out[0 .. n] is copied
+ * to out_host.
+ *   PLAIN     exclusive_scan_i32: info[1] = the total where the form reports one (PADNE_OK, PADNE_E_TOOLARGE), else -1;
+ *             info[2] = -1
+ *   FLAGGED   exclusive_scan_i32_flagged: info[1] = the total, info[2] = the negative flag
+ *   ASYNC     exclusive_scan_i32_async (nothing read back): info[1] = info[2] = -1
+ *   HALVES    scan_i32_begin / scan_i32_end with the total wanted: info[1], info[2] = what scan_i32_end handed out
+ * info[0] = the return code of the form.  The entry itself returns PADNE_OK whenever the probe worked, whatever the scan
+ * returned; PADNE_E_INVALID for an unknown form, a misalignment outside 0 .. 3, or in_place with n > 32768 (in == out is
+ * documented for the one-workgroup kernel only).  Waits for the context's stream. */
+enum { PADNE_TEST_SCAN_PLAIN = 0, PADNE_TEST_SCAN_FLAGGED = 1, PADNE_TEST_SCAN_ASYNC = 2, PADNE_TEST_SCAN_HALVES = 3 };
+int padne_test_scan(padne_ctx *ctx, int32_t form, int64_t n, const int32_t *in_host, int32_t misalign, int32_t in_place,
+                    int32_t *out_host, int64_t *info);
+
+/* ONE transpose or sparse product of the multigrid setup (amg.hip: transpose, spgemm) on the caller's matrices, as a new
+ * matrix the caller destroys (tests/test_sparse_primitives_vs_reference.py).  The setup's own entries: nothing is
+ * instantiated here.
+ *   TRANSPOSE      out = X^T               (Y, Z unused)
+ *   MATMUL         out = X Y               (Z unused); a sum that is exactly zero is not stored
+ *   MATMUL_CHAIN   out = X (Y Z), with Y Z left in its merge slots and read from there by the second product, as the setup
+ *                  forms R (A P); Y Z comes back as a matrix, and is read as one, only where its product had to be split
+ * PADNE_E_INVALID when the shapes do not chain.  Waits for the context's stream. */
+enum { PADNE_TEST_CSR_TRANSPOSE = 0, PADNE_TEST_CSR_MATMUL = 1, PADNE_TEST_CSR_MATMUL_CHAIN = 2 };
+int padne_test_csr_op(padne_ctx *ctx, int32_t op, const padne_csr *X, const padne_csr *Y, const padne_csr *Z, padne_csr **out);
 
 #ifdef __cplusplus
 }

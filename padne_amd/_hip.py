@@ -244,7 +244,8 @@ TEST_SIGNATURES = {
 
 # the test probes (include/padne_hip_probe.h): one product launcher of the solver, run once on a test's inputs; one device
 # array of a padne_kkt plan, copied out; what a multigrid level decided in its setup, copied out; the gathered operator, one
-# halo exchange and one cycle of a row-partitioned hierarchy
+# halo exchange and one cycle of a row-partitioned hierarchy; the counters of the allocator's guarded mode; one exclusive scan
+# and one transpose or sparse product of the multigrid setup on a test's inputs
 PROBE_SIGNATURES = {
     "padne_test_product": (C.c_int, [_P, _P, C.c_int32, _I64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P,
                                      _P, _P, _P, _P, C.c_double, _P, _PF64, _I64, _PI32]),
@@ -254,6 +255,8 @@ PROBE_SIGNATURES = {
     "padne_test_halo_exchange": (C.c_int, [_P, C.c_int32, _PF64, _PF64]),
     "padne_test_amg_apply_dist": (C.c_int, [_P, _P, _PF64, _PF64]),
     "padne_test_pool_guard": (C.c_int, [_P, C.c_int32, _P]),
+    "padne_test_scan": (C.c_int, [_P, C.c_int32, _I64, _PI32, C.c_int32, C.c_int32, _PI32, _PI64]),
+    "padne_test_csr_op": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.POINTER(_P)]),
 }
 
 _lib = None

@@ -3034,6 +3034,26 @@ struct SlotRows {
     }
 };
 
+// the rows of a product without their exact zeros, in place (one thread per row: runs only when compact_rows met one)
+__global__ void drop_zero_slots(int n, const int *__restrict__ place, long long *__restrict__ key, double *__restrict__ val,
+                                int *__restrict__ row_len) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int p = place[i], len = row_len[i];
+    int o = 0;
+    for (int k = 0; k < len; ++k) {
+        const double v = val[p + k];
+        if (v != 0.0) {
+            if (o != k) {
+                key[p + o] = key[p + k];
+                val[p + o] = v;
+            }
+            ++o;
+        }
+    }
+    row_len[i] = o;
+}
+
 __global__ void slot_row_ends(int n, const int *__restrict__ slot_ptr, const int *__restrict__ row_len, int *__restrict__ end) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) end[i] = slot_ptr[i] + row_len[i];
@@ -3237,8 +3257,31 @@ static int spgemm(padne_ctx *ctx, const padne_csr *X, const padne_csr *Y, padne_
         return PADNE_OK;
     }
     auto trampoline = [](void *f) -> int { return (*static_cast<const std::function<int()> *>(f))(); };
-    return csr_from_slots(ctx, n, Y->n_cols, row_begin != nullptr ? row_begin : slot_ptr, key, val, row_len, C,
-                          while_multiplying != nullptr ? +trampoline : nullptr, const_cast<std::function<int()> *>(while_multiplying));
+    // Exact zeros are not stored, here as in the assembly and the merges: a sum whose products cancel exactly (a stored 0.0
+    // otherwise) is dropped.  The row kernels keep the symbolic rows -- what reads a product in its slots sees those -- and
+    // such sums are rare, so the product is compacted as it is while compact_rows, which has every value in a register
+    // anyway, raises a flag over a zero; only then the rows are cleaned in their slots and compacted once more.
+    const int *place = row_begin != nullptr ? row_begin : slot_ptr;
+    int *zero_flag = nullptr;
+    PADNE_TRY(sc.alloc(&zero_flag, 1));
+    PADNE_HIP_CHECK(hipMemsetAsync(zero_flag, 0, sizeof(int), s));
+    PADNE_TRY(csr_from_slots(ctx, n, Y->n_cols, place, key, val, row_len, C,
+                             while_multiplying != nullptr ? +trampoline : nullptr, const_cast<std::function<int()> *>(while_multiplying),
+                             zero_flag));
+    int h_zero = 0;
+    int rc = n > 0 ? read_back(ctx, zero_flag, sizeof(int), &h_zero) : PADNE_OK;
+    if (rc == PADNE_OK && h_zero != 0) {
+        padne_csr_destroy(*C);
+        *C = nullptr;
+        hipLaunchKernelGGL(drop_zero_slots, dim3(nblk(n)), dim3(256), 0, s, n, place, key, val, row_len);
+        rc = hipGetLastError() == hipSuccess ? csr_from_slots(ctx, n, Y->n_cols, place, key, val, row_len, C) : PADNE_E_HIP;
+    }
+    if (rc != PADNE_OK && *C != nullptr) {
+        (void)hipStreamSynchronize(s);
+        padne_csr_destroy(*C);
+        *C = nullptr;
+    }
+    return rc;
 }
 
 // ---- W = P - c D^-1 (A P): coarse correction and post-smoothing of a level in ONE product ----------------------------
@@ -4782,10 +4825,6 @@ const padne_csr *amg_level_matrix(const padne_csr *A0, int level, int which) {
     return which == 0 ? L.A : (which == 1 ? L.P : L.R);
 }
 
-int csr_matmul(padne_ctx *ctx, const padne_csr *X, const padne_csr *Y, padne_csr **C) { return spgemm(ctx, X, Y, C); }
-const padne_csr *amg_level_matrix(const padne_csr *A0, int level, int which);
-int csr_transpose(padne_ctx *ctx, const padne_csr *M, padne_csr **T) { return transpose(ctx, M, T); }
-
 void amg_info(const padne_csr *A0, int *levels, double *complexity, double *setup_seconds, long long *coarse_n) {
     const Amg *amg = (const Amg *)A0->amg;
     if (!amg) return;
@@ -4841,6 +4880,54 @@ extern "C" int padne_test_amg_state(padne_ctx *ctx, const padne_csr *m, int32_t 
         int8_t *f = (int8_t *)out_host;
         for (long long i = 0; i < L.n; ++i) f[i] = f[i] == 1 ? 1 : 0;
     }
+    return PADNE_OK;
+}
+
+// ---- test entry: one transpose or sparse product of the setup on the caller's matrices (include/padne_hip_probe.h) ---------
+extern "C" int padne_test_csr_op(padne_ctx *ctx, int32_t op, const padne_csr *X, const padne_csr *Y, const padne_csr *Z,
+                                 padne_csr **out) {
+    PADNE_REQUIRE(ctx && X && out, "null argument");
+    PADNE_REQUIRE(op >= PADNE_TEST_CSR_TRANSPOSE && op <= PADNE_TEST_CSR_MATMUL_CHAIN, "unknown operation");
+    PADNE_REQUIRE(op == PADNE_TEST_CSR_TRANSPOSE || (Y != nullptr && X->n_cols == Y->n_rows), "shapes of X and Y");
+    PADNE_REQUIRE(op != PADNE_TEST_CSR_MATMUL_CHAIN || (Z != nullptr && Y->n_cols == Z->n_rows), "shapes of Y and Z");
+    PADNE_REQUIRE(X->n_rows < 2147483647LL, "row count");
+    PADNE_HIP_CHECK(hipSetDevice(ctx->device));
+    padne_csr *res = nullptr;
+    int rc = PADNE_OK;
+    if (op == PADNE_TEST_CSR_TRANSPOSE) {
+        rc = padne::transpose(ctx, X, &res);
+    } else if (op == PADNE_TEST_CSR_MATMUL) {
+        rc = padne::spgemm(ctx, X, Y, &res);
+    } else {
+        // as the setup forms R (A P): Y Z stays in its merge slots and the second product reads its rows there (it comes
+        // back as a matrix only when it had to be split)
+        padne_csr *YZ = nullptr;
+        padne::SlotRows yz_rows;
+        rc = padne::spgemm(ctx, Y, Z, &YZ, nullptr, &yz_rows);
+        if (rc == PADNE_OK && yz_rows.valid) {
+            padne_csr yz_shape;
+            yz_shape.n_rows = yz_rows.n_rows;
+            yz_shape.n_cols = yz_rows.n_cols;
+            rc = padne::spgemm(ctx, X, &yz_shape, &res, &yz_rows);
+        } else if (rc == PADNE_OK) {
+            rc = padne::spgemm(ctx, X, YZ, &res);
+        }
+        const hipError_t e = hipStreamSynchronize(ctx->stream);      // the slots go back to the pool with this scope
+        if (YZ) padne_csr_destroy(YZ);
+        if (rc == PADNE_OK && e != hipSuccess) {
+            padne::set_error("sparse product failed: %s", hipGetErrorString(e));
+            rc = PADNE_E_HIP;
+        }
+    }
+    if (rc == PADNE_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) {
+        padne::set_error("transpose or sparse product failed");
+        rc = PADNE_E_HIP;
+    }
+    if (rc != PADNE_OK) {
+        if (res) padne_csr_destroy(res);
+        return rc;
+    }
+    *out = res;
     return PADNE_OK;
 }
 

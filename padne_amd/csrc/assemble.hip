@@ -1401,39 +1401,6 @@ __global__ __launch_bounds__(256) void sort_long_rows_wave(long long n_list, con
     }
 }
 
-// The listed rows, one WORKGROUP each (rows of up to 1024 slots): keys and values into LDS, every thread ranks its elements
-// by counting smaller keys, sorted slots back in place -- the rank sort of sort_long_rows_wave over 256 threads.  The long
-// rows of a transposed prolongator (aggregates next to a via ring: several hundred fine rows interpolate from them) are a
-// few dozen; a wave that met them one after the other in its chunk took 1.2 ms, spread over workgroups they take 60 us.
-__global__ __launch_bounds__(256) void sort_listed_rows_block(const int *__restrict__ n_list, const int *__restrict__ row_list,
-                                                              const int *__restrict__ slot_ptr, long long *__restrict__ key,
-                                                              double *__restrict__ val) {
-    __shared__ long long Ks[kWaveSortCap];
-    __shared__ double Vs[kWaveSortCap];
-    const int cnt = *n_list;
-    for (int j = blockIdx.x; j < cnt; j += gridDim.x) {
-        const int r = row_list[j];
-        const int s0 = slot_ptr[r], n = slot_ptr[r + 1] - s0;
-        if (n > kWaveSortCap) continue;               // beyond the LDS: the one-lane merge sorts it
-        for (int e = threadIdx.x; e < n; e += 256) {
-            Ks[e] = key[s0 + e];
-            Vs[e] = val[s0 + e];
-        }
-        __syncthreads();
-        for (int e = threadIdx.x; e < n; e += 256) {
-            const long long k = Ks[e];
-            int rank = 0;
-            for (int f = 0; f < n; ++f) {
-                const long long kf = Ks[f];
-                rank += (kf < k || (kf == k && f < e)) ? 1 : 0;
-            }
-            key[s0 + rank] = k;
-            val[s0 + rank] = Vs[e];
-        }
-        __syncthreads();
-    }
-}
-
 // One lane per row.  MESH=true: slots with sequence 0/1 are raw cotangent terms of the row's
 // mesh, sequence 2 is the (zero valued) diagonal placeholder every row owns, 3+k is stamp k.
 // Every column group owns at least one slot and emits at most one entry, so the in-place
@@ -1700,7 +1667,8 @@ static int compact_rows_per_wave(long long n_rows, long long nnz) {
 __global__ __launch_bounds__(256) void compact_rows(long long n_rows, const int *__restrict__ slot_ptr,
                                                     const int *__restrict__ rowptr, const long long *__restrict__ key,
                                                     const double *__restrict__ val, int *__restrict__ cols,
-                                                    double *__restrict__ vals, const int rpw) {
+                                                    double *__restrict__ vals, const int rpw, int *__restrict__ zero_flag = nullptr) {
+    // zero_flag (may be null): set when an entry that goes out is exactly zero (the sparse products look at it, see spgemm)
     // rpw: rows per wave and turn (64 for mesh-like rows; 8 or 1 for the long rows of the small coarse operators, where 64
     // rows of hundreds of entries kept a wave busy for 80 us while most of the chip had nothing to do)
     __shared__ int rp_all[4][65];
@@ -1724,8 +1692,10 @@ __global__ __launch_bounds__(256) void compact_rows(long long n_rows, const int 
                 if (rp[mid] <= k) lo = mid; else hi = mid;
             }
             const int src = sp[lo] + (k - rp[lo]);
+            const double v = val[src];
             cols[k] = (int)(key[src] >> 32);
-            vals[k] = val[src];
+            vals[k] = v;
+            if (zero_flag != nullptr && v == 0.0) *zero_flag = 1;
         }
         asm volatile("" ::: "memory");
         __builtin_amdgcn_wave_barrier();
@@ -2207,7 +2177,8 @@ int merge_slots_generic(padne_ctx *ctx, long long n_rows, const int *slot_ptr, l
 // while_scanning: called between the launch of the scan of the row lengths and the look at its total (what the caller
 // launches there, for another stream, is launched while this stream works)
 int csr_from_slots(padne_ctx *ctx, long long n_rows, long long n_cols, const int *slot_ptr, const long long *key,
-                   const double *val, const int *row_len, padne_csr **out, int (*while_scanning)(void *), void *while_scanning_arg) {
+                   const double *val, const int *row_len, padne_csr **out, int (*while_scanning)(void *), void *while_scanning_arg,
+                   int *zero_flag) {
     hipStream_t s = ctx->stream;
     Scratch sc(ctx);
     int *rowptr_tmp = nullptr;
@@ -2238,65 +2209,12 @@ int csr_from_slots(padne_ctx *ctx, long long n_rows, long long n_cols, const int
     if (e == hipSuccess && n_rows > 0) {
         const int rpw = compact_rows_per_wave(n_rows, nnz);
         hipLaunchKernelGGL(compact_rows, dim3(std::min(nblk((n_rows + rpw - 1) / rpw, 4), 65536u)), dim3(256), 0, s, n_rows, slot_ptr,
-                           m->rowptr, key, val, m->cols, m->vals, rpw);
+                           m->rowptr, key, val, m->cols, m->vals, rpw, zero_flag);
         e = hipGetLastError();
     }
     // no synchronisation: the caller's scratch goes back to the pool, whose reuse is ordered on the same stream
     if (e != hipSuccess) {
         set_error("row compaction failed: %s", hipGetErrorString(e));
-        padne_csr_destroy(m);
-        return PADNE_E_HIP;
-    }
-    *out = m;
-    return PADNE_OK;
-}
-
-// slots that are already exact (row i occupies [slot_ptr[i], slot_ptr[i+1]) completely, e.g. a transpose whose
-// counts are exact and whose rows have been sorted): no scan, no per-row compaction, one streaming pass
-__global__ void unpack_slots_kernel(long long nnz, const long long *__restrict__ key, const double *__restrict__ val,
-                                    int *__restrict__ cols, double *__restrict__ vals) {
-    for (long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k < nnz; k += (long long)gridDim.x * blockDim.x) {
-        cols[k] = (int)(key[k] >> 32);
-        vals[k] = val[k];
-    }
-}
-
-// Slots that only need sorting (a transpose: no duplicates, nothing to add or drop): every row by one wave -- rank by
-// counting smaller keys in LDS, rows of up to 64 slots at full occupancy, longer ones with the 1024-slot variant, the
-// rare rest by the one-lane insertion sort.
-int sort_slots_exact(padne_ctx *ctx, long long n_rows, const int *slot_ptr, long long *key, double *val, int *row_len_scratch) {
-    // rows of up to 64 slots: eight rows per wave and turn, sorted in 2 KiB of LDS per wave; the rows beyond that are
-    // listed and sorted by a workgroup each (sort_listed_rows_block); what exceeds even its 1024 slots is left to the
-    // one-lane merge.  Nothing here needs the host.
-    Scratch sc(ctx);
-    int *long_list = nullptr;
-    PADNE_TRY(sc.alloc(&long_list, (size_t)n_rows + 1));
-    int *n_long = row_len_scratch + n_rows;          // the scratch has n_rows + 1 entries
-    PADNE_HIP_CHECK(hipMemsetAsync(n_long, 0, sizeof(int), ctx->stream));
-    hipLaunchKernelGGL((sort_long_rows_wave<64, 8>), dim3(std::min(nblk(n_rows, 32), 8192u)), dim3(256), 0, ctx->stream, n_rows,
-                       (const int *)nullptr, slot_ptr, key, val, 2, 0, n_long, (const int *)nullptr, long_list);
-    hipLaunchKernelGGL(sort_listed_rows_block, dim3(1024), dim3(256), 0, ctx->stream, (const int *)n_long, (const int *)long_list,
-                       slot_ptr, key, val);
-    hipLaunchKernelGGL(merge_rows<false>, dim3(nblk(n_rows, 128)), dim3(128), 0, ctx->stream, n_rows, 0LL, 0,
-                       (const long long *)nullptr, (const double *)nullptr, slot_ptr, key, val, row_len_scratch,
-                       (int *)nullptr, kWaveSortCap + 1);
-    PADNE_HIP_CHECK(hipGetLastError());
-    return PADNE_OK;
-}
-
-int csr_from_exact_slots(padne_ctx *ctx, long long n_rows, long long n_cols, long long nnz, const int *slot_ptr,
-                         const long long *key, const double *val, padne_csr **out) {
-    hipStream_t s = ctx->stream;
-    padne_csr *m = nullptr;
-    PADNE_TRY(csr_alloc(ctx, n_rows, n_cols, nnz, &m));
-    hipError_t e = hipMemcpyAsync(m->rowptr, slot_ptr, sizeof(int32_t) * (size_t)(n_rows + 1), hipMemcpyDeviceToDevice, s);
-    if (e == hipSuccess && nnz > 0) {
-        hipLaunchKernelGGL(unpack_slots_kernel, dim3((unsigned)std::min<long long>((nnz + 255) / 256, 8192)), dim3(256), 0, s,
-                           nnz, key, val, m->cols, m->vals);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) {
-        set_error("slot unpacking failed: %s", hipGetErrorString(e));
         padne_csr_destroy(m);
         return PADNE_E_HIP;
     }
@@ -3018,6 +2936,57 @@ extern "C" int padne_nearest_vertex_ties(padne_ctx *ctx, int64_t n_points, const
     PADNE_HIP_CHECK(hipMemcpyAsync(index_out_host, d_out, sizeof(long long) * (size_t)n_query, hipMemcpyDeviceToHost, s));
     if (tie_count_out_host != nullptr)
         PADNE_HIP_CHECK(hipMemcpyAsync(tie_count_out_host, d_outc, sizeof(int) * (size_t)n_query, hipMemcpyDeviceToHost, s));
+    PADNE_HIP_CHECK(hipStreamSynchronize(s));
+    return PADNE_OK;
+}
+
+// ---- test entry: one exclusive scan of the caller's counts (include/padne_hip_probe.h) -----------------------------------
+extern "C" int padne_test_scan(padne_ctx *ctx, int32_t form, int64_t n, const int32_t *in_host, int32_t misalign,
+                               int32_t in_place, int32_t *out_host, int64_t *info) {
+    PADNE_REQUIRE(ctx && out_host && info, "null argument");
+    PADNE_REQUIRE(form >= PADNE_TEST_SCAN_PLAIN && form <= PADNE_TEST_SCAN_HALVES, "unknown form of the scan");
+    PADNE_REQUIRE(n >= 0 && n < 2147483647LL - 16 && (n == 0 || in_host != nullptr), "input of the scan");
+    PADNE_REQUIRE(misalign >= 0 && misalign <= 3, "misalignment in int32 elements, 0 to 3");
+    PADNE_REQUIRE(!in_place || n <= kScanSmall, "in == out is documented for the one-workgroup kernel only");
+    PADNE_HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    Scratch sc(ctx);
+    // (the pool's alignment is not relied on: the 16-byte boundary is found here)
+    auto at_offset = [&](int32_t *p) {
+        return reinterpret_cast<int32_t *>((reinterpret_cast<unsigned long long>(p) + 15ull) & ~15ull) + misalign;
+    };
+    int32_t *in_raw = nullptr, *out_raw = nullptr;
+    PADNE_TRY(sc.alloc(&in_raw, (size_t)n + 1 + 8));
+    int32_t *in = at_offset(in_raw), *out = in;
+    if (!in_place) {
+        PADNE_TRY(sc.alloc(&out_raw, (size_t)n + 1 + 8));
+        out = at_offset(out_raw);
+        PADNE_HIP_CHECK(hipMemsetAsync(out, 0xff, sizeof(int32_t) * (size_t)(n + 1), s));      // what the scan leaves out reads as -1
+    }
+    if (n > 0) PADNE_HIP_CHECK(hipMemcpyAsync(in, in_host, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s));
+    int64_t total = -1;        // -1: the form does not report it
+    int64_t negative = -1;
+    int rc = PADNE_OK;
+    if (form == PADNE_TEST_SCAN_PLAIN) {
+        rc = exclusive_scan_i32(ctx, in, out, n, &total);
+    } else if (form == PADNE_TEST_SCAN_FLAGGED) {
+        bool neg = false;
+        rc = exclusive_scan_i32_flagged(ctx, in, out, n, &total, &neg);
+        negative = neg ? 1 : 0;
+    } else if (form == PADNE_TEST_SCAN_ASYNC) {
+        rc = exclusive_scan_i32_async(ctx, in, out, n);
+    } else {
+        ScanTicket ticket;
+        long long h[2] = {0, 0};
+        rc = scan_i32_begin(ctx, in, out, n, &ticket, true);
+        if (rc == PADNE_OK) rc = scan_i32_end(ctx, &ticket, h);
+        total = h[0];
+        negative = h[1];
+    }
+    info[0] = rc;
+    info[1] = total;
+    info[2] = negative;
+    PADNE_HIP_CHECK(hipMemcpyAsync(out_host, out, sizeof(int32_t) * (size_t)(n + 1), hipMemcpyDeviceToHost, s));
     PADNE_HIP_CHECK(hipStreamSynchronize(s));
     return PADNE_OK;
 }

@@ -48,8 +48,9 @@ def test_probe_symbols_are_exported_and_bound():
     build.build(verbose=False)
     lib = ctypes.CDLL(_hip.LIB_PATH)
     probe = declared_symbols("padne_hip_probe.h")
-    assert probe == ["padne_test_amg_apply_dist", "padne_test_amg_state", "padne_test_amg_tail", "padne_test_halo_exchange",
-                     "padne_test_kkt_state", "padne_test_pool_guard", "padne_test_product"]
+    assert probe == ["padne_test_amg_apply_dist", "padne_test_amg_state", "padne_test_amg_tail", "padne_test_csr_op",
+                     "padne_test_halo_exchange", "padne_test_kkt_state", "padne_test_pool_guard", "padne_test_product",
+                     "padne_test_scan"]
     for name in probe:
         assert hasattr(lib, name), f"{name} declared in padne_hip_probe.h but not exported"
     assert sorted(_hip.PROBE_SIGNATURES) == probe
