@@ -748,6 +748,54 @@ int padne_thermal_source_lists(padne_ctx *ctx, const padne_thermal *th, int32_t 
  * order of A_s, of (area_f / A_s) * mean[c][f], mean the face mean of padne_thermal_report.  Two calls give the same bits. */
 int padne_thermal_source_report(padne_ctx *ctx, padne_thermal *th, int32_t n_cols, double *temperature_out);
 
+/* ---- film curves: film coefficients that depend on the temperature rise, by Newton rounds ----------
+ * No reference counterpart ("Film curves").  The film of mesh m becomes a table: knots knot_ptr[m] ..
+ * knot_ptr[m + 1] (1 to 64 of them) with h = knot_film[i] at the rise knot_rise[i] [K above ambient], linear between the
+ * knots, held constant below the first (knot_rise = 0) and above the last.  About an iterate theta, vertex v of mesh m uses
+ * the segment i that contains theta_v (the largest i with rise_i <= theta_v), s its slope (h_{i+1} - h_i) / (t_{i+1} - t_i),
+ * s = 0 in both clamped ranges, and
+ *     h = h_i + s * (theta - t_i)     g = h + s * theta     d_v = g * M_v     c_v = ((s * theta) * theta) * M_v     hM_v = h * M_v
+ * A round solves (A - diag(hM0) + diag(d)) theta' = b + c from theta: the stored diagonal of vertex v is the one rounded sum
+ * D0_v + (d_v - hM0_v), D0 the diagonal and hM0 = film[m] M_v as the create call left them (stack coupling included).  + - *
+ * only on the device, -ffp-contract=off, fixed-order folds, no floating-point atomics: a host restatement reproduces every
+ * bit, two calls give the same bits.  At theta = 0, and for a table of one knot, d_v = hM0_v in bits and c_v = 0.
+ *
+ * padne_thermal_set_film_curves follows padne_thermal_create or padne_thermal_create_stacked: the tables go to the device,
+ * the place of every vertex row's diagonal is recorded, D0 and hM0 are copied.  PADNE_E_INVALID, with nothing changed, for a
+ * table without knots or of more than 64, a rise that does not start at 0 and ascend strictly, a value that is not finite, a
+ * film that is not positive, a loss density q(theta) = h(theta) theta that does not increase strictly (q' = h_i + s_i (2 theta
+ * - t_i) must be positive at both ends of every segment; the message names the segment), an n_mesh that is not the handle's,
+ * and a first knot_film of a mesh that differs in bits from the film[m] of the create call.  n_mesh = 0 removes the curves and
+ * puts D0 and hM0 back.  A second call replaces the curves. */
+int padne_thermal_set_film_curves(padne_ctx *ctx, padne_thermal *th, int32_t n_mesh, const int32_t *knot_ptr,
+                                  const double *knot_rise, const double *knot_film);
+/* The terms for any theta_host[n_vert] (tests): g_out, c_out and hM_out[n_vert], and *beyond_out = the number of vertices
+ * above the last knot of a table of more than one knot.  A pure function of theta: no state of the handle changes. */
+int padne_thermal_film_terms(padne_ctx *ctx, padne_thermal *th, const double *theta_host, double *g_out, double *c_out,
+                             double *hM_out, int64_t *beyond_out);
+/* Linearise about the held theta of a one-column solve (from_held = 1) or about zero (from_held = 0): the stored diagonals
+ * are written through the recorded places, c and a copy of the iterate are kept for the next solve, and what was derived
+ * from A's values (the multigrid hierarchy) is dropped and rebuilt by that solve. */
+int padne_thermal_film_linearise(padne_ctx *ctx, padne_thermal *th, int32_t from_held);
+/* On a handle with curves padne_thermal_solve, padne_thermal_solve_kkt and padne_coupled_solve_kkt take one column only
+ * (PADNE_E_INVALID otherwise, nothing changed), add the kept c to the load behind the faces, the triples and the heat
+ * sources, and start the iteration from the iterate of the last linearise (about zero: from zero, the bits of the solve
+ * without curves).  padne_transient_create and padne_tsens_create refuse such a handle: PADNE_E_INVALID.
+ * padne_thermal_solve_kkt_column: padne_thermal_solve_kkt for column `col` of the finished block of n_cols columns -- the
+ * face powers of that one column go into the handle, then a one-column solve (the triples' columns are 0); also without
+ * curves.  padne_thermal_resolve: the solve again on the load the last solve of the handle formed, plus the c of the last
+ * linearise; nothing else is recomputed.  PADNE_E_INVALID without curves or without such a load. */
+int padne_thermal_solve_kkt_column(padne_ctx *ctx, padne_thermal *th, padne_kkt *plan, int32_t n_cols, int32_t col,
+                                   int64_t n_heat, const int64_t *heat_node, const int32_t *heat_col, const double *heat_val,
+                                   const padne_solve_opts *opts, double *theta_host, padne_solve_info *info);
+int padne_thermal_resolve(padne_ctx *ctx, padne_thermal *th, const padne_solve_opts *opts, double *theta_host,
+                          padne_solve_info *info);
+/* After a one-column solve: *increment_out = max_v |theta_v - the iterate of the last linearise| over the vertices,
+ * *vertex_out that vertex (the lowest on a tie; 0 and -1 without vertices), *beyond_out as padne_thermal_film_terms counts
+ * it on the new theta; and hM_v = h(theta_v) M_v, so that padne_thermal_report's film loss is sum_v M_v q(theta_v). */
+int padne_thermal_film_increment(padne_ctx *ctx, padne_thermal *th, double *increment_out, int64_t *vertex_out,
+                                 int64_t *beyond_out);
+
 /* ---- temperature sensitivities: what cools a hotspot, by adjoints ---------------------------------
  * No reference counterpart ("Temperature sensitivities").  After padne_kkt_finish_block of the n_cases load cases
  * (M x_c = r_c) and padne_thermal_solve_kkt of as many columns (A theta_c = b(x_c)) on `th`, an objective j of case c is the

@@ -174,6 +174,13 @@ SIGNATURES = {
     "padne_thermal_source_power": (C.c_int, [_P, _P, C.c_int32, _PF64]),
     "padne_thermal_source_lists": (C.c_int, [_P, _P, C.c_int32, _I64, _PI64, _PI32]),
     "padne_thermal_source_report": (C.c_int, [_P, _P, C.c_int32, _PF64]),
+    "padne_thermal_set_film_curves": (C.c_int, [_P, _P, C.c_int32, _PI32, _PF64, _PF64]),
+    "padne_thermal_film_terms": (C.c_int, [_P, _P, _PF64, _PF64, _PF64, _PF64, _PI64]),
+    "padne_thermal_film_linearise": (C.c_int, [_P, _P, C.c_int32]),
+    "padne_thermal_solve_kkt_column": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _I64, _PI64, _PI32, _PF64, C.POINTER(SolveOpts),
+                                                 _PF64, C.POINTER(SolveInfo)]),
+    "padne_thermal_resolve": (C.c_int, [_P, _P, C.POINTER(SolveOpts), _PF64, C.POINTER(SolveInfo)]),
+    "padne_thermal_film_increment": (C.c_int, [_P, _P, _PF64, _PI64, _PI64]),
     "padne_tsens_create": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _PF64, C.POINTER(_P)]),
     "padne_tsens_destroy": (C.c_int, [_P]),
     "padne_tsens_thermal_adjoints": (C.c_int, [_P, _P, C.c_int32, _PI32, _PI32, _PI32, _PF64, _PI64, _PF64, C.c_int32, _PI32, _I64,
@@ -1128,7 +1135,11 @@ class Thermal:
 
     With ``mesh_layer`` (the layer of every mesh) the handle is made by ``padne_thermal_create_stacked`` (include/padne_hip.h,
     "stack"): ``pairs`` is a sequence of (layer a, layer b, g [W/(K mesh-unit^2)]) and the matrix is A' = A + G, the heat
-    conduction between the layers of every pair; ``stack_flows`` and the ``stack_*`` read-outs then work."""
+    conduction between the layers of every pair; ``stack_flows`` and the ``stack_*`` read-outs then work.
+
+    ``set_film_curves`` makes the film of every mesh a table over the temperature rise (include/padne_hip.h, "film curves"):
+    the solves then take one column, and a Newton round is ``film_linearise``, a solve (``solve``, ``solve_kkt_column``,
+    ``resolve``, ``Coupled.solve_kkt``) and ``film_increment``."""
 
     def __init__(self, L: "CsrMatrix", n_potential: int, kappa, film, link_a=(), link_b=(), link_g=(), *, mesh_layer=None,
                  pairs=(), n_layer=None):
@@ -1320,6 +1331,65 @@ class Thermal:
             raise ValueError("a block has at least one column")
         return self._solve(lambda *a: lib.padne_thermal_solve_kkt(self.ctx._h, self._h, plan._h, n_cols, *a), n_cols, heat, rtol,
                            max_iter, precond, download)
+
+    def set_film_curves(self, curves) -> None:
+        """The film curves of the handle (include/padne_hip.h, "film curves"): per mesh a pair (rise (n,), film (n,)) of 1 to
+        64 knots whose first film is the film the handle was made with; an empty sequence removes the curves.  ValueError
+        for what ``padne_thermal_set_film_curves`` refuses."""
+        curves = [(_f64(r).reshape(-1), _f64(f).reshape(-1)) for r, f in curves]
+        if any(r.shape != f.shape for r, f in curves):
+            raise ValueError("one film per rise")
+        ptr = _i32(np.concatenate([[0], np.cumsum([len(r) for r, _ in curves])]))
+        rise = _f64(np.concatenate([r for r, _ in curves])) if curves else np.zeros(0)
+        film = _f64(np.concatenate([f for _, f in curves])) if curves else np.zeros(0)
+        _check(self.ctx._lib.padne_thermal_set_film_curves(self.ctx._h, self._h, len(curves), _ptr(ptr, _PI32), _ptr(rise, _PF64),
+                                                           _ptr(film, _PF64)))
+
+    def film_terms(self, theta, n_vert: int):
+        """(g, c, hM) (n_vert,) each and the number of vertices above their last knot, for any ``theta`` (n_vert,)."""
+        th = _f64(theta).reshape(-1)
+        if th.shape[0] != int(n_vert):
+            raise ValueError("theta has one entry per vertex")
+        g, c, hM = (np.empty(int(n_vert), dtype=np.float64) for _ in range(3))
+        beyond = np.zeros(1, dtype=np.int64)
+        _check(self.ctx._lib.padne_thermal_film_terms(self.ctx._h, self._h, _ptr(th, _PF64), _ptr(g, _PF64), _ptr(c, _PF64),
+                                                      _ptr(hM, _PF64), _ptr(beyond, _PI64)))
+        return g, c, hM, int(beyond[0])
+
+    def film_linearise(self, from_held: bool) -> None:
+        """The film linearised about the held theta of a one-column solve, or about zero."""
+        _check(self.ctx._lib.padne_thermal_film_linearise(self.ctx._h, self._h, 1 if from_held else 0))
+
+    def film_increment(self) -> tuple:
+        """After a one-column solve: (max_v |theta_v - the iterate of the last linearise|, its vertex, the number of vertices
+        above their last knot); hM becomes h(theta_v) M_v for the reports."""
+        inc = np.zeros(1, dtype=np.float64)
+        vert, beyond = np.zeros(1, dtype=np.int64), np.zeros(1, dtype=np.int64)
+        _check(self.ctx._lib.padne_thermal_film_increment(self.ctx._h, self._h, _ptr(inc, _PF64), _ptr(vert, _PI64),
+                                                          _ptr(beyond, _PI64)))
+        return float(inc[0]), int(vert[0]), int(beyond[0])
+
+    def solve_kkt_column(self, plan: "KktPlan", n_cols: int, col: int, heat=None, *, rtol=1e-12, max_iter=200000, precond="amg",
+                         download=True):
+        """``solve_kkt`` for column ``col`` alone of the block of ``n_cols`` columns: theta (1, n_potential); the triples of
+        ``heat`` name column 0."""
+        lib = self.ctx._lib
+        return self._solve(lambda *a: lib.padne_thermal_solve_kkt_column(self.ctx._h, self._h, plan._h, int(n_cols), int(col), *a),
+                           1, heat, rtol, max_iter, precond, download)
+
+    def resolve(self, *, rtol=1e-12, max_iter=200000, precond="amg", download=True):
+        """The one-column solve again on the load the handle holds, with the c of the last ``film_linearise``."""
+        opts = CsrMatrix._opts(rtol, 0.0, max_iter, 0, False, precond=precond)
+        info = SolveInfo()
+        theta = np.empty((1, self.n_potential), dtype=np.float64) if download else None
+        rc = self.ctx._lib.padne_thermal_resolve(self.ctx._h, self._h, C.byref(opts), None if theta is None else _ptr(theta, _PF64),
+                                                 C.byref(info))
+        if rc != OK and rc != E_NOTCONVERGED:
+            _check(rc)
+        res = SolveResult(None, info.iterations, info.restarts, info.rel_residual, info.abs_residual, info.solve_seconds,
+                          info.status, info.spmv_seconds, info.precond_setup_seconds, info.operator_complexity, info.levels,
+                          info.precond_fallbacks)
+        return theta, res
 
     def face_power(self, n_cols: int, n_tri: int) -> np.ndarray:
         """The face powers (n_cols, n_tri) of the last solve, as the handle holds them."""

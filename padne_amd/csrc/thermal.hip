@@ -83,7 +83,7 @@ __global__ __launch_bounds__(256) void thermal_form_kernel(const long long n_row
 // P[c][t] = sigma sum_edges w_ik (V_i - V_k)^2 of every column c of V[..][n_cols], the arithmetic of
 // current_cases_face_kernel's per-mesh power.  One thread per face: corners, xy and weights once, the columns in register
 // chunks whose gathers are in flight together.  SCALED (the electro-thermal coupling): the one product sigma[m] * scale[t] in
-// the place of sigma[m]
+// the place of sigma[m].  ld: the columns of the block V (n_cols of them are taken, from the column V points at)
 template <bool SCALED>
 __global__ __launch_bounds__(256) void thermal_face_power_kernel(const long long n_tri, const int n_mesh,
                                                                  const int32_t *__restrict__ tri, const double *__restrict__ xy,
@@ -91,7 +91,8 @@ __global__ __launch_bounds__(256) void thermal_face_power_kernel(const long long
                                                                  const long long *__restrict__ toff,
                                                                  const double *__restrict__ sigma,
                                                                  const double *__restrict__ scale, const int n_cols,
-                                                                 const double *__restrict__ V, double *__restrict__ P,
+                                                                 const int ld, const double *__restrict__ V,
+                                                                 double *__restrict__ P,
                                                                  int *__restrict__ err) {
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     if (t >= n_tri) return;
@@ -109,7 +110,7 @@ __global__ __launch_bounds__(256) void thermal_face_power_kernel(const long long
     const double w23 = cot_half(x2, y2, x3, y3, x1, y1);     // edge 2-3, opposite 1
     const double w31 = cot_half(x3, y3, x1, y1, x2, y2);
     const double w12 = cot_half(x1, y1, x2, y2, x3, y3);
-    const double *p1 = V + g1 * n_cols, *p2 = V + g2 * n_cols, *p3 = V + g3 * n_cols;
+    const double *p1 = V + g1 * ld, *p2 = V + g2 * ld, *p3 = V + g3 * ld;
     for (int j0 = 0; j0 < n_cols; j0 += kThermalChunk) {
         double f1[kThermalChunk], f2[kThermalChunk], f3[kThermalChunk];
 #pragma unroll
@@ -311,6 +312,7 @@ static void thermal_free(padne_thermal *th) {
     if (th->A != nullptr) padne_csr_destroy(th->A);
     if (th->stack != nullptr) stack_free(ctx, th->stack);
     if (th->sources != nullptr) sources_free(ctx, th->sources);
+    if (th->film != nullptr) film_free(ctx, th->film);
     for (void *p : {(void *)th->vptr, (void *)th->vface, (void *)th->Mv, (void *)th->hM, (void *)th->P, (void *)th->theta})
         if (p != nullptr) pool_free(ctx, p);
     delete th;
@@ -386,10 +388,12 @@ int thermal_form_load(padne_ctx *ctx, padne_thermal *th, int32_t n_cols, int64_t
 }
 
 // What follows the face powers th->P[n_cols][n_tri]: b, the block solve, theta home.  PADNE_E_NOTCONVERGED still keeps and
-// returns the iterate
-static int thermal_solve_core(padne_ctx *ctx, padne_thermal *th, int32_t n_cols, int64_t n_heat, const int64_t *heat_node,
-                              const int32_t *heat_col, const double *heat_val, const padne_solve_opts *opts, double *theta_host,
-                              padne_solve_info *info) {
+// returns the iterate.  On a handle with film curves (film.hip; one column): the load is kept, the linearisation's c is added
+// to it, and the iteration starts from the iterate the film was linearised about; `resolve`: the kept load in the place of a
+// new one
+int thermal_solve_core(padne_ctx *ctx, padne_thermal *th, int32_t n_cols, int64_t n_heat, const int64_t *heat_node,
+                       const int32_t *heat_col, const double *heat_val, const padne_solve_opts *opts, double *theta_host,
+                       padne_solve_info *info, bool resolve) {
     hipStream_t s = ctx->stream;
     const long long n_pot = th->n_pot;
     PADNE_TRY(thermal_reserve(ctx, &th->theta, &th->theta_cap, (size_t)n_cols * (size_t)n_pot));
@@ -397,8 +401,21 @@ static int thermal_solve_core(padne_ctx *ctx, padne_thermal *th, int32_t n_cols,
     double *d_b = nullptr;
     PADNE_TRY(sc.alloc(&d_b, (size_t)n_cols * (size_t)n_pot));
     th->solved = false;
-    PADNE_TRY(thermal_form_load(ctx, th, n_cols, n_heat, heat_node, heat_col, heat_val, d_b));
-    PADNE_HIP_CHECK(hipMemsetAsync(th->theta, 0, sizeof(double) * (size_t)n_cols * (size_t)n_pot, s));
+    padne_film *fm = th->film;
+    const size_t pot_bytes = sizeof(double) * (size_t)n_pot;
+    if (resolve) {
+        PADNE_HIP_CHECK(hipMemcpyAsync(d_b, fm->b0, pot_bytes, hipMemcpyDeviceToDevice, s));
+    } else {
+        PADNE_TRY(thermal_form_load(ctx, th, n_cols, n_heat, heat_node, heat_col, heat_val, d_b));
+        if (fm != nullptr) {
+            PADNE_HIP_CHECK(hipMemcpyAsync(fm->b0, d_b, pot_bytes, hipMemcpyDeviceToDevice, s));
+            fm->have_load = true;
+        }
+    }
+    const bool warm = fm != nullptr && fm->warm;
+    if (fm != nullptr) PADNE_TRY(film_add_load(ctx, th, d_b));
+    if (warm) PADNE_HIP_CHECK(hipMemcpyAsync(th->theta, fm->lin, pot_bytes, hipMemcpyDeviceToDevice, s));
+    else PADNE_HIP_CHECK(hipMemsetAsync(th->theta, 0, sizeof(double) * (size_t)n_cols * (size_t)n_pot, s));
     padne_solve_opts o;
     if (opts != nullptr) {
         o = *opts;
@@ -411,6 +428,7 @@ static int thermal_solve_core(padne_ctx *ctx, padne_thermal *th, int32_t n_cols,
         o.flags = 0;
     }
     o.flags &= ~1;                                      // theta starts from zero: a zero column comes back as exact zeros
+    if (warm) o.flags |= 1;                             // (film curves: from the iterate of the last linearise)
     const int rc = padne_solve_spd_dev(ctx, th->A, d_b, th->theta, n_cols, &o, info);
     if (rc != PADNE_OK && rc != PADNE_E_NOTCONVERGED) return rc;
     th->n_cols = n_cols;
@@ -474,6 +492,7 @@ extern "C" int padne_thermal_create(padne_ctx *ctx, const padne_csr *L, int64_t 
     th->n_vert = L->mesh_n_vert;
     th->n_tri = L->mesh_n_tri;
     th->n_mesh = n_mesh;
+    th->film_host.assign(film, film + n_mesh);
     struct Guard {
         padne_thermal *th;
         ~Guard() { thermal_free(th); }
@@ -576,10 +595,13 @@ extern "C" int padne_thermal_solve(padne_ctx *ctx, padne_thermal *th, int32_t n_
                                    const int64_t *heat_node, const int32_t *heat_col, const double *heat_val,
                                    const padne_solve_opts *opts, double *theta_host, padne_solve_info *info) {
     PADNE_TRY(thermal_require("padne_thermal_solve", ctx, th));
+    PADNE_TRY(film_refuses("padne_thermal_solve", th, n_cols));
     PADNE_TRY(thermal_check_heat(th, n_cols, n_heat, heat_node, heat_col, heat_val));
     PADNE_TRY(thermal_upload_power(ctx, th, n_cols, face_power_host));
     return thermal_solve_core(ctx, th, n_cols, n_heat, heat_node, heat_col, heat_val, opts, theta_host, info);
 }
+
+static int thermal_face_power_of(padne_ctx *ctx, padne_thermal *th, int32_t n_cols, int32_t ld, const double *V, const double *scale);
 
 // the checks of an entry that reads the block `plan`'s last padne_kkt_finish_block left on the device: *V_out that block
 int padne::thermal_kkt_block(const char *entry, padne_ctx *ctx, const padne_thermal *th, padne_kkt *plan, int32_t n_cols,
@@ -594,6 +616,15 @@ int padne::thermal_kkt_block(const char *entry, padne_ctx *ctx, const padne_ther
 
 // th->P[n_cols][n_tri] from the block V of thermal_kkt_block (scale as in thermal_solve_kkt_scaled)
 int padne::thermal_kkt_face_power(padne_ctx *ctx, padne_thermal *th, int32_t n_cols, const double *V, const double *scale) {
+    return thermal_face_power_of(ctx, th, n_cols, n_cols, V, scale);
+}
+
+int padne::thermal_kkt_face_power_column(padne_ctx *ctx, padne_thermal *th, int32_t ld, int32_t col, const double *V,
+                                         const double *scale) {
+    return thermal_face_power_of(ctx, th, 1, ld, V + col, scale);
+}
+
+static int thermal_face_power_of(padne_ctx *ctx, padne_thermal *th, int32_t n_cols, int32_t ld, const double *V, const double *scale) {
     PADNE_HIP_CHECK(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     th->solved = false;
@@ -606,10 +637,10 @@ int padne::thermal_kkt_face_power(padne_ctx *ctx, padne_thermal *th, int32_t n_c
         PADNE_HIP_CHECK(hipMemsetAsync(d_bad, 0, sizeof(int), s));
         if (scale != nullptr)
             hipLaunchKernelGGL(thermal_face_power_kernel<true>, dim3(nblk(th->n_tri)), dim3(256), 0, s, th->n_tri, th->n_mesh, M.tri,
-                               M.xy, M.voff, M.toff, M.sigma, scale, (int)n_cols, V, th->P, d_bad);
+                               M.xy, M.voff, M.toff, M.sigma, scale, (int)n_cols, (int)ld, V, th->P, d_bad);
         else
             hipLaunchKernelGGL(thermal_face_power_kernel<false>, dim3(nblk(th->n_tri)), dim3(256), 0, s, th->n_tri, th->n_mesh, M.tri,
-                               M.xy, M.voff, M.toff, M.sigma, (const double *)nullptr, (int)n_cols, V, th->P, d_bad);
+                               M.xy, M.voff, M.toff, M.sigma, (const double *)nullptr, (int)n_cols, (int)ld, V, th->P, d_bad);
         PADNE_HIP_CHECK(hipGetLastError());
         PADNE_TRY(thermal_bad_flag(s, d_bad, "triangle index out of range"));
     }
@@ -622,6 +653,7 @@ int padne::thermal_solve_kkt_scaled(const char *entry, padne_ctx *ctx, padne_the
                                     padne_solve_info *info) {
     const double *V = nullptr;
     PADNE_TRY(thermal_kkt_block(entry, ctx, th, plan, n_cols, &V));
+    PADNE_TRY(film_refuses(entry, th, n_cols));
     PADNE_TRY(thermal_check_heat(th, n_cols, n_heat, heat_node, heat_col, heat_val));
     PADNE_TRY(thermal_kkt_face_power(ctx, th, n_cols, V, scale));
     return thermal_solve_core(ctx, th, n_cols, n_heat, heat_node, heat_col, heat_val, opts, theta_host, info);

@@ -1,7 +1,8 @@
 // The thermal handle (thermal.hip) as the translation units that work on it see it: thermal.hip itself, the electro-thermal
 // coupling (coupled.hip), which borrows the handle's vertex -> faces lists and its theta, the transient handle
 // (transient.hip), coupled_transient.hip, which joins the last two, sdirk.hip, which steps the transient handle by
-// error-controlled second-order steps, and periodic.hip, which puts states into it for the Krylov iteration on a period.
+// error-controlled second-order steps, periodic.hip, which puts states into it for the Krylov iteration on a period, and
+// film.hip, which rewrites A's diagonal and hM for a film that depends on the temperature.
 #pragma once
 
 #include "error.hpp"
@@ -51,6 +52,24 @@ struct padne_sources {
 };
 namespace padne { void sources_free(padne_ctx *ctx, padne_sources *sr); }
 
+// the film curves of a handle (film.hip): the tables, where every vertex row keeps its diagonal, what the create call left
+// there and in hM, and the linearisation the next solve uses
+struct padne_film {
+    std::vector<int> knot_ptr;               // [n_mesh + 1] the first knot of every mesh's table
+    std::vector<double> rise, film;          // the knots as given
+    // device (the context's pool)
+    int *kptr = nullptr;                     // [n_mesh + 1]
+    double *krise = nullptr, *kfilm = nullptr, *kslope = nullptr;   // [knots]; kslope[i] the slope of the segment that starts at knot i
+    int *diag = nullptr;                     // [n_vert] the entry of A's values that holds the diagonal of the vertex's row
+    double *D0 = nullptr, *hM0 = nullptr;    // [n_vert] that diagonal and hM as the create call left them
+    double *c = nullptr;                     // [n_vert] what the linearisation adds to the load
+    double *lin = nullptr;                   // [n_pot] the iterate the matrix is linearised about
+    double *b0 = nullptr;                    // [n_pot] the load of the last solve without c (padne_thermal_resolve)
+    bool warm = false;                       // linearised about a held iterate: the next solve starts from lin
+    bool have_load = false;                  // b0 holds the load of a solve
+};
+namespace padne { void film_free(padne_ctx *ctx, padne_film *fm); }
+
 struct padne_thermal {
     padne_ctx *ctx = nullptr;
     const padne_csr *L = nullptr;            // borrowed: the electrical system, for its mesh
@@ -67,6 +86,8 @@ struct padne_thermal {
     bool solved = false;
     padne_stack *stack = nullptr;            // owned: the inter-layer coupling of padne_thermal_create_stacked (stack.hip), or null
     padne_sources *sources = nullptr;        // owned: the heat sources of padne_thermal_set_sources (sources.hip), or null
+    std::vector<double> film_host;           // [n_mesh] the film coefficients of the create call
+    padne_film *film = nullptr;              // owned: the film curves of padne_thermal_set_film_curves (film.hip), or null
 };
 
 // The coupling handle (coupled.hip) and the transient handle (transient.hip), as coupled_transient.hip -- which steps the
@@ -138,6 +159,17 @@ int thermal_kkt_face_power(padne_ctx *ctx, padne_thermal *th, int32_t n_cols, co
 int thermal_form_load(padne_ctx *ctx, padne_thermal *th, int32_t n_cols, int64_t n_heat, const int64_t *heat_node,
                       const int32_t *heat_col, const double *heat_val, double *d_b);
 std::vector<long long> thermal_tiles(const std::vector<int64_t> &off);
+// thermal.hip: the block solve of one or more columns on the face powers th->P, b formed from them and the triples (null
+// lists with n_heat 0); film.hip's entries end in it.  thermal_kkt_face_power_column: th->P[1][n_tri] from column `col` of
+// the block V[..][ld]
+int thermal_solve_core(padne_ctx *ctx, padne_thermal *th, int32_t n_cols, int64_t n_heat, const int64_t *heat_node,
+                       const int32_t *heat_col, const double *heat_val, const padne_solve_opts *opts, double *theta_host,
+                       padne_solve_info *info, bool resolve = false);
+int thermal_kkt_face_power_column(padne_ctx *ctx, padne_thermal *th, int32_t ld, int32_t col, const double *V, const double *scale);
+// film.hip, for a handle with film curves.  film_add_load: b[v] = b[v] + c[v] behind thermal_form_load, queued.
+// film_refuses: PADNE_E_INVALID for a block of several columns on such a handle
+int film_add_load(padne_ctx *ctx, padne_thermal *th, double *d_b);
+int film_refuses(const char *entry, const padne_thermal *th, int32_t n_cols);
 // sources.hip: what thermal_form_load adds for a handle with heat sources -- their load into b[n_cols][n_pot] on the device,
 // queued behind the face gather and the triples; PADNE_E_INVALID without powers for exactly n_cols columns.  Nothing
 // without sources

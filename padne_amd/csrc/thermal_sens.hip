@@ -449,6 +449,7 @@ extern "C" int padne_tsens_create(padne_ctx *ctx, padne_thermal *th, padne_kkt *
     PADNE_REQUIRE(n_cases >= 1 && n_cases <= 4096, "between 1 and 4096 load cases");
     const double *V = nullptr;
     PADNE_TRY(thermal_kkt_block("padne_tsens_create", ctx, th, plan, n_cases, &V));
+    PADNE_REQUIRE(th->film == nullptr, "a thermal handle with film curves takes no sensitivity handle: the adjoint reads A and hM as constants");
     PADNE_REQUIRE(th->solved && th->n_cols == n_cases, "padne_tsens_create follows a thermal solve of as many columns");
     PADNE_REQUIRE(n_mesh == th->n_mesh, "n_mesh must be that of the system's mesh");
     for (int m = 0; m < n_mesh; ++m)

@@ -324,6 +324,7 @@ extern "C" int padne_transient_create(padne_ctx *ctx, padne_thermal *th, int32_t
     PADNE_REQUIRE(ctx && th && capacity && out, "null argument");
     PADNE_REQUIRE(th->ctx == ctx, "padne_transient_create: the thermal handle belongs to another context");
     PADNE_REQUIRE(n_mesh == th->n_mesh, "n_mesh must be that of the system's mesh");
+    PADNE_REQUIRE(th->film == nullptr, "a thermal handle with film curves takes no transient handle: the steps read A and hM as constants");
     for (int m = 0; m < n_mesh; ++m)
         PADNE_REQUIRE(std::isfinite(capacity[m]) && capacity[m] > 0.0, "the areal heat capacity of every mesh must be finite and positive");
     PADNE_REQUIRE(!th->A->cols_unsorted && th->A->nnz <= 0x7fffffffLL, "the thermal operator");

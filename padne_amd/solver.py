@@ -1887,13 +1887,119 @@ class CheckedHeatSource:
     power: object              # float, or a tuple of floats (one per load case)
 
 
+MAX_FILM_KNOTS = 64
+FILM_TOLERANCE = 0.01                   # [K] the defaults of ElectroThermalModel.tolerance and .max_rounds
+FILM_MAX_ROUNDS = 20
+
+
+class FilmCurve:
+    """A film coefficient that depends on the temperature rise (DESIGN.md "Film curves"): ``film[i]`` [W / (K mesh-unit^2)]
+    at the knots ``rise[i]`` [K above ambient], linear between the knots, held constant below the first knot and above the
+    last.  A table, not a formula: it takes measured or CFD data as well as the textbook laws, and the device evaluates it
+    with + - * only.  :func:`check_film_curve` states the rules; the constructor only copies."""
+
+    def __init__(self, rise, film):
+        self.rise = np.array(rise, dtype=DTYPE).reshape(-1)
+        self.film = np.array(film, dtype=DTYPE).reshape(-1)
+
+    def __repr__(self):
+        return f"FilmCurve({len(self.rise)} knots, h(0)={self.film[0] if len(self.film) else None!r})"
+
+    def __call__(self, theta):
+        """h at the rises ``theta``, by the rule above (host arithmetic: np.interp, not the device's order)."""
+        return np.interp(np.asarray(theta, dtype=DTYPE), self.rise, self.film)
+
+    def is_constant(self) -> bool:
+        """Every knot has the first knot's film: the curve is the float ``film[0]``."""
+        return bool((self.film == self.film[0]).all())
+
+    def __add__(self, other):
+        if isinstance(other, FilmCurve):
+            if self.rise.shape != other.rise.shape or not np.array_equal(self.rise, other.rise):
+                raise ValueError("two film curves are added knot by knot: their rises must be equal")
+            return FilmCurve(self.rise, self.film + other.film)
+        if isinstance(other, (int, float, np.integer, np.floating)) and not isinstance(other, bool):
+            return FilmCurve(self.rise, self.film + float(other))
+        return NotImplemented
+
+    __radd__ = __add__
+
+    @classmethod
+    def constant(cls, h) -> "FilmCurve":
+        """The one-knot curve of the float ``h``."""
+        return cls([0.0], [h])
+
+    @classmethod
+    def tabulate(cls, fn, upto, knots: int = 33) -> "FilmCurve":
+        """``fn`` (rise -> h, vectorised) at ``knots`` knots ``upto * (i / (knots - 1))^2``: dense near 0, where a law like
+        theta^(1/4) is steep."""
+        knots = int(knots)
+        if not 2 <= knots <= MAX_FILM_KNOTS:
+            raise ValueError(f"a tabulated film curve has between 2 and {MAX_FILM_KNOTS} knots, not {knots}")
+        upto = _positive_number(upto, "upto")
+        rise = upto * (np.arange(knots, dtype=DTYPE) / (knots - 1)) ** 2
+        return cls(rise, np.asarray(fn(rise), dtype=DTYPE))
+
+    @classmethod
+    def natural_convection(cls, coefficient, exponent=0.25, *, upto, knots: int = 33) -> "FilmCurve":
+        """h = coefficient * rise^exponent, the law of natural convection from a plate.  h(0) of the law is 0, which no film
+        may be: the first knot takes the value of the second, so the law holds from the second knot on."""
+        coefficient = _positive_number(coefficient, "the coefficient")
+        curve = cls.tabulate(lambda t: coefficient * t ** float(exponent), upto, knots)
+        if curve.film[0] == 0.0:
+            curve.film[0] = curve.film[1]
+        return curve
+
+    @classmethod
+    def radiation(cls, emissivity_sigma, ambient_kelvin, *, upto, knots: int = 33) -> "FilmCurve":
+        """h = emissivity_sigma ((Ta + rise)^2 + Ta^2) ((Ta + rise) + Ta), radiation to surroundings at ``ambient_kelvin``.
+        ``emissivity_sigma`` in mesh units: 5.67e-14 W/(mm^2 K^4) for a black surface with meshes in mm."""
+        es, ta = _positive_number(emissivity_sigma, "emissivity_sigma"), _positive_number(ambient_kelvin, "ambient_kelvin")
+        return cls.tabulate(lambda t: es * ((ta + t) ** 2 + ta ** 2) * ((ta + t) + ta), upto, knots)
+
+
+def check_film_curve(curve, what: str = "the film curve") -> FilmCurve:
+    """``curve`` as a checked copy, or ValueError -- before anything reaches the device -- for: no FilmCurve; fewer than 1
+    or more than 64 knots, or as many rises as films not; a value that is not finite; a film that is not positive; a
+    ``rise`` that does not start at 0 or does not ascend strictly; and a loss density q(theta) = h(theta) theta that does
+    not increase strictly for theta >= 0 -- on segment i with the slope s_i = (h_i+1 - h_i) / (t_i+1 - t_i) the derivative
+    q' = h_i + s_i (2 theta - t_i) must be positive at both ends; the message names the segment.  A curve that falls that
+    fast has more than one steady state."""
+    if not isinstance(curve, FilmCurve):
+        raise ValueError(f"{what} must be a FilmCurve, not {curve!r}")
+    rise, film = np.array(curve.rise, dtype=DTYPE).reshape(-1), np.array(curve.film, dtype=DTYPE).reshape(-1)
+    if rise.shape != film.shape:
+        raise ValueError(f"{what}: {len(rise)} rises and {len(film)} films; one film per knot")
+    if not 1 <= len(rise) <= MAX_FILM_KNOTS:
+        raise ValueError(f"{what} has {len(rise)} knots: between 1 and {MAX_FILM_KNOTS} are taken")
+    if not (np.isfinite(rise).all() and np.isfinite(film).all()):
+        raise ValueError(f"{what}: every rise and every film must be finite")
+    if not (film > 0.0).all():
+        raise ValueError(f"{what}: every film coefficient must be positive (knot {int(np.flatnonzero(~(film > 0.0))[0])})")
+    if rise[0] != 0.0:
+        raise ValueError(f"{what}: the first knot must be at a rise of 0, not {rise[0]!r}")
+    if not (np.diff(rise) > 0.0).all():
+        raise ValueError(f"{what}: the rises must ascend strictly (knot {int(np.flatnonzero(~(np.diff(rise) > 0.0))[0]) + 1})")
+    for i in range(len(rise) - 1):
+        s = (film[i + 1] - film[i]) / (rise[i + 1] - rise[i])
+        left, right = film[i] + s * (2 * rise[i] - rise[i]), film[i] + s * (2 * rise[i + 1] - rise[i])
+        if not (math.isfinite(s) and left > 0.0 and right > 0.0):
+            raise ValueError(f"{what} falls too fast on segment {i} ({rise[i]!r} K to {rise[i + 1]!r} K): the loss density "
+                             "h(theta) theta must increase strictly")
+    return FilmCurve(rise, film)
+
+
 @dataclass
 class ThermalModel:
     """What turns dissipated power into a temperature (see :func:`solve_meshed_thermal`).
 
     - ``film``: the film coefficient h [W / (K mesh-unit^2)] that lumps every loss from the sheet to ambient, one float for
       all layers or a mapping {layer or layer name: float} that names every layer.  Required: there is no sensible
-      default.  With meshes in mm, 10 W/(m^2 K) is 1e-5.
+      default.  With meshes in mm, 10 W/(m^2 K) is 1e-5.  In the place of any float a :class:`FilmCurve`: a film that
+      depends on the temperature rise (DESIGN.md "Film curves"), honoured by the steady and the electro-thermal calls by
+      Newton rounds and refused by the others.
+    - ``film_tolerance`` [K] and ``film_max_rounds``: the Newton loop on a film curve ends when no vertex moved by more than
+      the tolerance in a round, or after that many rounds with a SolverWarning.
     - ``ambient``: the ambient temperature, in the unit the temperatures are reported in.
     - ``sheet_conductance``: None, or a mapping {layer or name: kappa [W/K]}, the thermal conductance of a square of the
       sheet.  A layer that is not named gets Wiedemann-Franz, kappa = L0 T_ref layer.conductance.
@@ -1924,18 +2030,27 @@ class ThermalModel:
     reference_temperature: float = 293.15
     interlayer: Optional[Mapping] = None
     heat_sources: Optional[Sequence] = None
+    film_tolerance: float = FILM_TOLERANCE
+    film_max_rounds: int = FILM_MAX_ROUNDS
 
 
 @dataclass
 class CheckedThermalModel:
     """A :class:`ThermalModel` resolved against a Problem (:func:`check_thermal_model`)."""
-    film: list                 # per layer
+    film: list                 # per layer: the float, or h(0) of the layer's curve
     kappa: list                # per layer
     links: dict                # Resistor of the solved networks -> g [W/K]
     ambient: float
     element_heat: bool
     interlayer: list = field(default_factory=list)      # (layer index a < b, g [W / (K mesh-unit^2)]), in the mapping's order
     sources: list = field(default_factory=list)         # CheckedHeatSource, in the model's order
+    film_curves: Optional[list] = None                  # per layer: the checked FilmCurve, or None for a float; None: floats only
+    film_tolerance: float = FILM_TOLERANCE
+    film_max_rounds: int = FILM_MAX_ROUNDS
+
+    def curved(self) -> bool:
+        """Some layer's film depends on the temperature: the solve is a Newton loop.  Constant curves are floats."""
+        return self.film_curves is not None and any(c is not None and not c.is_constant() for c in self.film_curves)
 
 
 @dataclass
@@ -1959,6 +2074,11 @@ class ThermalReport:
     # one face under its middle, "temperature": the area-weighted mean of those faces' temperatures}
     sources: list = field(default_factory=list)
     source_heat: float = 0.0            # the powers of the sources in this case; part of total_heat
+    # None, or for a model with film curves how the Newton loop on the film went: {"rounds", "increments": per round the
+    # largest change of a vertex temperature [K], "vertices": the global vertex of each, "converged", "beyond": the
+    # vertices above the last knot of their curve, where it is held constant}.  ``info`` is then that of the last solve,
+    # and every loss is sum_v M_v h(theta_v) theta_v
+    film: Optional[dict] = None
 
 
 @dataclass
@@ -1983,8 +2103,10 @@ def _positive_number(value, what: str, allow_zero: bool = False) -> float:
     return x
 
 
-def _per_layer(prob, mapping, what: str) -> dict:
-    """{layer index: value} of a mapping {layer or layer name: value}; ValueError for a key that is no layer of ``prob``."""
+def _per_layer(prob, mapping, what: str, value_of=None) -> dict:
+    """{layer index: value} of a mapping {layer or layer name: value}; ValueError for a key that is no layer of ``prob``.
+    ``value_of(value, what)``: the check of a value, a positive number by default."""
+    value_of = _positive_number if value_of is None else value_of
     out = {}
     for key, value in mapping.items():
         if isinstance(key, str):
@@ -1994,7 +2116,7 @@ def _per_layer(prob, mapping, what: str) -> dict:
         if not found:
             raise ValueError(f"{what}: {key!r} is no layer of the Problem")
         for i in found:
-            out[i] = _positive_number(value, f"{what} of layer {prob.layers[i].name!r}")
+            out[i] = value_of(value, f"{what} of layer {prob.layers[i].name!r}")
     return out
 
 
@@ -2023,14 +2145,26 @@ def check_thermal_model(prob, model, filtered_networks=None) -> CheckedThermalMo
     n_layers = len(prob.layers)
     if model.film is None:
         raise ValueError("the film coefficient is required: a float, or a mapping {layer: float}")
+    def film_of(value, what):
+        return check_film_curve(value, what) if isinstance(value, FilmCurve) else _positive_number(value, what)
+
     if isinstance(model.film, Mapping):
-        given = _per_layer(prob, model.film, "film")
+        given = _per_layer(prob, model.film, "film", film_of)
         for i, layer in enumerate(prob.layers):
             if i not in given:
                 raise ValueError(f"layer {layer.name!r} has no film coefficient")
         film = [given[i] for i in range(n_layers)]
     else:
-        film = [_positive_number(model.film, "the film coefficient")] * n_layers
+        film = [film_of(model.film, "the film coefficient")] * n_layers
+    film_curves = [f if isinstance(f, FilmCurve) else None for f in film]
+    film = [float(f.film[0]) if isinstance(f, FilmCurve) else f for f in film]
+    film_tolerance = _positive_number(model.film_tolerance, "film_tolerance")
+    try:
+        film_max_rounds = int(model.film_max_rounds)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"film_max_rounds must be an integer, not {model.film_max_rounds!r}") from None
+    if film_max_rounds < 1 or film_max_rounds != model.film_max_rounds:
+        raise ValueError(f"film_max_rounds must be an integer of at least 1, not {model.film_max_rounds!r}")
     given = {} if model.sheet_conductance is None else _per_layer(prob, model.sheet_conductance, "sheet_conductance")
     kappa = []
     for i, layer in enumerate(prob.layers):
@@ -2083,7 +2217,17 @@ def check_thermal_model(prob, model, filtered_networks=None) -> CheckedThermalMo
                              "its temperature is undetermined (give a resistor at the node a link_conductance above 0)")
     return CheckedThermalModel(film=film, kappa=kappa, links=links, ambient=ambient, element_heat=bool(model.element_heat),
                                interlayer=_check_interlayer(prob, model.interlayer),
-                               sources=_check_heat_sources(prob, model.heat_sources))
+                               sources=_check_heat_sources(prob, model.heat_sources),
+                               film_curves=film_curves if any(c is not None for c in film_curves) else None,
+                               film_tolerance=film_tolerance, film_max_rounds=film_max_rounds)
+
+
+def _refuse_film_curves(checked: CheckedThermalModel, what: str) -> None:
+    """ValueError for a model whose film depends on the temperature, in a call that reads the film as a constant."""
+    if checked.curved():
+        raise ValueError(f"{what} does not honour a film curve that depends on the temperature: only the steady "
+                         "(solve_thermal) and the electro-thermal (solve_electrothermal) calls iterate on the film; give this "
+                         "call floats or constant curves")
 
 
 def _check_heat_sources(prob, heat_sources) -> list:
@@ -2230,10 +2374,23 @@ def _thermal_handle(L, n_potential: int, checked: CheckedThermalModel, layer_of,
     stack = {}
     if checked.interlayer:
         stack = dict(mesh_layer=[layer_of[i] for i in range(n_mesh)], pairs=checked.interlayer, n_layer=len(checked.film))
-    return _hip.Thermal(L.dev, n_potential, [checked.kappa[layer_of[i]] for i in range(n_mesh)],
-                        [checked.film[layer_of[i]] for i in range(n_mesh)],
-                        [row[1] for _, row in resistors], [row[2] for _, row in resistors],
-                        [checked.links[element] for element, _ in resistors], **stack)
+    thermal = _hip.Thermal(L.dev, n_potential, [checked.kappa[layer_of[i]] for i in range(n_mesh)],
+                           [checked.film[layer_of[i]] for i in range(n_mesh)],
+                           [row[1] for _, row in resistors], [row[2] for _, row in resistors],
+                           [checked.links[element] for element, _ in resistors], **stack)
+    if checked.curved():                     # (floats and constant curves: the handle of the float path, untouched)
+        try:
+            thermal.set_film_curves([_film_table(checked, layer_of[i]) for i in range(n_mesh)])
+        except BaseException:
+            thermal.close()
+            raise
+    return thermal
+
+
+def _film_table(checked: CheckedThermalModel, layer_i: int) -> tuple:
+    """(rise, film) of a layer of a checked model with curves; a float is the table of one knot."""
+    curve = checked.film_curves[layer_i]
+    return ([0.0], [checked.film[layer_i]]) if curve is None else (curve.rise, curve.film)
 
 
 def _stack_flows(thermal, checked: CheckedThermalModel, n_cols: int):
@@ -2438,6 +2595,9 @@ def _solve_block_thermal(prob, meshes, mesh_index_to_layer_index, checked: Check
     ([Solution], [ThermalReport], ThermalEnvelope).  ``fields``: with the per-case temperatures of vertices and faces.
     ``check``: see :func:`_thermal_block`.  ``inside(blk, theta, mesh_max, mesh_vert, sources)``, if given, runs after the reports
     have been read, while the block and the handle still live on the device; its value is returned as a fourth item."""
+    if checked.curved():
+        return _solve_block_thermal_curved(prob, meshes, mesh_index_to_layer_index, checked, cases, fields, filtered_networks,
+                                           disconnected_meshes_by_layer, laps, check)
     extra = None
     with _thermal_block(prob, meshes, mesh_index_to_layer_index, checked, cases, filtered_networks,
                         disconnected_meshes_by_layer, laps, "temperatures", check) as blk:
@@ -2462,6 +2622,99 @@ def _solve_block_thermal(prob, meshes, mesh_index_to_layer_index, checked: Check
     laps.lap("solutions")
     if inside is not None:
         return solutions, reports, envelope, extra
+    return solutions, reports, envelope
+
+
+def _film_layer_name(board: IndexedBoard, vertex: int) -> str:
+    """The name of the layer of the global vertex ``vertex`` (-1: no vertex)."""
+    if vertex < 0:
+        return "?"
+    mesh_i = int(np.searchsorted(np.asarray(board.vindex.offsets), vertex, side="right")) - 1
+    return board.prob.layers[board.layer_of[mesh_i]].name
+
+
+def _film_newton(thermal, first_solve, checked: CheckedThermalModel, where: str, board: IndexedBoard, rounds_log=None,
+                 case: int = 0) -> tuple:
+    """The Newton loop on the film curves of the handle ``thermal`` for one load: the film linearised about zero and
+    ``first_solve()`` (today's linear solve with h(0)), then rounds of (linearise about the held theta, ``resolve``), each
+    followed by ``film_increment``, until no vertex moved by more than ``checked.film_tolerance`` -- or
+    ``checked.film_max_rounds`` end the loop with a SolverWarning that begins with ``where``.  (theta (1, n_potential), the
+    SolveResult of the last solve, ``ThermalReport.film``).  On return hM of the handle is h(theta) M_v of the last iterate.
+    ``rounds_log``: a list that receives the laps of every round."""
+    increments, vertices, beyond, converged = [], [], 0, False
+    theta = tres = None
+    for round_i in range(1, checked.film_max_rounds + 1):
+        lap = {}
+        round_laps = _Laps(lap)
+        thermal.film_linearise(round_i > 1)
+        round_laps.lap("linearise")
+        theta, tres = first_solve() if round_i == 1 else thermal.resolve(rtol=RTOL, max_iter=MAX_ITER)
+        round_laps.lap("thermal_solve")
+        increment, vertex, beyond = thermal.film_increment()
+        round_laps.lap("increment")
+        increments.append(increment)
+        vertices.append(vertex)
+        if rounds_log is not None:
+            rounds_log.append(dict(lap, case=case, round=round_i, hierarchy=float(tres.setup_seconds),
+                                   iterations=int(tres.iterations)))
+        if increment <= checked.film_tolerance:
+            converged = True
+            break
+    if not converged:
+        warnings.warn(f"{where}: the film loop did not converge in {checked.film_max_rounds} round(s): the last change of a "
+                      f"vertex temperature was {increments[-1]:.3e} K, on layer {_film_layer_name(board, vertices[-1])!r}, above "
+                      f"the tolerance of {checked.film_tolerance:.3e} K", SolverWarning)
+    return theta, tres, {"rounds": len(increments), "increments": increments, "vertices": vertices, "converged": converged,
+                         "beyond": beyond}
+
+
+def _solve_block_thermal_curved(prob, meshes, mesh_index_to_layer_index, checked: CheckedThermalModel, cases, fields: bool,
+                                filtered_networks, disconnected_meshes_by_layer, laps: _Laps, check=None):
+    """:func:`_solve_block_thermal` for a model with film curves: the electrical block and the face powers as there, then
+    case by case the Newton loop of :func:`_film_newton` on the one-column thermal solve, with the one-column report, stack
+    flows and source report of every case.  The envelope is :func:`envelope_of` the cases' theta."""
+    rounds_log = []
+    if laps.timings is not None:
+        laps.timings["rounds"] = rounds_log
+    per_case = []
+    with _thermal_block(prob, meshes, mesh_index_to_layer_index, checked, cases, filtered_networks,
+                        disconnected_meshes_by_layer, laps, "temperatures by Newton rounds on the film", check) as blk:
+        k, thermal = blk.k, blk.thermal
+        for j in range(k):
+            where = f"Load case {j}" if k > 1 else "The thermal solve"
+            heat = None
+            if blk.heat is not None:
+                mine = blk.heat[1] == j
+                heat = (blk.heat[0][mine], np.zeros(int(mine.sum()), dtype=np.int32), blk.heat[2][mine])
+            if blk.sources is not None:
+                thermal.source_power(blk.source_power[j:j + 1])
+            theta, tres, film = _film_newton(
+                thermal, lambda: thermal.solve_kkt_column(blk.plan, k, j, heat, rtol=RTOL, max_iter=MAX_ITER), checked, where,
+                blk.board, rounds_log, j)
+            report = thermal.report(1, blk.n_tri, blk.n_vert, fields=fields, envelope=False)
+            per_case.append((theta, tres, film, report, _stack_flows(thermal, checked, 1),
+                             None if blk.sources is None else thermal.source_report(1)))
+        laps.lap("thermal_solve")
+    board = blk.board
+    infos = []
+    for j, (_theta, tres, _film, *_rest) in enumerate(per_case):
+        if tres.status != _hip.OK and not tres.rel_residual <= max(RTOL, STALL_WARN_ABOVE):
+            warnings.warn(f"{f'Load case {j}: ' if k > 1 else ''}The thermal solve stopped at a relative residual of "
+                          f"{tres.rel_residual:.3e}", SolverWarning)
+        infos.append({"iterations": int(tres.iterations), "rel_residual": float(tres.rel_residual), "seconds": float(tres.seconds)})
+    solutions = _block_solutions(blk)
+    theta = np.concatenate([c[0] for c in per_case])
+    stacked = [None if not fields and i == 0 else np.concatenate([c[3][i] for c in per_case]) for i in range(5)]
+    heat_val = blk.heat[2].reshape(k, len(blk.resistors), 2) if blk.heat is not None else None
+    stack = (np.concatenate([c[4][0] for c in per_case]), per_case[0][4][1]) if checked.interlayer else None
+    sources = None if blk.sources is None else (blk.sources, blk.source_power, np.concatenate([c[5] for c in per_case]))
+    reports = _thermal_reports(board, checked, blk.substituted, blk.resistors, fields, theta, *stacked, heat_val, infos, stack,
+                               sources)
+    for report, case in zip(reports, per_case):
+        report.film = case[2]
+    env, env_case = envelope_of(theta[:, :blk.n_vert])
+    envelope = _thermal_envelope(board, checked.ambient, env, env_case, reports)
+    laps.lap("solutions")
     return solutions, reports, envelope
 
 
@@ -2501,6 +2754,15 @@ def solve_meshed_thermal(prob, meshes, mesh_index_to_layer_index, model: Thermal
     the loaded area and faces, whether the fallback was taken, and the area-weighted mean temperature of the copper under
     it -- also with ``per_case_fields=False``.  A sequence of powers must have one entry per load case, and a source on
     no connected copper is refused: ValueError, the latter after the device handles have been closed.
+
+    With a :class:`FilmCurve` for some layer's ``model.film`` (DESIGN.md "Film curves") the film follows the temperature
+    rise and the solve is a Newton loop per load case: the film linearised about theta_k gives the diagonal q'(theta_k) M_v
+    and the load term (q'(theta_k) theta_k - q(theta_k)) M_v, q = h(theta) theta; the first round is the linear solve with
+    h(0), the loop ends when no vertex moved by more than ``model.film_tolerance`` or after ``model.film_max_rounds`` with a
+    SolverWarning.  The cases keep their one electrical block solve and go through the thermal rounds one at a time.
+    ``ThermalReport.film`` tells how the loop went, every ``loss`` and ``total_loss`` is sum_v M_v h(theta_v) theta_v, and
+    ``total_loss`` equals ``total_heat`` up to the last round's linearisation defect.  Floats and constant curves take the
+    linear path, a single solve with the bits it always gave.
 
     The electrical block is the load-case path; the thermal operator is then assembled from the meshes the device still
     holds, the face powers of every case are computed from the potentials it holds, and all cases go through one block
@@ -2827,6 +3089,7 @@ def solve_meshed_thermal_sensitivities(prob, meshes, mesh_index_to_layer_index, 
         raise ValueError("temperature sensitivities take a ThermalModel: the electro-thermal and the transient models are not "
                          f"accepted, not {type(model).__name__}")
     checked = check_thermal_model(prob, model, filtered_networks)
+    _refuse_film_curves(checked, "the temperature-sensitivity solve")
     single = cases is None
     checked_cases = [{}] if single else check_load_cases(prob, cases)
     given = objectives
@@ -2851,7 +3114,7 @@ def solve_thermal_sensitivities(prob, model: ThermalModel, objectives, mesher_co
     if not isinstance(model, ThermalModel):
         raise ValueError("temperature sensitivities take a ThermalModel: the electro-thermal and the transient models are not "
                          f"accepted, not {type(model).__name__}")
-    check_thermal_model(prob, model)
+    _refuse_film_curves(check_thermal_model(prob, model), "the temperature-sensitivity solve")
     if cases is not None:
         cases = check_load_cases(prob, cases)
     check_temperature_objectives(prob, model, objectives, 1 if cases is None else len(cases))
@@ -2959,6 +3222,7 @@ def check_transient_model(prob, model, filtered_networks=None) -> CheckedTransie
     if not isinstance(model, TransientModel):
         raise ValueError("model must be a TransientModel")
     thermal = check_thermal_model(prob, model.thermal, filtered_networks)
+    _refuse_film_curves(thermal, "a transient solve")
     if model.areal_capacity is None:
         raise ValueError("the areal heat capacity is required: a float, or a mapping {layer: float}")
     if isinstance(model.areal_capacity, Mapping):
@@ -3923,8 +4187,9 @@ def _revalued_solve(handles, board: IndexedBoard, pairs, case: dict, stamps, ele
 
 def _picard(round_fn, electro: CheckedElectroThermalModel) -> tuple:
     """The Picard loop: ``round_fn(round)`` runs a round and returns its increment d [K].  (the increments, the verdict of
-    :func:`picard_verdict` on them, None when ``electro.max_rounds`` ended the loop); with every alpha 0 one round converges."""
-    one_round = all(a == 0.0 for a in electro.alpha)
+    :func:`picard_verdict` on them, None when ``electro.max_rounds`` ended the loop); with every alpha 0 and no film curve
+    one round converges."""
+    one_round = all(a == 0.0 for a in electro.alpha) and not electro.thermal.curved()
     increments, verdict = [], None
     for round_i in range(1, electro.max_rounds + 1):
         increments.append(round_fn(round_i))
@@ -3958,6 +4223,7 @@ def _solve_electrothermal(prob, meshes, mesh_index_to_layer_index, checked: Chec
     """The checked ``cases`` of ``prob``, each converged by the Picard loop on one assembly and one thermal handle:
     ([Solution], [ThermalReport], [CouplingReport], ThermalEnvelope)."""
     thermal_model, n_layers = checked.thermal, len(prob.layers)
+    curved = thermal_model.curved()
     board, pairs, substituted, source_power, n_vert, k = _thermal_board(
         prob, meshes, mesh_index_to_layer_index, thermal_model, cases, filtered_networks, disconnected_meshes_by_layer)
     laps.lap("indexing")
@@ -3975,15 +4241,25 @@ def _solve_electrothermal(prob, meshes, mesh_index_to_layer_index, checked: Chec
             if sources is not None:                          # the same watts in every round: not scaled by the resistivity
                 thermal.source_power(source_power[j:j + 1])
             iterations, last = [], {}
+            film = {"increments": [], "vertices": [], "beyond": 0} if curved else None
 
             def one_round(round_i):
                 lap = {}
                 round_laps = _Laps(lap)
+                if curved:                                   # the film about the current theta: both couplings in one loop
+                    thermal.film_linearise(round_i > 1)
+                    round_laps.lap("linearise")
                 el = _revalued_solve(h, board, pairs, case, stamps, thermal_model.element_heat, round_laps)
                 theta, tres = coupled.solve_kkt(el.plan, el.heat, rtol=RTOL, max_iter=MAX_ITER)
                 round_laps.lap("thermal_solve")
                 increment = coupled.update()
                 round_laps.lap("update")
+                if curved:
+                    moved, vertex, film["beyond"] = thermal.film_increment()
+                    film["increments"].append(moved)
+                    film["vertices"].append(vertex)
+                    increment = max(increment, moved)
+                    round_laps.lap("increment")
                 iterations.append({"electrical": int(el.res.iterations), "thermal": int(tres.iterations)})
                 rounds_log.append(dict(lap, case=j, round=round_i))
                 last.update(el=el, theta=theta, tres=tres)
@@ -3999,13 +4275,16 @@ def _solve_electrothermal(prob, meshes, mesh_index_to_layer_index, checked: Chec
             stack_flows.append(_stack_flows(thermal, thermal_model, 1))
             if sources is not None:
                 source_rises.append(thermal.source_report(1))
+            if curved:
+                film = {"rounds": len(increments), "increments": film["increments"], "vertices": film["vertices"],
+                        "converged": converged, "beyond": film["beyond"]}
             per_case.append((el.V, el.residual_norms, el.res, el.cols, el.vals, power, scale, last["theta"], last["tres"], report,
-                             el.heat, increments, iterations, converged, el.flows))
+                             el.heat, increments, iterations, converged, el.flows, film))
         laps.lap("loop")
     laps.lap()
     solutions, couplings, infos = [], [], []
     for j, (V, residual_norms, res, cols, vals, power, scale, theta, tres, report, heat, increments, iterations,
-            converged, flows) in enumerate(per_case):
+            converged, flows, _film) in enumerate(per_case):
         where = f"Load case {j}: " if k > 1 else ""
         _warn_if_block_stalled(res, residual_norms, cols, vals, 1)
         if tres.status != _hip.OK and not tres.rel_residual <= max(RTOL, STALL_WARN_ABOVE):
@@ -4033,6 +4312,8 @@ def _solve_electrothermal(prob, meshes, mesh_index_to_layer_index, checked: Chec
     heat_sources = None if sources is None else (sources, source_power, np.concatenate(source_rises))
     reports = _thermal_reports(board, thermal_model, substituted, resistors, fields, theta, *stacked, heat_val, infos, stack,
                                heat_sources)
+    for report, case in zip(reports, per_case):
+        report.film = case[15]
     env, env_case = envelope_of(theta[:, :n_vert])
     envelope = _thermal_envelope(board, thermal_model.ambient, env, env_case, reports)
     laps.lap("solutions")
@@ -4056,7 +4337,12 @@ def solve_meshed_electrothermal(prob, meshes, mesh_index_to_layer_index, model: 
                   V_k from the electrical solve, the face powers with sigma_m s_f, theta_k from the thermal solve
                   d_k = max_f |thetabar_k,f - thetabar_k-1,f|;   s from theta_k;   stop when d_k <= model.tolerance
 
-    With every alpha 0 the loop is one round and the results have the bits of ``solve_meshed_thermal``.  The Solution holds
+    With every alpha 0 the loop is one round and the results have the bits of ``solve_meshed_thermal``.  With a
+    :class:`FilmCurve` in ``model.thermal.film`` (DESIGN.md "Film curves") the same loop serves both couplings: every round
+    linearises the film about the current theta before the thermal solve, d_k is the larger of the face means' and the
+    vertices' largest change, ``ThermalReport.film`` tells the film's share, and ``total_loss`` equals ``total_heat`` up to
+    the last round's linearisation defect; with every alpha 0 the results then have the bits of ``solve_meshed_thermal``
+    with the same curves (for equal tolerances).  The Solution holds
     the potentials and power densities of the last electrical solve and the ThermalReport is that of the last thermal
     solve, whose load came from that electrical solve with the same scale: ``total_loss`` equals ``total_heat`` equals the
     power the sources deliver in every round, converged or not.  Cases are converged one after another on one assembly and
