@@ -863,7 +863,7 @@ int padne_tsens_sources(padne_ctx *ctx, padne_tsens *ts, int32_t n_obj, int32_t 
  * Created with the copper at ambient: theta = 0, s = s^(0).  PADNE_E_INVALID for a null or foreign handle, an n_mesh that
  * is not the mesh's, a system whose rows' columns do not ascend (an uploaded matrix), an alpha or temperature that is not
  * finite, and a face whose 1 + alpha (T - T0) is not finite and positive (the message names the lowest such face).
- * Lumped resistors keep their resistance. */
+ * Lumped resistors keep their resistance unless padne_coupled_set_resistors names them. */
 typedef struct padne_coupled padne_coupled;
 int padne_coupled_create(padne_ctx *ctx, padne_csr *L, padne_thermal *th, int32_t n_mesh, const double *alpha, double ambient,
                          double conductance_temperature, padne_coupled **out);
@@ -897,6 +897,25 @@ int padne_coupled_solve_kkt(padne_ctx *ctx, padne_coupled *cp, padne_kkt *plan, 
 /* out_host[n_tri] = padne_kkt_power_density_block's value of the one column of `plan`'s finished block, times the used
  * scale of the face (one product on the device) */
 int padne_coupled_power_density(padne_ctx *ctx, padne_coupled *cp, padne_kkt *plan, double *out_host);
+/* Lumped resistors whose resistance follows their temperature ("Resistor coupling"): host arrays [n_res] of the
+ * ends a, b (potential unknowns, vertices or internal nodes), the resistance R the system was assembled with, alpha and T0.
+ * Resistor r conducts g_r s_r, g_r = 1 / R_r, with
+ *     mean_r = (theta[a_r] + theta[b_r]) / 2,   s_r = 1 / (1 + alpha_r * ((mean_r + ambient) - t0_r)).
+ * From then on padne_coupled_update, _update_transient and _reset also form s_r, the increment is the larger of the faces'
+ * and the resistors' largest change of a mean (an invalid face is named first, then the lowest invalid resistor), and
+ * padne_coupled_revalue follows the faces' pass, per row i a resistor touches and in ascending r, with t_r = (s_r - 1) * g_r,
+ * by L[i, j] = L[i, j] + t_r and L[i, i] = L[i, i] - t_r as sequential rounded updates, j the other end; t_r == 0.0 writes
+ * nothing and a resistor with a == b is left out.  The potential block stays symmetric bit for bit.  The resistors start at
+ * ambient (mean 0).  n_res = 0 removes them: every entry then does, bit for bit, what it does on a handle that never had any.
+ * PADNE_E_INVALID for an end outside [0, n_potential), an R that is not finite and positive, an alpha or T0 that is not
+ * finite, a resistor whose 1 + alpha (ambient - T0) is not finite and positive, and a stamp without a stored entry in L; the
+ * handle then keeps the resistors it had. */
+int padne_coupled_set_resistors(padne_ctx *ctx, padne_coupled *cp, int64_t n_res, const int64_t *a, const int64_t *b,
+                                const double *R, const double *alpha, const double *t0);
+/* padne_coupled_get_scale for the resistors: scale_out[n_res] the next revalue's s_r (used = 0) or the last one's (used = 1);
+ * mean_out[n_res] (may be null) the means of the last update.  n_res must be the number set. */
+int padne_coupled_get_resistors(padne_ctx *ctx, const padne_coupled *cp, int32_t used, int64_t n_res, double *scale_out,
+                                double *mean_out);
 
 /* ---- transient: the copper's temperature rise under a schedule of load cases ---------------------
  * No reference counterpart ("Transient").  Backward Euler on C dtheta/dt + A theta = b(t), A the thermal handle's

@@ -228,6 +228,8 @@ SIGNATURES = {
     "padne_coupled_update": (C.c_int, [_P, _P, _I64, _PF64, _PF64]),
     "padne_coupled_solve_kkt": (C.c_int, [_P, _P, _P, _I64, _PI64, _PI32, _PF64, C.POINTER(SolveOpts), _PF64, C.POINTER(SolveInfo)]),
     "padne_coupled_power_density": (C.c_int, [_P, _P, _P, _PF64]),
+    "padne_coupled_set_resistors": (C.c_int, [_P, _P, _I64, _PI64, _PI64, _PF64, _PF64, _PF64]),
+    "padne_coupled_get_resistors": (C.c_int, [_P, _P, C.c_int32, _I64, _PF64, _PF64]),
     "padne_transient_reserve_loads": (C.c_int, [_P, _P, C.c_int32]),
     "padne_coupled_transient_load": (C.c_int, [_P, _P, _P, _P, C.c_int32, _I64, _PI64, _PI32, _PF64, C.c_int32, _PF64]),
     "padne_coupled_update_transient": (C.c_int, [_P, _P, _P, C.c_int32, _PF64]),
@@ -1732,6 +1734,25 @@ class Coupled:
         mean = np.empty(int(n_tri), dtype=np.float64) if means else None
         _check(self.ctx._lib.padne_coupled_get_scale(self.ctx._h, self._h, 1 if used else 0, int(n_tri), _ptr(s, _PF64),
                                                      None if mean is None else _ptr(mean, _PF64)))
+        return (s, mean) if means else s
+
+    def set_resistors(self, a, b, resistance, alpha, t0) -> None:
+        """The lumped resistors whose resistance follows their temperature: ends ``a``, ``b`` (potential unknowns), the
+        assembled ``resistance``, ``alpha`` [1/K] and ``t0`` per resistor; empty arrays remove them."""
+        a, b = np.ascontiguousarray(a, dtype=np.int64).reshape(-1), np.ascontiguousarray(b, dtype=np.int64).reshape(-1)
+        r, al, t = _f64(resistance).reshape(-1), _f64(alpha).reshape(-1), _f64(t0).reshape(-1)
+        if not (a.shape == b.shape == r.shape == al.shape == t.shape):
+            raise ValueError("one end a, end b, resistance, alpha and t0 per resistor")
+        _check(self.ctx._lib.padne_coupled_set_resistors(self.ctx._h, self._h, a.shape[0], _ptr(a, _PI64), _ptr(b, _PI64),
+                                                         _ptr(r, _PF64), _ptr(al, _PF64), _ptr(t, _PF64)))
+
+    def get_resistors(self, n_res: int, used: bool = False, means: bool = False):
+        """``get_scale`` for the resistors: the next revalue's scale (n_res,), or with ``used`` the last one's; with ``means``
+        also the resistors' mean temperature rises of the last update."""
+        s = np.empty(int(n_res), dtype=np.float64)
+        mean = np.empty(int(n_res), dtype=np.float64) if means else None
+        _check(self.ctx._lib.padne_coupled_get_resistors(self.ctx._h, self._h, 1 if used else 0, int(n_res), _ptr(s, _PF64),
+                                                         None if mean is None else _ptr(mean, _PF64)))
         return (s, mean) if means else s
 
     def revalue(self) -> None:

@@ -104,6 +104,15 @@ struct padne_coupled {
     double *s = nullptr, *s_used = nullptr, *prev = nullptr;
     double *alpha = nullptr;                 // [n_mesh] on the device
     double ambient = 0.0, t0 = 0.0;
+    // The lumped resistors whose resistance follows their temperature (padne_coupled_set_resistors), all on the device;
+    // n_res 0 without.  [n_res]: the ends, g = 1 / R, alpha and T0, and s, s_used and prev as for the faces
+    long long n_res = 0, n_rrow = 0, n_inc = 0;
+    int *r_a = nullptr, *r_b = nullptr;
+    double *r_g = nullptr, *r_alpha = nullptr, *r_t0 = nullptr;
+    double *r_s = nullptr, *r_s_used = nullptr, *r_prev = nullptr;
+    // unknown -> resistors: rr_ptr[n_rrow + 1] over the touched rows, and per incidence (resistors ascending within a row)
+    // the resistor and the places in L->vals of the row's entry in the other end's column and of its diagonal
+    int *rr_ptr = nullptr, *rr_res = nullptr, *rr_other = nullptr, *rr_diag = nullptr;
 };
 
 struct padne_transient {
@@ -135,7 +144,8 @@ struct padne_transient {
 namespace padne {
 
 // coupled.hip: the scale kernel and its fold on `theta` (device, null: zeros) -- *d_out (may be null) the largest change of a
-// face mean; PADNE_E_INVALID names the lowest face whose scale is invalid
+// face mean; PADNE_E_INVALID names the lowest face whose scale is invalid.  With resistors set their pass follows: *d_out is
+// the larger of the two increments, and the lowest invalid resistor is named when every face is valid
 int coupled_run_scale(padne_ctx *ctx, padne_coupled *cp, const double *theta, double *d_out);
 
 // thermal.hip: padne_thermal_solve_kkt with every face's conductance sigma[m] * scale[t] in the place of sigma[m] (scale

@@ -4040,13 +4040,21 @@ class ElectroThermalModel:
       ``layer.conductance / (1 + alpha (T - conductance_temperature))``.
     - ``conductance_temperature``: T0, the temperature at which ``Layer.conductance`` holds, in the unit of
       ``thermal.ambient``.
-    - ``tolerance``: the loop stops when no face mean moved by more than this [K] in a round.
-    - ``max_rounds``: the most rounds of the loop."""
+    - ``tolerance``: the loop stops when no face mean (and no resistor's mean) moved by more than this [K] in a round.
+    - ``max_rounds``: the most rounds of the loop.
+    - ``resistor_coefficient``: None = lumped resistors keep their resistance; a float = that alpha [1/K] for every
+      ``Resistor`` of the solved networks (vias are copper barrels: 3.93e-3); a mapping {Resistor: alpha} names resistors by
+      identity or equality, the others get 0.  A resistor at the mean temperature T of its two ends has the resistance
+      ``resistance * (1 + alpha (T - resistor_temperature))``.
+    - ``resistor_temperature``: T0 of the resistors, the temperature at which ``Resistor.resistance`` holds; None =
+      ``conductance_temperature``."""
     thermal: ThermalModel
     temperature_coefficient: object = COPPER_TEMPERATURE_COEFFICIENT
     conductance_temperature: float = 20.0
     tolerance: float = 0.01
     max_rounds: int = 20
+    resistor_coefficient: object = None
+    resistor_temperature: Optional[float] = None
 
 
 @dataclass
@@ -4057,6 +4065,12 @@ class CheckedElectroThermalModel:
     conductance_temperature: float
     tolerance: float
     max_rounds: int
+    resistor_alpha: Optional[list] = None      # per resistor in the order of global_elements' ("R", a, b, R) rows, or None
+    resistor_t0: float = 20.0
+
+    def resistors_follow(self) -> bool:
+        """Whether a resistor's resistance moves with its temperature."""
+        return self.resistor_alpha is not None and any(a != 0.0 for a in self.resistor_alpha)
 
 
 @dataclass
@@ -4068,13 +4082,18 @@ class CouplingReport:
     conductance_scale: list    # per layer, per mesh: TwoForm of s_f, the scale the last electrical solve used
     iterations: list           # per round: {"electrical": iterations of the electrical solve, "thermal": of the thermal one}
     elements: dict             # lumped element -> its element_flows entry in the last electrical solve (current, power, ...)
+    # Resistor -> {"temperature", "scale", "resistance"} of the last electrical solve: the mean temperature of its ends, s_r
+    # and resistance / s_r; empty without a resistor_coefficient
+    resistors: dict = field(default_factory=dict)
 
 
 def check_electrothermal_model(prob, model, filtered_networks=None) -> CheckedElectroThermalModel:
     """``model`` resolved against ``prob``, or ValueError -- before anything reaches the device -- for what
     :func:`check_thermal_model` refuses in ``model.thermal``; a temperature coefficient or conductance temperature that is
     not finite; a mapping key that is no layer of the Problem; a tolerance that is not finite and positive; ``max_rounds``
-    below 1; and an ambient temperature at which a layer's 1 + alpha (ambient - T0) is not positive."""
+    below 1; an ambient temperature at which a layer's 1 + alpha (ambient - T0) is not positive; a resistor coefficient or
+    resistor temperature that is not finite; a ``resistor_coefficient`` key that is no Resistor of the Problem; and a
+    resistor whose 1 + alpha (ambient - T0) is not positive."""
     if not isinstance(model, ElectroThermalModel):
         raise ValueError("model must be an ElectroThermalModel")
     thermal = check_thermal_model(prob, model.thermal, filtered_networks)
@@ -4113,8 +4132,31 @@ def check_electrothermal_model(prob, model, filtered_networks=None) -> CheckedEl
         if not 1 + a * (thermal.ambient - t0) > 0.0:
             raise ValueError(f"layer {layer.name!r}: 1 + alpha (ambient - T0) = {1 + a * (thermal.ambient - t0)!r} is not "
                              "positive: the conductance model does not hold at the ambient temperature")
+    resistor_t0 = t0 if model.resistor_temperature is None else finite(model.resistor_temperature, "the resistor temperature")
+    resistor_alpha = None
+    if model.resistor_coefficient is not None:
+        networks = list(prob.networks) if filtered_networks is None else list(filtered_networks)
+        resistors = [e for network in networks for e in network.elements if element_kind(e) == "Resistor"]
+        if isinstance(model.resistor_coefficient, Mapping):
+            every = [e for network in prob.networks for e in network.elements]
+            given = []
+            for key, value in model.resistor_coefficient.items():
+                if element_kind(key) != "Resistor" or not any(e is key or e == key for e in every):
+                    raise ValueError(f"resistor_coefficient: {key!r} is no Resistor of the Problem")
+                given.append((key, finite(value, "the temperature coefficient of a Resistor")))
+            resistor_alpha = [0.0] * len(resistors)
+            for key, value in given:
+                for i, e in enumerate(resistors):
+                    if e is key or e == key:
+                        resistor_alpha[i] = value
+        else:
+            resistor_alpha = [finite(model.resistor_coefficient, "the resistor coefficient")] * len(resistors)
+        for e, a in zip(resistors, resistor_alpha):
+            if not 1 + a * (thermal.ambient - resistor_t0) > 0.0:
+                raise ValueError(f"{e!r}: 1 + alpha (ambient - T0) = {1 + a * (thermal.ambient - resistor_t0)!r} is not positive: "
+                                 "the resistance model does not hold at the ambient temperature")
     return CheckedElectroThermalModel(thermal=thermal, alpha=alpha, conductance_temperature=t0, tolerance=tolerance,
-                                      max_rounds=max_rounds)
+                                      max_rounds=max_rounds, resistor_alpha=resistor_alpha, resistor_t0=resistor_t0)
 
 
 def picard_verdict(increments, tolerance: float) -> Optional[str]:
@@ -4151,13 +4193,17 @@ def _coupled_handles(board: IndexedBoard, pairs, electro: CheckedElectroThermalM
         try:
             coupled = _hip.Coupled(L.dev, thermal, [electro.alpha[layer_of[i]] for i in range(n_mesh)], thermal_model.ambient,
                                    electro.conductance_temperature)
+            if electro.resistor_alpha is not None:
+                coupled.set_resistors([row[1] for _, row in resistors], [row[2] for _, row in resistors],
+                                      [row[3] for _, row in resistors], electro.resistor_alpha,
+                                      [electro.resistor_t0] * len(resistors))
             sources = _attach_heat_sources(thermal, board.prob, thermal_model, layer_of, n_mesh)
             if capacity is not None:
                 transient = _hip.Transient(thermal, [capacity[layer_of[i]] for i in range(n_mesh)])
                 transient.reserve_loads(n_loads)
             laps.lap("thermal_setup")
             yield types.SimpleNamespace(L=L, thermal=thermal, coupled=coupled, transient=transient, sources=sources,
-                                        resistors=resistors, n_tri=len(L.tri))
+                                        resistors=resistors, n_tri=len(L.tri), resistor_alpha=electro.resistor_alpha)
         finally:
             if transient is not None:
                 transient.close()
@@ -4175,21 +4221,27 @@ def _revalued_solve(handles, board: IndexedBoard, pairs, case: dict, stamps, ele
     rows, cols, vals = stamps
     _drop_plans(handles.L)
     handles.coupled.revalue()
+    resistor_state = None
+    if handles.resistor_alpha is not None:                   # (the used scale and the means it came from)
+        resistor_state = handles.coupled.get_resistors(len(handles.resistors), used=True, means=True)
     laps.lap("revalue")
     plan, V, residual_norms, res, _n_tri, _n_mesh = _solve_block_on_device(handles.L, rows, cols, vals, 1, 1, laps)
     local, Vu = _gather_element_rows([row for _, row in pairs], V, _ROW_UNKNOWNS)
     case_rows = _case_element_rows(pairs, local, case)
+    if resistor_state is not None:                           # the resistance this solve used: R_r / s_r, one division
+        scales = iter(resistor_state[0].tolist())
+        case_rows = [row[:3] + (row[3] / next(scales),) if row[0] == "R" else row for row in case_rows]
     flows = element_flows(case_rows, Vu[:, 0])
     heat = thermal_heat_triples(pairs, [flows]) if element_heat else None
     return types.SimpleNamespace(plan=plan, V=V, residual_norms=residual_norms, res=res, cols=cols, vals=vals,
-                                 case_rows=case_rows, flows=flows, heat=heat)
+                                 case_rows=case_rows, flows=flows, heat=heat, resistor_state=resistor_state)
 
 
 def _picard(round_fn, electro: CheckedElectroThermalModel) -> tuple:
     """The Picard loop: ``round_fn(round)`` runs a round and returns its increment d [K].  (the increments, the verdict of
-    :func:`picard_verdict` on them, None when ``electro.max_rounds`` ended the loop); with every alpha 0 and no film curve
-    one round converges."""
-    one_round = all(a == 0.0 for a in electro.alpha) and not electro.thermal.curved()
+    :func:`picard_verdict` on them, None when ``electro.max_rounds`` ended the loop); with every alpha 0, of the layers and
+    of the resistors, and no film curve one round converges."""
+    one_round = all(a == 0.0 for a in electro.alpha) and not electro.thermal.curved() and not electro.resistors_follow()
     increments, verdict = [], None
     for round_i in range(1, electro.max_rounds + 1):
         increments.append(round_fn(round_i))
@@ -4279,12 +4331,12 @@ def _solve_electrothermal(prob, meshes, mesh_index_to_layer_index, checked: Chec
                 film = {"rounds": len(increments), "increments": film["increments"], "vertices": film["vertices"],
                         "converged": converged, "beyond": film["beyond"]}
             per_case.append((el.V, el.residual_norms, el.res, el.cols, el.vals, power, scale, last["theta"], last["tres"], report,
-                             el.heat, increments, iterations, converged, el.flows, film))
+                             el.heat, increments, iterations, converged, el.flows, film, el.resistor_state))
         laps.lap("loop")
     laps.lap()
     solutions, couplings, infos = [], [], []
     for j, (V, residual_norms, res, cols, vals, power, scale, theta, tres, report, heat, increments, iterations,
-            converged, flows, _film) in enumerate(per_case):
+            converged, flows, _film, resistor_state) in enumerate(per_case):
         where = f"Load case {j}: " if k > 1 else ""
         _warn_if_block_stalled(res, residual_norms, cols, vals, 1)
         if tres.status != _hip.OK and not tres.rel_residual <= max(RTOL, STALL_WARN_ABOVE):
@@ -4302,9 +4354,14 @@ def _solve_electrothermal(prob, meshes, mesh_index_to_layer_index, checked: Chec
             scales.append(tfs)
         renamed = substituted[j][1]
         case_elements = [e for network in board.filtered_networks for e in renamed.get(id(network), network).elements]
+        followed = {}
+        if resistor_state is not None:
+            case_resistors = [e for e, (_, row) in zip(case_elements, pairs) if row[0] == "R"]
+            for e, (_, row), s_r, mean_r in zip(case_resistors, resistors, resistor_state[0].tolist(), resistor_state[1].tolist()):
+                followed[e] = {"temperature": mean_r + thermal_model.ambient, "scale": s_r, "resistance": row[3] / s_r}
         couplings.append(CouplingReport(rounds=len(increments), converged=converged, increments=increments,
                                         conductance_scale=scales, iterations=iterations,
-                                        elements=dict(zip(case_elements, flows))))
+                                        elements=dict(zip(case_elements, flows)), resistors=followed))
     theta = np.concatenate([c[7] for c in per_case])
     stacked = [None if not fields and i == 0 else np.concatenate([c[9][i] for c in per_case]) for i in range(5)]
     heat_val = np.stack([c[10][2].reshape(len(resistors), 2) for c in per_case]) if thermal_model.element_heat else None
@@ -4329,8 +4386,12 @@ def solve_meshed_electrothermal(prob, meshes, mesh_index_to_layer_index, model: 
 
     Face f of a mesh of layer m conducts ``sigma_m s_f`` with ``s_f = 1 / (1 + alpha_m (Tbar_f - T0))``, ``Tbar_f`` the mean
     of its corners' temperatures as the ThermalReport's ``face_temperatures`` hold it.  The thermal side stays as it is: by
-    Wiedemann-Franz kappa = L0 T sigma(T) is constant to first order.  Lumped resistors keep their resistance: a
-    temperature coefficient for vias and other lumped elements is out of scope.  The loop is Picard, one load case at a
+    Wiedemann-Franz kappa = L0 T sigma(T) is constant to first order.  Lumped resistors keep their resistance unless
+    ``model.resistor_coefficient`` is given (DESIGN.md "Resistor coupling"): resistor r then has ``R_r / s_r`` with ``s_r = 1 /
+    (1 + alpha_r (T_r - T0_r))``, ``T_r`` the mean temperature of its two ends; its stamps are revalued on the device with the
+    faces, d_k also covers the resistors' means, the element flows, ``CouplingReport.elements`` and the resistors' heat use
+    the resistance the solve used, ``CouplingReport.resistors`` tells it, and the thermal link of a resistor does not move with
+    R.  With every coefficient 0 the results have the bits of ``resistor_coefficient=None``.  The loop is Picard, one load case at a
     time, from the copper at ambient:
 
         round k:  L = L0 + sum_f (s_f - 1) sigma_m K_f     the electrical system revalued on the device, same pattern
@@ -4417,6 +4478,10 @@ class CouplingTrace:
     iterations: list           # per time: {"electrical": iterations of the electrical solve, "thermal": of the thermal one}
     potentials: dict           # node id -> V over time (NaN where no electrical solve ran)
     stopped: Optional[tuple]   # None, or (time, T, layer index, mesh index within the layer, vertex index, x, y) of the stop
+    # the smallest and the largest scale of a resistor in the step's electrical solve (NaN where no electrical solve ran or
+    # the networks hold no resistor); None without a resistor_coefficient
+    resistor_scale_min: Optional[np.ndarray] = None
+    resistor_scale_max: Optional[np.ndarray] = None
 
 
 _NO_SCENARIOS = ("the transient electro-thermal solve runs one scenario: several in lockstep are not built, because each "
@@ -4494,7 +4559,9 @@ def solve_meshed_electrothermal_transient(prob, meshes, mesh_index_to_layer_inde
     current-driven strip, stable exactly where a steady state exists.  Every step balances (stored_n+1 - stored_n) / dt +
     loss_n+1 against the heat of its own electrical solve, which ``TransientReport.total_heat`` and the layers' ``heat``
     now hold step by step; that heat is the power the sources deliver (``CouplingTrace.delivered``) plus the heat sources'.
-    Nothing iterates within a step, and lumped resistors keep their resistance.
+    Nothing iterates within a step.  Lumped resistors keep their resistance unless ``resistor_coefficient`` of
+    ``model.electrothermal`` is given: then s_r follows theta_n like s_f, the step's heat uses ``R_r / s_r``, and
+    ``CouplingTrace.resistor_scale_min`` / ``resistor_scale_max`` hold the range of s_r step by step.
 
     ``model.initial`` None starts at ambient; a case index starts from that case's steady state, found on the same handles
     by the Picard loop of :func:`solve_meshed_electrothermal` (``tolerance``, ``max_rounds`` and :func:`picard_verdict` of
@@ -4549,7 +4616,9 @@ def solve_meshed_electrothermal_transient(prob, meshes, mesh_index_to_layer_inde
             total = math.fsum(layer_heat + [math.fsum(el.heat[2].tolist()) if el.heat is not None else 0.0])
             if sources is not None:
                 total = total + math.fsum(source_power[j].tolist())
+            followed = el.resistor_state is not None and len(el.resistor_state[0]) > 0
             return types.SimpleNamespace(
+                resistor_range=(float(el.resistor_state[0].min()), float(el.resistor_state[0].max())) if followed else (nan, nan),
                 case=j, V=np.ascontiguousarray(el.V[:, 0]), residual_norm=el.residual_norms[0], res=el.res,
                 power=coupled.power_density(el.plan, h.n_tri) if want_power else None, layer_heat=layer_heat, total_heat=total,
                 delivered=_delivered_power(el.case_rows, el.flows), scale_range=coupled.scale_range(),
@@ -4636,6 +4705,9 @@ def solve_meshed_electrothermal_transient(prob, meshes, mesh_index_to_layer_inde
         potentials={node: np.array([nan if el is None else el.potentials[p] for el in led], dtype=DTYPE)
                     for p, node in enumerate(vprobe_nodes)},
         stopped=stopped)
+    if electro.resistor_alpha is not None:
+        trace.resistor_scale_min = np.array([nan if el is None else el.resistor_range[0] for el in led], dtype=DTYPE)
+        trace.resistor_scale_max = np.array([nan if el is None else el.resistor_range[1] for el in led], dtype=DTYPE)
     laps.lap("solutions")
     return solutions, report, trace
 
