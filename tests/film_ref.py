@@ -27,6 +27,7 @@ import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
 import coupled_ref as C
+import fold_ref
 import sources_ref as Q
 import stack_ref as K
 import thermal_ref as T
@@ -70,6 +71,22 @@ def terms(tables, voff, M, theta):
             if len(rise) > 1:
                 beyond += int((th > rise[-1]).sum())
     return g, c, hM, beyond
+
+
+def increment(voff, theta, lin) -> tuple:
+    """(d, vertex) of definition 5 in the kernels' own order (fold_ref, definitions 2 and 3): every mesh's vertices in tiles of
+    256 of that mesh, a lane without a vertex carrying (-inf, NO_INDEX); then one fold over the tiles of all meshes in mesh
+    order.  The value is max_v |theta[v] - lin[v]| and the vertex the lowest that attains it; (0.0, -1) without vertices."""
+    theta, lin = np.asarray(theta, dtype=np.float64), np.asarray(lin, dtype=np.float64)
+    empty = (-np.inf, fold_ref.NO_INDEX)
+    values, vertices = [np.zeros(0)], [np.zeros(0, dtype=np.int64)]
+    for m in range(len(voff) - 1):
+        lo, hi = int(voff[m]), int(voff[m + 1])
+        v, f = fold_ref.tile_tops(np.abs(theta[lo:hi] - lin[lo:hi]), np.arange(lo, hi, dtype=np.int64), empty=empty)
+        values.append(v)
+        vertices.append(f)
+    d, vertex = fold_ref.fold_top(np.concatenate(values), np.concatenate(vertices), empty=empty)
+    return (0.0, -1) if vertex == fold_ref.NO_INDEX else (d, vertex)
 
 
 def linearised(A0, M, hM0, tables, voff, theta) -> sp.csr_matrix:

@@ -95,13 +95,16 @@ def workgroup_top(values, indices):
     return float(tv[0]), int(tf[0])
 
 
-def _tile_tops(values, indices, empty=EMPTY):
-    """The top of every tile of 256 pairs, the ragged tail filled with ``empty``."""
+def tile_tops(values, indices, empty=EMPTY):
+    """(values (n_tiles,), indices (n_tiles,)): the top of every tile of 256 pairs, the ragged tail filled with ``empty``.  For
+    a kernel whose tiles are per mesh and whose fold runs over all of them (film_fold_kernel): the tops of each mesh,
+    concatenated, go to :func:`fold_top`."""
     return _workgroup_tops(_padded(values, empty[0], np.float64), _padded(indices, empty[1], np.int64))
 
 
-def _fold_top(values, indices, empty=EMPTY):
-    """Definition 2 for tops, on the tile tops of one mesh."""
+def fold_top(values, indices, empty=EMPTY):
+    """Definition 2 for tops, on a list of tile tops (one mesh's, or every mesh's in tile order): (value, index); ``empty``
+    for no tiles."""
     v, f = _padded(values, empty[0], np.float64), _padded(indices, empty[1], np.int64)
     pv, pf = np.full(TILE, float(empty[0])), np.full(TILE, int(empty[1]), dtype=np.int64)
     for rv, rf in zip(v, f):             # a thread without a tile in the last stride merges nothing: the fill is ``empty``
@@ -111,7 +114,7 @@ def _fold_top(values, indices, empty=EMPTY):
 
 def mesh_top(values, indices, empty=EMPTY):
     """One mesh's (value, index) pairs: tiles of 256, then the fold of the tile tops.  A mesh without items gives ``empty``."""
-    return _fold_top(*_tile_tops(values, indices, empty), empty=empty)
+    return fold_top(*tile_tops(values, indices, empty), empty=empty)
 
 
 def fold_bound(n_tiles: int, abs_sum: float) -> float:

@@ -196,19 +196,22 @@ def host_board(prob, meshes, layer_of, model, case=None) -> ResistorBoard:
 COPPER = solver.COPPER_TEMPERATURE_COEFFICIENT
 
 
-def strips_system():
-    """(meshes, sigma, n_vert, n_internal, element rows): two triangle strips of 300 vertices (tests/test_film.py's ``strip``)
-    joined vertex to vertex by 300 resistors -- with the internal node 601 touched rows: two full tiles of the row kernel and a
-    ragged one -- and: a second resistor on the pair of vertex 5, a chain 10 - internal node - 330, a resistor with both ends on
-    vertex 7, and vertex 20 with three resistors, one of them along the mesh edge 20 - 21 (an entry the faces write too), one
-    given from its higher end."""
+def strips_system(n: int = 300):
+    """(meshes, sigma, n_vert, n_internal, element rows): two triangle strips of ``n`` vertices (tests/test_film.py's
+    ``strip``), the second one beyond the end of the first, joined vertex to vertex by ``n`` resistors -- with the internal
+    node 2 n + 1 touched rows; for n = 300 two full tiles of the row kernel and a ragged one -- and: a second resistor on the
+    pair of vertex 5, a chain 10 - internal node - (n + 30), a resistor with both ends on vertex 7, and vertex 20 with three
+    resistors, one of them along the mesh edge 20 - 21 (an entry the faces write too), one given from its higher end.
+    n + 6 resistors, 2 (n + 5) incidences."""
     from test_film import strip
-    meshes = [strip(300, 0.0), strip(300, 200.0)]
-    n_vert = 600
+    n = int(n)
+    assert n > 30
+    meshes = [strip(n, 0.0), strip(n, max(200.0, 0.5 * n))]      # (a strip of n vertices is n / 4 + 0.2 long)
+    n_vert = 2 * n
     rng = np.random.default_rng(11)
-    rows = [("R", i, 300 + i, float(r)) for i, r in zip(range(300), rng.uniform(0.002, 0.02, 300))]
-    rows += [("R", 5, 305, 0.004), ("R", 10, n_vert, 0.003), ("R", n_vert, 330, 0.006), ("R", 7, 7, 0.01), ("R", 20, 21, 0.005),
-             ("R", 322, 20, 0.007)]
+    rows = [("R", i, n + i, float(r)) for i, r in zip(range(n), rng.uniform(0.002, 0.02, n))]
+    rows += [("R", 5, n + 5, 0.004), ("R", 10, n_vert, 0.003), ("R", n_vert, n + 30, 0.006), ("R", 7, 7, 0.01), ("R", 20, 21, 0.005),
+             ("R", n + 22, 20, 0.007)]
     return meshes, [2.0, 0.7], n_vert, 1, rows
 
 

@@ -2,7 +2,8 @@
 how check_thermal_model resolves floats, curves and mixed mappings, the calls that refuse a curve before anything reaches a
 device, the restatement's Newton loop (tests/film_ref.py) against the uniform plate's closed form, and the condition under
 which the device tests of tests/test_film.py may trust their round limit: on every board they use, the host loop from zero
-is converged to 1e-10 of the rise within 12 rounds, with no increment near the tolerance the device loop stops at."""
+is converged to 1e-10 of the rise within 12 rounds, with no increment near the tolerance the device loop stops at; and
+film_ref.increment, the increment in the kernels' order, against the plain rule (the maximum, the lowest vertex)."""
 import math
 
 import numpy as np
@@ -209,3 +210,75 @@ def test_the_boards_of_the_device_tests_converge_within_twelve_rounds(name, coup
     loss = math.fsum((got["hM"] * got["theta"][:spec.B.n_vert]).tolist())
     delivered = spec.B.delivered(got["flows"]) + sum(s.power for s in spec.checked.sources)
     assert abs(loss - delivered) <= 1e-9 * delivered
+
+
+# ---- the increment in the kernels' order --------------------------------------------------------------------------------------
+
+WIDE_VOFF = np.cumsum([0, 66_306, 4, 8_464, 16_770])        # tests/test_many_tiles.py's board: 260 + 1 + 34 + 66 = 361 tiles
+WIDE_TILE0 = np.cumsum([0, 260, 1, 34, 66])                  # the first global tile of every mesh
+
+
+def in_tile(tile: int, lane: int) -> int:
+    """The vertex of lane ``lane`` of the global tile ``tile`` of WIDE_VOFF (tiles are per mesh)."""
+    m = int(np.searchsorted(WIDE_TILE0, tile, side="right") - 1)
+    v = int(WIDE_VOFF[m]) + (tile - int(WIDE_TILE0[m])) * 256 + lane
+    assert v < WIDE_VOFF[m + 1]
+    return v
+
+
+def plain_increment(theta, lin):
+    """The rule as DESIGN.md words it: the largest |theta - lin| and the lowest vertex that attains it."""
+    moved = np.abs(theta - lin)
+    return float(moved.max()), int(np.argmax(moved))
+
+
+def exact_pair(n, seed):
+    """(theta, lin) in 64ths, so that every |theta - lin| is exact: below 1, of both signs, with many ties."""
+    rng = np.random.default_rng(seed)
+    lin = rng.integers(-640, 640, n) / 64.0
+    return lin + rng.choice([-1.0, 1.0], n) * (rng.integers(0, 64, n) / 64.0), lin
+
+
+def test_the_increment_is_the_plain_rule_with_ties_across_tiles_and_strides():
+    """Equal largest changes in tiles 3 (wave 0), 259 (A's ragged last tile: lane 3 of the second stride) and 300 (D: lane 44 of
+    the second stride) go to the lowest vertex; taken away one after the other, the next one wins; a larger one wins wherever it
+    sits, the board's last vertex (the ragged tile 360) included."""
+    n = int(WIDE_VOFF[-1])
+    theta, lin = exact_pair(n, 5)
+    assert F.increment(WIDE_VOFF, theta, lin) == plain_increment(theta, lin)
+    at = [in_tile(3, 77), in_tile(259, 1), in_tile(300, 200)]
+    assert at[1] // 256 == 259 and WIDE_VOFF[1] - at[1] < 256 and at[2] >= WIDE_VOFF[3]
+    for sign, v in zip((1.0, -1.0, 1.0), at):
+        theta[v] = lin[v] + sign * 2.0
+    for k, v in enumerate(at):
+        assert F.increment(WIDE_VOFF, theta, lin) == (2.0, v) == plain_increment(theta, lin)
+        theta[v] = lin[v]                                    # this one moves no more: the next tie holds the top
+    last = n - 1
+    assert last == in_tile(360, 129)
+    for v in (last, in_tile(259, 0), in_tile(260, 3), in_tile(256, 255), 0):
+        theta[v] = lin[v] - 3.0
+        assert F.increment(WIDE_VOFF, theta, lin) == (3.0, v) == plain_increment(theta, lin)
+        theta[v] = lin[v]
+    theta[last], theta[int(WIDE_VOFF[1]) - 1] = lin[last] + 3.0, lin[int(WIDE_VOFF[1]) - 1] - 3.0       # both ragged tiles tie
+    assert F.increment(WIDE_VOFF, theta, lin) == (3.0, int(WIDE_VOFF[1]) - 1)
+
+
+def test_the_increment_of_an_all_equal_vector_and_of_small_boards():
+    n = int(WIDE_VOFF[-1])
+    lin = np.linspace(0.0, 40.0, n)
+    assert F.increment(WIDE_VOFF, lin, lin) == (0.0, 0)                      # the complete tie over 361 tiles
+    assert not math.copysign(1.0, F.increment(WIDE_VOFF, lin, lin)[0]) < 0
+    assert F.increment(WIDE_VOFF, np.full(n, 4.5), np.full(n, 2.0)) == (2.5, 0)
+    for voff in ([0, 255], [0, 256], [0, 257], [0, 0, 300, 300, 513], [0, 1]):      # ragged, full, one into a second tile, empty meshes
+        theta, lin = exact_pair(voff[-1], voff[-1])
+        assert F.increment(voff, theta, lin) == plain_increment(theta, lin), voff
+        theta[-1] = lin[-1] + 1.0                            # the last lane of a ragged last tile
+        assert F.increment(voff, theta, lin) == (1.0, voff[-1] - 1)
+    assert F.increment([0, 0], np.zeros(0), np.zeros(0)) == (0.0, -1)
+
+
+def test_the_increment_reads_the_vertices_only():
+    """theta and lin run over all potential unknowns; what lies behind voff[-1] (internal nodes) is not looked at."""
+    theta, lin = exact_pair(700, 9)
+    theta[650] = lin[650] + 50.0
+    assert F.increment([0, 300, 600], theta, lin) == plain_increment(theta[:600], lin[:600])

@@ -1,6 +1,7 @@
 """tests/fold_ref.py against a literal lane-by-lane simulation of the kernels that fold in the order of error.hpp -- 256
 threads, ``__shfl_down(v, off, 64)`` where a lane whose source lies beyond lane 63 keeps its own value, the four LDS slots,
-the strided loop as the kernels write it -- and against math.fsum within fold_bound; ties of the tops.  No GPU."""
+the strided loop as the kernels write it -- and against math.fsum within fold_bound; ties of the tops; tile_tops and
+fold_top, the two halves of mesh_top, on their own.  No GPU."""
 import math
 
 import numpy as np
@@ -193,3 +194,66 @@ def test_workgroup_top_of_one_tile():
     assert F.workgroup_top(values, index) == F.EMPTY
     values[[65, 130]], index[[65, 130]] = 4.0, (9, 7)
     assert F.workgroup_top(values, index) == (4.0, 7)
+
+
+# ---- the two halves of mesh_top, for a fold that runs over the tiles of several meshes --------------------------------------
+
+def sim_fold_top(tv, tf, empty):
+    """The fold kernel alone on a list of tile tops: the strided loop as the kernels write it, then the workgroup's top."""
+    v, f = np.full(256, float(empty[0])), np.full(256, int(empty[1]), dtype=np.int64)
+    i = THREAD.copy()
+    while (i < len(tv)).any():
+        live = i < len(tv)
+        v[live], f[live] = sim_merge(v[live], f[live], tv[i[live]], tf[i[live]])
+        i = i + 256
+    v, f = sim_top4(*sim_wave_top(v, f))
+    return float(v), int(f)
+
+
+@pytest.mark.parametrize("empty", [F.EMPTY, (-np.inf, F.NO_INDEX)])
+@pytest.mark.parametrize("n", [0, 1, 255, 256, 257, 3 * 256 + 130])
+def test_tile_tops_are_the_simulations_and_the_plain_rule_per_tile(n, empty):
+    rng = np.random.default_rng(n + 1)
+    values = rng.integers(0, 7, n).astype(np.float64)
+    index = 1000 + np.arange(n, dtype=np.int64)
+    tv, tf = F.tile_tops(values, index, empty=empty)
+    assert tv.shape == tf.shape == (-(-n // 256),)
+    if n:
+        sv, sf = sim_top4(*sim_wave_top(sim_tiles(values, empty[0]), sim_tiles(index, empty[1])))
+        assert np.array_equal(tv, sv) and np.array_equal(tf, sf)
+    for t in range(len(tv)):
+        part = values[t * 256:(t + 1) * 256]
+        assert (tv[t], tf[t]) == (part.max(), 1000 + t * 256 + int(np.argmax(part)))
+    assert F.mesh_top(values, index, empty=empty) == F.fold_top(tv, tf, empty=empty)
+
+
+@pytest.mark.parametrize("empty", [F.EMPTY, (-np.inf, F.NO_INDEX)])
+@pytest.mark.parametrize("n_tiles", [0, 1, 64, 65, 256, 257, 361, 516, 770])
+def test_fold_top_is_the_simulation_and_the_plain_rule(n_tiles, empty):
+    """Tile tops as several meshes leave them: values with many ties, indices ascending with gaps (a ragged tile ends its mesh),
+    and tiles that hold nothing (``empty``) in between."""
+    rng = np.random.default_rng(n_tiles)
+    tv = rng.integers(0, 5, n_tiles).astype(np.float64)
+    tf = np.cumsum(rng.integers(1, 257, n_tiles)).astype(np.int64)
+    hollow = rng.random(n_tiles) < 0.2
+    tv[hollow], tf[hollow] = empty
+    got = F.fold_top(tv, tf, empty=empty)
+    assert got == sim_fold_top(tv, tf, empty)
+    if (~hollow).any():
+        top = tv[~hollow].max()
+        assert got == (top, int(tf[~hollow & (tv == top)].min()))
+    else:
+        assert got == (float(empty[0]), F.NO_INDEX)
+
+
+@pytest.mark.parametrize("where", [(3, 259), (259, 300), (104, 360), (0, 256), (255, 256), (200, 513), (256, 512)])
+def test_fold_top_ties_between_strides_and_waves_go_to_the_lowest_index(where):
+    lo, hi = where
+    tv, tf = np.zeros(516), 256 * np.arange(516, dtype=np.int64) + 17
+    tv[[lo, hi]] = 2.0
+    empty = (-np.inf, F.NO_INDEX)
+    assert F.fold_top(tv, tf, empty=empty) == (2.0, int(tf[lo])) == sim_fold_top(tv, tf, empty)
+    tv[hi] = np.nextafter(2.0, 3.0)
+    assert F.fold_top(tv, tf, empty=empty) == (tv[hi], int(tf[hi]))
+    tv[hi], tf[hi] = 2.0, 5                                  # the rule, not the position: the later tile holds the lower index
+    assert F.fold_top(tv, tf, empty=empty) == (2.0, 5) == sim_fold_top(tv, tf, empty)

@@ -29,6 +29,23 @@ Folds added after the first ones, and what each reaches on this board:
   coupled_transient_heat_fold_kernel       test_electrothermal_transient_load_and_...    per mesh as the faces above: A 514 tiles
   coupled_transient_range_fold_kernel      the same                                      all 708 face tiles by one workgroup: 3 strides, the
                                                                                          smallest in the last tile, the largest in tile 300
+  film_terms_kernel's count and            test_film_terms_and_the_count_above_the_...   the tiles of all meshes as one list, A 0-259, B 260,
+  film_fold_kernel's sum of it                                                           C 261-294, D 295-360: 361 tiles, lanes 0-104 take 2
+                                                                                         strides, all four waves; a count of 2 from tiles 256
+                                                                                         and 360 alone (lanes 0 and 104, second stride)
+  film_fold_kernel (increment, its         test_film_increment_its_vertex_the_count_...  the winner in tile 200 (wave 3, first stride), 259
+  vertex, the count), hM of the pass                                                     (lane 3, second), 300 (lane 44, second), 360 (lane 104,
+                                                                                         second, a ragged tile); the complete tie of 361 tiles
+  coupled_resistor_scale_kernel +          test_resistor_scale_means_and_increment_...   66 006 resistors of the long strips (below): 258
+  coupled_fold_kernel on its tiles                                                       tiles, lanes 0-1 take 2 strides, all four waves; the
+                                                                                         winner in tile 257, 256 (second stride), 200 (wave 3)
+  the lowest invalid resistor              test_the_lowest_invalid_resistor_across_...   tiles 100 and 257 of the 258; tile 257 alone
+  coupled_resistor_places_kernel,          test_resistor_revalue_on_516_tiles_of_rows    132 010 incidences and 132 001 touched rows: 516
+  coupled_resistor_revalue_kernel                                                        workgroups each (no fold: rows beyond a few tiles)
+
+The resistors' tests run on resistor_coupling_ref.strips_system(66 000), two strips of 66 000 vertices joined vertex to vertex,
+not on the board above, whose elements are a handful.  sample_fields_fold_kernel's three strides are held in
+tests/test_temperature_sampling.py (a raster of 516 tiles).
 
 Where the summed term is a device output, or one IEEE operation on device outputs, the per-mesh sum is compared bit for bit
 with fold_ref.  Elsewhere it is compared with math.fsum of the restatement's per-item terms within fold_ref.fold_bound plus
@@ -43,20 +60,24 @@ import scipy.sparse as sp
 
 import coupled_ref as CR
 import currents_ref as C
+import film_ref as FR
 import fold_ref as F
 import goal_ref as GR
 import helpers as H
+import resistor_coupling_ref as RC
 import sdirk_ref as SD
 import sensitivity_ref as S
 import sources_ref as SR
 import stack_ref as K
+import test_film as TF
 import test_thermal_sensitivity_kernels as KT
 import thermal_ref as T
 import transient_ref as R
 from padne_amd import _hip, mesh, problem as P, solver, synthetic
 from test_load_case_currents import finished_block, plan_cuts
+from test_resistor_coupling import AMBIENT, T0, coefficients, opened
 from test_stack_host import G
-from test_thermal import FILM_STIFF, links_of, per_mesh, quiet
+from test_thermal import FILM_STIFF, links_of, per_mesh, quiet, sorted_csr
 
 pytestmark = pytest.mark.gpu
 
@@ -636,3 +657,248 @@ def test_electrothermal_transient_load_and_scale_range(wide):
         assert mesh_heat[m] == F.mesh_sum(Pf[lo:hi]), m
         w.sum_check(mesh_heat[m], Pf[lo:hi], np.zeros(1), tiles(hi - lo), f"copper heat, mesh {m}")
     assert (mesh_heat > 0.0).all()
+
+
+# ---- film curves ----------------------------------------------------------------------------------------------------------------------
+
+FILM_ORDER = (64, 1, 2, 2)                                   # knots of the tables of A, B, C and D
+FILM_TILE0 = np.cumsum([0] + [COUNTS[name][1] for name in GRIDS])      # the first global tile of every mesh: A 0, B 260, C 261, D 295
+#            heated vertex as (mesh, tile of the mesh, lane), watts, the global tile of film_fold_kernel it lies in
+FILM_RUNS = [((0, 200, 5), 0.05, 200), ((0, 259, 1), 0.5, 259), ((3, 5, 9), 0.05, 300), ((3, 65, 129), 0.3, 360)]
+
+
+def film_tile(w, v):
+    """The global tile of film_terms_kernel that holds vertex v: the tiles are per mesh and numbered through."""
+    m = int(np.searchsorted(w.voff, v, side="right")) - 1
+    return int(FILM_TILE0[m]) + (int(v) - int(w.voff[m])) // 256
+
+
+def film_tables(w):
+    tables = TF.tables_for(w.film, FILM_ORDER)
+    assert [len(rise) for rise, _film in tables] == list(FILM_ORDER) and FILM_TILE0[-1] == 361
+    return tables
+
+
+def beyond_of(w, tables, theta):
+    """The vertices above the last knot of their mesh's table, tables of one knot left out."""
+    return np.concatenate([np.flatnonzero(theta[v0:v1] > rise[-1]) + v0 for (rise, _film), (v0, v1) in
+                           zip(tables, (w.verts(m) for m in range(w.n_mesh))) if len(rise) > 1] + [np.zeros(0, dtype=np.int64)])
+
+
+def test_film_terms_and_the_count_above_the_last_knot_on_361_tiles(wide):
+    """tests/test_film.py's comparison of the terms on this board: g, c, hM and the count for a theta on, beside and beyond the
+    knots; for 1e6 everywhere, where every tile of a table of more than one knot counts 256 or its ragged rest; and for two
+    vertices above their last knot, one in tile 256 and one at the end of tile 360 -- lanes 0 and 104 of film_fold_kernel, both
+    in the second stride.  Two calls give the same bits and the matrix keeps its own."""
+    w = wide
+    tables = film_tables(w)
+    two = np.zeros(w.n_vert)
+    planted = [256 * 256 + 3, w.n_vert - 1]
+    two[planted] = 100.0
+    assert [film_tile(w, v) for v in planted] == [256, 360] and all(rise[-1] < 100.0 for rise, _film in tables)
+    thetas = [TF.probing_theta(tables, w.voff, 3), np.full(w.n_vert, 1e6), two]
+    th = w.thermal()
+    try:
+        th.set_film_curves(tables)
+        before = th.matrix().to_scipy().data.copy()
+        got = [th.film_terms(theta, w.n_vert) for theta in thetas]
+        again = [th.film_terms(theta, w.n_vert) for theta in thetas]
+        after = th.matrix().to_scipy().data.copy()
+        M = th.lumped(w.n_vert)
+    finally:
+        th.close()
+    assert np.array_equal(M, w.M) and TF.same_bits(before, after)
+    for theta, out, twice in zip(thetas, got, again):
+        want = FR.terms(tables, w.voff, M, theta)
+        for k, what in enumerate(("g", "c", "hM")):
+            assert TF.same_bits(out[k], want[k]), what
+            assert TF.same_bits(twice[k], out[k]), what
+        print("above the last knot:", out[3])
+        assert out[3] == want[3] == twice[3] == len(beyond_of(w, tables, theta))
+    assert got[0][3] > 0 and (np.unique([film_tile(w, v) for v in beyond_of(w, tables, thetas[0])]) >= 256).any()
+    assert got[1][3] == COUNTS["A"][0] + COUNTS["C"][0] + COUNTS["D"][0] == w.n_vert - COUNTS["B"][0]
+    assert got[2][3] == 2
+
+
+def test_film_increment_its_vertex_the_count_and_hM_on_361_tiles(wide):
+    """Two Newton rounds by hand per heated vertex, node heat at one vertex each.  After every padne_thermal_film_increment the
+    triple is, exactly: the largest |theta_new - theta_lin| of the device's own downloaded thetas, the lowest vertex that attains
+    it, and the number of vertices above their last knot; film_ref.increment states the first two in the kernels' order and
+    agrees.  The condition under which this reaches what the table at the top says: the change peaks at the heated vertex in
+    both rounds (asserted on the expected value; on the host restatement of this board the runner-up of the second round, a
+    neighbour, lies 0.5 % to 5 % below), in tile 200 (wave 3 of the first stride), 259 (lane 3 of the second stride), 300 (lane
+    44) and 360 (lane 104: the board's last vertex, in a ragged tile).  0.5 W and 0.3 W lift the heated vertex of tiles 259 and
+    360 above the last knot, 90 K: a count that is not 0, from the second stride (asserted on the host's count).  The film loss
+    of the report afterwards holds the hM the increment pass rewrote: fold_ref's sum of hM(theta) theta bit for bit.  A dead
+    load is the complete tie over 361 tiles: (+0.0, vertex 0, 0).  With the curves removed the matrix has the bits it had."""
+    w = wide
+    tables = film_tables(w)
+    none = np.zeros((1, w.n_tri))
+    th = w.thermal()
+    runs = []
+    try:
+        before = th.matrix().to_scipy().data.copy()
+        th.set_film_curves(tables)
+        M = th.lumped(w.n_vert)
+        for (m, tile, lane), watts, _where in FILM_RUNS:
+            v = w.verts(m)[0] + tile * 256 + lane
+            th.film_linearise(False)
+            first, res = th.solve(none, ([v], [0], [watts]))
+            assert res.status == _hip.OK
+            rounds = [(th.film_increment(), first[0], np.zeros(w.n_pot))]
+            th.film_linearise(True)
+            second, res = th.resolve()
+            assert res.status == _hip.OK
+            rounds.append((th.film_increment(), second[0], first[0]))
+            runs.append((v, rounds, th.report(1, w.n_tri, w.n_vert, fields=False, envelope=False)[4][0]))
+        linearised = th.matrix().to_scipy().data.copy()
+        th.film_linearise(False)
+        cold, res = th.solve(none)
+        dead = th.film_increment()
+        th.set_film_curves([])
+        after = th.matrix().to_scipy().data.copy()
+    finally:
+        th.close()
+    assert runs[-1][0] == w.n_vert - 1
+    counted_late = 0
+    for (v, rounds, loss), (_at, watts, where) in zip(runs, FILM_RUNS):
+        for k, (got, new, lin) in enumerate(rounds):
+            moved = np.abs(new[:w.n_vert] - lin[:w.n_vert])
+            above = beyond_of(w, tables, new[:w.n_vert])
+            want = (float(moved.max()), int(np.argmax(moved)), len(above))
+            print("tile", where, "round", k, "device", got, "host", want, "runner-up", np.sort(moved)[-2])
+            assert film_tile(w, want[1]) == where and want[1] == v and want[0] > 0.0
+            assert got == want
+            assert FR.increment(w.voff, new, lin) == want[:2]
+            assert want[2] == FR.terms(tables, w.voff, M, new[:w.n_vert])[3]
+            if watts > 0.1:
+                assert want[2] > 0 and max(film_tile(w, u) for u in above) >= 256
+                counted_late += 1
+        theta = rounds[1][1]
+        hM_want = FR.terms(tables, w.voff, M, theta[:w.n_vert])[2]
+        assert not TF.same_bits(hM_want, w.hM)
+        for mesh_i in range(w.n_mesh):
+            v0, v1 = w.verts(mesh_i)
+            terms = hM_want[v0:v1] * theta[v0:v1]
+            assert loss[mesh_i] == F.mesh_sum(terms), (where, mesh_i)
+            assert abs(loss[mesh_i] - fsum(terms)) <= F.fold_bound(tiles(v1 - v0), fsum(np.abs(terms))), (where, mesh_i)
+    assert counted_late == 4
+    assert not cold.any() and dead == (0.0, 0, 0) and not np.signbit(dead[0])
+    assert TF.same_bits(after, before) and not TF.same_bits(linearised, before)
+
+
+# ---- resistors that follow their temperature -----------------------------------------------------------------------------------------
+
+N_LONG = 66_000
+
+
+@pytest.fixture(scope="module")
+def long_strips(ctx):
+    """resistor_coupling_ref.strips_system(66 000) on the device, opened as tests/test_resistor_coupling.py opens its strips:
+    66 006 resistors (258 tiles of coupled_resistor_scale_kernel), 132 001 touched rows (516 tiles of
+    coupled_resistor_revalue_kernel) and 132 010 incidences (516 tiles of coupled_resistor_places_kernel)."""
+    with opened(ctx, "strips", n=N_LONG) as d:
+        assert d.n_res == N_LONG + 6 and tiles(d.n_res) == 258 and d.n_pot == 2 * N_LONG + 1
+        incident = np.concatenate([d.a[d.a != d.b], d.b[d.a != d.b]])
+        assert len(incident) == 132_010 and len(np.unique(incident)) == 132_001 and tiles(132_001) == 516
+        try:
+            yield d
+        finally:
+            d.coupled.close()                                # (the revalue test leaves a handle of its own here)
+
+
+def test_resistor_scale_means_and_increment_on_258_tiles(long_strips):
+    """A random theta first: scales and means are the restatement's, the increment the larger of the faces' and the resistors'.
+    Then three thetas that differ from the one before at both ends of ONE resistor, in tile 257 (lane 1 of coupled_fold_kernel,
+    second stride), 256 (lane 0, second stride) and 200 (wave 3): the increment is that resistor's change.  It is the
+    resistors' and not the faces' because a face sees only one of the two ends, and through a third of its mean (asserted)."""
+    d = long_strips
+    cp = d.coupled
+    alpha, t0, thetas, _k = coefficients(d, np.random.default_rng(41))
+    bumped = (257 * 256 + 9, 256 * 256 + 100, 200 * 256 + 17)
+    assert all(r < N_LONG for r in bumped) and [r // 256 for r in bumped] == [257, 256, 200]
+    thetas = thetas[:1]
+    for r, bump in zip(bumped, (7.5, 3.25, 1.125)):
+        thetas.append(thetas[-1].copy())
+        thetas[-1][[d.a[r], d.b[r]]] += bump
+    cp.set_resistors(d.a, d.b, d.R, alpha, t0)
+    cp.reset()
+    got = []
+    for theta in thetas:
+        inc = cp.update(theta)
+        got.append((inc, *cp.get_resistors(d.n_res, means=True)))
+    prev, prev_f = np.zeros(d.n_res), np.zeros(d.n_tri)
+    for theta, (inc, s, mean), r in zip(thetas, got, (None,) + bumped):
+        s_want, mean_want, d_r = RC.resistor_scale(theta, d.a, d.b, alpha, AMBIENT, t0, prev)
+        mean_f = CR.face_means(d.tri, theta)
+        d_f = np.abs(mean_f - prev_f)
+        print("increment", inc, "resistors", d_r.max(), "at", int(np.argmax(d_r)), "tile", int(np.argmax(d_r)) // 256, "faces", d_f.max())
+        assert np.array_equal(s, s_want) and np.array_equal(mean, mean_want)
+        assert inc == max(d_f.max(), d_r.max()) and inc > 0.0
+        if r is not None:
+            assert inc == d_r.max() and int(np.argmax(d_r)) == r and d_r.max() > d_f.max()
+            assert np.count_nonzero(d_r) == 1
+        prev, prev_f = mean_want, mean_f
+
+
+def test_the_lowest_invalid_resistor_across_tiles(long_strips):
+    """alpha = -0.05 at 60 K above ambient, as tests/test_resistor_coupling.py provokes the report (a refusal by value): of two
+    in tiles 100 and 257 the one in tile 100 is named, and the one in tile 257 when it is alone."""
+    d = long_strips
+    cp = d.coupled
+    early, late = 100 * 256 + 7, 257 * 256 + 3
+    assert late < d.n_res and (early // 256, late // 256) == (100, 257)
+    for planted, named in (([early, late], early), ([late], late)):
+        bad = np.zeros(d.n_res)
+        bad[planted] = -0.05
+        cp.set_resistors(d.a, d.b, d.R, bad, np.full(d.n_res, T0))
+        with pytest.raises(ValueError, match=rf"resistor {named}\b"):
+            cp.update(np.full(d.n_pot, 60.0))
+    cp.set_resistors(d.a, d.b, d.R, np.zeros(d.n_res), np.full(d.n_res, T0))
+    assert cp.update(np.full(d.n_pot, 60.0)) >= 0.0          # and with none the same theta is taken
+
+
+def test_resistor_revalue_on_516_tiles_of_rows(long_strips):
+    """tests/test_resistor_coupling.py::test_revalue_is_the_restatement_bit_for_bit's sequence on the long strips: the values of
+    the restatement's sequential updates on 132 001 touched rows, a symmetric potential block, zero coefficients the face-only
+    bytes, and after the close the assembled bytes."""
+    d = long_strips
+    rng = np.random.default_rng(42)
+    alpha, t0, thetas, _k = coefficients(d, rng)
+    s_f = rng.uniform(0.5, 1.5, d.n_tri)
+    cp = d.coupled
+    L0 = sorted_csr(d.L.to_scipy())
+
+    def revalued(al):
+        cp.set_resistors(d.a, d.b, d.R, al, t0)
+        cp.update(thetas[0])
+        cp.set_scale(s_f)
+        cp.revalue()
+        return sorted_csr(d.L.to_scipy()), cp.get_resistors(d.n_res, used=True)
+
+    L, used = revalued(alpha)
+    L_again, _ = revalued(alpha)
+    L_ones, used_ones = revalued(np.zeros(d.n_res))
+    cp.set_resistors([], [], [], [], [])
+    cp.update(thetas[0])
+    cp.set_scale(s_f)
+    cp.revalue()
+    L_faces = sorted_csr(d.L.to_scipy())
+    cp.set_resistors(d.a, d.b, d.R, alpha, t0)
+    cp.revalue()
+    cp.close()
+    L_after = sorted_csr(d.L.to_scipy())
+    d.coupled = _hip.Coupled(d.L, d.thermal, d.face_alpha, AMBIENT, T0)      # for whichever test of the fixture runs next
+    sr, _mean, _d = RC.resistor_scale(thetas[0], d.a, d.b, alpha, AMBIENT, t0, np.zeros(d.n_res))
+    faces = CR.revalue(L0, d.xy, d.tri, d.face_mesh, d.sigma, s_f)
+    at = RC.places(L0, d.a, d.b)
+    want = RC.revalue_resistors(faces, at, sr, 1 / d.R)
+    assert len(at) == 132_010 and tiles(len({row for row, *_ in at})) == 516
+    assert np.array_equal(used, sr) and (used_ones == 1.0).all()
+    assert np.array_equal(L.indices, L0.indices) and np.array_equal(L.data, want.data) and np.array_equal(L_again.data, L.data)
+    assert (want != faces).nnz > 2 * N_LONG
+    K = L[:d.n_pot, :d.n_pot]
+    assert (K != K.T).nnz == 0
+    assert L_ones.data.tobytes() == L_faces.data.tobytes() == faces.data.tobytes()
+    assert np.array_equal(L_after.data, L0.data) and not np.array_equal(L.data, L0.data)
+    assert faces[20, 21] != L0[20, 21] and L[20, 21] != faces[20, 21] and L[20, 21] == L[21, 20]

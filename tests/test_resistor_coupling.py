@@ -40,11 +40,12 @@ def ctx():
 
 
 @contextlib.contextmanager
-def opened(ctx, name):
+def opened(ctx, name, n=300):
     """A board on the device with its thermal handle and a coupling handle: a namespace of ``L`` (the device matrix),
-    ``coupled``, the flattened mesh, ``sigma`` and ``face_alpha`` per mesh, and the resistors' ``a``, ``b``, ``R``."""
+    ``thermal``, ``coupled``, the flattened mesh, ``sigma`` and ``face_alpha`` per mesh, and the resistors' ``a``, ``b``, ``R``.
+    ``n``: the length of the strips of "strips" (tests/test_many_tiles.py takes long ones)."""
     if name == "strips":
-        flat, sigma, n_vert, n_internal, rows = RC.strips_system()
+        flat, sigma, n_vert, n_internal, rows = RC.strips_system(n)
         xy, tri, face_mesh, voff, toff = T.flatten(flat)
         n_pot = n_vert + n_internal
         L = ctx.assemble_system(n_pot, xy, np.concatenate([t for _xy, t in flat]), voff, toff, sigma, *RC.resistor_stamps(rows))
@@ -63,8 +64,8 @@ def opened(ctx, name):
         face_alpha = [3.93e-3 * (1 + 0.25 * m) for m in range(len(sigma))]
         coupled = _hip.Coupled(L, thermal, face_alpha, AMBIENT, T0)
         stack.callback(coupled.close)
-        yield types.SimpleNamespace(L=L, coupled=coupled, xy=xy, tri=tri, face_mesh=face_mesh, sigma=sigma, face_alpha=face_alpha,
-                                    n_pot=n_pot, n_tri=len(tri), a=np.array([row[1] for row in rows]),
+        yield types.SimpleNamespace(L=L, thermal=thermal, coupled=coupled, xy=xy, tri=tri, face_mesh=face_mesh, sigma=sigma,
+                                    face_alpha=face_alpha, n_pot=n_pot, n_tri=len(tri), a=np.array([row[1] for row in rows]),
                                     b=np.array([row[2] for row in rows]), R=np.array([row[3] for row in rows]), n_res=len(rows))
 
 

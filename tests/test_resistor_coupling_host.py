@@ -88,6 +88,34 @@ def test_the_scale_expressions():
     assert s.tolist() == [1 / (1 + 4e-3 * ((20.0 + 25.0) - 20.0)), 1.0, 1 / (1 + -1e-3 * ((50.0 + 25.0) - 30.0))]
 
 
+def test_the_strips_of_300_are_the_board_they_were_and_longer_ones_keep_their_shape():
+    """strips_system(n): for n = 300 (and by default) the board written out here, value for value; for another n the same
+    extras at the same places relative to n, strips that do not overlap, and every stamp on a stored entry."""
+    from test_film import strip
+    rng = np.random.default_rng(11)
+    rows = [("R", i, 300 + i, float(r)) for i, r in zip(range(300), rng.uniform(0.002, 0.02, 300))]
+    rows += [("R", 5, 305, 0.004), ("R", 10, 600, 0.003), ("R", 600, 330, 0.006), ("R", 7, 7, 0.01), ("R", 20, 21, 0.005),
+             ("R", 322, 20, 0.007)]
+    want = ([strip(300, 0.0), strip(300, 200.0)], [2.0, 0.7], 600, 1, rows)
+    for got in (RC.strips_system(), RC.strips_system(300)):
+        assert got[1:] == want[1:] and len(got[0]) == 2
+        for (xy, tri), (xy_want, tri_want) in zip(got[0], want[0]):
+            assert xy.tobytes() == xy_want.tobytes() and xy.dtype == xy_want.dtype
+            assert tri.tobytes() == tri_want.tobytes() and tri.dtype == tri_want.dtype
+    n = 1000
+    meshes, sigma, n_vert, n_internal, rows = RC.strips_system(n)
+    assert (sigma, n_vert, n_internal, len(rows)) == ([2.0, 0.7], 2 * n, 1, n + 6)
+    assert [len(xy) for xy, _tri in meshes] == [n, n] and meshes[0][0][:, 0].max() < meshes[1][0][:, 0].min()
+    assert [row[1:3] for row in rows[:n]] == [(i, n + i) for i in range(n)]
+    assert [row[1:] for row in rows[n:]] == [(5, n + 5, 0.004), (10, 2 * n, 0.003), (2 * n, n + 30, 0.006), (7, 7, 0.01), (20, 21, 0.005),
+                                            (n + 22, 20, 0.007)]
+    L0, _r = C.O.assemble_system([(xy, tri, g) for (xy, tri), g in zip(meshes, sigma)], n_internal, rows, 0)
+    L0 = sp.csr_matrix(L0)
+    L0.sort_indices()
+    at = RC.places(L0, [row[1] for row in rows], [row[2] for row in rows])      # (asserts that every entry is stored)
+    assert len(at) == 2 * (n + 5) and len({row for row, *_ in at}) == 2 * n + 1
+
+
 # ---- 2. a via in series with a current source ------------------------------------------------------------------------------
 
 def test_the_series_via_meets_its_closed_form():

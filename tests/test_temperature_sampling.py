@@ -1,8 +1,9 @@
 """``TemperatureSampler`` on the device: every sample of a block of fields against the brute-force restatement
 (tests/temperature_sampling_ref.py) bit for bit, the electrical sampler's bits through the same kernel, rasters and their
-tops, independence of the index, the steady and the transient reports end to end, the handle's lifetime and the C
-entries' refusals."""
+tops, independence of the index, the steady and the transient reports end to end, the handle's lifetime, the C entries'
+refusals, and a raster of 516 tiles, whose fold takes three strides."""
 import functools
+import types
 
 import numpy as np
 import pytest
@@ -371,3 +372,120 @@ def test_the_c_entries_refuse_with_nothing_written(ctx):
     want = TR.sample_fields(b, block[:3], kappa, 0, pts)
     assert np.array_equal(face, want[0]) and same_bits(T, want[1]) and same_bits(q, want[2]) and same_bits(hot, want[3])
     ts.close()
+
+
+# ---- 9. a raster of several hundred tiles --------------------------------------------------------------------------------------
+
+LARGE_W, LARGE_H = 300, 440                                  # 132 000 pixels: 516 tiles, lanes 0-3 of the fold take three strides
+LARGE_PIXEL = (0.0216, 0.0087)
+LARGE_FIRST_ROW, LARGE_FIRST_COL, LARGE_ROW_ON_COPPER = 46, 25, 255
+
+
+def forms_like(template, value_of):
+    """A field on the meshes of ``template`` (per layer, per mesh a ZeroForm) with the values ``value_of(points (n, 2))``."""
+    out = []
+    for forms in template:
+        out.append([])
+        for zf in forms:
+            new = mesh.ZeroForm(zf.mesh)
+            new.values = np.asarray(value_of(np.asarray(zf.mesh.points, dtype=np.float64).reshape(-1, 2)), dtype=np.float64).copy()
+            out[-1].append(new)
+    return out
+
+
+@pytest.fixture(scope="module")
+def large_raster(ctx):
+    """The ``grid`` board (704 faces on [0, 5.5] x [0, 4]) under four fields -- the seeded random one, zeros, the vertices' y
+    and minus that -- and a raster of 300 x 440 pixels that starts 10 % of the copper's extent outside it at the left and the
+    bottom, ends outside it at the right and inside it at the top.  Pixels of 0.0216 x 0.0087 put the first row on copper at
+    row 46 with its 255 pixels on copper in columns 25 .. 279: pixels 13 825 .. 14 079, all of them in tile 54 (13 824 ..
+    14 079), so the first tile that has copper holds the whole lowest row of it.  Everything is sampled once."""
+    prob, b, fields, _block, model, _kappa = thermal_board("grid")
+    mine = [fields[0], forms_like(fields[0], lambda p: np.zeros(len(p))), forms_like(fields[0], lambda p: p[:, 1]),
+            forms_like(fields[0], lambda p: -p[:, 1])]
+    lo, hi = b.xy.min(axis=0), b.xy.max(axis=0)
+    assert np.array_equal(lo, [0.0, 0.0]) and np.array_equal(hi, [5.5, 4.0])
+    origin = lo - 0.1 * (hi - lo)
+    lay = prob.layers[0]
+    with solver.TemperatureSampler(prob, mine, model=model) as ts:
+        img = ts.raster(lay, tuple(origin), LARGE_PIXEL, LARGE_W, LARGE_H)
+        lean = ts.raster(lay, tuple(origin), LARGE_PIXEL, LARGE_W, LARGE_H, per_field=False)
+        centres = R.raster_points(origin[0], origin[1], LARGE_PIXEL[0], LARGE_PIXEL[1], LARGE_W, LARGE_H)
+        flat = ts.points(lay, centres)
+        away = ts.raster(lay, tuple(hi + 1.0), LARGE_PIXEL, LARGE_W, LARGE_H)
+        faces = global_faces(ts, 0, flat)
+    return types.SimpleNamespace(b=b, block=TR.field_block(mine), img=img, lean=lean, centres=centres, flat=flat, away=away, faces=faces)
+
+
+def test_a_large_raster_lies_where_its_tiles_are_meant_to(large_raster):
+    """What makes the tests below reach the second and third stride of sample_fields_fold_kernel, from the image's own faces:
+    516 tiles; whole leading tiles off the copper; the first pixel on copper where the fixture says, its row's copper inside one
+    tile; copper in each of the tiles 512 .. 515; more than 100 000 pixels on copper."""
+    face = large_raster.img.face.reshape(-1)
+    assert len(face) == 132_000 and -(-len(face) // 256) == 516
+    on_copper = np.flatnonzero(face >= 0)
+    first = LARGE_FIRST_ROW * LARGE_W + LARGE_FIRST_COL
+    assert on_copper[0] == first and first // 256 == 54 and (face[:54 * 256] < 0).all()
+    row = face[LARGE_FIRST_ROW * LARGE_W:(LARGE_FIRST_ROW + 1) * LARGE_W]
+    assert np.array_equal(np.flatnonzero(row >= 0), LARGE_FIRST_COL + np.arange(LARGE_ROW_ON_COPPER))
+    assert (first + LARGE_ROW_ON_COPPER - 1) // 256 == 54
+    assert all((face[t * 256:(t + 1) * 256] >= 0).any() for t in (512, 513, 514, 515))
+    assert (face[-LARGE_W:] >= 0).any() and (face[-LARGE_W:] < 0).any()        # the top row: inside the copper, beyond it at both sides
+    assert len(on_copper) > 100_000
+
+
+def test_the_tops_of_a_large_raster(large_raster):
+    """All five slots against np.nanmax with the lowest pixel on the device's own temperatures.  The field of zeros ties on
+    every pixel on copper, across all three strides, and keeps the first one; the vertices' y peaks in the top row, in a tile
+    of the third stride; minus y in the first tile that has copper; the hottest slot is the sequential rule's; without the
+    per-field arrays the same tops and the same bits of ``hottest``."""
+    img, lean = large_raster.img, large_raster.lean
+    T, hot = img.temperature.reshape(4, -1), img.hottest.reshape(-1)
+    on_copper = np.flatnonzero(img.face.reshape(-1) >= 0)
+    tops = TR.tops_of(img, LARGE_W)
+    print("tops", tops, "tiles", [top[1] // 256 for top in tops])
+    assert len(tops) == 5 and None not in tops
+    assert tops == TR.raster_tops(T, hot)
+    assert (T[1][on_copper] == 0.0).all() and tops[1] == (0.0, int(on_copper[0])) and not np.signbit(tops[1][0])
+    assert tops[2][1] // 256 >= 512 and tops[2][1] // LARGE_W == LARGE_H - 1
+    assert tops[3][1] // 256 == on_copper[0] // 256 and tops[3][1] // LARGE_W == LARGE_FIRST_ROW
+    want_hot, want_field = TR.hottest_of(T)
+    assert same_bits(hot, want_hot) and np.array_equal(img.hottest_field.reshape(-1), want_field)
+    assert tops[4] == TR.raster_tops(T, want_hot)[4] and tops[4][0] == max(top[0] for top in tops[:4])
+    assert lean.temperature is None and same_bits(lean.hottest, img.hottest) and TR.tops_of(lean, LARGE_W) == tops
+    assert np.array_equal(lean.hottest_field, img.hottest_field) and np.array_equal(lean.face, img.face)
+
+
+def test_a_large_raster_is_its_pixel_centres(large_raster):
+    """Every array of the image against the point query at sampling_ref.raster_points: the centres formed from idx / width on
+    the device are the stated expression's up to the last pixel."""
+    img, flat, centres = large_raster.img, large_raster.flat, large_raster.centres
+    assert np.array_equal(img.points.reshape(-1, 2), centres)
+    assert np.array_equal(img.face.reshape(-1), flat.face) and np.array_equal(img.mesh.reshape(-1), flat.mesh)
+    assert same_bits(img.temperature.reshape(4, -1), flat.temperature)
+    assert same_bits(img.hottest.reshape(-1), flat.hottest)
+    assert np.array_equal(img.hottest_field.reshape(-1), flat.hottest_field)
+
+
+def test_a_large_raster_against_the_restatement_on_a_subset(large_raster):
+    """Brute force over all 704 faces at every pixel of the tiles 0, 255, 256, 511, 512 and 515 and at every 61st pixel of the
+    rest (the whole image takes the restatement longer than a test may)."""
+    r = large_raster
+    n = LARGE_W * LARGE_H
+    tile = np.arange(n) // 256
+    pick = np.isin(tile, (0, 255, 256, 511, 512, 515))
+    pick[np.flatnonzero(~pick)[::61]] = True
+    at = np.flatnonzero(pick)
+    face, T, _flux, hot, hot_field = TR.sample_fields(r.b, r.block, None, 0, r.centres[at])
+    print("pixels compared", len(at), "on copper", int((face >= 0).sum()))
+    assert len(at) >= 3000 and (face >= 0).sum() > 1000 and (face < 0).sum() > 300
+    assert np.array_equal(r.faces[at], face) and np.array_equal(r.img.face.reshape(-1)[at] >= 0, face >= 0)
+    assert same_bits(r.img.temperature.reshape(4, -1)[:, at], T)
+    assert same_bits(r.img.hottest.reshape(-1)[at], hot) and np.array_equal(r.img.hottest_field.reshape(-1)[at], hot_field)
+
+
+def test_a_large_raster_off_the_copper_has_no_tops(large_raster):
+    away = large_raster.away
+    assert away.face.shape == (LARGE_H, LARGE_W) and (away.face == -1).all() and (away.mesh == -1).all()
+    assert np.isnan(away.temperature).all() and np.isnan(away.hottest).all() and (away.hottest_field == -1).all()
+    assert away.tops == [None] * 5                           # every one of the 516 tile tops of every slot is the empty top
