@@ -48,6 +48,7 @@ typedef struct padne_ctx padne_ctx;   /* device, stream, workspaces, optional RC
 typedef struct padne_csr padne_csr;   /* device-resident CSR matrix (f64 values, i32 indices)  */
 typedef struct padne_kkt padne_kkt;   /* device-resident plan of solve_system for one assembled system */
 typedef struct padne_refine padne_refine;     /* device-resident result of one refinement round */
+typedef struct padne_polymesh padne_polymesh; /* device-resident meshes of one batch of polygons */
 typedef struct padne_sampler padne_sampler;   /* device-resident meshes, potentials and point-location index of a solved board */
 
 /* ---- library / context ------------------------------------------------------------------- */
@@ -547,6 +548,33 @@ int padne_refine_create(padne_ctx *ctx, int64_t n_vert, const double *xy_host, i
 int padne_refine_fetch(padne_ctx *ctx, const padne_refine *r, double *xy_out, int32_t *tri_out, int32_t *parent_out,
                        int32_t *ends_out);
 int padne_refine_destroy(padne_refine *r);     /* NULL is accepted */
+
+/* ---- grid mesher: first meshes of polygons with holes ------------------------------------------
+ * Stands where the reference's CGAL mesher stands (padne/mesh.py:662-795); not a replacement for it: isosurface stuffing on
+ * a uniform lattice of spacing h whose lines sit at global multiples of h ("Grid mesher"; the rules, expression
+ * by expression, at the top of csrc/polymesh.hip).  One call meshes a batch: polygon p has the rings
+ * poly_ring_ptr[p] .. poly_ring_ptr[p + 1] (the exterior first, then the holes; orientation does not matter under the
+ * even-odd rule), ring r the vertices ring_ptr[r] .. ring_ptr[r + 1] of ring_xy[..][2], without a closing duplicate.
+ * snap in (0, 1/2): a lattice vertex with a cut closer than snap * |edge| moves onto the boundary.
+ * The sizes of the result are known only afterwards, so it stays on the device behind a handle (destroyed before its
+ * context): vertex_count_out[n_poly] and face_count_out[n_poly] size the arrays of padne_polymesh_fetch.  The arrays may
+ * stay on the device: padne_polymesh_arrays hands out their device addresses (xy double[..][2], tri and kind int32, laid out
+ * as padne_polymesh_fetch returns them, valid until the handle is destroyed), which is what an assembly that takes mesh
+ * arrays already on the device (padne_assemble_system_ex) reads.
+ * Limits: a lattice (bounding box plus one cell on every side) of at most 2^24 vertices, a batch of at most 2^27 lattice
+ * vertices, fewer than 2^31 (segment, cell row) pairs; beyond them PADNE_E_INVALID.  PADNE_E_INVALID also for a ring with
+ * fewer than 3 vertices, a polygon without a ring, a coordinate that is not finite, h <= 0, snap outside (0, 1/2) and a
+ * null pointer.  Two calls give the same bits. */
+int padne_polymesh_create(padne_ctx *ctx, int64_t n_poly, const int64_t *poly_ring_ptr, const int64_t *ring_ptr,
+                          const double *ring_xy, double h, double snap, int64_t *vertex_count_out, int64_t *face_count_out,
+                          padne_polymesh **out);
+/* xy_out[sum of the vertex counts][2]; tri_out[sum of the face counts][3], counter-clockwise, with the vertex indices of
+ * their own polygon's mesh; kind_out[sum of the vertex counts]: 0 a lattice vertex, 1 a lattice vertex snapped onto the
+ * boundary, 2 a cut vertex on a lattice edge.  Polygon by polygon: lattice vertices row-major, then cuts by lattice vertex
+ * and family (E, N, NE); faces in cell order, the lower triangle first. */
+int padne_polymesh_fetch(padne_ctx *ctx, const padne_polymesh *pm, double *xy_out, int32_t *tri_out, int32_t *kind_out);
+int padne_polymesh_arrays(const padne_polymesh *pm, const void **xy_dev, const void **tri_dev, const void **kind_dev);
+int padne_polymesh_destroy(padne_polymesh *pm);     /* NULL is accepted */
 
 /* ---- field sampler: the solved fields at points and on rasters --------------------------------
  * No reference counterpart in the solver: the reference's viewer reads out the nearest vertex / nearest face centroid under

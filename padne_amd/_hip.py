@@ -141,6 +141,10 @@ SIGNATURES = {
                                       C.POINTER(_P)]),
     "padne_refine_fetch": (C.c_int, [_P, _P, _PF64, _PI32, _PI32, _PI32]),
     "padne_refine_destroy": (C.c_int, [_P]),
+    "padne_polymesh_create": (C.c_int, [_P, _I64, _PI64, _PI64, _PF64, C.c_double, C.c_double, _PI64, _PI64, C.POINTER(_P)]),
+    "padne_polymesh_fetch": (C.c_int, [_P, _P, _PF64, _PI32, _PI32]),
+    "padne_polymesh_arrays": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
+    "padne_polymesh_destroy": (C.c_int, [_P]),
     "padne_sampler_create": (C.c_int, [_P, _I64, _PF64, _I64, _PI32, C.c_int32, _PI64, _PI64, _PI32, _PF64, C.c_int32, _PF64, _I64,
                                        C.POINTER(_P)]),
     "padne_sampler_destroy": (C.c_int, [_P]),
@@ -2044,6 +2048,29 @@ def refine(ctx: "Context", xy, tri, mesh_vertex_offset, mesh_tri_offset, flags):
         ctx._lib.padne_refine_destroy(h)
     return xy_out, tri_out, parent, ends, n_vert_out, n_tri_out, {
         "edges": int(counts[0]), "marked_by_flags": int(counts[1]), "marked": int(counts[2]), "sweeps": int(counts[3])}
+
+
+def polymesh(ctx: "Context", polygons, h: float, snap: float = 0.25):
+    """One batch of the grid mesher (include/padne_hip.h, ``padne_polymesh_create`` / ``_fetch`` / ``_destroy``).
+    ``polygons``: a sequence of polygons, each a sequence of rings (the exterior first), each ring an (n, 2) array without a
+    closing duplicate.  Returns a list of (xy (n, 2) float64, tri (k, 3) int32, kind (n,) int32), one per polygon."""
+    rings = [_f64(r).reshape(-1, 2) for poly in polygons for r in poly]
+    poly_ring_ptr = _i64(np.concatenate([[0], np.cumsum([len(poly) for poly in polygons])]))
+    ring_ptr = _i64(np.concatenate([[0], np.cumsum([len(r) for r in rings])]))
+    ring_xy = _f64(np.concatenate(rings)) if rings else np.zeros((0, 2))
+    n_poly = len(polygons)
+    n_vert, n_tri = np.zeros(max(n_poly, 1), dtype=np.int64), np.zeros(max(n_poly, 1), dtype=np.int64)
+    h_ = _P()
+    _check(ctx._lib.padne_polymesh_create(ctx._h, n_poly, _ptr(poly_ring_ptr, _PI64), _ptr(ring_ptr, _PI64), _ptr(ring_xy, _PF64),
+                                          float(h), float(snap), _ptr(n_vert, _PI64), _ptr(n_tri, _PI64), C.byref(h_)))
+    try:
+        nv, nt = int(n_vert.sum()), int(n_tri.sum())
+        xy, tri, kind = np.empty((nv, 2), dtype=np.float64), np.empty((nt, 3), dtype=np.int32), np.empty(nv, dtype=np.int32)
+        _check(ctx._lib.padne_polymesh_fetch(ctx._h, h_, _ptr(xy, _PF64), _ptr(tri, _PI32), _ptr(kind, _PI32)))
+    finally:
+        ctx._lib.padne_polymesh_destroy(h_)
+    vo, to = np.concatenate([[0], np.cumsum(n_vert)]), np.concatenate([[0], np.cumsum(n_tri)])
+    return [(xy[vo[p]:vo[p + 1]], tri[to[p]:to[p + 1]], kind[vo[p]:vo[p + 1]]) for p in range(n_poly)]
 
 
 class CsrMatrix:

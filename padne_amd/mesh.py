@@ -331,8 +331,9 @@ class Mesher:
 
     ``Config`` carries the same fields and validation (``mesh.py:668-705``) so a caller can pass
     its configuration through ``solve(prob, mesher_config)`` unchanged; ``poly_to_mesh`` must be
-    supplied by the integrator (padne's own ``Mesher``) or by a structured generator such as
-    :class:`padne_amd.structured.StructuredMesher`.
+    supplied by the integrator (padne's own ``Mesher``), by a structured generator such as
+    :class:`padne_amd.structured.StructuredMesher`, or by :class:`padne_amd.gridmesh.GridMesher`, which meshes polygons
+    with holes on the device (a first mesh on a uniform lattice, not a CGAL replacement).
     """
 
     @dataclass(frozen=True)

@@ -956,7 +956,8 @@ def solve(prob, mesher_config: Optional[mesh.Mesher.Config] = None, *, mesher=No
 
     Meshing and the geometric connectivity pre-pass are out of scope (CGAL / shapely).  ``mesher``
     must offer ``poly_to_mesh(polygon, seed_points) -> Mesh`` (padne's own ``mesh.Mesher`` does, and
-    so does :class:`padne_amd.structured.StructuredMesher` for rectangles and annuli); every
+    so does :class:`padne_amd.structured.StructuredMesher` for rectangles and annuli, and
+    :class:`padne_amd.gridmesh.GridMesher` for polygons with holes, on the device); every
     polygon of every layer is meshed and treated as connected.
     """
     meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
@@ -973,9 +974,12 @@ def mesh_problem(prob, mesher_config=None, mesher=None):
     for layer_i, layer in enumerate(prob.layers):
         seeds = [mesh.Point(c.point.x, c.point.y) for net in prob.networks for c in net.connections
                  if c.layer is layer or c.layer == layer]
-        for geom in layer.geoms:
-            meshes.append(mesher.poly_to_mesh(geom, seeds))
-            mesh_index_to_layer_index.append(layer_i)
+        geoms = list(layer.geoms)
+        if hasattr(mesher, "polys_to_meshes"):          # a mesher that takes a batch: one call per layer
+            meshes.extend(mesher.polys_to_meshes(geoms, seeds))
+        else:
+            meshes.extend(mesher.poly_to_mesh(geom, seeds) for geom in geoms)
+        mesh_index_to_layer_index.extend([layer_i] * len(geoms))
     return meshes, mesh_index_to_layer_index
 
 
