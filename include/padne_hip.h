@@ -568,6 +568,32 @@ int padne_refine_destroy(padne_refine *r);     /* NULL is accepted */
 int padne_polymesh_create(padne_ctx *ctx, int64_t n_poly, const int64_t *poly_ring_ptr, const int64_t *ring_ptr,
                           const double *ring_xy, double h, double snap, int64_t *vertex_count_out, int64_t *face_count_out,
                           padne_polymesh **out);
+/* The same, graded: fine at the boundary and at the seeds, coarse inside ("Graded grid mesher").  Lattice, sign,
+ * cuts and snap as above; then, in integers only:
+ *   plain     a cell (ci, cj) of the lattice's (nx - 1) x (ny - 1) cells is plain when its four corners are inside and not
+ *             snapped; seed k makes the cell (floor(x / h) - i0, floor(y / h) - j0) of every polygon of the batch not plain
+ *             when that polygon's lattice has it (i0, j0: the global index of the lattice's first line); cells outside the
+ *             lattice are not plain;
+ *   distance  d(c) = the Chebyshev distance in cells from c to the nearest cell that is not plain, capped at
+ *             threshold[n_level - 1];
+ *   level     of a cell: the largest l < n_level such that the block of 2^l x 2^l cells that holds it, aligned at global
+ *             cell indices (i0 + ci and j0 + cj rounded down to multiples of 2^l), lies wholly in the lattice and min d over
+ *             it is at least threshold[l].  Such a block is a leaf.  threshold[0] = 0 and
+ *             threshold[l] >= threshold[l - 1] + 2^(l - 1): leaves that share a side then differ by at most one level;
+ *   faces     a level 0 cell emits what padne_polymesh_create emits for it.  Of a leaf of level l >= 1 the lower left cell
+ *             emits for all, from the leaf's corners v00, v10, v11, v01: a side hangs when the cell across it has a lower
+ *             level; no side hangs: (v00, v10, v11), (v00, v11, v01); otherwise, with c the lattice vertex at the centre and
+ *             the ring v00, [mid S], v10, [mid E], v11, [mid N], v01, [mid W] (a midpoint on a hanging side only), the faces
+ *             (c, ring[k], ring[k + 1]) cyclically from v00: 5 to 8, right-isosceles, counter-clockwise;
+ *   numbers   as padne_polymesh_fetch states them; a leaf's faces stand at its lower left cell.
+ * With n_level = 1 the result is padne_polymesh_create's bit for bit.  level_cells_out[n_poly][n_level] (may be NULL): the
+ * cells of every polygon's lattice by level.  The handle is padne_polymesh_create's: _fetch, _arrays, _destroy.
+ * PADNE_E_INVALID, beyond that entry's: n_level outside 1 .. 6, threshold[0] != 0, a threshold below the one before it plus
+ * 2^(l - 1), a seed coordinate that is not finite, 2^24 seeds or more, n_seed > 0 with seed_xy NULL. */
+int padne_polymesh_create_graded(padne_ctx *ctx, int64_t n_poly, const int64_t *poly_ring_ptr, const int64_t *ring_ptr,
+                                 const double *ring_xy, double h, double snap, int64_t n_level, const int32_t *threshold,
+                                 int64_t n_seed, const double *seed_xy, int64_t *vertex_count_out, int64_t *face_count_out,
+                                 int64_t *level_cells_out, padne_polymesh **out);
 /* xy_out[sum of the vertex counts][2]; tri_out[sum of the face counts][3], counter-clockwise, with the vertex indices of
  * their own polygon's mesh; kind_out[sum of the vertex counts]: 0 a lattice vertex, 1 a lattice vertex snapped onto the
  * boundary, 2 a cut vertex on a lattice edge.  Polygon by polygon: lattice vertices row-major, then cuts by lattice vertex

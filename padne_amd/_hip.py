@@ -142,6 +142,8 @@ SIGNATURES = {
     "padne_refine_fetch": (C.c_int, [_P, _P, _PF64, _PI32, _PI32, _PI32]),
     "padne_refine_destroy": (C.c_int, [_P]),
     "padne_polymesh_create": (C.c_int, [_P, _I64, _PI64, _PI64, _PF64, C.c_double, C.c_double, _PI64, _PI64, C.POINTER(_P)]),
+    "padne_polymesh_create_graded": (C.c_int, [_P, _I64, _PI64, _PI64, _PF64, C.c_double, C.c_double, _I64, _PI32, _I64, _PF64, _PI64,
+                                               _PI64, _PI64, C.POINTER(_P)]),
     "padne_polymesh_fetch": (C.c_int, [_P, _P, _PF64, _PI32, _PI32]),
     "padne_polymesh_arrays": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
     "padne_polymesh_destroy": (C.c_int, [_P]),
@@ -2071,6 +2073,39 @@ def polymesh(ctx: "Context", polygons, h: float, snap: float = 0.25):
         ctx._lib.padne_polymesh_destroy(h_)
     vo, to = np.concatenate([[0], np.cumsum(n_vert)]), np.concatenate([[0], np.cumsum(n_tri)])
     return [(xy[vo[p]:vo[p + 1]], tri[to[p]:to[p + 1]], kind[vo[p]:vo[p + 1]]) for p in range(n_poly)]
+
+
+def polymesh_graded(ctx: "Context", polygons, h: float, snap: float = 0.25, thresholds=(0,), seeds=()):
+    """One batch of the graded grid mesher (include/padne_hip.h, ``padne_polymesh_create_graded``).  ``polygons`` as
+    :func:`polymesh`; ``thresholds``: ``t[0] = 0 < t[1] < ...`` in cells, at most 6, ``t[l] >= t[l - 1] + 2^(l - 1)``;
+    ``seeds``: (n, 2) fine spots, applied to every polygon.  Returns a list of (xy, tri, kind, cells_per_level) per polygon,
+    the first three as :func:`polymesh`, the last the lattice's cells by level (int64, one entry per threshold)."""
+    rings = [_f64(r).reshape(-1, 2) for poly in polygons for r in poly]
+    poly_ring_ptr = _i64(np.concatenate([[0], np.cumsum([len(poly) for poly in polygons])]))
+    ring_ptr = _i64(np.concatenate([[0], np.cumsum([len(r) for r in rings])]))
+    ring_xy = _f64(np.concatenate(rings)) if rings else np.zeros((0, 2))
+    t = np.asarray(thresholds).reshape(-1)
+    if len(t) and not (np.issubdtype(t.dtype, np.integer) and t.min() >= -2 ** 31 and t.max() < 2 ** 31):
+        raise ValueError("the thresholds are 32-bit integers")
+    t = _i32(t) if len(t) else np.zeros(1, dtype=np.int32)
+    n_level = len(np.asarray(thresholds).reshape(-1))
+    seed_xy = _f64(seeds).reshape(-1, 2)
+    n_poly = len(polygons)
+    n_vert, n_tri = np.zeros(max(n_poly, 1), dtype=np.int64), np.zeros(max(n_poly, 1), dtype=np.int64)
+    cells = np.zeros((max(n_poly, 1), max(n_level, 1)), dtype=np.int64)
+    h_ = _P()
+    _check(ctx._lib.padne_polymesh_create_graded(ctx._h, n_poly, _ptr(poly_ring_ptr, _PI64), _ptr(ring_ptr, _PI64), _ptr(ring_xy, _PF64),
+                                                 float(h), float(snap), n_level, _ptr(t, _PI32), len(seed_xy),
+                                                 _ptr(seed_xy, _PF64) if len(seed_xy) else None, _ptr(n_vert, _PI64),
+                                                 _ptr(n_tri, _PI64), _ptr(cells, _PI64), C.byref(h_)))
+    try:
+        nv, nt = int(n_vert.sum()), int(n_tri.sum())
+        xy, tri, kind = np.empty((nv, 2), dtype=np.float64), np.empty((nt, 3), dtype=np.int32), np.empty(nv, dtype=np.int32)
+        _check(ctx._lib.padne_polymesh_fetch(ctx._h, h_, _ptr(xy, _PF64), _ptr(tri, _PI32), _ptr(kind, _PI32)))
+    finally:
+        ctx._lib.padne_polymesh_destroy(h_)
+    vo, to = np.concatenate([[0], np.cumsum(n_vert)]), np.concatenate([[0], np.cumsum(n_tri)])
+    return [(xy[vo[p]:vo[p + 1]], tri[to[p]:to[p + 1]], kind[vo[p]:vo[p + 1]], cells[p]) for p in range(n_poly)]
 
 
 class CsrMatrix:

@@ -1,7 +1,8 @@
 // The grid mesher ("Grid mesher"): first meshes of polygons with holes, by isosurface stuffing (Labelle and
 // Shewchuk) in two dimensions with every decision made from the unwarped lattice.  Stands where the reference's CGAL mesher
-// stands (padne/mesh.py:662-795 -- out of scope); no Delaunay refinement, no variable density, no exact corners.  One call
-// meshes a batch of polygons; polygon p = rings (exterior, holes), a ring = n >= 3 vertices without a closing duplicate.
+// stands (padne/mesh.py:662-795 -- out of scope); no Delaunay refinement, no exact corners, variable density only as the
+// quadtree of "Graded" below.  One call meshes a batch of polygons; polygon p = rings (exterior, holes), a ring = n >= 3
+// vertices without a closing duplicate.
 //
 //   lattice   i0 = floor(xmin / h) - 1, nx = ceil(xmax / h) + 1 - i0 + 1 vertices per row, rows likewise: the bounding box and
 //             one cell on every side; x_i = (i0 + i) * h.  Cells split by the diagonal v00-v11 into (v00, v10, v11) and
@@ -32,6 +33,25 @@
 // and fill with integer atomics: the order within a band is not fixed and nothing depends on it (parity, least and greatest
 // t).  No floating-point atomics; compiled with -ffp-contract=off, so the expressions round as written and
 // tests/gridmesh_ref.py reproduces them: two calls give the same bits.
+//
+// Graded (padne_polymesh_create_graded; DESIGN.md, "Graded grid mesher"; tests/gridmesh_graded_ref.py restates it): steps
+// lattice to snap as above, then a balanced quadtree over the cells the boundary does not touch.  Integers only.
+//
+//   plain     cell (ci, cj), ci < nx - 1, cj < ny - 1, is plain when its four corners have state +; a seed (x, y) makes the
+//             cell (floor(x / h) - i0, floor(y / h) - j0) not plain when that cell is in the lattice; cells outside are not plain;
+//   distance  d(c) = the Chebyshev distance in cells to the nearest cell that is not plain, capped at t[n_level - 1]: along
+//             the row dr = the least k with cell ci - k or ci + k not plain, then d = min over k of max(k, dr of row cj +- k);
+//   level     the largest l < n_level such that the block of 2^l x 2^l cells that holds the cell, aligned at global cell
+//             indices ((i0 + ci) and (j0 + cj) rounded down to multiples of 2^l), lies in the lattice and min d over it is at
+//             least t[l]: a leaf.  t[0] = 0 and t[l] >= t[l - 1] + 2^(l - 1), so leaves that share a side differ by one level
+//             at most.  The block minima come level by level from the four blocks below;
+//   faces     a level 0 cell as above.  Of a leaf of level l >= 1 the anchor (lower left) cell alone emits, and counts them as
+//             its lower triangle's: with the corners v00, v10, v11, v01 of the leaf, a side hangs when the cell across it at the
+//             anchor's end (below v00, right of v10, above v01, left of v00) has a lower level; none hangs: (v00, v10, v11),
+//             (v00, v11, v01); otherwise with c the lattice vertex at the centre and the ring v00, [mid S], v10, [mid E], v11,
+//             [mid N], v01, [mid W], a midpoint on a hanging side only: (c, ring[k], ring[k + 1]) cyclically from v00.
+//
+// The arrays of the new stages are indexed like the lattice's vertices (cell = its v00; the last row and column hold no cell).
 //
 // Limits, checked by padne_polymesh_create: a lattice of at most kPolymeshMaxLattice = 2^24 vertices, a batch of at most
 // kPolymeshMaxBatch = 2^27 lattice vertices (its 4 slots per vertex, 2 triangles per vertex and 3 cuts per vertex then fit
@@ -312,16 +332,195 @@ __device__ __forceinline__ void polymesh_faces(const PolyInfo &P, const int ix, 
     }
 }
 
-// fcount[2 v + which] = the faces of the two triangles of the cell whose v00 is v; flag = 1 on every slot they name
-__global__ __launch_bounds__(256) void polymesh_count_kernel(const int n_lat, const int n_poly, const PolyInfo *__restrict__ info, const double h,
-                                                             const signed char *__restrict__ state, const double *__restrict__ pos,
-                                                             const double *__restrict__ T, const double *__restrict__ seg,
-                                                             const int *__restrict__ band_ptr, const int *__restrict__ band_seg,
-                                                             int *__restrict__ fcount, int *flag) {
+constexpr int kPolymeshMaxLevels = 6;
+
+struct PolyLevels {
+    int n;                              // levels, 1 .. kPolymeshMaxLevels
+    int t[kPolymeshMaxLevels];          // t[0] = 0
+};
+
+// plain[v] = 1 when v is the v00 of a cell whose four corners are +
+__global__ __launch_bounds__(256) void polymesh_plain_kernel(const int n_lat, const int n_poly, const PolyInfo *__restrict__ info,
+                                                             const signed char *__restrict__ state, unsigned char *__restrict__ plain) {
     const int gv = blockIdx.x * 256 + threadIdx.x;
     if (gv >= n_lat) return;
     const PolyInfo P = info[polymesh_poly_of_vertex(info, n_poly, gv)];
     const int lv = gv - P.lat_off, ix = lv % P.nx, j = lv / P.nx;
+    bool is = false;
+    if (ix + 1 < P.nx && j + 1 < P.ny) is = state[gv] > 0 && state[gv + 1] > 0 && state[gv + P.nx] > 0 && state[gv + P.nx + 1] > 0;
+    plain[gv] = is ? 1 : 0;
+}
+
+// thread = (polygon, seed): the seed's cell, when the polygon's lattice has it, is not plain (idempotent plain stores)
+__global__ __launch_bounds__(256) void polymesh_seed_kernel(const int n_seed, const int n_poly, const PolyInfo *__restrict__ info,
+                                                            const double *__restrict__ seed, const double h, unsigned char *plain) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)n_seed * n_poly) return;
+    const PolyInfo P = info[i / n_seed];
+    const int k = (int)(i % n_seed);
+    const double fi = floor(seed[2 * k] / h) - (double)P.i0, fj = floor(seed[2 * k + 1] / h) - (double)P.j0;
+    if (fi >= 0.0 && fi < (double)(P.nx - 1) && fj >= 0.0 && fj < (double)(P.ny - 1)) plain[P.lat_off + (int)fj * P.nx + (int)fi] = 0;
+}
+
+// drow[v] = the least k <= cap with cell ci - k or ci + k of the row not plain (outside the row: not plain), else cap
+__global__ __launch_bounds__(256) void polymesh_rowdist_kernel(const int n_lat, const int n_poly, const PolyInfo *__restrict__ info,
+                                                               const unsigned char *__restrict__ plain, const int cap, int *__restrict__ drow) {
+    const int gv = blockIdx.x * 256 + threadIdx.x;
+    if (gv >= n_lat) return;
+    const PolyInfo P = info[polymesh_poly_of_vertex(info, n_poly, gv)];
+    const int lv = gv - P.lat_off, ix = lv % P.nx, j = lv / P.nx;
+    int k = 0;
+    if (ix + 1 < P.nx && j + 1 < P.ny) {
+        const unsigned char *row = plain + (gv - ix);
+        for (; k < cap; ++k) {
+            if (ix - k < 0 || ix + k >= P.nx - 1) break;
+            if (!row[ix - k] || !row[ix + k]) break;
+        }
+    }
+    drow[gv] = k;
+}
+
+// d[v] = min over k of max(k, drow of the rows cj - k and cj + k) (outside the lattice: 0), capped as drow is.  Adjacent
+// threads read adjacent cells of every row they visit
+__global__ __launch_bounds__(256) void polymesh_coldist_kernel(const int n_lat, const int n_poly, const PolyInfo *__restrict__ info,
+                                                               const int *__restrict__ drow, int *__restrict__ d) {
+    const int gv = blockIdx.x * 256 + threadIdx.x;
+    if (gv >= n_lat) return;
+    const PolyInfo P = info[polymesh_poly_of_vertex(info, n_poly, gv)];
+    const int lv = gv - P.lat_off, ix = lv % P.nx, j = lv / P.nx;
+    int best = 0;
+    if (ix + 1 < P.nx && j + 1 < P.ny) {
+        best = drow[gv];
+        for (int k = 1; k < best; ++k) {
+            const int below = j - k >= 0 ? drow[gv - k * P.nx] : 0, above = j + k < P.ny - 1 ? drow[gv + k * P.nx] : 0;
+            best = min(best, max(k, min(below, above)));
+        }
+    }
+    d[gv] = best;
+}
+
+// level l >= 1: bmin[a] at the anchor a of every aligned block of 2^l x 2^l cells inside the lattice = the least d of the
+// block, from the four blocks of level l - 1 (bmin of level 0 is d; in place: a block's anchor is read by that block alone);
+// bit l of ok[a] set when it is at least t[l]
+__global__ __launch_bounds__(256) void polymesh_blockmin_kernel(const int n_lat, const int n_poly, const PolyInfo *__restrict__ info,
+                                                                const int l, const int t_l, int *bmin, unsigned char *ok) {
+    const int gv = blockIdx.x * 256 + threadIdx.x;
+    if (gv >= n_lat) return;
+    const PolyInfo P = info[polymesh_poly_of_vertex(info, n_poly, gv)];
+    const int lv = gv - P.lat_off, ix = lv % P.nx, j = lv / P.nx;
+    const int s = 1 << l, hs = s >> 1;
+    if (((P.i0 + ix) & (s - 1)) != 0 || ((P.j0 + j) & (s - 1)) != 0 || ix + s > P.nx - 1 || j + s > P.ny - 1) return;
+    const int m = min(min(bmin[gv], bmin[gv + hs]), min(bmin[gv + hs * P.nx], bmin[gv + hs * P.nx + hs]));
+    bmin[gv] = m;
+    if (m >= t_l) ok[gv] = (unsigned char)(ok[gv] | (1u << l));
+}
+
+// level[v] of the cell whose v00 is v (0 where there is none); cells[p * kPolymeshMaxLevels + l] += the cells of level l
+__global__ __launch_bounds__(256) void polymesh_level_kernel(const int n_lat, const int n_poly, const PolyInfo *__restrict__ info,
+                                                             const int n_level, const unsigned char *__restrict__ ok,
+                                                             signed char *__restrict__ level, int *cells) {
+    __shared__ int hist[kPolymeshMaxLevels];
+    __shared__ int first_poly, mixed;
+    const int gv = blockIdx.x * 256 + threadIdx.x;
+    const bool live = gv < n_lat;
+    const int p = polymesh_poly_of_vertex(info, n_poly, live ? gv : n_lat - 1);
+    if (threadIdx.x < kPolymeshMaxLevels) hist[threadIdx.x] = 0;
+    if (threadIdx.x == 0) {
+        first_poly = p;
+        mixed = 0;
+    }
+    __syncthreads();
+    if (p != first_poly) mixed = 1;
+    __syncthreads();
+    const PolyInfo P = info[p];
+    const int lv = (live ? gv : n_lat - 1) - P.lat_off, ix = lv % P.nx, j = lv / P.nx;
+    const bool cell = live && ix + 1 < P.nx && j + 1 < P.ny;
+    int lev = 0;
+    if (cell)
+        for (int l = n_level - 1; l >= 1; --l) {
+            const int s = 1 << l, ai = ix - ((P.i0 + ix) & (s - 1)), aj = j - ((P.j0 + j) & (s - 1));
+            if (ai < 0 || aj < 0 || ai + s > P.nx - 1 || aj + s > P.ny - 1) continue;
+            if ((ok[P.lat_off + aj * P.nx + ai] >> l) & 1) {
+                lev = l;
+                break;
+            }
+        }
+    if (live) level[gv] = (signed char)lev;
+    if (cell) {
+        if (mixed) atomicAdd(cells + (long long)p * kPolymeshMaxLevels + lev, 1); else atomicAdd(hist + lev, 1);
+    }
+    __syncthreads();
+    if (!mixed && threadIdx.x < n_level && hist[threadIdx.x] > 0)
+        atomicAdd(cells + (long long)first_poly * kPolymeshMaxLevels + threadIdx.x, hist[threadIdx.x]);
+}
+
+// the faces of the leaf of level l >= 1 whose anchor cell's v00 is (ix, j), handed one by one to put(a, b, c) as slots:
+// the rule at the top of the file.  level: the polygon's own (level + lat_off)
+template <typename Put>
+__device__ __forceinline__ void polymesh_leaf(const PolyInfo &P, const int ix, const int j, const int l,
+                                              const signed char *__restrict__ level, Put put) {
+    const int s = 1 << l, hs = s >> 1, nx = P.nx;
+    auto level_at = [&](int ci, int cj) {
+        return ci < 0 || cj < 0 || ci >= nx - 1 || cj >= P.ny - 1 ? 0 : (int)level[cj * nx + ci];
+    };
+    const bool hang_s = level_at(ix, j - 1) < l, hang_e = level_at(ix + s, j) < l, hang_n = level_at(ix, j + s) < l,
+               hang_w = level_at(ix - 1, j) < l;
+    const int v00 = j * nx + ix, v10 = v00 + s, v01 = v00 + s * nx, v11 = v01 + s;
+    if (!(hang_s || hang_e || hang_n || hang_w)) {
+        put(v00, v10, v11);
+        put(v00, v11, v01);
+        return;
+    }
+    const int c = v00 + hs * nx + hs;
+    int prev = v00;
+    auto step = [&](int v) {
+        put(c, prev, v);
+        prev = v;
+    };
+    if (hang_s) step(v00 + hs);
+    step(v10);
+    if (hang_e) step(v10 + hs * nx);
+    step(v11);
+    if (hang_n) step(v01 + hs);
+    step(v01);
+    if (hang_w) step(v00 + hs * nx);
+    step(v00);
+}
+
+__device__ __forceinline__ bool polymesh_is_anchor(const PolyInfo &P, const int ix, const int j, const int l) {
+    const int s = 1 << l;
+    return ((P.i0 + ix) & (s - 1)) == 0 && ((P.j0 + j) & (s - 1)) == 0;
+}
+
+// fcount[2 v + which] = the faces of the two triangles of the cell whose v00 is v; flag = 1 on every slot they name.
+// GRADED: a cell of a leaf of level >= 1 counts the leaf's faces as its lower triangle's when it is the anchor, else none
+template <bool GRADED>
+__global__ __launch_bounds__(256) void polymesh_count_kernel(const int n_lat, const int n_poly, const PolyInfo *__restrict__ info, const double h,
+                                                             const signed char *__restrict__ state, const double *__restrict__ pos,
+                                                             const double *__restrict__ T, const double *__restrict__ seg,
+                                                             const int *__restrict__ band_ptr, const int *__restrict__ band_seg,
+                                                             const signed char *__restrict__ level, int *__restrict__ fcount, int *flag) {
+    const int gv = blockIdx.x * 256 + threadIdx.x;
+    if (gv >= n_lat) return;
+    const PolyInfo P = info[polymesh_poly_of_vertex(info, n_poly, gv)];
+    const int lv = gv - P.lat_off, ix = lv % P.nx, j = lv / P.nx;
+    if (GRADED) {
+        const int l = level[gv];
+        if (l > 0) {
+            int n = 0;
+            int *fl = flag + 4 * (long long)P.lat_off;
+            if (polymesh_is_anchor(P, ix, j, l))
+                polymesh_leaf(P, ix, j, l, level + P.lat_off, [&](int a, int b, int c) {
+                    fl[a] = 1;
+                    fl[b] = 1;
+                    fl[c] = 1;
+                    ++n;
+                });
+            fcount[2 * (long long)gv] = n;
+            fcount[2 * (long long)gv + 1] = 0;
+            return;
+        }
+    }
     for (int which = 0; which < 2; ++which) {
         PolyFaces f;
         f.n = 0;
@@ -369,11 +568,13 @@ __global__ __launch_bounds__(256) void polymesh_vertex_kernel(const int n_lat, c
 }
 
 // the faces of every cell at their offsets, with the vertex numbers of their polygon
+template <bool GRADED>
 __global__ __launch_bounds__(256) void polymesh_face_kernel(const int n_lat, const int n_poly, const PolyInfo *__restrict__ info, const double h,
                                                             const signed char *__restrict__ state, const double *__restrict__ pos,
                                                             const double *__restrict__ T, const double *__restrict__ seg,
                                                             const int *__restrict__ band_ptr, const int *__restrict__ band_seg,
-                                                            const int *__restrict__ vnum, const int *__restrict__ foff, int *__restrict__ tri) {
+                                                            const signed char *__restrict__ level, const int *__restrict__ vnum,
+                                                            const int *__restrict__ foff, int *__restrict__ tri) {
     const int gv = blockIdx.x * 256 + threadIdx.x;
     if (gv >= n_lat) return;
     const PolyInfo P = info[polymesh_poly_of_vertex(info, n_poly, gv)];
@@ -381,6 +582,20 @@ __global__ __launch_bounds__(256) void polymesh_face_kernel(const int n_lat, con
     if (ix + 1 >= P.nx || j + 1 >= P.ny) return;
     const int *num = vnum + 4 * (long long)P.lat_off;
     const int base = num[0];
+    if (GRADED) {
+        const int l = level[gv];
+        if (l > 0) {
+            if (!polymesh_is_anchor(P, ix, j, l)) return;
+            int *out = tri + 3 * (long long)foff[2 * (long long)gv];
+            polymesh_leaf(P, ix, j, l, level + P.lat_off, [&](int a, int b, int c) {
+                out[0] = num[a] - base;
+                out[1] = num[b] - base;
+                out[2] = num[c] - base;
+                out += 3;
+            });
+            return;
+        }
+    }
     for (int which = 0; which < 2; ++which) {
         PolyFaces f;
         polymesh_faces(P, ix, j, which, h, state, pos, T, seg, band_ptr, band_seg, f);
@@ -414,11 +629,10 @@ template <typename T> static int polymesh_alloc(padne_ctx *ctx, T **out, size_t 
     return *out ? PADNE_OK : PADNE_E_NOMEM;
 }
 
-extern "C" int padne_polymesh_create(padne_ctx *ctx, int64_t n_poly, const int64_t *poly_ring_ptr, const int64_t *ring_ptr,
-                                     const double *ring_xy, double h, double snap, int64_t *vertex_count_out,
-                                     int64_t *face_count_out, padne_polymesh **out) {
-    PADNE_REQUIRE(ctx && out, "null argument");
-    *out = nullptr;
+// both entries: lv.n == 1 is the uniform mesh, and runs what it ran before there were levels
+static int polymesh_create(padne_ctx *ctx, int64_t n_poly, const int64_t *poly_ring_ptr, const int64_t *ring_ptr, const double *ring_xy,
+                           double h, double snap, const PolyLevels &lv, int64_t n_seed, const double *seed_xy,
+                           int64_t *vertex_count_out, int64_t *face_count_out, int64_t *level_cells_out, padne_polymesh **out) {
     PADNE_REQUIRE(poly_ring_ptr && ring_ptr && ring_xy && vertex_count_out && face_count_out, "null argument");
     PADNE_REQUIRE(n_poly >= 1 && n_poly < (1LL << 24), "a batch holds at least one polygon");
     PADNE_REQUIRE(h > 0.0 && std::isfinite(h), "the spacing must be positive");
@@ -485,7 +699,8 @@ extern "C" int padne_polymesh_create(padne_ctx *ctx, int64_t n_poly, const int64
     double *d_seg = nullptr, *d_T = nullptr, *d_pos = nullptr;
     int *d_seg_poly = nullptr, *d_count = nullptr, *d_band_ptr = nullptr, *d_band_seg = nullptr, *d_fcount = nullptr, *d_foff = nullptr,
         *d_flag = nullptr, *d_vnum = nullptr, *d_vbase = nullptr, *d_fbase = nullptr;
-    signed char *d_sign = nullptr, *d_state = nullptr;
+    signed char *d_sign = nullptr, *d_state = nullptr, *d_level = nullptr;
+    const bool graded = lv.n > 1;
     PADNE_TRY(sc.alloc(&d_info, (size_t)n_poly + 1));
     PADNE_TRY(sc.alloc(&d_seg, 4 * (size_t)n_seg));
     PADNE_TRY(sc.alloc(&d_seg_poly, (size_t)n_seg));
@@ -530,11 +745,58 @@ extern "C" int padne_polymesh_create(padne_ctx *ctx, int64_t n_poly, const int64
                        (const signed char *)d_sign, (const double *)d_T, d_state, d_pos);
     PADNE_HIP_CHECK(hipGetLastError());
 
+    // ---- graded: plain cells, seeds, the capped distance, the block minima level by level, the level of every cell
+    std::vector<int> cells;
+    if (graded) {
+        unsigned char *d_plain = nullptr, *d_ok = nullptr;
+        int *d_drow = nullptr, *d_dist = nullptr, *d_cells = nullptr;
+        double *d_seed = nullptr;
+        PADNE_TRY(sc.alloc(&d_plain, (size_t)nl));
+        PADNE_TRY(sc.alloc(&d_ok, (size_t)nl));
+        PADNE_TRY(sc.alloc(&d_drow, (size_t)nl));
+        PADNE_TRY(sc.alloc(&d_dist, (size_t)nl));
+        PADNE_TRY(sc.alloc(&d_level, (size_t)nl));
+        PADNE_TRY(sc.alloc(&d_cells, (size_t)n_poly * kPolymeshMaxLevels));
+        hipLaunchKernelGGL(polymesh_plain_kernel, dim3(nblk(nl)), dim3(256), 0, s, nl, np, (const PolyInfo *)d_info,
+                           (const signed char *)d_state, d_plain);
+        PADNE_HIP_CHECK(hipGetLastError());
+        if (n_seed > 0) {
+            PADNE_TRY(sc.alloc(&d_seed, 2 * (size_t)n_seed));
+            PADNE_HIP_CHECK(hipMemcpyAsync(d_seed, seed_xy, sizeof(double) * 2 * (size_t)n_seed, hipMemcpyHostToDevice, s));
+            hipLaunchKernelGGL(polymesh_seed_kernel, dim3(nblk((long long)n_seed * n_poly)), dim3(256), 0, s, (int)n_seed, np,
+                               (const PolyInfo *)d_info, (const double *)d_seed, h, d_plain);
+            PADNE_HIP_CHECK(hipGetLastError());
+        }
+        hipLaunchKernelGGL(polymesh_rowdist_kernel, dim3(nblk(nl)), dim3(256), 0, s, nl, np, (const PolyInfo *)d_info,
+                           (const unsigned char *)d_plain, lv.t[lv.n - 1], d_drow);
+        PADNE_HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(polymesh_coldist_kernel, dim3(nblk(nl)), dim3(256), 0, s, nl, np, (const PolyInfo *)d_info, (const int *)d_drow,
+                           d_dist);
+        PADNE_HIP_CHECK(hipGetLastError());
+        PADNE_HIP_CHECK(hipMemsetAsync(d_ok, 0, (size_t)nl, s));
+        PADNE_HIP_CHECK(hipMemsetAsync(d_cells, 0, sizeof(int) * (size_t)n_poly * kPolymeshMaxLevels, s));
+        for (int l = 1; l < lv.n; ++l) {
+            hipLaunchKernelGGL(polymesh_blockmin_kernel, dim3(nblk(nl)), dim3(256), 0, s, nl, np, (const PolyInfo *)d_info, l, lv.t[l], d_dist,
+                               d_ok);
+            PADNE_HIP_CHECK(hipGetLastError());
+        }
+        hipLaunchKernelGGL(polymesh_level_kernel, dim3(nblk(nl)), dim3(256), 0, s, nl, np, (const PolyInfo *)d_info, lv.n,
+                           (const unsigned char *)d_ok, d_level, d_cells);
+        PADNE_HIP_CHECK(hipGetLastError());
+        cells.resize((size_t)n_poly * kPolymeshMaxLevels);
+        PADNE_HIP_CHECK(hipMemcpyAsync(cells.data(), d_cells, sizeof(int) * cells.size(), hipMemcpyDeviceToHost, s));
+    }
+
     // ---- counts and flags, the two scans
     PADNE_HIP_CHECK(hipMemsetAsync(d_flag, 0, sizeof(int) * 4 * (size_t)nl, s));
-    hipLaunchKernelGGL(polymesh_count_kernel, dim3(nblk(nl)), dim3(256), 0, s, nl, np, (const PolyInfo *)d_info, h, (const signed char *)d_state,
-                       (const double *)d_pos, (const double *)d_T, (const double *)d_seg, (const int *)d_band_ptr,
-                       (const int *)d_band_seg, d_fcount, d_flag);
+    if (graded)
+        hipLaunchKernelGGL(polymesh_count_kernel<true>, dim3(nblk(nl)), dim3(256), 0, s, nl, np, (const PolyInfo *)d_info, h,
+                           (const signed char *)d_state, (const double *)d_pos, (const double *)d_T, (const double *)d_seg,
+                           (const int *)d_band_ptr, (const int *)d_band_seg, (const signed char *)d_level, d_fcount, d_flag);
+    else
+        hipLaunchKernelGGL(polymesh_count_kernel<false>, dim3(nblk(nl)), dim3(256), 0, s, nl, np, (const PolyInfo *)d_info, h,
+                           (const signed char *)d_state, (const double *)d_pos, (const double *)d_T, (const double *)d_seg,
+                           (const int *)d_band_ptr, (const int *)d_band_seg, (const signed char *)nullptr, d_fcount, d_flag);
     PADNE_HIP_CHECK(hipGetLastError());
     PADNE_TRY(exclusive_scan_i32(ctx, d_flag, d_vnum, 4 * (int64_t)nl, &n_vert));
     PADNE_TRY(exclusive_scan_i32(ctx, d_fcount, d_foff, 2 * (int64_t)nl, &n_tri));
@@ -555,18 +817,62 @@ extern "C" int padne_polymesh_create(padne_ctx *ctx, int64_t n_poly, const int64
                        (const signed char *)d_state, (const double *)d_pos, (const double *)d_T, (const int *)d_flag, (const int *)d_vnum,
                        pm->xy, pm->kind);
     PADNE_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(polymesh_face_kernel, dim3(nblk(nl)), dim3(256), 0, s, nl, np, (const PolyInfo *)d_info, h, (const signed char *)d_state,
-                       (const double *)d_pos, (const double *)d_T, (const double *)d_seg, (const int *)d_band_ptr,
-                       (const int *)d_band_seg, (const int *)d_vnum, (const int *)d_foff, pm->tri);
+    if (graded)
+        hipLaunchKernelGGL(polymesh_face_kernel<true>, dim3(nblk(nl)), dim3(256), 0, s, nl, np, (const PolyInfo *)d_info, h,
+                           (const signed char *)d_state, (const double *)d_pos, (const double *)d_T, (const double *)d_seg,
+                           (const int *)d_band_ptr, (const int *)d_band_seg, (const signed char *)d_level, (const int *)d_vnum,
+                           (const int *)d_foff, pm->tri);
+    else
+        hipLaunchKernelGGL(polymesh_face_kernel<false>, dim3(nblk(nl)), dim3(256), 0, s, nl, np, (const PolyInfo *)d_info, h,
+                           (const signed char *)d_state, (const double *)d_pos, (const double *)d_T, (const double *)d_seg,
+                           (const int *)d_band_ptr, (const int *)d_band_seg, (const signed char *)nullptr, (const int *)d_vnum,
+                           (const int *)d_foff, pm->tri);
     PADNE_HIP_CHECK(hipGetLastError());
     PADNE_HIP_CHECK(hipStreamSynchronize(s));
     for (int64_t p = 0; p < n_poly; ++p) {
         vertex_count_out[p] = vbase[(size_t)p + 1] - vbase[(size_t)p];
         face_count_out[p] = fbase[(size_t)p + 1] - fbase[(size_t)p];
+        if (level_cells_out == nullptr) continue;
+        const PolyInfo &P = info[(size_t)p];
+        for (int l = 0; l < lv.n; ++l)
+            level_cells_out[p * lv.n + l] = graded ? cells[(size_t)p * kPolymeshMaxLevels + l] : (int64_t)(P.nx - 1) * (P.ny - 1);
     }
     guard.pm = nullptr;
     *out = pm;
     return PADNE_OK;
+}
+
+extern "C" int padne_polymesh_create(padne_ctx *ctx, int64_t n_poly, const int64_t *poly_ring_ptr, const int64_t *ring_ptr,
+                                     const double *ring_xy, double h, double snap, int64_t *vertex_count_out,
+                                     int64_t *face_count_out, padne_polymesh **out) {
+    PADNE_REQUIRE(ctx && out, "null argument");
+    *out = nullptr;
+    return polymesh_create(ctx, n_poly, poly_ring_ptr, ring_ptr, ring_xy, h, snap, PolyLevels{1, {0}}, 0, nullptr, vertex_count_out,
+                           face_count_out, nullptr, out);
+}
+
+extern "C" int padne_polymesh_create_graded(padne_ctx *ctx, int64_t n_poly, const int64_t *poly_ring_ptr, const int64_t *ring_ptr,
+                                            const double *ring_xy, double h, double snap, int64_t n_level,
+                                            const int32_t *threshold, int64_t n_seed, const double *seed_xy,
+                                            int64_t *vertex_count_out, int64_t *face_count_out, int64_t *level_cells_out,
+                                            padne_polymesh **out) {
+    PADNE_REQUIRE(ctx && out, "null argument");
+    *out = nullptr;
+    PADNE_REQUIRE(n_level >= 1 && n_level <= kPolymeshMaxLevels, "1 to 6 levels");
+    PADNE_REQUIRE(threshold != nullptr, "null argument");
+    PADNE_REQUIRE(threshold[0] == 0, "the threshold of level 0 is 0");
+    PolyLevels lv{(int)n_level, {0}};
+    for (int l = 1; l < lv.n; ++l) {
+        PADNE_REQUIRE((long long)threshold[l] >= (long long)threshold[l - 1] + (1LL << (l - 1)),
+                      "a threshold must be at least the one below it plus 2^(l - 1): the quadtree would not be balanced");
+        lv.t[l] = threshold[l];
+    }
+    PADNE_REQUIRE(n_seed >= 0 && n_seed < (1LL << 24), "the number of seeds");
+    PADNE_REQUIRE(n_seed == 0 || seed_xy != nullptr, "null argument");
+    for (int64_t k = 0; k < 2 * n_seed; ++k) PADNE_REQUIRE(std::isfinite(seed_xy[k]), "a seed coordinate is not finite");
+    PADNE_REQUIRE(n_poly < 1 || n_seed * n_poly < 0x7fffffffLL, "too many (seed, polygon) pairs for 32-bit indices");
+    return polymesh_create(ctx, n_poly, poly_ring_ptr, ring_ptr, ring_xy, h, snap, lv, n_seed, seed_xy, vertex_count_out,
+                           face_count_out, level_cells_out, out);
 }
 
 extern "C" int padne_polymesh_fetch(padne_ctx *ctx, const padne_polymesh *pm, double *xy_out, int32_t *tri_out, int32_t *kind_out) {

@@ -10,7 +10,9 @@ boundary crosses, lattice vertices close to a cut snapped onto the boundary, the
   point far from every vertex; both raise :class:`padne_amd.mesh.MeshingException`;
 * faces along the boundary may be obtuse, so the stiffness matrix has positive off-diagonal entries there (the ``|cot|``
   caveat of the README applies);
-* the spacing is uniform: ``minimum_angle`` and the variable-density fields of ``Mesher.Config`` are accepted and ignored;
+* the spacing is uniform unless ``graded=True``: then the interior is coarsened by a balanced quadtree over the lattice's
+  cells, by the variable-density fields of ``Mesher.Config`` (``padne_polymesh_create_graded``; DESIGN.md, "Graded grid
+  mesher").  ``minimum_angle`` and ``distance_map_quantization`` are accepted and ignored either way;
 * one GPU.
 
 ``refine_meshes`` and the adaptive loops of the solver improve such a first mesh where the error estimate asks.
@@ -114,25 +116,65 @@ def _device_engine(polygons, h, snap):
     return _hip.polymesh(solver.get_context(), polygons, h, snap)
 
 
+def _device_engine_graded(polygons, h, snap, thresholds, seeds):
+    from . import _hip, solver
+    return _hip.polymesh_graded(solver.get_context(), polygons, h, snap, thresholds, seeds)
+
+
+MAX_LEVEL = 5           # padne_polymesh_create_graded takes at most 6 levels, 0 to 5
+
+
+def graded_thresholds(h: float, factor: float, min_distance: float, max_distance: float, max_level: int = MAX_LEVEL) -> list:
+    """The thresholds ``t`` of ``padne_polymesh_create_graded``, in cells of spacing ``h``.  The size is to grow linearly from
+    ``maximum_size`` at ``min_distance`` from the boundary to ``factor * maximum_size`` at ``max_distance``; a leaf of level l
+    has ``2^l`` times the size, so level ``l >= 1`` exists while ``2^l <= factor`` and ``l <= max_level`` and needs the
+    distance ``dist_l = min_distance + (2^l - 1) / (factor - 1) * (max_distance - min_distance)``.  A cell at Chebyshev
+    distance d from a cell the boundary touches is at least ``(d - 1) h`` from the boundary, hence
+    ``t[l] = max(t[l - 1] + 2^(l - 1), 1 + ceil(dist_l / h))``; the first term keeps the quadtree balanced.  ``factor < 2``
+    gives ``[0]``: the uniform mesh."""
+    t = [0]
+    level = 1
+    while 2 ** level <= factor and level <= max_level:
+        dist = min_distance + (2 ** level - 1) / (factor - 1) * (max_distance - min_distance)
+        cells = 1 + math.ceil(dist / h)
+        if not cells < 2 ** 30:
+            raise ValueError(f"level {level} would start {dist / h:g} cells from the boundary: the spacing is too small for "
+                             "these variable-density distances")
+        t.append(max(t[-1] + 2 ** (level - 1), cells))
+        level += 1
+    return t
+
+
 class GridMesher:
     """``poly_to_mesh(poly, seed_points)`` for ``solver.solve(prob, mesher=GridMesher(config))``, and
     ``polys_to_meshes(polys, seed_points)``, which meshes a batch in one device call.
 
     ``config``: a ``mesh.Mesher.Config``; only ``maximum_size`` is read, the spacing is ``maximum_size / sqrt(2)`` so that the
     longest lattice edge is ``maximum_size`` (an edge next to the boundary may reach ``(1 + 2 snap) maximum_size``).
-    ``minimum_angle`` and the variable-density fields are accepted and ignored.  ``spacing`` overrides the lattice spacing;
+    ``minimum_angle`` and the variable-density fields are accepted and ignored (the latter unless ``graded``).  ``spacing``
+    overrides the lattice spacing;
     seeds are then held to ``sqrt(2) spacing``.  ``snap`` in (0, 1/2).  ``area_tolerance``: when given, mesh area over polygon
     area must lie within ``1 +- area_tolerance`` (no default).  ``crumbs``: ``"raise"`` when the mesh has more than one
     connected component, ``"drop"`` to keep the component with the most faces (the lowest label on a tie).
     ``engine``: what computes the lattice work, ``(polygons, h, snap) -> [(xy, tri, kind)]``; the device by default -- the
     tests hand in their host restatement of the kernels.
 
+    ``graded=True`` (off by default) coarsens the interior: a balanced quadtree over the cells the boundary does not touch,
+    leaves of ``2^l x 2^l`` cells, right-isosceles faces.  ``variable_size_maximum_factor``, ``variable_density_min_distance``
+    and ``variable_density_max_distance`` of the config give the thresholds (:func:`graded_thresholds`); levels are powers of
+    two, so the reference's default factor 3 gives one level, and ``max_level`` (0 to 5) caps them.  Distances are counted in
+    cells (Chebyshev), not Euclidean.  Seeds are fine spots: the cell of a seed stays at level 0 and the levels grow away from
+    it as from the boundary.  ``distance_map_quantization`` and ``minimum_angle`` stay ignored.  The engine is then called as
+    ``(polygons, h, snap, thresholds, seeds) -> [(xy, tri, kind, cells_per_level)]``.
+
     ``last_report``: per polygon of the last call a dict with ``lattice`` (nx, ny), ``vertices`` {"lattice", "snapped",
-    "cut"}, ``faces``, ``area_ratio`` and ``components`` (before any crumbs were dropped).
+    "cut"}, ``faces``, ``area_ratio`` and ``components`` (before any crumbs were dropped); with ``graded`` also
+    ``thresholds`` and ``cells_per_level``, the lattice's cells by level.
     """
 
     def __init__(self, config: Optional[mesh.Mesher.Config] = None, *, spacing: Optional[float] = None, snap: float = 0.25,
-                 area_tolerance: Optional[float] = None, crumbs: str = "raise", engine=None):
+                 area_tolerance: Optional[float] = None, crumbs: str = "raise", engine=None, graded: bool = False,
+                 max_level: int = MAX_LEVEL):
         self.config = config if config is not None else mesh.Mesher.Config()
         if spacing is not None and not (spacing > 0 and math.isfinite(spacing)):
             raise ValueError(f"spacing must be positive, got {spacing}")
@@ -143,7 +185,10 @@ class GridMesher:
         if area_tolerance is not None and not area_tolerance > 0:
             raise ValueError(f"area_tolerance must be positive, got {area_tolerance}")
         self.spacing, self.snap, self.area_tolerance, self.crumbs = spacing, float(snap), area_tolerance, crumbs
-        self.engine = engine if engine is not None else _device_engine
+        if not (isinstance(max_level, (int, np.integer)) and not isinstance(max_level, bool) and 0 <= max_level <= MAX_LEVEL):
+            raise ValueError(f"max_level must be an integer from 0 to {MAX_LEVEL}, got {max_level!r}")
+        self.graded, self.max_level = bool(graded), int(max_level)
+        self.engine = engine if engine is not None else (_device_engine_graded if self.graded else _device_engine)
         self.last_report: list = []
 
     def _sizes(self):
@@ -153,6 +198,15 @@ class GridMesher:
         if self.config.maximum_size == 0:
             raise mesh.MeshingException("GridMesher needs a maximum_size above 0, or a spacing: the lattice is uniform")
         return self.config.maximum_size / math.sqrt(2.0), float(self.config.maximum_size)
+
+    def thresholds(self) -> list:
+        """The thresholds of the levels at this mesher's spacing (``[0]`` when it is not graded)."""
+        if not self.graded:
+            return [0]
+        h, _reach = self._sizes()
+        c = self.config
+        return graded_thresholds(h, c.variable_size_maximum_factor, c.variable_density_min_distance,
+                                 c.variable_density_max_distance, self.max_level)
 
     def poly_to_mesh(self, poly, seed_points: Iterable = ()) -> mesh.Mesh:
         return self.polys_to_meshes([poly], seed_points)[0]
@@ -165,17 +219,25 @@ class GridMesher:
             return []
         seeds = np.array([(p.x, p.y) if hasattr(p, "x") else (p[0], p[1]) for p in seed_points], dtype=np.float64).reshape(-1, 2)
         meshes = []
+        if self.graded:
+            if not np.isfinite(seeds).all():
+                raise ValueError("a seed point is not finite")
+            t = self.thresholds()
+            for k, (rings, (xy, tri, kind, cells)) in enumerate(zip(polygons, self.engine(polygons, h, self.snap, t, seeds))):
+                meshes.append(self._checked(k, rings, np.asarray(xy), np.asarray(tri), np.asarray(kind), seeds, h, reach,
+                                            {"thresholds": list(t), "cells_per_level": [int(c) for c in cells]}))
+            return meshes
         for k, (rings, (xy, tri, kind)) in enumerate(zip(polygons, self.engine(polygons, h, self.snap))):
             meshes.append(self._checked(k, rings, np.asarray(xy), np.asarray(tri), np.asarray(kind), seeds, h, reach))
         return meshes
 
-    def _checked(self, k, rings, xy, tri, kind, seeds, h, reach) -> mesh.Mesh:
+    def _checked(self, k, rings, xy, tri, kind, seeds, h, reach, extra=None) -> mesh.Mesh:
         pts = np.concatenate(rings)
         nx = int(math.ceil(pts[:, 0].max() / h)) + 1 - (int(math.floor(pts[:, 0].min() / h)) - 1) + 1
         ny = int(math.ceil(pts[:, 1].max() / h)) + 1 - (int(math.floor(pts[:, 1].min() / h)) - 1) + 1
         report = {"lattice": (nx, ny), "vertices": {"lattice": int((kind == 0).sum()), "snapped": int((kind == 1).sum()),
                                                     "cut": int((kind == 2).sum())},
-                  "faces": len(tri), "area_ratio": 0.0, "components": 0}
+                  "faces": len(tri), "area_ratio": 0.0, "components": 0, **(extra or {})}
         self.last_report.append(report)
         if len(tri) == 0:
             raise mesh.MeshingException(f"polygon {k}: no lattice vertex of spacing {h:g} lies inside it, the mesh has no face; {LOWER}")
