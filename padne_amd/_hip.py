@@ -147,6 +147,9 @@ SIGNATURES = {
     "padne_polymesh_fetch": (C.c_int, [_P, _P, _PF64, _PI32, _PI32]),
     "padne_polymesh_arrays": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P)]),
     "padne_polymesh_destroy": (C.c_int, [_P]),
+    "padne_polygons_locate": (C.c_int, [_P, _I64, _PI64, _PI64, _PF64, _PI32, _I64, _PF64, _PI32, _PI64, C.POINTER(_P)]),
+    "padne_polygons_locate_fetch": (C.c_int, [_P, _P, _PI32, _PI32, _PI32]),
+    "padne_polygons_locate_destroy": (C.c_int, [_P]),
     "padne_sampler_create": (C.c_int, [_P, _I64, _PF64, _I64, _PI32, C.c_int32, _PI64, _PI64, _PI32, _PF64, C.c_int32, _PF64, _I64,
                                        C.POINTER(_P)]),
     "padne_sampler_destroy": (C.c_int, [_P]),
@@ -2106,6 +2109,42 @@ def polymesh_graded(ctx: "Context", polygons, h: float, snap: float = 0.25, thre
         ctx._lib.padne_polymesh_destroy(h_)
     vo, to = np.concatenate([[0], np.cumsum(n_vert)]), np.concatenate([[0], np.cumsum(n_tri)])
     return [(xy[vo[p]:vo[p + 1]], tri[to[p]:to[p + 1]], kind[vo[p]:vo[p + 1]], cells[p]) for p in range(n_poly)]
+
+
+def _groups(groups, n: int, what: str) -> np.ndarray:
+    g = np.asarray(groups).reshape(-1)
+    if len(g) != n:
+        raise ValueError(f"one group per {what}: {len(g)} groups for {n}")
+    if len(g) and not (np.issubdtype(g.dtype, np.integer) and g.min() >= -2 ** 31 and g.max() < 2 ** 31):
+        raise ValueError("the groups are 32-bit integers")
+    return _i32(g)
+
+
+def locate_polygons(ctx: "Context", polygons, groups, points, point_groups):
+    """The connectivity pre-pass's kernel (include/padne_hip.h, ``padne_polygons_locate`` / ``_fetch`` / ``_destroy``): which
+    polygons does every point touch.  ``polygons`` as :func:`polymesh`; ``groups``: the group (layer) of every polygon,
+    ascending; ``points``: (n, 2); ``point_groups``: the group of every point, which meets the polygons of its group only.
+    Returns (hit_ptr (n + 1,) int64, hit_poly int32, hit_kind int32): the hits of point q are
+    ``hit_ptr[q] .. hit_ptr[q + 1]``, in ascending polygon number; kind 1 inside, 2 on the boundary."""
+    rings = [_f64(r).reshape(-1, 2) for poly in polygons for r in poly]
+    poly_ring_ptr = _i64(np.concatenate([[0], np.cumsum([len(poly) for poly in polygons])]))
+    ring_ptr = _i64(np.concatenate([[0], np.cumsum([len(r) for r in rings])]))
+    ring_xy = _f64(np.concatenate(rings)) if rings else np.zeros((0, 2))
+    n_poly = len(polygons)
+    xy = _f64(points).reshape(-1, 2)
+    n_query = len(xy)
+    pg, qg = _groups(groups, n_poly, "polygon"), _groups(point_groups, n_query, "point")
+    n_hit = C.c_int64(0)
+    h_ = _P()
+    _check(ctx._lib.padne_polygons_locate(ctx._h, n_poly, _ptr(poly_ring_ptr, _PI64), _ptr(ring_ptr, _PI64), _ptr(ring_xy, _PF64),
+                                          _ptr(pg, _PI32), n_query, _ptr(xy, _PF64), _ptr(qg, _PI32), C.byref(n_hit), C.byref(h_)))
+    try:
+        hit_ptr = np.empty(n_query + 1, dtype=np.int32)
+        hit_poly, hit_kind = np.empty(n_hit.value, dtype=np.int32), np.empty(n_hit.value, dtype=np.int32)
+        _check(ctx._lib.padne_polygons_locate_fetch(ctx._h, h_, _ptr(hit_ptr, _PI32), _ptr(hit_poly, _PI32), _ptr(hit_kind, _PI32)))
+    finally:
+        ctx._lib.padne_polygons_locate_destroy(h_)
+    return hit_ptr.astype(np.int64), hit_poly, hit_kind
 
 
 class CsrMatrix:

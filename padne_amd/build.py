@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpadne_hip.so")
 SOURCES = ["capi.hip", "spmv.hip", "spmm.hip", "pcg.hip", "assemble.hip", "comm.hip", "amg.hip", "generate.hip", "kkt.hip", "sample.hip", "error.hip", "goal.hip", "refine.hip", "fields.hip", "cases.hip", "thermal.hip", "coupled.hip", "transient.hip", "stack.hip", "sources.hip",
-           "coupled_transient.hip", "sdirk.hip", "thermal_sens.hip", "periodic.hip", "film.hip", "polymesh.hip"]
+           "coupled_transient.hip", "sdirk.hip", "thermal_sens.hip", "periodic.hip", "film.hip", "polymesh.hip", "connectivity.hip"]
 HEADERS = ["common.hpp", "pool_book.hpp", "face.hpp", "error.hpp", "thermal.hpp", "locate.hpp", os.path.join("..", "..", "include", "padne_hip.h"),
            os.path.join("..", "..", "include", "padne_hip_test.h"), os.path.join("..", "..", "include", "padne_hip_probe.h")]
 ARCH = "gfx950"

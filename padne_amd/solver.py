@@ -14,6 +14,8 @@ stamp_network_into_system :469-541     host emits COO stamps in element order; t
 setup_ground_node :544-560             merges them after the mesh terms, in stamp order
 solve_system :767-780 (SuperLU)        reduction to SPD (reduction.py) + Jacobi-PCG kernels,
                                        multipliers recovered from device residual products
+compute_connectivity :245-260          ``prepare_board`` / ``solve(..., prune=True)``: ``polygons_locate_kernel`` finds the
+filter_dead_networks :618-668          polygons every connection touches, the graph over them runs on the host
 produce_layer_solutions :578-615       numpy slice per mesh (contiguous blocks) + power kernel
 compute_power_density :728-745         ``power_density_kernel``
 (several load cases of one board)      ``solve_load_cases``: one assembly and plan, one block solve, the block's
@@ -951,17 +953,20 @@ def solve_meshed(prob, meshes, mesh_index_to_layer_index, *, filtered_networks=N
     return Solution(problem=prob, layer_solutions=layer_solutions, solver_info=solver_info)
 
 
-def solve(prob, mesher_config: Optional[mesh.Mesher.Config] = None, *, mesher=None, partition=None) -> Solution:
+def solve(prob, mesher_config: Optional[mesh.Mesher.Config] = None, *, mesher=None, partition=None, prune=False) -> Solution:
     """``padne.solver.solve`` (``solver.py:815-902``).
 
-    Meshing and the geometric connectivity pre-pass are out of scope (CGAL / shapely).  ``mesher``
-    must offer ``poly_to_mesh(polygon, seed_points) -> Mesh`` (padne's own ``mesh.Mesher`` does, and
-    so does :class:`padne_amd.structured.StructuredMesher` for rectangles and annuli, and
-    :class:`padne_amd.gridmesh.GridMesher` for polygons with holes, on the device); every
-    polygon of every layer is meshed and treated as connected.
+    CGAL meshing is out of scope.  ``mesher`` must offer ``poly_to_mesh(polygon, seed_points) -> Mesh``
+    (padne's own ``mesh.Mesher`` does, and so does :class:`padne_amd.structured.StructuredMesher` for
+    rectangles and annuli, and :class:`padne_amd.gridmesh.GridMesher` for polygons with holes, on the
+    device).  By default every polygon of every layer is meshed and treated as connected
+    (:func:`mesh_problem`).  ``prune=True`` runs the reference's chain instead -- connectivity prune,
+    mesh, index, assemble, solve: :func:`prepare_board` finds on the device (one GPU) the copper a
+    driven network reaches, only that is meshed, and the networks on dead copper are left out.  The
+    other ``solve_*`` wrappers take the same keyword.
     """
-    meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
-    return solve_meshed(prob, meshes, mesh_index_to_layer_index, partition=partition)
+    meshes, mesh_index_to_layer_index, pruned = _meshed(prob, mesher_config, mesher, prune)
+    return solve_meshed(prob, meshes, mesh_index_to_layer_index, partition=partition, **pruned)
 
 
 def mesh_problem(prob, mesher_config=None, mesher=None):
@@ -981,6 +986,204 @@ def mesh_problem(prob, mesher_config=None, mesher=None):
             meshes.extend(mesher.poly_to_mesh(geom, seeds) for geom in geoms)
         mesh_index_to_layer_index.extend([layer_i] * len(geoms))
     return meshes, mesh_index_to_layer_index
+
+
+# --------------------------------------------------------------------------------------------
+# connectivity pre-pass: which copper does a driven network reach (DESIGN.md "Connectivity pre-pass")
+# --------------------------------------------------------------------------------------------
+
+@dataclass
+class BoardConnectivity:
+    """What :func:`compute_connectivity` found.  ``hits[n][c]``: the ``(geom_i, kind)`` of every polygon of its layer that
+    connection c of network n touches, in ascending geom_i; kind 1 inside, 2 on the boundary.  ``connected`` and ``roots``:
+    sets of ``(layer_i, geom_i)``.  ``unplaced``: the ``(network_i, connection_i)`` that touch no polygon."""
+    hits: list
+    connected: set
+    roots: set
+    unplaced: list
+
+
+@dataclass
+class PreparedBoard:
+    """What :func:`prepare_board` hands to ``solve_meshed*``.  ``skipped``: ``(layer_i, geom_i, reason)`` of the dead polygons
+    that got no display mesh."""
+    meshes: list
+    mesh_index_to_layer_index: list
+    filtered_networks: list
+    disconnected_meshes_by_layer: list
+    connectivity: BoardConnectivity
+    skipped: list
+
+
+def _device_locate(polygons, groups, points, point_groups):
+    return _hip.locate_polygons(get_context(), polygons, groups, points, point_groups)
+
+
+def compute_connectivity(prob, *, locate=None) -> BoardConnectivity:
+    """The reference's ``compute_connectivity`` (``solver.py:84-148, 232-260``) without shapely: one locate call for the
+    whole board -- all layers' polygons, all networks' connections -- and the graph on the host.
+
+    A node per (layer, geom); per network the polygons any of its connections touches (shapely's ``intersects``: inside or
+    on the boundary), all of them roots when the network has a source, all of them joined; connected is what can be
+    reached from a root.  Copper is joined through networks only, never by geometric contact.  ``locate``: the engine
+    ``(polygons, groups, points, point_groups) -> (hit_ptr, hit_poly, hit_kind)``, ``_hip.locate_polygons`` on the device
+    by default (one GPU); the rule is stated in ``include/padne_hip.h``.  The boundary test is exact and has no tolerance:
+    a point computed onto a slanted edge counts as inside or outside by parity.  The geoms are what
+    ``gridmesh.rings_of`` takes: a ``structured.Rect`` or anything with ``.exterior.coords`` and ``.interiors``."""
+    from . import gridmesh
+    if locate is None:
+        locate = _device_locate
+    polygons, groups, first = [], [], [0]
+    for layer_i, layer in enumerate(prob.layers):
+        polygons.extend(gridmesh.rings_of(geom) for geom in layer.geoms)
+        groups.extend([layer_i] * len(layer.geoms))
+        first.append(len(polygons))
+    points, point_groups = [], []
+    for network in prob.networks:
+        for conn in network.connections:
+            points.append((float(conn.point.x), float(conn.point.y)))
+            point_groups.append(prob.layers.index(conn.layer))
+    hit_ptr, hit_poly, hit_kind = locate(polygons, np.array(groups, dtype=np.int32), np.array(points, dtype=np.float64).reshape(-1, 2),
+                                         np.array(point_groups, dtype=np.int32))
+    # union-find over the polygons of the batch
+    parent = list(range(len(polygons)))
+
+    def find(a):
+        while parent[a] != a:
+            parent[a] = parent[parent[a]]
+            a = parent[a]
+        return a
+
+    hits, unplaced, root_polys, touched = [], [], set(), set()
+    q = 0
+    for network_i, network in enumerate(prob.networks):
+        of_network, members = [], []
+        for conn_i in range(len(network.connections)):
+            lo, hi = int(hit_ptr[q]), int(hit_ptr[q + 1])
+            base = first[point_groups[q]]
+            of_network.append([(int(hit_poly[k]) - base, int(hit_kind[k])) for k in range(lo, hi)])
+            members.extend(int(hit_poly[k]) for k in range(lo, hi))
+            if lo == hi:
+                unplaced.append((network_i, conn_i))
+            q += 1
+        hits.append(of_network)
+        touched.update(members)
+        if network.has_source:
+            root_polys.update(members)
+        for other in members[1:]:
+            parent[find(other)] = find(members[0])
+    live = {find(p) for p in root_polys}
+    layer_of_poly = np.searchsorted(np.asarray(first), np.arange(len(polygons)), side="right") - 1
+
+    def pair(p):
+        return int(layer_of_poly[p]), p - first[int(layer_of_poly[p])]
+
+    return BoardConnectivity(hits=hits, connected={pair(p) for p in touched if find(p) in live},
+                             roots={pair(p) for p in root_polys}, unplaced=unplaced)
+
+
+def filter_dead_networks(prob, connectivity: BoardConnectivity) -> list:
+    """The reference's ``filter_dead_networks`` (``solver.py:618-668``): the networks of ``prob`` none of whose connections
+    touches a polygon that is not connected.  A network with an unplaced connection stays, as in the reference."""
+    kept = []
+    for network, of_network in zip(prob.networks, connectivity.hits):
+        dead = any((prob.layers.index(conn.layer), geom_i) not in connectivity.connected
+                   for conn, of_conn in zip(network.connections, of_network) for geom_i, _kind in of_conn)
+        if not dead:
+            kept.append(network)
+    return kept
+
+
+def _display_meshes(mesher, layer_i: int, geoms, dead, skipped: list) -> list:
+    """Meshes of the dead polygons ``dead`` (geom indices) of a layer, for display; those that cannot be meshed go to
+    ``skipped``.  The batch first; where it raises, one polygon at a time."""
+    if hasattr(mesher, "crumbs"):
+        import copy
+        mesher = copy.copy(mesher)
+        mesher.crumbs = "drop"
+    made = None
+    if hasattr(mesher, "polys_to_meshes"):
+        try:
+            made = list(mesher.polys_to_meshes([geoms[g] for g in dead], []))
+        except mesh.MeshingException:
+            made = None
+    out = []
+    for k, g in enumerate(dead):
+        try:
+            m = made[k] if made is not None else mesher.poly_to_mesh(geoms[g], [])
+        except mesh.MeshingException as exc:
+            skipped.append((layer_i, g, str(exc)))
+            continue
+        if hasattr(m, "triangles") and len(m.triangles) == 0:
+            skipped.append((layer_i, g, "the mesh has no face"))
+            continue
+        out.append(m)
+    return out
+
+
+def prepare_board(prob, mesher_config=None, *, mesher=None, disconnected="skip", locate=None) -> PreparedBoard:
+    """Steps 1-3 of the reference's ``solve()`` with its connectivity pre-pass (``solver.py:245-330, 815-845``): only the
+    polygons a driven network reaches are meshed, in (layer, geom) order, and the networks on dead copper are dropped.
+
+    The seeds of a polygon are the connections that lie inside it (kind 1); a connection on its boundary is not a seed, as
+    in the reference.  A mesher that takes a batch (``polys_to_meshes``) gets a layer's connected polygons and their seeds in
+    one call, any other ``poly_to_mesh(geom, seeds of that geom)``.  A kept network with a connection on a layer that ends up
+    without a mesh is a ValueError.  ``disconnected``: ``"skip"`` leaves ``disconnected_meshes_by_layer`` empty; ``"mesh"``
+    meshes the dead polygons with the same mesher for display (a GridMesher with ``crumbs="drop"``) and lists those that
+    yield no face or raise MeshingException in ``skipped``.  The reference meshes them by a constrained triangulation with a
+    ``RELAXED`` config, which has no counterpart here.  ``locate``: see :func:`compute_connectivity`."""
+    if disconnected not in ("skip", "mesh"):
+        raise ValueError(f"disconnected must be 'skip' or 'mesh', got {disconnected!r}")
+    if mesher is None:
+        mesher = mesh.Mesher(mesher_config)
+    connectivity = compute_connectivity(prob, locate=locate)
+    kept = filter_dead_networks(prob, connectivity)
+    meshed_layers = {layer_i for layer_i, _geom_i in connectivity.connected}
+    for network in kept:
+        for conn in network.connections:
+            layer_i = prob.layers.index(conn.layer)
+            if layer_i not in meshed_layers:
+                raise ValueError(f"a connection at ({conn.point.x:g}, {conn.point.y:g}) lies on layer {layer_i} "
+                                 f"({getattr(conn.layer, 'name', '')!r}), which has no connected copper: no mesh to attach it to")
+    # the interior seeds of every connected polygon, and of every layer, in the order of the connections
+    seeds_of = {pair: [] for pair in connectivity.connected}
+    layer_seeds = [[] for _ in prob.layers]
+    for network, of_network in zip(prob.networks, connectivity.hits):
+        for conn, of_conn in zip(network.connections, of_network):
+            layer_i = prob.layers.index(conn.layer)
+            inside = [g for g, kind in of_conn if kind == 1 and (layer_i, g) in seeds_of]
+            for g in inside:
+                seeds_of[(layer_i, g)].append(mesh.Point(conn.point.x, conn.point.y))
+            if inside:
+                layer_seeds[layer_i].append(mesh.Point(conn.point.x, conn.point.y))
+    meshes, mesh_index_to_layer_index, skipped = [], [], []
+    disconnected_meshes_by_layer = [[] for _ in prob.layers]
+    log.info("Meshing the connected components")
+    for layer_i, layer in enumerate(prob.layers):
+        geoms = list(layer.geoms)
+        live = [g for g in range(len(geoms)) if (layer_i, g) in connectivity.connected]
+        if live and hasattr(mesher, "polys_to_meshes"):          # a mesher that takes a batch: one call per layer
+            meshes.extend(mesher.polys_to_meshes([geoms[g] for g in live], layer_seeds[layer_i]))
+        else:
+            meshes.extend(mesher.poly_to_mesh(geoms[g], seeds_of[(layer_i, g)]) for g in live)
+        mesh_index_to_layer_index.extend([layer_i] * len(live))
+        if disconnected == "mesh":
+            dead = [g for g in range(len(geoms)) if (layer_i, g) not in connectivity.connected]
+            if dead:
+                disconnected_meshes_by_layer[layer_i] = _display_meshes(mesher, layer_i, geoms, dead, skipped)
+    return PreparedBoard(meshes=meshes, mesh_index_to_layer_index=mesh_index_to_layer_index, filtered_networks=kept,
+                         disconnected_meshes_by_layer=disconnected_meshes_by_layer, connectivity=connectivity, skipped=skipped)
+
+
+def _meshed(prob, mesher_config, mesher, prune: bool) -> tuple:
+    """(meshes, mesh_index_to_layer_index, keywords for ``solve_meshed*``) for the ``solve_*`` wrappers: ``mesh_problem``,
+    or with ``prune`` :func:`prepare_board` and its kept networks and (empty) lists of disconnected meshes."""
+    if not prune:
+        meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
+        return meshes, mesh_index_to_layer_index, {}
+    board = prepare_board(prob, mesher_config, mesher=mesher)
+    return board.meshes, board.mesh_index_to_layer_index, {"filtered_networks": board.filtered_networks,
+                                                           "disconnected_meshes_by_layer": board.disconnected_meshes_by_layer}
 
 
 # --------------------------------------------------------------------------------------------
@@ -1198,12 +1401,12 @@ def solve_meshed_load_cases(prob, meshes, mesh_index_to_layer_index, cases, *, f
 
 
 def solve_load_cases(prob, cases, mesher_config: Optional[mesh.Mesher.Config] = None, *, mesher=None,
-                     partition=None) -> list:
+                     partition=None, prune=False) -> list:
     """``solve`` for several load cases of one board (see :func:`solve_meshed_load_cases`): the board is meshed once."""
     _refuse_partition(partition, "load cases")
     cases = check_load_cases(prob, cases)
-    meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
-    return solve_meshed_load_cases(prob, meshes, mesh_index_to_layer_index, cases)
+    meshes, mesh_index_to_layer_index, pruned = _meshed(prob, mesher_config, mesher, prune)
+    return solve_meshed_load_cases(prob, meshes, mesh_index_to_layer_index, cases, **pruned)
 
 
 # --------------------------------------------------------------------------------------------
@@ -1489,13 +1692,13 @@ def solve_meshed_sensitivities(prob, meshes, mesh_index_to_layer_index, objectiv
 
 
 def solve_sensitivities(prob, objectives, mesher_config: Optional[mesh.Mesher.Config] = None, *, mesher=None,
-                        partition=None):
+                        partition=None, prune=False):
     """``solve`` with the sensitivities of potential differences (see :func:`solve_meshed_sensitivities`): the board is
     meshed once.  Returns (Solution, [Sensitivity per objective])."""
     _refuse_partition(partition, "sensitivities")
     objectives = check_objectives(prob, objectives)
-    meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
-    return solve_meshed_sensitivities(prob, meshes, mesh_index_to_layer_index, objectives)
+    meshes, mesh_index_to_layer_index, pruned = _meshed(prob, mesher_config, mesher, prune)
+    return solve_meshed_sensitivities(prob, meshes, mesh_index_to_layer_index, objectives, **pruned)
 
 
 # --------------------------------------------------------------------------------------------
@@ -1646,14 +1849,14 @@ def solve_meshed_currents(prob, meshes, mesh_index_to_layer_index, cuts=(), *, f
     return solution, report
 
 
-def solve_currents(prob, cuts=(), mesher_config: Optional[mesh.Mesher.Config] = None, *, mesher=None, partition=None):
+def solve_currents(prob, cuts=(), mesher_config: Optional[mesh.Mesher.Config] = None, *, mesher=None, partition=None, prune=False):
     """``solve`` with where the current goes (see :func:`solve_meshed_currents`): the board is meshed once.  Returns
     (Solution, CurrentReport)."""
     _refuse_partition(partition, "currents")
     cuts = check_cuts(prob, cuts)
-    meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
+    meshes, mesh_index_to_layer_index, pruned = _meshed(prob, mesher_config, mesher, prune)
     return solve_meshed_currents(prob, meshes, mesh_index_to_layer_index,
-                                 [Cut(prob.layers[i], a, b) for i, a, b in cuts])
+                                 [Cut(prob.layers[i], a, b) for i, a, b in cuts], **pruned)
 
 
 # --------------------------------------------------------------------------------------------
@@ -1835,15 +2038,15 @@ def solve_meshed_load_case_currents(prob, meshes, mesh_index_to_layer_index, cas
 
 
 def solve_load_case_currents(prob, cases, cuts=(), mesher_config: Optional[mesh.Mesher.Config] = None, *, mesher=None,
-                             per_case_fields=True, partition=None):
+                             per_case_fields=True, partition=None, prune=False):
     """``solve`` for several load cases with their currents and the envelope (see
     :func:`solve_meshed_load_case_currents`): the board is meshed once."""
     _refuse_partition(partition, "load-case currents")
     cases = check_load_cases(prob, cases)
     cuts = check_cuts(prob, cuts)
-    meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
+    meshes, mesh_index_to_layer_index, pruned = _meshed(prob, mesher_config, mesher, prune)
     return solve_meshed_load_case_currents(prob, meshes, mesh_index_to_layer_index, cases,
-                                           [Cut(prob.layers[i], a, b) for i, a, b in cuts], per_case_fields=per_case_fields)
+                                           [Cut(prob.layers[i], a, b) for i, a, b in cuts], per_case_fields=per_case_fields, **pruned)
 
 
 # --------------------------------------------------------------------------------------------
@@ -2788,14 +2991,15 @@ def solve_meshed_thermal(prob, meshes, mesh_index_to_layer_index, model: Thermal
 
 
 def solve_thermal(prob, model: ThermalModel, mesher_config: Optional[mesh.Mesher.Config] = None, *, mesher=None, cases=None,
-                  per_case_fields=True, partition=None):
+                  per_case_fields=True, partition=None, prune=False):
     """``solve`` with the copper's temperatures (see :func:`solve_meshed_thermal`): the board is meshed once."""
     _refuse_partition(partition, "temperatures")
     check_thermal_model(prob, model)
     if cases is not None:
         cases = check_load_cases(prob, cases)
-    meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
-    return solve_meshed_thermal(prob, meshes, mesh_index_to_layer_index, model, cases=cases, per_case_fields=per_case_fields)
+    meshes, mesh_index_to_layer_index, pruned = _meshed(prob, mesher_config, mesher, prune)
+    return solve_meshed_thermal(prob, meshes, mesh_index_to_layer_index, model, cases=cases, per_case_fields=per_case_fields,
+                                **pruned)
 
 
 # --------------------------------------------------------------------------------------------
@@ -3111,7 +3315,7 @@ def solve_meshed_thermal_sensitivities(prob, meshes, mesh_index_to_layer_index, 
 
 
 def solve_thermal_sensitivities(prob, model: ThermalModel, objectives, mesher_config: Optional[mesh.Mesher.Config] = None, *,
-                                mesher=None, cases=None, partition=None):
+                                mesher=None, cases=None, partition=None, prune=False):
     """``solve`` with the temperatures and their sensitivities (see :func:`solve_meshed_thermal_sensitivities`): the board is
     meshed once."""
     _refuse_partition(partition, "temperature sensitivities")
@@ -3122,8 +3326,8 @@ def solve_thermal_sensitivities(prob, model: ThermalModel, objectives, mesher_co
     if cases is not None:
         cases = check_load_cases(prob, cases)
     check_temperature_objectives(prob, model, objectives, 1 if cases is None else len(cases))
-    meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
-    return solve_meshed_thermal_sensitivities(prob, meshes, mesh_index_to_layer_index, model, objectives, cases=cases)
+    meshes, mesh_index_to_layer_index, pruned = _meshed(prob, mesher_config, mesher, prune)
+    return solve_meshed_thermal_sensitivities(prob, meshes, mesh_index_to_layer_index, model, objectives, cases=cases, **pruned)
 
 
 # --------------------------------------------------------------------------------------------
@@ -3571,14 +3775,14 @@ def solve_meshed_thermal_transient(prob, meshes, mesh_index_to_layer_index, mode
 
 
 def solve_thermal_transient(prob, model: TransientModel, schedule, mesher_config: Optional[mesh.Mesher.Config] = None, *,
-                            mesher=None, cases=None, repeat=1, probes=(), keep="end", partition=None):
+                            mesher=None, cases=None, repeat=1, probes=(), keep="end", partition=None, prune=False):
     """``solve`` with the copper's temperatures over a schedule (see :func:`solve_meshed_thermal_transient`): the board is
     meshed once."""
     _refuse_partition(partition, "transient temperatures")
     _check_transient_arguments(prob, model, schedule, cases, repeat, probes, keep, None)
-    meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
+    meshes, mesh_index_to_layer_index, pruned = _meshed(prob, mesher_config, mesher, prune)
     return solve_meshed_thermal_transient(prob, meshes, mesh_index_to_layer_index, model, schedule, cases=cases, repeat=repeat,
-                                          probes=probes, keep=keep)
+                                          probes=probes, keep=keep, **pruned)
 
 
 # --------------------------------------------------------------------------------------------
@@ -3787,14 +3991,15 @@ def solve_meshed_thermal_periodic(prob, meshes, mesh_index_to_layer_index, model
 
 
 def solve_thermal_periodic(prob, model: TransientModel, schedule, mesher_config: Optional[mesh.Mesher.Config] = None, *,
-                           mesher=None, tolerance, cases=None, max_periods=64, probes=(), keep="end", partition=None):
+                           mesher=None, tolerance, cases=None, max_periods=64, probes=(), keep="end", partition=None,
+                           prune=False):
     """``solve`` with the periodic steady state of a duty cycle (see :func:`solve_meshed_thermal_periodic`): the board is
     meshed once."""
     _refuse_partition(partition, "periodic temperatures")
     _check_periodic_arguments(prob, model, schedule, cases, probes, keep, tolerance, max_periods, None)
-    meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
+    meshes, mesh_index_to_layer_index, pruned = _meshed(prob, mesher_config, mesher, prune)
     return solve_meshed_thermal_periodic(prob, meshes, mesh_index_to_layer_index, model, schedule, tolerance=tolerance, cases=cases,
-                                         max_periods=max_periods, probes=probes, keep=keep)
+                                         max_periods=max_periods, probes=probes, keep=keep, **pruned)
 
 
 # --------------------------------------------------------------------------------------------
@@ -4011,16 +4216,16 @@ def solve_meshed_thermal_transient_adaptive(prob, meshes, mesh_index_to_layer_in
 
 def solve_thermal_transient_adaptive(prob, model: TransientModel, schedule, mesher_config: Optional[mesh.Mesher.Config] = None, *,
                                      tolerance, mesher=None, cases=None, repeat=1, probes=(), keep="end", first_step=None,
-                                     min_step=None, max_steps=MAX_TRANSIENT_STEPS, partition=None):
+                                     min_step=None, max_steps=MAX_TRANSIENT_STEPS, partition=None, prune=False):
     """``solve`` with the copper's temperatures over a schedule of spans (see
     :func:`solve_meshed_thermal_transient_adaptive`): the board is meshed once."""
     _refuse_partition(partition, "transient temperatures")
     _check_adaptive_transient_arguments(prob, model, schedule, cases, repeat, probes, keep, tolerance, first_step, min_step,
                                         max_steps, None)
-    meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
+    meshes, mesh_index_to_layer_index, pruned = _meshed(prob, mesher_config, mesher, prune)
     return solve_meshed_thermal_transient_adaptive(prob, meshes, mesh_index_to_layer_index, model, schedule, tolerance=tolerance,
                                                    cases=cases, repeat=repeat, probes=probes, keep=keep, first_step=first_step,
-                                                   min_step=min_step, max_steps=max_steps)
+                                                   min_step=min_step, max_steps=max_steps, **pruned)
 
 
 # --------------------------------------------------------------------------------------------
@@ -4432,16 +4637,16 @@ def solve_meshed_electrothermal(prob, meshes, mesh_index_to_layer_index, model: 
 
 
 def solve_electrothermal(prob, model: ElectroThermalModel, mesher_config: Optional[mesh.Mesher.Config] = None, *, mesher=None,
-                         cases=None, per_case_fields=True, partition=None):
+                         cases=None, per_case_fields=True, partition=None, prune=False):
     """``solve`` with the copper's temperatures and the conductances that follow them (see
     :func:`solve_meshed_electrothermal`): the board is meshed once."""
     _refuse_partition(partition, "electro-thermal solves")
     check_electrothermal_model(prob, model)
     if cases is not None:
         cases = check_load_cases(prob, cases)
-    meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
+    meshes, mesh_index_to_layer_index, pruned = _meshed(prob, mesher_config, mesher, prune)
     return solve_meshed_electrothermal(prob, meshes, mesh_index_to_layer_index, model, cases=cases,
-                                       per_case_fields=per_case_fields)
+                                       per_case_fields=per_case_fields, **pruned)
 
 
 # --------------------------------------------------------------------------------------------
@@ -4718,15 +4923,15 @@ def solve_meshed_electrothermal_transient(prob, meshes, mesh_index_to_layer_inde
 
 def solve_electrothermal_transient(prob, model: ElectroThermalTransientModel, schedule,
                                    mesher_config: Optional[mesh.Mesher.Config] = None, *, mesher=None, cases=None, repeat=1,
-                                   probes=(), voltage_probes=(), stop_above=None, keep="end", partition=None):
+                                   probes=(), voltage_probes=(), stop_above=None, keep="end", partition=None, prune=False):
     """``solve`` with the copper's temperatures over a schedule and the conductances that follow them (see
     :func:`solve_meshed_electrothermal_transient`): the board is meshed once."""
     _refuse_partition(partition, "transient electro-thermal solves")
     _check_electrothermal_transient_arguments(prob, model, schedule, cases, repeat, probes, voltage_probes, stop_above, keep, None)
-    meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
+    meshes, mesh_index_to_layer_index, pruned = _meshed(prob, mesher_config, mesher, prune)
     return solve_meshed_electrothermal_transient(prob, meshes, mesh_index_to_layer_index, model, schedule, cases=cases,
                                                  repeat=repeat, probes=probes, voltage_probes=voltage_probes,
-                                                 stop_above=stop_above, keep=keep)
+                                                 stop_above=stop_above, keep=keep, **pruned)
 
 
 # --------------------------------------------------------------------------------------------
@@ -5012,14 +5217,15 @@ def solve_meshed_element_cases(prob, meshes, mesh_index_to_layer_index, cases, *
 
 
 def solve_element_cases(prob, cases, mesher_config: Optional[mesh.Mesher.Config] = None, *, mesher=None, objectives=None,
-                        fields=True, partition=None):
+                        fields=True, partition=None, prune=False):
     """``solve`` for element cases (see :func:`solve_meshed_element_cases`): the board is meshed once."""
     _refuse_partition(partition, "element cases")
     cases = check_element_cases(prob, cases)
     if objectives is not None:
         objectives = check_objectives(prob, objectives)
-    meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
-    return solve_meshed_element_cases(prob, meshes, mesh_index_to_layer_index, cases, objectives=objectives, fields=fields)
+    meshes, mesh_index_to_layer_index, pruned = _meshed(prob, mesher_config, mesher, prune)
+    return solve_meshed_element_cases(prob, meshes, mesh_index_to_layer_index, cases, objectives=objectives, fields=fields,
+                                      **pruned)
 
 
 # --------------------------------------------------------------------------------------------
@@ -5188,13 +5394,14 @@ def solve_meshed_error(prob, meshes, mesh_index_to_layer_index, *, tolerance=Non
     return solution, report
 
 
-def solve_error(prob, mesher_config: Optional[mesh.Mesher.Config] = None, *, tolerance=None, mesher=None, partition=None):
+def solve_error(prob, mesher_config: Optional[mesh.Mesher.Config] = None, *, tolerance=None, mesher=None, partition=None,
+                prune=False):
     """``solve`` with the error estimate of :func:`solve_meshed_error`: the board is meshed once.  Returns
     (Solution, ErrorReport)."""
     _refuse_partition(partition, "error estimates")
     tolerance = check_tolerance(tolerance)
-    meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
-    return solve_meshed_error(prob, meshes, mesh_index_to_layer_index, tolerance=tolerance)
+    meshes, mesh_index_to_layer_index, pruned = _meshed(prob, mesher_config, mesher, prune)
+    return solve_meshed_error(prob, meshes, mesh_index_to_layer_index, tolerance=tolerance, **pruned)
 
 
 # --------------------------------------------------------------------------------------------
@@ -5374,14 +5581,14 @@ def solve_meshed_adaptive(prob, meshes, mesh_index_to_layer_index, *, tolerance,
 
 
 def solve_adaptive(prob, mesher_config: Optional[mesh.Mesher.Config] = None, *, tolerance, mesher=None, max_rounds=8,
-                   max_faces=None, min_size=0.0, partition=None, timings: Optional[dict] = None):
+                   max_faces=None, min_size=0.0, partition=None, timings: Optional[dict] = None, prune=False):
     """``solve`` refined where the error estimate asks: the board is meshed once, then :func:`solve_meshed_adaptive`.
     Returns (Solution, ErrorReport, AdaptiveHistory)."""
     _refuse_partition(partition, "adaptive solves")
     check_adaptive_arguments(tolerance, max_rounds, max_faces, min_size)
-    meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
+    meshes, mesh_index_to_layer_index, pruned = _meshed(prob, mesher_config, mesher, prune)
     return solve_meshed_adaptive(prob, meshes, mesh_index_to_layer_index, tolerance=tolerance, max_rounds=max_rounds,
-                                 max_faces=max_faces, min_size=min_size, timings=timings)
+                                 max_faces=max_faces, min_size=min_size, timings=timings, **pruned)
 
 
 # --------------------------------------------------------------------------------------------
@@ -5540,14 +5747,14 @@ def solve_meshed_goal_error(prob, meshes, mesh_index_to_layer_index, objectives,
 
 
 def solve_goal_error(prob, objectives, mesher_config: Optional[mesh.Mesher.Config] = None, *, tolerance=None, mesher=None,
-                     partition=None):
+                     partition=None, prune=False):
     """``solve`` with the goal-oriented estimates of :func:`solve_meshed_goal_error`: the board is meshed once.  Returns
     (Solution, ErrorReport, [GoalError per objective])."""
     _refuse_partition(partition, "goal-oriented error estimates")
     objectives = check_objectives(prob, objectives)
     tolerance = check_goal_tolerance(tolerance)
-    meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
-    return solve_meshed_goal_error(prob, meshes, mesh_index_to_layer_index, objectives, tolerance=tolerance)
+    meshes, mesh_index_to_layer_index, pruned = _meshed(prob, mesher_config, mesher, prune)
+    return solve_meshed_goal_error(prob, meshes, mesh_index_to_layer_index, objectives, tolerance=tolerance, **pruned)
 
 
 @dataclass
@@ -5639,15 +5846,15 @@ def solve_meshed_goal_adaptive(prob, meshes, mesh_index_to_layer_index, objectiv
 
 
 def solve_goal_adaptive(prob, objectives, mesher_config: Optional[mesh.Mesher.Config] = None, *, tolerance, mesher=None,
-                        max_rounds=8, max_faces=None, min_size=0.0, partition=None, timings: Optional[dict] = None):
+                        max_rounds=8, max_faces=None, min_size=0.0, partition=None, timings: Optional[dict] = None, prune=False):
     """``solve`` refined where the voltage drops ask: the board is meshed once, then :func:`solve_meshed_goal_adaptive`.
     Returns (Solution, ErrorReport, [GoalError per objective], GoalAdaptiveHistory)."""
     _refuse_partition(partition, "adaptive solves")
     objectives = check_objectives(prob, objectives)
     check_goal_adaptive_arguments(tolerance, max_rounds, max_faces, min_size)
-    meshes, mesh_index_to_layer_index = mesh_problem(prob, mesher_config, mesher)
+    meshes, mesh_index_to_layer_index, pruned = _meshed(prob, mesher_config, mesher, prune)
     return solve_meshed_goal_adaptive(prob, meshes, mesh_index_to_layer_index, objectives, tolerance=tolerance,
-                                      max_rounds=max_rounds, max_faces=max_faces, min_size=min_size, timings=timings)
+                                      max_rounds=max_rounds, max_faces=max_faces, min_size=min_size, timings=timings, **pruned)
 
 
 # --------------------------------------------------------------------------------------------
