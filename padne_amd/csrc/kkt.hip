@@ -358,7 +358,7 @@ __global__ __launch_bounds__(256) void kkt_strip_keys(const long long n_free, co
     const double x = xy[2 * v], y = xy[2 * v + 1];
     const double x_lo = par[4 * m], span = par[4 * m + 1], y0 = par[4 * m + 2], height = par[4 * m + 3];
     long long strip = 0;
-    if (height > 0.0) strip = (long long)floor((y - y0) / height);
+    if (height > 0.0) strip = (long long)fmin(floor((y - y0) / height), 65536.0);      // (clamped before the cast, as the host's)
     if (strip < 0 || strip >= (1ll << strip_bits)) {        // (the host's bound of the field, computed from the same numbers)
         atomicExch(bad, 1);
         strip = 0;
@@ -428,7 +428,9 @@ static int kkt_apply_strip_order(padne_kkt *k) {
             x_lo = xmin;
             span = std::max(xmax - xmin, 1e-300);                               // reduction._strip_order
             y0 = ymin;
-            if (cnt >= 2.0) {                                                   // reduction.strip_index (a single point: strip 0)
+            // reduction.strip_index (a single point: strip 0).  A box of the owners with zero width or zero height has no area
+            // to take a spacing from: height stays 0 and kkt_strip_keys gives every owner of the mesh strip 0, the host's rule
+            if (cnt >= 2.0 && xmax - xmin != 0.0 && ymax - y0 != 0.0) {
                 const double area = std::max((xmax - xmin) * (ymax - y0), 1e-300);
                 height = 3.4 * sqrt(area / cnt);
             }

@@ -597,7 +597,10 @@ def strip_index(xy: np.ndarray, mesh_id: np.ndarray) -> np.ndarray:
     (3.4 * sqrt(bounding-box area / n)), so the neighbours of a vertex lie in its own strip or the two adjacent ones.
     Sorting by (strip, x) then gives a *band* numbering: the columns of 64 consecutive rows fall into three short
     index ranges, which is what the x-window path of the SpMV needs (on a random Delaunay mesh 96 % of the 64-row
-    tiles are covered by 3 runs of 128 entries; in Z-order none are) and what a scan-line numbering has anyway."""
+    tiles are covered by 3 runs of 128 entries; in Z-order none are) and what a scan-line numbering has anyway.
+    A mesh whose points' bounding box has zero width or zero height (two owners above each other, say) has no area to
+    take a spacing from: all its points get strip 0 (kkt.hip's kkt_apply_strip_order states the same rule).  The quotient
+    is clamped to 65 536 before the cast, so that a strip beyond the key field is a value the caller's guard sees."""
     strip = np.zeros(len(xy), dtype=np.int64)
     mesh_id = np.asarray(mesh_id)
     if len(xy) == 0:
@@ -613,9 +616,12 @@ def strip_index(xy: np.ndarray, mesh_id: np.ndarray) -> np.ndarray:
         if len(px) < 2:
             continue
         y0 = float(py.min())
-        area = max((float(px.max()) - float(px.min())) * (float(py.max()) - y0), 1e-300)
+        width, rise = float(px.max()) - float(px.min()), float(py.max()) - y0
+        if width == 0.0 or rise == 0.0:                      # a degenerate box: strip 0
+            continue
+        area = max(width * rise, 1e-300)
         height = 3.4 * np.sqrt(area / len(px))
-        strip[sel] = np.floor((py - y0) / height).astype(np.int64)
+        strip[sel] = np.minimum(np.floor((py - y0) / height), 65536.0).astype(np.int64)
     return strip
 
 
