@@ -9,7 +9,9 @@
 //   K3  beta = rz'/rz ; p = D^-1 r + beta p                      (32*N bytes)
 //       + workgroup 0 does the bookkeeping: iteration count, convergence / breakdown flags.
 // z = D^-1 r is never stored.  With multigrid K2 stops at r.r, the cycle produces z and the r.z partials
-// (its last stage), and K3 reads z.  Scalars never visit the host: every workgroup of the consuming
+// (its last stage), and K3 reads z.  The one-GPU multigrid loop keeps its books between K2 and the cycle
+// (pcg_decide_kernel, one workgroup): the iteration that converges ends there, without its cycle and its K3.
+// Scalars never visit the host: every workgroup of the consuming
 // kernel re-adds the producer's per-workgroup partials (<= 2048 doubles, L2 resident) in a
 // fixed order, so results are bitwise reproducible run to run (no float atomics).
 // In multi-GPU runs a one-workgroup kernel folds the partials into a scalar which is then
@@ -48,26 +50,37 @@ __device__ __forceinline__ double block_total(const double *__restrict__ partial
     return t;
 }
 
-// two such sums in ONE pass over the workgroup (the loads of both arrays in flight together, one pair of barriers): every
-// sum adds the same terms in the same order as block_total, hence the same bits.  `red2` = 8 doubles of LDS.
-__device__ __forceinline__ void block_total2(const double *__restrict__ pa, const int Pa, const double *__restrict__ pb, const int Pb,
-                                             double *red2, double *ta, double *tb) {
-    double sa = 0.0, sb = 0.0;
-    const int P = Pa > Pb ? Pa : Pb;
-    for (int i = threadIdx.x; i < P; i += 256) {
-        if (i < Pa) sa += pa[i];
-        if (i < Pb) sb += pb[i];
+// K such sums in ONE pass over the workgroup (one pair of barriers), with EVERY load issued before the first addition.
+// block_total waits for each load in turn (a conditional load and its wait per round: up to 8 round trips to L2 per array),
+// which the vector kernels of the multigrid loop paid in every workgroup of every launch before they touched a row.  The
+// loads here are unconditional (a round past the end reads entry 0, which every slot has, and is not added).  Each sum adds
+// the same terms in the same order as block_total, hence the same bits.  `red` = 4 * K doubles of LDS.
+template <int K>
+__device__ __forceinline__ void block_totals_ahead(const double *const (&pa)[K], const int (&P)[K], double *red, double (&t)[K]) {
+    constexpr int J = kMaxPartials / 256;
+    double v[K][J];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+#pragma unroll
+        for (int j = 0; j < J; ++j) {
+            const int i = threadIdx.x + 256 * j;
+            v[k][j] = pa[k][i < P[k] ? i : 0];
+        }
     }
-    sa = wave_sum_v(sa);
-    sb = wave_sum_v(sb);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) {
-        red2[w] = sa;
-        red2[4 + w] = sb;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        double s = 0.0;
+#pragma unroll
+        for (int j = 0; j < J; ++j)
+            if ((int)threadIdx.x + 256 * j < P[k]) s += v[k][j];
+        for (int i = threadIdx.x + 256 * J; i < P[k]; i += 256) s += pa[k][i];
+        s = wave_sum_v(s);
+        if (lane == 0) red[4 * k + w] = s;
     }
     __syncthreads();
-    *ta = (red2[0] + red2[1]) + (red2[2] + red2[3]);
-    *tb = (red2[4] + red2[5]) + (red2[6] + red2[7]);
+#pragma unroll
+    for (int k = 0; k < K; ++k) t[k] = (red[4 * k] + red[4 * k + 1]) + (red[4 * k + 2] + red[4 * k + 3]);
     __syncthreads();
 }
 
@@ -86,7 +99,9 @@ struct PcgStatus {       // lives in device memory, mirrored to pinned host memo
     int32_t iters;       // iterations completed
     int32_t done_seen;   // `done` as the x/r update of the current iteration read it.  The p update of the multigrid loop
                          // (which sets `done` itself, in its workgroup 0) takes its early exit from THIS word: a workgroup of
-                         // that launch dispatched after workgroup 0's store must still apply its share of x += alpha p
+                         // that launch dispatched after workgroup 0's store must still apply its share of x += alpha p.
+                         // 2 (pcg_decide_kernel): the loop ended IN this iteration, behind its x/r update and before its
+                         // cycle -- the p update has no direction to form, only a deferred x += alpha p to apply
     double rr;           // recurrence ||r||^2 after the last completed iteration
     double tol2;         // stop when rr <= tol2
     double bb;           // ||b||^2
@@ -259,24 +274,79 @@ __global__ __launch_bounds__(256) void pcg_update_xr_entry_kernel(
     const int stop = st->done;              // written by an EARLIER launch: every workgroup of this one reads the same value
     if (blockIdx.x == 0 && threadIdx.x == 0) st->done_seen = stop;
     if (stop) return;
-    double rz, pq;
-    block_total2(part_rz, P_rz, part_pq, P_pq, red, &rz, &pq);
+    // the workgroup's first rows of r and q are asked for BEFORE the partial sums are folded: nothing in them depends on
+    // alpha, and all workgroups of the launch are resident and fold at the same moment -- their first loads would otherwise
+    // start only behind the fold's load, reduction and barriers, in every launch
+    const long long i0 = (long long)blockIdx.x * 256 + threadIdx.x;
+    double r0 = 0.0, q0 = 0.0;
+    if (i0 < n) {
+        r0 = r[i0];
+        q0 = q[i0];
+    }
+    const double *const parts[2] = {part_rz, part_pq};
+    const int counts[2] = {P_rz, P_pq};
+    double tot[2];
+    block_totals_ahead<2>(parts, counts, red, tot);
+    const double rz = tot[0], pq = tot[1];
     const double s2 = *bb2;
     const double s_inv = s2 > 0.0 ? 1.0 / sqrt(s2) : 1.0;
     // p_hat: the search direction is stored as p / ||b|| in single precision (solve_one), q and p.q are those of the stored
     // vector: the step along it is alpha ||b||
     const double alpha = p_hat ? rz / (pq * (s2 > 0.0 ? sqrt(s2) : 1.0)) : rz / pq;
     double s_rr = 0.0;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const double ri = r[i] - alpha * q[i];
+    auto row = [&](const long long i, const double r_old, const double qi) {
+        const double ri = r_old - alpha * qi;
         if (x != nullptr) x[i] += alpha * p[i];      // null: pcg_update_p_z_kernel does it while it has p in registers
         r[i] = ri;
         s_rr += ri * ri;
         const float v = (float)(ri * s_inv);
         b32[i] = v;
         if (xa32 != nullptr) xa32[i] = c * dinv32[i] * v;      // (null: the cycle forms its first sweep from b32 itself)
-    }
+    };
+    if (i0 < n) row(i0, r0, q0);
+    for (long long i = i0 + (long long)gridDim.x * 256; i < n; i += (long long)gridDim.x * 256) row(i, r[i], q[i]);
     block_store_partial(s_rr, red, part_rr + blockIdx.x);
+}
+
+// The books of an iteration of the one-GPU multigrid loop, kept BEHIND its x/r update and BEFORE its cycle (one workgroup):
+// the iteration count, ||r||^2, the stopping decision and the breakdown tests on p.q and ||r||^2 -- everything the p update
+// used to settle at the END of the iteration except the test on the new r.z, which only the cycle produces.  In the
+// iteration that converges the cycle's kernels (they return on `done`) and the p update (done_seen == 2) then do no work:
+// their results, z and the next direction, were never read.  The sums are re-added exactly as the p update re-added them
+// (block_total over the same partials): rr, p.q and the step length keep their bits.
+// alpha_out (the search directions of the solve are kept): the step length along this iteration's direction, for
+// pcg_x_flush_kernel -- the double the p update recorded, alpha / ||b|| with alpha = r.z / p.q.
+__global__ __launch_bounds__(256) void pcg_decide_kernel(
+    const double *__restrict__ part_rz, const int P_rz, const double *__restrict__ part_pq, const int P_pq,
+    const double *__restrict__ part_rr, const int P_rr, PcgStatus *__restrict__ st, const int max_iter,
+    const double *__restrict__ bb2, double *__restrict__ alpha_out) {
+    __shared__ double red[12];
+    if (st->done) return;                    // written by an EARLIER launch; this one writes it behind a barrier every wave passes
+    const double *const parts[3] = {part_rr, part_pq, part_rz};
+    const int counts[3] = {P_rr, P_pq, P_rz};
+    double tot[3];
+    block_totals_ahead<3>(parts, counts, red, tot);
+    const double rr = tot[0], pq = tot[1];
+    if (alpha_out != nullptr) {
+        const double rz = tot[2];
+        const double s2 = *bb2;
+        const double z_mul = s2 > 0.0 ? sqrt(s2) : 1.0;
+        const double alpha = rz / pq;
+        if (threadIdx.x == 0) *alpha_out = alpha / z_mul;
+    }
+    if (threadIdx.x == 0) {
+        const int it = st->iters + 1;
+        st->iters = it;
+        st->rr = rr;
+        if (!(pq > 0.0) || !(rr == rr)) {
+            st->code = PADNE_E_BREAKDOWN;
+            st->done = 1;
+            st->done_seen = 2;
+        } else if (rr <= st->tol2 || it >= max_iter) {
+            st->done = 1;
+            st->done_seen = 2;
+        }
+    }
 }
 
 // p^ = z / ||b|| in single precision (the first search direction of a (re)start)
@@ -293,17 +363,52 @@ __global__ __launch_bounds__(256) void pcg_update_p_z_kernel(
     const int P_rz, const double *__restrict__ part_rr, const int P_rr, const double *__restrict__ part_pq,
     const int P_pq, const double *__restrict__ z, double *__restrict__ p, PcgStatus *__restrict__ st,
     const int max_iter, double *__restrict__ x_deferred, const float *__restrict__ z32, const double *__restrict__ bb2,
-    float *__restrict__ p32, float *__restrict__ p32_next = nullptr, double *__restrict__ alpha_out = nullptr) {
+    float *__restrict__ p32, float *__restrict__ p32_next = nullptr, double *__restrict__ alpha_out = nullptr,
+    const int decided = 0) {
     // p32_next / alpha_out (the search directions of a solve KEPT, solve_one): the new direction goes to a place of its own
     // and the step length along the old one is left for pcg_x_flush_kernel -- x is not touched here (x_deferred is null)
+    // decided: pcg_decide_kernel has kept this iteration's books (and recorded the step length): what is left for this
+    // kernel's first workgroup is the breakdown test on the new r.z
     __shared__ double red[8];
     // NOT st->done: workgroup 0 of this very launch sets it, and this kernel carries the deferred x += alpha p -- a
     // workgroup dispatched after that store would skip its slice of the last update.  done_seen is what the x/r update of
-    // this iteration read, i.e. a value from before this launch
-    if (st->done_seen) return;
-    double rz_new, rz_old;
-    block_total2(part_rz_new, P_rz, part_rz_old, P_rz, red, &rz_new, &rz_old);
+    // this iteration read (1), or what pcg_decide_kernel left behind that update (2: the loop ended in this iteration, x and
+    // r of it are applied, there was no cycle): either way a value from before this launch, the same in every workgroup
+    const int seen = st->done_seen;
+    if (seen == 1) return;
+    const bool last = seen == 2;
+    if (last && x_deferred == nullptr) return;      // (the kept directions: the flush forms x, nothing rides on this update)
+    // the first rows of z and p (kept directions) are asked for before the partial sums are folded, as in
+    // pcg_update_xr_entry_kernel
+    const long long i0 = (long long)blockIdx.x * 256 + threadIdx.x;
+    const bool ahead = p32_next != nullptr && i0 < n;
+    float z0 = 0.f, p0 = 0.f;
+    if (ahead) {
+        z0 = z32[i0];
+        p0 = p32[i0];
+    }
+    const double *const parts[2] = {part_rz_new, part_rz_old};
+    const int counts[2] = {P_rz, P_rz};
+    double tot[2];
+    block_totals_ahead<2>(parts, counts, red, tot);
+    // (the two floats stay floats up to here: their conversion to double, hoisted to the loads, made the wave wait for them
+    // before it asked for its partial sums)
+    asm volatile("" : "+v"(z0), "+v"(p0));
+    const double rz_new = tot[0], rz_old = tot[1];
     const double beta = rz_new / rz_old;
+    if (last) {
+        // no cycle ran: z and the new r.z are those of the iteration before.  Only the deferred x += alpha p of this iteration
+        // is due, with the products and the additions of the full update below
+        const double s2 = *bb2;
+        const double z_mul = s2 > 0.0 ? sqrt(s2) : 1.0;
+        const double alpha = rz_old / block_total(part_pq, P_pq, red);
+        const double alpha_hat = alpha / z_mul;
+        for (long long i = i0; i < n; i += (long long)gridDim.x * 256) {
+            if (p32 != nullptr) x_deferred[i] += alpha_hat * (double)p32[i];
+            else x_deferred[i] += alpha * p[i];
+        }
+        return;
+    }
     if (z32 != nullptr) {
         // the cycle left z in single precision and without its factor ||b|| (amg_apply, z32): the same double the exit stage
         // took its r.z from; with the deferred x update
@@ -311,7 +416,7 @@ __global__ __launch_bounds__(256) void pcg_update_p_z_kernel(
         const double z_mul = s2 > 0.0 ? sqrt(s2) : 1.0;
         // (the step length: every workgroup's where x rides on this update, the first workgroup's alone where the search
         // directions are kept and it is only recorded)
-        const bool need_alpha = p32_next == nullptr || blockIdx.x == 0;
+        const bool need_alpha = p32_next == nullptr || (blockIdx.x == 0 && !decided);
         const double alpha = need_alpha ? rz_old / block_total(part_pq, P_pq, red) : 0.0;
         if (p32 != nullptr) {
             // the search direction is KEPT in single precision, in the units of the cycle (p^ = p / ||b||, like z32: right-hand
@@ -320,8 +425,9 @@ __global__ __launch_bounds__(256) void pcg_update_p_z_kernel(
             // at the 1e-7 level, which the cycle's own single precision costs already
             const double alpha_hat = alpha / z_mul;
             if (p32_next != nullptr) {
-                if (blockIdx.x == 0 && threadIdx.x == 0) *alpha_out = alpha_hat;
-                for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
+                if (blockIdx.x == 0 && threadIdx.x == 0 && !decided) *alpha_out = alpha_hat;
+                if (ahead) p32_next[i0] = (float)((double)z0 + beta * (double)p0);
+                for (long long i = i0 + (long long)gridDim.x * 256; i < n; i += (long long)gridDim.x * 256)
                     p32_next[i] = (float)((double)z32[i] + beta * (double)p32[i]);
             } else {
                 for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
@@ -350,7 +456,13 @@ __global__ __launch_bounds__(256) void pcg_update_p_z_kernel(
         for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
             p[i] = z[i] + beta * p[i];
     }
-    if (blockIdx.x == 0) {
+    if (decided) {
+        // (`done` is written here and read by no workgroup of this launch: the next product and x/r update see it)
+        if (blockIdx.x == 0 && threadIdx.x == 0 && !(rz_new > 0.0)) {
+            st->code = PADNE_E_BREAKDOWN;
+            st->done = 1;
+        }
+    } else if (blockIdx.x == 0) {
         const double rr = block_total(part_rr, P_rr, red);
         const double pq = block_total(part_pq, P_pq, red);
         __syncthreads();
@@ -780,6 +892,8 @@ static int solve_one(padne_ctx *ctx, const padne_csr *a, const padne_csr *prec, 
     float *hist = n_hist > 0 ? (float *)((char *)ctx->ws + base_bytes) : nullptr;
     double *alpha_hist = n_hist > 0 ? (double *)(hist + hist_stride * (size_t)n_hist) : nullptr;
     if (hist != nullptr) p32 = hist;      // direction j of a (re)start lies in place j % n_hist
+    // the one-GPU loop settles an iteration behind its x/r update (pcg_decide_kernel): r.r needs no reduction over ranks there
+    const bool decide_early = z32 != nullptr;
     auto p_place = [&](long long j) { return hist + hist_stride * (size_t)(j % n_hist); };
 
     PADNE_HIP_CHECK(hipMemsetAsync(st, 0, sizeof(PcgStatus), s));
@@ -899,6 +1013,14 @@ static int solve_one(padne_ctx *ctx, const padne_csr *a, const padne_csr *prec, 
                         hipLaunchKernelGGL(pcg_update_xr_plain_kernel, dim3(gv), dim3(256), 0, s, n, rz_old, Pz, pq, Pq, p, q,
                                            x, r, slot(ctx, SLOT_RR), st);
                     PADNE_HIP_CHECK(hipGetLastError());
+                    if (decide_early) {
+                        // r.r of this iteration is complete: the books are kept here, and an iteration that converges ends
+                        // here -- its cycle and its p update return at once
+                        hipLaunchKernelGGL(pcg_decide_kernel, dim3(1), dim3(256), 0, s, rz_old, Pz, pq, Pq, rr, Pr, st,
+                                           max_iter - total_iters, bb_scalar,
+                                           hist != nullptr ? alpha_hist + (jq % n_hist) : (double *)nullptr);
+                        PADNE_HIP_CHECK(hipGetLastError());
+                    }
                     PADNE_TRY(amg_apply(ctx, prec, r, z, slot(ctx, rz_new_slot), &st->done, bb_scalar, fuse_entry, z32));
                     if (dist) {
                         PADNE_TRY(fold(slot(ctx, rz_new_slot), P_rz, kMaxPartials, 1, s_new));
@@ -908,14 +1030,17 @@ static int solve_one(padne_ctx *ctx, const padne_csr *a, const padne_csr *prec, 
                     if (hist != nullptr) {
                         hipLaunchKernelGGL(pcg_update_p_z_kernel, dim3(gv), dim3(256), 0, s, n, rz_new, rz_old, Pz, rr, Pr,
                                            pq, Pq, z, p, st, max_iter - total_iters, (double *)nullptr, (const float *)z32,
-                                           bb_scalar, p32, p_place(jq + 1), alpha_hist + (jq % n_hist));
+                                           bb_scalar, p32, p_place(jq + 1), alpha_hist + (jq % n_hist), decide_early ? 1 : 0);
                         ++jq;
-                        // the place of direction jf is written again by iteration jf + n_hist - 1
+                        // the place of direction jf is written again by iteration jf + n_hist - 1.  (The count the flush
+                        // reads advanced in pcg_decide_kernel, with the step length: both lie before the p update in the
+                        // stream, the flush behind it -- an iteration is counted if and only if its step length is there)
                         if (jq - jf >= n_hist - 1) PADNE_TRY(flush_x());
                     } else {
                         hipLaunchKernelGGL(pcg_update_p_z_kernel, dim3(gv), dim3(256), 0, s, n, rz_new, rz_old, Pz, rr, Pr,
                                            pq, Pq, z, p, st, max_iter - total_iters, defer_x ? x : (double *)nullptr,
-                                           (const float *)z32, bb_scalar, p32);
+                                           (const float *)z32, bb_scalar, p32, (float *)nullptr, (double *)nullptr,
+                                           decide_early ? 1 : 0);
                     }
                 } else {
                     hipLaunchKernelGGL(pcg_update_xr_kernel, dim3(gv), dim3(256), 0, s, n, rz_old, Pz, pq, Pq, p, q,
