@@ -131,9 +131,13 @@ int padne_dev_memset(padne_ctx *ctx, void *dev, int value, int64_t bytes);
 /* ---- matrices ------------------------------------------------------------------------------ */
 /* upload a host CSR (scipy layout: int32 indptr[n_rows+1], int32 indices[nnz], f64 data[nnz]).
  * Replaces L.tocsc() as the hand-off of the assembled system, solver.py:772.
- * The columns of a row need not ascend (scipy's canonical form does; the layout does not demand it): the upload remembers a
- * matrix whose rows do not, and the paths that count on column order (the order-preserving relabel of padne_csr_reduce)
- * leave such a matrix to the general ones, which sort. */
+ * The columns of a row need not ascend and a row may name a column more than once (scipy's canonical form does neither; the
+ * layout does not forbid it).  Such a matrix MEANS the matrix its entries sum to, as a non-canonical scipy csr_matrix does,
+ * and is STORED as that matrix in canonical form: the upload sorts every row by column and adds the parts of a repeated
+ * column in the order of their position (on the host, in the one pass that also checks the index range; a sum that comes to
+ * 0.0 stays a stored entry, as in scipy's sum_duplicates).  Every entry that takes the handle therefore sees unique, strictly
+ * ascending columns, and padne_csr_shape / padne_csr_to_host report the canonical arrays and their nnz, which is smaller than
+ * indptr[n_rows] when a column was repeated.  A canonical matrix is uploaded from the caller's arrays as they stand. */
 int padne_csr_from_host(padne_ctx *ctx, int64_t n_rows, int64_t n_cols,
                         const int32_t *indptr, const int32_t *indices, const double *data,
                         padne_csr **out);

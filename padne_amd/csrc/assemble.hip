@@ -2591,9 +2591,9 @@ int csr_relabel(padne_ctx *ctx, const padne_csr *m, const int32_t *row_map_host,
         PADNE_HIP_CHECK(hipMemcpyAsync(d_cmap, col_map_host, sizeof(int) * (size_t)m->n_cols, hipMemcpyDefault, s));
     }
     PADNE_HIP_CHECK(hipMemsetAsync(d_err, 0, sizeof(int) * ERR_WORDS, s));
-    if (m->n_rows > 0 && m->n_cols > 0 && n_rows_out > 0 && n_cols_out > 0 && !ctx->opt.force_relabel_slots && !m->cols_unsorted) {
-        // (a copy keeps the order of a row's entries: the source's columns must ascend, as everything built on the device
-        // does and padne_csr_from_host checks for what it uploads)
+    if (m->n_rows > 0 && m->n_cols > 0 && n_rows_out > 0 && n_cols_out > 0 && !ctx->opt.force_relabel_slots) {
+        // (a copy keeps the order of a row's entries: the source's columns ascend, as in everything built on the device and
+        // in everything padne_csr_from_host stores)
         // maps that only drop indices (the reduction to the potential block): count, scan, copy -- see map_is_compaction
         static_assert(ERR_WORDS >= 6, "two triples of flag words");
         hipLaunchKernelGGL(map_is_compaction, dim3(nblk(m->n_rows)), dim3(256), 0, s, (long long)m->n_rows, (const int *)d_map,

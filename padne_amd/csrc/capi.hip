@@ -598,26 +598,54 @@ int padne_csr_from_host(padne_ctx *ctx, int64_t n_rows, int64_t n_cols, const in
     PADNE_REQUIRE(indptr[0] == 0 && nnz >= 0, "indptr must start at 0");
     PADNE_REQUIRE(nnz == 0 || (indices && data), "null indices/data");
     for (int64_t i = 0; i < n_rows; ++i) PADNE_REQUIRE(indptr[i] <= indptr[i + 1], "indptr not monotone");
-    for (int64_t k = 0; k < nnz; ++k)
-        PADNE_REQUIRE(indices[k] >= 0 && indices[k] < n_cols, "column index out of range");
-    // (scipy's canonical form has ascending columns, but the layout does not demand it: remembered, not refused)
-    bool unsorted = false;
-    for (int64_t i = 0; i < n_rows && !unsorted; ++i)
-        for (int64_t k = indptr[i] + 1; k < indptr[i + 1]; ++k)
-            if (indices[k - 1] >= indices[k]) {
-                unsorted = true;
-                break;
+    // one pass over the indices: their range, and whether every row is strictly ascending (scipy's canonical form)
+    bool canonical = true;
+    for (int64_t i = 0; i < n_rows; ++i)
+        for (int64_t k = indptr[i]; k < indptr[i + 1]; ++k) {
+            PADNE_REQUIRE(indices[k] >= 0 && indices[k] < n_cols, "column index out of range");
+            if (k > indptr[i] && indices[k - 1] >= indices[k]) canonical = false;
+        }
+    // A matrix that is not canonical means the matrix its entries sum to, and is stored as that one: every row sorted by
+    // column (stably), the parts of a repeated column added in the order of their position.  On the host, before the upload --
+    // everything on the device may then count on unique, ascending columns, as it does for what is built there.  A canonical
+    // matrix is uploaded from the caller's arrays as they stand.
+    std::vector<int32_t> c_indptr, c_indices;
+    std::vector<double> c_data;
+    if (!canonical) {
+        c_indptr.assign((size_t)n_rows + 1, 0);
+        c_indices.reserve((size_t)nnz);
+        c_data.reserve((size_t)nnz);
+        std::vector<int32_t> order;
+        for (int64_t i = 0; i < n_rows; ++i) {
+            const int32_t k0 = indptr[i], len = indptr[i + 1] - k0;
+            order.resize((size_t)len);
+            for (int32_t t = 0; t < len; ++t) order[(size_t)t] = k0 + t;
+            std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return indices[a] < indices[b]; });
+            for (int32_t t = 0; t < len; ++t) {
+                const int32_t k = order[(size_t)t];
+                if (t > 0 && indices[k] == c_indices.back()) {
+                    c_data.back() += data[k];
+                } else {
+                    c_indices.push_back(indices[k]);
+                    c_data.push_back(data[k]);
+                }
             }
+            c_indptr[(size_t)i + 1] = (int32_t)c_indices.size();
+        }
+        indptr = c_indptr.data();
+        indices = c_indices.data();
+        data = c_data.data();
+    }
+    const int64_t nnz_up = canonical ? nnz : (int64_t)c_indices.size();
     PADNE_HIP_CHECK(hipSetDevice(ctx->device));
     padne_csr *m = nullptr;
-    PADNE_TRY(csr_alloc(ctx, n_rows, n_cols, nnz, &m));
-    m->cols_unsorted = unsorted;
+    PADNE_TRY(csr_alloc(ctx, n_rows, n_cols, nnz_up, &m));
     hipError_t e = hipMemcpyAsync(m->rowptr, indptr, sizeof(int32_t) * (size_t)(n_rows + 1),
                                   hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess && nnz > 0)
-        e = hipMemcpyAsync(m->cols, indices, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess && nnz > 0)
-        e = hipMemcpyAsync(m->vals, data, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess && nnz_up > 0)
+        e = hipMemcpyAsync(m->cols, indices, sizeof(int32_t) * (size_t)nnz_up, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess && nnz_up > 0)
+        e = hipMemcpyAsync(m->vals, data, sizeof(double) * (size_t)nnz_up, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) {
         set_error("matrix upload failed: %s", hipGetErrorString(e));

@@ -109,8 +109,6 @@ struct padne_csr {
     int split_n_int = 0, split_n_bnd = 0;
     int split_state = 0;                 // 0 = not examined, 1 = in use, -1 = not a row-partitioned operator / switched off
     bool hierarchy_operator = false;   // multigrid-internal operator: may use the wave-per-row SpMV
-    bool cols_unsorted = false;        // an uploaded matrix (padne_csr_from_host) with a row whose columns do not ascend: paths
-                                       // that count on column order (the order-preserving relabel) leave it to the general ones
     padne_csr *prec_block = nullptr;   // borrowed: owned x owned diagonal block for the preconditioner
     // the mesh the system was assembled from stays on the device with it (padne_assemble_system), so that the
     // post-processing of the solution (padne_csr_power_density) does not upload 40 bytes per vertex again

@@ -352,7 +352,6 @@ extern "C" int padne_coupled_create(padne_ctx *ctx, padne_csr *L, padne_thermal 
     PADNE_REQUIRE(L->owner == ctx, "the system must belong to this context");
     PADNE_REQUIRE(L->mesh_n_mesh > 0 && L->mesh_xy != nullptr, "the system matrix does not carry a mesh");
     PADNE_REQUIRE(n_mesh == L->mesh_n_mesh, "n_mesh must be that of the system's mesh");
-    PADNE_REQUIRE(!L->cols_unsorted, "the columns of every row must ascend");
     PADNE_REQUIRE(L->nnz <= 0x7fffffffLL, "too many entries");
     PADNE_REQUIRE(std::isfinite(ambient) && std::isfinite(conductance_temperature), "the temperatures must be finite");
     for (int m = 0; m < n_mesh; ++m) PADNE_REQUIRE(std::isfinite(alpha[m]), "the temperature coefficient of every mesh must be finite");
@@ -429,7 +428,6 @@ extern "C" int padne_coupled_set_resistors(padne_ctx *ctx, padne_coupled *cp, in
     const padne_csr *L = cp->L;
     const long long n_pot = cp->th->n_pot;
     PADNE_REQUIRE(n_pot <= L->n_rows, "the system has fewer rows than the thermal handle has potential unknowns");
-    PADNE_REQUIRE(!L->cols_unsorted, "the columns of every row must ascend");
     const size_t n = (size_t)n_res;
     std::vector<int> h_a(n), h_b(n);
     std::vector<double> h_g(n);
@@ -573,7 +571,6 @@ extern "C" int padne_coupled_revalue(padne_ctx *ctx, padne_coupled *cp) {
     PADNE_HIP_CHECK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     padne_csr *L = cp->L;
-    PADNE_REQUIRE(!L->cols_unsorted, "the columns of every row must ascend");
     coupled_invalidate(L);
     if (cp->n_tri > 0)
         PADNE_HIP_CHECK(hipMemcpyAsync(cp->s_used, cp->s, sizeof(double) * (size_t)cp->n_tri, hipMemcpyDeviceToDevice, st));

@@ -327,7 +327,7 @@ extern "C" int padne_transient_create(padne_ctx *ctx, padne_thermal *th, int32_t
     PADNE_REQUIRE(th->film == nullptr, "a thermal handle with film curves takes no transient handle: the steps read A and hM as constants");
     for (int m = 0; m < n_mesh; ++m)
         PADNE_REQUIRE(std::isfinite(capacity[m]) && capacity[m] > 0.0, "the areal heat capacity of every mesh must be finite and positive");
-    PADNE_REQUIRE(!th->A->cols_unsorted && th->A->nnz <= 0x7fffffffLL, "the thermal operator");
+    PADNE_REQUIRE(th->A->nnz <= 0x7fffffffLL, "the thermal operator");
     PADNE_HIP_CHECK(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     padne_transient *tr = new padne_transient;

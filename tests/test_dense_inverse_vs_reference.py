@@ -362,7 +362,7 @@ def test_another_context_gives_the_same_bits(switches, case, form):
 
 @pytest.mark.parametrize("form", FORMS)
 def test_rows_in_any_column_order_give_the_same_bits(switches, form):
-    """Every row's columns reversed: padne_csr_from_host marks the matrix as not ascending, dense_from_csr must not care."""
+    """Every row's columns reversed: padne_csr_from_host stores the canonical matrix, the inverse is the same to the bit."""
     A, cols = reference_of(switches, "a193")[:2]
     B = A.copy()
     for i in range(B.shape[0]):

@@ -2728,19 +2728,15 @@ def test_maps_that_only_drop_indices_are_relabelled_by_a_copy_with_holes(ctx, sw
         bad[9] = far
         with pytest.raises(ValueError):
             ctx.csr_from_scipy(M).reduce(bad, n - 1, 1.0)
-    # the C ABI takes rows whose columns do not ascend (padne_csr_from_host does not demand scipy's canonical form): a copy
-    # would keep their order, so such a matrix goes through the general path and comes out sorted
-    from padne_amd import _hip
+    # the C ABI takes rows whose columns do not ascend (padne_csr_from_host does not demand scipy's canonical form, it stores
+    # it): the reduction of such an upload is that of the sorted matrix (tests/test_noncanonical_upload.py has the rest)
+    from noncanonical_ref import upload_raw
     U = M.copy()
     for r in (5, 33, n - 1):
         k0, k1 = U.indptr[r], U.indptr[r + 1]
         U.indices[k0:k1] = U.indices[k0:k1][::-1].copy()
         U.data[k0:k1] = U.data[k0:k1][::-1].copy()
-    indptr, indices, data = U.indptr.astype(np.int32), U.indices.astype(np.int32), U.data.astype(np.float64)
-    h = _hip._P()
-    _hip._check(ctx._lib.padne_csr_from_host(ctx._h, n, n, _hip._ptr(indptr, _hip._PI32), _hip._ptr(indices, _hip._PI32),
-                                             _hip._ptr(data, _hip._PF64), _hip.C.byref(h)))
-    du = _hip.CsrMatrix(ctx, h)
+    du = upload_raw(ctx, U.indptr, U.indices, U.data, (n, n))
     m, keep = cmap_of(drops["scattered"])
     got = du.reduce(m, int(keep.sum()), -1.0).to_scipy()
     ref = (-1.0 * M[keep][:, keep]).tocsr()
